@@ -5,14 +5,20 @@ A "step" is one pass of the hot path (alac_decode_ab_small_kernel + alac_decode_
 alacgpu_decode_batch_device) over one batch of synthetic packets already resident in HBM.
 Workload of `value` at every N = BASELINE configs[1] ("cfg2"): 4 096 synthetic 16-bit stereo packets per GPU,
 4096 samples/frame, LPC order 8.  N>1: one process per GPU, every rank decodes its own shard (weak scaling, no data-path
-collective inside the timed region).  At N>1 the two multi-GPU configs of BASELINE.json are measured as well and
-reported under "extra_configs": cfg4 (16-bit mono, 8 192 packets per GPU) and cfg5 (mixed LPC order / bit depth,
-4 096 packets per GPU), each with the decoded-PCM all-gather north_star names -- alone (`allgather_ms`) and overlapped
-with the decode chunk by chunk (`decode_allgather_overlapped_ms`).
+collective inside the timed region).
+
+A plain run does only what `value` needs: set up, warm up, time exactly --steps steps, write the last step's outputs
+(--dump-outputs DIR) and print the line.  Everything else is measured or checked with --full only:
+  N=1: the whole batch against the CPU oracle (`parity_vs_oracle`) and the single-thread CPU port (`cpu_baseline`), the
+       PCIe-inclusive host path (`host_path`), a 32768-packet batch (`big_batch`), two batches in flight (`two_in_flight`);
+  N>1: the two multi-GPU configs of BASELINE.json under "extra_configs": cfg4 (16-bit mono, 8 192 packets per GPU) and
+       cfg5 (mixed LPC order / bit depth, 4 096 packets per GPU), each with the decoded-PCM all-gather north_star names --
+       alone (`allgather_ms`) and overlapped with the decode chunk by chunk (`decode_allgather_overlapped_ms`).
+The --no-* options switch single pieces of --full off.
 
 `python bench.py --gpus N` without a launcher starts the N ranks itself (torch.distributed.run as a child process,
 before anything in this process touches the GPU) and relays rank 0's JSON line and the children's exit code.
-Exit code: 0 only if every rank decoded with status OK and (N=1) the whole batch equals the oracle's output.
+Exit code: 0 only if every rank decoded with status OK and (N=1, --full) the whole batch equals the oracle's output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -32,6 +38,7 @@ for _p in (ROOT, os.path.join(ROOT, "oracle")):
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 PER_GPU_PACKETS = {2: 4096, 3: 8192, 4: 8192, 5: 4096}  # cfg4/cfg5 are quoted per 8 GPUs: 65536/8, 32768/8
+DUMP_BYTES = 60 << 20  # --dump-outputs may write 64 MB in all: room for the .npy headers
 NAMES = {2: "cfg2: 4096 synthetic 16-bit stereo packets, 4096 samples/frame, LPC order 8",
          3: "cfg3: 24-bit stereo, 8192-sample packets, LPC order 16",
          4: "cfg4: 16-bit mono, 4096-sample packets",
@@ -45,6 +52,11 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=int, default=2, help="BASELINE.json config number (2..5) behind `value`")
     ap.add_argument("--packets", type=int, default=None, help="packets per GPU (default: the config's batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the oracle parity, CPU baseline, host path, big batch, batches in flight (N=1) and the all-gather "
+                         "and extra configs (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="single-thread CPU baseline: run at least this long")
     ap.add_argument("--no-allgather", action="store_true")
@@ -57,7 +69,10 @@ def parse_args(argv=None):
     ap.add_argument("--no-in-flight", action="store_true", help="N=1: skip the extra line with two batches in flight (two streams)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse the N>1 path)")
     ap.add_argument("--same-device", action="store_true", help="rehearsal: every rank uses cuda:0 (needs --backend gloo)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -181,6 +196,38 @@ def timed_steps(torch, dist, w, steps, warmup, dev, distributed):
     elapsed = time.perf_counter() - t0
     kernel_ms = sum(e0.elapsed_time(e1) for e0, e1 in evs) / len(evs)
     return elapsed, float(kernel_ms)
+
+
+def dump_outputs(torch, np, w, outdir, rank, world):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as DIR/<name>.npy (suffix _rank<r> at N>1).
+    Per packet (float64): `status`, `out_bytes`, `out_samples` and `pcm_checksums` (the sum and the index-weighted sum of its
+    whole PCM, exact); `pcm_sample` (float32, exact for samples of up to 24 bits): the PCM of a fixed, seeded sample of
+    packets, whose indices are `pcm_sample_packets`.  Ints beyond a packet's n * channels, and the PCM of a packet whose status
+    is not 0, are scratch by contract (include/alacgpu.h) and are written as 0.  All ranks together stay within DUMP_BYTES."""
+    os.makedirs(outdir, exist_ok=True)
+    n, slot, dev = w.n_packets, w.slot, w.dev
+    st, ob, osm = w.d_st.cpu().numpy(), w.d_ob.cpu().numpy(), w.d_os.cpu().numpy()
+    ci = np.zeros(n, dtype=np.int64) if w.b["cfg_idx"] is None else w.b["cfg_idx"].astype(np.int64)
+    nc = np.array([int(c[5]) for c in w.b["stream_cfgs"]], dtype=np.int64)[ci]
+    cnt = np.where(st == 0, osm.astype(np.int64) * nc, 0)
+    d_cnt = torch.from_numpy(cnt).to(dev)
+    pos = torch.arange(slot, dtype=torch.int64, device=dev)
+    sums = []
+    for lo in range(0, n, 4096):     # int64 copies of 4096 rows at a time
+        x = w.d_pcm[lo:lo + 4096].to(torch.int64)
+        x = torch.where(pos[None, :] < d_cnt[lo:lo + 4096, None], x, 0)
+        sums.append(torch.stack([x.sum(1), (x * (pos + 1)).sum(1)], 1).cpu())
+    checksums = torch.cat(sums).numpy()
+    budget = DUMP_BYTES // world - 5 * 8 * n          # what is left for the sample after the per-packet arrays
+    k = max(0, min(n, budget // (4 * slot + 8)))
+    rows = np.sort(np.random.default_rng(0xA1AC).choice(n, size=k, replace=False))
+    sample = w.d_pcm[torch.from_numpy(rows).to(dev)].cpu().numpy()
+    sample[np.arange(slot)[None, :] >= cnt[rows][:, None]] = 0
+    sfx = "" if world == 1 else f"_rank{rank}"
+    for name, a, dt in (("status", st, np.float64), ("out_bytes", ob, np.float64), ("out_samples", osm, np.float64),
+                        ("pcm_checksums", checksums, np.float64), ("pcm_sample_packets", rows, np.float64),
+                        ("pcm_sample", sample, np.float32)):
+        np.save(os.path.join(outdir, name + sfx + ".npy"), a.astype(dt))
 
 
 def measure_in_flight(torch, w, dev, steps, k=2):
@@ -395,11 +442,13 @@ def main():
     # (right behind the timed region, before this process makes any other stream: the runtime maps streams onto a handful of
     # hardware queues in creation order, and two streams that share a queue do not overlap)
     in_flight = None
-    if rank == 0 and world == 1 and not args.no_in_flight:
+    if args.full and rank == 0 and world == 1 and not args.no_in_flight:
         try:
             in_flight = measure_in_flight(torch, w, dev, max(args.steps, 8))
         except Exception as e:   # noqa: BLE001
             in_flight = {"error": f"{type(e).__name__}: {e}"[:300]}
+    if args.dump_outputs:
+        dump_outputs(torch, np, w, args.dump_outputs, rank, world)
 
     status_ok = w.status_ok()
     total_samples = w.samples
@@ -468,7 +517,7 @@ def main():
             "parity_vs_oracle": parity, "status_ok": status_ok,
             "allgather_ms": None if allgather_ms is None else round(allgather_ms, 4),
             "decode_allgather_overlapped_ms": None if overlapped_ms is None else round(overlapped_ms, 4),
-            "allgather_ok": gather_ok if distributed else None, "allgather_via": gather_via,
+            "allgather_ok": gather_ok if distributed and args.full else None, "allgather_via": gather_via,
             "gen_seconds": round(w.gen_s, 2),
         }
         if traffic_note:
@@ -492,7 +541,7 @@ def main():
     # a collective that never returns (a fabric or library fault on a node this code has never met) must not take the headline
     # with it: past --extra-timeout seconds rank 0 prints the line it has and every rank leaves
     watchdog = None
-    if distributed and args.extra_timeout > 0:
+    if distributed and args.full and args.extra_timeout > 0:
         import threading
 
         def give_up():
@@ -507,10 +556,10 @@ def main():
     # (the headline measurement above is complete at this point; a failure below -- out of memory, a collective that the
     # node's fabric refuses -- is reported in the line as "extra_error" instead of taking `value` down with it)
     try:
-        if distributed and not args.no_allgather:
+        if distributed and args.full and not args.no_allgather:
             allgather_ms, overlapped_ms, gather_ok, gather_via = gather_figures(pkg, torch, dist, sharding, np, w, world, rank, dev, cdev,
                                                                                  args.backend)
-        if distributed and not args.no_extra:
+        if distributed and args.full and not args.no_extra:
             for cfgno in (4, 5):
                 if cfgno == args.config:
                     continue
@@ -548,7 +597,7 @@ def main():
 
     # ---- correctness + CPU baseline (rank 0, N=1 only; the oracle is the checker, never the product) ----
     b = w.b
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import alac_oracle_py as orc
 
         cfgs = orc.make_cfgs(b["stream_cfgs"])
@@ -585,10 +634,10 @@ def main():
                       f"AlacFile.DecodeFrame (oracle/alac_oracle.c; C# runtime unavailable), 1 thread pinned to one core",
             "all_cores_value": round(w.samples / cpuall_s / 1e6, 3), "all_cores": ncores,
         }
-    if rank == 0 and world == 1 and not args.no_host_path:
+    if args.full and rank == 0 and world == 1 and not args.no_host_path:
         host_path = measure_host_path(pkg, np, w)
     # ---- the same config in a batch big enough to fill the chip (never `value`: BASELINE quotes the metric on 4096 packets) ----
-    if rank == 0 and world == 1 and not args.no_big_batch and args.packets is None and args.config == 2:
+    if args.full and rank == 0 and world == 1 and not args.no_big_batch and args.packets is None and args.config == 2:
         try:
             wb = Workload(pkg, synth, torch, np, args.config, 32768, 0, dev, local_rank)
             el, kms = timed_steps(torch, dist, wb, 10, 3, dev, False)

@@ -31,7 +31,7 @@ def test_more_gpus_than_present_fails_loudly():
 @pytest.mark.gpu
 def test_two_ranks_started_by_bench_itself_product_path():
     r, j = _run(["--gpus", "2", "--backend", "gloo", "--same-device", "--packets", "256", "--extra-packets", "64", "--steps", "2",
-                 "--warmup", "1"])
+                 "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert j["n_gpus"] == 2 and j["steps"] == 2 and j["status_ok"] is True and j["allgather_ok"] is True
     assert j["config"]["packets_per_gpu"] == 256 and j["value"] > 0
@@ -43,7 +43,7 @@ def test_two_ranks_started_by_bench_itself_product_path():
 
 @pytest.mark.gpu
 def test_single_gpu_line_has_the_contract_keys_and_parity():
-    r, j = _run(["--packets", "512", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5", "--no-big-batch"])
+    r, j = _run(["--packets", "512", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5", "--no-big-batch", "--full"])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -60,7 +60,7 @@ def test_single_gpu_line_has_the_contract_keys_and_parity():
 @pytest.mark.parametrize("cfg", [3, 4, 5])
 def test_full_size_configs_equal_the_oracle(cfg):
     # BASELINE configs 3..5 at their full per-GPU size, every sample compared with the oracle inside bench.py
-    r, j = _run(["--config", str(cfg), "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.2", "--no-host-path"])
+    r, j = _run(["--config", str(cfg), "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.2", "--no-host-path", "--full"])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert j["parity_vs_oracle"] is True and j["status_ok"] is True
 
@@ -89,3 +89,34 @@ def test_every_rank_shard_of_the_eight_gpu_configs_equals_the_oracle(cfg, per_gp
         mask = np.arange(gp.shape[1])[None, :] < cnt[:, None]
         assert np.array_equal(gp[mask], op[mask]), rank
         assert (ost == 0).mean() > 0.9
+
+
+@pytest.mark.gpu
+def test_plain_run_times_only_its_steps_and_dumps_the_last_one(tmp_path, oracle, synth):
+    """Without --full the line carries `value` and nothing measured beside it; --dump-outputs writes what the timed path
+    returned in its last step, which must be the oracle's output (cfg5: two stream configs, short and escaped packets)."""
+    import numpy as np
+
+    r, j = _run(["--config", "5", "--packets", "256", "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert j["steps"] == 4 and j["ms_per_step"] > 0 and j["value"] > 0 and j["status_ok"] is True
+    assert j["cpu_baseline"] is None and j["parity_vs_oracle"] is None
+    for k in ("host_path", "big_batch", "two_in_flight", "extra_configs"):
+        assert k not in j
+    files = os.listdir(tmp_path)
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 << 20
+    d = {f[:-4]: np.load(tmp_path / f) for f in files}
+    assert set(d) == {"status", "out_bytes", "out_samples", "pcm_checksums", "pcm_sample_packets", "pcm_sample"}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    b = synth.make_config_batch(5, n_packets=256)
+    op, oob, oos, ost = oracle.decode_batch(oracle.make_cfgs(b["stream_cfgs"]), b["blob"], b["offsets"], b["sizes"],
+                                             b["cfg_idx"], b["slot_ints"])
+    assert np.array_equal(d["status"], ost) and np.array_equal(d["out_bytes"], oob) and np.array_equal(d["out_samples"], oos)
+    nc = np.array([b["stream_cfgs"][int(i)][5] for i in b["cfg_idx"]], dtype=np.int64)
+    cnt = np.where(ost == 0, oos.astype(np.int64) * nc, 0)
+    ref = np.where(np.arange(op.shape[1])[None, :] < cnt[:, None], op.astype(np.int64), 0)
+    pos = np.arange(1, op.shape[1] + 1, dtype=np.int64)
+    assert np.array_equal(d["pcm_checksums"], np.stack([ref.sum(1), (ref * pos).sum(1)], 1))
+    rows = d["pcm_sample_packets"].astype(np.int64)
+    assert np.array_equal(rows, np.arange(256))   # a batch this small fits whole
+    assert np.array_equal(d["pcm_sample"], ref[rows])

@@ -21,13 +21,13 @@ timeout -k 10 250 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/s
 timeout -k 10 250 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_sq_cfg2_32768 -- $B > $OUT/pmc_sq_cfg2_32768.log 2>&1 || exit 13
 if [ -z "$PROFILES_ONLY" ]; then
   for c in 2 3 4 5; do
-    timeout -k 10 250 python3 bench.py --config $c --steps 20 --warmup 3 --cpu-seconds 3 --no-host-path --no-big-batch 2>/dev/null | grep metric > $OUT/cfg$c.json || exit 7
+    timeout -k 10 250 python3 bench.py --full --config $c --steps 20 --warmup 3 --cpu-seconds 3 --no-host-path --no-big-batch 2>/dev/null | grep metric > $OUT/cfg$c.json || exit 7
   done
   for n in 8192 16384 32768; do
-    timeout -k 10 250 python3 bench.py --config 2 --packets $n --steps 20 --warmup 3 --no-cpu-baseline --no-host-path 2>/dev/null | grep metric > $OUT/cfg2_$n.json || exit 11
+    timeout -k 10 250 python3 bench.py --full --config 2 --packets $n --steps 20 --warmup 3 --no-cpu-baseline --no-host-path 2>/dev/null | grep metric > $OUT/cfg2_$n.json || exit 11
   done
-  timeout -k 10 300 python3 bench.py 2>/dev/null | grep metric > $OUT/bench_default.json || exit 8
-  timeout -k 10 300 python3 bench.py --gpus 2 --backend gloo --same-device --steps 5 --warmup 2 2>/dev/null | grep metric > $OUT/two_ranks_one_gpu_gloo.json || exit 14
+  timeout -k 10 300 python3 bench.py --full 2>/dev/null | grep metric > $OUT/bench_default.json || exit 8
+  timeout -k 10 300 python3 bench.py --full --gpus 2 --backend gloo --same-device --steps 5 --warmup 2 2>/dev/null | grep metric > $OUT/two_ranks_one_gpu_gloo.json || exit 14
   timeout -k 10 250 python3 tools/bench_m4a.py 2>/dev/null | tail -1 > $OUT/cfg1_m4a.json || exit 9
 fi
 echo collected

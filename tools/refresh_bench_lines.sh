@@ -8,12 +8,12 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/final2
 rm -rf "$OUT" && mkdir -p "$OUT"
 for c in 3 4 5; do
-  timeout -k 10 250 python3 bench.py --config $c --steps 20 --warmup 3 --cpu-seconds 3 --no-host-path --no-big-batch 2>/dev/null | grep metric > $OUT/cfg$c.json || exit 7
+  timeout -k 10 250 python3 bench.py --full --config $c --steps 20 --warmup 3 --cpu-seconds 3 --no-host-path --no-big-batch 2>/dev/null | grep metric > $OUT/cfg$c.json || exit 7
 done
 for n in 8192 16384 32768; do
-  timeout -k 10 250 python3 bench.py --config 2 --packets $n --steps 20 --warmup 3 --no-cpu-baseline --no-host-path 2>/dev/null | grep metric > $OUT/cfg2_$n.json || exit 11
+  timeout -k 10 250 python3 bench.py --full --config 2 --packets $n --steps 20 --warmup 3 --no-cpu-baseline --no-host-path 2>/dev/null | grep metric > $OUT/cfg2_$n.json || exit 11
 done
-timeout -k 10 300 python3 bench.py 2>/dev/null | grep metric > $OUT/bench_default.json || exit 8
+timeout -k 10 300 python3 bench.py --full 2>/dev/null | grep metric > $OUT/bench_default.json || exit 8
 python3 - <<'EOF'
 import json
 for f in ("bench_default", "cfg3", "cfg4", "cfg5"):

@@ -18,6 +18,10 @@ _LIB = None
 # per-packet status codes (include/alacgpu.h)
 ST_OK, ST_UNSUPPORTED_ELEMENT, ST_UNSUPPORTED_SAMPLE_SIZE, ST_UNSUPPORTED_PREDTYPE = 0, 1, 2, 3
 ST_BAD_SAMPLE_COUNT, ST_OVERRUN, ST_REF_THROWS, ST_UNSUPPORTED_PARAMS = 4, 5, 6, 7
+ST_DEST_RANGE = 8
+# alacgpu_decode_into_device: destination layout and element type
+DST_INTERLEAVED, DST_PLANAR = 0, 1
+DST_INT32, DST_FLOAT32 = 0, 1
 
 CFG_DTYPE = np.dtype(
     [
@@ -49,6 +53,8 @@ SYMBOLS = {
                                                _VP, _VP]),
     "alacgpu_decode_batch_device": (C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP, _VP, C.c_uint32, _VP, C.c_uint32, _VP,
                                               _VP, _VP, _VP]),
+    "alacgpu_decode_into_device": (C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, C.c_uint64,
+                                             C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP]),
     "alacgpu_decode_frame": (C.c_int, [_VP, C.c_uint32, _VP, C.c_uint32, _VP, C.c_uint32, _VP, _VP]),
     "alacgpu_expand_reference_layout": (C.c_size_t, [_VP, _VP, C.c_int32, _VP]),
     "alacgpu_format_samples": (C.c_size_t, [C.c_int, _VP, C.c_int32, _VP]),
@@ -189,6 +195,38 @@ class AlacGpuContext:
         rc = lib().alacgpu_decode_batch_device(self._ctx, dp(d_blob), blob_bytes, dp(d_offsets), dp(d_sizes),
                                                dp(d_cfg_idx), n_packets, dp(d_pcm), slot_ints, dp(d_out_bytes),
                                                dp(d_out_samples), dp(d_status), _VP(stream))
+        _check(rc, self._ctx)
+
+    def decode_into_device(self, d_blob, blob_bytes, d_offsets, d_sizes, d_cfg_idx, n_packets, d_dst_first, d_dst_frames, out,
+                           channels, layout="planar", plane_stride=0, d_out_samples=None, d_status=None, stream=0):
+        """alacgpu_decode_into_device: packet p's frames land at d_dst_first[p] of the gap-free tensor `out` (torch int32 or
+        float32 on this device, contiguous; its dtype picks the element type), interleaved ((first + i) * channels + c) or
+        planar (c * plane_stride + first + i).  d_* are torch device tensors (d_cfg_idx / d_out_samples may be None);
+        asynchronous on `stream` (raw hipStream_t)."""
+        import torch
+
+        if out.dtype == torch.int32:
+            dtype = DST_INT32
+        elif out.dtype == torch.float32:
+            dtype = DST_FLOAT32
+        else:
+            raise ValueError(f"out must be torch.int32 or torch.float32, not {out.dtype}")
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous")
+        if out.device.type != "cuda":
+            raise ValueError("out must be a device tensor")
+        lay = {"interleaved": DST_INTERLEAVED, "planar": DST_PLANAR}.get(layout)
+        if lay is None:
+            raise ValueError(f"layout must be 'interleaved' or 'planar', not {layout!r}")
+        if d_status is None:
+            raise ValueError("d_status is required")
+
+        def dp(t):
+            return _VP(t.data_ptr()) if t is not None else None
+
+        rc = lib().alacgpu_decode_into_device(self._ctx, dp(d_blob), blob_bytes, dp(d_offsets), dp(d_sizes), dp(d_cfg_idx),
+                                              n_packets, dp(d_dst_first), dp(d_dst_frames), dp(out), out.numel(), channels, lay,
+                                              dtype, plane_stride, dp(d_out_samples), dp(d_status), _VP(stream))
         _check(rc, self._ctx)
 
     def set_output_format(self, fmt):
@@ -369,6 +407,128 @@ def cfg_from_codec_data(codec_data_ints, samplesize, numchannels):
     cfg = np.zeros(1, dtype=CFG_DTYPE)
     _check(lib().alacgpu_cfg_from_codec_data(_ptr(arr), len(arr), samplesize, numchannels, _ptr(cfg)))
     return cfg
+
+
+# ---- whole files into one tensor (alacgpu_decode_into_device) ------------------------------------------------------------
+def _torch_dtype(torch, dtype):
+    if dtype not in (torch.float32, torch.int32):
+        raise ValueError(f"dtype must be torch.float32 or torch.int32, not {dtype}")
+    return dtype
+
+
+def _normalise_status(st, first_bytes):
+    """AlacContext.ReadBatch's reading of the statuses: a one-channel element with a prediction type other than 0 is an ordinary
+    packet (its un-predicted residuals, AlacFile.cs:484-496), an unsupported element a run of zeros (the reference decodes
+    nothing, AlacFile.cs:437)."""
+    mono = (first_bytes >> 5) == 0
+    st = np.where((st == ST_UNSUPPORTED_PREDTYPE) & mono, ST_OK, st)
+    return np.where(st == ST_UNSUPPORTED_ELEMENT, ST_OK, st)
+
+
+def _decode_tables(tables, cfgs, cfg_idx, keep, dst_first, dst_frames, out, channels, layout, plane_stride, device):
+    """One alacgpu_decode_into_device call over the packets `keep[f]` of every table; returns the statuses (host)."""
+    import torch
+
+    dev = torch.device("cuda", device)
+    blobs, offs, sizes, firsts = [], [], [], []
+    base = 0
+    for t, k in zip(tables, keep):
+        o, z = t["offsets"][k], t["sizes"][k]
+        used = int(o[-1]) + int(z[-1]) if len(o) else 0      # (the kept packets are a prefix: nothing behind them is uploaded)
+        blobs.append(t["blob"][:used])
+        offs.append(o.astype(np.uint64) + np.uint64(base))
+        sizes.append(z)
+        firsts.append(t["blob"][np.minimum(o, max(used - 1, 0)).astype(np.int64)] if used else np.zeros(len(o), np.uint8))
+        base += used
+    offsets = np.concatenate(offs) if offs else np.zeros(0, np.uint64)
+    n = len(offsets)
+    if n == 0:
+        return np.zeros(0, np.int32), np.zeros(0, np.uint8)
+    blob = np.zeros(base + 64, dtype=np.uint8)          # readable up to blob_bytes rounded up to 16
+    blob[:base] = np.concatenate(blobs)
+    d_blob = torch.from_numpy(blob).to(dev)
+    d_off = torch.from_numpy(offsets.astype(np.int64)).to(dev)
+    d_sz = torch.from_numpy(np.concatenate(sizes).astype(np.int32)).to(dev)
+    d_ci = torch.from_numpy(cfg_idx.astype(np.int16)).to(dev)
+    d_first = torch.from_numpy(dst_first.astype(np.int64)).to(dev)
+    d_frames = torch.from_numpy(dst_frames.astype(np.int32)).to(dev)
+    d_st = torch.empty(n, dtype=torch.int32, device=dev)
+    with AlacGpuContext(cfgs, device) as ctx:
+        stream = torch.cuda.current_stream(dev)
+        ctx.decode_into_device(d_blob, base, d_off, d_sz, d_ci, n, d_first, d_frames, out, channels, layout, plane_stride,
+                               None, d_st, stream=stream.cuda_stream)
+        st = d_st.cpu().numpy()     # (waits for the decode: the context's scratch is released behind it)
+    return st, np.concatenate(firsts)
+
+
+def load(source, device=0, dtype=None, layout="planar"):
+    """Decode a whole M4A file on the GPU into one gap-free tensor: returns (pcm, sample_rate), pcm [C, T] (planar) or [T, C]
+    (interleaved) on cuda:`device`, T = AlacContext.GetNumSamples().  float32 (default): sample * 2^-(bits-1), exact; int32:
+    the canonical sample.  `source`: file bytes, a path, or a seekable binary file object.  Raises AlacGpuError naming the first
+    packet that does not decode (statuses read as AlacContext.ReadBatch reads them)."""
+    import torch
+
+    from .container import packet_table
+
+    dtype = _torch_dtype(torch, torch.float32 if dtype is None else dtype)
+    if layout not in ("planar", "interleaved"):
+        raise ValueError(f"layout must be 'planar' or 'interleaved', not {layout!r}")
+    t = packet_table(source)
+    C_, T = int(t["num_channels"]), int(t["num_samples"])
+    shape = (C_, T) if layout == "planar" else (T, C_)
+    out = torch.zeros(shape, dtype=dtype, device=torch.device("cuda", device))
+    n = len(t["sizes"])
+    keep = np.ones(n, dtype=bool)
+    st, first = _decode_tables([t], t["cfg"], np.zeros(n, np.uint16), [keep], t["dst_first"], t["durations"], out, C_, layout,
+                               max(T, 1), device)
+    bad = np.nonzero(_normalise_status(st, first) != ST_OK)[0]
+    if len(bad):
+        p = int(bad[0])
+        raise AlacGpuError(f"packet {p} does not decode: status {int(st[p])} ({lib().alacgpu_status_string(int(st[p])).decode()})")
+    return out, int(t["sample_rate"])
+
+
+def load_batch(sources, device=0, dtype=None, max_frames=None):
+    """Decode several M4A files in ONE launch into a zero-padded [F, C, Tmax] tensor: returns (pcm, lengths[F], sample_rate)
+    (lengths: int64, host).  Files may mix 16- and 24-bit; they must share channel count and sample rate (ValueError).
+    max_frames: crop every file to at most that many frames (packets wholly past the crop are not uploaded)."""
+    import torch
+
+    from .container import packet_table
+
+    dtype = _torch_dtype(torch, torch.float32 if dtype is None else dtype)
+    tables = [packet_table(s) for s in sources]
+    if not tables:
+        raise ValueError("no sources")
+    if len(tables) > 65536:
+        raise ValueError("at most 65536 files per batch (one stream cfg each)")
+    C_, rate = int(tables[0]["num_channels"]), int(tables[0]["sample_rate"])
+    for i, t in enumerate(tables):
+        if int(t["num_channels"]) != C_ or int(t["sample_rate"]) != rate:
+            raise ValueError(f"source {i}: {t['num_channels']} channels at {t['sample_rate']} Hz, the first has {C_} at {rate} Hz")
+    lengths = np.array([t["num_samples"] for t in tables], dtype=np.int64)
+    if max_frames is not None:
+        lengths = np.minimum(lengths, max(int(max_frames), 0))
+    F, Tmax = len(tables), int(lengths.max())
+    out = torch.zeros((F, C_, Tmax), dtype=dtype, device=torch.device("cuda", device))
+    keep, ci, pk, firsts, frames = [], [], [], [], []
+    for f, t in enumerate(tables):
+        k = t["dst_first"] < lengths[f]
+        keep.append(k)
+        ci.append(np.full(int(np.count_nonzero(k)), f, dtype=np.uint16))
+        pk.append(np.nonzero(k)[0])
+        firsts.append(t["dst_first"][k] + f * C_ * Tmax)
+        frames.append(np.minimum(t["durations"][k], lengths[f] - t["dst_first"][k]))
+    cfgs = np.concatenate([t["cfg"] for t in tables])
+    st, first = _decode_tables(tables, cfgs, np.concatenate(ci), keep, np.concatenate(firsts), np.concatenate(frames), out, C_,
+                               "planar", max(Tmax, 1), device)
+    bad = np.nonzero(_normalise_status(st, first) != ST_OK)[0]
+    if len(bad):
+        p = int(bad[0])
+        f, q = int(np.concatenate(ci)[p]), int(np.concatenate(pk)[p])
+        raise AlacGpuError(f"source {f}, packet {q} does not decode: status {int(st[p])} "
+                           f"({lib().alacgpu_status_string(int(st[p])).decode()})")
+    return out, torch.from_numpy(lengths), rate
 
 
 class AlacFile:

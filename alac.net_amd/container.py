@@ -16,6 +16,7 @@ applied to the int[] buffer before formatting, so for 24-bit streams it is off b
 (AlacContext.cs:200-202,:284-286).
 """
 import io
+import os
 import struct
 
 import numpy as np
@@ -287,6 +288,55 @@ class QtMovieT:
         if self.s.Seek(self.saved_mdat_pos) != 0:
             return MDAT_CANNOT_SEEK
         return MDAT_OK
+
+
+def _open_source(source):
+    """bytes / bytearray / memoryview, a path, or a seekable binary file object -> (file object, whether to close it)"""
+    if isinstance(source, (bytes, bytearray, memoryview)):
+        return io.BytesIO(bytes(source)), True
+    if isinstance(source, (str, os.PathLike)):
+        return open(source, "rb"), True
+    return source, False
+
+
+def packet_table(source):
+    """The packet table of an M4A file, on the host only (no GPU context): what alacgpu_decode_into_device needs to place
+    every packet of the file in one gap-free tensor.  `source`: file bytes, a path, or a seekable binary file object.
+    Packets are taken as AlacContext.ReadBatch takes them: `stsz` sizes, `stts` durations, the bytes read back to back from
+    the start of the media data.  Returns a dict:
+      sizes[n] uint32, durations[n] int64 (frames), dst_first[n] int64 (exclusive prefix sum of the durations),
+      offsets[n] uint64 into blob, blob uint8 (the packet bytes), cfg (one alacgpu_cfg row), sample_rate, num_channels,
+      sample_size, num_samples (AlacContext.GetNumSamples: the sum of the durations)."""
+    f, close = _open_source(source)
+    try:
+        res = DemuxResT()
+        stream = _Stream(f)
+        head = QtMovieT(stream, res).ReadHeader()
+        if head in (MDAT_NONE, MDAT_CANNOT_SEEK):
+            raise IOError("Error while loading the QuickTime movie headers.")
+        # TryGetSampleInfo (AlacContext.cs:130-156) for every packet: the stts runs, cut where stsz or stts ends
+        counts = [int(c) for c, _ in res.TimeToSample[:res.NumTimeToSamples]]
+        durs = [int(d) for _, d in res.TimeToSample[:res.NumTimeToSamples]]
+        durations = np.repeat(np.array(durs, dtype=np.int64), np.maximum(np.array(counts, dtype=np.int64), 0))
+        n = min(len(res.SampleByteSize), len(durations))
+        durations = durations[:n].copy()
+        sizes = res.SampleByteSize[:n].astype(np.uint32)
+        blob = np.frombuffer(stream.Read(int(sizes.sum(dtype=np.int64))), dtype=np.uint8)
+        offsets = np.zeros(n, dtype=np.uint64)
+        if n > 1:
+            offsets[1:] = np.cumsum(sizes[:-1], dtype=np.uint64)
+        dst_first = np.zeros(n, dtype=np.int64)
+        if n > 1:
+            dst_first[1:] = np.cumsum(durations[:-1])
+        cfg = cfg_from_codec_data(res.CodecData[:48], res.SampleSize, res.NumChannels)
+        return dict(sizes=sizes, durations=durations, dst_first=dst_first, offsets=offsets, blob=blob, cfg=cfg,
+                    sample_rate=res.SampleRate if res.SampleRate != 0 else 44100,
+                    num_channels=res.NumChannels if res.NumChannels != 0 else 2,
+                    sample_size=res.SampleSize if res.SampleSize != 0 else 16,
+                    num_samples=int(durations.sum()))
+    finally:
+        if close:
+            f.close()
 
 
 class AlacContext:

@@ -757,6 +757,15 @@ struct Meta {
 };
 
 
+// Destination mode: packet pkt's run lies inside [0, out_elems) -- frames dst_first .. dst_first + dst_frames of every channel.
+__device__ __forceinline__ bool dst_run_inside(const alac_decode_params& p, uint32_t pkt) {
+    const uint64_t f0 = p.dst_first[pkt], nf = p.dst_frames[pkt];
+    // frames addressable from frame 0: interleaved out_elems / channels; planar what lies in front of the last channel's plane
+    const uint64_t lead = p.layout ? (uint64_t)(p.channels - 1u) * p.plane_stride : 0u;
+    const uint64_t cap = p.layout ? (lead <= p.out_elems ? p.out_elems - lead : 0u) : p.out_elems / p.channels;
+    return lead <= p.out_elems && f0 <= cap && nf <= cap - f0;
+}
+
 // Header parse (AlacFile.cs:435-475 / :584-641) for the stream (pkt, chan).  Every lane that needs a
 // stream's facts calls this itself (a handful of cached loads).  cfg receives the stream cfg.
 __device__ __forceinline__ Meta parse_meta(const alac_decode_params& p, uint32_t pkt, int chan, bool valid,
@@ -818,6 +827,10 @@ __device__ __forceinline__ Meta parse_meta(const alac_decode_params& p, uint32_t
         // every right sample is overwritten by the next left one); channel A is parked in the slot, which needs room for it
         else if (m.stereo && m.nc < 2 && (uint64_t)m.n * 2u > p.slot_ints) m.status = ALACGPU_ST_UNSUPPORTED_ELEMENT_D;
         else if (m.ss - m.ub * 8 < 8) m.status = ALACGPU_ST_UNSUPPORTED_PARAMS_D;
+        // destination mode: a packet whose run does not fit, or whose stream has another channel count, is switched off here
+        // for every role (and writes nothing)
+        if (p.dst_first && ((!badcfg && cfg.num_channels != p.channels) || !dst_run_inside(p, pkt)))
+            m.status = ALACGPU_ST_DEST_RANGE_D;
         m.rawbit = hdr_end;
         if (m.status == 0) {
             if (m.esc) {

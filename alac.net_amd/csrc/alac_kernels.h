@@ -20,7 +20,8 @@ enum {
     ALACGPU_ST_BAD_SAMPLE_COUNT_D = 4,
     ALACGPU_ST_OVERRUN_D = 5,
     ALACGPU_ST_REF_THROWS_D = 6,
-    ALACGPU_ST_UNSUPPORTED_PARAMS_D = 7
+    ALACGPU_ST_UNSUPPORTED_PARAMS_D = 7,
+    ALACGPU_ST_DEST_RANGE_D = 8
 };
 
 struct alac_decode_params {
@@ -55,6 +56,17 @@ struct alac_decode_params {
     // there; its value, the workgroup's turn on the CU, rotates the roles of the workgroup's waves over the SIMDs.
     // 2048 entries, never reset (only the value modulo 4 matters).  Null: roles in wave order.
     uint32_t* cu_arrivals;
+    // Destination mode (alacgpu_decode_into_device); dst_first == null: the slot layout above, and the rest is unused.
+    // Packet p's frame i, channel c goes to element (dst_first[p] + i) * channels + c (layout 0, interleaved) or
+    // c * plane_stride + dst_first[p] + i (layout 1, planar) of pcm_out, as int32 (dtype 0) or as float32 sample * 2^-(ss-1)
+    // (dtype 1); frames i >= dst_frames[p] are not stored.  A run outside [0, out_elems) or a stream cfg with another channel
+    // count is status ALACGPU_ST_DEST_RANGE_D, and such a packet writes nothing.  slot_ints is channels * Smax (the statuses
+    // of the slot layout) and channel A is parked at park + p * park_stride.
+    const uint64_t* dst_first;
+    const uint32_t* dst_frames;
+    uint64_t out_elems;
+    uint64_t plane_stride;
+    uint32_t channels, layout, dtype;
 };
 
 #ifdef __HIPCC__
@@ -67,6 +79,9 @@ extern "C" __global__ void alac_decode_ab_small_kernel(alac_decode_params p);   
 extern "C" __global__ void alac_decode_ab32_kernel(alac_decode_params p);
 // the first launch with 16 packets / 256-thread workgroup (one entropy wave for 16 streams, orders 1..16): big batches
 extern "C" __global__ void alac_decode_ab_dense_kernel(alac_decode_params p);
+// destination mode only, behind the launch pair: the zeros of every run (frames past a packet's decoded ones, the whole run of
+// a packet that failed)
+extern "C" __global__ void alac_dst_fill_kernel(alac_decode_params p);
 #endif
 
 #endif

@@ -24,17 +24,27 @@ using namespace alacdev;
 
 namespace {
 
-// Output store.  out_format 0: the canonical int32 per sample.  out_format 1: what AlacContext.Read hands
-// out -- FormatSamples (AlacContext.cs:214-256) fused into the store: 16-bit streams the low 16 bits little-endian
-// (:231-242), 24-bit streams the three bytes of the sample (:244-252 over the byte-per-int layout).
-__device__ __forceinline__ void store_sample(const alac_decode_params& p, const Meta& m, int32_t* pcm_slot, int64_t idx,
-                                             int val) {
+// Output store of sample i, channel c.  Slot layout (dst_first null): out_format 0 the canonical int32 per sample; out_format 1
+// what AlacContext.Read hands out -- FormatSamples (AlacContext.cs:214-256) fused into the store: 16-bit streams the low 16 bits
+// little-endian (:231-242), 24-bit streams the three bytes of the sample (:244-252 over the byte-per-int layout).
+// Destination mode (alac_decode_params::dst_first): `out` already points at the packet's frame 0 of channel 0, frames from
+// dst_lim on are not stored; int32 or float32 sample * 2^-(ss-1) (exact: |sample| <= 2^23).
+__device__ __forceinline__ void store_sample(const alac_decode_params& p, const Meta& m, int32_t* out, uint32_t dst_lim, int i,
+                                             int c, int val) {
+    if (__builtin_expect(p.dst_first != nullptr, 0)) {
+        if ((uint32_t)i >= dst_lim) return;
+        const int64_t idx = p.layout ? (int64_t)c * (int64_t)p.plane_stride + i : (int64_t)i * p.channels + c;
+        if (p.dtype) reinterpret_cast<float*>(out)[idx] = (float)val * (m.ss == 16 ? 0x1p-15f : 0x1p-23f);
+        else out[idx] = val;
+        return;
+    }
+    const int64_t idx = (int64_t)i * m.nc + c;
     if (p.out_format == 0) {
-        pcm_slot[idx] = val;
+        out[idx] = val;
     } else if (m.ss == 16) {
-        reinterpret_cast<uint16_t*>(pcm_slot)[idx] = (uint16_t)val;
+        reinterpret_cast<uint16_t*>(out)[idx] = (uint16_t)val;
     } else {
-        uint8_t* b = reinterpret_cast<uint8_t*>(pcm_slot) + idx * 3;
+        uint8_t* b = reinterpret_cast<uint8_t*>(out) + idx * 3;
         b[0] = (uint8_t)val;
         b[1] = (uint8_t)(val >> 8);
         b[2] = (uint8_t)(val >> 16);
@@ -825,13 +835,14 @@ struct AbOutBlock {
     Meta m;
     int n_out, bias;
     bool two_pass;
-    int32_t* pcm_slot;
+    int32_t* pcm_slot;      // destination mode: the packet's frame 0 of channel 0 in the destination
+    uint32_t dst_lim;       // destination mode: dst_frames of the packet (frames from here on are not stored)
     int32_t* park;
     AbRefill<NS> rf;
     int a_next[AB_CHUNK / 8];
     UbWin ub_next[AB_CHUNK / 8];   // the shift-byte windows of the samples stored at the NEXT step
     int cs, cq[2];          // conversion: this lane's stream and the quantiser masks (1 << q) - 1 of its two channels
-    __device__ AbOutBlock(const alac_decode_params& p_, uint32_t pkt0, int w_, int lane_, AbSharedT<NS>& sh_)
+    __device__ __forceinline__ AbOutBlock(const alac_decode_params& p_, uint32_t pkt0, int w_, int lane_, AbSharedT<NS>& sh_)
         : p(p_), sh(sh_), w(w_), lane(lane_), rf(p_, pkt0, w_, lane_, sh_) {
         const int row = lane >> 4, l = lane & 15, par = l & 1;
         j = l >> 1;
@@ -844,6 +855,12 @@ struct AbOutBlock {
         bias = 1 << (m.rss - 1);
         two_pass = n_out > 0 && m.stereo && !m.esc;   // A is parked in pass 0 and finished in pass 1
         pcm_slot = p.pcm_out + (int64_t)pkt * p.slot_ints;
+        dst_lim = 0;
+        if (p.dst_first && valid) {
+            const uint64_t f0 = p.dst_first[pkt];
+            pcm_slot = p.pcm_out + (p.layout ? f0 : f0 * p.channels);
+            dst_lim = p.dst_frames[pkt];
+        }
         park = p.park ? p.park + (int64_t)pkt * p.park_stride : pcm_slot + m.n;
 #pragma unroll
         for (int h = 0; h < AB_CHUNK / 8; h++) { a_next[h] = 0; ub_next[h].hi = ub_next[h].lo = 0; }
@@ -907,16 +924,16 @@ struct AbOutBlock {
                         const uint32_t bp = m.rawbit + (uint32_t)((i * nch + ch) * m.ss);
                         int val = __builtin_amdgcn_sbfe((int)peek_bits(m.base, m.limit, bp, m.ss), 0, m.ss);
                         if (m.ss == 24) val = __builtin_amdgcn_sbfe(val, 0, 24);
-                        if (ch < m.nc) store_sample(p, m, pcm_slot, (int64_t)i * m.nc + ch, val);
+                        if (ch < m.nc) store_sample(p, m, pcm_slot, dst_lim, i, ch, val);
                     }
-                    if (!m.stereo && m.nc > 1) store_sample(p, m, pcm_slot, (int64_t)i * m.nc + 1, 0);
+                    if (!m.stereo && m.nc > 1) store_sample(p, m, pcm_slot, dst_lim, i, 1, 0);
                 } else {
                     const int i = ih + cnt - 1 - j;
                     if (two_pass) {
                         park[i] = mine;
                     } else {                                            // one channel: done
-                        store_sample(p, m, pcm_slot, (int64_t)i * m.nc, ab_finish24<UB_AHEAD>(m, ub_cur[half], mine, i, 0));
-                        if (m.nc > 1) store_sample(p, m, pcm_slot, (int64_t)i * m.nc + 1, 0);
+                        store_sample(p, m, pcm_slot, dst_lim, i, 0, ab_finish24<UB_AHEAD>(m, ub_cur[half], mine, i, 0));
+                        if (m.nc > 1) store_sample(p, m, pcm_slot, dst_lim, i, 1, 0);
                     }
                 }
             }
@@ -957,8 +974,8 @@ struct AbOutBlock {
                     left = a;
                     right = bb;
                 }
-                store_sample(p, m, pcm_slot, (int64_t)i * m.nc, ab_finish24<UB_AHEAD>(m, ub_cur[half], left, i, 0));
-                if (m.nc > 1) store_sample(p, m, pcm_slot, (int64_t)i * m.nc + 1, ab_finish24<UB_AHEAD>(m, ub_cur[half], right, i, 1));
+                store_sample(p, m, pcm_slot, dst_lim, i, 0, ab_finish24<UB_AHEAD>(m, ub_cur[half], left, i, 0));
+                if (m.nc > 1) store_sample(p, m, pcm_slot, dst_lim, i, 1, ab_finish24<UB_AHEAD>(m, ub_cur[half], right, i, 1));
             }
         }
         if (b < nch1) rf.commit();
@@ -1159,6 +1176,32 @@ extern "C" __global__ __launch_bounds__(256) void alac_decode_ab32_kernel(alac_d
     const uint32_t f = p.ab_flags ? p.ab_flags[blockIdx.x] : 1u;
     if (f == 1u) ab_kernel_body<4>(p, sh);
     else if (f == 3u) ab_kernel_body<2>(p, sh);
+}
+// Destination mode, behind the launch pair (the statuses are final): the zeros of every run -- frames from a packet's decoded
+// ones up to dst_frames, and the whole run of a packet that failed.  Kept are the samples of an OK packet and of a one-channel
+// element with an unknown prediction type (its un-predicted residuals, status 3 as a warning: AlacFile.cs:484-496); a packet
+// with status ALACGPU_ST_DEST_RANGE_D writes nothing.  One wave per packet; nothing to do for the common packet.
+extern "C" __global__ __launch_bounds__(256) void alac_dst_fill_kernel(alac_decode_params p) {
+    const uint32_t pkt = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (pkt >= p.n_packets) return;
+    const int st = p.status[pkt];
+    if (st == ALACGPU_ST_DEST_RANGE_D) return;
+    alacgpu_cfg_dev cfg;
+    const Meta m = parse_meta(p, pkt, 0, true, cfg);
+    const uint32_t lim = p.dst_frames[pkt];
+    const bool kept = st == ALACGPU_ST_OK_D || (st == ALACGPU_ST_UNSUPPORTED_PREDTYPE_D && !m.stereo);
+    const uint32_t from = kept ? min((uint32_t)max(m.n, 0), lim) : 0u;
+    if (from >= lim) return;
+    const uint64_t f0 = p.dst_first[pkt];
+    int32_t* const out = p.pcm_out;   // (int32 0 and float32 +0.0 are the same bits)
+    if (p.layout) {
+        for (uint32_t c = 0; c < p.channels; c++)
+            for (uint32_t i = from + lane; i < lim; i += 64u) out[(uint64_t)c * p.plane_stride + f0 + i] = 0;
+    } else {
+        const uint64_t e1 = (f0 + lim) * p.channels;
+        for (uint64_t e = (f0 + from) * p.channels + lane; e < e1; e += 64u) out[e] = 0;
+    }
 }
 #endif
 #if !defined(ALAC_EMIT) || ALAC_EMIT == 3

@@ -32,6 +32,8 @@ constexpr int N_HOST_STREAMS = 4;   // chunks of the host-buffer pipeline (H2D k
 struct launch_slot {
     uint32_t* d_flags = nullptr;
     size_t flags_n = 0;
+    int32_t* d_park = nullptr;     // destination mode: where channel A waits (n_packets * park_stride ints, grown on demand)
+    size_t park_n = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool used = false;
 };
@@ -144,6 +146,17 @@ int launch(alacgpu_ctx* ctx, const alac_decode_params& p_in, hipStream_t stream)
         sl.flags_n = want;
     }
     p.ab_flags = sl.d_flags;
+    if (p.dst_first) {   // destination mode: channel A is parked in this slot's own place (the destination has no room for it)
+        const size_t want = (size_t)p.n_packets * p.park_stride;
+        if (want > sl.park_n) {
+            if (sl.d_park) (void)hipFree(sl.d_park);
+            sl.d_park = nullptr;
+            sl.park_n = 0;
+            HIP_TRY(ctx, hipMalloc((void**)&sl.d_park, sizeof(int32_t) * (want + want / 4)));
+            sl.park_n = want + want / 4;
+        }
+        p.park = sl.d_park;
+    }
     HIP_TRY(ctx, hipEventRecord(sl.ev0, stream));
     alac_decode_params args = p;
     void* kargs[] = {&args};
@@ -160,6 +173,8 @@ int launch(alacgpu_ctx* ctx, const alac_decode_params& p_in, hipStream_t stream)
         HIP_TRY(ctx, hipLaunchKernel(k, dim3((uint32_t)groups), dim3(256), kargs, 0, stream));
     }
     HIP_TRY(ctx, hipLaunchKernel((const void*)alac_decode_ab32_kernel, dim3((uint32_t)groups), dim3(256), kargs, 0, stream));
+    if (p.dst_first)
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_dst_fill_kernel, dim3((p.n_packets + 3u) / 4u), dim3(256), kargs, 0, stream));
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(sl.ev1, stream));
     sl.used = true;
@@ -196,6 +211,11 @@ int fill_params(alacgpu_ctx* ctx, alac_decode_params& p, const void* d_blob, uin
     p.cu_arrivals = nullptr;
     p.park = nullptr;
     p.park_stride = 0;
+    p.dst_first = nullptr;
+    p.dst_frames = nullptr;
+    p.out_elems = 0;
+    p.plane_stride = 0;
+    p.channels = p.layout = p.dtype = 0;
     return ALACGPU_OK;
 }
 
@@ -238,6 +258,7 @@ const char* alacgpu_status_string(int st) {
     case ALACGPU_ST_OVERRUN: return "bitstream overrun";
     case ALACGPU_ST_REF_THROWS: return "reference throws ArgumentException (order 0, > 4096 samples)";
     case ALACGPU_ST_UNSUPPORTED_PARAMS: return "unsupported parameter combination";
+    case ALACGPU_ST_DEST_RANGE: return "destination run outside the output, or stream channel count differs";
     default: return "unknown status";
     }
 }
@@ -323,6 +344,7 @@ void alacgpu_destroy(alacgpu_ctx* ctx) {
         launch_slot& sl = ctx->slots[i];
         if (sl.used) (void)hipEventSynchronize(sl.ev1);   // device-pointer calls on the caller's streams
         if (sl.d_flags) (void)hipFree(sl.d_flags);
+        if (sl.d_park) (void)hipFree(sl.d_park);
         if (sl.ev0) (void)hipEventDestroy(sl.ev0);
         if (sl.ev1) (void)hipEventDestroy(sl.ev1);
     }
@@ -359,6 +381,37 @@ int alacgpu_decode_batch_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t b
     int rc = fill_params(ctx, p, d_blob, blob_bytes, d_offsets, d_sizes, d_cfg_idx, n_packets, d_pcm_out, slot_ints,
                          d_out_bytes, d_out_samples, d_status);
     if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return launch(ctx, p, (hipStream_t)hip_stream);
+}
+
+int alacgpu_decode_into_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t blob_bytes, const void* d_offsets,
+                               const void* d_sizes, const void* d_cfg_idx, uint32_t n_packets, const void* d_dst_first,
+                               const void* d_dst_frames, void* d_out, uint64_t out_elems, uint32_t channels, int layout, int dtype,
+                               uint64_t plane_stride, void* d_out_samples, void* d_status, void* hip_stream) {
+    if (!ctx || !d_dst_first || !d_dst_frames || (channels != 1 && channels != 2)) return ALACGPU_ERR_BAD_ARG;
+    if ((layout != ALACGPU_DST_INTERLEAVED && layout != ALACGPU_DST_PLANAR) || (dtype != ALACGPU_DST_INT32 && dtype != ALACGPU_DST_FLOAT32))
+        return ALACGPU_ERR_BAD_ARG;
+    if (layout == ALACGPU_DST_PLANAR && plane_stride == 0) return ALACGPU_ERR_BAD_ARG;
+    if (((uintptr_t)d_dst_first & 7u) != 0 || ((uintptr_t)d_dst_frames & 3u) != 0) return ALACGPU_ERR_BAD_ARG;
+    // Smax: the longest frame any stream cfg declares (the reference's scratch holds 16384); statuses as in the slot layout
+    // with slot_ints = channels * Smax, and channel A parks in Smax ints per packet
+    uint32_t smax = 1;
+    for (uint32_t i = 0; i < ctx->n_cfgs; i++) smax = std::max(smax, std::min(ctx->h_cfgs[i].max_samples_per_frame, 16384u));
+    alac_decode_params p;
+    int rc = fill_params(ctx, p, d_blob, blob_bytes, d_offsets, d_sizes, d_cfg_idx, n_packets, d_out, channels * smax, nullptr,
+                         d_out_samples, d_status);
+    if (rc) return rc;
+    if (n_packets == 0) return ALACGPU_OK;
+    p.out_format = ALACGPU_OUT_INT32;
+    p.dst_first = (const uint64_t*)d_dst_first;
+    p.dst_frames = (const uint32_t*)d_dst_frames;
+    p.out_elems = out_elems;
+    p.plane_stride = layout == ALACGPU_DST_PLANAR ? plane_stride : 0;
+    p.channels = channels;
+    p.layout = (uint32_t)layout;
+    p.dtype = (uint32_t)dtype;
+    p.park_stride = smax;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return launch(ctx, p, (hipStream_t)hip_stream);
 }

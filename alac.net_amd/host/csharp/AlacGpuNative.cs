@@ -25,8 +25,9 @@ namespace ALACdotNET.Decoder
         private const string Lib = "alacgpu";   // libalacgpu.so
 
         public const int StOk = 0, StUnsupportedElement = 1, StUnsupportedSampleSize = 2, StUnsupportedPredType = 3,
-                         StBadSampleCount = 4, StOverrun = 5, StRefThrows = 6, StUnsupportedParams = 7;
+                         StBadSampleCount = 4, StOverrun = 5, StRefThrows = 6, StUnsupportedParams = 7, StDestRange = 8;
         public const int OutInt32 = 0, OutPackedLe = 1;
+        public const int DstInterleaved = 0, DstPlanar = 1, DstInt32 = 0, DstFloat32 = 1;
 
         [DllImport(Lib)] public static extern int alacgpu_version();
         [DllImport(Lib)] public static extern int alacgpu_device_count();
@@ -45,6 +46,11 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib, EntryPoint = "alacgpu_decode_batch")] public static extern int alacgpu_decode_batch_ptr(IntPtr ctx, IntPtr blob, ulong blobBytes,
             [In] ulong[] offsets, [In] uint[] sizes, [In] ushort[] cfgIdx, uint nPackets,
             IntPtr pcmOut, uint slotInts, [Out] int[] outBytes, [Out] int[] outSamples, [Out] int[] status);
+        /// <summary>Decode into a gap-free int32 / float32 PCM buffer in device memory (every pointer a device pointer,
+        /// asynchronous on hipStream); there is no host-buffer variant.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_decode_into_device(IntPtr ctx, IntPtr dBlob, ulong blobBytes, IntPtr dOffsets,
+            IntPtr dSizes, IntPtr dCfgIdx, uint nPackets, IntPtr dDstFirst, IntPtr dDstFrames, IntPtr dOut, ulong outElems,
+            uint channels, int layout, int dtype, ulong planeStride, IntPtr dOutSamples, IntPtr dStatus, IntPtr hipStream);
         [DllImport(Lib)] public static extern int alacgpu_decode_frame(IntPtr ctx, uint cfgIndex, [In] byte[] inbuffer, uint inBytes,
             [Out] int[] outbuffer, uint outCapacityInts, out int outBytes, out int status);
         /// <summary>0: one int per sample (default); 1: packed little-endian PCM, the bytes AlacContext.Read returns

@@ -49,7 +49,9 @@ enum {
     ALACGPU_ST_BAD_SAMPLE_COUNT = 4,        /* hassize count <= 0, > 16384 or > slot (IndexOutOfRangeException) */
     ALACGPU_ST_OVERRUN = 5,                 /* bitstream ran past the packet / zero run past the scratch (AlacFile.cs:242) */
     ALACGPU_ST_REF_THROWS = 6,              /* N == 0 && n > 4096: Array.Copy ArgumentException (AlacFile.cs:264-265) */
-    ALACGPU_ST_UNSUPPORTED_PARAMS = 7       /* header/parameter combination outside the supported domain */
+    ALACGPU_ST_UNSUPPORTED_PARAMS = 7,      /* header/parameter combination outside the supported domain */
+    ALACGPU_ST_DEST_RANGE = 8               /* alacgpu_decode_into_device: the packet's run lies outside the output, or its
+                                               stream cfg has another channel count; nothing of it is written */
 };
 
 /* Batch-level return codes */
@@ -175,6 +177,37 @@ int alacgpu_decode_batch_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t b
                                 const void* d_sizes, const void* d_cfg_idx, uint32_t n_packets, void* d_pcm_out,
                                 uint32_t slot_ints, void* d_out_bytes, void* d_out_samples, void* d_status,
                                 void* hip_stream);
+
+/*
+ * Decode straight into a gap-free PCM tensor in HBM (no counterpart in the reference, whose AlacContext.Read hands out one
+ * packet at a time): the slot layout above, compacted inside the kernels.  Device pointers, asynchronous on hip_stream, up
+ * to 8 calls in flight, alignment as for alacgpu_decode_batch_device; d_dst_first is 8-byte aligned, d_out 4-byte aligned.
+ *   d_dst_first[p]   uint64: frame index of packet p's first sample
+ *   d_dst_frames[p]  uint32: frames reserved for packet p (usually its stts duration)
+ *   d_out            out_elems elements of int32 (dtype ALACGPU_DST_INT32: the canonical sample, as the int32 slot format) or
+ *                    float32 (ALACGPU_DST_FLOAT32: sample * 2^-(sample_size-1), exact)
+ *   layout           ALACGPU_DST_INTERLEAVED: frame i, channel c of packet p at (d_dst_first[p] + i) * channels + c;
+ *                    ALACGPU_DST_PLANAR: at c * plane_stride + d_dst_first[p] + i (dst_first = f*C*T + t and plane_stride
+ *                    = T address a [F, C, T] tensor)
+ *   d_out_samples[p] samples per channel the packet decodes to; may be NULL
+ *   d_status[p]      ALACGPU_ST_*: what alacgpu_decode_batch_device reports with slot_ints = channels * Smax (Smax = the
+ *                    largest max_samples_per_frame of the ctx's cfgs, at most 16384), or ALACGPU_ST_DEST_RANGE
+ * Every element of a packet's run (frames 0 .. d_dst_frames[p] of every channel) is written unless its status is
+ * ALACGPU_ST_DEST_RANGE: the decoded frames (those from d_dst_frames[p] on are dropped: a last packet longer than its
+ * duration), then zeros.  A packet that fails gets a run of zeros; a one-channel element with an unknown prediction type
+ * (status 3) keeps its un-predicted residuals, as in the slot layout; a one-channel element in a two-channel stream has
+ * zeros in channel 1.  Elements outside every run are never touched.  Channel A of a two-channel packet waits in scratch
+ * the ctx owns (n_packets * Smax ints per call in flight, kept for reuse).  ALACGPU_ERR_BAD_ARG: a NULL ctx or array
+ * (d_cfg_idx and d_out_samples may be NULL), channels not 1 / 2, an unknown layout or dtype, planar with plane_stride 0.
+ * Host-buffer callers (the C# AlacContext) have no variant of this: they get the slot layout.
+ */
+enum { ALACGPU_DST_INTERLEAVED = 0, ALACGPU_DST_PLANAR = 1 };
+enum { ALACGPU_DST_INT32 = 0, ALACGPU_DST_FLOAT32 = 1 };
+int alacgpu_decode_into_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t blob_bytes, const void* d_offsets,
+                               const void* d_sizes, const void* d_cfg_idx, uint32_t n_packets,
+                               const void* d_dst_first, const void* d_dst_frames, void* d_out, uint64_t out_elems,
+                               uint32_t channels, int layout, int dtype, uint64_t plane_stride,
+                               void* d_out_samples, void* d_status, void* hip_stream);
 
 /* Single-packet drop-in for `int DecodeFrame(byte[] inbuffer, int[] outbuffer)` (AlacFile.cs:428):
  * writes the reference's own int[] layout (24-bit: one int per byte) and returns its byte count in

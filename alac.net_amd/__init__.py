@@ -55,6 +55,9 @@ SYMBOLS = {
                                               _VP, _VP, _VP]),
     "alacgpu_decode_into_device": (C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, C.c_uint64,
                                              C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP]),
+    "alacgpu_encode_max_packet_bytes": (C.c_size_t, [C.c_uint32, C.c_int, C.c_int]),
+    "alacgpu_encode_device": (C.c_int, [_VP, _VP, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP, C.c_uint32,
+                                        _VP, C.c_uint64, _VP, _VP, _VP]),
     "alacgpu_decode_frame": (C.c_int, [_VP, C.c_uint32, _VP, C.c_uint32, _VP, C.c_uint32, _VP, _VP]),
     "alacgpu_expand_reference_layout": (C.c_size_t, [_VP, _VP, C.c_int32, _VP]),
     "alacgpu_format_samples": (C.c_size_t, [C.c_int, _VP, C.c_int32, _VP]),
@@ -227,6 +230,36 @@ class AlacGpuContext:
         rc = lib().alacgpu_decode_into_device(self._ctx, dp(d_blob), blob_bytes, dp(d_offsets), dp(d_sizes), dp(d_cfg_idx),
                                               n_packets, dp(d_dst_first), dp(d_dst_frames), dp(out), out.numel(), channels, lay,
                                               dtype, plane_stride, dp(d_out_samples), dp(d_status), _VP(stream))
+        _check(rc, self._ctx)
+
+    def encode_device(self, pcm, channels, d_src_first, d_src_frames, d_cfg_idx, n_packets, d_packets, slot_bytes, d_sizes,
+                      d_status, layout="planar", plane_stride=0, stream=0):
+        """alacgpu_encode_device: packet p encodes frames d_src_first[p] .. + d_src_frames[p] of `pcm` (torch int32 or float32
+        on this device, contiguous; its dtype picks the element type) with stream cfg d_cfg_idx[p]; its bytes land at
+        d_packets[p * slot_bytes:] (a uint8 device tensor), its size in d_sizes[p], its status in d_status[p].  d_* are torch
+        device tensors; asynchronous on `stream` (raw hipStream_t)."""
+        import torch
+
+        if pcm.dtype == torch.int32:
+            dtype = DST_INT32
+        elif pcm.dtype == torch.float32:
+            dtype = DST_FLOAT32
+        else:
+            raise ValueError(f"pcm must be torch.int32 or torch.float32, not {pcm.dtype}")
+        if not pcm.is_contiguous():
+            raise ValueError("pcm must be contiguous")
+        if pcm.device.type != "cuda":
+            raise ValueError("pcm must be a device tensor")
+        lay = {"interleaved": DST_INTERLEAVED, "planar": DST_PLANAR}.get(layout)
+        if lay is None:
+            raise ValueError(f"layout must be 'interleaved' or 'planar', not {layout!r}")
+
+        def dp(t):
+            return _VP(t.data_ptr()) if t is not None else None
+
+        rc = lib().alacgpu_encode_device(self._ctx, dp(pcm), pcm.numel(), channels, lay, dtype, plane_stride, dp(d_src_first),
+                                         dp(d_src_frames), dp(d_cfg_idx), n_packets, dp(d_packets), slot_bytes, dp(d_sizes),
+                                         dp(d_status), _VP(stream))
         _check(rc, self._ctx)
 
     def set_output_format(self, fmt):
@@ -529,6 +562,140 @@ def load_batch(sources, device=0, dtype=None, max_frames=None):
         raise AlacGpuError(f"source {f}, packet {q} does not decode: status {int(st[p])} "
                            f"({lib().alacgpu_status_string(int(st[p])).decode()})")
     return out, torch.from_numpy(lengths), rate
+
+
+# ---- tensors to M4A files (alacgpu_encode_device) -----------------------------------------------------------------------------
+def encode_max_packet_bytes(frames, sample_size, channels):
+    """alacgpu_encode_max_packet_bytes: the largest packet the encoder writes for that many frames (an escape packet with its
+    sample count and the END tag, rounded up to 16 bytes)."""
+    return int(lib().alacgpu_encode_max_packet_bytes(int(frames), int(sample_size), int(channels)))
+
+
+def _check_save_args(pcm, batch, sample_size, frame_length, sample_rate):
+    """The host-side checks of save / save_batch, before any device work; returns (F, C, T)."""
+    import torch
+
+    want = 3 if batch else 2
+    if not isinstance(pcm, torch.Tensor) or pcm.dim() != want:
+        raise ValueError(f"pcm must be a torch tensor of shape {'[F, C, T]' if batch else '[C, T]'}")
+    F, C_, T = (pcm.shape[0], pcm.shape[1], pcm.shape[2]) if batch else (1, pcm.shape[0], pcm.shape[1])
+    if C_ not in (1, 2):
+        raise ValueError(f"{C_} channels: ALAC here is one or two channels")
+    if pcm.dtype not in (torch.int32, torch.float32):
+        raise ValueError(f"pcm must be torch.int32 or torch.float32, not {pcm.dtype}")
+    if sample_size not in (16, 24):
+        raise ValueError(f"sample_size must be 16 or 24, not {sample_size}")
+    if not isinstance(frame_length, (int, np.integer)) or not 1 <= int(frame_length) <= 16384:
+        raise ValueError(f"frame_length must be 1 .. 16384, not {frame_length}")
+    if not isinstance(sample_rate, (int, np.integer)) or not 1 <= int(sample_rate) < 1 << 32:
+        raise ValueError(f"sample_rate must be a positive 32-bit integer, not {sample_rate}")
+    if F == 0 or T == 0:
+        raise ValueError("empty input: nothing to encode")
+    return F, C_, T
+
+
+def _check_stco(T, C_, sample_size, frame_length):
+    """A file's 32-bit chunk offsets must hold its media data at its worst case (every packet an escape packet)."""
+    n = -(-int(T) // int(frame_length))
+    worst = n * encode_max_packet_bytes(frame_length, sample_size, C_) + 64 * n + 4096   # packets, the tables, the atoms
+    if worst >= 1 << 32:
+        raise ValueError(f"{T} frames can need {worst} bytes: more than the 32-bit chunk offsets (stco) of an M4A file address")
+
+
+def _encode_tensor(pcm, lengths, sample_size, frame_length, device):
+    """One alacgpu_encode_device call over every file of pcm[F, C, T] (frames 0 .. lengths[f]); returns per file the list of
+    packet bytes.  Only the packets' own bytes are copied to the host: they are compacted on the device first."""
+    import torch
+
+    F, C_, T = pcm.shape
+    dev = pcm.device
+    counts = [-(-int(L) // frame_length) for L in lengths]
+    file_of = np.repeat(np.arange(F, dtype=np.int64), counts)
+    first_in_file = np.concatenate([np.arange(c, dtype=np.int64) * frame_length for c in counts])
+    frames = np.minimum(np.repeat(np.asarray(lengths, dtype=np.int64), counts) - first_in_file, frame_length)
+    n = len(file_of)
+    cfgs = [(frame_length, sample_size, 40, 10, 14, C_)]
+    slot = encode_max_packet_bytes(frame_length, sample_size, C_)
+    d_first = torch.from_numpy(file_of * C_ * T + first_in_file).to(dev)
+    d_frames = torch.from_numpy(frames.astype(np.int32)).to(dev)
+    d_ci = torch.zeros(n, dtype=torch.int16, device=dev)
+    d_packets = torch.empty(n * slot, dtype=torch.uint8, device=dev)
+    d_sizes = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_st = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    src = pcm.contiguous()
+    with AlacGpuContext(cfgs, device) as ctx:
+        stream = torch.cuda.current_stream(dev)
+        ctx.encode_device(src, C_, d_first, d_frames, d_ci, n, d_packets, slot, d_sizes, d_st, layout="planar",
+                          plane_stride=T, stream=stream.cuda_stream)
+        st = d_st.cpu().numpy()     # (waits for the encode: the context's workspace is released behind it)
+    bad = np.nonzero(st != ST_OK)[0]
+    if len(bad):
+        p = int(bad[0])
+        raise AlacGpuError(f"packet {p} was not encoded: status {int(st[p])} ({lib().alacgpu_status_string(int(st[p])).decode()})")
+    # compact on the device: a gather of every packet's bytes, then one copy of exactly those bytes
+    sizes64 = d_sizes.to(torch.int64)
+    ends = torch.cumsum(sizes64, 0)
+    total = int(ends[-1])
+    starts = ends - sizes64
+    owner = torch.repeat_interleave(torch.arange(n, device=dev), sizes64, output_size=total)
+    src_idx = owner * slot + (torch.arange(total, device=dev) - starts[owner])
+    blob = d_packets[src_idx].cpu().numpy().tobytes()
+    sizes = d_sizes.cpu().numpy().astype(np.int64)
+    offs = np.concatenate([[0], np.cumsum(sizes)])
+    out, p = [], 0
+    for f in range(F):
+        out.append([blob[offs[q]:offs[q + 1]] for q in range(p, p + counts[f])])
+        p += counts[f]
+    return out, [frames[file_of == f] for f in range(F)]
+
+
+def _write_file(dest, packets, durations, frame_length, sample_size, channels, sample_rate):
+    from .container import write_m4a
+
+    sizes = [len(x) for x in packets]
+    frames = int(np.sum(durations))
+    seconds = frames / float(sample_rate)
+    avg = int(round(8 * sum(sizes) / seconds)) if seconds > 0 else 0
+    data = write_m4a(packets, [int(d) for d in durations], frame_len=frame_length, sample_size=sample_size, channels=channels,
+                     sample_rate=sample_rate, max_frame_bytes=max(sizes), avg_bitrate=min(avg, (1 << 32) - 1))
+    if isinstance(dest, (str, os.PathLike)):
+        with open(dest, "wb") as f:
+            f.write(data)
+    else:
+        dest.write(data)
+    return len(data)
+
+
+def save(dest, pcm, sample_rate, sample_size=16, frame_length=4096, device=0):
+    """Encode pcm [C, T] (planar, torch int32 -- the canonical sample -- or float32 -- sample * 2^-(bits-1), what `load`
+    returns) on the GPU to ALAC and write it as an M4A file to `dest` (a path or a writable binary file object).  Returns the
+    file's size in bytes.  ValueError (before any device work) for a channel count other than 1 / 2, a sample size other than
+    16 / 24, a frame_length outside 1 .. 16384, a tensor that is not on the GPU, an empty input, or a length whose file could
+    outgrow the 32-bit chunk offsets."""
+    F, C_, T = _check_save_args(pcm, False, sample_size, frame_length, sample_rate)
+    _check_stco(T, C_, sample_size, int(frame_length))
+    if pcm.device.type != "cuda":
+        raise ValueError("pcm must be on the GPU")
+    packets, durations = _encode_tensor(pcm.unsqueeze(0), [T], sample_size, int(frame_length), device)
+    return _write_file(dest, packets[0], durations[0], int(frame_length), sample_size, C_, int(sample_rate))
+
+
+def save_batch(dests, pcm, lengths, sample_rate, sample_size=16, frame_length=4096, device=0):
+    """`save` for F files in ONE launch: file f is frames 0 .. lengths[f] of pcm[f] ([F, C, Tmax], as `load_batch` returns
+    it); dests[f] a path or a writable binary file object.  Returns the file sizes."""
+    F, C_, T = _check_save_args(pcm, True, sample_size, frame_length, sample_rate)
+    lengths = [int(x) for x in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+    if len(dests) != F or len(lengths) != F:
+        raise ValueError(f"{F} files in pcm, {len(dests)} destinations and {len(lengths)} lengths")
+    for L in lengths:
+        if not 1 <= L <= T:
+            raise ValueError(f"length {L} outside 1 .. {T}")
+        _check_stco(L, C_, sample_size, int(frame_length))
+    if pcm.device.type != "cuda":
+        raise ValueError("pcm must be on the GPU")
+    packets, durations = _encode_tensor(pcm, lengths, sample_size, int(frame_length), device)
+    return [_write_file(d, packets[f], durations[f], int(frame_length), sample_size, C_, int(sample_rate))
+            for f, d in enumerate(dests)]
 
 
 class AlacFile:

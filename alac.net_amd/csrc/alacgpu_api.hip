@@ -13,6 +13,7 @@
 #include <thread>
 #include <vector>
 
+#include "alac_encode.h"
 #include "alac_kernels.h"
 #include "alacgpu.h"
 
@@ -64,6 +65,13 @@ struct alacgpu_ctx {
     void* d_ws = nullptr;
     size_t ws_bytes = 0;
     int32_t* h_frame = nullptr;        // pinned staging of alacgpu_decode_frame (one slot of the widest kind)
+    // alacgpu_encode_device: one workspace slot per workgroup of a round (codes and bit positions, grown on demand), and the
+    // event behind the last call's launches (the next call's stream waits for it before it reuses the workspace)
+    uint64_t* d_enc_code = nullptr;
+    uint32_t* d_enc_pos = nullptr;
+    size_t enc_items = 0;              // items the workspace holds (slots * alac_enc_items(smax))
+    hipEvent_t enc_done = nullptr;
+    bool enc_used = false;
     std::string last_error;
 };
 
@@ -349,6 +357,10 @@ void alacgpu_destroy(alacgpu_ctx* ctx) {
         if (sl.ev1) (void)hipEventDestroy(sl.ev1);
     }
     if (ctx->d_ws) (void)hipFree(ctx->d_ws);
+    if (ctx->enc_used) (void)hipEventSynchronize(ctx->enc_done);
+    if (ctx->enc_done) (void)hipEventDestroy(ctx->enc_done);
+    if (ctx->d_enc_code) (void)hipFree(ctx->d_enc_code);
+    if (ctx->d_enc_pos) (void)hipFree(ctx->d_enc_pos);
     if (ctx->d_cu_arrivals) cu_counters_release(ctx->device);
     if (ctx->h_frame) (void)hipHostFree(ctx->h_frame);
     if (ctx->d_cfgs) (void)hipFree(ctx->d_cfgs);
@@ -414,6 +426,90 @@ int alacgpu_decode_into_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t bl
     p.park_stride = smax;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return launch(ctx, p, (hipStream_t)hip_stream);
+}
+
+size_t alacgpu_encode_max_packet_bytes(uint32_t frames, int sample_size, int channels) {
+    // an escape packet with its sample count: header 23 + 32 bits, the raw samples, the END tag
+    const uint64_t bits = 23u + 32u + (uint64_t)frames * (uint64_t)(channels < 1 ? 1 : channels) * (uint64_t)(sample_size < 0 ? 0 : sample_size) + 3u;
+    return (size_t)align_up((bits + 7) / 8, 16);
+}
+
+int alacgpu_encode_device(alacgpu_ctx* ctx, const void* d_pcm, uint64_t src_elems, uint32_t channels, int layout, int dtype,
+                          uint64_t plane_stride, const void* d_src_first, const void* d_src_frames, const void* d_cfg_idx,
+                          uint32_t n_packets, void* d_packets, uint64_t slot_bytes, void* d_sizes, void* d_status,
+                          void* hip_stream) {
+    if (!ctx || !d_pcm || !d_src_first || !d_src_frames || !d_cfg_idx || !d_packets || !d_sizes || !d_status)
+        return ALACGPU_ERR_BAD_ARG;
+    if ((channels != 1 && channels != 2) || (layout != ALACGPU_DST_INTERLEAVED && layout != ALACGPU_DST_PLANAR) ||
+        (dtype != ALACGPU_DST_INT32 && dtype != ALACGPU_DST_FLOAT32) || (layout == ALACGPU_DST_PLANAR && plane_stride == 0))
+        return ALACGPU_ERR_BAD_ARG;
+    if (((uintptr_t)d_pcm & 3u) != 0 || ((uintptr_t)d_src_first & 7u) != 0 || ((uintptr_t)d_src_frames & 3u) != 0 ||
+        ((uintptr_t)d_cfg_idx & 1u) != 0 || ((uintptr_t)d_packets & 15u) != 0 || (slot_bytes & 15u) != 0 ||
+        ((uintptr_t)d_sizes & 3u) != 0 || ((uintptr_t)d_status & 3u) != 0)
+        return ALACGPU_ERR_BAD_ARG;
+    uint32_t smax = 1;
+    for (uint32_t i = 0; i < ctx->n_cfgs; i++) {
+        const alacgpu_cfg& c = ctx->h_cfgs[i];
+        if (c.num_channels != channels) return ALACGPU_ERR_BAD_ARG;
+        const uint32_t frames = std::min(c.max_samples_per_frame, 16384u);
+        if (slot_bytes < alacgpu_encode_max_packet_bytes(frames, c.sample_size, (int)channels)) return ALACGPU_ERR_BAD_ARG;
+        smax = std::max(smax, frames);
+    }
+    if (n_packets == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    // a round: up to 16 workgroups per CU, one packet and one workspace slot each
+    int n_cu = 0;
+    HIP_TRY(ctx, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    const uint32_t round = std::min<uint32_t>(n_packets, (uint32_t)std::max(n_cu, 1) * 16u);
+    const size_t items = (size_t)round * alac_enc_items(smax);
+    if (!ctx->enc_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->enc_done, hipEventDisableTiming));
+    if (items > ctx->enc_items) {
+        if (ctx->enc_used) HIP_TRY(ctx, hipEventSynchronize(ctx->enc_done));   // the last call has finished with it
+        if (ctx->d_enc_code) (void)hipFree(ctx->d_enc_code);
+        if (ctx->d_enc_pos) (void)hipFree(ctx->d_enc_pos);
+        ctx->d_enc_code = nullptr;
+        ctx->d_enc_pos = nullptr;
+        ctx->enc_items = 0;
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_enc_code, sizeof(uint64_t) * items));
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_enc_pos, sizeof(uint32_t) * (items + round)));
+        ctx->enc_items = items;
+    } else if (ctx->enc_used) {
+        HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->enc_done, 0));   // (a call on another stream may still use it)
+    }
+    alac_encode_params p;
+    p.pcm = d_pcm;
+    p.src_elems = src_elems;
+    p.plane_stride = layout == ALACGPU_DST_PLANAR ? plane_stride : 0;
+    p.channels = channels;
+    p.layout = (uint32_t)layout;
+    p.dtype = (uint32_t)dtype;
+    p.n_packets = n_packets;
+    p.src_first = (const uint64_t*)d_src_first;
+    p.src_frames = (const uint32_t*)d_src_frames;
+    p.cfg_idx = (const uint16_t*)d_cfg_idx;
+    p.cfgs = ctx->d_cfgs;
+    p.n_cfgs = ctx->n_cfgs;
+    p.smax = smax;
+    p.packets = (uint8_t*)d_packets;
+    p.slot_bytes = slot_bytes;
+    p.sizes = (uint32_t*)d_sizes;
+    p.status = (int32_t*)d_status;
+    p.ws_code = ctx->d_enc_code;
+    p.ws_pos = ctx->d_enc_pos;
+    for (uint32_t first = 0; first < n_packets; first += round) {
+        p.first_packet = first;
+        alac_encode_params args = p;
+        void* kargs[] = {&args};
+        const dim3 grid(std::min(round, n_packets - first)), block(ALAC_ENC_THREADS);
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_encode_analyse_kernel, grid, block, kargs, 0, stream));
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_encode_codes_kernel, grid, block, kargs, 0, stream));
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_encode_emit_kernel, grid, block, kargs, 0, stream));
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->enc_done, stream));
+    ctx->enc_used = true;
+    return ALACGPU_OK;
 }
 
 }  // extern "C"

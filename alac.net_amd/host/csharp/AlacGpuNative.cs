@@ -51,6 +51,12 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_decode_into_device(IntPtr ctx, IntPtr dBlob, ulong blobBytes, IntPtr dOffsets,
             IntPtr dSizes, IntPtr dCfgIdx, uint nPackets, IntPtr dDstFirst, IntPtr dDstFrames, IntPtr dOut, ulong outElems,
             uint channels, int layout, int dtype, ulong planeStride, IntPtr dOutSamples, IntPtr dStatus, IntPtr hipStream);
+        /// <summary>Encode PCM in device memory (int32 or float32, interleaved or planar) to ALAC packets in device memory, one
+        /// run of frames per packet, packet p at dPackets + p * slotBytes; asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern UIntPtr alacgpu_encode_max_packet_bytes(uint frames, int sampleSize, int channels);
+        [DllImport(Lib)] public static extern int alacgpu_encode_device(IntPtr ctx, IntPtr dPcm, ulong srcElems, uint channels, int layout,
+            int dtype, ulong planeStride, IntPtr dSrcFirst, IntPtr dSrcFrames, IntPtr dCfgIdx, uint nPackets, IntPtr dPackets,
+            ulong slotBytes, IntPtr dSizes, IntPtr dStatus, IntPtr hipStream);
         [DllImport(Lib)] public static extern int alacgpu_decode_frame(IntPtr ctx, uint cfgIndex, [In] byte[] inbuffer, uint inBytes,
             [Out] int[] outbuffer, uint outCapacityInts, out int outBytes, out int status);
         /// <summary>0: one int per sample (default); 1: packed little-endian PCM, the bytes AlacContext.Read returns

@@ -209,6 +209,36 @@ int alacgpu_decode_into_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t bl
                                uint32_t channels, int layout, int dtype, uint64_t plane_stride,
                                void* d_out_samples, void* d_status, void* hip_stream);
 
+/*
+ * Encoder (no counterpart in the reference, which only decodes): PCM in HBM to ALAC packets in HBM, one packet per run of
+ * frames, asynchronous on hip_stream.  Device pointers; d_pcm 4-byte, d_src_first 8-byte, d_packets 16-byte aligned.
+ *   d_pcm            src_elems int32 (ALACGPU_DST_INT32: the canonical sample, clamped to the sample range) or float32
+ *                    (ALACGPU_DST_FLOAT32: round(x * 2^(sample_size-1)), clamped) elements, laid out as for
+ *                    alacgpu_decode_into_device: frame t, channel c at t * channels + c or c * plane_stride + t
+ *   d_src_first[p]   uint64: first frame of packet p;  d_src_frames[p] uint32: its frame count (1 .. the cfg's
+ *                    max_samples_per_frame, at most 16384)
+ *   d_cfg_idx[p]     uint16: the stream cfg of packet p (ctx->cfgs); it gives sample_size (16 or 24), pb / mb / kb and
+ *                    max_samples_per_frame (hassize is set exactly when a packet is shorter)
+ *   d_packets        packet p is written at d_packets + p * slot_bytes; slot_bytes is a multiple of 16 and at least
+ *                    alacgpu_encode_max_packet_bytes(max_samples_per_frame, sample_size, channels) for every cfg
+ *   d_sizes[p]       uint32: packet p's size in bytes (0 when it failed)
+ *   d_status[p]      ALACGPU_ST_OK; ALACGPU_ST_BAD_SAMPLE_COUNT (0 frames or more than the cfg allows),
+ *                    ALACGPU_ST_DEST_RANGE (the run lies outside the source), ALACGPU_ST_UNSUPPORTED_SAMPLE_SIZE,
+ *                    ALACGPU_ST_UNSUPPORTED_PARAMS (cfg index out of range): such a packet's slot is not touched
+ * The encoder's fixed policy (alac_encode.hip): 16-bit without and 24-bit with one uncompressed low byte; a two-channel
+ * stream tries mix shift 2 with weights 0..4; LPC order 8 at q = 9, predictionType 0, ricemodifier 4; an escape packet when
+ * the compressed one would not be smaller, so no packet exceeds alacgpu_encode_max_packet_bytes.  The packet bytes past
+ * d_sizes[p] up to the next multiple of 4 are zero; the rest of the slot is not touched.  The ctx keeps a workspace
+ * (36 bytes per frame of max_samples_per_frame for each of up to 16 packets per CU); calls on one ctx run one after the other
+ * on the device.  ALACGPU_ERR_BAD_ARG: a NULL ctx or array, channels not those of every cfg of the ctx, an unknown layout or
+ * dtype, planar with plane_stride 0, a misaligned pointer, or a slot_bytes below the bound.
+ */
+size_t alacgpu_encode_max_packet_bytes(uint32_t frames, int sample_size, int channels);
+int alacgpu_encode_device(alacgpu_ctx* ctx, const void* d_pcm, uint64_t src_elems, uint32_t channels, int layout, int dtype,
+                          uint64_t plane_stride, const void* d_src_first, const void* d_src_frames, const void* d_cfg_idx,
+                          uint32_t n_packets, void* d_packets, uint64_t slot_bytes, void* d_sizes, void* d_status,
+                          void* hip_stream);
+
 /* Single-packet drop-in for `int DecodeFrame(byte[] inbuffer, int[] outbuffer)` (AlacFile.cs:428):
  * writes the reference's own int[] layout (24-bit: one int per byte) and returns its byte count in
  * *out_bytes.  status as above (the C# shim rethrows the reference's exceptions from it). */

@@ -22,6 +22,8 @@ ST_DEST_RANGE = 8
 # alacgpu_decode_into_device: destination layout and element type
 DST_INTERLEAVED, DST_PLANAR = 0, 1
 DST_INT32, DST_FLOAT32 = 0, 1
+_LAYOUTS = {"interleaved": DST_INTERLEAVED, "planar": DST_PLANAR}
+MAX_FRAME = 16384   # the longest frame the reference decodes (its scratch, AlacFile.cs:28)
 
 CFG_DTYPE = np.dtype(
     [
@@ -84,6 +86,22 @@ class AlacGpuError(RuntimeError):
     pass
 
 
+class _Closing:
+    """close() at the end of a with-block, and when the object is collected."""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def lib():
     """Load libalacgpu.so (built by __graft_entry__.build()).  Fails loudly: no fallback."""
     global _LIB
@@ -104,6 +122,47 @@ def lib():
 
 def _ptr(a):
     return a.ctypes.data_as(_VP) if a is not None else None
+
+
+def _dp(t):
+    """A torch device tensor's address (None stays NULL)."""
+    return _VP(t.data_ptr()) if t is not None else None
+
+
+def _pcm_view(name, t, layout):
+    """The element type and layout codes of a PCM tensor argument (decode_into_device, encode_device); ValueError for a tensor
+    the library cannot take."""
+    import torch
+
+    dtype = {torch.int32: DST_INT32, torch.float32: DST_FLOAT32}.get(t.dtype)
+    if dtype is None:
+        raise ValueError(f"{name} must be torch.int32 or torch.float32, not {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if t.device.type != "cuda":
+        raise ValueError(f"{name} must be a device tensor")
+    if layout not in _LAYOUTS:
+        raise ValueError(f"layout must be 'interleaved' or 'planar', not {layout!r}")
+    return dtype, _LAYOUTS[layout]
+
+
+def _status_text(st):
+    return f"status {int(st)} ({lib().alacgpu_status_string(int(st)).decode()})"
+
+
+def _raise_reference_exception(st, sample_size):
+    """The exception the reference throws where DecodeFrame ends with status `st` (AlacFile.cs:574,:650,:660,:715); no
+    exception for the others."""
+    if st == ST_UNSUPPORTED_SAMPLE_SIZE:
+        raise Exception("FIXME: unimplemented sample size " + str(sample_size))
+    if st == ST_UNSUPPORTED_PREDTYPE:
+        raise Exception("FIXME: unhandled predicition type")
+    if st in (ST_BAD_SAMPLE_COUNT, ST_OVERRUN):
+        raise IndexError("Index was outside the bounds of the array.")
+    if st == ST_REF_THROWS:
+        raise ValueError("Destination array was not long enough.")
+    if st == ST_UNSUPPORTED_PARAMS:
+        raise Exception("unsupported parameter combination")
 
 
 def make_cfgs(rows):
@@ -132,7 +191,31 @@ def _check(rc, ctx=None):
         raise AlacGpuError(f"alacgpu rc={rc}: {msg}")
 
 
-class AlacGpuContext:
+def _check_comm(rc, comm):
+    if rc != 0:
+        L = lib()
+        raise AlacGpuError(f"alacgpu rc={rc}: {L.alacgpu_strerror(rc).decode()} ({L.alacgpu_comm_last_error(comm).decode()})")
+
+
+def _host_batch(cfgs, blob, offsets, sizes, cfg_idx, slot_ints, out):
+    """The host-buffer decodes' arrays: returns the C call's arguments from `blob` on, and the outputs (pcm[n, slot_ints],
+    out_bytes[n], out_samples[n], status[n]); `out` is the pcm array to decode into, if given."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint32)
+    ci = None if cfg_idx is None else np.ascontiguousarray(cfg_idx, dtype=np.uint16)
+    n = len(sizes)
+    if slot_ints is None:
+        slot_ints = int(max(int(c["max_samples_per_frame"]) * int(c["num_channels"]) for c in cfgs))
+    pcm = out if out is not None else np.zeros((n, slot_ints), dtype=np.int32)
+    if pcm.dtype != np.int32 or pcm.shape != (n, slot_ints) or not pcm.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous int32 array of shape (n_packets, slot_ints)")
+    outs = (pcm, np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32))
+    args = (_ptr(blob), blob.size, _ptr(offsets), _ptr(sizes), _ptr(ci), n, _ptr(pcm), slot_ints) + tuple(_ptr(a) for a in outs[1:])
+    return args, outs
+
+
+class AlacGpuContext(_Closing):
     """Owns one alacgpu_ctx (one per host thread; calls are blocking unless stated)."""
 
     def __init__(self, cfgs, device=0):
@@ -150,54 +233,22 @@ class AlacGpuContext:
             lib().alacgpu_destroy(self._ctx)
             self._ctx = _VP()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
     # -- host buffers: H2D + kernel + D2H ---------------------------------------------------------
     def decode_batch(self, blob, offsets, sizes, cfg_idx=None, slot_ints=None, out=None):
         """Returns (pcm[n, slot_ints] int32, out_bytes[n], out_samples[n], status[n]).  `out`: a pcm array to decode
         into instead of a fresh one (a fresh 100+ MB array costs more in page faults than the whole decode)."""
-        blob = np.ascontiguousarray(blob, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        sizes = np.ascontiguousarray(sizes, dtype=np.uint32)
-        ci = None if cfg_idx is None else np.ascontiguousarray(cfg_idx, dtype=np.uint16)
-        n = len(sizes)
-        if slot_ints is None:
-            slot_ints = int(max(int(c["max_samples_per_frame"]) * int(c["num_channels"]) for c in self.cfgs))
-        if out is not None:
-            if out.dtype != np.int32 or out.shape != (n, slot_ints) or not out.flags.c_contiguous:
-                raise ValueError("out must be a C-contiguous int32 array of shape (n_packets, slot_ints)")
-            pcm = out
-        else:
-            pcm = np.zeros((n, slot_ints), dtype=np.int32)
-        ob = np.zeros(n, dtype=np.int32)
-        os_ = np.zeros(n, dtype=np.int32)
-        st = np.zeros(n, dtype=np.int32)
-        rc = lib().alacgpu_decode_batch(self._ctx, _ptr(blob), blob.size, _ptr(offsets), _ptr(sizes), _ptr(ci), n,
-                                        _ptr(pcm), slot_ints, _ptr(ob), _ptr(os_), _ptr(st))
-        _check(rc, self._ctx)
-        return pcm, ob, os_, st
+        args, outs = _host_batch(self.cfgs, blob, offsets, sizes, cfg_idx, slot_ints, out)
+        _check(lib().alacgpu_decode_batch(self._ctx, *args), self._ctx)
+        return outs
 
     # -- device buffers (torch tensors on this device), asynchronous on `stream` --------------------
     def decode_batch_device(self, d_blob, blob_bytes, d_offsets, d_sizes, d_cfg_idx, n_packets, d_pcm, slot_ints,
                             d_out_bytes, d_out_samples, d_status, stream=0):
         """All d_* are torch CUDA tensors (or None where the header allows NULL); `stream` is a raw
         hipStream_t handle (e.g. torch.cuda.current_stream().cuda_stream)."""
-        def dp(t):
-            return _VP(t.data_ptr()) if t is not None else None
-
-        rc = lib().alacgpu_decode_batch_device(self._ctx, dp(d_blob), blob_bytes, dp(d_offsets), dp(d_sizes),
-                                               dp(d_cfg_idx), n_packets, dp(d_pcm), slot_ints, dp(d_out_bytes),
-                                               dp(d_out_samples), dp(d_status), _VP(stream))
+        rc = lib().alacgpu_decode_batch_device(self._ctx, _dp(d_blob), blob_bytes, _dp(d_offsets), _dp(d_sizes),
+                                               _dp(d_cfg_idx), n_packets, _dp(d_pcm), slot_ints, _dp(d_out_bytes),
+                                               _dp(d_out_samples), _dp(d_status), _VP(stream))
         _check(rc, self._ctx)
 
     def decode_into_device(self, d_blob, blob_bytes, d_offsets, d_sizes, d_cfg_idx, n_packets, d_dst_first, d_dst_frames, out,
@@ -206,30 +257,12 @@ class AlacGpuContext:
         float32 on this device, contiguous; its dtype picks the element type), interleaved ((first + i) * channels + c) or
         planar (c * plane_stride + first + i).  d_* are torch device tensors (d_cfg_idx / d_out_samples may be None);
         asynchronous on `stream` (raw hipStream_t)."""
-        import torch
-
-        if out.dtype == torch.int32:
-            dtype = DST_INT32
-        elif out.dtype == torch.float32:
-            dtype = DST_FLOAT32
-        else:
-            raise ValueError(f"out must be torch.int32 or torch.float32, not {out.dtype}")
-        if not out.is_contiguous():
-            raise ValueError("out must be contiguous")
-        if out.device.type != "cuda":
-            raise ValueError("out must be a device tensor")
-        lay = {"interleaved": DST_INTERLEAVED, "planar": DST_PLANAR}.get(layout)
-        if lay is None:
-            raise ValueError(f"layout must be 'interleaved' or 'planar', not {layout!r}")
+        dtype, lay = _pcm_view("out", out, layout)
         if d_status is None:
             raise ValueError("d_status is required")
-
-        def dp(t):
-            return _VP(t.data_ptr()) if t is not None else None
-
-        rc = lib().alacgpu_decode_into_device(self._ctx, dp(d_blob), blob_bytes, dp(d_offsets), dp(d_sizes), dp(d_cfg_idx),
-                                              n_packets, dp(d_dst_first), dp(d_dst_frames), dp(out), out.numel(), channels, lay,
-                                              dtype, plane_stride, dp(d_out_samples), dp(d_status), _VP(stream))
+        rc = lib().alacgpu_decode_into_device(self._ctx, _dp(d_blob), blob_bytes, _dp(d_offsets), _dp(d_sizes), _dp(d_cfg_idx),
+                                              n_packets, _dp(d_dst_first), _dp(d_dst_frames), _dp(out), out.numel(), channels, lay,
+                                              dtype, plane_stride, _dp(d_out_samples), _dp(d_status), _VP(stream))
         _check(rc, self._ctx)
 
     def encode_device(self, pcm, channels, d_src_first, d_src_frames, d_cfg_idx, n_packets, d_packets, slot_bytes, d_sizes,
@@ -238,28 +271,10 @@ class AlacGpuContext:
         on this device, contiguous; its dtype picks the element type) with stream cfg d_cfg_idx[p]; its bytes land at
         d_packets[p * slot_bytes:] (a uint8 device tensor), its size in d_sizes[p], its status in d_status[p].  d_* are torch
         device tensors; asynchronous on `stream` (raw hipStream_t)."""
-        import torch
-
-        if pcm.dtype == torch.int32:
-            dtype = DST_INT32
-        elif pcm.dtype == torch.float32:
-            dtype = DST_FLOAT32
-        else:
-            raise ValueError(f"pcm must be torch.int32 or torch.float32, not {pcm.dtype}")
-        if not pcm.is_contiguous():
-            raise ValueError("pcm must be contiguous")
-        if pcm.device.type != "cuda":
-            raise ValueError("pcm must be a device tensor")
-        lay = {"interleaved": DST_INTERLEAVED, "planar": DST_PLANAR}.get(layout)
-        if lay is None:
-            raise ValueError(f"layout must be 'interleaved' or 'planar', not {layout!r}")
-
-        def dp(t):
-            return _VP(t.data_ptr()) if t is not None else None
-
-        rc = lib().alacgpu_encode_device(self._ctx, dp(pcm), pcm.numel(), channels, lay, dtype, plane_stride, dp(d_src_first),
-                                         dp(d_src_frames), dp(d_cfg_idx), n_packets, dp(d_packets), slot_bytes, dp(d_sizes),
-                                         dp(d_status), _VP(stream))
+        dtype, lay = _pcm_view("pcm", pcm, layout)
+        rc = lib().alacgpu_encode_device(self._ctx, _dp(pcm), pcm.numel(), channels, lay, dtype, plane_stride, _dp(d_src_first),
+                                         _dp(d_src_frames), _dp(d_cfg_idx), n_packets, _dp(d_packets), slot_bytes, _dp(d_sizes),
+                                         _dp(d_status), _VP(stream))
         _check(rc, self._ctx)
 
     def set_output_format(self, fmt):
@@ -275,7 +290,7 @@ class AlacGpuContext:
         Returns (ref_ints, out_bytes, status)."""
         pkt = np.frombuffer(bytes(packet), dtype=np.uint8)
         cfg = self.cfgs[cfg_index]
-        cap = 16384 * int(cfg["num_channels"]) * (3 if int(cfg["sample_size"]) == 24 else 1)
+        cap = MAX_FRAME * int(cfg["num_channels"]) * (3 if int(cfg["sample_size"]) == 24 else 1)
         out = np.zeros(cap, dtype=np.int32)
         ob = C.c_int32(0)
         st = C.c_int32(0)
@@ -294,7 +309,7 @@ def shard_ranges(sizes, world):
     return first
 
 
-class AlacGpuComm:
+class AlacGpuComm(_Closing):
     """alacgpu_comm: this rank's handle on the RCCL communicator for the all-gather of decoded PCM (one process per GPU).
     `unique_id()` on rank 0, hand the 128 bytes to the other ranks (torch.distributed broadcast, a file, MPI ...), then
     every rank constructs AlacGpuComm(ctx, id, rank, world) -- a collective call."""
@@ -302,9 +317,7 @@ class AlacGpuComm:
     @staticmethod
     def unique_id():
         buf = np.zeros(128, dtype=np.uint8)
-        rc = lib().alacgpu_comm_get_unique_id(_ptr(buf))
-        if rc != 0:
-            raise AlacGpuError(f"alacgpu rc={rc}: {lib().alacgpu_strerror(rc).decode()} ({lib().alacgpu_comm_last_error(None).decode()})")
+        _check_comm(lib().alacgpu_comm_get_unique_id(_ptr(buf)), None)
         return buf
 
     def __init__(self, ctx, unique_id, rank, world):
@@ -315,71 +328,40 @@ class AlacGpuComm:
         rc = lib().alacgpu_comm_create(ctx._ctx, _ptr(uid), rank, world, C.byref(self._comm))
         if rc != 0:
             self._comm = _VP()
-            raise AlacGpuError(f"alacgpu rc={rc}: {lib().alacgpu_strerror(rc).decode()} ({lib().alacgpu_comm_last_error(None).decode()})")
-
-    def _check(self, rc):
-        if rc != 0:
-            raise AlacGpuError(f"alacgpu rc={rc}: {lib().alacgpu_strerror(rc).decode()} ({lib().alacgpu_comm_last_error(self._comm).decode()})")
+        _check_comm(rc, None)
 
     def allgather_pcm(self, d_full, first, slot_ints, stream=0):
         """d_full: torch int32 CUDA tensor [n_packets, slot_ints] holding this rank's packets first[rank]..first[rank+1]
         decoded in place; asynchronous on `stream` (raw hipStream_t)."""
         first = np.ascontiguousarray(first, dtype=np.uint32)
-        self._check(lib().alacgpu_allgather_pcm(self._comm, _VP(d_full.data_ptr()), _ptr(first), slot_ints, _VP(stream)))
+        _check_comm(lib().alacgpu_allgather_pcm(self._comm, _dp(d_full), _ptr(first), slot_ints, _VP(stream)), self._comm)
 
     def decode_allgather_device(self, d_blob, blob_bytes, d_offsets, d_sizes, d_cfg_idx, first, d_full, slot_ints, d_out_bytes,
                                 d_out_samples, d_status, n_chunks=4, stream=0):
         """Decode this rank's range (device arrays indexed by GLOBAL packet number) in n_chunks pieces and gather piece k
         while piece k+1 decodes; asynchronous on `stream`."""
-        def dp(t):
-            return _VP(t.data_ptr()) if t is not None else None
         first = np.ascontiguousarray(first, dtype=np.uint32)
-        self._check(lib().alacgpu_decode_allgather_device(self.ctx._ctx, self._comm, dp(d_blob), blob_bytes, dp(d_offsets), dp(d_sizes),
-                                                          dp(d_cfg_idx), _ptr(first), dp(d_full), slot_ints, dp(d_out_bytes),
-                                                          dp(d_out_samples), dp(d_status), n_chunks, _VP(stream)))
+        _check_comm(lib().alacgpu_decode_allgather_device(self.ctx._ctx, self._comm, _dp(d_blob), blob_bytes, _dp(d_offsets),
+                                                          _dp(d_sizes), _dp(d_cfg_idx), _ptr(first), _dp(d_full), slot_ints,
+                                                          _dp(d_out_bytes), _dp(d_out_samples), _dp(d_status), n_chunks,
+                                                          _VP(stream)), self._comm)
 
     def close(self):
         if self._comm:
             lib().alacgpu_comm_destroy(self._comm)
             self._comm = _VP()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def decode_batch_sharded(contexts, blob, offsets, sizes, cfg_idx=None, slot_ints=None, out=None):
     """alacgpu_decode_batch_sharded: one host batch over several AlacGpuContext objects (one per GPU) from this process.
     Returns (pcm[n, slot_ints] int32, out_bytes[n], out_samples[n], status[n]) like AlacGpuContext.decode_batch."""
-    blob = np.ascontiguousarray(blob, dtype=np.uint8)
-    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-    sizes = np.ascontiguousarray(sizes, dtype=np.uint32)
-    ci = None if cfg_idx is None else np.ascontiguousarray(cfg_idx, dtype=np.uint16)
-    n = len(sizes)
-    if slot_ints is None:
-        slot_ints = int(max(int(c["max_samples_per_frame"]) * int(c["num_channels"]) for c in contexts[0].cfgs))
-    pcm = out if out is not None else np.zeros((n, slot_ints), dtype=np.int32)
-    if pcm.dtype != np.int32 or pcm.shape != (n, slot_ints) or not pcm.flags.c_contiguous:
-        raise ValueError("out must be a C-contiguous int32 array of shape (n_packets, slot_ints)")
-    ob = np.zeros(n, dtype=np.int32)
-    os_ = np.zeros(n, dtype=np.int32)
-    st = np.zeros(n, dtype=np.int32)
+    args, outs = _host_batch(contexts[0].cfgs, blob, offsets, sizes, cfg_idx, slot_ints, out)
     handles = (_VP * len(contexts))(*[c._ctx for c in contexts])
-    rc = lib().alacgpu_decode_batch_sharded(handles, len(contexts), _ptr(blob), blob.size, _ptr(offsets), _ptr(sizes), _ptr(ci), n,
-                                            _ptr(pcm), slot_ints, _ptr(ob), _ptr(os_), _ptr(st))
-    _check(rc, contexts[0]._ctx)
-    return pcm, ob, os_, st
+    _check(lib().alacgpu_decode_batch_sharded(handles, len(contexts), *args), contexts[0]._ctx)
+    return outs
 
 
-class PinnedBuffer:
+class PinnedBuffer(_Closing):
     """Page-locked host memory from alacgpu_alloc_pinned, viewed as a numpy array (batch buffers that are reused across
     calls: transfers from and to it run at link speed).  Free with close() / as a context manager."""
 
@@ -398,18 +380,6 @@ class PinnedBuffer:
             self.array = None
             lib().alacgpu_free_pinned(self._p)
             self._p = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def device_count():
@@ -517,7 +487,7 @@ def load(source, device=0, dtype=None, layout="planar"):
     bad = np.nonzero(_normalise_status(st, first) != ST_OK)[0]
     if len(bad):
         p = int(bad[0])
-        raise AlacGpuError(f"packet {p} does not decode: status {int(st[p])} ({lib().alacgpu_status_string(int(st[p])).decode()})")
+        raise AlacGpuError(f"packet {p} does not decode: {_status_text(st[p])}")
     return out, int(t["sample_rate"])
 
 
@@ -559,8 +529,7 @@ def load_batch(sources, device=0, dtype=None, max_frames=None):
     if len(bad):
         p = int(bad[0])
         f, q = int(np.concatenate(ci)[p]), int(np.concatenate(pk)[p])
-        raise AlacGpuError(f"source {f}, packet {q} does not decode: status {int(st[p])} "
-                           f"({lib().alacgpu_status_string(int(st[p])).decode()})")
+        raise AlacGpuError(f"source {f}, packet {q} does not decode: {_status_text(st[p])}")
     return out, torch.from_numpy(lengths), rate
 
 
@@ -585,8 +554,8 @@ def _check_save_args(pcm, batch, sample_size, frame_length, sample_rate):
         raise ValueError(f"pcm must be torch.int32 or torch.float32, not {pcm.dtype}")
     if sample_size not in (16, 24):
         raise ValueError(f"sample_size must be 16 or 24, not {sample_size}")
-    if not isinstance(frame_length, (int, np.integer)) or not 1 <= int(frame_length) <= 16384:
-        raise ValueError(f"frame_length must be 1 .. 16384, not {frame_length}")
+    if not isinstance(frame_length, (int, np.integer)) or not 1 <= int(frame_length) <= MAX_FRAME:
+        raise ValueError(f"frame_length must be 1 .. {MAX_FRAME}, not {frame_length}")
     if not isinstance(sample_rate, (int, np.integer)) or not 1 <= int(sample_rate) < 1 << 32:
         raise ValueError(f"sample_rate must be a positive 32-bit integer, not {sample_rate}")
     if F == 0 or T == 0:
@@ -631,7 +600,7 @@ def _encode_tensor(pcm, lengths, sample_size, frame_length, device):
     bad = np.nonzero(st != ST_OK)[0]
     if len(bad):
         p = int(bad[0])
-        raise AlacGpuError(f"packet {p} was not encoded: status {int(st[p])} ({lib().alacgpu_status_string(int(st[p])).decode()})")
+        raise AlacGpuError(f"packet {p} was not encoded: {_status_text(st[p])}")
     # compact on the device: a gather of every packet's bytes, then one copy of exactly those bytes
     sizes64 = d_sizes.to(torch.int64)
     ends = torch.cumsum(sizes64, 0)
@@ -715,19 +684,6 @@ class AlacFile:
             self._ctx.close()
         self._ctx = AlacGpuContext(self._cfg, self._device)
 
-    def _raise_for(self, st, predtype_hint=None):
-        # the reference signals these by exceptions (AlacFile.cs:574,:650,:660,:715)
-        if st == ST_UNSUPPORTED_SAMPLE_SIZE:
-            raise Exception("FIXME: unimplemented sample size " + str(int(self._cfg[0]["sample_size"])))
-        if st == ST_UNSUPPORTED_PREDTYPE:
-            raise Exception("FIXME: unhandled predicition type")
-        if st in (ST_BAD_SAMPLE_COUNT, ST_OVERRUN):
-            raise IndexError("Index was outside the bounds of the array.")
-        if st == ST_REF_THROWS:
-            raise ValueError("Destination array was not long enough.")
-        if st == ST_UNSUPPORTED_PARAMS:
-            raise Exception("unsupported parameter combination")
-
     def DecodeFrame(self, inbuffer, outbuffer):
         """int DecodeFrame(byte[] inbuffer, int[] outbuffer): fills outbuffer in the reference's layout,
         returns the byte count (AlacFile.cs:718)."""
@@ -747,7 +703,7 @@ class AlacFile:
             n = min(len(outbuffer), len(ref))
             outbuffer[:n] = ref[:n]
             return out_bytes
-        self._raise_for(st)
+        _raise_reference_exception(st, int(self._cfg[0]["sample_size"]))
         n = min(len(outbuffer), len(ref))
         outbuffer[:n] = ref[:n]
         return out_bytes

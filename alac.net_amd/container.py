@@ -21,7 +21,7 @@ import struct
 
 import numpy as np
 
-from . import AlacGpuContext, cfg_from_codec_data, expand_reference_layout, format_samples
+from . import MAX_FRAME, AlacGpuContext, _raise_reference_exception, cfg_from_codec_data, expand_reference_layout, format_samples
 
 MDAT_NONE, MDAT_OK, MDAT_NO_VALID_SAVED_POS, MDAT_CANNOT_SEEK = 0, 1, 2, 3
 
@@ -414,12 +414,12 @@ class AlacContext:
         blob = np.frombuffer(self._stream.Read(int(sum(sizes))), dtype=np.uint8)   # packets are read in file order (:195)
         sizes = np.array(sizes, dtype=np.uint32)
         offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.uint64)
-        slot = 16384 * int(self._cfg[0]["num_channels"])
+        slot = MAX_FRAME * int(self._cfg[0]["num_channels"])
         slot = min(slot, max(int(self._cfg[0]["max_samples_per_frame"]), 1) * int(self._cfg[0]["num_channels"]) + 8)
         pcm, ob, os_, st = self._gpu.decode_batch(blob, offsets, sizes, None, slot)
         # short frames carry their own sample count; give them room if the stream config under-declares it
         if (st == 4).any():
-            slot = 16384 * int(self._cfg[0]["num_channels"])
+            slot = MAX_FRAME * int(self._cfg[0]["num_channels"])
             pcm, ob, os_, st = self._gpu.decode_batch(blob, offsets, sizes, None, slot)
         self._currentSampleBlock += len(sizes)
         # a one-channel element with a prediction type other than 0: the reference skips the predictor without throwing and
@@ -432,18 +432,6 @@ class AlacContext:
             st = np.where((st == 2) & ((first >> 5) == 1) & (sizes > 0), 1, st).astype(np.int32)
         return pcm, ob, os_, st, np.array(durs)
 
-    def _raise_for(self, st):
-        if st == 2:
-            raise Exception("FIXME: unimplemented sample size " + str(self._demuxRes.SampleSize))
-        if st == 3:
-            raise Exception("FIXME: unhandled predicition type")
-        if st in (4, 5):
-            raise IndexError("Index was outside the bounds of the array.")
-        if st == 6:
-            raise ValueError("Destination array was not long enough.")
-        if st == 7:
-            raise Exception("unsupported parameter combination")
-
     def Read(self, buffer):
         """int Read(byte[] buffer): one packet per call, little-endian PCM bytes; 0 at end of stream (:163-172)."""
         if not self._ready:
@@ -455,7 +443,7 @@ class AlacContext:
                 self._ready.append((pcm[p], int(ob[p]), int(os_[p]), int(st[p]), int(durs[p])))
         pcm, out_bytes, n, st, dur = self._ready.pop(0)
         if st not in (0, 1):
-            self._raise_for(st)                                   # DecodeFrame throws before :198-199 count the packet
+            _raise_reference_exception(st, self._demuxRes.SampleSize)   # DecodeFrame throws before :198-199 count the packet
         self.LastSampleNumber += dur                              # :199
         ref = expand_reference_layout(self._cfg, pcm, max(n, 0)) if st == 0 else np.zeros(0, dtype=np.int32)
         bps = self.GetBytesPerSample()

@@ -16,6 +16,7 @@
 #include "alac_encode.h"
 #include "alac_kernels.h"
 #include "alacgpu.h"
+#include "alacgpu_ranges.h"
 
 static_assert(sizeof(alacgpu_cfg) == sizeof(alacgpu_cfg_dev), "cfg layouts must match");
 
@@ -26,15 +27,20 @@ constexpr uint32_t AB_SMALL_MAX_PACKETS = 4096;  // up to here: the build with 1
 constexpr uint32_t AB5_MIN_PACKETS = 10241;     // above: the 96-register build of the 8-packet arrangement (five workgroups per CU)
 constexpr uint32_t DENSE_MIN_PACKETS = 12289;   // measured cross-over of the two arrangements of the main kernel
 constexpr int N_HOST_STREAMS = 4;   // chunks of the host-buffer pipeline (H2D k+1 || decode k || D2H k-1)
+constexpr uint32_t MAX_FRAME = 16384;   // the longest frame the reference decodes (its scratch, AlacFile.cs:28)
+
+// ALACGPU_DENSE (A/B and tests): which build of the first launch runs.  Auto picks by batch size; "eight" picks among the
+// builds of the 8-packet arrangement by batch size; the others force one build whatever the batch size.
+enum dense_mode { DENSE_AUTO = -1, DENSE_EIGHT = 0, DENSE_ALWAYS = 1, DENSE_FORCE_AB5 = 2, DENSE_FORCE_SMALL = 3, DENSE_FORCE_AB = 4 };
 
 // What one launch pair (alac_decode_ab_kernel + alac_decode_ab32_kernel) owns while it is in flight: the group flags the
 // first kernel hands to the second, and the events that bracket the pair.  A slot is reused only after its last launch
 // has finished (hipEventSynchronize), so calls on different streams never share flags.
 struct launch_slot {
     uint32_t* d_flags = nullptr;
-    size_t flags_n = 0;
+    size_t flags_bytes = 0;
     int32_t* d_park = nullptr;     // destination mode: where channel A waits (n_packets * park_stride ints, grown on demand)
-    size_t park_n = 0;
+    size_t park_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool used = false;
 };
@@ -54,9 +60,7 @@ struct alacgpu_ctx {
     int last_slot = -1;
     uint32_t out_format = 0;           // 0 int32 per sample, 1 packed little-endian PCM
     int host_chunks = 0;               // 0 auto; 1..N_HOST_STREAMS forced (ALACGPU_HOST_CHUNKS, A/B only)
-    int dense = -1;                    // main kernel's 16-packet workgroups: -1 auto (by batch size), 0 never, 1 always (ALACGPU_DENSE; A/B and tests)
-                                       // 2 / 3 / 4 (ALACGPU_DENSE=..): never, and the 96-register build / the 16-step-unit build / the plain
-                                       // 128-register build of the 8-packet arrangement whatever the batch size (tests)
+    int dense = DENSE_AUTO;            // the first launch's build (dense_mode, ALACGPU_DENSE)
     uint32_t* d_cu_arrivals = nullptr; // per-CU workgroup counters (alac_decode_params::cu_arrivals): ONE array per device, shared by
                                        // every context of the process on it (cu_counters_acquire), so that launches of different
                                        // contexts take their turns on a CU from the same counter
@@ -67,9 +71,9 @@ struct alacgpu_ctx {
     int32_t* h_frame = nullptr;        // pinned staging of alacgpu_decode_frame (one slot of the widest kind)
     // alacgpu_encode_device: one workspace slot per workgroup of a round (codes and bit positions, grown on demand), and the
     // event behind the last call's launches (the next call's stream waits for it before it reuses the workspace)
-    uint64_t* d_enc_code = nullptr;
-    uint32_t* d_enc_pos = nullptr;
-    size_t enc_items = 0;              // items the workspace holds (slots * alac_enc_items(smax))
+    uint64_t* d_enc_code = nullptr;    // slots * alac_enc_items(smax) codes
+    uint32_t* d_enc_pos = nullptr;     // ... and as many bit positions, plus one per slot
+    size_t enc_code_bytes = 0, enc_pos_bytes = 0;
     hipEvent_t enc_done = nullptr;
     bool enc_used = false;
     std::string last_error;
@@ -114,27 +118,55 @@ void cu_counters_release(int device) {
     }
 }
 
+// A grow-only device buffer: when need_bytes exceed the have_bytes that p holds, p is freed and alloc_bytes allocated (the
+// caller has waited for every user of the old buffer and chooses the slack).
+template <class T>
+int grow(alacgpu_ctx* ctx, T*& p, size_t& have_bytes, size_t need_bytes, size_t alloc_bytes) {
+    if (need_bytes <= have_bytes) return ALACGPU_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    have_bytes = 0;
+    HIP_TRY(ctx, hipMalloc((void**)&p, alloc_bytes));
+    have_bytes = alloc_bytes;
+    return ALACGPU_OK;
+}
+
 int ensure_ws(alacgpu_ctx* ctx, size_t bytes) {
     if (bytes <= ctx->ws_bytes) return ALACGPU_OK;
     for (int i = 0; i < N_HOST_STREAMS; i++)
         if (ctx->streams[i]) HIP_TRY(ctx, hipStreamSynchronize(ctx->streams[i]));
     if (ctx->up_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->up_stream));
-    if (ctx->d_ws) (void)hipFree(ctx->d_ws);
-    ctx->d_ws = nullptr;
-    ctx->ws_bytes = 0;
-    size_t want = align_up(bytes + bytes / 4, 1 << 20);
-    HIP_TRY(ctx, hipMalloc(&ctx->d_ws, want));
-    ctx->ws_bytes = want;
-    return ALACGPU_OK;
+    return grow(ctx, ctx->d_ws, ctx->ws_bytes, bytes, align_up(bytes + bytes / 4, 1 << 20));
+}
+
+// The first launch's kernel.  Big batches (more workgroups than the chip holds at once: the launch is bound by instruction
+// issue, not by the length of one packet's serial chain) take the dense arrangement: 16 packets per workgroup share one
+// entropy wave.
+const void* first_kernel(const alacgpu_ctx* ctx, uint32_t n_packets) {
+    switch (ctx->dense) {
+    case DENSE_ALWAYS: return (const void*)alac_decode_ab_dense_kernel;
+    case DENSE_FORCE_AB5: return (const void*)alac_decode_ab5_kernel;
+    case DENSE_FORCE_SMALL: return (const void*)alac_decode_ab_small_kernel;
+    case DENSE_FORCE_AB: return (const void*)alac_decode_ab_kernel;
+    case DENSE_AUTO:
+        if (n_packets >= DENSE_MIN_PACKETS) return (const void*)alac_decode_ab_dense_kernel;
+        [[fallthrough]];
+    default:   // DENSE_EIGHT
+        if (n_packets >= AB5_MIN_PACKETS) return (const void*)alac_decode_ab5_kernel;
+        if (n_packets <= AB_SMALL_MAX_PACKETS) return (const void*)alac_decode_ab_small_kernel;
+        return (const void*)alac_decode_ab_kernel;
+    }
 }
 
 // The two-pass kernels: the first launch decodes the groups of 8 packets whose streams have LPC order 1..8 (the dense
 // arrangement: 1..16) and flags the others for the second launch right behind it on the same stream (two or four taps per
 // lane of the FIR wave).  A two-channel element needs room for parking channel A in its slot (2 n <= slot_ints): parse_meta
 // turns anything else into a per-packet status, also a two-channel element in a one-channel stream cfg, which is decoded
-// (its left channel comes out, AlacFile.cs:353-354) when the slot has that room.
+// (its left channel comes out, AlacFile.cs:353-354) when the slot has that room.  Every decode entry point ends here, with
+// its arguments checked.
 int launch(alacgpu_ctx* ctx, const alac_decode_params& p_in, hipStream_t stream) {
     if (p_in.n_packets == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
     alac_decode_params p = p_in;
     p.cu_arrivals = ctx->d_cu_arrivals;
     const int si = (int)(ctx->next_slot++ % N_SLOTS);
@@ -145,41 +177,20 @@ int launch(alacgpu_ctx* ctx, const alac_decode_params& p_in, hipStream_t stream)
     }
     if (sl.used) HIP_TRY(ctx, hipEventSynchronize(sl.ev1));   // the pair that last used these flags has finished
     const size_t groups = ((size_t)p.n_packets + 7) / 8;
-    if (groups > sl.flags_n) {
-        if (sl.d_flags) (void)hipFree(sl.d_flags);
-        sl.d_flags = nullptr;
-        sl.flags_n = 0;
-        const size_t want = groups + groups / 4 + 64;
-        HIP_TRY(ctx, hipMalloc((void**)&sl.d_flags, want * sizeof(uint32_t)));
-        sl.flags_n = want;
-    }
+    int rc = grow(ctx, sl.d_flags, sl.flags_bytes, sizeof(uint32_t) * groups, sizeof(uint32_t) * (groups + groups / 4 + 64));
+    if (rc) return rc;
     p.ab_flags = sl.d_flags;
     if (p.dst_first) {   // destination mode: channel A is parked in this slot's own place (the destination has no room for it)
         const size_t want = (size_t)p.n_packets * p.park_stride;
-        if (want > sl.park_n) {
-            if (sl.d_park) (void)hipFree(sl.d_park);
-            sl.d_park = nullptr;
-            sl.park_n = 0;
-            HIP_TRY(ctx, hipMalloc((void**)&sl.d_park, sizeof(int32_t) * (want + want / 4)));
-            sl.park_n = want + want / 4;
-        }
+        if ((rc = grow(ctx, sl.d_park, sl.park_bytes, sizeof(int32_t) * want, sizeof(int32_t) * (want + want / 4)))) return rc;
         p.park = sl.d_park;
     }
     HIP_TRY(ctx, hipEventRecord(sl.ev0, stream));
     alac_decode_params args = p;
     void* kargs[] = {&args};
-    // Big batches (more workgroups than the chip holds at once: the launch is bound by instruction issue, not by the
-    // length of one packet's serial chain) take the dense arrangement: 16 packets per workgroup share one entropy wave.
-    const bool dense = ctx->dense < 0 ? p.n_packets >= DENSE_MIN_PACKETS : ctx->dense == 1;
-    if (dense)
-        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_decode_ab_dense_kernel, dim3((uint32_t)((groups + 1) / 2)), dim3(256), kargs, 0, stream));
-    else
-    {
-        const void* k = (const void*)alac_decode_ab_kernel;
-        if (ctx->dense == 2 || (ctx->dense <= 0 && p.n_packets >= AB5_MIN_PACKETS)) k = (const void*)alac_decode_ab5_kernel;
-        else if (ctx->dense == 3 || (ctx->dense <= 0 && p.n_packets <= AB_SMALL_MAX_PACKETS)) k = (const void*)alac_decode_ab_small_kernel;
-        HIP_TRY(ctx, hipLaunchKernel(k, dim3((uint32_t)groups), dim3(256), kargs, 0, stream));
-    }
+    const void* k = first_kernel(ctx, p.n_packets);   // (the dense arrangement: two groups of 8 per workgroup)
+    const size_t first_groups = k == (const void*)alac_decode_ab_dense_kernel ? (groups + 1) / 2 : groups;
+    HIP_TRY(ctx, hipLaunchKernel(k, dim3((uint32_t)first_groups), dim3(256), kargs, 0, stream));
     HIP_TRY(ctx, hipLaunchKernel((const void*)alac_decode_ab32_kernel, dim3((uint32_t)groups), dim3(256), kargs, 0, stream));
     if (p.dst_first)
         HIP_TRY(ctx, hipLaunchKernel((const void*)alac_dst_fill_kernel, dim3((p.n_packets + 3u) / 4u), dim3(256), kargs, 0, stream));
@@ -190,14 +201,16 @@ int launch(alacgpu_ctx* ctx, const alac_decode_params& p_in, hipStream_t stream)
     return ALACGPU_OK;
 }
 
+// The arguments every decode shares, checked; the destination mode, a parking place and the stamps stay unset.
 int fill_params(alacgpu_ctx* ctx, alac_decode_params& p, const void* d_blob, uint64_t blob_bytes, const void* d_offsets,
                 const void* d_sizes, const void* d_cfg_idx, uint32_t n_packets, void* d_pcm_out, uint32_t slot_ints,
-                void* d_out_bytes, void* d_out_samples, void* d_status) {
+                void* d_out_bytes, void* d_out_samples, void* d_status, uint32_t out_format) {
     if (!d_blob || !d_offsets || !d_sizes || !d_pcm_out || !d_status || slot_ints == 0) return ALACGPU_ERR_BAD_ARG;
     if (((uintptr_t)d_blob & 15u) != 0 || ((uintptr_t)d_offsets & 7u) != 0 || ((uintptr_t)d_sizes & 3u) != 0 ||
         ((uintptr_t)d_pcm_out & 3u) != 0 || ((uintptr_t)d_status & 3u) != 0 || ((uintptr_t)d_cfg_idx & 1u) != 0 ||
         ((uintptr_t)d_out_bytes & 3u) != 0 || ((uintptr_t)d_out_samples & 3u) != 0)
         return ALACGPU_ERR_BAD_ARG;
+    p = alac_decode_params{};
     p.blob = (const uint8_t*)d_blob;
     p.blob_limit = align_up(blob_bytes, 16);
     p.offsets = (const uint64_t*)d_offsets;
@@ -211,20 +224,23 @@ int fill_params(alacgpu_ctx* ctx, alac_decode_params& p, const void* d_blob, uin
     p.out_bytes = (int32_t*)d_out_bytes;
     p.out_samples = (int32_t*)d_out_samples;
     p.status = (int32_t*)d_status;
-    p.out_format = ctx->out_format;
-#ifdef ALAC_DIAG
-    p.dbg = nullptr;
-#endif
-    p.ab_flags = nullptr;
-    p.cu_arrivals = nullptr;
-    p.park = nullptr;
-    p.park_stride = 0;
-    p.dst_first = nullptr;
-    p.dst_frames = nullptr;
-    p.out_elems = 0;
-    p.plane_stride = 0;
-    p.channels = p.layout = p.dtype = 0;
+    p.out_format = out_format;
     return ALACGPU_OK;
+}
+
+// Smax: the longest frame any stream cfg declares, at most MAX_FRAME
+uint32_t smax(const alacgpu_ctx* ctx) {
+    uint32_t s = 1;
+    for (uint32_t i = 0; i < ctx->n_cfgs; i++) s = std::max(s, std::min(ctx->h_cfgs[i].max_samples_per_frame, MAX_FRAME));
+    return s;
+}
+
+// A PCM tensor view (decode-into and encode): one or two channels, interleaved or planar with a plane stride, int32 or
+// float32, and 4-byte aligned.
+bool pcm_view_ok(const void* d_pcm, uint32_t channels, int layout, int dtype, uint64_t plane_stride) {
+    return (channels == 1 || channels == 2) && (layout == ALACGPU_DST_INTERLEAVED || layout == ALACGPU_DST_PLANAR) &&
+           (dtype == ALACGPU_DST_INT32 || dtype == ALACGPU_DST_FLOAT32) && (layout != ALACGPU_DST_PLANAR || plane_stride != 0) &&
+           ((uintptr_t)d_pcm & 3u) == 0;
 }
 
 // bytes per sample the packed format can put into a slot (2 or 3; the widest stream cfg decides)
@@ -391,31 +407,41 @@ int alacgpu_decode_batch_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t b
     if (n_packets == 0) return ALACGPU_OK;
     alac_decode_params p;
     int rc = fill_params(ctx, p, d_blob, blob_bytes, d_offsets, d_sizes, d_cfg_idx, n_packets, d_pcm_out, slot_ints,
-                         d_out_bytes, d_out_samples, d_status);
+                         d_out_bytes, d_out_samples, d_status, ctx->out_format);
     if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     return launch(ctx, p, (hipStream_t)hip_stream);
 }
+
+#ifdef ALAC_DIAG
+// Diagnostic twin of alacgpu_decode_batch_device (not part of include/alacgpu.h; tools/ only): the kernels additionally
+// write 8 clock / placement stamps per workgroup into d_stamps (8 * ceil(n_packets / 8) uint64, zeroed by the caller).
+int alacgpu_dbg_decode_batch_device_stamps(alacgpu_ctx* ctx, const void* d_blob, uint64_t blob_bytes, const void* d_offsets,
+                                           const void* d_sizes, const void* d_cfg_idx, uint32_t n_packets, void* d_pcm_out,
+                                           uint32_t slot_ints, void* d_out_bytes, void* d_out_samples, void* d_status,
+                                           void* hip_stream, void* d_stamps) {
+    if (!ctx || !d_stamps) return ALACGPU_ERR_BAD_ARG;
+    if (n_packets == 0) return ALACGPU_OK;
+    alac_decode_params p;
+    int rc = fill_params(ctx, p, d_blob, blob_bytes, d_offsets, d_sizes, d_cfg_idx, n_packets, d_pcm_out, slot_ints,
+                         d_out_bytes, d_out_samples, d_status, ctx->out_format);
+    if (rc) return rc;
+    p.dbg = (unsigned long long*)d_stamps;
+    return launch(ctx, p, (hipStream_t)hip_stream);
+}
+#endif
 
 int alacgpu_decode_into_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t blob_bytes, const void* d_offsets,
                                const void* d_sizes, const void* d_cfg_idx, uint32_t n_packets, const void* d_dst_first,
                                const void* d_dst_frames, void* d_out, uint64_t out_elems, uint32_t channels, int layout, int dtype,
                                uint64_t plane_stride, void* d_out_samples, void* d_status, void* hip_stream) {
-    if (!ctx || !d_dst_first || !d_dst_frames || (channels != 1 && channels != 2)) return ALACGPU_ERR_BAD_ARG;
-    if ((layout != ALACGPU_DST_INTERLEAVED && layout != ALACGPU_DST_PLANAR) || (dtype != ALACGPU_DST_INT32 && dtype != ALACGPU_DST_FLOAT32))
-        return ALACGPU_ERR_BAD_ARG;
-    if (layout == ALACGPU_DST_PLANAR && plane_stride == 0) return ALACGPU_ERR_BAD_ARG;
+    if (!ctx || !d_dst_first || !d_dst_frames || !pcm_view_ok(d_out, channels, layout, dtype, plane_stride)) return ALACGPU_ERR_BAD_ARG;
     if (((uintptr_t)d_dst_first & 7u) != 0 || ((uintptr_t)d_dst_frames & 3u) != 0) return ALACGPU_ERR_BAD_ARG;
-    // Smax: the longest frame any stream cfg declares (the reference's scratch holds 16384); statuses as in the slot layout
-    // with slot_ints = channels * Smax, and channel A parks in Smax ints per packet
-    uint32_t smax = 1;
-    for (uint32_t i = 0; i < ctx->n_cfgs; i++) smax = std::max(smax, std::min(ctx->h_cfgs[i].max_samples_per_frame, 16384u));
+    // statuses as in the slot layout with slot_ints = channels * Smax, and channel A parks in Smax ints per packet
+    const uint32_t s = smax(ctx);
     alac_decode_params p;
-    int rc = fill_params(ctx, p, d_blob, blob_bytes, d_offsets, d_sizes, d_cfg_idx, n_packets, d_out, channels * smax, nullptr,
-                         d_out_samples, d_status);
+    int rc = fill_params(ctx, p, d_blob, blob_bytes, d_offsets, d_sizes, d_cfg_idx, n_packets, d_out, channels * s, nullptr,
+                         d_out_samples, d_status, ALACGPU_OUT_INT32);
     if (rc) return rc;
-    if (n_packets == 0) return ALACGPU_OK;
-    p.out_format = ALACGPU_OUT_INT32;
     p.dst_first = (const uint64_t*)d_dst_first;
     p.dst_frames = (const uint32_t*)d_dst_frames;
     p.out_elems = out_elems;
@@ -423,8 +449,7 @@ int alacgpu_decode_into_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t bl
     p.channels = channels;
     p.layout = (uint32_t)layout;
     p.dtype = (uint32_t)dtype;
-    p.park_stride = smax;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    p.park_stride = s;
     return launch(ctx, p, (hipStream_t)hip_stream);
 }
 
@@ -440,20 +465,16 @@ int alacgpu_encode_device(alacgpu_ctx* ctx, const void* d_pcm, uint64_t src_elem
                           void* hip_stream) {
     if (!ctx || !d_pcm || !d_src_first || !d_src_frames || !d_cfg_idx || !d_packets || !d_sizes || !d_status)
         return ALACGPU_ERR_BAD_ARG;
-    if ((channels != 1 && channels != 2) || (layout != ALACGPU_DST_INTERLEAVED && layout != ALACGPU_DST_PLANAR) ||
-        (dtype != ALACGPU_DST_INT32 && dtype != ALACGPU_DST_FLOAT32) || (layout == ALACGPU_DST_PLANAR && plane_stride == 0))
-        return ALACGPU_ERR_BAD_ARG;
-    if (((uintptr_t)d_pcm & 3u) != 0 || ((uintptr_t)d_src_first & 7u) != 0 || ((uintptr_t)d_src_frames & 3u) != 0 ||
+    if (!pcm_view_ok(d_pcm, channels, layout, dtype, plane_stride)) return ALACGPU_ERR_BAD_ARG;
+    if (((uintptr_t)d_src_first & 7u) != 0 || ((uintptr_t)d_src_frames & 3u) != 0 ||
         ((uintptr_t)d_cfg_idx & 1u) != 0 || ((uintptr_t)d_packets & 15u) != 0 || (slot_bytes & 15u) != 0 ||
         ((uintptr_t)d_sizes & 3u) != 0 || ((uintptr_t)d_status & 3u) != 0)
         return ALACGPU_ERR_BAD_ARG;
-    uint32_t smax = 1;
     for (uint32_t i = 0; i < ctx->n_cfgs; i++) {
         const alacgpu_cfg& c = ctx->h_cfgs[i];
         if (c.num_channels != channels) return ALACGPU_ERR_BAD_ARG;
-        const uint32_t frames = std::min(c.max_samples_per_frame, 16384u);
+        const uint32_t frames = std::min(c.max_samples_per_frame, MAX_FRAME);
         if (slot_bytes < alacgpu_encode_max_packet_bytes(frames, c.sample_size, (int)channels)) return ALACGPU_ERR_BAD_ARG;
-        smax = std::max(smax, frames);
     }
     if (n_packets == 0) return ALACGPU_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -462,18 +483,15 @@ int alacgpu_encode_device(alacgpu_ctx* ctx, const void* d_pcm, uint64_t src_elem
     int n_cu = 0;
     HIP_TRY(ctx, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
     const uint32_t round = std::min<uint32_t>(n_packets, (uint32_t)std::max(n_cu, 1) * 16u);
-    const size_t items = (size_t)round * alac_enc_items(smax);
+    const uint32_t frames = smax(ctx);
+    const size_t items = (size_t)round * alac_enc_items(frames);
+    const size_t code_bytes = sizeof(uint64_t) * items, pos_bytes = sizeof(uint32_t) * (items + round);
     if (!ctx->enc_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->enc_done, hipEventDisableTiming));
-    if (items > ctx->enc_items) {
+    if (code_bytes > ctx->enc_code_bytes || pos_bytes > ctx->enc_pos_bytes) {
         if (ctx->enc_used) HIP_TRY(ctx, hipEventSynchronize(ctx->enc_done));   // the last call has finished with it
-        if (ctx->d_enc_code) (void)hipFree(ctx->d_enc_code);
-        if (ctx->d_enc_pos) (void)hipFree(ctx->d_enc_pos);
-        ctx->d_enc_code = nullptr;
-        ctx->d_enc_pos = nullptr;
-        ctx->enc_items = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_enc_code, sizeof(uint64_t) * items));
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_enc_pos, sizeof(uint32_t) * (items + round)));
-        ctx->enc_items = items;
+        int rc = grow(ctx, ctx->d_enc_code, ctx->enc_code_bytes, code_bytes, code_bytes);
+        if (rc) return rc;
+        if ((rc = grow(ctx, ctx->d_enc_pos, ctx->enc_pos_bytes, pos_bytes, pos_bytes))) return rc;
     } else if (ctx->enc_used) {
         HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->enc_done, 0));   // (a call on another stream may still use it)
     }
@@ -490,7 +508,7 @@ int alacgpu_encode_device(alacgpu_ctx* ctx, const void* d_pcm, uint64_t src_elem
     p.cfg_idx = (const uint16_t*)d_cfg_idx;
     p.cfgs = ctx->d_cfgs;
     p.n_cfgs = ctx->n_cfgs;
-    p.smax = smax;
+    p.smax = frames;
     p.packets = (uint8_t*)d_packets;
     p.slot_bytes = slot_bytes;
     p.sizes = (uint32_t*)d_sizes;
@@ -515,20 +533,6 @@ int alacgpu_encode_device(alacgpu_ctx* ctx, const void* d_pcm, uint64_t src_elem
 }  // extern "C"
 
 namespace {
-// the same with channel A parked at d_park + packet * park_stride instead of inside the output slot (see alac_decode_params)
-int decode_device_parked(alacgpu_ctx* ctx, const void* d_blob, uint64_t blob_bytes, const void* d_offsets, const void* d_sizes,
-                         const void* d_cfg_idx, uint32_t n_packets, void* pcm_out, uint32_t slot_ints, void* d_out_bytes,
-                         void* d_out_samples, void* d_status, int32_t* d_park, uint32_t park_stride, hipStream_t stream) {
-    if (n_packets == 0) return ALACGPU_OK;
-    alac_decode_params p;
-    int rc = fill_params(ctx, p, d_blob, blob_bytes, d_offsets, d_sizes, d_cfg_idx, n_packets, pcm_out, slot_ints, d_out_bytes,
-                         d_out_samples, d_status);
-    if (rc) return rc;
-    p.park = d_park;
-    p.park_stride = park_stride;
-    return launch(ctx, p, stream);
-}
-
 // pcm_out .. + bytes is page-locked host memory the device can store into: its device-side address, else null
 void* device_view_of_pinned(const void* host, size_t bytes) {
     if (bytes == 0) return nullptr;
@@ -539,52 +543,25 @@ void* device_view_of_pinned(const void* host, size_t bytes) {
     if ((const char*)a1.devicePointer - (const char*)a0.devicePointer != (ptrdiff_t)(bytes - 1)) return nullptr;   // one mapping
     return a0.devicePointer;
 }
-}  // namespace
-
-extern "C" {
-
-#ifdef ALAC_DIAG
-// Diagnostic twin of alacgpu_decode_batch_device (not part of include/alacgpu.h; tools/ only): the kernels additionally
-// write 8 clock / placement stamps per workgroup into d_stamps (8 * ceil(n_packets / 8) uint64, zeroed by the caller).
-int alacgpu_dbg_decode_batch_device_stamps(alacgpu_ctx* ctx, const void* d_blob, uint64_t blob_bytes, const void* d_offsets,
-                                           const void* d_sizes, const void* d_cfg_idx, uint32_t n_packets, void* d_pcm_out,
-                                           uint32_t slot_ints, void* d_out_bytes, void* d_out_samples, void* d_status,
-                                           void* hip_stream, void* d_stamps) {
-    if (!ctx || !d_stamps) return ALACGPU_ERR_BAD_ARG;
-    if (n_packets == 0) return ALACGPU_OK;
-    alac_decode_params p;
-    int rc = fill_params(ctx, p, d_blob, blob_bytes, d_offsets, d_sizes, d_cfg_idx, n_packets, d_pcm_out, slot_ints,
-                         d_out_bytes, d_out_samples, d_status);
-    if (rc) return rc;
-    p.dbg = (unsigned long long*)d_stamps;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return launch(ctx, p, (hipStream_t)hip_stream);
-}
-#endif
 
 // Host buffers: the batch is cut into contiguous packet ranges (two by default, up to four), each on its own stream, so that
 // the H2D copy of range k+1, the decode of range k and the D2H copy of range k-1 overlap (the two copy directions use
 // different DMA engines).  Issue order: all uploads and launches first, then the downloads in range order.
-int alacgpu_decode_batch(alacgpu_ctx* ctx, const uint8_t* blob, uint64_t blob_bytes, const uint64_t* offsets,
-                         const uint32_t* sizes, const uint16_t* cfg_idx, uint32_t n_packets, int32_t* pcm_out,
-                         uint32_t slot_ints, int32_t* out_bytes, int32_t* out_samples, int32_t* status) {
-    if (!ctx) return ALACGPU_ERR_BAD_ARG;
+int decode_host(alacgpu_ctx* ctx, const uint8_t* blob, uint64_t blob_bytes, const uint64_t* offsets, const uint32_t* sizes,
+                const uint16_t* cfg_idx, uint32_t n_packets, int32_t* pcm_out, uint32_t slot_ints, int32_t* out_bytes,
+                int32_t* out_samples, int32_t* status, uint32_t out_format) {
     if (n_packets == 0) return ALACGPU_OK;
     if (!blob || !offsets || !sizes || !pcm_out || !status || slot_ints == 0) return ALACGPU_ERR_BAD_ARG;
     // measured on cfg2 (4096 packets, tools/host_path_rate.py): 1 / 2 / 4 ranges = 4.20 / 3.97 / 4.05 ms with int32 output,
     // 2.99 / 2.63 / 3.21 ms packed: the link runs at 55 GB/s either way (134 MiB of int32 PCM alone are 2.5 ms), the copies
-    // from and to ordinary memory block the issuing thread, and a range's decode takes as long as the whole batch's
+    // from and to ordinary memory block the issuing thread, and a range's decode takes as long as the whole batch's (four
+    // ranges were measured too: 3.64 / 2.61 ms against 3.56 / 2.39 with two, cfg2, page-locked buffers)
     int nch = ctx->host_chunks ? ctx->host_chunks : (n_packets >= 1024u ? 2 : 1);
     nch = std::min<int>(nch, (int)n_packets);
-    const bool want_zc = ctx->zero_copy && device_view_of_pinned(pcm_out, sizeof(int32_t) * (size_t)n_packets * slot_ints) != nullptr;
-    (void)want_zc;   // (four ranges were measured too: 3.64 / 2.61 ms against 3.56 / 2.39 with two, cfg2, page-locked buffers)
     // validate, and find the blob range every chunk needs
     uint32_t lo[N_HOST_STREAMS + 1];
     uint64_t b0[N_HOST_STREAMS], b1[N_HOST_STREAMS];
-    for (int k = 0; k <= nch; k++) lo[k] = (uint32_t)(((uint64_t)n_packets * (uint64_t)k / (uint64_t)nch + 7u) & ~7ull);
-    lo[0] = 0;
-    lo[nch] = n_packets;
-    for (int k = 1; k < nch; k++) lo[k] = std::min(lo[k], n_packets);   // (multiples of 8: whole groups of the kernel)
+    for (int k = 0; k <= nch; k++) lo[k] = (uint32_t)alacgpu::group_cut(n_packets, k, nch);
     uint64_t range_sum = 0;
     for (int k = 0; k < nch; k++) {
         b0[k] = blob_bytes;
@@ -650,15 +627,16 @@ int alacgpu_decode_batch(alacgpu_ctx* ctx, const uint8_t* blob, uint64_t blob_by
         if (b1[k] > b0[k]) HIP_TRY(ctx, hipMemcpyAsync(d_blob + b0[k], blob + b0[k], b1[k] - b0[k], hipMemcpyHostToDevice, s0));
         HIP_TRY(ctx, hipEventRecord(ctx->ev_up[k], s0));
         HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_up[k], 0));
-        if (zc_pcm)
-            rc = decode_device_parked(ctx, d_blob, blob_bytes, d_off + lo[k], d_sz + lo[k], cfg_idx ? d_ci + lo[k] : nullptr, cnt,
-                                      zc_pcm + (size_t)lo[k] * slot_ints, slot_ints, d_ob + lo[k], d_os + lo[k], d_st + lo[k],
-                                      d_pcm + (size_t)lo[k] * park_stride, park_stride, s);
-        else
-            rc = alacgpu_decode_batch_device(ctx, d_blob, blob_bytes, d_off + lo[k], d_sz + lo[k], cfg_idx ? d_ci + lo[k] : nullptr,
-                                             cnt, d_pcm + (size_t)lo[k] * slot_ints, slot_ints, d_ob + lo[k], d_os + lo[k],
-                                             d_st + lo[k], s);
+        alac_decode_params p;
+        rc = fill_params(ctx, p, d_blob, blob_bytes, d_off + lo[k], d_sz + lo[k], cfg_idx ? d_ci + lo[k] : nullptr, cnt,
+                         (zc_pcm ? zc_pcm : d_pcm) + (size_t)lo[k] * slot_ints, slot_ints, d_ob + lo[k], d_os + lo[k], d_st + lo[k],
+                         out_format);
         if (rc) return rc;
+        if (zc_pcm) {   // channel A waits in device memory
+            p.park = d_pcm + (size_t)lo[k] * park_stride;
+            p.park_stride = park_stride;
+        }
+        if ((rc = launch(ctx, p, s))) return rc;
     }
     const size_t pitch = sizeof(int32_t) * (size_t)slot_ints;
     const size_t packed_w = std::min(pitch, packed_bytes_per_slot_int(ctx) * (size_t)slot_ints);
@@ -670,7 +648,7 @@ int alacgpu_decode_batch(alacgpu_ctx* ctx, const uint8_t* blob, uint64_t blob_by
         const int32_t* src = d_pcm + (size_t)lo[k] * slot_ints;
         if (zc_pcm) {
             // nothing to download: the kernels wrote into the caller's memory
-        } else if (ctx->out_format == ALACGPU_OUT_PACKED_LE) {
+        } else if (out_format == ALACGPU_OUT_PACKED_LE) {
             // a slot holds at most slot_ints samples of (ctor sample size / 8) bytes: copy that much of every slot
             HIP_TRY(ctx, hipMemcpy2DAsync(dst, pitch, src, pitch, packed_w, cnt, hipMemcpyDeviceToHost, s));
         } else {
@@ -683,6 +661,17 @@ int alacgpu_decode_batch(alacgpu_ctx* ctx, const uint8_t* blob, uint64_t blob_by
     for (int k = 0; k < nch; k++)
         if (ctx->streams[k]) HIP_TRY(ctx, hipStreamSynchronize(ctx->streams[k]));
     return ALACGPU_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int alacgpu_decode_batch(alacgpu_ctx* ctx, const uint8_t* blob, uint64_t blob_bytes, const uint64_t* offsets,
+                         const uint32_t* sizes, const uint16_t* cfg_idx, uint32_t n_packets, int32_t* pcm_out,
+                         uint32_t slot_ints, int32_t* out_bytes, int32_t* out_samples, int32_t* status) {
+    if (!ctx) return ALACGPU_ERR_BAD_ARG;
+    return decode_host(ctx, blob, blob_bytes, offsets, sizes, cfg_idx, n_packets, pcm_out, slot_ints, out_bytes, out_samples,
+                       status, ctx->out_format);
 }
 
 // One batch on HOST buffers over several contexts -- normally one per GPU of the node -- from one process: contiguous packet
@@ -764,19 +753,16 @@ int alacgpu_decode_frame(alacgpu_ctx* ctx, uint32_t cfg_index, const uint8_t* in
                          int32_t* outbuffer, uint32_t out_capacity_ints, int32_t* out_bytes, int32_t* status) {
     if (!ctx || !inbuffer || !outbuffer || !status || cfg_index >= ctx->n_cfgs) return ALACGPU_ERR_BAD_ARG;
     const alacgpu_cfg& cfg = ctx->h_cfgs[cfg_index];
-    const uint32_t slot = 16384u * cfg.num_channels;
-    if (!ctx->h_frame) {   // pinned, sized for the widest case once (16384 samples x 2 channels)
+    const uint32_t slot = MAX_FRAME * cfg.num_channels;
+    if (!ctx->h_frame) {   // pinned, sized for the widest case once (MAX_FRAME samples x 2 channels)
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_frame, sizeof(int32_t) * 16384u * 2u, hipHostMallocDefault));
+        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_frame, sizeof(int32_t) * MAX_FRAME * 2u, hipHostMallocDefault));
     }
     int32_t* pcm = ctx->h_frame;
     const uint64_t off = 0;
     const uint16_t ci = (uint16_t)cfg_index;
     int32_t ob = 0, os = 0, st = 0;
-    const uint32_t saved_format = ctx->out_format;
-    ctx->out_format = ALACGPU_OUT_INT32;
-    int rc = alacgpu_decode_batch(ctx, inbuffer, in_bytes, &off, &in_bytes, &ci, 1, pcm, slot, &ob, &os, &st);
-    ctx->out_format = saved_format;
+    int rc = decode_host(ctx, inbuffer, in_bytes, &off, &in_bytes, &ci, 1, pcm, slot, &ob, &os, &st, ALACGPU_OUT_INT32);
     if (rc == ALACGPU_OK) {
         *status = st;
         if (out_bytes) *out_bytes = ob;

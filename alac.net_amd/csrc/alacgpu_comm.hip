@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "alacgpu.h"
+#include "alacgpu_ranges.h"
 
 namespace {
 
@@ -49,7 +50,11 @@ rccl_api& rccl() {
         if (!api.handle)
             for (const char* n : names)
                 if ((api.handle = dlopen(n, RTLD_NOW | RTLD_GLOBAL))) break;
-        if (!api.handle) { api.error = std::string("librccl.so not found: ") + (dlerror() ? dlerror() : ""); return; }
+        if (!api.handle) {
+            const char* why = dlerror();   // (a second call would return null: the first one clears the message)
+            api.error = std::string("librccl.so not found: ") + (why ? why : "");
+            return;
+        }
         auto sym = [&](const char* s) { void* p = dlsym(api.handle, s); if (!p) api.error = std::string("RCCL symbol missing: ") + s; return p; };
         api.GetUniqueId = (int (*)(nccl_unique_id*))sym("ncclGetUniqueId");
         api.CommInitRank = (int (*)(nccl_comm_t*, int, nccl_unique_id, int))sym("ncclCommInitRank");
@@ -88,50 +93,48 @@ namespace {
             return ALACGPU_ERR_HIP;                                                              \
         }                                                                                        \
     } while (0)
-#define COMM_NCCL(c, expr)                                                                       \
-    do {                                                                                         \
-        int r_ = (expr);                                                                         \
-        if (r_ != NCCL_SUCCESS) {                                                                \
-            (c)->last_error = std::string(#expr) + ": " + (rccl().GetErrorString ? rccl().GetErrorString(r_) : "?"); \
-            return ALACGPU_ERR_COMM;                                                             \
-        }                                                                                        \
-    } while (0)
 
-// One in-place all-gather-v of packet ranges [first_r, first_r + count_r) of every rank r (a slot is slot_ints int32).
-// Equal pieces that lie side by side in rank order are one plain in-place ncclAllGather (RCCL picks the algorithm).  Pieces
-// that do not (unequal shards; the k-th piece of every shard in the overlapped form) are exchanged directly: inside one group
-// every rank sends its piece to every other rank and receives theirs, in place -- on a node whose GPUs are all linked to each
-// other (xGMI: 7 links per GPU) that uses every link at once, the pattern SURVEY.md section 8(e) asks for; grouped broadcasts
-// (one per owner) are the fallback when the library has no ncclSend / ncclRecv.
+int comm_fail(alacgpu_comm* c, const char* call, int r) {
+    c->last_error = std::string(call) + ": " + (rccl().GetErrorString ? rccl().GetErrorString(r) : "?");
+    return ALACGPU_ERR_COMM;
+}
+
+// One in-place all-gather-v of packet ranges [first_r, first_r + count_r) of every rank r (a slot is slot_ints int32), as
+// alacgpu::gather_plan lays it out.  Equal pieces side by side in rank order are one plain in-place ncclAllGather (RCCL picks
+// the algorithm).  Other pieces (unequal shards; the k-th piece of every shard in the overlapped form) go directly from
+// rank to rank inside one group: on a node whose GPUs are all linked to each other (xGMI: 7 links per GPU) that uses every
+// link at once, the pattern SURVEY.md section 8(e) asks for.  Grouped broadcasts (one per owner) are the fallback when the
+// library has no ncclSend / ncclRecv.  A group is always closed; the first failure is the one reported.
 int gather_pieces(alacgpu_comm* c, int32_t* d_full, uint32_t slot_ints, const std::vector<uint64_t>& first,
                   const std::vector<uint64_t>& count, hipStream_t s) {
     rccl_api& R = rccl();
-    bool equal = true;
-    for (int r = 0; r < c->world; r++) equal = equal && count[r] == count[0] && first[r] == first[0] + (uint64_t)r * count[0];
-    if (equal) {   // contiguous equal pieces in rank order: the plain in-place all-gather
-        if (count[0] == 0) return ALACGPU_OK;
-        COMM_NCCL(c, R.AllGather(d_full + (first[0] + (uint64_t)c->rank * count[0]) * slot_ints, d_full + first[0] * slot_ints,
-                                 (size_t)count[0] * slot_ints, NCCL_INT32, c->comm, s));
-        return ALACGPU_OK;
+    const alacgpu::gather_plan_t plan = alacgpu::gather_plan(c->rank, c->world, first.data(), count.data(), R.Send && R.Recv);
+    if (plan.grouped) {
+        const int r = R.GroupStart();
+        if (r != NCCL_SUCCESS) return comm_fail(c, "ncclGroupStart", r);
     }
-    if (c->world == 1) return ALACGPU_OK;   // nothing to exchange
-    COMM_NCCL(c, R.GroupStart());
-    if (R.Send && R.Recv) {
-        const int me = c->rank;
-        for (int k = 1; k < c->world; k++) {
-            const int to = (me + k) % c->world, from = (me - k + c->world) % c->world;   // (a different peer pair per round)
-            if (count[me]) COMM_NCCL(c, R.Send(d_full + first[me] * slot_ints, (size_t)count[me] * slot_ints, NCCL_INT32, to, c->comm, s));
-            if (count[from]) COMM_NCCL(c, R.Recv(d_full + first[from] * slot_ints, (size_t)count[from] * slot_ints, NCCL_INT32, from, c->comm, s));
+    const char* const names[] = {"ncclAllGather", "ncclSend", "ncclRecv", "ncclBroadcast"};   // (by gather_kind)
+    int rc = ALACGPU_OK;
+    for (const alacgpu::gather_op& op : plan.ops) {
+        int32_t* piece = d_full + op.first * slot_ints;
+        const size_t n = (size_t)op.count * slot_ints;
+        int r = NCCL_SUCCESS;
+        switch (op.kind) {
+        case alacgpu::GATHER_ALLGATHER: r = R.AllGather(piece + (size_t)c->rank * n, piece, n, NCCL_INT32, c->comm, s); break;
+        case alacgpu::GATHER_SEND: r = R.Send(piece, n, NCCL_INT32, op.peer, c->comm, s); break;
+        case alacgpu::GATHER_RECV: r = R.Recv(piece, n, NCCL_INT32, op.peer, c->comm, s); break;
+        case alacgpu::GATHER_BCAST: r = R.Broadcast(piece, piece, n, NCCL_INT32, op.peer, c->comm, s); break;
         }
-    } else {
-        for (int r = 0; r < c->world; r++) {
-            if (count[r] == 0) continue;
-            int32_t* piece = d_full + first[r] * slot_ints;
-            COMM_NCCL(c, R.Broadcast(piece, piece, (size_t)count[r] * slot_ints, NCCL_INT32, r, c->comm, s));
+        if (r != NCCL_SUCCESS) {
+            rc = comm_fail(c, names[op.kind], r);
+            break;
         }
     }
-    COMM_NCCL(c, R.GroupEnd());
-    return ALACGPU_OK;
+    if (plan.grouped) {
+        const int r = R.GroupEnd();
+        if (r != NCCL_SUCCESS && rc == ALACGPU_OK) rc = comm_fail(c, "ncclGroupEnd", r);
+    }
+    return rc;
 }
 
 }  // namespace
@@ -148,10 +151,7 @@ int alacgpu_shard_ranges(const uint32_t* sizes, uint32_t n_packets, uint32_t wor
     uint64_t total = 0;
     for (uint32_t i = 0; i < n_packets; i++) total += sizes[i];
     // by count
-    for (uint32_t r = 0; r <= world; r++)
-        first[r] = (uint32_t)std::min<uint64_t>(n_packets, (((uint64_t)n_packets * r / world) + 7u) & ~7ull);
-    first[0] = 0;
-    first[world] = n_packets;
+    for (uint32_t r = 0; r <= world; r++) first[r] = (uint32_t)alacgpu::group_cut(n_packets, r, world);
     uint64_t bmin = ~0ull, bmax = 0;
     for (uint32_t r = 0; r < world; r++) {
         uint64_t b = 0;
@@ -264,16 +264,13 @@ int alacgpu_decode_allgather_device(alacgpu_ctx* ctx, alacgpu_comm* c, const voi
                                     void* d_full_pcm, uint32_t slot_ints, void* d_out_bytes, void* d_out_samples,
                                     void* d_status, uint32_t n_chunks, void* hip_stream) {
     if (!ctx || !c || c->ctx != ctx || !first || !d_full_pcm || slot_ints == 0) return ALACGPU_ERR_BAD_ARG;
+    if (!d_blob || !d_offsets || !d_sizes || !d_status) return ALACGPU_ERR_BAD_ARG;   // (every rank alike: before any offset)
     n_chunks = std::max(1u, std::min(n_chunks, 4u));
     COMM_HIP(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)hip_stream;
     const int W = c->world;
     // piece k of rank r: whole groups of 8 packets
-    auto cut = [&](int r, uint32_t k) {
-        const uint64_t lo = first[r], cnt = first[r + 1] - first[r];
-        if (k >= n_chunks) return lo + cnt;
-        return lo + std::min<uint64_t>(cnt, ((cnt * k / n_chunks) + 7u) & ~7ull);
-    };
+    auto cut = [&](int r, uint32_t k) { return first[r] + alacgpu::group_cut(first[r + 1] - first[r], k, n_chunks); };
     for (int r = 0; r < W; r++)
         if (first[r + 1] < first[r]) return ALACGPU_ERR_BAD_ARG;
     for (uint32_t k = 0; k < n_chunks; k++) {

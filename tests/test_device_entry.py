@@ -107,6 +107,28 @@ def test_bad_arguments_are_refused(torch, pkg, synth):
         assert rc == 0       # empty batch: nothing to do
         assert L.alacgpu_decode_batch_device(None, vp(d.blob), d.nb, vp(d.off), vp(d.sz), None, d.n, vp(d.pcm), d.slot,
                                              None, None, vp(d.st), None) == -1
+        # the PCM view check decode-into and encode share: every bad view is refused before any launch
+        dev = torch.device("cuda", 0)
+        first = torch.arange(d.n, dtype=torch.int64, device=dev) * 4096
+        frames = torch.full((d.n,), 4096, dtype=torch.int32, device=dev)
+        ci = torch.zeros(d.n, dtype=torch.int16, device=dev)
+        view = torch.zeros(d.n * 4096 * 2 + 4, dtype=torch.int32, device=dev)
+        slot = pkg.encode_max_packet_bytes(4096, 16, 2)
+        packets = torch.zeros(d.n * slot, dtype=torch.uint8, device=dev)
+        sizes = torch.zeros(d.n, dtype=torch.int32, device=dev)
+
+        def into_and_encode(n, channels=2, layout=pkg.DST_PLANAR, dtype=pkg.DST_INT32, plane_stride=d.n * 4096, offset=0):
+            p = C.c_void_p(view.data_ptr() + offset)
+            return (L.alacgpu_decode_into_device(ctx._ctx, vp(d.blob), d.nb, vp(d.off), vp(d.sz), None, n, vp(first), vp(frames), p,
+                                                 d.n * 4096 * 2, channels, layout, dtype, plane_stride, None, vp(d.st), None),
+                    L.alacgpu_encode_device(ctx._ctx, p, d.n * 4096 * 2, channels, layout, dtype, plane_stride, vp(first),
+                                            vp(frames), vp(ci), n, vp(packets), slot, vp(sizes), vp(d.st), None))
+
+        assert into_and_encode(0) == (0, 0)                         # a good view (nothing to do)
+        for kw in (dict(channels=0), dict(channels=3), dict(layout=2), dict(dtype=2), dict(plane_stride=0), dict(offset=2)):
+            for n in (0, d.n):
+                assert into_and_encode(n, **kw) == (-1, -1), (kw, n)
+        torch.cuda.synchronize()
 
 
 def test_calls_in_flight_on_two_streams_share_one_ctx(torch, pkg, oracle, synth):

@@ -270,7 +270,9 @@ class AlacGpuContext(_Closing):
         """alacgpu_encode_device: packet p encodes frames d_src_first[p] .. + d_src_frames[p] of `pcm` (torch int32 or float32
         on this device, contiguous; its dtype picks the element type) with stream cfg d_cfg_idx[p]; its bytes land at
         d_packets[p * slot_bytes:] (a uint8 device tensor), its size in d_sizes[p], its status in d_status[p].  d_* are torch
-        device tensors; asynchronous on `stream` (raw hipStream_t)."""
+        device tensors; asynchronous on `stream` (raw hipStream_t).  Samples are taken as `save` takes them: int32 clamped to
+        the cfg's sample range; float32 times 2^(bits-1) (in float32), clamped, then rounded half to even; NaN the smallest
+        sample."""
         dtype, lay = _pcm_view("pcm", pcm, layout)
         rc = lib().alacgpu_encode_device(self._ctx, _dp(pcm), pcm.numel(), channels, lay, dtype, plane_stride, _dp(d_src_first),
                                          _dp(d_src_frames), _dp(d_cfg_idx), n_packets, _dp(d_packets), slot_bytes, _dp(d_sizes),
@@ -638,7 +640,9 @@ def _write_file(dest, packets, durations, frame_length, sample_size, channels, s
 def save(dest, pcm, sample_rate, sample_size=16, frame_length=4096, device=0):
     """Encode pcm [C, T] (planar, torch int32 -- the canonical sample -- or float32 -- sample * 2^-(bits-1), what `load`
     returns) on the GPU to ALAC and write it as an M4A file to `dest` (a path or a writable binary file object).  Returns the
-    file's size in bytes.  ValueError (before any device work) for a channel count other than 1 / 2, a sample size other than
+    file's size in bytes.  int32 samples outside the sample range are clamped to it.  float32 samples are multiplied by
+    2^(sample_size-1) in float32, clamped to the sample range (so +-1.0 and beyond, and +-inf, give the extremes), then
+    rounded to the nearest integer, half to even; NaN gives the smallest sample.  ValueError (before any device work) for a channel count other than 1 / 2, a sample size other than
     16 / 24, a frame_length outside 1 .. 16384, a tensor that is not on the GPU, an empty input, or a length whose file could
     outgrow the 32-bit chunk offsets."""
     F, C_, T = _check_save_args(pcm, False, sample_size, frame_length, sample_rate)

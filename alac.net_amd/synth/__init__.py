@@ -68,6 +68,8 @@ def lib():
         L = C.CDLL(path)
         L.alac_synth_encode_packet.restype = C.c_size_t
         L.alac_synth_encode_packet.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.alac_synth_encode_packet_bits.restype = C.c_size_t
+        L.alac_synth_encode_packet_bits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.alac_synth_make_pcm.restype = None
         L.alac_synth_make_pcm.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_uint32, C.c_void_p]
         L.alac_synth_make_batch.restype = C.c_size_t
@@ -125,6 +127,20 @@ def encode_packet(desc, pcm):
     if sz == 0:
         raise ValueError("alac_synth_encode_packet failed (bad recipe?)")
     return out[:sz].tobytes()
+
+
+def encode_packet_bits(desc, pcm):
+    """encode_packet, and the packet's exact length in bits (through the END tag, before the padding to the byte):
+    (bytes, nbits), or None when the recipe cannot be written (for instance a Rice stream the decoder cannot express)."""
+    desc = np.ascontiguousarray(desc).reshape(1)
+    pcm = np.ascontiguousarray(pcm, dtype=np.int32)
+    cap = int(lib().alac_synth_max_packet_bytes(int(desc["n"][0]), int(desc["sample_size"][0]), int(desc["stereo"][0])))
+    out = np.zeros(cap, dtype=np.uint8)
+    nbits = np.zeros(1, dtype=np.uint64)
+    sz = lib().alac_synth_encode_packet_bits(_ptr(desc), _ptr(pcm), _ptr(out), cap, _ptr(nbits))
+    if sz == 0:
+        return None
+    return out[:sz].tobytes(), int(nbits[0])
 
 
 def make_pcm(sig, index, sample_size, ch, n):

@@ -171,6 +171,10 @@ size_t alac_synth_max_packet_bytes(uint32_t n, int sample_size, int stereo) {
 }
 
 size_t alac_synth_encode_packet(const alac_synth_pkt* d, const int32_t* pcm, uint8_t* out, size_t cap) {
+    return alac_synth_encode_packet_bits(d, pcm, out, cap, NULL);
+}
+
+size_t alac_synth_encode_packet_bits(const alac_synth_pkt* d, const int32_t* pcm, uint8_t* out, size_t cap, uint64_t* nbits) {
     const int n = (int)d->n;
     const int ch = d->stereo ? 2 : 1;
     const int ss = d->sample_size;
@@ -248,6 +252,7 @@ size_t alac_synth_encode_packet(const alac_synth_pkt* d, const int32_t* pcm, uin
         if (bad) return 0;
     }
     put_bits(&w, 7, 3); /* END element tag, ignored by the reference decoder */
+    if (nbits) *nbits = w.bitpos;
     while (w.bitpos & 7) put_bits(&w, 0, 1);
     if (w.overflow) return 0;
     return w.bitpos >> 3;

@@ -53,6 +53,12 @@ typedef struct {
  * Returns the packet size in bytes, or 0 when `cap` is too small / parameters are invalid. */
 size_t alac_synth_encode_packet(const alac_synth_pkt* desc, const int32_t* pcm, uint8_t* out, size_t cap);
 
+/* The same, and *nbits (when not NULL) receives the packet's exact length in bits: through the END tag, before the zeros
+ * that pad it to the byte.  Returns 0 (and leaves *nbits) when the packet cannot be written -- for instance a Rice stream
+ * the decoder's state machine cannot express. */
+size_t alac_synth_encode_packet_bits(const alac_synth_pkt* desc, const int32_t* pcm, uint8_t* out, size_t cap,
+                                     uint64_t* nbits);
+
 /* Generate the PCM for packet `index` (interleaved, ch channels) */
 void alac_synth_make_pcm(const alac_synth_signal* sig, uint64_t index, int sample_size, int ch, uint32_t n,
                          int32_t* pcm);

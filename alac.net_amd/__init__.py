@@ -7,6 +7,7 @@ numchannels)`, `SetInfo(codecData)`, `DecodeFrame(inbuffer, outbuffer)` (AlacFil
 gfx950 GPU is usable, every entry point raises.
 """
 import ctypes as C
+import operator
 import os
 
 import numpy as np
@@ -57,6 +58,8 @@ SYMBOLS = {
                                               _VP, _VP, _VP]),
     "alacgpu_decode_into_device": (C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, C.c_uint64,
                                              C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP]),
+    "alacgpu_decode_window_into_device": (C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP,
+                                                    C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP]),
     "alacgpu_encode_max_packet_bytes": (C.c_size_t, [C.c_uint32, C.c_int, C.c_int]),
     "alacgpu_encode_device": (C.c_int, [_VP, _VP, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP, C.c_uint32,
                                         _VP, C.c_uint64, _VP, _VP, _VP]),
@@ -265,6 +268,21 @@ class AlacGpuContext(_Closing):
                                               dtype, plane_stride, _dp(d_out_samples), _dp(d_status), _VP(stream))
         _check(rc, self._ctx)
 
+    def decode_window_into_device(self, d_blob, blob_bytes, d_offsets, d_sizes, d_cfg_idx, n_packets, d_dst_first, d_dst_frames,
+                                  d_src_skip, out, channels, layout="planar", plane_stride=0, d_out_samples=None, d_status=None,
+                                  stream=0):
+        """alacgpu_decode_window_into_device: decode_into_device with packet p's run starting d_src_skip[p] frames into the
+        packet (an int32 device tensor, at most 16384 each; None: no skip, exactly decode_into_device): frames
+        d_src_skip[p] .. + d_dst_frames[p] land at d_dst_first[p] of `out`."""
+        dtype, lay = _pcm_view("out", out, layout)
+        if d_status is None:
+            raise ValueError("d_status is required")
+        rc = lib().alacgpu_decode_window_into_device(self._ctx, _dp(d_blob), blob_bytes, _dp(d_offsets), _dp(d_sizes),
+                                                     _dp(d_cfg_idx), n_packets, _dp(d_dst_first), _dp(d_dst_frames),
+                                                     _dp(d_src_skip), _dp(out), out.numel(), channels, lay, dtype, plane_stride,
+                                                     _dp(d_out_samples), _dp(d_status), _VP(stream))
+        _check(rc, self._ctx)
+
     def encode_device(self, pcm, channels, d_src_first, d_src_frames, d_cfg_idx, n_packets, d_packets, slot_bytes, d_sizes,
                       d_status, layout="planar", plane_stride=0, stream=0):
         """alacgpu_encode_device: packet p encodes frames d_src_first[p] .. + d_src_frames[p] of `pcm` (torch int32 or float32
@@ -430,20 +448,47 @@ def _normalise_status(st, first_bytes):
     return np.where(st == ST_UNSUPPORTED_ELEMENT, ST_OK, st)
 
 
-def _decode_tables(tables, cfgs, cfg_idx, keep, dst_first, dst_frames, out, channels, layout, plane_stride, device):
-    """One alacgpu_decode_into_device call over the packets `keep[f]` of every table; returns the statuses (host)."""
+def window_plan(dst_first, durations, offset, length):
+    """The packets of frames offset .. offset + length of one file, on the host.  Frame t belongs to the packet p with
+    dst_first[p] <= t < dst_first[p] + durations[p] (dst_first: the exclusive prefix sum of the durations, as packet_table
+    gives them).  Returns (p0, p1, first, frames, skip): the contiguous packet range p0 .. p1 that overlaps the window (a
+    window from frame 0 starts at packet 0; packets with no frames inside it are taken only between others), and per packet
+    of it the run's first frame relative to the window, its frame count and the frames skipped at the packet's start
+    (int64 arrays of p1 - p0).  A window of length 0 has no packets."""
+    dst_first = np.asarray(dst_first, dtype=np.int64)
+    durations = np.asarray(durations, dtype=np.int64)
+    offset, length = int(offset), int(length)
+    if offset < 0 or length < 0:
+        raise ValueError(f"offset {offset} and length {length} must not be negative")
+    end = offset + length
+    if length == 0:
+        p0 = p1 = 0
+    else:
+        p0 = 0 if offset == 0 else int(np.searchsorted(dst_first + durations, offset, side="right"))
+        p1 = max(int(np.searchsorted(dst_first, end, side="left")), p0)
+    f, d = dst_first[p0:p1], durations[p0:p1]
+    lo = np.maximum(f, offset)
+    frames = np.maximum(np.minimum(f + d, end) - lo, 0)
+    return p0, p1, lo - offset, frames, lo - f
+
+
+def _decode_tables(tables, cfgs, cfg_idx, ranges, dst_first, dst_frames, src_skip, out, channels, layout, plane_stride, device):
+    """One alacgpu_decode_window_into_device call over the packets ranges[f] = (p0, p1) of every table (only their bytes are
+    uploaded); src_skip None: no skip.  Returns the statuses and the packets' first bytes (host)."""
     import torch
 
     dev = torch.device("cuda", device)
     blobs, offs, sizes, firsts = [], [], [], []
     base = 0
-    for t, k in zip(tables, keep):
-        o, z = t["offsets"][k], t["sizes"][k]
-        used = int(o[-1]) + int(z[-1]) if len(o) else 0      # (the kept packets are a prefix: nothing behind them is uploaded)
-        blobs.append(t["blob"][:used])
-        offs.append(o.astype(np.uint64) + np.uint64(base))
+    for t, (p0, p1) in zip(tables, ranges):
+        o, z = t["offsets"][p0:p1], t["sizes"][p0:p1]
+        start = int(o[0]) if len(o) else 0
+        used = int(o[-1]) + int(z[-1]) - start if len(o) else 0   # (the range's bytes: nothing in front of or behind it)
+        blobs.append(t["blob"][start:start + used])
+        offs.append(o.astype(np.uint64) - np.uint64(start) + np.uint64(base))
         sizes.append(z)
-        firsts.append(t["blob"][np.minimum(o, max(used - 1, 0)).astype(np.int64)] if used else np.zeros(len(o), np.uint8))
+        firsts.append(t["blob"][start + np.minimum(o - np.uint64(start), max(used - 1, 0)).astype(np.int64)] if used
+                      else np.zeros(len(o), np.uint8))
         base += used
     offsets = np.concatenate(offs) if offs else np.zeros(0, np.uint64)
     n = len(offsets)
@@ -457,20 +502,48 @@ def _decode_tables(tables, cfgs, cfg_idx, keep, dst_first, dst_frames, out, chan
     d_ci = torch.from_numpy(cfg_idx.astype(np.int16)).to(dev)
     d_first = torch.from_numpy(dst_first.astype(np.int64)).to(dev)
     d_frames = torch.from_numpy(dst_frames.astype(np.int32)).to(dev)
+    # a packet decodes at most 16384 frames: a window that starts further into it (a stts duration above 16384) is frames
+    # that are zeros in the whole file too -- skip 16384 gives exactly those zeros, and the packet is still decoded and checked
+    d_skip = (torch.from_numpy(np.minimum(src_skip, MAX_FRAME).astype(np.int32)).to(dev) if src_skip is not None else None)
     d_st = torch.empty(n, dtype=torch.int32, device=dev)
     with AlacGpuContext(cfgs, device) as ctx:
         stream = torch.cuda.current_stream(dev)
-        ctx.decode_into_device(d_blob, base, d_off, d_sz, d_ci, n, d_first, d_frames, out, channels, layout, plane_stride,
-                               None, d_st, stream=stream.cuda_stream)
+        ctx.decode_window_into_device(d_blob, base, d_off, d_sz, d_ci, n, d_first, d_frames, d_skip, out, channels, layout,
+                                      plane_stride, None, d_st, stream=stream.cuda_stream)
         st = d_st.cpu().numpy()     # (waits for the decode: the context's scratch is released behind it)
     return st, np.concatenate(firsts)
 
 
-def load(source, device=0, dtype=None, layout="planar"):
-    """Decode a whole M4A file on the GPU into one gap-free tensor: returns (pcm, sample_rate), pcm [C, T] (planar) or [T, C]
-    (interleaved) on cuda:`device`, T = AlacContext.GetNumSamples().  float32 (default): sample * 2^-(bits-1), exact; int32:
-    the canonical sample.  `source`: file bytes, a path, or a seekable binary file object.  Raises AlacGpuError naming the first
-    packet that does not decode (statuses read as AlacContext.ReadBatch reads them)."""
+def _frame_count(name, value, minimum=0):
+    """An int argument (numpy ints too) that is at least `minimum`, else ValueError."""
+    try:
+        v = operator.index(value)
+    except TypeError:
+        raise ValueError(f"{name} must be an integer, not {value!r}") from None
+    if v < minimum:
+        raise ValueError(f"{name} must be at least {minimum}, not {v}")
+    return v
+
+
+def info(source):
+    """The stream facts of an M4A file from its headers alone (no packet bytes, no GPU context): a dict with num_frames
+    (AlacContext.GetNumSamples: the sum of the stts durations -- what `load` returns, and the frame offsets `load` and
+    `load_batch` accept are 0 .. num_frames), channels, sample_rate and sample_size.  `source` as for `load`."""
+    from .container import header_table
+
+    h = header_table(source)
+    return dict(num_frames=h["num_samples"], channels=h["num_channels"], sample_rate=h["sample_rate"],
+                sample_size=h["sample_size"])
+
+
+def load(source, device=0, dtype=None, layout="planar", frame_offset=0, num_frames=None):
+    """Decode an M4A file on the GPU into one gap-free tensor: returns (pcm, sample_rate), pcm [C, n] (planar) or [n, C]
+    (interleaved) on cuda:`device`.  float32 (default): sample * 2^-(bits-1), exact; int32: the canonical sample.  `source`:
+    file bytes, a path, or a seekable binary file object.  frame_offset / num_frames: the window of frames frame_offset ..
+    frame_offset + n, n = min(num_frames, T - frame_offset) (T = AlacContext.GetNumSamples(); num_frames None: to the end);
+    only the packets that overlap it are uploaded and decoded.  ValueError (before any device work) for a frame_offset outside
+    0 .. T or a negative num_frames.  Raises AlacGpuError naming the first packet (its index in the file) that does not decode
+    (statuses read as AlacContext.ReadBatch reads them)."""
     import torch
 
     from .container import packet_table
@@ -478,25 +551,35 @@ def load(source, device=0, dtype=None, layout="planar"):
     dtype = _torch_dtype(torch, torch.float32 if dtype is None else dtype)
     if layout not in ("planar", "interleaved"):
         raise ValueError(f"layout must be 'planar' or 'interleaved', not {layout!r}")
+    frame_offset = _frame_count("frame_offset", frame_offset)
+    if num_frames is not None:
+        num_frames = _frame_count("num_frames", num_frames)
     t = packet_table(source)
     C_, T = int(t["num_channels"]), int(t["num_samples"])
-    shape = (C_, T) if layout == "planar" else (T, C_)
+    if frame_offset > T:
+        raise ValueError(f"frame_offset {frame_offset} outside 0 .. {T}")
+    L = T - frame_offset if num_frames is None else min(num_frames, T - frame_offset)
+    if frame_offset == 0 and L == T:       # the whole file: every packet, as it always was
+        p0, p1, first, frames, skip = 0, len(t["sizes"]), t["dst_first"], t["durations"], None
+    else:
+        p0, p1, first, frames, skip = window_plan(t["dst_first"], t["durations"], frame_offset, L)
+    shape = (C_, L) if layout == "planar" else (L, C_)
     out = torch.zeros(shape, dtype=dtype, device=torch.device("cuda", device))
-    n = len(t["sizes"])
-    keep = np.ones(n, dtype=bool)
-    st, first = _decode_tables([t], t["cfg"], np.zeros(n, np.uint16), [keep], t["dst_first"], t["durations"], out, C_, layout,
-                               max(T, 1), device)
-    bad = np.nonzero(_normalise_status(st, first) != ST_OK)[0]
+    st, first_bytes = _decode_tables([t], t["cfg"], np.zeros(p1 - p0, np.uint16), [(p0, p1)], first, frames,
+                                     skip if skip is not None and skip.any() else None, out, C_, layout, max(L, 1), device)
+    bad = np.nonzero(_normalise_status(st, first_bytes) != ST_OK)[0]
     if len(bad):
         p = int(bad[0])
-        raise AlacGpuError(f"packet {p} does not decode: {_status_text(st[p])}")
+        raise AlacGpuError(f"packet {p0 + p} does not decode: {_status_text(st[p])}")
     return out, int(t["sample_rate"])
 
 
-def load_batch(sources, device=0, dtype=None, max_frames=None):
+def load_batch(sources, device=0, dtype=None, max_frames=None, frame_offsets=None):
     """Decode several M4A files in ONE launch into a zero-padded [F, C, Tmax] tensor: returns (pcm, lengths[F], sample_rate)
     (lengths: int64, host).  Files may mix 16- and 24-bit; they must share channel count and sample rate (ValueError).
-    max_frames: crop every file to at most that many frames (packets wholly past the crop are not uploaded)."""
+    frame_offsets: an int or one per file (default 0): file f's window starts there, and lengths[f] = T_f - frame_offsets[f].
+    max_frames: crop every window to at most that many frames.  Only the packets that overlap a window are uploaded and
+    decoded.  ValueError (before any device work) for an offset outside 0 .. T_f or a frame_offsets of another length."""
     import torch
 
     from .container import packet_table
@@ -511,23 +594,39 @@ def load_batch(sources, device=0, dtype=None, max_frames=None):
     for i, t in enumerate(tables):
         if int(t["num_channels"]) != C_ or int(t["sample_rate"]) != rate:
             raise ValueError(f"source {i}: {t['num_channels']} channels at {t['sample_rate']} Hz, the first has {C_} at {rate} Hz")
-    lengths = np.array([t["num_samples"] for t in tables], dtype=np.int64)
+    F = len(tables)
+    totals = np.array([t["num_samples"] for t in tables], dtype=np.int64)
+    if frame_offsets is None:
+        offsets = np.zeros(F, dtype=np.int64)
+    elif np.ndim(frame_offsets) == 0:
+        offsets = np.full(F, _frame_count("frame_offsets", frame_offsets), dtype=np.int64)
+    else:
+        offsets = np.array([_frame_count(f"frame_offsets[{f}]", o) for f, o in enumerate(frame_offsets)], dtype=np.int64)
+        if len(offsets) != F:
+            raise ValueError(f"{len(offsets)} frame offsets for {F} sources")
+    past = np.nonzero(offsets > totals)[0]
+    if len(past):
+        f = int(past[0])
+        raise ValueError(f"source {f}: frame offset {offsets[f]} outside 0 .. {totals[f]}")
+    lengths = totals - offsets
     if max_frames is not None:
         lengths = np.minimum(lengths, max(int(max_frames), 0))
-    F, Tmax = len(tables), int(lengths.max())
+    Tmax = int(lengths.max())
     out = torch.zeros((F, C_, Tmax), dtype=dtype, device=torch.device("cuda", device))
-    keep, ci, pk, firsts, frames = [], [], [], [], []
+    ranges, ci, pk, firsts, frames, skips = [], [], [], [], [], []
     for f, t in enumerate(tables):
-        k = t["dst_first"] < lengths[f]
-        keep.append(k)
-        ci.append(np.full(int(np.count_nonzero(k)), f, dtype=np.uint16))
-        pk.append(np.nonzero(k)[0])
-        firsts.append(t["dst_first"][k] + f * C_ * Tmax)
-        frames.append(np.minimum(t["durations"][k], lengths[f] - t["dst_first"][k]))
+        p0, p1, first, fr, skip = window_plan(t["dst_first"], t["durations"], offsets[f], lengths[f])
+        ranges.append((p0, p1))
+        ci.append(np.full(p1 - p0, f, dtype=np.uint16))
+        pk.append(np.arange(p0, p1))
+        firsts.append(first + f * C_ * Tmax)
+        frames.append(fr)
+        skips.append(skip)
     cfgs = np.concatenate([t["cfg"] for t in tables])
-    st, first = _decode_tables(tables, cfgs, np.concatenate(ci), keep, np.concatenate(firsts), np.concatenate(frames), out, C_,
-                               "planar", max(Tmax, 1), device)
-    bad = np.nonzero(_normalise_status(st, first) != ST_OK)[0]
+    skip = np.concatenate(skips)
+    st, first_bytes = _decode_tables(tables, cfgs, np.concatenate(ci), ranges, np.concatenate(firsts), np.concatenate(frames),
+                                     skip if skip.any() else None, out, C_, "planar", max(Tmax, 1), device)
+    bad = np.nonzero(_normalise_status(st, first_bytes) != ST_OK)[0]
     if len(bad):
         p = int(bad[0])
         f, q = int(np.concatenate(ci)[p]), int(np.concatenate(pk)[p])

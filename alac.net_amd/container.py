@@ -299,6 +299,45 @@ def _open_source(source):
     return source, False
 
 
+def _read_headers(f):
+    """The movie headers of an open file, read as packet_table reads them: (DemuxResT, the _Stream at the start of the media
+    data, durations[n] int64, sizes[n] uint32)."""
+    res = DemuxResT()
+    stream = _Stream(f)
+    head = QtMovieT(stream, res).ReadHeader()
+    if head in (MDAT_NONE, MDAT_CANNOT_SEEK):
+        raise IOError("Error while loading the QuickTime movie headers.")
+    # TryGetSampleInfo (AlacContext.cs:130-156) for every packet: the stts runs, cut where stsz or stts ends
+    counts = [int(c) for c, _ in res.TimeToSample[:res.NumTimeToSamples]]
+    durs = [int(d) for _, d in res.TimeToSample[:res.NumTimeToSamples]]
+    durations = np.repeat(np.array(durs, dtype=np.int64), np.maximum(np.array(counts, dtype=np.int64), 0))
+    n = min(len(res.SampleByteSize), len(durations))
+    return res, stream, durations[:n].copy(), res.SampleByteSize[:n].astype(np.uint32)
+
+
+def _stream_facts(res, durations):
+    return dict(sample_rate=res.SampleRate if res.SampleRate != 0 else 44100,
+                num_channels=res.NumChannels if res.NumChannels != 0 else 2,
+                sample_size=res.SampleSize if res.SampleSize != 0 else 16,
+                num_samples=int(durations.sum()))
+
+
+def header_table(source):
+    """What the headers of an M4A file say, without its packet bytes (host only, no GPU context): a dict with sizes[n] uint32,
+    durations[n] int64 (frames), sample_rate, num_channels, sample_size and num_samples, as packet_table gives them.  ValueError
+    for a source that is neither file bytes, a path nor a seekable binary file object."""
+    if not isinstance(source, (bytes, bytearray, memoryview, str, os.PathLike)) and \
+            not all(hasattr(source, a) for a in ("read", "seek", "tell")):
+        raise ValueError(f"source must be file bytes, a path or a seekable binary file object, not {type(source).__name__}")
+    f, close = _open_source(source)
+    try:
+        res, _, durations, sizes = _read_headers(f)
+        return dict(sizes=sizes, durations=durations, **_stream_facts(res, durations))
+    finally:
+        if close:
+            f.close()
+
+
 def packet_table(source):
     """The packet table of an M4A file, on the host only (no GPU context): what alacgpu_decode_into_device needs to place
     every packet of the file in one gap-free tensor.  `source`: file bytes, a path, or a seekable binary file object.
@@ -309,18 +348,8 @@ def packet_table(source):
       sample_size, num_samples (AlacContext.GetNumSamples: the sum of the durations)."""
     f, close = _open_source(source)
     try:
-        res = DemuxResT()
-        stream = _Stream(f)
-        head = QtMovieT(stream, res).ReadHeader()
-        if head in (MDAT_NONE, MDAT_CANNOT_SEEK):
-            raise IOError("Error while loading the QuickTime movie headers.")
-        # TryGetSampleInfo (AlacContext.cs:130-156) for every packet: the stts runs, cut where stsz or stts ends
-        counts = [int(c) for c, _ in res.TimeToSample[:res.NumTimeToSamples]]
-        durs = [int(d) for _, d in res.TimeToSample[:res.NumTimeToSamples]]
-        durations = np.repeat(np.array(durs, dtype=np.int64), np.maximum(np.array(counts, dtype=np.int64), 0))
-        n = min(len(res.SampleByteSize), len(durations))
-        durations = durations[:n].copy()
-        sizes = res.SampleByteSize[:n].astype(np.uint32)
+        res, stream, durations, sizes = _read_headers(f)
+        n = len(sizes)
         blob = np.frombuffer(stream.Read(int(sizes.sum(dtype=np.int64))), dtype=np.uint8)
         offsets = np.zeros(n, dtype=np.uint64)
         if n > 1:
@@ -330,10 +359,7 @@ def packet_table(source):
             dst_first[1:] = np.cumsum(durations[:-1])
         cfg = cfg_from_codec_data(res.CodecData[:48], res.SampleSize, res.NumChannels)
         return dict(sizes=sizes, durations=durations, dst_first=dst_first, offsets=offsets, blob=blob, cfg=cfg,
-                    sample_rate=res.SampleRate if res.SampleRate != 0 else 44100,
-                    num_channels=res.NumChannels if res.NumChannels != 0 else 2,
-                    sample_size=res.SampleSize if res.SampleSize != 0 else 16,
-                    num_samples=int(durations.sum()))
+                    **_stream_facts(res, durations))
     finally:
         if close:
             f.close()

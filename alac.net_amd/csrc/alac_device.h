@@ -828,7 +828,8 @@ __device__ __forceinline__ Meta parse_meta(const alac_decode_params& p, uint32_t
         else if (m.stereo && m.nc < 2 && (uint64_t)m.n * 2u > p.slot_ints) m.status = ALACGPU_ST_UNSUPPORTED_ELEMENT_D;
         else if (m.ss - m.ub * 8 < 8) m.status = ALACGPU_ST_UNSUPPORTED_PARAMS_D;
         // destination mode: a packet whose run does not fit, or whose stream has another channel count, is switched off here
-        // for every role (and writes nothing)
+        // for every role (and writes nothing).  (A window that starts past the longest frame reaches here as a run that does
+        // not fit: alac_window_first_kernel.)
         if (p.dst_first && ((!badcfg && cfg.num_channels != p.channels) || !dst_run_inside(p, pkt)))
             m.status = ALACGPU_ST_DEST_RANGE_D;
         m.rawbit = hdr_end;

@@ -62,8 +62,12 @@ struct alac_decode_params {
     // (dtype 1); frames i >= dst_frames[p] are not stored.  A run outside [0, out_elems) or a stream cfg with another channel
     // count is status ALACGPU_ST_DEST_RANGE_D, and such a packet writes nothing.  slot_ints is channels * Smax (the statuses
     // of the slot layout) and channel A is parked at park + p * park_stride.
+    // src_skip (may be null: no skip): a window of the packet -- frames i with src_skip[p] <= i < src_skip[p] + dst_frames[p]
+    // are stored, frame i at dst_first[p] + (i - src_skip[p]).  With src_skip, dst_first is the launch's own copy from
+    // alac_window_first_kernel: a skip above 16384 there turns into a run that does not fit (status ALACGPU_ST_DEST_RANGE_D).
     const uint64_t* dst_first;
     const uint32_t* dst_frames;
+    const uint32_t* src_skip;
     uint64_t out_elems;
     uint64_t plane_stride;
     uint32_t channels, layout, dtype;
@@ -79,9 +83,18 @@ extern "C" __global__ void alac_decode_ab_small_kernel(alac_decode_params p);   
 extern "C" __global__ void alac_decode_ab32_kernel(alac_decode_params p);
 // the first launch with 16 packets / 256-thread workgroup (one entropy wave for 16 streams, orders 1..16): big batches
 extern "C" __global__ void alac_decode_ab_dense_kernel(alac_decode_params p);
+// the window builds of the five above, for the calls with src_skip (only their output wave differs)
+extern "C" __global__ void alac_decode_ab_win_kernel(alac_decode_params p);
+extern "C" __global__ void alac_decode_ab5_win_kernel(alac_decode_params p);
+extern "C" __global__ void alac_decode_ab_small_win_kernel(alac_decode_params p);
+extern "C" __global__ void alac_decode_ab32_win_kernel(alac_decode_params p);
+extern "C" __global__ void alac_decode_ab_dense_win_kernel(alac_decode_params p);
 // destination mode only, behind the launch pair: the zeros of every run (frames past a packet's decoded ones, the whole run of
 // a packet that failed)
 extern "C" __global__ void alac_dst_fill_kernel(alac_decode_params p);
+// window calls only, in front of the launch pair: first[p] = dst_first[p], or ~0 (a run that never fits) where src_skip[p] > 16384
+extern "C" __global__ void alac_window_first_kernel(const uint64_t* dst_first, const uint32_t* src_skip, uint64_t* first,
+                                                    uint32_t n_packets);
 #endif
 
 #endif

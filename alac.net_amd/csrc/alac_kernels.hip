@@ -27,12 +27,19 @@ namespace {
 // Output store of sample i, channel c.  Slot layout (dst_first null): out_format 0 the canonical int32 per sample; out_format 1
 // what AlacContext.Read hands out -- FormatSamples (AlacContext.cs:214-256) fused into the store: 16-bit streams the low 16 bits
 // little-endian (:231-242), 24-bit streams the three bytes of the sample (:244-252 over the byte-per-int layout).
-// Destination mode (alac_decode_params::dst_first): `out` already points at the packet's frame 0 of channel 0, frames from
-// dst_lim on are not stored; int32 or float32 sample * 2^-(ss-1) (exact: |sample| <= 2^23).
+// Destination mode (alac_decode_params::dst_first): `out` points where the packet's frame 0 of channel 0 would go (its
+// destination frame 0, moved back by the skip in the window builds); frames from dst_lim on are not stored.  The window builds
+// (WIN, the *_win kernels: calls with src_skip) pack the window into the same register: dst_lim = end << 16 | skip (end =
+// skip + frames, at most 32768; i < 16384), and frame i is stored when skip <= i < end -- i in both halves minus dst_lim
+// leaves the sign of i - skip in bit 15 and that of i - end (less the low half's borrow) in bit 31.  (Two separate bounds
+// cost the dense arrangement 16 B/lane more scratch: the compiler keeps both live across the loops.  The window test in the
+// plain builds, behind a uniform branch, doubled their SGPR spills and cost calls without a skip 1.5 .. 3 %: hence two
+// builds.)  int32 or float32 sample * 2^-(ss-1) (exact: |sample| <= 2^23).
+template <bool WIN>
 __device__ __forceinline__ void store_sample(const alac_decode_params& p, const Meta& m, int32_t* out, uint32_t dst_lim, int i,
                                              int c, int val) {
     if (__builtin_expect(p.dst_first != nullptr, 0)) {
-        if ((uint32_t)i >= dst_lim) return;
+        if (WIN ? (((uint32_t)i * 0x10001u - dst_lim) & 0x80008000u) != 0x80000000u : (uint32_t)i >= dst_lim) return;
         const int64_t idx = p.layout ? (int64_t)c * (int64_t)p.plane_stride + i : (int64_t)i * p.channels + c;
         if (p.dtype) reinterpret_cast<float*>(out)[idx] = (float)val * (m.ss == 16 ? 0x1p-15f : 0x1p-23f);
         else out[idx] = val;
@@ -827,7 +834,7 @@ struct AbRefill {
 // Two lane -> stream mappings live here: the FIR wave's (lane 2 j + par of a row holds out[last - j] of stream 2 row + par),
 // for the queue of reconstructed samples, and a linear one (stream lane & 7, sample lane >> 3; or the other way round, QROWS) for the conversion of the code
 // values and for the ring refill.
-template <int NS>
+template <int NS, bool WIN>
 struct AbOutBlock {
     const alac_decode_params& p;
     AbSharedT<NS>& sh;
@@ -835,8 +842,8 @@ struct AbOutBlock {
     Meta m;
     int n_out, bias;
     bool two_pass;
-    int32_t* pcm_slot;      // destination mode: the packet's frame 0 of channel 0 in the destination
-    uint32_t dst_lim;       // destination mode: dst_frames of the packet (frames from here on are not stored)
+    int32_t* pcm_slot;      // destination mode: where the packet's frame 0 of channel 0 would go (dst_first - src_skip)
+    uint32_t dst_lim;       // destination mode: dst_frames; WIN: (src_skip + dst_frames) << 16 | src_skip (store_sample)
     int32_t* park;
     AbRefill<NS> rf;
     int a_next[AB_CHUNK / 8];
@@ -858,8 +865,17 @@ struct AbOutBlock {
         dst_lim = 0;
         if (p.dst_first && valid) {
             const uint64_t f0 = p.dst_first[pkt];
-            pcm_slot = p.pcm_out + (p.layout ? f0 : f0 * p.channels);
-            dst_lim = p.dst_frames[pkt];
+            if constexpr (WIN) {
+                // a skip above 16384 is status ALACGPU_ST_DEST_RANGE_D (nothing is stored), and no frame past 16384 is
+                // decoded: skip and end fit the 16-bit halves.  Only frames of the window are stored, at dst_first or behind it.
+                const uint32_t skip = p.src_skip[pkt];
+                const int64_t f = (int64_t)f0 - (int64_t)skip;
+                pcm_slot = p.pcm_out + (p.layout ? f : f * (int64_t)p.channels);
+                dst_lim = ((skip + min(p.dst_frames[pkt], (uint32_t)BUFFER_SIZE)) << 16) | skip;
+            } else {
+                pcm_slot = p.pcm_out + (p.layout ? f0 : f0 * p.channels);
+                dst_lim = p.dst_frames[pkt];
+            }
         }
         park = p.park ? p.park + (int64_t)pkt * p.park_stride : pcm_slot + m.n;
 #pragma unroll
@@ -924,16 +940,16 @@ struct AbOutBlock {
                         const uint32_t bp = m.rawbit + (uint32_t)((i * nch + ch) * m.ss);
                         int val = __builtin_amdgcn_sbfe((int)peek_bits(m.base, m.limit, bp, m.ss), 0, m.ss);
                         if (m.ss == 24) val = __builtin_amdgcn_sbfe(val, 0, 24);
-                        if (ch < m.nc) store_sample(p, m, pcm_slot, dst_lim, i, ch, val);
+                        if (ch < m.nc) store_sample<WIN>(p, m, pcm_slot, dst_lim, i, ch, val);
                     }
-                    if (!m.stereo && m.nc > 1) store_sample(p, m, pcm_slot, dst_lim, i, 1, 0);
+                    if (!m.stereo && m.nc > 1) store_sample<WIN>(p, m, pcm_slot, dst_lim, i, 1, 0);
                 } else {
                     const int i = ih + cnt - 1 - j;
                     if (two_pass) {
                         park[i] = mine;
                     } else {                                            // one channel: done
-                        store_sample(p, m, pcm_slot, dst_lim, i, 0, ab_finish24<UB_AHEAD>(m, ub_cur[half], mine, i, 0));
-                        if (m.nc > 1) store_sample(p, m, pcm_slot, dst_lim, i, 1, 0);
+                        store_sample<WIN>(p, m, pcm_slot, dst_lim, i, 0, ab_finish24<UB_AHEAD>(m, ub_cur[half], mine, i, 0));
+                        if (m.nc > 1) store_sample<WIN>(p, m, pcm_slot, dst_lim, i, 1, 0);
                     }
                 }
             }
@@ -974,19 +990,19 @@ struct AbOutBlock {
                     left = a;
                     right = bb;
                 }
-                store_sample(p, m, pcm_slot, dst_lim, i, 0, ab_finish24<UB_AHEAD>(m, ub_cur[half], left, i, 0));
-                if (m.nc > 1) store_sample(p, m, pcm_slot, dst_lim, i, 1, ab_finish24<UB_AHEAD>(m, ub_cur[half], right, i, 1));
+                store_sample<WIN>(p, m, pcm_slot, dst_lim, i, 0, ab_finish24<UB_AHEAD>(m, ub_cur[half], left, i, 0));
+                if (m.nc > 1) store_sample<WIN>(p, m, pcm_slot, dst_lim, i, 1, ab_finish24<UB_AHEAD>(m, ub_cur[half], right, i, 1));
             }
         }
         if (b < nch1) rf.commit();
     }
 };
 
-template <int NS>
+template <int NS, bool WIN>
 __device__ __forceinline__ void ab_output_wave(const alac_decode_params& p, uint32_t pkt0, int lane, AbSharedT<NS>& sh, int nch0, int nch1) {
-    AbOutBlock<NS> b0(p, pkt0, 0, lane, sh);
+    AbOutBlock<NS, WIN> b0(p, pkt0, 0, lane, sh);
     if constexpr (NS == 16) {
-        AbOutBlock<NS> b1(p, pkt0, 1, lane, sh);
+        AbOutBlock<NS, WIN> b1(p, pkt0, 1, lane, sh);
         for (int b = 0; b <= nch0 + 1; b++) {
             wg_sync();
             b0.pass0_step(b, nch0);
@@ -1027,7 +1043,8 @@ __device__ __forceinline__ void ab_fir_role(const alac_decode_params& p, uint32_
 //   0  first launch, dense arrangement (NS == 16): orders 1..16, one or two taps per lane per FIR wave; others flagged
 //   2  second launch: the groups flagged 3 (some stream with 9..16 taps): two taps per lane
 //   4  second launch: the groups flagged 1 (any order, the delta mode, order 0): four taps per lane
-template <int TSEL, int NS = 8>
+// WIN: the window build (alac_decode_params::src_skip non-null; the *_win kernels), only the output wave differs.
+template <int TSEL, int NS = 8, bool WIN = false>
 __device__ __forceinline__ void ab_kernel_body(const alac_decode_params& p, AbSharedT<NS>& sh) {
     static_assert((TSEL == 0) == (NS == 16), "the dense arrangement exists for the first launch only");
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1121,7 +1138,7 @@ __device__ __forceinline__ void ab_kernel_body(const alac_decode_params& p, AbSh
         __builtin_amdgcn_s_setprio(ALAC_ENTROPY_PRIO);
         ab_entropy_wave<NS>(p, pkt0, lane, sh, nch0, nch1);
     } else if (role == 1) {
-        ab_output_wave<NS>(p, pkt0, lane, sh, nch0, nch1);
+        ab_output_wave<NS, WIN>(p, pkt0, lane, sh, nch0, nch1);
     } else {
         __builtin_amdgcn_s_setprio(1);   // above the output waves, below the entropy waves (8192 packets: 1.074 -> 1.048 ms, cfg3 3.33 -> 3.25)
         const int w = role - 2;
@@ -1150,6 +1167,11 @@ extern "C" __global__ __launch_bounds__(256, 4) void alac_decode_ab_kernel(alac_
     __shared__ __attribute__((aligned(1024))) AbSharedT<8> sh;
     ab_kernel_body<1>(p, sh);
 }
+// Every decode kernel has a window build (*_win) for the calls with src_skip, launched in its place (alacgpu_api.hip: launch)
+extern "C" __global__ __launch_bounds__(256, 4) void alac_decode_ab_win_kernel(alac_decode_params p) {
+    __shared__ __attribute__((aligned(1024))) AbSharedT<8> sh;
+    ab_kernel_body<1, 8, true>(p, sh);
+}
 #endif
 #if !defined(ALAC_EMIT) || ALAC_EMIT == 5
 // The same as alac_decode_ab_kernel, its object compiled with speculative units of 16 steps (-DALAC_SPEC_UNIT=16), for batches
@@ -1160,6 +1182,10 @@ extern "C" __global__ __launch_bounds__(256, 4) void alac_decode_ab_small_kernel
     __shared__ __attribute__((aligned(1024))) AbSharedT<8> sh;
     ab_kernel_body<1>(p, sh);
 }
+extern "C" __global__ __launch_bounds__(256, 4) void alac_decode_ab_small_win_kernel(alac_decode_params p) {
+    __shared__ __attribute__((aligned(1024))) AbSharedT<8> sh;
+    ab_kernel_body<1, 8, true>(p, sh);
+}
 #endif
 #if !defined(ALAC_EMIT) || ALAC_EMIT == 4
 // The same with 96 registers, for the batches in between (10241 .. 12288 packets): five workgroups per CU instead of four
@@ -1167,6 +1193,10 @@ extern "C" __global__ __launch_bounds__(256, 4) void alac_decode_ab_small_kernel
 extern "C" __global__ __launch_bounds__(256, 5) void alac_decode_ab5_kernel(alac_decode_params p) {
     __shared__ __attribute__((aligned(1024))) AbSharedT<8> sh;
     ab_kernel_body<1>(p, sh);
+}
+extern "C" __global__ __launch_bounds__(256, 5) void alac_decode_ab5_win_kernel(alac_decode_params p) {
+    __shared__ __attribute__((aligned(1024))) AbSharedT<8> sh;
+    ab_kernel_body<1, 8, true>(p, sh);
 }
 #endif
 #if !defined(ALAC_EMIT) || ALAC_EMIT == 2
@@ -1177,10 +1207,17 @@ extern "C" __global__ __launch_bounds__(256) void alac_decode_ab32_kernel(alac_d
     if (f == 1u) ab_kernel_body<4>(p, sh);
     else if (f == 3u) ab_kernel_body<2>(p, sh);
 }
-// Destination mode, behind the launch pair (the statuses are final): the zeros of every run -- frames from a packet's decoded
-// ones up to dst_frames, and the whole run of a packet that failed.  Kept are the samples of an OK packet and of a one-channel
-// element with an unknown prediction type (its un-predicted residuals, status 3 as a warning: AlacFile.cs:484-496); a packet
-// with status ALACGPU_ST_DEST_RANGE_D writes nothing.  One wave per packet; nothing to do for the common packet.
+extern "C" __global__ __launch_bounds__(256) void alac_decode_ab32_win_kernel(alac_decode_params p) {
+    __shared__ __attribute__((aligned(1024))) AbSharedT<8> sh;
+    const uint32_t f = p.ab_flags ? p.ab_flags[blockIdx.x] : 1u;
+    if (f == 1u) ab_kernel_body<4, 8, true>(p, sh);
+    else if (f == 3u) ab_kernel_body<2, 8, true>(p, sh);
+}
+// Destination mode, behind the launch pair (the statuses are final): the zeros of every run -- the window's frames past a
+// packet's decoded ones (frames max(skip, decoded) .. skip + dst_frames, at destination frames from - skip on), and the whole
+// run of a packet that failed.  Kept are the samples of an OK packet and of a one-channel element with an unknown prediction
+// type (its un-predicted residuals, status 3 as a warning: AlacFile.cs:484-496); a packet with status ALACGPU_ST_DEST_RANGE_D
+// writes nothing.  One wave per packet; nothing to do for the common packet.
 extern "C" __global__ __launch_bounds__(256) void alac_dst_fill_kernel(alac_decode_params p) {
     const uint32_t pkt = blockIdx.x * 4u + (threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63u;
@@ -1190,8 +1227,10 @@ extern "C" __global__ __launch_bounds__(256) void alac_dst_fill_kernel(alac_deco
     alacgpu_cfg_dev cfg;
     const Meta m = parse_meta(p, pkt, 0, true, cfg);
     const uint32_t lim = p.dst_frames[pkt];
+    const uint32_t skip = p.src_skip ? p.src_skip[pkt] : 0u;   // (at most 16384: else the status is ALACGPU_ST_DEST_RANGE_D)
     const bool kept = st == ALACGPU_ST_OK_D || (st == ALACGPU_ST_UNSUPPORTED_PREDTYPE_D && !m.stereo);
-    const uint32_t from = kept ? min((uint32_t)max(m.n, 0), lim) : 0u;
+    // the first destination frame the decode did not store: past the decoded frames (none when the window starts there)
+    const uint32_t from = kept ? min((uint32_t)max(m.n - (int)skip, 0), lim) : 0u;
     if (from >= lim) return;
     const uint64_t f0 = p.dst_first[pkt];
     int32_t* const out = p.pcm_out;   // (int32 0 and float32 +0.0 are the same bits)
@@ -1203,6 +1242,14 @@ extern "C" __global__ __launch_bounds__(256) void alac_dst_fill_kernel(alac_deco
         for (uint64_t e = (f0 + from) * p.channels + lane; e < e1; e += 64u) out[e] = 0;
     }
 }
+// Window calls, in front of the launch pair: the launch's own copy of dst_first, with ~0 -- a run that never fits, so
+// parse_meta gives every role status ALACGPU_ST_DEST_RANGE_D -- where the skip exceeds the longest frame.  (Reading src_skip
+// in parse_meta instead cost every call 0.3 %, the slot layout's too: two more scalar registers in all the roles.)
+extern "C" __global__ __launch_bounds__(256) void alac_window_first_kernel(const uint64_t* dst_first, const uint32_t* src_skip,
+                                                                          uint64_t* first, uint32_t n_packets) {
+    const uint32_t pkt = blockIdx.x * 256u + threadIdx.x;
+    if (pkt < n_packets) first[pkt] = src_skip[pkt] > (uint32_t)BUFFER_SIZE ? ~0ull : dst_first[pkt];
+}
 #endif
 #if !defined(ALAC_EMIT) || ALAC_EMIT == 3
 // The dense arrangement for big batches: 16 packets per 256-thread workgroup: one entropy wave for all 16 streams (4 lanes
@@ -1212,5 +1259,9 @@ extern "C" __global__ __launch_bounds__(256) void alac_dst_fill_kernel(alac_deco
 extern "C" __global__ __launch_bounds__(256, 4) void alac_decode_ab_dense_kernel(alac_decode_params p) {
     __shared__ __attribute__((aligned(1024))) AbSharedT<16> sh;
     ab_kernel_body<0, 16>(p, sh);
+}
+extern "C" __global__ __launch_bounds__(256, 4) void alac_decode_ab_dense_win_kernel(alac_decode_params p) {
+    __shared__ __attribute__((aligned(1024))) AbSharedT<16> sh;
+    ab_kernel_body<0, 16, true>(p, sh);
 }
 #endif

@@ -41,6 +41,8 @@ struct launch_slot {
     size_t flags_bytes = 0;
     int32_t* d_park = nullptr;     // destination mode: where channel A waits (n_packets * park_stride ints, grown on demand)
     size_t park_bytes = 0;
+    uint64_t* d_first = nullptr;   // window calls: dst_first as alac_window_first_kernel leaves it (n_packets, grown on demand)
+    size_t first_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool used = false;
 };
@@ -158,6 +160,15 @@ const void* first_kernel(const alacgpu_ctx* ctx, uint32_t n_packets) {
     }
 }
 
+// A kernel's window build (calls with src_skip): the same kernel with the window test in its output wave's stores.
+const void* window_build(const void* k) {
+    if (k == (const void*)alac_decode_ab_dense_kernel) return (const void*)alac_decode_ab_dense_win_kernel;
+    if (k == (const void*)alac_decode_ab5_kernel) return (const void*)alac_decode_ab5_win_kernel;
+    if (k == (const void*)alac_decode_ab_small_kernel) return (const void*)alac_decode_ab_small_win_kernel;
+    if (k == (const void*)alac_decode_ab32_kernel) return (const void*)alac_decode_ab32_win_kernel;
+    return (const void*)alac_decode_ab_win_kernel;
+}
+
 // The two-pass kernels: the first launch decodes the groups of 8 packets whose streams have LPC order 1..8 (the dense
 // arrangement: 1..16) and flags the others for the second launch right behind it on the same stream (two or four taps per
 // lane of the FIR wave).  A two-channel element needs room for parking channel A in its slot (2 n <= slot_ints): parse_meta
@@ -185,13 +196,29 @@ int launch(alacgpu_ctx* ctx, const alac_decode_params& p_in, hipStream_t stream)
         if ((rc = grow(ctx, sl.d_park, sl.park_bytes, sizeof(int32_t) * want, sizeof(int32_t) * (want + want / 4)))) return rc;
         p.park = sl.d_park;
     }
+    if (p.src_skip) {    // window call: a skip past the longest frame becomes a run that does not fit (status ALACGPU_ST_DEST_RANGE)
+        const size_t want = p.n_packets;
+        if ((rc = grow(ctx, sl.d_first, sl.first_bytes, sizeof(uint64_t) * want, sizeof(uint64_t) * (want + want / 4)))) return rc;
+    }
     HIP_TRY(ctx, hipEventRecord(sl.ev0, stream));
+    if (p.src_skip) {
+        const uint64_t* src_first = p.dst_first;
+        void* wargs[] = {&src_first, &p.src_skip, &sl.d_first, &p.n_packets};
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_window_first_kernel, dim3((p.n_packets + 255u) / 256u), dim3(256), wargs, 0,
+                                     stream));
+        p.dst_first = sl.d_first;
+    }
     alac_decode_params args = p;
     void* kargs[] = {&args};
     const void* k = first_kernel(ctx, p.n_packets);   // (the dense arrangement: two groups of 8 per workgroup)
     const size_t first_groups = k == (const void*)alac_decode_ab_dense_kernel ? (groups + 1) / 2 : groups;
+    const void* k2 = (const void*)alac_decode_ab32_kernel;
+    if (p.src_skip) {    // window calls: the window builds of both launches (the plain builds carry no window test)
+        k = window_build(k);
+        k2 = window_build(k2);
+    }
     HIP_TRY(ctx, hipLaunchKernel(k, dim3((uint32_t)first_groups), dim3(256), kargs, 0, stream));
-    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_decode_ab32_kernel, dim3((uint32_t)groups), dim3(256), kargs, 0, stream));
+    HIP_TRY(ctx, hipLaunchKernel(k2, dim3((uint32_t)groups), dim3(256), kargs, 0, stream));
     if (p.dst_first)
         HIP_TRY(ctx, hipLaunchKernel((const void*)alac_dst_fill_kernel, dim3((p.n_packets + 3u) / 4u), dim3(256), kargs, 0, stream));
     HIP_TRY(ctx, hipGetLastError());
@@ -369,6 +396,7 @@ void alacgpu_destroy(alacgpu_ctx* ctx) {
         if (sl.used) (void)hipEventSynchronize(sl.ev1);   // device-pointer calls on the caller's streams
         if (sl.d_flags) (void)hipFree(sl.d_flags);
         if (sl.d_park) (void)hipFree(sl.d_park);
+        if (sl.d_first) (void)hipFree(sl.d_first);
         if (sl.ev0) (void)hipEventDestroy(sl.ev0);
         if (sl.ev1) (void)hipEventDestroy(sl.ev1);
     }
@@ -430,12 +458,14 @@ int alacgpu_dbg_decode_batch_device_stamps(alacgpu_ctx* ctx, const void* d_blob,
 }
 #endif
 
-int alacgpu_decode_into_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t blob_bytes, const void* d_offsets,
-                               const void* d_sizes, const void* d_cfg_idx, uint32_t n_packets, const void* d_dst_first,
-                               const void* d_dst_frames, void* d_out, uint64_t out_elems, uint32_t channels, int layout, int dtype,
-                               uint64_t plane_stride, void* d_out_samples, void* d_status, void* hip_stream) {
+int alacgpu_decode_window_into_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t blob_bytes, const void* d_offsets,
+                                      const void* d_sizes, const void* d_cfg_idx, uint32_t n_packets, const void* d_dst_first,
+                                      const void* d_dst_frames, const void* d_src_skip, void* d_out, uint64_t out_elems,
+                                      uint32_t channels, int layout, int dtype, uint64_t plane_stride, void* d_out_samples,
+                                      void* d_status, void* hip_stream) {
     if (!ctx || !d_dst_first || !d_dst_frames || !pcm_view_ok(d_out, channels, layout, dtype, plane_stride)) return ALACGPU_ERR_BAD_ARG;
-    if (((uintptr_t)d_dst_first & 7u) != 0 || ((uintptr_t)d_dst_frames & 3u) != 0) return ALACGPU_ERR_BAD_ARG;
+    if (((uintptr_t)d_dst_first & 7u) != 0 || ((uintptr_t)d_dst_frames & 3u) != 0 || ((uintptr_t)d_src_skip & 3u) != 0)
+        return ALACGPU_ERR_BAD_ARG;
     // statuses as in the slot layout with slot_ints = channels * Smax, and channel A parks in Smax ints per packet
     const uint32_t s = smax(ctx);
     alac_decode_params p;
@@ -444,6 +474,7 @@ int alacgpu_decode_into_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t bl
     if (rc) return rc;
     p.dst_first = (const uint64_t*)d_dst_first;
     p.dst_frames = (const uint32_t*)d_dst_frames;
+    p.src_skip = (const uint32_t*)d_src_skip;
     p.out_elems = out_elems;
     p.plane_stride = layout == ALACGPU_DST_PLANAR ? plane_stride : 0;
     p.channels = channels;
@@ -451,6 +482,15 @@ int alacgpu_decode_into_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t bl
     p.dtype = (uint32_t)dtype;
     p.park_stride = s;
     return launch(ctx, p, (hipStream_t)hip_stream);
+}
+
+int alacgpu_decode_into_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t blob_bytes, const void* d_offsets,
+                               const void* d_sizes, const void* d_cfg_idx, uint32_t n_packets, const void* d_dst_first,
+                               const void* d_dst_frames, void* d_out, uint64_t out_elems, uint32_t channels, int layout, int dtype,
+                               uint64_t plane_stride, void* d_out_samples, void* d_status, void* hip_stream) {
+    return alacgpu_decode_window_into_device(ctx, d_blob, blob_bytes, d_offsets, d_sizes, d_cfg_idx, n_packets, d_dst_first,
+                                             d_dst_frames, nullptr, d_out, out_elems, channels, layout, dtype, plane_stride,
+                                             d_out_samples, d_status, hip_stream);
 }
 
 size_t alacgpu_encode_max_packet_bytes(uint32_t frames, int sample_size, int channels) {

@@ -210,6 +210,25 @@ int alacgpu_decode_into_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t bl
                                void* d_out_samples, void* d_status, void* hip_stream);
 
 /*
+ * A window of every packet (no counterpart in the reference): alacgpu_decode_into_device, with packet p's run starting
+ * d_src_skip[p] frames into the packet -- what a crop of a file at any frame offset needs for the packet it starts in.
+ *   d_src_skip[p]    uint32, 4-byte aligned: frames i with d_src_skip[p] <= i < d_src_skip[p] + d_dst_frames[p] form the run;
+ *                    frame i, channel c goes to frame d_dst_first[p] + (i - d_src_skip[p]) in either layout.  A skip above
+ *                    16384 (the longest frame) is status ALACGPU_ST_DEST_RANGE.  NULL: no skip -- exactly
+ *                    alacgpu_decode_into_device, which is this entry point with NULL.
+ * Every element of a packet's run is written unless its status is ALACGPU_ST_DEST_RANGE: the decoded frames of the window, then
+ * zeros (for the window's frames past the packet's decoded ones); a packet that fails gets a run of zeros.  Statuses and
+ * d_out_samples[p] are those of alacgpu_decode_into_device (but for a skip above 16384): the whole packet is decoded, the
+ * skip only chooses what is stored.  With a skip array the ctx keeps n_packets uint64 more scratch per call in flight (kept for
+ * reuse).  ALACGPU_ERR_BAD_ARG as for alacgpu_decode_into_device, and for a misaligned d_src_skip.
+ */
+int alacgpu_decode_window_into_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t blob_bytes, const void* d_offsets,
+                                      const void* d_sizes, const void* d_cfg_idx, uint32_t n_packets,
+                                      const void* d_dst_first, const void* d_dst_frames, const void* d_src_skip,
+                                      void* d_out, uint64_t out_elems, uint32_t channels, int layout, int dtype,
+                                      uint64_t plane_stride, void* d_out_samples, void* d_status, void* hip_stream);
+
+/*
  * Encoder (no counterpart in the reference, which only decodes): PCM in HBM to ALAC packets in HBM, one packet per run of
  * frames, asynchronous on hip_stream.  Device pointers; d_pcm 4-byte, d_src_first 8-byte, d_packets 16-byte aligned.
  *   d_pcm            src_elems int32 (ALACGPU_DST_INT32: the canonical sample, clamped to the sample range) or float32

@@ -60,6 +60,8 @@ SYMBOLS = {
                                              C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP]),
     "alacgpu_decode_window_into_device": (C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP,
                                                     C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP]),
+    "alacgpu_plan_crops_device": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_uint32, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            C.c_uint64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alacgpu_encode_max_packet_bytes": (C.c_size_t, [C.c_uint32, C.c_int, C.c_int]),
     "alacgpu_encode_device": (C.c_int, [_VP, _VP, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP, C.c_uint32,
                                         _VP, C.c_uint64, _VP, _VP, _VP]),
@@ -821,3 +823,7 @@ class AlacFile:
         if self._ctx is not None:
             self._ctx.close()
             self._ctx = None
+
+
+# ---- a corpus resident in HBM and its random crops (alacgpu_plan_crops_device) -----------------------------------------------------
+from .corpus import Corpus, corpus_plan_host, corpus_tables, entries_per_crop  # noqa: E402  (it imports the names above)

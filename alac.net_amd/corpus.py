@@ -1,0 +1,366 @@
+"""A corpus of M4A files kept compressed in HBM, and random crops of it decoded without host work per step.
+
+`Corpus` demuxes every file once, uploads the packet bytes and the packet tables once and keeps one alacgpu_ctx.  A step,
+`crops(files, frame_offsets, num_frames)`, is two calls: alacgpu_plan_crops_device (the kernel of csrc/alac_corpus.hip does
+`window_plan` for every crop against the resident tables) and alacgpu_decode_window_into_device over the plan it wrote.  The
+host hands over (file, first frame) pairs -- or nothing at all when they are device tensors already.
+
+`corpus_tables` (the resident tables as numpy arrays), `entries_per_crop` (the K bound) and `corpus_plan_host` (the kernel's
+specification in numpy) need no device.
+"""
+import numpy as np
+
+from . import (MAX_FRAME, ST_OK, ST_UNSUPPORTED_ELEMENT, ST_UNSUPPORTED_PREDTYPE, AlacGpuContext, AlacGpuError, _Closing, _check,
+               _dp, _frame_count, _status_text, _torch_dtype, _VP, lib)
+
+PAD_CFG = 0xFFFF        # a padding entry's cfg_idx: never a row of the context, so the kernels switch the entry off
+MAX_CFGS = 65535
+
+
+def corpus_tables(tables):
+    """The resident tables of a corpus from its files' packet tables (dicts with sizes, durations, cfg, num_channels and
+    sample_rate, as container.packet_table returns them; the packet bytes are not looked at).  The packets of all files lie
+    back to back.  Returns a dict of numpy arrays: pkt_offset[P] uint64 (into the blob), pkt_size[P] uint32, pkt_end[P] uint64
+    (inclusive prefix sum of the durations within the packet's file), file_first[F + 1] uint32, file_cfg[F] uint16 (rows of
+    cfgs), cfgs (the distinct alacgpu_cfg rows), num_frames[F] int64, file_base[F + 1] uint64 (where a file's bytes start),
+    and channels, sample_rate, blob_bytes.  ValueError: no files, a file whose channel count or sample rate differs from the
+    first's, more than 65535 distinct stream cfgs, 2^32 packets or more."""
+    from . import CFG_DTYPE
+
+    if not len(tables):
+        raise ValueError("no sources")
+    channels, rate = int(tables[0]["num_channels"]), int(tables[0]["sample_rate"])
+    for i, t in enumerate(tables):
+        if int(t["num_channels"]) != channels or int(t["sample_rate"]) != rate:
+            raise ValueError(f"source {i}: {t['num_channels']} channels at {t['sample_rate']} Hz, the first has {channels} at {rate} Hz")
+    counts = np.array([len(t["sizes"]) for t in tables], dtype=np.int64)
+    if int(counts.sum()) >= 1 << 32:
+        raise ValueError(f"{int(counts.sum())} packets: a corpus holds fewer than 2^32")
+    file_first = np.zeros(len(tables) + 1, dtype=np.uint32)
+    file_first[1:] = np.cumsum(counts)
+    sizes = np.concatenate([np.asarray(t["sizes"], dtype=np.uint32) for t in tables])
+    ends = np.concatenate([np.cumsum(np.asarray(t["durations"], dtype=np.int64)) for t in tables]).astype(np.uint64)
+    pkt_offset = np.zeros(len(sizes), dtype=np.uint64)
+    if len(sizes) > 1:
+        pkt_offset[1:] = np.cumsum(sizes[:-1], dtype=np.uint64)
+    blob_bytes = int(sizes.sum(dtype=np.uint64))
+    file_base = np.concatenate([pkt_offset, [blob_bytes]]).astype(np.uint64)[file_first]
+    rows = np.concatenate([np.ascontiguousarray(t["cfg"], dtype=CFG_DTYPE).reshape(-1)[:1] for t in tables])
+    uniq, inverse = np.unique(rows.view(np.uint8).reshape(-1, CFG_DTYPE.itemsize), axis=0, return_inverse=True)
+    if len(uniq) > MAX_CFGS:
+        raise ValueError(f"{len(uniq)} distinct stream cfgs: a corpus holds at most {MAX_CFGS}")
+    num_frames = np.array([int(np.sum(np.asarray(t["durations"], dtype=np.int64))) for t in tables], dtype=np.int64)
+    return dict(pkt_offset=pkt_offset, pkt_size=sizes, pkt_end=ends, file_first=file_first,
+                file_cfg=np.asarray(inverse).reshape(-1).astype(np.uint16), cfgs=np.ascontiguousarray(uniq).view(CFG_DTYPE).reshape(-1),
+                num_frames=num_frames, file_base=file_base, channels=channels, sample_rate=rate, blob_bytes=blob_bytes)
+
+
+def entries_per_crop(pkt_end, file_first, num_frames):
+    """K(L): the most packets a window of num_frames frames takes in any file (the largest p1 - p0 of window_plan over every
+    offset), exact.  Inside the packet a window starts in, p0 is fixed and p1 grows with the offset, so the window from that
+    packet's last frame reaches furthest; a window from frame 0 starts at packet 0 whatever the durations.  Files of one frame
+    length fl: ceil((L - 1) / fl) + 1 when the file is long enough."""
+    pkt_end = np.asarray(pkt_end).astype(np.int64)
+    file_first = np.asarray(file_first).astype(np.int64)
+    L = int(num_frames)
+    F = len(file_first) - 1
+    if L <= 0 or len(pkt_end) == 0:
+        return 0
+    counts = np.diff(file_first)
+    file_of = np.repeat(np.arange(F, dtype=np.int64), counts)
+    local = np.arange(len(pkt_end), dtype=np.int64) - file_first[file_of]
+    start = np.where(local == 0, 0, np.concatenate([[0], pkt_end[:-1]]))
+    total = np.zeros(F, dtype=np.int64)
+    total[counts > 0] = pkt_end[file_first[1:][counts > 0] - 1]
+    # the candidate windows: from the last frame of every packet that has frames, and from frame 0 of every file
+    has = pkt_end > start
+    o = np.concatenate([pkt_end[has] - 1, np.zeros(F, dtype=np.int64)])
+    f = np.concatenate([file_of[has], np.arange(F, dtype=np.int64)])
+    p0 = np.concatenate([local[has], np.zeros(F, dtype=np.int64)])
+    p0 = np.where(o == 0, 0, p0)
+    end = np.minimum(o + L, total[f])
+    # p1: the file's packets that start in front of `end` -- one search over all files' starts, a file's keyed behind the last's
+    M = int(total.max()) + 2
+    if F * M < 1 << 62:
+        p1 = np.searchsorted(file_of * M + start, f * M + end, side="left") - file_first[f]
+    else:
+        p1 = np.array([np.searchsorted(start[file_first[k]:file_first[k + 1]], e, side="left") for k, e in zip(f, end)], dtype=np.int64)
+    return int(np.maximum(p1 - p0, 0).max())
+
+
+def corpus_plan_host(pkt_offset, pkt_size, pkt_end, file_first, file_cfg, crop_file, crop_offset, num_frames, entries, dst_stride):
+    """alacgpu_plan_crops_device on the host, in numpy: the kernel's specification (tests compare the two; `Corpus.crops` never
+    comes here).  Returns (offsets uint64, sizes uint32, cfg_idx uint16, dst_first uint64, dst_frames uint32, src_skip uint32)
+    of B * entries entries, crop-major, and lengths[B] int64: min(num_frames, T_f - offset); -1 for a file index >= F or an
+    offset > T_f; -2 for a crop that needs more than `entries` entries.  Entries behind a crop's packets are padding:
+    cfg_idx 0xFFFF and zeros."""
+    pkt_offset, pkt_size = np.asarray(pkt_offset, dtype=np.uint64), np.asarray(pkt_size, dtype=np.uint32)
+    ends_all = np.asarray(pkt_end).astype(np.int64)
+    file_first, file_cfg = np.asarray(file_first).astype(np.int64), np.asarray(file_cfg, dtype=np.uint16)
+    crop_file, crop_offset = np.asarray(crop_file, dtype=np.uint32), np.asarray(crop_offset, dtype=np.uint64)
+    B, K, L, F = len(crop_file), int(entries), int(num_frames), len(file_first) - 1
+    offsets, sizes = np.zeros(B * K, np.uint64), np.zeros(B * K, np.uint32)
+    cfg_idx = np.full(B * K, PAD_CFG, np.uint16)
+    dst_first, dst_frames, src_skip = np.zeros(B * K, np.uint64), np.zeros(B * K, np.uint32), np.zeros(B * K, np.uint32)
+    lengths = np.full(B, -1, np.int64)
+    for b in range(B):
+        f, o = int(crop_file[b]), int(crop_offset[b])
+        if f >= F:
+            continue
+        g0, g1 = int(file_first[f]), int(file_first[f + 1])
+        ends = ends_all[g0:g1]
+        total = int(ends[-1]) if g1 > g0 else 0
+        if o > total:
+            continue
+        length = min(L, total - o)
+        lengths[b] = length
+        if length == 0 or g1 == g0:
+            continue
+        end = o + length
+        starts = np.concatenate([[0], ends[:-1]])
+        p0 = 0 if o == 0 else int(np.searchsorted(ends, o, side="right"))       # the first packet that ends past o
+        p1 = max(int(np.searchsorted(starts, end, side="left")), p0)            # packets that start in front of the end
+        if p1 - p0 > K:
+            lengths[b] = -2
+            continue
+        j = slice(b * K, b * K + p1 - p0)
+        lo = np.maximum(starts[p0:p1], o)
+        offsets[j], sizes[j], cfg_idx[j] = pkt_offset[g0 + p0:g0 + p1], pkt_size[g0 + p0:g0 + p1], file_cfg[f]
+        dst_first[j] = (b * int(dst_stride) + (lo - o)).astype(np.uint64)
+        dst_frames[j] = np.maximum(np.minimum(ends[p0:p1], end) - lo, 0)
+        src_skip[j] = np.minimum(lo - starts[p0:p1], MAX_FRAME)
+    return offsets, sizes, cfg_idx, dst_first, dst_frames, src_skip, lengths
+
+
+class Corpus(_Closing):
+    """M4A files resident in HBM, compressed: Corpus(sources, device=0) demuxes every source once (file bytes, a path or a
+    seekable binary file object, as for `load`), uploads the packet bytes file by file into one device blob and the packet
+    tables next to it, and keeps one alacgpu_ctx until close().  All files share channel count and sample rate (ValueError
+    naming the first that differs); 16- and 24-bit may mix; files that share a stream cfg share its row (at most 65535
+    distinct ones).  num_files, num_frames (int64 host array [F]), channels, sample_rate.  Calls on one Corpus belong on one
+    stream: the plan arrays are reused from call to call."""
+
+    def __init__(self, sources, device=0):
+        import torch
+
+        from .container import header_table, packet_table
+
+        self._gpu = None
+        sources = list(sources)
+        # the headers first (no packet bytes): the blob's size; a file object is read twice from where it stands
+        where = [s.tell() if hasattr(s, "tell") and hasattr(s, "seek") else None for s in sources]
+        total = 0
+        for s, pos in zip(sources, where):
+            total += int(header_table(s)["sizes"].sum(dtype=np.int64))
+            if pos is not None:
+                s.seek(pos)
+        self.device = device
+        dev = self._dev = torch.device("cuda", device)
+        # readable up to blob_bytes rounded up to 16, as every decode entry point wants it (torch's allocations are aligned)
+        self._blob = torch.zeros(total + 64, dtype=torch.uint8, device=dev)
+        heads, base = [], 0
+        for s in sources:
+            t = packet_table(s)
+            n = int(t["sizes"].sum(dtype=np.int64))
+            if n:
+                self._blob[base:base + n].copy_(torch.from_numpy(np.array(t["blob"][:n])))
+            base += n
+            heads.append({k: t[k] for k in ("sizes", "durations", "cfg", "num_channels", "sample_rate")})
+        if base != total:
+            raise ValueError("a source changed while it was read")
+        tb = corpus_tables(heads)
+        self.num_files = len(heads)
+        self.num_frames = tb["num_frames"]
+        self.channels, self.sample_rate = tb["channels"], tb["sample_rate"]
+        self._host = tb
+        self._blob_bytes = tb["blob_bytes"]
+
+        def up(a, dtype):      # (an empty table still needs an address)
+            a = a.view(dtype)
+            return torch.from_numpy(a if len(a) else np.zeros(1, dtype)).to(dev)
+
+        self._pkt_offset, self._pkt_size = up(tb["pkt_offset"], np.int64), up(tb["pkt_size"], np.int32)
+        self._pkt_end, self._file_first = up(tb["pkt_end"], np.int64), up(tb["file_first"], np.int32)
+        self._file_cfg = up(tb["file_cfg"], np.int16)
+        self._d_num_frames = torch.from_numpy(self.num_frames).to(dev)
+        self._K = {}
+        self._plan, self._capacity, self._last = None, 0, 0
+        self._gpu = AlacGpuContext(tb["cfgs"], device)
+
+    def close(self):
+        if getattr(self, "_gpu", None) is not None:
+            self._gpu.close()
+            self._gpu = None
+            self._blob = self._plan = None
+
+    def entries_per_crop(self, num_frames):
+        """K for crops of num_frames frames: the entries the plan reserves per crop (computed once per length)."""
+        L = int(num_frames)
+        if L not in self._K:
+            self._K[L] = max(entries_per_crop(self._host["pkt_end"], self._host["file_first"], L), 1)
+        return self._K[L]
+
+    def _plan_arrays(self, n):
+        """The six plan arrays and the status array, kept and reused while n does not grow past them."""
+        import torch
+
+        if n > self._capacity:
+            dev, cap = self._dev, n
+            self._plan = None       # (the old ones go first)
+            self._plan = dict(offsets=torch.empty(cap, dtype=torch.int64, device=dev), sizes=torch.empty(cap, dtype=torch.int32, device=dev),
+                              cfg_idx=torch.empty(cap, dtype=torch.int16, device=dev), dst_first=torch.empty(cap, dtype=torch.int64, device=dev),
+                              dst_frames=torch.empty(cap, dtype=torch.int32, device=dev), src_skip=torch.empty(cap, dtype=torch.int32, device=dev),
+                              status=torch.empty(cap, dtype=torch.int32, device=dev), iota=torch.arange(cap, dtype=torch.int64, device=dev))
+            self._capacity = cap
+        return self._plan
+
+    def _indices(self, files, frame_offsets):
+        """The crops' (file, first frame) as device tensors (int32 / int64: the kernel reads them as unsigned) and whether they
+        came from the host (and are checked here) or were device tensors already (and are checked by the kernel)."""
+        import torch
+
+        on_device = [isinstance(x, torch.Tensor) and x.device.type == "cuda" for x in (files, frame_offsets)]
+        if all(on_device):
+            if files.dim() != 1 or frame_offsets.dim() != 1 or files.shape != frame_offsets.shape:
+                raise ValueError(f"files {tuple(files.shape)} and frame_offsets {tuple(frame_offsets.shape)} must be two vectors of one length")
+            if files.dtype.is_floating_point or frame_offsets.dtype.is_floating_point:
+                raise ValueError("files and frame_offsets must be integer tensors")
+            f = files if files.dtype == torch.int32 else files.clamp(-1, (1 << 31) - 1).to(torch.int32)
+            return f.to(self._dev).contiguous(), frame_offsets.to(self._dev, torch.int64).contiguous(), False
+        as_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        f, o = as_np(files), as_np(frame_offsets)
+        if f.ndim != 1 or o.ndim != 1 or len(f) != len(o):
+            raise ValueError(f"{f.shape} files and {o.shape} frame offsets: two sequences of one length")
+        if len(f) and (f.dtype.kind not in "iu" or o.dtype.kind not in "iu"):
+            raise ValueError("files and frame_offsets must be integers")
+        f, o = f.astype(np.int64), o.astype(np.int64)
+        bad = np.nonzero((f < 0) | (f >= self.num_files))[0]
+        if len(bad):
+            raise ValueError(f"crop {int(bad[0])}: file {int(f[bad[0]])} outside 0 .. {self.num_files - 1}")
+        bad = np.nonzero((o < 0) | (o > self.num_frames[f]))[0]
+        if len(bad):
+            b = int(bad[0])
+            raise ValueError(f"crop {b} (source {int(f[b])}): frame offset {int(o[b])} outside 0 .. {int(self.num_frames[f[b]])}")
+        return torch.from_numpy(f.astype(np.int32)).to(self._dev), torch.from_numpy(o).to(self._dev), True
+
+    def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True):
+        """Decode crop b = frames frame_offsets[b] .. + num_frames of file files[b] for every b in ONE launch pair: returns
+        (pcm [B, C, num_frames] on the device, zero behind lengths[b]; lengths [B], a DEVICE int64 tensor: min(num_frames,
+        T_f - offset)).  float32 (default) or int32, as `load`.  files / frame_offsets: sequences, numpy arrays or torch
+        tensors.  Tensors already on the device are used as they are -- no copy to the host, no synchronisation; a file index
+        or an offset outside the corpus then gives lengths[b] = -1 and a row of zeros.  Anything else is checked on the host
+        (ValueError before any device work) and uploaded.  out: a contiguous device tensor of that shape and dtype to decode
+        into (it is zeroed first).  check=True reads one small result back: AlacGpuError naming crop, source and packet (its
+        index in its file) for the first packet that does not decode (statuses read as `load_batch` reads them), ValueError for
+        the first crop with a negative length.  check=False reads nothing back and returns behind the enqueue: see
+        last_status()."""
+        import torch
+
+        dtype = _torch_dtype(torch, torch.float32 if dtype is None else dtype)
+        L = _frame_count("num_frames", num_frames)
+        if L >= 1 << 32:
+            raise ValueError(f"num_frames {L} does not fit 32 bits")
+        if self._gpu is None:
+            raise AlacGpuError("the corpus is closed")
+        d_files, d_offs, from_host = self._indices(files, frame_offsets)
+        B, C_ = int(d_files.shape[0]), self.channels
+        if out is not None:
+            if (not isinstance(out, torch.Tensor) or out.shape != (B, C_, L) or out.dtype != dtype or out.device != self._dev
+                    or not out.is_contiguous()):
+                raise ValueError(f"out must be a contiguous {dtype} tensor of shape {(B, C_, L)} on {self._dev}")
+            out.zero_()
+        else:
+            out = torch.zeros((B, C_, L), dtype=dtype, device=self._dev)
+        self._last = 0
+        if B == 0 or L == 0:
+            lengths = torch.zeros(B, dtype=torch.int64, device=self._dev)
+            if B and L == 0 and not from_host:     # (the kernel's length codes, without the kernel)
+                f64 = d_files.to(torch.int64)
+                ok = (f64 >= 0) & (f64 < self.num_files)
+                ok &= (d_offs >= 0) & (d_offs <= self._d_num_frames[f64.clamp(0, self.num_files - 1)])
+                lengths = torch.where(ok, lengths, lengths - 1)
+                if check:
+                    self._raise_bad_length(lengths, d_files, d_offs)
+            return out, lengths
+        K = self.entries_per_crop(L)
+        n = B * K
+        if n >= 1 << 32:
+            raise ValueError(f"{B} crops of up to {K} packets: a call plans fewer than 2^32 entries")
+        pl = self._plan_arrays(n)
+        lengths = torch.empty(B, dtype=torch.int64, device=self._dev)
+        stream = torch.cuda.current_stream(self._dev).cuda_stream
+        ctx = self._gpu
+        _check(lib().alacgpu_plan_crops_device(ctx._ctx, _dp(self._pkt_offset), _dp(self._pkt_size), _dp(self._pkt_end),
+                                               _dp(self._file_first), _dp(self._file_cfg), self.num_files, _dp(d_files), _dp(d_offs),
+                                               B, L, K, C_ * L, _dp(pl["offsets"]), _dp(pl["sizes"]), _dp(pl["cfg_idx"]),
+                                               _dp(pl["dst_first"]), _dp(pl["dst_frames"]), _dp(pl["src_skip"]), _dp(lengths),
+                                               _VP(stream)), ctx._ctx)
+        ctx.decode_window_into_device(self._blob, self._blob_bytes, pl["offsets"], pl["sizes"], pl["cfg_idx"], n, pl["dst_first"],
+                                      pl["dst_frames"], pl["src_skip"], out, C_, "planar", L, None, pl["status"], stream=stream)
+        self._last = n
+        if check:
+            self._check_last(lengths, d_files, d_offs, L, K)
+        return out, lengths
+
+    def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True):
+        """`batch` crops of num_frames frames drawn on the device: files uniform over the corpus, the first frame uniform in
+        0 .. max(T_f - num_frames, 0).  generator: a torch.Generator (of the corpus's device, or of the CPU: then the draws are
+        made there and uploaded).  Returns (pcm, lengths, files, frame_offsets), the draws as device int64 tensors."""
+        import torch
+
+        B, L = _frame_count("batch", batch), _frame_count("num_frames", num_frames)
+        dev = generator.device if generator is not None else self._dev
+        files = torch.randint(0, self.num_files, (B,), generator=generator, device=dev, dtype=torch.int64).to(self._dev)
+        u = torch.rand(B, generator=generator, device=dev, dtype=torch.float64).to(self._dev)
+        span = (self._d_num_frames[files] - L).clamp(min=0)
+        offs = torch.minimum(torch.floor(u * (span + 1).to(torch.float64)).to(torch.int64), span)
+        pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check)
+        return pcm, lengths, files, offs
+
+    def last_status(self):
+        """The last crops call's per-entry statuses (ALACGPU_ST_*, as the kernels wrote them) and the mask of the entries that
+        are packets (the others are padding): two device tensors of B * K entries, crop b's at b * K ..; no synchronisation.
+        They are views of arrays the next call overwrites."""
+        import torch
+
+        if not self._last:
+            return (torch.zeros(0, dtype=torch.int32, device=self._dev), torch.zeros(0, dtype=torch.bool, device=self._dev))
+        return self._plan["status"][:self._last], self._plan["cfg_idx"][:self._last] != -1
+
+    # -- check=True: one reduction on the device, one small read ------------------------------------------------------------------
+    def _raise_bad_length(self, lengths, d_files, d_offs):
+        import torch
+
+        B = lengths.shape[0]
+        first = int(torch.where(lengths < 0, torch.arange(B, device=self._dev), B).min())
+        if first < B:
+            self._bad_length(first, int(lengths[first]), d_files, d_offs)
+
+    def _bad_length(self, b, code, d_files, d_offs):
+        f, o = int(d_files[b]), int(d_offs[b])
+        if code == -2:
+            raise AlacGpuError(f"crop {b} (source {f}): more packets than the plan reserves per crop")
+        raise ValueError(f"crop {b}: file {f} or frame offset {o} outside the corpus")
+
+    def _check_last(self, lengths, d_files, d_offs, L, K):
+        import torch
+
+        n, B, pl = self._last, lengths.shape[0], self._plan
+        st, valid = pl["status"][:n], pl["cfg_idx"][:n] != -1
+        # statuses as AlacContext.ReadBatch reads them (_normalise_status): the element type is the packet's first three bits
+        first_byte = self._blob[pl["offsets"][:n].clamp(max=max(self._blob_bytes - 1, 0))]
+        mono = (first_byte >> 5) == 0
+        ok = (st == ST_OK) | (st == ST_UNSUPPORTED_ELEMENT) | ((st == ST_UNSUPPORTED_PREDTYPE) & mono)
+        bad_entry = torch.where(valid & ~ok, pl["iota"][:n], n).min()
+        bad_crop = torch.where(lengths < 0, pl["iota"][:B], B).min()
+        bad_entry, bad_crop = (int(x) for x in torch.stack([bad_entry, bad_crop]).cpu())      # the one read
+        if bad_crop < B:
+            self._bad_length(bad_crop, int(lengths[bad_crop]), d_files, d_offs)
+        if bad_entry < n:
+            b, i = divmod(bad_entry, K)
+            f, o = int(d_files[b]), int(d_offs[b])
+            h = self._host
+            g0, g1 = int(h["file_first"][f]), int(h["file_first"][f + 1])
+            ends = h["pkt_end"][g0:g1].astype(np.int64)
+            p0 = 0 if o == 0 else int(np.searchsorted(ends, o, side="right"))
+            raise AlacGpuError(f"crop {b} (source {f}), packet {p0 + i} does not decode: {_status_text(int(st[bad_entry]))}")

@@ -13,6 +13,7 @@
 #include <thread>
 #include <vector>
 
+#include "alac_corpus.h"
 #include "alac_encode.h"
 #include "alac_kernels.h"
 #include "alacgpu.h"
@@ -491,6 +492,52 @@ int alacgpu_decode_into_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t bl
     return alacgpu_decode_window_into_device(ctx, d_blob, blob_bytes, d_offsets, d_sizes, d_cfg_idx, n_packets, d_dst_first,
                                              d_dst_frames, nullptr, d_out, out_elems, channels, layout, dtype, plane_stride,
                                              d_out_samples, d_status, hip_stream);
+}
+
+int alacgpu_plan_crops_device(alacgpu_ctx* ctx, const void* d_pkt_offset, const void* d_pkt_size, const void* d_pkt_end,
+                              const void* d_file_first, const void* d_file_cfg, uint32_t n_files, const void* d_crop_file,
+                              const void* d_crop_offset, uint32_t n_crops, uint32_t crop_frames, uint32_t entries_per_crop,
+                              uint64_t dst_stride, void* d_offsets, void* d_sizes, void* d_cfg_idx, void* d_dst_first,
+                              void* d_dst_frames, void* d_src_skip, void* d_lengths, void* hip_stream) {
+    if (!ctx) return ALACGPU_ERR_BAD_ARG;
+    if (n_crops == 0) return ALACGPU_OK;
+    if (entries_per_crop == 0 || (uint64_t)n_crops * entries_per_crop > 0xFFFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (!d_pkt_offset || !d_pkt_size || !d_pkt_end || !d_file_first || !d_file_cfg || !d_crop_file || !d_crop_offset ||
+        !d_offsets || !d_sizes || !d_cfg_idx || !d_dst_first || !d_dst_frames || !d_src_skip || !d_lengths)
+        return ALACGPU_ERR_BAD_ARG;
+    if (((uintptr_t)d_pkt_offset & 7u) != 0 || ((uintptr_t)d_pkt_size & 3u) != 0 || ((uintptr_t)d_pkt_end & 7u) != 0 ||
+        ((uintptr_t)d_file_first & 3u) != 0 || ((uintptr_t)d_file_cfg & 1u) != 0 || ((uintptr_t)d_crop_file & 3u) != 0 ||
+        ((uintptr_t)d_crop_offset & 7u) != 0 || ((uintptr_t)d_offsets & 7u) != 0 || ((uintptr_t)d_sizes & 3u) != 0 ||
+        ((uintptr_t)d_cfg_idx & 1u) != 0 || ((uintptr_t)d_dst_first & 7u) != 0 || ((uintptr_t)d_dst_frames & 3u) != 0 ||
+        ((uintptr_t)d_src_skip & 3u) != 0 || ((uintptr_t)d_lengths & 7u) != 0)
+        return ALACGPU_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    alac_plan_params p;
+    p.pkt_offset = (const uint64_t*)d_pkt_offset;
+    p.pkt_size = (const uint32_t*)d_pkt_size;
+    p.pkt_end = (const uint64_t*)d_pkt_end;
+    p.file_first = (const uint32_t*)d_file_first;
+    p.file_cfg = (const uint16_t*)d_file_cfg;
+    p.n_files = n_files;
+    p.crop_file = (const uint32_t*)d_crop_file;
+    p.crop_offset = (const uint64_t*)d_crop_offset;
+    p.n_crops = n_crops;
+    p.crop_frames = crop_frames;
+    p.entries_per_crop = entries_per_crop;
+    p.dst_stride = dst_stride;
+    p.offsets = (uint64_t*)d_offsets;
+    p.sizes = (uint32_t*)d_sizes;
+    p.cfg_idx = (uint16_t*)d_cfg_idx;
+    p.dst_first = (uint64_t*)d_dst_first;
+    p.dst_frames = (uint32_t*)d_dst_frames;
+    p.src_skip = (uint32_t*)d_src_skip;
+    p.lengths = (int64_t*)d_lengths;
+    constexpr uint32_t per_wg = ALAC_PLAN_THREADS / 64;   // one wave per crop
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_plan_crops_kernel, dim3((n_crops + per_wg - 1u) / per_wg), dim3(ALAC_PLAN_THREADS),
+                                 kargs, 0, (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
 }
 
 size_t alacgpu_encode_max_packet_bytes(uint32_t frames, int sample_size, int channels) {

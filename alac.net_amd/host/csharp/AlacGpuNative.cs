@@ -51,6 +51,13 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_decode_into_device(IntPtr ctx, IntPtr dBlob, ulong blobBytes, IntPtr dOffsets,
             IntPtr dSizes, IntPtr dCfgIdx, uint nPackets, IntPtr dDstFirst, IntPtr dDstFrames, IntPtr dOut, ulong outElems,
             uint channels, int layout, int dtype, ulong planeStride, IntPtr dOutSamples, IntPtr dStatus, IntPtr hipStream);
+        /// <summary>Plan nCrops windows of cropFrames frames against a corpus's packet tables in device memory: writes the per-packet
+        /// arrays of a window decode (entriesPerCrop entries per crop, padding behind a crop's packets) and dLengths[b]; every
+        /// pointer a device pointer, asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_plan_crops_device(IntPtr ctx, IntPtr dPktOffset, IntPtr dPktSize, IntPtr dPktEnd,
+            IntPtr dFileFirst, IntPtr dFileCfg, uint nFiles, IntPtr dCropFile, IntPtr dCropOffset, uint nCrops, uint cropFrames,
+            uint entriesPerCrop, ulong dstStride, IntPtr dOffsets, IntPtr dSizes, IntPtr dCfgIdx, IntPtr dDstFirst, IntPtr dDstFrames,
+            IntPtr dSrcSkip, IntPtr dLengths, IntPtr hipStream);
         /// <summary>Encode PCM in device memory (int32 or float32, interleaved or planar) to ALAC packets in device memory, one
         /// run of frames per packet, packet p at dPackets + p * slotBytes; asynchronous on hipStream.</summary>
         [DllImport(Lib)] public static extern UIntPtr alacgpu_encode_max_packet_bytes(uint frames, int sampleSize, int channels);

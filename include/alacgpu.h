@@ -229,6 +229,41 @@ int alacgpu_decode_window_into_device(alacgpu_ctx* ctx, const void* d_blob, uint
                                       uint64_t plane_stride, void* d_out_samples, void* d_status, void* hip_stream);
 
 /*
+ * Plan the crops of a corpus that is resident in HBM (no counterpart in the reference): for n_crops windows of crop_frames
+ * frames each, crop b = (file d_crop_file[b], first frame d_crop_offset[b]), write the per-packet arrays that
+ * alacgpu_decode_window_into_device reads -- one more call decodes every crop, and the host never sees the plan.  Device
+ * pointers only (natural alignment), asynchronous on hip_stream; nothing of the ctx is used but its device.
+ * The resident tables, built once per corpus (P packets of F files, the files' packets back to back):
+ *   d_pkt_offset[P]   uint64: byte offset of the packet into the resident blob
+ *   d_pkt_size[P]     uint32: its size (stsz)
+ *   d_pkt_end[P]      uint64: the frames of the packet's FILE up to and including this packet (inclusive prefix sum of the
+ *                     stts durations, starting anew with every file); T_f, a file's frame count, is its last packet's value
+ *   d_file_first[F+1] uint32: the first packet of file f; file f's packets are d_file_first[f] .. d_file_first[f+1]
+ *   d_file_cfg[F]     uint16: the file's stream cfg (a row of the decoding ctx)
+ * The call: d_crop_file[b] uint32, d_crop_offset[b] uint64, and entries_per_crop (K): the entries reserved per crop.
+ * The plan, n_crops * K entries, crop b's at j = b * K + i: d_offsets[j] uint64, d_sizes[j] uint32, d_cfg_idx[j] uint16,
+ * d_dst_first[j] uint64 = b * dst_stride + the run's first frame in the crop (dst_stride = C * crop_frames addresses a
+ * planar [B, C, crop_frames] tensor), d_dst_frames[j] uint32, d_src_skip[j] uint32 (at most 16384: frames further into a
+ * packet are zeros); and d_lengths[b] int64:
+ *   min(crop_frames, T_f - offset)   the crop's frames; its entries are the packets that overlap frames offset .. offset +
+ *                                    length of the file, in file order (a crop from frame 0 starts at packet 0; packets
+ *                                    without frames are taken only between others; a crop of length 0 has no packets)
+ *   -1                               d_crop_file[b] >= n_files or offset > T_f: no packets
+ *   -2                               the crop needs more than K entries: no packets
+ * The entries behind a crop's packets are padding: cfg_idx 0xFFFF and zeros.  In a decode call such an entry has status
+ * ALACGPU_ST_UNSUPPORTED_PARAMS, costs no decode step and writes nothing (a ctx has at most 65535 cfgs for that).  Nothing
+ * outside the n_crops * K entries and the n_crops lengths is ever written.  n_crops == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG: a NULL ctx or array, a misaligned array, K == 0, or n_crops * K above 2^32 - 1.  The tables are the
+ * caller's: d_file_first ascending with d_file_first[F] <= P, d_pkt_end ascending within a file.
+ */
+int alacgpu_plan_crops_device(alacgpu_ctx* ctx, const void* d_pkt_offset, const void* d_pkt_size, const void* d_pkt_end,
+                              const void* d_file_first, const void* d_file_cfg, uint32_t n_files,
+                              const void* d_crop_file, const void* d_crop_offset, uint32_t n_crops,
+                              uint32_t crop_frames, uint32_t entries_per_crop, uint64_t dst_stride,
+                              void* d_offsets, void* d_sizes, void* d_cfg_idx, void* d_dst_first, void* d_dst_frames,
+                              void* d_src_skip, void* d_lengths, void* hip_stream);
+
+/*
  * Encoder (no counterpart in the reference, which only decodes): PCM in HBM to ALAC packets in HBM, one packet per run of
  * frames, asynchronous on hip_stream.  Device pointers; d_pcm 4-byte, d_src_first 8-byte, d_packets 16-byte aligned.
  *   d_pcm            src_elems int32 (ALACGPU_DST_INT32: the canonical sample, clamped to the sample range) or float32

@@ -1,0 +1,133 @@
+"""What a resident corpus is worth per training step: B random crops of L frames out of synthetic M4A files (stereo 16-bit,
+4096-frame packets, 60 s each), three ways on the same crops --
+  (a) load_batch  load_batch(file bytes of every crop, frame_offsets=, max_frames=): demux, plan, upload and a context per call
+  (b) corpus_host corpus.crops with host index arrays and check=True (two small uploads, one small read)
+  (c) corpus_dev  corpus.crops with device index tensors and check=False (nothing but the enqueue)
+Per (B, L): the wall time of a step (torch.cuda.synchronize() in front of and behind it, median of --steps steps after
+--warmup), the planning kernel's time (HIP events around --plan-reps back-to-back launches, divided by them, median) and the
+padding share 1 - packets / (B * K).  The three are checked equal once.  One JSON line.
+  python tools/bench_corpus.py [--files 32] [--seconds 60] [--steps 30] [--warmup 5]
+Kernel times of the decode pair: run one way alone under the profiler's kernel trace, e.g.
+  rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_corpus.py --only corpus_dev --shape 64x88200"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def make_file(synth, frames, seed):
+    from alac.net_amd.synth import m4a
+
+    n = -(-frames // 4096)
+    d = synth.packet_descs(n, stereo=1)
+    d["n"][-1] = frames - (n - 1) * 4096
+    b = synth.make_batch(d, synth.default_signal(seed))
+    packets = [bytes(b["blob"][int(o):int(o) + int(s)]) for o, s in zip(b["offsets"], b["sizes"])]
+    return m4a.write_m4a(packets, [int(x) for x in d["n"]], sample_size=16, channels=2, sample_rate=44100)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=32)
+    ap.add_argument("--seconds", type=float, default=60.0)
+    ap.add_argument("--distinct", type=int, default=2, help="distinct files behind the sources (the bytes are shared)")
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--plan-reps", type=int, default=20)
+    ap.add_argument("--shape", action="append", help="BxL, repeatable (default 64x88200 and 256x44100)")
+    ap.add_argument("--only", choices=["load_batch", "corpus_host", "corpus_dev"], help="run this way alone (for a kernel trace)")
+    args = ap.parse_args()
+    import torch
+
+    import alac.net_amd as pkg
+    from alac.net_amd import synth
+
+    synth.build()
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    T = int(args.seconds * 44100)
+    distinct = [make_file(synth, T, 11 + k) for k in range(args.distinct)]
+    blobs = [distinct[f % len(distinct)] for f in range(args.files)]
+    shapes = [tuple(int(x) for x in s.split("x")) for s in (args.shape or ["64x88200", "256x44100"])]
+    corpus = pkg.Corpus(blobs)
+    results = []
+    for B, L in shapes:
+        rng = np.random.default_rng(B + L)
+        draws = [(rng.integers(0, args.files, B).astype(np.int64), rng.integers(0, T - L + 1, B).astype(np.int64))
+                 for _ in range(args.steps + args.warmup)]
+        on_device = [(torch.from_numpy(f).to(dev), torch.from_numpy(o).to(dev)) for f, o in draws]
+
+        def load_batch(i):
+            f, o = draws[i]
+            return pkg.load_batch([blobs[k] for k in f], frame_offsets=o, max_frames=L)[0]
+
+        def corpus_host(i):
+            return corpus.crops(draws[i][0], draws[i][1], L)[0]
+
+        def corpus_dev(i):
+            return corpus.crops(on_device[i][0], on_device[i][1], L, check=False)[0]
+
+        modes = {"load_batch": load_batch, "corpus_host": corpus_host, "corpus_dev": corpus_dev}
+        if args.only:
+            modes = {args.only: modes[args.only]}
+        else:
+            outs = [fn(0) for fn in modes.values()]
+            assert all(torch.equal(outs[0], x) for x in outs[1:]), "the three ways differ"
+            del outs
+        wall = {m: [] for m in modes}
+        for i in range(args.steps + args.warmup):          # the ways alternate inside every step: drift hits them alike
+            for m, fn in modes.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = fn(i)
+                torch.cuda.synchronize()
+                dt = (time.perf_counter() - t0) * 1e3
+                del out
+                if i >= args.warmup:
+                    wall[m].append(dt)
+        med = lambda v: round(float(np.median(v)), 4)
+        r = {"crops": B, "crop_frames": L, "wall_ms": {m: med(v) for m, v in wall.items()}}
+        if not args.only:
+            # the planner alone, and the padding share of the plan it writes
+            K = corpus.entries_per_crop(L)
+            corpus.crops(on_device[0][0], on_device[0][1], L, check=False)
+            valid = corpus.last_status()[1]
+            pl, lengths = corpus._plan, torch.empty(B, dtype=torch.int64, device=dev)
+            stream = torch.cuda.current_stream(dev)
+
+            f, o = on_device[0][0].to(torch.int32), on_device[0][1]
+
+            def plan():
+                rc = pkg.lib().alacgpu_plan_crops_device(
+                    corpus._gpu._ctx, pkg._dp(corpus._pkt_offset), pkg._dp(corpus._pkt_size), pkg._dp(corpus._pkt_end),
+                    pkg._dp(corpus._file_first), pkg._dp(corpus._file_cfg), corpus.num_files, pkg._dp(f), pkg._dp(o), B, L, K,
+                    2 * L, pkg._dp(pl["offsets"]), pkg._dp(pl["sizes"]), pkg._dp(pl["cfg_idx"]), pkg._dp(pl["dst_first"]),
+                    pkg._dp(pl["dst_frames"]), pkg._dp(pl["src_skip"]), pkg._dp(lengths), pkg._VP(stream.cuda_stream))
+                assert rc == 0, rc
+
+            ms = []
+            for rep in range(args.steps + args.warmup):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for _ in range(args.plan_reps):
+                    plan()
+                e1.record(stream)
+                e1.synchronize()
+                if rep >= args.warmup:
+                    ms.append(e0.elapsed_time(e1) / args.plan_reps)
+            r.update(entries_per_crop=K, packets=int(valid.sum()), padding_share=round(1.0 - float(valid.sum()) / (B * K), 4),
+                     plan_kernel_ms=med(ms), speedup_dev_vs_load_batch=round(med(wall["load_batch"]) / med(wall["corpus_dev"]), 2))
+        results.append(r)
+    corpus.close()
+    print(json.dumps({"files": args.files, "seconds": args.seconds, "steps": args.steps, "warmup": args.warmup,
+                      "blob_mb": round(corpus._blob_bytes / 1e6, 1), "results": results}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

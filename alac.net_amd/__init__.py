@@ -62,6 +62,7 @@ SYMBOLS = {
                                                     C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP]),
     "alacgpu_plan_crops_device": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_uint32, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32,
                                             C.c_uint64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "alacgpu_compact_packets_device": (C.c_int, [_VP, _VP, C.c_uint64, _VP, C.c_uint32, _VP, C.c_uint64, C.c_uint64, _VP, _VP, _VP]),
     "alacgpu_encode_max_packet_bytes": (C.c_size_t, [C.c_uint32, C.c_int, C.c_int]),
     "alacgpu_encode_device": (C.c_int, [_VP, _VP, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP, C.c_uint32,
                                         _VP, C.c_uint64, _VP, _VP, _VP]),
@@ -297,6 +298,17 @@ class AlacGpuContext(_Closing):
         rc = lib().alacgpu_encode_device(self._ctx, _dp(pcm), pcm.numel(), channels, lay, dtype, plane_stride, _dp(d_src_first),
                                          _dp(d_src_frames), _dp(d_cfg_idx), n_packets, _dp(d_packets), slot_bytes, _dp(d_sizes),
                                          _dp(d_status), _VP(stream))
+        _check(rc, self._ctx)
+
+    def compact_packets_device(self, d_packets, slot_bytes, d_sizes, n_packets, d_blob, base, blob_capacity, d_pkt_offset, d_total,
+                               stream=0):
+        """alacgpu_compact_packets_device: the packets the encoder left in slots (packet p at d_packets[p * slot_bytes:], its
+        size in d_sizes[p]) back to back into d_blob from byte `base` on; d_pkt_offset[p] (int64 device tensor) = base + the
+        sizes in front of p, d_total[0] (int64 device tensor) the sum of the sizes.  A packet that would end behind
+        blob_capacity is not copied (offsets and total are complete all the same); nothing of d_blob outside the copied
+        packets is written.  Asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_compact_packets_device(self._ctx, _dp(d_packets), slot_bytes, _dp(d_sizes), n_packets, _dp(d_blob), base,
+                                                  blob_capacity, _dp(d_pkt_offset), _dp(d_total), _VP(stream))
         _check(rc, self._ctx)
 
     def set_output_format(self, fmt):
@@ -674,54 +686,79 @@ def _check_stco(T, C_, sample_size, frame_length):
         raise ValueError(f"{T} frames can need {worst} bytes: more than the 32-bit chunk offsets (stco) of an M4A file address")
 
 
-def _encode_tensor(pcm, lengths, sample_size, frame_length, device):
-    """One alacgpu_encode_device call over every file of pcm[F, C, T] (frames 0 .. lengths[f]); returns per file the list of
-    packet bytes.  Only the packets' own bytes are copied to the host: they are compacted on the device first."""
+class _Encoded:
+    """What _encode_slots leaves behind: the batch's packet list (host) and the encoder's slot buffer, sizes and statuses
+    (device)."""
+
+
+def _encode_slots(ctx, pcm, lengths, frame_length, stream):
+    """The packet list of pcm[F, C, T] (frames 0 .. lengths[f] of every file, frame_length frames per packet, a shorter last
+    one) and ONE alacgpu_encode_device call over it with cfg 0 of `ctx` on `stream` (raw hipStream_t), into a fresh slot
+    buffer.  Nothing is read back."""
     import torch
 
     F, C_, T = pcm.shape
     dev = pcm.device
-    counts = [-(-int(L) // frame_length) for L in lengths]
-    file_of = np.repeat(np.arange(F, dtype=np.int64), counts)
-    first_in_file = np.concatenate([np.arange(c, dtype=np.int64) * frame_length for c in counts])
-    frames = np.minimum(np.repeat(np.asarray(lengths, dtype=np.int64), counts) - first_in_file, frame_length)
-    n = len(file_of)
-    cfgs = [(frame_length, sample_size, 40, 10, 14, C_)]
-    slot = encode_max_packet_bytes(frame_length, sample_size, C_)
-    d_first = torch.from_numpy(file_of * C_ * T + first_in_file).to(dev)
-    d_frames = torch.from_numpy(frames.astype(np.int32)).to(dev)
+    e = _Encoded()
+    e.counts = [-(-int(L) // frame_length) for L in lengths]
+    e.file_of = np.repeat(np.arange(F, dtype=np.int64), e.counts)
+    first_in_file = np.concatenate([np.arange(c, dtype=np.int64) * frame_length for c in e.counts])
+    e.frames = np.minimum(np.repeat(np.asarray(lengths, dtype=np.int64), e.counts) - first_in_file, frame_length)
+    n = e.n = len(e.file_of)
+    e.slot = encode_max_packet_bytes(frame_length, int(ctx.cfgs[0]["sample_size"]), C_)
+    d_first = torch.from_numpy(e.file_of * C_ * T + first_in_file).to(dev)
+    d_frames = torch.from_numpy(e.frames.astype(np.int32)).to(dev)
     d_ci = torch.zeros(n, dtype=torch.int16, device=dev)
-    d_packets = torch.empty(n * slot, dtype=torch.uint8, device=dev)
-    d_sizes = torch.zeros(n, dtype=torch.int32, device=dev)
-    d_st = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    src = pcm.contiguous()
-    with AlacGpuContext(cfgs, device) as ctx:
-        stream = torch.cuda.current_stream(dev)
-        ctx.encode_device(src, C_, d_first, d_frames, d_ci, n, d_packets, slot, d_sizes, d_st, layout="planar",
-                          plane_stride=T, stream=stream.cuda_stream)
-        st = d_st.cpu().numpy()     # (waits for the encode: the context's workspace is released behind it)
-    bad = np.nonzero(st != ST_OK)[0]
-    if len(bad):
-        p = int(bad[0])
-        raise AlacGpuError(f"packet {p} was not encoded: {_status_text(st[p])}")
-    # compact on the device: a gather of every packet's bytes, then one copy of exactly those bytes
-    sizes64 = d_sizes.to(torch.int64)
-    ends = torch.cumsum(sizes64, 0)
-    total = int(ends[-1])
-    starts = ends - sizes64
-    owner = torch.repeat_interleave(torch.arange(n, device=dev), sizes64, output_size=total)
-    src_idx = owner * slot + (torch.arange(total, device=dev) - starts[owner])
-    blob = d_packets[src_idx].cpu().numpy().tobytes()
-    sizes = d_sizes.cpu().numpy().astype(np.int64)
+    e.d_packets = torch.empty(n * e.slot, dtype=torch.uint8, device=dev)
+    e.d_sizes = torch.zeros(n, dtype=torch.int32, device=dev)
+    e.d_st = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    ctx.encode_device(pcm.contiguous(), C_, d_first, d_frames, d_ci, n, e.d_packets, e.slot, e.d_sizes, e.d_st, layout="planar",
+                      plane_stride=T, stream=stream)
+    return e
+
+
+def _compact_slots(ctx, e, d_blob, base, capacity, d_pkt_offset, stream):
+    """One alacgpu_compact_packets_device call over the slots of `e` behind its encode, and the ONE small read: returns (the
+    packets' bytes in all, the first packet whose status is not ALACGPU_ST_OK or e.n), both reduced on the device."""
+    import torch
+
+    dev = e.d_sizes.device
+    d_total = torch.zeros(1, dtype=torch.int64, device=dev)
+    ctx.compact_packets_device(e.d_packets, e.slot, e.d_sizes, e.n, d_blob, base, capacity, d_pkt_offset, d_total, stream=stream)
+    bad = torch.where(e.d_st != ST_OK, torch.arange(e.n, dtype=torch.int64, device=dev), e.n).min()
+    total, bad = (int(x) for x in torch.stack([d_total[0], bad]).cpu())
+    return total, bad
+
+
+def _encode_tensor(pcm, lengths, sample_size, frame_length, device):
+    """One alacgpu_encode_device call over every file of pcm[F, C, T] (frames 0 .. lengths[f]); returns per file the list of
+    packet bytes.  Only the packets' own bytes are copied to the host: they are compacted on the device first
+    (alacgpu_compact_packets_device: once without room, for the size, then into exactly that many bytes)."""
+    import torch
+
+    F, C_, T = pcm.shape
+    dev = pcm.device
+    with AlacGpuContext([(frame_length, sample_size, 40, 10, 14, C_)], device) as ctx:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        e = _encode_slots(ctx, pcm, lengths, frame_length, stream)
+        d_off = torch.empty(e.n, dtype=torch.int64, device=dev)
+        d_blob = torch.empty(16, dtype=torch.uint8, device=dev)
+        total, bad = _compact_slots(ctx, e, d_blob, 0, 0, d_off, stream)
+        if bad < e.n:
+            raise AlacGpuError(f"packet {bad} was not encoded: {_status_text(int(e.d_st[bad]))}")
+        d_blob = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+        _compact_slots(ctx, e, d_blob, 0, total, d_off, stream)   # (its read waits for the copy: the context may go)
+    blob = d_blob[:total].cpu().numpy().tobytes()
+    sizes = e.d_sizes.cpu().numpy().astype(np.int64)
     offs = np.concatenate([[0], np.cumsum(sizes)])
     out, p = [], 0
     for f in range(F):
-        out.append([blob[offs[q]:offs[q + 1]] for q in range(p, p + counts[f])])
-        p += counts[f]
-    return out, [frames[file_of == f] for f in range(F)]
+        out.append([blob[offs[q]:offs[q + 1]] for q in range(p, p + e.counts[f])])
+        p += e.counts[f]
+    return out, [e.frames[e.file_of == f] for f in range(F)]
 
 
-def _write_file(dest, packets, durations, frame_length, sample_size, channels, sample_rate):
+def _write_file(dest, packets, durations, frame_length, sample_size, channels, sample_rate, rice=(40, 10, 14)):
     from .container import write_m4a
 
     sizes = [len(x) for x in packets]
@@ -729,7 +766,8 @@ def _write_file(dest, packets, durations, frame_length, sample_size, channels, s
     seconds = frames / float(sample_rate)
     avg = int(round(8 * sum(sizes) / seconds)) if seconds > 0 else 0
     data = write_m4a(packets, [int(d) for d in durations], frame_len=frame_length, sample_size=sample_size, channels=channels,
-                     sample_rate=sample_rate, max_frame_bytes=max(sizes), avg_bitrate=min(avg, (1 << 32) - 1))
+                     sample_rate=sample_rate, pb=rice[0], mb=rice[1], kb=rice[2], max_frame_bytes=max(sizes),
+                     avg_bitrate=min(avg, (1 << 32) - 1))
     if isinstance(dest, (str, os.PathLike)):
         with open(dest, "wb") as f:
             f.write(data)
@@ -754,19 +792,26 @@ def save(dest, pcm, sample_rate, sample_size=16, frame_length=4096, device=0):
     return _write_file(dest, packets[0], durations[0], int(frame_length), sample_size, C_, int(sample_rate))
 
 
-def save_batch(dests, pcm, lengths, sample_rate, sample_size=16, frame_length=4096, device=0):
-    """`save` for F files in ONE launch: file f is frames 0 .. lengths[f] of pcm[f] ([F, C, Tmax], as `load_batch` returns
-    it); dests[f] a path or a writable binary file object.  Returns the file sizes."""
+def _check_batch_args(pcm, lengths, sample_rate, sample_size, frame_length, dests=None):
+    """The host-side checks of save_batch and Corpus.from_pcm for one batch, before any device work; returns (F, C, T, the
+    lengths as a list of ints)."""
     F, C_, T = _check_save_args(pcm, True, sample_size, frame_length, sample_rate)
     lengths = [int(x) for x in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-    if len(dests) != F or len(lengths) != F:
-        raise ValueError(f"{F} files in pcm, {len(dests)} destinations and {len(lengths)} lengths")
+    if dests is not None and len(dests) != F or len(lengths) != F:
+        raise ValueError(f"{F} files in pcm, " + (f"{len(dests)} destinations and " if dests is not None else "") + f"{len(lengths)} lengths")
     for L in lengths:
         if not 1 <= L <= T:
             raise ValueError(f"length {L} outside 1 .. {T}")
         _check_stco(L, C_, sample_size, int(frame_length))
     if pcm.device.type != "cuda":
         raise ValueError("pcm must be on the GPU")
+    return F, C_, T, lengths
+
+
+def save_batch(dests, pcm, lengths, sample_rate, sample_size=16, frame_length=4096, device=0):
+    """`save` for F files in ONE launch: file f is frames 0 .. lengths[f] of pcm[f] ([F, C, Tmax], as `load_batch` returns
+    it); dests[f] a path or a writable binary file object.  Returns the file sizes."""
+    F, C_, T, lengths = _check_batch_args(pcm, lengths, sample_rate, sample_size, frame_length, dests)
     packets, durations = _encode_tensor(pcm, lengths, sample_size, int(frame_length), device)
     return [_write_file(d, packets[f], durations[f], int(frame_length), sample_size, C_, int(sample_rate))
             for f, d in enumerate(dests)]
@@ -826,4 +871,4 @@ class AlacFile:
 
 
 # ---- a corpus resident in HBM and its random crops (alacgpu_plan_crops_device) -----------------------------------------------------
-from .corpus import Corpus, corpus_plan_host, corpus_tables, entries_per_crop  # noqa: E402  (it imports the names above)
+from .corpus import Corpus, compact_plan_host, corpus_plan_host, corpus_tables, entries_per_crop  # noqa: E402  (it imports the names above)

@@ -5,13 +5,18 @@
 `window_plan` for every crop against the resident tables) and alacgpu_decode_window_into_device over the plan it wrote.  The
 host hands over (file, first frame) pairs -- or nothing at all when they are device tensors already.
 
-`corpus_tables` (the resident tables as numpy arrays), `entries_per_crop` (the K bound) and `corpus_plan_host` (the kernel's
-specification in numpy) need no device.
+`Corpus.from_pcm` builds the same corpus from PCM that is on the GPU already, without the file system: per batch one
+alacgpu_encode_device call into slots, one alacgpu_compact_packets_device call that packs them behind the packets so far (and
+writes their offsets), one small read.  `Corpus.save` writes any corpus back as M4A files: its checkpoint.
+
+`corpus_tables` (the resident tables as numpy arrays), `entries_per_crop` (the K bound), `corpus_plan_host` and
+`compact_plan_host` (the two kernels' specifications in numpy) need no device.
 """
 import numpy as np
 
-from . import (MAX_FRAME, ST_OK, ST_UNSUPPORTED_ELEMENT, ST_UNSUPPORTED_PREDTYPE, AlacGpuContext, AlacGpuError, _Closing, _check,
-               _dp, _frame_count, _status_text, _torch_dtype, _VP, lib)
+from . import (MAX_FRAME, ST_OK, ST_UNSUPPORTED_ELEMENT, ST_UNSUPPORTED_PREDTYPE, AlacGpuContext, AlacGpuError, _Closing,
+               _check, _check_batch_args, _compact_slots, _dp, _encode_slots, _frame_count, _status_text, _torch_dtype, _VP,
+               _write_file, lib, make_cfgs)
 
 PAD_CFG = 0xFFFF        # a padding entry's cfg_idx: never a row of the context, so the kernels switch the entry off
 MAX_CFGS = 65535
@@ -132,6 +137,20 @@ def corpus_plan_host(pkt_offset, pkt_size, pkt_end, file_first, file_cfg, crop_f
     return offsets, sizes, cfg_idx, dst_first, dst_frames, src_skip, lengths
 
 
+def compact_plan_host(sizes, slot_bytes, base, capacity):
+    """alacgpu_compact_packets_device on the host, in numpy: the kernel's specification (tests compare the two; the product
+    never comes here).  Returns (pkt_offset uint64 [n]: base + the counted sizes in front of a packet -- a size above
+    slot_bytes counts as 0 --, total: the sum of the counted sizes whatever the capacity, copied bool [n]: the packets with
+    pkt_offset + size <= capacity -- those, whole, are all that is written to the blob)."""
+    sizes = np.asarray(sizes, dtype=np.uint32).astype(np.uint64)
+    counted = np.where(sizes <= np.uint64(slot_bytes), sizes, np.uint64(0))
+    ends = np.cumsum(counted, dtype=np.uint64)
+    pkt_offset = np.uint64(base) + ends - counted
+    total = int(ends[-1]) if len(ends) else 0
+    copied = pkt_offset.astype(object) + counted.astype(object) <= int(capacity) if len(ends) else np.zeros(0, dtype=bool)
+    return pkt_offset.astype(np.uint64), total, np.asarray(copied, dtype=bool)
+
+
 class Corpus(_Closing):
     """M4A files resident in HBM, compressed: Corpus(sources, device=0) demuxes every source once (file bytes, a path or a
     seekable binary file object, as for `load`), uploads the packet bytes file by file into one device blob and the packet
@@ -154,8 +173,7 @@ class Corpus(_Closing):
             total += int(header_table(s)["sizes"].sum(dtype=np.int64))
             if pos is not None:
                 s.seek(pos)
-        self.device = device
-        dev = self._dev = torch.device("cuda", device)
+        dev = torch.device("cuda", device)
         # readable up to blob_bytes rounded up to 16, as every decode entry point wants it (torch's allocations are aligned)
         self._blob = torch.zeros(total + 64, dtype=torch.uint8, device=dev)
         heads, base = [], 0
@@ -168,24 +186,158 @@ class Corpus(_Closing):
             heads.append({k: t[k] for k in ("sizes", "durations", "cfg", "num_channels", "sample_rate")})
         if base != total:
             raise ValueError("a source changed while it was read")
-        tb = corpus_tables(heads)
-        self.num_files = len(heads)
+        self._install(device, corpus_tables(heads))
+
+    def _install(self, device, tb, d_pkt_offset=None, d_pkt_size=None, gpu=None):
+        """The end of both constructors: self._blob holds the packets; tb: the host tables (pkt_end, file_first, file_cfg, cfgs,
+        num_frames, channels, sample_rate, blob_bytes, and pkt_offset and pkt_size unless they are on the device already: the
+        two tensors; `save` fetches them then); gpu: the context to keep, if there is one already."""
+        import torch
+
+        dev = self._dev = torch.device("cuda", device)
+        self.device = device
+
+        def up(a, dtype):      # (an empty table still needs an address)
+            a = np.ascontiguousarray(a).view(dtype)
+            return torch.from_numpy(a if len(a) else np.zeros(1, dtype)).to(dev)
+
+        self.num_files = len(tb["file_cfg"])
         self.num_frames = tb["num_frames"]
         self.channels, self.sample_rate = tb["channels"], tb["sample_rate"]
         self._host = tb
         self._blob_bytes = tb["blob_bytes"]
-
-        def up(a, dtype):      # (an empty table still needs an address)
-            a = a.view(dtype)
-            return torch.from_numpy(a if len(a) else np.zeros(1, dtype)).to(dev)
-
-        self._pkt_offset, self._pkt_size = up(tb["pkt_offset"], np.int64), up(tb["pkt_size"], np.int32)
+        self._pkt_offset = d_pkt_offset if d_pkt_offset is not None else up(tb["pkt_offset"], np.int64)
+        self._pkt_size = d_pkt_size if d_pkt_size is not None else up(tb["pkt_size"], np.int32)
         self._pkt_end, self._file_first = up(tb["pkt_end"], np.int64), up(tb["file_first"], np.int32)
         self._file_cfg = up(tb["file_cfg"], np.int16)
         self._d_num_frames = torch.from_numpy(self.num_frames).to(dev)
         self._K = {}
         self._plan, self._capacity, self._last = None, 0, 0
-        self._gpu = AlacGpuContext(tb["cfgs"], device)
+        self._gpu = gpu if gpu is not None else AlacGpuContext(tb["cfgs"], device)
+
+    @classmethod
+    def from_pcm(cls, pcm, lengths=None, sample_rate=None, sample_size=16, frame_length=4096):
+        """The corpus of PCM that is on the GPU, without files in between: from_pcm(pcm, lengths, sample_rate, sample_size=16,
+        frame_length=4096) -- exactly `save_batch`'s arguments and checks (file f is frames 0 .. lengths[f] of pcm[f],
+        [F, C, Tmax] int32 or float32) -- or from_pcm(batches, sample_rate=...) with an iterable of (pcm, lengths) pairs, taken
+        one after the other so that the PCM never has to exist all at once; every batch has the same channel count, F and
+        Tmax may differ.  Files are numbered in the order given; the device is the tensors'.  Per batch: one encode into
+        slots, one compaction behind the packets so far, one small read; the blob grows geometrically where a batch does
+        not fit (build_stats: batches, compactions, grown, capacity).  The corpus is byte for byte the one
+        Corpus(the files save_batch writes) is.  ValueError before a batch's device work as for save_batch; "no sources"
+        for an empty iterable; AlacGpuError naming file and packet for a packet that was not encoded."""
+        import torch
+
+        single = isinstance(pcm, torch.Tensor) or lengths is not None
+        batches = [(pcm, lengths)] if single else pcm
+        self = cls.__new__(cls)
+        self._gpu = None
+        gpu = dev = None
+        blob, cap, base = None, 0, 0
+        stats = dict(batches=0, compactions=0, grown=0, capacity=0)
+        offs, sizes, ends, counts, frames_of = [], [], [], [], []
+        try:
+            for x, lens in batches:
+                F, C_, T, lens = _check_batch_args(x, lens, sample_rate, sample_size, frame_length)
+                fl = int(frame_length)
+                if gpu is None:
+                    dev, channels = x.device, C_
+                    row = make_cfgs([(fl, sample_size, 40, 10, 14, C_)])
+                    row["ctor_sample_size"] = sample_size      # (as the file's cookie and sample entry give it)
+                    gpu = AlacGpuContext(row, dev.index if dev.index is not None else torch.cuda.current_device())
+                elif C_ != channels or x.device != dev:
+                    raise ValueError(f"batch {stats['batches']}: {C_} channels on {x.device}, the first has {channels} on {dev}")
+                with torch.cuda.device(dev):
+                    stream = torch.cuda.current_stream(dev).cuda_stream
+                    e = _encode_slots(gpu, x, lens, fl, stream)
+                    if sum(counts) + e.n >= 1 << 32:
+                        raise ValueError("a corpus holds fewer than 2^32 packets")
+                    if blob is None:    # the first guess: three quarters of the samples' bytes (cfg2-shaped audio takes two thirds)
+                        cap = max(sum(lens) * C_ * (sample_size // 8) * 3 // 4, 4096)
+                        blob = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
+                    d_off = torch.empty(e.n, dtype=torch.int64, device=dev)
+                    while True:
+                        total, bad = _compact_slots(gpu, e, blob, base, cap, d_off, stream)
+                        stats["compactions"] += 1
+                        if bad < e.n:
+                            f, q = int(e.file_of[bad]), bad - int(np.sum(e.counts[:int(e.file_of[bad])]))
+                            raise AlacGpuError(f"file {len(counts) + f}, packet {q} was not encoded: {_status_text(int(e.d_st[bad]))}")
+                        if base + total <= cap:
+                            break
+                        # it did not fit: a larger blob, what is there copied over, and the compaction alone again
+                        cap = max(base + total, cap + cap // 2)
+                        old, blob = blob, None
+                        if base == 0:
+                            old = None                           # (nothing to keep: the old one goes first)
+                        blob = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
+                        if old is not None:
+                            blob[:base].copy_(old[:base])
+                        old = None
+                        stats["grown"] += 1
+                    base += total
+                    offs.append(d_off)
+                    sizes.append(e.d_sizes)
+                    counts += e.counts
+                    ends += [np.cumsum(e.frames[e.file_of == f]) for f in range(F)]
+                    frames_of += lens
+                    stats["batches"] += 1
+                    e = None                                     # the slot buffer goes before the next batch is encoded
+            if gpu is None:
+                raise ValueError("no sources")
+        except BaseException:
+            if gpu is not None:
+                gpu.close()
+            raise
+        blob[base:base + 64].zero_()      # (a compaction that did not fit may have left packets behind the last one)
+        stats["capacity"] = cap
+        file_first = np.zeros(len(counts) + 1, dtype=np.uint32)
+        file_first[1:] = np.cumsum(np.asarray(counts, dtype=np.int64))
+        tb = dict(pkt_end=np.concatenate(ends).astype(np.uint64), file_first=file_first,
+                  file_cfg=np.zeros(len(counts), dtype=np.uint16), cfgs=gpu.cfgs, num_frames=np.asarray(frames_of, dtype=np.int64),
+                  channels=channels, sample_rate=int(sample_rate), blob_bytes=base)
+        self._blob = blob
+        self.build_stats = stats
+        self._install(gpu.device, tb, torch.cat(offs) if len(offs) > 1 else offs[0], torch.cat(sizes) if len(sizes) > 1 else sizes[0], gpu)
+        return self
+
+    def _host_table(self, name):
+        """pkt_offset / pkt_size on the host: a corpus from PCM has them on the device only until somebody asks."""
+        if name not in self._host:
+            dtype = np.uint64 if name == "pkt_offset" else np.uint32
+            d = self._pkt_offset if name == "pkt_offset" else self._pkt_size
+            self._host[name] = d.cpu().numpy().view(dtype)[:len(self._host["pkt_end"])]
+        return self._host[name]
+
+    def save(self, dests, sample_rate=None):
+        """Write file f of the corpus as an M4A file to dests[f] (paths or writable binary file objects; sample_rate: the
+        corpus's unless given): the checkpoint of a corpus -- Corpus(those files) is the same corpus again, and for a corpus
+        from_pcm made the files are byte for byte what save_batch writes for the same arguments.  A packet's duration is the
+        difference of its pkt_end to the one in front; frame length, sample size and the Rice parameters are the file's cfg
+        row's.  The packets cross to the host file by file.  Returns the file sizes."""
+        if self._gpu is None:
+            raise AlacGpuError("the corpus is closed")
+        dests = list(dests)
+        if len(dests) != self.num_files:
+            raise ValueError(f"{self.num_files} files in the corpus and {len(dests)} destinations")
+        rate = self.sample_rate if sample_rate is None else sample_rate
+        if not isinstance(rate, (int, np.integer)) or not 1 <= int(rate) < 1 << 32:
+            raise ValueError(f"sample_rate must be a positive 32-bit integer, not {rate}")
+        h = self._host
+        off, size = self._host_table("pkt_offset").astype(np.int64), self._host_table("pkt_size").astype(np.int64)
+        out = []
+        for f, dest in enumerate(dests):
+            g0, g1 = int(h["file_first"][f]), int(h["file_first"][f + 1])
+            if g1 == g0:
+                raise ValueError(f"file {f} has no packets: nothing to write")
+            lo, hi = int(off[g0]), int(off[g1 - 1] + size[g1 - 1])
+            data = self._blob[lo:hi].cpu().numpy().tobytes()
+            packets = [data[int(off[g]) - lo:int(off[g]) - lo + int(size[g])] for g in range(g0, g1)]
+            ends = h["pkt_end"][g0:g1].astype(np.int64)
+            durations = np.diff(np.concatenate([[0], ends]))
+            c = h["cfgs"][int(h["file_cfg"][f])]
+            out.append(_write_file(dest, packets, durations, int(c["max_samples_per_frame"]), int(c["sample_size"]), self.channels,
+                                   int(rate), rice=(int(c["rice_history_mult"]), int(c["rice_initial_history"]), int(c["rice_kmodifier"]))))
+        return out
 
     def close(self):
         if getattr(self, "_gpu", None) is not None:

@@ -1,4 +1,5 @@
-// alac_corpus.h -- the crop planner's launch parameters (alac_corpus.hip), shared with the C ABI (alacgpu_api.hip).
+// alac_corpus.h -- the launch parameters of the crop planner and of the packet compaction (alac_corpus.hip), shared with the C
+// ABI (alacgpu_api.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,3 +34,45 @@ struct alac_plan_params {
 };
 
 __global__ void alac_plan_crops_kernel(alac_plan_params p);
+
+// ---- packet compaction (include/alacgpu.h: alacgpu_compact_packets_device) ----------------------------------------------------
+constexpr int ALAC_SCAN_THREADS = 256;
+constexpr uint32_t ALAC_SCAN_ITEMS = 8;                                      // consecutive elements per thread
+constexpr uint32_t ALAC_SCAN_TILE = ALAC_SCAN_THREADS * ALAC_SCAN_ITEMS;     // elements per workgroup: 2048
+constexpr int ALAC_COPY_THREADS = 256;
+constexpr uint32_t ALAC_COPY_CHUNKS = 4;                                     // 16-byte destination chunks per thread and tile
+constexpr uint64_t ALAC_COPY_TILE = (uint64_t)ALAC_COPY_THREADS * ALAC_COPY_CHUNKS * 16u;   // destination bytes per tile: 16 KiB
+
+// One level of the scan.  T = uint32_t: the packet sizes (one above `slot_bytes` counts as 0); T = uint64_t: the sums of the
+// level below.  alac_scan_sums_kernel writes a tile's sum to sums[tile]; alac_scan_tiles_kernel writes out[i] = add +
+// tile_base[tile] (0 if null) + the sum of the tile's elements in front of i, and the workgroup of the last tile the grand
+// total to total[0] if that is not null (only asked of a single-tile launch).  in == out is allowed.
+template <class T>
+struct alac_scan_params {
+    const T* in;
+    uint64_t n;
+    uint64_t slot_bytes;
+    uint64_t* sums;
+    const uint64_t* tile_base;
+    uint64_t add;
+    uint64_t* out;
+    uint64_t* total;
+};
+
+struct alac_copy_params {
+    const uint8_t* packets;       // packet p at packets + p * slot_bytes, 16-byte aligned
+    uint64_t slot_bytes;          // a multiple of 16
+    const uint32_t* sizes;        // [n]
+    const uint64_t* pkt_offset;   // [n] as the scan left it: base + the counted sizes in front
+    const uint64_t* total;        // [1]
+    uint32_t n_packets;
+    uint8_t* blob;
+    uint64_t base;
+    uint64_t capacity;
+};
+
+__global__ void alac_scan_sums_u32_kernel(alac_scan_params<uint32_t> p);
+__global__ void alac_scan_sums_u64_kernel(alac_scan_params<uint64_t> p);
+__global__ void alac_scan_tiles_u32_kernel(alac_scan_params<uint32_t> p);
+__global__ void alac_scan_tiles_u64_kernel(alac_scan_params<uint64_t> p);
+__global__ void alac_compact_copy_kernel(alac_copy_params p);

@@ -7,6 +7,16 @@
 // of up to 4096 packets takes two dependent loads per search and one of 262144 three (a binary search: 12 and 18).  Then the
 // lanes stride over the crop's K entries: neighbouring lanes read neighbouring packets of the tables and write neighbouring
 // entries of the six arrays.  Every output element has exactly one writer; all stores are plain vector stores.
+//
+// Behind it, the packet compaction (alacgpu_compact_packets_device): what brings the encoder's packets -- packet p in its own
+// slot at p * slot_bytes -- into the resident layout, back to back.  An exclusive scan of the sizes gives pkt_offset; it is
+// hierarchical in separate launches (sums of tiles of 2048, the scan of those sums, the scan of the tiles on top of it: three
+// levels reach 2^33 packets), so no workgroup ever waits for another.  The copy is spread over the DESTINATION bytes, not
+// over the packets: a thread owns 16-byte aligned chunks of the blob, finds the packet a chunk lies in with a binary search
+// of pkt_offset (narrowed to the tile's packets first) and, when the whole chunk belongs to one packet, stores it with one
+// 16-byte store built from two aligned 16-byte loads of the slot (v_alignbyte); a chunk with a packet boundary in it goes
+// dword by dword the same way, and only the dwords that hold a boundary themselves byte by byte.  So 11 KB packets move at 16
+// bytes per lane and a batch of 10-byte packets still fills its waves.  Nothing outside the copied packets is stored to.
 #include "alac_corpus.h"
 
 namespace {
@@ -105,5 +115,176 @@ __global__ __launch_bounds__(ALAC_PLAN_THREADS) void alac_plan_crops_kernel(alac
         p.dst_first[j0 + i] = first;
         p.dst_frames[j0 + i] = frames;
         p.src_skip[j0 + i] = skip;
+    }
+}
+
+// ---- packet compaction -----------------------------------------------------------------------------------------------------------
+namespace {
+
+// a size above the slot counts as 0: whatever the device data say, no read leaves a slot
+__device__ __forceinline__ uint64_t counted(uint32_t size, uint64_t slot_bytes) { return size <= slot_bytes ? size : 0u; }
+__device__ __forceinline__ uint64_t counted(uint64_t sum, uint64_t) { return sum; }
+
+// The thread's ALAC_SCAN_ITEMS consecutive elements of the tile (0 behind n) and their sum.
+template <class T>
+__device__ __forceinline__ uint64_t scan_load(const alac_scan_params<T>& p, uint64_t first, uint64_t (&v)[ALAC_SCAN_ITEMS]) {
+    uint64_t sum = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < ALAC_SCAN_ITEMS; i++) {
+        v[i] = first + i < p.n ? counted(p.in[first + i], p.slot_bytes) : 0u;
+        sum += v[i];
+    }
+    return sum;
+}
+
+// The sum of `v` over the threads in front of this one, and over the whole workgroup in `total`.
+__device__ __forceinline__ uint64_t block_exclusive(uint64_t v, uint64_t& total) {
+    __shared__ uint64_t wave_sum[ALAC_SCAN_THREADS / 64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    unsigned long long inc = v;
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const unsigned long long t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += t;
+    }
+    if (lane == 63u) wave_sum[wave] = inc;
+    __syncthreads();
+    uint64_t front = 0;
+    total = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < ALAC_SCAN_THREADS / 64; w++) {
+        if (w < wave) front += wave_sum[w];
+        total += wave_sum[w];
+    }
+    return front + inc - v;
+}
+
+template <class T>
+__device__ __forceinline__ void scan_sums(const alac_scan_params<T>& p) {
+    uint64_t v[ALAC_SCAN_ITEMS], total;
+    const uint64_t sum = scan_load(p, (uint64_t)blockIdx.x * ALAC_SCAN_TILE + (uint64_t)threadIdx.x * ALAC_SCAN_ITEMS, v);
+    (void)block_exclusive(sum, total);
+    if (threadIdx.x == 0) p.sums[blockIdx.x] = total;
+}
+
+template <class T>
+__device__ __forceinline__ void scan_tiles(const alac_scan_params<T>& p) {
+    uint64_t v[ALAC_SCAN_ITEMS], total;
+    const uint64_t first = (uint64_t)blockIdx.x * ALAC_SCAN_TILE + (uint64_t)threadIdx.x * ALAC_SCAN_ITEMS;
+    const uint64_t sum = scan_load(p, first, v);          // (every load of the tile is in front of the barrier: in == out is safe)
+    const uint64_t front = p.tile_base ? p.tile_base[blockIdx.x] : 0u;
+    uint64_t run = p.add + front + block_exclusive(sum, total);
+#pragma unroll
+    for (uint32_t i = 0; i < ALAC_SCAN_ITEMS; i++) {
+        if (first + i < p.n) p.out[first + i] = run;
+        run += v[i];
+    }
+    if (p.total && blockIdx.x == gridDim.x - 1u && threadIdx.x == 0) p.total[0] = front + total;
+}
+
+// The last packet of lo .. hi (both inclusive) whose offset is at most x; pkt_offset[lo] <= x.  Behind packets of size 0,
+// which share their offset with the next one, this is the packet that owns byte x (for x in front of the end of all packets).
+__device__ __forceinline__ uint32_t find_packet(const uint64_t* __restrict__ pkt_offset, uint32_t lo, uint32_t hi, uint64_t x) {
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+        if (pkt_offset[mid] <= x) lo = mid; else hi = mid - 1u;
+    }
+    return lo;
+}
+
+struct packet_span {
+    uint64_t begin, end;          // the packet's bytes as positions (blob offset + shift)
+    const uint8_t* src;           // its slot
+    bool fits;                    // ... and whether it is copied at all
+};
+
+__device__ __forceinline__ packet_span span_of(const alac_copy_params& p, uint32_t lo, uint32_t hi, uint64_t q, uint32_t shift) {
+    const uint32_t k = find_packet(p.pkt_offset, lo, hi, q - shift);
+    const uint64_t off = p.pkt_offset[k], size = counted(p.sizes[k], p.slot_bytes);
+    packet_span s;
+    s.begin = off + shift;
+    s.end = s.begin + size;
+    s.src = p.packets + (uint64_t)k * p.slot_bytes;
+    s.fits = off + size <= p.capacity;
+    return s;
+}
+
+// The 16-byte chunk of the blob at position q0 (a multiple of 16); positions lie `shift` in front of blob offsets so that they
+// are aligned as the addresses are.  q_lo .. q_hi: the positions of all packet bytes in front of the capacity.
+__device__ __forceinline__ void copy_chunk(const alac_copy_params& p, uint64_t q0, uint64_t q_lo, uint64_t q_hi, uint32_t shift,
+                                           uint32_t lo, uint32_t hi) {
+    const uint64_t a = q0 > q_lo ? q0 : q_lo, b = q0 + 16u < q_hi ? q0 + 16u : q_hi;
+    if (a >= b) return;
+    packet_span s = span_of(p, lo, hi, a, shift);
+    if (q0 >= s.begin && q0 + 16u <= s.end) {            // the whole chunk is one packet's: one store
+        if (!s.fits) return;
+        const uint64_t at = q0 - s.begin;                // (at + 16 <= size <= slot_bytes)
+        const uint32_t r = (uint32_t)at & 15u;
+        const uint4* v = (const uint4*)(s.src + (at - r));
+        const uint4 v0 = v[0];
+        uint4 v1 = make_uint4(0u, 0u, 0u, 0u);
+        if (r) v1 = v[1];                                // at - r + 16 < at + 16 <= slot_bytes, a multiple of 16: inside the slot
+        const bool k2 = (r & 8u) != 0, k1 = (r & 4u) != 0;
+        const uint32_t a0 = k2 ? v0.z : v0.x, a1 = k2 ? v0.w : v0.y, a2 = k2 ? v1.x : v0.z, a3 = k2 ? v1.y : v0.w;
+        const uint32_t a4 = k2 ? v1.z : v1.x, a5 = k2 ? v1.w : v1.y;
+        const uint32_t b0 = k1 ? a1 : a0, b1 = k1 ? a2 : a1, b2 = k1 ? a3 : a2, b3 = k1 ? a4 : a3, b4 = k1 ? a5 : a4;
+        const uint32_t j = r & 3u;
+        uint4 o;
+        o.x = __builtin_amdgcn_alignbyte(b1, b0, j);
+        o.y = __builtin_amdgcn_alignbyte(b2, b1, j);
+        o.z = __builtin_amdgcn_alignbyte(b3, b2, j);
+        o.w = __builtin_amdgcn_alignbyte(b4, b3, j);
+        *(uint4*)(p.blob + (q0 - shift)) = o;
+        return;
+    }
+    for (uint32_t d = 0; d < 4u; d++) {                  // a packet starts or ends in the chunk: dword by dword
+        const uint64_t dq = q0 + 4u * d;
+        const uint64_t da = dq > a ? dq : a, db = dq + 4u < b ? dq + 4u : b;
+        if (da >= db) continue;
+        if (da >= s.end) s = span_of(p, lo, hi, da, shift);
+        if (dq >= s.begin && dq + 4u <= s.end) {
+            if (!s.fits) continue;
+            const uint64_t at = dq - s.begin;
+            const uint32_t j = (uint32_t)at & 3u;
+            const uint32_t* w = (const uint32_t*)(s.src + (at - j));
+            const uint32_t w0 = w[0];
+            const uint32_t w1 = j ? w[1] : 0u;           // at - j + 4 < at + 4 <= slot_bytes: inside the slot
+            *(uint32_t*)(p.blob + (dq - shift)) = __builtin_amdgcn_alignbyte(w1, w0, j);
+            continue;
+        }
+        for (uint64_t q = da; q < db; q++) {             // the dword holds a boundary: its bytes one by one
+            if (q >= s.end) s = span_of(p, lo, hi, q, shift);
+            if (s.fits) p.blob[q - shift] = s.src[q - s.begin];
+        }
+    }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(ALAC_SCAN_THREADS) void alac_scan_sums_u32_kernel(alac_scan_params<uint32_t> p) { scan_sums(p); }
+__global__ __launch_bounds__(ALAC_SCAN_THREADS) void alac_scan_sums_u64_kernel(alac_scan_params<uint64_t> p) { scan_sums(p); }
+__global__ __launch_bounds__(ALAC_SCAN_THREADS) void alac_scan_tiles_u32_kernel(alac_scan_params<uint32_t> p) { scan_tiles(p); }
+__global__ __launch_bounds__(ALAC_SCAN_THREADS) void alac_scan_tiles_u64_kernel(alac_scan_params<uint64_t> p) { scan_tiles(p); }
+
+__global__ __launch_bounds__(ALAC_COPY_THREADS) void alac_compact_copy_kernel(alac_copy_params p) {
+    __shared__ uint32_t range[2];
+    const uint32_t shift = (uint32_t)((uintptr_t)p.blob & 15u);
+    const uint64_t end = p.base + p.total[0];
+    const uint64_t q_lo = p.base + shift, q_hi = (end < p.capacity ? end : p.capacity) + shift;
+    const uint64_t q_first = q_lo & ~(uint64_t)15;
+    for (uint64_t t = blockIdx.x;; t += gridDim.x) {     // tiles of the destination; every condition here is workgroup-uniform
+        const uint64_t tq = q_first + t * ALAC_COPY_TILE;
+        if (tq >= q_hi) break;
+        if (threadIdx.x == 0) {                          // the tile's packets: the searches below stay among them
+            const uint64_t a = tq > q_lo ? tq : q_lo, b = tq + ALAC_COPY_TILE < q_hi ? tq + ALAC_COPY_TILE : q_hi;
+            range[0] = find_packet(p.pkt_offset, 0u, p.n_packets - 1u, a - shift);
+            range[1] = find_packet(p.pkt_offset, range[0], p.n_packets - 1u, b - 1u - shift);
+        }
+        __syncthreads();
+        const uint32_t lo = range[0], hi = range[1];
+#pragma unroll
+        for (uint32_t c = 0; c < ALAC_COPY_CHUNKS; c++)
+            copy_chunk(p, tq + ((uint64_t)c * ALAC_COPY_THREADS + threadIdx.x) * 16u, q_lo, q_hi, shift, lo, hi);
+        __syncthreads();
     }
 }

@@ -79,6 +79,12 @@ struct alacgpu_ctx {
     size_t enc_code_bytes = 0, enc_pos_bytes = 0;
     hipEvent_t enc_done = nullptr;
     bool enc_used = false;
+    // alacgpu_compact_packets_device: the partial sums of the scan's upper levels (grown on demand, kept for reuse) and the
+    // event behind the last call's launches, as for the encoder's workspace
+    uint64_t* d_scan = nullptr;
+    size_t scan_bytes = 0;
+    hipEvent_t scan_done = nullptr;
+    bool scan_used = false;
     std::string last_error;
 };
 
@@ -406,6 +412,9 @@ void alacgpu_destroy(alacgpu_ctx* ctx) {
     if (ctx->enc_done) (void)hipEventDestroy(ctx->enc_done);
     if (ctx->d_enc_code) (void)hipFree(ctx->d_enc_code);
     if (ctx->d_enc_pos) (void)hipFree(ctx->d_enc_pos);
+    if (ctx->scan_used) (void)hipEventSynchronize(ctx->scan_done);
+    if (ctx->scan_done) (void)hipEventDestroy(ctx->scan_done);
+    if (ctx->d_scan) (void)hipFree(ctx->d_scan);
     if (ctx->d_cu_arrivals) cu_counters_release(ctx->device);
     if (ctx->h_frame) (void)hipHostFree(ctx->h_frame);
     if (ctx->d_cfgs) (void)hipFree(ctx->d_cfgs);
@@ -537,6 +546,100 @@ int alacgpu_plan_crops_device(alacgpu_ctx* ctx, const void* d_pkt_offset, const 
     HIP_TRY(ctx, hipLaunchKernel((const void*)alac_plan_crops_kernel, dim3((n_crops + per_wg - 1u) / per_wg), dim3(ALAC_PLAN_THREADS),
                                  kargs, 0, (hipStream_t)hip_stream));
     HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
+}
+
+int alacgpu_compact_packets_device(alacgpu_ctx* ctx, const void* d_packets, uint64_t slot_bytes, const void* d_sizes,
+                                   uint32_t n_packets, void* d_blob, uint64_t base, uint64_t blob_capacity,
+                                   void* d_pkt_offset, void* d_total, void* hip_stream) {
+    if (!ctx || !d_total || ((uintptr_t)d_total & 7u) != 0 || slot_bytes == 0 || (slot_bytes & 15u) != 0) return ALACGPU_ERR_BAD_ARG;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (n_packets == 0) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipMemsetAsync(d_total, 0, sizeof(uint64_t), stream));
+        return ALACGPU_OK;
+    }
+    if (!d_packets || !d_sizes || !d_blob || !d_pkt_offset) return ALACGPU_ERR_BAD_ARG;
+    if (((uintptr_t)d_packets & 15u) != 0 || ((uintptr_t)d_sizes & 3u) != 0 || ((uintptr_t)d_pkt_offset & 7u) != 0)
+        return ALACGPU_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the scan's levels: the sizes, the sums of their tiles, the sums of those sums' tiles (at most 1024 for 2^32 - 1 packets)
+    const uint64_t t1 = ((uint64_t)n_packets + ALAC_SCAN_TILE - 1u) / ALAC_SCAN_TILE;
+    const uint64_t t2 = (t1 + ALAC_SCAN_TILE - 1u) / ALAC_SCAN_TILE;
+    const size_t need = t1 > 1 ? sizeof(uint64_t) * (size_t)(t1 + t2) : 0;
+    if (!ctx->scan_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->scan_done, hipEventDisableTiming));
+    if (need > ctx->scan_bytes) {
+        if (ctx->scan_used) HIP_TRY(ctx, hipEventSynchronize(ctx->scan_done));   // the last call has finished with it
+        int rc = grow(ctx, ctx->d_scan, ctx->scan_bytes, need, align_up(need + need / 4, 4096));
+        if (rc) return rc;
+    } else if (need && ctx->scan_used) {
+        HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->scan_done, 0));             // (a call on another stream may still use it)
+    }
+    uint64_t* const l1 = ctx->d_scan;
+    uint64_t* const l2 = l1 ? l1 + t1 : nullptr;
+    alac_scan_params<uint32_t> s0;
+    s0.in = (const uint32_t*)d_sizes;
+    s0.n = n_packets;
+    s0.slot_bytes = slot_bytes;
+    s0.sums = l1;
+    s0.tile_base = t1 > 1 ? l1 : nullptr;
+    s0.add = base;
+    s0.out = (uint64_t*)d_pkt_offset;
+    s0.total = (uint64_t*)d_total;
+    const dim3 block(ALAC_SCAN_THREADS);
+    if (t1 > 1) {
+        alac_scan_params<uint64_t> s1;
+        s1.in = l1;
+        s1.n = t1;
+        s1.slot_bytes = 0;
+        s1.sums = l2;
+        s1.tile_base = t2 > 1 ? l2 : nullptr;
+        s1.add = 0;
+        s1.out = l1;
+        s1.total = nullptr;
+        void* a0[] = {&s0};
+        void* a1[] = {&s1};
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_sums_u32_kernel, dim3((uint32_t)t1), block, a0, 0, stream));
+        if (t2 > 1) {
+            alac_scan_params<uint64_t> s2 = s1;          // t2 <= 1024: one tile
+            s2.in = l2;
+            s2.n = t2;
+            s2.sums = nullptr;
+            s2.tile_base = nullptr;
+            s2.out = l2;
+            void* a2[] = {&s2};
+            HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_sums_u64_kernel, dim3((uint32_t)t2), block, a1, 0, stream));
+            HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_tiles_u64_kernel, dim3(1), block, a2, 0, stream));
+        }
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_tiles_u64_kernel, dim3((uint32_t)t2), block, a1, 0, stream));
+    }
+    {
+        void* a0[] = {&s0};
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_tiles_u32_kernel, dim3((uint32_t)t1), block, a0, 0, stream));
+    }
+    // the copy: tiles of the destination, as many as the packets can fill at most (the true end is d_total's, on the device)
+    const uint64_t most = slot_bytes > UINT64_MAX / n_packets ? UINT64_MAX : slot_bytes * n_packets;
+    const uint64_t room = blob_capacity > base ? blob_capacity - base : 0;
+    const uint64_t bound = std::min(most, room);
+    if (bound) {
+        alac_copy_params c;
+        c.packets = (const uint8_t*)d_packets;
+        c.slot_bytes = slot_bytes;
+        c.sizes = (const uint32_t*)d_sizes;
+        c.pkt_offset = (const uint64_t*)d_pkt_offset;
+        c.total = (const uint64_t*)d_total;
+        c.n_packets = n_packets;
+        c.blob = (uint8_t*)d_blob;
+        c.base = base;
+        c.capacity = blob_capacity;
+        const uint64_t tiles = bound / ALAC_COPY_TILE + 2u;   // (a tile more for the bytes in front of the first aligned chunk)
+        void* ac[] = {&c};
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_compact_copy_kernel, dim3((uint32_t)std::min<uint64_t>(tiles, 1u << 16)),
+                                     dim3(ALAC_COPY_THREADS), ac, 0, stream));
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->scan_done, stream));
+    ctx->scan_used = true;
     return ALACGPU_OK;
 }
 

@@ -58,6 +58,11 @@ namespace ALACdotNET.Decoder
             IntPtr dFileFirst, IntPtr dFileCfg, uint nFiles, IntPtr dCropFile, IntPtr dCropOffset, uint nCrops, uint cropFrames,
             uint entriesPerCrop, ulong dstStride, IntPtr dOffsets, IntPtr dSizes, IntPtr dCfgIdx, IntPtr dDstFirst, IntPtr dDstFrames,
             IntPtr dSrcSkip, IntPtr dLengths, IntPtr hipStream);
+        /// <summary>Compact the encoder's packets (packet p in its slot at dPackets + p * slotBytes, its size in dSizes[p]) back to
+        /// back into dBlob from byte baseOffset on: writes dPktOffset[p] (ulong) and dTotal[0] (ulong); a packet that would end behind
+        /// blobCapacity is not copied.  Every pointer a device pointer, asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_compact_packets_device(IntPtr ctx, IntPtr dPackets, ulong slotBytes, IntPtr dSizes,
+            uint nPackets, IntPtr dBlob, ulong baseOffset, ulong blobCapacity, IntPtr dPktOffset, IntPtr dTotal, IntPtr hipStream);
         /// <summary>Encode PCM in device memory (int32 or float32, interleaved or planar) to ALAC packets in device memory, one
         /// run of frames per packet, packet p at dPackets + p * slotBytes; asynchronous on hipStream.</summary>
         [DllImport(Lib)] public static extern UIntPtr alacgpu_encode_max_packet_bytes(uint frames, int sampleSize, int channels);

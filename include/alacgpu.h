@@ -293,6 +293,30 @@ int alacgpu_encode_device(alacgpu_ctx* ctx, const void* d_pcm, uint64_t src_elem
                           uint32_t n_packets, void* d_packets, uint64_t slot_bytes, void* d_sizes, void* d_status,
                           void* hip_stream);
 
+/*
+ * Compact the encoder's packets into the resident layout of a corpus (no counterpart in the reference): from packet p in its
+ * own slot at d_packets + p * slot_bytes (what alacgpu_encode_device leaves behind) to the packets back to back, byte
+ * granular, in d_blob from byte `base` on, plus the offsets the decoder and alacgpu_plan_crops_device read.  Device pointers,
+ * asynchronous on hip_stream; the library reads nothing back.
+ *   d_packets        16-byte aligned, slot_bytes a multiple of 16;  d_sizes[p] uint32: packet p's size.  A size above
+ *                    slot_bytes counts as 0: whatever the device data say, nothing outside a slot is read
+ *   d_pkt_offset[p]  uint64, written: base + the counted sizes of the packets q < p (base of any alignment: a second batch
+ *                    lands right behind the first; base + the total must fit 64 bits)
+ *   d_total[0]       uint64, written: the sum of the counted sizes
+ *   d_blob           any alignment.  Packet p is copied to d_blob + d_pkt_offset[p] iff d_pkt_offset[p] + its size <=
+ *                    blob_capacity; a packet that does not fit is not copied at all (the caller sees base + total >
+ *                    blob_capacity, grows the blob and calls again).  No byte of d_blob outside the copied packets is
+ *                    written.  d_pkt_offset and d_total are written in full either way.
+ * n_packets == 0: d_total[0] = 0 and nothing else.  The ctx keeps the scan's partial sums (8 bytes per 2048 packets); calls
+ * on one ctx run one after the other on the device.  The scan is a hierarchy of launches (no workgroup waits for another);
+ * the copy is spread over the destination's bytes, so many small packets cost what few large ones do.
+ * ALACGPU_ERR_BAD_ARG: a NULL ctx or array, slot_bytes 0 or not a multiple of 16, a misaligned d_packets (16), d_sizes (4),
+ * d_pkt_offset (8) or d_total (8).
+ */
+int alacgpu_compact_packets_device(alacgpu_ctx* ctx, const void* d_packets, uint64_t slot_bytes, const void* d_sizes,
+                                   uint32_t n_packets, void* d_blob, uint64_t base, uint64_t blob_capacity,
+                                   void* d_pkt_offset, void* d_total, void* hip_stream);
+
 /* Single-packet drop-in for `int DecodeFrame(byte[] inbuffer, int[] outbuffer)` (AlacFile.cs:428):
  * writes the reference's own int[] layout (24-bit: one int per byte) and returns its byte count in
  * *out_bytes.  status as above (the C# shim rethrows the reference's exceptions from it). */

@@ -63,6 +63,8 @@ SYMBOLS = {
     "alacgpu_plan_crops_device": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_uint32, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32,
                                             C.c_uint64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alacgpu_compact_packets_device": (C.c_int, [_VP, _VP, C.c_uint64, _VP, C.c_uint32, _VP, C.c_uint64, C.c_uint64, _VP, _VP, _VP]),
+    "alacgpu_stage_packets_device": (C.c_int, [_VP, _VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP, C.c_uint32, _VP, C.c_uint64, _VP, _VP,
+                                               _VP]),
     "alacgpu_encode_max_packet_bytes": (C.c_size_t, [C.c_uint32, C.c_int, C.c_int]),
     "alacgpu_encode_device": (C.c_int, [_VP, _VP, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP, C.c_uint32,
                                         _VP, C.c_uint64, _VP, _VP, _VP]),
@@ -309,6 +311,19 @@ class AlacGpuContext(_Closing):
         packets is written.  Asynchronous on `stream` (raw hipStream_t); nothing is read back."""
         rc = lib().alacgpu_compact_packets_device(self._ctx, _dp(d_packets), slot_bytes, _dp(d_sizes), n_packets, _dp(d_blob), base,
                                                   blob_capacity, _dp(d_pkt_offset), _dp(d_total), _VP(stream))
+        _check(rc, self._ctx)
+
+    def stage_packets_device(self, d_blob_lo, lo_bytes, blob_hi, hi_bytes, d_src_offset, d_sizes, n_packets, d_stage, stage_capacity,
+                             d_stage_offset, d_total, stream=0):
+        """alacgpu_stage_packets_device: gather the n_packets packets at d_src_offset / d_sizes (int64 / int32 device tensors,
+        a plan's) out of the source space -- d_blob_lo (a device tensor or None) first, blob_hi (a device tensor, the address
+        of page-locked host memory, or None) behind it -- into d_stage (uint8 device tensor), each at the next multiple of
+        16; d_stage_offset[j] (int64 device tensor) = where packet j went, d_total[0] the bytes all of them take.  A packet
+        that would end behind stage_capacity is not copied.  Asynchronous on `stream` (raw hipStream_t); nothing is read
+        back."""
+        hi = _dp(blob_hi) if hasattr(blob_hi, "data_ptr") else (_VP(blob_hi) if blob_hi else None)
+        rc = lib().alacgpu_stage_packets_device(self._ctx, _dp(d_blob_lo), lo_bytes, hi, hi_bytes, _dp(d_src_offset), _dp(d_sizes),
+                                                n_packets, _dp(d_stage), stage_capacity, _dp(d_stage_offset), _dp(d_total), _VP(stream))
         _check(rc, self._ctx)
 
     def set_output_format(self, fmt):
@@ -871,4 +886,5 @@ class AlacFile:
 
 
 # ---- a corpus resident in HBM and its random crops (alacgpu_plan_crops_device) -----------------------------------------------------
-from .corpus import Corpus, compact_plan_host, corpus_plan_host, corpus_tables, entries_per_crop  # noqa: E402  (it imports the names above)
+from .corpus import (Corpus, compact_plan_host, corpus_plan_host, corpus_tables, entries_per_crop,  # noqa: E402  (it imports the names above)
+                     stage_bytes_per_crop, stage_plan_host, tier_split)

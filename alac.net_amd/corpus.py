@@ -9,14 +9,19 @@ host hands over (file, first frame) pairs -- or nothing at all when they are dev
 alacgpu_encode_device call into slots, one alacgpu_compact_packets_device call that packs them behind the packets so far (and
 writes their offsets), one small read.  `Corpus.save` writes any corpus back as M4A files: its checkpoint.
 
-`corpus_tables` (the resident tables as numpy arrays), `entries_per_crop` (the K bound), `corpus_plan_host` and
-`compact_plan_host` (the two kernels' specifications in numpy) need no device.
+`Corpus(sources, hbm_bytes=n)` keeps only the first files, as many as fit n bytes, in HBM and the others in page-locked host
+memory.  A step is then three calls: between the plan and the decode, alacgpu_stage_packets_device gathers the plan's packets
+from both tiers into a small staging blob in HBM, and the decode reads that.
+
+`corpus_tables` (the resident tables as numpy arrays), `entries_per_crop` (the K bound), `stage_bytes_per_crop` (the staging
+bound), `tier_split`, `corpus_plan_host`, `compact_plan_host` and `stage_plan_host` (the three kernels' specifications in
+numpy) need no device.
 """
 import numpy as np
 
-from . import (MAX_FRAME, ST_OK, ST_UNSUPPORTED_ELEMENT, ST_UNSUPPORTED_PREDTYPE, AlacGpuContext, AlacGpuError, _Closing,
-               _check, _check_batch_args, _compact_slots, _dp, _encode_slots, _frame_count, _status_text, _torch_dtype, _VP,
-               _write_file, lib, make_cfgs)
+from . import (MAX_FRAME, ST_OK, ST_UNSUPPORTED_ELEMENT, ST_UNSUPPORTED_PREDTYPE, AlacGpuContext, AlacGpuError, PinnedBuffer,
+               _Closing, _check, _check_batch_args, _compact_slots, _dp, _encode_slots, _frame_count, _status_text, _torch_dtype,
+               _VP, _write_file, lib, make_cfgs)
 
 PAD_CFG = 0xFFFF        # a padding entry's cfg_idx: never a row of the context, so the kernels switch the entry off
 MAX_CFGS = 65535
@@ -60,17 +65,17 @@ def corpus_tables(tables):
                 num_frames=num_frames, file_base=file_base, channels=channels, sample_rate=rate, blob_bytes=blob_bytes)
 
 
-def entries_per_crop(pkt_end, file_first, num_frames):
-    """K(L): the most packets a window of num_frames frames takes in any file (the largest p1 - p0 of window_plan over every
-    offset), exact.  Inside the packet a window starts in, p0 is fixed and p1 grows with the offset, so the window from that
-    packet's last frame reaches furthest; a window from frame 0 starts at packet 0 whatever the durations.  Files of one frame
-    length fl: ceil((L - 1) / fl) + 1 when the file is long enough."""
+def _widest_windows(pkt_end, file_first, num_frames):
+    """The windows of num_frames frames that take the most packets: (g0, g1), two int64 arrays of global packet ranges, among
+    which every window's range p0 .. p1 of window_plan is contained in one.  Inside the packet a window starts in, p0 is fixed
+    and p1 grows with the offset, so the window from that packet's last frame reaches furthest; a window from frame 0 starts
+    at packet 0 whatever the durations."""
     pkt_end = np.asarray(pkt_end).astype(np.int64)
     file_first = np.asarray(file_first).astype(np.int64)
     L = int(num_frames)
     F = len(file_first) - 1
     if L <= 0 or len(pkt_end) == 0:
-        return 0
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
     counts = np.diff(file_first)
     file_of = np.repeat(np.arange(F, dtype=np.int64), counts)
     local = np.arange(len(pkt_end), dtype=np.int64) - file_first[file_of]
@@ -90,7 +95,41 @@ def entries_per_crop(pkt_end, file_first, num_frames):
         p1 = np.searchsorted(file_of * M + start, f * M + end, side="left") - file_first[f]
     else:
         p1 = np.array([np.searchsorted(start[file_first[k]:file_first[k + 1]], e, side="left") for k, e in zip(f, end)], dtype=np.int64)
-    return int(np.maximum(p1 - p0, 0).max())
+    p1 = np.maximum(p1, p0)
+    return file_first[f] + p0, file_first[f] + p1
+
+
+def entries_per_crop(pkt_end, file_first, num_frames):
+    """K(L): the most packets a window of num_frames frames takes in any file (the largest p1 - p0 of window_plan over every
+    offset), exact: see _widest_windows.  Files of one frame length fl: ceil((L - 1) / fl) + 1 when the file is long enough."""
+    g0, g1 = _widest_windows(pkt_end, file_first, num_frames)
+    return int((g1 - g0).max()) if len(g0) else 0
+
+
+def stage_bytes_per_crop(pkt_size, pkt_end, file_first, num_frames):
+    """S(L): the most bytes a window of num_frames frames takes in a staging blob, where every packet starts at a multiple of
+    16 -- the largest sum of the sizes, each rounded up to 16, over the packets p0 .. p1 of window_plan over every offset of
+    every file, exact (some offset reaches it; see _widest_windows: the widest windows contain every other window's packets).
+    Never more than the largest such sum over K(L) consecutive packets of one file, and equal to it where one file both takes
+    K(L) packets and has the largest ones.  B crops never stage more than B * S(L) bytes."""
+    g0, g1 = _widest_windows(pkt_end, file_first, num_frames)
+    if not len(g0):
+        return 0
+    rounded = (np.asarray(pkt_size).astype(np.int64) + 15) // 16 * 16
+    run = np.concatenate([[0], np.cumsum(rounded)])
+    return int((run[g1] - run[g0]).max())
+
+
+def tier_split(file_bytes, hbm_bytes):
+    """How many of a corpus's files go to the device blob: the longest prefix of the files (in order; file_bytes[f]: the packet
+    bytes of file f) whose bytes together fit hbm_bytes; every file behind it goes to the host blob, so a file is never
+    split.  None: all of them.  ValueError: hbm_bytes negative or not an integer."""
+    file_bytes = np.asarray(file_bytes).astype(np.int64)
+    if hbm_bytes is None:
+        return len(file_bytes)
+    if isinstance(hbm_bytes, (bool, np.bool_)) or not isinstance(hbm_bytes, (int, np.integer)) or int(hbm_bytes) < 0:
+        raise ValueError(f"hbm_bytes must be None or a non-negative integer, not {hbm_bytes!r}")
+    return int(np.searchsorted(np.cumsum(file_bytes), int(hbm_bytes), side="right"))
 
 
 def corpus_plan_host(pkt_offset, pkt_size, pkt_end, file_first, file_cfg, crop_file, crop_offset, num_frames, entries, dst_stride):
@@ -151,44 +190,90 @@ def compact_plan_host(sizes, slot_bytes, base, capacity):
     return pkt_offset.astype(np.uint64), total, np.asarray(copied, dtype=bool)
 
 
+def stage_plan_host(src_offset, sizes, lo_bytes, hi_bytes, capacity):
+    """alacgpu_stage_packets_device on the host, in numpy: the kernel's specification (tests compare the two; the product
+    never comes here).  The source space is lo_bytes of one part and hi_bytes of another behind it; a packet counts with its
+    size when it lies wholly inside one part, else as 0.  Returns (stage_offset uint64 [n]: the counted sizes in front of a
+    packet, each rounded up to 16, total: that sum over all packets whatever the capacity, copied bool [n]: the packets with
+    a counted size above 0 and stage_offset + the rounded size <= capacity -- those, whole, are all that is copied)."""
+    off = [int(x) for x in np.asarray(src_offset, dtype=np.uint64)]
+    size = [int(x) for x in np.asarray(sizes, dtype=np.uint32)]
+    lo, hi = int(lo_bytes), int(hi_bytes)
+    inside = [(o < lo and o + n <= lo) or (o >= lo and o + n <= lo + hi) for o, n in zip(off, size)]
+    rounded = np.array([(n + 15) // 16 * 16 if ok else 0 for n, ok in zip(size, inside)], dtype=np.uint64).reshape(-1)
+    ends = np.cumsum(rounded, dtype=np.uint64)
+    stage_offset = ends - rounded
+    total = int(ends[-1]) if len(ends) else 0
+    copied = np.array([r > 0 and int(e) <= int(capacity) for r, e in zip(rounded, ends)], dtype=bool).reshape(-1)
+    return stage_offset.astype(np.uint64), total, copied
+
+
 class Corpus(_Closing):
     """M4A files resident in HBM, compressed: Corpus(sources, device=0) demuxes every source once (file bytes, a path or a
     seekable binary file object, as for `load`), uploads the packet bytes file by file into one device blob and the packet
     tables next to it, and keeps one alacgpu_ctx until close().  All files share channel count and sample rate (ValueError
     naming the first that differs); 16- and 24-bit may mix; files that share a stream cfg share its row (at most 65535
     distinct ones).  num_files, num_frames (int64 host array [F]), channels, sample_rate.  Calls on one Corpus belong on one
-    stream: the plan arrays are reused from call to call."""
+    stream: the plan arrays are reused from call to call.
 
-    def __init__(self, sources, device=0):
+    hbm_bytes: None keeps every file in HBM.  An integer keeps the longest prefix of the files whose packet bytes fit that
+    many bytes in HBM and every file behind it in one page-locked host blob (`tier_split`; a file is never split, 0 puts all
+    of them on the host; ValueError when negative or not an integer); tier_bytes is (device bytes, host bytes).  Crops of
+    such a corpus are what they are of the resident one, bit for bit: a step additionally gathers the packets it needs from
+    both tiers into a staging blob in HBM (alacgpu_stage_packets_device; at most batch * stage_bytes_per_crop(num_frames)
+    bytes, kept and reused), and the decode reads that.  When every file fits, the corpus is the resident one."""
+
+    def __init__(self, sources, device=0, hbm_bytes=None):
         import torch
 
         from .container import header_table, packet_table
 
-        self._gpu = None
+        self._gpu = self._pinned = None
         sources = list(sources)
-        # the headers first (no packet bytes): the blob's size; a file object is read twice from where it stands
+        # the headers first (no packet bytes): the blobs' sizes; a file object is read twice from where it stands
         where = [s.tell() if hasattr(s, "tell") and hasattr(s, "seek") else None for s in sources]
-        total = 0
+        file_bytes = []
         for s, pos in zip(sources, where):
-            total += int(header_table(s)["sizes"].sum(dtype=np.int64))
+            file_bytes.append(int(header_table(s)["sizes"].sum(dtype=np.int64)))
             if pos is not None:
                 s.seek(pos)
+        on_device = tier_split(file_bytes, hbm_bytes)
+        total, lo_bytes = sum(file_bytes), sum(file_bytes[:on_device])
         dev = torch.device("cuda", device)
         # readable up to blob_bytes rounded up to 16, as every decode entry point wants it (torch's allocations are aligned)
-        self._blob = torch.zeros(total + 64, dtype=torch.uint8, device=dev)
-        heads, base = [], 0
-        for s in sources:
-            t = packet_table(s)
-            n = int(t["sizes"].sum(dtype=np.int64))
-            if n:
-                self._blob[base:base + n].copy_(torch.from_numpy(np.array(t["blob"][:n])))
-            base += n
-            heads.append({k: t[k] for k in ("sizes", "durations", "cfg", "num_channels", "sample_rate")})
-        if base != total:
-            raise ValueError("a source changed while it was read")
-        self._install(device, corpus_tables(heads))
+        self._blob = torch.zeros(lo_bytes + 64, dtype=torch.uint8, device=dev)
+        try:
+            if total > lo_bytes:
+                with torch.cuda.device(dev):
+                    self._pinned = PinnedBuffer(total - lo_bytes + 64, np.uint8)
+                self._pinned.array[total - lo_bytes:] = 0
+            heads, base = [], 0
+            for f, s in enumerate(sources):
+                t = packet_table(s)
+                n = int(t["sizes"].sum(dtype=np.int64))
+                if n and f < on_device:
+                    self._blob[base:base + n].copy_(torch.from_numpy(np.array(t["blob"][:n])))
+                elif n:
+                    if base - lo_bytes + n > total - lo_bytes:
+                        raise ValueError("a source changed while it was read")
+                    self._pinned.array[base - lo_bytes:base - lo_bytes + n] = t["blob"][:n]
+                base += n
+                if f + 1 == on_device and base != lo_bytes:
+                    raise ValueError("a source changed while it was read")
+                heads.append({k: t[k] for k in ("sizes", "durations", "cfg", "num_channels", "sample_rate")})
+            if base != total:
+                raise ValueError("a source changed while it was read")
+            self._install(device, corpus_tables(heads), host_bytes=total - lo_bytes)
+        except BaseException:
+            self._free_pinned()
+            raise
 
-    def _install(self, device, tb, d_pkt_offset=None, d_pkt_size=None, gpu=None):
+    def _free_pinned(self):
+        if getattr(self, "_pinned", None) is not None:
+            self._pinned.close()
+            self._pinned = None
+
+    def _install(self, device, tb, d_pkt_offset=None, d_pkt_size=None, gpu=None, host_bytes=0):
         """The end of both constructors: self._blob holds the packets; tb: the host tables (pkt_end, file_first, file_cfg, cfgs,
         num_frames, channels, sample_rate, blob_bytes, and pkt_offset and pkt_size unless they are on the device already: the
         two tensors; `save` fetches them then); gpu: the context to keep, if there is one already."""
@@ -211,8 +296,14 @@ class Corpus(_Closing):
         self._pkt_end, self._file_first = up(tb["pkt_end"], np.int64), up(tb["file_first"], np.int32)
         self._file_cfg = up(tb["file_cfg"], np.int16)
         self._d_num_frames = torch.from_numpy(self.num_frames).to(dev)
-        self._K = {}
+        self._K, self._S = {}, {}
         self._plan, self._capacity, self._last = None, 0, 0
+        # the tiers: the first bytes of the packets' address space are self._blob's, the others the page-locked blob's
+        self._pinned = getattr(self, "_pinned", None)
+        self._hi_bytes = int(host_bytes)
+        self._lo_bytes = self._blob_bytes - self._hi_bytes
+        self._stage = self._stage_plan = None
+        self._stage_room, self._stage_entries, self._stage_bytes = 0, 0, 0
         self._gpu = gpu if gpu is not None else AlacGpuContext(tb["cfgs"], device)
 
     @classmethod
@@ -330,7 +421,10 @@ class Corpus(_Closing):
             if g1 == g0:
                 raise ValueError(f"file {f} has no packets: nothing to write")
             lo, hi = int(off[g0]), int(off[g1 - 1] + size[g1 - 1])
-            data = self._blob[lo:hi].cpu().numpy().tobytes()
+            if self._hi_bytes and lo >= self._lo_bytes:       # a file of the host tier: straight from the host blob
+                data = self._pinned.array[lo - self._lo_bytes:hi - self._lo_bytes].tobytes()
+            else:
+                data = self._blob[lo:hi].cpu().numpy().tobytes()
             packets = [data[int(off[g]) - lo:int(off[g]) - lo + int(size[g])] for g in range(g0, g1)]
             ends = h["pkt_end"][g0:g1].astype(np.int64)
             durations = np.diff(np.concatenate([[0], ends]))
@@ -343,7 +437,37 @@ class Corpus(_Closing):
         if getattr(self, "_gpu", None) is not None:
             self._gpu.close()
             self._gpu = None
-            self._blob = self._plan = None
+            self._blob = self._plan = self._stage = self._stage_plan = None
+        self._free_pinned()
+
+    @property
+    def tier_bytes(self):
+        """(device_bytes, host_bytes): the packet bytes in HBM and those in page-locked host memory"""
+        return self._lo_bytes, self._hi_bytes
+
+    def stage_bytes_per_crop(self, num_frames):
+        """S for crops of num_frames frames: the bytes the staging blob reserves per crop (computed once per length)."""
+        L = int(num_frames)
+        if L not in self._S:
+            self._S[L] = stage_bytes_per_crop(self._host_table("pkt_size"), self._host["pkt_end"], self._host["file_first"], L)
+        return self._S[L]
+
+    def _stage_arrays(self, n, room):
+        """The staging blob (room bytes and 64 more: readable past blob_bytes, as the resident blob is) and the staged offsets
+        of n entries, kept and reused while neither grows."""
+        import torch
+
+        room = max(room, 16)        # (a step whose packets are all empty still hands the library a blob)
+        if room > self._stage_room:
+            self._stage = None      # (the old one goes first)
+            self._stage = torch.zeros(room + 64, dtype=torch.uint8, device=self._dev)
+            self._stage_room = room
+        if n > self._stage_entries:
+            self._stage_plan = None
+            self._stage_plan = dict(offsets=torch.empty(n, dtype=torch.int64, device=self._dev),
+                                    total=torch.zeros(1, dtype=torch.int64, device=self._dev))
+            self._stage_entries = n
+        return self._stage, self._stage_plan
 
     def entries_per_crop(self, num_frames):
         """K for crops of num_frames frames: the entries the plan reserves per crop (computed once per length)."""
@@ -447,7 +571,17 @@ class Corpus(_Closing):
                                                B, L, K, C_ * L, _dp(pl["offsets"]), _dp(pl["sizes"]), _dp(pl["cfg_idx"]),
                                                _dp(pl["dst_first"]), _dp(pl["dst_frames"]), _dp(pl["src_skip"]), _dp(lengths),
                                                _VP(stream)), ctx._ctx)
-        ctx.decode_window_into_device(self._blob, self._blob_bytes, pl["offsets"], pl["sizes"], pl["cfg_idx"], n, pl["dst_first"],
+        blob, blob_bytes, offsets = self._blob, self._blob_bytes, pl["offsets"]
+        if self._hi_bytes:
+            # the packets of this step from both tiers into the staging blob, each at a multiple of 16; the decode reads that
+            blob_bytes = B * self.stage_bytes_per_crop(L)
+            blob, sp = self._stage_arrays(n, blob_bytes)
+            self._stage_bytes = blob_bytes
+            offsets = sp["offsets"]
+            ctx.stage_packets_device(self._blob if self._lo_bytes else None, self._lo_bytes, self._pinned.array.ctypes.data,
+                                     self._hi_bytes, pl["offsets"], pl["sizes"], n, blob, blob_bytes, offsets, sp["total"],
+                                     stream=stream)
+        ctx.decode_window_into_device(blob, blob_bytes, offsets, pl["sizes"], pl["cfg_idx"], n, pl["dst_first"],
                                       pl["dst_frames"], pl["src_skip"], out, C_, "planar", L, None, pl["status"], stream=stream)
         self._last = n
         if check:
@@ -468,6 +602,12 @@ class Corpus(_Closing):
         offs = torch.minimum(torch.floor(u * (span + 1).to(torch.float64)).to(torch.int64), span)
         pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check)
         return pcm, lengths, files, offs
+
+    def last_staged_bytes(self):
+        """The bytes the last crops call of a tiered corpus staged (every packet rounded up to 16): a device int64 tensor of one
+        element, no synchronisation; None for a corpus without a host tier or before the first such call.  It is a view of an
+        array the next call overwrites."""
+        return self._stage_plan["total"] if self._stage_plan is not None else None
 
     def last_status(self):
         """The last crops call's per-entry statuses (ALACGPU_ST_*, as the kernels wrote them) and the mask of the entries that
@@ -500,7 +640,10 @@ class Corpus(_Closing):
         n, B, pl = self._last, lengths.shape[0], self._plan
         st, valid = pl["status"][:n], pl["cfg_idx"][:n] != -1
         # statuses as AlacContext.ReadBatch reads them (_normalise_status): the element type is the packet's first three bits
-        first_byte = self._blob[pl["offsets"][:n].clamp(max=max(self._blob_bytes - 1, 0))]
+        if self._hi_bytes:      # (where the packet is now: in the staging blob)
+            first_byte = self._stage[self._stage_plan["offsets"][:n].clamp(max=max(self._stage_bytes - 1, 0))]
+        else:
+            first_byte = self._blob[pl["offsets"][:n].clamp(max=max(self._blob_bytes - 1, 0))]
         mono = (first_byte >> 5) == 0
         ok = (st == ST_OK) | (st == ST_UNSUPPORTED_ELEMENT) | ((st == ST_UNSUPPORTED_PREDTYPE) & mono)
         bad_entry = torch.where(valid & ~ok, pl["iota"][:n], n).min()

@@ -17,6 +17,13 @@
 // 16-byte store built from two aligned 16-byte loads of the slot (v_alignbyte); a chunk with a packet boundary in it goes
 // dword by dword the same way, and only the dwords that hold a boundary themselves byte by byte.  So 11 KB packets move at 16
 // bytes per lane and a batch of 10-byte packets still fills its waves.  Nothing outside the copied packets is stored to.
+//
+// And the packet staging (alacgpu_stage_packets_device): the gather of a plan's packets out of a corpus that lies partly in
+// page-locked host memory into a small blob in HBM, each packet at the next multiple of 16.  The same scan (a size counts
+// rounded up to 16, or as 0 when the packet does not lie inside one of the two parts) and the same copy over destination
+// chunks, but shaped for the link: a thread first finds the sources of all its chunks of a tile, then issues every load of
+// them -- up to 2 * ALAC_STAGE_CHUNKS independent 16-byte loads per lane -- and only then combines and stores.  Every
+// destination chunk is one packet's, so there is no dword or byte path.
 #include "alac_corpus.h"
 
 namespace {
@@ -125,13 +132,25 @@ namespace {
 __device__ __forceinline__ uint64_t counted(uint32_t size, uint64_t slot_bytes) { return size <= slot_bytes ? size : 0u; }
 __device__ __forceinline__ uint64_t counted(uint64_t sum, uint64_t) { return sum; }
 
+// staging: a packet counts, rounded up to 16, when it lies wholly inside one of the two parts of the source space (offsets
+// below lo_bytes: the first part).  Whatever the device data say, no read leaves the parts
+__device__ __forceinline__ uint64_t staged(uint32_t size, uint64_t off, uint64_t lo_bytes, uint64_t hi_bytes) {
+    const bool in_lo = off < lo_bytes && size <= lo_bytes - off;
+    const bool in_hi = off >= lo_bytes && off - lo_bytes <= hi_bytes && size <= hi_bytes - (off - lo_bytes);
+    return in_lo || in_hi ? ((uint64_t)size + 15u) & ~(uint64_t)15 : 0u;
+}
+
 // The thread's ALAC_SCAN_ITEMS consecutive elements of the tile (0 behind n) and their sum.
-template <class T>
+template <bool STAGE, class T>
 __device__ __forceinline__ uint64_t scan_load(const alac_scan_params<T>& p, uint64_t first, uint64_t (&v)[ALAC_SCAN_ITEMS]) {
     uint64_t sum = 0;
 #pragma unroll
     for (uint32_t i = 0; i < ALAC_SCAN_ITEMS; i++) {
-        v[i] = first + i < p.n ? counted(p.in[first + i], p.slot_bytes) : 0u;
+        v[i] = 0u;
+        if (first + i < p.n) {
+            if constexpr (STAGE) v[i] = staged(p.in[first + i], p.src_offset[first + i], p.lo_bytes, p.hi_bytes);
+            else v[i] = counted(p.in[first + i], p.slot_bytes);
+        }
         sum += v[i];
     }
     return sum;
@@ -159,19 +178,19 @@ __device__ __forceinline__ uint64_t block_exclusive(uint64_t v, uint64_t& total)
     return front + inc - v;
 }
 
-template <class T>
+template <bool STAGE, class T>
 __device__ __forceinline__ void scan_sums(const alac_scan_params<T>& p) {
     uint64_t v[ALAC_SCAN_ITEMS], total;
-    const uint64_t sum = scan_load(p, (uint64_t)blockIdx.x * ALAC_SCAN_TILE + (uint64_t)threadIdx.x * ALAC_SCAN_ITEMS, v);
+    const uint64_t sum = scan_load<STAGE>(p, (uint64_t)blockIdx.x * ALAC_SCAN_TILE + (uint64_t)threadIdx.x * ALAC_SCAN_ITEMS, v);
     (void)block_exclusive(sum, total);
     if (threadIdx.x == 0) p.sums[blockIdx.x] = total;
 }
 
-template <class T>
+template <bool STAGE, class T>
 __device__ __forceinline__ void scan_tiles(const alac_scan_params<T>& p) {
     uint64_t v[ALAC_SCAN_ITEMS], total;
     const uint64_t first = (uint64_t)blockIdx.x * ALAC_SCAN_TILE + (uint64_t)threadIdx.x * ALAC_SCAN_ITEMS;
-    const uint64_t sum = scan_load(p, first, v);          // (every load of the tile is in front of the barrier: in == out is safe)
+    const uint64_t sum = scan_load<STAGE>(p, first, v);          // (every load of the tile is in front of the barrier: in == out is safe)
     const uint64_t front = p.tile_base ? p.tile_base[blockIdx.x] : 0u;
     uint64_t run = p.add + front + block_exclusive(sum, total);
 #pragma unroll
@@ -190,6 +209,21 @@ __device__ __forceinline__ uint32_t find_packet(const uint64_t* __restrict__ pkt
         if (pkt_offset[mid] <= x) lo = mid; else hi = mid - 1u;
     }
     return lo;
+}
+
+// Sixteen bytes from byte r (0 .. 15) of the 32 bytes v0, v1
+__device__ __forceinline__ uint4 align16(uint4 v0, uint4 v1, uint32_t r) {
+    const bool k2 = (r & 8u) != 0, k1 = (r & 4u) != 0;
+    const uint32_t a0 = k2 ? v0.z : v0.x, a1 = k2 ? v0.w : v0.y, a2 = k2 ? v1.x : v0.z, a3 = k2 ? v1.y : v0.w;
+    const uint32_t a4 = k2 ? v1.z : v1.x, a5 = k2 ? v1.w : v1.y;
+    const uint32_t b0 = k1 ? a1 : a0, b1 = k1 ? a2 : a1, b2 = k1 ? a3 : a2, b3 = k1 ? a4 : a3, b4 = k1 ? a5 : a4;
+    const uint32_t j = r & 3u;
+    uint4 o;
+    o.x = __builtin_amdgcn_alignbyte(b1, b0, j);
+    o.y = __builtin_amdgcn_alignbyte(b2, b1, j);
+    o.z = __builtin_amdgcn_alignbyte(b3, b2, j);
+    o.w = __builtin_amdgcn_alignbyte(b4, b3, j);
+    return o;
 }
 
 struct packet_span {
@@ -224,17 +258,7 @@ __device__ __forceinline__ void copy_chunk(const alac_copy_params& p, uint64_t q
         const uint4 v0 = v[0];
         uint4 v1 = make_uint4(0u, 0u, 0u, 0u);
         if (r) v1 = v[1];                                // at - r + 16 < at + 16 <= slot_bytes, a multiple of 16: inside the slot
-        const bool k2 = (r & 8u) != 0, k1 = (r & 4u) != 0;
-        const uint32_t a0 = k2 ? v0.z : v0.x, a1 = k2 ? v0.w : v0.y, a2 = k2 ? v1.x : v0.z, a3 = k2 ? v1.y : v0.w;
-        const uint32_t a4 = k2 ? v1.z : v1.x, a5 = k2 ? v1.w : v1.y;
-        const uint32_t b0 = k1 ? a1 : a0, b1 = k1 ? a2 : a1, b2 = k1 ? a3 : a2, b3 = k1 ? a4 : a3, b4 = k1 ? a5 : a4;
-        const uint32_t j = r & 3u;
-        uint4 o;
-        o.x = __builtin_amdgcn_alignbyte(b1, b0, j);
-        o.y = __builtin_amdgcn_alignbyte(b2, b1, j);
-        o.z = __builtin_amdgcn_alignbyte(b3, b2, j);
-        o.w = __builtin_amdgcn_alignbyte(b4, b3, j);
-        *(uint4*)(p.blob + (q0 - shift)) = o;
+        *(uint4*)(p.blob + (q0 - shift)) = align16(v0, v1, r);
         return;
     }
     for (uint32_t d = 0; d < 4u; d++) {                  // a packet starts or ends in the chunk: dword by dword
@@ -259,12 +283,43 @@ __device__ __forceinline__ void copy_chunk(const alac_copy_params& p, uint64_t q
     }
 }
 
+// Where the 16-byte chunk at position q of the staging blob comes from: v, the aligned 16 bytes of the source that hold its
+// first byte (null: the chunk is not copied), r, that byte's place in them, and whether the 16 bytes behind v hold bytes of
+// the packet too.  lo .. hi: the tile's packets.
+struct stage_src {
+    const uint4* v;
+    uint32_t r;
+    bool two;
+};
+
+__device__ __forceinline__ stage_src stage_locate(const alac_stage_params& p, uint64_t q, uint64_t q_hi, uint32_t lo, uint32_t hi) {
+    stage_src s;
+    s.v = nullptr;
+    s.r = 0;
+    s.two = false;
+    if (q >= q_hi) return s;
+    const uint32_t k = find_packet(p.stage_offset, lo, hi, q);
+    const uint64_t off = p.stage_offset[k], src = p.src_offset[k];
+    const uint32_t size = p.sizes[k];
+    const uint64_t room = staged(size, src, p.lo_bytes, p.hi_bytes);     // 0, or the packet lies inside one part
+    const uint64_t at = q - off;                                         // (off <= q < capacity)
+    if (at >= room || room > p.capacity - off) return s;                 // a packet that does not fit is not copied at all
+    const bool in_lo = src < p.lo_bytes;
+    const uint64_t from = (in_lo ? src : src - p.lo_bytes) + at;         // at < size: a byte of the packet
+    s.r = (uint32_t)from & 15u;
+    s.v = (const uint4*)((in_lo ? p.lo : p.hi) + (from - s.r));
+    s.two = s.r != 0 && 16u - s.r < size - at;                           // only then v[1] holds a byte of the packet: inside the part
+    return s;
+}
+
 }  // namespace
 
-__global__ __launch_bounds__(ALAC_SCAN_THREADS) void alac_scan_sums_u32_kernel(alac_scan_params<uint32_t> p) { scan_sums(p); }
-__global__ __launch_bounds__(ALAC_SCAN_THREADS) void alac_scan_sums_u64_kernel(alac_scan_params<uint64_t> p) { scan_sums(p); }
-__global__ __launch_bounds__(ALAC_SCAN_THREADS) void alac_scan_tiles_u32_kernel(alac_scan_params<uint32_t> p) { scan_tiles(p); }
-__global__ __launch_bounds__(ALAC_SCAN_THREADS) void alac_scan_tiles_u64_kernel(alac_scan_params<uint64_t> p) { scan_tiles(p); }
+__global__ __launch_bounds__(ALAC_SCAN_THREADS) void alac_scan_sums_u32_kernel(alac_scan_params<uint32_t> p) { scan_sums<false>(p); }
+__global__ __launch_bounds__(ALAC_SCAN_THREADS) void alac_scan_sums_u64_kernel(alac_scan_params<uint64_t> p) { scan_sums<false>(p); }
+__global__ __launch_bounds__(ALAC_SCAN_THREADS) void alac_scan_tiles_u32_kernel(alac_scan_params<uint32_t> p) { scan_tiles<false>(p); }
+__global__ __launch_bounds__(ALAC_SCAN_THREADS) void alac_scan_tiles_u64_kernel(alac_scan_params<uint64_t> p) { scan_tiles<false>(p); }
+__global__ __launch_bounds__(ALAC_SCAN_THREADS) void alac_scan_sums_stage_kernel(alac_scan_params<uint32_t> p) { scan_sums<true>(p); }
+__global__ __launch_bounds__(ALAC_SCAN_THREADS) void alac_scan_tiles_stage_kernel(alac_scan_params<uint32_t> p) { scan_tiles<true>(p); }
 
 __global__ __launch_bounds__(ALAC_COPY_THREADS) void alac_compact_copy_kernel(alac_copy_params p) {
     __shared__ uint32_t range[2];
@@ -285,6 +340,43 @@ __global__ __launch_bounds__(ALAC_COPY_THREADS) void alac_compact_copy_kernel(al
 #pragma unroll
         for (uint32_t c = 0; c < ALAC_COPY_CHUNKS; c++)
             copy_chunk(p, tq + ((uint64_t)c * ALAC_COPY_THREADS + threadIdx.x) * 16u, q_lo, q_hi, shift, lo, hi);
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(ALAC_STAGE_THREADS) void alac_stage_copy_kernel(alac_stage_params p) {
+    __shared__ uint32_t range[2];
+    const uint64_t total = p.total[0];
+    const uint64_t q_hi = total < p.capacity ? total : p.capacity;
+    const uint64_t tiles = q_hi / ALAC_STAGE_TILE + (q_hi % ALAC_STAGE_TILE ? 1u : 0u);
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {      // tiles of the destination; the bound is workgroup-uniform
+        const uint64_t tq = t * ALAC_STAGE_TILE;
+        if (threadIdx.x < 64u) {                         // the first wave, whole: the tile's packets, by two 64-ary searches
+            const uint64_t last = (q_hi - tq < ALAC_STAGE_TILE ? q_hi : tq + ALAC_STAGE_TILE) - 1u;
+            const uint32_t lo = wave_search<true>(p.stage_offset, 0u, p.n_packets, tq, threadIdx.x) - 1u;     // (stage_offset[0] is 0)
+            const uint32_t hi = wave_search<true>(p.stage_offset, lo, p.n_packets, last, threadIdx.x) - 1u;
+            if (threadIdx.x == 0) {
+                range[0] = lo;
+                range[1] = hi;
+            }
+        }
+        __syncthreads();
+        const uint32_t lo = range[0], hi = range[1];
+        // every source first, then every load, then the stores: the loads of all chunks are in flight together
+        stage_src s[ALAC_STAGE_CHUNKS];
+        uint4 v0[ALAC_STAGE_CHUNKS], v1[ALAC_STAGE_CHUNKS];
+#pragma unroll
+        for (uint32_t c = 0; c < ALAC_STAGE_CHUNKS; c++)
+            s[c] = stage_locate(p, tq + ((uint64_t)c * ALAC_STAGE_THREADS + threadIdx.x) * 16u, q_hi, lo, hi);
+#pragma unroll
+        for (uint32_t c = 0; c < ALAC_STAGE_CHUNKS; c++) {
+            v0[c] = v1[c] = make_uint4(0u, 0u, 0u, 0u);
+            if (s[c].v) v0[c] = s[c].v[0];
+            if (s[c].two) v1[c] = s[c].v[1];
+        }
+#pragma unroll
+        for (uint32_t c = 0; c < ALAC_STAGE_CHUNKS; c++)
+            if (s[c].v) *(uint4*)(p.stage + tq + ((uint64_t)c * ALAC_STAGE_THREADS + threadIdx.x) * 16u) = align16(v0[c], v1[c], s[c].r);
         __syncthreads();
     }
 }

@@ -100,6 +100,7 @@ namespace {
     } while (0)
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+void* device_view_of_pinned(const void* host, size_t bytes);   // (below, with the host-buffer entry points)
 
 // The per-CU turn counters of a device (see alac_decode_params::cu_arrivals), reference-counted per process: two contexts on
 // one GPU -- two-in-flight from two contexts, alacgpu_decode_batch_sharded rehearsed on one device -- must not each believe
@@ -549,6 +550,57 @@ int alacgpu_plan_crops_device(alacgpu_ctx* ctx, const void* d_pkt_offset, const 
     return ALACGPU_OK;
 }
 
+// The exclusive scan both alacgpu_compact_packets_device and alacgpu_stage_packets_device begin with: s0 holds the sizes, how
+// they count, `add`, `out` and `total`; the two kernels are the level-0 pair that counts that way.  The levels: the sizes, the
+// sums of their tiles, the sums of those sums' tiles (at most 1024 for 2^32 - 1 packets), in the ctx's scratch.
+static int scan_sizes(alacgpu_ctx* ctx, alac_scan_params<uint32_t> s0, const void* sums_kernel, const void* tiles_kernel, hipStream_t stream) {
+    const uint64_t t1 = (s0.n + ALAC_SCAN_TILE - 1u) / ALAC_SCAN_TILE;
+    const uint64_t t2 = (t1 + ALAC_SCAN_TILE - 1u) / ALAC_SCAN_TILE;
+    const size_t need = t1 > 1 ? sizeof(uint64_t) * (size_t)(t1 + t2) : 0;
+    if (!ctx->scan_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->scan_done, hipEventDisableTiming));
+    if (need > ctx->scan_bytes) {
+        if (ctx->scan_used) HIP_TRY(ctx, hipEventSynchronize(ctx->scan_done));   // the last call has finished with it
+        int rc = grow(ctx, ctx->d_scan, ctx->scan_bytes, need, align_up(need + need / 4, 4096));
+        if (rc) return rc;
+    } else if (need && ctx->scan_used) {
+        HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->scan_done, 0));             // (a call on another stream may still use it)
+    }
+    uint64_t* const l1 = ctx->d_scan;
+    uint64_t* const l2 = l1 ? l1 + t1 : nullptr;
+    s0.sums = l1;
+    s0.tile_base = t1 > 1 ? l1 : nullptr;
+    const dim3 block(ALAC_SCAN_THREADS);
+    if (t1 > 1) {
+        alac_scan_params<uint64_t> s1 = {};
+        s1.in = l1;
+        s1.n = t1;
+        s1.slot_bytes = 0;
+        s1.sums = l2;
+        s1.tile_base = t2 > 1 ? l2 : nullptr;
+        s1.add = 0;
+        s1.out = l1;
+        s1.total = nullptr;
+        void* a0[] = {&s0};
+        void* a1[] = {&s1};
+        HIP_TRY(ctx, hipLaunchKernel(sums_kernel, dim3((uint32_t)t1), block, a0, 0, stream));
+        if (t2 > 1) {
+            alac_scan_params<uint64_t> s2 = s1;          // t2 <= 1024: one tile
+            s2.in = l2;
+            s2.n = t2;
+            s2.sums = nullptr;
+            s2.tile_base = nullptr;
+            s2.out = l2;
+            void* a2[] = {&s2};
+            HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_sums_u64_kernel, dim3((uint32_t)t2), block, a1, 0, stream));
+            HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_tiles_u64_kernel, dim3(1), block, a2, 0, stream));
+        }
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_tiles_u64_kernel, dim3((uint32_t)t2), block, a1, 0, stream));
+    }
+    void* a0[] = {&s0};
+    HIP_TRY(ctx, hipLaunchKernel(tiles_kernel, dim3((uint32_t)t1), block, a0, 0, stream));
+    return ALACGPU_OK;
+}
+
 int alacgpu_compact_packets_device(alacgpu_ctx* ctx, const void* d_packets, uint64_t slot_bytes, const void* d_sizes,
                                    uint32_t n_packets, void* d_blob, uint64_t base, uint64_t blob_capacity,
                                    void* d_pkt_offset, void* d_total, void* hip_stream) {
@@ -563,60 +615,15 @@ int alacgpu_compact_packets_device(alacgpu_ctx* ctx, const void* d_packets, uint
     if (((uintptr_t)d_packets & 15u) != 0 || ((uintptr_t)d_sizes & 3u) != 0 || ((uintptr_t)d_pkt_offset & 7u) != 0)
         return ALACGPU_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the scan's levels: the sizes, the sums of their tiles, the sums of those sums' tiles (at most 1024 for 2^32 - 1 packets)
-    const uint64_t t1 = ((uint64_t)n_packets + ALAC_SCAN_TILE - 1u) / ALAC_SCAN_TILE;
-    const uint64_t t2 = (t1 + ALAC_SCAN_TILE - 1u) / ALAC_SCAN_TILE;
-    const size_t need = t1 > 1 ? sizeof(uint64_t) * (size_t)(t1 + t2) : 0;
-    if (!ctx->scan_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->scan_done, hipEventDisableTiming));
-    if (need > ctx->scan_bytes) {
-        if (ctx->scan_used) HIP_TRY(ctx, hipEventSynchronize(ctx->scan_done));   // the last call has finished with it
-        int rc = grow(ctx, ctx->d_scan, ctx->scan_bytes, need, align_up(need + need / 4, 4096));
-        if (rc) return rc;
-    } else if (need && ctx->scan_used) {
-        HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->scan_done, 0));             // (a call on another stream may still use it)
-    }
-    uint64_t* const l1 = ctx->d_scan;
-    uint64_t* const l2 = l1 ? l1 + t1 : nullptr;
-    alac_scan_params<uint32_t> s0;
+    alac_scan_params<uint32_t> s0 = {};
     s0.in = (const uint32_t*)d_sizes;
     s0.n = n_packets;
     s0.slot_bytes = slot_bytes;
-    s0.sums = l1;
-    s0.tile_base = t1 > 1 ? l1 : nullptr;
     s0.add = base;
     s0.out = (uint64_t*)d_pkt_offset;
     s0.total = (uint64_t*)d_total;
-    const dim3 block(ALAC_SCAN_THREADS);
-    if (t1 > 1) {
-        alac_scan_params<uint64_t> s1;
-        s1.in = l1;
-        s1.n = t1;
-        s1.slot_bytes = 0;
-        s1.sums = l2;
-        s1.tile_base = t2 > 1 ? l2 : nullptr;
-        s1.add = 0;
-        s1.out = l1;
-        s1.total = nullptr;
-        void* a0[] = {&s0};
-        void* a1[] = {&s1};
-        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_sums_u32_kernel, dim3((uint32_t)t1), block, a0, 0, stream));
-        if (t2 > 1) {
-            alac_scan_params<uint64_t> s2 = s1;          // t2 <= 1024: one tile
-            s2.in = l2;
-            s2.n = t2;
-            s2.sums = nullptr;
-            s2.tile_base = nullptr;
-            s2.out = l2;
-            void* a2[] = {&s2};
-            HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_sums_u64_kernel, dim3((uint32_t)t2), block, a1, 0, stream));
-            HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_tiles_u64_kernel, dim3(1), block, a2, 0, stream));
-        }
-        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_tiles_u64_kernel, dim3((uint32_t)t2), block, a1, 0, stream));
-    }
-    {
-        void* a0[] = {&s0};
-        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_tiles_u32_kernel, dim3((uint32_t)t1), block, a0, 0, stream));
-    }
+    int rc = scan_sizes(ctx, s0, (const void*)alac_scan_sums_u32_kernel, (const void*)alac_scan_tiles_u32_kernel, stream);
+    if (rc) return rc;
     // the copy: tiles of the destination, as many as the packets can fill at most (the true end is d_total's, on the device)
     const uint64_t most = slot_bytes > UINT64_MAX / n_packets ? UINT64_MAX : slot_bytes * n_packets;
     const uint64_t room = blob_capacity > base ? blob_capacity - base : 0;
@@ -636,6 +643,66 @@ int alacgpu_compact_packets_device(alacgpu_ctx* ctx, const void* d_packets, uint
         void* ac[] = {&c};
         HIP_TRY(ctx, hipLaunchKernel((const void*)alac_compact_copy_kernel, dim3((uint32_t)std::min<uint64_t>(tiles, 1u << 16)),
                                      dim3(ALAC_COPY_THREADS), ac, 0, stream));
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->scan_done, stream));
+    ctx->scan_used = true;
+    return ALACGPU_OK;
+}
+
+int alacgpu_stage_packets_device(alacgpu_ctx* ctx, const void* d_blob_lo, uint64_t lo_bytes, const void* blob_hi, uint64_t hi_bytes,
+                                 const void* d_src_offset, const void* d_sizes, uint32_t n_packets, void* d_stage,
+                                 uint64_t stage_capacity, void* d_stage_offset, void* d_total, void* hip_stream) {
+    if (!ctx || !d_total || ((uintptr_t)d_total & 7u) != 0) return ALACGPU_ERR_BAD_ARG;
+    if ((!d_blob_lo && lo_bytes) || (!blob_hi && hi_bytes) || ((uintptr_t)d_blob_lo & 15u) != 0 || ((uintptr_t)blob_hi & 15u) != 0)
+        return ALACGPU_ERR_BAD_ARG;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (n_packets == 0) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipMemsetAsync(d_total, 0, sizeof(uint64_t), stream));
+        return ALACGPU_OK;
+    }
+    if (!d_src_offset || !d_sizes || !d_stage || !d_stage_offset) return ALACGPU_ERR_BAD_ARG;
+    if (((uintptr_t)d_src_offset & 7u) != 0 || ((uintptr_t)d_sizes & 3u) != 0 || ((uintptr_t)d_stage & 15u) != 0 ||
+        ((uintptr_t)d_stage_offset & 7u) != 0 || lo_bytes > UINT64_MAX - hi_bytes)
+        return ALACGPU_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the second part as the kernels address it: device memory as it is, page-locked host memory by its device view
+    const void* hi_view = nullptr;
+    if (hi_bytes) {
+        hipPointerAttribute_t a;
+        if (hipPointerGetAttributes(&a, blob_hi) != hipSuccess) { (void)hipGetLastError(); return ALACGPU_ERR_BAD_ARG; }
+        hi_view = a.type == hipMemoryTypeDevice ? blob_hi : device_view_of_pinned(blob_hi, (size_t)hi_bytes);
+        if (!hi_view) return ALACGPU_ERR_BAD_ARG;
+    }
+    alac_scan_params<uint32_t> s0 = {};
+    s0.in = (const uint32_t*)d_sizes;
+    s0.n = n_packets;
+    s0.src_offset = (const uint64_t*)d_src_offset;
+    s0.lo_bytes = lo_bytes;
+    s0.hi_bytes = hi_bytes;
+    s0.out = (uint64_t*)d_stage_offset;
+    s0.total = (uint64_t*)d_total;
+    int rc = scan_sizes(ctx, s0, (const void*)alac_scan_sums_stage_kernel, (const void*)alac_scan_tiles_stage_kernel, stream);
+    if (rc) return rc;
+    // the copy: tiles of the staging blob, as many as its capacity holds (the true end is d_total's, on the device)
+    if (stage_capacity >= 16u) {
+        alac_stage_params c;
+        c.lo = (const uint8_t*)d_blob_lo;
+        c.hi = (const uint8_t*)hi_view;
+        c.lo_bytes = lo_bytes;
+        c.hi_bytes = hi_bytes;
+        c.src_offset = (const uint64_t*)d_src_offset;
+        c.sizes = (const uint32_t*)d_sizes;
+        c.stage_offset = (const uint64_t*)d_stage_offset;
+        c.total = (const uint64_t*)d_total;
+        c.n_packets = n_packets;
+        c.stage = (uint8_t*)d_stage;
+        c.capacity = stage_capacity;
+        const uint64_t tiles = stage_capacity / ALAC_STAGE_TILE + 1u;
+        void* ac[] = {&c};
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_stage_copy_kernel, dim3((uint32_t)std::min<uint64_t>(tiles, 1u << 16)),
+                                     dim3(ALAC_STAGE_THREADS), ac, 0, stream));
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->scan_done, stream));

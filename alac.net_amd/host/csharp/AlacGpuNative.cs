@@ -63,6 +63,13 @@ namespace ALACdotNET.Decoder
         /// blobCapacity is not copied.  Every pointer a device pointer, asynchronous on hipStream.</summary>
         [DllImport(Lib)] public static extern int alacgpu_compact_packets_device(IntPtr ctx, IntPtr dPackets, ulong slotBytes, IntPtr dSizes,
             uint nPackets, IntPtr dBlob, ulong baseOffset, ulong blobCapacity, IntPtr dPktOffset, IntPtr dTotal, IntPtr hipStream);
+        /// <summary>Gather the packets of a plan (dSrcOffset ulong, dSizes uint) out of a corpus whose first loBytes lie at dBlobLo in
+        /// device memory and whose other hiBytes at blobHi (device memory or page-locked host memory) into dStage, each at the next
+        /// multiple of 16: writes dStageOffset[j] (ulong) and dTotal[0] (ulong); a packet that would end behind stageCapacity is not
+        /// copied.  Asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_stage_packets_device(IntPtr ctx, IntPtr dBlobLo, ulong loBytes, IntPtr blobHi,
+            ulong hiBytes, IntPtr dSrcOffset, IntPtr dSizes, uint nPackets, IntPtr dStage, ulong stageCapacity, IntPtr dStageOffset,
+            IntPtr dTotal, IntPtr hipStream);
         /// <summary>Encode PCM in device memory (int32 or float32, interleaved or planar) to ALAC packets in device memory, one
         /// run of frames per packet, packet p at dPackets + p * slotBytes; asynchronous on hipStream.</summary>
         [DllImport(Lib)] public static extern UIntPtr alacgpu_encode_max_packet_bytes(uint frames, int sampleSize, int channels);

@@ -317,6 +317,38 @@ int alacgpu_compact_packets_device(alacgpu_ctx* ctx, const void* d_packets, uint
                                    uint32_t n_packets, void* d_blob, uint64_t base, uint64_t blob_capacity,
                                    void* d_pkt_offset, void* d_total, void* hip_stream);
 
+/*
+ * Stage the packets of a plan (no counterpart in the reference): gather them out of a corpus that lies partly in device memory
+ * and partly in page-locked host memory into one small blob in device memory, every packet at the next multiple of 16.  It
+ * sits between alacgpu_plan_crops_device and alacgpu_decode_window_into_device, which then reads d_stage with d_stage_offset
+ * as its offsets and stage_capacity as its blob_bytes; the decode kernels never read host memory themselves.  Asynchronous on
+ * hip_stream; the library reads nothing back.
+ *   the source       one address space: offset x < lo_bytes is byte x of d_blob_lo (device memory), every other one byte
+ *                    x - lo_bytes of blob_hi.  Either part may be NULL with 0 bytes.  blob_hi is a device pointer or
+ *                    page-locked host memory (alacgpu_alloc_pinned, hipHostMalloc, hipHostRegister): the library takes its
+ *                    device view.  Both bases 16-byte aligned and readable up to their size rounded up to 16
+ *   d_src_offset[j]  uint64, d_sizes[j] uint32: packet j of the plan (a plan's offsets and sizes, padding entries included).
+ *                    A packet counts with its size when it lies wholly inside one of the two parts; one that reaches past
+ *                    the end of the space or straddles lo_bytes counts as 0: whatever the device data say, nothing outside
+ *                    the two parts' rounded-up extents is read.  Size 0 copies nothing
+ *   d_stage_offset[j] uint64, written in full: the sum over q < j of the counted sizes each rounded up to 16
+ *   d_total[0]       uint64, written: that sum over all packets, whatever the capacity
+ *   d_stage          16-byte aligned.  Packet j is copied to d_stage + d_stage_offset[j] iff d_stage_offset[j] + its size
+ *                    rounded up to 16 <= stage_capacity, otherwise not at all.  No byte at or behind min(total,
+ *                    stage_capacity) is written; the bytes between a packet's end and its round-up are unspecified
+ * n_packets == 0: d_total[0] = 0 and nothing else.  The scan is the compaction's (a hierarchy of launches, no workgroup waits
+ * for another) and shares the ctx's partial sums with it: calls on one ctx run one after the other on the device.  The copy
+ * is spread over the staging blob's 16-byte chunks, each one packet's and one store; it is shaped for the link: a lane has up
+ * to sixteen independent 16-byte loads in flight before its first store, a source that is not aligned as its destination is
+ * read as two aligned chunks, and no source byte is fetched by more than the two lanes that share a chunk edge.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx or array, a NULL base with non-zero bytes, a misaligned base
+ * or d_stage (16), d_sizes (4), d_src_offset, d_stage_offset or d_total (8), a blob_hi that is neither device memory nor
+ * page-locked.
+ */
+int alacgpu_stage_packets_device(alacgpu_ctx* ctx, const void* d_blob_lo, uint64_t lo_bytes, const void* blob_hi, uint64_t hi_bytes,
+                                 const void* d_src_offset, const void* d_sizes, uint32_t n_packets, void* d_stage,
+                                 uint64_t stage_capacity, void* d_stage_offset, void* d_total, void* hip_stream);
+
 /* Single-packet drop-in for `int DecodeFrame(byte[] inbuffer, int[] outbuffer)` (AlacFile.cs:428):
  * writes the reference's own int[] layout (24-bit: one int per byte) and returns its byte count in
  * *out_bytes.  status as above (the C# shim rethrows the reference's exceptions from it). */

@@ -7,6 +7,9 @@ Per (B, L): the wall time of a step (torch.cuda.synchronize() in front of and be
 --warmup), the planning kernel's time (HIP events around --plan-reps back-to-back launches, divided by them, median) and the
 padding share 1 - packets / (B * K).  The three are checked equal once.  One JSON line.
   python tools/bench_corpus.py [--files 32] [--seconds 60] [--steps 30] [--warmup 5]
+With --hbm-bytes N a fourth way on a second corpus, Corpus(files, hbm_bytes=N):
+  (d) corpus_tiered  as (c), the packets of the step staged from page-locked host memory (alacgpu_stage_packets_device)
+and per shape the staging capacity and the bytes a step staged.
 Kernel times of the decode pair: run one way alone under the profiler's kernel trace, e.g.
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_corpus.py --only corpus_dev --shape 64x88200"""
 import argparse
@@ -41,8 +44,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--plan-reps", type=int, default=20)
     ap.add_argument("--shape", action="append", help="BxL, repeatable (default 64x88200 and 256x44100)")
-    ap.add_argument("--only", choices=["load_batch", "corpus_host", "corpus_dev"], help="run this way alone (for a kernel trace)")
+    ap.add_argument("--only", choices=["load_batch", "corpus_host", "corpus_dev", "corpus_tiered"], help="run this way alone (for a kernel trace)")
+    ap.add_argument("--hbm-bytes", type=int, help="also measure a corpus that keeps only this many packet bytes in HBM (way corpus_tiered)")
     args = ap.parse_args()
+    if args.only == "corpus_tiered" and args.hbm_bytes is None:
+        ap.error("--only corpus_tiered needs --hbm-bytes")
     import torch
 
     import alac.net_amd as pkg
@@ -56,6 +62,7 @@ def main():
     blobs = [distinct[f % len(distinct)] for f in range(args.files)]
     shapes = [tuple(int(x) for x in s.split("x")) for s in (args.shape or ["64x88200", "256x44100"])]
     corpus = pkg.Corpus(blobs)
+    tiered = pkg.Corpus(blobs, hbm_bytes=args.hbm_bytes) if args.hbm_bytes is not None else None
     results = []
     for B, L in shapes:
         rng = np.random.default_rng(B + L)
@@ -73,12 +80,17 @@ def main():
         def corpus_dev(i):
             return corpus.crops(on_device[i][0], on_device[i][1], L, check=False)[0]
 
+        def corpus_tiered(i):
+            return tiered.crops(on_device[i][0], on_device[i][1], L, check=False)[0]
+
         modes = {"load_batch": load_batch, "corpus_host": corpus_host, "corpus_dev": corpus_dev}
+        if tiered is not None:
+            modes["corpus_tiered"] = corpus_tiered
         if args.only:
             modes = {args.only: modes[args.only]}
         else:
             outs = [fn(0) for fn in modes.values()]
-            assert all(torch.equal(outs[0], x) for x in outs[1:]), "the three ways differ"
+            assert all(torch.equal(outs[0], x) for x in outs[1:]), "the three ways differ" if tiered is None else "the four ways differ"
             del outs
         wall = {m: [] for m in modes}
         for i in range(args.steps + args.warmup):          # the ways alternate inside every step: drift hits them alike
@@ -123,10 +135,17 @@ def main():
                     ms.append(e0.elapsed_time(e1) / args.plan_reps)
             r.update(entries_per_crop=K, packets=int(valid.sum()), padding_share=round(1.0 - float(valid.sum()) / (B * K), 4),
                      plan_kernel_ms=med(ms), speedup_dev_vs_load_batch=round(med(wall["load_batch"]) / med(wall["corpus_dev"]), 2))
+        if tiered is not None and tiered.tier_bytes[1]:
+            tiered.crops(on_device[0][0], on_device[0][1], L, check=False)
+            r.update(stage_capacity_bytes=B * tiered.stage_bytes_per_crop(L), staged_bytes=int(tiered.last_staged_bytes()[0]))
         results.append(r)
     corpus.close()
-    print(json.dumps({"files": args.files, "seconds": args.seconds, "steps": args.steps, "warmup": args.warmup,
-                      "blob_mb": round(corpus._blob_bytes / 1e6, 1), "results": results}), flush=True)
+    head = {"files": args.files, "seconds": args.seconds, "steps": args.steps, "warmup": args.warmup,
+            "blob_mb": round(corpus._blob_bytes / 1e6, 1)}
+    if tiered is not None:
+        head.update(hbm_bytes=args.hbm_bytes, tier_bytes=list(tiered.tier_bytes))
+        tiered.close()
+    print(json.dumps({**head, "results": results}), flush=True)
 
 
 if __name__ == "__main__":

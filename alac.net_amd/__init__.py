@@ -65,6 +65,8 @@ SYMBOLS = {
     "alacgpu_compact_packets_device": (C.c_int, [_VP, _VP, C.c_uint64, _VP, C.c_uint32, _VP, C.c_uint64, C.c_uint64, _VP, _VP, _VP]),
     "alacgpu_stage_packets_device": (C.c_int, [_VP, _VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP, C.c_uint32, _VP, C.c_uint64, _VP, _VP,
                                                _VP]),
+    "alacgpu_resample_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, _VP, _VP, _VP, C.c_uint64, C.c_uint32, C.c_uint32,
+                                          C.c_uint32, _VP, _VP, C.c_int, _VP, _VP]),
     "alacgpu_encode_max_packet_bytes": (C.c_size_t, [C.c_uint32, C.c_int, C.c_int]),
     "alacgpu_encode_device": (C.c_int, [_VP, _VP, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP, C.c_uint32,
                                         _VP, C.c_uint64, _VP, _VP, _VP]),
@@ -324,6 +326,18 @@ class AlacGpuContext(_Closing):
         hi = _dp(blob_hi) if hasattr(blob_hi, "data_ptr") else (_VP(blob_hi) if blob_hi else None)
         rc = lib().alacgpu_stage_packets_device(self._ctx, _dp(d_blob_lo), lo_bytes, hi, hi_bytes, _dp(d_src_offset), _dp(d_sizes),
                                                 n_packets, _dp(d_stage), stage_capacity, _dp(d_stage_offset), _dp(d_total), _VP(stream))
+        _check(rc, self._ctx)
+
+    def resample_device(self, d_src, rows, channels, src_stride, d_src_origin, d_src_valid, d_out_first, out_frames, a, b, width,
+                        d_d0, d_weights, mono, d_out, stream=0):
+        """alacgpu_resample_device: d_src (float32 device tensor, planar [rows, channels, src_stride]) resampled by a : b with
+        the table d_d0 / d_weights (resample.device_table) into d_out (float32 [rows, 1 if mono else channels, out_frames],
+        every element written).  Row r holds the source frames d_src_origin[r] .. + d_src_valid[r] of a signal that is zero
+        elsewhere, and its output starts at target frame d_out_first[r] (three int64 device tensors).  Asynchronous on
+        `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_resample_device(self._ctx, _dp(d_src), rows, channels, src_stride, _dp(d_src_origin), _dp(d_src_valid),
+                                           _dp(d_out_first), out_frames, a, b, width, _dp(d_d0), _dp(d_weights), int(bool(mono)),
+                                           _dp(d_out), _VP(stream))
         _check(rc, self._ctx)
 
     def set_output_format(self, fmt):
@@ -888,3 +902,5 @@ class AlacFile:
 # ---- a corpus resident in HBM and its random crops (alacgpu_plan_crops_device) -----------------------------------------------------
 from .corpus import (Corpus, compact_plan_host, corpus_plan_host, corpus_tables, entries_per_crop,  # noqa: E402  (it imports the names above)
                      stage_bytes_per_crop, stage_plan_host, tier_split)
+# ---- crops and tensors at another sample rate (alacgpu_resample_device) ---------------------------------------------------------------
+from .resample import resample, resample_host, resample_table, source_window  # noqa: E402

@@ -13,6 +13,10 @@ writes their offsets), one small read.  `Corpus.save` writes any corpus back as 
 memory.  A step is then three calls: between the plan and the decode, alacgpu_stage_packets_device gathers the plan's packets
 from both tiers into a small staging blob in HBM, and the decode reads that.
 
+`crops(..., sample_rate=R, mono=)` gives the crops at another rate and as one channel: the source frames a crop needs are
+decoded as above into a scratch the corpus keeps, and one alacgpu_resample_device call (resample.py states the filter)
+resamples every crop out of it.
+
 `corpus_tables` (the resident tables as numpy arrays), `entries_per_crop` (the K bound), `stage_bytes_per_crop` (the staging
 bound), `tier_split`, `corpus_plan_host`, `compact_plan_host` and `stage_plan_host` (the three kernels' specifications in
 numpy) need no device.
@@ -304,6 +308,7 @@ class Corpus(_Closing):
         self._lo_bytes = self._blob_bytes - self._hi_bytes
         self._stage = self._stage_plan = None
         self._stage_room, self._stage_entries, self._stage_bytes = 0, 0, 0
+        self._rs_scratch, self._rs_frames = None, {}      # crops at another rate: the decoded source crops; Ty per ratio
         self._gpu = gpu if gpu is not None else AlacGpuContext(tb["cfgs"], device)
 
     @classmethod
@@ -437,7 +442,7 @@ class Corpus(_Closing):
         if getattr(self, "_gpu", None) is not None:
             self._gpu.close()
             self._gpu = None
-            self._blob = self._plan = self._stage = self._stage_plan = None
+            self._blob = self._plan = self._stage = self._stage_plan = self._rs_scratch = None
         self._free_pinned()
 
     @property
@@ -490,10 +495,13 @@ class Corpus(_Closing):
             self._capacity = cap
         return self._plan
 
-    def _indices(self, files, frame_offsets):
+    def _indices(self, files, frame_offsets, totals=None):
         """The crops' (file, first frame) as device tensors (int32 / int64: the kernel reads them as unsigned) and whether they
-        came from the host (and are checked here) or were device tensors already (and are checked by the kernel)."""
+        came from the host (and are checked here) or were device tensors already (and are checked by the kernel).  totals: the
+        files' frame counts the offsets are checked against (default num_frames)."""
         import torch
+
+        totals = self.num_frames if totals is None else totals
 
         on_device = [isinstance(x, torch.Tensor) and x.device.type == "cuda" for x in (files, frame_offsets)]
         if all(on_device):
@@ -513,13 +521,13 @@ class Corpus(_Closing):
         bad = np.nonzero((f < 0) | (f >= self.num_files))[0]
         if len(bad):
             raise ValueError(f"crop {int(bad[0])}: file {int(f[bad[0]])} outside 0 .. {self.num_files - 1}")
-        bad = np.nonzero((o < 0) | (o > self.num_frames[f]))[0]
+        bad = np.nonzero((o < 0) | (o > totals[f]))[0]
         if len(bad):
             b = int(bad[0])
-            raise ValueError(f"crop {b} (source {int(f[b])}): frame offset {int(o[b])} outside 0 .. {int(self.num_frames[f[b]])}")
+            raise ValueError(f"crop {b} (source {int(f[b])}): frame offset {int(o[b])} outside 0 .. {int(totals[f[b]])}")
         return torch.from_numpy(f.astype(np.int32)).to(self._dev), torch.from_numpy(o).to(self._dev), True
 
-    def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True):
+    def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True, sample_rate=None, mono=False):
         """Decode crop b = frames frame_offsets[b] .. + num_frames of file files[b] for every b in ONE launch pair: returns
         (pcm [B, C, num_frames] on the device, zero behind lengths[b]; lengths [B], a DEVICE int64 tensor: min(num_frames,
         T_f - offset)).  float32 (default) or int32, as `load`.  files / frame_offsets: sequences, numpy arrays or torch
@@ -529,9 +537,15 @@ class Corpus(_Closing):
         into (it is zeroed first).  check=True reads one small result back: AlacGpuError naming crop, source and packet (its
         index in its file) for the first packet that does not decode (statuses read as `load_batch` reads them), ValueError for
         the first crop with a negative length.  check=False reads nothing back and returns behind the enqueue: see
-        last_status()."""
+        last_status().
+
+        sample_rate / mono: crops at another rate and as one channel (`_resampled_crops`): frame_offsets and num_frames then
+        count frames at sample_rate, pcm is float32 [B, 1 if mono else C, num_frames].  The defaults -- and the corpus's own
+        rate, and mono of one channel -- are the path above."""
         import torch
 
+        if (mono and self.channels == 2) or (sample_rate is not None and sample_rate != self.sample_rate):
+            return self._resampled_crops(files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono)
         dtype = _torch_dtype(torch, torch.float32 if dtype is None else dtype)
         L = _frame_count("num_frames", num_frames)
         if L >= 1 << 32:
@@ -588,19 +602,97 @@ class Corpus(_Closing):
             self._check_last(lengths, d_files, d_offs, L, K)
         return out, lengths
 
-    def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True):
+    def resampled_frames(self, sample_rate):
+        """Ty_f: the frames of every file at sample_rate, ceil(b * T_f / a) (int64 host array [F])."""
+        return self._rate(sample_rate)[0]
+
+    def _rate(self, sample_rate):
+        """(Ty host, Ty device, the device table) of the corpus's rate to sample_rate (None: the corpus's), once per rate"""
+        import torch
+
+        from .resample import device_table, resampled_frames
+
+        R = self.sample_rate if sample_rate is None else sample_rate
+        if R not in self._rs_frames:
+            table = device_table(self.sample_rate, R, self._dev)       # (ValueError for a rate the filter does not take)
+            Ty = resampled_frames(self.num_frames, table[0], table[1])
+            self._rs_frames[R] = (Ty, torch.from_numpy(Ty).to(self._dev), table)
+        return self._rs_frames[R]
+
+    def _resampled_crops(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono):
+        """crops(..., sample_rate=R, mono=) : crop b is frames frame_offsets[b] .. + num_frames of file files[b] RESAMPLED AS A
+        WHOLE to R Hz (resample.py states the filter), zero behind its end; lengths[b] = min(num_frames, Ty_f - offset) with
+        Ty_f = ceil(b * T_f / a), -1 for a file index or an offset outside the corpus -- the host checks and the device-tensor
+        rule are those of `crops`, with Ty_f for T_f.  A step: the source frames a crop needs (`source_window`: Ls(num_frames)
+        of them from (o // b) * a - width on, by integer operations on the device) are planned, staged and decoded as crops
+        of the source into a float32 scratch [B, C, Ls] the corpus keeps, then ONE alacgpu_resample_device call filters every
+        crop out of it.  mono: two channels become their mean in front of the filter.  sample_rate None or the corpus's own
+        never comes here without `mono`; with it there is no filter, the kernel only takes the mean (resample.identity_table).
+        dtype: float32 (ValueError otherwise)."""
+        import torch
+
+        from .resample import source_window
+
+        if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
+            raise ValueError("crops at another sample rate or as mono are float32")
+        L = _frame_count("num_frames", num_frames)
+        if self._gpu is None:
+            raise AlacGpuError("the corpus is closed")
+        if self.channels not in (1, 2):
+            raise ValueError(f"{self.channels} channels: the resampler takes 1 or 2")
+        Ty, d_Ty, (a, b, width, d_d0, d_w) = self._rate(sample_rate)
+        Ls = source_window(0, max(L, 1), a, b, width)[1]
+        if Ls >= 1 << 32:
+            raise ValueError(f"num_frames {L} needs {Ls} source frames: that does not fit 32 bits")
+        d_files, d_offs, _ = self._indices(files, frame_offsets, Ty)
+        B, C_ = int(d_files.shape[0]), self.channels
+        Co = 1 if mono else C_
+        if out is not None:
+            if (not isinstance(out, torch.Tensor) or out.shape != (B, Co, L) or out.dtype != torch.float32 or out.device != self._dev
+                    or not out.is_contiguous()):
+                raise ValueError(f"out must be a contiguous torch.float32 tensor of shape {(B, Co, L)} on {self._dev}")
+        else:
+            out = torch.empty((B, Co, L), dtype=torch.float32, device=self._dev)
+        # the crops in source frames: where the target offset is inside its file, else an offset the planner refuses (-1)
+        f64 = d_files.to(torch.int64)
+        ok = (f64 >= 0) & (f64 < self.num_files)
+        Ty_f = d_Ty[f64.clamp(0, self.num_files - 1)]
+        ok &= (d_offs >= 0) & (d_offs <= Ty_f)
+        origin = (torch.div(d_offs, b, rounding_mode="floor") * a - width).clamp(min=0)
+        src_offs = torch.where(ok, origin, -1)
+        lengths = torch.where(ok, (Ty_f - d_offs).clamp(max=L), -1)
+        if B == 0 or L == 0:
+            self._last = 0
+            if check and B:
+                self._raise_bad_length(lengths, d_files, d_offs)
+            return out, lengths
+        n = B * C_ * Ls
+        if self._rs_scratch is None or self._rs_scratch.numel() < n:
+            self._rs_scratch = None     # (the old one goes first)
+            self._rs_scratch = torch.empty(n, dtype=torch.float32, device=self._dev)
+        scratch = self._rs_scratch[:n].view(B, C_, Ls)
+        _, valid = self.crops(d_files, src_offs, Ls, out=scratch, check=False)
+        self._gpu.resample_device(scratch, B, C_, Ls, origin, valid, d_offs, L, a, b, width, d_d0, d_w, mono, out,
+                                  stream=torch.cuda.current_stream(self._dev).cuda_stream)
+        if check:
+            self._check_last(valid, d_files, src_offs, Ls, self.entries_per_crop(Ls), d_shown=d_offs)
+        return out, lengths
+
+    def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True, sample_rate=None, mono=False):
         """`batch` crops of num_frames frames drawn on the device: files uniform over the corpus, the first frame uniform in
         0 .. max(T_f - num_frames, 0).  generator: a torch.Generator (of the corpus's device, or of the CPU: then the draws are
-        made there and uploaded).  Returns (pcm, lengths, files, frame_offsets), the draws as device int64 tensors."""
+        made there and uploaded).  Returns (pcm, lengths, files, frame_offsets), the draws as device int64 tensors.
+        sample_rate / mono as for `crops`: the frames, T_f included, then count at sample_rate."""
         import torch
 
         B, L = _frame_count("batch", batch), _frame_count("num_frames", num_frames)
         dev = generator.device if generator is not None else self._dev
         files = torch.randint(0, self.num_files, (B,), generator=generator, device=dev, dtype=torch.int64).to(self._dev)
         u = torch.rand(B, generator=generator, device=dev, dtype=torch.float64).to(self._dev)
-        span = (self._d_num_frames[files] - L).clamp(min=0)
+        totals = self._d_num_frames if sample_rate is None else self._rate(sample_rate)[1]
+        span = (totals[files] - L).clamp(min=0)
         offs = torch.minimum(torch.floor(u * (span + 1).to(torch.float64)).to(torch.int64), span)
-        pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check)
+        pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono)
         return pcm, lengths, files, offs
 
     def last_staged_bytes(self):
@@ -634,7 +726,8 @@ class Corpus(_Closing):
             raise AlacGpuError(f"crop {b} (source {f}): more packets than the plan reserves per crop")
         raise ValueError(f"crop {b}: file {f} or frame offset {o} outside the corpus")
 
-    def _check_last(self, lengths, d_files, d_offs, L, K):
+    def _check_last(self, lengths, d_files, d_offs, L, K, d_shown=None):
+        """d_shown: the offsets a message about a crop outside the corpus names (default d_offs)"""
         import torch
 
         n, B, pl = self._last, lengths.shape[0], self._plan
@@ -650,7 +743,7 @@ class Corpus(_Closing):
         bad_crop = torch.where(lengths < 0, pl["iota"][:B], B).min()
         bad_entry, bad_crop = (int(x) for x in torch.stack([bad_entry, bad_crop]).cpu())      # the one read
         if bad_crop < B:
-            self._bad_length(bad_crop, int(lengths[bad_crop]), d_files, d_offs)
+            self._bad_length(bad_crop, int(lengths[bad_crop]), d_files, d_offs if d_shown is None else d_shown)
         if bad_entry < n:
             b, i = divmod(bad_entry, K)
             f, o = int(d_files[b]), int(d_offs[b])

@@ -1,0 +1,37 @@
+// alac_resample.h -- the launch parameters of the polyphase resampler (alac_resample.hip), shared with the C ABI
+// (alacgpu_api.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+constexpr int ALAC_RESAMPLE_THREADS = 256;
+constexpr uint32_t ALAC_RESAMPLE_MAX_TABLE = 16384u;    // weights of a table: 64 KiB of LDS
+constexpr uint32_t ALAC_RESAMPLE_MAX_TILE = 1024u;      // output frames of a tile: four per thread
+constexpr uint32_t ALAC_RESAMPLE_MAX_TILES_PER_WG = 8u; // consecutive tiles a workgroup takes with one load of the table
+constexpr size_t ALAC_RESAMPLE_LDS_PREFERRED = 64u << 10;   // two workgroups and more per CU
+constexpr size_t ALAC_RESAMPLE_LDS_MAX = 160u << 10;        // what a CU has
+
+// The source frames a tile of `tile` output frames reads: floor(j a / b) - width .. floor((j + tile - 1) a / b) + width.
+__host__ __device__ inline uint64_t alac_resample_span(uint64_t tile, uint64_t a, uint64_t b, uint64_t width) {
+    return ((tile - 1u) * a) / b + 2u * width + 2u;
+}
+
+struct alac_resample_params {
+    const float* src;             // [rows, channels, src_stride]
+    uint64_t src_stride;
+    const int64_t* src_origin;    // [rows] the absolute source frame of element 0
+    const int64_t* src_valid;     // [rows] the frames behind it that hold signal
+    const int64_t* out_first;     // [rows] the absolute target frame of output element 0
+    float* out;                   // [rows, mono ? 1 : channels, out_frames]
+    uint64_t out_frames;
+    const int32_t* d0;            // [b]
+    const float* weights;         // [b, 2 * width + 1]
+    uint32_t a, b, width;
+    uint32_t channels;
+    uint32_t mono;
+    uint32_t tile;                // output frames per tile, at most ALAC_RESAMPLE_MAX_TILE
+    uint32_t span;                // alac_resample_span(tile, a, b, width)
+    uint32_t tiles_per_wg;
+};
+
+__global__ void alac_resample_kernel(alac_resample_params p);

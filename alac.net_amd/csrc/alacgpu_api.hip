@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "alac_corpus.h"
+#include "alac_resample.h"
 #include "alac_encode.h"
 #include "alac_kernels.h"
 #include "alacgpu.h"
@@ -707,6 +708,60 @@ int alacgpu_stage_packets_device(alacgpu_ctx* ctx, const void* d_blob_lo, uint64
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->scan_done, stream));
     ctx->scan_used = true;
+    return ALACGPU_OK;
+}
+
+int alacgpu_resample_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,
+                            const void* d_src_origin, const void* d_src_valid, const void* d_out_first, uint64_t out_frames,
+                            uint32_t a, uint32_t b, uint32_t width, const void* d_d0, const void* d_weights, int mono, void* d_out,
+                            void* hip_stream) {
+    if (!ctx || !d_src || !d_src_origin || !d_src_valid || !d_out_first || !d_d0 || !d_weights || !d_out) return ALACGPU_ERR_BAD_ARG;
+    if (((uintptr_t)d_src & 3u) != 0 || ((uintptr_t)d_src_origin & 7u) != 0 || ((uintptr_t)d_src_valid & 7u) != 0 ||
+        ((uintptr_t)d_out_first & 7u) != 0 || ((uintptr_t)d_d0 & 3u) != 0 || ((uintptr_t)d_weights & 3u) != 0 ||
+        ((uintptr_t)d_out & 3u) != 0)
+        return ALACGPU_ERR_BAD_ARG;
+    if (a == 0 || b == 0 || width == 0 || channels < 1 || channels > 2) return ALACGPU_ERR_BAD_ARG;
+    const uint64_t table = (uint64_t)b * (2u * (uint64_t)width + 1u);
+    if (table > ALAC_RESAMPLE_MAX_TABLE) return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0 || out_frames == 0) return ALACGPU_OK;
+    // the tile: as many output frames as leave a CU room for two workgroups, down to 256; fewer only where the span of 256
+    // does not fit the CU at all (a / b in the hundreds) -- one frame's span, 2 width + 2, always fits next to the table
+    const auto lds_bytes = [&](uint64_t tile) { return sizeof(float) * (size_t)(((table + 3u) & ~3ull) + alac_resample_span(tile, a, b, width)); };
+    uint32_t tile = ALAC_RESAMPLE_MAX_TILE;
+    while (tile > 256u && lds_bytes(tile) > ALAC_RESAMPLE_LDS_PREFERRED) tile /= 2u;
+    while (tile > 1u && lds_bytes(tile) > ALAC_RESAMPLE_LDS_MAX) tile /= 2u;
+    const size_t lds = lds_bytes(tile);
+    // the grid: a workgroup takes up to eight consecutive tiles with one load of the table, while a thousand workgroups remain
+    const uint64_t tiles = (out_frames + tile - 1u) / tile;
+    const uint64_t planes = (uint64_t)rows * (mono ? 1u : channels);
+    if (tiles > 0xFFFFFFFFull || tiles * planes > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    const uint64_t per_wg = std::min<uint64_t>(std::max<uint64_t>(tiles * planes / 1024u, 1u), std::min<uint64_t>(tiles, ALAC_RESAMPLE_MAX_TILES_PER_WG));
+    const uint64_t groups = (tiles + per_wg - 1u) / per_wg;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (lds > ALAC_RESAMPLE_LDS_PREFERRED)
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)alac_resample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    alac_resample_params p;
+    p.src = (const float*)d_src;
+    p.src_stride = src_stride;
+    p.src_origin = (const int64_t*)d_src_origin;
+    p.src_valid = (const int64_t*)d_src_valid;
+    p.out_first = (const int64_t*)d_out_first;
+    p.out = (float*)d_out;
+    p.out_frames = out_frames;
+    p.d0 = (const int32_t*)d_d0;
+    p.weights = (const float*)d_weights;
+    p.a = a;
+    p.b = b;
+    p.width = width;
+    p.channels = channels;
+    p.mono = mono ? 1u : 0u;
+    p.tile = tile;
+    p.span = (uint32_t)alac_resample_span(tile, a, b, width);
+    p.tiles_per_wg = (uint32_t)per_wg;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_resample_kernel, dim3((uint32_t)(groups * planes)), dim3(ALAC_RESAMPLE_THREADS),
+                                 kargs, lds, (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
     return ALACGPU_OK;
 }
 

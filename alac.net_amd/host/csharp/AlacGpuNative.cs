@@ -70,6 +70,13 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_stage_packets_device(IntPtr ctx, IntPtr dBlobLo, ulong loBytes, IntPtr blobHi,
             ulong hiBytes, IntPtr dSrcOffset, IntPtr dSizes, uint nPackets, IntPtr dStage, ulong stageCapacity, IntPtr dStageOffset,
             IntPtr dTotal, IntPtr hipStream);
+        /// <summary>Resample decoded PCM (float32, planar [rows, channels, srcStride]) by the reduced ratio a : b with a polyphase
+        /// table (dD0 int[b], dWeights float[b, 2 * width + 1]) into dOut [rows, mono ? 1 : channels, outFrames]; row r holds the
+        /// source frames dSrcOrigin[r] .. + dSrcValid[r] (long) of a signal that is zero elsewhere and starts at target frame
+        /// dOutFirst[r] (long).  Every pointer a device pointer, asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_resample_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
+            ulong srcStride, IntPtr dSrcOrigin, IntPtr dSrcValid, IntPtr dOutFirst, ulong outFrames, uint a, uint b, uint width,
+            IntPtr dD0, IntPtr dWeights, int mono, IntPtr dOut, IntPtr hipStream);
         /// <summary>Encode PCM in device memory (int32 or float32, interleaved or planar) to ALAC packets in device memory, one
         /// run of frames per packet, packet p at dPackets + p * slotBytes; asynchronous on hipStream.</summary>
         [DllImport(Lib)] public static extern UIntPtr alacgpu_encode_max_packet_bytes(uint frames, int sampleSize, int channels);

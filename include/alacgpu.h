@@ -349,6 +349,37 @@ int alacgpu_stage_packets_device(alacgpu_ctx* ctx, const void* d_blob_lo, uint64
                                  const void* d_src_offset, const void* d_sizes, uint32_t n_packets, void* d_stage,
                                  uint64_t stage_capacity, void* d_stage_offset, void* d_total, void* hip_stream);
 
+/*
+ * Resample decoded PCM to another rate (no counterpart in the reference): a polyphase Hann-windowed sinc behind the decode.
+ * a : b is the reduced ratio source rate : target rate.  The filter is the caller's table (alac.net_amd/resample.py builds the
+ * one this library documents: rolloff 0.99, 6 zero crossings): target frame j = i + b * m is
+ *   y[j] = sum over n < N of d_weights[i * N + n] * x[m * a + d_d0[i] + n],   N = 2 * width + 1,
+ * in float32 with one fused multiply-add per tap in ascending n.  d_d0[i] (int32, [b]) is floor(i * a / b) - width for every
+ * table that call builds; the kernel relies on d_d0 ascending with i and on d_d0[i] + N <= d_d0[0] + a + 2 * width + 1.
+ * Device pointers only, asynchronous on hip_stream, nothing is read back; nothing of the ctx is used but its device.
+ *   d_src            float32, planar [rows, channels, src_stride]; channels 1 or 2
+ *   d_src_origin[r]  int64: the absolute source frame of element 0 of row r
+ *   d_src_valid[r]   int64: the frames behind it that hold signal (clamped to 0 .. src_stride).  x is zero at every frame
+ *                    outside [origin, origin + valid), negative frames included, whatever the memory holds: nothing outside
+ *                    that range is read
+ *   d_out_first[r]   int64: the absolute target frame of output element 0 of row r
+ *   d_out            float32 [rows, mono ? 1 : channels, out_frames]; every element is written.  The resampled signal of row r
+ *                    has ceil(b * (origin + valid) / a) frames; an output frame outside 0 .. that count is written as zero
+ *   mono             non-zero: two channels become one, (x[0] + x[1]) * 0.5 in float32 in front of the filter; with one
+ *                    channel it changes nothing
+ * A whole signal is origin 0, first 0, valid its length and out_frames ceil(b * valid / a).  b * (origin + valid) and
+ * (first + out_frames) * a must fit 63 bits.  A workgroup holds the table and the source span of a tile of output frames in
+ * LDS (up to 160 KiB for ratios in the hundreds; 64 KiB and less for audio rates).  rows == 0 or out_frames == 0: nothing
+ * happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx or array, a misaligned array (8 for the three int64 arrays, 4
+ * for the others), a, b or width 0, b * (2 * width + 1) above 16384, channels not 1 or 2, 2^31 tiles of output or more (a tile
+ * is 1024 frames of one row and channel for audio rates).
+ */
+int alacgpu_resample_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,
+                            const void* d_src_origin, const void* d_src_valid, const void* d_out_first, uint64_t out_frames,
+                            uint32_t a, uint32_t b, uint32_t width, const void* d_d0, const void* d_weights, int mono,
+                            void* d_out, void* hip_stream);
+
 /* Single-packet drop-in for `int DecodeFrame(byte[] inbuffer, int[] outbuffer)` (AlacFile.cs:428):
  * writes the reference's own int[] layout (24-bit: one int per byte) and returns its byte count in
  * *out_bytes.  status as above (the C# shim rethrows the reference's exceptions from it). */

@@ -62,11 +62,15 @@ SYMBOLS = {
                                                     C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP]),
     "alacgpu_plan_crops_device": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_uint32, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32,
                                             C.c_uint64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "alacgpu_plan_crops_frames_device": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, C.c_uint32, C.c_uint32,
+                                                   C.c_uint32, C.c_uint64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alacgpu_compact_packets_device": (C.c_int, [_VP, _VP, C.c_uint64, _VP, C.c_uint32, _VP, C.c_uint64, C.c_uint64, _VP, _VP, _VP]),
     "alacgpu_stage_packets_device": (C.c_int, [_VP, _VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP, C.c_uint32, _VP, C.c_uint64, _VP, _VP,
                                                _VP]),
     "alacgpu_resample_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, _VP, _VP, _VP, C.c_uint64, C.c_uint32, C.c_uint32,
                                           C.c_uint32, _VP, _VP, C.c_int, _VP, _VP]),
+    "alacgpu_resample_rows_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, _VP, _VP, _VP, C.c_uint64, _VP, _VP,
+                                               C.c_uint32, _VP, _VP, _VP, C.c_int, _VP, _VP]),
     "alacgpu_encode_max_packet_bytes": (C.c_size_t, [C.c_uint32, C.c_int, C.c_int]),
     "alacgpu_encode_device": (C.c_int, [_VP, _VP, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP, C.c_uint32,
                                         _VP, C.c_uint64, _VP, _VP, _VP]),
@@ -338,6 +342,20 @@ class AlacGpuContext(_Closing):
         rc = lib().alacgpu_resample_device(self._ctx, _dp(d_src), rows, channels, src_stride, _dp(d_src_origin), _dp(d_src_valid),
                                            _dp(d_out_first), out_frames, a, b, width, _dp(d_d0), _dp(d_weights), int(bool(mono)),
                                            _dp(d_out), _VP(stream))
+        _check(rc, self._ctx)
+
+    def resample_rows_device(self, d_src, rows, channels, src_stride, d_src_origin, d_src_valid, d_out_first, out_frames, tables,
+                             d_tables, d_d0, d_weights, d_row_table, mono, d_out, stream=0):
+        """alacgpu_resample_rows_device: resample_device with a table per row.  tables: the descriptors on the host, a uint32
+        array [n_tables, 5] of (a, b, width, where the table's d0 starts in d_d0, where its weights start in d_weights:
+        resample.device_tables); d_tables: the same on the device (int32 device tensor); d_row_table[r] (int32 device tensor,
+        read as unsigned): the table of row r, n_tables and above for a row of zeros.  Asynchronous on `stream` (raw
+        hipStream_t); nothing is read back."""
+        tables = np.ascontiguousarray(tables, dtype=np.uint32).reshape(-1, 5)
+        rc = lib().alacgpu_resample_rows_device(self._ctx, _dp(d_src), rows, channels, src_stride, _dp(d_src_origin),
+                                                _dp(d_src_valid), _dp(d_out_first), out_frames, _ptr(tables), _dp(d_tables),
+                                                len(tables), _dp(d_d0), _dp(d_weights), _dp(d_row_table), int(bool(mono)),
+                                                _dp(d_out), _VP(stream))
         _check(rc, self._ctx)
 
     def set_output_format(self, fmt):

@@ -17,6 +17,10 @@ from both tiers into a small staging blob in HBM, and the decode reads that.
 decoded as above into a scratch the corpus keeps, and one alacgpu_resample_device call (resample.py states the filter)
 resamples every crop out of it.
 
+`Corpus(sources, mixed_rates=True)` takes files of different sample rates.  Crops of such a corpus exist at a target rate only;
+a step is the same launches, with a source window per crop in the plan (alacgpu_plan_crops_frames_device) and a filter table
+per row in the resampler (alacgpu_resample_rows_device).
+
 `corpus_tables` (the resident tables as numpy arrays), `entries_per_crop` (the K bound), `stage_bytes_per_crop` (the staging
 bound), `tier_split`, `corpus_plan_host`, `compact_plan_host` and `stage_plan_host` (the three kernels' specifications in
 numpy) need no device.
@@ -31,22 +35,27 @@ PAD_CFG = 0xFFFF        # a padding entry's cfg_idx: never a row of the context,
 MAX_CFGS = 65535
 
 
-def corpus_tables(tables):
+def corpus_tables(tables, mixed_rates=False):
     """The resident tables of a corpus from its files' packet tables (dicts with sizes, durations, cfg, num_channels and
     sample_rate, as container.packet_table returns them; the packet bytes are not looked at).  The packets of all files lie
     back to back.  Returns a dict of numpy arrays: pkt_offset[P] uint64 (into the blob), pkt_size[P] uint32, pkt_end[P] uint64
     (inclusive prefix sum of the durations within the packet's file), file_first[F + 1] uint32, file_cfg[F] uint16 (rows of
     cfgs), cfgs (the distinct alacgpu_cfg rows), num_frames[F] int64, file_base[F + 1] uint64 (where a file's bytes start),
-    and channels, sample_rate, blob_bytes.  ValueError: no files, a file whose channel count or sample rate differs from the
-    first's, more than 65535 distinct stream cfgs, 2^32 packets or more."""
+    file_rate[F] int64 (a file's sample rate), and channels, sample_rate, blob_bytes.  ValueError: no files, a file whose
+    channel count or sample rate differs from the first's, more than 65535 distinct stream cfgs, 2^32 packets or more.
+    mixed_rates: the files may differ in sample rate (not in channel count); sample_rate is then the rate they share, or None
+    when they do not share one."""
     from . import CFG_DTYPE
 
     if not len(tables):
         raise ValueError("no sources")
     channels, rate = int(tables[0]["num_channels"]), int(tables[0]["sample_rate"])
     for i, t in enumerate(tables):
-        if int(t["num_channels"]) != channels or int(t["sample_rate"]) != rate:
+        if int(t["num_channels"]) != channels or (int(t["sample_rate"]) != rate and not mixed_rates):
             raise ValueError(f"source {i}: {t['num_channels']} channels at {t['sample_rate']} Hz, the first has {channels} at {rate} Hz")
+    file_rate = np.array([int(t["sample_rate"]) for t in tables], dtype=np.int64)
+    if (file_rate != rate).any():
+        rate = None
     counts = np.array([len(t["sizes"]) for t in tables], dtype=np.int64)
     if int(counts.sum()) >= 1 << 32:
         raise ValueError(f"{int(counts.sum())} packets: a corpus holds fewer than 2^32")
@@ -66,19 +75,26 @@ def corpus_tables(tables):
     num_frames = np.array([int(np.sum(np.asarray(t["durations"], dtype=np.int64))) for t in tables], dtype=np.int64)
     return dict(pkt_offset=pkt_offset, pkt_size=sizes, pkt_end=ends, file_first=file_first,
                 file_cfg=np.asarray(inverse).reshape(-1).astype(np.uint16), cfgs=np.ascontiguousarray(uniq).view(CFG_DTYPE).reshape(-1),
-                num_frames=num_frames, file_base=file_base, channels=channels, sample_rate=rate, blob_bytes=blob_bytes)
+                num_frames=num_frames, file_base=file_base, file_rate=file_rate, channels=channels, sample_rate=rate,
+                blob_bytes=blob_bytes)
 
 
 def _widest_windows(pkt_end, file_first, num_frames):
     """The windows of num_frames frames that take the most packets: (g0, g1), two int64 arrays of global packet ranges, among
     which every window's range p0 .. p1 of window_plan is contained in one.  Inside the packet a window starts in, p0 is fixed
     and p1 grows with the offset, so the window from that packet's last frame reaches furthest; a window from frame 0 starts
-    at packet 0 whatever the durations."""
+    at packet 0 whatever the durations.  num_frames: one length, or an array [F] of a length per file (a file's windows are
+    then as long as its own entry says; a file with 0 has none)."""
     pkt_end = np.asarray(pkt_end).astype(np.int64)
     file_first = np.asarray(file_first).astype(np.int64)
-    L = int(num_frames)
     F = len(file_first) - 1
-    if L <= 0 or len(pkt_end) == 0:
+    if np.ndim(num_frames) == 0:
+        L = np.full(F, int(num_frames), dtype=np.int64)
+    else:
+        L = np.asarray(num_frames).astype(np.int64).reshape(-1)
+        if len(L) != F:
+            raise ValueError(f"{len(L)} window lengths for {F} files")
+    if not (L > 0).any() or len(pkt_end) == 0:
         return np.zeros(0, np.int64), np.zeros(0, np.int64)
     counts = np.diff(file_first)
     file_of = np.repeat(np.arange(F, dtype=np.int64), counts)
@@ -92,7 +108,9 @@ def _widest_windows(pkt_end, file_first, num_frames):
     f = np.concatenate([file_of[has], np.arange(F, dtype=np.int64)])
     p0 = np.concatenate([local[has], np.zeros(F, dtype=np.int64)])
     p0 = np.where(o == 0, 0, p0)
-    end = np.minimum(o + L, total[f])
+    keep = L[f] > 0
+    o, f, p0 = o[keep], f[keep], p0[keep]
+    end = np.minimum(o + L[f], total[f])
     # p1: the file's packets that start in front of `end` -- one search over all files' starts, a file's keyed behind the last's
     M = int(total.max()) + 2
     if F * M < 1 << 62:
@@ -105,7 +123,9 @@ def _widest_windows(pkt_end, file_first, num_frames):
 
 def entries_per_crop(pkt_end, file_first, num_frames):
     """K(L): the most packets a window of num_frames frames takes in any file (the largest p1 - p0 of window_plan over every
-    offset), exact: see _widest_windows.  Files of one frame length fl: ceil((L - 1) / fl) + 1 when the file is long enough."""
+    offset), exact: see _widest_windows.  Files of one frame length fl: ceil((L - 1) / fl) + 1 when the file is long enough.
+    num_frames may be an array [F]: file f's windows are num_frames[f] frames long (crops at one target rate of files of
+    different rates), and K is the most any file's own windows take."""
     g0, g1 = _widest_windows(pkt_end, file_first, num_frames)
     return int((g1 - g0).max()) if len(g0) else 0
 
@@ -115,7 +135,8 @@ def stage_bytes_per_crop(pkt_size, pkt_end, file_first, num_frames):
     16 -- the largest sum of the sizes, each rounded up to 16, over the packets p0 .. p1 of window_plan over every offset of
     every file, exact (some offset reaches it; see _widest_windows: the widest windows contain every other window's packets).
     Never more than the largest such sum over K(L) consecutive packets of one file, and equal to it where one file both takes
-    K(L) packets and has the largest ones.  B crops never stage more than B * S(L) bytes."""
+    K(L) packets and has the largest ones.  B crops never stage more than B * S(L) bytes.  num_frames may be an array [F] of a
+    window length per file, as for entries_per_crop."""
     g0, g1 = _widest_windows(pkt_end, file_first, num_frames)
     if not len(g0):
         return 0
@@ -136,12 +157,15 @@ def tier_split(file_bytes, hbm_bytes):
     return int(np.searchsorted(np.cumsum(file_bytes), int(hbm_bytes), side="right"))
 
 
-def corpus_plan_host(pkt_offset, pkt_size, pkt_end, file_first, file_cfg, crop_file, crop_offset, num_frames, entries, dst_stride):
+def corpus_plan_host(pkt_offset, pkt_size, pkt_end, file_first, file_cfg, crop_file, crop_offset, num_frames, entries, dst_stride,
+                     crop_frames=None):
     """alacgpu_plan_crops_device on the host, in numpy: the kernel's specification (tests compare the two; `Corpus.crops` never
     comes here).  Returns (offsets uint64, sizes uint32, cfg_idx uint16, dst_first uint64, dst_frames uint32, src_skip uint32)
     of B * entries entries, crop-major, and lengths[B] int64: min(num_frames, T_f - offset); -1 for a file index >= F or an
     offset > T_f; -2 for a crop that needs more than `entries` entries.  Entries behind a crop's packets are padding:
-    cfg_idx 0xFFFF and zeros."""
+    cfg_idx 0xFFFF and zeros.  crop_frames: alacgpu_plan_crops_frames_device -- a window length per crop [B] (uint32) with
+    num_frames as their bound: lengths[b] = min(crop_frames[b], T_f - offset), and -1 with padding only for a crop_frames[b]
+    above num_frames."""
     pkt_offset, pkt_size = np.asarray(pkt_offset, dtype=np.uint64), np.asarray(pkt_size, dtype=np.uint32)
     ends_all = np.asarray(pkt_end).astype(np.int64)
     file_first, file_cfg = np.asarray(file_first).astype(np.int64), np.asarray(file_cfg, dtype=np.uint16)
@@ -151,9 +175,15 @@ def corpus_plan_host(pkt_offset, pkt_size, pkt_end, file_first, file_cfg, crop_f
     cfg_idx = np.full(B * K, PAD_CFG, np.uint16)
     dst_first, dst_frames, src_skip = np.zeros(B * K, np.uint64), np.zeros(B * K, np.uint32), np.zeros(B * K, np.uint32)
     lengths = np.full(B, -1, np.int64)
+    each = None if crop_frames is None else np.asarray(crop_frames, dtype=np.uint32)
+    if each is not None and each.shape != (B,):
+        raise ValueError(f"{each.shape} window lengths for {B} crops")
+    bound = L
     for b in range(B):
         f, o = int(crop_file[b]), int(crop_offset[b])
-        if f >= F:
+        if each is not None:
+            L = int(each[b])
+        if f >= F or L > bound:
             continue
         g0, g1 = int(file_first[f]), int(file_first[f + 1])
         ends = ends_all[g0:g1]
@@ -225,9 +255,15 @@ class Corpus(_Closing):
     of them on the host; ValueError when negative or not an integer); tier_bytes is (device bytes, host bytes).  Crops of
     such a corpus are what they are of the resident one, bit for bit: a step additionally gathers the packets it needs from
     both tiers into a staging blob in HBM (alacgpu_stage_packets_device; at most batch * stage_bytes_per_crop(num_frames)
-    bytes, kept and reused), and the decode reads that.  When every file fits, the corpus is the resident one."""
+    bytes, kept and reused), and the decode reads that.  When every file fits, the corpus is the resident one.
 
-    def __init__(self, sources, device=0, hbm_bytes=None):
+    mixed_rates=True: the files may differ in sample rate (not in channel count).  sample_rates (int64 host array [F]) has
+    every file's; sample_rate is the one they share, or None when they differ.  num_frames stays in source frames.  Crops of
+    a corpus whose rates differ exist at a target rate only: crops / random_crops want sample_rate=R (`_mixed_crops`), and
+    every file is resampled by its own ratio in the same launches.  Files that happen to share one rate make the corpus
+    Corpus(sources) is, call for call."""
+
+    def __init__(self, sources, device=0, hbm_bytes=None, mixed_rates=False):
         import torch
 
         from .container import header_table, packet_table
@@ -267,7 +303,7 @@ class Corpus(_Closing):
                 heads.append({k: t[k] for k in ("sizes", "durations", "cfg", "num_channels", "sample_rate")})
             if base != total:
                 raise ValueError("a source changed while it was read")
-            self._install(device, corpus_tables(heads), host_bytes=total - lo_bytes)
+            self._install(device, corpus_tables(heads, mixed_rates=mixed_rates), host_bytes=total - lo_bytes)
         except BaseException:
             self._free_pinned()
             raise
@@ -293,6 +329,7 @@ class Corpus(_Closing):
         self.num_files = len(tb["file_cfg"])
         self.num_frames = tb["num_frames"]
         self.channels, self.sample_rate = tb["channels"], tb["sample_rate"]
+        self.sample_rates = np.asarray(tb["file_rate"] if "file_rate" in tb else np.full(self.num_files, tb["sample_rate"]), dtype=np.int64)
         self._host = tb
         self._blob_bytes = tb["blob_bytes"]
         self._pkt_offset = d_pkt_offset if d_pkt_offset is not None else up(tb["pkt_offset"], np.int64)
@@ -309,6 +346,7 @@ class Corpus(_Closing):
         self._stage = self._stage_plan = None
         self._stage_room, self._stage_entries, self._stage_bytes = 0, 0, 0
         self._rs_scratch, self._rs_frames = None, {}      # crops at another rate: the decoded source crops; Ty per ratio
+        self._mx_rates, self._mx_windows = {}, {}         # differing rates: the per-file tables per target rate; Ls, K, S per (R, L)
         self._gpu = gpu if gpu is not None else AlacGpuContext(tb["cfgs"], device)
 
     @classmethod
@@ -406,7 +444,7 @@ class Corpus(_Closing):
 
     def save(self, dests, sample_rate=None):
         """Write file f of the corpus as an M4A file to dests[f] (paths or writable binary file objects; sample_rate: the
-        corpus's unless given): the checkpoint of a corpus -- Corpus(those files) is the same corpus again, and for a corpus
+        file's own unless given): the checkpoint of a corpus -- Corpus(those files) is the same corpus again, and for a corpus
         from_pcm made the files are byte for byte what save_batch writes for the same arguments.  A packet's duration is the
         difference of its pkt_end to the one in front; frame length, sample size and the Rice parameters are the file's cfg
         row's.  The packets cross to the host file by file.  Returns the file sizes."""
@@ -415,9 +453,8 @@ class Corpus(_Closing):
         dests = list(dests)
         if len(dests) != self.num_files:
             raise ValueError(f"{self.num_files} files in the corpus and {len(dests)} destinations")
-        rate = self.sample_rate if sample_rate is None else sample_rate
-        if not isinstance(rate, (int, np.integer)) or not 1 <= int(rate) < 1 << 32:
-            raise ValueError(f"sample_rate must be a positive 32-bit integer, not {rate}")
+        if sample_rate is not None and (not isinstance(sample_rate, (int, np.integer)) or not 1 <= int(sample_rate) < 1 << 32):
+            raise ValueError(f"sample_rate must be a positive 32-bit integer, not {sample_rate}")
         h = self._host
         off, size = self._host_table("pkt_offset").astype(np.int64), self._host_table("pkt_size").astype(np.int64)
         out = []
@@ -434,6 +471,7 @@ class Corpus(_Closing):
             ends = h["pkt_end"][g0:g1].astype(np.int64)
             durations = np.diff(np.concatenate([[0], ends]))
             c = h["cfgs"][int(h["file_cfg"][f])]
+            rate = self.sample_rates[f] if sample_rate is None else sample_rate
             out.append(_write_file(dest, packets, durations, int(c["max_samples_per_frame"]), int(c["sample_size"]), self.channels,
                                    int(rate), rice=(int(c["rice_history_mult"]), int(c["rice_initial_history"]), int(c["rice_kmodifier"]))))
         return out
@@ -450,8 +488,12 @@ class Corpus(_Closing):
         """(device_bytes, host_bytes): the packet bytes in HBM and those in page-locked host memory"""
         return self._lo_bytes, self._hi_bytes
 
-    def stage_bytes_per_crop(self, num_frames):
-        """S for crops of num_frames frames: the bytes the staging blob reserves per crop (computed once per length)."""
+    def stage_bytes_per_crop(self, num_frames, sample_rate=None):
+        """S for crops of num_frames frames: the bytes the staging blob reserves per crop (computed once per length).
+        sample_rate, for a corpus whose rates differ: S of the crops of num_frames frames at that rate -- a file counts with
+        the source window its own ratio needs."""
+        if sample_rate is not None and self.sample_rate is None:
+            return self._mixed_window(sample_rate, num_frames)["S"]
         L = int(num_frames)
         if L not in self._S:
             self._S[L] = stage_bytes_per_crop(self._host_table("pkt_size"), self._host["pkt_end"], self._host["file_first"], L)
@@ -474,8 +516,11 @@ class Corpus(_Closing):
             self._stage_entries = n
         return self._stage, self._stage_plan
 
-    def entries_per_crop(self, num_frames):
-        """K for crops of num_frames frames: the entries the plan reserves per crop (computed once per length)."""
+    def entries_per_crop(self, num_frames, sample_rate=None):
+        """K for crops of num_frames frames: the entries the plan reserves per crop (computed once per length).  sample_rate,
+        for a corpus whose rates differ: K of the crops of num_frames frames at that rate, as for stage_bytes_per_crop."""
+        if sample_rate is not None and self.sample_rate is None:
+            return self._mixed_window(sample_rate, num_frames)["K"]
         L = int(num_frames)
         if L not in self._K:
             self._K[L] = max(entries_per_crop(self._host["pkt_end"], self._host["file_first"], L), 1)
@@ -541,9 +586,14 @@ class Corpus(_Closing):
 
         sample_rate / mono: crops at another rate and as one channel (`_resampled_crops`): frame_offsets and num_frames then
         count frames at sample_rate, pcm is float32 [B, 1 if mono else C, num_frames].  The defaults -- and the corpus's own
-        rate, and mono of one channel -- are the path above."""
+        rate, and mono of one channel -- are the path above.  A corpus whose files differ in rate (mixed_rates=True) has no
+        rate of its own: sample_rate is required (ValueError without), and every crop comes through `_mixed_crops`."""
         import torch
 
+        if self.sample_rate is None:
+            if sample_rate is None:
+                raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
+            return self._mixed_crops(files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono)
         if (mono and self.channels == 2) or (sample_rate is not None and sample_rate != self.sample_rate):
             return self._resampled_crops(files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono)
         dtype = _torch_dtype(torch, torch.float32 if dtype is None else dtype)
@@ -576,19 +626,35 @@ class Corpus(_Closing):
         n = B * K
         if n >= 1 << 32:
             raise ValueError(f"{B} crops of up to {K} packets: a call plans fewer than 2^32 entries")
+        lengths = self._plan_and_decode(d_files, d_offs, L, K, self.stage_bytes_per_crop(L) if self._hi_bytes else 0, out)
+        if check:
+            self._check_last(lengths, d_files, d_offs, L, K)
+        return out, lengths
+
+    def _plan_and_decode(self, d_files, d_offs, L, K, S, out, d_frames=None):
+        """The launches of a step: the plan of the crops (d_files, d_offs) of L frames with K entries each, the staging of its
+        packets (a tiered corpus: S bytes per crop) and the decode into out [B, C, L]; returns the planner's lengths.
+        d_frames: a window length per crop (int32 device tensor, at most L each; alacgpu_plan_crops_frames_device)."""
+        import torch
+
+        B, C_ = int(d_files.shape[0]), self.channels
+        n = B * K
         pl = self._plan_arrays(n)
         lengths = torch.empty(B, dtype=torch.int64, device=self._dev)
         stream = torch.cuda.current_stream(self._dev).cuda_stream
         ctx = self._gpu
-        _check(lib().alacgpu_plan_crops_device(ctx._ctx, _dp(self._pkt_offset), _dp(self._pkt_size), _dp(self._pkt_end),
-                                               _dp(self._file_first), _dp(self._file_cfg), self.num_files, _dp(d_files), _dp(d_offs),
-                                               B, L, K, C_ * L, _dp(pl["offsets"]), _dp(pl["sizes"]), _dp(pl["cfg_idx"]),
-                                               _dp(pl["dst_first"]), _dp(pl["dst_frames"]), _dp(pl["src_skip"]), _dp(lengths),
-                                               _VP(stream)), ctx._ctx)
+        tables = (ctx._ctx, _dp(self._pkt_offset), _dp(self._pkt_size), _dp(self._pkt_end), _dp(self._file_first), _dp(self._file_cfg),
+                  self.num_files, _dp(d_files), _dp(d_offs))
+        plan = (B, L, K, C_ * L, _dp(pl["offsets"]), _dp(pl["sizes"]), _dp(pl["cfg_idx"]), _dp(pl["dst_first"]), _dp(pl["dst_frames"]),
+                _dp(pl["src_skip"]), _dp(lengths), _VP(stream))
+        if d_frames is None:
+            _check(lib().alacgpu_plan_crops_device(*tables, *plan), ctx._ctx)
+        else:
+            _check(lib().alacgpu_plan_crops_frames_device(*tables, _dp(d_frames), *plan), ctx._ctx)
         blob, blob_bytes, offsets = self._blob, self._blob_bytes, pl["offsets"]
         if self._hi_bytes:
             # the packets of this step from both tiers into the staging blob, each at a multiple of 16; the decode reads that
-            blob_bytes = B * self.stage_bytes_per_crop(L)
+            blob_bytes = B * S
             blob, sp = self._stage_arrays(n, blob_bytes)
             self._stage_bytes = blob_bytes
             offsets = sp["offsets"]
@@ -598,12 +664,13 @@ class Corpus(_Closing):
         ctx.decode_window_into_device(blob, blob_bytes, offsets, pl["sizes"], pl["cfg_idx"], n, pl["dst_first"],
                                       pl["dst_frames"], pl["src_skip"], out, C_, "planar", L, None, pl["status"], stream=stream)
         self._last = n
-        if check:
-            self._check_last(lengths, d_files, d_offs, L, K)
-        return out, lengths
+        return lengths
 
     def resampled_frames(self, sample_rate):
-        """Ty_f: the frames of every file at sample_rate, ceil(b * T_f / a) (int64 host array [F])."""
+        """Ty_f: the frames of every file at sample_rate, ceil(b * T_f / a) with the file's own reduced ratio a : b (int64 host
+        array [F])."""
+        if self.sample_rate is None:
+            return self._mixed_rate(sample_rate)["Ty"]
         return self._rate(sample_rate)[0]
 
     def _rate(self, sample_rate):
@@ -678,6 +745,104 @@ class Corpus(_Closing):
             self._check_last(valid, d_files, src_offs, Ls, self.entries_per_crop(Ls), d_shown=d_offs)
         return out, lengths
 
+    def _mixed_rate(self, sample_rate):
+        """What crops at sample_rate of a corpus whose rates differ need, once per rate: the tables of the files' ratios
+        (resample.rows_tables: host descriptors and the three device arrays), per file on the device the table, a, b, width
+        and Ty, and Ty on the host.  ValueError: a rate the filter does not take, naming the first file whose table is too
+        large."""
+        import torch
+
+        from .resample import resampled_frames, rows_tables
+
+        R = sample_rate
+        if R not in self._mx_rates:
+            table_of, desc, d0, w = rows_tables(self.sample_rates.tolist(), R)
+            a, b, width = (desc[table_of, k].astype(np.int64) for k in range(3))
+            Ty = resampled_frames(self.num_frames, a, b)
+            up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(self._dev)
+            self._mx_rates[R] = dict(desc=desc, d_desc=up(desc.view(np.int32)), d_d0=up(d0), d_w=up(w), table_of=table_of, a=a, b=b,
+                                     width=width, Ty=Ty, d_table_of=up(table_of), d_a=up(a), d_b=up(b), d_width=up(width), d_Ty=up(Ty))
+        return self._mx_rates[R]
+
+    def _mixed_window(self, sample_rate, num_frames):
+        """Per (rate, crop length): Ls_f, the source window of file f (resample.source_window with the file's ratio) on the
+        host and as an int32 device tensor, the largest of them, and K and S where a file counts with its own Ls_f."""
+        import torch
+
+        rt = self._mixed_rate(sample_rate)
+        L = _frame_count("num_frames", num_frames)
+        key = (sample_rate, L)
+        if key not in self._mx_windows:
+            Ls = ((max(L, 1) - 1) // rt["b"] + 2) * rt["a"] + 2 * rt["width"]
+            if int(Ls.max()) >= 1 << 32:
+                raise ValueError(f"num_frames {L} needs {int(Ls.max())} source frames: that does not fit 32 bits")
+            h = self._host
+            K = max(entries_per_crop(h["pkt_end"], h["file_first"], Ls), 1)
+            S = stage_bytes_per_crop(self._host_table("pkt_size"), h["pkt_end"], h["file_first"], Ls) if self._hi_bytes else 0
+            self._mx_windows[key] = dict(Ls=Ls, d_Ls=torch.from_numpy(Ls.astype(np.uint32).view(np.int32)).to(self._dev),
+                                         Ls_max=int(Ls.max()), K=K, S=S)
+        return self._mx_windows[key]
+
+    def _mixed_crops(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono):
+        """crops(..., sample_rate=R) of a corpus whose files differ in rate: `_resampled_crops` with file f's own reduced
+        ratio a_f : b_f -- crop b is frames frame_offsets[b] .. + num_frames of file files[b] resampled as a whole to R Hz,
+        lengths[b] = min(num_frames, Ty_f - offset), Ty_f = ceil(b_f * T_f / a_f).  The same launches whatever the rates:
+        per crop, from per-file device tables by integer operations, the source origin (o // b_f) * a_f - width_f (clamped
+        at 0), the source window Ls_f and the table; ONE plan with a window length per crop
+        (alacgpu_plan_crops_frames_device: a crop of a 16 kHz file does not decode what a crop of a 48 kHz file needs), the
+        staging, ONE decode into the scratch [B, C, max Ls_f], and ONE alacgpu_resample_rows_device call.  A file already
+        at R goes through the table that copies."""
+        import torch
+
+        if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
+            raise ValueError("crops at another sample rate or as mono are float32")
+        L = _frame_count("num_frames", num_frames)
+        if self._gpu is None:
+            raise AlacGpuError("the corpus is closed")
+        if self.channels not in (1, 2):
+            raise ValueError(f"{self.channels} channels: the resampler takes 1 or 2")
+        rt = self._mixed_rate(sample_rate)
+        win = self._mixed_window(sample_rate, L)
+        Ls, K = win["Ls_max"], win["K"]
+        d_files, d_offs, _ = self._indices(files, frame_offsets, rt["Ty"])
+        B, C_, F = int(d_files.shape[0]), self.channels, self.num_files
+        Co = 1 if mono else C_
+        if out is not None:
+            if (not isinstance(out, torch.Tensor) or out.shape != (B, Co, L) or out.dtype != torch.float32 or out.device != self._dev
+                    or not out.is_contiguous()):
+                raise ValueError(f"out must be a contiguous torch.float32 tensor of shape {(B, Co, L)} on {self._dev}")
+        else:
+            out = torch.empty((B, Co, L), dtype=torch.float32, device=self._dev)
+        if B * K >= 1 << 32:
+            raise ValueError(f"{B} crops of up to {K} packets: a call plans fewer than 2^32 entries")
+        # the crops in source frames: where the target offset is inside its file, else an offset the planner refuses (-1)
+        f64 = d_files.to(torch.int64)
+        ok = (f64 >= 0) & (f64 < F)
+        fc = f64.clamp(0, F - 1)
+        Ty_f = rt["d_Ty"][fc]
+        ok &= (d_offs >= 0) & (d_offs <= Ty_f)
+        origin = (torch.div(d_offs, rt["d_b"][fc], rounding_mode="floor") * rt["d_a"][fc] - rt["d_width"][fc]).clamp(min=0)
+        src_offs = torch.where(ok, origin, -1)
+        lengths = torch.where(ok, (Ty_f - d_offs).clamp(max=L), -1)
+        if B == 0 or L == 0:
+            self._last = 0
+            if check and B:
+                self._raise_bad_length(lengths, d_files, d_offs)
+            return out, lengths
+        row_table = torch.where(ok, rt["d_table_of"][fc], len(rt["desc"])).to(torch.int32)
+        n = B * C_ * Ls
+        if self._rs_scratch is None or self._rs_scratch.numel() < n:
+            self._rs_scratch = None     # (the old one goes first)
+            self._rs_scratch = torch.empty(n, dtype=torch.float32, device=self._dev)
+        scratch = self._rs_scratch[:n].view(B, C_, Ls)
+        scratch.zero_()
+        valid = self._plan_and_decode(d_files, src_offs, Ls, K, win["S"], scratch, d_frames=win["d_Ls"][fc])
+        self._gpu.resample_rows_device(scratch, B, C_, Ls, origin, valid, d_offs, L, rt["desc"], rt["d_desc"], rt["d_d0"], rt["d_w"],
+                                       row_table, mono, out, stream=torch.cuda.current_stream(self._dev).cuda_stream)
+        if check:
+            self._check_last(valid, d_files, src_offs, Ls, K, d_shown=d_offs)
+        return out, lengths
+
     def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True, sample_rate=None, mono=False):
         """`batch` crops of num_frames frames drawn on the device: files uniform over the corpus, the first frame uniform in
         0 .. max(T_f - num_frames, 0).  generator: a torch.Generator (of the corpus's device, or of the CPU: then the draws are
@@ -689,7 +854,12 @@ class Corpus(_Closing):
         dev = generator.device if generator is not None else self._dev
         files = torch.randint(0, self.num_files, (B,), generator=generator, device=dev, dtype=torch.int64).to(self._dev)
         u = torch.rand(B, generator=generator, device=dev, dtype=torch.float64).to(self._dev)
-        totals = self._d_num_frames if sample_rate is None else self._rate(sample_rate)[1]
+        if self.sample_rate is None:
+            if sample_rate is None:
+                raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
+            totals = self._mixed_rate(sample_rate)["d_Ty"]
+        else:
+            totals = self._d_num_frames if sample_rate is None else self._rate(sample_rate)[1]
         span = (totals[files] - L).clamp(min=0)
         offs = torch.minimum(torch.floor(u * (span + 1).to(torch.float64)).to(torch.int64), span)
         pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono)

@@ -21,6 +21,7 @@ struct alac_plan_params {
     const uint64_t* crop_offset;  // [B]
     uint32_t n_crops;
     uint32_t crop_frames;         // L
+    const uint32_t* crop_frames_each;   // [B] alac_plan_crops_frames_kernel only: a length per crop, L their bound
     uint32_t entries_per_crop;    // K
     uint64_t dst_stride;
     // the plan: B * K entries, crop-major
@@ -34,6 +35,7 @@ struct alac_plan_params {
 };
 
 __global__ void alac_plan_crops_kernel(alac_plan_params p);
+__global__ void alac_plan_crops_frames_kernel(alac_plan_params p);
 
 // ---- packet compaction (include/alacgpu.h: alacgpu_compact_packets_device) ----------------------------------------------------
 constexpr int ALAC_SCAN_THREADS = 256;

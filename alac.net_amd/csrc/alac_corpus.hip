@@ -1,6 +1,7 @@
 // alac_corpus.hip -- the crop planner: window_plan (alac.net_amd/__init__.py) for B crops at once against a corpus's packet
 // tables in HBM.  It writes the per-packet arrays alacgpu_decode_window_into_device reads, so a step of random crops needs
-// nothing from the host but (file, first frame) pairs.
+// nothing from the host but (file, first frame) pairs.  alac_plan_crops_frames_kernel is the same wave with a window length
+// per crop (the crops of files of different sample rates need different numbers of source frames).
 //
 // One wave per crop.  The crop's facts (file, packet range, the two searches) are wave-uniform; the searches are 64-ary:
 // every step the 64 lanes probe the ends of 64 equal parts of the range with one load and a ballot picks the part, so a file
@@ -52,9 +53,10 @@ __device__ __forceinline__ uint32_t wave_search(const uint64_t* __restrict__ a, 
     return lo;
 }
 
-}  // namespace
-
-__global__ __launch_bounds__(ALAC_PLAN_THREADS) void alac_plan_crops_kernel(alac_plan_params p) {
+// EACH: every crop has a window length of its own, p.crop_frames_each[b], and p.crop_frames is their bound
+// (alacgpu_plan_crops_frames_device)
+template <bool EACH>
+__device__ __forceinline__ void plan_crops(const alac_plan_params& p) {
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t b64 = (uint64_t)blockIdx.x * (ALAC_PLAN_THREADS / 64) + wave;
@@ -63,18 +65,24 @@ __global__ __launch_bounds__(ALAC_PLAN_THREADS) void alac_plan_crops_kernel(alac
     const uint32_t K = p.entries_per_crop;
     const uint32_t f = p.crop_file[b];
     const uint64_t o = p.crop_offset[b];
+    uint32_t frames_b = p.crop_frames;
+    bool fits = true;
+    if constexpr (EACH) {                                // a window longer than the bound would leave its row: no such crop
+        frames_b = p.crop_frames_each[b];
+        fits = frames_b <= p.crop_frames;
+    }
 
     // the crop's file and length: -1 for a file or an offset that does not exist
     int64_t length = -1;
     uint32_t g0 = 0, n = 0;
     uint32_t cfg = ALAC_PLAN_PAD_CFG;
-    if (f < p.n_files) {
+    if (f < p.n_files && fits) {
         g0 = p.file_first[f];
         n = p.file_first[f + 1u] - g0;
         const uint64_t total = n ? p.pkt_end[g0 + n - 1u] : 0u;
         if (o <= total) {
             const uint64_t left = total - o;
-            length = (int64_t)(left < p.crop_frames ? left : (uint64_t)p.crop_frames);
+            length = (int64_t)(left < frames_b ? left : (uint64_t)frames_b);
             cfg = p.file_cfg[f];
         }
     }
@@ -124,6 +132,11 @@ __global__ __launch_bounds__(ALAC_PLAN_THREADS) void alac_plan_crops_kernel(alac
         p.src_skip[j0 + i] = skip;
     }
 }
+
+}  // namespace
+
+__global__ __launch_bounds__(ALAC_PLAN_THREADS) void alac_plan_crops_kernel(alac_plan_params p) { plan_crops<false>(p); }
+__global__ __launch_bounds__(ALAC_PLAN_THREADS) void alac_plan_crops_frames_kernel(alac_plan_params p) { plan_crops<true>(p); }
 
 // ---- packet compaction -----------------------------------------------------------------------------------------------------------
 namespace {

@@ -35,3 +35,34 @@ struct alac_resample_params {
 };
 
 __global__ void alac_resample_kernel(alac_resample_params p);
+
+// ---- a table per row (include/alacgpu.h: alacgpu_resample_rows_device) ---------------------------------------------------------
+// One table of such a call: alacgpu_resample_table of include/alacgpu.h, field for field
+struct alac_resample_table {
+    uint32_t a, b, width;
+    uint32_t d0_first;            // its d0[b] starts at this element of the call's d0 array
+    uint32_t weights_first;       // its weights[b, 2 * width + 1] at this element of the call's weights array
+};
+
+// What it shares with alac_resample_params has the same names: the two kernels share their body.
+struct alac_resample_rows_params {
+    const float* src;             // [rows, channels, src_stride]
+    uint64_t src_stride;
+    const int64_t* src_origin;    // [rows]
+    const int64_t* src_valid;     // [rows]
+    const int64_t* out_first;     // [rows]
+    float* out;                   // [rows, mono ? 1 : channels, out_frames]
+    uint64_t out_frames;
+    const alac_resample_table* tables;   // [n_tables]
+    const int32_t* d0;            // the tables' d0 arrays, one behind the other
+    const float* weights;         // ... and their weights
+    const uint32_t* row_table;    // [rows] the table of a row; n_tables and above: the row is written as zeros
+    uint32_t n_tables;
+    uint32_t channels;
+    uint32_t mono;
+    uint32_t tile;                // output frames per tile, the same for every row
+    uint32_t lds_floats;          // the dynamic LDS of the launch: the largest table (rounded up to 4) + span of a tile
+    uint32_t tiles_per_wg;
+};
+
+__global__ void alac_resample_rows_kernel(alac_resample_rows_params p);

@@ -12,33 +12,53 @@
 // store neighbouring output frames.  Every output element has exactly one writer; there are no atomics, and all loads and
 // stores are plain vector ones.  The arithmetic is nothing (N flops per output frame): what the shape is for is one pass over
 // the source and full cache lines both ways.
+//
+// alacgpu_resample_rows_device is the same workgroup with a table per row: a row names one of the call's tables, the
+// workgroup reads that table's descriptor (it is workgroup-uniform: scalar loads), loads that table into LDS and uses that
+// table's span; the tile is the call's.  Row for row the arithmetic is the one above, so a row is bit for bit what the
+// one-table call gives for it.  A row that names no table is written as zeros.
 #include "alac_resample.h"
 
-__global__ __launch_bounds__(ALAC_RESAMPLE_THREADS) void alac_resample_kernel(alac_resample_params p) {
-    extern __shared__ __align__(16) float lds[];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t N = 2u * p.width + 1u;
-    const uint32_t table = p.b * N;
-    float* const w = lds;
-    float* const xs = lds + ((table + 3u) & ~3u);
+namespace {
 
-    // blockIdx.x: (row, output channel, group of tiles), the group fastest
+// The table a workgroup works with and the source span a tile of it reads
+struct resample_table_view {
+    const int32_t* d0;            // [b]
+    const float* weights;         // [b, 2 * width + 1]
+    uint32_t a, b, width;
+    uint32_t span;                // alac_resample_span(tile, a, b, width)
+};
+
+// blockIdx.x: (row, output channel, group of tiles), the group fastest
+template <class P>
+__device__ __forceinline__ void resample_place(const P& p, uint32_t& group, uint32_t& c, uint64_t& row) {
     const uint32_t out_channels = p.mono ? 1u : p.channels;
     const uint32_t tiles = (uint32_t)((p.out_frames + p.tile - 1u) / p.tile);
     const uint32_t groups = (tiles + p.tiles_per_wg - 1u) / p.tiles_per_wg;
-    const uint32_t group = blockIdx.x % groups;
+    group = blockIdx.x % groups;
     const uint32_t plane = blockIdx.x / groups;
-    const uint32_t c = plane % out_channels;
-    const uint64_t row = plane / out_channels;
+    c = plane % out_channels;
+    row = plane / out_channels;
+}
 
-    for (uint32_t i = tid; i < table; i += ALAC_RESAMPLE_THREADS) w[i] = p.weights[i];
+// The workgroup's tiles of (row, output channel c) with the table t; P: the fields the two kernels' parameters share.
+template <class P>
+__device__ __forceinline__ void resample_tiles(const P& p, const resample_table_view& tb, float* lds, uint32_t group, uint32_t c, uint64_t row) {
+    const uint32_t tid = threadIdx.x;
+    const uint32_t N = 2u * tb.width + 1u;
+    const uint32_t table = tb.b * N;
+    float* const w = lds;
+    float* const xs = lds + ((table + 3u) & ~3u);
+    const uint32_t out_channels = p.mono ? 1u : p.channels;
+
+    for (uint32_t i = tid; i < table; i += ALAC_RESAMPLE_THREADS) w[i] = tb.weights[i];
 
     const int64_t origin = p.src_origin[row];
     int64_t valid = p.src_valid[row];
     valid = valid < 0 ? 0 : (valid > (int64_t)p.src_stride ? (int64_t)p.src_stride : valid);
     const int64_t first = p.out_first[row];
     // the resampled signal has ceil(b (origin + valid) / a) frames: j is one of them iff 0 <= j and j a < b (origin + valid)
-    const int64_t end_b = (origin + valid) * (int64_t)p.b;
+    const int64_t end_b = (origin + valid) * (int64_t)tb.b;
     const bool two = p.mono && p.channels == 2u;
     const float* const s0 = p.src + (row * p.channels + c) * p.src_stride;
     const float* const s1 = s0 + p.src_stride;
@@ -49,16 +69,16 @@ __global__ __launch_bounds__(ALAC_RESAMPLE_THREADS) void alac_resample_kernel(al
         if (k0 >= p.out_frames) break;
         // the tile's first frame j0 = i0 + b m0 (floored: a j below 0 is written as zero, but its taps must not wrap)
         const int64_t j0 = first + (int64_t)k0;
-        int64_t m0 = j0 / (int64_t)p.b;
-        int32_t i0 = (int32_t)(j0 - m0 * (int64_t)p.b);
+        int64_t m0 = j0 / (int64_t)tb.b;
+        int32_t i0 = (int32_t)(j0 - m0 * (int64_t)tb.b);
         if (i0 < 0) {
-            i0 += (int32_t)p.b;
+            i0 += (int32_t)tb.b;
             m0 -= 1;
         }
-        const int32_t d00 = p.d0[i0];
-        const int64_t s_lo = m0 * (int64_t)p.a + d00;      // the first source frame of the tile
+        const int32_t d00 = tb.d0[i0];
+        const int64_t s_lo = m0 * (int64_t)tb.a + d00;      // the first source frame of the tile
         __syncthreads();                                    // (the tile before has been computed)
-        for (uint32_t idx = tid; idx < p.span; idx += ALAC_RESAMPLE_THREADS) {
+        for (uint32_t idx = tid; idx < tb.span; idx += ALAC_RESAMPLE_THREADS) {
             const int64_t rel = s_lo + idx - origin;
             float v = 0.0f;
             if (rel >= 0 && rel < valid) {
@@ -72,16 +92,72 @@ __global__ __launch_bounds__(ALAC_RESAMPLE_THREADS) void alac_resample_kernel(al
         const uint32_t n_out = left < p.tile ? (uint32_t)left : p.tile;
         for (uint32_t k = tid; k < n_out; k += ALAC_RESAMPLE_THREADS) {
             const uint32_t ii = (uint32_t)i0 + k;
-            const uint32_t mo = ii / p.b;
-            const uint32_t i = ii - mo * p.b;
-            uint32_t rel = mo * p.a + (uint32_t)(p.d0[i] - d00);
-            rel = rel > p.span - N ? p.span - N : rel;      // (a table that is what resample.py makes it never gets here)
+            const uint32_t mo = ii / tb.b;
+            const uint32_t i = ii - mo * tb.b;
+            uint32_t rel = mo * tb.a + (uint32_t)(tb.d0[i] - d00);
+            rel = rel > tb.span - N ? tb.span - N : rel;      // (a table that is what resample.py makes it never gets here)
             const float* const wr = w + i * N;
             const float* const x = xs + rel;
             float acc = 0.0f;
             for (uint32_t n = 0; n < N; ++n) acc = __builtin_fmaf(wr[n], x[n], acc);
             const int64_t j = j0 + (int64_t)k;
-            dst[k0 + k] = (j >= 0 && j * (int64_t)p.a < end_b) ? acc : 0.0f;
+            dst[k0 + k] = (j >= 0 && j * (int64_t)tb.a < end_b) ? acc : 0.0f;
         }
     }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(ALAC_RESAMPLE_THREADS) void alac_resample_kernel(alac_resample_params p) {
+    extern __shared__ __align__(16) float lds[];
+    uint32_t group, c;
+    uint64_t row;
+    resample_place(p, group, c, row);
+    resample_table_view t;
+    t.d0 = p.d0;
+    t.weights = p.weights;
+    t.a = p.a;
+    t.b = p.b;
+    t.width = p.width;
+    t.span = p.span;
+    resample_tiles(p, t, lds, group, c, row);
+}
+
+__global__ __launch_bounds__(ALAC_RESAMPLE_THREADS) void alac_resample_rows_kernel(alac_resample_rows_params p) {
+    extern __shared__ __align__(16) float lds[];
+    uint32_t group, c;
+    uint64_t row;
+    resample_place(p, group, c, row);
+    // the row's table: everything here is workgroup-uniform.  A descriptor that is not what the host was shown (no ratio, a
+    // table or a span that does not fit the LDS of this launch) counts as no table: nothing is ever stored outside the LDS
+    const uint32_t ti = p.row_table[row];
+    bool has = ti < p.n_tables;
+    resample_table_view t = {};
+    if (has) {
+        const alac_resample_table d = p.tables[ti];
+        const uint64_t weights = (uint64_t)d.b * (2u * (uint64_t)d.width + 1u);
+        has = d.a != 0 && d.b != 0 && d.width != 0 && weights <= ALAC_RESAMPLE_MAX_TABLE;
+        if (has) {
+            const uint64_t span = alac_resample_span(p.tile, d.a, d.b, d.width);
+            has = ((weights + 3u) & ~3ull) + span <= p.lds_floats;
+            t.d0 = p.d0 + d.d0_first;
+            t.weights = p.weights + d.weights_first;
+            t.a = d.a;
+            t.b = d.b;
+            t.width = d.width;
+            t.span = (uint32_t)span;
+        }
+    }
+    if (has) {
+        resample_tiles(p, t, lds, group, c, row);
+        return;
+    }
+    // a row without a table (the crop of a file or an offset outside the corpus): zeros
+    const uint32_t out_channels = p.mono ? 1u : p.channels;
+    float* const dst = p.out + (row * out_channels + c) * p.out_frames;
+    const uint64_t k0 = (uint64_t)group * p.tiles_per_wg * p.tile;
+    const uint64_t left = p.out_frames > k0 ? p.out_frames - k0 : 0u;
+    const uint64_t most = (uint64_t)p.tiles_per_wg * p.tile;
+    const uint32_t n_out = (uint32_t)(left < most ? left : most);
+    for (uint32_t k = threadIdx.x; k < n_out; k += ALAC_RESAMPLE_THREADS) dst[k0 + k] = 0.0f;
 }

@@ -2,6 +2,7 @@
 // No CPU fallback anywhere in this file: every decode goes through alac_decode_ab_kernel / alac_decode_ab32_kernel.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cstddef>
 
 #include <cstdio>
 #include <cstdlib>
@@ -505,11 +506,12 @@ int alacgpu_decode_into_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t bl
                                              d_out_samples, d_status, hip_stream);
 }
 
-int alacgpu_plan_crops_device(alacgpu_ctx* ctx, const void* d_pkt_offset, const void* d_pkt_size, const void* d_pkt_end,
-                              const void* d_file_first, const void* d_file_cfg, uint32_t n_files, const void* d_crop_file,
-                              const void* d_crop_offset, uint32_t n_crops, uint32_t crop_frames, uint32_t entries_per_crop,
-                              uint64_t dst_stride, void* d_offsets, void* d_sizes, void* d_cfg_idx, void* d_dst_first,
-                              void* d_dst_frames, void* d_src_skip, void* d_lengths, void* hip_stream) {
+// Both planner entry points; each: every crop has a window length of its own, d_crop_frames[n_crops]
+static int plan_crops(alacgpu_ctx* ctx, const void* d_pkt_offset, const void* d_pkt_size, const void* d_pkt_end,
+                      const void* d_file_first, const void* d_file_cfg, uint32_t n_files, const void* d_crop_file,
+                      const void* d_crop_offset, bool each, const void* d_crop_frames, uint32_t n_crops, uint32_t crop_frames,
+                      uint32_t entries_per_crop, uint64_t dst_stride, void* d_offsets, void* d_sizes, void* d_cfg_idx,
+                      void* d_dst_first, void* d_dst_frames, void* d_src_skip, void* d_lengths, void* hip_stream) {
     if (!ctx) return ALACGPU_ERR_BAD_ARG;
     if (n_crops == 0) return ALACGPU_OK;
     if (entries_per_crop == 0 || (uint64_t)n_crops * entries_per_crop > 0xFFFFFFFFull) return ALACGPU_ERR_BAD_ARG;
@@ -522,6 +524,7 @@ int alacgpu_plan_crops_device(alacgpu_ctx* ctx, const void* d_pkt_offset, const 
         ((uintptr_t)d_cfg_idx & 1u) != 0 || ((uintptr_t)d_dst_first & 7u) != 0 || ((uintptr_t)d_dst_frames & 3u) != 0 ||
         ((uintptr_t)d_src_skip & 3u) != 0 || ((uintptr_t)d_lengths & 7u) != 0)
         return ALACGPU_ERR_BAD_ARG;
+    if (each && (!d_crop_frames || ((uintptr_t)d_crop_frames & 3u) != 0)) return ALACGPU_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     alac_plan_params p;
     p.pkt_offset = (const uint64_t*)d_pkt_offset;
@@ -534,6 +537,7 @@ int alacgpu_plan_crops_device(alacgpu_ctx* ctx, const void* d_pkt_offset, const 
     p.crop_offset = (const uint64_t*)d_crop_offset;
     p.n_crops = n_crops;
     p.crop_frames = crop_frames;
+    p.crop_frames_each = each ? (const uint32_t*)d_crop_frames : nullptr;
     p.entries_per_crop = entries_per_crop;
     p.dst_stride = dst_stride;
     p.offsets = (uint64_t*)d_offsets;
@@ -545,10 +549,32 @@ int alacgpu_plan_crops_device(alacgpu_ctx* ctx, const void* d_pkt_offset, const 
     p.lengths = (int64_t*)d_lengths;
     constexpr uint32_t per_wg = ALAC_PLAN_THREADS / 64;   // one wave per crop
     void* kargs[] = {&p};
-    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_plan_crops_kernel, dim3((n_crops + per_wg - 1u) / per_wg), dim3(ALAC_PLAN_THREADS),
-                                 kargs, 0, (hipStream_t)hip_stream));
+    const void* const kernel = each ? (const void*)alac_plan_crops_frames_kernel : (const void*)alac_plan_crops_kernel;
+    HIP_TRY(ctx, hipLaunchKernel(kernel, dim3((n_crops + per_wg - 1u) / per_wg), dim3(ALAC_PLAN_THREADS), kargs, 0,
+                                 (hipStream_t)hip_stream));
     HIP_TRY(ctx, hipGetLastError());
     return ALACGPU_OK;
+}
+
+int alacgpu_plan_crops_device(alacgpu_ctx* ctx, const void* d_pkt_offset, const void* d_pkt_size, const void* d_pkt_end,
+                              const void* d_file_first, const void* d_file_cfg, uint32_t n_files, const void* d_crop_file,
+                              const void* d_crop_offset, uint32_t n_crops, uint32_t crop_frames, uint32_t entries_per_crop,
+                              uint64_t dst_stride, void* d_offsets, void* d_sizes, void* d_cfg_idx, void* d_dst_first,
+                              void* d_dst_frames, void* d_src_skip, void* d_lengths, void* hip_stream) {
+    return plan_crops(ctx, d_pkt_offset, d_pkt_size, d_pkt_end, d_file_first, d_file_cfg, n_files, d_crop_file, d_crop_offset, false,
+                      nullptr, n_crops, crop_frames, entries_per_crop, dst_stride, d_offsets, d_sizes, d_cfg_idx, d_dst_first,
+                      d_dst_frames, d_src_skip, d_lengths, hip_stream);
+}
+
+int alacgpu_plan_crops_frames_device(alacgpu_ctx* ctx, const void* d_pkt_offset, const void* d_pkt_size, const void* d_pkt_end,
+                                     const void* d_file_first, const void* d_file_cfg, uint32_t n_files, const void* d_crop_file,
+                                     const void* d_crop_offset, const void* d_crop_frames, uint32_t n_crops, uint32_t crop_frames,
+                                     uint32_t entries_per_crop, uint64_t dst_stride, void* d_offsets, void* d_sizes,
+                                     void* d_cfg_idx, void* d_dst_first, void* d_dst_frames, void* d_src_skip, void* d_lengths,
+                                     void* hip_stream) {
+    return plan_crops(ctx, d_pkt_offset, d_pkt_size, d_pkt_end, d_file_first, d_file_cfg, n_files, d_crop_file, d_crop_offset, true,
+                      d_crop_frames, n_crops, crop_frames, entries_per_crop, dst_stride, d_offsets, d_sizes, d_cfg_idx, d_dst_first,
+                      d_dst_frames, d_src_skip, d_lengths, hip_stream);
 }
 
 // The exclusive scan both alacgpu_compact_packets_device and alacgpu_stage_packets_device begin with: s0 holds the sizes, how
@@ -711,6 +737,30 @@ int alacgpu_stage_packets_device(alacgpu_ctx* ctx, const void* d_blob_lo, uint64
     return ALACGPU_OK;
 }
 
+// The tile of a resample launch: as many output frames as leave a CU room for two workgroups, down to 256; fewer only where the
+// span of 256 does not fit the CU at all (a / b in the hundreds) -- one frame's span, 2 width + 2, always fits next to the table.
+// lds_bytes(tile): the dynamic LDS a workgroup needs for that tile.
+extern "C++" {
+template <class F>
+static uint32_t resample_tile(const F& lds_bytes) {
+    uint32_t tile = ALAC_RESAMPLE_MAX_TILE;
+    while (tile > 256u && lds_bytes(tile) > ALAC_RESAMPLE_LDS_PREFERRED) tile /= 2u;
+    while (tile > 1u && lds_bytes(tile) > ALAC_RESAMPLE_LDS_MAX) tile /= 2u;
+    return tile;
+}
+}
+
+// The grid: a workgroup takes up to eight consecutive tiles with one load of the table, while a thousand workgroups remain.
+// false: 2^31 tiles of output or more.
+static bool resample_grid(uint64_t out_frames, uint32_t tile, uint64_t planes, uint32_t& per_wg, uint32_t& blocks) {
+    const uint64_t tiles = (out_frames + tile - 1u) / tile;
+    if (tiles > 0xFFFFFFFFull || tiles * planes > 0x7FFFFFFFull) return false;
+    const uint64_t n = std::min<uint64_t>(std::max<uint64_t>(tiles * planes / 1024u, 1u), std::min<uint64_t>(tiles, ALAC_RESAMPLE_MAX_TILES_PER_WG));
+    per_wg = (uint32_t)n;
+    blocks = (uint32_t)((tiles + n - 1u) / n * planes);
+    return true;
+}
+
 int alacgpu_resample_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,
                             const void* d_src_origin, const void* d_src_valid, const void* d_out_first, uint64_t out_frames,
                             uint32_t a, uint32_t b, uint32_t width, const void* d_d0, const void* d_weights, int mono, void* d_out,
@@ -724,19 +774,11 @@ int alacgpu_resample_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, 
     const uint64_t table = (uint64_t)b * (2u * (uint64_t)width + 1u);
     if (table > ALAC_RESAMPLE_MAX_TABLE) return ALACGPU_ERR_BAD_ARG;
     if (rows == 0 || out_frames == 0) return ALACGPU_OK;
-    // the tile: as many output frames as leave a CU room for two workgroups, down to 256; fewer only where the span of 256
-    // does not fit the CU at all (a / b in the hundreds) -- one frame's span, 2 width + 2, always fits next to the table
     const auto lds_bytes = [&](uint64_t tile) { return sizeof(float) * (size_t)(((table + 3u) & ~3ull) + alac_resample_span(tile, a, b, width)); };
-    uint32_t tile = ALAC_RESAMPLE_MAX_TILE;
-    while (tile > 256u && lds_bytes(tile) > ALAC_RESAMPLE_LDS_PREFERRED) tile /= 2u;
-    while (tile > 1u && lds_bytes(tile) > ALAC_RESAMPLE_LDS_MAX) tile /= 2u;
+    const uint32_t tile = resample_tile(lds_bytes);
     const size_t lds = lds_bytes(tile);
-    // the grid: a workgroup takes up to eight consecutive tiles with one load of the table, while a thousand workgroups remain
-    const uint64_t tiles = (out_frames + tile - 1u) / tile;
-    const uint64_t planes = (uint64_t)rows * (mono ? 1u : channels);
-    if (tiles > 0xFFFFFFFFull || tiles * planes > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
-    const uint64_t per_wg = std::min<uint64_t>(std::max<uint64_t>(tiles * planes / 1024u, 1u), std::min<uint64_t>(tiles, ALAC_RESAMPLE_MAX_TILES_PER_WG));
-    const uint64_t groups = (tiles + per_wg - 1u) / per_wg;
+    uint32_t per_wg, blocks;
+    if (!resample_grid(out_frames, tile, (uint64_t)rows * (mono ? 1u : channels), per_wg, blocks)) return ALACGPU_ERR_BAD_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (lds > ALAC_RESAMPLE_LDS_PREFERRED)
         HIP_TRY(ctx, hipFuncSetAttribute((const void*)alac_resample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -757,10 +799,73 @@ int alacgpu_resample_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, 
     p.mono = mono ? 1u : 0u;
     p.tile = tile;
     p.span = (uint32_t)alac_resample_span(tile, a, b, width);
-    p.tiles_per_wg = (uint32_t)per_wg;
+    p.tiles_per_wg = per_wg;
     void* kargs[] = {&p};
-    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_resample_kernel, dim3((uint32_t)(groups * planes)), dim3(ALAC_RESAMPLE_THREADS),
-                                 kargs, lds, (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_resample_kernel, dim3(blocks), dim3(ALAC_RESAMPLE_THREADS), kargs, lds,
+                                 (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
+}
+
+static_assert(sizeof(alacgpu_resample_table) == sizeof(alac_resample_table) && offsetof(alacgpu_resample_table, weights_first) ==
+              offsetof(alac_resample_table, weights_first), "the kernel reads the header's table descriptors as they are");
+
+int alacgpu_resample_rows_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,
+                                 const void* d_src_origin, const void* d_src_valid, const void* d_out_first, uint64_t out_frames,
+                                 const alacgpu_resample_table* tables, const void* d_tables, uint32_t n_tables, const void* d_d0,
+                                 const void* d_weights, const void* d_row_table, int mono, void* d_out, void* hip_stream) {
+    if (!ctx || !d_src || !d_src_origin || !d_src_valid || !d_out_first || !tables || !d_tables || !d_d0 || !d_weights ||
+        !d_row_table || !d_out)
+        return ALACGPU_ERR_BAD_ARG;
+    if (((uintptr_t)d_src & 3u) != 0 || ((uintptr_t)d_src_origin & 7u) != 0 || ((uintptr_t)d_src_valid & 7u) != 0 ||
+        ((uintptr_t)d_out_first & 7u) != 0 || ((uintptr_t)tables & 3u) != 0 || ((uintptr_t)d_tables & 3u) != 0 || ((uintptr_t)d_d0 & 3u) != 0 ||
+        ((uintptr_t)d_weights & 3u) != 0 || ((uintptr_t)d_row_table & 3u) != 0 || ((uintptr_t)d_out & 3u) != 0)
+        return ALACGPU_ERR_BAD_ARG;
+    if (n_tables == 0 || channels < 1 || channels > 2) return ALACGPU_ERR_BAD_ARG;
+    for (uint32_t t = 0; t < n_tables; t++) {
+        const alacgpu_resample_table& d = tables[t];
+        if (d.a == 0 || d.b == 0 || d.width == 0 || (uint64_t)d.b * (2u * (uint64_t)d.width + 1u) > ALAC_RESAMPLE_MAX_TABLE)
+            return ALACGPU_ERR_BAD_ARG;
+    }
+    if (rows == 0 || out_frames == 0) return ALACGPU_OK;
+    // one tile for the launch, and the LDS of the table that needs the most for it; a workgroup uses its own table's span
+    const auto lds_bytes = [&](uint64_t tile) {
+        uint64_t most = 0;
+        for (uint32_t t = 0; t < n_tables; t++) {
+            const alacgpu_resample_table& d = tables[t];
+            const uint64_t table = (uint64_t)d.b * (2u * (uint64_t)d.width + 1u);
+            most = std::max<uint64_t>(most, ((table + 3u) & ~3ull) + alac_resample_span(tile, d.a, d.b, d.width));
+        }
+        return sizeof(float) * (size_t)most;
+    };
+    const uint32_t tile = resample_tile(lds_bytes);
+    const size_t lds = lds_bytes(tile);
+    uint32_t per_wg, blocks;
+    if (!resample_grid(out_frames, tile, (uint64_t)rows * (mono ? 1u : channels), per_wg, blocks)) return ALACGPU_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (lds > ALAC_RESAMPLE_LDS_PREFERRED)
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)alac_resample_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    alac_resample_rows_params p;
+    p.src = (const float*)d_src;
+    p.src_stride = src_stride;
+    p.src_origin = (const int64_t*)d_src_origin;
+    p.src_valid = (const int64_t*)d_src_valid;
+    p.out_first = (const int64_t*)d_out_first;
+    p.out = (float*)d_out;
+    p.out_frames = out_frames;
+    p.tables = (const alac_resample_table*)d_tables;
+    p.d0 = (const int32_t*)d_d0;
+    p.weights = (const float*)d_weights;
+    p.row_table = (const uint32_t*)d_row_table;
+    p.n_tables = n_tables;
+    p.channels = channels;
+    p.mono = mono ? 1u : 0u;
+    p.tile = tile;
+    p.lds_floats = (uint32_t)(lds / sizeof(float));
+    p.tiles_per_wg = per_wg;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_resample_rows_kernel, dim3(blocks), dim3(ALAC_RESAMPLE_THREADS), kargs, lds,
+                                 (hipStream_t)hip_stream));
     HIP_TRY(ctx, hipGetLastError());
     return ALACGPU_OK;
 }

@@ -58,6 +58,12 @@ namespace ALACdotNET.Decoder
             IntPtr dFileFirst, IntPtr dFileCfg, uint nFiles, IntPtr dCropFile, IntPtr dCropOffset, uint nCrops, uint cropFrames,
             uint entriesPerCrop, ulong dstStride, IntPtr dOffsets, IntPtr dSizes, IntPtr dCfgIdx, IntPtr dDstFirst, IntPtr dDstFrames,
             IntPtr dSrcSkip, IntPtr dLengths, IntPtr hipStream);
+        /// <summary>alacgpu_plan_crops_device with a window length per crop, dCropFrames[b] (uint), cropFrames their bound: a crop
+        /// whose length is above it gets dLengths[b] = -1 and no packets.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_plan_crops_frames_device(IntPtr ctx, IntPtr dPktOffset, IntPtr dPktSize,
+            IntPtr dPktEnd, IntPtr dFileFirst, IntPtr dFileCfg, uint nFiles, IntPtr dCropFile, IntPtr dCropOffset, IntPtr dCropFrames,
+            uint nCrops, uint cropFrames, uint entriesPerCrop, ulong dstStride, IntPtr dOffsets, IntPtr dSizes, IntPtr dCfgIdx,
+            IntPtr dDstFirst, IntPtr dDstFrames, IntPtr dSrcSkip, IntPtr dLengths, IntPtr hipStream);
         /// <summary>Compact the encoder's packets (packet p in its slot at dPackets + p * slotBytes, its size in dSizes[p]) back to
         /// back into dBlob from byte baseOffset on: writes dPktOffset[p] (ulong) and dTotal[0] (ulong); a packet that would end behind
         /// blobCapacity is not copied.  Every pointer a device pointer, asynchronous on hipStream.</summary>
@@ -77,6 +83,15 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_resample_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
             ulong srcStride, IntPtr dSrcOrigin, IntPtr dSrcValid, IntPtr dOutFirst, ulong outFrames, uint a, uint b, uint width,
             IntPtr dD0, IntPtr dWeights, int mono, IntPtr dOut, IntPtr hipStream);
+        /// <summary>One table of alacgpu_resample_rows_device: the ratio a : b, the filter's width, and where the table's d0[b] and
+        /// weights[b, 2 * width + 1] start in the call's two arrays (in elements).</summary>
+        [StructLayout(LayoutKind.Sequential)] public struct ResampleTable { public uint a, b, width, d0First, weightsFirst; }
+        /// <summary>alacgpu_resample_device with a table per row: nTables descriptors (tables on the host, dTables the same on the
+        /// device), their d0 and weights one behind the other in dD0 and dWeights, and dRowTable[r] (uint) the table of row r;
+        /// a row whose index is nTables or above is written as zeros.  Asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_resample_rows_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
+            ulong srcStride, IntPtr dSrcOrigin, IntPtr dSrcValid, IntPtr dOutFirst, ulong outFrames, [In] ResampleTable[] tables,
+            IntPtr dTables, uint nTables, IntPtr dD0, IntPtr dWeights, IntPtr dRowTable, int mono, IntPtr dOut, IntPtr hipStream);
         /// <summary>Encode PCM in device memory (int32 or float32, interleaved or planar) to ALAC packets in device memory, one
         /// run of frames per packet, packet p at dPackets + p * slotBytes; asynchronous on hipStream.</summary>
         [DllImport(Lib)] public static extern UIntPtr alacgpu_encode_max_packet_bytes(uint frames, int sampleSize, int channels);

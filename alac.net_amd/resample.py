@@ -11,7 +11,8 @@ for |d - i * a / b| < Z * a / f <= width, so the N = 2 * width + 1 taps from d0[
 them, and output j reads the source frames floor(j * a / b) - width .. + N.  (The filter torchaudio.functional.resample uses by
 default, with only the non-zero taps kept.)
 
-`resample_table`, `resample_host` (the kernel's specification in numpy) and `source_window` need no device.  `resample` is the
+`resample_table`, `resample_host` (the kernel's specification in numpy), `source_window` and `rows_tables` (the tables of a
+call whose rows have different source rates, alacgpu_resample_rows_device) need no device.  `resample` is the
 call on device tensors.
 """
 import math
@@ -70,6 +71,33 @@ def identity_table():
     """The table that copies: a = b = 1 with one tap of weight 1 between two of weight 0 (the kernel wants width >= 1).  What
     `mono` alone runs through the kernel; the filter of equal rates is never built."""
     return 1, 1, 1, np.array([-1], dtype=np.int32), np.array([[0.0, 1.0, 0.0]], dtype=np.float32)
+
+
+def rows_tables(rates, new_rate):
+    """The tables of a call with a table per row (alacgpu_resample_rows_device) for sources of the sample rates `rates` that
+    all go to new_rate: one table per distinct reduced ratio, in the order the ratios first appear, a source already at
+    new_rate with `identity_table`.  Returns (table_of int64 [len(rates)]: a source's table, desc uint32 [n_tables, 5]: a, b,
+    width and where the table's d0 and weights start in the two arrays, d0 int32: the tables' d0 one behind the other,
+    weights float32: their weights, flat).  ValueError: a rate that is not a positive integer; a table of more than 16384
+    weights, naming the first source that needs it."""
+    index, desc, d0s, ws, table_of = {}, [], [], [], []
+    n_d0 = n_w = 0
+    for f, rate in enumerate(rates):
+        a, b = _ratio(rate, new_rate)
+        if (a, b) not in index:
+            try:
+                a, b, width, d0, w = identity_table() if a == b else resample_table(rate, new_rate)
+            except ValueError as e:
+                raise ValueError(f"source {f}: {e}") from None
+            index[(a, b)] = len(desc)
+            desc.append((a, b, width, n_d0, n_w))
+            d0s.append(d0.reshape(-1))
+            ws.append(w.reshape(-1))
+            n_d0, n_w = n_d0 + d0.size, n_w + w.size
+        table_of.append(index[(a, b)])
+    return (np.asarray(table_of, dtype=np.int64), np.asarray(desc, dtype=np.uint32).reshape(-1, 5),
+            np.concatenate(d0s).astype(np.int32) if d0s else np.zeros(0, np.int32),
+            np.concatenate(ws).astype(np.float32) if ws else np.zeros(0, np.float32))
 
 
 def source_window(o, L, a, b, width):

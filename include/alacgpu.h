@@ -264,6 +264,23 @@ int alacgpu_plan_crops_device(alacgpu_ctx* ctx, const void* d_pkt_offset, const 
                               void* d_src_skip, void* d_lengths, void* hip_stream);
 
 /*
+ * alacgpu_plan_crops_device with a window length per crop (no counterpart in the reference): the crops of files of different
+ * sample rates need different numbers of source frames for the same frames at the target rate.  Everything is as above but
+ *   d_crop_frames[b]  uint32: crop b's window length; crop_frames is the bound of them all and dst_stride stays the uniform
+ *                     row stride (C * crop_frames addresses a planar [B, C, crop_frames] tensor)
+ *   d_lengths[b]      min(d_crop_frames[b], T_f - offset); -1 also for a d_crop_frames[b] above crop_frames: no packets, so
+ *                     nothing is ever planned outside a row; -2 as above
+ * With every d_crop_frames[b] equal to crop_frames the plan is the one alacgpu_plan_crops_device writes, bit for bit.
+ * ALACGPU_ERR_BAD_ARG as above, and for a NULL or misaligned (4) d_crop_frames.
+ */
+int alacgpu_plan_crops_frames_device(alacgpu_ctx* ctx, const void* d_pkt_offset, const void* d_pkt_size, const void* d_pkt_end,
+                                     const void* d_file_first, const void* d_file_cfg, uint32_t n_files,
+                                     const void* d_crop_file, const void* d_crop_offset, const void* d_crop_frames,
+                                     uint32_t n_crops, uint32_t crop_frames, uint32_t entries_per_crop, uint64_t dst_stride,
+                                     void* d_offsets, void* d_sizes, void* d_cfg_idx, void* d_dst_first, void* d_dst_frames,
+                                     void* d_src_skip, void* d_lengths, void* hip_stream);
+
+/*
  * Encoder (no counterpart in the reference, which only decodes): PCM in HBM to ALAC packets in HBM, one packet per run of
  * frames, asynchronous on hip_stream.  Device pointers; d_pcm 4-byte, d_src_first 8-byte, d_packets 16-byte aligned.
  *   d_pcm            src_elems int32 (ALACGPU_DST_INT32: the canonical sample, clamped to the sample range) or float32
@@ -379,6 +396,34 @@ int alacgpu_resample_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, 
                             const void* d_src_origin, const void* d_src_valid, const void* d_out_first, uint64_t out_frames,
                             uint32_t a, uint32_t b, uint32_t width, const void* d_d0, const void* d_weights, int mono,
                             void* d_out, void* hip_stream);
+
+/*
+ * alacgpu_resample_device with a table per row (no counterpart in the reference): the rows of one call are crops of files of
+ * different sample rates, all resampled to one target rate.  The call has n_tables tables; table t is a : b and width as
+ * above, its d0[b] starts at element d0_first of d_d0 and its weights[b, 2 * width + 1] at element weights_first of d_weights.
+ *   tables, d_tables  the n_tables descriptors twice: in host memory, where the call checks them and sizes the launch, and in
+ *                     device memory (4-byte aligned), where the kernel reads them.  They must agree; a workgroup that reads a
+ *                     descriptor that does not fit the launch writes its row as zeros, so nothing outside d_out or the
+ *                     workgroup's LDS is ever stored to.  Nothing is read back
+ *   d_row_table[r]    uint32: the table of row r.  A row with d_row_table[r] >= n_tables is written as zeros (the row of a
+ *                     crop outside the corpus)
+ * Everything else -- d_src, d_src_origin, d_src_valid, d_out_first, d_out, mono -- is alacgpu_resample_device's, and row r is
+ * what that call computes for the row with row r's table: the same float32 fused multiply-adds in the same order, so the two
+ * agree bit for bit.  One tile (output frames per workgroup step) serves the whole launch, chosen as above for the table that
+ * needs the most LDS for it; a workgroup loads its own row's table and uses its own table's span.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: as above, and n_tables == 0, a NULL or misaligned `tables`, d_tables or
+ * d_row_table, or any table with a, b or width 0 or b * (2 * width + 1) above 16384.
+ */
+typedef struct alacgpu_resample_table {
+    uint32_t a, b, width;
+    uint32_t d0_first;
+    uint32_t weights_first;
+} alacgpu_resample_table;
+int alacgpu_resample_rows_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,
+                                 const void* d_src_origin, const void* d_src_valid, const void* d_out_first, uint64_t out_frames,
+                                 const alacgpu_resample_table* tables, const void* d_tables, uint32_t n_tables,
+                                 const void* d_d0, const void* d_weights, const void* d_row_table, int mono, void* d_out,
+                                 void* hip_stream);
 
 /* Single-packet drop-in for `int DecodeFrame(byte[] inbuffer, int[] outbuffer)` (AlacFile.cs:428):
  * writes the reference's own int[] layout (24-bit: one int per byte) and returns its byte count in

@@ -1,0 +1,168 @@
+"""What crops at a target rate cost per training step when the files differ in sample rate: synthetic M4A files (stereo 16-bit,
+4096-frame packets, 60 s each), device index tensors and check=False throughout, 64 crops of 2 s --
+  (a) single_rate   the step of tools/bench_resample.py on a corpus at 44.1 kHz: crops(..., sample_rate=16000, mono=True) and
+                    crops(..., sample_rate=48000).  With --parent DIR (a built tree of the parent commit) the same calls on the
+                    parent's package, alternating with this one: this tree's median has to lie inside the parent's p10 .. p90
+  (b) mixed         Corpus(half the files at 44.1 kHz, half at 48 kHz, mixed_rates=True): crops(..., sample_rate=16000,
+                    mono=True), half the crops from either half, in one call; HIP events around the plan + decode pair and
+                    around the one resample call (--reps back-to-back launches)
+  (c) two_corpora   the two single-rate corpora of the same files and the same crops in two calls of half the batch each
+Wall time of a step: torch.cuda.synchronize() in front of and behind it, the ways alternating inside every step, median and
+p10 .. p90 of --steps steps after --warmup.  One JSON document, printed and written to --out.
+  python tools/bench_corpus_mixed.py [--parent DIR] [--steps 200] [--warmup 20] [--out profiles/corpus_mixed_rates.json]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def make_file(synth, frames, seed, rate):
+    from alac.net_amd.synth import m4a
+
+    n = -(-frames // 4096)
+    d = synth.packet_descs(n, stereo=1)
+    d["n"][-1] = frames - (n - 1) * 4096
+    b = synth.make_batch(d, synth.default_signal(seed))
+    packets = [bytes(b["blob"][int(o):int(o) + int(s)]) for o, s in zip(b["offsets"], b["sizes"])]
+    return m4a.write_m4a(packets, [int(x) for x in d["n"]], sample_size=16, channels=2, sample_rate=rate)
+
+
+def event_ms(torch, stream, fn, reps):
+    ms = []
+    for rep in range(30 + 5):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record(stream)
+        for _ in range(reps):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        if rep >= 5:
+            ms.append(e0.elapsed_time(e1) / reps)
+    return ms
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=32)
+    ap.add_argument("--seconds", type=float, default=60.0)
+    ap.add_argument("--crops", type=int, default=64)
+    ap.add_argument("--crop-seconds", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--parent", help="a built tree of the parent commit: its single-rate steps alternate with this tree's")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "corpus_mixed_rates.json"))
+    args = ap.parse_args()
+    import torch
+
+    import alac.net_amd as pkg
+    from alac.net_amd import synth
+    from bench_resample import load_parent, stats
+
+    synth.build()
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.current_stream(dev)
+    half, B, R = args.files // 2, args.crops, 16000
+    L = args.crop_seconds * R
+    rates = (44100, 48000)
+    blobs = {r: [make_file(synth, int(args.seconds * r), 11 + k, r) for k in range(2)] for r in rates}
+    of_rate = {r: [blobs[r][f % 2] for f in range(half)] for r in rates}
+    n_steps = args.steps + args.warmup
+    rng = np.random.default_rng(B)
+    doc = {"command": "python tools/bench_corpus_mixed.py " + " ".join(sys.argv[1:]), "files": args.files, "seconds": args.seconds,
+           "crops": B, "crop_seconds": args.crop_seconds, "steps": args.steps, "warmup": args.warmup, "reps": args.reps}
+
+    def measure(ways):
+        wall = {m: [] for m in ways}
+        for i in range(n_steps):
+            for m, fn in ways.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = fn(i)
+                torch.cuda.synchronize()
+                dt = (time.perf_counter() - t0) * 1e3
+                del out
+                if i >= args.warmup:
+                    wall[m].append(dt)
+        return {m: stats(v) for m, v in wall.items()}
+
+    # (a) the single-rate step, this tree against the parent
+    single = pkg.Corpus(of_rate[44100] + of_rate[44100])
+    parent = load_parent(args.parent).Corpus(of_rate[44100] + of_rate[44100]) if args.parent else None
+    T = int(args.seconds * 44100)
+    files = [torch.from_numpy(rng.integers(0, 2 * half, B)).to(dev) for _ in range(n_steps)]
+    u = [rng.random(B) for _ in range(n_steps)]
+    offs = {r: [torch.from_numpy((x * (-(-r * T // 44100) - args.crop_seconds * r + 1)).astype(np.int64)).to(dev) for x in u] for r in (16000, 48000)}
+    ways = {}
+    for name, c in (("this", single), ("parent", parent)):
+        if c is not None:
+            ways[f"{name}_16000_mono"] = lambda i, c=c: c.crops(files[i], offs[16000][i], L, check=False, sample_rate=16000, mono=True)[0]
+            ways[f"{name}_48000"] = lambda i, c=c: c.crops(files[i], offs[48000][i], args.crop_seconds * 48000, check=False, sample_rate=48000)[0]
+    if parent is not None:
+        for k in ("16000_mono", "48000"):
+            assert torch.equal(ways[f"this_{k}"](0), ways[f"parent_{k}"](0)), "the crops differ from the parent's"
+    a = {"wall_ms": measure(ways)}
+    if parent is not None:
+        for k in ("16000_mono", "48000"):
+            p, n = a["wall_ms"][f"parent_{k}"], a["wall_ms"][f"this_{k}"]
+            a[f"{k}_inside_parent_p10_p90"] = bool(p["p10"] <= n["median"] <= p["p90"])
+        parent.close()
+    single.close()
+    doc["single_rate"] = a
+
+    # (b) the mixed step and (c) the two single-rate corpora over the same crops
+    mixed = pkg.Corpus(of_rate[44100] + of_rate[48000], mixed_rates=True)
+    two = [pkg.Corpus(of_rate[r]) for r in rates]
+    Ty = torch.from_numpy(mixed.resampled_frames(R)).to(dev)
+    files = [torch.from_numpy(np.concatenate([rng.integers(0, half, B // 2), half + rng.integers(0, half, B - B // 2)])).to(dev) for _ in range(n_steps)]
+    offs = [torch.floor(torch.from_numpy(rng.random(B)).to(dev) * (Ty[f] - L + 1).to(torch.float64)).to(torch.int64) for f in files]
+    h = B // 2
+
+    def both(i):
+        x = two[0].crops(files[i][:h], offs[i][:h], L, check=False, sample_rate=R, mono=True)[0]
+        y = two[1].crops(files[i][h:] - half, offs[i][h:], L, check=False, sample_rate=R, mono=True)[0]
+        return x, y
+
+    ways = {"mixed": lambda i: mixed.crops(files[i], offs[i], L, check=False, sample_rate=R, mono=True)[0], "two_corpora": both}
+    assert torch.equal(ways["mixed"](0), torch.cat(both(0))), "the mixed crops differ from the single-rate corpora's"
+    b = {"wall_ms": measure(ways)}
+    b["mixed_over_two_corpora"] = round(b["wall_ms"]["mixed"]["median"] / b["wall_ms"]["two_corpora"]["median"], 3)
+    # the two halves of the mixed step alone, over the first step's crops
+    rt, win = mixed._mixed_rate(R), mixed._mixed_window(R, L)
+    out, _ = mixed.crops(files[0], offs[0], L, check=False, sample_rate=R, mono=True)
+    f = files[0]
+    origin = (torch.div(offs[0], rt["d_b"][f], rounding_mode="floor") * rt["d_a"][f] - rt["d_width"][f]).clamp(min=0)
+    Ls, K = win["Ls_max"], win["K"]
+    scratch = mixed._rs_scratch[:B * 2 * Ls].view(B, 2, Ls)
+    d_files, d_frames, row_table = f.to(torch.int32), win["d_Ls"][f], rt["d_table_of"][f].to(torch.int32)
+    valid = mixed._plan_and_decode(d_files, origin, Ls, K, win["S"], scratch, d_frames=d_frames).clone()
+    decode = lambda: mixed._plan_and_decode(d_files, origin, Ls, K, win["S"], scratch, d_frames=d_frames)
+    kernel = lambda: mixed._gpu.resample_rows_device(scratch, B, 2, Ls, origin, valid, offs[0], L, rt["desc"], rt["d_desc"], rt["d_d0"], rt["d_w"],
+                                                     row_table, True, out, stream=stream.cuda_stream)
+    moved = int(valid.sum()) * 2 * 4 + out.numel() * 4
+    k = stats(event_ms(torch, stream, kernel, args.reps))
+    b.update({"source_frames_per_crop": {str(r): int(x) for r, x in zip(rates, (win["Ls"][0], win["Ls"][half]))}, "entries_per_crop": K,
+              "out_frames": L, "table_weights": [int(d[1] * (2 * d[2] + 1)) for d in rt["desc"]], "resample_call_ms": k,
+              "bytes_read_plus_written": moved, "resample_call_gb_per_s": round(moved / k["median"] / 1e6, 1),
+              "decode_pair_ms_events_around_plan_and_decode": stats(event_ms(torch, stream, decode, 1))})
+    doc["mixed"] = b
+    mixed.close()
+    for c in two:
+        c.close()
+    text = json.dumps(doc, indent=1)
+    print(text, flush=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -9,6 +9,11 @@ Case k (59 and 34 bits per sample against the ring's top-up) is the one most lik
 to the entropy wave is run through this file, run it alone, once, in a process and under a time limit of its own:
     timeout 200 python -m pytest tests/test_entropy_tiers.py -m gpu -x -k "k_59 or k_34"
 and go on to the rest only when that came back clean.  (Its place at the head of the parameter list is a convenience, not a guard.)
+
+These batches have 16 packets, mixed FIR orders and the plain builds.  tests/test_fir_steps.py runs the FIR groups with every order
+inside one class -- one build of the steady-state FIR step per group -- and embeds them and the cases of this file in launches
+of 2056 packets, where orders above 16 take the four-taps-per-lane step; tests/test_window_tiers.py sends the store-pattern
+cases through the window builds (decode_window_into_device) with directed skips.
 """
 import numpy as np
 import pytest

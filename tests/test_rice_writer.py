@@ -94,6 +94,7 @@ def test_case_premises_and_oracle_status(oracle, name, stereo, is24):
     # the builder asserts the premise; every packet decodes with status 0 in the C oracle but the one that is there for a status
     for oc in tc.ORDER_CLASSES:
         g = tc.build(name, stereo, is24, oc)
+        assert (max(g.ns) > 4096) == ((name, stereo, is24) in tc.OVER_4096_FRAMES), "tc.OVER_4096_FRAMES is out of date"
         b = g.batch()
         o = oracle.decode_batch(oracle.make_cfgs(b["stream_cfgs"]), b["blob"], b["offsets"], b["sizes"], b["cfg_idx"], b["slot_ints"],
                                 n_threads=8)
@@ -142,6 +143,54 @@ def test_fir_case_premises_and_oracles(oracle, kind, stereo, is24):
         else:
             for cfg, pkt, status, n in _packets(g):
                 assert oracle.decode_frame(cfg, pkt + bytes(16))[0] == 0
+
+
+@pytest.mark.parametrize("stereo,is24", tc.VARIANTS)
+@pytest.mark.parametrize("order_class", tc.ORDER_CLASSES)
+@pytest.mark.parametrize("kind", tc.FIR_KINDS)
+def test_fir_order_class_premises_and_oracles(oracle, kind, order_class, stereo, is24):
+    # the builder asserts the premise and the routing facts (every order inside its class) per class
+    for block in tc.fir_blocks(kind, order_class):
+        g = tc.build_fir(kind, stereo, is24, block, order_class)
+        if block == 0:
+            check_group_on_both_oracles(oracle, g)
+        else:
+            for cfg, pkt, status, n in _packets(g):
+                assert oracle.decode_frame(cfg, pkt + bytes(16))[0] == 0
+
+
+def test_the_four_tap_threshold_is_the_kernels():
+    # Group.embed builds launches of L16_MAX_GROUPS + 1 groups so that orders above 16 take the four-taps-per-lane step
+    import os
+    import re
+
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "alac.net_amd", "csrc", "alac_kernels.hip")
+    with open(src) as f:
+        found = re.findall(r"^#define\s+ALAC_L16_MAX_GROUPS\s+(\d+)", f.read(), re.M)
+    assert found == [str(tc.L16_MAX_GROUPS)], found
+    assert tc.EMBED_PACKETS == 8 * 256 + 8 == 2056
+
+
+@pytest.mark.parametrize("stereo,is24", [(True, False), (False, True)])
+def test_embedded_batch_layout_and_oracle(oracle, stereo, is24):
+    # the group at group 0, in the middle (rolled by 3) and last (rolled by 5), filler everywhere else; the oracle takes it all
+    g = tc.build_fir("drift", stereo, is24, 0, "second_launch")
+    filler = tc.embed_filler(stereo, is24)
+    b = g.embed(filler)
+    n = tc.EMBED_PACKETS
+    assert len(b["offsets"]) == len(b["sizes"]) == len(b["cfg_idx"]) == len(b["status"]) == n
+    pkt = lambda i: bytes(b["blob"][int(b["offsets"][i]):int(b["offsets"][i]) + int(b["sizes"][i])])
+    mid = 8 * (tc.EMBED_GROUPS // 2)
+    assert [i for i, _ in b["order"]] == list(range(8)) + list(range(mid, mid + 8)) + list(range(n - 8, n))
+    assert [j for _, j in b["order"]] == list(range(8)) + [(k + 3) % 8 for k in range(8)] + [(k + 5) % 8 for k in range(8)]
+    own = dict(b["order"])
+    for i in range(n):
+        assert pkt(i) == (g.packets[own[i]] if i in own else filler.packets[i % 8])
+    assert b["slot_ints"] == 160 * (2 if stereo else 1) + 8 and max(filler.ns) <= 32
+    o = oracle.decode_batch(oracle.make_cfgs(b["stream_cfgs"]), b["blob"], b["offsets"], b["sizes"], b["cfg_idx"], b["slot_ints"],
+                            n_threads=8)
+    assert o[3].tolist() == b["status"]
+    assert o[2].tolist() == [g.ns[own[i]] if i in own else filler.ns[i % 8] for i in range(n)]
 
 
 def test_fir_replay_equals_the_oracle_predictor(oracle):

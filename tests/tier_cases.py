@@ -3,7 +3,8 @@
 Every case is a workgroup of eight packets whose Rice streams are written symbol by symbol.  A builder first asserts the case's
 premise from the writer's trace -- a statement about the bitstream, for unit sizes 8 and 16 both -- and returns the packets;
 tests/test_rice_writer.py runs every builder on the CPU (premises, both oracles), tests/test_entropy_tiers.py compares the GPU with
-the oracle on them.  Sample i of a channel belongs to unit i // U and chunk i // 32.
+the oracle on them; tests/test_fir_steps.py does so per build of the FIR step (FIR groups of one order class, Group.embed for the
+four-tap step), tests/test_window_tiers.py through the window builds.  Sample i of a channel belongs to unit i // U and chunk i // 32.
 """
 import functools
 import random
@@ -17,6 +18,12 @@ from rice_writer import ChannelWriter
 VARIANTS = [(False, False), (True, False), (False, True), (True, True)]      # (stereo, is24): rss 16, 17, 24, 25
 ORDER_CLASSES = ["first_launch", "two_taps", "second_launch"]              # orders 1..8, 9..16, {0, 17..30, 31}
 UNITS = (8, 16)
+# The second launch gives orders above 16 two FIR waves (16 lanes per stream, two taps per lane) in launches of up to this many
+# groups of eight packets, and the one wave with four taps per lane above it: ALAC_L16_MAX_GROUPS of alac_kernels.hip, which
+# tests/test_rice_writer.py reads back, so that a retuned threshold cannot move the embedded batches off the four-tap step
+L16_MAX_GROUPS = 256
+EMBED_GROUPS = L16_MAX_GROUPS + 1                  # Group.embed: 8 * 256 + 8 == 2056 packets in one launch
+EMBED_PACKETS = 8 * EMBED_GROUPS
 PLAIN = 3000            # a history level without run symbols or escape codes (k = 3)
 
 
@@ -62,6 +69,45 @@ class Group:
                     sizes=np.array([len(self.packets[j]) for j in order], dtype=np.uint32),
                     cfg_idx=np.array([self.cfg_idx[j] for j in order], dtype=np.uint16), stream_cfgs=self.cfgs,
                     slot_ints=max(self.ns) * nc + 8, status=[self.status[j] for j in order], order=order)
+
+    def embed(self, filler, groups=None):
+        """the group three times inside a launch of `groups` groups of eight packets (default: one more than the second launch
+        gives two FIR waves, so that orders above 16 take the four-taps-per-lane step): at group 0, in the middle (rolled by
+        3) and as the last group (rolled by 5); every other group is `filler`'s eight packets -- a warm-up FIR group of at
+        most 32 frames per packet.  The same keys as batch(); `order`: the group's own packets as (batch index, packet)."""
+        groups = groups or EMBED_GROUPS
+        assert groups >= 3 and len(self.packets) == len(filler.packets) == 8 and max(filler.ns) <= 32 and not any(filler.status)
+        assert filler.cfgs[0][1] == self.cfgs[0][1] and filler.cfgs[0][5] == self.cfgs[0][5], "filler of another stream layout"
+        cfgs = list(self.cfgs)
+        if filler.cfgs[0] not in cfgs:
+            cfgs.append(filler.cfgs[0])
+        fidx = cfgs.index(filler.cfgs[0])
+        copies = {0: 0, groups // 2: 3, groups - 1: 5}
+        fill_blob = b"".join(filler.packets)
+        blob, offs, sizes, ci, status, order = bytearray(), [], [], [], [], []
+        for grp in range(groups):
+            if grp not in copies:
+                pos = len(blob)
+                for pkt in filler.packets:
+                    offs.append(pos)
+                    sizes.append(len(pkt))
+                    pos += len(pkt)
+                blob += fill_blob
+                ci += [fidx] * 8
+                status += [0] * 8
+                continue
+            for j in ((k + copies[grp]) % 8 for k in range(8)):
+                order.append((len(offs), j))
+                offs.append(len(blob))
+                sizes.append(len(self.packets[j]))
+                blob += self.packets[j]
+                ci.append(self.cfg_idx[j])
+                status.append(self.status[j])
+        blob += bytes(64)
+        nc = self.cfgs[0][5]
+        return dict(blob=np.frombuffer(bytes(blob), dtype=np.uint8), offsets=np.array(offs, dtype=np.uint64),
+                    sizes=np.array(sizes, dtype=np.uint32), cfg_idx=np.array(ci, dtype=np.uint16), stream_cfgs=cfgs,
+                    slot_ints=max(self.ns + filler.ns) * nc + 8, status=status, order=order)
 
 
 _SYMS = {}          # the steered symbol lists per (case, stereo, is24): what build() below cannot share between order classes
@@ -556,6 +602,9 @@ def case_l(stereo, is24, oc):
     return g
 
 
+# the (case, stereo, is24) whose packets have more than 4096 frames: left out where every packet must fit a 4096-frame stream
+# (tests/test_fir_steps.py: the embedded batches); tests/test_rice_writer.py checks the set against the built groups
+OVER_4096_FRAMES = {("k_34", True, True)}
 CASES = {"a": case_a, "b": case_b, "c": case_c, "d": case_d, "e": case_e, "f": case_f, "f_ends": case_f_ends, "g": case_g,
          "h": case_h, "i": case_i, "j": case_j, "k_59": case_k_59, "k_34": case_k_34, "l": case_l}
 
@@ -599,20 +648,46 @@ def fir_replay(res, rss, coefs, q):
 FIR_KINDS = ["uniform", "patterns", "drift", "flat_and_tie", "warmup"]
 
 
-def fir_group(kind, stereo, is24, block=0):
-    """eight packets whose entropy content is plain (canonical codes of the chosen residuals); `block` moves through orders 1..31"""
+FIR_CLASS_ORDERS = {"first_launch": (1, 8), "two_taps": (1, 16), "second_launch": (17, 30)}
+FIR_SPECIAL_KINDS = ("uniform", "patterns", "warmup")      # kinds whose premise asks fir_replay (orders 1..30) nothing
+
+
+def fir_class_orders(r, order_class):
+    """eight orders of one class for a group: (j + 3 c) % 8 of them is stream (packet j, channel c).  Which FIR step a group of
+    eight packets runs on follows from its orders alone (alac_kernels.hip: ab_kernel_body): all in 1..8 one tap per lane in the
+    first launch, some in 9..16 and none outside 1..16 two taps per lane (second launch; the dense arrangement: first), any
+    other order the second launch's four-tap (launches above L16_MAX_GROUPS groups) or 16-lane two-tap step."""
+    lo, hi = FIR_CLASS_ORDERS[order_class]
+    must = {"first_launch": [1, 8], "two_taps": [16, r.randrange(9, 16), r.randrange(1, 9)], "second_launch": [17, 30]}[order_class]
+    orders = must + [r.randrange(lo, hi + 1) for _ in range(8 - len(must))]
+    r.shuffle(orders)
+    return orders
+
+
+def fir_group(kind, stereo, is24, block=0, order_class=None):
+    """eight packets whose entropy content is plain (canonical codes of the chosen residuals); `block` moves through orders 1..31.
+    With an order_class every stream of the group takes its order from that class (fir_class_orders; `block` then only reseeds),
+    so that the whole group runs on one build of the FIR step; in the second_launch class of the kinds in FIR_SPECIAL_KINDS
+    channel A of packet 2 has order 31 and the last channel of packet 5 order 0 (the modes of the special step)."""
     ss = 24 if is24 else 16
     nc = 2 if stereo else 1
     rss = ss + stereo
     cfg = (4096, ss, 40, 10, 14, nc)
     top = (1 << (rss - 1)) - 1
-    r = random.Random(zlib.crc32(repr((kind, stereo, is24, block)).encode()))
-    packets, traces, ns, facts = [], [], [], dict(peak=0, ties=0, flat=0)
+    key = (kind, stereo, is24, block) if order_class is None else (kind, stereo, is24, block, order_class)
+    r = random.Random(zlib.crc32(repr(key).encode()))
+    class_orders = fir_class_orders(r, order_class) if order_class else None
+    packets, traces, ns, facts = [], [], [], dict(peak=0, ties=0, flat=0, lo=0, hi=0, orders=[])
     for j in range(8):
         n = 160
         hdrs, syms = [], []
         for c in range(nc):
             order = 1 + (8 * block + j + 15 * c) % 31
+            special = False
+            if order_class:
+                order = class_orders[(j + 3 * c) % 8]
+                if order_class == "second_launch" and kind in FIR_SPECIAL_KINDS and (j, c) in ((2, 0), (5, nc - 1)):
+                    order, special = (31 if j == 2 else 0), True
             q = [0, 1, 9, 15][(j + c + block) % 4]
             coefs = [r.choice([r.randrange(-32768, 32768), r.randrange(-3000, 3000)]) for _ in range(order)]
             if kind == "uniform":
@@ -622,19 +697,24 @@ def fir_group(kind, stereo, is24, block=0):
                 pat = ["pos", "neg", "alt", "pos", "neg", "alt", "pos", "rnd"][j]
                 res = [{"pos": m, "neg": -m, "alt": m if i % 2 else -m, "rnd": r.choice([-1, 0, 1])}[pat] for i in range(n)]
             elif kind == "drift":
-                order = [1, 2, 4, 8, 12, 16, 24, 30][(j + c) % 8]
+                if not order_class:
+                    order = [1, 2, 4, 8, 12, 16, 24, 30][(j + c) % 8]
                 q = [15, 9, 1, 0][(j + block) % 4]
                 coefs = [32767 if (j + t) % 2 == 0 else -32768 for t in range(order)]
                 res = [(1 if j % 2 else -1) * (1 + (i % 3 == 0)) for i in range(n)]
             elif kind == "flat_and_tie":
-                order = [1, 2, 3, 4, 6, 8, 12, 20][(j + c) % 8]
+                if not order_class:
+                    order = [1, 2, 3, 4, 6, 8, 12, 20][(j + c) % 8]
                 q = [0, 0, 1, 2][(j + block) % 4]
                 coefs = [r.randrange(-3, 4) << q for _ in range(order)]
                 # a constant output (all-equal history), a first error against it, then small errors over small differences
                 res = [5] + [0] * (order + 3) + [r.choice([-3, -2, -1, 1, 2, 3, 4, 6]) for _ in range(n - order - 4)]
             else:   # warmup: n from 1 to order + 2
-                order = [1, 4, 8, 12, 20, 30][block % 6]
-                n = 1 + (8 * (block // 6) + j) % (order + 2)
+                if not order_class:
+                    order = [1, 4, 8, 12, 20, 30][block % 6]
+                    n = 1 + (8 * (block // 6) + j) % (order + 2)
+                elif c == 0:      # (the packet's length goes by channel A's order; orders 0 and 31 have no warm-up: a few samples)
+                    n = 1 + (8 * block + 5 * j) % (order + 2 if order < 31 else 9)
                 q = 9
                 coefs = [r.randrange(-3000, 3000) for _ in range(order)]
                 res = [r.randrange(-top - 1, top + 1) for _ in range(n)]
@@ -643,23 +723,49 @@ def fir_group(kind, stereo, is24, block=0):
                 facts["peak"] = max(facts["peak"], peak)
                 facts["ties"] += ties
                 facts["flat"] += flat
+            facts["lo"], facts["hi"] = min(facts["lo"], min(res)), max(facts["hi"], max(res))
+            facts["orders"].append((order, special))
             hdrs.append(rw.channel_header(order=order, coefs=coefs, quant=q, ricemod=4))
             syms.append(rw.symbols_for_residuals(cfg, rss, 4, res))
         pkt, tr, _ = rw.write_packet(cfg, n, hdrs, syms, mix_shift=2 if stereo else 0, mix_weight=(j % 3) if stereo else 0)
         packets.append(pkt)
         traces.append(tr)
         ns.append(n)
-    g = Group(f"fir_{kind}", [cfg], [0] * 8, packets, traces, [0] * 8, ns)
+    g = Group(f"fir_{kind}" + (f"_{order_class}" if order_class else ""), [cfg], [0] * 8, packets, traces, [0] * 8, ns)
     g.facts = facts
+    # the width the kernels route by (rss > 23: the 32-bit multiply) is the stream's sample size plus one for a channel-pair
+    # element: read back from what was written -- the element tag in the packet's first three bits, the stream configuration
+    assert all(p[0] >> 5 == (1 if stereo else 0) for p in packets) and cfg[1] + (packets[0][0] >> 5) == rss
+    assert rss == {(False, False): 16, (True, False): 17, (False, True): 24, (True, True): 25}[(bool(stereo), bool(is24))]
     if kind == "drift":
         assert facts["peak"] > 32768, facts        # some coefficient left the int16 range it was read in
     if kind == "flat_and_tie":
         assert facts["ties"] > 0 and facts["flat"] > 0, facts
+    if kind == "uniform":                          # the residuals span the rss range: its outermost 16th on either side is met
+        assert facts["lo"] < -top + (top >> 4) and facts["hi"] > top - (top >> 4), facts
+    if order_class:                                # the routing facts: every order lies in its class, and the edges of the class are met
+        lo, hi = FIR_CLASS_ORDERS[order_class]
+        plain_orders = [o for o, sp in facts["orders"] if not sp]
+        assert all(lo <= o <= hi for o in plain_orders), facts
+        assert [o for o, sp in facts["orders"] if sp] == ([31, 0] if order_class == "second_launch" and kind in FIR_SPECIAL_KINDS else [])
+        if order_class == "first_launch":
+            assert {1, 8} <= set(plain_orders)
+        elif order_class == "two_taps":
+            assert 16 in plain_orders and any(8 < o < 16 for o in plain_orders) and any(o <= 8 for o in plain_orders)
+        if kind != "warmup":                       # every stream as long as the others: chunks 1.. run the steady-state step
+            assert set(ns) == {160}
     return g
 
 
-def fir_blocks(kind):
+def fir_blocks(kind, order_class=None):
+    if order_class:
+        return range(3) if kind == "warmup" else range(2)
     return range(12) if kind == "warmup" else range(4)
+
+
+def embed_filler(stereo, is24):
+    """Group.embed's filler: a warm-up group (order 30, one to eight frames per packet) of the usual stream configuration"""
+    return build_fir("warmup", stereo, is24, 5)
 
 
 @functools.lru_cache(maxsize=None)
@@ -668,5 +774,5 @@ def build(name, stereo, is24, oc):
 
 
 @functools.lru_cache(maxsize=None)
-def build_fir(kind, stereo, is24, block):
-    return fir_group(kind, stereo, is24, block)
+def build_fir(kind, stereo, is24, block, order_class=None):
+    return fir_group(kind, stereo, is24, block, order_class)

@@ -71,6 +71,8 @@ SYMBOLS = {
                                           C.c_uint32, _VP, _VP, C.c_int, _VP, _VP]),
     "alacgpu_resample_rows_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, _VP, _VP, _VP, C.c_uint64, _VP, _VP,
                                                C.c_uint32, _VP, _VP, _VP, C.c_int, _VP, _VP]),
+    "alacgpu_logmel_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _VP,
+                                        _VP, _VP, C.c_int, C.c_float, _VP, C.c_uint64, _VP]),
     "alacgpu_encode_max_packet_bytes": (C.c_size_t, [C.c_uint32, C.c_int, C.c_int]),
     "alacgpu_encode_device": (C.c_int, [_VP, _VP, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP, C.c_uint32,
                                         _VP, C.c_uint64, _VP, _VP, _VP]),
@@ -356,6 +358,17 @@ class AlacGpuContext(_Closing):
                                                 _dp(d_src_valid), _dp(d_out_first), out_frames, _ptr(tables), _dp(d_tables),
                                                 len(tables), _dp(d_d0), _dp(d_weights), _dp(d_row_table), int(bool(mono)),
                                                 _dp(d_out), _VP(stream))
+        _check(rc, self._ctx)
+
+    def logmel_device(self, d_src, rows, channels, src_stride, frames, n_fft, hop, n_mels, d_window, d_basis, d_fb, log_mode, floor,
+                      d_out, out_frames, stream=0):
+        """alacgpu_logmel_device: the log-mel features of d_src (float32 device tensor, planar [rows, channels, src_stride], the
+        first `frames` of a plane are signal) into d_out (float32 [rows, channels, n_mels, out_frames], out_frames =
+        1 + frames // hop, every element written) with the tables d_window [n_fft], d_basis [n_fft, 2 * (n_fft // 2 + 1)] and
+        d_fb [n_mels, n_fft // 2 + 1] (features.LogMel builds them); log_mode 0: mel power, 1: ln, 2: log10 of
+        max(., floor).  Asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_logmel_device(self._ctx, _dp(d_src), rows, channels, src_stride, frames, n_fft, hop, n_mels, _dp(d_window),
+                                         _dp(d_basis), _dp(d_fb), log_mode, floor, _dp(d_out), out_frames, _VP(stream))
         _check(rc, self._ctx)
 
     def set_output_format(self, fmt):
@@ -922,3 +935,5 @@ from .corpus import (Corpus, compact_plan_host, corpus_plan_host, corpus_tables,
                      stage_bytes_per_crop, stage_plan_host, tier_split)
 # ---- crops and tensors at another sample rate (alacgpu_resample_device) ---------------------------------------------------------------
 from .resample import resample, resample_host, resample_table, source_window  # noqa: E402
+# ---- log-mel features of crops and tensors (alacgpu_logmel_device) -----------------------------------------------------------------
+from .features import LogMel, log_mel, logmel_host, mel_filterbank  # noqa: E402

@@ -346,6 +346,7 @@ class Corpus(_Closing):
         self._stage = self._stage_plan = None
         self._stage_room, self._stage_entries, self._stage_bytes = 0, 0, 0
         self._rs_scratch, self._rs_frames = None, {}      # crops at another rate: the decoded source crops; Ty per ratio
+        self._ft_scratch = None                           # crops(features=): the crops the feature kernel reads
         self._mx_rates, self._mx_windows = {}, {}         # differing rates: the per-file tables per target rate; Ls, K, S per (R, L)
         self._gpu = gpu if gpu is not None else AlacGpuContext(tb["cfgs"], device)
 
@@ -480,7 +481,7 @@ class Corpus(_Closing):
         if getattr(self, "_gpu", None) is not None:
             self._gpu.close()
             self._gpu = None
-            self._blob = self._plan = self._stage = self._stage_plan = self._rs_scratch = None
+            self._blob = self._plan = self._stage = self._stage_plan = self._rs_scratch = self._ft_scratch = None
         self._free_pinned()
 
     @property
@@ -572,7 +573,7 @@ class Corpus(_Closing):
             raise ValueError(f"crop {b} (source {int(f[b])}): frame offset {int(o[b])} outside 0 .. {int(totals[f[b]])}")
         return torch.from_numpy(f.astype(np.int32)).to(self._dev), torch.from_numpy(o).to(self._dev), True
 
-    def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True, sample_rate=None, mono=False):
+    def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True, features=None, sample_rate=None, mono=False):
         """Decode crop b = frames frame_offsets[b] .. + num_frames of file files[b] for every b in ONE launch pair: returns
         (pcm [B, C, num_frames] on the device, zero behind lengths[b]; lengths [B], a DEVICE int64 tensor: min(num_frames,
         T_f - offset)).  float32 (default) or int32, as `load`.  files / frame_offsets: sequences, numpy arrays or torch
@@ -587,9 +588,15 @@ class Corpus(_Closing):
         sample_rate / mono: crops at another rate and as one channel (`_resampled_crops`): frame_offsets and num_frames then
         count frames at sample_rate, pcm is float32 [B, 1 if mono else C, num_frames].  The defaults -- and the corpus's own
         rate, and mono of one channel -- are the path above.  A corpus whose files differ in rate (mixed_rates=True) has no
-        rate of its own: sample_rate is required (ValueError without), and every crop comes through `_mixed_crops`."""
+        rate of its own: sample_rate is required (ValueError without), and every crop comes through `_mixed_crops`.
+
+        features: a features.LogMel -- the crops' log-mel features instead of their PCM (`_feature_crops`): returns (feats
+        float32 [B, 1 if mono else C, n_mels, 1 + num_frames // hop], feat_lengths [B] int64 on the device: lengths // hop + 1,
+        -1 where lengths is -1); `out` is then the features tensor.  Pass it by keyword, and sample_rate and mono as well."""
         import torch
 
+        if features is not None:
+            return self._feature_crops(files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, features)
         if self.sample_rate is None:
             if sample_rate is None:
                 raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
@@ -630,6 +637,53 @@ class Corpus(_Closing):
         if check:
             self._check_last(lengths, d_files, d_offs, L, K)
         return out, lengths
+
+    def _feature_crops(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, spec):
+        """crops(..., features=spec): the crops are made exactly as without -- on the native, the `_resampled_crops` or the
+        `_mixed_crops` path, `mono` honoured, `check` as there -- into a float32 scratch [B, Co, num_frames] the corpus keeps,
+        then ONE alacgpu_logmel_device call on the same stream turns every row, the zeros behind its length included, into
+        features (features.py states the transform).  ValueError before any device work: a spec.sample_rate that is not the
+        rate of the crops (sample_rate if given, else the corpus's own), a dtype other than float32, num_frames <=
+        n_fft // 2, an `out` that is not a contiguous float32 [B, Co, n_mels, 1 + num_frames // hop] on the device."""
+        import torch
+
+        from .features import LogMel, feature_lengths
+
+        if not isinstance(spec, LogMel):
+            raise ValueError(f"features must be a features.LogMel, not {spec!r} (sample_rate= and mono= go by keyword)")
+        if self.sample_rate is None and sample_rate is None:
+            raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
+        rate = self.sample_rate if sample_rate is None else sample_rate
+        if spec.sample_rate != rate:
+            raise ValueError(f"features for {spec.sample_rate} Hz, crops at {rate} Hz")
+        if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
+            raise ValueError("features are computed from float32 crops")
+        L = _frame_count("num_frames", num_frames)
+        if L <= spec.n_fft // 2:
+            raise ValueError(f"num_frames {L}: the transform needs more than n_fft // 2 = {spec.n_fft // 2}")
+        if self._gpu is None:
+            raise AlacGpuError("the corpus is closed")
+        B = int(files.shape[0]) if isinstance(files, torch.Tensor) and files.dim() == 1 else len(np.asarray(files))
+        Co = 1 if mono else self.channels
+        Tf = spec.frames(L)
+        shape = (B, Co, spec.n_mels, Tf)
+        if out is not None:
+            if (not isinstance(out, torch.Tensor) or out.shape != shape or out.dtype != torch.float32 or out.device != self._dev
+                    or not out.is_contiguous()):
+                raise ValueError(f"out must be a contiguous torch.float32 tensor of shape {shape} on {self._dev}")
+        else:
+            out = torch.empty(shape, dtype=torch.float32, device=self._dev)
+        n = B * Co * L
+        if self._ft_scratch is None or self._ft_scratch.numel() < n:
+            self._ft_scratch = None     # (the old one goes first)
+            self._ft_scratch = torch.empty(n, dtype=torch.float32, device=self._dev)
+        pcm = self._ft_scratch[:n].view(B, Co, L)
+        _, lengths = self.crops(files, frame_offsets, L, out=pcm, check=check, sample_rate=sample_rate, mono=mono)
+        if B:
+            window, basis, fb = spec.device_tables(self._dev)
+            self._gpu.logmel_device(pcm, B, Co, L, L, spec.n_fft, spec.hop_length, spec.n_mels, window, basis, fb, spec.log_mode,
+                                    spec.floor, out, Tf, stream=torch.cuda.current_stream(self._dev).cuda_stream)
+        return out, feature_lengths(lengths, spec.hop_length)
 
     def _plan_and_decode(self, d_files, d_offs, L, K, S, out, d_frames=None):
         """The launches of a step: the plan of the crops (d_files, d_offs) of L frames with K entries each, the staging of its
@@ -843,11 +897,13 @@ class Corpus(_Closing):
             self._check_last(valid, d_files, src_offs, Ls, K, d_shown=d_offs)
         return out, lengths
 
-    def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True, sample_rate=None, mono=False):
+    def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True, features=None, sample_rate=None,
+                     mono=False):
         """`batch` crops of num_frames frames drawn on the device: files uniform over the corpus, the first frame uniform in
         0 .. max(T_f - num_frames, 0).  generator: a torch.Generator (of the corpus's device, or of the CPU: then the draws are
         made there and uploaded).  Returns (pcm, lengths, files, frame_offsets), the draws as device int64 tensors.
-        sample_rate / mono as for `crops`: the frames, T_f included, then count at sample_rate."""
+        sample_rate / mono as for `crops`: the frames, T_f included, then count at sample_rate.  features as for `crops`:
+        (feats, feat_lengths, files, frame_offsets)."""
         import torch
 
         B, L = _frame_count("batch", batch), _frame_count("num_frames", num_frames)
@@ -862,7 +918,8 @@ class Corpus(_Closing):
             totals = self._d_num_frames if sample_rate is None else self._rate(sample_rate)[1]
         span = (totals[files] - L).clamp(min=0)
         offs = torch.minimum(torch.floor(u * (span + 1).to(torch.float64)).to(torch.int64), span)
-        pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono)
+        pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,
+                                  features=features)
         return pcm, lengths, files, offs
 
     def last_staged_bytes(self):

@@ -2,6 +2,7 @@
 // No CPU fallback anywhere in this file: every decode goes through alac_decode_ab_kernel / alac_decode_ab32_kernel.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 
 #include <cstdio>
@@ -16,6 +17,7 @@
 
 #include "alac_corpus.h"
 #include "alac_resample.h"
+#include "alac_features.h"
 #include "alac_encode.h"
 #include "alac_kernels.h"
 #include "alacgpu.h"
@@ -866,6 +868,52 @@ int alacgpu_resample_rows_device(alacgpu_ctx* ctx, const void* d_src, uint32_t r
     void* kargs[] = {&p};
     HIP_TRY(ctx, hipLaunchKernel((const void*)alac_resample_rows_kernel, dim3(blocks), dim3(ALAC_RESAMPLE_THREADS), kargs, lds,
                                  (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
+}
+
+int alacgpu_logmel_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,
+                          uint64_t frames, uint32_t n_fft, uint32_t hop, uint32_t n_mels, const void* d_window,
+                          const void* d_basis, const void* d_fb, int log_mode, float floor, void* d_out, uint64_t out_frames,
+                          void* hip_stream) {
+    if (!ctx || !d_src || !d_window || !d_basis || !d_fb || !d_out) return ALACGPU_ERR_BAD_ARG;
+    if (((uintptr_t)d_src & 3u) != 0 || ((uintptr_t)d_window & 3u) != 0 || ((uintptr_t)d_basis & 3u) != 0 ||
+        ((uintptr_t)d_fb & 3u) != 0 || ((uintptr_t)d_out & 3u) != 0)
+        return ALACGPU_ERR_BAD_ARG;
+    if (n_fft < ALAC_FEATURES_MIN_NFFT || n_fft > ALAC_FEATURES_MAX_NFFT || hop < 1 || hop > n_fft || n_mels < 1 ||
+        n_mels > ALAC_FEATURES_MAX_MELS || channels == 0)
+        return ALACGPU_ERR_BAD_ARG;
+    if (!(floor > 0.0f) || !std::isfinite(floor)) return ALACGPU_ERR_BAD_ARG;
+    if (log_mode != ALAC_FEATURES_LOG_NONE && log_mode != ALAC_FEATURES_LOG_LN && log_mode != ALAC_FEATURES_LOG_10) return ALACGPU_ERR_BAD_ARG;
+    if (frames <= n_fft / 2u || frames > src_stride || frames > (1ull << 62) || out_frames != 1u + frames / hop) return ALACGPU_ERR_BAD_ARG;
+    const uint32_t tile = alac_features_tile(n_fft, hop);
+    const uint64_t tiles = (out_frames + tile - 1u) / tile;
+    if (tiles > 0x7FFFFFFFull || tiles * channels > 0x7FFFFFFFull || tiles * channels * rows > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0) return ALACGPU_OK;
+    const size_t lds = alac_features_lds_layout(n_fft, hop, n_mels).bytes();
+    if (lds > ALAC_FEATURES_LDS_MAX) return ALACGPU_ERR_BAD_ARG;    // (the limits above keep every layout below it)
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (lds > ALAC_FEATURES_LDS_DEFAULT)
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)alac_logmel_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    alac_features_params p;
+    p.src = (const float*)d_src;
+    p.src_stride = src_stride;
+    p.frames = frames;
+    p.out = (float*)d_out;
+    p.out_frames = out_frames;
+    p.window = (const float*)d_window;
+    p.basis = (const float*)d_basis;
+    p.fb = (const float*)d_fb;
+    p.n_fft = n_fft;
+    p.hop = hop;
+    p.n_mels = n_mels;
+    p.tile = tile;
+    p.tiles = (uint32_t)tiles;
+    p.log_mode = (uint32_t)log_mode;
+    p.floor = floor;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_logmel_kernel, dim3((uint32_t)(tiles * channels * rows)), dim3(ALAC_FEATURES_THREADS),
+                                 kargs, lds, (hipStream_t)hip_stream));
     HIP_TRY(ctx, hipGetLastError());
     return ALACGPU_OK;
 }

@@ -92,6 +92,13 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_resample_rows_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
             ulong srcStride, IntPtr dSrcOrigin, IntPtr dSrcValid, IntPtr dOutFirst, ulong outFrames, [In] ResampleTable[] tables,
             IntPtr dTables, uint nTables, IntPtr dD0, IntPtr dWeights, IntPtr dRowTable, int mono, IntPtr dOut, IntPtr hipStream);
+        /// <summary>Log-mel features of float PCM in device memory (planar [rows, channels, srcStride], the first `frames` of a plane
+        /// are signal): frames centred on t * hop with reflection, dWindow [nFft], the DFT against dBasis [nFft, 2 * (nFft / 2 + 1)],
+        /// power, dFb [nMels, nFft / 2 + 1], and logMode 0 (none), 1 (ln) or 2 (log10) of max(., floor) into dOut
+        /// [rows, channels, nMels, outFrames], outFrames = 1 + frames / hop.  Asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_logmel_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
+            ulong srcStride, ulong frames, uint nFft, uint hop, uint nMels, IntPtr dWindow, IntPtr dBasis, IntPtr dFb, int logMode,
+            float floor, IntPtr dOut, ulong outFrames, IntPtr hipStream);
         /// <summary>Encode PCM in device memory (int32 or float32, interleaved or planar) to ALAC packets in device memory, one
         /// run of frames per packet, packet p at dPackets + p * slotBytes; asynchronous on hipStream.</summary>
         [DllImport(Lib)] public static extern UIntPtr alacgpu_encode_max_packet_bytes(uint frames, int sampleSize, int channels);

@@ -425,6 +425,37 @@ int alacgpu_resample_rows_device(alacgpu_ctx* ctx, const void* d_src, uint32_t r
                                  const void* d_d0, const void* d_weights, const void* d_row_table, int mono, void* d_out,
                                  void* hip_stream);
 
+/*
+ * Log-mel features of decoded PCM (no counterpart in the reference): framing, window, DFT, power, mel projection and log in
+ * one launch.  For every plane (row, channel) x[0 .. frames) and every frame t of 0 .. out_frames, out_frames =
+ * 1 + frames / hop, centred on sample t * hop:
+ *   x_t[n]   = x[t * hop - n_fft / 2 + n], n < n_fft, reflected once at either end (index -i reads x[i], index
+ *              frames - 1 + i reads x[frames - 1 - i]; what one reflection does not bring inside 0 .. frames -- only an odd
+ *              n_fft at frames = n_fft / 2 + 1 -- counts as zero)
+ *   X[j]     = sum over n of (d_window[n] * x_t[n]) * d_basis[n * 2 * n_bins + j],   j < 2 * n_bins, n_bins = n_fft / 2 + 1
+ *   P[k]     = X[k]^2 + X[n_bins + k]^2
+ *   M[m]     = sum over k of d_fb[m * n_bins + k] * P[k]
+ *   out[m,t] = M[m] (log_mode 0), ln(max(M[m], floor)) (1) or log10(max(M[m], floor)) (2)
+ * in float32: one rounding of the window product, then fused multiply-adds in ascending n and k (the DFT on the exact-f32
+ * matrix instruction).  The three tables are the caller's (alac.net_amd/features.py builds the ones this library documents: a
+ * periodic Hann window, the real DFT's cosines and negated sines, a Slaney or HTK mel filterbank), so any window, basis or
+ * filterbank of those shapes is honoured.  Device pointers only, asynchronous on hip_stream, nothing is read back; nothing of
+ * the ctx is used but its device.
+ *   d_src     float32, planar [rows, channels, src_stride]; only the first `frames` elements of a plane are signal and only
+ *             they are read
+ *   d_window  float32 [n_fft];  d_basis  float32 [n_fft, 2 * n_bins];  d_fb  float32 [n_mels, n_bins]
+ *   d_out     float32 [rows, channels, n_mels, out_frames]; every element is written, each by one thread
+ * A workgroup takes 32 consecutive frames of one plane (fewer where 31 * hop + n_fft is above 19456 samples) and holds their
+ * span of signal in LDS, 61 KiB in all at n_fft 400, hop 160 and 80 mels and at most 153 KiB.  rows == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx or array, a misaligned array (4), n_fft outside 16 .. 2048, hop
+ * outside 1 .. n_fft, n_mels outside 1 .. 256, a floor that is not positive and finite, a log_mode other than 0, 1, 2,
+ * channels 0, frames <= n_fft / 2 or above src_stride, out_frames != 1 + frames / hop, 2^31 workgroups or more.
+ */
+int alacgpu_logmel_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,
+                          uint64_t frames, uint32_t n_fft, uint32_t hop, uint32_t n_mels, const void* d_window,
+                          const void* d_basis, const void* d_fb, int log_mode, float floor, void* d_out,
+                          uint64_t out_frames, void* hip_stream);
+
 /* Single-packet drop-in for `int DecodeFrame(byte[] inbuffer, int[] outbuffer)` (AlacFile.cs:428):
  * writes the reference's own int[] layout (24-bit: one int per byte) and returns its byte count in
  * *out_bytes.  status as above (the C# shim rethrows the reference's exceptions from it). */

@@ -13,13 +13,13 @@ writes their offsets), one small read.  `Corpus.save` writes any corpus back as 
 memory.  A step is then three calls: between the plan and the decode, alacgpu_stage_packets_device gathers the plan's packets
 from both tiers into a small staging blob in HBM, and the decode reads that.
 
-`crops(..., sample_rate=R, mono=)` gives the crops at another rate and as one channel: the source frames a crop needs are
-decoded as above into a scratch the corpus keeps, and one alacgpu_resample_device call (resample.py states the filter)
-resamples every crop out of it.
+`crops(..., sample_rate=R, mono=)` gives the crops at another rate and as one channel (`Corpus._rate_crops`): the source
+frames a crop needs are decoded as above into a scratch the corpus keeps, and one alacgpu_resample_device call (resample.py
+states the filter) resamples every crop out of it.
 
 `Corpus(sources, mixed_rates=True)` takes files of different sample rates.  Crops of such a corpus exist at a target rate only;
-a step is the same launches, with a source window per crop in the plan (alacgpu_plan_crops_frames_device) and a filter table
-per row in the resampler (alacgpu_resample_rows_device).
+a step is the same method and the same launches, with a source window per crop in the plan
+(alacgpu_plan_crops_frames_device) and a filter table per row in the resampler (alacgpu_resample_rows_device).
 
 `corpus_tables` (the resident tables as numpy arrays), `entries_per_crop` (the K bound), `stage_bytes_per_crop` (the staging
 bound), `tier_split`, `corpus_plan_host`, `compact_plan_host` and `stage_plan_host` (the three kernels' specifications in
@@ -259,7 +259,7 @@ class Corpus(_Closing):
 
     mixed_rates=True: the files may differ in sample rate (not in channel count).  sample_rates (int64 host array [F]) has
     every file's; sample_rate is the one they share, or None when they differ.  num_frames stays in source frames.  Crops of
-    a corpus whose rates differ exist at a target rate only: crops / random_crops want sample_rate=R (`_mixed_crops`), and
+    a corpus whose rates differ exist at a target rate only: crops / random_crops want sample_rate=R (`_rate_crops`), and
     every file is resampled by its own ratio in the same launches.  Files that happen to share one rate make the corpus
     Corpus(sources) is, call for call."""
 
@@ -337,7 +337,6 @@ class Corpus(_Closing):
         self._pkt_end, self._file_first = up(tb["pkt_end"], np.int64), up(tb["file_first"], np.int32)
         self._file_cfg = up(tb["file_cfg"], np.int16)
         self._d_num_frames = torch.from_numpy(self.num_frames).to(dev)
-        self._K, self._S = {}, {}
         self._plan, self._capacity, self._last = None, 0, 0
         # the tiers: the first bytes of the packets' address space are self._blob's, the others the page-locked blob's
         self._pinned = getattr(self, "_pinned", None)
@@ -345,9 +344,9 @@ class Corpus(_Closing):
         self._lo_bytes = self._blob_bytes - self._hi_bytes
         self._stage = self._stage_plan = None
         self._stage_room, self._stage_entries, self._stage_bytes = 0, 0, 0
-        self._rs_scratch, self._rs_frames = None, {}      # crops at another rate: the decoded source crops; Ty per ratio
+        self._rs_scratch = None                           # crops at another rate: the decoded source crops
         self._ft_scratch = None                           # crops(features=): the crops the feature kernel reads
-        self._mx_rates, self._mx_windows = {}, {}         # differing rates: the per-file tables per target rate; Ls, K, S per (R, L)
+        self._rates, self._windows = {}, {}               # `_rate` per target rate; `_window` per (target rate or None, L)
         self._gpu = gpu if gpu is not None else AlacGpuContext(tb["cfgs"], device)
 
     @classmethod
@@ -449,8 +448,7 @@ class Corpus(_Closing):
         from_pcm made the files are byte for byte what save_batch writes for the same arguments.  A packet's duration is the
         difference of its pkt_end to the one in front; frame length, sample size and the Rice parameters are the file's cfg
         row's.  The packets cross to the host file by file.  Returns the file sizes."""
-        if self._gpu is None:
-            raise AlacGpuError("the corpus is closed")
+        self._open()
         dests = list(dests)
         if len(dests) != self.num_files:
             raise ValueError(f"{self.num_files} files in the corpus and {len(dests)} destinations")
@@ -477,6 +475,10 @@ class Corpus(_Closing):
                                    int(rate), rice=(int(c["rice_history_mult"]), int(c["rice_initial_history"]), int(c["rice_kmodifier"]))))
         return out
 
+    def _open(self):
+        if self._gpu is None:
+            raise AlacGpuError("the corpus is closed")
+
     def close(self):
         if getattr(self, "_gpu", None) is not None:
             self._gpu.close()
@@ -493,12 +495,10 @@ class Corpus(_Closing):
         """S for crops of num_frames frames: the bytes the staging blob reserves per crop (computed once per length).
         sample_rate, for a corpus whose rates differ: S of the crops of num_frames frames at that rate -- a file counts with
         the source window its own ratio needs."""
-        if sample_rate is not None and self.sample_rate is None:
-            return self._mixed_window(sample_rate, num_frames)["S"]
-        L = int(num_frames)
-        if L not in self._S:
-            self._S[L] = stage_bytes_per_crop(self._host_table("pkt_size"), self._host["pkt_end"], self._host["file_first"], L)
-        return self._S[L]
+        win = self._window_of(num_frames, sample_rate)
+        if win["S"] is None:        # (no host tier: no step has needed it)
+            win["S"] = stage_bytes_per_crop(self._host_table("pkt_size"), self._host["pkt_end"], self._host["file_first"], win["Ls"])
+        return win["S"]
 
     def _stage_arrays(self, n, room):
         """The staging blob (room bytes and 64 more: readable past blob_bytes, as the resident blob is) and the staged offsets
@@ -520,12 +520,36 @@ class Corpus(_Closing):
     def entries_per_crop(self, num_frames, sample_rate=None):
         """K for crops of num_frames frames: the entries the plan reserves per crop (computed once per length).  sample_rate,
         for a corpus whose rates differ: K of the crops of num_frames frames at that rate, as for stage_bytes_per_crop."""
+        return self._window_of(num_frames, sample_rate)["K"]
+
+    def _window_of(self, num_frames, sample_rate):
+        """The window behind the public K and S: a corpus that has a rate of its own ignores sample_rate"""
         if sample_rate is not None and self.sample_rate is None:
-            return self._mixed_window(sample_rate, num_frames)["K"]
-        L = int(num_frames)
-        if L not in self._K:
-            self._K[L] = max(entries_per_crop(self._host["pkt_end"], self._host["file_first"], L), 1)
-        return self._K[L]
+            return self._window(sample_rate, _frame_count("num_frames", num_frames))
+        return self._window(None, int(num_frames))
+
+    def _window(self, R, L):
+        """Per (target rate, crop length), once: Ls, the source frames a crop's window takes -- L itself for R None, the native
+        window; else resample.source_window's bound, an int, or where the rates differ int64 [F] with file f's by its own
+        ratio, and then d_Ls as well, the same as an int32 device tensor --, Ls_max, the largest, and K and S, where a file
+        counts with its own Ls.  S only where there is a host tier, else None: the packet sizes of a corpus from PCM would
+        have to come from the device for it."""
+        import torch
+
+        if (R, L) not in self._windows:
+            Ls = L
+            if R is not None:
+                rt = self._rate(R)
+                Ls = ((max(L, 1) - 1) // rt["b"] + 2) * rt["a"] + 2 * rt["width"]
+                if int(np.max(Ls)) >= 1 << 32:
+                    raise ValueError(f"num_frames {L} needs {int(np.max(Ls))} source frames: that does not fit 32 bits")
+            h = self._host
+            win = dict(Ls=Ls, Ls_max=int(np.max(Ls)), K=max(entries_per_crop(h["pkt_end"], h["file_first"], Ls), 1),
+                       S=stage_bytes_per_crop(self._host_table("pkt_size"), h["pkt_end"], h["file_first"], Ls) if self._hi_bytes else None)
+            if np.ndim(Ls):
+                win["d_Ls"] = torch.from_numpy(Ls.astype(np.uint32).view(np.int32)).to(self._dev)
+            self._windows[R, L] = win
+        return self._windows[R, L]
 
     def _plan_arrays(self, n):
         """The six plan arrays and the status array, kept and reused while n does not grow past them."""
@@ -585,10 +609,10 @@ class Corpus(_Closing):
         the first crop with a negative length.  check=False reads nothing back and returns behind the enqueue: see
         last_status().
 
-        sample_rate / mono: crops at another rate and as one channel (`_resampled_crops`): frame_offsets and num_frames then
+        sample_rate / mono: crops at another rate and as one channel (`_rate_crops`): frame_offsets and num_frames then
         count frames at sample_rate, pcm is float32 [B, 1 if mono else C, num_frames].  The defaults -- and the corpus's own
         rate, and mono of one channel -- are the path above.  A corpus whose files differ in rate (mixed_rates=True) has no
-        rate of its own: sample_rate is required (ValueError without), and every crop comes through `_mixed_crops`.
+        rate of its own: sample_rate is required (ValueError without), and every crop comes through `_rate_crops`.
 
         features: a features.LogMel -- the crops' log-mel features instead of their PCM (`_feature_crops`): returns (feats
         float32 [B, 1 if mono else C, n_mels, 1 + num_frames // hop], feat_lengths [B] int64 on the device: lengths // hop + 1,
@@ -597,54 +621,42 @@ class Corpus(_Closing):
 
         if features is not None:
             return self._feature_crops(files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, features)
-        if self.sample_rate is None:
-            if sample_rate is None:
-                raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
-            return self._mixed_crops(files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono)
-        if (mono and self.channels == 2) or (sample_rate is not None and sample_rate != self.sample_rate):
-            return self._resampled_crops(files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono)
+        if self.sample_rate is None and sample_rate is None:
+            raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
+        if self.sample_rate is None or (mono and self.channels == 2) or (sample_rate is not None and sample_rate != self.sample_rate):
+            return self._rate_crops(files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono)
         dtype = _torch_dtype(torch, torch.float32 if dtype is None else dtype)
         L = _frame_count("num_frames", num_frames)
         if L >= 1 << 32:
             raise ValueError(f"num_frames {L} does not fit 32 bits")
-        if self._gpu is None:
-            raise AlacGpuError("the corpus is closed")
+        self._open()
         d_files, d_offs, from_host = self._indices(files, frame_offsets)
-        B, C_ = int(d_files.shape[0]), self.channels
-        if out is not None:
-            if (not isinstance(out, torch.Tensor) or out.shape != (B, C_, L) or out.dtype != dtype or out.device != self._dev
-                    or not out.is_contiguous()):
-                raise ValueError(f"out must be a contiguous {dtype} tensor of shape {(B, C_, L)} on {self._dev}")
-            out.zero_()
-        else:
-            out = torch.zeros((B, C_, L), dtype=dtype, device=self._dev)
+        B = int(d_files.shape[0])
+        out = self._out(out, (B, self.channels, L), dtype, zero=True)
         self._last = 0
         if B == 0 or L == 0:
             lengths = torch.zeros(B, dtype=torch.int64, device=self._dev)
             if B and L == 0 and not from_host:     # (the kernel's length codes, without the kernel)
-                f64 = d_files.to(torch.int64)
-                ok = (f64 >= 0) & (f64 < self.num_files)
-                ok &= (d_offs >= 0) & (d_offs <= self._d_num_frames[f64.clamp(0, self.num_files - 1)])
-                lengths = torch.where(ok, lengths, lengths - 1)
+                lengths = torch.where(self._inside(d_files, d_offs, self._d_num_frames)[0], lengths, lengths - 1)
                 if check:
                     self._raise_bad_length(lengths, d_files, d_offs)
             return out, lengths
-        K = self.entries_per_crop(L)
-        n = B * K
-        if n >= 1 << 32:
+        win = self._window(None, L)
+        K = win["K"]
+        if B * K >= 1 << 32:
             raise ValueError(f"{B} crops of up to {K} packets: a call plans fewer than 2^32 entries")
-        lengths = self._plan_and_decode(d_files, d_offs, L, K, self.stage_bytes_per_crop(L) if self._hi_bytes else 0, out)
+        lengths = self._plan_and_decode(d_files, d_offs, L, K, win["S"], out)
         if check:
             self._check_last(lengths, d_files, d_offs, L, K)
         return out, lengths
 
     def _feature_crops(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, spec):
-        """crops(..., features=spec): the crops are made exactly as without -- on the native, the `_resampled_crops` or the
-        `_mixed_crops` path, `mono` honoured, `check` as there -- into a float32 scratch [B, Co, num_frames] the corpus keeps,
-        then ONE alacgpu_logmel_device call on the same stream turns every row, the zeros behind its length included, into
-        features (features.py states the transform).  ValueError before any device work: a spec.sample_rate that is not the
-        rate of the crops (sample_rate if given, else the corpus's own), a dtype other than float32, num_frames <=
-        n_fft // 2, an `out` that is not a contiguous float32 [B, Co, n_mels, 1 + num_frames // hop] on the device."""
+        """crops(..., features=spec): the crops are made exactly as without -- on the native or the `_rate_crops` path, `mono`
+        honoured, `check` as there -- into a float32 scratch [B, Co, num_frames] the corpus keeps, then ONE
+        alacgpu_logmel_device call on the same stream turns every row, the zeros behind its length included, into features
+        (features.py states the transform).  ValueError before any device work: a spec.sample_rate that is not the rate of
+        the crops (sample_rate if given, else the corpus's own), a dtype other than float32, num_frames <= n_fft // 2, an
+        `out` that is not a contiguous float32 [B, Co, n_mels, 1 + num_frames // hop] on the device."""
         import torch
 
         from .features import LogMel, feature_lengths
@@ -661,29 +673,50 @@ class Corpus(_Closing):
         L = _frame_count("num_frames", num_frames)
         if L <= spec.n_fft // 2:
             raise ValueError(f"num_frames {L}: the transform needs more than n_fft // 2 = {spec.n_fft // 2}")
-        if self._gpu is None:
-            raise AlacGpuError("the corpus is closed")
+        self._open()
         B = int(files.shape[0]) if isinstance(files, torch.Tensor) and files.dim() == 1 else len(np.asarray(files))
         Co = 1 if mono else self.channels
         Tf = spec.frames(L)
-        shape = (B, Co, spec.n_mels, Tf)
-        if out is not None:
-            if (not isinstance(out, torch.Tensor) or out.shape != shape or out.dtype != torch.float32 or out.device != self._dev
-                    or not out.is_contiguous()):
-                raise ValueError(f"out must be a contiguous torch.float32 tensor of shape {shape} on {self._dev}")
-        else:
-            out = torch.empty(shape, dtype=torch.float32, device=self._dev)
-        n = B * Co * L
-        if self._ft_scratch is None or self._ft_scratch.numel() < n:
-            self._ft_scratch = None     # (the old one goes first)
-            self._ft_scratch = torch.empty(n, dtype=torch.float32, device=self._dev)
-        pcm = self._ft_scratch[:n].view(B, Co, L)
+        out = self._out(out, (B, Co, spec.n_mels, Tf), torch.float32, zero=False)
+        pcm = self._scratch("_ft_scratch", (B, Co, L))
         _, lengths = self.crops(files, frame_offsets, L, out=pcm, check=check, sample_rate=sample_rate, mono=mono)
         if B:
             window, basis, fb = spec.device_tables(self._dev)
             self._gpu.logmel_device(pcm, B, Co, L, L, spec.n_fft, spec.hop_length, spec.n_mels, window, basis, fb, spec.log_mode,
                                     spec.floor, out, Tf, stream=torch.cuda.current_stream(self._dev).cuda_stream)
         return out, feature_lengths(lengths, spec.hop_length)
+
+    def _out(self, out, shape, dtype, zero):
+        """The tensor a call writes: `out` checked against shape and dtype, or a new one; zeroed where the decode relies on it"""
+        import torch
+
+        if out is None:
+            return (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self._dev)
+        if (not isinstance(out, torch.Tensor) or out.shape != shape or out.dtype != dtype or out.device != self._dev
+                or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous {dtype} tensor of shape {shape} on {self._dev}")
+        return out.zero_() if zero else out
+
+    def _scratch(self, name, shape):
+        """A float32 view of `shape` on the flat scratch the corpus keeps under the attribute `name`, which grows when a call
+        needs more"""
+        import torch
+
+        n = int(np.prod(shape))
+        if getattr(self, name) is None or getattr(self, name).numel() < n:
+            setattr(self, name, None)       # (the old one goes first)
+            setattr(self, name, torch.empty(n, dtype=torch.float32, device=self._dev))
+        return getattr(self, name)[:n].view(shape)
+
+    def _inside(self, d_files, d_offs, d_totals):
+        """Which crops are inside the corpus, on the device: (ok [B] bool -- a file index in 0 .. F - 1 and an offset in 0 ..
+        d_totals[file] --, the file indices clamped into 0 .. F - 1 as int64, d_totals gathered with them)"""
+        f64 = d_files.long()
+        ok = (f64 >= 0) & (f64 < self.num_files)
+        fc = f64.clamp(0, self.num_files - 1)
+        totals = d_totals[fc]
+        ok &= (d_offs >= 0) & (d_offs <= totals)
+        return ok, fc, totals
 
     def _plan_and_decode(self, d_files, d_offs, L, K, S, out, d_frames=None):
         """The launches of a step: the plan of the crops (d_files, d_offs) of L frames with K entries each, the staging of its
@@ -723,62 +756,68 @@ class Corpus(_Closing):
     def resampled_frames(self, sample_rate):
         """Ty_f: the frames of every file at sample_rate, ceil(b * T_f / a) with the file's own reduced ratio a : b (int64 host
         array [F])."""
-        if self.sample_rate is None:
-            return self._mixed_rate(sample_rate)["Ty"]
-        return self._rate(sample_rate)[0]
+        return self._rate(sample_rate)["Ty"]
 
     def _rate(self, sample_rate):
-        """(Ty host, Ty device, the device table) of the corpus's rate to sample_rate (None: the corpus's), once per rate"""
+        """What crops at sample_rate (None: the corpus's own rate) need, once per rate: Ty on the host and d_Ty on the device,
+        and the filter.  A corpus of one rate: a, b, width as ints and its table d_d0, d_w (resample.device_table).  One whose
+        rates differ: a, b, width as int64 host arrays [F], the same on the device as d_a, d_b, d_width next to d_table_of,
+        a file's table, and the tables of the files' ratios (resample.rows_tables: desc on the host, d_desc, d_d0, d_w).
+        ValueError: a rate the filter does not take, naming the first file whose table is too large."""
         import torch
 
-        from .resample import device_table, resampled_frames
+        from .resample import device_table, resampled_frames, rows_tables
 
         R = self.sample_rate if sample_rate is None else sample_rate
-        if R not in self._rs_frames:
-            table = device_table(self.sample_rate, R, self._dev)       # (ValueError for a rate the filter does not take)
-            Ty = resampled_frames(self.num_frames, table[0], table[1])
-            self._rs_frames[R] = (Ty, torch.from_numpy(Ty).to(self._dev), table)
-        return self._rs_frames[R]
+        if R not in self._rates:
+            up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(self._dev)
+            if self.sample_rate is not None:
+                rt = dict(zip(("a", "b", "width", "d_d0", "d_w"), device_table(self.sample_rate, R, self._dev)))
+            else:
+                table_of, desc, d0, w = rows_tables(self.sample_rates.tolist(), R)
+                a, b, width = (desc[table_of, k].astype(np.int64) for k in range(3))
+                rt = dict(a=a, b=b, width=width, d_a=up(a), d_b=up(b), d_width=up(width), d_table_of=up(table_of), desc=desc,
+                          d_desc=up(desc.view(np.int32)), d_d0=up(d0), d_w=up(w))
+            Ty = resampled_frames(self.num_frames, rt["a"], rt["b"])
+            self._rates[R] = dict(rt, rate=R, Ty=Ty, d_Ty=up(Ty))
+        return self._rates[R]
 
-    def _resampled_crops(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono):
-        """crops(..., sample_rate=R, mono=) : crop b is frames frame_offsets[b] .. + num_frames of file files[b] RESAMPLED AS A
-        WHOLE to R Hz (resample.py states the filter), zero behind its end; lengths[b] = min(num_frames, Ty_f - offset) with
-        Ty_f = ceil(b * T_f / a), -1 for a file index or an offset outside the corpus -- the host checks and the device-tensor
-        rule are those of `crops`, with Ty_f for T_f.  A step: the source frames a crop needs (`source_window`: Ls(num_frames)
-        of them from (o // b) * a - width on, by integer operations on the device) are planned, staged and decoded as crops
-        of the source into a float32 scratch [B, C, Ls] the corpus keeps, then ONE alacgpu_resample_device call filters every
-        crop out of it.  mono: two channels become their mean in front of the filter.  sample_rate None or the corpus's own
-        never comes here without `mono`; with it there is no filter, the kernel only takes the mean (resample.identity_table).
-        dtype: float32 (ValueError otherwise)."""
+    def _rate_crops(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono):
+        """crops(..., sample_rate=R, mono=): crop b is frames frame_offsets[b] .. + num_frames of file files[b] RESAMPLED AS A
+        WHOLE to R Hz (resample.py states the filter) by the file's reduced ratio a : b, zero behind its end; lengths[b] =
+        min(num_frames, Ty_f - offset) with Ty_f = ceil(b * T_f / a), -1 for a file index or an offset outside the corpus --
+        the host checks and the device-tensor rule are those of `crops`, with Ty_f for T_f.  A step: the source frames a crop
+        needs (`source_window`: Ls(num_frames) of them from (o // b) * a - width on, clamped at 0, by integer operations on
+        the device) are planned, staged and decoded as crops of the source into a zeroed float32 scratch [B, C, Ls] the corpus
+        keeps, then ONE resample call filters every crop out of it.  mono: two channels become their mean in front of the
+        filter.  dtype: float32 (ValueError otherwise).  The step varies in three places with the kind of corpus:
+          one rate      a, b, width are ints; alacgpu_plan_crops_device; alacgpu_resample_device.  sample_rate None or the
+                        corpus's own never comes here without `mono`; with it there is no filter, the kernel only takes the
+                        mean (resample.identity_table).
+          rates differ  a, b, width are gathered per crop from the per-file device arrays; alacgpu_plan_crops_frames_device
+                        with the crop's own window Ls_f in a scratch [B, C, max Ls_f] (a crop of a 16 kHz file does not decode
+                        what a crop of a 48 kHz file needs); alacgpu_resample_rows_device with a table per row, none (a row of
+                        zeros) for a crop outside the corpus.  A file already at R goes through the table that copies."""
         import torch
-
-        from .resample import source_window
 
         if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
             raise ValueError("crops at another sample rate or as mono are float32")
         L = _frame_count("num_frames", num_frames)
-        if self._gpu is None:
-            raise AlacGpuError("the corpus is closed")
+        self._open()
         if self.channels not in (1, 2):
             raise ValueError(f"{self.channels} channels: the resampler takes 1 or 2")
-        Ty, d_Ty, (a, b, width, d_d0, d_w) = self._rate(sample_rate)
-        Ls = source_window(0, max(L, 1), a, b, width)[1]
-        if Ls >= 1 << 32:
-            raise ValueError(f"num_frames {L} needs {Ls} source frames: that does not fit 32 bits")
-        d_files, d_offs, _ = self._indices(files, frame_offsets, Ty)
+        rt = self._rate(sample_rate)
+        win = self._window(rt["rate"], L)
+        Ls, K = win["Ls_max"], win["K"]
+        d_files, d_offs, _ = self._indices(files, frame_offsets, rt["Ty"])
         B, C_ = int(d_files.shape[0]), self.channels
-        Co = 1 if mono else C_
-        if out is not None:
-            if (not isinstance(out, torch.Tensor) or out.shape != (B, Co, L) or out.dtype != torch.float32 or out.device != self._dev
-                    or not out.is_contiguous()):
-                raise ValueError(f"out must be a contiguous torch.float32 tensor of shape {(B, Co, L)} on {self._dev}")
-        else:
-            out = torch.empty((B, Co, L), dtype=torch.float32, device=self._dev)
+        out = self._out(out, (B, 1 if mono else C_, L), torch.float32, zero=False)
+        if B * K >= 1 << 32:
+            raise ValueError(f"{B} crops of up to {K} packets: a call plans fewer than 2^32 entries")
         # the crops in source frames: where the target offset is inside its file, else an offset the planner refuses (-1)
-        f64 = d_files.to(torch.int64)
-        ok = (f64 >= 0) & (f64 < self.num_files)
-        Ty_f = d_Ty[f64.clamp(0, self.num_files - 1)]
-        ok &= (d_offs >= 0) & (d_offs <= Ty_f)
+        ok, fc, Ty_f = self._inside(d_files, d_offs, rt["d_Ty"])
+        rows = "desc" in rt
+        a, b, width = (rt["d_a"][fc], rt["d_b"][fc], rt["d_width"][fc]) if rows else (rt["a"], rt["b"], rt["width"])
         origin = (torch.div(d_offs, b, rounding_mode="floor") * a - width).clamp(min=0)
         src_offs = torch.where(ok, origin, -1)
         lengths = torch.where(ok, (Ty_f - d_offs).clamp(max=L), -1)
@@ -787,112 +826,17 @@ class Corpus(_Closing):
             if check and B:
                 self._raise_bad_length(lengths, d_files, d_offs)
             return out, lengths
-        n = B * C_ * Ls
-        if self._rs_scratch is None or self._rs_scratch.numel() < n:
-            self._rs_scratch = None     # (the old one goes first)
-            self._rs_scratch = torch.empty(n, dtype=torch.float32, device=self._dev)
-        scratch = self._rs_scratch[:n].view(B, C_, Ls)
-        _, valid = self.crops(d_files, src_offs, Ls, out=scratch, check=False)
-        self._gpu.resample_device(scratch, B, C_, Ls, origin, valid, d_offs, L, a, b, width, d_d0, d_w, mono, out,
-                                  stream=torch.cuda.current_stream(self._dev).cuda_stream)
-        if check:
-            self._check_last(valid, d_files, src_offs, Ls, self.entries_per_crop(Ls), d_shown=d_offs)
-        return out, lengths
-
-    def _mixed_rate(self, sample_rate):
-        """What crops at sample_rate of a corpus whose rates differ need, once per rate: the tables of the files' ratios
-        (resample.rows_tables: host descriptors and the three device arrays), per file on the device the table, a, b, width
-        and Ty, and Ty on the host.  ValueError: a rate the filter does not take, naming the first file whose table is too
-        large."""
-        import torch
-
-        from .resample import resampled_frames, rows_tables
-
-        R = sample_rate
-        if R not in self._mx_rates:
-            table_of, desc, d0, w = rows_tables(self.sample_rates.tolist(), R)
-            a, b, width = (desc[table_of, k].astype(np.int64) for k in range(3))
-            Ty = resampled_frames(self.num_frames, a, b)
-            up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(self._dev)
-            self._mx_rates[R] = dict(desc=desc, d_desc=up(desc.view(np.int32)), d_d0=up(d0), d_w=up(w), table_of=table_of, a=a, b=b,
-                                     width=width, Ty=Ty, d_table_of=up(table_of), d_a=up(a), d_b=up(b), d_width=up(width), d_Ty=up(Ty))
-        return self._mx_rates[R]
-
-    def _mixed_window(self, sample_rate, num_frames):
-        """Per (rate, crop length): Ls_f, the source window of file f (resample.source_window with the file's ratio) on the
-        host and as an int32 device tensor, the largest of them, and K and S where a file counts with its own Ls_f."""
-        import torch
-
-        rt = self._mixed_rate(sample_rate)
-        L = _frame_count("num_frames", num_frames)
-        key = (sample_rate, L)
-        if key not in self._mx_windows:
-            Ls = ((max(L, 1) - 1) // rt["b"] + 2) * rt["a"] + 2 * rt["width"]
-            if int(Ls.max()) >= 1 << 32:
-                raise ValueError(f"num_frames {L} needs {int(Ls.max())} source frames: that does not fit 32 bits")
-            h = self._host
-            K = max(entries_per_crop(h["pkt_end"], h["file_first"], Ls), 1)
-            S = stage_bytes_per_crop(self._host_table("pkt_size"), h["pkt_end"], h["file_first"], Ls) if self._hi_bytes else 0
-            self._mx_windows[key] = dict(Ls=Ls, d_Ls=torch.from_numpy(Ls.astype(np.uint32).view(np.int32)).to(self._dev),
-                                         Ls_max=int(Ls.max()), K=K, S=S)
-        return self._mx_windows[key]
-
-    def _mixed_crops(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono):
-        """crops(..., sample_rate=R) of a corpus whose files differ in rate: `_resampled_crops` with file f's own reduced
-        ratio a_f : b_f -- crop b is frames frame_offsets[b] .. + num_frames of file files[b] resampled as a whole to R Hz,
-        lengths[b] = min(num_frames, Ty_f - offset), Ty_f = ceil(b_f * T_f / a_f).  The same launches whatever the rates:
-        per crop, from per-file device tables by integer operations, the source origin (o // b_f) * a_f - width_f (clamped
-        at 0), the source window Ls_f and the table; ONE plan with a window length per crop
-        (alacgpu_plan_crops_frames_device: a crop of a 16 kHz file does not decode what a crop of a 48 kHz file needs), the
-        staging, ONE decode into the scratch [B, C, max Ls_f], and ONE alacgpu_resample_rows_device call.  A file already
-        at R goes through the table that copies."""
-        import torch
-
-        if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
-            raise ValueError("crops at another sample rate or as mono are float32")
-        L = _frame_count("num_frames", num_frames)
-        if self._gpu is None:
-            raise AlacGpuError("the corpus is closed")
-        if self.channels not in (1, 2):
-            raise ValueError(f"{self.channels} channels: the resampler takes 1 or 2")
-        rt = self._mixed_rate(sample_rate)
-        win = self._mixed_window(sample_rate, L)
-        Ls, K = win["Ls_max"], win["K"]
-        d_files, d_offs, _ = self._indices(files, frame_offsets, rt["Ty"])
-        B, C_, F = int(d_files.shape[0]), self.channels, self.num_files
-        Co = 1 if mono else C_
-        if out is not None:
-            if (not isinstance(out, torch.Tensor) or out.shape != (B, Co, L) or out.dtype != torch.float32 or out.device != self._dev
-                    or not out.is_contiguous()):
-                raise ValueError(f"out must be a contiguous torch.float32 tensor of shape {(B, Co, L)} on {self._dev}")
-        else:
-            out = torch.empty((B, Co, L), dtype=torch.float32, device=self._dev)
-        if B * K >= 1 << 32:
-            raise ValueError(f"{B} crops of up to {K} packets: a call plans fewer than 2^32 entries")
-        # the crops in source frames: where the target offset is inside its file, else an offset the planner refuses (-1)
-        f64 = d_files.to(torch.int64)
-        ok = (f64 >= 0) & (f64 < F)
-        fc = f64.clamp(0, F - 1)
-        Ty_f = rt["d_Ty"][fc]
-        ok &= (d_offs >= 0) & (d_offs <= Ty_f)
-        origin = (torch.div(d_offs, rt["d_b"][fc], rounding_mode="floor") * rt["d_a"][fc] - rt["d_width"][fc]).clamp(min=0)
-        src_offs = torch.where(ok, origin, -1)
-        lengths = torch.where(ok, (Ty_f - d_offs).clamp(max=L), -1)
-        if B == 0 or L == 0:
-            self._last = 0
-            if check and B:
-                self._raise_bad_length(lengths, d_files, d_offs)
-            return out, lengths
-        row_table = torch.where(ok, rt["d_table_of"][fc], len(rt["desc"])).to(torch.int32)
-        n = B * C_ * Ls
-        if self._rs_scratch is None or self._rs_scratch.numel() < n:
-            self._rs_scratch = None     # (the old one goes first)
-            self._rs_scratch = torch.empty(n, dtype=torch.float32, device=self._dev)
-        scratch = self._rs_scratch[:n].view(B, C_, Ls)
+        scratch = self._scratch("_rs_scratch", (B, C_, Ls))
         scratch.zero_()
-        valid = self._plan_and_decode(d_files, src_offs, Ls, K, win["S"], scratch, d_frames=win["d_Ls"][fc])
-        self._gpu.resample_rows_device(scratch, B, C_, Ls, origin, valid, d_offs, L, rt["desc"], rt["d_desc"], rt["d_d0"], rt["d_w"],
-                                       row_table, mono, out, stream=torch.cuda.current_stream(self._dev).cuda_stream)
+        valid = self._plan_and_decode(d_files, src_offs, Ls, K, win["S"], scratch, d_frames=win["d_Ls"][fc] if rows else None)
+        stream = torch.cuda.current_stream(self._dev).cuda_stream
+        if rows:
+            row_table = torch.where(ok, rt["d_table_of"][fc], len(rt["desc"])).to(torch.int32)
+            self._gpu.resample_rows_device(scratch, B, C_, Ls, origin, valid, d_offs, L, rt["desc"], rt["d_desc"], rt["d_d0"], rt["d_w"],
+                                           row_table, mono, out, stream=stream)
+        else:
+            self._gpu.resample_device(scratch, B, C_, Ls, origin, valid, d_offs, L, a, b, width, rt["d_d0"], rt["d_w"], mono, out,
+                                      stream=stream)
         if check:
             self._check_last(valid, d_files, src_offs, Ls, K, d_shown=d_offs)
         return out, lengths
@@ -910,12 +854,9 @@ class Corpus(_Closing):
         dev = generator.device if generator is not None else self._dev
         files = torch.randint(0, self.num_files, (B,), generator=generator, device=dev, dtype=torch.int64).to(self._dev)
         u = torch.rand(B, generator=generator, device=dev, dtype=torch.float64).to(self._dev)
-        if self.sample_rate is None:
-            if sample_rate is None:
-                raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
-            totals = self._mixed_rate(sample_rate)["d_Ty"]
-        else:
-            totals = self._d_num_frames if sample_rate is None else self._rate(sample_rate)[1]
+        if self.sample_rate is None and sample_rate is None:
+            raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
+        totals = self._d_num_frames if sample_rate is None else self._rate(sample_rate)["d_Ty"]
         span = (totals[files] - L).clamp(min=0)
         offs = torch.minimum(torch.floor(u * (span + 1).to(torch.float64)).to(torch.int64), span)
         pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,

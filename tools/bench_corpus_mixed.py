@@ -5,7 +5,8 @@
                     parent's package, alternating with this one: this tree's median has to lie inside the parent's p10 .. p90
   (b) mixed         Corpus(half the files at 44.1 kHz, half at 48 kHz, mixed_rates=True): crops(..., sample_rate=16000,
                     mono=True), half the crops from either half, in one call; HIP events around the plan + decode pair and
-                    around the one resample call (--reps back-to-back launches)
+                    around the one resample call (--reps back-to-back launches).  With --parent the parent's mixed corpus takes
+                    the same step, alternating with this one, under the same criterion
   (c) two_corpora   the two single-rate corpora of the same files and the same crops in two calls of half the batch each
 Wall time of a step: torch.cuda.synchronize() in front of and behind it, the ways alternating inside every step, median and
 p10 .. p90 of --steps steps after --warmup.  One JSON document, printed and written to --out.
@@ -58,7 +59,7 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--parent", help="a built tree of the parent commit: its single-rate steps alternate with this tree's")
+    ap.add_argument("--parent", help="a built tree of the parent commit: its single-rate and mixed steps alternate with this tree's")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "corpus_mixed_rates.json"))
     args = ap.parse_args()
     import torch
@@ -96,8 +97,9 @@ def main():
         return {m: stats(v) for m, v in wall.items()}
 
     # (a) the single-rate step, this tree against the parent
+    parent_pkg = load_parent(args.parent) if args.parent else None
     single = pkg.Corpus(of_rate[44100] + of_rate[44100])
-    parent = load_parent(args.parent).Corpus(of_rate[44100] + of_rate[44100]) if args.parent else None
+    parent = parent_pkg.Corpus(of_rate[44100] + of_rate[44100]) if args.parent else None
     T = int(args.seconds * 44100)
     files = [torch.from_numpy(rng.integers(0, 2 * half, B)).to(dev) for _ in range(n_steps)]
     u = [rng.random(B) for _ in range(n_steps)]
@@ -121,6 +123,7 @@ def main():
 
     # (b) the mixed step and (c) the two single-rate corpora over the same crops
     mixed = pkg.Corpus(of_rate[44100] + of_rate[48000], mixed_rates=True)
+    parent = parent_pkg.Corpus(of_rate[44100] + of_rate[48000], mixed_rates=True) if args.parent else None
     two = [pkg.Corpus(of_rate[r]) for r in rates]
     Ty = torch.from_numpy(mixed.resampled_frames(R)).to(dev)
     files = [torch.from_numpy(np.concatenate([rng.integers(0, half, B // 2), half + rng.integers(0, half, B - B // 2)])).to(dev) for _ in range(n_steps)]
@@ -134,10 +137,17 @@ def main():
 
     ways = {"mixed": lambda i: mixed.crops(files[i], offs[i], L, check=False, sample_rate=R, mono=True)[0], "two_corpora": both}
     assert torch.equal(ways["mixed"](0), torch.cat(both(0))), "the mixed crops differ from the single-rate corpora's"
+    if parent is not None:
+        ways["parent_mixed"] = lambda i: parent.crops(files[i], offs[i], L, check=False, sample_rate=R, mono=True)[0]
+        assert torch.equal(ways["mixed"](0), ways["parent_mixed"](0)), "the mixed crops differ from the parent's"
     b = {"wall_ms": measure(ways)}
+    if parent is not None:
+        p = b["wall_ms"]["parent_mixed"]
+        b["mixed_inside_parent_p10_p90"] = bool(p["p10"] <= b["wall_ms"]["mixed"]["median"] <= p["p90"])
+        parent.close()
     b["mixed_over_two_corpora"] = round(b["wall_ms"]["mixed"]["median"] / b["wall_ms"]["two_corpora"]["median"], 3)
     # the two halves of the mixed step alone, over the first step's crops
-    rt, win = mixed._mixed_rate(R), mixed._mixed_window(R, L)
+    rt, win = mixed._rate(R), mixed._window(R, L)
     out, _ = mixed.crops(files[0], offs[0], L, check=False, sample_rate=R, mono=True)
     f = files[0]
     origin = (torch.div(offs[0], rt["d_b"][f], rounding_mode="floor") * rt["d_a"][f] - rt["d_width"][f]).clamp(min=0)

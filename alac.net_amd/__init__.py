@@ -936,4 +936,4 @@ from .corpus import (Corpus, compact_plan_host, corpus_plan_host, corpus_tables,
 # ---- crops and tensors at another sample rate (alacgpu_resample_device) ---------------------------------------------------------------
 from .resample import resample, resample_host, resample_table, source_window  # noqa: E402
 # ---- log-mel features of crops and tensors (alacgpu_logmel_device) -----------------------------------------------------------------
-from .features import LogMel, log_mel, logmel_host, mel_filterbank  # noqa: E402
+from .features import LogMel, log_mel, logmel_host, logmel_host_f32, mel_filterbank  # noqa: E402

@@ -169,7 +169,7 @@ __global__ __launch_bounds__(ALAC_FEATURES_THREADS) void alac_logmel_kernel(alac
         for (uint32_t m = tid >> 5; m < n_mels; m += ALAC_FEATURES_THREADS / 32u) {
             float v = mel[m * ALAC_FEATURES_TILE + t];
             if (p.log_mode != ALAC_FEATURES_LOG_NONE) {
-                v = v > p.floor ? v : p.floor;
+                v = v < p.floor ? p.floor : v;     // (a NaN stays a NaN, as in np.maximum and torch.clamp)
                 v = p.log_mode == ALAC_FEATURES_LOG_LN ? logf(v) : log10f(v);
             }
             out[(uint64_t)m * p.out_frames] = v;

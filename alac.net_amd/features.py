@@ -29,6 +29,13 @@ u = 2^-24 and a_n = |window[n] * x_t[n]| that stays within
 
 of the exact value; `logmel_host(..., bound=True)` returns dM.
 
+Input that is not finite follows IEEE arithmetic and is never hidden.  A NaN or an infinity at sample i reaches the frames that
+have a tap on i -- the tap whose window weight is zero too, 0 * inf being NaN -- and only those: every other frame, and every
+other plane, is bit for bit what it is for the same signal without it.  In such a frame an element is whatever the sums above
+give in IEEE arithmetic (with the tables of this module NaN throughout: every filter has a weight of zero somewhere, and
+0 * inf is NaN), and max(M, floor) keeps a NaN as np.maximum and torch.clamp do: its log is NaN, never log(floor).  Where the
+sums do give +inf the log is +inf.
+
 `mel_filterbank`, `LogMel` and `logmel_host` (the kernel's specification in numpy) need no device.  `log_mel` is the call on
 device tensors.
 """
@@ -234,6 +241,50 @@ def logmel_host(x, spec, bound=False):
         out[r] = M.T
     out = out.reshape(x.shape[:-1] + (spec.n_mels, T))
     return (out, dM.reshape(out.shape)) if bound else out
+
+
+def logmel_host_f32(x, spec):
+    """The kernel's arithmetic in numpy, one float32 operation at a time: x float32 [..., L] to float32 [..., n_mels, T'], the
+    mel power (spec.log and spec.floor are not applied).  The window product is rounded once; X[j] is a chain of fused
+    multiply-adds in ascending n from zero; P = fma(re, re, round(im * im)); M[m] is a chain of fused multiply-adds in
+    ascending k from zero.  (An fma of float32 values is evaluated as the float64 product, which is exact, plus the float64
+    addend, rounded to float64 and then to float32: twice where the hardware rounds once, which differs in the last bit of
+    rare elements only.)  Its distance from `logmel_host` is what a correct float32 evaluation costs: the tests hold the
+    kernel to a small multiple of that, far inside dM."""
+    x = np.asarray(x)
+    if x.dtype != np.float32:
+        raise ValueError(f"x must be float32, not {x.dtype}")
+    L = x.shape[-1] if x.ndim else 0
+    if x.ndim < 1 or L <= spec.n_fft // 2:
+        raise ValueError(f"x must be [..., L] with L > n_fft // 2 = {spec.n_fft // 2}, not {x.shape}")
+    f32, f64 = np.float32, np.float64
+    n_bins = spec.n_bins
+    idx, inside = frame_index(L, spec.n_fft, spec.hop_length)
+    T = idx.shape[0]
+    basis = spec.basis.astype(f64)
+    fb = spec.fb.astype(f64)
+    rows = x.reshape(-1, L)
+    out = np.empty((rows.shape[0], spec.n_mels, T), dtype=f32)
+
+    def chain(a, b):
+        """a [T, K] float32, b [K, N] float64 holding float32 values: fma(a[:, k], b[k], acc) for k = 0 .. K - 1, from zero"""
+        a = np.ascontiguousarray(a.T, dtype=f64)                                           # [K, T]
+        acc, wide = np.zeros((a.shape[1], b.shape[1]), dtype=f32), np.zeros((a.shape[1], b.shape[1]), dtype=f64)
+        tmp = np.empty_like(wide)
+        for k in range(a.shape[0]):
+            np.multiply(a[k][:, None], b[k][None, :], out=tmp)
+            tmp += wide
+            acc[...] = tmp                                                                 # the rounding to float32
+            wide[...] = acc
+        return acc
+
+    for r, row in enumerate(rows):
+        fr = (np.where(inside, row[idx], f32(0)) * spec.window[None, :]).astype(f32)       # [T, n_fft]
+        X = chain(fr, basis)
+        re, im = X[:, :n_bins].astype(f64), X[:, n_bins:].astype(f64)
+        P = (re * re + (im * im).astype(f32).astype(f64)).astype(f32)
+        out[r] = chain(P, np.ascontiguousarray(fb.T)).T
+    return out.reshape(x.shape[:-1] + (spec.n_mels, T))
 
 
 # ---- on the device -------------------------------------------------------------------------------------------------------------

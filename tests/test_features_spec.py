@@ -1,14 +1,40 @@
 """features.py without a device: the mel scales and the filterbank against known answers written out from their formulas, the
-specification (logmel_host) against numpy's own padding and FFT, and the derived bound against a plain float32 evaluation."""
+specification (logmel_host) against numpy's own padding and FFT, the derived bound against a plain float32 evaluation
+(logmel_host_f32), and that evaluation as a yardstick: which broken tables it sees that the bound does not."""
 import math
 
 import numpy as np
 import pytest
 
-from alac.net_amd.features import (LogMel, dft_basis, frame_index, hann_window, hz_to_mel, logmel_host, mel_filterbank,
-                                   mel_to_hz)
+from alac.net_amd.features import (LogMel, dft_basis, frame_index, hann_window, hz_to_mel, logmel_host, logmel_host_f32,
+                                   mel_filterbank, mel_to_hz)
 
 SHAPES = [(400, 160, 80, 5000), (25, 10, 8, 333), (512, 128, 64, 4000), (2048, 512, 128, 9000), (16, 1, 4, 40)]
+
+# (n_fft, hop, n_mels, L) by the branch of alac_features.hip each is there for; test_the_grid_is_what_it_claims holds every
+# claim against the constants of alac_features.h.  tests/test_features_paths.py runs the kernel on them.
+GRID = [
+    (16, 2, 1, 50),             # hop 2, one mel
+    (18, 3, 5, 60),             # even n_fft, one whole k-step left over
+    (20, 20, 7, 130),           # hop = n_fft, fewer than 8 mels, a filter row of zeros
+    (17, 5, 3, 70),             # odd n_fft whose only leftover step is the half one
+    (33, 16, 9, 200),           # the same with two groups of eight k-steps
+    (62, 31, 12, 700),          # 32 bins: one block, no clamped column
+    (126, 64, 33, 1500),        # 64 bins: two blocks, no clamped column
+    (63, 7, 12, 300),           # odd n_fft with 32 bins
+    (402, 161, 80, 3000),       # one leftover step at the working size, a large odd hop
+    (401, 160, 80, 3000),       # odd n_fft at the working size
+    (510, 255, 40, 4000),       # exactly 8 blocks: one full round
+    (1000, 250, 100, 5000),     # 4 leftover k-steps, 16 blocks: two full rounds
+    (1022, 2, 8, 600),          # hop 2 under a long window, 301 frames in 10 tiles
+    (1024, 1024, 17, 6000),     # 17 blocks: the last round has a single block
+    (2046, 1024, 255, 9000),    # 1024 bins, 7 leftover k-steps, 255 mels
+    (2048, 560, 256, 20000),    # the largest LDS layout of a full tile
+    (2048, 561, 256, 20000),    # the last hop with a full tile
+    (2048, 562, 256, 20000),    # the first hop with a shortened tile
+    (2048, 580, 256, 20000),    # the largest LDS layout of all: a shortened tile, 8 samples short of the span limit
+    (400, 160, 256, 3000),      # 45 filter rows of zeros
+]
 
 
 def test_mel_scales_known_answers():
@@ -167,38 +193,28 @@ def test_log_and_floor():
         logmel_host(x.astype(np.float64), LogMel(16000))
 
 
-def float32_serial(x, sp):
-    """The specification in plain float32, one operation at a time: the window product rounded once, then chains of fused
-    multiply-adds in ascending n and k (an fma of float32 values is the float64 product and sum rounded once to float32: the
-    product of two float32 is exact in float64, and the double rounding of the sum is what this check allows for)"""
-    f32 = np.float32
-    idx, inside = frame_index(len(x), sp.n_fft, sp.hop_length)
-    fr = (np.where(inside, x[idx], f32(0)) * sp.window[None, :]).astype(f32)               # [T, n_fft]
-    X = np.zeros((fr.shape[0], 2 * sp.n_bins), dtype=f32)
-    basis = sp.basis.astype(np.float64)
-    for n in range(sp.n_fft):
-        X = (fr[:, n:n + 1].astype(np.float64) * basis[n][None, :] + X.astype(np.float64)).astype(f32)
-    re, im = X[:, :sp.n_bins].astype(np.float64), X[:, sp.n_bins:].astype(np.float64)
-    P = (re * re + (im * im).astype(f32).astype(np.float64)).astype(f32)
-    M = np.zeros((fr.shape[0], sp.n_mels), dtype=f32)
-    fb = sp.fb.astype(np.float64)
-    for k in range(sp.n_bins):
-        M = (P[:, k:k + 1].astype(np.float64) * fb[:, k][None, :] + M.astype(np.float64)).astype(f32)
-    return M.T
+float32_serial = logmel_host_f32           # the specification in plain float32, one operation at a time (features.py)
 
 
-@pytest.mark.parametrize("n_fft,hop,n_mels,L", SHAPES)
+@pytest.mark.parametrize("n_fft,hop,n_mels,L", SHAPES + GRID)
 def test_a_float32_evaluation_stays_inside_the_bound(n_fft, hop, n_mels, L):
+    """(On the grid a filter may be all zeros -- no bin between its points: there M = dM = 0 and the evaluation gives 0; the
+    bound is asserted positive and below 0.1 M on all other elements, which on SHAPES are all.  The grid's noise is the first
+    row of what tests/test_features_paths.py gives the kernel.)"""
     sp = LogMel(16000, n_fft, hop, n_mels, log=None)
-    rng = np.random.default_rng(n_fft + 1)
+    rng = np.random.default_rng(n_fft + ((n_fft, hop, n_mels, L) in SHAPES))
     tone = np.sin(2 * np.pi * (n_fft // 8) * np.arange(L) / n_fft).astype(np.float32)
+    empty = (sp.fb == 0).all(axis=1)
+    assert not empty.any() or (n_fft, hop, n_mels, L) in GRID
     for name, x in (("noise", rng.uniform(-1, 1, L).astype(np.float32)), ("tone", tone)):
         M, dM = logmel_host(x, sp, bound=True)
-        err = np.abs(float32_serial(x, sp).astype(np.float64) - M)
+        got = float32_serial(x, sp)
+        err = np.abs(got.astype(np.float64) - M)
         ratio = np.max(err / np.maximum(dM, 1e-300))
         print(f"({n_fft},{hop},{n_mels}) {name}: max err / dM {ratio:.3f}")
         assert (err <= dM).all()
-        assert (dM > 0).all() and (dM <= 0.1 * M).all() if name == "noise" else True
+        assert (M[empty] == 0).all() and (dM[empty] == 0).all() and (got[empty] == 0).all()
+        assert (dM[~empty] > 0).all() and (dM[~empty] <= 0.1 * M[~empty]).all() if name == "noise" else True
     # the centre tap dropped is outside the bound in most elements: it does not hide a bug
     x = rng.uniform(-1, 1, L).astype(np.float32)
     M, dM = logmel_host(x, sp, bound=True)
@@ -206,7 +222,7 @@ def test_a_float32_evaluation_stays_inside_the_bound(n_fft, hop, n_mels, L):
     w = np.array(broken.window)
     w[n_fft // 2] = 0.0
     object.__setattr__(broken, "window", w)
-    assert (np.abs(logmel_host(x, broken) - M) > dM).mean() > 0.5
+    assert (np.abs(logmel_host(x, broken) - M) > dM)[~empty].mean() > 0.5
 
 
 def test_crops_take_features_and_keep_their_other_arguments():
@@ -220,3 +236,152 @@ def test_crops_take_features_and_keep_their_other_arguments():
         assert list(p)[:7] == head and p["features"].default is None
         assert p["sample_rate"].default is None and p["mono"].default is False
     assert pkg.log_mel and pkg.LogMel is LogMel and pkg.mel_filterbank is mel_filterbank and pkg.logmel_host is logmel_host
+
+
+def _broken(sp, window=None, fb=None):
+    """sp with one of its tables replaced (a specification with a bug in it)"""
+    b = LogMel(16000, sp.n_fft, sp.hop_length, sp.n_mels, log=None)
+    for name, table in (("window", window), ("fb", fb)):
+        if table is not None:
+            object.__setattr__(b, name, table)
+    return b
+
+
+def _mutations(sp):
+    """name -> a broken specification, tables changed only: (a) the last tap dropped; (b) the first bin of the second block of
+    32 removed from every filter, as a round of the mel chain that starts one bin late would (None where there is one block);
+    (c) the tap nearest either end whose window weight is at least 1e-3 dropped, and its mirror image at the front"""
+    w = np.array(sp.window)
+    last = sp.n_fft - 1 - int(np.argmax(w[::-1] >= 1e-3))
+    first = int(np.argmax(w >= 1e-3))
+    assert w[last] >= 1e-3 and (w[last + 1:] < 1e-3).all() and sp.n_fft - 1 - last <= first
+    out = {}
+    for name, taps in (("a", [sp.n_fft - 1]), ("c", [last]), ("c front", [first])):
+        v = w.copy()
+        v[taps] = 0.0
+        out[name] = _broken(sp, window=v)
+    out["b"] = None
+    if sp.n_bins > 32:
+        fb = np.array(sp.fb)
+        assert (fb[:, 32] > 0).any()
+        fb[:, 32] = 0.0
+        out["b"] = _broken(sp, fb=fb)
+    return out
+
+
+# What the bound dM alone (tests/test_features.py before the twin) makes of each mutation: True = it is blind to it, the broken
+# evaluation is inside dM in every element.  Measured here, with the reasons:
+#   (400, 160, 80): dM / M is 0.5 to 1.6 %, a tap of weight 6e-5 (a) or 1.5e-3 (c) moves the power by less.  A whole bin gone from
+#   the two filters that hold it (b) is far outside.
+#   (126, 64, 33) and (25, 10, 8): dM / M is below 1e-3 with so short a chain of roundings, and the last tap weighs 6e-4 and
+#   1.6e-2: the bound sees a lost tap already.  (25, 10, 8) has 13 bins, one block: (b) does not exist there, so (126, 64, 33),
+#   the smallest grid shape with a second block, stands in for it.
+BLIND = {(400, 160, 80, 5000): {"a": True, "b": False, "c": True, "c front": True},
+         (126, 64, 33, 1500): {"a": False, "b": False, "c": False, "c front": False},
+         (25, 10, 8, 333): {"a": False, "b": None, "c": False, "c front": False}}
+
+
+@pytest.mark.parametrize("shape", list(BLIND))
+def test_the_twin_sees_what_the_bound_does_not(shape):
+    """A float32 evaluation of a specification with one table entry wrong, against the true M: every mutation is outside
+    4 r_ref, r_ref the twin's own max err / dM on the same input, so the test of r_gpu <= 4 r_ref fails a kernel that has it.
+    At the working size the lost taps are inside dM in every element -- the bound alone passes them.  BLIND says where the
+    bound is blind and where it is not, and why."""
+    n_fft, hop, n_mels, L = shape
+    sp = LogMel(16000, n_fft, hop, n_mels, log=None)
+    x = np.random.default_rng(n_fft + 1).uniform(-1, 1, L).astype(np.float32)
+    M, dM = logmel_host(x, sp, bound=True)
+    r_ref = float(np.max(np.abs(logmel_host_f32(x, sp) - M) / dM))
+    assert 0 < r_ref < 0.25                                     # 4 r_ref is inside the bound: the yardstick is the tighter one
+    seen_only_by_the_twin = 0
+    for name, broken in _mutations(sp).items():
+        assert (broken is None) == (BLIND[shape][name] is None)
+        if broken is None:
+            continue
+        err = np.abs(logmel_host_f32(x, broken) - M)
+        ratio = float(np.max(err / dM))
+        inside = bool((err <= dM).all())
+        print(f"({n_fft},{hop},{n_mels}) {name}: inside dM {inside}, max err / dM {ratio:.4f} against 4 r_ref = {4 * r_ref:.4f}")
+        assert inside == BLIND[shape][name], name
+        assert ratio > 4 * r_ref, name
+        seen_only_by_the_twin += inside
+    assert seen_only_by_the_twin == sum(v is True for v in BLIND[shape].values())
+
+
+def test_the_grid_is_what_it_claims():
+    """Every branch GRID names, from the constants of alac_features.h and alac_features.hip: a later change of one of them
+    cannot quietly turn two entries into duplicates."""
+    from test_features import header_constant, kernel_blocks, kernel_lds_bytes, kernel_tile
+
+    tile, block, per_round = (header_constant("ALAC_FEATURES_" + n) for n in ("TILE", "BLOCK", "ROUND_BLOCKS"))
+    ahead = header_constant("AHEAD", "alac_features.hip")
+    assert (tile, block, per_round, ahead) == (32, 32, 8, 8)
+    assert len(set(GRID)) == len(GRID) and not set(GRID) & set(SHAPES)
+
+    def facts(n_fft, hop, n_mels, L):
+        T = 1 + L // hop
+        return dict(left=(n_fft // 2) % ahead, half=n_fft % 2, blocks=kernel_blocks(n_fft), clamped=(n_fft // 2 + 1) % block != 0,
+                    tile=kernel_tile(n_fft, hop), tiles=-(-T // kernel_tile(n_fft, hop)), frames=T,
+                    empty=int((LogMel(16000, n_fft, hop, n_mels).fb == 0).all(axis=1).sum()))
+
+    want = {
+        (16, 2, 1, 50): dict(left=0, half=0, blocks=1),
+        (18, 3, 5, 60): dict(left=1, half=0),
+        (20, 20, 7, 130): dict(left=2, half=0, empty=1),
+        (17, 5, 3, 70): dict(left=0, half=1),
+        (33, 16, 9, 200): dict(left=0, half=1),
+        (62, 31, 12, 700): dict(blocks=1, clamped=False),
+        (126, 64, 33, 1500): dict(blocks=2, clamped=False),
+        (63, 7, 12, 300): dict(blocks=1, clamped=False, half=1),
+        (402, 161, 80, 3000): dict(left=1, half=0, blocks=7),
+        (401, 160, 80, 3000): dict(left=0, half=1, blocks=7),
+        (510, 255, 40, 4000): dict(blocks=per_round, clamped=False),
+        (1000, 250, 100, 5000): dict(left=4, blocks=2 * per_round, clamped=True),
+        (1022, 2, 8, 600): dict(blocks=2 * per_round, clamped=False, frames=301, tiles=10),
+        (1024, 1024, 17, 6000): dict(blocks=2 * per_round + 1, tile=19),
+        (2046, 1024, 255, 9000): dict(left=7, blocks=4 * per_round, clamped=False, tile=18),
+        (2048, 560, 256, 20000): dict(tile=tile, tiles=2, blocks=4 * per_round + 1),
+        (2048, 561, 256, 20000): dict(tile=tile, tiles=2),
+        (2048, 562, 256, 20000): dict(tile=tile - 1, tiles=2),
+        (2048, 580, 256, 20000): dict(tile=tile - 1, tiles=2),
+        (400, 160, 256, 3000): dict(empty=45),
+    }
+    assert set(want) == set(GRID)
+    for shape, claims in want.items():
+        got = facts(*shape)
+        assert {k: got[k] for k in claims} == claims, shape
+    # every even n_fft of SHAPES has n_fft / 2 divisible by AHEAD, none of its n_bins is a multiple of the block: what the grid adds
+    assert all(facts(*s)["left"] == 0 and facts(*s)["clamped"] for s in SHAPES if s[0] % 2 == 0)
+    # the layouts: 561 is the last hop with a full tile at n_fft 2048; 560 has the largest layout of all full tiles (an even hop
+    # is skewed), and the largest of all is a shortened tile; all fit a CU's LDS
+    most, lds_max = header_constant("ALAC_FEATURES_MAX_SPAN"), header_constant("ALAC_FEATURES_LDS_MAX")
+    assert (tile - 1) * 561 + 2048 <= most < (tile - 1) * 562 + 2048
+    sizes = {(n_fft, hop): kernel_lds_bytes(n_fft, hop, 256) for n_fft in (2047, 2048) for hop in range(1, n_fft + 1)}
+    full = {k: v for k, v in sizes.items() if kernel_tile(*k) == tile}
+    assert max(full, key=full.get) == (2048, 560) and full[2048, 560] == 151500
+    assert max(sizes, key=sizes.get) == (2048, 580) and sizes[2048, 580] == 151656 <= lds_max == 160 << 10
+
+
+def test_what_is_not_finite_stays_in_its_frames_and_is_never_hidden():
+    """The specification on a NaN and on an infinity (features.py): NaN in every element of the frames with a tap on it -- the
+    tap of weight zero too -- with and without a log; every other frame is bit for bit the clean signal's."""
+    n_fft, hop, L, i = 400, 160, 4000, 2050
+    x = np.random.default_rng(2).uniform(-1, 1, L).astype(np.float32)
+    t = np.arange(1 + L // hop)
+    hit = (t * hop - n_fft // 2 <= i) & (i < t * hop - n_fft // 2 + n_fft)
+    assert t[hit].tolist() == [12, 13, 14]
+    for log in (None, "ln", "log10"):
+        sp = LogMel(16000, log=log)
+        clean = logmel_host(x, sp)
+        for bad in (np.nan, np.inf, -np.inf):
+            y = x.copy()
+            y[i] = bad
+            with np.errstate(invalid="ignore"):
+                got = logmel_host(y, sp)
+            assert np.isnan(got[:, hit]).all() and np.array_equal(got[:, ~hit], clean[:, ~hit])
+    # the tap of weight zero: frame 14 starts on sample 2040
+    y = x.copy()
+    y[14 * hop - n_fft // 2] = np.inf
+    with np.errstate(invalid="ignore"):
+        got = logmel_host(y, LogMel(16000))
+    assert np.isnan(got[:, 12:15]).all() and np.isfinite(got[:, :12]).all() and np.isfinite(got[:, 15:]).all()

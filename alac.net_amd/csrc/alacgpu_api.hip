@@ -1,110 +1,48 @@
-// alacgpu_api.hip -- C ABI of include/alacgpu.h on top of the gfx950 kernels.
-// No CPU fallback anywhere in this file: every decode goes through alac_decode_ab_kernel / alac_decode_ab32_kernel.
+// alacgpu_api.hip -- C ABI of include/alacgpu.h, the decode path: lifecycle, launch slots, the device and the host-buffer decodes
+// (the stages around them: alacgpu_stages.hip).  No CPU fallback: every decode goes through alac_decode_ab_kernel / alac_decode_ab32_kernel.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <cmath>
-#include <cstddef>
-
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
 #include <new>
-#include <string>
 #include <thread>
 #include <vector>
 
-#include "alac_corpus.h"
-#include "alac_resample.h"
-#include "alac_features.h"
-#include "alac_encode.h"
-#include "alac_kernels.h"
-#include "alacgpu.h"
+#include "alacgpu_ctx.h"
 #include "alacgpu_ranges.h"
 
 static_assert(sizeof(alacgpu_cfg) == sizeof(alacgpu_cfg_dev), "cfg layouts must match");
 
-namespace {
+// What alacgpu_stages.hip uses too (alacgpu_ctx.h declares them).
+// Smax: the longest frame any stream cfg declares, at most MAX_FRAME
+uint32_t smax(const alacgpu_ctx* ctx) {
+    uint32_t s = 1;
+    for (uint32_t i = 0; i < ctx->n_cfgs; i++) s = std::max(s, std::min(ctx->h_cfgs[i].max_samples_per_frame, MAX_FRAME));
+    return s;
+}
 
-constexpr int N_SLOTS = 8;          // launch pairs that may be in flight at once on one ctx (any streams)
-constexpr uint32_t AB_SMALL_MAX_PACKETS = 4096;  // up to here: the build with 16-step speculative units (latency-bound launches)
-constexpr uint32_t AB5_MIN_PACKETS = 10241;     // above: the 96-register build of the 8-packet arrangement (five workgroups per CU)
-constexpr uint32_t DENSE_MIN_PACKETS = 12289;   // measured cross-over of the two arrangements of the main kernel
-constexpr int N_HOST_STREAMS = 4;   // chunks of the host-buffer pipeline (H2D k+1 || decode k || D2H k-1)
-constexpr uint32_t MAX_FRAME = 16384;   // the longest frame the reference decodes (its scratch, AlacFile.cs:28)
+// A PCM tensor view (decode-into and encode): one or two channels, interleaved or planar with a plane stride, int32 or
+// float32, and 4-byte aligned.
+bool pcm_view_ok(const void* d_pcm, uint32_t channels, int layout, int dtype, uint64_t plane_stride) {
+    return (channels == 1 || channels == 2) && (layout == ALACGPU_DST_INTERLEAVED || layout == ALACGPU_DST_PLANAR) &&
+           (dtype == ALACGPU_DST_INT32 || dtype == ALACGPU_DST_FLOAT32) && (layout != ALACGPU_DST_PLANAR || plane_stride != 0) &&
+           args_ok({{d_pcm, 4, false}});
+}
 
-// ALACGPU_DENSE (A/B and tests): which build of the first launch runs.  Auto picks by batch size; "eight" picks among the
-// builds of the 8-packet arrangement by batch size; the others force one build whatever the batch size.
-enum dense_mode { DENSE_AUTO = -1, DENSE_EIGHT = 0, DENSE_ALWAYS = 1, DENSE_FORCE_AB5 = 2, DENSE_FORCE_SMALL = 3, DENSE_FORCE_AB = 4 };
-
-// What one launch pair (alac_decode_ab_kernel + alac_decode_ab32_kernel) owns while it is in flight: the group flags the
-// first kernel hands to the second, and the events that bracket the pair.  A slot is reused only after its last launch
-// has finished (hipEventSynchronize), so calls on different streams never share flags.
-struct launch_slot {
-    uint32_t* d_flags = nullptr;
-    size_t flags_bytes = 0;
-    int32_t* d_park = nullptr;     // destination mode: where channel A waits (n_packets * park_stride ints, grown on demand)
-    size_t park_bytes = 0;
-    uint64_t* d_first = nullptr;   // window calls: dst_first as alac_window_first_kernel leaves it (n_packets, grown on demand)
-    size_t first_bytes = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool used = false;
-};
-
-}  // namespace
-
-struct alacgpu_ctx {
-    int device = 0;
-    uint32_t n_cfgs = 0;
-    alacgpu_cfg* h_cfgs = nullptr;
-    alacgpu_cfg_dev* d_cfgs = nullptr;
-    hipStream_t streams[N_HOST_STREAMS] = {};   // used by the host-buffer entry points: range k decodes (and downloads) on streams[k]
-    hipStream_t up_stream = nullptr;            // ... and every upload runs on this one, range after range
-    hipEvent_t ev_up[N_HOST_STREAMS] = {};   // range k's packets (and, for k = 0, the batch's metadata) are in HBM
-    launch_slot slots[N_SLOTS];
-    unsigned next_slot = 0;
-    int last_slot = -1;
-    uint32_t out_format = 0;           // 0 int32 per sample, 1 packed little-endian PCM
-    int host_chunks = 0;               // 0 auto; 1..N_HOST_STREAMS forced (ALACGPU_HOST_CHUNKS, A/B only)
-    int dense = DENSE_AUTO;            // the first launch's build (dense_mode, ALACGPU_DENSE)
-    uint32_t* d_cu_arrivals = nullptr; // per-CU workgroup counters (alac_decode_params::cu_arrivals): ONE array per device, shared by
-                                       // every context of the process on it (cu_counters_acquire), so that launches of different
-                                       // contexts take their turns on a CU from the same counter
-    bool zero_copy = true;             // host-buffer entry points store straight into page-locked output (ALACGPU_ZERO_COPY=0: A/B)
-    // grow-only device workspace for the host-buffer entry points
-    void* d_ws = nullptr;
-    size_t ws_bytes = 0;
-    int32_t* h_frame = nullptr;        // pinned staging of alacgpu_decode_frame (one slot of the widest kind)
-    // alacgpu_encode_device: one workspace slot per workgroup of a round (codes and bit positions, grown on demand), and the
-    // event behind the last call's launches (the next call's stream waits for it before it reuses the workspace)
-    uint64_t* d_enc_code = nullptr;    // slots * alac_enc_items(smax) codes
-    uint32_t* d_enc_pos = nullptr;     // ... and as many bit positions, plus one per slot
-    size_t enc_code_bytes = 0, enc_pos_bytes = 0;
-    hipEvent_t enc_done = nullptr;
-    bool enc_used = false;
-    // alacgpu_compact_packets_device: the partial sums of the scan's upper levels (grown on demand, kept for reuse) and the
-    // event behind the last call's launches, as for the encoder's workspace
-    uint64_t* d_scan = nullptr;
-    size_t scan_bytes = 0;
-    hipEvent_t scan_done = nullptr;
-    bool scan_used = false;
-    std::string last_error;
-};
+// pcm_out .. + bytes is page-locked host memory the device can store into: its device-side address, else null
+void* device_view_of_pinned(const void* host, size_t bytes) {
+    if (bytes == 0) return nullptr;
+    hipPointerAttribute_t a0, a1;
+    if (hipPointerGetAttributes(&a0, host) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (hipPointerGetAttributes(&a1, (const char*)host + bytes - 1) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (a0.type != hipMemoryTypeHost || a1.type != hipMemoryTypeHost || !a0.devicePointer || !a1.devicePointer) return nullptr;
+    if ((const char*)a1.devicePointer - (const char*)a0.devicePointer != (ptrdiff_t)(bytes - 1)) return nullptr;   // one mapping
+    return a0.devicePointer;
+}
 
 namespace {
-
-#define HIP_TRY(ctx, expr)                                                                      \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) {                                                                 \
-            (ctx)->last_error = std::string(#expr) + ": " + hipGetErrorString(e_);              \
-            return ALACGPU_ERR_HIP;                                                             \
-        }                                                                                       \
-    } while (0)
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-void* device_view_of_pinned(const void* host, size_t bytes);   // (below, with the host-buffer entry points)
 
 // The per-CU turn counters of a device (see alac_decode_params::cu_arrivals), reference-counted per process: two contexts on
 // one GPU -- two-in-flight from two contexts, alacgpu_decode_batch_sharded rehearsed on one device -- must not each believe
@@ -130,19 +68,6 @@ void cu_counters_release(int device) {
         if (it->second.d) (void)hipFree(it->second.d);
         g_cu_by_device.erase(it);
     }
-}
-
-// A grow-only device buffer: when need_bytes exceed the have_bytes that p holds, p is freed and alloc_bytes allocated (the
-// caller has waited for every user of the old buffer and chooses the slack).
-template <class T>
-int grow(alacgpu_ctx* ctx, T*& p, size_t& have_bytes, size_t need_bytes, size_t alloc_bytes) {
-    if (need_bytes <= have_bytes) return ALACGPU_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    have_bytes = 0;
-    HIP_TRY(ctx, hipMalloc((void**)&p, alloc_bytes));
-    have_bytes = alloc_bytes;
-    return ALACGPU_OK;
 }
 
 int ensure_ws(alacgpu_ctx* ctx, size_t bytes) {
@@ -244,10 +169,8 @@ int launch(alacgpu_ctx* ctx, const alac_decode_params& p_in, hipStream_t stream)
 int fill_params(alacgpu_ctx* ctx, alac_decode_params& p, const void* d_blob, uint64_t blob_bytes, const void* d_offsets,
                 const void* d_sizes, const void* d_cfg_idx, uint32_t n_packets, void* d_pcm_out, uint32_t slot_ints,
                 void* d_out_bytes, void* d_out_samples, void* d_status, uint32_t out_format) {
-    if (!d_blob || !d_offsets || !d_sizes || !d_pcm_out || !d_status || slot_ints == 0) return ALACGPU_ERR_BAD_ARG;
-    if (((uintptr_t)d_blob & 15u) != 0 || ((uintptr_t)d_offsets & 7u) != 0 || ((uintptr_t)d_sizes & 3u) != 0 ||
-        ((uintptr_t)d_pcm_out & 3u) != 0 || ((uintptr_t)d_status & 3u) != 0 || ((uintptr_t)d_cfg_idx & 1u) != 0 ||
-        ((uintptr_t)d_out_bytes & 3u) != 0 || ((uintptr_t)d_out_samples & 3u) != 0)
+    if (!args_ok({{d_blob, 16}, {d_offsets, 8}, {d_sizes, 4}, {d_cfg_idx, 2, false}, {d_pcm_out, 4}, {d_out_bytes, 4, false},
+                  {d_out_samples, 4, false}, {d_status, 4}}) || slot_ints == 0)
         return ALACGPU_ERR_BAD_ARG;
     p = alac_decode_params{};
     p.blob = (const uint8_t*)d_blob;
@@ -267,21 +190,6 @@ int fill_params(alacgpu_ctx* ctx, alac_decode_params& p, const void* d_blob, uin
     return ALACGPU_OK;
 }
 
-// Smax: the longest frame any stream cfg declares, at most MAX_FRAME
-uint32_t smax(const alacgpu_ctx* ctx) {
-    uint32_t s = 1;
-    for (uint32_t i = 0; i < ctx->n_cfgs; i++) s = std::max(s, std::min(ctx->h_cfgs[i].max_samples_per_frame, MAX_FRAME));
-    return s;
-}
-
-// A PCM tensor view (decode-into and encode): one or two channels, interleaved or planar with a plane stride, int32 or
-// float32, and 4-byte aligned.
-bool pcm_view_ok(const void* d_pcm, uint32_t channels, int layout, int dtype, uint64_t plane_stride) {
-    return (channels == 1 || channels == 2) && (layout == ALACGPU_DST_INTERLEAVED || layout == ALACGPU_DST_PLANAR) &&
-           (dtype == ALACGPU_DST_INT32 || dtype == ALACGPU_DST_FLOAT32) && (layout != ALACGPU_DST_PLANAR || plane_stride != 0) &&
-           ((uintptr_t)d_pcm & 3u) == 0;
-}
-
 // bytes per sample the packed format can put into a slot (2 or 3; the widest stream cfg decides)
 size_t packed_bytes_per_slot_int(const alacgpu_ctx* ctx) {
     size_t bps = 2;
@@ -290,6 +198,125 @@ size_t packed_bytes_per_slot_int(const alacgpu_ctx* ctx) {
         bps = std::max(bps, (size_t)std::min(std::max(ss / 8, 2), 4));
     }
     return bps;
+}
+
+// Host buffers: the batch is cut into contiguous packet ranges (two by default, up to four), each on its own stream, so that
+// the H2D copy of range k+1, the decode of range k and the D2H copy of range k-1 overlap (the two copy directions use
+// different DMA engines).  Issue order: all uploads and launches first, then the downloads in range order.
+int decode_host(alacgpu_ctx* ctx, const uint8_t* blob, uint64_t blob_bytes, const uint64_t* offsets, const uint32_t* sizes,
+                const uint16_t* cfg_idx, uint32_t n_packets, int32_t* pcm_out, uint32_t slot_ints, int32_t* out_bytes,
+                int32_t* out_samples, int32_t* status, uint32_t out_format) {
+    if (n_packets == 0) return ALACGPU_OK;
+    if (!blob || !offsets || !sizes || !pcm_out || !status || slot_ints == 0) return ALACGPU_ERR_BAD_ARG;
+    // measured on cfg2 (4096 packets, tools/host_path_rate.py): 1 / 2 / 4 ranges = 4.20 / 3.97 / 4.05 ms with int32 output,
+    // 2.99 / 2.63 / 3.21 ms packed: the link runs at 55 GB/s either way (134 MiB of int32 PCM alone are 2.5 ms), the copies
+    // from and to ordinary memory block the issuing thread, and a range's decode takes as long as the whole batch's (four
+    // ranges were measured too: 3.64 / 2.61 ms against 3.56 / 2.39 with two, cfg2, page-locked buffers)
+    int nch = ctx->host_chunks ? ctx->host_chunks : (n_packets >= 1024u ? 2 : 1);
+    nch = std::min<int>(nch, (int)n_packets);
+    // validate, and find the blob range every chunk needs
+    uint32_t lo[N_HOST_STREAMS + 1];
+    uint64_t b0[N_HOST_STREAMS], b1[N_HOST_STREAMS];
+    for (int k = 0; k <= nch; k++) lo[k] = (uint32_t)alacgpu::group_cut(n_packets, k, nch);
+    uint64_t range_sum = 0;
+    for (int k = 0; k < nch; k++) {
+        b0[k] = blob_bytes;
+        b1[k] = 0;
+        for (uint32_t i = lo[k]; i < lo[k + 1]; i++) {
+            if (offsets[i] > blob_bytes || (uint64_t)sizes[i] > blob_bytes - offsets[i]) return ALACGPU_ERR_BAD_ARG;
+            b0[k] = std::min(b0[k], offsets[i]);
+            b1[k] = std::max(b1[k], offsets[i] + sizes[i]);
+        }
+        if (b1[k] < b0[k]) b0[k] = b1[k] = 0;
+        b0[k] &= ~(uint64_t)15;
+        range_sum += b1[k] - b0[k];
+    }
+    if (nch > 1 && range_sum > blob_bytes + blob_bytes / 2) {   // packets not laid out in batch order: one upload
+        nch = 1;
+        lo[1] = n_packets;
+        b0[0] = 0;
+        b1[0] = blob_bytes;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // Page-locked output (alacgpu_alloc_pinned, hipHostMalloc, hipHostRegister ...): the kernels store the PCM straight into
+    // the caller's memory -- the link carries it WHILE the batch decodes (50 GB/s measured: a cfg2 batch's 134 MB of int32 PCM
+    // in 2.7 ms, its 67 MB of packed PCM in 1.4 ms) and there is no download behind the decode.  Channel A is then parked in
+    // device memory (a read-back across the link would cost more than the decode).
+    int32_t* const zc_pcm = ctx->zero_copy ? (int32_t*)device_view_of_pinned(pcm_out, sizeof(int32_t) * (size_t)n_packets * slot_ints) : nullptr;
+    const uint32_t park_stride = (slot_ints + 1u) / 2u;
+    // workspace carve-up (all 256-byte aligned)
+    const size_t blob_sz = align_up(blob_bytes + 64, 256);
+    const size_t off_sz = align_up(sizeof(uint64_t) * n_packets, 256);
+    const size_t sz_sz = align_up(sizeof(uint32_t) * n_packets, 256);
+    const size_t ci_sz = align_up(sizeof(uint16_t) * n_packets, 256);
+    const size_t i32_sz = align_up(sizeof(int32_t) * n_packets, 256);
+    const size_t pcm_sz = align_up(sizeof(int32_t) * (size_t)n_packets * (zc_pcm ? park_stride : slot_ints), 256);
+    int rc = ensure_ws(ctx, blob_sz + off_sz + sz_sz + ci_sz + 3 * i32_sz + pcm_sz);
+    if (rc) return rc;
+    uint8_t* w = (uint8_t*)ctx->d_ws;
+    uint8_t* d_blob = w; w += blob_sz;
+    uint64_t* d_off = (uint64_t*)w; w += off_sz;
+    uint32_t* d_sz = (uint32_t*)w; w += sz_sz;
+    uint16_t* d_ci = (uint16_t*)w; w += ci_sz;
+    int32_t* d_ob = (int32_t*)w; w += i32_sz;
+    int32_t* d_os = (int32_t*)w; w += i32_sz;
+    int32_t* d_st = (int32_t*)w; w += i32_sz;
+    int32_t* d_pcm = (int32_t*)w;
+    if (!ctx->up_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->up_stream, hipStreamNonBlocking));
+    hipStream_t s0 = ctx->up_stream;
+    HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, sizeof(uint64_t) * n_packets, hipMemcpyHostToDevice, s0));
+    HIP_TRY(ctx, hipMemcpyAsync(d_sz, sizes, sizeof(uint32_t) * n_packets, hipMemcpyHostToDevice, s0));
+    if (cfg_idx) HIP_TRY(ctx, hipMemcpyAsync(d_ci, cfg_idx, sizeof(uint16_t) * n_packets, hipMemcpyHostToDevice, s0));
+    for (int k = 1; k < nch; k++)
+        if (!ctx->streams[k]) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->streams[k], hipStreamNonBlocking));
+    // Every upload goes through ONE stream, range after range (uploads issued on several streams run side by side and share the
+    // link: all of them would finish together, at the end); range k's decode waits for its own upload only, so the first
+    // range decodes -- and with page-locked output writes its PCM across the link, which is full duplex -- while the others
+    // are still on their way up.
+    for (int k = 0; k < nch; k++)
+        if (!ctx->ev_up[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_up[k], hipEventDisableTiming));
+    for (int k = 0; k < nch; k++) {
+        hipStream_t s = ctx->streams[k];
+        const uint32_t cnt = lo[k + 1] - lo[k];
+        if (cnt == 0) continue;
+        // (upload k, then launch k, then upload k + 1: a copy from ordinary memory blocks this thread while it is staged)
+        if (b1[k] > b0[k]) HIP_TRY(ctx, hipMemcpyAsync(d_blob + b0[k], blob + b0[k], b1[k] - b0[k], hipMemcpyHostToDevice, s0));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_up[k], s0));
+        HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_up[k], 0));
+        alac_decode_params p;
+        rc = fill_params(ctx, p, d_blob, blob_bytes, d_off + lo[k], d_sz + lo[k], cfg_idx ? d_ci + lo[k] : nullptr, cnt,
+                         (zc_pcm ? zc_pcm : d_pcm) + (size_t)lo[k] * slot_ints, slot_ints, d_ob + lo[k], d_os + lo[k], d_st + lo[k],
+                         out_format);
+        if (rc) return rc;
+        if (zc_pcm) {   // channel A waits in device memory
+            p.park = d_pcm + (size_t)lo[k] * park_stride;
+            p.park_stride = park_stride;
+        }
+        if ((rc = launch(ctx, p, s))) return rc;
+    }
+    const size_t pitch = sizeof(int32_t) * (size_t)slot_ints;
+    const size_t packed_w = std::min(pitch, packed_bytes_per_slot_int(ctx) * (size_t)slot_ints);
+    for (int k = 0; k < nch; k++) {
+        hipStream_t s = ctx->streams[k];
+        const uint32_t cnt = lo[k + 1] - lo[k];
+        if (cnt == 0) continue;
+        int32_t* dst = pcm_out + (size_t)lo[k] * slot_ints;
+        const int32_t* src = d_pcm + (size_t)lo[k] * slot_ints;
+        if (zc_pcm) {
+            // nothing to download: the kernels wrote into the caller's memory
+        } else if (out_format == ALACGPU_OUT_PACKED_LE) {
+            // a slot holds at most slot_ints samples of (ctor sample size / 8) bytes: copy that much of every slot
+            HIP_TRY(ctx, hipMemcpy2DAsync(dst, pitch, src, pitch, packed_w, cnt, hipMemcpyDeviceToHost, s));
+        } else {
+            HIP_TRY(ctx, hipMemcpyAsync(dst, src, pitch * cnt, hipMemcpyDeviceToHost, s));
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(status + lo[k], d_st + lo[k], sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, s));
+        if (out_bytes) HIP_TRY(ctx, hipMemcpyAsync(out_bytes + lo[k], d_ob + lo[k], sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, s));
+        if (out_samples) HIP_TRY(ctx, hipMemcpyAsync(out_samples + lo[k], d_os + lo[k], sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, s));
+    }
+    for (int k = 0; k < nch; k++)
+        if (ctx->streams[k]) HIP_TRY(ctx, hipStreamSynchronize(ctx->streams[k]));
+    return ALACGPU_OK;
 }
 
 }  // namespace
@@ -413,13 +440,8 @@ void alacgpu_destroy(alacgpu_ctx* ctx) {
         if (sl.ev1) (void)hipEventDestroy(sl.ev1);
     }
     if (ctx->d_ws) (void)hipFree(ctx->d_ws);
-    if (ctx->enc_used) (void)hipEventSynchronize(ctx->enc_done);
-    if (ctx->enc_done) (void)hipEventDestroy(ctx->enc_done);
-    if (ctx->d_enc_code) (void)hipFree(ctx->d_enc_code);
-    if (ctx->d_enc_pos) (void)hipFree(ctx->d_enc_pos);
-    if (ctx->scan_used) (void)hipEventSynchronize(ctx->scan_done);
-    if (ctx->scan_done) (void)hipEventDestroy(ctx->scan_done);
-    if (ctx->d_scan) (void)hipFree(ctx->d_scan);
+    ctx->enc.destroy();
+    ctx->scan.destroy();
     if (ctx->d_cu_arrivals) cu_counters_release(ctx->device);
     if (ctx->h_frame) (void)hipHostFree(ctx->h_frame);
     if (ctx->d_cfgs) (void)hipFree(ctx->d_cfgs);
@@ -478,8 +500,8 @@ int alacgpu_decode_window_into_device(alacgpu_ctx* ctx, const void* d_blob, uint
                                       const void* d_dst_frames, const void* d_src_skip, void* d_out, uint64_t out_elems,
                                       uint32_t channels, int layout, int dtype, uint64_t plane_stride, void* d_out_samples,
                                       void* d_status, void* hip_stream) {
-    if (!ctx || !d_dst_first || !d_dst_frames || !pcm_view_ok(d_out, channels, layout, dtype, plane_stride)) return ALACGPU_ERR_BAD_ARG;
-    if (((uintptr_t)d_dst_first & 7u) != 0 || ((uintptr_t)d_dst_frames & 3u) != 0 || ((uintptr_t)d_src_skip & 3u) != 0)
+    if (!ctx || !args_ok({{d_dst_first, 8}, {d_dst_frames, 4}, {d_src_skip, 4, false}}) ||
+        !pcm_view_ok(d_out, channels, layout, dtype, plane_stride))
         return ALACGPU_ERR_BAD_ARG;
     // statuses as in the slot layout with slot_ints = channels * Smax, and channel A parks in Smax ints per packet
     const uint32_t s = smax(ctx);
@@ -508,628 +530,6 @@ int alacgpu_decode_into_device(alacgpu_ctx* ctx, const void* d_blob, uint64_t bl
                                              d_out_samples, d_status, hip_stream);
 }
 
-// Both planner entry points; each: every crop has a window length of its own, d_crop_frames[n_crops]
-static int plan_crops(alacgpu_ctx* ctx, const void* d_pkt_offset, const void* d_pkt_size, const void* d_pkt_end,
-                      const void* d_file_first, const void* d_file_cfg, uint32_t n_files, const void* d_crop_file,
-                      const void* d_crop_offset, bool each, const void* d_crop_frames, uint32_t n_crops, uint32_t crop_frames,
-                      uint32_t entries_per_crop, uint64_t dst_stride, void* d_offsets, void* d_sizes, void* d_cfg_idx,
-                      void* d_dst_first, void* d_dst_frames, void* d_src_skip, void* d_lengths, void* hip_stream) {
-    if (!ctx) return ALACGPU_ERR_BAD_ARG;
-    if (n_crops == 0) return ALACGPU_OK;
-    if (entries_per_crop == 0 || (uint64_t)n_crops * entries_per_crop > 0xFFFFFFFFull) return ALACGPU_ERR_BAD_ARG;
-    if (!d_pkt_offset || !d_pkt_size || !d_pkt_end || !d_file_first || !d_file_cfg || !d_crop_file || !d_crop_offset ||
-        !d_offsets || !d_sizes || !d_cfg_idx || !d_dst_first || !d_dst_frames || !d_src_skip || !d_lengths)
-        return ALACGPU_ERR_BAD_ARG;
-    if (((uintptr_t)d_pkt_offset & 7u) != 0 || ((uintptr_t)d_pkt_size & 3u) != 0 || ((uintptr_t)d_pkt_end & 7u) != 0 ||
-        ((uintptr_t)d_file_first & 3u) != 0 || ((uintptr_t)d_file_cfg & 1u) != 0 || ((uintptr_t)d_crop_file & 3u) != 0 ||
-        ((uintptr_t)d_crop_offset & 7u) != 0 || ((uintptr_t)d_offsets & 7u) != 0 || ((uintptr_t)d_sizes & 3u) != 0 ||
-        ((uintptr_t)d_cfg_idx & 1u) != 0 || ((uintptr_t)d_dst_first & 7u) != 0 || ((uintptr_t)d_dst_frames & 3u) != 0 ||
-        ((uintptr_t)d_src_skip & 3u) != 0 || ((uintptr_t)d_lengths & 7u) != 0)
-        return ALACGPU_ERR_BAD_ARG;
-    if (each && (!d_crop_frames || ((uintptr_t)d_crop_frames & 3u) != 0)) return ALACGPU_ERR_BAD_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    alac_plan_params p;
-    p.pkt_offset = (const uint64_t*)d_pkt_offset;
-    p.pkt_size = (const uint32_t*)d_pkt_size;
-    p.pkt_end = (const uint64_t*)d_pkt_end;
-    p.file_first = (const uint32_t*)d_file_first;
-    p.file_cfg = (const uint16_t*)d_file_cfg;
-    p.n_files = n_files;
-    p.crop_file = (const uint32_t*)d_crop_file;
-    p.crop_offset = (const uint64_t*)d_crop_offset;
-    p.n_crops = n_crops;
-    p.crop_frames = crop_frames;
-    p.crop_frames_each = each ? (const uint32_t*)d_crop_frames : nullptr;
-    p.entries_per_crop = entries_per_crop;
-    p.dst_stride = dst_stride;
-    p.offsets = (uint64_t*)d_offsets;
-    p.sizes = (uint32_t*)d_sizes;
-    p.cfg_idx = (uint16_t*)d_cfg_idx;
-    p.dst_first = (uint64_t*)d_dst_first;
-    p.dst_frames = (uint32_t*)d_dst_frames;
-    p.src_skip = (uint32_t*)d_src_skip;
-    p.lengths = (int64_t*)d_lengths;
-    constexpr uint32_t per_wg = ALAC_PLAN_THREADS / 64;   // one wave per crop
-    void* kargs[] = {&p};
-    const void* const kernel = each ? (const void*)alac_plan_crops_frames_kernel : (const void*)alac_plan_crops_kernel;
-    HIP_TRY(ctx, hipLaunchKernel(kernel, dim3((n_crops + per_wg - 1u) / per_wg), dim3(ALAC_PLAN_THREADS), kargs, 0,
-                                 (hipStream_t)hip_stream));
-    HIP_TRY(ctx, hipGetLastError());
-    return ALACGPU_OK;
-}
-
-int alacgpu_plan_crops_device(alacgpu_ctx* ctx, const void* d_pkt_offset, const void* d_pkt_size, const void* d_pkt_end,
-                              const void* d_file_first, const void* d_file_cfg, uint32_t n_files, const void* d_crop_file,
-                              const void* d_crop_offset, uint32_t n_crops, uint32_t crop_frames, uint32_t entries_per_crop,
-                              uint64_t dst_stride, void* d_offsets, void* d_sizes, void* d_cfg_idx, void* d_dst_first,
-                              void* d_dst_frames, void* d_src_skip, void* d_lengths, void* hip_stream) {
-    return plan_crops(ctx, d_pkt_offset, d_pkt_size, d_pkt_end, d_file_first, d_file_cfg, n_files, d_crop_file, d_crop_offset, false,
-                      nullptr, n_crops, crop_frames, entries_per_crop, dst_stride, d_offsets, d_sizes, d_cfg_idx, d_dst_first,
-                      d_dst_frames, d_src_skip, d_lengths, hip_stream);
-}
-
-int alacgpu_plan_crops_frames_device(alacgpu_ctx* ctx, const void* d_pkt_offset, const void* d_pkt_size, const void* d_pkt_end,
-                                     const void* d_file_first, const void* d_file_cfg, uint32_t n_files, const void* d_crop_file,
-                                     const void* d_crop_offset, const void* d_crop_frames, uint32_t n_crops, uint32_t crop_frames,
-                                     uint32_t entries_per_crop, uint64_t dst_stride, void* d_offsets, void* d_sizes,
-                                     void* d_cfg_idx, void* d_dst_first, void* d_dst_frames, void* d_src_skip, void* d_lengths,
-                                     void* hip_stream) {
-    return plan_crops(ctx, d_pkt_offset, d_pkt_size, d_pkt_end, d_file_first, d_file_cfg, n_files, d_crop_file, d_crop_offset, true,
-                      d_crop_frames, n_crops, crop_frames, entries_per_crop, dst_stride, d_offsets, d_sizes, d_cfg_idx, d_dst_first,
-                      d_dst_frames, d_src_skip, d_lengths, hip_stream);
-}
-
-// The exclusive scan both alacgpu_compact_packets_device and alacgpu_stage_packets_device begin with: s0 holds the sizes, how
-// they count, `add`, `out` and `total`; the two kernels are the level-0 pair that counts that way.  The levels: the sizes, the
-// sums of their tiles, the sums of those sums' tiles (at most 1024 for 2^32 - 1 packets), in the ctx's scratch.
-static int scan_sizes(alacgpu_ctx* ctx, alac_scan_params<uint32_t> s0, const void* sums_kernel, const void* tiles_kernel, hipStream_t stream) {
-    const uint64_t t1 = (s0.n + ALAC_SCAN_TILE - 1u) / ALAC_SCAN_TILE;
-    const uint64_t t2 = (t1 + ALAC_SCAN_TILE - 1u) / ALAC_SCAN_TILE;
-    const size_t need = t1 > 1 ? sizeof(uint64_t) * (size_t)(t1 + t2) : 0;
-    if (!ctx->scan_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->scan_done, hipEventDisableTiming));
-    if (need > ctx->scan_bytes) {
-        if (ctx->scan_used) HIP_TRY(ctx, hipEventSynchronize(ctx->scan_done));   // the last call has finished with it
-        int rc = grow(ctx, ctx->d_scan, ctx->scan_bytes, need, align_up(need + need / 4, 4096));
-        if (rc) return rc;
-    } else if (need && ctx->scan_used) {
-        HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->scan_done, 0));             // (a call on another stream may still use it)
-    }
-    uint64_t* const l1 = ctx->d_scan;
-    uint64_t* const l2 = l1 ? l1 + t1 : nullptr;
-    s0.sums = l1;
-    s0.tile_base = t1 > 1 ? l1 : nullptr;
-    const dim3 block(ALAC_SCAN_THREADS);
-    if (t1 > 1) {
-        alac_scan_params<uint64_t> s1 = {};
-        s1.in = l1;
-        s1.n = t1;
-        s1.slot_bytes = 0;
-        s1.sums = l2;
-        s1.tile_base = t2 > 1 ? l2 : nullptr;
-        s1.add = 0;
-        s1.out = l1;
-        s1.total = nullptr;
-        void* a0[] = {&s0};
-        void* a1[] = {&s1};
-        HIP_TRY(ctx, hipLaunchKernel(sums_kernel, dim3((uint32_t)t1), block, a0, 0, stream));
-        if (t2 > 1) {
-            alac_scan_params<uint64_t> s2 = s1;          // t2 <= 1024: one tile
-            s2.in = l2;
-            s2.n = t2;
-            s2.sums = nullptr;
-            s2.tile_base = nullptr;
-            s2.out = l2;
-            void* a2[] = {&s2};
-            HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_sums_u64_kernel, dim3((uint32_t)t2), block, a1, 0, stream));
-            HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_tiles_u64_kernel, dim3(1), block, a2, 0, stream));
-        }
-        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_tiles_u64_kernel, dim3((uint32_t)t2), block, a1, 0, stream));
-    }
-    void* a0[] = {&s0};
-    HIP_TRY(ctx, hipLaunchKernel(tiles_kernel, dim3((uint32_t)t1), block, a0, 0, stream));
-    return ALACGPU_OK;
-}
-
-int alacgpu_compact_packets_device(alacgpu_ctx* ctx, const void* d_packets, uint64_t slot_bytes, const void* d_sizes,
-                                   uint32_t n_packets, void* d_blob, uint64_t base, uint64_t blob_capacity,
-                                   void* d_pkt_offset, void* d_total, void* hip_stream) {
-    if (!ctx || !d_total || ((uintptr_t)d_total & 7u) != 0 || slot_bytes == 0 || (slot_bytes & 15u) != 0) return ALACGPU_ERR_BAD_ARG;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (n_packets == 0) {
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipMemsetAsync(d_total, 0, sizeof(uint64_t), stream));
-        return ALACGPU_OK;
-    }
-    if (!d_packets || !d_sizes || !d_blob || !d_pkt_offset) return ALACGPU_ERR_BAD_ARG;
-    if (((uintptr_t)d_packets & 15u) != 0 || ((uintptr_t)d_sizes & 3u) != 0 || ((uintptr_t)d_pkt_offset & 7u) != 0)
-        return ALACGPU_ERR_BAD_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    alac_scan_params<uint32_t> s0 = {};
-    s0.in = (const uint32_t*)d_sizes;
-    s0.n = n_packets;
-    s0.slot_bytes = slot_bytes;
-    s0.add = base;
-    s0.out = (uint64_t*)d_pkt_offset;
-    s0.total = (uint64_t*)d_total;
-    int rc = scan_sizes(ctx, s0, (const void*)alac_scan_sums_u32_kernel, (const void*)alac_scan_tiles_u32_kernel, stream);
-    if (rc) return rc;
-    // the copy: tiles of the destination, as many as the packets can fill at most (the true end is d_total's, on the device)
-    const uint64_t most = slot_bytes > UINT64_MAX / n_packets ? UINT64_MAX : slot_bytes * n_packets;
-    const uint64_t room = blob_capacity > base ? blob_capacity - base : 0;
-    const uint64_t bound = std::min(most, room);
-    if (bound) {
-        alac_copy_params c;
-        c.packets = (const uint8_t*)d_packets;
-        c.slot_bytes = slot_bytes;
-        c.sizes = (const uint32_t*)d_sizes;
-        c.pkt_offset = (const uint64_t*)d_pkt_offset;
-        c.total = (const uint64_t*)d_total;
-        c.n_packets = n_packets;
-        c.blob = (uint8_t*)d_blob;
-        c.base = base;
-        c.capacity = blob_capacity;
-        const uint64_t tiles = bound / ALAC_COPY_TILE + 2u;   // (a tile more for the bytes in front of the first aligned chunk)
-        void* ac[] = {&c};
-        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_compact_copy_kernel, dim3((uint32_t)std::min<uint64_t>(tiles, 1u << 16)),
-                                     dim3(ALAC_COPY_THREADS), ac, 0, stream));
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->scan_done, stream));
-    ctx->scan_used = true;
-    return ALACGPU_OK;
-}
-
-int alacgpu_stage_packets_device(alacgpu_ctx* ctx, const void* d_blob_lo, uint64_t lo_bytes, const void* blob_hi, uint64_t hi_bytes,
-                                 const void* d_src_offset, const void* d_sizes, uint32_t n_packets, void* d_stage,
-                                 uint64_t stage_capacity, void* d_stage_offset, void* d_total, void* hip_stream) {
-    if (!ctx || !d_total || ((uintptr_t)d_total & 7u) != 0) return ALACGPU_ERR_BAD_ARG;
-    if ((!d_blob_lo && lo_bytes) || (!blob_hi && hi_bytes) || ((uintptr_t)d_blob_lo & 15u) != 0 || ((uintptr_t)blob_hi & 15u) != 0)
-        return ALACGPU_ERR_BAD_ARG;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (n_packets == 0) {
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipMemsetAsync(d_total, 0, sizeof(uint64_t), stream));
-        return ALACGPU_OK;
-    }
-    if (!d_src_offset || !d_sizes || !d_stage || !d_stage_offset) return ALACGPU_ERR_BAD_ARG;
-    if (((uintptr_t)d_src_offset & 7u) != 0 || ((uintptr_t)d_sizes & 3u) != 0 || ((uintptr_t)d_stage & 15u) != 0 ||
-        ((uintptr_t)d_stage_offset & 7u) != 0 || lo_bytes > UINT64_MAX - hi_bytes)
-        return ALACGPU_ERR_BAD_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the second part as the kernels address it: device memory as it is, page-locked host memory by its device view
-    const void* hi_view = nullptr;
-    if (hi_bytes) {
-        hipPointerAttribute_t a;
-        if (hipPointerGetAttributes(&a, blob_hi) != hipSuccess) { (void)hipGetLastError(); return ALACGPU_ERR_BAD_ARG; }
-        hi_view = a.type == hipMemoryTypeDevice ? blob_hi : device_view_of_pinned(blob_hi, (size_t)hi_bytes);
-        if (!hi_view) return ALACGPU_ERR_BAD_ARG;
-    }
-    alac_scan_params<uint32_t> s0 = {};
-    s0.in = (const uint32_t*)d_sizes;
-    s0.n = n_packets;
-    s0.src_offset = (const uint64_t*)d_src_offset;
-    s0.lo_bytes = lo_bytes;
-    s0.hi_bytes = hi_bytes;
-    s0.out = (uint64_t*)d_stage_offset;
-    s0.total = (uint64_t*)d_total;
-    int rc = scan_sizes(ctx, s0, (const void*)alac_scan_sums_stage_kernel, (const void*)alac_scan_tiles_stage_kernel, stream);
-    if (rc) return rc;
-    // the copy: tiles of the staging blob, as many as its capacity holds (the true end is d_total's, on the device)
-    if (stage_capacity >= 16u) {
-        alac_stage_params c;
-        c.lo = (const uint8_t*)d_blob_lo;
-        c.hi = (const uint8_t*)hi_view;
-        c.lo_bytes = lo_bytes;
-        c.hi_bytes = hi_bytes;
-        c.src_offset = (const uint64_t*)d_src_offset;
-        c.sizes = (const uint32_t*)d_sizes;
-        c.stage_offset = (const uint64_t*)d_stage_offset;
-        c.total = (const uint64_t*)d_total;
-        c.n_packets = n_packets;
-        c.stage = (uint8_t*)d_stage;
-        c.capacity = stage_capacity;
-        const uint64_t tiles = stage_capacity / ALAC_STAGE_TILE + 1u;
-        void* ac[] = {&c};
-        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_stage_copy_kernel, dim3((uint32_t)std::min<uint64_t>(tiles, 1u << 16)),
-                                     dim3(ALAC_STAGE_THREADS), ac, 0, stream));
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->scan_done, stream));
-    ctx->scan_used = true;
-    return ALACGPU_OK;
-}
-
-// The tile of a resample launch: as many output frames as leave a CU room for two workgroups, down to 256; fewer only where the
-// span of 256 does not fit the CU at all (a / b in the hundreds) -- one frame's span, 2 width + 2, always fits next to the table.
-// lds_bytes(tile): the dynamic LDS a workgroup needs for that tile.
-extern "C++" {
-template <class F>
-static uint32_t resample_tile(const F& lds_bytes) {
-    uint32_t tile = ALAC_RESAMPLE_MAX_TILE;
-    while (tile > 256u && lds_bytes(tile) > ALAC_RESAMPLE_LDS_PREFERRED) tile /= 2u;
-    while (tile > 1u && lds_bytes(tile) > ALAC_RESAMPLE_LDS_MAX) tile /= 2u;
-    return tile;
-}
-}
-
-// The grid: a workgroup takes up to eight consecutive tiles with one load of the table, while a thousand workgroups remain.
-// false: 2^31 tiles of output or more.
-static bool resample_grid(uint64_t out_frames, uint32_t tile, uint64_t planes, uint32_t& per_wg, uint32_t& blocks) {
-    const uint64_t tiles = (out_frames + tile - 1u) / tile;
-    if (tiles > 0xFFFFFFFFull || tiles * planes > 0x7FFFFFFFull) return false;
-    const uint64_t n = std::min<uint64_t>(std::max<uint64_t>(tiles * planes / 1024u, 1u), std::min<uint64_t>(tiles, ALAC_RESAMPLE_MAX_TILES_PER_WG));
-    per_wg = (uint32_t)n;
-    blocks = (uint32_t)((tiles + n - 1u) / n * planes);
-    return true;
-}
-
-int alacgpu_resample_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,
-                            const void* d_src_origin, const void* d_src_valid, const void* d_out_first, uint64_t out_frames,
-                            uint32_t a, uint32_t b, uint32_t width, const void* d_d0, const void* d_weights, int mono, void* d_out,
-                            void* hip_stream) {
-    if (!ctx || !d_src || !d_src_origin || !d_src_valid || !d_out_first || !d_d0 || !d_weights || !d_out) return ALACGPU_ERR_BAD_ARG;
-    if (((uintptr_t)d_src & 3u) != 0 || ((uintptr_t)d_src_origin & 7u) != 0 || ((uintptr_t)d_src_valid & 7u) != 0 ||
-        ((uintptr_t)d_out_first & 7u) != 0 || ((uintptr_t)d_d0 & 3u) != 0 || ((uintptr_t)d_weights & 3u) != 0 ||
-        ((uintptr_t)d_out & 3u) != 0)
-        return ALACGPU_ERR_BAD_ARG;
-    if (a == 0 || b == 0 || width == 0 || channels < 1 || channels > 2) return ALACGPU_ERR_BAD_ARG;
-    const uint64_t table = (uint64_t)b * (2u * (uint64_t)width + 1u);
-    if (table > ALAC_RESAMPLE_MAX_TABLE) return ALACGPU_ERR_BAD_ARG;
-    if (rows == 0 || out_frames == 0) return ALACGPU_OK;
-    const auto lds_bytes = [&](uint64_t tile) { return sizeof(float) * (size_t)(((table + 3u) & ~3ull) + alac_resample_span(tile, a, b, width)); };
-    const uint32_t tile = resample_tile(lds_bytes);
-    const size_t lds = lds_bytes(tile);
-    uint32_t per_wg, blocks;
-    if (!resample_grid(out_frames, tile, (uint64_t)rows * (mono ? 1u : channels), per_wg, blocks)) return ALACGPU_ERR_BAD_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (lds > ALAC_RESAMPLE_LDS_PREFERRED)
-        HIP_TRY(ctx, hipFuncSetAttribute((const void*)alac_resample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    alac_resample_params p;
-    p.src = (const float*)d_src;
-    p.src_stride = src_stride;
-    p.src_origin = (const int64_t*)d_src_origin;
-    p.src_valid = (const int64_t*)d_src_valid;
-    p.out_first = (const int64_t*)d_out_first;
-    p.out = (float*)d_out;
-    p.out_frames = out_frames;
-    p.d0 = (const int32_t*)d_d0;
-    p.weights = (const float*)d_weights;
-    p.a = a;
-    p.b = b;
-    p.width = width;
-    p.channels = channels;
-    p.mono = mono ? 1u : 0u;
-    p.tile = tile;
-    p.span = (uint32_t)alac_resample_span(tile, a, b, width);
-    p.tiles_per_wg = per_wg;
-    void* kargs[] = {&p};
-    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_resample_kernel, dim3(blocks), dim3(ALAC_RESAMPLE_THREADS), kargs, lds,
-                                 (hipStream_t)hip_stream));
-    HIP_TRY(ctx, hipGetLastError());
-    return ALACGPU_OK;
-}
-
-static_assert(sizeof(alacgpu_resample_table) == sizeof(alac_resample_table) && offsetof(alacgpu_resample_table, weights_first) ==
-              offsetof(alac_resample_table, weights_first), "the kernel reads the header's table descriptors as they are");
-
-int alacgpu_resample_rows_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,
-                                 const void* d_src_origin, const void* d_src_valid, const void* d_out_first, uint64_t out_frames,
-                                 const alacgpu_resample_table* tables, const void* d_tables, uint32_t n_tables, const void* d_d0,
-                                 const void* d_weights, const void* d_row_table, int mono, void* d_out, void* hip_stream) {
-    if (!ctx || !d_src || !d_src_origin || !d_src_valid || !d_out_first || !tables || !d_tables || !d_d0 || !d_weights ||
-        !d_row_table || !d_out)
-        return ALACGPU_ERR_BAD_ARG;
-    if (((uintptr_t)d_src & 3u) != 0 || ((uintptr_t)d_src_origin & 7u) != 0 || ((uintptr_t)d_src_valid & 7u) != 0 ||
-        ((uintptr_t)d_out_first & 7u) != 0 || ((uintptr_t)tables & 3u) != 0 || ((uintptr_t)d_tables & 3u) != 0 || ((uintptr_t)d_d0 & 3u) != 0 ||
-        ((uintptr_t)d_weights & 3u) != 0 || ((uintptr_t)d_row_table & 3u) != 0 || ((uintptr_t)d_out & 3u) != 0)
-        return ALACGPU_ERR_BAD_ARG;
-    if (n_tables == 0 || channels < 1 || channels > 2) return ALACGPU_ERR_BAD_ARG;
-    for (uint32_t t = 0; t < n_tables; t++) {
-        const alacgpu_resample_table& d = tables[t];
-        if (d.a == 0 || d.b == 0 || d.width == 0 || (uint64_t)d.b * (2u * (uint64_t)d.width + 1u) > ALAC_RESAMPLE_MAX_TABLE)
-            return ALACGPU_ERR_BAD_ARG;
-    }
-    if (rows == 0 || out_frames == 0) return ALACGPU_OK;
-    // one tile for the launch, and the LDS of the table that needs the most for it; a workgroup uses its own table's span
-    const auto lds_bytes = [&](uint64_t tile) {
-        uint64_t most = 0;
-        for (uint32_t t = 0; t < n_tables; t++) {
-            const alacgpu_resample_table& d = tables[t];
-            const uint64_t table = (uint64_t)d.b * (2u * (uint64_t)d.width + 1u);
-            most = std::max<uint64_t>(most, ((table + 3u) & ~3ull) + alac_resample_span(tile, d.a, d.b, d.width));
-        }
-        return sizeof(float) * (size_t)most;
-    };
-    const uint32_t tile = resample_tile(lds_bytes);
-    const size_t lds = lds_bytes(tile);
-    uint32_t per_wg, blocks;
-    if (!resample_grid(out_frames, tile, (uint64_t)rows * (mono ? 1u : channels), per_wg, blocks)) return ALACGPU_ERR_BAD_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (lds > ALAC_RESAMPLE_LDS_PREFERRED)
-        HIP_TRY(ctx, hipFuncSetAttribute((const void*)alac_resample_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    alac_resample_rows_params p;
-    p.src = (const float*)d_src;
-    p.src_stride = src_stride;
-    p.src_origin = (const int64_t*)d_src_origin;
-    p.src_valid = (const int64_t*)d_src_valid;
-    p.out_first = (const int64_t*)d_out_first;
-    p.out = (float*)d_out;
-    p.out_frames = out_frames;
-    p.tables = (const alac_resample_table*)d_tables;
-    p.d0 = (const int32_t*)d_d0;
-    p.weights = (const float*)d_weights;
-    p.row_table = (const uint32_t*)d_row_table;
-    p.n_tables = n_tables;
-    p.channels = channels;
-    p.mono = mono ? 1u : 0u;
-    p.tile = tile;
-    p.lds_floats = (uint32_t)(lds / sizeof(float));
-    p.tiles_per_wg = per_wg;
-    void* kargs[] = {&p};
-    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_resample_rows_kernel, dim3(blocks), dim3(ALAC_RESAMPLE_THREADS), kargs, lds,
-                                 (hipStream_t)hip_stream));
-    HIP_TRY(ctx, hipGetLastError());
-    return ALACGPU_OK;
-}
-
-int alacgpu_logmel_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,
-                          uint64_t frames, uint32_t n_fft, uint32_t hop, uint32_t n_mels, const void* d_window,
-                          const void* d_basis, const void* d_fb, int log_mode, float floor, void* d_out, uint64_t out_frames,
-                          void* hip_stream) {
-    if (!ctx || !d_src || !d_window || !d_basis || !d_fb || !d_out) return ALACGPU_ERR_BAD_ARG;
-    if (((uintptr_t)d_src & 3u) != 0 || ((uintptr_t)d_window & 3u) != 0 || ((uintptr_t)d_basis & 3u) != 0 ||
-        ((uintptr_t)d_fb & 3u) != 0 || ((uintptr_t)d_out & 3u) != 0)
-        return ALACGPU_ERR_BAD_ARG;
-    if (n_fft < ALAC_FEATURES_MIN_NFFT || n_fft > ALAC_FEATURES_MAX_NFFT || hop < 1 || hop > n_fft || n_mels < 1 ||
-        n_mels > ALAC_FEATURES_MAX_MELS || channels == 0)
-        return ALACGPU_ERR_BAD_ARG;
-    if (!(floor > 0.0f) || !std::isfinite(floor)) return ALACGPU_ERR_BAD_ARG;
-    if (log_mode != ALAC_FEATURES_LOG_NONE && log_mode != ALAC_FEATURES_LOG_LN && log_mode != ALAC_FEATURES_LOG_10) return ALACGPU_ERR_BAD_ARG;
-    if (frames <= n_fft / 2u || frames > src_stride || frames > (1ull << 62) || out_frames != 1u + frames / hop) return ALACGPU_ERR_BAD_ARG;
-    const uint32_t tile = alac_features_tile(n_fft, hop);
-    const uint64_t tiles = (out_frames + tile - 1u) / tile;
-    if (tiles > 0x7FFFFFFFull || tiles * channels > 0x7FFFFFFFull || tiles * channels * rows > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
-    if (rows == 0) return ALACGPU_OK;
-    const size_t lds = alac_features_lds_layout(n_fft, hop, n_mels).bytes();
-    if (lds > ALAC_FEATURES_LDS_MAX) return ALACGPU_ERR_BAD_ARG;    // (the limits above keep every layout below it)
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (lds > ALAC_FEATURES_LDS_DEFAULT)
-        HIP_TRY(ctx, hipFuncSetAttribute((const void*)alac_logmel_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    alac_features_params p;
-    p.src = (const float*)d_src;
-    p.src_stride = src_stride;
-    p.frames = frames;
-    p.out = (float*)d_out;
-    p.out_frames = out_frames;
-    p.window = (const float*)d_window;
-    p.basis = (const float*)d_basis;
-    p.fb = (const float*)d_fb;
-    p.n_fft = n_fft;
-    p.hop = hop;
-    p.n_mels = n_mels;
-    p.tile = tile;
-    p.tiles = (uint32_t)tiles;
-    p.log_mode = (uint32_t)log_mode;
-    p.floor = floor;
-    void* kargs[] = {&p};
-    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_logmel_kernel, dim3((uint32_t)(tiles * channels * rows)), dim3(ALAC_FEATURES_THREADS),
-                                 kargs, lds, (hipStream_t)hip_stream));
-    HIP_TRY(ctx, hipGetLastError());
-    return ALACGPU_OK;
-}
-
-size_t alacgpu_encode_max_packet_bytes(uint32_t frames, int sample_size, int channels) {
-    // an escape packet with its sample count: header 23 + 32 bits, the raw samples, the END tag
-    const uint64_t bits = 23u + 32u + (uint64_t)frames * (uint64_t)(channels < 1 ? 1 : channels) * (uint64_t)(sample_size < 0 ? 0 : sample_size) + 3u;
-    return (size_t)align_up((bits + 7) / 8, 16);
-}
-
-int alacgpu_encode_device(alacgpu_ctx* ctx, const void* d_pcm, uint64_t src_elems, uint32_t channels, int layout, int dtype,
-                          uint64_t plane_stride, const void* d_src_first, const void* d_src_frames, const void* d_cfg_idx,
-                          uint32_t n_packets, void* d_packets, uint64_t slot_bytes, void* d_sizes, void* d_status,
-                          void* hip_stream) {
-    if (!ctx || !d_pcm || !d_src_first || !d_src_frames || !d_cfg_idx || !d_packets || !d_sizes || !d_status)
-        return ALACGPU_ERR_BAD_ARG;
-    if (!pcm_view_ok(d_pcm, channels, layout, dtype, plane_stride)) return ALACGPU_ERR_BAD_ARG;
-    if (((uintptr_t)d_src_first & 7u) != 0 || ((uintptr_t)d_src_frames & 3u) != 0 ||
-        ((uintptr_t)d_cfg_idx & 1u) != 0 || ((uintptr_t)d_packets & 15u) != 0 || (slot_bytes & 15u) != 0 ||
-        ((uintptr_t)d_sizes & 3u) != 0 || ((uintptr_t)d_status & 3u) != 0)
-        return ALACGPU_ERR_BAD_ARG;
-    for (uint32_t i = 0; i < ctx->n_cfgs; i++) {
-        const alacgpu_cfg& c = ctx->h_cfgs[i];
-        if (c.num_channels != channels) return ALACGPU_ERR_BAD_ARG;
-        const uint32_t frames = std::min(c.max_samples_per_frame, MAX_FRAME);
-        if (slot_bytes < alacgpu_encode_max_packet_bytes(frames, c.sample_size, (int)channels)) return ALACGPU_ERR_BAD_ARG;
-    }
-    if (n_packets == 0) return ALACGPU_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t stream = (hipStream_t)hip_stream;
-    // a round: up to 16 workgroups per CU, one packet and one workspace slot each
-    int n_cu = 0;
-    HIP_TRY(ctx, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    const uint32_t round = std::min<uint32_t>(n_packets, (uint32_t)std::max(n_cu, 1) * 16u);
-    const uint32_t frames = smax(ctx);
-    const size_t items = (size_t)round * alac_enc_items(frames);
-    const size_t code_bytes = sizeof(uint64_t) * items, pos_bytes = sizeof(uint32_t) * (items + round);
-    if (!ctx->enc_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->enc_done, hipEventDisableTiming));
-    if (code_bytes > ctx->enc_code_bytes || pos_bytes > ctx->enc_pos_bytes) {
-        if (ctx->enc_used) HIP_TRY(ctx, hipEventSynchronize(ctx->enc_done));   // the last call has finished with it
-        int rc = grow(ctx, ctx->d_enc_code, ctx->enc_code_bytes, code_bytes, code_bytes);
-        if (rc) return rc;
-        if ((rc = grow(ctx, ctx->d_enc_pos, ctx->enc_pos_bytes, pos_bytes, pos_bytes))) return rc;
-    } else if (ctx->enc_used) {
-        HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->enc_done, 0));   // (a call on another stream may still use it)
-    }
-    alac_encode_params p;
-    p.pcm = d_pcm;
-    p.src_elems = src_elems;
-    p.plane_stride = layout == ALACGPU_DST_PLANAR ? plane_stride : 0;
-    p.channels = channels;
-    p.layout = (uint32_t)layout;
-    p.dtype = (uint32_t)dtype;
-    p.n_packets = n_packets;
-    p.src_first = (const uint64_t*)d_src_first;
-    p.src_frames = (const uint32_t*)d_src_frames;
-    p.cfg_idx = (const uint16_t*)d_cfg_idx;
-    p.cfgs = ctx->d_cfgs;
-    p.n_cfgs = ctx->n_cfgs;
-    p.smax = frames;
-    p.packets = (uint8_t*)d_packets;
-    p.slot_bytes = slot_bytes;
-    p.sizes = (uint32_t*)d_sizes;
-    p.status = (int32_t*)d_status;
-    p.ws_code = ctx->d_enc_code;
-    p.ws_pos = ctx->d_enc_pos;
-    for (uint32_t first = 0; first < n_packets; first += round) {
-        p.first_packet = first;
-        alac_encode_params args = p;
-        void* kargs[] = {&args};
-        const dim3 grid(std::min(round, n_packets - first)), block(ALAC_ENC_THREADS);
-        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_encode_analyse_kernel, grid, block, kargs, 0, stream));
-        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_encode_codes_kernel, grid, block, kargs, 0, stream));
-        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_encode_emit_kernel, grid, block, kargs, 0, stream));
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->enc_done, stream));
-    ctx->enc_used = true;
-    return ALACGPU_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// pcm_out .. + bytes is page-locked host memory the device can store into: its device-side address, else null
-void* device_view_of_pinned(const void* host, size_t bytes) {
-    if (bytes == 0) return nullptr;
-    hipPointerAttribute_t a0, a1;
-    if (hipPointerGetAttributes(&a0, host) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    if (hipPointerGetAttributes(&a1, (const char*)host + bytes - 1) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    if (a0.type != hipMemoryTypeHost || a1.type != hipMemoryTypeHost || !a0.devicePointer || !a1.devicePointer) return nullptr;
-    if ((const char*)a1.devicePointer - (const char*)a0.devicePointer != (ptrdiff_t)(bytes - 1)) return nullptr;   // one mapping
-    return a0.devicePointer;
-}
-
-// Host buffers: the batch is cut into contiguous packet ranges (two by default, up to four), each on its own stream, so that
-// the H2D copy of range k+1, the decode of range k and the D2H copy of range k-1 overlap (the two copy directions use
-// different DMA engines).  Issue order: all uploads and launches first, then the downloads in range order.
-int decode_host(alacgpu_ctx* ctx, const uint8_t* blob, uint64_t blob_bytes, const uint64_t* offsets, const uint32_t* sizes,
-                const uint16_t* cfg_idx, uint32_t n_packets, int32_t* pcm_out, uint32_t slot_ints, int32_t* out_bytes,
-                int32_t* out_samples, int32_t* status, uint32_t out_format) {
-    if (n_packets == 0) return ALACGPU_OK;
-    if (!blob || !offsets || !sizes || !pcm_out || !status || slot_ints == 0) return ALACGPU_ERR_BAD_ARG;
-    // measured on cfg2 (4096 packets, tools/host_path_rate.py): 1 / 2 / 4 ranges = 4.20 / 3.97 / 4.05 ms with int32 output,
-    // 2.99 / 2.63 / 3.21 ms packed: the link runs at 55 GB/s either way (134 MiB of int32 PCM alone are 2.5 ms), the copies
-    // from and to ordinary memory block the issuing thread, and a range's decode takes as long as the whole batch's (four
-    // ranges were measured too: 3.64 / 2.61 ms against 3.56 / 2.39 with two, cfg2, page-locked buffers)
-    int nch = ctx->host_chunks ? ctx->host_chunks : (n_packets >= 1024u ? 2 : 1);
-    nch = std::min<int>(nch, (int)n_packets);
-    // validate, and find the blob range every chunk needs
-    uint32_t lo[N_HOST_STREAMS + 1];
-    uint64_t b0[N_HOST_STREAMS], b1[N_HOST_STREAMS];
-    for (int k = 0; k <= nch; k++) lo[k] = (uint32_t)alacgpu::group_cut(n_packets, k, nch);
-    uint64_t range_sum = 0;
-    for (int k = 0; k < nch; k++) {
-        b0[k] = blob_bytes;
-        b1[k] = 0;
-        for (uint32_t i = lo[k]; i < lo[k + 1]; i++) {
-            if (offsets[i] > blob_bytes || (uint64_t)sizes[i] > blob_bytes - offsets[i]) return ALACGPU_ERR_BAD_ARG;
-            b0[k] = std::min(b0[k], offsets[i]);
-            b1[k] = std::max(b1[k], offsets[i] + sizes[i]);
-        }
-        if (b1[k] < b0[k]) b0[k] = b1[k] = 0;
-        b0[k] &= ~(uint64_t)15;
-        range_sum += b1[k] - b0[k];
-    }
-    if (nch > 1 && range_sum > blob_bytes + blob_bytes / 2) {   // packets not laid out in batch order: one upload
-        nch = 1;
-        lo[1] = n_packets;
-        b0[0] = 0;
-        b1[0] = blob_bytes;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // Page-locked output (alacgpu_alloc_pinned, hipHostMalloc, hipHostRegister ...): the kernels store the PCM straight into
-    // the caller's memory -- the link carries it WHILE the batch decodes (50 GB/s measured: a cfg2 batch's 134 MB of int32 PCM
-    // in 2.7 ms, its 67 MB of packed PCM in 1.4 ms) and there is no download behind the decode.  Channel A is then parked in
-    // device memory (a read-back across the link would cost more than the decode).
-    int32_t* const zc_pcm = ctx->zero_copy ? (int32_t*)device_view_of_pinned(pcm_out, sizeof(int32_t) * (size_t)n_packets * slot_ints) : nullptr;
-    const uint32_t park_stride = (slot_ints + 1u) / 2u;
-    // workspace carve-up (all 256-byte aligned)
-    const size_t blob_sz = align_up(blob_bytes + 64, 256);
-    const size_t off_sz = align_up(sizeof(uint64_t) * n_packets, 256);
-    const size_t sz_sz = align_up(sizeof(uint32_t) * n_packets, 256);
-    const size_t ci_sz = align_up(sizeof(uint16_t) * n_packets, 256);
-    const size_t i32_sz = align_up(sizeof(int32_t) * n_packets, 256);
-    const size_t pcm_sz = align_up(sizeof(int32_t) * (size_t)n_packets * (zc_pcm ? park_stride : slot_ints), 256);
-    int rc = ensure_ws(ctx, blob_sz + off_sz + sz_sz + ci_sz + 3 * i32_sz + pcm_sz);
-    if (rc) return rc;
-    uint8_t* w = (uint8_t*)ctx->d_ws;
-    uint8_t* d_blob = w; w += blob_sz;
-    uint64_t* d_off = (uint64_t*)w; w += off_sz;
-    uint32_t* d_sz = (uint32_t*)w; w += sz_sz;
-    uint16_t* d_ci = (uint16_t*)w; w += ci_sz;
-    int32_t* d_ob = (int32_t*)w; w += i32_sz;
-    int32_t* d_os = (int32_t*)w; w += i32_sz;
-    int32_t* d_st = (int32_t*)w; w += i32_sz;
-    int32_t* d_pcm = (int32_t*)w;
-    if (!ctx->up_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->up_stream, hipStreamNonBlocking));
-    hipStream_t s0 = ctx->up_stream;
-    HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, sizeof(uint64_t) * n_packets, hipMemcpyHostToDevice, s0));
-    HIP_TRY(ctx, hipMemcpyAsync(d_sz, sizes, sizeof(uint32_t) * n_packets, hipMemcpyHostToDevice, s0));
-    if (cfg_idx) HIP_TRY(ctx, hipMemcpyAsync(d_ci, cfg_idx, sizeof(uint16_t) * n_packets, hipMemcpyHostToDevice, s0));
-    for (int k = 1; k < nch; k++)
-        if (!ctx->streams[k]) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->streams[k], hipStreamNonBlocking));
-    // Every upload goes through ONE stream, range after range (uploads issued on several streams run side by side and share the
-    // link: all of them would finish together, at the end); range k's decode waits for its own upload only, so the first
-    // range decodes -- and with page-locked output writes its PCM across the link, which is full duplex -- while the others
-    // are still on their way up.
-    for (int k = 0; k < nch; k++)
-        if (!ctx->ev_up[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_up[k], hipEventDisableTiming));
-    for (int k = 0; k < nch; k++) {
-        hipStream_t s = ctx->streams[k];
-        const uint32_t cnt = lo[k + 1] - lo[k];
-        if (cnt == 0) continue;
-        // (upload k, then launch k, then upload k + 1: a copy from ordinary memory blocks this thread while it is staged)
-        if (b1[k] > b0[k]) HIP_TRY(ctx, hipMemcpyAsync(d_blob + b0[k], blob + b0[k], b1[k] - b0[k], hipMemcpyHostToDevice, s0));
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_up[k], s0));
-        HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_up[k], 0));
-        alac_decode_params p;
-        rc = fill_params(ctx, p, d_blob, blob_bytes, d_off + lo[k], d_sz + lo[k], cfg_idx ? d_ci + lo[k] : nullptr, cnt,
-                         (zc_pcm ? zc_pcm : d_pcm) + (size_t)lo[k] * slot_ints, slot_ints, d_ob + lo[k], d_os + lo[k], d_st + lo[k],
-                         out_format);
-        if (rc) return rc;
-        if (zc_pcm) {   // channel A waits in device memory
-            p.park = d_pcm + (size_t)lo[k] * park_stride;
-            p.park_stride = park_stride;
-        }
-        if ((rc = launch(ctx, p, s))) return rc;
-    }
-    const size_t pitch = sizeof(int32_t) * (size_t)slot_ints;
-    const size_t packed_w = std::min(pitch, packed_bytes_per_slot_int(ctx) * (size_t)slot_ints);
-    for (int k = 0; k < nch; k++) {
-        hipStream_t s = ctx->streams[k];
-        const uint32_t cnt = lo[k + 1] - lo[k];
-        if (cnt == 0) continue;
-        int32_t* dst = pcm_out + (size_t)lo[k] * slot_ints;
-        const int32_t* src = d_pcm + (size_t)lo[k] * slot_ints;
-        if (zc_pcm) {
-            // nothing to download: the kernels wrote into the caller's memory
-        } else if (out_format == ALACGPU_OUT_PACKED_LE) {
-            // a slot holds at most slot_ints samples of (ctor sample size / 8) bytes: copy that much of every slot
-            HIP_TRY(ctx, hipMemcpy2DAsync(dst, pitch, src, pitch, packed_w, cnt, hipMemcpyDeviceToHost, s));
-        } else {
-            HIP_TRY(ctx, hipMemcpyAsync(dst, src, pitch * cnt, hipMemcpyDeviceToHost, s));
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(status + lo[k], d_st + lo[k], sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, s));
-        if (out_bytes) HIP_TRY(ctx, hipMemcpyAsync(out_bytes + lo[k], d_ob + lo[k], sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, s));
-        if (out_samples) HIP_TRY(ctx, hipMemcpyAsync(out_samples + lo[k], d_os + lo[k], sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, s));
-    }
-    for (int k = 0; k < nch; k++)
-        if (ctx->streams[k]) HIP_TRY(ctx, hipStreamSynchronize(ctx->streams[k]));
-    return ALACGPU_OK;
-}
-}  // namespace
-
-extern "C" {
 
 int alacgpu_decode_batch(alacgpu_ctx* ctx, const uint8_t* blob, uint64_t blob_bytes, const uint64_t* offsets,
                          const uint32_t* sizes, const uint16_t* cfg_idx, uint32_t n_packets, int32_t* pcm_out,

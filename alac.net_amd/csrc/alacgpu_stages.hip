@@ -1,0 +1,451 @@
+// alacgpu_stages.hip -- C ABI of include/alacgpu.h, the stages around the decode: the crop planner, the scan with the packet
+// compaction and staging, the resamplers, log-mel and the encoder.  Of the ctx they use the device, the cfgs, last_error and
+// their own scratch; the decode path is alacgpu_api.hip.  No CPU fallback here either: every stage is its kernels.
+#include <algorithm>
+#include <cmath>
+
+#include "alac_corpus.h"
+#include "alac_resample.h"
+#include "alac_features.h"
+#include "alac_encode.h"
+#include "alacgpu_ctx.h"
+
+namespace {
+
+// Both planner entry points; each: every crop has a window length of its own, d_crop_frames[n_crops]
+int plan_crops(alacgpu_ctx* ctx, const void* d_pkt_offset, const void* d_pkt_size, const void* d_pkt_end,
+               const void* d_file_first, const void* d_file_cfg, uint32_t n_files, const void* d_crop_file,
+               const void* d_crop_offset, bool each, const void* d_crop_frames, uint32_t n_crops, uint32_t crop_frames,
+               uint32_t entries_per_crop, uint64_t dst_stride, void* d_offsets, void* d_sizes, void* d_cfg_idx,
+               void* d_dst_first, void* d_dst_frames, void* d_src_skip, void* d_lengths, void* hip_stream) {
+    if (!ctx) return ALACGPU_ERR_BAD_ARG;
+    if (n_crops == 0) return ALACGPU_OK;
+    if (entries_per_crop == 0 || (uint64_t)n_crops * entries_per_crop > 0xFFFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (!args_ok({{d_pkt_offset, 8}, {d_pkt_size, 4}, {d_pkt_end, 8}, {d_file_first, 4}, {d_file_cfg, 2}, {d_crop_file, 4},
+                  {d_crop_offset, 8}, {d_crop_frames, 4, each}, {d_offsets, 8}, {d_sizes, 4}, {d_cfg_idx, 2}, {d_dst_first, 8},
+                  {d_dst_frames, 4}, {d_src_skip, 4}, {d_lengths, 8}}))
+        return ALACGPU_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    alac_plan_params p;
+    p.pkt_offset = (const uint64_t*)d_pkt_offset;
+    p.pkt_size = (const uint32_t*)d_pkt_size;
+    p.pkt_end = (const uint64_t*)d_pkt_end;
+    p.file_first = (const uint32_t*)d_file_first;
+    p.file_cfg = (const uint16_t*)d_file_cfg;
+    p.n_files = n_files;
+    p.crop_file = (const uint32_t*)d_crop_file;
+    p.crop_offset = (const uint64_t*)d_crop_offset;
+    p.n_crops = n_crops;
+    p.crop_frames = crop_frames;
+    p.crop_frames_each = each ? (const uint32_t*)d_crop_frames : nullptr;
+    p.entries_per_crop = entries_per_crop;
+    p.dst_stride = dst_stride;
+    p.offsets = (uint64_t*)d_offsets;
+    p.sizes = (uint32_t*)d_sizes;
+    p.cfg_idx = (uint16_t*)d_cfg_idx;
+    p.dst_first = (uint64_t*)d_dst_first;
+    p.dst_frames = (uint32_t*)d_dst_frames;
+    p.src_skip = (uint32_t*)d_src_skip;
+    p.lengths = (int64_t*)d_lengths;
+    constexpr uint32_t per_wg = ALAC_PLAN_THREADS / 64;   // one wave per crop
+    void* kargs[] = {&p};
+    const void* const kernel = each ? (const void*)alac_plan_crops_frames_kernel : (const void*)alac_plan_crops_kernel;
+    HIP_TRY(ctx, hipLaunchKernel(kernel, dim3((n_crops + per_wg - 1u) / per_wg), dim3(ALAC_PLAN_THREADS), kargs, 0,
+                                 (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
+}
+
+// The exclusive scan both alacgpu_compact_packets_device and alacgpu_stage_packets_device begin with: s0 holds the sizes, how
+// they count, `add`, `out` and `total`; the two kernels are the level-0 pair that counts that way.  The levels: the sizes, the
+// sums of their tiles, the sums of those sums' tiles (at most 1024 for 2^32 - 1 packets), in the ctx's scratch (none for one tile).
+int scan_sizes(alacgpu_ctx* ctx, alac_scan_params<uint32_t> s0, const void* sums_kernel, const void* tiles_kernel, hipStream_t stream) {
+    const uint64_t t1 = (s0.n + ALAC_SCAN_TILE - 1u) / ALAC_SCAN_TILE;
+    const uint64_t t2 = (t1 + ALAC_SCAN_TILE - 1u) / ALAC_SCAN_TILE;
+    const size_t need = t1 > 1 ? sizeof(uint64_t) * (size_t)(t1 + t2) : 0;
+    int rc = ctx->scan.acquire(ctx, stream, need, align_up(need + need / 4, 4096));
+    if (rc) return rc;
+    uint64_t* const l1 = (uint64_t*)ctx->scan.buf[0];
+    uint64_t* const l2 = l1 ? l1 + t1 : nullptr;
+    s0.sums = l1;
+    s0.tile_base = t1 > 1 ? l1 : nullptr;
+    const dim3 block(ALAC_SCAN_THREADS);
+    if (t1 > 1) {
+        alac_scan_params<uint64_t> s1 = {};
+        s1.in = l1;
+        s1.n = t1;
+        s1.slot_bytes = 0;
+        s1.sums = l2;
+        s1.tile_base = t2 > 1 ? l2 : nullptr;
+        s1.add = 0;
+        s1.out = l1;
+        s1.total = nullptr;
+        void* a0[] = {&s0};
+        void* a1[] = {&s1};
+        HIP_TRY(ctx, hipLaunchKernel(sums_kernel, dim3((uint32_t)t1), block, a0, 0, stream));
+        if (t2 > 1) {
+            alac_scan_params<uint64_t> s2 = s1;          // t2 <= 1024: one tile
+            s2.in = l2;
+            s2.n = t2;
+            s2.sums = nullptr;
+            s2.tile_base = nullptr;
+            s2.out = l2;
+            void* a2[] = {&s2};
+            HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_sums_u64_kernel, dim3((uint32_t)t2), block, a1, 0, stream));
+            HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_tiles_u64_kernel, dim3(1), block, a2, 0, stream));
+        }
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_scan_tiles_u64_kernel, dim3((uint32_t)t2), block, a1, 0, stream));
+    }
+    void* a0[] = {&s0};
+    HIP_TRY(ctx, hipLaunchKernel(tiles_kernel, dim3((uint32_t)t1), block, a0, 0, stream));
+    return ALACGPU_OK;
+}
+
+// What alacgpu_compact_packets_device and alacgpu_stage_packets_device begin and end with.  scan_begin: the ctx and d_total
+// checked and the device made current; without packets (done) d_total[0] = 0 is the whole call.  scan_end releases the scratch.
+int scan_begin(alacgpu_ctx* ctx, void* d_total, uint32_t n_packets, hipStream_t stream, bool& done) {
+    done = n_packets == 0;
+    if (!ctx || !args_ok({{d_total, 8}})) return ALACGPU_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (done) HIP_TRY(ctx, hipMemsetAsync(d_total, 0, sizeof(uint64_t), stream));
+    return ALACGPU_OK;
+}
+
+int scan_end(alacgpu_ctx* ctx, hipStream_t stream) {
+    HIP_TRY(ctx, hipGetLastError());
+    return ctx->scan.release(ctx, stream);
+}
+
+// The tile of a resample launch: as many output frames as leave a CU room for two workgroups, down to 256; fewer only where the
+// span of 256 does not fit the CU at all (a / b in the hundreds) -- one frame's span, 2 width + 2, always fits next to the table.
+// lds_bytes(tile): the dynamic LDS a workgroup needs for that tile.
+template <class F>
+uint32_t resample_tile(const F& lds_bytes) {
+    uint32_t tile = ALAC_RESAMPLE_MAX_TILE;
+    while (tile > 256u && lds_bytes(tile) > ALAC_RESAMPLE_LDS_PREFERRED) tile /= 2u;
+    while (tile > 1u && lds_bytes(tile) > ALAC_RESAMPLE_LDS_MAX) tile /= 2u;
+    return tile;
+}
+
+// The grid: a workgroup takes up to eight consecutive tiles with one load of the table, while a thousand workgroups remain.
+// false: 2^31 tiles of output or more.
+bool resample_grid(uint64_t out_frames, uint32_t tile, uint64_t planes, uint32_t& per_wg, uint32_t& blocks) {
+    const uint64_t tiles = (out_frames + tile - 1u) / tile;
+    if (tiles > 0xFFFFFFFFull || tiles * planes > 0x7FFFFFFFull) return false;
+    const uint64_t n = std::min<uint64_t>(std::max<uint64_t>(tiles * planes / 1024u, 1u), std::min<uint64_t>(tiles, ALAC_RESAMPLE_MAX_TILES_PER_WG));
+    per_wg = (uint32_t)n;
+    blocks = (uint32_t)((tiles + n - 1u) / n * planes);
+    return true;
+}
+
+// What alacgpu_resample_device and alacgpu_resample_rows_device share, behind the checks of their own tables: the pointers they
+// have in common, the launch's tile, grid and LDS from lds_bytes(tile), the fields their parameter structs share by name --
+// own(p, tile, lds) sets the four that differ -- and the launch.
+template <class P, class F, class G>
+int resample(alacgpu_ctx* ctx, const void* kernel, const F& lds_bytes, const G& own, const void* d_src, uint32_t rows, uint32_t channels,
+             uint64_t src_stride, const void* d_src_origin, const void* d_src_valid, const void* d_out_first, uint64_t out_frames,
+             const void* d_d0, const void* d_weights, int mono, void* d_out, void* hip_stream) {
+    if (!ctx || !args_ok({{d_src, 4}, {d_src_origin, 8}, {d_src_valid, 8}, {d_out_first, 8}, {d_d0, 4}, {d_weights, 4}, {d_out, 4}}) ||
+        channels < 1 || channels > 2)
+        return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0 || out_frames == 0) return ALACGPU_OK;
+    const uint32_t tile = resample_tile(lds_bytes);
+    const size_t lds = lds_bytes(tile);
+    uint32_t per_wg, blocks;
+    if (!resample_grid(out_frames, tile, (uint64_t)rows * (mono ? 1u : channels), per_wg, blocks)) return ALACGPU_ERR_BAD_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (lds > ALAC_RESAMPLE_LDS_PREFERRED) HIP_TRY(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    P p;
+    p.src = (const float*)d_src;
+    p.src_stride = src_stride;
+    p.src_origin = (const int64_t*)d_src_origin;
+    p.src_valid = (const int64_t*)d_src_valid;
+    p.out_first = (const int64_t*)d_out_first;
+    p.out = (float*)d_out;
+    p.out_frames = out_frames;
+    p.d0 = (const int32_t*)d_d0;
+    p.weights = (const float*)d_weights;
+    p.channels = channels;
+    p.mono = mono ? 1u : 0u;
+    p.tile = tile;
+    p.tiles_per_wg = per_wg;
+    own(p, tile, lds);
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel(kernel, dim3(blocks), dim3(ALAC_RESAMPLE_THREADS), kargs, lds, (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int alacgpu_plan_crops_device(alacgpu_ctx* ctx, const void* d_pkt_offset, const void* d_pkt_size, const void* d_pkt_end,
+                              const void* d_file_first, const void* d_file_cfg, uint32_t n_files, const void* d_crop_file,
+                              const void* d_crop_offset, uint32_t n_crops, uint32_t crop_frames, uint32_t entries_per_crop,
+                              uint64_t dst_stride, void* d_offsets, void* d_sizes, void* d_cfg_idx, void* d_dst_first,
+                              void* d_dst_frames, void* d_src_skip, void* d_lengths, void* hip_stream) {
+    return plan_crops(ctx, d_pkt_offset, d_pkt_size, d_pkt_end, d_file_first, d_file_cfg, n_files, d_crop_file, d_crop_offset, false,
+                      nullptr, n_crops, crop_frames, entries_per_crop, dst_stride, d_offsets, d_sizes, d_cfg_idx, d_dst_first,
+                      d_dst_frames, d_src_skip, d_lengths, hip_stream);
+}
+
+int alacgpu_plan_crops_frames_device(alacgpu_ctx* ctx, const void* d_pkt_offset, const void* d_pkt_size, const void* d_pkt_end,
+                                     const void* d_file_first, const void* d_file_cfg, uint32_t n_files, const void* d_crop_file,
+                                     const void* d_crop_offset, const void* d_crop_frames, uint32_t n_crops, uint32_t crop_frames,
+                                     uint32_t entries_per_crop, uint64_t dst_stride, void* d_offsets, void* d_sizes,
+                                     void* d_cfg_idx, void* d_dst_first, void* d_dst_frames, void* d_src_skip, void* d_lengths,
+                                     void* hip_stream) {
+    return plan_crops(ctx, d_pkt_offset, d_pkt_size, d_pkt_end, d_file_first, d_file_cfg, n_files, d_crop_file, d_crop_offset, true,
+                      d_crop_frames, n_crops, crop_frames, entries_per_crop, dst_stride, d_offsets, d_sizes, d_cfg_idx, d_dst_first,
+                      d_dst_frames, d_src_skip, d_lengths, hip_stream);
+}
+
+int alacgpu_compact_packets_device(alacgpu_ctx* ctx, const void* d_packets, uint64_t slot_bytes, const void* d_sizes,
+                                   uint32_t n_packets, void* d_blob, uint64_t base, uint64_t blob_capacity,
+                                   void* d_pkt_offset, void* d_total, void* hip_stream) {
+    if (slot_bytes == 0 || (slot_bytes & 15u) != 0) return ALACGPU_ERR_BAD_ARG;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    bool done;
+    int rc = scan_begin(ctx, d_total, n_packets, stream, done);
+    if (rc || done) return rc;
+    if (!args_ok({{d_packets, 16}, {d_sizes, 4}, {d_blob, 1}, {d_pkt_offset, 8}})) return ALACGPU_ERR_BAD_ARG;
+    alac_scan_params<uint32_t> s0 = {};
+    s0.in = (const uint32_t*)d_sizes;
+    s0.n = n_packets;
+    s0.slot_bytes = slot_bytes;
+    s0.add = base;
+    s0.out = (uint64_t*)d_pkt_offset;
+    s0.total = (uint64_t*)d_total;
+    if ((rc = scan_sizes(ctx, s0, (const void*)alac_scan_sums_u32_kernel, (const void*)alac_scan_tiles_u32_kernel, stream))) return rc;
+    // the copy: tiles of the destination, as many as the packets can fill at most (the true end is d_total's, on the device)
+    const uint64_t most = slot_bytes > UINT64_MAX / n_packets ? UINT64_MAX : slot_bytes * n_packets;
+    const uint64_t room = blob_capacity > base ? blob_capacity - base : 0;
+    const uint64_t bound = std::min(most, room);
+    if (bound) {
+        alac_copy_params c;
+        c.packets = (const uint8_t*)d_packets;
+        c.slot_bytes = slot_bytes;
+        c.sizes = (const uint32_t*)d_sizes;
+        c.pkt_offset = (const uint64_t*)d_pkt_offset;
+        c.total = (const uint64_t*)d_total;
+        c.n_packets = n_packets;
+        c.blob = (uint8_t*)d_blob;
+        c.base = base;
+        c.capacity = blob_capacity;
+        const uint64_t tiles = bound / ALAC_COPY_TILE + 2u;   // (a tile more for the bytes in front of the first aligned chunk)
+        void* ac[] = {&c};
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_compact_copy_kernel, dim3((uint32_t)std::min<uint64_t>(tiles, 1u << 16)),
+                                     dim3(ALAC_COPY_THREADS), ac, 0, stream));
+    }
+    return scan_end(ctx, stream);
+}
+
+int alacgpu_stage_packets_device(alacgpu_ctx* ctx, const void* d_blob_lo, uint64_t lo_bytes, const void* blob_hi, uint64_t hi_bytes,
+                                 const void* d_src_offset, const void* d_sizes, uint32_t n_packets, void* d_stage,
+                                 uint64_t stage_capacity, void* d_stage_offset, void* d_total, void* hip_stream) {
+    if (!args_ok({{d_blob_lo, 16, lo_bytes != 0}, {blob_hi, 16, hi_bytes != 0}})) return ALACGPU_ERR_BAD_ARG;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    bool done;
+    int rc = scan_begin(ctx, d_total, n_packets, stream, done);
+    if (rc || done) return rc;
+    if (!args_ok({{d_src_offset, 8}, {d_sizes, 4}, {d_stage, 16}, {d_stage_offset, 8}}) || lo_bytes > UINT64_MAX - hi_bytes)
+        return ALACGPU_ERR_BAD_ARG;
+    // the second part as the kernels address it: device memory as it is, page-locked host memory by its device view
+    const void* hi_view = nullptr;
+    if (hi_bytes) {
+        hipPointerAttribute_t a;
+        if (hipPointerGetAttributes(&a, blob_hi) != hipSuccess) { (void)hipGetLastError(); return ALACGPU_ERR_BAD_ARG; }
+        hi_view = a.type == hipMemoryTypeDevice ? blob_hi : device_view_of_pinned(blob_hi, (size_t)hi_bytes);
+        if (!hi_view) return ALACGPU_ERR_BAD_ARG;
+    }
+    alac_scan_params<uint32_t> s0 = {};
+    s0.in = (const uint32_t*)d_sizes;
+    s0.n = n_packets;
+    s0.src_offset = (const uint64_t*)d_src_offset;
+    s0.lo_bytes = lo_bytes;
+    s0.hi_bytes = hi_bytes;
+    s0.out = (uint64_t*)d_stage_offset;
+    s0.total = (uint64_t*)d_total;
+    if ((rc = scan_sizes(ctx, s0, (const void*)alac_scan_sums_stage_kernel, (const void*)alac_scan_tiles_stage_kernel, stream))) return rc;
+    // the copy: tiles of the staging blob, as many as its capacity holds (the true end is d_total's, on the device)
+    if (stage_capacity >= 16u) {
+        alac_stage_params c;
+        c.lo = (const uint8_t*)d_blob_lo;
+        c.hi = (const uint8_t*)hi_view;
+        c.lo_bytes = lo_bytes;
+        c.hi_bytes = hi_bytes;
+        c.src_offset = (const uint64_t*)d_src_offset;
+        c.sizes = (const uint32_t*)d_sizes;
+        c.stage_offset = (const uint64_t*)d_stage_offset;
+        c.total = (const uint64_t*)d_total;
+        c.n_packets = n_packets;
+        c.stage = (uint8_t*)d_stage;
+        c.capacity = stage_capacity;
+        const uint64_t tiles = stage_capacity / ALAC_STAGE_TILE + 1u;
+        void* ac[] = {&c};
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_stage_copy_kernel, dim3((uint32_t)std::min<uint64_t>(tiles, 1u << 16)),
+                                     dim3(ALAC_STAGE_THREADS), ac, 0, stream));
+    }
+    return scan_end(ctx, stream);
+}
+
+int alacgpu_resample_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,
+                            const void* d_src_origin, const void* d_src_valid, const void* d_out_first, uint64_t out_frames,
+                            uint32_t a, uint32_t b, uint32_t width, const void* d_d0, const void* d_weights, int mono, void* d_out,
+                            void* hip_stream) {
+    const uint64_t table = (uint64_t)b * (2u * (uint64_t)width + 1u);
+    if (a == 0 || b == 0 || width == 0 || table > ALAC_RESAMPLE_MAX_TABLE) return ALACGPU_ERR_BAD_ARG;
+    const auto lds_bytes = [&](uint64_t tile) { return sizeof(float) * (size_t)(((table + 3u) & ~3ull) + alac_resample_span(tile, a, b, width)); };
+    const auto own = [&](alac_resample_params& p, uint32_t tile, size_t lds) {
+        p.a = a;
+        p.b = b;
+        p.width = width;
+        p.span = (uint32_t)alac_resample_span(tile, a, b, width);
+    };
+    return resample<alac_resample_params>(ctx, (const void*)alac_resample_kernel, lds_bytes, own, d_src, rows, channels, src_stride,
+                                          d_src_origin, d_src_valid, d_out_first, out_frames, d_d0, d_weights, mono, d_out, hip_stream);
+}
+
+static_assert(sizeof(alacgpu_resample_table) == sizeof(alac_resample_table) && offsetof(alacgpu_resample_table, weights_first) ==
+              offsetof(alac_resample_table, weights_first), "the kernel reads the header's table descriptors as they are");
+
+int alacgpu_resample_rows_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,
+                                 const void* d_src_origin, const void* d_src_valid, const void* d_out_first, uint64_t out_frames,
+                                 const alacgpu_resample_table* tables, const void* d_tables, uint32_t n_tables, const void* d_d0,
+                                 const void* d_weights, const void* d_row_table, int mono, void* d_out, void* hip_stream) {
+    if (!args_ok({{tables, 4}, {d_tables, 4}, {d_row_table, 4}}) || n_tables == 0) return ALACGPU_ERR_BAD_ARG;
+    for (uint32_t t = 0; t < n_tables; t++) {
+        const alacgpu_resample_table& d = tables[t];
+        if (d.a == 0 || d.b == 0 || d.width == 0 || (uint64_t)d.b * (2u * (uint64_t)d.width + 1u) > ALAC_RESAMPLE_MAX_TABLE)
+            return ALACGPU_ERR_BAD_ARG;
+    }
+    // one tile for the launch, and the LDS of the table that needs the most for it; a workgroup uses its own table's span
+    const auto lds_bytes = [&](uint64_t tile) {
+        uint64_t most = 0;
+        for (uint32_t t = 0; t < n_tables; t++) {
+            const alacgpu_resample_table& d = tables[t];
+            const uint64_t table = (uint64_t)d.b * (2u * (uint64_t)d.width + 1u);
+            most = std::max<uint64_t>(most, ((table + 3u) & ~3ull) + alac_resample_span(tile, d.a, d.b, d.width));
+        }
+        return sizeof(float) * (size_t)most;
+    };
+    const auto own = [&](alac_resample_rows_params& p, uint32_t tile, size_t lds) {
+        p.tables = (const alac_resample_table*)d_tables;
+        p.row_table = (const uint32_t*)d_row_table;
+        p.n_tables = n_tables;
+        p.lds_floats = (uint32_t)(lds / sizeof(float));
+    };
+    return resample<alac_resample_rows_params>(ctx, (const void*)alac_resample_rows_kernel, lds_bytes, own, d_src, rows, channels,
+                                               src_stride, d_src_origin, d_src_valid, d_out_first, out_frames, d_d0, d_weights, mono,
+                                               d_out, hip_stream);
+}
+
+int alacgpu_logmel_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,
+                          uint64_t frames, uint32_t n_fft, uint32_t hop, uint32_t n_mels, const void* d_window,
+                          const void* d_basis, const void* d_fb, int log_mode, float floor, void* d_out, uint64_t out_frames,
+                          void* hip_stream) {
+    if (!ctx || !args_ok({{d_src, 4}, {d_window, 4}, {d_basis, 4}, {d_fb, 4}, {d_out, 4}})) return ALACGPU_ERR_BAD_ARG;
+    if (n_fft < ALAC_FEATURES_MIN_NFFT || n_fft > ALAC_FEATURES_MAX_NFFT || hop < 1 || hop > n_fft || n_mels < 1 ||
+        n_mels > ALAC_FEATURES_MAX_MELS || channels == 0)
+        return ALACGPU_ERR_BAD_ARG;
+    if (!(floor > 0.0f) || !std::isfinite(floor)) return ALACGPU_ERR_BAD_ARG;
+    if (log_mode != ALAC_FEATURES_LOG_NONE && log_mode != ALAC_FEATURES_LOG_LN && log_mode != ALAC_FEATURES_LOG_10) return ALACGPU_ERR_BAD_ARG;
+    if (frames <= n_fft / 2u || frames > src_stride || frames > (1ull << 62) || out_frames != 1u + frames / hop) return ALACGPU_ERR_BAD_ARG;
+    const uint32_t tile = alac_features_tile(n_fft, hop);
+    const uint64_t tiles = (out_frames + tile - 1u) / tile;
+    if (tiles > 0x7FFFFFFFull || tiles * channels > 0x7FFFFFFFull || tiles * channels * rows > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0) return ALACGPU_OK;
+    const size_t lds = alac_features_lds_layout(n_fft, hop, n_mels).bytes();
+    if (lds > ALAC_FEATURES_LDS_MAX) return ALACGPU_ERR_BAD_ARG;    // (the limits above keep every layout below it)
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (lds > ALAC_FEATURES_LDS_DEFAULT)
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)alac_logmel_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    alac_features_params p;
+    p.src = (const float*)d_src;
+    p.src_stride = src_stride;
+    p.frames = frames;
+    p.out = (float*)d_out;
+    p.out_frames = out_frames;
+    p.window = (const float*)d_window;
+    p.basis = (const float*)d_basis;
+    p.fb = (const float*)d_fb;
+    p.n_fft = n_fft;
+    p.hop = hop;
+    p.n_mels = n_mels;
+    p.tile = tile;
+    p.tiles = (uint32_t)tiles;
+    p.log_mode = (uint32_t)log_mode;
+    p.floor = floor;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_logmel_kernel, dim3((uint32_t)(tiles * channels * rows)), dim3(ALAC_FEATURES_THREADS),
+                                 kargs, lds, (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
+}
+
+size_t alacgpu_encode_max_packet_bytes(uint32_t frames, int sample_size, int channels) {
+    // an escape packet with its sample count: header 23 + 32 bits, the raw samples, the END tag
+    const uint64_t bits = 23u + 32u + (uint64_t)frames * (uint64_t)(channels < 1 ? 1 : channels) * (uint64_t)(sample_size < 0 ? 0 : sample_size) + 3u;
+    return (size_t)align_up((bits + 7) / 8, 16);
+}
+
+int alacgpu_encode_device(alacgpu_ctx* ctx, const void* d_pcm, uint64_t src_elems, uint32_t channels, int layout, int dtype,
+                          uint64_t plane_stride, const void* d_src_first, const void* d_src_frames, const void* d_cfg_idx,
+                          uint32_t n_packets, void* d_packets, uint64_t slot_bytes, void* d_sizes, void* d_status,
+                          void* hip_stream) {
+    if (!ctx || !args_ok({{d_pcm, 4}, {d_src_first, 8}, {d_src_frames, 4}, {d_cfg_idx, 2}, {d_packets, 16}, {d_sizes, 4}, {d_status, 4}}))
+        return ALACGPU_ERR_BAD_ARG;
+    if (!pcm_view_ok(d_pcm, channels, layout, dtype, plane_stride) || (slot_bytes & 15u) != 0) return ALACGPU_ERR_BAD_ARG;
+    for (uint32_t i = 0; i < ctx->n_cfgs; i++) {
+        const alacgpu_cfg& c = ctx->h_cfgs[i];
+        if (c.num_channels != channels) return ALACGPU_ERR_BAD_ARG;
+        const uint32_t frames = std::min(c.max_samples_per_frame, MAX_FRAME);
+        if (slot_bytes < alacgpu_encode_max_packet_bytes(frames, c.sample_size, (int)channels)) return ALACGPU_ERR_BAD_ARG;
+    }
+    if (n_packets == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    // a round: up to 16 workgroups per CU, one packet and one workspace slot each
+    int n_cu = 0;
+    HIP_TRY(ctx, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    const uint32_t round = std::min<uint32_t>(n_packets, (uint32_t)std::max(n_cu, 1) * 16u);
+    const uint32_t frames = smax(ctx);
+    const size_t items = (size_t)round * alac_enc_items(frames);
+    const size_t code_bytes = sizeof(uint64_t) * items, pos_bytes = sizeof(uint32_t) * (items + round);
+    int rc = ctx->enc.acquire(ctx, stream, code_bytes, code_bytes, pos_bytes, pos_bytes);
+    if (rc) return rc;
+    alac_encode_params p;
+    p.pcm = d_pcm;
+    p.src_elems = src_elems;
+    p.plane_stride = layout == ALACGPU_DST_PLANAR ? plane_stride : 0;
+    p.channels = channels;
+    p.layout = (uint32_t)layout;
+    p.dtype = (uint32_t)dtype;
+    p.n_packets = n_packets;
+    p.src_first = (const uint64_t*)d_src_first;
+    p.src_frames = (const uint32_t*)d_src_frames;
+    p.cfg_idx = (const uint16_t*)d_cfg_idx;
+    p.cfgs = ctx->d_cfgs;
+    p.n_cfgs = ctx->n_cfgs;
+    p.smax = frames;
+    p.packets = (uint8_t*)d_packets;
+    p.slot_bytes = slot_bytes;
+    p.sizes = (uint32_t*)d_sizes;
+    p.status = (int32_t*)d_status;
+    p.ws_code = (uint64_t*)ctx->enc.buf[0];
+    p.ws_pos = (uint32_t*)ctx->enc.buf[1];
+    for (uint32_t first = 0; first < n_packets; first += round) {
+        p.first_packet = first;
+        alac_encode_params args = p;
+        void* kargs[] = {&args};
+        const dim3 grid(std::min(round, n_packets - first)), block(ALAC_ENC_THREADS);
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_encode_analyse_kernel, grid, block, kargs, 0, stream));
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_encode_codes_kernel, grid, block, kargs, 0, stream));
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_encode_emit_kernel, grid, block, kargs, 0, stream));
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return ctx->enc.release(ctx, stream);
+}
+
+}  // extern "C"

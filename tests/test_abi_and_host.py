@@ -102,7 +102,10 @@ def test_product_kernels_carry_no_diagnostics():
     import subprocess
 
     csrc = os.path.join(ROOT, "alac.net_amd", "csrc")
-    for src, emits in (("alac_kernels.hip", ("1", "2", "3", "4", "5")), ("alacgpu_api.hip", (None,)), ("alacgpu_comm.hip", (None,))):
+    # per translation unit: its ALAC_EMIT builds (None: host code) and where this repository's own text begins in its output
+    units = (("alac_kernels.hip", ("1", "2", "3", "4", "5"), "namespace alacdev"), ("alacgpu_api.hip", (None,), "struct alacgpu_ctx"),
+             ("alacgpu_stages.hip", (None,), "struct alacgpu_ctx"), ("alacgpu_comm.hip", (None,), "struct rccl_api"))
+    for src, emits, begins in units:
         for emit in emits:
             cmd = ["/opt/rocm/bin/hipcc", "-E", "-P", "--offload-arch=gfx950", "--cuda-device-only" if emit else "--cuda-host-only",
                    "-I", os.path.join(ROOT, "include"), "-I", csrc, os.path.join(csrc, src)]
@@ -111,7 +114,8 @@ def test_product_kernels_carry_no_diagnostics():
             r = subprocess.run(cmd, capture_output=True, text=True)
             assert r.returncode == 0, r.stderr[-2000:]
             # only what comes from this repository's own sources (the HIP headers mention clock64 themselves)
-            own = r.stdout[r.stdout.rfind("namespace alacdev"):] if emit else r.stdout[r.stdout.rfind("struct alacgpu_ctx"):] if "api" in src else r.stdout[r.stdout.rfind("struct rccl_api"):]
+            assert begins in r.stdout, (src, emit)
+            own = r.stdout[r.stdout.rfind(begins):]
             assert len(own) > 2000, (src, emit)
             for word in ("clock64", "s_memtime", "dbg", "ALAC_EXPERIMENT", "SpecStats st;\n    st."):
                 assert word not in own, f"{src} (ALAC_EMIT={emit}): `{word}` in the product translation unit"

@@ -73,6 +73,10 @@ SYMBOLS = {
                                                C.c_uint32, _VP, _VP, _VP, C.c_int, _VP, _VP]),
     "alacgpu_logmel_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _VP,
                                         _VP, _VP, C.c_int, C.c_float, _VP, C.c_uint64, _VP]),
+    "alacgpu_normalize_meanvar_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, C.c_int, C.c_int,
+                                                   C.c_float, _VP]),
+    "alacgpu_normalize_top_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
+                                               C.c_float, C.c_int, _VP]),
     "alacgpu_encode_max_packet_bytes": (C.c_size_t, [C.c_uint32, C.c_int, C.c_int]),
     "alacgpu_encode_device": (C.c_int, [_VP, _VP, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP, C.c_uint32,
                                         _VP, C.c_uint64, _VP, _VP, _VP]),
@@ -369,6 +373,25 @@ class AlacGpuContext(_Closing):
         max(., floor).  Asynchronous on `stream` (raw hipStream_t); nothing is read back."""
         rc = lib().alacgpu_logmel_device(self._ctx, _dp(d_src), rows, channels, src_stride, frames, n_fft, hop, n_mels, _dp(d_window),
                                          _dp(d_basis), _dp(d_fb), log_mode, floor, _dp(d_out), out_frames, _VP(stream))
+        _check(rc, self._ctx)
+
+    def normalize_meanvar_device(self, d_src, d_out, rows, lines_per_row, line_stride, line_len, d_valid, centre, scale, eps, stream=0):
+        """alacgpu_normalize_meanvar_device: every line of d_src (float32 device tensor [rows, lines_per_row, line_stride], the
+        first line_len of a line are data) to zero mean (centre) and unit variance (scale; eps under the root) over its first
+        v = min(max(d_valid[row], 0), line_len) elements, zeros behind them up to line_len, into d_out (d_src itself or the
+        same layout apart from it).  d_valid: an int64 device tensor [rows], or None for whole lines.  normalize.py states the
+        arithmetic.  Asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_normalize_meanvar_device(self._ctx, _dp(d_src), _dp(d_out), rows, lines_per_row, line_stride, line_len,
+                                                    _dp(d_valid), int(bool(centre)), int(bool(scale)), eps, _VP(stream))
+        _check(rc, self._ctx)
+
+    def normalize_top_device(self, d_src, d_out, rows, lines_per_row, line_stride, line_len, top, scale, offset, relative, stream=0):
+        """alacgpu_normalize_top_device: with mx the maximum of row r of d_src (float32 device tensor
+        [rows, lines_per_row, line_stride], the first line_len of a line are data), scale * (max(x, mx - top) [- mx with
+        relative]) + offset into d_out (d_src itself or the same layout apart from it); a row with a NaN is NaN throughout.
+        Two launches, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_normalize_top_device(self._ctx, _dp(d_src), _dp(d_out), rows, lines_per_row, line_stride, line_len, top,
+                                                scale, offset, int(bool(relative)), _VP(stream))
         _check(rc, self._ctx)
 
     def set_output_format(self, fmt):
@@ -937,3 +960,6 @@ from .corpus import (Corpus, compact_plan_host, corpus_plan_host, corpus_tables,
 from .resample import resample, resample_host, resample_table, source_window  # noqa: E402
 # ---- log-mel features of crops and tensors (alacgpu_logmel_device) -----------------------------------------------------------------
 from .features import LogMel, log_mel, logmel_host, logmel_host_f32, mel_filterbank  # noqa: E402
+
+# ---- normalised crops and features (alacgpu_normalize_meanvar_device, alacgpu_normalize_top_device) ------------------------------
+from .normalize import MeanVar, TopDb, normalize, normalize_host, normalize_host_f32  # noqa: E402

@@ -597,7 +597,8 @@ class Corpus(_Closing):
             raise ValueError(f"crop {b} (source {int(f[b])}): frame offset {int(o[b])} outside 0 .. {int(totals[f[b]])}")
         return torch.from_numpy(f.astype(np.int32)).to(self._dev), torch.from_numpy(o).to(self._dev), True
 
-    def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True, features=None, sample_rate=None, mono=False):
+    def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True, features=None, normalize=None, sample_rate=None,
+              mono=False):
         """Decode crop b = frames frame_offsets[b] .. + num_frames of file files[b] for every b in ONE launch pair: returns
         (pcm [B, C, num_frames] on the device, zero behind lengths[b]; lengths [B], a DEVICE int64 tensor: min(num_frames,
         T_f - offset)).  float32 (default) or int32, as `load`.  files / frame_offsets: sequences, numpy arrays or torch
@@ -616,9 +617,15 @@ class Corpus(_Closing):
 
         features: a features.LogMel -- the crops' log-mel features instead of their PCM (`_feature_crops`): returns (feats
         float32 [B, 1 if mono else C, n_mels, 1 + num_frames // hop], feat_lengths [B] int64 on the device: lengths // hop + 1,
-        -1 where lengths is -1); `out` is then the features tensor.  Pass it by keyword, and sample_rate and mono as well."""
+        -1 where lengths is -1); `out` is then the features tensor.  Pass it by keyword, and sample_rate and mono as well.
+
+        normalize: a normalize.MeanVar or normalize.TopDb (`_normalized_crops`), applied in place behind everything above, on
+        the same stream: bit for bit normalize.normalize(what the call returns without it, normalize, lengths).  By keyword, as
+        features, sample_rate and mono."""
         import torch
 
+        if normalize is not None:
+            return self._normalized_crops(normalize, files, frame_offsets, num_frames, dtype, out, check, features, sample_rate, mono)
         if features is not None:
             return self._feature_crops(files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, features)
         if self.sample_rate is None and sample_rate is None:
@@ -649,6 +656,29 @@ class Corpus(_Closing):
         if check:
             self._check_last(lengths, d_files, d_offs, L, K)
         return out, lengths
+
+    def _normalized_crops(self, how, files, frame_offsets, num_frames, dtype, out, check, features, sample_rate, mono):
+        """crops(..., normalize=how): the crops, or with features=spec their features, are made exactly as without, then
+        normalised in place by the corpus's own context on the same stream (normalize.py states the arithmetic).  A MeanVar
+        takes every line over its valid elements -- lengths for PCM on every path, feat_lengths for features, so a crop outside
+        the corpus (-1) is zeros; a TopDb takes every crop of features, or every channel of it with per_channel.  What is
+        returned otherwise, `check` and last_status() are those of the call without.  ValueError before any device work: a
+        TopDb without features, a MeanVar with int32 crops, anything else that is neither."""
+        import torch
+
+        from .normalize import MeanVar, TopDb, _normalize
+
+        if not isinstance(how, (MeanVar, TopDb)):
+            raise ValueError(f"normalize must be a normalize.MeanVar or a normalize.TopDb, not {how!r}")
+        if features is None:
+            if isinstance(how, TopDb):
+                raise ValueError("a TopDb clamps log-mel features: it needs features=")
+            if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
+                raise ValueError("a MeanVar normalises float32 crops")
+        res, lengths = self.crops(files, frame_offsets, num_frames, dtype=dtype, out=out, check=check, features=features,
+                                  sample_rate=sample_rate, mono=mono)
+        _normalize(lambda: self._gpu, res, how, lengths, res)
+        return res, lengths
 
     def _feature_crops(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, spec):
         """crops(..., features=spec): the crops are made exactly as without -- on the native or the `_rate_crops` path, `mono`
@@ -841,13 +871,13 @@ class Corpus(_Closing):
             self._check_last(valid, d_files, src_offs, Ls, K, d_shown=d_offs)
         return out, lengths
 
-    def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True, features=None, sample_rate=None,
-                     mono=False):
+    def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True, features=None, normalize=None,
+                     sample_rate=None, mono=False):
         """`batch` crops of num_frames frames drawn on the device: files uniform over the corpus, the first frame uniform in
         0 .. max(T_f - num_frames, 0).  generator: a torch.Generator (of the corpus's device, or of the CPU: then the draws are
         made there and uploaded).  Returns (pcm, lengths, files, frame_offsets), the draws as device int64 tensors.
         sample_rate / mono as for `crops`: the frames, T_f included, then count at sample_rate.  features as for `crops`:
-        (feats, feat_lengths, files, frame_offsets)."""
+        (feats, feat_lengths, files, frame_offsets).  normalize as for `crops`."""
         import torch
 
         B, L = _frame_count("batch", batch), _frame_count("num_frames", num_frames)
@@ -860,7 +890,7 @@ class Corpus(_Closing):
         span = (totals[files] - L).clamp(min=0)
         offs = torch.minimum(torch.floor(u * (span + 1).to(torch.float64)).to(torch.int64), span)
         pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,
-                                  features=features)
+                                  features=features, normalize=normalize)
         return pcm, lengths, files, offs
 
     def last_staged_bytes(self):

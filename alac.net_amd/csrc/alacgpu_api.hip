@@ -442,6 +442,7 @@ void alacgpu_destroy(alacgpu_ctx* ctx) {
     if (ctx->d_ws) (void)hipFree(ctx->d_ws);
     ctx->enc.destroy();
     ctx->scan.destroy();
+    ctx->norm.destroy();
     if (ctx->d_cu_arrivals) cu_counters_release(ctx->device);
     if (ctx->h_frame) (void)hipHostFree(ctx->h_frame);
     if (ctx->d_cfgs) (void)hipFree(ctx->d_cfgs);

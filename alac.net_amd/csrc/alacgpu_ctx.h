@@ -97,6 +97,7 @@ struct alacgpu_ctx {
     int32_t* h_frame = nullptr;        // pinned staging of alacgpu_decode_frame (one slot of the widest kind)
     scratch enc;     // alacgpu_encode_device: per workgroup of a round alac_enc_items(smax) codes (buf[0]) and bit positions + 1 (buf[1])
     scratch scan;    // alacgpu_compact_packets_device, alacgpu_stage_packets_device: the partial sums of the scan's upper levels
+    scratch norm;    // alacgpu_normalize_top_device: the maxima of the parts of every row, [rows, parts] floats
     std::string last_error;
 };
 

@@ -1,5 +1,5 @@
 // alacgpu_stages.hip -- C ABI of include/alacgpu.h, the stages around the decode: the crop planner, the scan with the packet
-// compaction and staging, the resamplers, log-mel and the encoder.  Of the ctx they use the device, the cfgs, last_error and
+// compaction and staging, the resamplers, log-mel, the normalisations and the encoder.  Of the ctx they use the device, the cfgs, last_error and
 // their own scratch; the decode path is alacgpu_api.hip.  No CPU fallback here either: every stage is its kernels.
 #include <algorithm>
 #include <cmath>
@@ -7,6 +7,7 @@
 #include "alac_corpus.h"
 #include "alac_resample.h"
 #include "alac_features.h"
+#include "alac_normalize.h"
 #include "alac_encode.h"
 #include "alacgpu_ctx.h"
 
@@ -174,6 +175,18 @@ int resample(alacgpu_ctx* ctx, const void* kernel, const F& lds_bytes, const G& 
     HIP_TRY(ctx, hipLaunchKernel(kernel, dim3(blocks), dim3(ALAC_RESAMPLE_THREADS), kargs, lds, (hipStream_t)hip_stream));
     HIP_TRY(ctx, hipGetLastError());
     return ALACGPU_OK;
+}
+
+// What the two normalisations share in front of their own limits: the ctx and the arrays, the shape of the lines, and d_src
+// and d_out either the same array or apart.  lines: rows * lines_per_row
+bool normalize_args_ok(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t lines_per_row, uint64_t line_stride,
+                       uint64_t line_len, uint64_t& lines) {
+    if (!ctx || !args_ok({{d_src, 4}, {d_out, 4}}) || lines_per_row == 0 || line_len == 0 || line_len > line_stride) return false;
+    lines = (uint64_t)rows * lines_per_row;
+    if (line_stride > (1ull << 60) / sizeof(float) / std::max<uint64_t>(lines, 1u)) return false;      // (the extent fits 60 bits)
+    const uint64_t extent = lines ? sizeof(float) * ((lines - 1u) * line_stride + line_len) : 0u;
+    const uintptr_t a = (uintptr_t)d_src, b = (uintptr_t)d_out;
+    return a == b || a + extent <= b || b + extent <= a;
 }
 
 }  // namespace
@@ -382,6 +395,75 @@ int alacgpu_logmel_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, ui
                                  kargs, lds, (hipStream_t)hip_stream));
     HIP_TRY(ctx, hipGetLastError());
     return ALACGPU_OK;
+}
+
+int alacgpu_normalize_meanvar_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t lines_per_row,
+                                     uint64_t line_stride, uint64_t line_len, const void* d_valid, int centre, int scale, float eps,
+                                     void* hip_stream) {
+    uint64_t lines;
+    if (!normalize_args_ok(ctx, d_src, d_out, rows, lines_per_row, line_stride, line_len, lines) || !args_ok({{d_valid, 8, false}}))
+        return ALACGPU_ERR_BAD_ARG;
+    if (!(eps >= 0.0f) || !std::isfinite(eps) || (!centre && !scale)) return ALACGPU_ERR_BAD_ARG;
+    const uint64_t grid = alac_meanvar_grid(lines, line_len);
+    if (grid > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    alac_meanvar_params p;
+    p.src = (const float*)d_src;
+    p.out = (float*)d_out;
+    p.valid = (const int64_t*)d_valid;
+    p.lines = lines;
+    p.lines_per_row = lines_per_row;
+    p.line_stride = line_stride;
+    p.line_len = line_len;
+    p.centre = centre ? 1u : 0u;
+    p.scale = scale ? 1u : 0u;
+    p.eps = eps;
+    const bool wave = line_len <= ALAC_NORM_WAVE_MAX;
+    const void* const kernel = wave ? (const void*)alac_meanvar_wave_kernel
+                                    : line_len <= ALAC_NORM_LDS_MAX ? (const void*)alac_meanvar_lds_kernel : (const void*)alac_meanvar_mem_kernel;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel(kernel, dim3((uint32_t)grid), dim3(wave ? ALAC_NORM_WAVE_THREADS : ALAC_NORM_LINE_THREADS), kargs, 0,
+                                 (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
+}
+
+int alacgpu_normalize_top_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t lines_per_row,
+                                 uint64_t line_stride, uint64_t line_len, float top, float scale, float offset, int relative,
+                                 void* hip_stream) {
+    uint64_t lines;
+    if (!normalize_args_ok(ctx, d_src, d_out, rows, lines_per_row, line_stride, line_len, lines)) return ALACGPU_ERR_BAD_ARG;
+    if (!(top >= 0.0f) || !std::isfinite(top) || !std::isfinite(scale) || !std::isfinite(offset)) return ALACGPU_ERR_BAD_ARG;
+    const uint64_t row_elems = (uint64_t)lines_per_row * line_len;      // (at most the extent: it fits)
+    const uint32_t parts = alac_top_parts(row_elems);
+    const uint64_t grid = (uint64_t)rows * parts;
+    if (grid > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const size_t need = sizeof(float) * (size_t)grid;
+    int rc = ctx->norm.acquire(ctx, stream, need, align_up(need + need / 4, 4096));
+    if (rc) return rc;
+    alac_top_params p;
+    p.src = (const float*)d_src;
+    p.out = (float*)d_out;
+    p.maxima = (float*)ctx->norm.buf[0];
+    p.lines_per_row = lines_per_row;
+    p.line_stride = line_stride;
+    p.line_len = line_len;
+    p.row_elems = row_elems;
+    p.part_elems = alac_top_part_elems(row_elems);
+    p.parts = parts;
+    p.top = top;
+    p.scale = scale;
+    p.offset = offset;
+    p.relative = relative ? 1u : 0u;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_top_reduce_kernel, dim3((uint32_t)grid), dim3(ALAC_TOP_THREADS), kargs, 0, stream));
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_top_apply_kernel, dim3((uint32_t)grid), dim3(ALAC_TOP_THREADS), kargs, 0, stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ctx->norm.release(ctx, stream);
 }
 
 size_t alacgpu_encode_max_packet_bytes(uint32_t frames, int sample_size, int channels) {

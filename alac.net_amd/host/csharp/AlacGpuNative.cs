@@ -99,6 +99,16 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_logmel_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
             ulong srcStride, ulong frames, uint nFft, uint hop, uint nMels, IntPtr dWindow, IntPtr dBasis, IntPtr dFb, int logMode,
             float floor, IntPtr dOut, ulong outFrames, IntPtr hipStream);
+        /// <summary>Mean and variance per line of float data in device memory ([rows, linesPerRow, lineStride], the first lineLen of
+        /// a line are data) over the first min(max(dValid[row], 0), lineLen) elements (dValid: long[rows] or IntPtr.Zero for whole
+        /// lines): (x - mean) / sqrt(var + eps), zeros behind them, into dOut (dSrc itself or the same layout).  Asynchronous on
+        /// hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_normalize_meanvar_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, uint rows,
+            uint linesPerRow, ulong lineStride, ulong lineLen, IntPtr dValid, int centre, int scale, float eps, IntPtr hipStream);
+        /// <summary>The clamp relative to the maximum mx of a row of the same layout: scale * (max(x, mx - top) [- mx with relative])
+        /// + offset into dOut; a row with a NaN is NaN throughout.  Two launches, asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_normalize_top_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, uint rows,
+            uint linesPerRow, ulong lineStride, ulong lineLen, float top, float scale, float offset, int relative, IntPtr hipStream);
         /// <summary>Encode PCM in device memory (int32 or float32, interleaved or planar) to ALAC packets in device memory, one
         /// run of frames per packet, packet p at dPackets + p * slotBytes; asynchronous on hipStream.</summary>
         [DllImport(Lib)] public static extern UIntPtr alacgpu_encode_max_packet_bytes(uint frames, int sampleSize, int channels);

@@ -456,6 +456,52 @@ int alacgpu_logmel_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, ui
                           const void* d_basis, const void* d_fb, int log_mode, float floor, void* d_out,
                           uint64_t out_frames, void* hip_stream);
 
+/*
+ * The two normalisations between crops or their features and a model (no counterpart in the reference).  The data of both is
+ * float32 [rows, lines_per_row, line_stride]: the first line_len <= line_stride elements of a line are data, what lies behind
+ * them is neither read nor written.  Features [B, C, n_mels, Tf] are rows = B, lines_per_row = C * n_mels; a waveform
+ * [B, C, T] is rows = B, lines_per_row = C.  d_out is d_src itself (in place) or an array of the same layout apart from it.
+ * Device pointers only, asynchronous on hip_stream, nothing is read back.  rows == 0: nothing happens.
+ *
+ * alacgpu_normalize_meanvar_device: mean and variance per line over the valid elements, one launch.  For line l of row r,
+ * v = min(max(d_valid[r], 0), line_len) (d_valid: int64 [rows]; NULL: v = line_len) and
+ *   mean = (sum of x[0 .. v)) / v
+ *   var  = (sum of (x[i] - mean)^2) / v                      two passes, never E[x^2] - mean^2
+ *   y[i] = (x[i] - mean) / sqrt(var + eps)    for i < v      (x[i] - mean with scale 0; x[i] / sqrt(var + eps) with centre 0)
+ *   y[i] = 0                                  for v <= i < line_len
+ * v = 0 (d_valid[r] = -1 included) writes a line of zeros and reads nothing.  Every operation is one IEEE float32 operation,
+ * the divisions and the root correctly rounded, no multiply fused into an add.  The sums are float32 in a fixed order: with
+ * P = 64 for line_len <= 256 and P = 1024 above, partial j is ((0 + t[j]) + t[j + P]) + t[j + 2 P] ... in ascending index
+ * below v; each run of 64 partials is added as a tree of halves (q[j] += q[j + h], h = 32 .. 1) and the 16 sums of those
+ * runs by the same tree (h = 8 .. 1).  A constant line with eps = 0 is 0 / 0 = NaN; a NaN or an infinity inside 0 .. v
+ * reaches its own line and no other, one at or behind v nothing.  Lines of up to 256 elements are taken by a wave each, four
+ * to a workgroup, and held in registers between the passes; longer ones by a workgroup of 1024 threads each, held in LDS up
+ * to 8192 elements and read again from memory (the L2) above.  Nothing of the ctx is used but its device.
+ *
+ * alacgpu_normalize_top_device: the clamp relative to the maximum of a row, two launches, no atomics.  With mx the maximum
+ * of all lines_per_row * line_len elements of the row,
+ *   c = mx - top;  z = max(x, c);  z = z - mx (only with relative != 0);  y = (scale * z) + offset
+ * each operation rounded once to float32, the product and the sum apart.  A maximum keeps a NaN as np.max does: a row with a
+ * NaN anywhere is NaN everywhere, every other row is untouched by it; mx = +inf follows IEEE (c = +inf, and inf - inf with
+ * relative).  The result is therefore specified bit for bit, but for the sign of a zero.  Whisper's input is log10 mel power
+ * with top 8, scale 0.25, offset 1; decibels with a top_db of 80 are top 8, scale 10, offset 0 on log10 power.  The first
+ * launch writes the maximum of every part of a row -- 4096 consecutive elements, or the smallest multiple of 4096 that keeps
+ * a row within 1024 parts -- into the ctx's scratch [rows, parts], the second combines a row's parts and writes the result;
+ * both are grids of rows * parts workgroups.  Calls of one ctx share that scratch one after the other, whatever their
+ * streams (as alacgpu_compact_packets_device's do).
+ *
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx, d_src or d_out, a misaligned array (4; 8 for d_valid),
+ * lines_per_row 0, line_len 0 or above line_stride, d_src and d_out that overlap without being equal, an extent of 2^60
+ * bytes or more, 2^31 workgroups or more; eps negative or not finite, centre and scale both 0; top negative or not finite,
+ * scale or offset not finite.
+ */
+int alacgpu_normalize_meanvar_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t lines_per_row,
+                                     uint64_t line_stride, uint64_t line_len, const void* d_valid, int centre, int scale,
+                                     float eps, void* hip_stream);
+int alacgpu_normalize_top_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t lines_per_row,
+                                 uint64_t line_stride, uint64_t line_len, float top, float scale, float offset, int relative,
+                                 void* hip_stream);
+
 /* Single-packet drop-in for `int DecodeFrame(byte[] inbuffer, int[] outbuffer)` (AlacFile.cs:428):
  * writes the reference's own int[] layout (24-bit: one int per byte) and returns its byte count in
  * *out_bytes.  status as above (the C# shim rethrows the reference's exceptions from it). */

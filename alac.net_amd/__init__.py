@@ -77,6 +77,8 @@ SYMBOLS = {
                                                    C.c_float, _VP]),
     "alacgpu_normalize_top_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
                                                C.c_float, C.c_int, _VP]),
+    "alacgpu_mix_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _VP,
+                                     _VP, _VP]),
     "alacgpu_encode_max_packet_bytes": (C.c_size_t, [C.c_uint32, C.c_int, C.c_int]),
     "alacgpu_encode_device": (C.c_int, [_VP, _VP, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP, C.c_uint32,
                                         _VP, C.c_uint64, _VP, _VP, _VP]),
@@ -392,6 +394,18 @@ class AlacGpuContext(_Closing):
         Two launches, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
         rc = lib().alacgpu_normalize_top_device(self._ctx, _dp(d_src), _dp(d_out), rows, lines_per_row, line_stride, line_len, top,
                                                 scale, offset, int(bool(relative)), _VP(stream))
+        _check(rc, self._ctx)
+
+    def mix_device(self, d_src, d_out, d_noise, rows, channels, noise_channels, stride, noise_stride, frames, d_valid, d_noise_valid,
+                   d_ratio, stream=0):
+        """alacgpu_mix_device: y = x + g n, g = d_ratio[row] * sqrt(Ps / Pn), for every row of d_src (float32 device tensor,
+        planar [rows, channels, stride], the first `frames` of a plane are data) and d_noise ([rows, noise_channels,
+        noise_stride], noise_channels 1 or channels) over the first v = min(max(d_valid[row], 0), frames) frames, the noise's
+        first vn repeated where vn < v, into d_out (d_src itself or the same layout apart from it).  d_valid, d_noise_valid:
+        int64 device tensors [rows], or None for `frames`; d_ratio: float32 [rows], 0 for a row that gets no noise.  mix.py
+        states the arithmetic.  Two launches, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_mix_device(self._ctx, _dp(d_src), _dp(d_out), _dp(d_noise), rows, channels, noise_channels, stride,
+                                      noise_stride, frames, _dp(d_valid), _dp(d_noise_valid), _dp(d_ratio), _VP(stream))
         _check(rc, self._ctx)
 
     def set_output_format(self, fmt):
@@ -963,3 +977,5 @@ from .features import LogMel, log_mel, logmel_host, logmel_host_f32, mel_filterb
 
 # ---- normalised crops and features (alacgpu_normalize_meanvar_device, alacgpu_normalize_top_device) ------------------------------
 from .normalize import MeanVar, TopDb, normalize, normalize_host, normalize_host_f32  # noqa: E402
+# ---- noise at a target signal-to-noise ratio into crops and tensors (alacgpu_mix_device) ----------------------------------------
+from .mix import AddNoise, mix, mix_host, mix_host_f32  # noqa: E402

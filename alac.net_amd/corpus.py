@@ -17,6 +17,10 @@ from both tiers into a small staging blob in HBM, and the decode reads that.
 frames a crop needs are decoded as above into a scratch the corpus keeps, and one alacgpu_resample_device call (resample.py
 states the filter) resamples every crop out of it.
 
+`crops(..., mix=AddNoise(noise_corpus, snr_db))` adds noise from a second corpus at a signal-to-noise ratio drawn per crop
+(`Corpus._mixed_crops`): the noise crops are made by that corpus at the rate of the crops, and one alacgpu_mix_device call
+(mix.py states the arithmetic) adds them in place, in front of `features=` and `normalize=`.
+
 `Corpus(sources, mixed_rates=True)` takes files of different sample rates.  Crops of such a corpus exist at a target rate only;
 a step is the same method and the same launches, with a source window per crop in the plan
 (alacgpu_plan_crops_frames_device) and a filter table per row in the resampler (alacgpu_resample_rows_device).
@@ -346,6 +350,7 @@ class Corpus(_Closing):
         self._stage_room, self._stage_entries, self._stage_bytes = 0, 0, 0
         self._rs_scratch = None                           # crops at another rate: the decoded source crops
         self._ft_scratch = None                           # crops(features=): the crops the feature kernel reads
+        self._mix_scratch = None                          # crops(mix=): the noise crops, whichever corpus makes them
         self._rates, self._windows = {}, {}               # `_rate` per target rate; `_window` per (target rate or None, L)
         self._gpu = gpu if gpu is not None else AlacGpuContext(tb["cfgs"], device)
 
@@ -483,7 +488,7 @@ class Corpus(_Closing):
         if getattr(self, "_gpu", None) is not None:
             self._gpu.close()
             self._gpu = None
-            self._blob = self._plan = self._stage = self._stage_plan = self._rs_scratch = self._ft_scratch = None
+            self._blob = self._plan = self._stage = self._stage_plan = self._rs_scratch = self._ft_scratch = self._mix_scratch = None
         self._free_pinned()
 
     @property
@@ -597,8 +602,8 @@ class Corpus(_Closing):
             raise ValueError(f"crop {b} (source {int(f[b])}): frame offset {int(o[b])} outside 0 .. {int(totals[f[b]])}")
         return torch.from_numpy(f.astype(np.int32)).to(self._dev), torch.from_numpy(o).to(self._dev), True
 
-    def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True, features=None, normalize=None, sample_rate=None,
-              mono=False):
+    def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True, features=None, normalize=None, mix=None,
+              sample_rate=None, mono=False):
         """Decode crop b = frames frame_offsets[b] .. + num_frames of file files[b] for every b in ONE launch pair: returns
         (pcm [B, C, num_frames] on the device, zero behind lengths[b]; lengths [B], a DEVICE int64 tensor: min(num_frames,
         T_f - offset)).  float32 (default) or int32, as `load`.  files / frame_offsets: sequences, numpy arrays or torch
@@ -621,13 +626,22 @@ class Corpus(_Closing):
 
         normalize: a normalize.MeanVar or normalize.TopDb (`_normalized_crops`), applied in place behind everything above, on
         the same stream: bit for bit normalize.normalize(what the call returns without it, normalize, lengths).  By keyword, as
-        features, sample_rate and mono."""
+        features, sample_rate and mono.
+
+        mix: noise from a second corpus into the waveform (`_mixed_crops`), behind the waveform and in front of features and
+        normalize: a mix.AddNoise, whose draws are then made here from the device's default generator, or the pair
+        (AddNoise, draws) with the draws that its `draw(B, num_frames, rate of the crops)` returned.  Bit for bit
+        mix.mix(the crops without it, the noise crops, snr_db, lengths, their lengths).  By keyword."""
         import torch
 
+        if mix is not None:
+            mix = self._mix_spec(mix, dtype, sample_rate, mono)
         if normalize is not None:
-            return self._normalized_crops(normalize, files, frame_offsets, num_frames, dtype, out, check, features, sample_rate, mono)
+            return self._normalized_crops(normalize, files, frame_offsets, num_frames, dtype, out, check, features, sample_rate, mono, mix)
         if features is not None:
-            return self._feature_crops(files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, features)
+            return self._feature_crops(files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, features, mix)
+        if mix is not None:
+            return self._mixed_crops(mix, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono)
         if self.sample_rate is None and sample_rate is None:
             raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
         if self.sample_rate is None or (mono and self.channels == 2) or (sample_rate is not None and sample_rate != self.sample_rate):
@@ -657,7 +671,69 @@ class Corpus(_Closing):
             self._check_last(lengths, d_files, d_offs, L, K)
         return out, lengths
 
-    def _normalized_crops(self, how, files, frame_offsets, num_frames, dtype, out, check, features, sample_rate, mono):
+    def _mix_spec(self, mix, dtype, sample_rate, mono):
+        """crops(mix=) as the pair (AddNoise, draws or None), checked: ValueError for anything else, for int32 crops, for a
+        noise corpus that is closed, on another device or of a channel count the crops cannot take, and for crops without a
+        rate.  Nothing is done on the device."""
+        import torch
+
+        from .mix import AddNoise
+
+        aug, draws = mix if isinstance(mix, tuple) and len(mix) == 2 else (mix, None)
+        if not isinstance(aug, AddNoise):
+            raise ValueError(f"mix must be a mix.AddNoise or (AddNoise, what its draw() returned), not {mix!r}")
+        if draws is not None:
+            ok = isinstance(draws, tuple) and len(draws) == 3 and all(isinstance(t, torch.Tensor) and t.dim() == 1 for t in draws)
+            if not ok or not (draws[0].shape == draws[1].shape == draws[2].shape) or not draws[2].dtype.is_floating_point:
+                raise ValueError("the draws of mix= must be the three tensors (noise_files, noise_offsets, snr_db) of AddNoise.draw")
+            if any(t.device != self._dev for t in draws):
+                raise ValueError(f"the draws of mix= must be on {self._dev}")
+        if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
+            raise ValueError("noise is mixed into float32 crops")
+        noise = aug.noise
+        if noise._gpu is None:
+            raise ValueError("the noise corpus is closed")
+        if noise._dev != self._dev:
+            raise ValueError(f"the noise corpus is on {noise._dev}, the crops on {self._dev}")
+        if (self.sample_rate if sample_rate is None else sample_rate) is None:
+            raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=, and the noise a rate to crop at")
+        Co = 1 if mono else self.channels
+        if noise.channels != Co and noise.channels not in (1, 2):
+            raise ValueError(f"a noise corpus of {noise.channels} channels into crops of {Co}: it can become one channel from 1 or 2 only")
+        return aug, draws
+
+    def _mixed_crops(self, mix, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono):
+        """crops(..., mix=): the noise crops first -- noise.crops(noise_files, noise_offsets, num_frames, sample_rate=the rate
+        of the crops, mono=the noise corpus's channel count is not the crops', check=check) into a scratch THIS corpus keeps,
+        so that the noise corpus may be this one --, then the crops exactly as without mix, then ONE alacgpu_mix_device call
+        by the corpus's own context on the same stream adds the noise in place over lengths (mix.py states the arithmetic; a
+        noise crop shorter than the crop is repeated, a crop that drew NaN for its ratio or lies outside the corpus stays as
+        it is).  lengths, `check` and last_status() are those of the call without mix; with check=True the noise corpus's own
+        check runs too, and first."""
+        import torch
+
+        from .mix import _mix, snr_ratio
+
+        aug, draws = mix
+        noise = aug.noise
+        L = _frame_count("num_frames", num_frames)
+        self._open()
+        rate = self.sample_rate if sample_rate is None else sample_rate
+        B = int(files.shape[0]) if isinstance(files, torch.Tensor) and files.dim() == 1 else len(np.asarray(files))
+        if draws is None:
+            draws = aug.draw(B, L, sample_rate=rate)
+        nf, no, snr = draws
+        if nf.shape[0] != B:
+            raise ValueError(f"{nf.shape[0]} draws for {B} crops")
+        Co = 1 if mono else self.channels
+        Cn = Co if noise.channels == Co else 1
+        d_noise = self._scratch("_mix_scratch", (B, Cn, L))
+        _, noise_lengths = noise.crops(nf, no, L, out=d_noise, check=check, sample_rate=rate, mono=noise.channels != Co)
+        pcm, lengths = self.crops(files, frame_offsets, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono)
+        _mix(lambda: self._gpu, pcm, d_noise, lambda: snr_ratio(snr, B, self._dev), lengths, noise_lengths, pcm)
+        return pcm, lengths
+
+    def _normalized_crops(self, how, files, frame_offsets, num_frames, dtype, out, check, features, sample_rate, mono, mix=None):
         """crops(..., normalize=how): the crops, or with features=spec their features, are made exactly as without, then
         normalised in place by the corpus's own context on the same stream (normalize.py states the arithmetic).  A MeanVar
         takes every line over its valid elements -- lengths for PCM on every path, feat_lengths for features, so a crop outside
@@ -676,11 +752,11 @@ class Corpus(_Closing):
             if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
                 raise ValueError("a MeanVar normalises float32 crops")
         res, lengths = self.crops(files, frame_offsets, num_frames, dtype=dtype, out=out, check=check, features=features,
-                                  sample_rate=sample_rate, mono=mono)
+                                  sample_rate=sample_rate, mono=mono, mix=mix)
         _normalize(lambda: self._gpu, res, how, lengths, res)
         return res, lengths
 
-    def _feature_crops(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, spec):
+    def _feature_crops(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, spec, mix=None):
         """crops(..., features=spec): the crops are made exactly as without -- on the native or the `_rate_crops` path, `mono`
         honoured, `check` as there -- into a float32 scratch [B, Co, num_frames] the corpus keeps, then ONE
         alacgpu_logmel_device call on the same stream turns every row, the zeros behind its length included, into features
@@ -709,7 +785,7 @@ class Corpus(_Closing):
         Tf = spec.frames(L)
         out = self._out(out, (B, Co, spec.n_mels, Tf), torch.float32, zero=False)
         pcm = self._scratch("_ft_scratch", (B, Co, L))
-        _, lengths = self.crops(files, frame_offsets, L, out=pcm, check=check, sample_rate=sample_rate, mono=mono)
+        _, lengths = self.crops(files, frame_offsets, L, out=pcm, check=check, sample_rate=sample_rate, mono=mono, mix=mix)
         if B:
             window, basis, fb = spec.device_tables(self._dev)
             self._gpu.logmel_device(pcm, B, Co, L, L, spec.n_fft, spec.hop_length, spec.n_mels, window, basis, fb, spec.log_mode,
@@ -872,15 +948,18 @@ class Corpus(_Closing):
         return out, lengths
 
     def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True, features=None, normalize=None,
-                     sample_rate=None, mono=False):
+                     mix=None, sample_rate=None, mono=False):
         """`batch` crops of num_frames frames drawn on the device: files uniform over the corpus, the first frame uniform in
         0 .. max(T_f - num_frames, 0).  generator: a torch.Generator (of the corpus's device, or of the CPU: then the draws are
         made there and uploaded).  Returns (pcm, lengths, files, frame_offsets), the draws as device int64 tensors.
         sample_rate / mono as for `crops`: the frames, T_f included, then count at sample_rate.  features as for `crops`:
-        (feats, feat_lengths, files, frame_offsets).  normalize as for `crops`."""
+        (feats, feat_lengths, files, frame_offsets).  normalize as for `crops`.  mix as for `crops`; an AddNoise is drawn from
+        `generator`, behind the call's own two draws (AddNoise.draw states its four)."""
         import torch
 
         B, L = _frame_count("batch", batch), _frame_count("num_frames", num_frames)
+        if mix is not None:
+            mix = self._mix_spec(mix, dtype, sample_rate, mono)
         dev = generator.device if generator is not None else self._dev
         files = torch.randint(0, self.num_files, (B,), generator=generator, device=dev, dtype=torch.int64).to(self._dev)
         u = torch.rand(B, generator=generator, device=dev, dtype=torch.float64).to(self._dev)
@@ -889,8 +968,10 @@ class Corpus(_Closing):
         totals = self._d_num_frames if sample_rate is None else self._rate(sample_rate)["d_Ty"]
         span = (totals[files] - L).clamp(min=0)
         offs = torch.minimum(torch.floor(u * (span + 1).to(torch.float64)).to(torch.int64), span)
+        if mix is not None and mix[1] is None:
+            mix = (mix[0], mix[0].draw(B, L, sample_rate=self.sample_rate if sample_rate is None else sample_rate, generator=generator))
         pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,
-                                  features=features, normalize=normalize)
+                                  features=features, normalize=normalize, mix=mix)
         return pcm, lengths, files, offs
 
     def last_staged_bytes(self):

@@ -443,6 +443,7 @@ void alacgpu_destroy(alacgpu_ctx* ctx) {
     ctx->enc.destroy();
     ctx->scan.destroy();
     ctx->norm.destroy();
+    ctx->mix.destroy();
     if (ctx->d_cu_arrivals) cu_counters_release(ctx->device);
     if (ctx->h_frame) (void)hipHostFree(ctx->h_frame);
     if (ctx->d_cfgs) (void)hipFree(ctx->d_cfgs);

@@ -98,6 +98,7 @@ struct alacgpu_ctx {
     scratch enc;     // alacgpu_encode_device: per workgroup of a round alac_enc_items(smax) codes (buf[0]) and bit positions + 1 (buf[1])
     scratch scan;    // alacgpu_compact_packets_device, alacgpu_stage_packets_device: the partial sums of the scan's upper levels
     scratch norm;    // alacgpu_normalize_top_device: the maxima of the parts of every row, [rows, parts] floats
+    scratch mix;     // alacgpu_mix_device: the sums of the squares of the signal and the noise over the parts of every row, [rows, parts, 2] floats
     std::string last_error;
 };
 

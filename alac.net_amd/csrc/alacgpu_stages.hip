@@ -1,5 +1,5 @@
 // alacgpu_stages.hip -- C ABI of include/alacgpu.h, the stages around the decode: the crop planner, the scan with the packet
-// compaction and staging, the resamplers, log-mel, the normalisations and the encoder.  Of the ctx they use the device, the cfgs, last_error and
+// compaction and staging, the resamplers, log-mel, the noise mix, the normalisations and the encoder.  Of the ctx they use the device, the cfgs, last_error and
 // their own scratch; the decode path is alacgpu_api.hip.  No CPU fallback here either: every stage is its kernels.
 #include <algorithm>
 #include <cmath>
@@ -8,6 +8,7 @@
 #include "alac_resample.h"
 #include "alac_features.h"
 #include "alac_normalize.h"
+#include "alac_mix.h"
 #include "alac_encode.h"
 #include "alacgpu_ctx.h"
 
@@ -187,6 +188,18 @@ bool normalize_args_ok(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_
     const uint64_t extent = lines ? sizeof(float) * ((lines - 1u) * line_stride + line_len) : 0u;
     const uintptr_t a = (uintptr_t)d_src, b = (uintptr_t)d_out;
     return a == b || a + extent <= b || b + extent <= a;
+}
+
+// The bytes from the first element of float32 [planes, stride], of which the first `len` of a plane are data, to behind its
+// last; false: 2^60 bytes or more
+bool planes_extent(uint64_t planes, uint64_t stride, uint64_t len, uint64_t& extent) {
+    if (stride > (1ull << 60) / sizeof(float) / std::max<uint64_t>(planes, 1u)) return false;
+    extent = planes ? sizeof(float) * ((planes - 1u) * stride + len) : 0u;
+    return true;
+}
+
+bool apart(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+    return (uintptr_t)a + a_bytes <= (uintptr_t)b || (uintptr_t)b + b_bytes <= (uintptr_t)a;
 }
 
 }  // namespace
@@ -464,6 +477,52 @@ int alacgpu_normalize_top_device(alacgpu_ctx* ctx, const void* d_src, void* d_ou
     HIP_TRY(ctx, hipLaunchKernel((const void*)alac_top_apply_kernel, dim3((uint32_t)grid), dim3(ALAC_TOP_THREADS), kargs, 0, stream));
     HIP_TRY(ctx, hipGetLastError());
     return ctx->norm.release(ctx, stream);
+}
+
+int alacgpu_mix_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, const void* d_noise, uint32_t rows, uint32_t channels,
+                       uint32_t noise_channels, uint64_t stride, uint64_t noise_stride, uint64_t frames, const void* d_valid,
+                       const void* d_noise_valid, const void* d_ratio, void* hip_stream) {
+    if (!ctx || !args_ok({{d_src, 4}, {d_out, 4}, {d_noise, 4}, {d_valid, 8, false}, {d_noise_valid, 8, false}, {d_ratio, 4}}))
+        return ALACGPU_ERR_BAD_ARG;
+    if (channels == 0 || (noise_channels != 1u && noise_channels != channels) || frames == 0 || frames > stride || frames > noise_stride)
+        return ALACGPU_ERR_BAD_ARG;
+    uint64_t extent, noise_extent;
+    if (!planes_extent((uint64_t)rows * channels, stride, frames, extent) ||
+        !planes_extent((uint64_t)rows * noise_channels, noise_stride, frames, noise_extent))
+        return ALACGPU_ERR_BAD_ARG;
+    if ((d_src != d_out && !apart(d_src, extent, d_out, extent)) || !apart(d_noise, noise_extent, d_out, extent)) return ALACGPU_ERR_BAD_ARG;
+    const uint32_t parts = alac_mix_parts(frames);
+    const uint64_t grid = (uint64_t)rows * parts;
+    if (grid > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const size_t need = 2u * sizeof(float) * (size_t)grid;
+    int rc = ctx->mix.acquire(ctx, stream, need, align_up(need + need / 4, 4096));
+    if (rc) return rc;
+    const auto wide = [](const void* base, uint64_t plane_stride) { return ((uintptr_t)base & 15u) == 0u && (plane_stride & 3u) == 0u; };
+    alac_mix_params p;
+    p.src = (const float*)d_src;
+    p.out = (float*)d_out;
+    p.noise = (const float*)d_noise;
+    p.valid = (const int64_t*)d_valid;
+    p.noise_valid = (const int64_t*)d_noise_valid;
+    p.ratio = (const float*)d_ratio;
+    p.sums = (float*)ctx->mix.buf[0];
+    p.channels = channels;
+    p.noise_channels = noise_channels;
+    p.stride = stride;
+    p.noise_stride = noise_stride;
+    p.frames = frames;
+    p.part_frames = alac_mix_part_frames(frames);
+    p.parts = parts;
+    p.vec = wide(d_src, stride) && wide(d_out, stride) ? 1u : 0u;
+    p.noise_vec = wide(d_noise, noise_stride) ? 1u : 0u;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_mix_reduce_kernel, dim3((uint32_t)grid), dim3(ALAC_MIX_THREADS), kargs, 0, stream));
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_mix_apply_kernel, dim3((uint32_t)grid), dim3(ALAC_MIX_THREADS), kargs, 0, stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ctx->mix.release(ctx, stream);
 }
 
 size_t alacgpu_encode_max_packet_bytes(uint32_t frames, int sample_size, int channels) {

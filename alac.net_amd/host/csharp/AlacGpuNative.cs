@@ -109,6 +109,14 @@ namespace ALACdotNET.Decoder
         /// + offset into dOut; a row with a NaN is NaN throughout.  Two launches, asynchronous on hipStream.</summary>
         [DllImport(Lib)] public static extern int alacgpu_normalize_top_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, uint rows,
             uint linesPerRow, ulong lineStride, ulong lineLen, float top, float scale, float offset, int relative, IntPtr hipStream);
+        /// <summary>Noise at a target signal-to-noise ratio into planar float crops in device memory (dSrc, dOut
+        /// [rows, channels, stride], dNoise [rows, noiseChannels, noiseStride], noiseChannels 1 or channels; the first frames of a
+        /// plane are data): y = x + g n with g = dRatio[row] * sqrt(Ps / Pn) over the first dValid[row] frames of the signal and
+        /// dNoiseValid[row] of the noise (long[rows] or IntPtr.Zero for all), the noise repeated where it is the shorter; a ratio
+        /// of 0 leaves the row as it is.  dOut is dSrc itself or apart from it.  Two launches, asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_mix_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, IntPtr dNoise, uint rows,
+            uint channels, uint noiseChannels, ulong stride, ulong noiseStride, ulong frames, IntPtr dValid, IntPtr dNoiseValid,
+            IntPtr dRatio, IntPtr hipStream);
         /// <summary>Encode PCM in device memory (int32 or float32, interleaved or planar) to ALAC packets in device memory, one
         /// run of frames per packet, packet p at dPackets + p * slotBytes; asynchronous on hipStream.</summary>
         [DllImport(Lib)] public static extern UIntPtr alacgpu_encode_max_packet_bytes(uint frames, int sampleSize, int channels);

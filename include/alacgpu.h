@@ -502,6 +502,41 @@ int alacgpu_normalize_top_device(alacgpu_ctx* ctx, const void* d_src, void* d_ou
                                  uint64_t line_stride, uint64_t line_len, float top, float scale, float offset, int relative,
                                  void* hip_stream);
 
+/*
+ * alacgpu_mix_device: noise at a target signal-to-noise ratio into the crops, in front of the features (no counterpart in the
+ * reference); two launches, no atomics.  The layout is planar float32: d_src and d_out [rows, channels, stride], d_noise
+ * [rows, noise_channels, noise_stride] with noise_channels 1 (the one channel goes into every channel of the signal) or
+ * channels; the first `frames` elements of a plane are data, what lies behind them is neither read nor written.  d_out is
+ * d_src itself (in place) or an array of that layout apart from it.  For row r, with v = min(max(d_valid[r], 0), frames),
+ * vn = min(max(d_noise_valid[r], 0), frames) (int64 [rows]; NULL: frames) and a = d_ratio[r] (float32 [rows]; the amplitude
+ * ratio 10^(-snr_db / 20), computed by the caller: a power of ten is not correctly rounded and is not this kernel's),
+ *   Ps = (sum over c, i < v  of x[c, i]^2) / fl(channels * v)
+ *   Pn = (sum over c, i < vn of n[c, i]^2) / fl(noise_channels * vn)       over the noise's own frames, not the repeated ones
+ *   g  = a * sqrt(Ps / Pn)                                                 but g = 0 where a == 0, v == 0, vn == 0 or Pn == 0
+ *   y[c, i] = x[c, i] + g * n[c mod noise_channels, i mod vn]   for i < v      noise shorter than the crop is repeated
+ *   y[c, i] = x[c, i]                                           for v <= i < frames (in place: untouched)
+ * Where g == 0 the row's noise is not read by the second launch and y is x bit for bit (in place: nothing is written); a row
+ * with a == 0, v == 0 or vn == 0 reads no noise at all, so "no noise for this crop" is a ratio of 0 and a silent noise clip
+ * cannot make a NaN.  Every operation is one IEEE float32 operation, the divisions and the root correctly rounded, no multiply
+ * fused into an add; the counts are converted with one rounding.  Anything else follows IEEE: a negative, infinite or NaN
+ * ratio is data; a NaN or an infinity in x below v, or in n below vn of a row with a != 0, reaches that row and no other; one
+ * at or behind v (vn) is never read; Ps == 0 gives g = 0 by the formula.  The sums are float32 in a fixed order: a row is cut
+ * into parts of 4096 frames (the smallest multiple of 4096 that keeps a row within 256 parts); within a part partial j of
+ * 1024 takes the squares of the frames j, j + 1024, ... of the part, channel after channel, in ascending order; the 4
+ * partials of a thread, the 64 sums of a wave and the 4 of a workgroup are each added as a tree of halves (q[j] += q[j + h],
+ * h = 2, 1; 32 .. 1; 2, 1), and the parts of a row in ascending order.  The first launch writes both sums of every part into
+ * the ctx's scratch [rows, parts, 2], the second combines a row's parts, computes g and writes its part of y; both are grids
+ * of rows * parts workgroups, with 16-byte loads and stores where an array's base and stride are multiples of 16 bytes.
+ * Calls of one ctx share that scratch one after the other, whatever their streams (as alacgpu_normalize_top_device's do).
+ * Device pointers only, asynchronous on hip_stream, nothing is read back.  rows == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx, d_src, d_out, d_noise or d_ratio, a misaligned array (4; 8 for
+ * d_valid and d_noise_valid), channels 0, noise_channels neither 1 nor channels, frames 0 or above either stride, d_src and
+ * d_out that overlap without being equal, d_noise overlapping d_out, an extent of 2^60 bytes or more, 2^31 workgroups or more.
+ */
+int alacgpu_mix_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, const void* d_noise, uint32_t rows, uint32_t channels,
+                       uint32_t noise_channels, uint64_t stride, uint64_t noise_stride, uint64_t frames,
+                       const void* d_valid, const void* d_noise_valid, const void* d_ratio, void* hip_stream);
+
 /* Single-packet drop-in for `int DecodeFrame(byte[] inbuffer, int[] outbuffer)` (AlacFile.cs:428):
  * writes the reference's own int[] layout (24-bit: one int per byte) and returns its byte count in
  * *out_bytes.  status as above (the C# shim rethrows the reference's exceptions from it). */

@@ -79,6 +79,8 @@ SYMBOLS = {
                                                C.c_float, C.c_int, _VP]),
     "alacgpu_mix_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _VP,
                                      _VP, _VP]),
+    "alacgpu_reverb_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
+                                        C.c_uint64, _VP, _VP, _VP]),
     "alacgpu_encode_max_packet_bytes": (C.c_size_t, [C.c_uint32, C.c_int, C.c_int]),
     "alacgpu_encode_device": (C.c_int, [_VP, _VP, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP, C.c_uint32,
                                         _VP, C.c_uint64, _VP, _VP, _VP]),
@@ -406,6 +408,18 @@ class AlacGpuContext(_Closing):
         states the arithmetic.  Two launches, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
         rc = lib().alacgpu_mix_device(self._ctx, _dp(d_src), _dp(d_out), _dp(d_noise), rows, channels, noise_channels, stride,
                                       noise_stride, frames, _dp(d_valid), _dp(d_noise_valid), _dp(d_ratio), _VP(stream))
+        _check(rc, self._ctx)
+
+    def reverb_device(self, d_src, d_out, d_rir, rows, channels, rir_channels, stride, rir_stride, frames, rir_frames, d_valid,
+                      d_rir_valid, stream=0):
+        """alacgpu_reverb_device: every row of d_src (float32 device tensor, planar [rows, channels, stride], the first `frames`
+        of a plane are data) convolved with its impulse response in d_rir ([rows, rir_channels, rir_stride], rir_channels 1 or
+        channels, the first `rir_frames` are data), aligned on the response's direct path and scaled to unit energy, over the
+        first v = min(max(d_valid[row], 0), frames) frames, into d_out (d_src itself or the same layout apart from it).
+        d_valid, d_rir_valid: int64 device tensors [rows], or None for all; a row whose d_rir_valid is 0 stays as it is.
+        reverb.py states the arithmetic.  Two launches, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_reverb_device(self._ctx, _dp(d_src), _dp(d_out), _dp(d_rir), rows, channels, rir_channels, stride,
+                                         rir_stride, frames, rir_frames, _dp(d_valid), _dp(d_rir_valid), _VP(stream))
         _check(rc, self._ctx)
 
     def set_output_format(self, fmt):
@@ -979,3 +993,5 @@ from .features import LogMel, log_mel, logmel_host, logmel_host_f32, mel_filterb
 from .normalize import MeanVar, TopDb, normalize, normalize_host, normalize_host_f32  # noqa: E402
 # ---- noise at a target signal-to-noise ratio into crops and tensors (alacgpu_mix_device) ----------------------------------------
 from .mix import AddNoise, mix, mix_host, mix_host_f32  # noqa: E402
+# ---- room reverberation into crops and tensors (alacgpu_reverb_device) ------------------------------------------------------------
+from .reverb import Reverb, reverb, reverb_host, reverb_host_f32  # noqa: E402

@@ -21,6 +21,10 @@ states the filter) resamples every crop out of it.
 (`Corpus._mixed_crops`): the noise crops are made by that corpus at the rate of the crops, and one alacgpu_mix_device call
 (mix.py states the arithmetic) adds them in place, in front of `features=` and `normalize=`.
 
+`crops(..., reverb=Reverb(rir_corpus))` convolves every crop with a room impulse response drawn from a second corpus
+(`Corpus._reverb_crops`): the responses are cropped by that corpus at the rate of the crops, and one alacgpu_reverb_device
+call (reverb.py states the arithmetic) reverberates the crops in place, behind the waveform and in front of `mix=`.
+
 `Corpus(sources, mixed_rates=True)` takes files of different sample rates.  Crops of such a corpus exist at a target rate only;
 a step is the same method and the same launches, with a source window per crop in the plan
 (alacgpu_plan_crops_frames_device) and a filter table per row in the resampler (alacgpu_resample_rows_device).
@@ -351,6 +355,7 @@ class Corpus(_Closing):
         self._rs_scratch = None                           # crops at another rate: the decoded source crops
         self._ft_scratch = None                           # crops(features=): the crops the feature kernel reads
         self._mix_scratch = None                          # crops(mix=): the noise crops, whichever corpus makes them
+        self._reverb_scratch = None                       # crops(reverb=): the impulse responses of the crops
         self._rates, self._windows = {}, {}               # `_rate` per target rate; `_window` per (target rate or None, L)
         self._gpu = gpu if gpu is not None else AlacGpuContext(tb["cfgs"], device)
 
@@ -488,7 +493,7 @@ class Corpus(_Closing):
         if getattr(self, "_gpu", None) is not None:
             self._gpu.close()
             self._gpu = None
-            self._blob = self._plan = self._stage = self._stage_plan = self._rs_scratch = self._ft_scratch = self._mix_scratch = None
+            self._blob = self._plan = self._stage = self._stage_plan = self._rs_scratch = self._ft_scratch = self._mix_scratch = self._reverb_scratch = None
         self._free_pinned()
 
     @property
@@ -603,7 +608,7 @@ class Corpus(_Closing):
         return torch.from_numpy(f.astype(np.int32)).to(self._dev), torch.from_numpy(o).to(self._dev), True
 
     def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True, features=None, normalize=None, mix=None,
-              sample_rate=None, mono=False):
+              reverb=None, sample_rate=None, mono=False):
         """Decode crop b = frames frame_offsets[b] .. + num_frames of file files[b] for every b in ONE launch pair: returns
         (pcm [B, C, num_frames] on the device, zero behind lengths[b]; lengths [B], a DEVICE int64 tensor: min(num_frames,
         T_f - offset)).  float32 (default) or int32, as `load`.  files / frame_offsets: sequences, numpy arrays or torch
@@ -631,17 +636,28 @@ class Corpus(_Closing):
         mix: noise from a second corpus into the waveform (`_mixed_crops`), behind the waveform and in front of features and
         normalize: a mix.AddNoise, whose draws are then made here from the device's default generator, or the pair
         (AddNoise, draws) with the draws that its `draw(B, num_frames, rate of the crops)` returned.  Bit for bit
-        mix.mix(the crops without it, the noise crops, snr_db, lengths, their lengths).  By keyword."""
+        mix.mix(the crops without it, the noise crops, snr_db, lengths, their lengths).  By keyword.
+
+        reverb: room reverberation of the waveform (`_reverb_crops`), behind the waveform and in front of mix, features and
+        normalize: a reverb.Reverb, whose draws are then made here from the device's default generator, or the pair
+        (Reverb, draws) with the draws that its `draw(B)` returned.  Bit for bit reverb.reverb(the crops without it, the
+        first frames of the drawn responses at the rate of the crops, lengths, their lengths, 0 where a crop drew none).  By
+        keyword."""
         import torch
 
         if mix is not None:
             mix = self._mix_spec(mix, dtype, sample_rate, mono)
+        if reverb is not None:
+            reverb = self._reverb_spec(reverb, dtype, sample_rate, mono)
         if normalize is not None:
-            return self._normalized_crops(normalize, files, frame_offsets, num_frames, dtype, out, check, features, sample_rate, mono, mix)
+            return self._normalized_crops(normalize, files, frame_offsets, num_frames, dtype, out, check, features, sample_rate, mono, mix,
+                                          reverb)
         if features is not None:
-            return self._feature_crops(files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, features, mix)
+            return self._feature_crops(files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, features, mix, reverb)
         if mix is not None:
-            return self._mixed_crops(mix, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono)
+            return self._mixed_crops(mix, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, reverb)
+        if reverb is not None:
+            return self._reverb_crops(reverb, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono)
         if self.sample_rate is None and sample_rate is None:
             raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
         if self.sample_rate is None or (mono and self.channels == 2) or (sample_rate is not None and sample_rate != self.sample_rate):
@@ -702,7 +718,71 @@ class Corpus(_Closing):
             raise ValueError(f"a noise corpus of {noise.channels} channels into crops of {Co}: it can become one channel from 1 or 2 only")
         return aug, draws
 
-    def _mixed_crops(self, mix, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono):
+    def _reverb_spec(self, reverb, dtype, sample_rate, mono):
+        """crops(reverb=) as the pair (Reverb, draws or None), checked: ValueError for anything else, for int32 crops, for a
+        corpus of responses that is closed, on another device or of a channel count the crops cannot take, and for crops
+        without a rate.  Nothing is done on the device."""
+        import torch
+
+        from .reverb import Reverb
+
+        aug, draws = reverb if isinstance(reverb, tuple) and len(reverb) == 2 else (reverb, None)
+        if not isinstance(aug, Reverb):
+            raise ValueError(f"reverb must be a reverb.Reverb or (Reverb, what its draw() returned), not {reverb!r}")
+        if draws is not None:
+            ok = isinstance(draws, tuple) and len(draws) == 2 and all(isinstance(t, torch.Tensor) and t.dim() == 1 for t in draws)
+            if not ok or draws[0].shape != draws[1].shape or draws[0].dtype.is_floating_point or draws[1].dtype != torch.bool:
+                raise ValueError("the draws of reverb= must be the two tensors (rir_files, keep) of Reverb.draw")
+            if any(t.device != self._dev for t in draws):
+                raise ValueError(f"the draws of reverb= must be on {self._dev}")
+        if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
+            raise ValueError("float32 crops are reverberated")
+        rirs = aug.rirs
+        if rirs._gpu is None:
+            raise ValueError("the corpus of impulse responses is closed")
+        if rirs._dev != self._dev:
+            raise ValueError(f"the corpus of impulse responses is on {rirs._dev}, the crops on {self._dev}")
+        if (self.sample_rate if sample_rate is None else sample_rate) is None:
+            raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=, and the responses a rate to crop at")
+        Co = 1 if mono else self.channels
+        if rirs.channels != Co and rirs.channels not in (1, 2):
+            raise ValueError(f"impulse responses of {rirs.channels} channels into crops of {Co}: they can become one channel from 1 or 2 only")
+        return aug, draws
+
+    def _reverb_crops(self, reverb, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono):
+        """crops(..., reverb=): the responses first -- rirs.crops(rir_files, 0, K, sample_rate=the rate of the crops, mono=the
+        corpus of responses' channel count is not the crops', check=check), K = Reverb.frames(that rate), into a scratch THIS
+        corpus keeps --, then the crops exactly as without reverb, then ONE alacgpu_reverb_device call by the corpus's own
+        context on the same stream reverberates them in place over lengths (reverb.py states the arithmetic), a crop that drew
+        none (keep False: a response of 0 frames) or lies outside the corpus staying as it is.  lengths, `check` and
+        last_status() are those of the call without reverb; with check=True the corpus of responses' own check runs too, and
+        first."""
+        import torch
+
+        from .reverb import _reverb
+
+        aug, draws = reverb
+        rirs = aug.rirs
+        L = _frame_count("num_frames", num_frames)
+        self._open()
+        rate = self.sample_rate if sample_rate is None else sample_rate
+        B = int(files.shape[0]) if isinstance(files, torch.Tensor) and files.dim() == 1 else len(np.asarray(files))
+        if draws is None:
+            draws = aug.draw(B)
+        rf, keep = draws
+        if rf.shape[0] != B:
+            raise ValueError(f"{rf.shape[0]} draws for {B} crops")
+        K = aug.frames(rate)
+        Co = 1 if mono else self.channels
+        Ch = Co if rirs.channels == Co else 1
+        d_rir = self._scratch("_reverb_scratch", (B, Ch, K))
+        _, rir_lengths = rirs.crops(rf, torch.zeros(B, dtype=torch.int64, device=self._dev), K, out=d_rir, check=check, sample_rate=rate,
+                                    mono=rirs.channels != Co)
+        pcm, lengths = self.crops(files, frame_offsets, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono)
+        _reverb(lambda: self._gpu, pcm, d_rir, lengths, torch.where(keep, rir_lengths, 0), pcm)
+        return pcm, lengths
+
+    def _mixed_crops(self, mix, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, reverb=None):
         """crops(..., mix=): the noise crops first -- noise.crops(noise_files, noise_offsets, num_frames, sample_rate=the rate
         of the crops, mono=the noise corpus's channel count is not the crops', check=check) into a scratch THIS corpus keeps,
         so that the noise corpus may be this one --, then the crops exactly as without mix, then ONE alacgpu_mix_device call
@@ -729,11 +809,12 @@ class Corpus(_Closing):
         Cn = Co if noise.channels == Co else 1
         d_noise = self._scratch("_mix_scratch", (B, Cn, L))
         _, noise_lengths = noise.crops(nf, no, L, out=d_noise, check=check, sample_rate=rate, mono=noise.channels != Co)
-        pcm, lengths = self.crops(files, frame_offsets, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono)
+        pcm, lengths = self.crops(files, frame_offsets, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,
+                                  reverb=reverb)
         _mix(lambda: self._gpu, pcm, d_noise, lambda: snr_ratio(snr, B, self._dev), lengths, noise_lengths, pcm)
         return pcm, lengths
 
-    def _normalized_crops(self, how, files, frame_offsets, num_frames, dtype, out, check, features, sample_rate, mono, mix=None):
+    def _normalized_crops(self, how, files, frame_offsets, num_frames, dtype, out, check, features, sample_rate, mono, mix=None, reverb=None):
         """crops(..., normalize=how): the crops, or with features=spec their features, are made exactly as without, then
         normalised in place by the corpus's own context on the same stream (normalize.py states the arithmetic).  A MeanVar
         takes every line over its valid elements -- lengths for PCM on every path, feat_lengths for features, so a crop outside
@@ -752,11 +833,11 @@ class Corpus(_Closing):
             if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
                 raise ValueError("a MeanVar normalises float32 crops")
         res, lengths = self.crops(files, frame_offsets, num_frames, dtype=dtype, out=out, check=check, features=features,
-                                  sample_rate=sample_rate, mono=mono, mix=mix)
+                                  sample_rate=sample_rate, mono=mono, mix=mix, reverb=reverb)
         _normalize(lambda: self._gpu, res, how, lengths, res)
         return res, lengths
 
-    def _feature_crops(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, spec, mix=None):
+    def _feature_crops(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, spec, mix=None, reverb=None):
         """crops(..., features=spec): the crops are made exactly as without -- on the native or the `_rate_crops` path, `mono`
         honoured, `check` as there -- into a float32 scratch [B, Co, num_frames] the corpus keeps, then ONE
         alacgpu_logmel_device call on the same stream turns every row, the zeros behind its length included, into features
@@ -785,7 +866,7 @@ class Corpus(_Closing):
         Tf = spec.frames(L)
         out = self._out(out, (B, Co, spec.n_mels, Tf), torch.float32, zero=False)
         pcm = self._scratch("_ft_scratch", (B, Co, L))
-        _, lengths = self.crops(files, frame_offsets, L, out=pcm, check=check, sample_rate=sample_rate, mono=mono, mix=mix)
+        _, lengths = self.crops(files, frame_offsets, L, out=pcm, check=check, sample_rate=sample_rate, mono=mono, mix=mix, reverb=reverb)
         if B:
             window, basis, fb = spec.device_tables(self._dev)
             self._gpu.logmel_device(pcm, B, Co, L, L, spec.n_fft, spec.hop_length, spec.n_mels, window, basis, fb, spec.log_mode,
@@ -948,18 +1029,21 @@ class Corpus(_Closing):
         return out, lengths
 
     def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True, features=None, normalize=None,
-                     mix=None, sample_rate=None, mono=False):
+                     mix=None, reverb=None, sample_rate=None, mono=False):
         """`batch` crops of num_frames frames drawn on the device: files uniform over the corpus, the first frame uniform in
         0 .. max(T_f - num_frames, 0).  generator: a torch.Generator (of the corpus's device, or of the CPU: then the draws are
         made there and uploaded).  Returns (pcm, lengths, files, frame_offsets), the draws as device int64 tensors.
         sample_rate / mono as for `crops`: the frames, T_f included, then count at sample_rate.  features as for `crops`:
         (feats, feat_lengths, files, frame_offsets).  normalize as for `crops`.  mix as for `crops`; an AddNoise is drawn from
-        `generator`, behind the call's own two draws (AddNoise.draw states its four)."""
+        `generator`, behind the call's own two draws (AddNoise.draw states its four).  reverb as for `crops`; a Reverb is
+        drawn from `generator` behind those (Reverb.draw states its two)."""
         import torch
 
         B, L = _frame_count("batch", batch), _frame_count("num_frames", num_frames)
         if mix is not None:
             mix = self._mix_spec(mix, dtype, sample_rate, mono)
+        if reverb is not None:
+            reverb = self._reverb_spec(reverb, dtype, sample_rate, mono)
         dev = generator.device if generator is not None else self._dev
         files = torch.randint(0, self.num_files, (B,), generator=generator, device=dev, dtype=torch.int64).to(self._dev)
         u = torch.rand(B, generator=generator, device=dev, dtype=torch.float64).to(self._dev)
@@ -970,8 +1054,10 @@ class Corpus(_Closing):
         offs = torch.minimum(torch.floor(u * (span + 1).to(torch.float64)).to(torch.int64), span)
         if mix is not None and mix[1] is None:
             mix = (mix[0], mix[0].draw(B, L, sample_rate=self.sample_rate if sample_rate is None else sample_rate, generator=generator))
+        if reverb is not None and reverb[1] is None:
+            reverb = (reverb[0], reverb[0].draw(B, generator=generator))
         pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,
-                                  features=features, normalize=normalize, mix=mix)
+                                  features=features, normalize=normalize, mix=mix, reverb=reverb)
         return pcm, lengths, files, offs
 
     def last_staged_bytes(self):

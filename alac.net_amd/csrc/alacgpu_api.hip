@@ -444,6 +444,8 @@ void alacgpu_destroy(alacgpu_ctx* ctx) {
     ctx->scan.destroy();
     ctx->norm.destroy();
     ctx->mix.destroy();
+    ctx->reverb.destroy();
+    if (ctx->d_reverb_twiddles) (void)hipFree(ctx->d_reverb_twiddles);
     if (ctx->d_cu_arrivals) cu_counters_release(ctx->device);
     if (ctx->h_frame) (void)hipHostFree(ctx->h_frame);
     if (ctx->d_cfgs) (void)hipFree(ctx->d_cfgs);

@@ -1,14 +1,16 @@
 // alacgpu_stages.hip -- C ABI of include/alacgpu.h, the stages around the decode: the crop planner, the scan with the packet
-// compaction and staging, the resamplers, log-mel, the noise mix, the normalisations and the encoder.  Of the ctx they use the device, the cfgs, last_error and
+// compaction and staging, the resamplers, log-mel, the reverberation, the noise mix, the normalisations and the encoder.  Of the ctx they use the device, the cfgs, last_error and
 // their own scratch; the decode path is alacgpu_api.hip.  No CPU fallback here either: every stage is its kernels.
 #include <algorithm>
 #include <cmath>
+#include <vector>
 
 #include "alac_corpus.h"
 #include "alac_resample.h"
 #include "alac_features.h"
 #include "alac_normalize.h"
 #include "alac_mix.h"
+#include "alac_reverb.h"
 #include "alac_encode.h"
 #include "alacgpu_ctx.h"
 
@@ -477,6 +479,74 @@ int alacgpu_normalize_top_device(alacgpu_ctx* ctx, const void* d_src, void* d_ou
     HIP_TRY(ctx, hipLaunchKernel((const void*)alac_top_apply_kernel, dim3((uint32_t)grid), dim3(ALAC_TOP_THREADS), kargs, 0, stream));
     HIP_TRY(ctx, hipGetLastError());
     return ctx->norm.release(ctx, stream);
+}
+
+int alacgpu_reverb_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, const void* d_rir, uint32_t rows, uint32_t channels,
+                          uint32_t rir_channels, uint64_t stride, uint64_t rir_stride, uint64_t frames, uint64_t rir_frames,
+                          const void* d_valid, const void* d_rir_valid, void* hip_stream) {
+    if (!ctx || !args_ok({{d_src, 4}, {d_out, 4}, {d_rir, 4}, {d_valid, 8, false}, {d_rir_valid, 8, false}})) return ALACGPU_ERR_BAD_ARG;
+    if (channels == 0 || (rir_channels != 1u && rir_channels != channels) || frames == 0 || frames > stride || rir_frames == 0 ||
+        rir_frames > rir_stride)
+        return ALACGPU_ERR_BAD_ARG;
+    uint64_t extent, rir_extent;
+    if (!planes_extent((uint64_t)rows * channels, stride, frames, extent) ||
+        !planes_extent((uint64_t)rows * rir_channels, rir_stride, rir_frames, rir_extent))
+        return ALACGPU_ERR_BAD_ARG;
+    if ((d_src != d_out && !apart(d_src, extent, d_out, extent)) || !apart(d_rir, rir_extent, d_out, extent)) return ALACGPU_ERR_BAD_ARG;
+    // (frames and rir_frames are below 2^58: the sums fit)
+    const uint64_t x_blocks = alac_reverb_x_blocks(frames), parts = alac_reverb_parts(rir_frames);
+    const uint64_t out_blocks = alac_reverb_out_blocks(frames, rir_frames);
+    if (x_blocks > 0x7FFFFFFFull / channels || parts > 0x7FFFFFFFull / rir_channels || out_blocks > 0x7FFFFFFFull / channels)
+        return ALACGPU_ERR_BAD_ARG;
+    const uint64_t units = channels * x_blocks + rir_channels * parts + 1u;
+    if (units * std::max<uint64_t>(rows, 1u) > 0x7FFFFFFFull || out_blocks * channels * std::max<uint64_t>(rows, 1u) > 0x7FFFFFFFull)
+        return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (!ctx->d_reverb_twiddles) {                          // once per ctx: exp(-2 pi i k / N) in double, rounded once
+        std::vector<float2> table(ALAC_REVERB_N);
+        for (uint32_t k = 0; k < ALAC_REVERB_N; k++) {
+            const double a = 2.0 * 3.14159265358979323846 * (double)k / (double)ALAC_REVERB_N;
+            table[k] = make_float2((float)std::cos(a), (float)-std::sin(a));
+        }
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_reverb_twiddles, sizeof(float2) * ALAC_REVERB_N));
+        const hipError_t e = hipMemcpy(ctx->d_reverb_twiddles, table.data(), sizeof(float2) * ALAC_REVERB_N, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(ctx->d_reverb_twiddles);
+            ctx->d_reverb_twiddles = nullptr;
+            HIP_TRY(ctx, e);
+        }
+    }
+    const size_t spectra = sizeof(float2) * ALAC_REVERB_N * (size_t)(units - 1u) * rows;
+    const size_t need = spectra + sizeof(alac_reverb_row) * (size_t)rows;
+    int rc = ctx->reverb.acquire(ctx, stream, need, align_up(need + need / 4, 4096));
+    if (rc) return rc;
+    alac_reverb_params p;
+    p.src = (const float*)d_src;
+    p.out = (float*)d_out;
+    p.rir = (const float*)d_rir;
+    p.valid = (const int64_t*)d_valid;
+    p.rir_valid = (const int64_t*)d_rir_valid;
+    p.twiddles = (const float2*)ctx->d_reverb_twiddles;
+    p.spectra = (float2*)ctx->reverb.buf[0];
+    p.verdict = (alac_reverb_row*)((char*)ctx->reverb.buf[0] + spectra);
+    p.channels = channels;
+    p.rir_channels = rir_channels;
+    p.stride = stride;
+    p.rir_stride = rir_stride;
+    p.frames = frames;
+    p.rir_frames = rir_frames;
+    p.x_blocks = (uint32_t)x_blocks;
+    p.rir_parts = (uint32_t)parts;
+    p.units = (uint32_t)units;
+    p.out_blocks = (uint32_t)out_blocks;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_reverb_analyse_kernel, dim3((uint32_t)(units * rows)), dim3(ALAC_REVERB_THREADS), kargs, 0, stream));
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_reverb_synth_kernel, dim3((uint32_t)(out_blocks * channels * rows)), dim3(ALAC_REVERB_THREADS),
+                                 kargs, 0, stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ctx->reverb.release(ctx, stream);
 }
 
 int alacgpu_mix_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, const void* d_noise, uint32_t rows, uint32_t channels,

@@ -117,6 +117,15 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_mix_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, IntPtr dNoise, uint rows,
             uint channels, uint noiseChannels, ulong stride, ulong noiseStride, ulong frames, IntPtr dValid, IntPtr dNoiseValid,
             IntPtr dRatio, IntPtr hipStream);
+        /// <summary>Room reverberation into planar float crops in device memory (dSrc, dOut [rows, channels, stride], dRir
+        /// [rows, rirChannels, rirStride], rirChannels 1 or channels; the first frames / rirFrames of a plane are data): every
+        /// row convolved with its impulse response over the first dValid[row] frames of the signal and dRirValid[row] of the
+        /// response (long[rows] or IntPtr.Zero for all), aligned on the response's largest tap and scaled to unit energy; a
+        /// response of 0 valid frames leaves the row as it is.  dOut is dSrc itself or apart from it.  Two launches,
+        /// asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_reverb_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, IntPtr dRir, uint rows,
+            uint channels, uint rirChannels, ulong stride, ulong rirStride, ulong frames, ulong rirFrames, IntPtr dValid,
+            IntPtr dRirValid, IntPtr hipStream);
         /// <summary>Encode PCM in device memory (int32 or float32, interleaved or planar) to ALAC packets in device memory, one
         /// run of frames per packet, packet p at dPackets + p * slotBytes; asynchronous on hipStream.</summary>
         [DllImport(Lib)] public static extern UIntPtr alacgpu_encode_max_packet_bytes(uint frames, int sampleSize, int channels);

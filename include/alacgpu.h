@@ -537,6 +537,43 @@ int alacgpu_mix_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, const v
                        uint32_t noise_channels, uint64_t stride, uint64_t noise_stride, uint64_t frames,
                        const void* d_valid, const void* d_noise_valid, const void* d_ratio, void* hip_stream);
 
+/*
+ * alacgpu_reverb_device: room reverberation into the crops, in front of the noise mix (no counterpart in the reference): every
+ * crop convolved with its own impulse response by a uniformly partitioned overlap-save convolution; two launches, no atomics,
+ * the same inputs give the same bits.  The layout is planar float32: d_src and d_out [rows, channels, stride], d_rir [rows,
+ * rir_channels, rir_stride] with rir_channels 1 (the one channel goes into every channel of the signal) or channels; the first
+ * `frames` (`rir_frames`) elements of a plane are data, what lies behind them is neither read nor written.  d_out is d_src
+ * itself (in place) or an array of that layout apart from it.  For row r, with v = min(max(d_valid[r], 0), frames) and
+ * vh = min(max(d_rir_valid[r], 0), rir_frames) (int64 [rows]; NULL: frames, rir_frames),
+ *   d = the first k < vh at which |h[0, k]| is largest          the direct path; channel 0 decides for every channel
+ *   e = (sum over c < rir_channels, k < vh of h[c, k]^2) / rir_channels,  g = 1 / sqrt(e)       one gain for every channel
+ *   y[c, i] = g * sum over k < vh of h[c mod rir_channels, k] * x[c, i + d - k]   for i < v, x taken as 0 outside 0 .. v
+ *   y[c, i] = x[c, i]                                                              for v <= i < frames (in place: untouched)
+ * The result is as long as the crop and aligned on the direct path; the tail behind v is dropped.  A row with v == 0, with
+ * vh == 0 ("no reverberation for this crop"), with e == 0 (a silent response) or with an e that is not finite is left as it
+ * is bit for bit (in place: nothing is written), and only the analysis reads its response.  A NaN or an infinity in x below v
+ * reaches that row and no other (one in h below vh makes e not finite: the row stays); one at or behind v (vh) is never read.
+ * The arithmetic is float32, every operation rounded once, none fused, division and root correctly rounded: blocks of 4096
+ * frames at a hop of 2048, transformed as 4096 complex points by a radix-4 transform in LDS whose twiddles are a table made in
+ * double precision and rounded once; the response is cut into ceil(vh / 2048) partitions.  The first launch writes the spectrum
+ * of every block of every signal plane and of every partition of every response plane, and per row d, g and the verdict, into
+ * the ctx's scratch (8 * 4096 bytes a spectrum: rows * (channels * (ceil(frames / 2048) + 1) + rir_channels *
+ * ceil(rir_frames / 2048)) spectra); the sum of squares is float32 in a fixed order: partial t of 256 takes the frames t,
+ * t + 256, ... of channel 0, then of channel 1, and the 256 partials are added as a tree of halves (q[t] += q[t + s],
+ * s = 128 .. 1).  The second launch, one workgroup per row, channel and block of 2048 outputs, adds X[m - p] . H[p] over the
+ * partitions in ascending p, transforms back once, and stores g * w[i + d] over i < v.  csrc/alac_reverb.h states the
+ * transform and the layout.  Calls of one ctx share the scratch one after the other, whatever their streams (as
+ * alacgpu_mix_device's do); the first call of a ctx uploads the twiddle table with a blocking copy.  Device pointers only,
+ * asynchronous on hip_stream, nothing is read back.  rows == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx, d_src, d_out or d_rir, a misaligned array (4; 8 for d_valid and
+ * d_rir_valid), channels 0, rir_channels neither 1 nor channels, frames 0 or above stride, rir_frames 0 or above rir_stride,
+ * d_src and d_out that overlap without being equal, d_rir overlapping d_out, an extent of 2^60 bytes or more, 2^31 workgroups
+ * or more in either launch.
+ */
+int alacgpu_reverb_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, const void* d_rir, uint32_t rows, uint32_t channels,
+                          uint32_t rir_channels, uint64_t stride, uint64_t rir_stride, uint64_t frames, uint64_t rir_frames,
+                          const void* d_valid, const void* d_rir_valid, void* hip_stream);
+
 /* Single-packet drop-in for `int DecodeFrame(byte[] inbuffer, int[] outbuffer)` (AlacFile.cs:428):
  * writes the reference's own int[] layout (24-bit: one int per byte) and returns its byte count in
  * *out_bytes.  status as above (the C# shim rethrows the reference's exceptions from it). */

@@ -1,0 +1,150 @@
+"""What room reverberation costs, per call and per training step --
+  call      the alacgpu_reverb_device call alone (ctx.reverb_device, in place) on [64, 1, 32000] with responses of K = 8000 and
+            K = 16000 frames and random lengths for both, against what a user writes today in torch on the same tensors:
+            torch.fft.rfft of both at a common length, their product, irfft, the shift to the largest tap by a gather, the
+            energy gain and a `where` over the lengths.  HIP events around --reps back-to-back calls, the two ways alternating
+            inside every step, --steps times after --warmup: median and p10 .. p90 of the time per call.
+  step      corpus.random_crops(64, 32000, sample_rate=16000, mono=True, features=spec, check=False) with
+            reverb=Reverb(a corpus of responses, max_seconds=0.5) and without, the ways alternating inside every step,
+            torch.cuda.synchronize() in front of and behind each: wall time, median and p10 .. p90.  With --parent DIR (a built
+            tree of the parent commit) the call without reverb on the parent's package as `parent`, alternating with the
+            others: nothing that existed may have moved.
+One JSON document, printed and written to --out.
+  python tools/bench_reverb.py [--parent DIR] [--steps 200] [--warmup 20] [--out profiles/reverb.json]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def composition(torch, x, h, lengths, hlen, out):
+    """The torch composition on x [B, C, T], h [B, Ch, K]: out = g (h * x)[i + d] below lengths, x behind them"""
+    B, C, T = x.shape
+    K = h.shape[2]
+    i, k = torch.arange(T, device=x.device), torch.arange(K, device=x.device)
+    v, vh = lengths.clamp(0, T), hlen.clamp(0, K)
+    mx, mh = (i < v[:, None])[:, None, :], (k < vh[:, None])[:, None, :]
+    xs, hs = torch.where(mx, x, 0.0), torch.where(mh, h, 0.0)
+    n = T + K - 1
+    w = torch.fft.irfft(torch.fft.rfft(xs, n) * torch.fft.rfft(hs, n), n)
+    d = hs[:, 0].abs().argmax(1)
+    e = (hs * hs).sum((1, 2)) / h.shape[1]
+    g = torch.rsqrt(e)
+    idx = (i[None, :] + d[:, None])[:, None, :].expand(B, C, T)
+    y = g[:, None, None] * torch.gather(w, 2, idx)
+    live = (v > 0) & (vh > 0) & (e > 0) & torch.isfinite(e)
+    return torch.where(mx & live[:, None, None], y, x, out=out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=16)
+    ap.add_argument("--seconds", type=float, default=30.0)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--parent", help="a built tree of the parent commit: its step without reverb alternates with this tree's")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "reverb.json"))
+    args = ap.parse_args()
+    import torch
+
+    import alac.net_amd as pkg
+    from alac.net_amd import synth
+    from bench_corpus import make_file
+    from bench_resample import load_parent, stats
+
+    synth.build()
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.current_stream(dev)
+    n_steps = args.steps + args.warmup
+    rng = np.random.default_rng(1)
+
+    # ---- the call alone --------------------------------------------------------------------------------------------------------
+    calls = []
+    with pkg.AlacGpuContext([(4096, 16, 40, 10, 14, 2)], device=0) as ctx:
+        B, T = 64, 32000
+        for K in (8000, 16000):
+            x0 = torch.from_numpy(rng.uniform(-1, 1, (B, 1, T)).astype(np.float32)).to(dev)
+            taps = rng.standard_normal((B, 1, K)) * np.exp(-np.arange(K) / (K / 6.0))
+            taps[:, 0, 40] = 4.0
+            h = torch.from_numpy(taps.astype(np.float32)).to(dev)
+            lengths = torch.from_numpy(rng.integers(T // 4, T + 1, B)).to(dev)
+            hlen = torch.from_numpy(rng.integers(K // 2, K + 1, B)).to(dev)
+            res, res_t = torch.empty_like(x0), torch.empty_like(x0)
+            ctx.reverb_device(x0, res, h, B, 1, 1, T, K, T, K, lengths, hlen, stream=stream.cuda_stream)
+            composition(torch, x0, h, lengths, hlen, res_t)
+            close = bool(torch.allclose(res, res_t, rtol=1e-3, atol=1e-4))
+            x = x0.clone()                                 # in place, as crops() calls it: the values drift, the work does not
+            ours = lambda: ctx.reverb_device(x, x, h, B, 1, 1, T, K, T, K, lengths, hlen, stream=stream.cuda_stream)
+            theirs = lambda: composition(torch, x0, h, lengths, hlen, res_t)
+            ms = {"reverb_call": [], "torch_composition": []}
+            for rep in range(n_steps):
+                for way, fn in (("reverb_call", ours), ("torch_composition", theirs)):
+                    if way == "reverb_call":
+                        x.copy_(x0)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record(stream)
+                    for _ in range(args.reps):
+                        fn()
+                    e1.record(stream)
+                    e1.synchronize()
+                    if rep >= args.warmup:
+                        ms[way].append(e0.elapsed_time(e1) / args.reps)
+            r, c = stats(ms["reverb_call"]), stats(ms["torch_composition"])
+            calls.append({"shape": [B, 1, T], "rir_frames": K, "agrees_with_torch": close,
+                          "ms_per_call_events_around_reps_calls": {"reverb_call": r, "torch_composition": c},
+                          "reverb_call_median_below_torch_p10": bool(r["median"] < c["p10"])})
+
+    # ---- the step --------------------------------------------------------------------------------------------------------------
+    rate, R, B, L = 44100, 16000, 64, 32000
+    T = int(args.seconds * rate)
+    distinct = [make_file(synth, T, 11 + k) for k in range(2)]
+    blobs = [distinct[f % 2] for f in range(args.files)]
+    corpus, rirs = pkg.Corpus(blobs), pkg.Corpus([make_file(synth, 2 * R, 31 + k) for k in range(4)])
+    parent_pkg = load_parent(args.parent) if args.parent else None
+    parent = parent_pkg.Corpus(blobs) if args.parent else None
+    spec = pkg.LogMel(R, 400, 160, 80)
+    aug = pkg.Reverb(rirs, max_seconds=0.5)
+    kw = dict(sample_rate=R, mono=True, features=spec, check=False)
+    ways = {"reverb": lambda: corpus.random_crops(B, L, reverb=aug, **kw)[0], "without": lambda: corpus.random_crops(B, L, **kw)[0]}
+    if parent is not None:
+        parent_spec = parent_pkg.LogMel(R, 400, 160, 80)
+        ways["parent"] = lambda: parent.random_crops(B, L, sample_rate=R, mono=True, features=parent_spec, check=False)[0]
+    wall = {m: [] for m in ways}
+    for i in range(n_steps):
+        for m, fn in ways.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            dt = (time.perf_counter() - t0) * 1e3
+            del out
+            if i >= args.warmup:
+                wall[m].append(dt)
+    step = {"step": "random_crops(64, 32000, sample_rate=16000, mono=True, features=LogMel(16000, 400, 160, 80), check=False)",
+            "reverb": "Reverb(4 stereo files of 32000 frames at 44.1 kHz, max_seconds=0.5): K = 8000, taken as one channel", "wall_ms": {m: stats(v) for m, v in wall.items()}}
+    if parent is not None:
+        p, w = step["wall_ms"]["parent"], step["wall_ms"]["without"]
+        step["without_median_inside_parent_p10_p90"] = bool(p["p10"] <= w["median"] <= p["p90"])
+    corpus.close(), rirs.close()
+    if parent is not None:
+        parent.close()
+    doc = {"command": "python tools/bench_reverb.py " + " ".join(sys.argv[1:]), "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
+           "calls": calls, "step": step}
+    text = json.dumps(doc, indent=1)
+    print(text, flush=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -17,13 +17,11 @@ from both tiers into a small staging blob in HBM, and the decode reads that.
 frames a crop needs are decoded as above into a scratch the corpus keeps, and one alacgpu_resample_device call (resample.py
 states the filter) resamples every crop out of it.
 
-`crops(..., mix=AddNoise(noise_corpus, snr_db))` adds noise from a second corpus at a signal-to-noise ratio drawn per crop
-(`Corpus._mixed_crops`): the noise crops are made by that corpus at the rate of the crops, and one alacgpu_mix_device call
-(mix.py states the arithmetic) adds them in place, in front of `features=` and `normalize=`.
-
-`crops(..., reverb=Reverb(rir_corpus))` convolves every crop with a room impulse response drawn from a second corpus
-(`Corpus._reverb_crops`): the responses are cropped by that corpus at the rate of the crops, and one alacgpu_reverb_device
-call (reverb.py states the arithmetic) reverberates the crops in place, behind the waveform and in front of `mix=`.
+`crops(..., reverb=, mix=, features=, normalize=)` runs up to four stages behind the waveform, and `crops` is the one place
+that lists them: the refusals of all of them, the crops the second corpora make (`Corpus._companion_crops`: the noise of an
+AddNoise, then the impulse responses of a Reverb, each cropped by its own corpus at the rate of the crops), the waveform once
+(`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_logmel_device and
+the normalisation (reverb.py, mix.py, features.py and normalize.py state the arithmetic), each only if asked for.
 
 `Corpus(sources, mixed_rates=True)` takes files of different sample rates.  Crops of such a corpus exist at a target rate only;
 a step is the same method and the same launches, with a source window per crop in the plan
@@ -38,9 +36,25 @@ import numpy as np
 from . import (MAX_FRAME, ST_OK, ST_UNSUPPORTED_ELEMENT, ST_UNSUPPORTED_PREDTYPE, AlacGpuContext, AlacGpuError, PinnedBuffer,
                _Closing, _check, _check_batch_args, _compact_slots, _dp, _encode_slots, _frame_count, _status_text, _torch_dtype,
                _VP, _write_file, lib, make_cfgs)
+from .features import LogMel, feature_lengths
+from .mix import AddNoise, _mix, snr_ratio
+from .normalize import MeanVar, TopDb, _normalize
+from .reverb import Reverb, _reverb
 
 PAD_CFG = 0xFFFF        # a padding entry's cfg_idx: never a row of the context, so the kernels switch the entry off
 MAX_CFGS = 65535
+# crops(mix=) and crops(reverb=) for `Corpus._second_corpus`: the specification's class, its attribute that holds the second
+# corpus, how many tensors its draw() returns and what their dtypes have to be, and the nouns of the messages
+_MIX = dict(arg="mix", spec=AddNoise, corpus="noise", theirs="the noise corpus", they="the noise",
+            what="mix must be a mix.AddNoise or (AddNoise, what its draw() returned)",
+            draws=3, dtypes=lambda torch, files, offsets, snr_db: snr_db.is_floating_point,
+            tensors="the three tensors (noise_files, noise_offsets, snr_db) of AddNoise.draw", f32="noise is mixed into float32 crops",
+            channels="a noise corpus of {n} channels into crops of {Co}: it can become one channel from 1 or 2 only")
+_REVERB = dict(arg="reverb", spec=Reverb, corpus="rirs", theirs="the corpus of impulse responses", they="the responses",
+               what="reverb must be a reverb.Reverb or (Reverb, what its draw() returned)",
+               draws=2, dtypes=lambda torch, files, keep: not files.is_floating_point and keep == torch.bool,
+               tensors="the two tensors (rir_files, keep) of Reverb.draw", f32="float32 crops are reverberated",
+               channels="impulse responses of {n} channels into crops of {Co}: they can become one channel from 1 or 2 only")
 
 
 def corpus_tables(tables, mixed_rates=False):
@@ -625,43 +639,107 @@ class Corpus(_Closing):
         rate, and mono of one channel -- are the path above.  A corpus whose files differ in rate (mixed_rates=True) has no
         rate of its own: sample_rate is required (ValueError without), and every crop comes through `_rate_crops`.
 
-        features: a features.LogMel -- the crops' log-mel features instead of their PCM (`_feature_crops`): returns (feats
-        float32 [B, 1 if mono else C, n_mels, 1 + num_frames // hop], feat_lengths [B] int64 on the device: lengths // hop + 1,
-        -1 where lengths is -1); `out` is then the features tensor.  Pass it by keyword, and sample_rate and mono as well.
+        The four stages behind the waveform go by keyword, as sample_rate and mono do, and run in this order whichever are
+        given, in place, by the corpus's own context on the same stream; lengths, `check` and last_status() are those of the
+        call without them (with check=True a second corpus's own check runs too, and first).  ValueError before any device
+        work for what a stage cannot take.
 
-        normalize: a normalize.MeanVar or normalize.TopDb (`_normalized_crops`), applied in place behind everything above, on
-        the same stream: bit for bit normalize.normalize(what the call returns without it, normalize, lengths).  By keyword, as
-        features, sample_rate and mono.
+        reverb: room reverberation of the waveform: a reverb.Reverb, whose draws are then made here from the device's default
+        generator, or the pair (Reverb, draws) with the draws that its `draw(B)` returned.  Bit for bit reverb.reverb(the crops
+        without it, the first Reverb.frames(rate) frames of the drawn responses at the rate of the crops, lengths, their
+        lengths, 0 where a crop drew none).
 
-        mix: noise from a second corpus into the waveform (`_mixed_crops`), behind the waveform and in front of features and
-        normalize: a mix.AddNoise, whose draws are then made here from the device's default generator, or the pair
-        (AddNoise, draws) with the draws that its `draw(B, num_frames, rate of the crops)` returned.  Bit for bit
-        mix.mix(the crops without it, the noise crops, snr_db, lengths, their lengths).  By keyword.
+        mix: noise from a second corpus into the waveform: a mix.AddNoise, whose draws are then made here from the device's
+        default generator (in front of a Reverb's), or the pair (AddNoise, draws) with the draws that its `draw(B, num_frames,
+        rate of the crops)` returned.  Bit for bit mix.mix(the crops without it, the noise crops, snr_db, lengths, their
+        lengths).  The noise and the responses are cropped by their own corpus's `crops` at the rate of the crops, as one
+        channel when its channel count is not theirs, into scratches THIS corpus keeps: a second corpus may be this one.
 
-        reverb: room reverberation of the waveform (`_reverb_crops`), behind the waveform and in front of mix, features and
-        normalize: a reverb.Reverb, whose draws are then made here from the device's default generator, or the pair
-        (Reverb, draws) with the draws that its `draw(B)` returned.  Bit for bit reverb.reverb(the crops without it, the
-        first frames of the drawn responses at the rate of the crops, lengths, their lengths, 0 where a crop drew none).  By
-        keyword."""
+        features: a features.LogMel -- the crops' log-mel features instead of their PCM: the waveform goes into a float32
+        scratch the corpus keeps and ONE alacgpu_logmel_device call turns every row, the zeros behind its length included,
+        into features.  Returns (feats float32 [B, 1 if mono else C, n_mels, 1 + num_frames // hop], feat_lengths [B] int64
+        on the device: lengths // hop + 1, -1 where lengths is -1); `out` is then the features tensor.  ValueError: a
+        spec.sample_rate that is not the rate of the crops, a dtype other than float32, num_frames <= n_fft // 2.
+
+        normalize: a normalize.MeanVar -- every line over its valid elements: lengths for PCM, feat_lengths for features, so a
+        crop outside the corpus is zeros -- or a normalize.TopDb -- every crop of features, or every channel of it with
+        per_channel.  Bit for bit normalize.normalize(what the call returns without it, normalize, lengths).  ValueError: a
+        TopDb without features, a MeanVar with int32 crops."""
         import torch
 
+        # 1. every refusal that needs no device work: mix, reverb, normalize, features; the waveform's own are `_waveform`'s
+        rate = self.sample_rate if sample_rate is None else sample_rate
+        Co = 1 if mono else self.channels
+        is_f32 = lambda: _torch_dtype(torch, torch.float32 if dtype is None else dtype) == torch.float32
         if mix is not None:
-            mix = self._mix_spec(mix, dtype, sample_rate, mono)
+            mix = self._second_corpus(mix, _MIX, dtype, rate, Co)
         if reverb is not None:
-            reverb = self._reverb_spec(reverb, dtype, sample_rate, mono)
+            reverb = self._second_corpus(reverb, _REVERB, dtype, rate, Co)
         if normalize is not None:
-            return self._normalized_crops(normalize, files, frame_offsets, num_frames, dtype, out, check, features, sample_rate, mono, mix,
-                                          reverb)
+            if not isinstance(normalize, (MeanVar, TopDb)):
+                raise ValueError(f"normalize must be a normalize.MeanVar or a normalize.TopDb, not {normalize!r}")
+            if features is None and isinstance(normalize, TopDb):
+                raise ValueError("a TopDb clamps log-mel features: it needs features=")
+            if features is None and not is_f32():
+                raise ValueError("a MeanVar normalises float32 crops")
         if features is not None:
-            return self._feature_crops(files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, features, mix, reverb)
+            if not isinstance(features, LogMel):
+                raise ValueError(f"features must be a features.LogMel, not {features!r} (sample_rate= and mono= go by keyword)")
+            if rate is None:
+                raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
+            if features.sample_rate != rate:
+                raise ValueError(f"features for {features.sample_rate} Hz, crops at {rate} Hz")
+            if not is_f32():
+                raise ValueError("features are computed from float32 crops")
+        if features is not None or mix is not None or reverb is not None:
+            L = _frame_count("num_frames", num_frames)
+            if features is not None and L <= features.n_fft // 2:
+                raise ValueError(f"num_frames {L}: the transform needs more than n_fft // 2 = {features.n_fft // 2}")
+            self._open()
+            B = int(files.shape[0]) if isinstance(files, torch.Tensor) and files.dim() == 1 else len(np.asarray(files))
+        if features is not None:
+            feats = self._out(out, (B, Co, features.n_mels, features.frames(L)), torch.float32, zero=False)
+            out = self._scratch("_ft_scratch", (B, Co, L))
+        # 2. the companion crops, by the second corpora's own `crops`: the noise, then the responses
         if mix is not None:
-            return self._mixed_crops(mix, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, reverb)
+            nf, no, snr = mix[0].draw(B, L, sample_rate=rate) if mix[1] is None else mix[1]
+            d_noise, noise_lengths = self._companion_crops(mix[0].noise, "_mix_scratch", nf, no, L, B=B, Co=Co, rate=rate,
+                                                           check=check)
         if reverb is not None:
-            return self._reverb_crops(reverb, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono)
+            rf, keep = reverb[0].draw(B) if reverb[1] is None else reverb[1]
+            from_0 = torch.zeros(B, dtype=torch.int64, device=self._dev)
+            d_rir, rir_lengths = self._companion_crops(reverb[0].rirs, "_reverb_scratch", rf, from_0, reverb[0].frames(rate), B=B, Co=Co,
+                                                       rate=rate, check=check)
+        # 3. the waveform, once: into `out`, or into the scratch the features are computed from
+        res, lengths = self._waveform(files, frame_offsets, num_frames, dtype=dtype, out=out, check=check, sample_rate=sample_rate,
+                                      mono=mono)
+        # 4. the stages, in place and in this order on the same stream, by the corpus's own context
+        ctx = lambda: self._gpu
+        if reverb is not None:
+            _reverb(ctx, res, d_rir, lengths, torch.where(keep, rir_lengths, 0), res)
+        if mix is not None:
+            _mix(ctx, res, d_noise, lambda: snr_ratio(snr, B, self._dev), lengths, noise_lengths, res)
+        if features is not None:
+            if B:
+                window, basis, fb = features.device_tables(self._dev)
+                self._gpu.logmel_device(res, B, Co, L, L, features.n_fft, features.hop_length, features.n_mels, window, basis, fb,
+                                        features.log_mode, features.floor, feats, feats.shape[3],
+                                        stream=torch.cuda.current_stream(self._dev).cuda_stream)
+            res, lengths = feats, feature_lengths(lengths, features.hop_length)
+        if normalize is not None:
+            _normalize(ctx, res, normalize, lengths, res)
+        return res, lengths
+
+    def _waveform(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono):
+        """The crops themselves, what `crops` returns without a stage: through `_rate_crops` at another rate, as one channel
+        of two, or of a corpus whose rates differ; else planned and decoded here"""
+        import torch
+
         if self.sample_rate is None and sample_rate is None:
             raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
         if self.sample_rate is None or (mono and self.channels == 2) or (sample_rate is not None and sample_rate != self.sample_rate):
-            return self._rate_crops(files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono)
+            return self._rate_crops(files, frame_offsets, num_frames, dtype=dtype, out=out, check=check, sample_rate=sample_rate,
+                                    mono=mono)
         dtype = _torch_dtype(torch, torch.float32 if dtype is None else dtype)
         L = _frame_count("num_frames", num_frames)
         if L >= 1 << 32:
@@ -687,191 +765,43 @@ class Corpus(_Closing):
             self._check_last(lengths, d_files, d_offs, L, K)
         return out, lengths
 
-    def _mix_spec(self, mix, dtype, sample_rate, mono):
-        """crops(mix=) as the pair (AddNoise, draws or None), checked: ValueError for anything else, for int32 crops, for a
-        noise corpus that is closed, on another device or of a channel count the crops cannot take, and for crops without a
-        rate.  Nothing is done on the device."""
+    def _second_corpus(self, given, stage, dtype, rate, Co):
+        """crops(mix=) or crops(reverb=) (`stage`: _MIX or _REVERB) as the pair (its specification, draws or None), checked:
+        ValueError for anything else, for int32 crops, for a second corpus that is closed, on another device or of a channel
+        count that crops of Co channels cannot take, and for crops without a rate.  Nothing is done on the device."""
         import torch
 
-        from .mix import AddNoise
-
-        aug, draws = mix if isinstance(mix, tuple) and len(mix) == 2 else (mix, None)
-        if not isinstance(aug, AddNoise):
-            raise ValueError(f"mix must be a mix.AddNoise or (AddNoise, what its draw() returned), not {mix!r}")
+        spec, draws = given if isinstance(given, tuple) and len(given) == 2 else (given, None)
+        if not isinstance(spec, stage["spec"]):
+            raise ValueError(f"{stage['what']}, not {given!r}")
         if draws is not None:
-            ok = isinstance(draws, tuple) and len(draws) == 3 and all(isinstance(t, torch.Tensor) and t.dim() == 1 for t in draws)
-            if not ok or not (draws[0].shape == draws[1].shape == draws[2].shape) or not draws[2].dtype.is_floating_point:
-                raise ValueError("the draws of mix= must be the three tensors (noise_files, noise_offsets, snr_db) of AddNoise.draw")
+            ok = isinstance(draws, tuple) and len(draws) == stage["draws"] and all(isinstance(t, torch.Tensor) and t.dim() == 1
+                                                                                   for t in draws)
+            if not ok or any(t.shape != draws[0].shape for t in draws) or not stage["dtypes"](torch, *(t.dtype for t in draws)):
+                raise ValueError(f"the draws of {stage['arg']}= must be {stage['tensors']}")
             if any(t.device != self._dev for t in draws):
-                raise ValueError(f"the draws of mix= must be on {self._dev}")
+                raise ValueError(f"the draws of {stage['arg']}= must be on {self._dev}")
         if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
-            raise ValueError("noise is mixed into float32 crops")
-        noise = aug.noise
-        if noise._gpu is None:
-            raise ValueError("the noise corpus is closed")
-        if noise._dev != self._dev:
-            raise ValueError(f"the noise corpus is on {noise._dev}, the crops on {self._dev}")
-        if (self.sample_rate if sample_rate is None else sample_rate) is None:
-            raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=, and the noise a rate to crop at")
-        Co = 1 if mono else self.channels
-        if noise.channels != Co and noise.channels not in (1, 2):
-            raise ValueError(f"a noise corpus of {noise.channels} channels into crops of {Co}: it can become one channel from 1 or 2 only")
-        return aug, draws
+            raise ValueError(stage["f32"])
+        other = getattr(spec, stage["corpus"])
+        if other._gpu is None:
+            raise ValueError(f"{stage['theirs']} is closed")
+        if other._dev != self._dev:
+            raise ValueError(f"{stage['theirs']} is on {other._dev}, the crops on {self._dev}")
+        if rate is None:
+            raise ValueError(f"the files of this corpus differ in sample rate: crops need sample_rate=, and {stage['they']} a rate to crop at")
+        if other.channels != Co and other.channels not in (1, 2):
+            raise ValueError(stage["channels"].format(n=other.channels, Co=Co))
+        return spec, draws
 
-    def _reverb_spec(self, reverb, dtype, sample_rate, mono):
-        """crops(reverb=) as the pair (Reverb, draws or None), checked: ValueError for anything else, for int32 crops, for a
-        corpus of responses that is closed, on another device or of a channel count the crops cannot take, and for crops
-        without a rate.  Nothing is done on the device."""
-        import torch
-
-        from .reverb import Reverb
-
-        aug, draws = reverb if isinstance(reverb, tuple) and len(reverb) == 2 else (reverb, None)
-        if not isinstance(aug, Reverb):
-            raise ValueError(f"reverb must be a reverb.Reverb or (Reverb, what its draw() returned), not {reverb!r}")
-        if draws is not None:
-            ok = isinstance(draws, tuple) and len(draws) == 2 and all(isinstance(t, torch.Tensor) and t.dim() == 1 for t in draws)
-            if not ok or draws[0].shape != draws[1].shape or draws[0].dtype.is_floating_point or draws[1].dtype != torch.bool:
-                raise ValueError("the draws of reverb= must be the two tensors (rir_files, keep) of Reverb.draw")
-            if any(t.device != self._dev for t in draws):
-                raise ValueError(f"the draws of reverb= must be on {self._dev}")
-        if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
-            raise ValueError("float32 crops are reverberated")
-        rirs = aug.rirs
-        if rirs._gpu is None:
-            raise ValueError("the corpus of impulse responses is closed")
-        if rirs._dev != self._dev:
-            raise ValueError(f"the corpus of impulse responses is on {rirs._dev}, the crops on {self._dev}")
-        if (self.sample_rate if sample_rate is None else sample_rate) is None:
-            raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=, and the responses a rate to crop at")
-        Co = 1 if mono else self.channels
-        if rirs.channels != Co and rirs.channels not in (1, 2):
-            raise ValueError(f"impulse responses of {rirs.channels} channels into crops of {Co}: they can become one channel from 1 or 2 only")
-        return aug, draws
-
-    def _reverb_crops(self, reverb, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono):
-        """crops(..., reverb=): the responses first -- rirs.crops(rir_files, 0, K, sample_rate=the rate of the crops, mono=the
-        corpus of responses' channel count is not the crops', check=check), K = Reverb.frames(that rate), into a scratch THIS
-        corpus keeps --, then the crops exactly as without reverb, then ONE alacgpu_reverb_device call by the corpus's own
-        context on the same stream reverberates them in place over lengths (reverb.py states the arithmetic), a crop that drew
-        none (keep False: a response of 0 frames) or lies outside the corpus staying as it is.  lengths, `check` and
-        last_status() are those of the call without reverb; with check=True the corpus of responses' own check runs too, and
-        first."""
-        import torch
-
-        from .reverb import _reverb
-
-        aug, draws = reverb
-        rirs = aug.rirs
-        L = _frame_count("num_frames", num_frames)
-        self._open()
-        rate = self.sample_rate if sample_rate is None else sample_rate
-        B = int(files.shape[0]) if isinstance(files, torch.Tensor) and files.dim() == 1 else len(np.asarray(files))
-        if draws is None:
-            draws = aug.draw(B)
-        rf, keep = draws
-        if rf.shape[0] != B:
-            raise ValueError(f"{rf.shape[0]} draws for {B} crops")
-        K = aug.frames(rate)
-        Co = 1 if mono else self.channels
-        Ch = Co if rirs.channels == Co else 1
-        d_rir = self._scratch("_reverb_scratch", (B, Ch, K))
-        _, rir_lengths = rirs.crops(rf, torch.zeros(B, dtype=torch.int64, device=self._dev), K, out=d_rir, check=check, sample_rate=rate,
-                                    mono=rirs.channels != Co)
-        pcm, lengths = self.crops(files, frame_offsets, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono)
-        _reverb(lambda: self._gpu, pcm, d_rir, lengths, torch.where(keep, rir_lengths, 0), pcm)
-        return pcm, lengths
-
-    def _mixed_crops(self, mix, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, reverb=None):
-        """crops(..., mix=): the noise crops first -- noise.crops(noise_files, noise_offsets, num_frames, sample_rate=the rate
-        of the crops, mono=the noise corpus's channel count is not the crops', check=check) into a scratch THIS corpus keeps,
-        so that the noise corpus may be this one --, then the crops exactly as without mix, then ONE alacgpu_mix_device call
-        by the corpus's own context on the same stream adds the noise in place over lengths (mix.py states the arithmetic; a
-        noise crop shorter than the crop is repeated, a crop that drew NaN for its ratio or lies outside the corpus stays as
-        it is).  lengths, `check` and last_status() are those of the call without mix; with check=True the noise corpus's own
-        check runs too, and first."""
-        import torch
-
-        from .mix import _mix, snr_ratio
-
-        aug, draws = mix
-        noise = aug.noise
-        L = _frame_count("num_frames", num_frames)
-        self._open()
-        rate = self.sample_rate if sample_rate is None else sample_rate
-        B = int(files.shape[0]) if isinstance(files, torch.Tensor) and files.dim() == 1 else len(np.asarray(files))
-        if draws is None:
-            draws = aug.draw(B, L, sample_rate=rate)
-        nf, no, snr = draws
-        if nf.shape[0] != B:
-            raise ValueError(f"{nf.shape[0]} draws for {B} crops")
-        Co = 1 if mono else self.channels
-        Cn = Co if noise.channels == Co else 1
-        d_noise = self._scratch("_mix_scratch", (B, Cn, L))
-        _, noise_lengths = noise.crops(nf, no, L, out=d_noise, check=check, sample_rate=rate, mono=noise.channels != Co)
-        pcm, lengths = self.crops(files, frame_offsets, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,
-                                  reverb=reverb)
-        _mix(lambda: self._gpu, pcm, d_noise, lambda: snr_ratio(snr, B, self._dev), lengths, noise_lengths, pcm)
-        return pcm, lengths
-
-    def _normalized_crops(self, how, files, frame_offsets, num_frames, dtype, out, check, features, sample_rate, mono, mix=None, reverb=None):
-        """crops(..., normalize=how): the crops, or with features=spec their features, are made exactly as without, then
-        normalised in place by the corpus's own context on the same stream (normalize.py states the arithmetic).  A MeanVar
-        takes every line over its valid elements -- lengths for PCM on every path, feat_lengths for features, so a crop outside
-        the corpus (-1) is zeros; a TopDb takes every crop of features, or every channel of it with per_channel.  What is
-        returned otherwise, `check` and last_status() are those of the call without.  ValueError before any device work: a
-        TopDb without features, a MeanVar with int32 crops, anything else that is neither."""
-        import torch
-
-        from .normalize import MeanVar, TopDb, _normalize
-
-        if not isinstance(how, (MeanVar, TopDb)):
-            raise ValueError(f"normalize must be a normalize.MeanVar or a normalize.TopDb, not {how!r}")
-        if features is None:
-            if isinstance(how, TopDb):
-                raise ValueError("a TopDb clamps log-mel features: it needs features=")
-            if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
-                raise ValueError("a MeanVar normalises float32 crops")
-        res, lengths = self.crops(files, frame_offsets, num_frames, dtype=dtype, out=out, check=check, features=features,
-                                  sample_rate=sample_rate, mono=mono, mix=mix, reverb=reverb)
-        _normalize(lambda: self._gpu, res, how, lengths, res)
-        return res, lengths
-
-    def _feature_crops(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, spec, mix=None, reverb=None):
-        """crops(..., features=spec): the crops are made exactly as without -- on the native or the `_rate_crops` path, `mono`
-        honoured, `check` as there -- into a float32 scratch [B, Co, num_frames] the corpus keeps, then ONE
-        alacgpu_logmel_device call on the same stream turns every row, the zeros behind its length included, into features
-        (features.py states the transform).  ValueError before any device work: a spec.sample_rate that is not the rate of
-        the crops (sample_rate if given, else the corpus's own), a dtype other than float32, num_frames <= n_fft // 2, an
-        `out` that is not a contiguous float32 [B, Co, n_mels, 1 + num_frames // hop] on the device."""
-        import torch
-
-        from .features import LogMel, feature_lengths
-
-        if not isinstance(spec, LogMel):
-            raise ValueError(f"features must be a features.LogMel, not {spec!r} (sample_rate= and mono= go by keyword)")
-        if self.sample_rate is None and sample_rate is None:
-            raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
-        rate = self.sample_rate if sample_rate is None else sample_rate
-        if spec.sample_rate != rate:
-            raise ValueError(f"features for {spec.sample_rate} Hz, crops at {rate} Hz")
-        if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
-            raise ValueError("features are computed from float32 crops")
-        L = _frame_count("num_frames", num_frames)
-        if L <= spec.n_fft // 2:
-            raise ValueError(f"num_frames {L}: the transform needs more than n_fft // 2 = {spec.n_fft // 2}")
-        self._open()
-        B = int(files.shape[0]) if isinstance(files, torch.Tensor) and files.dim() == 1 else len(np.asarray(files))
-        Co = 1 if mono else self.channels
-        Tf = spec.frames(L)
-        out = self._out(out, (B, Co, spec.n_mels, Tf), torch.float32, zero=False)
-        pcm = self._scratch("_ft_scratch", (B, Co, L))
-        _, lengths = self.crops(files, frame_offsets, L, out=pcm, check=check, sample_rate=sample_rate, mono=mono, mix=mix, reverb=reverb)
-        if B:
-            window, basis, fb = spec.device_tables(self._dev)
-            self._gpu.logmel_device(pcm, B, Co, L, L, spec.n_fft, spec.hop_length, spec.n_mels, window, basis, fb, spec.log_mode,
-                                    spec.floor, out, Tf, stream=torch.cuda.current_stream(self._dev).cuda_stream)
-        return out, feature_lengths(lengths, spec.hop_length)
+    def _companion_crops(self, other, scratch, files, offsets, frames, B, Co, rate, check):
+        """What a stage needs of a second corpus for B crops of Co channels at `rate`: other.crops(files, offsets, frames) at
+        that rate, as one channel when other's channel count is not Co, into the scratch THIS corpus keeps under the
+        attribute `scratch` -- so `other` may be this corpus.  Returns (the crops [B, Co or 1, frames], their lengths)."""
+        if files.shape[0] != B:
+            raise ValueError(f"{files.shape[0]} draws for {B} crops")
+        view = self._scratch(scratch, (B, Co if other.channels == Co else 1, frames))
+        return view, other.crops(files, offsets, frames, out=view, check=check, sample_rate=rate, mono=other.channels != Co)[1]
 
     def _out(self, out, shape, dtype, zero):
         """The tensor a call writes: `out` checked against shape and dtype, or a new one; zeroed where the decode relies on it"""
@@ -1040,10 +970,11 @@ class Corpus(_Closing):
         import torch
 
         B, L = _frame_count("batch", batch), _frame_count("num_frames", num_frames)
+        rate = self.sample_rate if sample_rate is None else sample_rate
         if mix is not None:
-            mix = self._mix_spec(mix, dtype, sample_rate, mono)
+            mix = self._second_corpus(mix, _MIX, dtype, rate, 1 if mono else self.channels)
         if reverb is not None:
-            reverb = self._reverb_spec(reverb, dtype, sample_rate, mono)
+            reverb = self._second_corpus(reverb, _REVERB, dtype, rate, 1 if mono else self.channels)
         dev = generator.device if generator is not None else self._dev
         files = torch.randint(0, self.num_files, (B,), generator=generator, device=dev, dtype=torch.int64).to(self._dev)
         u = torch.rand(B, generator=generator, device=dev, dtype=torch.float64).to(self._dev)
@@ -1053,7 +984,7 @@ class Corpus(_Closing):
         span = (totals[files] - L).clamp(min=0)
         offs = torch.minimum(torch.floor(u * (span + 1).to(torch.float64)).to(torch.int64), span)
         if mix is not None and mix[1] is None:
-            mix = (mix[0], mix[0].draw(B, L, sample_rate=self.sample_rate if sample_rate is None else sample_rate, generator=generator))
+            mix = (mix[0], mix[0].draw(B, L, sample_rate=rate, generator=generator))
         if reverb is not None and reverb[1] is None:
             reverb = (reverb[0], reverb[0].draw(B, generator=generator))
         pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,

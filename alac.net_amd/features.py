@@ -303,11 +303,12 @@ def log_mel(pcm, spec, lengths=None):
     entry of -1 stays -1)."""
     import torch
 
-    from .resample import _context
+    from ._stageargs import _device_context
 
     if not isinstance(spec, LogMel):
         raise ValueError("spec must be a LogMel")
-    if not isinstance(pcm, torch.Tensor) or pcm.device.type != "cuda" or pcm.dtype != torch.float32 or pcm.dim() < 1:
+    ctx = _device_context("pcm", pcm, "[..., T]")
+    if pcm.dtype != torch.float32 or pcm.dim() < 1:
         raise ValueError("pcm must be a float32 device tensor [..., T]")
     T = pcm.shape[-1]
     if T <= spec.n_fft // 2:
@@ -319,9 +320,8 @@ def log_mel(pcm, spec, lengths=None):
     if planes:
         window, basis, fb = spec.device_tables(dev)
         with torch.cuda.device(dev):
-            _context(dev.index).logmel_device(pcm.contiguous(), planes, 1, T, T, spec.n_fft, spec.hop_length, spec.n_mels, window,
-                                              basis, fb, spec.log_mode, spec.floor, out,
-                                              Tf, stream=torch.cuda.current_stream(dev).cuda_stream)
+            ctx().logmel_device(pcm.contiguous(), planes, 1, T, T, spec.n_fft, spec.hop_length, spec.n_mels, window, basis, fb,
+                                spec.log_mode, spec.floor, out, Tf, stream=torch.cuda.current_stream(dev).cuda_stream)
     if lengths is None:
         return out
     lens = lengths if isinstance(lengths, torch.Tensor) else torch.as_tensor(np.asarray(lengths, dtype=np.int64))

@@ -52,11 +52,10 @@ negative, infinite or NaN ratio is data like any other.
 `AddNoise`, `mix_host` and `mix_host_f32` need no device.  `mix` is the call on device tensors; `Corpus.crops(mix=)` and
 `Corpus.random_crops(mix=)` put it between the waveform and `features=`.
 """
-import math
 
 import numpy as np
 
-from .normalize import _Spec, _f32_finite, _lines
+from ._stageargs import _device_context, _f32_finite, _lengths_host, _signal_and_companion, _Spec, _tree
 
 _U = 2.0 ** -24
 # csrc/alac_mix.h
@@ -138,15 +137,6 @@ class AddNoise(_Spec):
 
 
 # ---- the specification and its float32 twin ------------------------------------------------------------------------------------
-def _lengths_host(name, lengths, B, T):
-    if lengths is None:
-        return np.full(B, T, dtype=np.int64)
-    lens = np.asarray(lengths)
-    if lens.shape != (B,) or (B and lens.dtype.kind not in "iu"):
-        raise ValueError(f"{name} must be {B} integers, not {lens.shape} {lens.dtype}")
-    return np.clip(lens.astype(np.int64), 0, T)
-
-
 def _host_args(x, noise, ratio, lengths, noise_lengths):
     x, noise = np.asarray(x), np.asarray(noise)
     if x.dtype != np.float32 or noise.dtype != np.float32:
@@ -197,15 +187,6 @@ def mix_host(x, noise, ratio, lengths=None, noise_lengths=None, bound=False):
                 dg = g1 + g2 + 4 * _U
                 dY[b, :, :k] = np.abs(gn) * (dg + _U * (1 + dg)) + _U * np.abs(y[b, :, :k])
     return (y, dY) if bound else y
-
-
-def _tree(q):
-    """q [..., 2^k] float32 added over its last axis as a tree of halves: q[j] += q[j + h] for h = 2^(k-1) .. 1"""
-    h = q.shape[-1] // 2
-    while h >= 1:
-        q = (q[..., :h] + q[..., h:2 * h]).astype(np.float32)
-        h //= 2
-    return q[..., 0]
 
 
 def _sum_squares(X, k):
@@ -277,74 +258,16 @@ def snr_ratio(snr_db, batch, device):
     return torch.where(s.isnan(), 0.0, torch.pow(10.0, s * (-1.0 / 20.0)))
 
 
-def _lengths_device(name, lengths, B, device):
-    import torch
-
-    if lengths is None:
-        return None
-    if isinstance(lengths, torch.Tensor):
-        if lengths.dtype.is_floating_point or lengths.dtype == torch.bool or lengths.shape != (B,):
-            raise ValueError(f"{name} must be {B} integers")
-        return lengths.to(device, torch.int64).contiguous()
-    lens = np.asarray(lengths)
-    if lens.shape != (B,) or (B and lens.dtype.kind not in "iu"):
-        raise ValueError(f"{name} must be {B} integers")
-    return torch.from_numpy(lens.astype(np.int64)).to(device)
-
-
-def _planes(name, t, B=None, T=None, channels=None):
-    """The plane stride of t, a float32 device tensor [B, C, T], contiguous or the slice [..., :T] of a contiguous one"""
-    import torch
-
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.float32 or t.dim() != 3 or t.shape[1] == 0:
-        raise ValueError(f"{name} must be a float32 device tensor [B, C, T]")
-    if (B is not None and t.shape[0] != B) or (T is not None and t.shape[2] != T) or (channels is not None and t.shape[1] not in channels):
-        raise ValueError(f"{name} must be [{B}, {' or '.join(str(c) for c in channels)}, {T}], not {tuple(t.shape)}")
-    layout = _lines(t) if t.numel() else (max(t.shape[-1], 1), t.shape[-1])
-    if layout is None:
-        raise ValueError(f"{name} must be contiguous or the slice [..., :T] of a contiguous tensor")
-    return layout[0]
-
-
-def _span(t, stride):
-    """The addresses [first, behind the last) of the elements of t [B, C, T] with that plane stride"""
-    B, C, T = t.shape
-    return t.data_ptr(), t.data_ptr() + 4 * ((B * C - 1) * stride + T)
-
-
 def _mix(ctx, x, noise, ratio, lengths, noise_lengths, out):
     """`mix` behind its first checks; ratio() gives the ratio (a float32 device tensor [B]) and ctx() the context that runs it
     (the corpus's own inside `Corpus.crops`), both asked for behind the checks"""
     import torch
 
-    S = _planes("x", x)
-    B, C, T = x.shape
-    Sn = _planes("noise", noise, B, T, (C, 1) if C != 1 else (1,))
-    if noise.device != x.device:
-        raise ValueError("x and noise must be on one device")
-    if out is not None and out is not x and (
-            not isinstance(out, torch.Tensor) or out.shape != x.shape or out.dtype != x.dtype or out.device != x.device
-            or (x.numel() and (_lines(out) is None or _lines(out)[0] != S))):
-        raise ValueError("out must be x itself or a float32 tensor of x's shape, layout and device")
-    for name, lens in (("lengths", lengths), ("noise_lengths", noise_lengths)):
-        if lens is not None and not isinstance(lens, torch.Tensor):
-            _lengths_host(name, lens, B, T)
-        elif lens is not None and (lens.dtype.is_floating_point or lens.dtype == torch.bool or lens.shape != (B,)):
-            raise ValueError(f"{name} must be {B} integers")
-    if x.numel():
-        (x0, x1), (n0, n1) = _span(x, S), _span(noise, Sn)
-        o0, o1 = (x0, x1) if out is None else _span(out, S)
-        if out is not None and x0 != o0 and x0 < o1 and o0 < x1:
-            raise ValueError("out overlaps x without being x")
-        if out is not None and n0 < o1 and o0 < n1:
-            raise ValueError("noise overlaps out")
+    S, Sn, out, d_valid, d_noise_valid = _signal_and_companion(x, "noise", noise, lengths, noise_lengths, out, same_frames=True)
     ratio = ratio()
-    if out is None:
-        out = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=x.device)
-    d_valid = _lengths_device("lengths", lengths, B, x.device)
-    d_noise_valid = _lengths_device("noise_lengths", noise_lengths, B, x.device)
     if x.numel() == 0:
         return out
+    B, C, T = x.shape
     with torch.cuda.device(x.device):
         stream = torch.cuda.current_stream(x.device).cuda_stream
         ctx().mix_device(x, out, noise, B, C, noise.shape[1], S, Sn, T, d_valid, d_noise_valid, ratio.contiguous(), stream=stream)
@@ -360,11 +283,5 @@ def mix(x, noise, snr_db, lengths=None, noise_lengths=None, out=None):
     and, in the noise, are used, repeated where they are fewer; default: T.  out: x itself (in place) or a tensor of x's shape
     and layout that neither x nor noise overlaps; default: a new one of x's layout.  Returns out.  Two launches behind one
     small torch expression for the ratio, asynchronous on the current stream; ValueError before any device work."""
-    import torch
-
-    from .resample import _context
-
-    if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
-        raise ValueError("x must be a float32 device tensor [B, C, T]")
-    index = x.device.index if x.device.index is not None else torch.cuda.current_device()
-    return _mix(lambda: _context(index), x, noise, lambda: snr_ratio(snr_db, x.shape[0], x.device), lengths, noise_lengths, out)
+    ctx = _device_context("x", x, "[B, C, T]")
+    return _mix(ctx, x, noise, lambda: snr_ratio(snr_db, x.shape[0], x.device), lengths, noise_lengths, out)

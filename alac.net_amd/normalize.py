@@ -51,43 +51,13 @@ mx = +inf gives c = +inf, and inf - inf = NaN with relative.
 
 `MeanVar`, `TopDb`, `normalize_host` and `normalize_host_f32` need no device.  `normalize` is the call on device tensors.
 """
-import math
-
 import numpy as np
+
+from ._stageargs import _device_context, _f32_finite, _lengths_device, _lines, _Spec
 
 _U = 2.0 ** -24
 WAVE_MAX = 256            # ALAC_NORM_WAVE_MAX of csrc/alac_normalize.h: up to here a line has 64 partial sums, above 1024
 _LANES, _LINE_THREADS = 64, 1024
-_F32_OVERFLOW = float(2 ** 128 - 2 ** 103)      # what rounds to infinity in float32, and above
-
-
-def _f32_finite(name, v, least=None):
-    """v as a float that is finite in float32 (and at least `least`); ValueError otherwise"""
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise ValueError(f"{name} must be a number, not {v!r}")
-    v = float(v)
-    if not math.isfinite(v) or abs(v) >= _F32_OVERFLOW or (least is not None and v < least):
-        raise ValueError(f"{name} must be finite in float32{'' if least is None else f' and at least {least}'}, not {v!r}")
-    return v
-
-
-class _Spec:
-    __slots__ = ()
-
-    def __setattr__(self, name, value):
-        raise AttributeError(f"a {type(self).__name__} is immutable")
-
-    def __delattr__(self, name):
-        raise AttributeError(f"a {type(self).__name__} is immutable")
-
-    def __eq__(self, other):
-        return type(other) is type(self) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
-
-    def __hash__(self):
-        return hash((type(self).__name__,) + tuple(getattr(self, k) for k in self.__slots__))
-
-    def __repr__(self):
-        return f"{type(self).__name__}({', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__)})"
 
 
 class MeanVar(_Spec):
@@ -271,28 +241,6 @@ def normalize_host_f32(x, how, lengths=None):
 
 
 # ---- on the device -------------------------------------------------------------------------------------------------------------
-def _lines(x):
-    """(line_stride, n) of x [B, ..., n]: x is contiguous (line_stride = n) or the slice [..., :n] of a contiguous tensor
-    whose last dimension is line_stride; None for any other view"""
-    n = x.shape[-1]
-    if n != 1 and x.stride(-1) != 1:
-        return None
-    S, expect = None, None
-    for k in range(x.dim() - 2, -1, -1):
-        if x.shape[k] == 1:
-            continue
-        if S is None:
-            S = x.stride(k)
-            if S < n:
-                return None
-            expect = S * x.shape[k]
-        else:
-            if x.stride(k) != expect:
-                return None
-            expect *= x.shape[k]
-    return (n if S is None else S), n
-
-
 def _normalize(ctx, x, how, lengths, out):
     """`normalize`; ctx() gives the context that runs it (the corpus's own inside `Corpus.crops`), asked for behind the checks"""
     import torch
@@ -314,17 +262,7 @@ def _normalize(ctx, x, how, lengths, out):
           or (x.numel() and _lines(out) != layout)):
         raise ValueError("out must be x itself or a float32 tensor of x's shape, layout and device")
     B = x.shape[0]
-    d_valid = None
-    if lengths is not None and not top:
-        if isinstance(lengths, torch.Tensor):
-            if lengths.dtype.is_floating_point or lengths.dtype == torch.bool or lengths.shape != (B,):
-                raise ValueError(f"lengths must be {B} integers")
-            d_valid = lengths.to(x.device, torch.int64).contiguous()
-        else:
-            lens = np.asarray(lengths)
-            if lens.shape != (B,) or (B and lens.dtype.kind not in "iu"):
-                raise ValueError(f"lengths must be {B} integers")
-            d_valid = torch.from_numpy(lens.astype(np.int64)).to(x.device)
+    d_valid = None if top else _lengths_device("lengths", lengths, B, x.device)
     if x.numel() == 0:
         return out
     rows = B * x.shape[1] if top and how.per_channel else B
@@ -346,13 +284,7 @@ def normalize(x, how, lengths=None, out=None):
     tensor (as `crops` returns them; -1 counts as 0, more than n as n), used by MeanVar only; default: whole lines.  out: x
     itself (in place) or a tensor of x's shape and layout; default: a new one of x's layout.  Returns out.  One launch
     (MeanVar) or two (TopDb), asynchronous on the current stream; ValueError before any device work."""
-    import torch
-
-    from .resample import _context
-
-    if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
-        raise ValueError("x must be a float32 device tensor [B, ..., n]")
-    index = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    ctx = _device_context("x", x, "[B, ..., n]")
     if not isinstance(how, (MeanVar, TopDb)):
         raise ValueError(f"how must be a MeanVar or a TopDb, not {how!r}")
-    return _normalize(lambda: _context(index), x, how, lengths, out)
+    return _normalize(ctx, x, how, lengths, out)

@@ -65,8 +65,7 @@ import math
 
 import numpy as np
 
-from .mix import _lengths_device, _planes, _span, _tree
-from .normalize import _Spec, _f32_finite, _lines
+from ._stageargs import _device_context, _f32_finite, _lengths_host, _signal_and_companion, _Spec, _tree
 
 _U = 2.0 ** -24
 # csrc/alac_reverb.h
@@ -137,15 +136,6 @@ class Reverb(_Spec):
 
 
 # ---- the specification and its float32 twin ------------------------------------------------------------------------------------
-def _lengths_host(name, lengths, B, T):
-    if lengths is None:
-        return np.full(B, T, dtype=np.int64)
-    lens = np.asarray(lengths)
-    if lens.shape != (B,) or (B and lens.dtype.kind not in "iu"):
-        raise ValueError(f"{name} must be {B} integers, not {lens.shape} {lens.dtype}")
-    return np.clip(lens.astype(np.int64), 0, T)
-
-
 def _host_args(x, rir, lengths, rir_lengths):
     x, rir = np.asarray(x), np.asarray(rir)
     if x.dtype != np.float32 or rir.dtype != np.float32:
@@ -341,41 +331,13 @@ def _reverb(ctx, x, rir, lengths, rir_lengths, out):
     for behind the checks"""
     import torch
 
-    S = _planes("x", x)
-    B, C, T = x.shape
-    if not isinstance(rir, torch.Tensor) or rir.dim() != 3:
-        raise ValueError("rir must be a float32 device tensor [B, C or 1, K]")
-    K = rir.shape[2]
-    Sh = _planes("rir", rir, B, K, (C, 1) if C != 1 else (1,))
-    if rir.device != x.device:
-        raise ValueError("x and rir must be on one device")
-    if x.numel() and K == 0:
-        raise ValueError("rir must have at least one frame")
-    if out is not None and out is not x and (
-            not isinstance(out, torch.Tensor) or out.shape != x.shape or out.dtype != x.dtype or out.device != x.device
-            or (x.numel() and (_lines(out) is None or _lines(out)[0] != S))):
-        raise ValueError("out must be x itself or a float32 tensor of x's shape, layout and device")
-    for name, lens, most in (("lengths", lengths, T), ("rir_lengths", rir_lengths, K)):
-        if lens is not None and not isinstance(lens, torch.Tensor):
-            _lengths_host(name, lens, B, most)
-        elif lens is not None and (lens.dtype.is_floating_point or lens.dtype == torch.bool or lens.shape != (B,)):
-            raise ValueError(f"{name} must be {B} integers")
-    if x.numel():
-        (x0, x1), (h0, h1) = _span(x, S), _span(rir, Sh)
-        o0, o1 = (x0, x1) if out is None else _span(out, S)
-        if out is not None and x0 != o0 and x0 < o1 and o0 < x1:
-            raise ValueError("out overlaps x without being x")
-        if h0 < o1 and o0 < h1 and out is not None:
-            raise ValueError("rir overlaps out")
-    if out is None:
-        out = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=x.device)
-    d_valid = _lengths_device("lengths", lengths, B, x.device)
-    d_rir_valid = _lengths_device("rir_lengths", rir_lengths, B, x.device)
+    S, Sh, out, d_valid, d_rir_valid = _signal_and_companion(x, "rir", rir, lengths, rir_lengths, out, same_frames=False)
     if x.numel() == 0:
         return out
+    B, C, T = x.shape
     with torch.cuda.device(x.device):
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        ctx().reverb_device(x, out, rir, B, C, rir.shape[1], S, Sh, T, K, d_valid, d_rir_valid, stream=stream)
+        ctx().reverb_device(x, out, rir, B, C, rir.shape[1], S, Sh, T, rir.shape[2], d_valid, d_rir_valid, stream=stream)
     return out
 
 
@@ -388,11 +350,4 @@ def reverb(x, rir, lengths=None, rir_lengths=None, out=None):
     response; a response of 0 frames leaves the row as it is, bit for bit; default: T and K.  out: x itself (in place) or a
     tensor of x's shape and layout that neither x nor rir overlaps; default: a new one of x's layout.  Returns out.  Two
     launches, asynchronous on the current stream; ValueError before any device work."""
-    import torch
-
-    from .resample import _context
-
-    if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
-        raise ValueError("x must be a float32 device tensor [B, C, T]")
-    index = x.device.index if x.device.index is not None else torch.cuda.current_device()
-    return _reverb(lambda: _context(index), x, rir, lengths, rir_lengths, out)
+    return _reverb(_device_context("x", x, "[B, C, T]"), x, rir, lengths, rir_lengths, out)

@@ -5,10 +5,11 @@
             energy gain and a `where` over the lengths.  HIP events around --reps back-to-back calls, the two ways alternating
             inside every step, --steps times after --warmup: median and p10 .. p90 of the time per call.
   step      corpus.random_crops(64, 32000, sample_rate=16000, mono=True, features=spec, check=False) with
-            reverb=Reverb(a corpus of responses, max_seconds=0.5) and without, the ways alternating inside every step,
-            torch.cuda.synchronize() in front of and behind each: wall time, median and p10 .. p90.  With --parent DIR (a built
-            tree of the parent commit) the call without reverb on the parent's package as `parent`, alternating with the
-            others: nothing that existed may have moved.
+            reverb=Reverb(a corpus of responses, max_seconds=0.5), without,
+            and with all four stages (reverb=, mix=AddNoise(the corpus itself, (5, 20)), normalize=MeanVar()), the ways
+            alternating inside every step, torch.cuda.synchronize() in front of and behind each: wall time, median and
+            p10 .. p90.  With --parent DIR (a built tree of the parent commit) the same three steps on the parent's package
+            as `parent_...`, alternating with the others: nothing that existed may have moved.
 One JSON document, printed and written to --out.
   python tools/bench_reverb.py [--parent DIR] [--steps 200] [--warmup 20] [--out profiles/reverb.json]"""
 import argparse
@@ -109,16 +110,24 @@ def main():
     T = int(args.seconds * rate)
     distinct = [make_file(synth, T, 11 + k) for k in range(2)]
     blobs = [distinct[f % 2] for f in range(args.files)]
-    corpus, rirs = pkg.Corpus(blobs), pkg.Corpus([make_file(synth, 2 * R, 31 + k) for k in range(4)])
-    parent_pkg = load_parent(args.parent) if args.parent else None
-    parent = parent_pkg.Corpus(blobs) if args.parent else None
-    spec = pkg.LogMel(R, 400, 160, 80)
-    aug = pkg.Reverb(rirs, max_seconds=0.5)
-    kw = dict(sample_rate=R, mono=True, features=spec, check=False)
-    ways = {"reverb": lambda: corpus.random_crops(B, L, reverb=aug, **kw)[0], "without": lambda: corpus.random_crops(B, L, **kw)[0]}
-    if parent is not None:
-        parent_spec = parent_pkg.LogMel(R, 400, 160, 80)
-        ways["parent"] = lambda: parent.random_crops(B, L, sample_rate=R, mono=True, features=parent_spec, check=False)[0]
+    rir_files = [make_file(synth, 2 * R, 31 + k) for k in range(4)]
+    corpus, rirs = pkg.Corpus(blobs), pkg.Corpus(rir_files)
+    kw = dict(sample_rate=R, mono=True, check=False)
+
+    def steps(p, corpus, rirs):
+        """The three steps on the package p: with reverb=, without, and with all four stages (the noise from the corpus itself)"""
+        spec, aug = p.LogMel(R, 400, 160, 80), p.Reverb(rirs, max_seconds=0.5)
+        add, how = p.AddNoise(corpus, (5, 20)), p.MeanVar()
+        return {"reverb": lambda: corpus.random_crops(B, L, reverb=aug, features=spec, **kw)[0],
+                "without": lambda: corpus.random_crops(B, L, features=spec, **kw)[0],
+                "all_stages": lambda: corpus.random_crops(B, L, reverb=aug, mix=add, features=spec, normalize=how, **kw)[0]}
+
+    ways = steps(pkg, corpus, rirs)
+    parent = parent_rirs = None
+    if args.parent:
+        parent_pkg = load_parent(args.parent)
+        parent, parent_rirs = parent_pkg.Corpus(blobs), parent_pkg.Corpus(rir_files)
+        ways.update({"parent_" + m: fn for m, fn in steps(parent_pkg, parent, parent_rirs).items()})
     wall = {m: [] for m in ways}
     for i in range(n_steps):
         for m, fn in ways.items():
@@ -131,13 +140,16 @@ def main():
             if i >= args.warmup:
                 wall[m].append(dt)
     step = {"step": "random_crops(64, 32000, sample_rate=16000, mono=True, features=LogMel(16000, 400, 160, 80), check=False)",
-            "reverb": "Reverb(4 stereo files of 32000 frames at 44.1 kHz, max_seconds=0.5): K = 8000, taken as one channel", "wall_ms": {m: stats(v) for m, v in wall.items()}}
+            "reverb": "Reverb(4 stereo files of 32000 frames at 44.1 kHz, max_seconds=0.5): K = 8000, taken as one channel",
+            "all_stages": "reverb= as above, mix=AddNoise(the corpus itself, (5, 20)), normalize=MeanVar()",
+            "wall_ms": {m: stats(v) for m, v in wall.items()}}
     if parent is not None:
-        p, w = step["wall_ms"]["parent"], step["wall_ms"]["without"]
-        step["without_median_inside_parent_p10_p90"] = bool(p["p10"] <= w["median"] <= p["p90"])
+        for m in ("reverb", "without", "all_stages"):
+            p, w = step["wall_ms"]["parent_" + m], step["wall_ms"][m]
+            step[m + "_median_inside_parent_p10_p90_or_below"] = bool(w["median"] <= p["p90"])
     corpus.close(), rirs.close()
     if parent is not None:
-        parent.close()
+        parent.close(), parent_rirs.close()
     doc = {"command": "python tools/bench_reverb.py " + " ".join(sys.argv[1:]), "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
            "calls": calls, "step": step}
     text = json.dumps(doc, indent=1)

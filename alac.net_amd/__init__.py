@@ -81,6 +81,8 @@ SYMBOLS = {
                                      _VP, _VP]),
     "alacgpu_reverb_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
                                         C.c_uint64, _VP, _VP, _VP]),
+    "alacgpu_specaugment_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, _VP, _VP,
+                                             C.c_uint32, _VP, C.c_uint32, C.c_float, _VP]),
     "alacgpu_encode_max_packet_bytes": (C.c_size_t, [C.c_uint32, C.c_int, C.c_int]),
     "alacgpu_encode_device": (C.c_int, [_VP, _VP, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, _VP, _VP, _VP, C.c_uint32,
                                         _VP, C.c_uint64, _VP, _VP, _VP]),
@@ -420,6 +422,20 @@ class AlacGpuContext(_Closing):
         reverb.py states the arithmetic.  Two launches, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
         rc = lib().alacgpu_reverb_device(self._ctx, _dp(d_src), _dp(d_out), _dp(d_rir), rows, channels, rir_channels, stride,
                                          rir_stride, frames, rir_frames, _dp(d_valid), _dp(d_rir_valid), _VP(stream))
+        _check(rc, self._ctx)
+
+    def specaugment_device(self, d_src, d_out, rows, channels, n_mels, line_stride, line_len, d_valid, d_warp, d_freq, d_time, fill,
+                           stream=0):
+        """alacgpu_specaugment_device: SpecAugment on d_src (float32 device tensor [rows, channels, n_mels, line_stride], the
+        first line_len of a line are frames) into d_out (d_src itself or the same layout apart from it), over the first
+        tau = min(max(d_valid[row], 0), line_len) frames of every row: the time warp d_warp (int32 device tensor [rows, 2] of
+        (c, c'), or None), then the frequency masks d_freq [rows, n_freq, 2] and the time masks d_time [rows, n_time, 2]
+        (int32, (first, width); None for none) set to `fill`.  d_valid: an int64 device tensor [rows], or None for whole
+        lines.  augment.py states the arithmetic.  One launch, asynchronous on `stream` (raw hipStream_t); nothing is read
+        back."""
+        rc = lib().alacgpu_specaugment_device(self._ctx, _dp(d_src), _dp(d_out), rows, channels, n_mels, line_stride, line_len,
+                                              _dp(d_valid), _dp(d_warp), _dp(d_freq), 0 if d_freq is None else d_freq.shape[1],
+                                              _dp(d_time), 0 if d_time is None else d_time.shape[1], fill, _VP(stream))
         _check(rc, self._ctx)
 
     def set_output_format(self, fmt):
@@ -995,3 +1011,5 @@ from .normalize import MeanVar, TopDb, normalize, normalize_host, normalize_host
 from .mix import AddNoise, mix, mix_host, mix_host_f32  # noqa: E402
 # ---- room reverberation into crops and tensors (alacgpu_reverb_device) ------------------------------------------------------------
 from .reverb import Reverb, reverb, reverb_host, reverb_host_f32  # noqa: E402
+# ---- SpecAugment on the features: time warp, frequency and time masks (alacgpu_specaugment_device) -------------------------------
+from .augment import SpecAugment, spec_augment, specaugment_host, specaugment_host_f32  # noqa: E402

@@ -1,4 +1,4 @@
-"""What the stage calls behind the crops -- `reverb`, `mix`, `log_mel`, `normalize` -- share in front of their one library
+"""What the stage calls behind the crops -- `reverb`, `mix`, `log_mel`, `normalize`, `spec_augment` -- share in front of their one library
 call: the immutable specification base (`_Spec`, `_f32_finite`), the lengths on both sides (`_lengths_host`,
 `_lengths_device`), the layouts a kernel takes (`_lines`, `_planes`, `_span`), the context of a tensor's device
 (`_device_context`), the tree of halves of the float32 twins (`_tree`), and `_signal_and_companion`: the one check of a

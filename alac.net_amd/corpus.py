@@ -36,6 +36,7 @@ import numpy as np
 from . import (MAX_FRAME, ST_OK, ST_UNSUPPORTED_ELEMENT, ST_UNSUPPORTED_PREDTYPE, AlacGpuContext, AlacGpuError, PinnedBuffer,
                _Closing, _check, _check_batch_args, _compact_slots, _dp, _encode_slots, _frame_count, _status_text, _torch_dtype,
                _VP, _write_file, lib, make_cfgs)
+from .augment import LDS_MAX as _WARP_MAX, _check_draws, _how, _spec_augment
 from .features import LogMel, feature_lengths
 from .mix import AddNoise, _mix, snr_ratio
 from .normalize import MeanVar, TopDb, _normalize
@@ -622,7 +623,7 @@ class Corpus(_Closing):
         return torch.from_numpy(f.astype(np.int32)).to(self._dev), torch.from_numpy(o).to(self._dev), True
 
     def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True, features=None, normalize=None, mix=None,
-              reverb=None, sample_rate=None, mono=False):
+              reverb=None, augment=None, sample_rate=None, mono=False):
         """Decode crop b = frames frame_offsets[b] .. + num_frames of file files[b] for every b in ONE launch pair: returns
         (pcm [B, C, num_frames] on the device, zero behind lengths[b]; lengths [B], a DEVICE int64 tensor: min(num_frames,
         T_f - offset)).  float32 (default) or int32, as `load`.  files / frame_offsets: sequences, numpy arrays or torch
@@ -639,7 +640,7 @@ class Corpus(_Closing):
         rate, and mono of one channel -- are the path above.  A corpus whose files differ in rate (mixed_rates=True) has no
         rate of its own: sample_rate is required (ValueError without), and every crop comes through `_rate_crops`.
 
-        The four stages behind the waveform go by keyword, as sample_rate and mono do, and run in this order whichever are
+        The five stages behind the waveform go by keyword, as sample_rate and mono do, and run in this order whichever are
         given, in place, by the corpus's own context on the same stream; lengths, `check` and last_status() are those of the
         call without them (with check=True a second corpus's own check runs too, and first).  ValueError before any device
         work for what a stage cannot take.
@@ -664,10 +665,17 @@ class Corpus(_Closing):
         normalize: a normalize.MeanVar -- every line over its valid elements: lengths for PCM, feat_lengths for features, so a
         crop outside the corpus is zeros -- or a normalize.TopDb -- every crop of features, or every channel of it with
         per_channel.  Bit for bit normalize.normalize(what the call returns without it, normalize, lengths).  ValueError: a
-        TopDb without features, a MeanVar with int32 crops."""
+        TopDb without features, a MeanVar with int32 crops.
+
+        augment: SpecAugment on the features, the last stage: an augment.SpecAugment, whose draws are then made here from the
+        device's default generator (behind an AddNoise's and a Reverb's), or the pair (SpecAugment, draws) with the three
+        tensors that its `draw(n_mels, feat_lengths)` returned.  Bit for bit augment.spec_augment(what the call returns without
+        it, augment, feat_lengths); a crop outside the corpus (feat_lengths -1) is left as it is.  ValueError: no features=,
+        draws that are not three int32 tensors [B, 2], [B, masks, 2], [B, masks, 2] on the corpus's device, a time warp of
+        more than 16384 feature frames."""
         import torch
 
-        # 1. every refusal that needs no device work: mix, reverb, normalize, features; the waveform's own are `_waveform`'s
+        # 1. every refusal that needs no device work: mix, reverb, normalize, features, augment; the waveform's own are `_waveform`'s
         rate = self.sample_rate if sample_rate is None else sample_rate
         Co = 1 if mono else self.channels
         is_f32 = lambda: _torch_dtype(torch, torch.float32 if dtype is None else dtype) == torch.float32
@@ -691,6 +699,10 @@ class Corpus(_Closing):
                 raise ValueError(f"features for {features.sample_rate} Hz, crops at {rate} Hz")
             if not is_f32():
                 raise ValueError("features are computed from float32 crops")
+        if augment is not None:
+            augment = _how(augment, "augment")
+            if features is None:
+                raise ValueError("a SpecAugment masks log-mel features: it needs features=")
         if features is not None or mix is not None or reverb is not None:
             L = _frame_count("num_frames", num_frames)
             if features is not None and L <= features.n_fft // 2:
@@ -698,6 +710,11 @@ class Corpus(_Closing):
             self._open()
             B = int(files.shape[0]) if isinstance(files, torch.Tensor) and files.dim() == 1 else len(np.asarray(files))
         if features is not None:
+            if augment is not None:
+                if augment[1] is not None:
+                    augment = (augment[0], tuple(_check_draws(augment[1], B, self._dev)))
+                if augment[0].time_warp and features.frames(L) > _WARP_MAX:
+                    raise ValueError(f"features of {features.frames(L)} frames: a time warp takes at most {_WARP_MAX}")
             feats = self._out(out, (B, Co, features.n_mels, features.frames(L)), torch.float32, zero=False)
             out = self._scratch("_ft_scratch", (B, Co, L))
         # 2. the companion crops, by the second corpora's own `crops`: the noise, then the responses
@@ -728,6 +745,8 @@ class Corpus(_Closing):
             res, lengths = feats, feature_lengths(lengths, features.hop_length)
         if normalize is not None:
             _normalize(ctx, res, normalize, lengths, res)
+        if augment is not None:
+            _spec_augment(ctx, res, augment[0] if augment[1] is None else augment, lengths, res)
         return res, lengths
 
     def _waveform(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono):
@@ -959,14 +978,15 @@ class Corpus(_Closing):
         return out, lengths
 
     def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True, features=None, normalize=None,
-                     mix=None, reverb=None, sample_rate=None, mono=False):
+                     mix=None, reverb=None, augment=None, sample_rate=None, mono=False):
         """`batch` crops of num_frames frames drawn on the device: files uniform over the corpus, the first frame uniform in
         0 .. max(T_f - num_frames, 0).  generator: a torch.Generator (of the corpus's device, or of the CPU: then the draws are
         made there and uploaded).  Returns (pcm, lengths, files, frame_offsets), the draws as device int64 tensors.
         sample_rate / mono as for `crops`: the frames, T_f included, then count at sample_rate.  features as for `crops`:
         (feats, feat_lengths, files, frame_offsets).  normalize as for `crops`.  mix as for `crops`; an AddNoise is drawn from
         `generator`, behind the call's own two draws (AddNoise.draw states its four).  reverb as for `crops`; a Reverb is
-        drawn from `generator` behind those (Reverb.draw states its two)."""
+        drawn from `generator` behind those (Reverb.draw states its two).  augment as for `crops`; a SpecAugment is drawn from
+        `generator` behind those, for the feat_lengths the call returns (augment.py states its draws)."""
         import torch
 
         B, L = _frame_count("batch", batch), _frame_count("num_frames", num_frames)
@@ -975,6 +995,10 @@ class Corpus(_Closing):
             mix = self._second_corpus(mix, _MIX, dtype, rate, 1 if mono else self.channels)
         if reverb is not None:
             reverb = self._second_corpus(reverb, _REVERB, dtype, rate, 1 if mono else self.channels)
+        if augment is not None:
+            augment = _how(augment, "augment")
+            if features is None:
+                raise ValueError("a SpecAugment masks log-mel features: it needs features=")
         dev = generator.device if generator is not None else self._dev
         files = torch.randint(0, self.num_files, (B,), generator=generator, device=dev, dtype=torch.int64).to(self._dev)
         u = torch.rand(B, generator=generator, device=dev, dtype=torch.float64).to(self._dev)
@@ -987,8 +1011,11 @@ class Corpus(_Closing):
             mix = (mix[0], mix[0].draw(B, L, sample_rate=rate, generator=generator))
         if reverb is not None and reverb[1] is None:
             reverb = (reverb[0], reverb[0].draw(B, generator=generator))
+        if augment is not None and augment[1] is None and isinstance(features, LogMel):
+            feat_lengths = feature_lengths((totals[files] - offs).clamp(max=L), features.hop_length)
+            augment = (augment[0], augment[0].draw(features.n_mels, feat_lengths, generator=generator))
         pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,
-                                  features=features, normalize=normalize, mix=mix, reverb=reverb)
+                                  features=features, normalize=normalize, mix=mix, reverb=reverb, augment=augment)
         return pcm, lengths, files, offs
 
     def last_staged_bytes(self):

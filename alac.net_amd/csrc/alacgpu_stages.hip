@@ -1,5 +1,5 @@
 // alacgpu_stages.hip -- C ABI of include/alacgpu.h, the stages around the decode: the crop planner, the scan with the packet
-// compaction and staging, the resamplers, log-mel, the reverberation, the noise mix, the normalisations and the encoder.  Of the ctx they use the device, the cfgs, last_error and
+// compaction and staging, the resamplers, log-mel, the reverberation, the noise mix, the normalisations, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
 // their own scratch; the decode path is alacgpu_api.hip.  No CPU fallback here either: every stage is its kernels.
 #include <algorithm>
 #include <cmath>
@@ -9,6 +9,7 @@
 #include "alac_resample.h"
 #include "alac_features.h"
 #include "alac_normalize.h"
+#include "alac_augment.h"
 #include "alac_mix.h"
 #include "alac_reverb.h"
 #include "alac_encode.h"
@@ -479,6 +480,46 @@ int alacgpu_normalize_top_device(alacgpu_ctx* ctx, const void* d_src, void* d_ou
     HIP_TRY(ctx, hipLaunchKernel((const void*)alac_top_apply_kernel, dim3((uint32_t)grid), dim3(ALAC_TOP_THREADS), kargs, 0, stream));
     HIP_TRY(ctx, hipGetLastError());
     return ctx->norm.release(ctx, stream);
+}
+
+int alacgpu_specaugment_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t channels, uint32_t n_mels,
+                               uint64_t line_stride, uint64_t line_len, const void* d_valid, const void* d_warp, const void* d_freq,
+                               uint32_t n_freq, const void* d_time, uint32_t n_time, float fill, void* hip_stream) {
+    uint64_t lines;
+    if (channels == 0 || n_mels == 0 || (uint64_t)channels * n_mels > 0xFFFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (!normalize_args_ok(ctx, d_src, d_out, rows, channels * n_mels, line_stride, line_len, lines) ||
+        !args_ok({{d_valid, 8, false}, {d_warp, 4, false}, {d_freq, 4, n_freq != 0}, {d_time, 4, n_time != 0}}))
+        return ALACGPU_ERR_BAD_ARG;
+    if (!std::isfinite(fill) || n_freq > ALAC_AUG_MAX_MASKS || n_time > ALAC_AUG_MAX_MASKS || (d_warp && line_len > ALAC_AUG_LDS_MAX))
+        return ALACGPU_ERR_BAD_ARG;
+    const uint64_t grid = alac_augment_grid(lines, line_len);
+    if (grid > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool wave = line_len <= ALAC_AUG_WAVE_MAX;
+    const void* const kernel = wave ? (const void*)alac_specaugment_wave_kernel : (const void*)alac_specaugment_line_kernel;
+    const size_t lds = alac_augment_lds_bytes(line_len, n_time, d_warp != nullptr);      // (at most 72 KiB by the limits above)
+    if (lds > 32768u) HIP_TRY(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    alac_augment_params p;
+    p.src = (const float*)d_src;
+    p.out = (float*)d_out;
+    p.valid = (const int64_t*)d_valid;
+    p.warp = (const int32_t*)d_warp;
+    p.freq = (const int32_t*)d_freq;
+    p.time = (const int32_t*)d_time;
+    p.lines = lines;
+    p.lines_per_row = channels * n_mels;
+    p.n_mels = n_mels;
+    p.n_freq = n_freq;
+    p.n_time = n_time;
+    p.stage = d_warp ? (uint32_t)line_len : 0u;
+    p.line_stride = line_stride;
+    p.line_len = line_len;
+    p.fill = fill;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel(kernel, dim3((uint32_t)grid), dim3(ALAC_AUG_THREADS), kargs, lds, (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
 }
 
 int alacgpu_reverb_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, const void* d_rir, uint32_t rows, uint32_t channels,

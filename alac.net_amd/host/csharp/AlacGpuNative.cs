@@ -126,6 +126,14 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_reverb_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, IntPtr dRir, uint rows,
             uint channels, uint rirChannels, ulong stride, ulong rirStride, ulong frames, ulong rirFrames, IntPtr dValid,
             IntPtr dRirValid, IntPtr hipStream);
+        /// <summary>SpecAugment on float features in device memory (dSrc, dOut [rows, channels, nMels, lineStride], the first
+        /// lineLen of a line are frames), one launch: per row a time warp (dWarp int[rows, 2]: (c, c'), or IntPtr.Zero for
+        /// none), nFreq frequency masks and nTime time masks (dFreq int[rows, nFreq, 2], dTime int[rows, nTime, 2]: (first,
+        /// width)) over the first dValid[row] frames (long[rows] or IntPtr.Zero for all), masked elements set to fill.  dOut
+        /// is dSrc itself or apart from it.  Asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_specaugment_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, uint rows,
+            uint channels, uint nMels, ulong lineStride, ulong lineLen, IntPtr dValid, IntPtr dWarp, IntPtr dFreq, uint nFreq,
+            IntPtr dTime, uint nTime, float fill, IntPtr hipStream);
         /// <summary>Encode PCM in device memory (int32 or float32, interleaved or planar) to ALAC packets in device memory, one
         /// run of frames per packet, packet p at dPackets + p * slotBytes; asynchronous on hipStream.</summary>
         [DllImport(Lib)] public static extern UIntPtr alacgpu_encode_max_packet_bytes(uint frames, int sampleSize, int channels);

@@ -574,6 +574,41 @@ int alacgpu_reverb_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, cons
                           uint32_t rir_channels, uint64_t stride, uint64_t rir_stride, uint64_t frames, uint64_t rir_frames,
                           const void* d_valid, const void* d_rir_valid, void* hip_stream);
 
+/*
+ * alacgpu_specaugment_device: SpecAugment on the features, behind the normalisations (no counterpart in the reference): a time
+ * warp, frequency masks and time masks per crop in one launch, no atomics, no scratch.  The data is float32 [rows, channels,
+ * n_mels, line_stride]: a line is one mel bin of one channel of a row, its first line_len <= line_stride elements are
+ * frames, what lies behind them is neither read nor written.  d_out is d_src itself (in place) or an array of the same layout
+ * apart from it.  All lines of row r share its draws, int32 on the device: d_warp [rows, 2] = (c, c') (NULL: no warp in this
+ * call), d_freq [rows, n_freq, 2] and d_time [rows, n_time, 2] = (first, width).  With tau = min(max(d_valid[r], 0),
+ * line_len) (d_valid: int64 [rows]; NULL: line_len), in this order:
+ *   warp    only where 1 <= c, c' <= tau - 2 and c != c'.  Frame t < tau reads the source position
+ *             s(t) = t c / c'                                       for t <= c'
+ *             s(t) = c + (t - c') (tau - 1 - c) / (tau - 1 - c')    for t >  c'
+ *           as i = floor(s) and the remainder r over the denominator den, in integers:
+ *             y[t] = x[i]                                  where r == 0 (x[i + 1] is not read; t = 0, c' and tau - 1 are such)
+ *             y[t] = x[i] + f * (x[i + 1] - x[i]),  f = fl(r) / fl(den)      the division, the difference, the product and the
+ *                                                                            sum each rounded once, nothing contracted
+ *   freq    mask k sets every frame t < tau of the bins first .. first + width - 1 (within 0 .. n_mels - 1) to fill
+ *   time    mask k sets the frames first .. first + width - 1 (within 0 .. tau - 1) of every bin to fill
+ * A width <= 0 is no mask; (0, 0) is no warp.  Frames at and behind tau, and every row with d_valid[r] <= 0, stay bit for bit
+ * (out of place: are copied).  A line of a row without a warp is neither read nor rewritten as a whole in place: its masked
+ * spans are stored and nothing else is touched; a frequency-masked line is stored without being loaded.  A warped line is
+ * held in LDS, its tau frames, before any of it is written, and the masks are applied while it is stored.  Lines of up to 256
+ * frames are taken by a wave each, four to a workgroup, longer ones by a workgroup of 256 threads each; accesses are 16 bytes
+ * wide where a line's address allows, and single frames in front of and behind those.  A line of more than 16384 frames cannot
+ * be warped (64 KiB of LDS); masks alone have no such limit.  Device pointers only, asynchronous on hip_stream, nothing is read
+ * back; nothing of the ctx is used but its device.  rows == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx, d_src or d_out, d_freq NULL with n_freq != 0, d_time NULL with
+ * n_time != 0, a misaligned array (4; 8 for d_valid), channels 0, n_mels 0, channels * n_mels of 2^32 or more, line_len 0 or
+ * above line_stride, d_src and d_out that overlap without being equal, an extent of 2^60 bytes or more, 2^31 workgroups or
+ * more, a fill that is not finite, more than 1024 masks of a kind, d_warp with line_len above 16384.
+ */
+int alacgpu_specaugment_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t channels, uint32_t n_mels,
+                               uint64_t line_stride, uint64_t line_len, const void* d_valid, const void* d_warp,
+                               const void* d_freq, uint32_t n_freq, const void* d_time, uint32_t n_time, float fill,
+                               void* hip_stream);
+
 /* Single-packet drop-in for `int DecodeFrame(byte[] inbuffer, int[] outbuffer)` (AlacFile.cs:428):
  * writes the reference's own int[] layout (24-bit: one int per byte) and returns its byte count in
  * *out_bytes.  status as above (the C# shim rethrows the reference's exceptions from it). */

@@ -71,6 +71,8 @@ SYMBOLS = {
                                           C.c_uint32, _VP, _VP, C.c_int, _VP, _VP]),
     "alacgpu_resample_rows_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, _VP, _VP, _VP, C.c_uint64, _VP, _VP,
                                                C.c_uint32, _VP, _VP, _VP, C.c_int, _VP, _VP]),
+    "alacgpu_resample_ratio_rows_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, _VP, _VP, _VP, C.c_uint64, _VP, _VP,
+                                                     C.c_uint32, _VP, C.c_int, _VP, _VP]),
     "alacgpu_logmel_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _VP,
                                         _VP, _VP, C.c_int, C.c_float, _VP, C.c_uint64, _VP]),
     "alacgpu_normalize_meanvar_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, C.c_int, C.c_int,
@@ -368,6 +370,19 @@ class AlacGpuContext(_Closing):
                                                 _dp(d_src_valid), _dp(d_out_first), out_frames, _ptr(tables), _dp(d_tables),
                                                 len(tables), _dp(d_d0), _dp(d_weights), _dp(d_row_table), int(bool(mono)),
                                                 _dp(d_out), _VP(stream))
+        _check(rc, self._ctx)
+
+    def resample_ratio_rows_device(self, d_src, rows, channels, src_stride, d_src_origin, d_src_valid, d_out_first, out_frames, ratios,
+                                   d_ratios, d_row_ratio, mono, d_out, stream=0):
+        """alacgpu_resample_ratio_rows_device: resample_device without tables, a ratio per row and every weight evaluated per
+        tap (speed.py states the arithmetic).  ratios: the ratios on the host, a uint32 array [n_ratios, 3] of (a, b, width);
+        d_ratios: the same on the device (int32 device tensor); d_row_ratio[r] (int32 device tensor, read as unsigned): the
+        ratio of row r -- n_ratios and above, or a ratio with a == 0: the row is skipped, its part of d_out left as it is.
+        Asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        ratios = np.ascontiguousarray(ratios, dtype=np.uint32).reshape(-1, 3)
+        rc = lib().alacgpu_resample_ratio_rows_device(self._ctx, _dp(d_src), rows, channels, src_stride, _dp(d_src_origin),
+                                                      _dp(d_src_valid), _dp(d_out_first), out_frames, _ptr(ratios), _dp(d_ratios),
+                                                      len(ratios), _dp(d_row_ratio), int(bool(mono)), _dp(d_out), _VP(stream))
         _check(rc, self._ctx)
 
     def logmel_device(self, d_src, rows, channels, src_stride, frames, n_fft, hop, n_mels, d_window, d_basis, d_fb, log_mode, floor,
@@ -1013,3 +1028,4 @@ from .mix import AddNoise, mix, mix_host, mix_host_f32  # noqa: E402
 from .reverb import Reverb, reverb, reverb_host, reverb_host_f32  # noqa: E402
 # ---- SpecAugment on the features: time warp, frequency and time masks (alacgpu_specaugment_device) -------------------------------
 from .augment import SpecAugment, spec_augment, specaugment_host, specaugment_host_f32  # noqa: E402
+from .speed import SpeedPerturb, speed_host, speed_host_f32, speed_perturb  # noqa: E402

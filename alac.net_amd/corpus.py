@@ -23,6 +23,10 @@ AddNoise, then the impulse responses of a Reverb, each cropped by its own corpus
 (`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_logmel_device and
 the normalisation (reverb.py, mix.py, features.py and normalize.py state the arithmetic), each only if asked for.
 
+`crops(..., speed=)` plays every crop at a drawn factor in front of all that (`Corpus._speed_crops`, speed.py): the step of a
+corpus whose rates differ, with a ratio per (file rate, factor) in place of one per file rate; the crops at factor 1 go through
+the table kernels, the others through alacgpu_resample_ratio_rows_device, which evaluates its weights per tap.
+
 `Corpus(sources, mixed_rates=True)` takes files of different sample rates.  Crops of such a corpus exist at a target rate only;
 a step is the same method and the same launches, with a source window per crop in the plan
 (alacgpu_plan_crops_frames_device) and a filter table per row in the resampler (alacgpu_resample_rows_device).
@@ -41,6 +45,7 @@ from .features import LogMel, feature_lengths
 from .mix import AddNoise, _mix, snr_ratio
 from .normalize import MeanVar, TopDb, _normalize
 from .reverb import Reverb, _reverb
+from .speed import MAX_WIDTH as _SPEED_MAX_WIDTH, SpeedPerturb, ratio as _speed_ratio
 
 PAD_CFG = 0xFFFF        # a padding entry's cfg_idx: never a row of the context, so the kernels switch the entry off
 MAX_CFGS = 65535
@@ -553,17 +558,24 @@ class Corpus(_Closing):
             return self._window(sample_rate, _frame_count("num_frames", num_frames))
         return self._window(None, int(num_frames))
 
-    def _window(self, R, L):
-        """Per (target rate, crop length), once: Ls, the source frames a crop's window takes -- L itself for R None, the native
+    def _window(self, R, L, speed=None):
+        """Per (target rate, crop length, speed), once: Ls, the source frames a crop's window takes -- L itself for R None, the native
         window; else resample.source_window's bound, an int, or where the rates differ int64 [F] with file f's by its own
         ratio, and then d_Ls as well, the same as an int32 device tensor --, Ls_max, the largest, and K and S, where a file
         counts with its own Ls.  S only where there is a host tier, else None: the packet sizes of a corpus from PCM would
-        have to come from the device for it."""
+        have to come from the device for it.  speed (a SpeedPerturb; R is then a rate): a file counts with the largest
+        window over the factors, and d_Ls is int32 [rates * factors], the window of every (file rate, factor)."""
         import torch
 
-        if (R, L) not in self._windows:
+        if (R, L, speed) not in self._windows:
             Ls = L
-            if R is not None:
+            if speed is not None:
+                st = self._speed_rate(R, speed)
+                each = ((max(L, 1) - 1) // st["b"] + 2) * st["a"] + 2 * st["width"]            # [rates, factors]
+                Ls = each.max(axis=1)[st["rate_of"]]
+                if int(np.max(Ls)) >= 1 << 32:
+                    raise ValueError(f"num_frames {L} needs {int(np.max(Ls))} source frames: that does not fit 32 bits")
+            elif R is not None:
                 rt = self._rate(R)
                 Ls = ((max(L, 1) - 1) // rt["b"] + 2) * rt["a"] + 2 * rt["width"]
                 if int(np.max(Ls)) >= 1 << 32:
@@ -571,10 +583,12 @@ class Corpus(_Closing):
             h = self._host
             win = dict(Ls=Ls, Ls_max=int(np.max(Ls)), K=max(entries_per_crop(h["pkt_end"], h["file_first"], Ls), 1),
                        S=stage_bytes_per_crop(self._host_table("pkt_size"), h["pkt_end"], h["file_first"], Ls) if self._hi_bytes else None)
-            if np.ndim(Ls):
+            if speed is not None:
+                win["d_Ls"] = torch.from_numpy(each.reshape(-1).astype(np.uint32).view(np.int32)).to(self._dev)
+            elif np.ndim(Ls):
                 win["d_Ls"] = torch.from_numpy(Ls.astype(np.uint32).view(np.int32)).to(self._dev)
-            self._windows[R, L] = win
-        return self._windows[R, L]
+            self._windows[R, L, speed] = win
+        return self._windows[R, L, speed]
 
     def _plan_arrays(self, n):
         """The six plan arrays and the status array, kept and reused while n does not grow past them."""
@@ -623,7 +637,7 @@ class Corpus(_Closing):
         return torch.from_numpy(f.astype(np.int32)).to(self._dev), torch.from_numpy(o).to(self._dev), True
 
     def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True, features=None, normalize=None, mix=None,
-              reverb=None, augment=None, sample_rate=None, mono=False):
+              reverb=None, speed=None, augment=None, sample_rate=None, mono=False):
         """Decode crop b = frames frame_offsets[b] .. + num_frames of file files[b] for every b in ONE launch pair: returns
         (pcm [B, C, num_frames] on the device, zero behind lengths[b]; lengths [B], a DEVICE int64 tensor: min(num_frames,
         T_f - offset)).  float32 (default) or int32, as `load`.  files / frame_offsets: sequences, numpy arrays or torch
@@ -639,6 +653,13 @@ class Corpus(_Closing):
         count frames at sample_rate, pcm is float32 [B, 1 if mono else C, num_frames].  The defaults -- and the corpus's own
         rate, and mono of one channel -- are the path above.  A corpus whose files differ in rate (mixed_rates=True) has no
         rate of its own: sample_rate is required (ValueError without), and every crop comes through `_rate_crops`.
+
+        speed: speed perturbation of the waveform, in front of everything else: a speed.SpeedPerturb, whose draws are then made
+        here from the device's default generator, or the pair (SpeedPerturb, draws) with the int64 tensor [B] that its
+        `draw(B)` returned.  Crop b is then frames frame_offsets[b] .. + num_frames of its file PLAYED AT ITS FACTOR and
+        resampled as a whole to the rate of the crops (`_speed_crops`); a crop that draws factor 1 is bit for bit the crop of
+        the call without speed=.  Every stage behind it sees the perturbed waveform.  ValueError: int32 crops, a corpus of
+        more than 2 channels, draws that are not an integer tensor [B] on the corpus's device.
 
         The five stages behind the waveform go by keyword, as sample_rate and mono do, and run in this order whichever are
         given, in place, by the corpus's own context on the same stream; lengths, `check` and last_status() are those of the
@@ -679,6 +700,8 @@ class Corpus(_Closing):
         rate = self.sample_rate if sample_rate is None else sample_rate
         Co = 1 if mono else self.channels
         is_f32 = lambda: _torch_dtype(torch, torch.float32 if dtype is None else dtype) == torch.float32
+        if speed is not None:
+            speed = self._speed_given(speed, dtype, rate)
         if mix is not None:
             mix = self._second_corpus(mix, _MIX, dtype, rate, Co)
         if reverb is not None:
@@ -703,12 +726,14 @@ class Corpus(_Closing):
             augment = _how(augment, "augment")
             if features is None:
                 raise ValueError("a SpecAugment masks log-mel features: it needs features=")
-        if features is not None or mix is not None or reverb is not None:
+        if features is not None or mix is not None or reverb is not None or speed is not None:
             L = _frame_count("num_frames", num_frames)
             if features is not None and L <= features.n_fft // 2:
                 raise ValueError(f"num_frames {L}: the transform needs more than n_fft // 2 = {features.n_fft // 2}")
             self._open()
             B = int(files.shape[0]) if isinstance(files, torch.Tensor) and files.dim() == 1 else len(np.asarray(files))
+        if speed is not None and speed[1] is not None and speed[1].shape[0] != B:
+            raise ValueError(f"{speed[1].shape[0]} draws of speed= for {B} crops")
         if features is not None:
             if augment is not None:
                 if augment[1] is not None:
@@ -729,7 +754,7 @@ class Corpus(_Closing):
                                                        rate=rate, check=check)
         # 3. the waveform, once: into `out`, or into the scratch the features are computed from
         res, lengths = self._waveform(files, frame_offsets, num_frames, dtype=dtype, out=out, check=check, sample_rate=sample_rate,
-                                      mono=mono)
+                                      mono=mono, speed=speed)
         # 4. the stages, in place and in this order on the same stream, by the corpus's own context
         ctx = lambda: self._gpu
         if reverb is not None:
@@ -749,13 +774,16 @@ class Corpus(_Closing):
             _spec_augment(ctx, res, augment[0] if augment[1] is None else augment, lengths, res)
         return res, lengths
 
-    def _waveform(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono):
-        """The crops themselves, what `crops` returns without a stage: through `_rate_crops` at another rate, as one channel
-        of two, or of a corpus whose rates differ; else planned and decoded here"""
+    def _waveform(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, speed=None):
+        """The crops themselves, what `crops` returns without a stage: through `_speed_crops` with speed=; through
+        `_rate_crops` at another rate, as one channel of two, or of a corpus whose rates differ; else planned and decoded here"""
         import torch
 
         if self.sample_rate is None and sample_rate is None:
             raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
+        if speed is not None:
+            return self._speed_crops(files, frame_offsets, num_frames, out=out, check=check, sample_rate=sample_rate, mono=mono,
+                                     speed=speed)
         if self.sample_rate is None or (mono and self.channels == 2) or (sample_rate is not None and sample_rate != self.sample_rate):
             return self._rate_crops(files, frame_offsets, num_frames, dtype=dtype, out=out, check=check, sample_rate=sample_rate,
                                     mono=mono)
@@ -811,6 +839,26 @@ class Corpus(_Closing):
             raise ValueError(f"the files of this corpus differ in sample rate: crops need sample_rate=, and {stage['they']} a rate to crop at")
         if other.channels != Co and other.channels not in (1, 2):
             raise ValueError(stage["channels"].format(n=other.channels, Co=Co))
+        return spec, draws
+
+    def _speed_given(self, given, dtype, rate):
+        """crops(speed=) as the pair (SpeedPerturb, draws or None), checked: ValueError for anything else, for int32 crops,
+        for a corpus of more than 2 channels and for crops without a rate.  Nothing is done on the device; the draws' length
+        is `_speed_crops`'s to check, where B is known."""
+        import torch
+
+        spec, draws = given if isinstance(given, tuple) and len(given) == 2 else (given, None)
+        if not isinstance(spec, SpeedPerturb):
+            raise ValueError(f"speed must be a speed.SpeedPerturb or (SpeedPerturb, what its draw() returned), not {given!r}")
+        if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
+            raise ValueError("float32 crops are speed-perturbed")
+        if self.channels not in (1, 2):
+            raise ValueError(f"{self.channels} channels: the resampler takes 1 or 2")
+        if rate is None:
+            raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
+        if draws is not None and (not isinstance(draws, torch.Tensor) or draws.dim() != 1 or draws.dtype.is_floating_point
+                                  or draws.dtype == torch.bool or draws.device != self._dev):
+            raise ValueError(f"the draws of speed= must be the integer tensor [B] of SpeedPerturb.draw on {self._dev}")
         return spec, draws
 
     def _companion_crops(self, other, scratch, files, offsets, frames, B, Co, rate, check):
@@ -889,10 +937,107 @@ class Corpus(_Closing):
         self._last = n
         return lengths
 
-    def resampled_frames(self, sample_rate):
+    def resampled_frames(self, sample_rate, speed=None):
         """Ty_f: the frames of every file at sample_rate, ceil(b * T_f / a) with the file's own reduced ratio a : b (int64 host
-        array [F])."""
+        array [F]).  speed (a SpeedPerturb): int64 [F, len(speed.factors)], the file played at every factor."""
+        if speed is not None:
+            if not isinstance(speed, SpeedPerturb):
+                raise ValueError(f"speed must be a speed.SpeedPerturb, not {speed!r}")
+            return self._speed_rate(self.sample_rate if sample_rate is None else sample_rate, speed)["Ty"]
         return self._rate(sample_rate)["Ty"]
+
+    def _speed_rate(self, R, speed):
+        """What crops at R Hz with the factors of `speed` need, once per (R, factors): the distinct file rates and rate_of
+        [F], a file's; per (rate, factor) a, b, width (speed.ratio; int64 host arrays [rates, factors]) and `ratios`, the same
+        flat as the kernel's uint32 [rates * factors, 3] -- with a = 0, a ratio that is skipped, at factor 1, whose crops go
+        through the tables --; Ty [F, factors]; `tables`, resample.rows_tables of the rates at factor 1; and the device copies
+        d_rate_of, d_a, d_b, d_width, d_Ty (flat), d_ratios, d_table_of [rates].  ValueError: a rate or a ratio the filters
+        do not take."""
+        import torch
+
+        from .resample import resampled_frames, rows_tables
+
+        if R is None:
+            raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
+        key = ("speed", R, speed.factors)
+        if key not in self._rates:
+            up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(self._dev)
+            rates, rate_of = np.unique(self.sample_rates, return_inverse=True)
+            rate_of = rate_of.reshape(-1).astype(np.int64)
+            abw = np.array([[_speed_ratio(int(r), f, R) for f in speed.factors] for r in rates], dtype=np.int64)
+            if int(abw[..., 2].max()) > _SPEED_MAX_WIDTH:
+                raise ValueError(f"{int(rates.max())} Hz to {R} Hz: a filter of width {int(abw[..., 2].max())}, the kernel takes {_SPEED_MAX_WIDTH}")
+            a, b, width = abw[..., 0], abw[..., 1], abw[..., 2]
+            ratios = abw.reshape(-1, 3).astype(np.uint32)
+            ratios[speed.one::len(speed.factors)] = (0, 1, 0)
+            table_of, desc, d0, w = rows_tables(rates.tolist(), R)
+            Ty = resampled_frames(self.num_frames[:, None], a[rate_of], b[rate_of])
+            self._rates[key] = dict(rates=rates, rate_of=rate_of, a=a, b=b, width=width, ratios=ratios, Ty=Ty, desc=desc,
+                                    d_rate_of=up(rate_of), d_a=up(a.reshape(-1)), d_b=up(b.reshape(-1)), d_width=up(width.reshape(-1)),
+                                    d_Ty=up(Ty.reshape(-1)), d_ratios=up(ratios.view(np.int32)), d_table_of=up(table_of),
+                                    d_desc=up(desc.view(np.int32)), d_d0=up(d0), d_w=up(w))
+        return self._rates[key]
+
+    def _speed_crops(self, files, frame_offsets, num_frames, out, check, sample_rate, mono, speed):
+        """crops(..., speed=(spec, draws)): crop b is frames frame_offsets[b] .. + num_frames of file files[b] played at the
+        factor k = draws[b] and RESAMPLED AS A WHOLE to the rate of the crops by a_c : b_c = speed.ratio(the file's rate,
+        factor, rate); lengths[b] = min(num_frames, Ty - offset) with Ty = ceil(b_c * T_f / a_c), -1 for a file, a draw or an
+        offset outside.  The step is `_rate_crops`'s for a corpus whose rates differ, with a ratio per (file rate, factor):
+        everything per crop is gathered from the device copies of `_speed_rate`'s small tables by integer operations,
+        alacgpu_plan_crops_frames_device plans the crop's own source window, and the scratch is resampled into `out` by two
+        calls: alacgpu_resample_rows_device for the crops at factor 1 -- the table of the file's rate, as without speed=, so
+        those crops are bit for bit what they are without it; every other row as zeros --, then
+        alacgpu_resample_ratio_rows_device for the others, which skips the rest.  Host-given offsets are checked on the host
+        against the file's largest Ty over the factors; the exact check is the device's."""
+        import torch
+
+        spec, draws = speed
+        L = _frame_count("num_frames", num_frames)
+        self._open()
+        st = self._speed_rate(self.sample_rate if sample_rate is None else sample_rate, spec)
+        R, nk = (self.sample_rate if sample_rate is None else sample_rate), len(spec.factors)
+        win = self._window(R, L, spec)
+        Ls, K = win["Ls_max"], win["K"]
+        d_files, d_offs, _ = self._indices(files, frame_offsets, st["Ty"].max(axis=1))
+        B, C_ = int(d_files.shape[0]), self.channels
+        if draws is None:
+            draws = spec.draw(B, device=self._dev)
+        if draws.shape[0] != B:
+            raise ValueError(f"{draws.shape[0]} draws for {B} crops")
+        out = self._out(out, (B, 1 if mono else C_, L), torch.float32, zero=False)
+        if B * K >= 1 << 32:
+            raise ValueError(f"{B} crops of up to {K} packets: a call plans fewer than 2^32 entries")
+        k64 = draws.to(torch.int64)
+        f64 = d_files.long()
+        ok = (f64 >= 0) & (f64 < self.num_files) & (k64 >= 0) & (k64 < nk)
+        fc, kc = f64.clamp(0, self.num_files - 1), k64.clamp(0, nk - 1)
+        Ty = st["d_Ty"][fc * nk + kc]
+        ok &= (d_offs >= 0) & (d_offs <= Ty)
+        idx = st["d_rate_of"][fc] * nk + kc
+        a, b, width = st["d_a"][idx], st["d_b"][idx], st["d_width"][idx]
+        origin = (torch.div(d_offs, b, rounding_mode="floor") * a - width).clamp(min=0)
+        src_offs = torch.where(ok, origin, -1)
+        lengths = torch.where(ok, (Ty - d_offs).clamp(max=L), -1)
+        if B == 0 or L == 0:
+            self._last = 0
+            if check and B:
+                self._raise_bad_length(lengths, d_files, d_offs)
+            return out, lengths
+        scratch = self._scratch("_rs_scratch", (B, C_, Ls))
+        scratch.zero_()
+        valid = self._plan_and_decode(d_files, src_offs, Ls, K, win["S"], scratch, d_frames=win["d_Ls"][idx])
+        stream = torch.cuda.current_stream(self._dev).cuda_stream
+        plain = kc == spec.one
+        row_table = torch.where(ok & plain, st["d_table_of"][st["d_rate_of"][fc]], len(st["desc"])).to(torch.int32)
+        self._gpu.resample_rows_device(scratch, B, C_, Ls, origin, valid, d_offs, L, st["desc"], st["d_desc"], st["d_d0"], st["d_w"],
+                                       row_table, mono, out, stream=stream)
+        if nk > 1:
+            row_ratio = torch.where(ok & ~plain, idx, len(st["ratios"])).to(torch.int32)
+            self._gpu.resample_ratio_rows_device(scratch, B, C_, Ls, origin, valid, d_offs, L, st["ratios"], st["d_ratios"], row_ratio,
+                                                 mono, out, stream=stream)
+        if check:
+            self._check_last(valid, d_files, src_offs, Ls, K, d_shown=d_offs)
+        return out, lengths
 
     def _rate(self, sample_rate):
         """What crops at sample_rate (None: the corpus's own rate) need, once per rate: Ty on the host and d_Ty on the device,
@@ -978,7 +1123,7 @@ class Corpus(_Closing):
         return out, lengths
 
     def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True, features=None, normalize=None,
-                     mix=None, reverb=None, augment=None, sample_rate=None, mono=False):
+                     mix=None, reverb=None, speed=None, augment=None, sample_rate=None, mono=False):
         """`batch` crops of num_frames frames drawn on the device: files uniform over the corpus, the first frame uniform in
         0 .. max(T_f - num_frames, 0).  generator: a torch.Generator (of the corpus's device, or of the CPU: then the draws are
         made there and uploaded).  Returns (pcm, lengths, files, frame_offsets), the draws as device int64 tensors.
@@ -986,11 +1131,16 @@ class Corpus(_Closing):
         (feats, feat_lengths, files, frame_offsets).  normalize as for `crops`.  mix as for `crops`; an AddNoise is drawn from
         `generator`, behind the call's own two draws (AddNoise.draw states its four).  reverb as for `crops`; a Reverb is
         drawn from `generator` behind those (Reverb.draw states its two).  augment as for `crops`; a SpecAugment is drawn from
-        `generator` behind those, for the feat_lengths the call returns (augment.py states its draws)."""
+        `generator` behind those, for the feat_lengths the call returns (augment.py states its draws).  speed as for `crops`;
+        a SpeedPerturb is drawn from `generator` behind the call's own two draws and in front of an AddNoise's
+        (SpeedPerturb.draw states its two), and the first frame is then uniform in 0 .. max(Ty[f, k] - num_frames, 0), from the
+        same u, with the frames of the file at its factor."""
         import torch
 
         B, L = _frame_count("batch", batch), _frame_count("num_frames", num_frames)
         rate = self.sample_rate if sample_rate is None else sample_rate
+        if speed is not None:
+            speed = self._speed_given(speed, dtype, rate)
         if mix is not None:
             mix = self._second_corpus(mix, _MIX, dtype, rate, 1 if mono else self.channels)
         if reverb is not None:
@@ -1004,18 +1154,26 @@ class Corpus(_Closing):
         u = torch.rand(B, generator=generator, device=dev, dtype=torch.float64).to(self._dev)
         if self.sample_rate is None and sample_rate is None:
             raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
-        totals = self._d_num_frames if sample_rate is None else self._rate(sample_rate)["d_Ty"]
-        span = (totals[files] - L).clamp(min=0)
+        if speed is not None:       # the frames of the crop's file played at the crop's factor
+            if speed[1] is None:
+                speed = (speed[0], speed[0].draw(B, generator=generator, device=self._dev))
+            elif speed[1].shape[0] != B:
+                raise ValueError(f"{speed[1].shape[0]} draws for {B} crops")
+            nk = len(speed[0].factors)
+            ends = self._speed_rate(rate, speed[0])["d_Ty"][files * nk + speed[1].to(torch.int64).clamp(0, nk - 1)]
+        else:
+            ends = (self._d_num_frames if sample_rate is None else self._rate(sample_rate)["d_Ty"])[files]
+        span = (ends - L).clamp(min=0)
         offs = torch.minimum(torch.floor(u * (span + 1).to(torch.float64)).to(torch.int64), span)
         if mix is not None and mix[1] is None:
             mix = (mix[0], mix[0].draw(B, L, sample_rate=rate, generator=generator))
         if reverb is not None and reverb[1] is None:
             reverb = (reverb[0], reverb[0].draw(B, generator=generator))
         if augment is not None and augment[1] is None and isinstance(features, LogMel):
-            feat_lengths = feature_lengths((totals[files] - offs).clamp(max=L), features.hop_length)
+            feat_lengths = feature_lengths((ends - offs).clamp(max=L), features.hop_length)
             augment = (augment[0], augment[0].draw(features.n_mels, feat_lengths, generator=generator))
         pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,
-                                  features=features, normalize=normalize, mix=mix, reverb=reverb, augment=augment)
+                                  features=features, normalize=normalize, mix=mix, reverb=reverb, augment=augment, speed=speed)
         return pcm, lengths, files, offs
 
     def last_staged_bytes(self):

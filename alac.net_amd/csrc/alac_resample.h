@@ -66,3 +66,32 @@ struct alac_resample_rows_params {
 };
 
 __global__ void alac_resample_rows_kernel(alac_resample_rows_params p);
+
+// ---- a ratio per row, no table (include/alacgpu.h: alacgpu_resample_ratio_rows_device) -----------------------------------------
+// One ratio of such a call: alacgpu_resample_ratio of include/alacgpu.h, field for field
+struct alac_resample_ratio {
+    uint32_t a, b, width;         // a == 0: the rows that name it are skipped
+};
+
+constexpr uint32_t ALAC_RESAMPLE_RATIO_MAX_WIDTH = (uint32_t)(ALAC_RESAMPLE_LDS_MAX / sizeof(float) - 2u) / 2u;   // a frame's span fits
+
+// What it shares with alac_resample_params has the same names: the kernels share resample_place and the staging of a span.
+struct alac_resample_ratio_params {
+    const float* src;             // [rows, channels, src_stride]
+    uint64_t src_stride;
+    const int64_t* src_origin;    // [rows]
+    const int64_t* src_valid;     // [rows]
+    const int64_t* out_first;     // [rows]
+    float* out;                   // [rows, mono ? 1 : channels, out_frames]
+    uint64_t out_frames;
+    const alac_resample_ratio* ratios;   // [n_ratios]
+    const uint32_t* row_ratio;    // [rows] the ratio of a row; n_ratios and above: the row is skipped
+    uint32_t n_ratios;
+    uint32_t channels;
+    uint32_t mono;
+    uint32_t tile;                // output frames per tile, the same for every row
+    uint32_t lds_floats;          // the dynamic LDS of the launch: the largest span of a tile over the call's ratios
+    uint32_t tiles_per_wg;
+};
+
+__global__ void alac_resample_ratio_rows_kernel(alac_resample_ratio_params p);

@@ -17,6 +17,11 @@
 // workgroup reads that table's descriptor (it is workgroup-uniform: scalar loads), loads that table into LDS and uses that
 // table's span; the tile is the call's.  Row for row the arithmetic is the one above, so a row is bit for bit what the
 // one-table call gives for it.  A row that names no table is written as zeros.
+//
+// alacgpu_resample_ratio_rows_device (the end of this file) has no table at all: a ratio per row, and every tap's weight
+// evaluated where it is used.  It shares the placement of the workgroups and the staging of a tile's source span.
+#include <type_traits>
+
 #include "alac_resample.h"
 
 namespace {
@@ -39,6 +44,23 @@ __device__ __forceinline__ void resample_place(const P& p, uint32_t& group, uint
     const uint32_t plane = blockIdx.x / groups;
     c = plane % out_channels;
     row = plane / out_channels;
+}
+
+// The source span of a tile into LDS: xs[idx] = x[s_lo + idx], idx < span -- a frame outside [origin, origin + valid) is zero
+// whatever the memory holds, two channels become their mean here -- between the barriers that fence it from the tile before.
+__device__ __forceinline__ void resample_stage(float* xs, uint32_t span, int64_t s_lo, int64_t origin, int64_t valid, const float* s0,
+                                               const float* s1, bool two) {
+    __syncthreads();                                        // (the tile before has been computed)
+    for (uint32_t idx = threadIdx.x; idx < span; idx += ALAC_RESAMPLE_THREADS) {
+        const int64_t rel = s_lo + idx - origin;
+        float v = 0.0f;
+        if (rel >= 0 && rel < valid) {
+            v = s0[rel];
+            if (two) v = (v + s1[rel]) * 0.5f;
+        }
+        xs[idx] = v;
+    }
+    __syncthreads();
 }
 
 // The workgroup's tiles of (row, output channel c) with the table t; P: the fields the two kernels' parameters share.
@@ -77,17 +99,7 @@ __device__ __forceinline__ void resample_tiles(const P& p, const resample_table_
         }
         const int32_t d00 = tb.d0[i0];
         const int64_t s_lo = m0 * (int64_t)tb.a + d00;      // the first source frame of the tile
-        __syncthreads();                                    // (the tile before has been computed)
-        for (uint32_t idx = tid; idx < tb.span; idx += ALAC_RESAMPLE_THREADS) {
-            const int64_t rel = s_lo + idx - origin;
-            float v = 0.0f;
-            if (rel >= 0 && rel < valid) {
-                v = s0[rel];
-                if (two) v = (v + s1[rel]) * 0.5f;
-            }
-            xs[idx] = v;
-        }
-        __syncthreads();
+        resample_stage(xs, tb.span, s_lo, origin, valid, s0, s1, two);
         const uint64_t left = p.out_frames - k0;
         const uint32_t n_out = left < p.tile ? (uint32_t)left : p.tile;
         for (uint32_t k = tid; k < n_out; k += ALAC_RESAMPLE_THREADS) {
@@ -160,4 +172,154 @@ __global__ __launch_bounds__(ALAC_RESAMPLE_THREADS) void alac_resample_rows_kern
     const uint64_t most = (uint64_t)p.tiles_per_wg * p.tile;
     const uint32_t n_out = (uint32_t)(left < most ? left : most);
     for (uint32_t k = threadIdx.x; k < n_out; k += ALAC_RESAMPLE_THREADS) dst[k0 + k] = 0.0f;
+}
+
+// ---- a ratio per row, the weights evaluated per tap (alacgpu_resample_ratio_rows_device) ---------------------------------------
+// Speed perturbation makes ratios whose tables no LDS holds (44.1 kHz at factor 0.9 to 16 kHz is 3969 : 1600, 52800 weights),
+// and a different one per row.  The filter is one function of one variable (alac.net_amd/speed.py states all of this operation
+// by operation, and its numpy twin restates it): with M = max(a, b), the tap at source frame floor(j a / b) + d of output frame
+// j, j a = q b + r, has
+//     n = d b - r,   v = 99 n / (100 M),   weight = scale * sinc(v) * cos^2(pi v / 12) for |v| < 6, else 0,
+// scale = 0.99 min(a, b) / a.  k = 99 n is an exact integer that grows by 99 b from tap to tap; so does its residue modulo the
+// period 200 M of sin(pi v), with one conditional subtraction.  sin(pi |v|) is then +-sin(pi x), x = m / (100 M) in [0, 1/2]
+// from an integer m, and cos(pi v / 12) is sin(pi x), x = (600 M - |k|) / (1200 M) in (0, 1/2]: both arguments are reduced
+// before anything is rounded, and one odd polynomial of degree 13 serves both.  Nothing here is contracted, the division is the
+// correctly rounded one, and no hardware transcendental is used.
+//
+// The workgroup is the table kernels': tiles of `tile` output frames of one (row, output channel), the tile's source span in
+// LDS, a thread per output frame, N fused multiply-adds in ascending tap order, one writer per element.  The integers are 32
+// bits wide where 1200 M and every k fit 31 bits (every audio ratio), else 64.
+#pragma clang fp contract(off)
+
+namespace {
+
+// sin(pi x) for 0 <= x <= 1/2: the Taylor polynomial of degree 13, its coefficients (-1)^k pi^(2k+1) / (2k+1)! rounded to float32
+__device__ __forceinline__ float ratio_sinpi(float x) {
+    const float z = x * x;
+    float p = 0x1.e8f434p-12f;
+    p = __builtin_fmaf(p, z, -0x1.e3075p-8f);
+    p = __builtin_fmaf(p, z, 0x1.507834p-4f);
+    p = __builtin_fmaf(p, z, -0x1.32d2ccp-1f);
+    p = __builtin_fmaf(p, z, 0x1.466bc6p+1f);
+    p = __builtin_fmaf(p, z, -0x1.4abbcep+2f);
+    p = __builtin_fmaf(p, z, 0x1.921fb6p+1f);
+    return x * p;
+}
+
+// A row's ratio as the taps use it; I: int32_t or int64_t
+template <class I>
+struct ratio_view {
+    I period, half, quarter;      // 200 M, 100 M, 50 M
+    I reach;                      // 600 M: |k| at and above it is outside the filter
+    I step;                       // 99 b
+    float inv100, inv1200;        // 1 / float(100 M), 1 / float(1200 M)
+    float scale;                  // float(99 min(a, b)) / float(100 a)
+};
+
+// The weight of the tap with k = 99 n and m = k mod 200 M (in 0 .. 200 M)
+template <class I>
+__device__ __forceinline__ float ratio_weight(const ratio_view<I>& r, I k, I m) {
+    const I mag = k < 0 ? -k : k;
+    I ms = (k < 0 && m != 0) ? r.period - m : m;            // |k| mod 200 M
+    const bool minus = ms >= r.half;
+    ms = minus ? ms - r.half : ms;
+    ms = ms > r.quarter ? r.half - ms : ms;
+    const float s = ratio_sinpi((float)ms * r.inv100);
+    const float c = ratio_sinpi((float)(r.reach - mag) * r.inv1200);
+    const float pv = ((float)mag * r.inv100) * 0x1.921fb6p+1f;
+    const float g = ((minus ? -s : s) * (c * c)) / pv;
+    const float w = mag == 0 ? r.scale : r.scale * g;
+    return mag >= r.reach ? 0.0f : w;
+}
+
+template <class I>
+__device__ __forceinline__ void ratio_tiles(const alac_resample_ratio_params& p, const alac_resample_ratio d, uint32_t span, float* xs,
+                                            uint32_t group, uint32_t c, uint64_t row) {
+    typedef typename std::conditional<sizeof(I) == 4, uint32_t, uint64_t>::type U;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t N = 2u * d.width + 1u;
+    const uint32_t out_channels = p.mono ? 1u : p.channels;
+    const uint64_t M = d.a > d.b ? d.a : d.b;
+    ratio_view<I> r;
+    r.period = (I)(200u * M);
+    r.half = (I)(100u * M);
+    r.quarter = (I)(50u * M);
+    r.reach = (I)(600u * M);
+    r.step = (I)(99u * (uint64_t)d.b);
+    r.inv100 = 1.0f / (float)(int64_t)(100u * M);
+    r.inv1200 = 1.0f / (float)(int64_t)(1200u * M);
+    r.scale = (float)(int64_t)(99u * (uint64_t)(d.a < d.b ? d.a : d.b)) / (float)(int64_t)(100u * (uint64_t)d.a);
+
+    const int64_t origin = p.src_origin[row];
+    int64_t valid = p.src_valid[row];
+    valid = valid < 0 ? 0 : (valid > (int64_t)p.src_stride ? (int64_t)p.src_stride : valid);
+    const int64_t first = p.out_first[row];
+    const int64_t end_b = (origin + valid) * (int64_t)d.b;
+    const bool two = p.mono && p.channels == 2u;
+    const float* const s0 = p.src + (row * p.channels + c) * p.src_stride;
+    const float* const s1 = s0 + p.src_stride;
+    float* const dst = p.out + (row * out_channels + c) * p.out_frames;
+
+    for (uint32_t t = 0; t < p.tiles_per_wg; ++t) {
+        const uint64_t k0 = ((uint64_t)group * p.tiles_per_wg + t) * p.tile;
+        if (k0 >= p.out_frames) break;
+        // the tile's first frame: j0 a = q0 b + r0, floored (a j below 0 is written as zero, but its taps must not wrap)
+        const int64_t j0 = first + (int64_t)k0;
+        const int64_t ja = j0 * (int64_t)d.a;
+        int64_t q0 = ja / (int64_t)d.b;
+        int64_t r0 = ja - q0 * (int64_t)d.b;
+        if (r0 < 0) {
+            r0 += (int64_t)d.b;
+            q0 -= 1;
+        }
+        resample_stage(xs, span, q0 - (int64_t)d.width, origin, valid, s0, s1, two);
+        const uint64_t left = p.out_frames - k0;
+        const uint32_t n_out = left < p.tile ? (uint32_t)left : p.tile;
+        for (uint32_t k = tid; k < n_out; k += ALAC_RESAMPLE_THREADS) {
+            // frame j0 + k: (j0 + k) a = (q0 + q) b + rem -- its taps are xs[q ..+ N], the first one d = -width from floor(j a / b)
+            const U ta = (U)r0 + (U)k * (U)d.a;
+            const U q = ta / (U)d.b;
+            const U rem = ta - q * (U)d.b;
+            uint32_t rel = (uint32_t)q;
+            rel = rel > span - N ? span - N : rel;            // (never: span is alac_resample_span of this tile)
+            const U below = (U)99u * ((U)d.width * (U)d.b + rem);     // -k of the first tap, above 0
+            const U mm = below % (U)r.period;
+            I kk = -(I)below;
+            I m = mm ? r.period - (I)mm : (I)0;
+            const float* const x = xs + rel;
+            float acc = 0.0f;
+            for (uint32_t n = 0; n < N; ++n) {
+                acc = __builtin_fmaf(ratio_weight(r, kk, m), x[n], acc);
+                kk += r.step;
+                m += r.step;
+                m = m >= r.period ? m - r.period : m;
+            }
+            const int64_t j = j0 + (int64_t)k;
+            dst[k0 + k] = (j >= 0 && j * (int64_t)d.a < end_b) ? acc : 0.0f;
+        }
+    }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(ALAC_RESAMPLE_THREADS) void alac_resample_ratio_rows_kernel(alac_resample_ratio_params p) {
+    extern __shared__ __align__(16) float lds[];
+    uint32_t group, c;
+    uint64_t row;
+    resample_place(p, group, c, row);
+    // the row's ratio: workgroup-uniform.  A row that names none, a ratio with a == 0, and a descriptor that is not what the
+    // host was shown (a span that does not fit the LDS of this launch) are skipped: the row's output stays as it is
+    const uint32_t ri = p.row_ratio[row];
+    if (ri >= p.n_ratios) return;
+    const alac_resample_ratio d = p.ratios[ri];
+    if (d.a == 0 || d.b == 0 || d.width == 0 || d.width > ALAC_RESAMPLE_RATIO_MAX_WIDTH || (d.a | d.b) >> 31) return;
+    const uint64_t span = alac_resample_span(p.tile, d.a, d.b, d.width);
+    if (span > p.lds_floats) return;
+    // 32-bit integers where 1200 M, the first tap's 99 (width b + b) and a tile's r0 + (tile - 1) a all stay below 2^31
+    const uint64_t M = d.a > d.b ? d.a : d.b;
+    const uint64_t most = 99u * ((uint64_t)d.width + 2u) * d.b;
+    if (1200u * M < (1ull << 31) && most < (1ull << 31) && (uint64_t)p.tile * d.a + d.b < (1ull << 31))
+        ratio_tiles<int32_t>(p, d, (uint32_t)span, lds, group, c, row);
+    else
+        ratio_tiles<int64_t>(p, d, (uint32_t)span, lds, group, c, row);
 }

@@ -143,15 +143,14 @@ bool resample_grid(uint64_t out_frames, uint32_t tile, uint64_t planes, uint32_t
     return true;
 }
 
-// What alacgpu_resample_device and alacgpu_resample_rows_device share, behind the checks of their own tables: the pointers they
-// have in common, the launch's tile, grid and LDS from lds_bytes(tile), the fields their parameter structs share by name --
-// own(p, tile, lds) sets the four that differ -- and the launch.
+// What the three resample entries share, behind the checks of their own tables or ratios: the pointers they have in common, the
+// launch's tile, grid and LDS from lds_bytes(tile), the fields their parameter structs share by name -- own(p, tile, lds) sets
+// the ones that differ -- and the launch.
 template <class P, class F, class G>
 int resample(alacgpu_ctx* ctx, const void* kernel, const F& lds_bytes, const G& own, const void* d_src, uint32_t rows, uint32_t channels,
              uint64_t src_stride, const void* d_src_origin, const void* d_src_valid, const void* d_out_first, uint64_t out_frames,
-             const void* d_d0, const void* d_weights, int mono, void* d_out, void* hip_stream) {
-    if (!ctx || !args_ok({{d_src, 4}, {d_src_origin, 8}, {d_src_valid, 8}, {d_out_first, 8}, {d_d0, 4}, {d_weights, 4}, {d_out, 4}}) ||
-        channels < 1 || channels > 2)
+             int mono, void* d_out, void* hip_stream) {
+    if (!ctx || !args_ok({{d_src, 4}, {d_src_origin, 8}, {d_src_valid, 8}, {d_out_first, 8}, {d_out, 4}}) || channels < 1 || channels > 2)
         return ALACGPU_ERR_BAD_ARG;
     if (rows == 0 || out_frames == 0) return ALACGPU_OK;
     const uint32_t tile = resample_tile(lds_bytes);
@@ -168,8 +167,6 @@ int resample(alacgpu_ctx* ctx, const void* kernel, const F& lds_bytes, const G& 
     p.out_first = (const int64_t*)d_out_first;
     p.out = (float*)d_out;
     p.out_frames = out_frames;
-    p.d0 = (const int32_t*)d_d0;
-    p.weights = (const float*)d_weights;
     p.channels = channels;
     p.mono = mono ? 1u : 0u;
     p.tile = tile;
@@ -324,16 +321,18 @@ int alacgpu_resample_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, 
                             uint32_t a, uint32_t b, uint32_t width, const void* d_d0, const void* d_weights, int mono, void* d_out,
                             void* hip_stream) {
     const uint64_t table = (uint64_t)b * (2u * (uint64_t)width + 1u);
-    if (a == 0 || b == 0 || width == 0 || table > ALAC_RESAMPLE_MAX_TABLE) return ALACGPU_ERR_BAD_ARG;
+    if (!args_ok({{d_d0, 4}, {d_weights, 4}}) || a == 0 || b == 0 || width == 0 || table > ALAC_RESAMPLE_MAX_TABLE) return ALACGPU_ERR_BAD_ARG;
     const auto lds_bytes = [&](uint64_t tile) { return sizeof(float) * (size_t)(((table + 3u) & ~3ull) + alac_resample_span(tile, a, b, width)); };
     const auto own = [&](alac_resample_params& p, uint32_t tile, size_t lds) {
+        p.d0 = (const int32_t*)d_d0;
+        p.weights = (const float*)d_weights;
         p.a = a;
         p.b = b;
         p.width = width;
         p.span = (uint32_t)alac_resample_span(tile, a, b, width);
     };
     return resample<alac_resample_params>(ctx, (const void*)alac_resample_kernel, lds_bytes, own, d_src, rows, channels, src_stride,
-                                          d_src_origin, d_src_valid, d_out_first, out_frames, d_d0, d_weights, mono, d_out, hip_stream);
+                                          d_src_origin, d_src_valid, d_out_first, out_frames, mono, d_out, hip_stream);
 }
 
 static_assert(sizeof(alacgpu_resample_table) == sizeof(alac_resample_table) && offsetof(alacgpu_resample_table, weights_first) ==
@@ -343,7 +342,7 @@ int alacgpu_resample_rows_device(alacgpu_ctx* ctx, const void* d_src, uint32_t r
                                  const void* d_src_origin, const void* d_src_valid, const void* d_out_first, uint64_t out_frames,
                                  const alacgpu_resample_table* tables, const void* d_tables, uint32_t n_tables, const void* d_d0,
                                  const void* d_weights, const void* d_row_table, int mono, void* d_out, void* hip_stream) {
-    if (!args_ok({{tables, 4}, {d_tables, 4}, {d_row_table, 4}}) || n_tables == 0) return ALACGPU_ERR_BAD_ARG;
+    if (!args_ok({{tables, 4}, {d_tables, 4}, {d_d0, 4}, {d_weights, 4}, {d_row_table, 4}}) || n_tables == 0) return ALACGPU_ERR_BAD_ARG;
     for (uint32_t t = 0; t < n_tables; t++) {
         const alacgpu_resample_table& d = tables[t];
         if (d.a == 0 || d.b == 0 || d.width == 0 || (uint64_t)d.b * (2u * (uint64_t)d.width + 1u) > ALAC_RESAMPLE_MAX_TABLE)
@@ -361,13 +360,49 @@ int alacgpu_resample_rows_device(alacgpu_ctx* ctx, const void* d_src, uint32_t r
     };
     const auto own = [&](alac_resample_rows_params& p, uint32_t tile, size_t lds) {
         p.tables = (const alac_resample_table*)d_tables;
+        p.d0 = (const int32_t*)d_d0;
+        p.weights = (const float*)d_weights;
         p.row_table = (const uint32_t*)d_row_table;
         p.n_tables = n_tables;
         p.lds_floats = (uint32_t)(lds / sizeof(float));
     };
     return resample<alac_resample_rows_params>(ctx, (const void*)alac_resample_rows_kernel, lds_bytes, own, d_src, rows, channels,
-                                               src_stride, d_src_origin, d_src_valid, d_out_first, out_frames, d_d0, d_weights, mono,
-                                               d_out, hip_stream);
+                                               src_stride, d_src_origin, d_src_valid, d_out_first, out_frames, mono, d_out, hip_stream);
+}
+
+static_assert(sizeof(alacgpu_resample_ratio) == sizeof(alac_resample_ratio) && offsetof(alacgpu_resample_ratio, width) ==
+              offsetof(alac_resample_ratio, width), "the kernel reads the header's ratios as they are");
+
+int alacgpu_resample_ratio_rows_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,
+                                       const void* d_src_origin, const void* d_src_valid, const void* d_out_first, uint64_t out_frames,
+                                       const alacgpu_resample_ratio* ratios, const void* d_ratios, uint32_t n_ratios,
+                                       const void* d_row_ratio, int mono, void* d_out, void* hip_stream) {
+    if (!args_ok({{ratios, 4}, {d_ratios, 4}, {d_row_ratio, 4}}) || n_ratios == 0) return ALACGPU_ERR_BAD_ARG;
+    bool any = false;
+    for (uint32_t t = 0; t < n_ratios; t++) {
+        const alacgpu_resample_ratio& d = ratios[t];
+        if (d.b == 0 || d.a >= (1u << 31) || d.b >= (1u << 31)) return ALACGPU_ERR_BAD_ARG;
+        // a ratio that is used: a frame's span, 2 width + 2, has to fit the LDS of a CU (a / b up to about 3378)
+        if (d.a != 0 && (d.width == 0 || d.width > ALAC_RESAMPLE_RATIO_MAX_WIDTH)) return ALACGPU_ERR_BAD_ARG;
+        any = any || d.a != 0;
+    }
+    // one tile for the launch, and the LDS of the ratio whose span of it is the longest; a workgroup uses its own ratio's span
+    const auto lds_bytes = [&](uint64_t tile) {
+        uint64_t most = 0;
+        for (uint32_t t = 0; t < n_ratios; t++)
+            if (ratios[t].a != 0) most = std::max<uint64_t>(most, alac_resample_span(tile, ratios[t].a, ratios[t].b, ratios[t].width));
+        return sizeof(float) * (size_t)most;
+    };
+    const auto own = [&](alac_resample_ratio_params& p, uint32_t tile, size_t lds) {
+        p.ratios = (const alac_resample_ratio*)d_ratios;
+        p.row_ratio = (const uint32_t*)d_row_ratio;
+        p.n_ratios = n_ratios;
+        p.lds_floats = (uint32_t)(lds / sizeof(float));
+    };
+    // (every ratio with a == 0: the shared checks still run, with no output frames nothing is launched)
+    return resample<alac_resample_ratio_params>(ctx, (const void*)alac_resample_ratio_rows_kernel, lds_bytes, own, d_src, rows, channels,
+                                                src_stride, d_src_origin, d_src_valid, d_out_first, any ? out_frames : 0u, mono, d_out,
+                                                hip_stream);
 }
 
 int alacgpu_logmel_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,

@@ -92,6 +92,15 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_resample_rows_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
             ulong srcStride, IntPtr dSrcOrigin, IntPtr dSrcValid, IntPtr dOutFirst, ulong outFrames, [In] ResampleTable[] tables,
             IntPtr dTables, uint nTables, IntPtr dD0, IntPtr dWeights, IntPtr dRowTable, int mono, IntPtr dOut, IntPtr hipStream);
+        /// <summary>One ratio of alacgpu_resample_ratio_rows_device: a : b and the filter's width; a == 0: the rows that name it
+        /// are skipped.</summary>
+        [StructLayout(LayoutKind.Sequential)] public struct ResampleRatio { public uint a, b, width; }
+        /// <summary>alacgpu_resample_device without tables: nRatios ratios (ratios on the host, dRatios the same on the device) and
+        /// dRowRatio[r] (uint) the ratio of row r; every tap's weight is evaluated where it is used.  A row whose index is nRatios
+        /// or above, or whose ratio has a == 0, is skipped: its part of dOut stays as it is.  Asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_resample_ratio_rows_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
+            ulong srcStride, IntPtr dSrcOrigin, IntPtr dSrcValid, IntPtr dOutFirst, ulong outFrames, [In] ResampleRatio[] ratios,
+            IntPtr dRatios, uint nRatios, IntPtr dRowRatio, int mono, IntPtr dOut, IntPtr hipStream);
         /// <summary>Log-mel features of float PCM in device memory (planar [rows, channels, srcStride], the first `frames` of a plane
         /// are signal): frames centred on t * hop with reflection, dWindow [nFft], the DFT against dBasis [nFft, 2 * (nFft / 2 + 1)],
         /// power, dFb [nMels, nFft / 2 + 1], and logMode 0 (none), 1 (ln) or 2 (log10) of max(., floor) into dOut

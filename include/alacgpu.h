@@ -426,6 +426,39 @@ int alacgpu_resample_rows_device(alacgpu_ctx* ctx, const void* d_src, uint32_t r
                                  void* hip_stream);
 
 /*
+ * The resampler without tables (no counterpart in the reference): a ratio per row, and every tap's weight evaluated where it is
+ * used -- what speed perturbation needs, whose ratios (44.1 kHz played at 0.9 to 16 kHz is 3969 : 1600, 52800 weights) no table
+ * in LDS holds.  Row r with the ratio a : b and width computes what alacgpu_resample_device defines,
+ *   y[j] = sum over d = -width .. width of w(d b - (j a mod b)) * x[floor(j a / b) + d],
+ *   w(n) = scale * sinc(v) * cos^2(pi v / 12) for |v| < 6, else 0,   v = 99 n / (100 max(a, b)),   scale = 0.99 min(a, b) / a,
+ * with j a mod b and floor(j a / b) in 64-bit integers.  A weight is evaluated in float32 from the integer 99 n, reduced modulo
+ * the period of the sine before anything is rounded, by a polynomial of degree 13 for each of sin(pi v) and cos(pi v / 12), one
+ * correctly rounded division and four products (alac.net_amd/speed.py states every operation, and its numpy twin restates it: no
+ * hardware approximation is used); it is within 2^-18 * scale of the weight above.  The taps are accumulated by fused
+ * multiply-adds in ascending d, as the table kernels do.
+ *   ratios, d_ratios  the n_ratios ratios twice: in host memory, where the call checks them and sizes the launch, and in device
+ *                     memory (4-byte aligned), where the kernel reads them.  They must agree; a workgroup that reads a ratio
+ *                     that does not fit the launch skips its row.  width: the filter's reach in source frames, at least
+ *                     600 a / (99 min(a, b)) for the whole filter (resample.filter_width); taps outside |v| < 6 weigh nothing
+ *   d_row_ratio[r]    uint32: the ratio of row r.  A row with d_row_ratio[r] >= n_ratios, or whose ratio has a == 0, is SKIPPED:
+ *                     its part of d_out is left as it is (rows another call has written or will write)
+ * Everything else -- d_src, d_src_origin, d_src_valid, d_out_first, d_out, mono -- is alacgpu_resample_device's; every element
+ * of a row that is not skipped is written, by one writer.  One tile serves the whole launch, chosen as above for the ratio whose
+ * span of it is the longest; the LDS holds that span only.  The largest ratio: a frame's own span, 2 width + 2 floats, has to
+ * fit 160 KiB, so width <= 20479 and a / b up to about 3378 (48 kHz at factor 1.1 to 8 kHz is 33 : 5).
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: as alacgpu_resample_device for what it shares, and n_ratios == 0, a NULL or
+ * misaligned `ratios`, d_ratios or d_row_ratio, any ratio with b == 0 or with a or b at or above 2^31, any ratio with a != 0 and
+ * width 0 or above 20479.
+ */
+typedef struct alacgpu_resample_ratio {
+    uint32_t a, b, width;
+} alacgpu_resample_ratio;
+int alacgpu_resample_ratio_rows_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,
+                                       const void* d_src_origin, const void* d_src_valid, const void* d_out_first,
+                                       uint64_t out_frames, const alacgpu_resample_ratio* ratios, const void* d_ratios,
+                                       uint32_t n_ratios, const void* d_row_ratio, int mono, void* d_out, void* hip_stream);
+
+/*
  * Log-mel features of decoded PCM (no counterpart in the reference): framing, window, DFT, power, mel projection and log in
  * one launch.  For every plane (row, channel) x[0 .. frames) and every frame t of 0 .. out_frames, out_frames =
  * 1 + frames / hop, centred on sample t * hop:

@@ -1,0 +1,126 @@
+"""What speed perturbation costs, per call and per training step --
+  call      alacgpu_resample_ratio_rows_device alone (ctx.resample_ratio_rows_device) on [64, 1, Ls] into [64, 1, 32000], Ls the
+            source frames 32000 output frames need, at 9 : 10 and 11 : 10 against alac.resample's kernel on the same rows
+            (ctx.resample_device with the ratio's table: the table kernel can do those two), and at 3969 : 1600 alone, which
+            no table kernel here can do.  HIP events around --reps back-to-back calls, the two ways alternating inside every
+            step, --steps times after --warmup: median and p10 .. p90 of the time per call.
+  step      corpus.random_crops(64, 32000, sample_rate=16000, mono=True, check=False) on 44.1 kHz files with
+            speed=SpeedPerturb() and without, alternating inside every step, torch.cuda.synchronize() in front of and behind
+            each: wall time, median and p10 .. p90.
+One JSON document, printed and written to --out.
+  python tools/bench_speed.py [--steps 200] [--warmup 20] [--out profiles/speed.json]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=16)
+    ap.add_argument("--seconds", type=float, default=30.0)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "speed.json"))
+    args = ap.parse_args()
+    import torch
+
+    import alac.net_amd as pkg
+    from alac.net_amd import synth
+    from alac.net_amd.resample import device_table, filter_width
+    from bench_corpus import make_file
+    from bench_resample import stats
+
+    synth.build()
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.current_stream(dev)
+    n_steps = args.steps + args.warmup
+    rng = np.random.default_rng(1)
+
+    # ---- the call alone --------------------------------------------------------------------------------------------------------
+    calls = []
+    B, L = 64, 32000
+    with pkg.AlacGpuContext([(4096, 16, 40, 10, 14, 2)], device=0) as ctx:
+        for a, b in ((9, 10), (11, 10), (3969, 1600)):
+            width = filter_width(a, b)
+            Ls = -(-L * a // b)
+            x = torch.from_numpy(rng.uniform(-1, 1, (B, 1, Ls)).astype(np.float32)).to(dev)
+            zeros = torch.zeros(B, dtype=torch.int64, device=dev)
+            valid = torch.full((B,), Ls, dtype=torch.int64, device=dev)
+            ratios = np.array([[a, b, width]], dtype=np.uint32)
+            d_ratios = torch.from_numpy(ratios.view(np.int32)).to(dev)
+            row_ratio = torch.zeros(B, dtype=torch.int32, device=dev)
+            out, out_t = torch.empty((B, 1, L), dtype=torch.float32, device=dev), torch.empty((B, 1, L), dtype=torch.float32, device=dev)
+            ways = {"ratio_call": lambda: ctx.resample_ratio_rows_device(x, B, 1, Ls, zeros, valid, zeros, L, ratios, d_ratios, row_ratio,
+                                                                         False, out, stream=stream.cuda_stream)}
+            table = b * (2 * width + 1) <= 16384
+            if table:
+                _, _, _, d_d0, d_w = device_table(a, b, dev)
+                ways["table_call"] = lambda: ctx.resample_device(x, B, 1, Ls, zeros, valid, zeros, L, a, b, width, d_d0, d_w, False, out_t,
+                                                                 stream=stream.cuda_stream)
+            for fn in ways.values():
+                fn()
+            torch.cuda.synchronize()
+            ms = {m: [] for m in ways}
+            for rep in range(n_steps):
+                for way, fn in ways.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record(stream)
+                    for _ in range(args.reps):
+                        fn()
+                    e1.record(stream)
+                    e1.synchronize()
+                    if rep >= args.warmup:
+                        ms[way].append(e0.elapsed_time(e1) / args.reps)
+            doc = {"ratio": [a, b], "width": width, "src_shape": [B, 1, Ls], "out_shape": [B, 1, L],
+                   "ms_per_call_events_around_reps_calls": {m: stats(v) for m, v in ms.items()}}
+            if table:
+                doc["max_abs_difference_to_table_call"] = float((out - out_t).abs().max())
+                r, t = doc["ms_per_call_events_around_reps_calls"]["ratio_call"], doc["ms_per_call_events_around_reps_calls"]["table_call"]
+                doc["ratio_call_median_over_table_call_median"] = r["median"] / t["median"]
+            calls.append(doc)
+
+    # ---- the step --------------------------------------------------------------------------------------------------------------
+    rate, R = 44100, 16000
+    T = int(args.seconds * rate)
+    distinct = [make_file(synth, T, 11 + k) for k in range(2)]
+    corpus = pkg.Corpus([distinct[f % 2] for f in range(args.files)])
+    kw = dict(sample_rate=R, mono=True, check=False)
+    sp = pkg.SpeedPerturb()
+    ways = {"speed": lambda: corpus.random_crops(B, L, speed=sp, **kw)[0], "without": lambda: corpus.random_crops(B, L, **kw)[0]}
+    wall = {m: [] for m in ways}
+    for i in range(n_steps):
+        for m, fn in ways.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            dt = (time.perf_counter() - t0) * 1e3
+            del out
+            if i >= args.warmup:
+                wall[m].append(dt)
+    corpus.close()
+    step = {"step": "random_crops(64, 32000, sample_rate=16000, mono=True, check=False) on 44.1 kHz stereo files",
+            "speed": "speed=SpeedPerturb(): 0.9 / 1.0 / 1.1, that is 3969 : 1600, 441 : 160 (the table kernel) and 4851 : 1600",
+            "wall_ms": {m: stats(v) for m, v in wall.items()}}
+    shown = [a for i, a in enumerate(sys.argv[1:], 1) if a != "--out" and sys.argv[i - 1] != "--out"]     # (where it was written says nothing)
+    doc = {"command": " ".join(["python tools/bench_speed.py"] + shown), "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
+           "calls": calls, "step": step}
+    text = json.dumps(doc, indent=1)
+    print(text, flush=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -75,6 +75,8 @@ SYMBOLS = {
                                                      C.c_uint32, _VP, C.c_int, _VP, _VP]),
     "alacgpu_logmel_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _VP,
                                         _VP, _VP, C.c_int, C.c_float, _VP, C.c_uint64, _VP]),
+    "alacgpu_fbank_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                       _VP, _VP, _VP, C.c_uint32, C.c_float, C.c_float, _VP, C.c_uint64, _VP]),
     "alacgpu_normalize_meanvar_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, C.c_int, C.c_int,
                                                    C.c_float, _VP]),
     "alacgpu_normalize_top_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
@@ -394,6 +396,18 @@ class AlacGpuContext(_Closing):
         max(., floor).  Asynchronous on `stream` (raw hipStream_t); nothing is read back."""
         rc = lib().alacgpu_logmel_device(self._ctx, _dp(d_src), rows, channels, src_stride, frames, n_fft, hop, n_mels, _dp(d_window),
                                          _dp(d_basis), _dp(d_fb), log_mode, floor, _dp(d_out), out_frames, _VP(stream))
+        _check(rc, self._ctx)
+
+    def fbank_device(self, d_src, rows, channels, src_stride, frames, win_length, n_fft, hop, n_mels, d_window, d_basis, d_fb, flags,
+                     preemphasis, scale, d_out, out_frames, stream=0):
+        """alacgpu_fbank_device: Kaldi's fbank features of d_src (float32 device tensor, planar [rows, channels, src_stride], the
+        first `frames` of a plane are signal) into d_out (float32 [rows, channels, n_mels, out_frames], out_frames as
+        fbank.KaldiFbank.frames gives it, every element written) with the tables d_window [win_length], d_basis [win_length,
+        2 * (n_fft // 2 + 1)] and d_fb [n_mels, n_fft // 2 + 1] (fbank.KaldiFbank builds them); flags: 1 snip_edges,
+        2 remove_dc_offset, 4 use_power, 8 log.  Asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_fbank_device(self._ctx, _dp(d_src), rows, channels, src_stride, frames, win_length, n_fft, hop, n_mels,
+                                        _dp(d_window), _dp(d_basis), _dp(d_fb), flags, preemphasis, scale, _dp(d_out), out_frames,
+                                        _VP(stream))
         _check(rc, self._ctx)
 
     def normalize_meanvar_device(self, d_src, d_out, rows, lines_per_row, line_stride, line_len, d_valid, centre, scale, eps, stream=0):
@@ -1019,6 +1033,8 @@ from .corpus import (Corpus, compact_plan_host, corpus_plan_host, corpus_tables,
 from .resample import resample, resample_host, resample_table, source_window  # noqa: E402
 # ---- log-mel features of crops and tensors (alacgpu_logmel_device) -----------------------------------------------------------------
 from .features import LogMel, log_mel, logmel_host, logmel_host_f32, mel_filterbank  # noqa: E402
+# ---- Kaldi filterbank features of crops and tensors (alacgpu_fbank_device) ----------------------------------------------------------
+from .fbank import KaldiFbank, fbank, fbank_host, fbank_host_f32, fbank_lengths, kaldi_mel_banks, kaldi_window  # noqa: E402
 
 # ---- normalised crops and features (alacgpu_normalize_meanvar_device, alacgpu_normalize_top_device) ------------------------------
 from .normalize import MeanVar, TopDb, normalize, normalize_host, normalize_host_f32  # noqa: E402

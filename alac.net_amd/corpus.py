@@ -20,7 +20,7 @@ states the filter) resamples every crop out of it.
 `crops(..., reverb=, mix=, features=, normalize=)` runs up to four stages behind the waveform, and `crops` is the one place
 that lists them: the refusals of all of them, the crops the second corpora make (`Corpus._companion_crops`: the noise of an
 AddNoise, then the impulse responses of a Reverb, each cropped by its own corpus at the rate of the crops), the waveform once
-(`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_logmel_device and
+(`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_logmel_device (or alacgpu_fbank_device) and
 the normalisation (reverb.py, mix.py, features.py and normalize.py state the arithmetic), each only if asked for.
 
 `crops(..., speed=)` plays every crop at a drawn factor in front of all that (`Corpus._speed_crops`, speed.py): the step of a
@@ -41,7 +41,8 @@ from . import (MAX_FRAME, ST_OK, ST_UNSUPPORTED_ELEMENT, ST_UNSUPPORTED_PREDTYPE
                _Closing, _check, _check_batch_args, _compact_slots, _dp, _encode_slots, _frame_count, _status_text, _torch_dtype,
                _VP, _write_file, lib, make_cfgs)
 from .augment import LDS_MAX as _WARP_MAX, _check_draws, _how, _spec_augment
-from .features import LogMel, feature_lengths
+from .fbank import KaldiFbank
+from .features import LogMel
 from .mix import AddNoise, _mix, snr_ratio
 from .normalize import MeanVar, TopDb, _normalize
 from .reverb import Reverb, _reverb
@@ -677,11 +678,13 @@ class Corpus(_Closing):
         lengths).  The noise and the responses are cropped by their own corpus's `crops` at the rate of the crops, as one
         channel when its channel count is not theirs, into scratches THIS corpus keeps: a second corpus may be this one.
 
-        features: a features.LogMel -- the crops' log-mel features instead of their PCM: the waveform goes into a float32
-        scratch the corpus keeps and ONE alacgpu_logmel_device call turns every row, the zeros behind its length included,
-        into features.  Returns (feats float32 [B, 1 if mono else C, n_mels, 1 + num_frames // hop], feat_lengths [B] int64
-        on the device: lengths // hop + 1, -1 where lengths is -1); `out` is then the features tensor.  ValueError: a
-        spec.sample_rate that is not the rate of the crops, a dtype other than float32, num_frames <= n_fft // 2.
+        features: a features.LogMel or a fbank.KaldiFbank -- the crops' log-mel or Kaldi fbank features instead of their PCM:
+        the waveform goes into a float32 scratch the corpus keeps and ONE alacgpu_logmel_device or alacgpu_fbank_device call
+        turns every row, the zeros behind its length included, into features.  Returns (feats float32 [B, 1 if mono else C,
+        n_mels, features.frames(num_frames)], feat_lengths [B] int64 on the device: features.lengths(lengths) -- lengths // hop
+        + 1 for a LogMel, fbank.fbank_lengths for a KaldiFbank --, -1 where lengths is -1); `out` is then the features tensor.
+        ValueError: a spec.sample_rate that is not the rate of the crops, a dtype other than float32, num_frames below
+        features.min_frames (n_fft // 2 + 1 for a LogMel; what gives no frame for a KaldiFbank).
 
         normalize: a normalize.MeanVar -- every line over its valid elements: lengths for PCM, feat_lengths for features, so a
         crop outside the corpus is zeros -- or a normalize.TopDb -- every crop of features, or every channel of it with
@@ -714,8 +717,9 @@ class Corpus(_Closing):
             if features is None and not is_f32():
                 raise ValueError("a MeanVar normalises float32 crops")
         if features is not None:
-            if not isinstance(features, LogMel):
-                raise ValueError(f"features must be a features.LogMel, not {features!r} (sample_rate= and mono= go by keyword)")
+            if not isinstance(features, (LogMel, KaldiFbank)):
+                raise ValueError(f"features must be a features.LogMel or a fbank.KaldiFbank, not {features!r} (sample_rate= and mono= "
+                                 f"go by keyword)")
             if rate is None:
                 raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
             if features.sample_rate != rate:
@@ -728,8 +732,8 @@ class Corpus(_Closing):
                 raise ValueError("a SpecAugment masks log-mel features: it needs features=")
         if features is not None or mix is not None or reverb is not None or speed is not None:
             L = _frame_count("num_frames", num_frames)
-            if features is not None and L <= features.n_fft // 2:
-                raise ValueError(f"num_frames {L}: the transform needs more than n_fft // 2 = {features.n_fft // 2}")
+            if features is not None and L < features.min_frames:
+                raise ValueError(features.short(L))
             self._open()
             B = int(files.shape[0]) if isinstance(files, torch.Tensor) and files.dim() == 1 else len(np.asarray(files))
         if speed is not None and speed[1] is not None and speed[1].shape[0] != B:
@@ -763,11 +767,8 @@ class Corpus(_Closing):
             _mix(ctx, res, d_noise, lambda: snr_ratio(snr, B, self._dev), lengths, noise_lengths, res)
         if features is not None:
             if B:
-                window, basis, fb = features.device_tables(self._dev)
-                self._gpu.logmel_device(res, B, Co, L, L, features.n_fft, features.hop_length, features.n_mels, window, basis, fb,
-                                        features.log_mode, features.floor, feats, feats.shape[3],
-                                        stream=torch.cuda.current_stream(self._dev).cuda_stream)
-            res, lengths = feats, feature_lengths(lengths, features.hop_length)
+                features.launch(self._gpu, res, B, Co, L, L, feats, torch.cuda.current_stream(self._dev).cuda_stream)
+            res, lengths = feats, features.lengths(lengths)
         if normalize is not None:
             _normalize(ctx, res, normalize, lengths, res)
         if augment is not None:
@@ -1169,8 +1170,8 @@ class Corpus(_Closing):
             mix = (mix[0], mix[0].draw(B, L, sample_rate=rate, generator=generator))
         if reverb is not None and reverb[1] is None:
             reverb = (reverb[0], reverb[0].draw(B, generator=generator))
-        if augment is not None and augment[1] is None and isinstance(features, LogMel):
-            feat_lengths = feature_lengths((ends - offs).clamp(max=L), features.hop_length)
+        if augment is not None and augment[1] is None and isinstance(features, (LogMel, KaldiFbank)):
+            feat_lengths = features.lengths((ends - offs).clamp(max=L))
             augment = (augment[0], augment[0].draw(features.n_mels, feat_lengths, generator=generator))
         pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,
                                   features=features, normalize=normalize, mix=mix, reverb=reverb, augment=augment, speed=speed)

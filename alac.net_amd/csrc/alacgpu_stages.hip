@@ -1,5 +1,5 @@
 // alacgpu_stages.hip -- C ABI of include/alacgpu.h, the stages around the decode: the crop planner, the scan with the packet
-// compaction and staging, the resamplers, log-mel, the reverberation, the noise mix, the normalisations, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
+// compaction and staging, the resamplers, log-mel, Kaldi fbank, the reverberation, the noise mix, the normalisations, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
 // their own scratch; the decode path is alacgpu_api.hip.  No CPU fallback here either: every stage is its kernels.
 #include <algorithm>
 #include <cmath>
@@ -8,6 +8,7 @@
 #include "alac_corpus.h"
 #include "alac_resample.h"
 #include "alac_features.h"
+#include "alac_fbank.h"
 #include "alac_normalize.h"
 #include "alac_augment.h"
 #include "alac_mix.h"
@@ -443,6 +444,52 @@ int alacgpu_logmel_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, ui
     p.floor = floor;
     void* kargs[] = {&p};
     HIP_TRY(ctx, hipLaunchKernel((const void*)alac_logmel_kernel, dim3((uint32_t)(tiles * channels * rows)), dim3(ALAC_FEATURES_THREADS),
+                                 kargs, lds, (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
+}
+
+int alacgpu_fbank_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride, uint64_t frames,
+                         uint32_t win_length, uint32_t n_fft, uint32_t hop, uint32_t n_mels, const void* d_window, const void* d_basis,
+                         const void* d_fb, uint32_t flags, float preemphasis, float scale, void* d_out, uint64_t out_frames,
+                         void* hip_stream) {
+    if (!ctx || !args_ok({{d_src, 4}, {d_window, 4}, {d_basis, 4}, {d_fb, 4}, {d_out, 4}})) return ALACGPU_ERR_BAD_ARG;
+    if (win_length < ALAC_FBANK_MIN_WIN || win_length > ALAC_FBANK_MAX_WIN || n_fft < win_length || n_fft > ALAC_FBANK_MAX_NFFT ||
+        hop < 1 || hop > win_length || n_mels < 1 || n_mels > ALAC_FEATURES_MAX_MELS || channels == 0 || (flags & ~(uint32_t)ALAC_FBANK_FLAGS))
+        return ALACGPU_ERR_BAD_ARG;
+    if (!(preemphasis >= 0.0f && preemphasis <= 1.0f) || !std::isfinite(scale) || scale == 0.0f) return ALACGPU_ERR_BAD_ARG;
+    if (frames < 1 || frames > src_stride || frames > (1ull << 61) ||
+        out_frames != alac_fbank_frames(frames, win_length, hop, (flags & ALAC_FBANK_SNIP_EDGES) != 0u))
+        return ALACGPU_ERR_BAD_ARG;
+    const uint32_t tile = alac_features_tile(win_length, hop);
+    const uint64_t tiles = (out_frames + tile - 1u) / tile;
+    if (tiles > 0x7FFFFFFFull || tiles * channels > 0x7FFFFFFFull || tiles * channels * rows > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    const size_t lds = alac_fbank_lds_layout(win_length, n_fft, hop, n_mels).bytes();
+    if (lds > ALAC_FEATURES_LDS_MAX) return ALACGPU_ERR_BAD_ARG;    // (the limits above keep every layout below it)
+    if (rows == 0 || out_frames == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (lds > ALAC_FEATURES_LDS_DEFAULT)
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)alac_fbank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    alac_fbank_params p;
+    p.src = (const float*)d_src;
+    p.src_stride = src_stride;
+    p.frames = frames;
+    p.out = (float*)d_out;
+    p.out_frames = out_frames;
+    p.window = (const float*)d_window;
+    p.basis = (const float*)d_basis;
+    p.fb = (const float*)d_fb;
+    p.win = win_length;
+    p.n_fft = n_fft;
+    p.hop = hop;
+    p.n_mels = n_mels;
+    p.tile = tile;
+    p.tiles = (uint32_t)tiles;
+    p.flags = flags;
+    p.preemphasis = preemphasis;
+    p.scale = scale;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_fbank_kernel, dim3((uint32_t)(tiles * channels * rows)), dim3(ALAC_FEATURES_THREADS),
                                  kargs, lds, (hipStream_t)hip_stream));
     HIP_TRY(ctx, hipGetLastError());
     return ALACGPU_OK;

@@ -194,6 +194,28 @@ class LogMel:
             self._device[index] = tuple(torch.from_numpy(np.array(a)).to(dev) for a in (self.window, self.basis, self.fb))
         return self._device[index]
 
+    # what `Corpus.crops` needs of a transform (fbank.KaldiFbank has the same four): the shortest row, what refuses a shorter
+    # one, the device lengths and the launch
+    @property
+    def min_frames(self):
+        """The shortest row the transform takes: n_fft // 2 + 1"""
+        return self.n_fft // 2 + 1
+
+    def short(self, L):
+        """What refuses a row of L < min_frames samples"""
+        return f"num_frames {L}: the transform needs more than n_fft // 2 = {self.n_fft // 2}"
+
+    def lengths(self, lengths):
+        """`feature_lengths(lengths, hop_length)`"""
+        return feature_lengths(lengths, self.hop_length)
+
+    def launch(self, gpu, src, rows, channels, src_stride, L, out, stream):
+        """The features of src (float32 device tensor, planar [rows, channels, src_stride], the first L of a plane are signal)
+        into out [rows, channels, n_mels, frames(L)] by the AlacGpuContext `gpu`: one alacgpu_logmel_device call on `stream`"""
+        window, basis, fb = self.device_tables(src.device)
+        gpu.logmel_device(src, rows, channels, src_stride, L, self.n_fft, self.hop_length, self.n_mels, window, basis, fb,
+                          self.log_mode, self.floor, out, self.frames(L), stream=stream)
+
 
 def frame_index(L, n_fft, hop):
     """(idx int64 [T', n_fft], inside bool [T', n_fft]): where frame t's tap n reads x, after the reflection; `inside` is False

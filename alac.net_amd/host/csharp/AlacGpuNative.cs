@@ -108,6 +108,14 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_logmel_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
             ulong srcStride, ulong frames, uint nFft, uint hop, uint nMels, IntPtr dWindow, IntPtr dBasis, IntPtr dFb, int logMode,
             float floor, IntPtr dOut, ulong outFrames, IntPtr hipStream);
+        /// <summary>Kaldi's fbank features of float PCM in device memory (planar [rows, channels, srcStride], the first `frames` of a
+        /// plane are signal): frames of winLength samples every hop (flags: 1 snip_edges, else centred with Kaldi's reflection), the
+        /// frame's mean removed (2), pre-emphasis, dWindow [winLength], the nFft-point DFT against dBasis [winLength,
+        /// 2 * (nFft / 2 + 1)], power (4, else magnitude), dFb [nMels, nFft / 2 + 1] and ln(max(., 2^-23)) (8) into dOut
+        /// [rows, channels, nMels, outFrames].  Asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_fbank_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
+            ulong srcStride, ulong frames, uint winLength, uint nFft, uint hop, uint nMels, IntPtr dWindow, IntPtr dBasis, IntPtr dFb,
+            uint flags, float preemphasis, float scale, IntPtr dOut, ulong outFrames, IntPtr hipStream);
         /// <summary>Mean and variance per line of float data in device memory ([rows, linesPerRow, lineStride], the first lineLen of
         /// a line are data) over the first min(max(dValid[row], 0), lineLen) elements (dValid: long[rows] or IntPtr.Zero for whole
         /// lines): (x - mean) / sqrt(var + eps), zeros behind them, into dOut (dSrc itself or the same layout).  Asynchronous on

@@ -490,6 +490,44 @@ int alacgpu_logmel_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, ui
                           uint64_t out_frames, void* hip_stream);
 
 /*
+ * Kaldi filterbank features of decoded PCM (no counterpart in the reference): what Kaldi's compute-fbank-feats computes, in one
+ * launch.  For every plane (row, channel) x[0 .. frames) and every frame t of 0 .. out_frames, with N = win_length and
+ * n_bins = n_fft / 2 + 1:
+ *   flags & 1 (snip_edges)   out_frames = 0 for frames < N, else 1 + (frames - N) / hop; frame t starts at g0 = t * hop
+ *   otherwise                out_frames = (frames + hop / 2) / hop; g0 = t * hop + hop / 2 - N / 2, and an index g outside
+ *                            0 .. frames is reflected as Kaldi does: m = g mod 2 frames (floored), then m if m < frames, else
+ *                            2 frames - 1 - m
+ *   s[n]     = scale * x[g0 + n],  n < N
+ *   d[n]     = s[n] - (sum of s) / N                       (flags & 2, remove_dc_offset; else d = s)
+ *   y[n]     = d[n] - preemphasis * d[n - 1], d[-1] = d[0]  (preemphasis != 0; else y = d)
+ *   X[j]     = sum over n of (d_window[n] * y[n]) * d_basis[n * 2 * n_bins + j],   j < 2 * n_bins
+ *   P[k]     = X[k]^2 + X[n_bins + k]^2                     (flags & 4, use_power; else its square root)
+ *   M[m]     = sum over k of d_fb[m * n_bins + k] * P[k]
+ *   out[m,t] = ln(max(M[m], 2^-23)) (flags & 8, log) or M[m]
+ * in float32, every operation rounded once: the sum of a frame as eight partial sums (partial j over the taps j, j + 8 ... in
+ * ascending order) added as ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)), the division and the root correctly rounded, y one
+ * fused multiply-add, then fused multiply-adds in ascending n and k (the DFT on the exact-f32 matrix instruction).  The three
+ * tables are the caller's (alac.net_amd/fbank.py builds Kaldi's: the Povey window and its kin, the cosines and negated sines
+ * of the n_fft-point transform for the N taps that are not padding, mel banks linear on the mel axis), so any window, basis or
+ * filterbank of those shapes is honoured.  Device pointers only, asynchronous on hip_stream, nothing is read back; nothing of
+ * the ctx is used but its device.
+ *   d_src     float32, planar [rows, channels, src_stride]; only the first `frames` elements of a plane are signal and only
+ *             they are read
+ *   d_window  float32 [N];  d_basis  float32 [N, 2 * n_bins];  d_fb  float32 [n_mels, n_bins]
+ *   d_out     float32 [rows, channels, n_mels, out_frames]; every element is written, each by one thread
+ * A workgroup takes 32 consecutive frames of one plane (fewer where 31 * hop + N is above 19456 samples) and holds their span of
+ * signal in LDS.  rows == 0 or out_frames == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx or array, a misaligned array (4), win_length outside 16 .. 2048,
+ * n_fft outside win_length .. 2048, hop outside 1 .. win_length, n_mels outside 1 .. 256, flags above 15, a preemphasis outside
+ * 0 .. 1, a scale that is zero or not finite, channels 0, frames 0 or above src_stride, out_frames other than the count above,
+ * 2^31 workgroups or more.
+ */
+int alacgpu_fbank_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,
+                         uint64_t frames, uint32_t win_length, uint32_t n_fft, uint32_t hop, uint32_t n_mels,
+                         const void* d_window, const void* d_basis, const void* d_fb, uint32_t flags, float preemphasis,
+                         float scale, void* d_out, uint64_t out_frames, void* hip_stream);
+
+/*
  * The two normalisations between crops or their features and a model (no counterpart in the reference).  The data of both is
  * float32 [rows, lines_per_row, line_stride]: the first line_len <= line_stride elements of a line are data, what lies behind
  * them is neither read nor written.  Features [B, C, n_mels, Tf] are rows = B, lines_per_row = C * n_mels; a waveform

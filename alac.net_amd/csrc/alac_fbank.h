@@ -1,5 +1,5 @@
 // alac_fbank.h -- the launch parameters of the fused Kaldi fbank kernel (alac_fbank.hip), shared with the C ABI
-// (alacgpu_stages.hip).  The tile, block, round and skew constants are the log-mel kernel's (alac_features.h).
+// (alacgpu_stages.hip).  The shared launch fields, the LDS layout, the constants and the tile body are alac_features.h's.
 #pragma once
 #include "alac_features.h"
 
@@ -17,38 +17,9 @@ __host__ __device__ inline uint64_t alac_fbank_frames(uint64_t frames, uint32_t 
     return (frames + hop / 2u) / hop;
 }
 
-// LDS: the window, the mel sums, the power of a round of bin blocks, the means of the tile's frames, the skewed span -- the
-// log-mel kernel's layout with a window of win taps, the bins of n_fft and the means
-struct alac_fbank_lds {
-    uint32_t window, mel, power, mean, span;   // floats of each part, in this order
-    __host__ __device__ size_t bytes() const { return sizeof(float) * ((size_t)window + mel + power + mean + span); }
-};
+constexpr uint32_t ALAC_FBANK_LDS_EXTRA = ALAC_FEATURES_TILE;  // the kernel's own part of alac_features_lds_layout: the means of the tile's frames
 
-__host__ __device__ inline alac_fbank_lds alac_fbank_lds_layout(uint32_t win, uint32_t n_fft, uint32_t hop, uint32_t n_mels) {
-    const uint32_t n_bins = n_fft / 2u + 1u;
-    const uint32_t blocks = (n_bins + ALAC_FEATURES_BLOCK - 1u) / ALAC_FEATURES_BLOCK;
-    const uint32_t span = (alac_features_tile(win, hop) - 1u) * hop + win;
-    alac_fbank_lds l;
-    l.window = (win + 3u) & ~3u;
-    l.mel = n_mels * ALAC_FEATURES_TILE;
-    l.power = (blocks < ALAC_FEATURES_ROUND_BLOCKS ? blocks : ALAC_FEATURES_ROUND_BLOCKS) * ALAC_FEATURES_BLOCK * ALAC_FEATURES_TILE;
-    l.mean = ALAC_FEATURES_TILE;
-    l.span = span + alac_features_skew(hop) * ((span - 1u) / hop + 1u);
-    return l;
-}
-
-struct alac_fbank_params {
-    const float* src;             // [planes, src_stride]
-    uint64_t src_stride;
-    uint64_t frames;              // the samples of a plane that are signal: L >= 1
-    float* out;                   // [planes, n_mels, out_frames]
-    uint64_t out_frames;          // alac_fbank_frames(frames, win, hop, snip_edges) >= 1
-    const float* window;          // [win]
-    const float* basis;           // [win, 2 * n_bins]
-    const float* fb;              // [n_mels, n_bins]
-    uint32_t win, n_fft, hop, n_mels;
-    uint32_t tile;                // alac_features_tile(win, hop)
-    uint32_t tiles;               // ceil(out_frames / tile): blockIdx.x = plane * tiles + tile index
+struct alac_fbank_params : alac_stft_mel_params {   // taps: win; frames: L >= 1; out_frames: alac_fbank_frames(...) >= 1
     uint32_t flags;               // ALAC_FBANK_*
     float preemphasis, scale;
 };

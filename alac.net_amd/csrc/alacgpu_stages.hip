@@ -203,6 +203,42 @@ bool apart(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
     return (uintptr_t)a + a_bytes <= (uintptr_t)b || (uintptr_t)b + b_bytes <= (uintptr_t)a;
 }
 
+// What alacgpu_logmel_device and alacgpu_fbank_device do behind their own argument checks: the grid of tiles, the LDS layout
+// (with `extra` floats of the kernel's own), the shared fields of p and the launch of `kernel`, whose argument p is
+template <typename Params>
+int launch_stft_mel(alacgpu_ctx* ctx, const void* kernel, Params& p, uint32_t extra, const void* d_src, uint32_t rows,
+                           uint32_t channels, uint64_t src_stride, uint64_t frames, uint32_t taps, uint32_t n_fft, uint32_t hop,
+                           uint32_t n_mels, const void* d_window, const void* d_basis, const void* d_fb, void* d_out,
+                           uint64_t out_frames, void* hip_stream) {
+    const uint32_t tile = alac_features_tile(taps, hop);
+    const uint64_t tiles = (out_frames + tile - 1u) / tile;
+    if (tiles > 0x7FFFFFFFull || tiles * channels > 0x7FFFFFFFull || tiles * channels * rows > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    const size_t lds = alac_features_lds_layout(taps, n_fft, hop, n_mels, extra).bytes();
+    if (lds > ALAC_FEATURES_LDS_MAX) return ALACGPU_ERR_BAD_ARG;    // (the callers' limits keep every layout below it)
+    if (rows == 0 || out_frames == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (lds > ALAC_FEATURES_LDS_DEFAULT) HIP_TRY(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    p.src = (const float*)d_src;
+    p.src_stride = src_stride;
+    p.frames = frames;
+    p.out = (float*)d_out;
+    p.out_frames = out_frames;
+    p.window = (const float*)d_window;
+    p.basis = (const float*)d_basis;
+    p.fb = (const float*)d_fb;
+    p.taps = taps;
+    p.n_fft = n_fft;
+    p.hop = hop;
+    p.n_mels = n_mels;
+    p.tile = tile;
+    p.tiles = (uint32_t)tiles;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel(kernel, dim3((uint32_t)(tiles * channels * rows)), dim3(ALAC_FEATURES_THREADS), kargs, lds,
+                                 (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -417,36 +453,11 @@ int alacgpu_logmel_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, ui
     if (!(floor > 0.0f) || !std::isfinite(floor)) return ALACGPU_ERR_BAD_ARG;
     if (log_mode != ALAC_FEATURES_LOG_NONE && log_mode != ALAC_FEATURES_LOG_LN && log_mode != ALAC_FEATURES_LOG_10) return ALACGPU_ERR_BAD_ARG;
     if (frames <= n_fft / 2u || frames > src_stride || frames > (1ull << 62) || out_frames != 1u + frames / hop) return ALACGPU_ERR_BAD_ARG;
-    const uint32_t tile = alac_features_tile(n_fft, hop);
-    const uint64_t tiles = (out_frames + tile - 1u) / tile;
-    if (tiles > 0x7FFFFFFFull || tiles * channels > 0x7FFFFFFFull || tiles * channels * rows > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
-    if (rows == 0) return ALACGPU_OK;
-    const size_t lds = alac_features_lds_layout(n_fft, hop, n_mels).bytes();
-    if (lds > ALAC_FEATURES_LDS_MAX) return ALACGPU_ERR_BAD_ARG;    // (the limits above keep every layout below it)
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (lds > ALAC_FEATURES_LDS_DEFAULT)
-        HIP_TRY(ctx, hipFuncSetAttribute((const void*)alac_logmel_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     alac_features_params p;
-    p.src = (const float*)d_src;
-    p.src_stride = src_stride;
-    p.frames = frames;
-    p.out = (float*)d_out;
-    p.out_frames = out_frames;
-    p.window = (const float*)d_window;
-    p.basis = (const float*)d_basis;
-    p.fb = (const float*)d_fb;
-    p.n_fft = n_fft;
-    p.hop = hop;
-    p.n_mels = n_mels;
-    p.tile = tile;
-    p.tiles = (uint32_t)tiles;
     p.log_mode = (uint32_t)log_mode;
     p.floor = floor;
-    void* kargs[] = {&p};
-    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_logmel_kernel, dim3((uint32_t)(tiles * channels * rows)), dim3(ALAC_FEATURES_THREADS),
-                                 kargs, lds, (hipStream_t)hip_stream));
-    HIP_TRY(ctx, hipGetLastError());
-    return ALACGPU_OK;
+    return launch_stft_mel(ctx, (const void*)alac_logmel_kernel, p, 0u, d_src, rows, channels, src_stride, frames, n_fft, n_fft, hop,
+                           n_mels, d_window, d_basis, d_fb, d_out, out_frames, hip_stream);
 }
 
 int alacgpu_fbank_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride, uint64_t frames,
@@ -461,38 +472,12 @@ int alacgpu_fbank_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uin
     if (frames < 1 || frames > src_stride || frames > (1ull << 61) ||
         out_frames != alac_fbank_frames(frames, win_length, hop, (flags & ALAC_FBANK_SNIP_EDGES) != 0u))
         return ALACGPU_ERR_BAD_ARG;
-    const uint32_t tile = alac_features_tile(win_length, hop);
-    const uint64_t tiles = (out_frames + tile - 1u) / tile;
-    if (tiles > 0x7FFFFFFFull || tiles * channels > 0x7FFFFFFFull || tiles * channels * rows > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
-    const size_t lds = alac_fbank_lds_layout(win_length, n_fft, hop, n_mels).bytes();
-    if (lds > ALAC_FEATURES_LDS_MAX) return ALACGPU_ERR_BAD_ARG;    // (the limits above keep every layout below it)
-    if (rows == 0 || out_frames == 0) return ALACGPU_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (lds > ALAC_FEATURES_LDS_DEFAULT)
-        HIP_TRY(ctx, hipFuncSetAttribute((const void*)alac_fbank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     alac_fbank_params p;
-    p.src = (const float*)d_src;
-    p.src_stride = src_stride;
-    p.frames = frames;
-    p.out = (float*)d_out;
-    p.out_frames = out_frames;
-    p.window = (const float*)d_window;
-    p.basis = (const float*)d_basis;
-    p.fb = (const float*)d_fb;
-    p.win = win_length;
-    p.n_fft = n_fft;
-    p.hop = hop;
-    p.n_mels = n_mels;
-    p.tile = tile;
-    p.tiles = (uint32_t)tiles;
     p.flags = flags;
     p.preemphasis = preemphasis;
     p.scale = scale;
-    void* kargs[] = {&p};
-    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_fbank_kernel, dim3((uint32_t)(tiles * channels * rows)), dim3(ALAC_FEATURES_THREADS),
-                                 kargs, lds, (hipStream_t)hip_stream));
-    HIP_TRY(ctx, hipGetLastError());
-    return ALACGPU_OK;
+    return launch_stft_mel(ctx, (const void*)alac_fbank_kernel, p, ALAC_FBANK_LDS_EXTRA, d_src, rows, channels, src_stride, frames,
+                           win_length, n_fft, hop, n_mels, d_window, d_basis, d_fb, d_out, out_frames, hip_stream);
 }
 
 int alacgpu_normalize_meanvar_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t lines_per_row,

@@ -70,7 +70,7 @@ device tensors.
 import numpy as np
 
 from ._stageargs import _f32_finite
-from .features import _int
+from .features import _chain, _int, _on_device, _Transform, dft_basis  # noqa: F401 (_chain: the twin's, once)
 
 MIN_WIN, MAX_WIN, MAX_NFFT, MAX_MELS = 16, 2048, 2048, 256
 FLOOR = 2.0 ** -23                                              # FLT_EPSILON
@@ -136,11 +136,8 @@ def kaldi_mel_banks(sample_rate, n_fft, n_mels, low_freq=20.0, high_freq=0.0):
 
 
 def fbank_basis(win_length, n_fft):
-    """float32 [win_length, 2 * n_bins]: cos and -sin of 2 pi ((n k) mod n_fft) / n_fft for n < win_length"""
-    n_bins = n_fft // 2 + 1
-    nk = (np.arange(win_length, dtype=np.int64)[:, None] * np.arange(n_bins, dtype=np.int64)[None, :]) % n_fft
-    ang = 2.0 * np.pi * (nk.astype(np.float64) / n_fft)
-    return np.concatenate([np.cos(ang), -np.sin(ang)], axis=1).astype(np.float32)
+    """`features.dft_basis` with win_length rows: float32 [win_length, 2 * n_bins]"""
+    return dft_basis(n_fft, win_length)
 
 
 def _flag(name, v):
@@ -149,7 +146,7 @@ def _flag(name, v):
     return bool(v)
 
 
-class KaldiFbank:
+class KaldiFbank(_Transform):
     """An immutable description of Kaldi's fbank transform (see the module) together with its three float32 tables: `window`
     [win_length], `basis` [win_length, 2 * n_bins] and `fb` [n_mels, n_bins] (read-only arrays).  Lengths are in samples:
     Kaldi's frame_length 25 ms and frame_shift 10 ms at 16 kHz are win_length 400 and hop_length 160.  The features are
@@ -158,13 +155,11 @@ class KaldiFbank:
     zero in float32, a window of `WINDOWS`."""
 
     __slots__ = ("sample_rate", "win_length", "hop_length", "n_mels", "n_fft", "n_bins", "low_freq", "high_freq", "preemphasis",
-                 "remove_dc_offset", "window_type", "round_to_power_of_two", "snip_edges", "use_power", "log", "scale", "window",
-                 "basis", "fb", "_device")
+                 "remove_dc_offset", "window_type", "round_to_power_of_two", "snip_edges", "use_power", "log", "scale")
 
     def __init__(self, sample_rate, win_length=400, hop_length=160, n_mels=80, low_freq=20.0, high_freq=0.0, preemphasis=0.97,
                  remove_dc_offset=True, window="povey", round_to_power_of_two=True, snip_edges=True, use_power=True, log=True,
                  scale=32768.0):
-        s = object.__setattr__
         sample_rate = _int("sample_rate", sample_rate, 1)
         win_length = _int("win_length", win_length, MIN_WIN, MAX_WIN)
         hop_length = _int("hop_length", hop_length, 1, win_length)
@@ -183,20 +178,10 @@ class KaldiFbank:
         scale = float(np.float32(_f32_finite("scale", scale)))
         if scale == 0.0:
             raise ValueError("scale must not be zero in float32")
-        tables = {"window": kaldi_window(window, win_length), "basis": fbank_basis(win_length, n_fft),
-                  "fb": kaldi_mel_banks(sample_rate, n_fft, n_mels, low_freq, high_freq)}
-        for a in tables.values():
-            a.flags.writeable = False
-        for name, v in dict(sample_rate=sample_rate, win_length=win_length, hop_length=hop_length, n_mels=n_mels, n_fft=n_fft,
-                            n_bins=n_fft // 2 + 1, low_freq=low_freq, high_freq=high_freq, preemphasis=preemphasis,
-                            window_type=window, scale=scale, _device={}, **flags, **tables).items():
-            s(self, name, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError("a KaldiFbank is immutable")
-
-    def __delattr__(self, name):
-        raise AttributeError("a KaldiFbank is immutable")
+        self._freeze(kaldi_window(window, win_length), fbank_basis(win_length, n_fft),
+                     kaldi_mel_banks(sample_rate, n_fft, n_mels, low_freq, high_freq), sample_rate=sample_rate,
+                     win_length=win_length, hop_length=hop_length, n_mels=n_mels, n_fft=n_fft, n_bins=n_fft // 2 + 1,
+                     low_freq=low_freq, high_freq=high_freq, preemphasis=preemphasis, window_type=window, scale=scale, **flags)
 
     def __repr__(self):
         return (f"KaldiFbank(sample_rate={self.sample_rate}, win_length={self.win_length}, hop_length={self.hop_length}, "
@@ -229,16 +214,6 @@ class KaldiFbank:
     def lengths(self, lengths):
         """`fbank_lengths(lengths, self)`"""
         return fbank_lengths(lengths, self)
-
-    def device_tables(self, device):
-        """(window, basis, fb) on the device (a torch.device), uploaded once per device"""
-        import torch
-
-        index = device.index if device.index is not None else torch.cuda.current_device()
-        if index not in self._device:
-            dev = torch.device("cuda", index)
-            self._device[index] = tuple(torch.from_numpy(np.array(a)).to(dev) for a in (self.window, self.basis, self.fb))
-        return self._device[index]
 
     def launch(self, gpu, src, rows, channels, src_stride, L, out, stream):
         """The features of src (float32 device tensor, planar [rows, channels, src_stride], the first L of a plane are signal)
@@ -320,22 +295,6 @@ def fbank_host(x, spec, bound=False):
     return (out, dM.reshape(out.shape)) if bound else out
 
 
-def _chain(a, b):
-    """a [T, K] float32, b [K, N] float64 holding float32 values: fma(a[:, k], b[k], acc) for k = 0 .. K - 1, from zero (an
-    fma of float32 values as the exact float64 product plus the float64 addend, rounded to float64 and then to float32: twice
-    where the hardware rounds once, which differs in the last bit of rare elements only)"""
-    a = np.ascontiguousarray(a.T, dtype=np.float64)                 # [K, T]
-    acc = np.zeros((a.shape[1], b.shape[1]), dtype=np.float32)
-    wide = np.zeros(acc.shape, dtype=np.float64)
-    tmp = np.empty_like(wide)
-    for k in range(a.shape[0]):
-        np.multiply(a[k][:, None], b[k][None, :], out=tmp)
-        tmp += wide
-        acc[...] = tmp                                               # the rounding to float32
-        wide[...] = acc
-    return acc
-
-
 def fbank_host_f32(x, spec):
     """The kernel's arithmetic in numpy, one float32 operation at a time in the order the module states: x float32 [..., L] to
     float32 [..., n_mels, T'] (with spec.log the log is numpy's float32 one, not the device's logf).  Its distance from
@@ -410,24 +369,6 @@ def fbank(pcm, spec, lengths=None):
     T >= 1, to float32 [..., spec.n_mels, spec.frames(T)]; one kernel, asynchronous on the current stream.  Every row is
     transformed over its whole T.  A T that gives no frame gives an empty tensor and no launch.  lengths (a sequence or an
     integer tensor): returns (features, `fbank_lengths` of them as an int64 tensor where `lengths` was)."""
-    import torch
-
-    from ._stageargs import _device_context
-
-    if not isinstance(spec, KaldiFbank):
-        raise ValueError("spec must be a KaldiFbank")
-    ctx = _device_context("pcm", pcm, "[..., T]")
-    if pcm.dtype != torch.float32 or pcm.dim() < 1 or pcm.shape[-1] < 1:
-        raise ValueError("pcm must be a float32 device tensor [..., T], T >= 1")
-    T = pcm.shape[-1]
-    dev = pcm.device
-    planes = int(np.prod(pcm.shape[:-1], dtype=np.int64))
-    Tf = spec.frames(T)
-    out = torch.empty(tuple(pcm.shape[:-1]) + (spec.n_mels, Tf), dtype=torch.float32, device=dev)
-    if planes and Tf:
-        with torch.cuda.device(dev):
-            spec.launch(ctx(), pcm.contiguous(), planes, 1, T, T, out, torch.cuda.current_stream(dev).cuda_stream)
-    if lengths is None:
-        return out
-    lens = lengths if isinstance(lengths, torch.Tensor) else torch.as_tensor(np.asarray(lengths, dtype=np.int64))
-    return out, fbank_lengths(lens, spec)
+    takes = "[..., T], T >= 1"
+    short = lambda T: f"pcm must be a float32 device tensor {takes}" if T < 1 else None
+    return _on_device(pcm, spec, KaldiFbank, takes, short, lengths)

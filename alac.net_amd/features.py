@@ -119,27 +119,58 @@ def hann_window(n_fft):
     return (0.5 - 0.5 * np.cos(2.0 * np.pi * n / n_fft)).astype(np.float32)
 
 
-def dft_basis(n_fft):
-    """float32 [n_fft, 2 * n_bins]: cos and -sin of 2 pi ((n k) mod n_fft) / n_fft"""
+def dft_basis(n_fft, rows=None):
+    """float32 [rows, 2 * n_bins], rows = n_fft unless given (fbank's window is shorter than its n_fft: the zeros that pad a
+    frame have no rows): cos and -sin of 2 pi ((n k) mod n_fft) / n_fft"""
     n_bins = n_fft // 2 + 1
-    nk = (np.arange(n_fft, dtype=np.int64)[:, None] * np.arange(n_bins, dtype=np.int64)[None, :]) % n_fft
+    rows = n_fft if rows is None else rows
+    nk = (np.arange(rows, dtype=np.int64)[:, None] * np.arange(n_bins, dtype=np.int64)[None, :]) % n_fft
     ang = 2.0 * np.pi * (nk.astype(np.float64) / n_fft)
     return np.concatenate([np.cos(ang), -np.sin(ang)], axis=1).astype(np.float32)
 
 
-class LogMel:
+class _Transform:
+    """What `LogMel` and `fbank.KaldiFbank` share: three read-only float32 tables (window, basis, fb) beside their own fields,
+    immutability, and the tables on a device.  What `Corpus.crops` and `_on_device` need of a transform is the subclass's:
+    `frames`, `min_frames`, `short`, `lengths` and `launch`."""
+
+    __slots__ = ("window", "basis", "fb", "_device")
+
+    def _freeze(self, window, basis, fb, **fields):
+        """The end of a subclass's __init__: the tables made read-only, and they and the fields assigned"""
+        for a in (window, basis, fb):
+            a.flags.writeable = False
+        for name, v in dict(fields, window=window, basis=basis, fb=fb, _device={}).items():
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError(f"a {type(self).__name__} is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError(f"a {type(self).__name__} is immutable")
+
+    def device_tables(self, device):
+        """(window, basis, fb) on the device (a torch.device), uploaded once per device"""
+        import torch
+
+        index = device.index if device.index is not None else torch.cuda.current_device()
+        if index not in self._device:
+            dev = torch.device("cuda", index)
+            self._device[index] = tuple(torch.from_numpy(np.array(a)).to(dev) for a in (self.window, self.basis, self.fb))
+        return self._device[index]
+
+
+class LogMel(_Transform):
     """An immutable description of a log-mel transform together with its three float32 tables: `window` [n_fft], `basis`
     [n_fft, 2 * n_bins] and `fb` [n_mels, n_bins] (read-only arrays).  filterbank: the caller's own [n_mels, n_bins] array
     instead of `mel_filterbank` (n_mels is then its row count; f_min, f_max, scale and norm describe nothing).  log: "ln",
     "log10", or None for mel power (floor is then ignored).  ValueError unless 16 <= n_fft <= 2048, 1 <= hop_length <= n_fft,
     1 <= n_mels <= 256, floor > 0 and finite, 0 <= f_min < f_max <= sample_rate / 2."""
 
-    __slots__ = ("sample_rate", "n_fft", "hop_length", "n_mels", "n_bins", "f_min", "f_max", "scale", "norm", "log", "floor",
-                 "window", "basis", "fb", "_device")
+    __slots__ = ("sample_rate", "n_fft", "hop_length", "n_mels", "n_bins", "f_min", "f_max", "scale", "norm", "log", "floor")
 
     def __init__(self, sample_rate, n_fft=400, hop_length=160, n_mels=80, f_min=0.0, f_max=None, scale="slaney", norm="slaney",
                  log="ln", floor=1e-10, filterbank=None):
-        s = object.__setattr__
         sample_rate = _int("sample_rate", sample_rate, 1)
         n_fft = _int("n_fft", n_fft, MIN_NFFT, MAX_NFFT)
         hop_length = _int("hop_length", hop_length, 1, n_fft)
@@ -158,18 +189,8 @@ class LogMel:
             if fb.ndim != 2 or fb.shape[1] != n_bins or not 1 <= fb.shape[0] <= MAX_MELS:
                 raise ValueError(f"filterbank must be [1 .. {MAX_MELS}, {n_bins}], not {fb.shape}")
             n_mels = fb.shape[0]
-        tables = {"window": hann_window(n_fft), "basis": dft_basis(n_fft), "fb": fb}
-        for a in tables.values():
-            a.flags.writeable = False
-        for name, v in dict(sample_rate=sample_rate, n_fft=n_fft, hop_length=hop_length, n_mels=n_mels, n_bins=n_bins, f_min=f_min,
-                            f_max=f_max, scale=scale, norm=norm, log=log, floor=floor, _device={}, **tables).items():
-            s(self, name, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError("a LogMel is immutable")
-
-    def __delattr__(self, name):
-        raise AttributeError("a LogMel is immutable")
+        self._freeze(hann_window(n_fft), dft_basis(n_fft), fb, sample_rate=sample_rate, n_fft=n_fft, hop_length=hop_length,
+                     n_mels=n_mels, n_bins=n_bins, f_min=f_min, f_max=f_max, scale=scale, norm=norm, log=log, floor=floor)
 
     def __repr__(self):
         return (f"LogMel(sample_rate={self.sample_rate}, n_fft={self.n_fft}, hop_length={self.hop_length}, n_mels={self.n_mels}, "
@@ -183,16 +204,6 @@ class LogMel:
     def frames(self, L):
         """T' = 1 + L // hop_length (numpy arrays too)"""
         return 1 + L // self.hop_length
-
-    def device_tables(self, device):
-        """(window, basis, fb) on the device (a torch.device), uploaded once per device"""
-        import torch
-
-        index = device.index if device.index is not None else torch.cuda.current_device()
-        if index not in self._device:
-            dev = torch.device("cuda", index)
-            self._device[index] = tuple(torch.from_numpy(np.array(a)).to(dev) for a in (self.window, self.basis, self.fb))
-        return self._device[index]
 
     # what `Corpus.crops` needs of a transform (fbank.KaldiFbank has the same four): the shortest row, what refuses a shorter
     # one, the device lengths and the launch
@@ -265,6 +276,22 @@ def logmel_host(x, spec, bound=False):
     return (out, dM.reshape(out.shape)) if bound else out
 
 
+def _chain(a, b):
+    """a [T, K] float32, b [K, N] float64 holding float32 values: fma(a[:, k], b[k], acc) for k = 0 .. K - 1, from zero (an
+    fma of float32 values as the exact float64 product plus the float64 addend, rounded to float64 and then to float32: twice
+    where the hardware rounds once, which differs in the last bit of rare elements only)"""
+    a = np.ascontiguousarray(a.T, dtype=np.float64)                 # [K, T]
+    acc = np.zeros((a.shape[1], b.shape[1]), dtype=np.float32)
+    wide = np.zeros(acc.shape, dtype=np.float64)
+    tmp = np.empty_like(wide)
+    for k in range(a.shape[0]):
+        np.multiply(a[k][:, None], b[k][None, :], out=tmp)
+        tmp += wide
+        acc[...] = tmp                                               # the rounding to float32
+        wide[...] = acc
+    return acc
+
+
 def logmel_host_f32(x, spec):
     """The kernel's arithmetic in numpy, one float32 operation at a time: x float32 [..., L] to float32 [..., n_mels, T'], the
     mel power (spec.log and spec.floor are not applied).  The window product is rounded once; X[j] is a chain of fused
@@ -288,24 +315,12 @@ def logmel_host_f32(x, spec):
     rows = x.reshape(-1, L)
     out = np.empty((rows.shape[0], spec.n_mels, T), dtype=f32)
 
-    def chain(a, b):
-        """a [T, K] float32, b [K, N] float64 holding float32 values: fma(a[:, k], b[k], acc) for k = 0 .. K - 1, from zero"""
-        a = np.ascontiguousarray(a.T, dtype=f64)                                           # [K, T]
-        acc, wide = np.zeros((a.shape[1], b.shape[1]), dtype=f32), np.zeros((a.shape[1], b.shape[1]), dtype=f64)
-        tmp = np.empty_like(wide)
-        for k in range(a.shape[0]):
-            np.multiply(a[k][:, None], b[k][None, :], out=tmp)
-            tmp += wide
-            acc[...] = tmp                                                                 # the rounding to float32
-            wide[...] = acc
-        return acc
-
     for r, row in enumerate(rows):
         fr = (np.where(inside, row[idx], f32(0)) * spec.window[None, :]).astype(f32)       # [T, n_fft]
-        X = chain(fr, basis)
+        X = _chain(fr, basis)
         re, im = X[:, :n_bins].astype(f64), X[:, n_bins:].astype(f64)
         P = (re * re + (im * im).astype(f32).astype(f64)).astype(f32)
-        out[r] = chain(P, np.ascontiguousarray(fb.T)).T
+        out[r] = _chain(P, np.ascontiguousarray(fb.T)).T
     return out.reshape(x.shape[:-1] + (spec.n_mels, T))
 
 
@@ -317,36 +332,45 @@ def feature_lengths(lengths, hop):
     return torch.where(lengths >= 0, torch.div(lengths, hop, rounding_mode="floor") + 1, torch.full_like(lengths, -1))
 
 
+def _on_device(pcm, spec, kind, takes, short, lengths):
+    """`log_mel` and `fbank.fbank` behind their names: spec is a `kind`, pcm a float32 device tensor whose shape the messages
+    call `takes` and for whose T `short(T)` is None (the ValueError's text otherwise); the output, one `spec.launch` over all
+    planes unless there is nothing to compute, and `spec.lengths` of the lengths"""
+    import torch
+
+    from ._stageargs import _device_context
+
+    if not isinstance(spec, kind):
+        raise ValueError(f"spec must be a {kind.__name__}")
+    ctx = _device_context("pcm", pcm, "[..., T]")
+    if pcm.dtype != torch.float32 or pcm.dim() < 1:
+        raise ValueError(f"pcm must be a float32 device tensor {takes}")
+    T = pcm.shape[-1]
+    if short(T) is not None:
+        raise ValueError(short(T))
+    dev = pcm.device
+    planes = int(np.prod(pcm.shape[:-1], dtype=np.int64))
+    Tf = spec.frames(T)
+    out = torch.empty(tuple(pcm.shape[:-1]) + (spec.n_mels, Tf), dtype=torch.float32, device=dev)
+    if planes and Tf:
+        with torch.cuda.device(dev):
+            spec.launch(ctx(), pcm.contiguous(), planes, 1, T, T, out, torch.cuda.current_stream(dev).cuda_stream)
+    if lengths is None:
+        return out
+    lens = lengths if isinstance(lengths, torch.Tensor) else torch.as_tensor(np.asarray(lengths, dtype=np.int64))
+    if lens.dtype.is_floating_point:
+        raise ValueError("lengths must be integers")
+    return out, spec.lengths(lens.to(torch.int64))
+
+
 def log_mel(pcm, spec, lengths=None):
     """Log-mel features on the GPU: pcm float32 [..., T] on the device (as `load`, `load_batch` and `crops` return it),
     T > n_fft // 2, to float32 [..., spec.n_mels, 1 + T // hop]; one kernel, asynchronous on the current stream.  Every row is
     transformed over its whole T (what lies behind a file's or a crop's length is the zeros the decode wrote).  lengths
     (a sequence or an integer tensor): returns (features, lengths // hop + 1 as an int64 tensor where `lengths` was; an
     entry of -1 stays -1)."""
-    import torch
+    def short(T):
+        if T <= spec.n_fft // 2:
+            return f"T = {T} frames: the transform needs more than n_fft // 2 = {spec.n_fft // 2}"
 
-    from ._stageargs import _device_context
-
-    if not isinstance(spec, LogMel):
-        raise ValueError("spec must be a LogMel")
-    ctx = _device_context("pcm", pcm, "[..., T]")
-    if pcm.dtype != torch.float32 or pcm.dim() < 1:
-        raise ValueError("pcm must be a float32 device tensor [..., T]")
-    T = pcm.shape[-1]
-    if T <= spec.n_fft // 2:
-        raise ValueError(f"T = {T} frames: the transform needs more than n_fft // 2 = {spec.n_fft // 2}")
-    dev = pcm.device
-    planes = int(np.prod(pcm.shape[:-1], dtype=np.int64))
-    Tf = spec.frames(T)
-    out = torch.empty(tuple(pcm.shape[:-1]) + (spec.n_mels, Tf), dtype=torch.float32, device=dev)
-    if planes:
-        window, basis, fb = spec.device_tables(dev)
-        with torch.cuda.device(dev):
-            ctx().logmel_device(pcm.contiguous(), planes, 1, T, T, spec.n_fft, spec.hop_length, spec.n_mels, window, basis, fb,
-                                spec.log_mode, spec.floor, out, Tf, stream=torch.cuda.current_stream(dev).cuda_stream)
-    if lengths is None:
-        return out
-    lens = lengths if isinstance(lengths, torch.Tensor) else torch.as_tensor(np.asarray(lengths, dtype=np.int64))
-    if lens.dtype.is_floating_point:
-        raise ValueError("lengths must be integers")
-    return out, feature_lengths(lens.to(torch.int64), spec.hop_length)
+    return _on_device(pcm, spec, LogMel, "[..., T]", short, lengths)

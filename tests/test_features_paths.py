@@ -6,8 +6,8 @@ and the number of tiles, not on the length of the audio."""
 import numpy as np
 import pytest
 
-from test_features import (U, check_log_any, check_power, gpu, header_constant, kernel_tile, noise, run_kernel,  # noqa: F401
-                           specs)
+from test_features import (GUARD, U, check_log_any, check_power, gpu, header_constant, kernel_tile, noise,  # noqa: F401
+                           run_kernel, specs)
 from test_features_spec import GRID
 
 pytestmark = pytest.mark.gpu
@@ -178,3 +178,53 @@ def test_what_is_not_finite_stays_in_its_frames_and_is_never_hidden(gpu):
             assert np.isnan(got[row, 0][:, hit]).all(), (log, row)
             assert np.array_equal(bits(got[row, 0][:, ~hit]), bits(want[row, 0][:, ~hit])), (log, row)
         assert np.array_equal(bits(got[1]), bits(want[1])) and np.array_equal(bits(got[3]), bits(want[3])), log
+
+
+@pytest.mark.parametrize("n,hop", [(64, 16), (400, 100), (50, 5), (16, 1)])
+def test_the_fbank_entry_is_the_logmel_entry_on_the_same_tables(gpu, n, hop):
+    """alacgpu_fbank_device with win_length = n_fft = n, snip_edges, use_power, no mean, no pre-emphasis and scale 1 on LogMel's
+    three tables against alacgpu_logmel_device without a log: fbank's frame t begins at sample t hop, log-mel's frame
+    t + n / (2 hop) does too and reflects nothing, so they are bit for bit equal -- 1 * x and x - 0 are exact, the B operand is
+    the same single product, the chains run in the same order, and a frame's arithmetic does not depend on its place in a tile
+    (the two calls put it at different ones).  (64, 16): an even hop, a skewed span, three tiles; (400, 100): the speech
+    window, seven bin blocks in one round; (50, 5): an odd hop without skew, and K = 50 leaves one whole k-step to the remainder
+    loop; (16, 1): the hop-1 start of (q, r)."""
+    torch, pkg, ctx = gpu
+    from alac.net_amd.fbank import FLAG_SNIP_EDGES, FLAG_USE_POWER
+    from alac.net_amd.features import LogMel
+
+    dev = torch.device("cuda", 0)
+    sp = LogMel(16000, n, hop, n_mels=8, log=None)
+    shift, frames, slack = n // (2 * hop), 71, 37
+    L = n + (frames - 1) * hop
+    assert shift * 2 * hop == n and sp.frames(L) >= frames + shift
+    x = noise(np.random.default_rng(n + hop), 1, 1, L)
+    src = np.full((1, 1, L + slack), np.nan, dtype=np.float32)
+    src[:, :, :L] = x
+    d_src = torch.from_numpy(src).to(dev)
+    window, basis, fb = sp.device_tables(dev)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def guarded(count):
+        raw = torch.full(((count + 2 * GUARD) * 4,), 0x5A, dtype=torch.uint8, device=dev).view(torch.float32)
+        raw[GUARD:GUARD + count].fill_(float("nan"))
+        return raw
+
+    def result(raw, count, T):
+        torch.cuda.synchronize()
+        host = raw.cpu().numpy()
+        edge = np.full(GUARD * 4, 0x5A, dtype=np.uint8)
+        assert np.array_equal(host[:GUARD].view(np.uint8), edge) and np.array_equal(host[GUARD + count:].view(np.uint8), edge)
+        return host[GUARD:GUARD + count].reshape(sp.n_mels, T)
+
+    Tl = sp.frames(L)
+    raw = guarded(sp.n_mels * Tl)
+    ctx.logmel_device(d_src, 1, 1, L + slack, L, n, hop, sp.n_mels, window, basis, fb, 0, sp.floor, raw[GUARD:GUARD + sp.n_mels * Tl], Tl,
+                      stream=stream)
+    logmel = result(raw, sp.n_mels * Tl, Tl)
+    raw = guarded(sp.n_mels * frames)
+    ctx.fbank_device(d_src, 1, 1, L + slack, L, n, n, hop, sp.n_mels, window, basis, fb, FLAG_SNIP_EDGES | FLAG_USE_POWER, 0.0, 1.0,
+                     raw[GUARD:GUARD + sp.n_mels * frames], frames, stream=stream)
+    fbank = result(raw, sp.n_mels * frames, frames)
+    assert np.isfinite(fbank).all() and (fbank > 0).any()
+    assert np.array_equal(fbank.view(np.uint32), np.ascontiguousarray(logmel[:, shift:shift + frames]).view(np.uint32)), (n, hop)

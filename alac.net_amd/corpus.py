@@ -13,7 +13,7 @@ writes their offsets), one small read.  `Corpus.save` writes any corpus back as 
 memory.  A step is then three calls: between the plan and the decode, alacgpu_stage_packets_device gathers the plan's packets
 from both tiers into a small staging blob in HBM, and the decode reads that.
 
-`crops(..., sample_rate=R, mono=)` gives the crops at another rate and as one channel (`Corpus._rate_crops`): the source
+`crops(..., sample_rate=R, mono=)` gives the crops at another rate and as one channel (`Corpus._resampled_crops`): the source
 frames a crop needs are decoded as above into a scratch the corpus keeps, and one alacgpu_resample_device call (resample.py
 states the filter) resamples every crop out of it.
 
@@ -23,9 +23,9 @@ AddNoise, then the impulse responses of a Reverb, each cropped by its own corpus
 (`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_logmel_device (or alacgpu_fbank_device) and
 the normalisation (reverb.py, mix.py, features.py and normalize.py state the arithmetic), each only if asked for.
 
-`crops(..., speed=)` plays every crop at a drawn factor in front of all that (`Corpus._speed_crops`, speed.py): the step of a
-corpus whose rates differ, with a ratio per (file rate, factor) in place of one per file rate; the crops at factor 1 go through
-the table kernels, the others through alacgpu_resample_ratio_rows_device, which evaluates its weights per tap.
+`crops(..., speed=)` plays every crop at a drawn factor in front of all that (the same method, speed.py): the step of a corpus
+whose rates differ, with a ratio per (file rate, factor) in place of one per file rate; the crops at factor 1 go through the
+table kernels, the others through alacgpu_resample_ratio_rows_device, which evaluates its weights per tap.
 
 `Corpus(sources, mixed_rates=True)` takes files of different sample rates.  Crops of such a corpus exist at a target rate only;
 a step is the same method and the same launches, with a source window per crop in the plan
@@ -50,6 +50,7 @@ from .speed import MAX_WIDTH as _SPEED_MAX_WIDTH, SpeedPerturb, ratio as _speed_
 
 PAD_CFG = 0xFFFF        # a padding entry's cfg_idx: never a row of the context, so the kernels switch the entry off
 MAX_CFGS = 65535
+_NEEDS_RATE = "the files of this corpus differ in sample rate: crops need sample_rate="
 # crops(mix=) and crops(reverb=) for `Corpus._second_corpus`: the specification's class, its attribute that holds the second
 # corpus, how many tensors its draw() returns and what their dtypes have to be, and the nouns of the messages
 _MIX = dict(arg="mix", spec=AddNoise, corpus="noise", theirs="the noise corpus", they="the noise",
@@ -57,11 +58,17 @@ _MIX = dict(arg="mix", spec=AddNoise, corpus="noise", theirs="the noise corpus",
             draws=3, dtypes=lambda torch, files, offsets, snr_db: snr_db.is_floating_point,
             tensors="the three tensors (noise_files, noise_offsets, snr_db) of AddNoise.draw", f32="noise is mixed into float32 crops",
             channels="a noise corpus of {n} channels into crops of {Co}: it can become one channel from 1 or 2 only")
+_SPEED = dict(arg="speed", spec=SpeedPerturb, what="speed must be a speed.SpeedPerturb or (SpeedPerturb, what its draw() returned)",
+              f32="float32 crops are speed-perturbed")
 _REVERB = dict(arg="reverb", spec=Reverb, corpus="rirs", theirs="the corpus of impulse responses", they="the responses",
                what="reverb must be a reverb.Reverb or (Reverb, what its draw() returned)",
                draws=2, dtypes=lambda torch, files, keep: not files.is_floating_point and keep == torch.bool,
                tensors="the two tensors (rir_files, keep) of Reverb.draw", f32="float32 crops are reverberated",
                channels="impulse responses of {n} channels into crops of {Co}: they can become one channel from 1 or 2 only")
+
+
+def _is_f32(torch, dtype):
+    return _torch_dtype(torch, torch.float32 if dtype is None else dtype) == torch.float32
 
 
 def corpus_tables(tables, mixed_rates=False):
@@ -288,7 +295,7 @@ class Corpus(_Closing):
 
     mixed_rates=True: the files may differ in sample rate (not in channel count).  sample_rates (int64 host array [F]) has
     every file's; sample_rate is the one they share, or None when they differ.  num_frames stays in source frames.  Crops of
-    a corpus whose rates differ exist at a target rate only: crops / random_crops want sample_rate=R (`_rate_crops`), and
+    a corpus whose rates differ exist at a target rate only: crops / random_crops want sample_rate=R (`_resampled_crops`), and
     every file is resampled by its own ratio in the same launches.  Files that happen to share one rate make the corpus
     Corpus(sources) is, call for call."""
 
@@ -377,7 +384,7 @@ class Corpus(_Closing):
         self._ft_scratch = None                           # crops(features=): the crops the feature kernel reads
         self._mix_scratch = None                          # crops(mix=): the noise crops, whichever corpus makes them
         self._reverb_scratch = None                       # crops(reverb=): the impulse responses of the crops
-        self._rates, self._windows = {}, {}               # `_rate` per target rate; `_window` per (target rate or None, L)
+        self._rates, self._windows = {}, {}               # `_rate` per (target rate, factors); `_window` per (rate or None, L, factors)
         self._gpu = gpu if gpu is not None else AlacGpuContext(tb["cfgs"], device)
 
     @classmethod
@@ -560,36 +567,30 @@ class Corpus(_Closing):
         return self._window(None, int(num_frames))
 
     def _window(self, R, L, speed=None):
-        """Per (target rate, crop length, speed), once: Ls, the source frames a crop's window takes -- L itself for R None, the native
-        window; else resample.source_window's bound, an int, or where the rates differ int64 [F] with file f's by its own
-        ratio, and then d_Ls as well, the same as an int32 device tensor --, Ls_max, the largest, and K and S, where a file
-        counts with its own Ls.  S only where there is a host tier, else None: the packet sizes of a corpus from PCM would
-        have to come from the device for it.  speed (a SpeedPerturb; R is then a rate): a file counts with the largest
-        window over the factors, and d_Ls is int32 [rates * factors], the window of every (file rate, factor)."""
+        """Per (target rate, crop length, factors), once: Ls, the source frames a crop's window takes -- L itself for R None,
+        the native window; else resample.source_window's bound by `_rate(R, speed)`: an int, or for its per-crop variant
+        int64 [F], a file's largest window over the factors (speed: a SpeedPerturb; None: the one factor 1), and then d_Ls as
+        well, int32 [kinds] on the device, the window of every kind --, Ls_max, the largest, and K and S, where a file counts
+        with its own Ls.  S only where there is a host tier, else None: the packet sizes of a corpus from PCM would have to
+        come from the device for it."""
         import torch
 
-        if (R, L, speed) not in self._windows:
-            Ls = L
-            if speed is not None:
-                st = self._speed_rate(R, speed)
-                each = ((max(L, 1) - 1) // st["b"] + 2) * st["a"] + 2 * st["width"]            # [rates, factors]
-                Ls = each.max(axis=1)[st["rate_of"]]
-                if int(np.max(Ls)) >= 1 << 32:
-                    raise ValueError(f"num_frames {L} needs {int(np.max(Ls))} source frames: that does not fit 32 bits")
-            elif R is not None:
-                rt = self._rate(R)
-                Ls = ((max(L, 1) - 1) // rt["b"] + 2) * rt["a"] + 2 * rt["width"]
+        key = (R, L, None if speed is None else speed.factors)
+        if key not in self._windows:
+            Ls = each = L
+            if R is not None:
+                rt = self._rate(R, speed)
+                each = ((max(L, 1) - 1) // rt["b"] + 2) * rt["a"] + 2 * rt["width"]
+                Ls = each.reshape(-1, rt["nk"]).max(axis=1)[rt["rate_of"]] if np.ndim(each) else each
                 if int(np.max(Ls)) >= 1 << 32:
                     raise ValueError(f"num_frames {L} needs {int(np.max(Ls))} source frames: that does not fit 32 bits")
             h = self._host
             win = dict(Ls=Ls, Ls_max=int(np.max(Ls)), K=max(entries_per_crop(h["pkt_end"], h["file_first"], Ls), 1),
                        S=stage_bytes_per_crop(self._host_table("pkt_size"), h["pkt_end"], h["file_first"], Ls) if self._hi_bytes else None)
-            if speed is not None:
-                win["d_Ls"] = torch.from_numpy(each.reshape(-1).astype(np.uint32).view(np.int32)).to(self._dev)
-            elif np.ndim(Ls):
-                win["d_Ls"] = torch.from_numpy(Ls.astype(np.uint32).view(np.int32)).to(self._dev)
-            self._windows[R, L, speed] = win
-        return self._windows[R, L, speed]
+            if np.ndim(each):
+                win["d_Ls"] = torch.from_numpy(each.astype(np.uint32).view(np.int32)).to(self._dev)
+            self._windows[key] = win
+        return self._windows[key]
 
     def _plan_arrays(self, n):
         """The six plan arrays and the status array, kept and reused while n does not grow past them."""
@@ -650,15 +651,15 @@ class Corpus(_Closing):
         the first crop with a negative length.  check=False reads nothing back and returns behind the enqueue: see
         last_status().
 
-        sample_rate / mono: crops at another rate and as one channel (`_rate_crops`): frame_offsets and num_frames then
+        sample_rate / mono: crops at another rate and as one channel (`_resampled_crops`): frame_offsets and num_frames then
         count frames at sample_rate, pcm is float32 [B, 1 if mono else C, num_frames].  The defaults -- and the corpus's own
         rate, and mono of one channel -- are the path above.  A corpus whose files differ in rate (mixed_rates=True) has no
-        rate of its own: sample_rate is required (ValueError without), and every crop comes through `_rate_crops`.
+        rate of its own: sample_rate is required (ValueError without), and every crop comes through it.
 
         speed: speed perturbation of the waveform, in front of everything else: a speed.SpeedPerturb, whose draws are then made
         here from the device's default generator, or the pair (SpeedPerturb, draws) with the int64 tensor [B] that its
         `draw(B)` returned.  Crop b is then frames frame_offsets[b] .. + num_frames of its file PLAYED AT ITS FACTOR and
-        resampled as a whole to the rate of the crops (`_speed_crops`); a crop that draws factor 1 is bit for bit the crop of
+        resampled as a whole to the rate of the crops (`_resampled_crops`); a crop that draws factor 1 is bit for bit the crop of
         the call without speed=.  Every stage behind it sees the perturbed waveform.  ValueError: int32 crops, a corpus of
         more than 2 channels, draws that are not an integer tensor [B] on the corpus's device.
 
@@ -699,10 +700,9 @@ class Corpus(_Closing):
         more than 16384 feature frames."""
         import torch
 
-        # 1. every refusal that needs no device work: mix, reverb, normalize, features, augment; the waveform's own are `_waveform`'s
+        # 1. every refusal that needs no device work: speed, mix, reverb, normalize, features, augment; the waveform's own are `_waveform`'s
         rate = self.sample_rate if sample_rate is None else sample_rate
         Co = 1 if mono else self.channels
-        is_f32 = lambda: _torch_dtype(torch, torch.float32 if dtype is None else dtype) == torch.float32
         if speed is not None:
             speed = self._speed_given(speed, dtype, rate)
         if mix is not None:
@@ -714,17 +714,17 @@ class Corpus(_Closing):
                 raise ValueError(f"normalize must be a normalize.MeanVar or a normalize.TopDb, not {normalize!r}")
             if features is None and isinstance(normalize, TopDb):
                 raise ValueError("a TopDb clamps log-mel features: it needs features=")
-            if features is None and not is_f32():
+            if features is None and not _is_f32(torch, dtype):
                 raise ValueError("a MeanVar normalises float32 crops")
         if features is not None:
             if not isinstance(features, (LogMel, KaldiFbank)):
                 raise ValueError(f"features must be a features.LogMel or a fbank.KaldiFbank, not {features!r} (sample_rate= and mono= "
                                  f"go by keyword)")
             if rate is None:
-                raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
+                raise ValueError(_NEEDS_RATE)
             if features.sample_rate != rate:
                 raise ValueError(f"features for {features.sample_rate} Hz, crops at {rate} Hz")
-            if not is_f32():
+            if not _is_f32(torch, dtype):
                 raise ValueError("features are computed from float32 crops")
         if augment is not None:
             augment = _how(augment, "augment")
@@ -776,18 +776,16 @@ class Corpus(_Closing):
         return res, lengths
 
     def _waveform(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, speed=None):
-        """The crops themselves, what `crops` returns without a stage: through `_speed_crops` with speed=; through
-        `_rate_crops` at another rate, as one channel of two, or of a corpus whose rates differ; else planned and decoded here"""
+        """The crops themselves, what `crops` returns without a stage: through `_resampled_crops` with speed=, at another
+        rate, as one channel of two, or of a corpus whose rates differ; else planned and decoded here"""
         import torch
 
         if self.sample_rate is None and sample_rate is None:
-            raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
-        if speed is not None:
-            return self._speed_crops(files, frame_offsets, num_frames, out=out, check=check, sample_rate=sample_rate, mono=mono,
-                                     speed=speed)
-        if self.sample_rate is None or (mono and self.channels == 2) or (sample_rate is not None and sample_rate != self.sample_rate):
-            return self._rate_crops(files, frame_offsets, num_frames, dtype=dtype, out=out, check=check, sample_rate=sample_rate,
-                                    mono=mono)
+            raise ValueError(_NEEDS_RATE)
+        if (speed is not None or self.sample_rate is None or (mono and self.channels == 2)
+                or (sample_rate is not None and sample_rate != self.sample_rate)):
+            return self._resampled_crops(files, frame_offsets, num_frames, dtype=dtype, out=out, check=check, sample_rate=sample_rate,
+                                         mono=mono, speed=speed)
         dtype = _torch_dtype(torch, torch.float32 if dtype is None else dtype)
         L = _frame_count("num_frames", num_frames)
         if L >= 1 << 32:
@@ -813,15 +811,22 @@ class Corpus(_Closing):
             self._check_last(lengths, d_files, d_offs, L, K)
         return out, lengths
 
+    @staticmethod
+    def _pair(given, stage):
+        """The front of `_second_corpus` and `_speed_given`: crops(mix= / reverb= / speed=) as the pair (its specification, draws
+        or None); ValueError for anything else"""
+        spec, draws = given if isinstance(given, tuple) and len(given) == 2 else (given, None)
+        if not isinstance(spec, stage["spec"]):
+            raise ValueError(f"{stage['what']}, not {given!r}")
+        return spec, draws
+
     def _second_corpus(self, given, stage, dtype, rate, Co):
         """crops(mix=) or crops(reverb=) (`stage`: _MIX or _REVERB) as the pair (its specification, draws or None), checked:
         ValueError for anything else, for int32 crops, for a second corpus that is closed, on another device or of a channel
         count that crops of Co channels cannot take, and for crops without a rate.  Nothing is done on the device."""
         import torch
 
-        spec, draws = given if isinstance(given, tuple) and len(given) == 2 else (given, None)
-        if not isinstance(spec, stage["spec"]):
-            raise ValueError(f"{stage['what']}, not {given!r}")
+        spec, draws = self._pair(given, stage)
         if draws is not None:
             ok = isinstance(draws, tuple) and len(draws) == stage["draws"] and all(isinstance(t, torch.Tensor) and t.dim() == 1
                                                                                    for t in draws)
@@ -829,7 +834,7 @@ class Corpus(_Closing):
                 raise ValueError(f"the draws of {stage['arg']}= must be {stage['tensors']}")
             if any(t.device != self._dev for t in draws):
                 raise ValueError(f"the draws of {stage['arg']}= must be on {self._dev}")
-        if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
+        if not _is_f32(torch, dtype):
             raise ValueError(stage["f32"])
         other = getattr(spec, stage["corpus"])
         if other._gpu is None:
@@ -837,7 +842,7 @@ class Corpus(_Closing):
         if other._dev != self._dev:
             raise ValueError(f"{stage['theirs']} is on {other._dev}, the crops on {self._dev}")
         if rate is None:
-            raise ValueError(f"the files of this corpus differ in sample rate: crops need sample_rate=, and {stage['they']} a rate to crop at")
+            raise ValueError(f"{_NEEDS_RATE}, and {stage['they']} a rate to crop at")
         if other.channels != Co and other.channels not in (1, 2):
             raise ValueError(stage["channels"].format(n=other.channels, Co=Co))
         return spec, draws
@@ -845,18 +850,16 @@ class Corpus(_Closing):
     def _speed_given(self, given, dtype, rate):
         """crops(speed=) as the pair (SpeedPerturb, draws or None), checked: ValueError for anything else, for int32 crops,
         for a corpus of more than 2 channels and for crops without a rate.  Nothing is done on the device; the draws' length
-        is `_speed_crops`'s to check, where B is known."""
+        is `_resampled_crops`'s to check, where B is known."""
         import torch
 
-        spec, draws = given if isinstance(given, tuple) and len(given) == 2 else (given, None)
-        if not isinstance(spec, SpeedPerturb):
-            raise ValueError(f"speed must be a speed.SpeedPerturb or (SpeedPerturb, what its draw() returned), not {given!r}")
-        if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
-            raise ValueError("float32 crops are speed-perturbed")
+        spec, draws = self._pair(given, _SPEED)
+        if not _is_f32(torch, dtype):
+            raise ValueError(_SPEED["f32"])
         if self.channels not in (1, 2):
             raise ValueError(f"{self.channels} channels: the resampler takes 1 or 2")
         if rate is None:
-            raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
+            raise ValueError(_NEEDS_RATE)
         if draws is not None and (not isinstance(draws, torch.Tensor) or draws.dim() != 1 or draws.dtype.is_floating_point
                                   or draws.dtype == torch.bool or draws.device != self._dev):
             raise ValueError(f"the draws of speed= must be the integer tensor [B] of SpeedPerturb.draw on {self._dev}")
@@ -893,15 +896,24 @@ class Corpus(_Closing):
             setattr(self, name, torch.empty(n, dtype=torch.float32, device=self._dev))
         return getattr(self, name)[:n].view(shape)
 
-    def _inside(self, d_files, d_offs, d_totals):
+    @staticmethod
+    def _at(files, draws, nk):
+        """Where (file, drawn factor) is in a flat table [F * nk] of `_rate`: the file itself without draws"""
+        return files if draws is None else files * nk + draws.long().clamp(0, nk - 1)
+
+    def _inside(self, d_files, d_offs, d_totals, draws=None, nk=1):
         """Which crops are inside the corpus, on the device: (ok [B] bool -- a file index in 0 .. F - 1 and an offset in 0 ..
-        d_totals[file] --, the file indices clamped into 0 .. F - 1 as int64, d_totals gathered with them)"""
+        its total --, `at`: where the crop's total is in d_totals, int64, from the file index clamped into 0 .. F - 1, and
+        the totals gathered with it).  draws (int tensor [B]): d_totals is [F * nk], a file's total at each of nk factors;
+        a crop's draw has to be in 0 .. nk - 1 as well, and `at` is file * nk + the draw, clamped."""
         f64 = d_files.long()
         ok = (f64 >= 0) & (f64 < self.num_files)
-        fc = f64.clamp(0, self.num_files - 1)
-        totals = d_totals[fc]
+        if draws is not None:
+            ok &= (draws >= 0) & (draws < nk)
+        at = self._at(f64.clamp(0, self.num_files - 1), draws, nk)
+        totals = d_totals[at]
         ok &= (d_offs >= 0) & (d_offs <= totals)
-        return ok, fc, totals
+        return ok, at, totals
 
     def _plan_and_decode(self, d_files, d_offs, L, K, S, out, d_frames=None):
         """The launches of a step: the plan of the crops (d_files, d_offs) of L frames with K entries each, the staging of its
@@ -941,81 +953,122 @@ class Corpus(_Closing):
     def resampled_frames(self, sample_rate, speed=None):
         """Ty_f: the frames of every file at sample_rate, ceil(b * T_f / a) with the file's own reduced ratio a : b (int64 host
         array [F]).  speed (a SpeedPerturb): int64 [F, len(speed.factors)], the file played at every factor."""
-        if speed is not None:
-            if not isinstance(speed, SpeedPerturb):
-                raise ValueError(f"speed must be a speed.SpeedPerturb, not {speed!r}")
-            return self._speed_rate(self.sample_rate if sample_rate is None else sample_rate, speed)["Ty"]
-        return self._rate(sample_rate)["Ty"]
+        if speed is not None and not isinstance(speed, SpeedPerturb):
+            raise ValueError(f"speed must be a speed.SpeedPerturb, not {speed!r}")
+        Ty = self._rate(sample_rate, speed)["Ty"]
+        return Ty if speed is not None else Ty[:, 0]
 
-    def _speed_rate(self, R, speed):
-        """What crops at R Hz with the factors of `speed` need, once per (R, factors): the distinct file rates and rate_of
-        [F], a file's; per (rate, factor) a, b, width (speed.ratio; int64 host arrays [rates, factors]) and `ratios`, the same
-        flat as the kernel's uint32 [rates * factors, 3] -- with a = 0, a ratio that is skipped, at factor 1, whose crops go
-        through the tables --; Ty [F, factors]; `tables`, resample.rows_tables of the rates at factor 1; and the device copies
-        d_rate_of, d_a, d_b, d_width, d_Ty (flat), d_ratios, d_table_of [rates].  ValueError: a rate or a ratio the filters
-        do not take."""
+    def _rate(self, sample_rate, speed=None):
+        """What crops at sample_rate (None: the corpus's own rate) need, played at the factors of `speed` (a SpeedPerturb; None:
+        the one factor 1), once per (rate, factors).  Every entry: rate; nk, the number of factors; Ty, int64 [F, nk] on the
+        host, file f's frames at the rate at factor k, Ty_max [F], the most over the factors, and d_Ty, Ty flat on the device;
+        a, b, width; and the filter tables d_d0, d_w.  The two variants of `_resampled_crops`:
+          uniform   a corpus of one rate without speed: a, b, width are ints and d_d0, d_w the one table (resample.device_table).
+          per crop  everything else.  A crop's kind is (its file's rate, its factor): the distinct rates (without speed in the
+                    order they first appear, with it ascending: the order `desc` and `ratios` have had in either case),
+                    rate_of [F] a file's, kind = rate_of * nk + factor.  Per kind, int64 host arrays [kinds]: a, b,
+                    width -- without speed the table's (resample.rows_tables of the rates: desc on the host, d_desc, d_d0,
+                    d_w), with it speed.ratio's --, and `ratios`, the same as the kernel's uint32 [kinds, 3] with a = 0, a
+                    ratio that is skipped, at factor 1, whose crops go through the tables (d_ratios).  On the device d_kind
+                    [F * nk], the kind of (file, factor), and d_kinds [kinds, 5], a kind's whole row for one gather: a, b,
+                    width, its table (factor 1; else len(desc): a row of zeros) and its ratio (the kind itself; at factor 1
+                    len(ratios): skipped).
+        ValueError: a rate or a ratio the filters do not take, naming the first file whose table is too large (with speed, the
+        place of its rate among the ascending rates)."""
         import torch
 
-        from .resample import resampled_frames, rows_tables
+        from .resample import device_table, resampled_frames, rows_tables
 
-        if R is None:
-            raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
-        key = ("speed", R, speed.factors)
+        R = self.sample_rate if sample_rate is None else sample_rate
+        if R is None and speed is not None:
+            raise ValueError(_NEEDS_RATE)
+        key = (R, None if speed is None else speed.factors)
         if key not in self._rates:
             up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(self._dev)
-            rates, rate_of = np.unique(self.sample_rates, return_inverse=True)
-            rate_of = rate_of.reshape(-1).astype(np.int64)
-            abw = np.array([[_speed_ratio(int(r), f, R) for f in speed.factors] for r in rates], dtype=np.int64)
-            if int(abw[..., 2].max()) > _SPEED_MAX_WIDTH:
-                raise ValueError(f"{int(rates.max())} Hz to {R} Hz: a filter of width {int(abw[..., 2].max())}, the kernel takes {_SPEED_MAX_WIDTH}")
-            a, b, width = abw[..., 0], abw[..., 1], abw[..., 2]
-            ratios = abw.reshape(-1, 3).astype(np.uint32)
-            ratios[speed.one::len(speed.factors)] = (0, 1, 0)
-            table_of, desc, d0, w = rows_tables(rates.tolist(), R)
-            Ty = resampled_frames(self.num_frames[:, None], a[rate_of], b[rate_of])
-            self._rates[key] = dict(rates=rates, rate_of=rate_of, a=a, b=b, width=width, ratios=ratios, Ty=Ty, desc=desc,
-                                    d_rate_of=up(rate_of), d_a=up(a.reshape(-1)), d_b=up(b.reshape(-1)), d_width=up(width.reshape(-1)),
-                                    d_Ty=up(Ty.reshape(-1)), d_ratios=up(ratios.view(np.int32)), d_table_of=up(table_of),
-                                    d_desc=up(desc.view(np.int32)), d_d0=up(d0), d_w=up(w))
+            nk = 1 if speed is None else len(speed.factors)
+            if self.sample_rate is not None and speed is None:
+                rt = dict(zip(("a", "b", "width", "d_d0", "d_w"), device_table(self.sample_rate, R, self._dev)))
+                Ty = resampled_frames(self.num_frames, rt["a"], rt["b"])[:, None]
+            else:
+                rates, first, rate_of = np.unique(self.sample_rates, return_index=True, return_inverse=True)
+                rate_of = rate_of.reshape(-1)
+                if speed is not None:
+                    abw = np.array([_speed_ratio(int(r), f, R) for r in rates for f in speed.factors], dtype=np.int64)
+                    if int(abw[:, 2].max()) > _SPEED_MAX_WIDTH:
+                        raise ValueError(f"{int(rates.max())} Hz to {R} Hz: a filter of width {int(abw[:, 2].max())}, the kernel takes {_SPEED_MAX_WIDTH}")
+                else:       # the rates, and so the tables, in the order they first appear among the files
+                    order = np.argsort(first)
+                    rates, first, rate_of = rates[order], first[order], np.argsort(order)[rate_of]
+                try:
+                    table_of, desc, d0, w = rows_tables(rates.tolist(), R)
+                except ValueError as e:     # "source i: ...", i the rate's place: without speed the message names the rate's first file
+                    i, colon, what = str(e).partition(":")
+                    raise ValueError(f"source {first[int(i[7:])]}:{what}" if speed is None and colon and i[:7] == "source " else str(e)) from None
+                if speed is None:
+                    abw = desc[table_of, :3].astype(np.int64)
+                kind = np.arange(len(abw))
+                plain = kind % nk == (0 if speed is None else speed.one)
+                ratios = abw.astype(np.uint32)
+                ratios[plain] = (0, 1, 0)
+                kinds = np.column_stack([abw, np.where(plain, table_of[kind // nk], len(desc)), np.where(plain, len(abw), kind)])
+                kind_of = rate_of[:, None] * nk + np.arange(nk)
+                a, b, width = abw.T
+                Ty = resampled_frames(self.num_frames[:, None], a[kind_of], b[kind_of])
+                rt = dict(a=a, b=b, width=width, rate_of=rate_of, desc=desc, ratios=ratios, d_kind=up(kind_of.reshape(-1)),
+                          d_kinds=up(kinds), d_desc=up(desc.view(np.int32)), d_d0=up(d0), d_w=up(w), d_ratios=up(ratios.view(np.int32)))
+            self._rates[key] = dict(rt, rate=R, nk=nk, Ty=Ty, Ty_max=Ty.max(axis=1), d_Ty=up(Ty.reshape(-1)))
         return self._rates[key]
 
-    def _speed_crops(self, files, frame_offsets, num_frames, out, check, sample_rate, mono, speed):
-        """crops(..., speed=(spec, draws)): crop b is frames frame_offsets[b] .. + num_frames of file files[b] played at the
-        factor k = draws[b] and RESAMPLED AS A WHOLE to the rate of the crops by a_c : b_c = speed.ratio(the file's rate,
-        factor, rate); lengths[b] = min(num_frames, Ty - offset) with Ty = ceil(b_c * T_f / a_c), -1 for a file, a draw or an
-        offset outside.  The step is `_rate_crops`'s for a corpus whose rates differ, with a ratio per (file rate, factor):
-        everything per crop is gathered from the device copies of `_speed_rate`'s small tables by integer operations,
-        alacgpu_plan_crops_frames_device plans the crop's own source window, and the scratch is resampled into `out` by two
-        calls: alacgpu_resample_rows_device for the crops at factor 1 -- the table of the file's rate, as without speed=, so
-        those crops are bit for bit what they are without it; every other row as zeros --, then
-        alacgpu_resample_ratio_rows_device for the others, which skips the rest.  Host-given offsets are checked on the host
-        against the file's largest Ty over the factors; the exact check is the device's."""
+    def _resampled_crops(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, speed=None):
+        """crops(..., sample_rate=R, mono=, speed=(spec, draws)): crop b is frames frame_offsets[b] .. + num_frames of file
+        files[b], played at the factor k = draws[b] with speed=, RESAMPLED AS A WHOLE to R Hz (resample.py states the filter,
+        speed.py the one without tables) by the reduced ratio a : b of its kind, zero behind its end; lengths[b] =
+        min(num_frames, Ty - offset) with Ty = ceil(b * T_f / a), -1 for a file index, a draw or an offset outside -- the host
+        checks and the device-tensor rule are those of `crops`, with Ty for T_f (with speed= the host checks against the
+        file's largest Ty over the factors; the exact check is the device's).  A step: the source frames a crop needs
+        (`source_window`: Ls(num_frames) of them from (o // b) * a - width on, clamped at 0, by integer operations on the
+        device) are planned, staged and decoded as crops of the source into a zeroed float32 scratch [B, C, Ls] the corpus
+        keeps, then the resample call filters every crop out of it.  mono: two channels become their mean in front of the
+        filter.  dtype: float32 (ValueError otherwise).  The step has the two variants of `_rate`:
+          uniform   a, b, width are ints; alacgpu_plan_crops_device; alacgpu_resample_device.  sample_rate None or the
+                    corpus's own never comes here without `mono`; with it there is no filter, the kernel only takes the mean
+                    (resample.identity_table).
+          per crop  a, b, width, table and ratio are the crop's kind's row of d_kinds, one gather;
+                    alacgpu_plan_crops_frames_device with the crop's own window in a scratch [B, C, the largest] (a crop of a
+                    16 kHz file does not decode what a crop of a 48 kHz file needs); alacgpu_resample_rows_device with a
+                    table per row for the crops at factor 1 -- so those are bit for bit what they are without speed=; a file
+                    already at R goes through the table that copies --, every other row as zeros: a crop outside the corpus,
+                    and the crops at another factor, which alacgpu_resample_ratio_rows_device then fills where there is
+                    more than one factor; it skips the rest."""
         import torch
 
-        spec, draws = speed
+        if not _is_f32(torch, dtype):
+            raise ValueError("crops at another sample rate or as mono are float32")
         L = _frame_count("num_frames", num_frames)
         self._open()
-        st = self._speed_rate(self.sample_rate if sample_rate is None else sample_rate, spec)
-        R, nk = (self.sample_rate if sample_rate is None else sample_rate), len(spec.factors)
-        win = self._window(R, L, spec)
+        if self.channels not in (1, 2):
+            raise ValueError(f"{self.channels} channels: the resampler takes 1 or 2")
+        spec, draws = (None, None) if speed is None else speed
+        rt = self._rate(sample_rate, spec)
+        win = self._window(rt["rate"], L, spec)
         Ls, K = win["Ls_max"], win["K"]
-        d_files, d_offs, _ = self._indices(files, frame_offsets, st["Ty"].max(axis=1))
+        d_files, d_offs, _ = self._indices(files, frame_offsets, rt["Ty_max"])
         B, C_ = int(d_files.shape[0]), self.channels
-        if draws is None:
+        if spec is not None and draws is None:
             draws = spec.draw(B, device=self._dev)
-        if draws.shape[0] != B:
+        if draws is not None and draws.shape[0] != B:
             raise ValueError(f"{draws.shape[0]} draws for {B} crops")
         out = self._out(out, (B, 1 if mono else C_, L), torch.float32, zero=False)
         if B * K >= 1 << 32:
             raise ValueError(f"{B} crops of up to {K} packets: a call plans fewer than 2^32 entries")
-        k64 = draws.to(torch.int64)
-        f64 = d_files.long()
-        ok = (f64 >= 0) & (f64 < self.num_files) & (k64 >= 0) & (k64 < nk)
-        fc, kc = f64.clamp(0, self.num_files - 1), k64.clamp(0, nk - 1)
-        Ty = st["d_Ty"][fc * nk + kc]
-        ok &= (d_offs >= 0) & (d_offs <= Ty)
-        idx = st["d_rate_of"][fc] * nk + kc
-        a, b, width = st["d_a"][idx], st["d_b"][idx], st["d_width"][idx]
+        # the crops in source frames: where the target offset is inside its file, else an offset the planner refuses (-1)
+        ok, at, Ty = self._inside(d_files, d_offs, rt["d_Ty"], draws, rt["nk"])
+        rows = "d_kinds" in rt
+        if rows:
+            kind = rt["d_kind"][at]
+            a, b, width, table, ratio = rt["d_kinds"][kind].unbind(1)
+        else:
+            a, b, width = rt["a"], rt["b"], rt["width"]
         origin = (torch.div(d_offs, b, rounding_mode="floor") * a - width).clamp(min=0)
         src_offs = torch.where(ok, origin, -1)
         lengths = torch.where(ok, (Ty - d_offs).clamp(max=L), -1)
@@ -1026,99 +1079,17 @@ class Corpus(_Closing):
             return out, lengths
         scratch = self._scratch("_rs_scratch", (B, C_, Ls))
         scratch.zero_()
-        valid = self._plan_and_decode(d_files, src_offs, Ls, K, win["S"], scratch, d_frames=win["d_Ls"][idx])
+        valid = self._plan_and_decode(d_files, src_offs, Ls, K, win["S"], scratch, d_frames=win["d_Ls"][kind] if rows else None)
+        rows_of = (scratch, B, C_, Ls, origin, valid, d_offs, L)
         stream = torch.cuda.current_stream(self._dev).cuda_stream
-        plain = kc == spec.one
-        row_table = torch.where(ok & plain, st["d_table_of"][st["d_rate_of"][fc]], len(st["desc"])).to(torch.int32)
-        self._gpu.resample_rows_device(scratch, B, C_, Ls, origin, valid, d_offs, L, st["desc"], st["d_desc"], st["d_d0"], st["d_w"],
-                                       row_table, mono, out, stream=stream)
-        if nk > 1:
-            row_ratio = torch.where(ok & ~plain, idx, len(st["ratios"])).to(torch.int32)
-            self._gpu.resample_ratio_rows_device(scratch, B, C_, Ls, origin, valid, d_offs, L, st["ratios"], st["d_ratios"], row_ratio,
-                                                 mono, out, stream=stream)
-        if check:
-            self._check_last(valid, d_files, src_offs, Ls, K, d_shown=d_offs)
-        return out, lengths
-
-    def _rate(self, sample_rate):
-        """What crops at sample_rate (None: the corpus's own rate) need, once per rate: Ty on the host and d_Ty on the device,
-        and the filter.  A corpus of one rate: a, b, width as ints and its table d_d0, d_w (resample.device_table).  One whose
-        rates differ: a, b, width as int64 host arrays [F], the same on the device as d_a, d_b, d_width next to d_table_of,
-        a file's table, and the tables of the files' ratios (resample.rows_tables: desc on the host, d_desc, d_d0, d_w).
-        ValueError: a rate the filter does not take, naming the first file whose table is too large."""
-        import torch
-
-        from .resample import device_table, resampled_frames, rows_tables
-
-        R = self.sample_rate if sample_rate is None else sample_rate
-        if R not in self._rates:
-            up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(self._dev)
-            if self.sample_rate is not None:
-                rt = dict(zip(("a", "b", "width", "d_d0", "d_w"), device_table(self.sample_rate, R, self._dev)))
-            else:
-                table_of, desc, d0, w = rows_tables(self.sample_rates.tolist(), R)
-                a, b, width = (desc[table_of, k].astype(np.int64) for k in range(3))
-                rt = dict(a=a, b=b, width=width, d_a=up(a), d_b=up(b), d_width=up(width), d_table_of=up(table_of), desc=desc,
-                          d_desc=up(desc.view(np.int32)), d_d0=up(d0), d_w=up(w))
-            Ty = resampled_frames(self.num_frames, rt["a"], rt["b"])
-            self._rates[R] = dict(rt, rate=R, Ty=Ty, d_Ty=up(Ty))
-        return self._rates[R]
-
-    def _rate_crops(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono):
-        """crops(..., sample_rate=R, mono=): crop b is frames frame_offsets[b] .. + num_frames of file files[b] RESAMPLED AS A
-        WHOLE to R Hz (resample.py states the filter) by the file's reduced ratio a : b, zero behind its end; lengths[b] =
-        min(num_frames, Ty_f - offset) with Ty_f = ceil(b * T_f / a), -1 for a file index or an offset outside the corpus --
-        the host checks and the device-tensor rule are those of `crops`, with Ty_f for T_f.  A step: the source frames a crop
-        needs (`source_window`: Ls(num_frames) of them from (o // b) * a - width on, clamped at 0, by integer operations on
-        the device) are planned, staged and decoded as crops of the source into a zeroed float32 scratch [B, C, Ls] the corpus
-        keeps, then ONE resample call filters every crop out of it.  mono: two channels become their mean in front of the
-        filter.  dtype: float32 (ValueError otherwise).  The step varies in three places with the kind of corpus:
-          one rate      a, b, width are ints; alacgpu_plan_crops_device; alacgpu_resample_device.  sample_rate None or the
-                        corpus's own never comes here without `mono`; with it there is no filter, the kernel only takes the
-                        mean (resample.identity_table).
-          rates differ  a, b, width are gathered per crop from the per-file device arrays; alacgpu_plan_crops_frames_device
-                        with the crop's own window Ls_f in a scratch [B, C, max Ls_f] (a crop of a 16 kHz file does not decode
-                        what a crop of a 48 kHz file needs); alacgpu_resample_rows_device with a table per row, none (a row of
-                        zeros) for a crop outside the corpus.  A file already at R goes through the table that copies."""
-        import torch
-
-        if _torch_dtype(torch, torch.float32 if dtype is None else dtype) != torch.float32:
-            raise ValueError("crops at another sample rate or as mono are float32")
-        L = _frame_count("num_frames", num_frames)
-        self._open()
-        if self.channels not in (1, 2):
-            raise ValueError(f"{self.channels} channels: the resampler takes 1 or 2")
-        rt = self._rate(sample_rate)
-        win = self._window(rt["rate"], L)
-        Ls, K = win["Ls_max"], win["K"]
-        d_files, d_offs, _ = self._indices(files, frame_offsets, rt["Ty"])
-        B, C_ = int(d_files.shape[0]), self.channels
-        out = self._out(out, (B, 1 if mono else C_, L), torch.float32, zero=False)
-        if B * K >= 1 << 32:
-            raise ValueError(f"{B} crops of up to {K} packets: a call plans fewer than 2^32 entries")
-        # the crops in source frames: where the target offset is inside its file, else an offset the planner refuses (-1)
-        ok, fc, Ty_f = self._inside(d_files, d_offs, rt["d_Ty"])
-        rows = "desc" in rt
-        a, b, width = (rt["d_a"][fc], rt["d_b"][fc], rt["d_width"][fc]) if rows else (rt["a"], rt["b"], rt["width"])
-        origin = (torch.div(d_offs, b, rounding_mode="floor") * a - width).clamp(min=0)
-        src_offs = torch.where(ok, origin, -1)
-        lengths = torch.where(ok, (Ty_f - d_offs).clamp(max=L), -1)
-        if B == 0 or L == 0:
-            self._last = 0
-            if check and B:
-                self._raise_bad_length(lengths, d_files, d_offs)
-            return out, lengths
-        scratch = self._scratch("_rs_scratch", (B, C_, Ls))
-        scratch.zero_()
-        valid = self._plan_and_decode(d_files, src_offs, Ls, K, win["S"], scratch, d_frames=win["d_Ls"][fc] if rows else None)
-        stream = torch.cuda.current_stream(self._dev).cuda_stream
-        if rows:
-            row_table = torch.where(ok, rt["d_table_of"][fc], len(rt["desc"])).to(torch.int32)
-            self._gpu.resample_rows_device(scratch, B, C_, Ls, origin, valid, d_offs, L, rt["desc"], rt["d_desc"], rt["d_d0"], rt["d_w"],
-                                           row_table, mono, out, stream=stream)
+        if not rows:
+            self._gpu.resample_device(*rows_of, a, b, width, rt["d_d0"], rt["d_w"], mono, out, stream=stream)
         else:
-            self._gpu.resample_device(scratch, B, C_, Ls, origin, valid, d_offs, L, a, b, width, rt["d_d0"], rt["d_w"], mono, out,
-                                      stream=stream)
+            row_table = torch.where(ok, table, len(rt["desc"])).to(torch.int32)
+            self._gpu.resample_rows_device(*rows_of, rt["desc"], rt["d_desc"], rt["d_d0"], rt["d_w"], row_table, mono, out, stream=stream)
+            if rt["nk"] > 1:
+                row_ratio = torch.where(ok, ratio, len(rt["ratios"])).to(torch.int32)
+                self._gpu.resample_ratio_rows_device(*rows_of, rt["ratios"], rt["d_ratios"], row_ratio, mono, out, stream=stream)
         if check:
             self._check_last(valid, d_files, src_offs, Ls, K, d_shown=d_offs)
         return out, lengths
@@ -1154,16 +1125,18 @@ class Corpus(_Closing):
         files = torch.randint(0, self.num_files, (B,), generator=generator, device=dev, dtype=torch.int64).to(self._dev)
         u = torch.rand(B, generator=generator, device=dev, dtype=torch.float64).to(self._dev)
         if self.sample_rate is None and sample_rate is None:
-            raise ValueError("the files of this corpus differ in sample rate: crops need sample_rate=")
-        if speed is not None:       # the frames of the crop's file played at the crop's factor
+            raise ValueError(_NEEDS_RATE)
+        if speed is not None:
             if speed[1] is None:
                 speed = (speed[0], speed[0].draw(B, generator=generator, device=self._dev))
             elif speed[1].shape[0] != B:
                 raise ValueError(f"{speed[1].shape[0]} draws for {B} crops")
-            nk = len(speed[0].factors)
-            ends = self._speed_rate(rate, speed[0])["d_Ty"][files * nk + speed[1].to(torch.int64).clamp(0, nk - 1)]
-        else:
-            ends = (self._d_num_frames if sample_rate is None else self._rate(sample_rate)["d_Ty"])[files]
+        spec, draws = (None, None) if speed is None else speed
+        if sample_rate is None and spec is None:    # the native crops: the files' own frames, and nothing to upload
+            ends = self._d_num_frames[files]
+        else:                                       # the frames of the crop's file at the rate of the crops, played at its factor
+            rt = self._rate(sample_rate, spec)
+            ends = rt["d_Ty"][self._at(files, draws, rt["nk"])]
         span = (ends - L).clamp(min=0)
         offs = torch.minimum(torch.floor(u * (span + 1).to(torch.float64)).to(torch.int64), span)
         if mix is not None and mix[1] is None:

@@ -16,7 +16,9 @@ __host__ __device__ inline uint64_t alac_resample_span(uint64_t tile, uint64_t a
     return ((tile - 1u) * a) / b + 2u * width + 2u;
 }
 
-struct alac_resample_params {
+// What every resample launch has: the rows' source and output and the placement of the workgroups.  The three parameter structs
+// contain it; the host fills it once (alacgpu_stages.hip: resample<P>).
+struct alac_resample_io {
     const float* src;             // [rows, channels, src_stride]
     uint64_t src_stride;
     const int64_t* src_origin;    // [rows] the absolute source frame of element 0
@@ -24,14 +26,18 @@ struct alac_resample_params {
     const int64_t* out_first;     // [rows] the absolute target frame of output element 0
     float* out;                   // [rows, mono ? 1 : channels, out_frames]
     uint64_t out_frames;
-    const int32_t* d0;            // [b]
-    const float* weights;         // [b, 2 * width + 1]
-    uint32_t a, b, width;
     uint32_t channels;
     uint32_t mono;
-    uint32_t tile;                // output frames per tile, at most ALAC_RESAMPLE_MAX_TILE
-    uint32_t span;                // alac_resample_span(tile, a, b, width)
+    uint32_t tile;                // output frames per tile, the same for every row, at most ALAC_RESAMPLE_MAX_TILE
     uint32_t tiles_per_wg;
+};
+
+struct alac_resample_params {
+    alac_resample_io io;
+    uint32_t a, b, width;         // (the scalars behind io's: a workgroup reads them with the same load)
+    uint32_t span;                // alac_resample_span(tile, a, b, width)
+    const int32_t* d0;            // [b]
+    const float* weights;         // [b, 2 * width + 1]
 };
 
 __global__ void alac_resample_kernel(alac_resample_params p);
@@ -44,25 +50,14 @@ struct alac_resample_table {
     uint32_t weights_first;       // its weights[b, 2 * width + 1] at this element of the call's weights array
 };
 
-// What it shares with alac_resample_params has the same names: the two kernels share their body.
 struct alac_resample_rows_params {
-    const float* src;             // [rows, channels, src_stride]
-    uint64_t src_stride;
-    const int64_t* src_origin;    // [rows]
-    const int64_t* src_valid;     // [rows]
-    const int64_t* out_first;     // [rows]
-    float* out;                   // [rows, mono ? 1 : channels, out_frames]
-    uint64_t out_frames;
+    alac_resample_io io;
     const alac_resample_table* tables;   // [n_tables]
     const int32_t* d0;            // the tables' d0 arrays, one behind the other
     const float* weights;         // ... and their weights
     const uint32_t* row_table;    // [rows] the table of a row; n_tables and above: the row is written as zeros
     uint32_t n_tables;
-    uint32_t channels;
-    uint32_t mono;
-    uint32_t tile;                // output frames per tile, the same for every row
     uint32_t lds_floats;          // the dynamic LDS of the launch: the largest table (rounded up to 4) + span of a tile
-    uint32_t tiles_per_wg;
 };
 
 __global__ void alac_resample_rows_kernel(alac_resample_rows_params p);
@@ -75,23 +70,12 @@ struct alac_resample_ratio {
 
 constexpr uint32_t ALAC_RESAMPLE_RATIO_MAX_WIDTH = (uint32_t)(ALAC_RESAMPLE_LDS_MAX / sizeof(float) - 2u) / 2u;   // a frame's span fits
 
-// What it shares with alac_resample_params has the same names: the kernels share resample_place and the staging of a span.
 struct alac_resample_ratio_params {
-    const float* src;             // [rows, channels, src_stride]
-    uint64_t src_stride;
-    const int64_t* src_origin;    // [rows]
-    const int64_t* src_valid;     // [rows]
-    const int64_t* out_first;     // [rows]
-    float* out;                   // [rows, mono ? 1 : channels, out_frames]
-    uint64_t out_frames;
+    alac_resample_io io;
     const alac_resample_ratio* ratios;   // [n_ratios]
     const uint32_t* row_ratio;    // [rows] the ratio of a row; n_ratios and above: the row is skipped
     uint32_t n_ratios;
-    uint32_t channels;
-    uint32_t mono;
-    uint32_t tile;                // output frames per tile, the same for every row
     uint32_t lds_floats;          // the dynamic LDS of the launch: the largest span of a tile over the call's ratios
-    uint32_t tiles_per_wg;
 };
 
 __global__ void alac_resample_ratio_rows_kernel(alac_resample_ratio_params p);

@@ -19,7 +19,8 @@
 // one-table call gives for it.  A row that names no table is written as zeros.
 //
 // alacgpu_resample_ratio_rows_device (the end of this file) has no table at all: a ratio per row, and every tap's weight
-// evaluated where it is used.  It shares the placement of the workgroups and the staging of a tile's source span.
+// evaluated where it is used.  The three kernels share the placement of the workgroups, the row view and one tile body
+// (resample_tiles), to which each passes where a tile starts and what a frame's taps weigh.
 #include <type_traits>
 
 #include "alac_resample.h"
@@ -35,8 +36,7 @@ struct resample_table_view {
 };
 
 // blockIdx.x: (row, output channel, group of tiles), the group fastest
-template <class P>
-__device__ __forceinline__ void resample_place(const P& p, uint32_t& group, uint32_t& c, uint64_t& row) {
+__device__ __forceinline__ void resample_place(const alac_resample_io& p, uint32_t& group, uint32_t& c, uint64_t& row) {
     const uint32_t out_channels = p.mono ? 1u : p.channels;
     const uint32_t tiles = (uint32_t)((p.out_frames + p.tile - 1u) / p.tile);
     const uint32_t groups = (tiles + p.tiles_per_wg - 1u) / p.tiles_per_wg;
@@ -46,76 +46,105 @@ __device__ __forceinline__ void resample_place(const P& p, uint32_t& group, uint
     row = plane / out_channels;
 }
 
+// One (row, output channel c) of a launch, for a ratio whose target side is b
+struct resample_row {
+    int64_t origin, valid;        // the source frames [origin, origin + valid) hold signal, valid clamped into 0 .. src_stride
+    int64_t first;                // the absolute target frame of output element 0
+    int64_t end_b;                // the resampled signal has ceil(b (origin + valid) / a) frames: j is one iff 0 <= j and j a < end_b
+    bool two;                     // two channels become their mean on the load
+    const float *s0, *s1;
+    float* dst;
+};
+
+__device__ __forceinline__ resample_row resample_row_of(const alac_resample_io& p, uint32_t c, uint64_t row, uint32_t b) {
+    resample_row r;
+    r.origin = p.src_origin[row];
+    const int64_t valid = p.src_valid[row];
+    r.valid = valid < 0 ? 0 : (valid > (int64_t)p.src_stride ? (int64_t)p.src_stride : valid);
+    r.first = p.out_first[row];
+    r.end_b = (r.origin + r.valid) * (int64_t)b;
+    r.two = p.mono && p.channels == 2u;
+    r.s0 = p.src + (row * p.channels + c) * p.src_stride;
+    r.s1 = r.s0 + p.src_stride;
+    r.dst = p.out + (row * (p.mono ? 1u : p.channels) + c) * p.out_frames;
+    return r;
+}
+
 // The source span of a tile into LDS: xs[idx] = x[s_lo + idx], idx < span -- a frame outside [origin, origin + valid) is zero
 // whatever the memory holds, two channels become their mean here -- between the barriers that fence it from the tile before.
-__device__ __forceinline__ void resample_stage(float* xs, uint32_t span, int64_t s_lo, int64_t origin, int64_t valid, const float* s0,
-                                               const float* s1, bool two) {
+__device__ __forceinline__ void resample_stage(float* xs, uint32_t span, int64_t s_lo, const resample_row& r) {
     __syncthreads();                                        // (the tile before has been computed)
     for (uint32_t idx = threadIdx.x; idx < span; idx += ALAC_RESAMPLE_THREADS) {
-        const int64_t rel = s_lo + idx - origin;
+        const int64_t rel = s_lo + idx - r.origin;
         float v = 0.0f;
-        if (rel >= 0 && rel < valid) {
-            v = s0[rel];
-            if (two) v = (v + s1[rel]) * 0.5f;
+        if (rel >= 0 && rel < r.valid) {
+            v = r.s0[rel];
+            if (r.two) v = (v + r.s1[rel]) * 0.5f;
         }
         xs[idx] = v;
     }
     __syncthreads();
 }
 
-// The workgroup's tiles of (row, output channel c) with the table t; P: the fields the two kernels' parameters share.
-template <class P>
-__device__ __forceinline__ void resample_tiles(const P& p, const resample_table_view& tb, float* lds, uint32_t group, uint32_t c, uint64_t row) {
-    const uint32_t tid = threadIdx.x;
-    const uint32_t N = 2u * tb.width + 1u;
-    const uint32_t table = tb.b * N;
-    float* const w = lds;
-    float* const xs = lds + ((table + 3u) & ~3u);
-    const uint32_t out_channels = p.mono ? 1u : p.channels;
-
-    for (uint32_t i = tid; i < table; i += ALAC_RESAMPLE_THREADS) w[i] = tb.weights[i];
-
-    const int64_t origin = p.src_origin[row];
-    int64_t valid = p.src_valid[row];
-    valid = valid < 0 ? 0 : (valid > (int64_t)p.src_stride ? (int64_t)p.src_stride : valid);
-    const int64_t first = p.out_first[row];
-    // the resampled signal has ceil(b (origin + valid) / a) frames: j is one of them iff 0 <= j and j a < b (origin + valid)
-    const int64_t end_b = (origin + valid) * (int64_t)tb.b;
-    const bool two = p.mono && p.channels == 2u;
-    const float* const s0 = p.src + (row * p.channels + c) * p.src_stride;
-    const float* const s1 = s0 + p.src_stride;
-    float* const dst = p.out + (row * out_channels + c) * p.out_frames;
-
+// The workgroup's tiles of (row, output channel c) with the ratio a : b, N taps a frame and `span` source frames a tile in xs.
+// The tile's first frame j0 gives num j0 = q0 b + r0, floored (a j below 0 is written as zero, but its taps must not wrap); the
+// kernels say the rest: start(q0, r0) is the first source frame of the tile, and frame(r0, k, rel) sets rel, where in the span
+// the taps of frame j0 + k start, and returns its weights: weight(n) is tap n's, asked for once each in ascending n.  Every
+// thread calls start once per tile, in front of that tile's frame calls: what start leaves behind (the table kernels' d00)
+// is the tile's, and frame may read it.
+template <class Start, class Frame>
+__device__ __forceinline__ void resample_tiles(const alac_resample_io& p, uint32_t a, uint32_t b, uint32_t N, uint32_t span, uint32_t num,
+                                               float* xs, uint32_t group, uint32_t c, uint64_t row, const Start& start, const Frame& frame) {
+    const resample_row r = resample_row_of(p, c, row, b);
     for (uint32_t t = 0; t < p.tiles_per_wg; ++t) {
         const uint64_t k0 = ((uint64_t)group * p.tiles_per_wg + t) * p.tile;
         if (k0 >= p.out_frames) break;
-        // the tile's first frame j0 = i0 + b m0 (floored: a j below 0 is written as zero, but its taps must not wrap)
-        const int64_t j0 = first + (int64_t)k0;
-        int64_t m0 = j0 / (int64_t)tb.b;
-        int32_t i0 = (int32_t)(j0 - m0 * (int64_t)tb.b);
-        if (i0 < 0) {
-            i0 += (int32_t)tb.b;
-            m0 -= 1;
+        const int64_t j0 = r.first + (int64_t)k0;
+        const int64_t jn = j0 * (int64_t)num;
+        int64_t q0 = jn / (int64_t)b;
+        int64_t r0 = jn - q0 * (int64_t)b;
+        if (r0 < 0) {
+            r0 += (int64_t)b;
+            q0 -= 1;
         }
-        const int32_t d00 = tb.d0[i0];
-        const int64_t s_lo = m0 * (int64_t)tb.a + d00;      // the first source frame of the tile
-        resample_stage(xs, tb.span, s_lo, origin, valid, s0, s1, two);
+        resample_stage(xs, span, start(q0, r0), r);
         const uint64_t left = p.out_frames - k0;
         const uint32_t n_out = left < p.tile ? (uint32_t)left : p.tile;
-        for (uint32_t k = tid; k < n_out; k += ALAC_RESAMPLE_THREADS) {
-            const uint32_t ii = (uint32_t)i0 + k;
-            const uint32_t mo = ii / tb.b;
-            const uint32_t i = ii - mo * tb.b;
-            uint32_t rel = mo * tb.a + (uint32_t)(tb.d0[i] - d00);
-            rel = rel > tb.span - N ? tb.span - N : rel;      // (a table that is what resample.py makes it never gets here)
-            const float* const wr = w + i * N;
+        for (uint32_t k = threadIdx.x; k < n_out; k += ALAC_RESAMPLE_THREADS) {
+            uint32_t rel;
+            auto weight = frame(r0, k, rel);
+            rel = rel > span - N ? span - N : rel;            // (never, for a table that is what resample.py makes it and for a ratio)
             const float* const x = xs + rel;
             float acc = 0.0f;
-            for (uint32_t n = 0; n < N; ++n) acc = __builtin_fmaf(wr[n], x[n], acc);
+            for (uint32_t n = 0; n < N; ++n) acc = __builtin_fmaf(weight(n), x[n], acc);
             const int64_t j = j0 + (int64_t)k;
-            dst[k0 + k] = (j >= 0 && j * (int64_t)tb.a < end_b) ? acc : 0.0f;
+            r.dst[k0 + k] = (j >= 0 && j * (int64_t)a < r.end_b) ? acc : 0.0f;
         }
     }
+}
+
+// The table kernels' tiles: the table into LDS in front of the span; frame j = i + b m reads from m a + d0[i] on (d0 is the
+// caller's), and tap n weighs w[i][n]
+__device__ __forceinline__ void table_tiles(const alac_resample_io& p, const resample_table_view& tb, float* lds, uint32_t group, uint32_t c,
+                                            uint64_t row) {
+    const uint32_t N = 2u * tb.width + 1u;
+    const uint32_t table = tb.b * N;
+    float* const w = lds;
+    for (uint32_t i = threadIdx.x; i < table; i += ALAC_RESAMPLE_THREADS) w[i] = tb.weights[i];
+    int32_t d00;
+    resample_tiles(p, tb.a, tb.b, N, tb.span, 1u, lds + ((table + 3u) & ~3u), group, c, row,
+                   [&](int64_t m0, int64_t i0) {
+                       d00 = tb.d0[i0];
+                       return m0 * (int64_t)tb.a + d00;
+                   },
+                   [&](int64_t i0, uint32_t k, uint32_t& rel) {
+                       const uint32_t ii = (uint32_t)i0 + k;
+                       const uint32_t mo = ii / tb.b;
+                       const uint32_t i = ii - mo * tb.b;
+                       rel = mo * tb.a + (uint32_t)(tb.d0[i] - d00);
+                       const float* const wr = w + i * N;
+                       return [wr](uint32_t n) { return wr[n]; };
+                   });
 }
 
 }  // namespace
@@ -124,22 +153,15 @@ __global__ __launch_bounds__(ALAC_RESAMPLE_THREADS) void alac_resample_kernel(al
     extern __shared__ __align__(16) float lds[];
     uint32_t group, c;
     uint64_t row;
-    resample_place(p, group, c, row);
-    resample_table_view t;
-    t.d0 = p.d0;
-    t.weights = p.weights;
-    t.a = p.a;
-    t.b = p.b;
-    t.width = p.width;
-    t.span = p.span;
-    resample_tiles(p, t, lds, group, c, row);
+    resample_place(p.io, group, c, row);
+    table_tiles(p.io, {p.d0, p.weights, p.a, p.b, p.width, p.span}, lds, group, c, row);
 }
 
 __global__ __launch_bounds__(ALAC_RESAMPLE_THREADS) void alac_resample_rows_kernel(alac_resample_rows_params p) {
     extern __shared__ __align__(16) float lds[];
     uint32_t group, c;
     uint64_t row;
-    resample_place(p, group, c, row);
+    resample_place(p.io, group, c, row);
     // the row's table: everything here is workgroup-uniform.  A descriptor that is not what the host was shown (no ratio, a
     // table or a span that does not fit the LDS of this launch) counts as no table: nothing is ever stored outside the LDS
     const uint32_t ti = p.row_table[row];
@@ -150,26 +172,21 @@ __global__ __launch_bounds__(ALAC_RESAMPLE_THREADS) void alac_resample_rows_kern
         const uint64_t weights = (uint64_t)d.b * (2u * (uint64_t)d.width + 1u);
         has = d.a != 0 && d.b != 0 && d.width != 0 && weights <= ALAC_RESAMPLE_MAX_TABLE;
         if (has) {
-            const uint64_t span = alac_resample_span(p.tile, d.a, d.b, d.width);
+            const uint64_t span = alac_resample_span(p.io.tile, d.a, d.b, d.width);
             has = ((weights + 3u) & ~3ull) + span <= p.lds_floats;
-            t.d0 = p.d0 + d.d0_first;
-            t.weights = p.weights + d.weights_first;
-            t.a = d.a;
-            t.b = d.b;
-            t.width = d.width;
-            t.span = (uint32_t)span;
+            t = {p.d0 + d.d0_first, p.weights + d.weights_first, d.a, d.b, d.width, (uint32_t)span};
         }
     }
     if (has) {
-        resample_tiles(p, t, lds, group, c, row);
+        table_tiles(p.io, t, lds, group, c, row);
         return;
     }
     // a row without a table (the crop of a file or an offset outside the corpus): zeros
-    const uint32_t out_channels = p.mono ? 1u : p.channels;
-    float* const dst = p.out + (row * out_channels + c) * p.out_frames;
-    const uint64_t k0 = (uint64_t)group * p.tiles_per_wg * p.tile;
-    const uint64_t left = p.out_frames > k0 ? p.out_frames - k0 : 0u;
-    const uint64_t most = (uint64_t)p.tiles_per_wg * p.tile;
+    const uint32_t out_channels = p.io.mono ? 1u : p.io.channels;
+    float* const dst = p.io.out + (row * out_channels + c) * p.io.out_frames;
+    const uint64_t k0 = (uint64_t)group * p.io.tiles_per_wg * p.io.tile;
+    const uint64_t left = p.io.out_frames > k0 ? p.io.out_frames - k0 : 0u;
+    const uint64_t most = (uint64_t)p.io.tiles_per_wg * p.io.tile;
     const uint32_t n_out = (uint32_t)(left < most ? left : most);
     for (uint32_t k = threadIdx.x; k < n_out; k += ALAC_RESAMPLE_THREADS) dst[k0 + k] = 0.0f;
 }
@@ -232,13 +249,12 @@ __device__ __forceinline__ float ratio_weight(const ratio_view<I>& r, I k, I m) 
     return mag >= r.reach ? 0.0f : w;
 }
 
+// The ratio kernel's tiles: frame j, j a = q b + rem, reads from q - width on, and tap n weighs ratio_weight at k = 99 (n b -
+// width b - rem), which grows by 99 b from tap to tap, its residue m with it
 template <class I>
-__device__ __forceinline__ void ratio_tiles(const alac_resample_ratio_params& p, const alac_resample_ratio d, uint32_t span, float* xs,
-                                            uint32_t group, uint32_t c, uint64_t row) {
+__device__ __forceinline__ void ratio_tiles(const alac_resample_io& p, const alac_resample_ratio d, uint32_t span, float* xs, uint32_t group,
+                                            uint32_t c, uint64_t row) {
     typedef typename std::conditional<sizeof(I) == 4, uint32_t, uint64_t>::type U;
-    const uint32_t tid = threadIdx.x;
-    const uint32_t N = 2u * d.width + 1u;
-    const uint32_t out_channels = p.mono ? 1u : p.channels;
     const uint64_t M = d.a > d.b ? d.a : d.b;
     ratio_view<I> r;
     r.period = (I)(200u * M);
@@ -249,55 +265,26 @@ __device__ __forceinline__ void ratio_tiles(const alac_resample_ratio_params& p,
     r.inv100 = 1.0f / (float)(int64_t)(100u * M);
     r.inv1200 = 1.0f / (float)(int64_t)(1200u * M);
     r.scale = (float)(int64_t)(99u * (uint64_t)(d.a < d.b ? d.a : d.b)) / (float)(int64_t)(100u * (uint64_t)d.a);
-
-    const int64_t origin = p.src_origin[row];
-    int64_t valid = p.src_valid[row];
-    valid = valid < 0 ? 0 : (valid > (int64_t)p.src_stride ? (int64_t)p.src_stride : valid);
-    const int64_t first = p.out_first[row];
-    const int64_t end_b = (origin + valid) * (int64_t)d.b;
-    const bool two = p.mono && p.channels == 2u;
-    const float* const s0 = p.src + (row * p.channels + c) * p.src_stride;
-    const float* const s1 = s0 + p.src_stride;
-    float* const dst = p.out + (row * out_channels + c) * p.out_frames;
-
-    for (uint32_t t = 0; t < p.tiles_per_wg; ++t) {
-        const uint64_t k0 = ((uint64_t)group * p.tiles_per_wg + t) * p.tile;
-        if (k0 >= p.out_frames) break;
-        // the tile's first frame: j0 a = q0 b + r0, floored (a j below 0 is written as zero, but its taps must not wrap)
-        const int64_t j0 = first + (int64_t)k0;
-        const int64_t ja = j0 * (int64_t)d.a;
-        int64_t q0 = ja / (int64_t)d.b;
-        int64_t r0 = ja - q0 * (int64_t)d.b;
-        if (r0 < 0) {
-            r0 += (int64_t)d.b;
-            q0 -= 1;
-        }
-        resample_stage(xs, span, q0 - (int64_t)d.width, origin, valid, s0, s1, two);
-        const uint64_t left = p.out_frames - k0;
-        const uint32_t n_out = left < p.tile ? (uint32_t)left : p.tile;
-        for (uint32_t k = tid; k < n_out; k += ALAC_RESAMPLE_THREADS) {
-            // frame j0 + k: (j0 + k) a = (q0 + q) b + rem -- its taps are xs[q ..+ N], the first one d = -width from floor(j a / b)
-            const U ta = (U)r0 + (U)k * (U)d.a;
-            const U q = ta / (U)d.b;
-            const U rem = ta - q * (U)d.b;
-            uint32_t rel = (uint32_t)q;
-            rel = rel > span - N ? span - N : rel;            // (never: span is alac_resample_span of this tile)
-            const U below = (U)99u * ((U)d.width * (U)d.b + rem);     // -k of the first tap, above 0
-            const U mm = below % (U)r.period;
-            I kk = -(I)below;
-            I m = mm ? r.period - (I)mm : (I)0;
-            const float* const x = xs + rel;
-            float acc = 0.0f;
-            for (uint32_t n = 0; n < N; ++n) {
-                acc = __builtin_fmaf(ratio_weight(r, kk, m), x[n], acc);
-                kk += r.step;
-                m += r.step;
-                m = m >= r.period ? m - r.period : m;
-            }
-            const int64_t j = j0 + (int64_t)k;
-            dst[k0 + k] = (j >= 0 && j * (int64_t)d.a < end_b) ? acc : 0.0f;
-        }
-    }
+    resample_tiles(p, d.a, d.b, 2u * d.width + 1u, span, d.a, xs, group, c, row,
+                   [&](int64_t q0, int64_t r0) { return q0 - (int64_t)d.width; },
+                   [&](int64_t r0, uint32_t k, uint32_t& rel) {
+                       // frame j0 + k: (j0 + k) a = (q0 + q) b + rem -- its taps are xs[q ..+ N], the first one d = -width
+                       const U ta = (U)r0 + (U)k * (U)d.a;
+                       const U q = ta / (U)d.b;
+                       const U rem = ta - q * (U)d.b;
+                       rel = (uint32_t)q;
+                       const U below = (U)99u * ((U)d.width * (U)d.b + rem);     // -k of the first tap, above 0
+                       const U mm = below % (U)r.period;
+                       I kk = -(I)below;
+                       I m = mm ? r.period - (I)mm : (I)0;
+                       return [&r, kk, m](uint32_t n) mutable {
+                           const float w = ratio_weight(r, kk, m);
+                           kk += r.step;
+                           m += r.step;
+                           m = m >= r.period ? m - r.period : m;
+                           return w;
+                       };
+                   });
 }
 
 }  // namespace
@@ -306,20 +293,20 @@ __global__ __launch_bounds__(ALAC_RESAMPLE_THREADS) void alac_resample_ratio_row
     extern __shared__ __align__(16) float lds[];
     uint32_t group, c;
     uint64_t row;
-    resample_place(p, group, c, row);
+    resample_place(p.io, group, c, row);
     // the row's ratio: workgroup-uniform.  A row that names none, a ratio with a == 0, and a descriptor that is not what the
     // host was shown (a span that does not fit the LDS of this launch) are skipped: the row's output stays as it is
     const uint32_t ri = p.row_ratio[row];
     if (ri >= p.n_ratios) return;
     const alac_resample_ratio d = p.ratios[ri];
     if (d.a == 0 || d.b == 0 || d.width == 0 || d.width > ALAC_RESAMPLE_RATIO_MAX_WIDTH || (d.a | d.b) >> 31) return;
-    const uint64_t span = alac_resample_span(p.tile, d.a, d.b, d.width);
+    const uint64_t span = alac_resample_span(p.io.tile, d.a, d.b, d.width);
     if (span > p.lds_floats) return;
     // 32-bit integers where 1200 M, the first tap's 99 (width b + b) and a tile's r0 + (tile - 1) a all stay below 2^31
     const uint64_t M = d.a > d.b ? d.a : d.b;
     const uint64_t most = 99u * ((uint64_t)d.width + 2u) * d.b;
-    if (1200u * M < (1ull << 31) && most < (1ull << 31) && (uint64_t)p.tile * d.a + d.b < (1ull << 31))
-        ratio_tiles<int32_t>(p, d, (uint32_t)span, lds, group, c, row);
+    if (1200u * M < (1ull << 31) && most < (1ull << 31) && (uint64_t)p.io.tile * d.a + d.b < (1ull << 31))
+        ratio_tiles<int32_t>(p.io, d, (uint32_t)span, lds, group, c, row);
     else
-        ratio_tiles<int64_t>(p, d, (uint32_t)span, lds, group, c, row);
+        ratio_tiles<int64_t>(p.io, d, (uint32_t)span, lds, group, c, row);
 }

@@ -145,8 +145,8 @@ bool resample_grid(uint64_t out_frames, uint32_t tile, uint64_t planes, uint32_t
 }
 
 // What the three resample entries share, behind the checks of their own tables or ratios: the pointers they have in common, the
-// launch's tile, grid and LDS from lds_bytes(tile), the fields their parameter structs share by name -- own(p, tile, lds) sets
-// the ones that differ -- and the launch.
+// launch's tile, grid and LDS from lds_bytes(tile), the alac_resample_io their parameter structs contain -- own(p, tile, lds) sets
+// the fields that differ -- and the launch.
 template <class P, class F, class G>
 int resample(alacgpu_ctx* ctx, const void* kernel, const F& lds_bytes, const G& own, const void* d_src, uint32_t rows, uint32_t channels,
              uint64_t src_stride, const void* d_src_origin, const void* d_src_valid, const void* d_out_first, uint64_t out_frames,
@@ -161,17 +161,8 @@ int resample(alacgpu_ctx* ctx, const void* kernel, const F& lds_bytes, const G& 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (lds > ALAC_RESAMPLE_LDS_PREFERRED) HIP_TRY(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     P p;
-    p.src = (const float*)d_src;
-    p.src_stride = src_stride;
-    p.src_origin = (const int64_t*)d_src_origin;
-    p.src_valid = (const int64_t*)d_src_valid;
-    p.out_first = (const int64_t*)d_out_first;
-    p.out = (float*)d_out;
-    p.out_frames = out_frames;
-    p.channels = channels;
-    p.mono = mono ? 1u : 0u;
-    p.tile = tile;
-    p.tiles_per_wg = per_wg;
+    p.io = {(const float*)d_src, src_stride, (const int64_t*)d_src_origin, (const int64_t*)d_src_valid, (const int64_t*)d_out_first,
+            (float*)d_out, out_frames, channels, mono ? 1u : 0u, tile, per_wg};
     own(p, tile, lds);
     void* kargs[] = {&p};
     HIP_TRY(ctx, hipLaunchKernel(kernel, dim3(blocks), dim3(ALAC_RESAMPLE_THREADS), kargs, lds, (hipStream_t)hip_stream));

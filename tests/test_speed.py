@@ -160,3 +160,58 @@ def test_speed_perturb_on_a_batch(batch):
     for bad in (dict(factors=[0.9]), dict(factors=3.0), dict(lengths=[1.0, 2.0])):
         with pytest.raises(ValueError):
             pkg.speed_perturb(dev["src"][:2], **dict(dict(factors=1.1, orig_rate=16000), **bad))
+
+
+# (a, b, valid, out_first, origin): ratios whose integers need 64 bits -- 1200 * max(a, b) is 2^31 and more -- next to one that does not
+WIDE = [(1999993, 2000003, 1200, 0, 0), (1999993, 2000003, 1200, -5, 0), (2000003, 1999993, 1200, 0, 0),
+        (1999993, 2000003, 1200, 1000003, 999992), (9, 10, 1200, 0, 0)]
+
+
+def test_ratios_that_need_64_bit_integers():
+    """The kernel's 64-bit instantiation: [5, 2, 1200] into 1101 frames, two tiles a plane and the second one partial.  Coprime
+    ratios near 1 of two million a side, one with leading zeros (taps that must not wrap), one with a > b, one whose j * a is
+    far above 2^32, and a row at 9 : 10 that takes the 32-bit instantiation in the same launch.  Bit for bit the float32 twin,
+    which evaluates only the phases used (the specification's table would have 30 million weights); the twin's weights of those
+    phases within EPS_W * scale of resample.py's closed form in float64; zeros where the twin has zeros; and a row whose ratio
+    is skipped keeps its sentinel."""
+    import torch
+
+    from alac.net_amd.resample import ROLLOFF, ZERO_CROSSINGS, _context, filter_width
+    from alac.net_amd.speed import EPS_W, speed_host_f32, weights_f32
+
+    n, frames = 1200, 1101
+    rng = np.random.default_rng(78)
+    t = np.arange(n) / 44100.0
+    x = np.stack([np.stack([0.3 * np.sin(2 * np.pi * (300 + 170 * r) * t + c) + 0.05 * rng.standard_normal(n) for c in (0, 1)])
+                  for r in range(len(WIDE))]).astype(np.float32)
+    assert all(filter_width(a, b) == 7 for a, b, *_ in WIDE)
+    # the weights of the phases used against the closed form: t = f (d b - r) / (a b), w = (f / a) sinc(t) cos^2(pi t / 12)
+    d = np.arange(-7, 8, dtype=np.int64)
+    for a, b, _, first, _ in WIDE:
+        assert (1200 * max(a, b) >= 1 << 31) == (a != 9)
+        phases = np.unique(((first + np.arange(frames, dtype=np.int64)) * a) % b)
+        f = ROLLOFF * min(a, b)
+        u = f * ((d[None, :] * b - phases[:, None]).astype(np.float64) / (a * b))
+        w64 = np.where(np.abs(u) < ZERO_CROSSINGS, (f / a) * np.sinc(u) * np.cos(np.pi * u / (2 * ZERO_CROSSINGS)) ** 2, 0.0)
+        err = np.abs(weights_f32(a, b, 7, phases).astype(np.float64) - w64).max() / (f / a)
+        print(f"{a} : {b} from {first}: weights within {err * 2 ** 24:.1f} units of 2^-24 of the closed form")
+        assert err <= EPS_W
+    ratios = np.array([(1999993, 2000003, 7), (2000003, 1999993, 7), (9, 10, 7)], dtype=np.uint32)
+    up = lambda v, dt: torch.from_numpy(np.asarray(v, dtype=dt)).to("cuda")
+    src, d_ratios = torch.from_numpy(x).to("cuda"), up(ratios.view(np.int32), np.int32)
+    valid, first, origin = (up([r[k] for r in WIDE], np.int64) for k in (2, 3, 4))
+    for mono in (False, True):
+        twin = np.stack([speed_host_f32(x[r, :, :v], a, b, 7, mono=mono, origin=o, first=j, num_frames=frames)
+                         for r, (a, b, v, j, o) in enumerate(WIDE)])
+        got = {}
+        for skipped in (None, 3):
+            row_ratio = [0, 0, 1, 0, 2]
+            if skipped is not None:
+                row_ratio[skipped] = len(ratios)
+            out = torch.full((len(WIDE), 1 if mono else 2, frames), SENTINEL, dtype=torch.float32, device="cuda")
+            _context(0).resample_ratio_rows_device(src, len(WIDE), 2, n, origin, valid, first, frames, ratios, d_ratios,
+                                                   up(row_ratio, np.int32), mono, out, stream=torch.cuda.current_stream().cuda_stream)
+            got[skipped] = out.cpu().numpy()
+        assert np.array_equal(bits(got[None]), bits(twin)), [int((bits(got[None][r]) != bits(twin[r])).sum()) for r in range(len(WIDE))]
+        assert not got[None][twin == 0].any() and not got[None][1, :, :5].any() and all(got[None][r].any() for r in range(len(WIDE)))
+        assert (got[3][3] == SENTINEL).all() and np.array_equal(bits(np.delete(got[3], 3, 0)), bits(np.delete(twin, 3, 0)))

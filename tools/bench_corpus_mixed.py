@@ -150,10 +150,12 @@ def main():
     rt, win = mixed._rate(R), mixed._window(R, L)
     out, _ = mixed.crops(files[0], offs[0], L, check=False, sample_rate=R, mono=True)
     f = files[0]
-    origin = (torch.div(offs[0], rt["d_b"][f], rounding_mode="floor") * rt["d_a"][f] - rt["d_width"][f]).clamp(min=0)
+    kind = rt["d_kind"][f]
+    a_, b_, width_, table, _ = rt["d_kinds"][kind].unbind(1)
+    origin = (torch.div(offs[0], b_, rounding_mode="floor") * a_ - width_).clamp(min=0)
     Ls, K = win["Ls_max"], win["K"]
     scratch = mixed._rs_scratch[:B * 2 * Ls].view(B, 2, Ls)
-    d_files, d_frames, row_table = f.to(torch.int32), win["d_Ls"][f], rt["d_table_of"][f].to(torch.int32)
+    d_files, d_frames, row_table = f.to(torch.int32), win["d_Ls"][kind], table.to(torch.int32)
     valid = mixed._plan_and_decode(d_files, origin, Ls, K, win["S"], scratch, d_frames=d_frames).clone()
     decode = lambda: mixed._plan_and_decode(d_files, origin, Ls, K, win["S"], scratch, d_frames=d_frames)
     kernel = lambda: mixed._gpu.resample_rows_device(scratch, B, 2, Ls, origin, valid, offs[0], L, rt["desc"], rt["d_desc"], rt["d_d0"], rt["d_w"],

@@ -5,7 +5,8 @@
   (b) 16000_mono   corpus.crops(..., sample_rate=16000, mono=True) and
       48000        corpus.crops(..., sample_rate=48000) for the same duration; the resample call alone (HIP events around
                    --reps back-to-back launches over the step's scratch) with its bytes per second from the bytes it reads
-                   (the valid source frames) plus those it writes, and the decode pair alone over the same source windows
+                   (the valid source frames) plus those it writes, and the decode pair alone over the same source windows;
+                   with --parent the parent's resample call over the same scratch too, alternating with this one
   (c) conv1d       for comparison only, the do-it-yourself route: a native crop of equal duration, then the same filter as a
                    strided torch.nn.functional.conv1d with b output channels (what torchaudio's resample does)
 Wall time of a step: torch.cuda.synchronize() in front of and behind it, the ways alternating inside every step, median and
@@ -134,9 +135,19 @@ def main():
             def decode():
                 corpus.crops(files[0], origin, Ls, out=scratch, check=False)
 
-            ms = {"resample_call": [], "decode_pair": []}
-            for name, fn, reps in (("resample_call", kernel, args.reps), ("decode_pair", decode, 1)):
-                for rep in range(30 + 5):
+            def parent_kernel():
+                parent._gpu.resample_device(scratch, B, 2, Ls, origin, valid, offs[R][0], L[R], a, b, width, d_d0, d_w, mono, theirs,
+                                            stream=stream.cuda_stream)
+
+            timed = [("resample_call", kernel, args.reps), ("decode_pair", decode, 1)]
+            if parent is not None:
+                theirs = torch.empty_like(out)
+                parent_kernel()
+                assert torch.equal(out, theirs), "the resample call's output differs from the parent's"
+                timed.insert(1, ("parent_resample_call", parent_kernel, args.reps))
+            ms = {name: [] for name, _, _ in timed}
+            for rep in range(args.steps + args.warmup if parent is not None else 30 + 5):
+                for name, fn, reps in timed:
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     torch.cuda.synchronize()
                     e0.record(stream)
@@ -144,7 +155,7 @@ def main():
                         fn()
                     e1.record(stream)
                     e1.synchronize()
-                    if rep >= 5:
+                    if rep >= (args.warmup if parent is not None else 5):
                         ms[name].append(e0.elapsed_time(e1) / reps)
             moved = int(valid.sum()) * 2 * 4 + out.numel() * 4
             k = stats(ms["resample_call"])
@@ -152,6 +163,10 @@ def main():
                 "source_frames_per_crop": Ls, "out_frames": L[R], "table_weights": b * (2 * width + 1), "resample_call_ms": k,
                 "bytes_read_plus_written": moved, "resample_call_gb_per_s": round(moved / k["median"] / 1e6, 1),
                 "decode_pair_ms_events_around_plan_and_decode": stats(ms["decode_pair"])}
+            if parent is not None:
+                q = stats(ms["parent_resample_call"])
+                r[f"{R}{'_mono' if mono else ''}"].update({"parent_resample_call_ms": q,
+                                                           "resample_call_inside_parent_p10_p90": bool(q["p10"] <= k["median"] <= q["p90"])})
         results.append(r)
     doc = {"command": "python tools/bench_resample.py " + " ".join(sys.argv[1:]), "files": args.files, "seconds": args.seconds,
            "steps": args.steps, "warmup": args.warmup, "reps": args.reps, "blob_mb": round(corpus._blob_bytes / 1e6, 1), "results": results}

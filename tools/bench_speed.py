@@ -7,8 +7,10 @@
   step      corpus.random_crops(64, 32000, sample_rate=16000, mono=True, check=False) on 44.1 kHz files with
             speed=SpeedPerturb() and without, alternating inside every step, torch.cuda.synchronize() in front of and behind
             each: wall time, median and p10 .. p90.
+With --parent DIR (a built tree of the parent commit) the parent's ratio call and the parent's speed step alternate with this
+tree's: the outputs have to be equal, and this tree's median has to lie inside the parent's p10 .. p90.
 One JSON document, printed and written to --out.
-  python tools/bench_speed.py [--steps 200] [--warmup 20] [--out profiles/speed.json]"""
+  python tools/bench_speed.py [--parent DIR] [--steps 200] [--warmup 20] [--out profiles/speed.json]"""
 import argparse
 import json
 import os
@@ -29,6 +31,7 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--parent", help="a built tree of the parent commit: its ratio call and its speed step alternate with this tree's")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "speed.json"))
     args = ap.parse_args()
     import torch
@@ -37,7 +40,7 @@ def main():
     from alac.net_amd import synth
     from alac.net_amd.resample import device_table, filter_width
     from bench_corpus import make_file
-    from bench_resample import stats
+    from bench_resample import load_parent, stats
 
     synth.build()
     torch.cuda.set_device(0)
@@ -45,10 +48,13 @@ def main():
     stream = torch.cuda.current_stream(dev)
     n_steps = args.steps + args.warmup
     rng = np.random.default_rng(1)
+    parent_pkg = load_parent(args.parent) if args.parent else None
+    inside = lambda ms, new, old: bool(ms[old]["p10"] <= ms[new]["median"] <= ms[old]["p90"])
 
     # ---- the call alone --------------------------------------------------------------------------------------------------------
     calls = []
     B, L = 64, 32000
+    parent_ctx = parent_pkg.AlacGpuContext([(4096, 16, 40, 10, 14, 2)], device=0) if parent_pkg else None
     with pkg.AlacGpuContext([(4096, 16, 40, 10, 14, 2)], device=0) as ctx:
         for a, b in ((9, 10), (11, 10), (3969, 1600)):
             width = filter_width(a, b)
@@ -67,9 +73,14 @@ def main():
                 _, _, _, d_d0, d_w = device_table(a, b, dev)
                 ways["table_call"] = lambda: ctx.resample_device(x, B, 1, Ls, zeros, valid, zeros, L, a, b, width, d_d0, d_w, False, out_t,
                                                                  stream=stream.cuda_stream)
+            if parent_pkg is not None:
+                theirs = torch.empty((B, 1, L), dtype=torch.float32, device=dev)
+                ways["parent_ratio_call"] = lambda: parent_ctx.resample_ratio_rows_device(x, B, 1, Ls, zeros, valid, zeros, L, ratios, d_ratios,
+                                                                                         row_ratio, False, theirs, stream=stream.cuda_stream)
             for fn in ways.values():
                 fn()
             torch.cuda.synchronize()
+            assert parent_pkg is None or torch.equal(out, theirs), "the ratio call's output differs from the parent's"
             ms = {m: [] for m in ways}
             for rep in range(n_steps):
                 for way, fn in ways.items():
@@ -84,6 +95,8 @@ def main():
                         ms[way].append(e0.elapsed_time(e1) / args.reps)
             doc = {"ratio": [a, b], "width": width, "src_shape": [B, 1, Ls], "out_shape": [B, 1, L],
                    "ms_per_call_events_around_reps_calls": {m: stats(v) for m, v in ms.items()}}
+            if parent_pkg is not None:
+                doc["ratio_call_inside_parent_p10_p90"] = inside(doc["ms_per_call_events_around_reps_calls"], "ratio_call", "parent_ratio_call")
             if table:
                 doc["max_abs_difference_to_table_call"] = float((out - out_t).abs().max())
                 r, t = doc["ms_per_call_events_around_reps_calls"]["ratio_call"], doc["ms_per_call_events_around_reps_calls"]["table_call"]
@@ -98,6 +111,16 @@ def main():
     kw = dict(sample_rate=R, mono=True, check=False)
     sp = pkg.SpeedPerturb()
     ways = {"speed": lambda: corpus.random_crops(B, L, speed=sp, **kw)[0], "without": lambda: corpus.random_crops(B, L, **kw)[0]}
+    if parent_pkg is not None:
+        parent_ctx.close()
+        parent, psp = parent_pkg.Corpus([distinct[f % 2] for f in range(args.files)]), parent_pkg.SpeedPerturb()
+        ways["parent_speed"] = lambda: parent.random_crops(B, L, speed=psp, **kw)[0]
+        ways["parent_without"] = lambda: parent.random_crops(B, L, **kw)[0]
+        for seed in (3, 4):      # one seeded generator on both sides: the same draws, and the same crops of them
+            g = [torch.Generator(device=dev).manual_seed(seed) for _ in range(2)]
+            for mine, theirs in ((corpus.random_crops(B, L, speed=sp, generator=g[0], **kw), parent.random_crops(B, L, speed=psp, generator=g[1], **kw)),
+                                 (corpus.random_crops(B, L, generator=g[0], **kw), parent.random_crops(B, L, generator=g[1], **kw))):
+                assert all(torch.equal(x, y) for x, y in zip(mine, theirs)), "random_crops differs from the parent's"
     wall = {m: [] for m in ways}
     for i in range(n_steps):
         for m, fn in ways.items():
@@ -110,10 +133,14 @@ def main():
             if i >= args.warmup:
                 wall[m].append(dt)
     corpus.close()
+    if parent_pkg is not None:
+        parent.close()
     step = {"step": "random_crops(64, 32000, sample_rate=16000, mono=True, check=False) on 44.1 kHz stereo files",
             "speed": "speed=SpeedPerturb(): 0.9 / 1.0 / 1.1, that is 3969 : 1600, 441 : 160 (the table kernel) and 4851 : 1600",
             "wall_ms": {m: stats(v) for m, v in wall.items()}}
-    shown = [a for i, a in enumerate(sys.argv[1:], 1) if a != "--out" and sys.argv[i - 1] != "--out"]     # (where it was written says nothing)
+    if parent_pkg is not None:
+        step.update({f"{m}_inside_parent_p10_p90": inside(step["wall_ms"], m, "parent_" + m) for m in ("speed", "without")})
+    shown = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--out", "--parent") and sys.argv[i - 1] not in ("--out", "--parent")]     # (where it was written, and where the parent's tree lay, say nothing)
     doc = {"command": " ".join(["python tools/bench_speed.py"] + shown), "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
            "calls": calls, "step": step}
     text = json.dumps(doc, indent=1)

@@ -3,26 +3,18 @@
             on [16, 1, 128, 3000], the slice [..., :3000] of 3001, with random lengths; masks only (two of each kind) and with
             time_warp=5 as well, against what a user writes today in torch on the same tensors: broadcast compares and a `where`
             for the masks (a masked fill), a batched index computation, two gathers and a lerp for the warp (float32 positions: close to the
-            kernel's, not its bits).  HIP events around --reps back-to-back calls, --steps times after --warmup: median and
-            p10 .. p90 of the time per call.
+            kernel's, not its bits).  _measure.event_ms, one way after the other: median and p10 .. p90 of the time per call.
   step      corpus.random_crops(64, 32000, sample_rate=16000, mono=True, features=spec, normalize=MeanVar(), check=False) with
-            augment=SpecAugment(time_warp=5) and without, the ways alternating inside every step, torch.cuda.synchronize() in
-            front of and behind each: wall time, median and p10 .. p90.  With --parent DIR (a built tree of the parent commit)
+            augment=SpecAugment(time_warp=5) and without: _measure.wall_ms, median and p10 .. p90.  With --parent DIR (a built tree of the parent commit)
             the call without augment on the parent's package as `parent`, alternating with the others: nothing that existed may
             have moved.  Without --parent the document says that it was not measured.
 One JSON document, printed and written to --out.
   python tools/bench_augment.py [--parent DIR] [--steps 200] [--warmup 20] [--out profiles/augment.json]"""
 import argparse
-import json
-import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from _measure import arguments, command, device, emit, event_ms, inside, load_parent, make_file, stats, wall_ms
 
 
 def composition(torch, x, warp, freq, time_, lengths, fill, with_warp):
@@ -53,24 +45,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=16)
     ap.add_argument("--seconds", type=float, default=30.0)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--parent", help="a built tree of the parent commit: its step without augment alternates with this tree's")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "augment.json"))
+    arguments(ap, "augment.json", reps=10, parent="a built tree of the parent commit: its step without augment alternates with this tree's")
     args = ap.parse_args()
     import torch
 
     import alac.net_amd as pkg
     from alac.net_amd import synth
-    from bench_corpus import make_file
-    from bench_resample import load_parent, stats
 
     synth.build()
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda", 0)
-    stream = torch.cuda.current_stream(dev)
-    n_steps = args.steps + args.warmup
+    dev, stream = device(torch)
     rng = np.random.default_rng(1)
 
     # ---- the call alone --------------------------------------------------------------------------------------------------------
@@ -91,18 +74,8 @@ def main():
                 theirs = lambda: composition(torch, theirs_x, warp, freq, time_, lengths, 0.0, bool(W))
                 ours(), theirs()
                 close = bool(torch.allclose(ours_x, theirs_x, rtol=1e-3, atol=1e-3))
-                ms = {"specaugment_call": [], "torch_composition": []}
-                for way, fn in (("specaugment_call", ours), ("torch_composition", theirs)):
-                    for rep in range(n_steps):
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        torch.cuda.synchronize()
-                        e0.record(stream)
-                        for _ in range(args.reps):
-                            fn()
-                        e1.record(stream)
-                        e1.synchronize()
-                        if rep >= args.warmup:
-                            ms[way].append(e0.elapsed_time(e1) / args.reps)
+                ms = event_ms(torch, stream, {"specaugment_call": ours, "torch_composition": theirs}, args.steps, args.warmup, args.reps,
+                              alternate=False)
                 k, c = stats(ms["specaugment_call"]), stats(ms["torch_composition"])
                 calls.append({"shape": [B, 1, M, N], "line_stride": S, "time_warp": W, "in_place": True,
                               "first_call_agrees_with_torch_to_1e-3": close,
@@ -120,37 +93,23 @@ def main():
     spec = pkg.LogMel(R, 400, 160, 80)
     aug = pkg.SpecAugment(time_warp=5)
     kw = dict(sample_rate=R, mono=True, features=spec, normalize=pkg.MeanVar(), check=False)
-    ways = {"augment": lambda: corpus.random_crops(B, L, augment=aug, **kw)[0], "without": lambda: corpus.random_crops(B, L, **kw)[0]}
+    ways = {"augment": lambda i: corpus.random_crops(B, L, augment=aug, **kw)[0], "without": lambda i: corpus.random_crops(B, L, **kw)[0]}
     if parent is not None:
         parent_kw = dict(sample_rate=R, mono=True, features=parent_pkg.LogMel(R, 400, 160, 80), normalize=parent_pkg.MeanVar(), check=False)
-        ways["parent"] = lambda: parent.random_crops(B, L, **parent_kw)[0]
-    wall = {m: [] for m in ways}
-    for i in range(n_steps):
-        for m, fn in ways.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            out = fn()
-            torch.cuda.synchronize()
-            dt = (time.perf_counter() - t0) * 1e3
-            del out
-            if i >= args.warmup:
-                wall[m].append(dt)
+        ways["parent"] = lambda i: parent.random_crops(B, L, **parent_kw)[0]
+    wall = wall_ms(torch, ways, args.steps, args.warmup)
     step = {"step": "random_crops(64, 32000, sample_rate=16000, mono=True, features=LogMel(16000, 400, 160, 80), normalize=MeanVar(), check=False)",
             "augment": "SpecAugment(time_warp=5)", "wall_ms": {m: stats(v) for m, v in wall.items()}}
     if parent is not None:
-        p, w = step["wall_ms"]["parent"], step["wall_ms"]["without"]
-        step["without_median_inside_parent_p10_p90"] = bool(p["p10"] <= w["median"] <= p["p90"])
+        step["without_median_inside_parent_p10_p90"] = inside(step["wall_ms"]["parent"], step["wall_ms"]["without"])
     else:
         step["parent"] = "not measured: no tree of the parent commit was given (--parent)"
     corpus.close()
     if parent is not None:
         parent.close()
-    doc = {"command": "python tools/bench_augment.py " + " ".join(sys.argv[1:]), "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
+    doc = {"command": command(__file__), "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
            "calls": calls, "step": step}
-    text = json.dumps(doc, indent=1)
-    print(text, flush=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    emit(doc, args.out)
 
 
 if __name__ == "__main__":

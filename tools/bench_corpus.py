@@ -3,9 +3,9 @@
   (a) load_batch  load_batch(file bytes of every crop, frame_offsets=, max_frames=): demux, plan, upload and a context per call
   (b) corpus_host corpus.crops with host index arrays and check=True (two small uploads, one small read)
   (c) corpus_dev  corpus.crops with device index tensors and check=False (nothing but the enqueue)
-Per (B, L): the wall time of a step (torch.cuda.synchronize() in front of and behind it, median of --steps steps after
---warmup), the planning kernel's time (HIP events around --plan-reps back-to-back launches, divided by them, median) and the
-padding share 1 - packets / (B * K).  The three are checked equal once.  One JSON line.
+Per (B, L): the wall time of a step (_measure.wall_ms, median), the planning kernel's time (HIP events around --plan-reps
+back-to-back launches, divided by them, median) and the padding share 1 - packets / (B * K).  The three are checked equal
+once.  One JSON line.
   python tools/bench_corpus.py [--files 32] [--seconds 60] [--steps 30] [--warmup 5]
 With --hbm-bytes N a fourth way on a second corpus, Corpus(files, hbm_bytes=N):
   (d) corpus_tiered  as (c), the packets of the step staged from page-locked host memory (alacgpu_stage_packets_device)
@@ -14,25 +14,10 @@ Kernel times of the decode pair: run one way alone under the profiler's kernel t
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_corpus.py --only corpus_dev --shape 64x88200"""
 import argparse
 import json
-import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def make_file(synth, frames, seed):
-    from alac.net_amd.synth import m4a
-
-    n = -(-frames // 4096)
-    d = synth.packet_descs(n, stereo=1)
-    d["n"][-1] = frames - (n - 1) * 4096
-    b = synth.make_batch(d, synth.default_signal(seed))
-    packets = [bytes(b["blob"][int(o):int(o) + int(s)]) for o, s in zip(b["offsets"], b["sizes"])]
-    return m4a.write_m4a(packets, [int(x) for x in d["n"]], sample_size=16, channels=2, sample_rate=44100)
+from _measure import device, make_file, wall_ms
 
 
 def main():
@@ -55,8 +40,7 @@ def main():
     from alac.net_amd import synth
 
     synth.build()
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda", 0)
+    dev, stream = device(torch)
     T = int(args.seconds * 44100)
     distinct = [make_file(synth, T, 11 + k) for k in range(args.distinct)]
     blobs = [distinct[f % len(distinct)] for f in range(args.files)]
@@ -92,17 +76,7 @@ def main():
             outs = [fn(0) for fn in modes.values()]
             assert all(torch.equal(outs[0], x) for x in outs[1:]), "the three ways differ" if tiered is None else "the four ways differ"
             del outs
-        wall = {m: [] for m in modes}
-        for i in range(args.steps + args.warmup):          # the ways alternate inside every step: drift hits them alike
-            for m, fn in modes.items():
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                out = fn(i)
-                torch.cuda.synchronize()
-                dt = (time.perf_counter() - t0) * 1e3
-                del out
-                if i >= args.warmup:
-                    wall[m].append(dt)
+        wall = wall_ms(torch, modes, args.steps, args.warmup)
         med = lambda v: round(float(np.median(v)), 4)
         r = {"crops": B, "crop_frames": L, "wall_ms": {m: med(v) for m, v in wall.items()}}
         if not args.only:
@@ -111,7 +85,6 @@ def main():
             corpus.crops(on_device[0][0], on_device[0][1], L, check=False)
             valid = corpus.last_status()[1]
             pl, lengths = corpus._plan, torch.empty(B, dtype=torch.int64, device=dev)
-            stream = torch.cuda.current_stream(dev)
 
             f, o = on_device[0][0].to(torch.int32), on_device[0][1]
 
@@ -123,7 +96,7 @@ def main():
                     pkg._dp(pl["dst_frames"]), pkg._dp(pl["src_skip"]), pkg._dp(lengths), pkg._VP(stream.cuda_stream))
                 assert rc == 0, rc
 
-            ms = []
+            ms = []                                         # (no synchronize in front of the events: not _measure.event_ms)
             for rep in range(args.steps + args.warmup):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(stream)

@@ -4,50 +4,17 @@
                     crops(..., sample_rate=48000).  With --parent DIR (a built tree of the parent commit) the same calls on the
                     parent's package, alternating with this one: this tree's median has to lie inside the parent's p10 .. p90
   (b) mixed         Corpus(half the files at 44.1 kHz, half at 48 kHz, mixed_rates=True): crops(..., sample_rate=16000,
-                    mono=True), half the crops from either half, in one call; HIP events around the plan + decode pair and
-                    around the one resample call (--reps back-to-back launches).  With --parent the parent's mixed corpus takes
-                    the same step, alternating with this one, under the same criterion
+                    mono=True), half the crops from either half, in one call; _measure.event_ms around the plan + decode
+                    pair and around the one resample call (--reps back-to-back launches), 30 after 5, one after the other.
+                    With --parent the parent's mixed corpus takes the same step, alternating with this one, same criterion
   (c) two_corpora   the two single-rate corpora of the same files and the same crops in two calls of half the batch each
-Wall time of a step: torch.cuda.synchronize() in front of and behind it, the ways alternating inside every step, median and
-p10 .. p90 of --steps steps after --warmup.  One JSON document, printed and written to --out.
+Wall time of a step: _measure.wall_ms, median and p10 .. p90.  One JSON document, printed and written to --out.
   python tools/bench_corpus_mixed.py [--parent DIR] [--steps 200] [--warmup 20] [--out profiles/corpus_mixed_rates.json]"""
 import argparse
-import json
-import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-
-def make_file(synth, frames, seed, rate):
-    from alac.net_amd.synth import m4a
-
-    n = -(-frames // 4096)
-    d = synth.packet_descs(n, stereo=1)
-    d["n"][-1] = frames - (n - 1) * 4096
-    b = synth.make_batch(d, synth.default_signal(seed))
-    packets = [bytes(b["blob"][int(o):int(o) + int(s)]) for o, s in zip(b["offsets"], b["sizes"])]
-    return m4a.write_m4a(packets, [int(x) for x in d["n"]], sample_size=16, channels=2, sample_rate=rate)
-
-
-def event_ms(torch, stream, fn, reps):
-    ms = []
-    for rep in range(30 + 5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record(stream)
-        for _ in range(reps):
-            fn()
-        e1.record(stream)
-        e1.synchronize()
-        if rep >= 5:
-            ms.append(e0.elapsed_time(e1) / reps)
-    return ms
+from _measure import arguments, command, device, emit, event_ms, inside, load_parent, make_file, stats, wall_ms
 
 
 def main():
@@ -56,22 +23,16 @@ def main():
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--crops", type=int, default=64)
     ap.add_argument("--crop-seconds", type=int, default=2)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--parent", help="a built tree of the parent commit: its single-rate and mixed steps alternate with this tree's")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "corpus_mixed_rates.json"))
+    arguments(ap, "corpus_mixed_rates.json", reps=20,
+              parent="a built tree of the parent commit: its single-rate and mixed steps alternate with this tree's")
     args = ap.parse_args()
     import torch
 
     import alac.net_amd as pkg
     from alac.net_amd import synth
-    from bench_resample import load_parent, stats
 
     synth.build()
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda", 0)
-    stream = torch.cuda.current_stream(dev)
+    dev, stream = device(torch)
     half, B, R = args.files // 2, args.crops, 16000
     L = args.crop_seconds * R
     rates = (44100, 48000)
@@ -79,22 +40,11 @@ def main():
     of_rate = {r: [blobs[r][f % 2] for f in range(half)] for r in rates}
     n_steps = args.steps + args.warmup
     rng = np.random.default_rng(B)
-    doc = {"command": "python tools/bench_corpus_mixed.py " + " ".join(sys.argv[1:]), "files": args.files, "seconds": args.seconds,
+    doc = {"command": command(__file__), "files": args.files, "seconds": args.seconds,
            "crops": B, "crop_seconds": args.crop_seconds, "steps": args.steps, "warmup": args.warmup, "reps": args.reps}
 
     def measure(ways):
-        wall = {m: [] for m in ways}
-        for i in range(n_steps):
-            for m, fn in ways.items():
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                out = fn(i)
-                torch.cuda.synchronize()
-                dt = (time.perf_counter() - t0) * 1e3
-                del out
-                if i >= args.warmup:
-                    wall[m].append(dt)
-        return {m: stats(v) for m, v in wall.items()}
+        return {m: stats(v) for m, v in wall_ms(torch, ways, args.steps, args.warmup).items()}
 
     # (a) the single-rate step, this tree against the parent
     parent_pkg = load_parent(args.parent) if args.parent else None
@@ -115,8 +65,7 @@ def main():
     a = {"wall_ms": measure(ways)}
     if parent is not None:
         for k in ("16000_mono", "48000"):
-            p, n = a["wall_ms"][f"parent_{k}"], a["wall_ms"][f"this_{k}"]
-            a[f"{k}_inside_parent_p10_p90"] = bool(p["p10"] <= n["median"] <= p["p90"])
+            a[f"{k}_inside_parent_p10_p90"] = inside(a["wall_ms"][f"parent_{k}"], a["wall_ms"][f"this_{k}"])
         parent.close()
     single.close()
     doc["single_rate"] = a
@@ -142,8 +91,7 @@ def main():
         assert torch.equal(ways["mixed"](0), ways["parent_mixed"](0)), "the mixed crops differ from the parent's"
     b = {"wall_ms": measure(ways)}
     if parent is not None:
-        p = b["wall_ms"]["parent_mixed"]
-        b["mixed_inside_parent_p10_p90"] = bool(p["p10"] <= b["wall_ms"]["mixed"]["median"] <= p["p90"])
+        b["mixed_inside_parent_p10_p90"] = inside(b["wall_ms"]["parent_mixed"], b["wall_ms"]["mixed"])
         parent.close()
     b["mixed_over_two_corpora"] = round(b["wall_ms"]["mixed"]["median"] / b["wall_ms"]["two_corpora"]["median"], 3)
     # the two halves of the mixed step alone, over the first step's crops
@@ -161,19 +109,17 @@ def main():
     kernel = lambda: mixed._gpu.resample_rows_device(scratch, B, 2, Ls, origin, valid, offs[0], L, rt["desc"], rt["d_desc"], rt["d_d0"], rt["d_w"],
                                                      row_table, True, out, stream=stream.cuda_stream)
     moved = int(valid.sum()) * 2 * 4 + out.numel() * 4
-    k = stats(event_ms(torch, stream, kernel, args.reps))
+    alone = lambda fn, reps: stats(event_ms(torch, stream, {"call": fn}, 30, 5, reps, alternate=False)["call"])
+    k = alone(kernel, args.reps)
     b.update({"source_frames_per_crop": {str(r): int(x) for r, x in zip(rates, (win["Ls"][0], win["Ls"][half]))}, "entries_per_crop": K,
               "out_frames": L, "table_weights": [int(d[1] * (2 * d[2] + 1)) for d in rt["desc"]], "resample_call_ms": k,
               "bytes_read_plus_written": moved, "resample_call_gb_per_s": round(moved / k["median"] / 1e6, 1),
-              "decode_pair_ms_events_around_plan_and_decode": stats(event_ms(torch, stream, decode, 1))})
+              "decode_pair_ms_events_around_plan_and_decode": alone(decode, 1)})
     doc["mixed"] = b
     mixed.close()
     for c in two:
         c.close()
-    text = json.dumps(doc, indent=1)
-    print(text, flush=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    emit(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -6,13 +6,10 @@ output is checked against the slot layout's once.  One JSON line per batch size.
   python tools/bench_decode_into.py [--packets 4096 32768] [--rounds 30] [--warmup 5]"""
 import argparse
 import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import _measure  # noqa: F401  (the repository root on sys.path)
 
 MODES = ["slots_int32", "int32_interleaved", "int32_planar", "float32_interleaved", "float32_planar"]
 

@@ -7,14 +7,11 @@ its PCM (GPU decoder).  One JSON line per batch size.  Kernel time: run it under
   python tools/bench_encode.py [--packets 4096 32768] [--iters 30] [--warmup 5] [--threads 16]"""
 import argparse
 import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import _measure  # noqa: F401  (the repository root on sys.path)
 
 
 def main():

@@ -4,45 +4,31 @@
                      window -> pad to 512 -> rfft -> abs()^2 -> matmul with the mel banks -> clamp(min=2^-23) -> log
   logmel_call        the alacgpu_logmel_device call at n_fft 400, hop 160, 80 mels on the same tensor: the same GEMM shape with
                      K 400 and 201 bins where fbank has 257
-HIP events around --reps back-to-back calls, --steps times after --warmup, median and p10 .. p90.  Then the step
+_measure.event_ms, the three ways alternating inside every repetition: median and p10 .. p90.  Then the step
 corpus.random_crops(64, 32000, sample_rate=16000, mono=True, features=..., check=False) with the KaldiFbank against the same
-step with LogMel(16000, 400, 160, 80), out of synthetic M4A files (stereo 16-bit at 44.1 kHz, 4096-frame packets): wall time
-with torch.cuda.synchronize() in front of and behind it, the two alternating inside every step.  One JSON document, printed and
-written to --out.
+step with LogMel(16000, 400, 160, 80), out of synthetic M4A files (stereo 16-bit at 44.1 kHz, 4096-frame packets):
+_measure.wall_ms, the generator seeded with the step in front of either way.  One JSON document, printed and written to --out.
   python tools/bench_fbank.py [--steps 200] [--warmup 20] [--out profiles/fbank.json]"""
 import argparse
-import json
-import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from _measure import arguments, command, device, emit, event_ms, make_file, stats, wall_ms
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=32)
     ap.add_argument("--seconds", type=float, default=60.0)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fbank.json"))
+    arguments(ap, "fbank.json", reps=10)
     args = ap.parse_args()
     import torch
 
     import alac.net_amd as pkg
     from alac.net_amd import synth
-    from bench_corpus import make_file
-    from bench_resample import stats
 
     synth.build()
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda", 0)
-    stream = torch.cuda.current_stream(dev)
+    dev, stream = device(torch)
     B, L, R = 64, 32000, 16000
     kaldi, logmel = pkg.KaldiFbank(R), pkg.LogMel(R, 400, 160, 80)
     gpu = pkg.AlacGpuContext([(4096, 16, 40, 10, 14, 2)])
@@ -65,19 +51,7 @@ def main():
              "logmel_call": lambda: logmel.launch(gpu, x, B, 1, L, L, out_l, stream.cuda_stream)}
     calls["fbank_call"]()
     worst = float((out_k - compose(x)).abs().max())
-    ms = {name: [] for name in calls}
-    for rep in range(args.steps + args.warmup):
-        for name, fn in calls.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record(stream)
-            for _ in range(args.reps):
-                fn()
-            e1.record(stream)
-            e1.synchronize()
-            if rep >= args.warmup:
-                ms[name].append(e0.elapsed_time(e1) / args.reps)
-    alone = {name: stats(v) for name, v in ms.items()}
+    alone = {name: stats(v) for name, v in event_ms(torch, stream, calls, args.steps, args.warmup, args.reps, alternate=True).items()}
     flop = lambda spec, K: 2.0 * B * spec.frames(L) * (K * 2 * spec.n_bins + spec.n_mels * spec.n_bins)
     call = {"tensor": [B, 1, L], "feature_frames": kaldi.frames(L), "max_abs_difference_to_torch_in_ln": round(worst, 6),
             "alone_ms_events_around_reps_calls": alone,
@@ -93,31 +67,17 @@ def main():
     distinct = [make_file(synth, T, 11 + k) for k in range(2)]
     corpus = pkg.Corpus([distinct[f % 2] for f in range(args.files)])
     kw = dict(sample_rate=R, mono=True, check=False)
-    ways = {"kaldi_fbank": lambda g: corpus.random_crops(B, L, generator=g, features=kaldi, **kw)[0],
-            "log_mel": lambda g: corpus.random_crops(B, L, generator=g, features=logmel, **kw)[0]}
-    wall = {m: [] for m in ways}
     g = torch.Generator(device=dev)
-    for i in range(args.steps + args.warmup):
-        for m, fn in ways.items():
-            g.manual_seed(i)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            out = fn(g)
-            torch.cuda.synchronize()
-            dt = (time.perf_counter() - t0) * 1e3
-            del out
-            if i >= args.warmup:
-                wall[m].append(dt)
+    ways = {"kaldi_fbank": lambda i: corpus.random_crops(B, L, generator=g, features=kaldi, **kw)[0],
+            "log_mel": lambda i: corpus.random_crops(B, L, generator=g, features=logmel, **kw)[0]}
+    wall = wall_ms(torch, ways, args.steps, args.warmup, before=g.manual_seed)
     step = {"step": "random_crops(64, 32000, sample_rate=16000, mono=True, features=..., check=False)", "files": args.files,
             "seconds": args.seconds, "wall_ms": {m: stats(v) for m, v in wall.items()}}
     corpus.close()
     gpu.close()
-    doc = {"command": "python tools/bench_fbank.py " + " ".join(sys.argv[1:]), "steps": args.steps, "warmup": args.warmup,
+    doc = {"command": command(__file__), "steps": args.steps, "warmup": args.warmup,
            "reps": args.reps, "kaldi": repr(kaldi), "log_mel": repr(logmel), "call": call, "step": step}
-    text = json.dumps(doc, indent=1)
-    print(text, flush=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    emit(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -7,52 +7,37 @@
                with this one: nothing that existed may have moved
   torch        for comparison, what a user writes today on the same crops: torch.stft(center, reflect, periodic Hann) ->
                abs()^2 -> matmul with spec.fb -> clamp(min=floor) -> log
-Wall time of a step: torch.cuda.synchronize() in front of and behind it, the ways alternating inside every step, median and
-p10 .. p90 of --steps steps after --warmup.  Then, over one step's crops, HIP events around --reps back-to-back calls, again
---steps times after --warmup: the alacgpu_logmel_device call alone, and the torch composition alone.  One JSON document,
-printed and written to --out.
+Wall time of a step: _measure.wall_ms, median and p10 .. p90.  Then, over one step's crops, _measure.event_ms, one way after
+the other: the alacgpu_logmel_device call alone, and the torch composition alone.  One JSON document, printed and written to
+--out.
   python tools/bench_features.py [--parent DIR] [--steps 200] [--warmup 20] [--out profiles/corpus_features.json]"""
 import argparse
-import json
-import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from _measure import arguments, command, device, emit, event_ms, inside, load_parent, make_file, stats, wall_ms
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=32)
     ap.add_argument("--seconds", type=float, default=60.0)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--shape", action="append", help="BxSECONDS, repeatable (default 64x2 and 256x1)")
-    ap.add_argument("--parent", help="a built tree of the parent commit: its crops alternate with this tree's")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "corpus_features.json"))
+    arguments(ap, "corpus_features.json", reps=10, parent="a built tree of the parent commit: its crops alternate with this tree's")
     args = ap.parse_args()
     import torch
 
     import alac.net_amd as pkg
     from alac.net_amd import synth
-    from bench_corpus import make_file
-    from bench_resample import load_parent, stats
 
     synth.build()
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda", 0)
+    dev, stream = device(torch)
     rate, R = 44100, 16000
     T = int(args.seconds * rate)
     distinct = [make_file(synth, T, 11 + k) for k in range(2)]
     blobs = [distinct[f % 2] for f in range(args.files)]
     corpus = pkg.Corpus(blobs)
     parent = load_parent(args.parent).Corpus(blobs) if args.parent else None
-    stream = torch.cuda.current_stream(dev)
     spec = pkg.LogMel(R, 400, 160, 80)
     window, basis, fb = spec.device_tables(dev)
     hann = torch.hann_window(spec.n_fft, periodic=True, device=dev)
@@ -78,22 +63,11 @@ def main():
         ways["torch"] = lambda i: compose(corpus.crops(files[i], offs[i], L, **kw)[0])
         ours, theirs = ways["features"](0), ways["torch"](0)
         worst = float((ours - theirs).abs().max())
-        wall = {m: [] for m in ways}
-        for i in range(n_steps):
-            for m, fn in ways.items():
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                out = fn(i)
-                torch.cuda.synchronize()
-                dt = (time.perf_counter() - t0) * 1e3
-                del out
-                if i >= args.warmup:
-                    wall[m].append(dt)
+        wall = wall_ms(torch, ways, args.steps, args.warmup)
         r = {"crops": B, "seconds": seconds, "feature_frames": spec.frames(L), "max_abs_difference_to_torch_in_ln": round(worst, 6),
              "wall_ms": {m: stats(v) for m, v in wall.items()}}
         if parent is not None:
-            p, n = r["wall_ms"]["parent"], r["wall_ms"]["crops"]
-            r["crops_median_inside_parent_p10_p90"] = bool(p["p10"] <= n["median"] <= p["p90"])
+            r["crops_median_inside_parent_p10_p90"] = inside(r["wall_ms"]["parent"], r["wall_ms"]["crops"])
         # the two feature computations alone, over one step's crops
         pcm = corpus.crops(files[0], offs[0], L, **kw)[0]
         out = torch.empty((B, 1, spec.n_mels, spec.frames(L)), dtype=torch.float32, device=dev)
@@ -102,33 +76,20 @@ def main():
             corpus._gpu.logmel_device(pcm, B, 1, L, L, spec.n_fft, spec.hop_length, spec.n_mels, window, basis, fb, spec.log_mode,
                                       spec.floor, out, spec.frames(L), stream=stream.cuda_stream)
 
-        ms = {"logmel_call": [], "torch_composition": []}
-        for name, fn in (("logmel_call", native), ("torch_composition", lambda: compose(pcm))):
-            for rep in range(n_steps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                e0.record(stream)
-                for _ in range(args.reps):
-                    fn()
-                e1.record(stream)
-                e1.synchronize()
-                if rep >= args.warmup:
-                    ms[name].append(e0.elapsed_time(e1) / args.reps)
+        ms = event_ms(torch, stream, {"logmel_call": native, "torch_composition": lambda: compose(pcm)}, args.steps, args.warmup, args.reps,
+                      alternate=False)
         k, c = stats(ms["logmel_call"]), stats(ms["torch_composition"])
         flop = 2.0 * B * spec.frames(L) * (spec.n_fft * 2 * spec.n_bins + spec.n_mels * spec.n_bins)
         r["alone_ms_events_around_reps_calls"] = {"logmel_call": k, "torch_composition": c}
         r["logmel_call_tflops"] = round(flop / k["median"] / 1e9, 2)
         r["logmel_median_below_torch_p10"] = bool(k["median"] < c["p10"])
         results.append(r)
-    doc = {"command": "python tools/bench_features.py " + " ".join(sys.argv[1:]), "files": args.files, "seconds": args.seconds,
+    doc = {"command": command(__file__), "files": args.files, "seconds": args.seconds,
            "steps": args.steps, "warmup": args.warmup, "reps": args.reps, "spec": repr(spec), "results": results}
     corpus.close()
     if parent is not None:
         parent.close()
-    text = json.dumps(doc, indent=1)
-    print(text, flush=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    emit(doc, args.out)
 
 
 if __name__ == "__main__":

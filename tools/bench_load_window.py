@@ -6,25 +6,11 @@ events around the decode call) are taken, and the medians reported.  The crops a
   python tools/bench_load_window.py [--files 128] [--seconds 180] [--crop 2.0] [--rounds 3] [--distinct 2]"""
 import argparse
 import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def make_file(synth, frames, seed):
-    from alac.net_amd.synth import m4a
-
-    n = -(-frames // 4096)
-    d = synth.packet_descs(n, stereo=1)
-    d["n"][-1] = frames - (n - 1) * 4096
-    b = synth.make_batch(d, synth.default_signal(seed))
-    packets = [bytes(b["blob"][int(o):int(o) + int(s)]) for o, s in zip(b["offsets"], b["sizes"])]
-    return m4a.write_m4a(packets, [int(x) for x in d["n"]], sample_size=16, channels=2, sample_rate=44100)
+from _measure import make_file
 
 
 def main():

@@ -1,25 +1,19 @@
 """What noise at a target signal-to-noise ratio costs, per call and per training step --
   call      the alacgpu_mix_device call alone (ctx.mix_device, in place, the ratio given) on [64, 1, 32000] and [16, 1, 480000]
             with random lengths for the signal and the noise, against what a user writes today in torch on the same tensors:
-            masks from the lengths, masked squares and sums, the gain, a gather of the noise at i mod vn and an add.  HIP
-            events around --reps back-to-back calls, --steps times after --warmup: median and p10 .. p90 of the time per call.
+            masks from the lengths, masked squares and sums, the gain, a gather of the noise at i mod vn and an add.
+            _measure.event_ms, one way after the other: median and p10 .. p90 of the time per call.
   step      corpus.random_crops(64, 32000, sample_rate=16000, mono=True, features=spec, check=False) with mix=AddNoise(a second
-            corpus, (5, 20)) and without, the ways alternating inside every step, torch.cuda.synchronize() in front of and
-            behind each: wall time, median and p10 .. p90.  With --parent DIR (a built tree of the parent commit) the call
-            without mix on the parent's package as `parent`, alternating with the others: nothing that existed may have moved.
+            corpus, (5, 20)) and without: _measure.wall_ms, median and p10 .. p90.  With --parent DIR (a built tree of the
+            parent commit) the call without mix on the parent's package as `parent`, alternating with the others: nothing that
+            existed may have moved.
 One JSON document, printed and written to --out.
   python tools/bench_mix.py [--parent DIR] [--steps 200] [--warmup 20] [--out profiles/mix.json]"""
 import argparse
-import json
-import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from _measure import arguments, command, device, emit, event_ms, inside, load_parent, make_file, stats, wall_ms
 
 
 def composition(torch, x, n, ratio, lengths, nlen, out):
@@ -41,25 +35,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=16)
     ap.add_argument("--seconds", type=float, default=30.0)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--parent", help="a built tree of the parent commit: its step without mix alternates with this tree's")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mix.json"))
+    arguments(ap, "mix.json", reps=10, parent="a built tree of the parent commit: its step without mix alternates with this tree's")
     args = ap.parse_args()
     import torch
 
     import alac.net_amd as pkg
     from alac.net_amd import synth
     from alac.net_amd.mix import snr_ratio
-    from bench_corpus import make_file
-    from bench_resample import load_parent, stats
 
     synth.build()
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda", 0)
-    stream = torch.cuda.current_stream(dev)
-    n_steps = args.steps + args.warmup
+    dev, stream = device(torch)
     rng = np.random.default_rng(1)
 
     # ---- the call alone --------------------------------------------------------------------------------------------------------
@@ -76,18 +61,8 @@ def main():
             theirs = lambda: composition(torch, x, n, ratio, lengths, nlen, res_t)
             ours(), theirs()
             close = bool(torch.allclose(res, res_t, rtol=1e-4, atol=1e-5))
-            ms = {"mix_call": [], "torch_composition": []}
-            for way, fn in (("mix_call", ours), ("torch_composition", theirs)):
-                for rep in range(n_steps):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    torch.cuda.synchronize()
-                    e0.record(stream)
-                    for _ in range(args.reps):
-                        fn()
-                    e1.record(stream)
-                    e1.synchronize()
-                    if rep >= args.warmup:
-                        ms[way].append(e0.elapsed_time(e1) / args.reps)
+            ms = event_ms(torch, stream, {"mix_call": ours, "torch_composition": theirs}, args.steps, args.warmup, args.reps,
+                          alternate=False)
             k, c = stats(ms["mix_call"]), stats(ms["torch_composition"])
             least = 4.0 * float(2 * lengths.clamp(max=T).sum() + torch.minimum(lengths, nlen).sum())      # read x and n, write y
             calls.append({"shape": [B, 1, T], "agrees_with_torch": close, "ms_per_call_events_around_reps_calls": {"mix_call": k, "torch_composition": c},
@@ -105,35 +80,21 @@ def main():
     spec = pkg.LogMel(R, 400, 160, 80)
     aug = pkg.AddNoise(noise, (5, 20))
     kw = dict(sample_rate=R, mono=True, features=spec, check=False)
-    ways = {"mix": lambda: corpus.random_crops(B, L, mix=aug, **kw)[0], "without": lambda: corpus.random_crops(B, L, **kw)[0]}
+    ways = {"mix": lambda i: corpus.random_crops(B, L, mix=aug, **kw)[0], "without": lambda i: corpus.random_crops(B, L, **kw)[0]}
     if parent is not None:
         parent_spec = parent_pkg.LogMel(R, 400, 160, 80)
-        ways["parent"] = lambda: parent.random_crops(B, L, sample_rate=R, mono=True, features=parent_spec, check=False)[0]
-    wall = {m: [] for m in ways}
-    for i in range(n_steps):
-        for m, fn in ways.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            out = fn()
-            torch.cuda.synchronize()
-            dt = (time.perf_counter() - t0) * 1e3
-            del out
-            if i >= args.warmup:
-                wall[m].append(dt)
+        ways["parent"] = lambda i: parent.random_crops(B, L, sample_rate=R, mono=True, features=parent_spec, check=False)[0]
+    wall = wall_ms(torch, ways, args.steps, args.warmup)
     step = {"step": "random_crops(64, 32000, sample_rate=16000, mono=True, features=LogMel(16000, 400, 160, 80), check=False)",
             "wall_ms": {m: stats(v) for m, v in wall.items()}}
     if parent is not None:
-        p, w = step["wall_ms"]["parent"], step["wall_ms"]["without"]
-        step["without_median_inside_parent_p10_p90"] = bool(p["p10"] <= w["median"] <= p["p90"])
+        step["without_median_inside_parent_p10_p90"] = inside(step["wall_ms"]["parent"], step["wall_ms"]["without"])
     corpus.close(), noise.close()
     if parent is not None:
         parent.close()
-    doc = {"command": "python tools/bench_mix.py " + " ".join(sys.argv[1:]), "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
+    doc = {"command": command(__file__), "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
            "calls": calls, "step": step}
-    text = json.dumps(doc, indent=1)
-    print(text, flush=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    emit(doc, args.out)
 
 
 if __name__ == "__main__":

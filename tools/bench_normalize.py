@@ -6,8 +6,8 @@
 against
   TopDb                amax over the row -> maximum -> mul -> add (four launches and a temporary)
   MeanVar              a mask from lengths, masked mean, masked var, where (a dozen launches)
-each into a preallocated result.  HIP events around --reps back-to-back calls, --steps times after --warmup: median and
-p10 .. p90 of the time per call.  One JSON document, printed and written to --out.
+each into a preallocated result.  _measure.event_ms, one way after the other: median and p10 .. p90 of the time per call.
+One JSON document, printed and written to --out.
   python tools/bench_normalize.py [--steps 200] [--warmup 20] [--out profiles/normalize.json]
 Kernel times come from a run of their own under the profiler, which this tool only feeds and reads:
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o normalize -- python tools/bench_normalize.py --loop 50
@@ -15,14 +15,10 @@ Kernel times come from a run of their own under the profiler, which this tool on
 import argparse
 import csv
 import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from _measure import arguments, command, device, emit, event_ms, stats
 
 
 def cases(torch, pkg, dev):
@@ -79,12 +75,9 @@ def read_kernel_stats(path):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--loop", type=int, help="only call every case's two ways that many times (the run under the profiler)")
     ap.add_argument("--kernel-stats", help="a rocprofv3 kernel stats CSV of a --loop run: added to --out as kernel_stats")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "normalize.json"))
+    arguments(ap, "normalize.json", reps=10)
     args = ap.parse_args()
     if args.kernel_stats is not None:
         doc = json.load(open(args.out))
@@ -95,11 +88,8 @@ def main():
     import torch
 
     import alac.net_amd as pkg
-    from bench_resample import stats
 
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda", 0)
-    stream = torch.cuda.current_stream(dev)
+    dev, stream = device(torch)
     todo = cases(torch, pkg, dev)
     if args.loop:
         for name, ours, theirs in todo:
@@ -112,27 +102,13 @@ def main():
     for name, ours, theirs in todo:
         a, b = ours().clone(), theirs().clone()
         close = bool(torch.allclose(a, b, rtol=1e-4, atol=1e-4, equal_nan=True))
-        ms = {"normalize": [], "torch_composition": []}
-        for way, fn in (("normalize", ours), ("torch_composition", theirs)):
-            for rep in range(args.steps + args.warmup):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                e0.record(stream)
-                for _ in range(args.reps):
-                    fn()
-                e1.record(stream)
-                e1.synchronize()
-                if rep >= args.warmup:
-                    ms[way].append(e0.elapsed_time(e1) / args.reps)
+        ms = event_ms(torch, stream, {"normalize": ours, "torch_composition": theirs}, args.steps, args.warmup, args.reps, alternate=False)
         k, c = stats(ms["normalize"]), stats(ms["torch_composition"])
         results.append({"case": name, "agrees_with_torch": close, "ms_per_call_events_around_reps_calls": {"normalize": k, "torch_composition": c},
                         "normalize_median_below_torch_p10": bool(k["median"] < c["p10"])})
-    doc = {"command": "python tools/bench_normalize.py " + " ".join(sys.argv[1:]), "steps": args.steps, "warmup": args.warmup,
+    doc = {"command": command(__file__), "steps": args.steps, "warmup": args.warmup,
            "reps": args.reps, "results": results}
-    text = json.dumps(doc, indent=1)
-    print(text, flush=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    emit(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -3,41 +3,20 @@
   (a) native       corpus.crops(files, offsets, L) at the files' rate: the path that must not change.  With --parent DIR (a
                    built tree of the parent commit) the same call on the parent's package, alternating with this one
   (b) 16000_mono   corpus.crops(..., sample_rate=16000, mono=True) and
-      48000        corpus.crops(..., sample_rate=48000) for the same duration; the resample call alone (HIP events around
-                   --reps back-to-back launches over the step's scratch) with its bytes per second from the bytes it reads
-                   (the valid source frames) plus those it writes, and the decode pair alone over the same source windows;
-                   with --parent the parent's resample call over the same scratch too, alternating with this one
+      48000        corpus.crops(..., sample_rate=48000) for the same duration; the resample call alone (_measure.event_ms
+                   around --reps back-to-back launches over the step's scratch) with its bytes per second from the bytes it
+                   reads (the valid source frames) plus those it writes, and the decode pair alone (one call between the
+                   events) over the same source windows, the two alternating inside every repetition, 30 after 5; with
+                   --parent the parent's resample call over the same scratch too, alternating with them, --steps after --warmup
   (c) conv1d       for comparison only, the do-it-yourself route: a native crop of equal duration, then the same filter as a
                    strided torch.nn.functional.conv1d with b output channels (what torchaudio's resample does)
-Wall time of a step: torch.cuda.synchronize() in front of and behind it, the ways alternating inside every step, median and
-p10 .. p90 of --steps steps after --warmup.  One JSON document, printed and written to --out.
+Wall time of a step: _measure.wall_ms, median and p10 .. p90.  One JSON document, printed and written to --out.
   python tools/bench_resample.py [--parent DIR] [--steps 200] [--warmup 20] [--out profiles/corpus_resample.json]"""
 import argparse
-import importlib.util
-import json
-import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-
-def load_parent(tree):
-    """The package of another tree under another name (its own libalacgpu.so next to it)"""
-    d = os.path.join(tree, "alac.net_amd")
-    spec = importlib.util.spec_from_file_location("alac_parent", os.path.join(d, "__init__.py"), submodule_search_locations=[d])
-    mod = importlib.util.module_from_spec(spec)
-    sys.modules["alac_parent"] = mod
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def stats(v):
-    return {"median": round(float(np.median(v)), 4), "p10": round(float(np.percentile(v, 10)), 4), "p90": round(float(np.percentile(v, 90)), 4)}
+from _measure import arguments, command, device, emit, event_ms, inside, load_parent, make_file, stats, wall_ms
 
 
 def conv1d_resample(torch, table, dev):
@@ -61,30 +40,23 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=32)
     ap.add_argument("--seconds", type=float, default=60.0)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--shape", action="append", help="BxSECONDS, repeatable (default 64x2 and 256x1)")
-    ap.add_argument("--parent", help="a built tree of the parent commit: its crops alternate with this tree's")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "corpus_resample.json"))
+    arguments(ap, "corpus_resample.json", reps=20, parent="a built tree of the parent commit: its crops alternate with this tree's")
     args = ap.parse_args()
     import torch
 
     import alac.net_amd as pkg
     from alac.net_amd import synth
     from alac.net_amd.resample import device_table, resample_table, source_window
-    from bench_corpus import make_file
 
     synth.build()
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda", 0)
+    dev, stream = device(torch)
     rate = 44100
     T = int(args.seconds * rate)
     distinct = [make_file(synth, T, 11 + k) for k in range(2)]
     blobs = [distinct[f % 2] for f in range(args.files)]
     corpus = pkg.Corpus(blobs)
     parent = load_parent(args.parent).Corpus(blobs) if args.parent else None
-    stream = torch.cuda.current_stream(dev)
     results = []
     for B, seconds in [tuple(int(x) for x in s.split("x")) for s in (args.shape or ["64x2", "256x1"])]:
         n_steps = args.steps + args.warmup
@@ -104,21 +76,10 @@ def main():
         ways["conv1d_48000"] = lambda i: conv[48000](corpus.crops(files[i], offs[rate][i], L[rate], check=False)[0])
         if parent is not None:
             assert torch.equal(ways["native"](0), ways["parent"](0)), "the native crops differ from the parent's"
-        wall = {m: [] for m in ways}
-        for i in range(n_steps):
-            for m, fn in ways.items():
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                out = fn(i)
-                torch.cuda.synchronize()
-                dt = (time.perf_counter() - t0) * 1e3
-                del out
-                if i >= args.warmup:
-                    wall[m].append(dt)
+        wall = wall_ms(torch, ways, args.steps, args.warmup)
         r = {"crops": B, "seconds": seconds, "wall_ms": {m: stats(v) for m, v in wall.items()}}
         if parent is not None:
-            p, n = r["wall_ms"]["parent"], r["wall_ms"]["native"]
-            r["native_inside_parent_p10_p90"] = bool(p["p10"] <= n["median"] <= p["p90"])
+            r["native_inside_parent_p10_p90"] = inside(r["wall_ms"]["parent"], r["wall_ms"]["native"])
         # the resample call alone over the last step's scratch, and the decode pair over the same source windows
         for R, mono in ((16000, True), (48000, False)):
             a, b, width, d_d0, d_w = tables[R]
@@ -139,24 +100,15 @@ def main():
                 parent._gpu.resample_device(scratch, B, 2, Ls, origin, valid, offs[R][0], L[R], a, b, width, d_d0, d_w, mono, theirs,
                                             stream=stream.cuda_stream)
 
-            timed = [("resample_call", kernel, args.reps), ("decode_pair", decode, 1)]
+            timed, reps = {"resample_call": kernel}, {"resample_call": args.reps, "parent_resample_call": args.reps, "decode_pair": 1}
             if parent is not None:
                 theirs = torch.empty_like(out)
                 parent_kernel()
                 assert torch.equal(out, theirs), "the resample call's output differs from the parent's"
-                timed.insert(1, ("parent_resample_call", parent_kernel, args.reps))
-            ms = {name: [] for name, _, _ in timed}
-            for rep in range(args.steps + args.warmup if parent is not None else 30 + 5):
-                for name, fn, reps in timed:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    torch.cuda.synchronize()
-                    e0.record(stream)
-                    for _ in range(reps):
-                        fn()
-                    e1.record(stream)
-                    e1.synchronize()
-                    if rep >= (args.warmup if parent is not None else 5):
-                        ms[name].append(e0.elapsed_time(e1) / reps)
+                timed["parent_resample_call"] = parent_kernel
+            timed["decode_pair"] = decode
+            steps, warmup = (args.steps, args.warmup) if parent is not None else (30, 5)
+            ms = event_ms(torch, stream, timed, steps, warmup, reps, alternate=True)
             moved = int(valid.sum()) * 2 * 4 + out.numel() * 4
             k = stats(ms["resample_call"])
             r[f"{R}{'_mono' if mono else ''}"] = {
@@ -166,17 +118,14 @@ def main():
             if parent is not None:
                 q = stats(ms["parent_resample_call"])
                 r[f"{R}{'_mono' if mono else ''}"].update({"parent_resample_call_ms": q,
-                                                           "resample_call_inside_parent_p10_p90": bool(q["p10"] <= k["median"] <= q["p90"])})
+                                                           "resample_call_inside_parent_p10_p90": inside(q, k)})
         results.append(r)
-    doc = {"command": "python tools/bench_resample.py " + " ".join(sys.argv[1:]), "files": args.files, "seconds": args.seconds,
+    doc = {"command": command(__file__), "files": args.files, "seconds": args.seconds,
            "steps": args.steps, "warmup": args.warmup, "reps": args.reps, "blob_mb": round(corpus._blob_bytes / 1e6, 1), "results": results}
     corpus.close()
     if parent is not None:
         parent.close()
-    text = json.dumps(doc, indent=1)
-    print(text, flush=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    emit(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -2,27 +2,20 @@
   call      the alacgpu_reverb_device call alone (ctx.reverb_device, in place) on [64, 1, 32000] with responses of K = 8000 and
             K = 16000 frames and random lengths for both, against what a user writes today in torch on the same tensors:
             torch.fft.rfft of both at a common length, their product, irfft, the shift to the largest tap by a gather, the
-            energy gain and a `where` over the lengths.  HIP events around --reps back-to-back calls, the two ways alternating
-            inside every step, --steps times after --warmup: median and p10 .. p90 of the time per call.
+            energy gain and a `where` over the lengths.  _measure.event_ms, the two ways alternating inside every repetition:
+            median and p10 .. p90 of the time per call.
   step      corpus.random_crops(64, 32000, sample_rate=16000, mono=True, features=spec, check=False) with
             reverb=Reverb(a corpus of responses, max_seconds=0.5), without,
-            and with all four stages (reverb=, mix=AddNoise(the corpus itself, (5, 20)), normalize=MeanVar()), the ways
-            alternating inside every step, torch.cuda.synchronize() in front of and behind each: wall time, median and
-            p10 .. p90.  With --parent DIR (a built tree of the parent commit) the same three steps on the parent's package
-            as `parent_...`, alternating with the others: nothing that existed may have moved.
+            and with all four stages (reverb=, mix=AddNoise(the corpus itself, (5, 20)), normalize=MeanVar()):
+            _measure.wall_ms, median and p10 .. p90.  With --parent DIR (a built tree of the parent commit) the same three
+            steps on the parent's package as `parent_...`, alternating with the others: nothing that existed may have moved.
 One JSON document, printed and written to --out.
   python tools/bench_reverb.py [--parent DIR] [--steps 200] [--warmup 20] [--out profiles/reverb.json]"""
 import argparse
-import json
-import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from _measure import arguments, command, device, emit, event_ms, load_parent, make_file, not_above, stats, wall_ms
 
 
 def composition(torch, x, h, lengths, hlen, out):
@@ -48,24 +41,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=16)
     ap.add_argument("--seconds", type=float, default=30.0)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--parent", help="a built tree of the parent commit: its step without reverb alternates with this tree's")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "reverb.json"))
+    arguments(ap, "reverb.json", reps=10, parent="a built tree of the parent commit: its step without reverb alternates with this tree's")
     args = ap.parse_args()
     import torch
 
     import alac.net_amd as pkg
     from alac.net_amd import synth
-    from bench_corpus import make_file
-    from bench_resample import load_parent, stats
 
     synth.build()
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda", 0)
-    stream = torch.cuda.current_stream(dev)
-    n_steps = args.steps + args.warmup
+    dev, stream = device(torch)
     rng = np.random.default_rng(1)
 
     # ---- the call alone --------------------------------------------------------------------------------------------------------
@@ -86,20 +70,8 @@ def main():
             x = x0.clone()                                 # in place, as crops() calls it: the values drift, the work does not
             ours = lambda: ctx.reverb_device(x, x, h, B, 1, 1, T, K, T, K, lengths, hlen, stream=stream.cuda_stream)
             theirs = lambda: composition(torch, x0, h, lengths, hlen, res_t)
-            ms = {"reverb_call": [], "torch_composition": []}
-            for rep in range(n_steps):
-                for way, fn in (("reverb_call", ours), ("torch_composition", theirs)):
-                    if way == "reverb_call":
-                        x.copy_(x0)
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    torch.cuda.synchronize()
-                    e0.record(stream)
-                    for _ in range(args.reps):
-                        fn()
-                    e1.record(stream)
-                    e1.synchronize()
-                    if rep >= args.warmup:
-                        ms[way].append(e0.elapsed_time(e1) / args.reps)
+            ms = event_ms(torch, stream, {"reverb_call": ours, "torch_composition": theirs}, args.steps, args.warmup, args.reps,
+                          alternate=True, before={"reverb_call": lambda: x.copy_(x0)})
             r, c = stats(ms["reverb_call"]), stats(ms["torch_composition"])
             calls.append({"shape": [B, 1, T], "rir_frames": K, "agrees_with_torch": close,
                           "ms_per_call_events_around_reps_calls": {"reverb_call": r, "torch_composition": c},
@@ -118,9 +90,9 @@ def main():
         """The three steps on the package p: with reverb=, without, and with all four stages (the noise from the corpus itself)"""
         spec, aug = p.LogMel(R, 400, 160, 80), p.Reverb(rirs, max_seconds=0.5)
         add, how = p.AddNoise(corpus, (5, 20)), p.MeanVar()
-        return {"reverb": lambda: corpus.random_crops(B, L, reverb=aug, features=spec, **kw)[0],
-                "without": lambda: corpus.random_crops(B, L, features=spec, **kw)[0],
-                "all_stages": lambda: corpus.random_crops(B, L, reverb=aug, mix=add, features=spec, normalize=how, **kw)[0]}
+        return {"reverb": lambda i: corpus.random_crops(B, L, reverb=aug, features=spec, **kw)[0],
+                "without": lambda i: corpus.random_crops(B, L, features=spec, **kw)[0],
+                "all_stages": lambda i: corpus.random_crops(B, L, reverb=aug, mix=add, features=spec, normalize=how, **kw)[0]}
 
     ways = steps(pkg, corpus, rirs)
     parent = parent_rirs = None
@@ -128,34 +100,20 @@ def main():
         parent_pkg = load_parent(args.parent)
         parent, parent_rirs = parent_pkg.Corpus(blobs), parent_pkg.Corpus(rir_files)
         ways.update({"parent_" + m: fn for m, fn in steps(parent_pkg, parent, parent_rirs).items()})
-    wall = {m: [] for m in ways}
-    for i in range(n_steps):
-        for m, fn in ways.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            out = fn()
-            torch.cuda.synchronize()
-            dt = (time.perf_counter() - t0) * 1e3
-            del out
-            if i >= args.warmup:
-                wall[m].append(dt)
+    wall = wall_ms(torch, ways, args.steps, args.warmup)
     step = {"step": "random_crops(64, 32000, sample_rate=16000, mono=True, features=LogMel(16000, 400, 160, 80), check=False)",
             "reverb": "Reverb(4 stereo files of 32000 frames at 44.1 kHz, max_seconds=0.5): K = 8000, taken as one channel",
             "all_stages": "reverb= as above, mix=AddNoise(the corpus itself, (5, 20)), normalize=MeanVar()",
             "wall_ms": {m: stats(v) for m, v in wall.items()}}
     if parent is not None:
         for m in ("reverb", "without", "all_stages"):
-            p, w = step["wall_ms"]["parent_" + m], step["wall_ms"][m]
-            step[m + "_median_inside_parent_p10_p90_or_below"] = bool(w["median"] <= p["p90"])
+            step[m + "_median_inside_parent_p10_p90_or_below"] = not_above(step["wall_ms"]["parent_" + m], step["wall_ms"][m])
     corpus.close(), rirs.close()
     if parent is not None:
         parent.close(), parent_rirs.close()
-    doc = {"command": "python tools/bench_reverb.py " + " ".join(sys.argv[1:]), "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
+    doc = {"command": command(__file__), "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
            "calls": calls, "step": step}
-    text = json.dumps(doc, indent=1)
-    print(text, flush=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    emit(doc, args.out)
 
 
 if __name__ == "__main__":

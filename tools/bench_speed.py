@@ -2,54 +2,38 @@
   call      alacgpu_resample_ratio_rows_device alone (ctx.resample_ratio_rows_device) on [64, 1, Ls] into [64, 1, 32000], Ls the
             source frames 32000 output frames need, at 9 : 10 and 11 : 10 against alac.resample's kernel on the same rows
             (ctx.resample_device with the ratio's table: the table kernel can do those two), and at 3969 : 1600 alone, which
-            no table kernel here can do.  HIP events around --reps back-to-back calls, the two ways alternating inside every
-            step, --steps times after --warmup: median and p10 .. p90 of the time per call.
+            no table kernel here can do.  _measure.event_ms, the ways alternating inside every repetition: median and
+            p10 .. p90 of the time per call.
   step      corpus.random_crops(64, 32000, sample_rate=16000, mono=True, check=False) on 44.1 kHz files with
-            speed=SpeedPerturb() and without, alternating inside every step, torch.cuda.synchronize() in front of and behind
-            each: wall time, median and p10 .. p90.
+            speed=SpeedPerturb() and without: _measure.wall_ms, median and p10 .. p90.
 With --parent DIR (a built tree of the parent commit) the parent's ratio call and the parent's speed step alternate with this
 tree's: the outputs have to be equal, and this tree's median has to lie inside the parent's p10 .. p90.
 One JSON document, printed and written to --out.
   python tools/bench_speed.py [--parent DIR] [--steps 200] [--warmup 20] [--out profiles/speed.json]"""
 import argparse
-import json
-import os
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from _measure import arguments, device, emit, event_ms, inside, load_parent, make_file, stats, wall_ms
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", type=int, default=16)
     ap.add_argument("--seconds", type=float, default=30.0)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--parent", help="a built tree of the parent commit: its ratio call and its speed step alternate with this tree's")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "speed.json"))
+    arguments(ap, "speed.json", reps=10, parent="a built tree of the parent commit: its ratio call and its speed step alternate with this tree's")
     args = ap.parse_args()
     import torch
 
     import alac.net_amd as pkg
     from alac.net_amd import synth
     from alac.net_amd.resample import device_table, filter_width
-    from bench_corpus import make_file
-    from bench_resample import load_parent, stats
 
     synth.build()
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda", 0)
-    stream = torch.cuda.current_stream(dev)
-    n_steps = args.steps + args.warmup
+    dev, stream = device(torch)
     rng = np.random.default_rng(1)
     parent_pkg = load_parent(args.parent) if args.parent else None
-    inside = lambda ms, new, old: bool(ms[old]["p10"] <= ms[new]["median"] <= ms[old]["p90"])
 
     # ---- the call alone --------------------------------------------------------------------------------------------------------
     calls = []
@@ -81,22 +65,12 @@ def main():
                 fn()
             torch.cuda.synchronize()
             assert parent_pkg is None or torch.equal(out, theirs), "the ratio call's output differs from the parent's"
-            ms = {m: [] for m in ways}
-            for rep in range(n_steps):
-                for way, fn in ways.items():
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    torch.cuda.synchronize()
-                    e0.record(stream)
-                    for _ in range(args.reps):
-                        fn()
-                    e1.record(stream)
-                    e1.synchronize()
-                    if rep >= args.warmup:
-                        ms[way].append(e0.elapsed_time(e1) / args.reps)
+            ms = event_ms(torch, stream, ways, args.steps, args.warmup, args.reps, alternate=True)
             doc = {"ratio": [a, b], "width": width, "src_shape": [B, 1, Ls], "out_shape": [B, 1, L],
                    "ms_per_call_events_around_reps_calls": {m: stats(v) for m, v in ms.items()}}
             if parent_pkg is not None:
-                doc["ratio_call_inside_parent_p10_p90"] = inside(doc["ms_per_call_events_around_reps_calls"], "ratio_call", "parent_ratio_call")
+                doc["ratio_call_inside_parent_p10_p90"] = inside(doc["ms_per_call_events_around_reps_calls"]["parent_ratio_call"],
+                                                                 doc["ms_per_call_events_around_reps_calls"]["ratio_call"])
             if table:
                 doc["max_abs_difference_to_table_call"] = float((out - out_t).abs().max())
                 r, t = doc["ms_per_call_events_around_reps_calls"]["ratio_call"], doc["ms_per_call_events_around_reps_calls"]["table_call"]
@@ -110,28 +84,18 @@ def main():
     corpus = pkg.Corpus([distinct[f % 2] for f in range(args.files)])
     kw = dict(sample_rate=R, mono=True, check=False)
     sp = pkg.SpeedPerturb()
-    ways = {"speed": lambda: corpus.random_crops(B, L, speed=sp, **kw)[0], "without": lambda: corpus.random_crops(B, L, **kw)[0]}
+    ways = {"speed": lambda i: corpus.random_crops(B, L, speed=sp, **kw)[0], "without": lambda i: corpus.random_crops(B, L, **kw)[0]}
     if parent_pkg is not None:
         parent_ctx.close()
         parent, psp = parent_pkg.Corpus([distinct[f % 2] for f in range(args.files)]), parent_pkg.SpeedPerturb()
-        ways["parent_speed"] = lambda: parent.random_crops(B, L, speed=psp, **kw)[0]
-        ways["parent_without"] = lambda: parent.random_crops(B, L, **kw)[0]
+        ways["parent_speed"] = lambda i: parent.random_crops(B, L, speed=psp, **kw)[0]
+        ways["parent_without"] = lambda i: parent.random_crops(B, L, **kw)[0]
         for seed in (3, 4):      # one seeded generator on both sides: the same draws, and the same crops of them
             g = [torch.Generator(device=dev).manual_seed(seed) for _ in range(2)]
             for mine, theirs in ((corpus.random_crops(B, L, speed=sp, generator=g[0], **kw), parent.random_crops(B, L, speed=psp, generator=g[1], **kw)),
                                  (corpus.random_crops(B, L, generator=g[0], **kw), parent.random_crops(B, L, generator=g[1], **kw))):
                 assert all(torch.equal(x, y) for x, y in zip(mine, theirs)), "random_crops differs from the parent's"
-    wall = {m: [] for m in ways}
-    for i in range(n_steps):
-        for m, fn in ways.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            out = fn()
-            torch.cuda.synchronize()
-            dt = (time.perf_counter() - t0) * 1e3
-            del out
-            if i >= args.warmup:
-                wall[m].append(dt)
+    wall = wall_ms(torch, ways, args.steps, args.warmup)
     corpus.close()
     if parent_pkg is not None:
         parent.close()
@@ -139,14 +103,11 @@ def main():
             "speed": "speed=SpeedPerturb(): 0.9 / 1.0 / 1.1, that is 3969 : 1600, 441 : 160 (the table kernel) and 4851 : 1600",
             "wall_ms": {m: stats(v) for m, v in wall.items()}}
     if parent_pkg is not None:
-        step.update({f"{m}_inside_parent_p10_p90": inside(step["wall_ms"], m, "parent_" + m) for m in ("speed", "without")})
+        step.update({f"{m}_inside_parent_p10_p90": inside(step["wall_ms"]["parent_" + m], step["wall_ms"][m]) for m in ("speed", "without")})
     shown = [a for i, a in enumerate(sys.argv[1:], 1) if a not in ("--out", "--parent") and sys.argv[i - 1] not in ("--out", "--parent")]     # (where it was written, and where the parent's tree lay, say nothing)
     doc = {"command": " ".join(["python tools/bench_speed.py"] + shown), "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
            "calls": calls, "step": step}
-    text = json.dumps(doc, indent=1)
-    print(text, flush=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    emit(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -11,7 +11,6 @@
 Every comparison is torch.equal; the first that fails ends the run.  One JSON document with the counts, printed and written to --out.
   python tools/compare_parent.py --parent DIR [--out profiles/crop_pipeline_speed_equal.json]"""
 import argparse
-import json
 import os
 import subprocess
 import sys
@@ -19,9 +18,9 @@ import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+from _measure import ROOT, emit, load_parent
+
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 ENTRIES = ("resample_device", "resample_rows_device", "resample_ratio_rows_device")
 KERNEL_TESTS = ["tests/test_resample.py", "tests/test_resample_rows.py", "tests/test_speed.py"]
 
@@ -100,7 +99,6 @@ def main():
 
     import alac.net_amd as pkg
     from alac.net_amd import synth
-    from bench_resample import load_parent
     import test_corpus_resample as tr
     import test_corpus_speed as ts
 
@@ -132,10 +130,7 @@ def main():
             assert torch.equal(pcm, pcm_p) and torch.equal(lengths, lengths_p), f"{name}: differs from the parent's"
         doc.update(crop_calls_equal=len(mine), crop_tensors_equal=2 * len(mine), crops_equal=int(sum(m[1].shape[0] for m in mine)),
                    crop_calls_with_a_nonzero_sample=int(sum(bool(m[1].any()) for m in mine)))
-    text = json.dumps(doc, indent=1)
-    print(text, flush=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
+    emit(doc, args.out)
 
 
 if __name__ == "__main__":

@@ -209,7 +209,9 @@ __device__ __forceinline__ int rice_step(Rice& s, const RiceCfg& c, int remainin
 // reads are address-masked, nothing else is touched).
 // WANT_R: return the residual (else 0).  RAW: return the unsigned code value dv instead of the signed residual
 // (dv >> 1) ^ -(dv & 1) (:225-226) -- the output wave, which has cycles to spare, does that conversion (xq_from_code).
-// What the plain step leaves out, and how the caller finds out (rice_plain_ok) that nothing was missed:
+// This is the NARROW plain step, the hot path; rice_spec_step_any below is the same step (window, prefix, Readbits, slide --
+// the AlacFile.cs lines are cited there) with other history arithmetic.  What the narrow step leaves out, and how the caller
+// finds out (rice_narrow_ok) that nothing was missed:
 //  * s.hist holds H = history + 1536 while the plain steps run (the caller adds and removes the bias): k = 22 - clz(H)
 //    without the addition, and history - ((history * mult) >> 9) is one 24-bit multiply-add and a shift (c.keep_mult = 512 -
 //    mult, c.keep_bias = 1536 * mult + 511) -- exact while H < 2^23 (the sum stays below 2^32) and history * mult < 2^31
@@ -268,194 +270,72 @@ __device__ __forceinline__ void rice_cfg_finish(RiceCfg& c) {
     const int mbits = 32 - __builtin_clz((uint32_t)c.hist_mult | 1u);        // hist_mult < 2^mbits
     c.cfloor = max(max(9, mbits + 1), 22 - c.kmod);
 }
-// The plain step for every history and every kmod (streams the narrow step's arithmetic does not hold: k at its cap, history
-// + 1536 >= 2^23 -- full-scale noise): k capped (:222), the decay term by a full 32-bit multiply.  It leaves out the history
-// clamp for values above 0xFFFF (:229; two instructions) and tracks the largest value in vmax instead; the caller sends a unit
-// with vmax > 0xFFFF to the escape tier, whose step does clamp.
-template <bool WANT_R, bool RAW = false>
-__device__ __forceinline__ int rice_spec_step_wide(Rice& s, const RiceCfg& c, uint32_t ring, uint32_t& xmax,
-                                              int& hmin, uint32_t& vmax) {
+// The speculative step of every other tier: for every history and every kmod (streams the narrow step's arithmetic does not
+// hold: k at its cap, history + 1536 >= 2^23 -- full-scale noise), with k capped (:222) and the decay term by a full 32-bit
+// multiply.  Still straight-line code, checked per unit as above.  With no flag it is the WIDE PLAIN step: it leaves out the
+// history clamp for values above 0xFFFF (:229; two instructions) and tracks the largest value in *vmax instead; the caller
+// sends a unit with vmax > 0xFFFF to an escape tier.  Every flag switches the clamp on, and adds:
+//   ESC   escape codes (nine 1s + rss raw bits, :198-202), for rss <= 23: the raw value then lies inside the 32-bit window
+//         (9 + rss <= 32), and a step still consumes at most 32 bits -- the window slides by at most one dword.  Four
+//         instructions over the plain step.  Loud / noisy 16-bit content lives here: the history clamp keeps k small and
+//         escapes are frequent.
+//   LONG  (with ESC) escape codes for any rss (24-bit streams): the raw value is up to 25 bits and reaches into the next
+//         window; a step consumes up to 9 + 25 = 34 bits, so the window slides by 0, 1 or 2 dwords and a fourth dword (*w3,
+//         loaded by the caller before the unit) is kept prefetched.  With ZRUN, twenty instructions more than ESC alone.
+//   ZRUN  units in which some lane starts inside a zero run or with signModifier pending (digital silence): such a lane
+//         emits 0 without touching the bitstream while zrun > 0, and adds signModifier to its next value (:224).  A lane
+//         in a run stays out of xmax and hmin; the caller recomputes nforce after the unit.
+// Only a NEW run symbol (history < 128 after a value) -- and, without ESC, an escape code -- sends the unit to rice_step.
+template <bool WANT_R, bool RAW, bool ESC, bool ZRUN, bool LONG>
+__device__ __forceinline__ int rice_spec_step_any(Rice& s, const RiceCfg& c, uint32_t ring, uint32_t& xmax, int& hmin,
+                                                  uint32_t* w3, uint32_t* vmax) {
+    static_assert(ESC || !LONG, "LONG widens the escape read");
+    constexpr bool CLAMP = ESC || ZRUN;
+    const bool inrun = ZRUN && s.zrun > 0;
     const uint32_t win = rice_window(s);
+    const uint32_t win2 = LONG ? __builtin_amdgcn_alignbit(s.w1, s.w2, s.cur) : 0u;    // the 32 bits after `win`
     const uint32_t x = (uint32_t)__builtin_clz(~win | 0x00400000u);          // leading ones, capped at 9 (:196)
-    xmax = max(xmax, x);
+    const bool esc = ESC && x > 8u;
+    xmax = max(xmax, inrun ? 0u : x);
     // (hist >> 9) + 3 == (hist + 1536) >> 9 for hist >= 0, so k = min(31 - clz(..), kmod) = min(22 - clz(hist + 1536), kmod)
     const int k = min(22 - __builtin_clz((uint32_t)(s.hist + 1536)), c.kmod);      // :221-222
     const uint32_t e = __builtin_amdgcn_ubfe(win, (uint32_t)(31 - k) - x, (uint32_t)k);  // Readbits(k) (:205)
     const uint32_t m = __builtin_amdgcn_ubfe(0xFFFFFFFFu, 0u, (uint32_t)k);        // (1 << k) - 1
-    const uint32_t v = __umul24(x, m) + (e > 1u ? e - 1u : 0u);                    // :206-208
-    vmax = max(vmax, v);
-    const uint32_t cur2 = s.cur - (x + (uint32_t)k) - (e > 1u ? 1u : 0u);    // bits used: x+1+k, minus the un-read one (:210)
-    int r = 0;
-    if (WANT_R) r = RAW ? (int)v : (int)(v >> 1) ^ -(int)(v & 1u);           // :225-226
-    const int h = s.hist;
-    const int hn = (int)(__umul24(v, (uint32_t)c.hist_mult) + (uint32_t)h) - (wmul(h, c.hist_mult) >> 9);   // :229 without the clamp
-    hmin = min(hmin, hn);
-    const uint32_t a2 = rice_w2_addr(cur2, ring);
-    const bool adv = a2 != s.ra;
-    s.cur = cur2;
-    s.w0 = adv ? s.w1 : s.w0;
-    s.w1 = adv ? s.w2 : s.w1;
-    s.ra = a2;
-    s.w2 = lds_load(a2);
-    s.hist = hn;
-    return r;
-}
-// rice_spec_step plus escape codes (nine 1s + rss raw bits, AlacFile.cs:198-202), for rss <= 23: the raw value then lies
-// inside the 32-bit window (9 + rss <= 32), and a step still consumes at most 32 bits -- the window slides by at most one
-// dword, so this is the plain step plus four instructions (the escape-capable rice_spec_step_full costs twenty more).
-// Loud / noisy 16-bit content lives here.
-template <bool WANT_R, bool RAW = false>
-__device__ __forceinline__ int rice_spec_step_esc(Rice& s, const RiceCfg& c, uint32_t ring, uint32_t& xmax,
-                                                  int& hmin) {
-    const uint32_t win = rice_window(s);
-    const uint32_t x = (uint32_t)__builtin_clz(~win | 0x00400000u);
-    const bool esc = x > 8u;
-    xmax = max(xmax, x);
-    const int k = min(22 - __builtin_clz((uint32_t)(s.hist + 1536)), c.kmod);
-    const uint32_t e = __builtin_amdgcn_ubfe(win, (uint32_t)(31 - k) - x, (uint32_t)k);
-    const uint32_t m = __builtin_amdgcn_ubfe(0xFFFFFFFFu, 0u, (uint32_t)k);
-    const uint32_t vn = __umul24(x, m) + (e > 1u ? e - 1u : 0u);
-    const uint32_t raw = __builtin_amdgcn_ubfe(win, (uint32_t)(23 - c.rss), (uint32_t)c.rss);   // bits 9 .. 9+rss of the window
-    const uint32_t v = esc ? raw : vn;
+    const uint32_t vn = __umul24(x, m) + (e > 1u ? e - 1u : 0u);                   // :206-208
+    uint32_t raw = 0;                                                        // bits 9 .. 9+rss of the stream
+    if constexpr (ESC)
+        raw = LONG ? __builtin_amdgcn_alignbit(win, win2, 23) >> (32 - c.rss)
+                   : __builtin_amdgcn_ubfe(win, (uint32_t)(23 - c.rss), (uint32_t)c.rss);
+    const uint32_t v = (esc ? raw : vn) + (ZRUN ? (uint32_t)s.signmod : 0u);       // :224
+    // bits used: x+1+k, minus the un-read one (:210)
     const uint32_t used = esc ? (uint32_t)(9 + c.rss) : x + (uint32_t)k + (e > 1u ? 1u : 0u);
-    const uint32_t cur2 = s.cur - used;
+    if constexpr (!CLAMP) *vmax = max(*vmax, v);
+    const uint32_t cur2 = inrun ? s.cur : s.cur - used;
     int r = 0;
-    if (WANT_R) r = RAW ? (int)v : (int)(v >> 1) ^ -(int)(v & 1u);
+    if (WANT_R) r = inrun ? 0 : (RAW ? (int)v : (int)(v >> 1) ^ -(int)(v & 1u));   // :225-226
     const int h = s.hist;
-    int hx = (int)(__umul24(v, (uint32_t)c.hist_mult) + (uint32_t)h) - (wmul(h, c.hist_mult) >> 9);
-    asm volatile("" : "+v"(hx));
-    const int hn = (int)v > 0xFFFF ? 0xFFFF : hx;
-    hmin = min(hmin, hn);
-    const uint32_t a2 = rice_w2_addr(cur2, ring);
-    const bool adv = a2 != s.ra;
-    s.cur = cur2;
-    s.w0 = adv ? s.w1 : s.w0;
-    s.w1 = adv ? s.w2 : s.w1;
-    s.ra = a2;
-    s.w2 = lds_load(a2);
-    s.hist = hn;
-    return r;
-}
-// Same, for units in which some lane starts inside a zero run or with signModifier pending (digital
-// silence): such a lane emits 0 without touching the bitstream while zrun > 0, and adds signModifier to
-// its next value.  Still straight-line; only a NEW run symbol (history < 128 after a value) or an escape
-// code sends the unit to rice_step.
-template <bool WANT_R, bool RAW = false>
-__device__ __forceinline__ int rice_spec_step_z(Rice& s, const RiceCfg& c, uint32_t ring, uint32_t& xmax,
-                                                int& hmin) {
-    const bool inrun = s.zrun > 0;
-    const uint32_t win = rice_window(s);
-    const uint32_t x = (uint32_t)__builtin_clz(~win | 0x00400000u);
-    xmax = max(xmax, inrun ? 0u : x);
-    const int k = min(22 - __builtin_clz((uint32_t)(s.hist + 1536)), c.kmod);
-    const uint32_t e = __builtin_amdgcn_ubfe(win, (uint32_t)(31 - k) - x, (uint32_t)k);
-    const uint32_t m = __builtin_amdgcn_ubfe(0xFFFFFFFFu, 0u, (uint32_t)k);
-    const uint32_t v = __umul24(x, m) + (e > 1u ? e - 1u : 0u) + (uint32_t)s.signmod;   // :224
-    const uint32_t cur2 = inrun ? s.cur : s.cur - (x + (uint32_t)k) - (e > 1u ? 1u : 0u);
-    int r = 0;
-    if (WANT_R) r = inrun ? 0 : (RAW ? (int)v : (int)(v >> 1) ^ -(int)(v & 1u));
-    const int h = s.hist;
-    int hx = (int)(__umul24(v, (uint32_t)c.hist_mult) + (uint32_t)h) - (wmul(h, c.hist_mult) >> 9);
-    asm volatile("" : "+v"(hx));
-    const int hv = (int)v > 0xFFFF ? 0xFFFF : hx;
-    hmin = min(hmin, inrun ? 0x7FFFFFFF : hv);
-    const uint32_t a2 = rice_w2_addr(cur2, ring);
-    const bool adv = a2 != s.ra;
-    s.cur = cur2;
-    s.w0 = adv ? s.w1 : s.w0;
-    s.w1 = adv ? s.w2 : s.w1;
-    s.ra = a2;
-    s.w2 = lds_load(a2);
-    s.hist = inrun ? h : hv;
-    s.signmod = inrun ? s.signmod : 0;
-    s.zrun -= inrun ? 1 : 0;
-    return r;
-}
-// Full-featured speculative step: additionally handles, still as straight-line code,
-//   * lanes inside a zero run / with signModifier pending (digital silence): emit 0 without touching the
-//     bitstream while zrun > 0, add signModifier to the next value;
-//   * escape codes (nine 1s + rss raw bits, AlacFile.cs:198-202): loud / noisy content, where the history
-//     clamp (:229) keeps k small and escapes are frequent.  An escape consumes up to 9 + 25 bits, so the
-//     window slides by 0, 1 or 2 dwords per step and a fourth dword (w3) is kept prefetched.
-// Only a NEW run symbol (history < 128 after a value) sends the unit to rice_step.
-template <bool WANT_R, bool RAW = false>
-__device__ __forceinline__ int rice_spec_step_full(Rice& s, uint32_t& w3, const RiceCfg& c, uint32_t ring, uint32_t& xmax,
-                                                   int& hmin) {
-    const bool inrun = s.zrun > 0;
-    const uint32_t win = rice_window(s);
-    const uint32_t win2 = __builtin_amdgcn_alignbit(s.w1, s.w2, s.cur);      // the 32 bits after `win`
-    const uint32_t x = (uint32_t)__builtin_clz(~win | 0x00400000u);
-    const bool esc = x > 8u;
-    xmax = max(xmax, inrun ? 0u : x);
-    const int k = min(22 - __builtin_clz((uint32_t)(s.hist + 1536)), c.kmod);
-    const uint32_t e = __builtin_amdgcn_ubfe(win, (uint32_t)(31 - k) - x, (uint32_t)k);
-    const uint32_t m = __builtin_amdgcn_ubfe(0xFFFFFFFFu, 0u, (uint32_t)k);
-    const uint32_t vn = __umul24(x, m) + (e > 1u ? e - 1u : 0u);
-    const uint32_t raw = __builtin_amdgcn_alignbit(win, win2, 23) >> (32 - c.rss);   // bits 9 .. 9+rss of the stream
-    const uint32_t v = (esc ? raw : vn) + (uint32_t)s.signmod;                        // :224
-    const int used = esc ? 9 + c.rss : (int)(x + (uint32_t)k) + (e > 1u ? 1 : 0);
-    const uint32_t cur2 = inrun ? s.cur : s.cur - (uint32_t)used;             // up to 34 bits: w2 moves by 0, 1 or 2 dwords
-    int r = 0;
-    if (WANT_R) r = inrun ? 0 : (RAW ? (int)v : (int)(v >> 1) ^ -(int)(v & 1u));
-    const int h = s.hist;
-    int hx = (int)(__umul24(v, (uint32_t)c.hist_mult) + (uint32_t)h) - (wmul(h, c.hist_mult) >> 9);
-    asm volatile("" : "+v"(hx));
-    const int hv = (int)v > 0xFFFF ? 0xFFFF : hx;                             // :229 (hx is unused garbage when v is huge)
-    hmin = min(hmin, inrun ? 0x7FFFFFFF : hv);
+    int hn = (int)(__umul24(v, (uint32_t)c.hist_mult) + (uint32_t)h) - (wmul(h, c.hist_mult) >> 9);   // :229 without the clamp
+    if constexpr (CLAMP) {
+        asm volatile("" : "+v"(hn));
+        hn = (int)v > 0xFFFF ? 0xFFFF : hn;                                  // :229 (the sum is unused garbage when v is huge)
+    }
+    hmin = min(hmin, inrun ? 0x7FFFFFFF : hn);
     const uint32_t na = rice_w2_addr(cur2, ring);
-    const bool a1 = na != s.ra;                                               // slid by at least one dword
-    const bool a2 = na == (((s.ra + 8u) & RING_MASK) | ring);                 // slid by two
+    const bool a1 = na != s.ra;                                              // slid by at least one dword
+    const bool a2 = LONG && na == (((s.ra + 8u) & RING_MASK) | ring);        // slid by two
     s.cur = cur2;
     const uint32_t n0 = a2 ? s.w2 : (a1 ? s.w1 : s.w0);
-    const uint32_t n1 = a2 ? w3 : (a1 ? s.w2 : s.w1);
+    const uint32_t n1 = a2 ? *w3 : (a1 ? s.w2 : s.w1);
     s.w0 = n0;
     s.w1 = n1;
     s.ra = na;
     s.w2 = lds_load(na);
-    w3 = lds_load(((na + 4u) & RING_MASK) | ring);
-    s.hist = inrun ? h : hv;
-    s.signmod = inrun ? s.signmod : 0;
-    s.zrun -= inrun ? 1 : 0;
-    return r;
-}
-// rice_spec_step_esc for any rss (24-bit streams: the raw value of an escape is up to 25 bits and reaches into the next
-// window; a step consumes up to 34 bits, so the window slides by 0, 1 or 2 dwords and w3 is kept prefetched, as in
-// rice_spec_step_full) -- but without that step's zero-run / signModifier selects.
-template <bool WANT_R, bool RAW = false>
-__device__ __forceinline__ int rice_spec_step_esc_wide(Rice& s, uint32_t& w3, const RiceCfg& c, uint32_t ring, uint32_t& xmax,
-                                                       int& hmin) {
-    const uint32_t win = rice_window(s);
-    const uint32_t win2 = __builtin_amdgcn_alignbit(s.w1, s.w2, s.cur);
-    const uint32_t x = (uint32_t)__builtin_clz(~win | 0x00400000u);
-    const bool esc = x > 8u;
-    xmax = max(xmax, x);
-    const int k = min(22 - __builtin_clz((uint32_t)(s.hist + 1536)), c.kmod);
-    const uint32_t e = __builtin_amdgcn_ubfe(win, (uint32_t)(31 - k) - x, (uint32_t)k);
-    const uint32_t m = __builtin_amdgcn_ubfe(0xFFFFFFFFu, 0u, (uint32_t)k);
-    const uint32_t vn = __umul24(x, m) + (e > 1u ? e - 1u : 0u);
-    const uint32_t raw = __builtin_amdgcn_alignbit(win, win2, 23) >> (32 - c.rss);
-    const uint32_t v = esc ? raw : vn;
-    const uint32_t used = esc ? (uint32_t)(9 + c.rss) : x + (uint32_t)k + (e > 1u ? 1u : 0u);
-    const uint32_t cur2 = s.cur - used;
-    int r = 0;
-    if (WANT_R) r = RAW ? (int)v : (int)(v >> 1) ^ -(int)(v & 1u);
-    const int h = s.hist;
-    int hx = (int)(__umul24(v, (uint32_t)c.hist_mult) + (uint32_t)h) - (wmul(h, c.hist_mult) >> 9);
-    asm volatile("" : "+v"(hx));
-    const int hn = (int)v > 0xFFFF ? 0xFFFF : hx;
-    hmin = min(hmin, hn);
-    const uint32_t na = rice_w2_addr(cur2, ring);
-    const bool a1 = na != s.ra;
-    const bool a2 = na == (((s.ra + 8u) & RING_MASK) | ring);
-    s.cur = cur2;
-    const uint32_t n0 = a2 ? s.w2 : (a1 ? s.w1 : s.w0);
-    const uint32_t n1 = a2 ? w3 : (a1 ? s.w2 : s.w1);
-    s.w0 = n0;
-    s.w1 = n1;
-    s.ra = na;
-    s.w2 = lds_load(na);
-    w3 = lds_load(((na + 4u) & RING_MASK) | ring);
-    s.hist = hn;
+    if constexpr (LONG) *w3 = lds_load(((na + 4u) & RING_MASK) | ring);
+    s.hist = inrun ? h : hn;
+    if constexpr (ZRUN) {
+        s.signmod = inrun ? s.signmod : 0;
+        s.zrun -= inrun ? 1 : 0;
+    }
     return r;
 }
 #ifndef ALAC_SPEC_UNIT

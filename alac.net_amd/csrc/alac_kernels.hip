@@ -72,12 +72,12 @@ __device__ __forceinline__ T wave_max(T v) {
     return v;
 }
 
-// One speculative unit (SPEC_UNIT samples) of the entropy wave.  Tiers, cheapest first:
-//   1  rice_spec_step       plain values only
-//   2  rice_spec_step_z     + zero runs in progress / signModifier pending   (digital silence)
-//   1E rice_spec_step_esc   plain values and escape codes, raw value <= 23 bits (loud / noisy 16-bit content)
-//      rice_spec_step_esc_wide  the same for wider raw values (24-bit streams; the window slides by up to two dwords)
-//   3  rice_spec_step_full  escape codes of any width together with zero runs / signModifier
+// One speculative unit (SPEC_UNIT samples) of the entropy wave.  Tiers, cheapest first, with the flags of rice_spec_step_any:
+//   1  rice_spec_step  the narrow plain step: plain values only (rice_spec_step_any without a flag: the wide plain step)
+//   2  ZRUN            + zero runs in progress / signModifier pending   (digital silence)
+//   1E ESC             plain values and escape codes, raw value <= 23 bits (loud / noisy 16-bit content)
+//      ESC LONG        the same for wider raw values (24-bit streams; the window slides by up to two dwords)
+//   3  ESC ZRUN LONG   escape codes of any width together with zero runs / signModifier
 // A unit whose lanes met something its tier cannot do is restored from its snapshot and retried higher; a NEW run
 // symbol (history < 128 after a value) is beyond all tiers: the function then returns false with the state
 // restored, and the caller decodes the unit with rice_step.  After an escape was seen the wave stays on the escape
@@ -157,6 +157,34 @@ __device__ __forceinline__ void spec_store(int* q, int ii, int (&acc)[4], int r)
     }
 }
 
+// The steps of a unit: CNT times `step`, a speculative step of any tier, and their queue stores (`acc` is the caller's, one
+// for all tiers of a unit).
+template <int CNT, int QSTRIDE, bool WANT_R, typename Step>
+__device__ __forceinline__ void spec_steps(int* q, int (&acc)[4], Step step) {
+#pragma unroll
+    for (int ii = 0; ii < CNT; ii++) {
+        const int r = step();
+        if (WANT_R) spec_store<QSTRIDE>(q, ii, acc, r);
+    }
+}
+
+// A unit on an escape-capable tier: 1E (for raw values of up to 23 bits, and LONG ones) or, with ZRUN, 3.  An escape code -- a
+// unary prefix above `prefix` -- keeps the wave on these tiers for `hold` more units.
+template <bool WANT_R, int QSTRIDE, bool RAW, bool ZRUN, bool LONG>
+__device__ __forceinline__ void esc_unit(Rice& rs, const Rice& snap, bool parked, TierState& ts, const RiceCfg& c, uint32_t ring,
+                                         int* q, int (&acc)[4], uint32_t& xmax, int& hmin, uint32_t prefix, int hold, SpecStats& st) {
+    uint32_t w3 = LONG ? lds_load(((rs.ra + 4u) & RING_MASK) | ring) : 0u;
+    spec_steps<SPEC_UNIT, QSTRIDE, WANT_R>(
+        q, acc, [&] { return rice_spec_step_any<WANT_R, RAW, /*ESC*/ true, ZRUN, LONG>(rs, c, ring, xmax, hmin, &w3, nullptr); });
+    if (ZRUN) rs.nforce = (rs.zrun > 0 || rs.signmod != 0) ? 0u : 0xFFFFFFFFu;
+    else spec_unpark<WANT_R, QSTRIDE>(rs, snap, parked, xmax, hmin, q);
+    const bool sawesc = __builtin_amdgcn_ballot_w64(xmax > prefix) != 0;
+    ts.full_left = sawesc ? hold : ts.full_left - 1;
+    ts.since = sawesc ? 0 : ts.since + 1;
+    if (ZRUN) SPEC_COUNT(full_units);
+    else SPEC_COUNT(esc_units);
+}
+
 template <bool WANT_R, int QSTRIDE, bool RAW = false>
 __device__ __forceinline__ bool spec_unit(Rice& rs, TierState& ts, const RiceCfg& c, uint32_t ring, int* q, SpecStats& st) {
     const Rice snap = rs;
@@ -175,11 +203,7 @@ __device__ __forceinline__ bool spec_unit(Rice& rs, TierState& ts, const RiceCfg
             // the narrow plain step (rice_spec_step): the hot path of the whole kernel
             uint32_t cmin = 32;
             rs.hist += RICE_PLAIN_BIAS;            // (the narrow step's form of the history)
-#pragma unroll
-            for (int ii = 0; ii < SPEC_UNIT; ii++) {
-                const int r = rice_spec_step<WANT_R, RAW>(rs, c, ring, xmax, hmin, cmin);
-                if (WANT_R) spec_store<QSTRIDE>(q, ii, acc, r);
-            }
+            spec_steps<SPEC_UNIT, QSTRIDE, WANT_R>(q, acc, [&] { return rice_spec_step<WANT_R, RAW>(rs, c, ring, xmax, hmin, cmin); });
             rs.hist -= RICE_PLAIN_BIAS;
             hmin -= RICE_PLAIN_BIAS;
             spec_unpark<WANT_R, QSTRIDE>(rs, snap, parked, xmax, hmin, q);
@@ -200,11 +224,8 @@ __device__ __forceinline__ bool spec_unit(Rice& rs, TierState& ts, const RiceCfg
         }
         if (!special && wide) {
             uint32_t vmax = 0;
-#pragma unroll
-            for (int ii = 0; ii < SPEC_UNIT; ii++) {
-                const int r = rice_spec_step_wide<WANT_R, RAW>(rs, c, ring, xmax, hmin, vmax);
-                if (WANT_R) spec_store<QSTRIDE>(q, ii, acc, r);
-            }
+            spec_steps<SPEC_UNIT, QSTRIDE, WANT_R>(
+                q, acc, [&] { return rice_spec_step_any<WANT_R, RAW, /*ESC*/ false, /*ZRUN*/ false, /*LONG*/ false>(rs, c, ring, xmax, hmin, nullptr, &vmax); });
             spec_unpark<WANT_R, QSTRIDE>(rs, snap, parked, xmax, hmin, q);
             newrun = __builtin_amdgcn_ballot_w64(hmin < 128) != 0;
             // an escape code -- or a value whose history update needs the clamp the plain steps leave out
@@ -216,11 +237,8 @@ __device__ __forceinline__ bool spec_unit(Rice& rs, TierState& ts, const RiceCfg
             if (NARROW_PLAIN) SPEC_COUNT(wide_units);
             if (__builtin_expect(!newrun && !sawesc, 1)) { if (!NARROW_PLAIN) SPEC_COUNT(plain_ok); ts.since++; return true; }
         } else if (special) {
-#pragma unroll
-            for (int ii = 0; ii < SPEC_UNIT; ii++) {
-                const int r = rice_spec_step_z<WANT_R, RAW>(rs, c, ring, xmax, hmin);
-                if (WANT_R) spec_store<QSTRIDE>(q, ii, acc, r);
-            }
+            spec_steps<SPEC_UNIT, QSTRIDE, WANT_R>(
+                q, acc, [&] { return rice_spec_step_any<WANT_R, RAW, /*ESC*/ false, /*ZRUN*/ true, /*LONG*/ false>(rs, c, ring, xmax, hmin, nullptr, nullptr); });
             rs.nforce = (rs.zrun > 0 || rs.signmod != 0) ? 0u : 0xFFFFFFFFu;
             newrun = __builtin_amdgcn_ballot_w64(hmin < 128) != 0;
             sawesc = __builtin_amdgcn_ballot_w64(xmax > 8u) != 0;
@@ -234,42 +252,12 @@ __device__ __forceinline__ bool spec_unit(Rice& rs, TierState& ts, const RiceCfg
         xmax = 0;
         hmin = 0x7FFFFFFF;
     }
-    if (!special && __builtin_amdgcn_ballot_w64(c.rss > 23) == 0) {   // tier 1E (rss is per stream: ask the whole wave)
-#pragma unroll
-        for (int ii = 0; ii < SPEC_UNIT; ii++) {
-            const int r = rice_spec_step_esc<WANT_R, RAW>(rs, c, ring, xmax, hmin);
-            if (WANT_R) spec_store<QSTRIDE>(q, ii, acc, r);
-        }
-        spec_unpark<WANT_R, QSTRIDE>(rs, snap, parked, xmax, hmin, q);
-        const bool sawesc = __builtin_amdgcn_ballot_w64(xmax > (unsigned)ALAC_ESC_PREFIX) != 0;
-        ts.full_left = sawesc ? ts.hold : ts.full_left - 1;
-        ts.since = sawesc ? 0 : ts.since + 1;
-        SPEC_COUNT(esc_units);
-    } else if (!special) {                 // tier 1E for wide raw values (24-bit streams)
-        uint32_t w3 = lds_load(((rs.ra + 4u) & RING_MASK) | ring);
-#pragma unroll
-        for (int ii = 0; ii < SPEC_UNIT; ii++) {
-            const int r = rice_spec_step_esc_wide<WANT_R, RAW>(rs, w3, c, ring, xmax, hmin);
-            if (WANT_R) spec_store<QSTRIDE>(q, ii, acc, r);
-        }
-        spec_unpark<WANT_R, QSTRIDE>(rs, snap, parked, xmax, hmin, q);
-        const bool sawesc = __builtin_amdgcn_ballot_w64(xmax > 8u) != 0;
-        ts.full_left = sawesc ? ts.hold : ts.full_left - 1;
-        ts.since = sawesc ? 0 : ts.since + 1;
-        SPEC_COUNT(esc_units);
-    } else {                               // tier 3
-        uint32_t w3 = lds_load(((rs.ra + 4u) & RING_MASK) | ring);
-#pragma unroll
-        for (int ii = 0; ii < SPEC_UNIT; ii++) {
-            const int r = rice_spec_step_full<WANT_R, RAW>(rs, w3, c, ring, xmax, hmin);
-            if (WANT_R) spec_store<QSTRIDE>(q, ii, acc, r);
-        }
-        rs.nforce = (rs.zrun > 0 || rs.signmod != 0) ? 0u : 0xFFFFFFFFu;
-        const bool sawesc = __builtin_amdgcn_ballot_w64(xmax > 8u) != 0;
-        ts.full_left = sawesc ? FULL_HOLD : ts.full_left - 1;
-        ts.since = sawesc ? 0 : ts.since + 1;
-        SPEC_COUNT(full_units);
-    }
+    if (!special && __builtin_amdgcn_ballot_w64(c.rss > 23) == 0)     // tier 1E (rss is per stream: ask the whole wave)
+        esc_unit<WANT_R, QSTRIDE, RAW, /*ZRUN*/ false, /*LONG*/ false>(rs, snap, parked, ts, c, ring, q, acc, xmax, hmin, ALAC_ESC_PREFIX, ts.hold, st);
+    else if (!special)                     // tier 1E for wide raw values (24-bit streams)
+        esc_unit<WANT_R, QSTRIDE, RAW, /*ZRUN*/ false, /*LONG*/ true>(rs, snap, parked, ts, c, ring, q, acc, xmax, hmin, 8u, ts.hold, st);
+    else                                   // tier 3
+        esc_unit<WANT_R, QSTRIDE, RAW, /*ZRUN*/ true, /*LONG*/ true>(rs, snap, parked, ts, c, ring, q, acc, xmax, hmin, 8u, FULL_HOLD, st);
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(hmin < 128) != 0, 0)) {
         rs = snap;
         SPEC_COUNT(late_run);
@@ -298,11 +286,9 @@ __device__ __forceinline__ bool esc_chunk(Rice& rs, TierState& ts, const RiceCfg
     uint32_t xmax = 0;
     int hmin = 0x7FFFFFFF;
     int acc[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int ii = 0; ii < CNT; ii++) {
-        const int r = rice_spec_step_esc<true, true>(rs, c, ring, xmax, hmin);
-        spec_store<QSTRIDE>(q, ii, acc, r);
-    }
+    spec_steps<CNT, QSTRIDE, true>(q, acc, [&] {
+        return rice_spec_step_any<true, true, /*ESC*/ true, /*ZRUN*/ false, /*LONG*/ false>(rs, c, ring, xmax, hmin, nullptr, nullptr);
+    });
     spec_unpark<true, QSTRIDE, CNT>(rs, snap, parked, xmax, hmin, q);
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(hmin < 128) != 0, 0)) {
         rs = snap;

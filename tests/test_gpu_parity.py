@@ -506,7 +506,7 @@ def test_tiny_batches_and_degenerate_packets(pkg, oracle, synth):
 def test_speculative_tiers_on_full_length_streams(pkg, oracle, synth, is24, content):
     # Full-length packets of equal length keep the entropy wave on its speculative units from the first chunk to the
     # last, so the tier a unit lands on is decided by the content alone:
-    #   loud                         escape codes in most units (rice_spec_step_esc; _esc_wide for 24-bit raw values)
+    #   loud                         escape codes in most units (rice_spec_step_any with ESC; ESC LONG for 24-bit raw values)
     #   one_silent_stream_in_eight   long zero runs in one stream of a wave while the others carry signal (parked streams)
     #   very_quiet                   new run symbols every few samples (units redone by rice_step, run-aware tier)
     count = 32

@@ -77,6 +77,10 @@ SYMBOLS = {
                                         _VP, _VP, C.c_int, C.c_float, _VP, C.c_uint64, _VP]),
     "alacgpu_fbank_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                        _VP, _VP, _VP, C.c_uint32, C.c_float, C.c_float, _VP, C.c_uint64, _VP]),
+    "alacgpu_mfcc_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      C.c_uint32, _VP, _VP, _VP, _VP, _VP, C.c_uint32, C.c_float, C.c_float, C.c_float, _VP, C.c_uint64, _VP]),
+    "alacgpu_deltas_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, _VP,
+                                        C.c_uint32, C.c_uint32, _VP, _VP]),
     "alacgpu_normalize_meanvar_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, C.c_int, C.c_int,
                                                    C.c_float, _VP]),
     "alacgpu_normalize_top_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
@@ -408,6 +412,30 @@ class AlacGpuContext(_Closing):
         rc = lib().alacgpu_fbank_device(self._ctx, _dp(d_src), rows, channels, src_stride, frames, win_length, n_fft, hop, n_mels,
                                         _dp(d_window), _dp(d_basis), _dp(d_fb), flags, preemphasis, scale, _dp(d_out), out_frames,
                                         _VP(stream))
+        _check(rc, self._ctx)
+
+    def mfcc_device(self, d_src, rows, channels, src_stride, frames, win_length, n_fft, hop, n_mels, n_ceps, d_window, d_basis, d_fb,
+                    d_dct, d_lifter, flags, preemphasis, scale, energy_floor, d_out, out_frames, stream=0):
+        """alacgpu_mfcc_device: Kaldi's MFCC features of d_src (float32 device tensor, planar [rows, channels, src_stride], the
+        first `frames` of a plane are signal) into d_out (float32 [rows, channels, n_ceps, out_frames], out_frames as
+        mfcc.KaldiMfcc.frames gives it, every element written) with fbank_device's three tables for n_mels filters, d_dct
+        [n_ceps, n_mels] and d_lifter [n_ceps] (mfcc.KaldiMfcc builds them); flags: 1 snip_edges, 2 remove_dc_offset,
+        4 use_power, 16 use_energy, 32 raw_energy.  Asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_mfcc_device(self._ctx, _dp(d_src), rows, channels, src_stride, frames, win_length, n_fft, hop, n_mels, n_ceps,
+                                       _dp(d_window), _dp(d_basis), _dp(d_fb), _dp(d_dct), _dp(d_lifter), flags, preemphasis, scale,
+                                       energy_floor, _dp(d_out), out_frames, _VP(stream))
+        _check(rc, self._ctx)
+
+    def deltas_device(self, d_src, d_out, rows, channels, n_feats, src_stride, out_stride, line_len, d_lengths, order, window, d_scales,
+                      stream=0):
+        """alacgpu_deltas_device: the features d_src (float32 device tensor [rows, channels, n_feats, src_stride], the first
+        line_len of a line are frames) and their deltas of order 1 .. order into d_out (float32 [rows, channels,
+        (order + 1) * n_feats, out_stride], apart from d_src) with the scales d_scales (deltas.Deltas builds them), the clamp of
+        every order into the first len = min(max(d_lengths[row], 0), line_len) frames; zeros behind them.  d_lengths: an int64
+        device tensor [rows], or None for line_len.  deltas.py states the arithmetic.  One launch, asynchronous on `stream`
+        (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_deltas_device(self._ctx, _dp(d_src), _dp(d_out), rows, channels, n_feats, src_stride, out_stride, line_len,
+                                         _dp(d_lengths), order, window, _dp(d_scales), _VP(stream))
         _check(rc, self._ctx)
 
     def normalize_meanvar_device(self, d_src, d_out, rows, lines_per_row, line_stride, line_len, d_valid, centre, scale, eps, stream=0):
@@ -1035,6 +1063,9 @@ from .resample import resample, resample_host, resample_table, source_window  # 
 from .features import LogMel, log_mel, logmel_host, logmel_host_f32, mel_filterbank  # noqa: E402
 # ---- Kaldi filterbank features of crops and tensors (alacgpu_fbank_device) ----------------------------------------------------------
 from .fbank import KaldiFbank, fbank, fbank_host, fbank_host_f32, fbank_lengths, kaldi_mel_banks, kaldi_window  # noqa: E402
+# ---- Kaldi MFCC features of crops and tensors (alacgpu_mfcc_device) and delta features behind any features (alacgpu_deltas_device) --
+from .mfcc import KaldiMfcc, kaldi_dct, kaldi_lifter, mfcc, mfcc_host, mfcc_host_f32  # noqa: E402
+from .deltas import Deltas, add_deltas, delta_scales, deltas_host, deltas_host_f32  # noqa: E402
 
 # ---- normalised crops and features (alacgpu_normalize_meanvar_device, alacgpu_normalize_top_device) ------------------------------
 from .normalize import MeanVar, TopDb, normalize, normalize_host, normalize_host_f32  # noqa: E402

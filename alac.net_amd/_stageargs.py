@@ -1,7 +1,7 @@
 """What the stage calls behind the crops -- `reverb`, `mix`, `log_mel`, `normalize`, `spec_augment` -- share in front of their one library
 call: the immutable specification base (`_Spec`, `_f32_finite`), the lengths on both sides (`_lengths_host`,
 `_lengths_device`), the layouts a kernel takes (`_lines`, `_planes`, `_span`), the context of a tensor's device
-(`_device_context`), the tree of halves of the float32 twins (`_tree`), and `_signal_and_companion`: the one check of a
+(`_device_context`), the tree of halves and the exact fused multiply-add of the float32 twins (`_tree`, `_fma32`), and `_signal_and_companion`: the one check of a
 float32 signal [B, C, T] with a companion [B, C or 1, T'], two optional lengths and an `out`, which is all of `_mix` and
 `_reverb` but their library call.  A new stage takes what it needs from here, never from another stage's module.
 """
@@ -48,6 +48,21 @@ def _tree(q):
         q = (q[..., :h] + q[..., h:2 * h]).astype(np.float32)
         h //= 2
     return q[..., 0]
+
+
+def _fma32(x, y, z):
+    """fma(x, y, z) of float32 arrays, exactly: the product is exact in float64, the sum is rounded to odd there (TwoSum tells
+    which way the exact sum lies), and 53 bits rounded to odd round to float32 as the exact value does"""
+    p = np.asarray(x, dtype=np.float32).astype(np.float64) * np.asarray(y, dtype=np.float32).astype(np.float64)
+    z = np.asarray(z, dtype=np.float32).astype(np.float64)
+    p, z = np.broadcast_arrays(p, z)
+    s = p + z
+    t = s - p
+    err = (p - (s - t)) + (z - t)
+    bits = np.ascontiguousarray(s).view(np.int64)
+    fix = (err != 0) & ((bits & 1) == 0)
+    bits = np.where(fix, bits + np.where((err > 0) == (s > 0), 1, -1), bits)
+    return bits.view(np.float64).astype(np.float32)
 
 
 def _lengths_host(name, lengths, B, T):

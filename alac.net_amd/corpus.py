@@ -20,7 +20,7 @@ states the filter) resamples every crop out of it.
 `crops(..., reverb=, mix=, features=, normalize=)` runs up to four stages behind the waveform, and `crops` is the one place
 that lists them: the refusals of all of them, the crops the second corpora make (`Corpus._companion_crops`: the noise of an
 AddNoise, then the impulse responses of a Reverb, each cropped by its own corpus at the rate of the crops), the waveform once
-(`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_logmel_device (or alacgpu_fbank_device) and
+(`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_logmel_device (or alacgpu_fbank_device or alacgpu_mfcc_device), alacgpu_deltas_device and
 the normalisation (reverb.py, mix.py, features.py and normalize.py state the arithmetic), each only if asked for.
 
 `crops(..., speed=)` plays every crop at a drawn factor in front of all that (the same method, speed.py): the step of a corpus
@@ -41,7 +41,9 @@ from . import (MAX_FRAME, ST_OK, ST_UNSUPPORTED_ELEMENT, ST_UNSUPPORTED_PREDTYPE
                _Closing, _check, _check_batch_args, _compact_slots, _dp, _encode_slots, _frame_count, _status_text, _torch_dtype,
                _VP, _write_file, lib, make_cfgs)
 from .augment import LDS_MAX as _WARP_MAX, _check_draws, _how, _spec_augment
+from .deltas import Deltas, _add_deltas
 from .fbank import KaldiFbank
+from .mfcc import KaldiMfcc
 from .features import LogMel
 from .mix import AddNoise, _mix, snr_ratio
 from .normalize import MeanVar, TopDb, _normalize
@@ -51,6 +53,7 @@ from .speed import MAX_WIDTH as _SPEED_MAX_WIDTH, SpeedPerturb, ratio as _speed_
 PAD_CFG = 0xFFFF        # a padding entry's cfg_idx: never a row of the context, so the kernels switch the entry off
 MAX_CFGS = 65535
 _NEEDS_RATE = "the files of this corpus differ in sample rate: crops need sample_rate="
+_FEATURES = (LogMel, KaldiFbank, KaldiMfcc)              # what crops(features=) takes
 # crops(mix=) and crops(reverb=) for `Corpus._second_corpus`: the specification's class, its attribute that holds the second
 # corpus, how many tensors its draw() returns and what their dtypes have to be, and the nouns of the messages
 _MIX = dict(arg="mix", spec=AddNoise, corpus="noise", theirs="the noise corpus", they="the noise",
@@ -382,6 +385,7 @@ class Corpus(_Closing):
         self._stage_room, self._stage_entries, self._stage_bytes = 0, 0, 0
         self._rs_scratch = None                           # crops at another rate: the decoded source crops
         self._ft_scratch = None                           # crops(features=): the crops the feature kernel reads
+        self._delta_scratch = None                        # crops(deltas=): the features the delta kernel reads
         self._mix_scratch = None                          # crops(mix=): the noise crops, whichever corpus makes them
         self._reverb_scratch = None                       # crops(reverb=): the impulse responses of the crops
         self._rates, self._windows = {}, {}               # `_rate` per (target rate, factors); `_window` per (rate or None, L, factors)
@@ -521,7 +525,7 @@ class Corpus(_Closing):
         if getattr(self, "_gpu", None) is not None:
             self._gpu.close()
             self._gpu = None
-            self._blob = self._plan = self._stage = self._stage_plan = self._rs_scratch = self._ft_scratch = self._mix_scratch = self._reverb_scratch = None
+            self._blob = self._plan = self._stage = self._stage_plan = self._rs_scratch = self._ft_scratch = self._delta_scratch = self._mix_scratch = self._reverb_scratch = None
         self._free_pinned()
 
     @property
@@ -639,7 +643,7 @@ class Corpus(_Closing):
         return torch.from_numpy(f.astype(np.int32)).to(self._dev), torch.from_numpy(o).to(self._dev), True
 
     def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True, features=None, normalize=None, mix=None,
-              reverb=None, speed=None, augment=None, sample_rate=None, mono=False):
+              reverb=None, speed=None, deltas=None, augment=None, sample_rate=None, mono=False):
         """Decode crop b = frames frame_offsets[b] .. + num_frames of file files[b] for every b in ONE launch pair: returns
         (pcm [B, C, num_frames] on the device, zero behind lengths[b]; lengths [B], a DEVICE int64 tensor: min(num_frames,
         T_f - offset)).  float32 (default) or int32, as `load`.  files / frame_offsets: sequences, numpy arrays or torch
@@ -663,8 +667,9 @@ class Corpus(_Closing):
         the call without speed=.  Every stage behind it sees the perturbed waveform.  ValueError: int32 crops, a corpus of
         more than 2 channels, draws that are not an integer tensor [B] on the corpus's device.
 
-        The five stages behind the waveform go by keyword, as sample_rate and mono do, and run in this order whichever are
-        given, in place, by the corpus's own context on the same stream; lengths, `check` and last_status() are those of the
+        The six stages behind the waveform go by keyword, as sample_rate and mono do, and run in this order whichever are
+        given -- reverb, mix, features, deltas, normalize, augment --, in place but for the features and the deltas, by the
+        corpus's own context on the same stream; lengths, `check` and last_status() are those of the
         call without them (with check=True a second corpus's own check runs too, and first).  ValueError before any device
         work for what a stage cannot take.
 
@@ -679,13 +684,20 @@ class Corpus(_Closing):
         lengths).  The noise and the responses are cropped by their own corpus's `crops` at the rate of the crops, as one
         channel when its channel count is not theirs, into scratches THIS corpus keeps: a second corpus may be this one.
 
-        features: a features.LogMel or a fbank.KaldiFbank -- the crops' log-mel or Kaldi fbank features instead of their PCM:
-        the waveform goes into a float32 scratch the corpus keeps and ONE alacgpu_logmel_device or alacgpu_fbank_device call
-        turns every row, the zeros behind its length included, into features.  Returns (feats float32 [B, 1 if mono else C,
+        features: a features.LogMel, a fbank.KaldiFbank or a mfcc.KaldiMfcc -- the crops' log-mel, Kaldi fbank or Kaldi MFCC
+        features instead of their PCM (n_mels below is then the transform's line count: a KaldiMfcc's n_ceps):
+        the waveform goes into a float32 scratch the corpus keeps and ONE alacgpu_logmel_device, alacgpu_fbank_device or
+        alacgpu_mfcc_device call turns every row, the zeros behind its length included, into features.  Returns (feats float32 [B, 1 if mono else C,
         n_mels, features.frames(num_frames)], feat_lengths [B] int64 on the device: features.lengths(lengths) -- lengths // hop
         + 1 for a LogMel, fbank.fbank_lengths for a KaldiFbank --, -1 where lengths is -1); `out` is then the features tensor.
         ValueError: a spec.sample_rate that is not the rate of the crops, a dtype other than float32, num_frames below
         features.min_frames (n_fft // 2 + 1 for a LogMel; what gives no frame for a KaldiFbank).
+
+        deltas: a deltas.Deltas -- Kaldi's add-deltas behind the features: the features go into a second scratch the corpus
+        keeps and ONE alacgpu_deltas_device call writes feats [B, 1 if mono else C, (order + 1) * n_mels, frames] (`out` is
+        then that tensor); feat_lengths are unchanged.  Bit for bit deltas.add_deltas(what the call returns without it, deltas,
+        feat_lengths): a crop outside the corpus keeps its features as computed and gets zero deltas.  The stages behind it
+        see (order + 1) * n_mels lines.  ValueError: no features=.
 
         normalize: a normalize.MeanVar -- every line over its valid elements: lengths for PCM, feat_lengths for features, so a
         crop outside the corpus is zeros -- or a normalize.TopDb -- every crop of features, or every channel of it with
@@ -717,15 +729,20 @@ class Corpus(_Closing):
             if features is None and not _is_f32(torch, dtype):
                 raise ValueError("a MeanVar normalises float32 crops")
         if features is not None:
-            if not isinstance(features, (LogMel, KaldiFbank)):
-                raise ValueError(f"features must be a features.LogMel or a fbank.KaldiFbank, not {features!r} (sample_rate= and mono= "
-                                 f"go by keyword)")
+            if not isinstance(features, _FEATURES):
+                raise ValueError(f"features must be a features.LogMel or a fbank.KaldiFbank or a mfcc.KaldiMfcc, not {features!r} "
+                                 f"(sample_rate= and mono= go by keyword)")
             if rate is None:
                 raise ValueError(_NEEDS_RATE)
             if features.sample_rate != rate:
                 raise ValueError(f"features for {features.sample_rate} Hz, crops at {rate} Hz")
             if not _is_f32(torch, dtype):
                 raise ValueError("features are computed from float32 crops")
+        if deltas is not None:
+            if not isinstance(deltas, Deltas):
+                raise ValueError(f"deltas must be a deltas.Deltas, not {deltas!r}")
+            if features is None:
+                raise ValueError("Deltas are derivatives of features: they need features=")
         if augment is not None:
             augment = _how(augment, "augment")
             if features is None:
@@ -744,7 +761,10 @@ class Corpus(_Closing):
                     augment = (augment[0], tuple(_check_draws(augment[1], B, self._dev)))
                 if augment[0].time_warp and features.frames(L) > _WARP_MAX:
                     raise ValueError(f"features of {features.frames(L)} frames: a time warp takes at most {_WARP_MAX}")
-            feats = self._out(out, (B, Co, features.n_mels, features.frames(L)), torch.float32, zero=False)
+            lines = features.n_mels if deltas is None else deltas.lines(features.n_mels)
+            feats = self._out(out, (B, Co, lines, features.frames(L)), torch.float32, zero=False)
+            if deltas is not None:      # the features into a scratch, their deltas into what the call returns
+                stacked, feats = feats, self._scratch("_delta_scratch", (B, Co, features.n_mels, features.frames(L)))
             out = self._scratch("_ft_scratch", (B, Co, L))
         # 2. the companion crops, by the second corpora's own `crops`: the noise, then the responses
         if mix is not None:
@@ -769,6 +789,8 @@ class Corpus(_Closing):
             if B:
                 features.launch(self._gpu, res, B, Co, L, L, feats, torch.cuda.current_stream(self._dev).cuda_stream)
             res, lengths = feats, features.lengths(lengths)
+        if deltas is not None:
+            res = _add_deltas(ctx, res, deltas, lengths, stacked)
         if normalize is not None:
             _normalize(ctx, res, normalize, lengths, res)
         if augment is not None:
@@ -1095,12 +1117,12 @@ class Corpus(_Closing):
         return out, lengths
 
     def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True, features=None, normalize=None,
-                     mix=None, reverb=None, speed=None, augment=None, sample_rate=None, mono=False):
+                     mix=None, reverb=None, speed=None, deltas=None, augment=None, sample_rate=None, mono=False):
         """`batch` crops of num_frames frames drawn on the device: files uniform over the corpus, the first frame uniform in
         0 .. max(T_f - num_frames, 0).  generator: a torch.Generator (of the corpus's device, or of the CPU: then the draws are
         made there and uploaded).  Returns (pcm, lengths, files, frame_offsets), the draws as device int64 tensors.
         sample_rate / mono as for `crops`: the frames, T_f included, then count at sample_rate.  features as for `crops`:
-        (feats, feat_lengths, files, frame_offsets).  normalize as for `crops`.  mix as for `crops`; an AddNoise is drawn from
+        (feats, feat_lengths, files, frame_offsets).  deltas and normalize as for `crops`.  mix as for `crops`; an AddNoise is drawn from
         `generator`, behind the call's own two draws (AddNoise.draw states its four).  reverb as for `crops`; a Reverb is
         drawn from `generator` behind those (Reverb.draw states its two).  augment as for `crops`; a SpecAugment is drawn from
         `generator` behind those, for the feat_lengths the call returns (augment.py states its draws).  speed as for `crops`;
@@ -1121,6 +1143,8 @@ class Corpus(_Closing):
             augment = _how(augment, "augment")
             if features is None:
                 raise ValueError("a SpecAugment masks log-mel features: it needs features=")
+        if deltas is not None and features is None:
+            raise ValueError("Deltas are derivatives of features: they need features=")
         dev = generator.device if generator is not None else self._dev
         files = torch.randint(0, self.num_files, (B,), generator=generator, device=dev, dtype=torch.int64).to(self._dev)
         u = torch.rand(B, generator=generator, device=dev, dtype=torch.float64).to(self._dev)
@@ -1143,11 +1167,13 @@ class Corpus(_Closing):
             mix = (mix[0], mix[0].draw(B, L, sample_rate=rate, generator=generator))
         if reverb is not None and reverb[1] is None:
             reverb = (reverb[0], reverb[0].draw(B, generator=generator))
-        if augment is not None and augment[1] is None and isinstance(features, (LogMel, KaldiFbank)):
+        if augment is not None and augment[1] is None and isinstance(features, _FEATURES):
             feat_lengths = features.lengths((ends - offs).clamp(max=L))
-            augment = (augment[0], augment[0].draw(features.n_mels, feat_lengths, generator=generator))
+            lines = deltas.lines(features.n_mels) if isinstance(deltas, Deltas) else features.n_mels
+            augment = (augment[0], augment[0].draw(lines, feat_lengths, generator=generator))
         pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,
-                                  features=features, normalize=normalize, mix=mix, reverb=reverb, augment=augment, speed=speed)
+                                  features=features, normalize=normalize, mix=mix, reverb=reverb, augment=augment, speed=speed,
+                                  deltas=deltas)
         return pcm, lengths, files, offs
 
     def last_staged_bytes(self):

@@ -1,6 +1,6 @@
 // alac_features.h -- the fused STFT + mel kernels: the launch parameters and the LDS layout, shared with the C ABI
-// (alacgpu_stages.hip), and the tile body (alac_stft_mel_tile) that the log-mel kernel (alac_features.hip) and the Kaldi fbank
-// kernel (alac_fbank.hip, alac_fbank.h) are both made of.  A kernel supplies what is its own -- how a sample of the span is
+// (alacgpu_stages.hip), and the tile body (alac_stft_mel_tile) that the log-mel kernel (alac_features.hip), the Kaldi fbank
+// kernel (alac_fbank.hip, alac_fbank.h) and the Kaldi MFCC kernel (alac_mfcc.hip, alac_mfcc.h) are made of.  A kernel supplies what is its own -- how a sample of the span is
 // read, the B operand of a tap, what becomes of a bin's power, what becomes of a mel sum -- as lambdas, which inline; the loop
 // over K, its remainder, the scatter of D and the mel sums exist here and nowhere else.
 //
@@ -63,7 +63,7 @@ __host__ __device__ inline uint32_t alac_features_tile(uint32_t taps, uint32_t h
 __host__ __device__ inline uint32_t alac_features_skew(uint32_t hop) { return (hop & 1u) ? 0u : 1u; }
 
 // LDS: the window, the mel sums, the power of a round of bin blocks, what the kernel keeps of its own (`extra` floats: none
-// for log-mel, the means of the tile's frames for fbank), the skewed span
+// for log-mel, the means of the tile's frames for fbank, the means and the energies for MFCC), the skewed span
 struct alac_features_lds {
     uint32_t window, mel, power, extra, span;   // floats of each part, in this order
     __host__ __device__ size_t bytes() const { return sizeof(float) * ((size_t)window + mel + power + extra + span); }
@@ -166,10 +166,11 @@ struct alac_stft_mel_tile {
         __syncthreads();
     }
 
-    // The rounds and the store.  tap(n, q, r): the B operand of tap n = q hop + r of the lane's frame (called for lanes with a
-    // frame and n < taps only); power(re, im): what a bin adds to the mel sums; finish(v): what is stored for a mel sum v.
-    template <uint32_t AHEAD, typename Tap, typename Power, typename Finish>
-    __device__ __forceinline__ void transform(Tap tap, Power power, Finish finish) const {
+    // The rounds, which leave the finished mel sums in LDS (mel[m * ALAC_FEATURES_TILE + t], behind a barrier; thread (m, t)
+    // wrote the sum it owns).  tap(n, q, r): the B operand of tap n = q hop + r of the lane's frame (called for lanes with a
+    // frame and n < taps only); power(re, im): what a bin adds to the mel sums.
+    template <uint32_t AHEAD, typename Tap, typename Power>
+    __device__ __forceinline__ void rounds(Tap tap, Power power) const {
         const uint32_t taps = p.taps, hop = p.hop, n_mels = p.n_mels;
         const uint32_t ldb = 2u * n_bins;
         const uint32_t n_blocks = (n_bins + ALAC_FEATURES_BLOCK - 1u) / ALAC_FEATURES_BLOCK;
@@ -254,12 +255,23 @@ struct alac_stft_mel_tile {
             }
             __syncthreads();
         }
+    }
 
-        // (a thread reads the sums it wrote itself)
+    // The store: finish(v) is what is stored for a mel sum v (a thread reads the sums it wrote itself)
+    template <typename Finish>
+    __device__ __forceinline__ void store(Finish finish) const {
+        const uint32_t n_mels = p.n_mels;
         if (frame_ok) {
             float* const out = p.out + plane * n_mels * p.out_frames + t0 + t;
             for (uint32_t m = tid >> 5; m < n_mels; m += ALAC_FEATURES_THREADS / 32u)
                 out[(uint64_t)m * p.out_frames] = finish(mel[m * ALAC_FEATURES_TILE + t]);
         }
+    }
+
+    // What the log-mel and the fbank kernel do: the rounds, then the store
+    template <uint32_t AHEAD, typename Tap, typename Power, typename Finish>
+    __device__ __forceinline__ void transform(Tap tap, Power power, Finish finish) const {
+        rounds<AHEAD>(tap, power);
+        store(finish);
     }
 };

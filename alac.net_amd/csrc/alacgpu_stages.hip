@@ -1,5 +1,5 @@
 // alacgpu_stages.hip -- C ABI of include/alacgpu.h, the stages around the decode: the crop planner, the scan with the packet
-// compaction and staging, the resamplers, log-mel, Kaldi fbank, the reverberation, the noise mix, the normalisations, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
+// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the reverberation, the noise mix, the normalisations, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
 // their own scratch; the decode path is alacgpu_api.hip.  No CPU fallback here either: every stage is its kernels.
 #include <algorithm>
 #include <cmath>
@@ -9,6 +9,8 @@
 #include "alac_resample.h"
 #include "alac_features.h"
 #include "alac_fbank.h"
+#include "alac_mfcc.h"
+#include "alac_deltas.h"
 #include "alac_normalize.h"
 #include "alac_augment.h"
 #include "alac_mix.h"
@@ -194,7 +196,7 @@ bool apart(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
     return (uintptr_t)a + a_bytes <= (uintptr_t)b || (uintptr_t)b + b_bytes <= (uintptr_t)a;
 }
 
-// What alacgpu_logmel_device and alacgpu_fbank_device do behind their own argument checks: the grid of tiles, the LDS layout
+// What alacgpu_logmel_device, alacgpu_fbank_device and alacgpu_mfcc_device do behind their own argument checks: the grid of tiles, the LDS layout
 // (with `extra` floats of the kernel's own), the shared fields of p and the launch of `kernel`, whose argument p is
 template <typename Params>
 int launch_stft_mel(alacgpu_ctx* ctx, const void* kernel, Params& p, uint32_t extra, const void* d_src, uint32_t rows,
@@ -469,6 +471,72 @@ int alacgpu_fbank_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uin
     p.scale = scale;
     return launch_stft_mel(ctx, (const void*)alac_fbank_kernel, p, ALAC_FBANK_LDS_EXTRA, d_src, rows, channels, src_stride, frames,
                            win_length, n_fft, hop, n_mels, d_window, d_basis, d_fb, d_out, out_frames, hip_stream);
+}
+
+int alacgpu_mfcc_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride, uint64_t frames,
+                        uint32_t win_length, uint32_t n_fft, uint32_t hop, uint32_t n_mels, uint32_t n_ceps, const void* d_window,
+                        const void* d_basis, const void* d_fb, const void* d_dct, const void* d_lifter, uint32_t flags,
+                        float preemphasis, float scale, float energy_floor, void* d_out, uint64_t out_frames, void* hip_stream) {
+    if (!ctx || !args_ok({{d_src, 4}, {d_window, 4}, {d_basis, 4}, {d_fb, 4}, {d_dct, 4}, {d_lifter, 4}, {d_out, 4}})) return ALACGPU_ERR_BAD_ARG;
+    if (win_length < ALAC_FBANK_MIN_WIN || win_length > ALAC_FBANK_MAX_WIN || n_fft < win_length || n_fft > ALAC_FBANK_MAX_NFFT ||
+        hop < 1 || hop > win_length || n_mels < 1 || n_mels > ALAC_FEATURES_MAX_MELS || n_ceps < 1 || n_ceps > n_mels || channels == 0 ||
+        (flags & ~(uint32_t)ALAC_MFCC_FLAGS) || ((flags & ALAC_MFCC_RAW_ENERGY) && !(flags & ALAC_MFCC_USE_ENERGY)))
+        return ALACGPU_ERR_BAD_ARG;
+    if (!(preemphasis >= 0.0f && preemphasis <= 1.0f) || !std::isfinite(scale) || scale == 0.0f || !(energy_floor >= 0.0f) ||
+        !std::isfinite(energy_floor))
+        return ALACGPU_ERR_BAD_ARG;
+    if (frames < 1 || frames > src_stride || frames > (1ull << 61) ||
+        out_frames != alac_fbank_frames(frames, win_length, hop, (flags & ALAC_FBANK_SNIP_EDGES) != 0u))
+        return ALACGPU_ERR_BAD_ARG;
+    alac_mfcc_params p;
+    p.dct = (const float*)d_dct;
+    p.lifter = (const float*)d_lifter;
+    p.n_ceps = n_ceps;
+    p.flags = flags;
+    p.preemphasis = preemphasis;
+    p.scale = scale;
+    p.log_energy_floor = energy_floor > 0.0f ? (float)std::log((double)energy_floor) : -INFINITY;   // (rounded once, as mfcc.py's)
+    return launch_stft_mel(ctx, (const void*)alac_mfcc_kernel, p, ALAC_MFCC_LDS_EXTRA, d_src, rows, channels, src_stride, frames,
+                           win_length, n_fft, hop, n_mels, d_window, d_basis, d_fb, d_out, out_frames, hip_stream);
+}
+
+int alacgpu_deltas_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t channels, uint32_t n_feats,
+                          uint64_t src_stride, uint64_t out_stride, uint64_t line_len, const void* d_lengths, uint32_t order,
+                          uint32_t window, const void* d_scales, void* hip_stream) {
+    if (!ctx || !args_ok({{d_src, 4}, {d_out, 4}, {d_lengths, 8, false}, {d_scales, 4}})) return ALACGPU_ERR_BAD_ARG;
+    if (channels == 0 || n_feats == 0 || (uint64_t)channels * n_feats > 0xFFFFFFFFull / (ALAC_DELTAS_MAX_ORDER + 1u) || line_len == 0 ||
+        line_len > src_stride || line_len > out_stride || order < 1 || order > ALAC_DELTAS_MAX_ORDER || window < 1 ||
+        window > ALAC_DELTAS_MAX_WINDOW)
+        return ALACGPU_ERR_BAD_ARG;
+    const uint64_t lines = (uint64_t)rows * channels * n_feats;
+    uint64_t extent, out_extent;
+    if (!planes_extent(lines, src_stride, line_len, extent) || !planes_extent(lines * (order + 1u), out_stride, line_len, out_extent) ||
+        !apart(d_src, extent, d_out, out_extent))
+        return ALACGPU_ERR_BAD_ARG;
+    const uint64_t tiles = (line_len + ALAC_DELTAS_TILE - 1u) / ALAC_DELTAS_TILE;
+    const uint64_t groups = (lines + ALAC_DELTAS_LINES - 1u) / ALAC_DELTAS_LINES;
+    if (tiles > 0x7FFFFFFFull || groups > 0x7FFFFFFFull || tiles * groups > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    alac_deltas_params p;
+    p.src = (const float*)d_src;
+    p.out = (float*)d_out;
+    p.lengths = (const int64_t*)d_lengths;
+    p.scales = (const float*)d_scales;
+    p.lines = lines;
+    p.src_stride = src_stride;
+    p.out_stride = out_stride;
+    p.line_len = line_len;
+    p.lines_per_row = channels * n_feats;
+    p.n_feats = n_feats;
+    p.order = order;
+    p.window = window;
+    p.tiles = (uint32_t)tiles;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_deltas_kernel, dim3((uint32_t)(tiles * groups)), dim3(ALAC_DELTAS_THREADS), kargs, 0,
+                                 (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
 }
 
 int alacgpu_normalize_meanvar_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t lines_per_row,

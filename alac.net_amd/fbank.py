@@ -62,7 +62,8 @@ tap (without remove_dc_offset the window's zero weights at both ends do, 0 * NaN
 what it is without it.  max(M, floor) keeps a NaN, as np.maximum and torch.clamp do.
 
 Out of scope: `dither` (Kaldi draws it per frame element; there is nothing to hold a device generator to, and torchaudio's
-and lhotse's default is 0), `use_energy`, `raw_energy` and `htk_compat`, VTLN, MFCC and deltas.
+and lhotse's default is 0), `use_energy` and `raw_energy` (mfcc.KaldiMfcc has them: here they would change the transform's
+line count), `htk_compat` and VTLN.  MFCCs are mfcc.py's, on this module's framing, window and banks; deltas are deltas.py's.
 
 `kaldi_window`, `kaldi_mel_banks`, `KaldiFbank`, `fbank_host` and `fbank_host_f32` need no device.  `fbank` is the call on
 device tensors.
@@ -146,53 +147,37 @@ def _flag(name, v):
     return bool(v)
 
 
-class KaldiFbank(_Transform):
-    """An immutable description of Kaldi's fbank transform (see the module) together with its three float32 tables: `window`
-    [win_length], `basis` [win_length, 2 * n_bins] and `fb` [n_mels, n_bins] (read-only arrays).  Lengths are in samples:
-    Kaldi's frame_length 25 ms and frame_shift 10 ms at 16 kHz are win_length 400 and hop_length 160.  The features are
-    [..., n_mels, T']: Kaldi's matrix transposed.  ValueError unless 16 <= win_length <= 2048, 1 <= hop_length <= win_length,
-    1 <= n_mels <= 256, n_fft <= 2048, 0 <= low_freq < high <= sample_rate / 2, 0 <= preemphasis <= 1, scale finite and not
-    zero in float32, a window of `WINDOWS`."""
+def _kaldi_fields(sample_rate, win_length, hop_length, n_mels, low_freq, high_freq, preemphasis, window, scale, **flags):
+    """What `KaldiFbank` and mfcc.KaldiMfcc check and build alike: ((window, basis, fb), the fields of `_Transform._freeze`
+    but n_mels); `flags`: the transform's switches by name, each True or False.  ValueError as `KaldiFbank` states."""
+    sample_rate = _int("sample_rate", sample_rate, 1)
+    win_length = _int("win_length", win_length, MIN_WIN, MAX_WIN)
+    hop_length = _int("hop_length", hop_length, 1, win_length)
+    n_mels = _int("n_mels", n_mels, 1, MAX_MELS)
+    flags = {n: _flag(n, v) for n, v in flags.items()}
+    n_fft = 1 << (win_length - 1).bit_length() if flags["round_to_power_of_two"] else win_length
+    if n_fft > MAX_NFFT:
+        raise ValueError(f"n_fft = {n_fft} is above {MAX_NFFT}")
+    low_freq, high_freq = float(low_freq), float(high_freq)
+    _kaldi_band(sample_rate, low_freq, high_freq)
+    if isinstance(preemphasis, (bool, np.bool_)) or not isinstance(preemphasis, (int, float, np.integer, np.floating)) \
+            or not 0.0 <= float(preemphasis) <= 1.0:
+        raise ValueError(f"preemphasis must be a number of 0 .. 1, not {preemphasis!r}")
+    preemphasis = float(np.float32(preemphasis))
+    scale = float(np.float32(_f32_finite("scale", scale)))
+    if scale == 0.0:
+        raise ValueError("scale must not be zero in float32")
+    tables = (kaldi_window(window, win_length), fbank_basis(win_length, n_fft),
+              kaldi_mel_banks(sample_rate, n_fft, n_mels, low_freq, high_freq))
+    return tables, dict(sample_rate=sample_rate, win_length=win_length, hop_length=hop_length, n_fft=n_fft, n_bins=n_fft // 2 + 1,
+                        low_freq=low_freq, high_freq=high_freq, preemphasis=preemphasis, window_type=window, scale=scale, **flags)
 
-    __slots__ = ("sample_rate", "win_length", "hop_length", "n_mels", "n_fft", "n_bins", "low_freq", "high_freq", "preemphasis",
-                 "remove_dc_offset", "window_type", "round_to_power_of_two", "snip_edges", "use_power", "log", "scale")
 
-    def __init__(self, sample_rate, win_length=400, hop_length=160, n_mels=80, low_freq=20.0, high_freq=0.0, preemphasis=0.97,
-                 remove_dc_offset=True, window="povey", round_to_power_of_two=True, snip_edges=True, use_power=True, log=True,
-                 scale=32768.0):
-        sample_rate = _int("sample_rate", sample_rate, 1)
-        win_length = _int("win_length", win_length, MIN_WIN, MAX_WIN)
-        hop_length = _int("hop_length", hop_length, 1, win_length)
-        n_mels = _int("n_mels", n_mels, 1, MAX_MELS)
-        flags = {n: _flag(n, v) for n, v in dict(remove_dc_offset=remove_dc_offset, round_to_power_of_two=round_to_power_of_two,
-                                                 snip_edges=snip_edges, use_power=use_power, log=log).items()}
-        n_fft = 1 << (win_length - 1).bit_length() if flags["round_to_power_of_two"] else win_length
-        if n_fft > MAX_NFFT:
-            raise ValueError(f"n_fft = {n_fft} is above {MAX_NFFT}")
-        low_freq, high_freq = float(low_freq), float(high_freq)
-        _kaldi_band(sample_rate, low_freq, high_freq)
-        if isinstance(preemphasis, (bool, np.bool_)) or not isinstance(preemphasis, (int, float, np.integer, np.floating)) \
-                or not 0.0 <= float(preemphasis) <= 1.0:
-            raise ValueError(f"preemphasis must be a number of 0 .. 1, not {preemphasis!r}")
-        preemphasis = float(np.float32(preemphasis))
-        scale = float(np.float32(_f32_finite("scale", scale)))
-        if scale == 0.0:
-            raise ValueError("scale must not be zero in float32")
-        self._freeze(kaldi_window(window, win_length), fbank_basis(win_length, n_fft),
-                     kaldi_mel_banks(sample_rate, n_fft, n_mels, low_freq, high_freq), sample_rate=sample_rate,
-                     win_length=win_length, hop_length=hop_length, n_mels=n_mels, n_fft=n_fft, n_bins=n_fft // 2 + 1,
-                     low_freq=low_freq, high_freq=high_freq, preemphasis=preemphasis, window_type=window, scale=scale, **flags)
+class _KaldiFraming:
+    """Kaldi's framing as `Corpus.crops` and `_on_device` ask a transform for it: what `KaldiFbank` and mfcc.KaldiMfcc share
+    beside their tables"""
 
-    def __repr__(self):
-        return (f"KaldiFbank(sample_rate={self.sample_rate}, win_length={self.win_length}, hop_length={self.hop_length}, "
-                f"n_mels={self.n_mels}, n_fft={self.n_fft}, window={self.window_type!r}, snip_edges={self.snip_edges}, "
-                f"preemphasis={self.preemphasis}, log={self.log})")
-
-    @property
-    def flags(self):
-        """alacgpu_fbank_device's flags: 1 snip_edges, 2 remove_dc_offset, 4 use_power, 8 log"""
-        return (FLAG_SNIP_EDGES * self.snip_edges | FLAG_REMOVE_DC * self.remove_dc_offset | FLAG_USE_POWER * self.use_power |
-                FLAG_LOG * self.log)
+    __slots__ = ()
 
     def frames(self, L):
         """T' of a row of L samples (numpy arrays too)"""
@@ -215,6 +200,37 @@ class KaldiFbank(_Transform):
         """`fbank_lengths(lengths, self)`"""
         return fbank_lengths(lengths, self)
 
+
+class KaldiFbank(_KaldiFraming, _Transform):
+    """An immutable description of Kaldi's fbank transform (see the module) together with its three float32 tables: `window`
+    [win_length], `basis` [win_length, 2 * n_bins] and `fb` [n_mels, n_bins] (read-only arrays).  Lengths are in samples:
+    Kaldi's frame_length 25 ms and frame_shift 10 ms at 16 kHz are win_length 400 and hop_length 160.  The features are
+    [..., n_mels, T']: Kaldi's matrix transposed.  ValueError unless 16 <= win_length <= 2048, 1 <= hop_length <= win_length,
+    1 <= n_mels <= 256, n_fft <= 2048, 0 <= low_freq < high <= sample_rate / 2, 0 <= preemphasis <= 1, scale finite and not
+    zero in float32, a window of `WINDOWS`."""
+
+    __slots__ = ("sample_rate", "win_length", "hop_length", "n_mels", "n_fft", "n_bins", "low_freq", "high_freq", "preemphasis",
+                 "remove_dc_offset", "window_type", "round_to_power_of_two", "snip_edges", "use_power", "log", "scale")
+
+    def __init__(self, sample_rate, win_length=400, hop_length=160, n_mels=80, low_freq=20.0, high_freq=0.0, preemphasis=0.97,
+                 remove_dc_offset=True, window="povey", round_to_power_of_two=True, snip_edges=True, use_power=True, log=True,
+                 scale=32768.0):
+        tables, fields = _kaldi_fields(sample_rate, win_length, hop_length, n_mels, low_freq, high_freq, preemphasis, window, scale,
+                                       remove_dc_offset=remove_dc_offset, round_to_power_of_two=round_to_power_of_two,
+                                       snip_edges=snip_edges, use_power=use_power, log=log)
+        self._freeze(*tables, n_mels=tables[2].shape[0], **fields)
+
+    def __repr__(self):
+        return (f"KaldiFbank(sample_rate={self.sample_rate}, win_length={self.win_length}, hop_length={self.hop_length}, "
+                f"n_mels={self.n_mels}, n_fft={self.n_fft}, window={self.window_type!r}, snip_edges={self.snip_edges}, "
+                f"preemphasis={self.preemphasis}, log={self.log})")
+
+    @property
+    def flags(self):
+        """alacgpu_fbank_device's flags: 1 snip_edges, 2 remove_dc_offset, 4 use_power, 8 log"""
+        return (FLAG_SNIP_EDGES * self.snip_edges | FLAG_REMOVE_DC * self.remove_dc_offset | FLAG_USE_POWER * self.use_power |
+                FLAG_LOG * self.log)
+
     def launch(self, gpu, src, rows, channels, src_stride, L, out, stream):
         """The features of src (float32 device tensor, planar [rows, channels, src_stride], the first L of a plane are signal)
         into out [rows, channels, n_mels, frames(L)] by the AlacGpuContext `gpu`: one alacgpu_fbank_device call on `stream`"""
@@ -234,15 +250,62 @@ def fbank_frame_index(L, spec):
     return g
 
 
-def _rows_of(x, spec):
+def _rows_of(x, spec, kind=None):
     x = np.asarray(x)
     if x.dtype != np.float32:
         raise ValueError(f"x must be float32, not {x.dtype}")
     if x.ndim < 1 or x.shape[-1] < 1:
         raise ValueError(f"x must be [..., L] with L >= 1, not {x.shape}")
-    if not isinstance(spec, KaldiFbank):
-        raise ValueError("spec must be a KaldiFbank")
+    if not isinstance(spec, kind or KaldiFbank):
+        raise ValueError(f"spec must be a {(kind or KaldiFbank).__name__}")
     return x, x.shape[-1]
+
+
+def _prev(v):
+    """v[:, n - 1], v[:, 0] its own predecessor"""
+    return np.concatenate([v[:, :1], v[:, :-1]], axis=1)
+
+
+def _row_f64(row, idx, spec, bound):
+    """One row of `fbank_host` (row float64 [L], idx `fbank_frame_index`), and what mfcc.mfcc_host needs of it beside M: returns
+    (M [T', n_mels], dM or None, d, a, e_d, e_a) -- d [T', N] the frames after scale and mean, a the windowed frames, e_d and
+    e_a how far a float32 evaluation may be from them (the module's e_d and e_a; None without bound)"""
+    N, n_bins, c = spec.win_length, spec.n_bins, spec.preemphasis
+    w = spec.window.astype(np.float64)[None, :]
+    basis = spec.basis.astype(np.float64)
+    fb = spec.fb.astype(np.float64)
+    T = idx.shape[0]
+    s = spec.scale * row[idx]                                        # [T, N]
+    d = s - s.sum(axis=1, keepdims=True) / N if spec.remove_dc_offset else s
+    y = d - c * _prev(d) if c != 0.0 else d
+    a = w * y
+    X = a @ basis
+    P = X[:, :n_bins] ** 2 + X[:, n_bins:] ** 2
+    dM = e_d = e_a = None
+    if bound:
+        e = _U * np.abs(s)
+        if spec.remove_dc_offset:
+            e_mu = (N / 8 + 6) * _U * np.abs(s).sum(axis=1, keepdims=True) / N + e.sum(axis=1, keepdims=True) / N
+            e = e + e_mu + _U * np.abs(d)
+        e_d = e
+        if c != 0.0:
+            e = e + c * _prev(e) + _U * np.abs(y)
+        e_a = e = w * e + _U * np.abs(a)
+        E = e @ np.abs(basis)
+        chain = np.empty_like(X)
+        for t in range(T):                                           # the partial sums of frame t's chains, [N, 2 n_bins]
+            chain[t] = np.abs(np.cumsum(a[t][:, None] * basis, axis=0)).sum(axis=0)
+        delta = E + (1 + 2.0 ** -10) * _U * (N * E + chain)
+        dre, dim = delta[:, :n_bins], delta[:, n_bins:]
+        dP = 2 * np.abs(X[:, :n_bins]) * dre + dre ** 2 + 2 * np.abs(X[:, n_bins:]) * dim + dim ** 2 + 3 * _U * P
+        if not spec.use_power:
+            dP = np.sqrt(P + dP) - np.sqrt(np.maximum(P - dP, 0.0)) + 2 * _U * np.sqrt(P + dP)
+    if not spec.use_power:
+        P = np.sqrt(P)
+    M = P @ fb.T                                                     # [T, n_mels]
+    if bound:
+        dM = dP @ fb.T + (n_bins + 1) * _U * M
+    return M, dM, d, a, e_d, e_a
 
 
 def fbank_host(x, spec, bound=False):
@@ -251,48 +314,50 @@ def fbank_host(x, spec, bound=False):
     out: how far a float32 evaluation in the kernel's order may be from M (the module docstring's bound; in the domain of M,
     whatever spec.log is)."""
     x, L = _rows_of(x, spec)
-    N, n_bins, c = spec.win_length, spec.n_bins, spec.preemphasis
     idx = fbank_frame_index(L, spec)
     T = idx.shape[0]
-    w = spec.window.astype(np.float64)[None, :]
-    basis = spec.basis.astype(np.float64)
-    fb = spec.fb.astype(np.float64)
     rows = x.reshape(-1, L).astype(np.float64)
     out = np.empty((rows.shape[0], spec.n_mels, T), dtype=np.float64)
     dM = np.empty_like(out) if bound else None
-    prev = lambda v: np.concatenate([v[:, :1], v[:, :-1]], axis=1)
     for r, row in enumerate(rows):
-        s = spec.scale * row[idx]                                    # [T, N]
-        d = s - s.sum(axis=1, keepdims=True) / N if spec.remove_dc_offset else s
-        y = d - c * prev(d) if c != 0.0 else d
-        a = w * y
-        X = a @ basis
-        P = X[:, :n_bins] ** 2 + X[:, n_bins:] ** 2
+        M, dM_r = _row_f64(row, idx, spec, bound)[:2]
         if bound:
-            e = _U * np.abs(s)
-            if spec.remove_dc_offset:
-                e_mu = (N / 8 + 6) * _U * np.abs(s).sum(axis=1, keepdims=True) / N + e.sum(axis=1, keepdims=True) / N
-                e = e + e_mu + _U * np.abs(d)
-            if c != 0.0:
-                e = e + c * prev(e) + _U * np.abs(y)
-            e = w * e + _U * np.abs(a)
-            E = e @ np.abs(basis)
-            chain = np.empty_like(X)
-            for t in range(T):                                       # the partial sums of frame t's chains, [N, 2 n_bins]
-                chain[t] = np.abs(np.cumsum(a[t][:, None] * basis, axis=0)).sum(axis=0)
-            delta = E + (1 + 2.0 ** -10) * _U * (N * E + chain)
-            dre, dim = delta[:, :n_bins], delta[:, n_bins:]
-            dP = 2 * np.abs(X[:, :n_bins]) * dre + dre ** 2 + 2 * np.abs(X[:, n_bins:]) * dim + dim ** 2 + 3 * _U * P
-            if not spec.use_power:
-                dP = np.sqrt(P + dP) - np.sqrt(np.maximum(P - dP, 0.0)) + 2 * _U * np.sqrt(P + dP)
-        if not spec.use_power:
-            P = np.sqrt(P)
-        M = P @ fb.T                                                 # [T, n_mels]
-        if bound:
-            dM[r] = (dP @ fb.T + (n_bins + 1) * _U * M).T
+            dM[r] = dM_r.T
         out[r] = (np.log(np.maximum(M, FLOOR)) if spec.log else M).T
     out = out.reshape(x.shape[:-1] + (spec.n_mels, T))
     return (out, dM.reshape(out.shape)) if bound else out
+
+
+def _row_f32(row, idx, spec):
+    """One row of `fbank_host_f32` (row float32 [L]), and what mfcc.mfcc_host_f32 needs of it beside M: returns (M float32
+    [T', n_mels], d, a) -- d [T', N] the frames after scale and mean, a the windowed frames, as the kernel rounds them"""
+    f32, f64 = np.float32, np.float64
+    N, n_bins = spec.win_length, spec.n_bins
+    c, scale = f32(spec.preemphasis), f32(spec.scale)
+    T = idx.shape[0]
+    basis = spec.basis.astype(f64)
+    fbT = np.ascontiguousarray(spec.fb.astype(f64).T)
+    s = (scale * row[idx]).astype(f32)                               # [T, N]
+    d = s
+    if spec.remove_dc_offset:
+        part = np.zeros((T, MEAN_PARTIALS), dtype=f32)
+        for n in range(N):                                           # partial n % 8 takes tap n, ascending
+            part[:, n % MEAN_PARTIALS] += s[:, n]
+        p = part
+        while p.shape[1] > 1:                                        # neighbours first: ((p0 + p1) + (p2 + p3)) + ...
+            p = p[:, 0::2] + p[:, 1::2]
+        mu = (p / f32(N)).astype(f32)                                # [T, 1]
+        d = (s - mu).astype(f32)
+    y = d
+    if spec.preemphasis != 0.0:                                      # fma(-c, d[n - 1], d[n]): the product is exact in float64
+        y = (d.astype(f64) - f64(c) * _prev(d).astype(f64)).astype(f32)
+    a = (spec.window[None, :] * y).astype(f32)
+    X = _chain(a, basis)
+    re, im = X[:, :n_bins].astype(f64), X[:, n_bins:].astype(f64)
+    P = (re * re + (im * im).astype(f32).astype(f64)).astype(f32)
+    if not spec.use_power:
+        P = np.sqrt(P)                                               # float32, correctly rounded
+    return _chain(P, fbT), d, a
 
 
 def fbank_host_f32(x, spec):
@@ -301,40 +366,14 @@ def fbank_host_f32(x, spec):
     `fbank_host` is what a correct float32 evaluation costs: the tests hold the kernel to a small multiple of that, far
     inside dM."""
     x, L = _rows_of(x, spec)
-    f32, f64 = np.float32, np.float64
-    N, n_bins = spec.win_length, spec.n_bins
-    c, scale = f32(spec.preemphasis), f32(spec.scale)
     idx = fbank_frame_index(L, spec)
     T = idx.shape[0]
-    basis = spec.basis.astype(f64)
-    fbT = np.ascontiguousarray(spec.fb.astype(f64).T)
     rows = x.reshape(-1, L)
-    out = np.empty((rows.shape[0], spec.n_mels, T), dtype=f32)
-    prev = lambda v: np.concatenate([v[:, :1], v[:, :-1]], axis=1)
+    out = np.empty((rows.shape[0], spec.n_mels, T), dtype=np.float32)
     for r, row in enumerate(rows):
-        s = (scale * row[idx]).astype(f32)                           # [T, N]
-        d = s
-        if spec.remove_dc_offset:
-            part = np.zeros((T, MEAN_PARTIALS), dtype=f32)
-            for n in range(N):                                       # partial n % 8 takes tap n, ascending
-                part[:, n % MEAN_PARTIALS] += s[:, n]
-            p = part
-            while p.shape[1] > 1:                                    # neighbours first: ((p0 + p1) + (p2 + p3)) + ...
-                p = p[:, 0::2] + p[:, 1::2]
-            mu = (p / f32(N)).astype(f32)                            # [T, 1]
-            d = (s - mu).astype(f32)
-        y = d
-        if spec.preemphasis != 0.0:                                  # fma(-c, d[n - 1], d[n]): the product is exact in float64
-            y = (d.astype(f64) - f64(c) * prev(d).astype(f64)).astype(f32)
-        a = (spec.window[None, :] * y).astype(f32)
-        X = _chain(a, basis)
-        re, im = X[:, :n_bins].astype(f64), X[:, n_bins:].astype(f64)
-        P = (re * re + (im * im).astype(f32).astype(f64)).astype(f32)
-        if not spec.use_power:
-            P = np.sqrt(P)                                           # float32, correctly rounded
-        M = _chain(P, fbT)
+        M = _row_f32(row, idx, spec)[0]
         if spec.log:
-            M = np.log(np.maximum(M, f32(FLOOR)))
+            M = np.log(np.maximum(M, np.float32(FLOOR)))
         out[r] = M.T
     return out.reshape(x.shape[:-1] + (spec.n_mels, T))
 

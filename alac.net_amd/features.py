@@ -130,17 +130,19 @@ def dft_basis(n_fft, rows=None):
 
 
 class _Transform:
-    """What `LogMel` and `fbank.KaldiFbank` share: three read-only float32 tables (window, basis, fb) beside their own fields,
-    immutability, and the tables on a device.  What `Corpus.crops` and `_on_device` need of a transform is the subclass's:
-    `frames`, `min_frames`, `short`, `lengths` and `launch`."""
+    """What `LogMel`, `fbank.KaldiFbank` and `mfcc.KaldiMfcc` share: read-only float32 tables (window, basis, fb; a subclass
+    names more in `_TABLES`) beside their own fields, immutability, and the tables on a device.  What `Corpus.crops` and
+    `_on_device` need of a transform is the subclass's: `frames`, `min_frames`, `short`, `lengths` and `launch`."""
 
     __slots__ = ("window", "basis", "fb", "_device")
+    _TABLES = ("window", "basis", "fb")
 
     def _freeze(self, window, basis, fb, **fields):
         """The end of a subclass's __init__: the tables made read-only, and they and the fields assigned"""
-        for a in (window, basis, fb):
-            a.flags.writeable = False
-        for name, v in dict(fields, window=window, basis=basis, fb=fb, _device={}).items():
+        fields = dict(fields, window=window, basis=basis, fb=fb, _device={})
+        for name in self._TABLES:
+            fields[name].flags.writeable = False
+        for name, v in fields.items():
             object.__setattr__(self, name, v)
 
     def __setattr__(self, name, value):
@@ -150,13 +152,13 @@ class _Transform:
         raise AttributeError(f"a {type(self).__name__} is immutable")
 
     def device_tables(self, device):
-        """(window, basis, fb) on the device (a torch.device), uploaded once per device"""
+        """The tables (window, basis, fb and what else `_TABLES` names) on the device (a torch.device), uploaded once per device"""
         import torch
 
         index = device.index if device.index is not None else torch.cuda.current_device()
         if index not in self._device:
             dev = torch.device("cuda", index)
-            self._device[index] = tuple(torch.from_numpy(np.array(a)).to(dev) for a in (self.window, self.basis, self.fb))
+            self._device[index] = tuple(torch.from_numpy(np.array(getattr(self, a))).to(dev) for a in self._TABLES)
         return self._device[index]
 
 
@@ -333,7 +335,7 @@ def feature_lengths(lengths, hop):
 
 
 def _on_device(pcm, spec, kind, takes, short, lengths):
-    """`log_mel` and `fbank.fbank` behind their names: spec is a `kind`, pcm a float32 device tensor whose shape the messages
+    """`log_mel`, `fbank.fbank` and `mfcc.mfcc` behind their names: spec is a `kind`, pcm a float32 device tensor whose shape the messages
     call `takes` and for whose T `short(T)` is None (the ValueError's text otherwise); the output, one `spec.launch` over all
     planes unless there is nothing to compute, and `spec.lengths` of the lengths"""
     import torch

@@ -116,6 +116,23 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_fbank_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
             ulong srcStride, ulong frames, uint winLength, uint nFft, uint hop, uint nMels, IntPtr dWindow, IntPtr dBasis, IntPtr dFb,
             uint flags, float preemphasis, float scale, IntPtr dOut, ulong outFrames, IntPtr hipStream);
+        /// <summary>Kaldi's MFCC features of float PCM in device memory: alacgpu_fbank_device's frames, mean, pre-emphasis, window,
+        /// DFT and nMels mel sums (flags 1, 2, 4 as there), then ln(max(., 2^-23)), the projection on dDct [nCeps, nMels] and the
+        /// product with dLifter [nCeps] into dOut [rows, channels, nCeps, outFrames]; flags 16 (use_energy): line 0 is the log
+        /// energy of the frame (32, raw_energy: before pre-emphasis and window), at least ln(energyFloor) for energyFloor > 0.
+        /// Asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_mfcc_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
+            ulong srcStride, ulong frames, uint winLength, uint nFft, uint hop, uint nMels, uint nCeps, IntPtr dWindow, IntPtr dBasis,
+            IntPtr dFb, IntPtr dDct, IntPtr dLifter, uint flags, float preemphasis, float scale, float energyFloor, IntPtr dOut,
+            ulong outFrames, IntPtr hipStream);
+        /// <summary>Kaldi's add-deltas on float features in device memory (dSrc [rows, channels, nFeats, srcStride], the first lineLen
+        /// of a line are frames): the features and their deltas of order 1 .. order (1 .. 3) over window (1 .. 4) frames per order
+        /// with the scales dScales, every order clamped into the first min(max(dLengths[row], 0), lineLen) frames of the features
+        /// (dLengths: long[rows] or IntPtr.Zero for lineLen), zeros behind them, into dOut [rows, channels, (order + 1) * nFeats,
+        /// outStride] apart from dSrc.  Asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_deltas_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, uint rows, uint channels,
+            uint nFeats, ulong srcStride, ulong outStride, ulong lineLen, IntPtr dLengths, uint order, uint window, IntPtr dScales,
+            IntPtr hipStream);
         /// <summary>Mean and variance per line of float data in device memory ([rows, linesPerRow, lineStride], the first lineLen of
         /// a line are data) over the first min(max(dValid[row], 0), lineLen) elements (dValid: long[rows] or IntPtr.Zero for whole
         /// lines): (x - mean) / sqrt(var + eps), zeros behind them, into dOut (dSrc itself or the same layout).  Asynchronous on

@@ -49,7 +49,7 @@ from fractions import Fraction
 
 import numpy as np
 
-from ._stageargs import _f32_finite, _Spec
+from ._stageargs import _f32_finite, _fma32, _Spec
 from .resample import _ratio, _table, apply_table, filter_width, identity_table, resampled_frames
 
 EPS_W = 2.0 ** -18
@@ -157,21 +157,6 @@ def speed_bound(x, a, b, width, mono=False, origin=0, first=0, num_frames=None):
     ones = np.ones((b, N), dtype=np.float32)
     return ((N + 2) * 2.0 ** -24 * speed_host(x, a, b, width, **kw)
             + EPS_W * (0.99 * min(a, b) / a) * apply_table(x, a, b, width, d0, ones, **kw))
-
-
-def _fma32(x, y, z):
-    """fma(x, y, z) of float32 arrays, exactly: the product is exact in float64, the sum is rounded to odd there (TwoSum tells
-    which way the exact sum lies), and 53 bits rounded to odd round to float32 as the exact value does"""
-    p = np.asarray(x, dtype=np.float32).astype(np.float64) * np.asarray(y, dtype=np.float32).astype(np.float64)
-    z = np.asarray(z, dtype=np.float32).astype(np.float64)
-    p, z = np.broadcast_arrays(p, z)
-    s = p + z
-    t = s - p
-    err = (p - (s - t)) + (z - t)
-    bits = np.ascontiguousarray(s).view(np.int64)
-    fix = (err != 0) & ((bits & 1) == 0)
-    bits = np.where(fix, bits + np.where((err > 0) == (s > 0), 1, -1), bits)
-    return bits.view(np.float64).astype(np.float32)
 
 
 def _sinpi32(x):

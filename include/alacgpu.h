@@ -528,6 +528,60 @@ int alacgpu_fbank_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uin
                          float scale, void* d_out, uint64_t out_frames, void* hip_stream);
 
 /*
+ * Kaldi MFCC features of decoded PCM (no counterpart in the reference): what Kaldi's compute-mfcc-feats computes, in one
+ * launch.  Frames, s, d, y, X, P and M are alacgpu_fbank_device's, by the same flags 1 (snip_edges), 2 (remove_dc_offset) and
+ * 4 (use_power) and in the same float32 order; the log is not a choice (flag 8 is refused).  Then per frame, c < n_ceps:
+ *   lm[m]    = ln(max(M[m], 2^-23))
+ *   C[c]     = sum over m of d_dct[c * n_mels + m] * lm[m]      (fused multiply-adds in ascending m from zero)
+ *   out[c,t] = d_lifter[c] * C[c]                               (one product)
+ *   E        = ln(max(sum over n of e[n]^2, 2^-23))             (flags & 16, use_energy.  flags & 32, raw_energy: e = d, the
+ *                                                                frame after scale and mean, before pre-emphasis and window;
+ *                                                                else e = d_window[n] * y[n])
+ *   E        = max(E, ln(energy_floor))                         (energy_floor > 0; its log is taken once, in double, and rounded)
+ *   out[0,t] = E                                                (use_energy: in the place of C[0], un-liftered)
+ * The sum of the squares follows the mean: eight partial sums, partial j over the taps j, j + 8 ... in ascending order, each a
+ * chain part = fma(e, e, part), added as ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)).  The five tables are the caller's
+ * (alac.net_amd/mfcc.py builds Kaldi's: fbank's three, the orthonormal DCT-II and the lifter 1 + Q / 2 sin(pi c / Q)).  Device
+ * pointers only, asynchronous on hip_stream, nothing is read back; nothing of the ctx is used but its device.
+ *   d_src     float32, planar [rows, channels, src_stride]; only the first `frames` elements of a plane are signal and only
+ *             they are read
+ *   d_window  float32 [N];  d_basis  float32 [N, 2 * n_bins];  d_fb  float32 [n_mels, n_bins]
+ *   d_dct     float32 [n_ceps, n_mels];  d_lifter  float32 [n_ceps]
+ *   d_out     float32 [rows, channels, n_ceps, out_frames]; every element is written, each by one thread
+ * A workgroup is alacgpu_fbank_device's, with 32 more floats of LDS for the energies; the projection runs on the mel sums
+ * where they are.  rows == 0 or out_frames == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: what alacgpu_fbank_device refuses, n_ceps outside 1 .. n_mels, a NULL or
+ * misaligned d_dct or d_lifter, flags outside 1, 2, 4, 16, 32, flag 32 without 16, an energy_floor that is negative or not
+ * finite.
+ */
+int alacgpu_mfcc_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride,
+                        uint64_t frames, uint32_t win_length, uint32_t n_fft, uint32_t hop, uint32_t n_mels, uint32_t n_ceps,
+                        const void* d_window, const void* d_basis, const void* d_fb, const void* d_dct, const void* d_lifter,
+                        uint32_t flags, float preemphasis, float scale, float energy_floor, void* d_out, uint64_t out_frames,
+                        void* hip_stream);
+
+/*
+ * Kaldi's add-deltas behind the features (no counterpart in the reference): the features and their time derivatives up to
+ * `order`, in one launch.  d_src is float32 [rows, channels, n_feats, src_stride], d_out float32 [rows, channels,
+ * (order + 1) * n_feats, out_stride]; the first line_len elements of a line are frames, what lies behind them is neither
+ * read nor written.  With W = window, len = min(max(d_lengths[row], 0), line_len) (line_len for a NULL d_lengths) and the
+ * scales of order k, 2 k W + 1 of them, at d_scales + W k (k - 1) + (k - 1):
+ *   out[f, t]               = x[f, t]                                                          every t < line_len
+ *   out[k * n_feats + f, t] = sum over j = -k W .. k W of scales_k[j + k W] * x[f, clamp(t + j, 0, len - 1)]    t < len
+ *                           = 0                                                                len <= t < line_len
+ * one chain of float32 fused multiply-adds in ascending j from zero.  The clamp is into x for every order, as in Kaldi's
+ * DeltaFeatures (alac.net_amd/deltas.py builds its scales: scales_k = scales_{k-1} convolved with [-W .. W] / (2 sum of j^2));
+ * any table of that length is honoured.  For a delta nothing at or behind len is read.  Device pointers only, asynchronous on
+ * hip_stream, nothing is read back; nothing of the ctx is used but its device.  rows == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx, d_src, d_out or d_scales, a misaligned array (4; d_lengths 8),
+ * channels, n_feats or line_len 0, channels * n_feats * 4 above 2^32 - 1, line_len above a stride, order outside 1 .. 3, window
+ * outside 1 .. 4, d_src and d_out that overlap, 2^31 workgroups or more.
+ */
+int alacgpu_deltas_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t channels, uint32_t n_feats,
+                          uint64_t src_stride, uint64_t out_stride, uint64_t line_len, const void* d_lengths, uint32_t order,
+                          uint32_t window, const void* d_scales, void* hip_stream);
+
+/*
  * The two normalisations between crops or their features and a model (no counterpart in the reference).  The data of both is
  * float32 [rows, lines_per_row, line_stride]: the first line_len <= line_stride elements of a line are data, what lies behind
  * them is neither read nor written.  Features [B, C, n_mels, Tf] are rows = B, lines_per_row = C * n_mels; a waveform

@@ -1,6 +1,9 @@
 """alacgpu_deltas_device on the GPU against its float32 twin (deltas.deltas_host_f32) bit for bit -- there is no transcendental
 in it, so the twin is exact -- with NaNs behind every line of the input and the output prefilled with NaN between guards of
 0x5A bytes, as tests/test_fbank.py does it.  The kernel's tile is 64 frames of 4 lines."""
+import os
+import re
+
 import numpy as np
 import pytest
 
@@ -8,6 +11,14 @@ pytestmark = pytest.mark.gpu
 
 GUARD = 64
 TILE = 64
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def header_constant(name):
+    src = open(os.path.join(ROOT, "alac.net_amd", "csrc", "alac_deltas.h")).read()
+    m = re.search(r"constexpr\s+uint32_t\s+" + name + r"\s*=\s*(\d+)u\s*;", src)
+    assert m, f"alac_deltas.h does not define {name}"
+    return int(m.group(1))
 
 
 @pytest.fixture(scope="module")
@@ -20,22 +31,23 @@ def gpu():
         yield torch, pkg, ctx
 
 
-def run_kernel(torch, ctx, x, spec, lengths=None, slack=5):
-    """The call over x [B, C, F, T] (numpy float32), stored with `slack` NaNs behind every line, into an output with `slack`
-    elements behind every line too, prefilled with NaN, between guards; returns (out [B, C, (order + 1) F, T], what lies behind
-    the lines of the output is still NaN and the guards are intact)"""
+def run_kernel(torch, ctx, x, spec, lengths=None, slack=5, out_slack=None):
+    """The call over x [B, C, F, T] (numpy float32), stored with `slack` NaNs behind every line, into an output with `out_slack`
+    elements (default: `slack` too) behind every line, prefilled with NaN, between guards; returns (out [B, C, (order + 1) F, T],
+    what lies behind the lines of the output is still NaN and the guards are intact)"""
     B, C_, F, T = x.shape
+    out_slack = slack if out_slack is None else out_slack
     src = np.full((B, C_, F, T + slack), np.nan, dtype=np.float32)
     src[..., :T] = x
     lines = B * C_ * (spec.order + 1) * F
-    n = lines * (T + slack)
+    n = lines * (T + out_slack)
     raw = torch.full(((n + 2 * GUARD) * 4,), 0x5A, dtype=torch.uint8, device="cuda").view(torch.float32)
     raw[GUARD:GUARD + n].fill_(float("nan"))
     d_len = None if lengths is None else torch.tensor(lengths, dtype=torch.int64, device="cuda")
-    ctx.deltas_device(torch.from_numpy(src).cuda(), raw[GUARD:], B, C_, F, T + slack, T + slack, T, d_len, spec.order, spec.window,
+    ctx.deltas_device(torch.from_numpy(src).cuda(), raw[GUARD:], B, C_, F, T + slack, T + out_slack, T, d_len, spec.order, spec.window,
                       spec.device_scales(torch.device("cuda", 0)), stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
-    out = raw[GUARD:GUARD + n].cpu().numpy().reshape(B, C_, (spec.order + 1) * F, T + slack)
+    out = raw[GUARD:GUARD + n].cpu().numpy().reshape(B, C_, (spec.order + 1) * F, T + out_slack)
     intact = bool((torch.cat([raw[:GUARD], raw[GUARD + n:]]).view(torch.uint8) == 0x5A).all()) and bool(np.isnan(out[..., T:]).all())
     return out[..., :T], intact
 
@@ -44,13 +56,18 @@ def same_bits(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.int32), b.view(np.int32))
 
 
-@pytest.mark.parametrize("order,window", [(1, 2), (2, 2), (3, 1), (2, 4)])
+@pytest.mark.parametrize("order,window", [(1, 2), (2, 2), (3, 1), (2, 4), (3, 4), (1, 1), (1, 4), (3, 2)])
 def test_kernel_equals_its_twin(gpu, order, window):
+    """(3, 4) is ALAC_DELTAS_MAX_HALO, which sizes the kernel's LDS array.  (3, 2, 5, 70) and (2, 2, 3, TILE + 12) have rows
+    and channels above one together, so a line's row is line / (C F) and nothing simpler; their lengths differ by row."""
     torch, pkg, ctx = gpu
+    assert (header_constant("ALAC_DELTAS_MAX_ORDER"), header_constant("ALAC_DELTAS_MAX_WINDOW")) == (3, 4)
+    assert TILE == header_constant("ALAC_DELTAS_TILE")
     spec = pkg.Deltas(order, window)
     rng = np.random.default_rng(10 * order + window)
     halo = order * window
-    for shape in ((2, 1, 13, 198), (1, 2, 5, 33)) + tuple((3, 1, 2, T) for T in (1, 2, 4, 5, 9, TILE + 1)):
+    shapes = ((2, 1, 13, 198), (1, 2, 5, 33), (3, 2, 5, 70), (2, 2, 3, TILE + 12))
+    for shape in shapes + tuple((3, 1, 2, T) for T in (1, 2, 4, 5, 9, TILE + 1)):
         x = (rng.standard_normal(shape) * 10).astype(np.float32)
         B, T = shape[0], shape[3]
         got, intact = run_kernel(torch, ctx, x, spec)
@@ -60,6 +77,18 @@ def test_kernel_equals_its_twin(gpu, order, window):
             lens = lens[:B]
             got, intact = run_kernel(torch, ctx, x, spec, lens)
             assert intact and same_bits(got, pkg.deltas_host_f32(x, spec, lens)), (shape, lens)
+
+
+def test_source_and_output_strides_differ(gpu):
+    """src_stride above out_stride and below it, at the widest filter and with a length per row: two tiles of two rows of
+    two channels"""
+    torch, pkg, ctx = gpu
+    spec = pkg.Deltas(3, 4)
+    x = (np.random.default_rng(34).standard_normal((2, 2, 3, TILE + 12)) * 10).astype(np.float32)
+    for slack, out_slack in ((9, 2), (0, 7), (3, 0)):
+        for lens in (None, [TILE - 3, TILE + 12], [TILE, 1]):
+            got, intact = run_kernel(torch, ctx, x, spec, lens, slack=slack, out_slack=out_slack)
+            assert intact and same_bits(got, pkg.deltas_host_f32(x, spec, lens)), (slack, out_slack, lens)
 
 
 def test_a_nan_behind_len_stays_there(gpu):

@@ -9,6 +9,23 @@ from alac.net_amd.fbank import (FLOOR, KaldiFbank, fbank_frame_index, fbank_host
 # (win, hop, round_to_power_of_two, n_mels, L): the shapes tests/test_fbank.py runs on the device
 GRID = [(400, 160, True, 80, 5000), (25, 10, True, 8, 333), (16, 1, True, 4, 40), (512, 128, True, 64, 4000),
         (400, 160, False, 80, 5000), (2048, 512, True, 40, 9000)]
+# (win, hop, n_mels, n_ceps, frames with snip_edges): one shape per code path of alac_fbank.hip and alac_mfcc.hip that depends on
+# the tile, the lane or the skew; tests/test_kaldi_paths.py runs them on the device, tests/test_mfcc_spec.py on the CPU as here
+PATHS = [(63, 7, 12, 12, 2 * 32 + 7),        # an odd hop above 1: no skew, q and r are real; odd K, whole k-steps in the remainder
+         (401, 161, 40, 13, 2 * 32 + 3),     # an odd window and an odd hop at speech size: 200 pairs and an odd tail, two rounds
+         (64, 16, 8, 8, 2 * 32 + 7),         # an even hop that divides the window: r == 0 at every hop boundary, two words back
+         (16, 16, 4, 4, 70),                 # hop == win: a sample belongs to one frame, q stays 0
+         (2048, 600, 40, 20, 30 + 3),        # a tile of 30 frames with the taps at the cap, two tiles
+         (2048, 2048, 23, 13, 9 + 2),        # a tile of 9, hop == win at the largest window
+         (2048, 560, 256, 23, 33)]           # the largest LDS layout: 256 filters, the span at the cap, the kernel's own floats
+
+
+def paths_length(win, hop, frames):
+    """The L that gives `frames` frames with snip_edges, and three samples to spare"""
+    return win + (frames - 1) * hop + 3
+
+
+PATH_GRID = [(win, hop, True, n_mels, paths_length(win, hop, frames)) for win, hop, n_mels, _, frames in PATHS]
 
 
 def noise(rng, *shape):
@@ -161,9 +178,11 @@ def test_the_gemm_is_the_zero_padded_transform(win, hop, pow2, n_mels, L):
         assert mag.shape == M.shape and (mag <= np.sqrt(M * spec.fb.astype(np.float64).sum(axis=1)[:, None]) * (1 + 1e-9) + 1e-9).all()
 
 
-@pytest.mark.parametrize("win,hop,pow2,n_mels,L", GRID)
+@pytest.mark.parametrize("win,hop,pow2,n_mels,L", GRID + PATH_GRID)
 def test_the_float32_twin_is_inside_the_bound(win, hop, pow2, n_mels, L):
-    rng = np.random.default_rng(win)
+    """PATH_GRID as well: what tests/test_kaldi_paths.py rests on holds for the reference alone -- the twin inside dM (at
+    2048 taps the device test leaves the twin to this one) and the narrow share that keeps its log check from being vacuous"""
+    rng = np.random.default_rng(win + hop if (win, hop, pow2, n_mels, L) in PATH_GRID else win)
     x = noise(rng, 1, L)
     for snip in (True, False):
         spec = KaldiFbank(16000, win, hop, n_mels, round_to_power_of_two=pow2, snip_edges=snip, log=False)

@@ -8,6 +8,8 @@ import re
 import numpy as np
 import pytest
 
+from test_fbank_spec import PATHS, paths_length
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (win, hop, filters, cepstra, L, snip_edges): tests/test_mfcc.py's grid
 GRID = [(400, 160, 23, 13, 5000, True), (400, 160, 80, 80, 5000, False), (25, 10, 8, 5, 333, True), (16, 1, 4, 4, 40, True),
@@ -159,7 +161,8 @@ def test_silence():
 
 @pytest.fixture(scope="module")
 def on_the_grid():
-    """(out, dC, the twin's result) for every case of the grid, computed once"""
+    """(out, dC, the twin's result) for every case of the grid and, with both values of snip_edges, of the code-path grid that
+    tests/test_kaldi_paths.py runs on the device (tests/test_fbank_spec.py: PATHS), computed once"""
     import alac.net_amd as pkg
 
     res = {}
@@ -168,6 +171,12 @@ def on_the_grid():
         x = noise(np.random.default_rng(win), 1, L)
         out, dC = pkg.mfcc_host(x, spec, bound=True)
         res[win, n_mels] = (out, dC, pkg.mfcc_host_f32(x, spec))
+    for win, hop, n_mels, n_ceps, frames in PATHS:
+        x = noise(np.random.default_rng(win + hop), 1, paths_length(win, hop, frames))
+        for snip in (True, False):
+            spec = pkg.KaldiMfcc(16000, win, hop, n_mels, n_ceps, snip_edges=snip)
+            out, dC = pkg.mfcc_host(x, spec, bound=True)
+            res["paths", win, hop, n_mels, snip] = (out, dC, pkg.mfcc_host_f32(x, spec))
     return res
 
 
@@ -177,11 +186,19 @@ def test_the_twin_is_inside_the_bound(on_the_grid):
         err = np.abs(twin.astype(np.float64) - out)
         print(f"{key}: max err {err.max():.3e}, max err / dC {np.max(err / dC):.4f}")
         assert (err <= dC).all(), key
-        assert err.max() <= 2e-4, key                                # a float32 evaluation of values of a few units
+        # a float32 evaluation of values of a few units -- but for 256 filters at 2048 taps, the one shape whose dC is not
+        # below 1 (test_the_bound_is_not_vacuous says why): the logs of its lowest filters are ill-conditioned for the twin too
+        assert err.max() <= 2e-4 or key[:4] == ("paths", 2048, 560, 256), key
 
 
 def test_the_bound_is_not_vacuous(on_the_grid):
+    """(2048, 560, 256, 23) of PATHS stays out: 256 filters over 1025 bins are a few bins each, pre-emphasis leaves the lowest
+    of them little power, their logs' intervals are wide and dC reaches 3.4 -- the condition below does not hold there, so
+    tests/test_kaldi_paths.py does not use dC for that shape (it holds the cepstra to the DCT of the fbank kernel's bits)"""
+    assert ("paths", 2048, 560, 256, True) in on_the_grid
     for key, (out, dC, _) in on_the_grid.items():
+        if key[:4] == ("paths", 2048, 560, 256):
+            continue
         print(f"{key}: max dC {dC.max():.4f}, median |out| {np.median(np.abs(out)):.2f}")
         assert (dC > 0).all() and dC.max() <= 1.0, key
         assert np.median(np.abs(out)) > 3.0, key

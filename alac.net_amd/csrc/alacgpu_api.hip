@@ -446,6 +446,7 @@ void alacgpu_destroy(alacgpu_ctx* ctx) {
     ctx->mix.destroy();
     ctx->reverb.destroy();
     if (ctx->d_reverb_twiddles) (void)hipFree(ctx->d_reverb_twiddles);
+    if (ctx->h_reverb_twiddles) (void)hipHostFree(ctx->h_reverb_twiddles);   // (reverb.destroy() has waited for the copy)
     if (ctx->d_cu_arrivals) cu_counters_release(ctx->device);
     if (ctx->h_frame) (void)hipHostFree(ctx->h_frame);
     if (ctx->d_cfgs) (void)hipFree(ctx->d_cfgs);

@@ -102,6 +102,7 @@ struct alacgpu_ctx {
     scratch reverb;  // alacgpu_reverb_device: the spectra of every block of the signal and partition of the impulse response of every row,
                      // [rows, units, ALAC_REVERB_N] float2, and behind them one alac_reverb_row per row (alac_reverb.h)
     void* d_reverb_twiddles = nullptr;   // alacgpu_reverb_device: exp(-2 pi i k / N), float2 [ALAC_REVERB_N], made at the first call
+    void* h_reverb_twiddles = nullptr;   // ... and the page-locked table it is copied from on that call's stream
     std::string last_error;
 };
 
@@ -138,6 +139,19 @@ inline int scratch::release(alacgpu_ctx* ctx, hipStream_t stream) {
     held = false;
     return ALACGPU_OK;
 }
+
+// What a call that acquires a scratch declares in front of the acquire: a return between the acquire and the release (a launch
+// that failed behind others that went out) still records the event on the call's stream, so the next call, whatever its
+// stream, is ordered behind the launches that did go out.  Behind a release it does nothing; last_error stays the call's.
+struct scratch_hold {
+    scratch& s;
+    hipStream_t stream;
+    ~scratch_hold() {
+        if (!s.held) return;
+        if (s.done && hipEventRecord(s.done, stream) == hipSuccess) s.used = true;
+        s.held = false;
+    }
+};
 
 inline void scratch::destroy() {
     if (used) (void)hipEventSynchronize(done);

@@ -73,10 +73,10 @@ int scan_sizes(alacgpu_ctx* ctx, alac_scan_params<uint32_t> s0, const void* sums
     const size_t need = t1 > 1 ? sizeof(uint64_t) * (size_t)(t1 + t2) : 0;
     int rc = ctx->scan.acquire(ctx, stream, need, align_up(need + need / 4, 4096));
     if (rc) return rc;
-    uint64_t* const l1 = (uint64_t*)ctx->scan.buf[0];
+    uint64_t* const l1 = t1 > 1 ? (uint64_t*)ctx->scan.buf[0] : nullptr;   // (one tile: the call owns none of the buffer, and gets none)
     uint64_t* const l2 = l1 ? l1 + t1 : nullptr;
     s0.sums = l1;
-    s0.tile_base = t1 > 1 ? l1 : nullptr;
+    s0.tile_base = l1;
     const dim3 block(ALAC_SCAN_THREADS);
     if (t1 > 1) {
         alac_scan_params<uint64_t> s1 = {};
@@ -273,6 +273,7 @@ int alacgpu_compact_packets_device(alacgpu_ctx* ctx, const void* d_packets, uint
     s0.add = base;
     s0.out = (uint64_t*)d_pkt_offset;
     s0.total = (uint64_t*)d_total;
+    scratch_hold hold{ctx->scan, stream};
     if ((rc = scan_sizes(ctx, s0, (const void*)alac_scan_sums_u32_kernel, (const void*)alac_scan_tiles_u32_kernel, stream))) return rc;
     // the copy: tiles of the destination, as many as the packets can fill at most (the true end is d_total's, on the device)
     const uint64_t most = slot_bytes > UINT64_MAX / n_packets ? UINT64_MAX : slot_bytes * n_packets;
@@ -323,6 +324,7 @@ int alacgpu_stage_packets_device(alacgpu_ctx* ctx, const void* d_blob_lo, uint64
     s0.hi_bytes = hi_bytes;
     s0.out = (uint64_t*)d_stage_offset;
     s0.total = (uint64_t*)d_total;
+    scratch_hold hold{ctx->scan, stream};
     if ((rc = scan_sizes(ctx, s0, (const void*)alac_scan_sums_stage_kernel, (const void*)alac_scan_tiles_stage_kernel, stream))) return rc;
     // the copy: tiles of the staging blob, as many as its capacity holds (the true end is d_total's, on the device)
     if (stage_capacity >= 16u) {
@@ -585,6 +587,7 @@ int alacgpu_normalize_top_device(alacgpu_ctx* ctx, const void* d_src, void* d_ou
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)hip_stream;
     const size_t need = sizeof(float) * (size_t)grid;
+    scratch_hold hold{ctx->norm, stream};
     int rc = ctx->norm.acquire(ctx, stream, need, align_up(need + need / 4, 4096));
     if (rc) return rc;
     alac_top_params p;
@@ -671,24 +674,29 @@ int alacgpu_reverb_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, cons
     if (rows == 0) return ALACGPU_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)hip_stream;
-    if (!ctx->d_reverb_twiddles) {                          // once per ctx: exp(-2 pi i k / N) in double, rounded once
-        std::vector<float2> table(ALAC_REVERB_N);
+    const size_t spectra = sizeof(float2) * ALAC_REVERB_N * (size_t)(units - 1u) * rows;
+    const size_t need = spectra + sizeof(alac_reverb_row) * (size_t)rows;
+    scratch_hold hold{ctx->reverb, stream};
+    int rc = ctx->reverb.acquire(ctx, stream, need, align_up(need + need / 4, 4096));
+    if (rc) return rc;
+    if (!ctx->d_reverb_twiddles) {
+        // once per ctx: exp(-2 pi i k / N) in double, rounded once, in page-locked memory of the ctx and copied on the call's own
+        // stream in front of its launches -- a synchronous copy would hold the host behind whatever else the device is busy with
+        if (!ctx->h_reverb_twiddles) HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_reverb_twiddles, sizeof(float2) * ALAC_REVERB_N));
+        float2* const table = (float2*)ctx->h_reverb_twiddles;
         for (uint32_t k = 0; k < ALAC_REVERB_N; k++) {
             const double a = 2.0 * 3.14159265358979323846 * (double)k / (double)ALAC_REVERB_N;
             table[k] = make_float2((float)std::cos(a), (float)-std::sin(a));
         }
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_reverb_twiddles, sizeof(float2) * ALAC_REVERB_N));
-        const hipError_t e = hipMemcpy(ctx->d_reverb_twiddles, table.data(), sizeof(float2) * ALAC_REVERB_N, hipMemcpyHostToDevice);
+        void* d_table = nullptr;
+        HIP_TRY(ctx, hipMalloc(&d_table, sizeof(float2) * ALAC_REVERB_N));
+        const hipError_t e = hipMemcpyAsync(d_table, table, sizeof(float2) * ALAC_REVERB_N, hipMemcpyHostToDevice, stream);
         if (e != hipSuccess) {
-            (void)hipFree(ctx->d_reverb_twiddles);
-            ctx->d_reverb_twiddles = nullptr;
+            (void)hipFree(d_table);
             HIP_TRY(ctx, e);
         }
+        ctx->d_reverb_twiddles = d_table;     // (a later call on another stream waits for this call's event, so for the copy)
     }
-    const size_t spectra = sizeof(float2) * ALAC_REVERB_N * (size_t)(units - 1u) * rows;
-    const size_t need = spectra + sizeof(alac_reverb_row) * (size_t)rows;
-    int rc = ctx->reverb.acquire(ctx, stream, need, align_up(need + need / 4, 4096));
-    if (rc) return rc;
     alac_reverb_params p;
     p.src = (const float*)d_src;
     p.out = (float*)d_out;
@@ -735,6 +743,7 @@ int alacgpu_mix_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, const v
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)hip_stream;
     const size_t need = 2u * sizeof(float) * (size_t)grid;
+    scratch_hold hold{ctx->mix, stream};
     int rc = ctx->mix.acquire(ctx, stream, need, align_up(need + need / 4, 4096));
     if (rc) return rc;
     const auto wide = [](const void* base, uint64_t plane_stride) { return ((uintptr_t)base & 15u) == 0u && (plane_stride & 3u) == 0u; };
@@ -791,6 +800,7 @@ int alacgpu_encode_device(alacgpu_ctx* ctx, const void* d_pcm, uint64_t src_elem
     const uint32_t frames = smax(ctx);
     const size_t items = (size_t)round * alac_enc_items(frames);
     const size_t code_bytes = sizeof(uint64_t) * items, pos_bytes = sizeof(uint32_t) * (items + round);
+    scratch_hold hold{ctx->enc, stream};
     int rc = ctx->enc.acquire(ctx, stream, code_bytes, code_bytes, pos_bytes, pos_bytes);
     if (rc) return rc;
     alac_encode_params p;

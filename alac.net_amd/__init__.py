@@ -99,6 +99,9 @@ SYMBOLS = {
     "alacgpu_format_samples": (C.c_size_t, [C.c_int, _VP, C.c_int32, _VP]),
     "alacgpu_last_kernel_ms": (C.c_float, [_VP]),
     "alacgpu_set_output_format": (C.c_int, [_VP, C.c_int]),
+    "alacgpu_set_pairing": (C.c_int, [_VP, C.c_int]),
+    "alacgpu_pairing_stats": (C.c_int, [_VP, _VP]),
+    "alacgpu_pairing_shift_starts": (C.c_int, [_VP]),
     "alacgpu_strerror": (C.c_char_p, [C.c_int]),
     "alacgpu_status_string": (C.c_char_p, [C.c_int]),
     "alacgpu_last_error": (C.c_char_p, [_VP]),
@@ -499,6 +502,22 @@ class AlacGpuContext(_Closing):
         """0: int32 per sample (default).  1: packed little-endian PCM bytes (FormatSamples fused into the store);
         packet p's bytes are pcm[p].view(uint8)[:out_bytes[p]]."""
         _check(lib().alacgpu_set_output_format(self._ctx, fmt), self._ctx)
+
+    def set_pairing(self, on):
+        """Pairing (include/alacgpu.h): decode_batch_device on up to 4096 resident packets it has decoded before takes both
+        channels of a packet in one pass, from a remembered and verified start of channel B.  On by default."""
+        _check(lib().alacgpu_set_pairing(self._ctx, int(bool(on))), self._ctx)
+
+    def pairing_stats(self):
+        """(paired, missed, wrong): packets decoded paired, two-channel packets without a remembered start, packets whose
+        remembered start was wrong, since the context was made.  Waits for the device."""
+        out = np.zeros(3, dtype=np.uint64)
+        _check(lib().alacgpu_pairing_stats(self._ctx, _ptr(out)), self._ctx)
+        return tuple(int(v) for v in out)
+
+    def pairing_shift_starts(self):
+        """For tests of the check: every remembered start one bit on.  Waits for the device."""
+        _check(lib().alacgpu_pairing_shift_starts(self._ctx), self._ctx)
 
     def last_kernel_ms(self):
         return float(lib().alacgpu_last_kernel_ms(self._ctx))

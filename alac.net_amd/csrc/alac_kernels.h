@@ -24,6 +24,16 @@ enum {
     ALACGPU_ST_DEST_RANGE_D = 8
 };
 
+// One entry of the pairing table, 16 bytes, written and read as one vector: the tag -- the packet's device address (48 bits), its
+// size (its low 16 bits beside the address, all of it in the hash) and a hash of the size and the packet's first 16 bytes --
+// and the bit position, from the 16-byte aligned-down packet start, at which channel B's Rice stream starts.  An entry that is
+// torn, stale or from another packet costs a decode (the paired kernel verifies the start), never a wrong result.
+struct alac_pair_entry { uint32_t addr_lo, addr_hi_size, hash, start; };
+static_assert(sizeof(alac_pair_entry) == 16, "one vector store per entry");
+enum { PAIR_COUNTERS = 5 };       // alac_decode_params::pair_stats
+enum { PAIR_WAYS = 8 };           // entries per set of the pairing table: one 128-byte line, looked at by 8 lanes at once
+enum { AB_FLAG_PAIR_LEFT = 8 };   // alac_decode_params::ab_flags: the paired kernel left packets of this group undecoded
+
 struct alac_decode_params {
     const uint8_t* blob;        // 16-byte aligned
     uint64_t blob_limit;        // readable bytes from blob (blob_bytes rounded up to 16)
@@ -51,6 +61,9 @@ struct alac_decode_params {
     // alac_decode_ab_kernel, then alac_decode_ab32_kernel: flag g covers packets 8g .. 8g+7.  The first writes 0 where it
     // decoded the group and 1 where it did not; the second decodes the groups flagged 1 and writes 2 there.  One array per
     // launch pair in flight (the host keeps a pool, alacgpu_api.hip: launch_slot).
+    // With the paired kernel in front (pair_ran): it sets the flag of a group of which it left four packets undecoded to
+    // AB_FLAG_PAIR_LEFT (the flags are zeroed in front of it); alac_decode_ab_small_kernel then decodes the groups flagged so,
+    // all eight packets, and leaves the others alone (their flag stays 0).
     uint32_t* ab_flags;
     // Two-pass kernels: one counter per CU (index: XCC_ID, SE_ID, SH_ID, CU_ID), bumped by every workgroup that starts
     // there; its value, the workgroup's turn on the CU, rotates the roles of the workgroup's waves over the SIMDs.
@@ -71,6 +84,18 @@ struct alac_decode_params {
     uint64_t out_elems;
     uint64_t plane_stride;
     uint32_t channels, layout, dtype;
+    // Pairing (alac_decode_ab_pair_kernel): where channel B of a two-channel packet starts, remembered from
+    // an earlier decode of the same packet.  pair_table: pair_mask + 1 sets (a power of two) of PAIR_WAYS entries, null
+    // in calls that neither read nor write it; the two-pass kernels write an entry per compressed two-channel packet, the paired
+    // kernel reads them.  pair_stats: PAIR_COUNTERS device counters -- packets the paired kernel finished with a verified start,
+    // packets it found no entry for, packets whose remembered start was wrong, workgroups that left their packets to the launch
+    // behind (for any reason), workgroups that finished theirs; pair_stats_host: their page-locked copy, brought up
+    // to date by the launch behind the paired kernel.  pair_ran: the paired kernel ran in front of this launch.
+    alac_pair_entry* pair_table;
+    uint32_t pair_mask;
+    uint32_t pair_ran;
+    unsigned long long* pair_stats;
+    unsigned long long* pair_stats_host;
 };
 
 #ifdef __HIPCC__
@@ -78,6 +103,11 @@ struct alac_decode_params {
 extern "C" __global__ void alac_decode_ab_kernel(alac_decode_params p);
 extern "C" __global__ void alac_decode_ab5_kernel(alac_decode_params p);         // the same with 96 registers (five workgroups per CU)
 extern "C" __global__ void alac_decode_ab_small_kernel(alac_decode_params p);   // the same with 16-step units (batches up to 4096 packets)
+// one pass, 4 packets / workgroup, both channels of a packet side by side from a remembered start of channel B; in front of
+// alac_decode_ab_small_kernel, which decodes what this one leaves
+extern "C" __global__ void alac_decode_ab_pair_kernel(alac_decode_params p);
+// test hook (alacgpu_pairing_shift_starts): every remembered start + 1
+extern "C" __global__ void alac_pair_shift_kernel(alac_pair_entry* table, uint32_t entries);
 // the second launch, for the groups of 8 packets the first one flagged: two taps per lane of the FIR wave (orders 9..16) or
 // four (any order, delta mode, order 0)
 extern "C" __global__ void alac_decode_ab32_kernel(alac_decode_params p);

@@ -550,7 +550,40 @@ __device__ __forceinline__ uint32_t ab_entropy_pass(const alac_decode_params& p,
     return ended ? endpos : rice_bitpos(rs);
 }
 
-template <int NS>
+// ALAC_PAIRING=1: the object takes part in pairing (see ab_pair_body) -- its two-pass kernels remember where channel B starts, and
+// its first launch leaves the groups alone that the paired kernel finished.  The small-batch object (its plain kernel: the
+// window build stays as it was) and the paired kernel's do; the others carry none of it.
+#ifndef ALAC_PAIRING
+#define ALAC_PAIRING 0
+#endif
+constexpr bool PAIRING = ALAC_PAIRING != 0;
+// Pairing table (alac_pair_entry): a packet's tag and its place in the table.  The hash takes the packet's size and its first 16
+// bytes (zeros behind a shorter packet's end).
+struct PairKey { uint32_t addr_lo, addr_hi_size, hash, idx; };
+__device__ __forceinline__ PairKey pair_key(const alac_decode_params& p, uint32_t pkt, const Meta& m) {
+    const uint64_t off = p.offsets[pkt];
+    const uint32_t size = p.sizes[pkt];
+    const uint64_t addr = (uint64_t)(uintptr_t)p.blob + off;
+    const uint32_t bit0 = (uint32_t)(off & 15u) * 8u;
+    uint32_t h = size * 0x9E3779B1u;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        h = (h ^ peek_bits(m.base, m.limit, bit0 + 32u * (uint32_t)k, 32)) * 0x85EBCA6Bu;
+        h ^= h >> 15;
+    }
+    PairKey key;
+    key.addr_lo = (uint32_t)addr;
+    key.addr_hi_size = (uint32_t)(addr >> 32) ^ (size << 16);
+    key.hash = h;
+    key.idx = ((uint32_t)((addr * 0x9E3779B97F4A7C15ull) >> 40) & p.pair_mask) * (uint32_t)PAIR_WAYS;   // the set's first entry
+    return key;
+}
+__device__ __forceinline__ bool pair_match(const uint4& e, const PairKey& key) {
+    return e.x == key.addr_lo && e.y == key.addr_hi_size && e.z == key.hash;
+}
+
+// REMEMBER: the build writes where channel B starts into the pairing table (the plain small-batch kernel only)
+template <int NS, bool REMEMBER = false>
 __device__ __forceinline__ void ab_entropy_wave(const alac_decode_params& p, uint32_t pkt0, int lane, AbSharedT<NS>& sh, int nch0, int nch1) {
     constexpr int LPS = 64 / NS;
     const int g = lane / LPS, sub = lane % LPS;
@@ -580,6 +613,20 @@ __device__ __forceinline__ void ab_entropy_wave(const alac_decode_params& p, uin
                                              compressed && (ph == 0 || m.stereo), g, sub, lane, ph ? nch1 : nch0, &fl DIAG_ONLY(, st));
         if (ph == 0) { end_a = end_b = end; flags_a = fl; }
         else { end_b = end; flags_b = fl; }
+        // where B starts, remembered for the paired kernel (calls that keep a pairing table)
+        // (a stream's lanes look at one way of the packet's set each: the way that holds the packet, else a free one, else any)
+        if (REMEMBER && NS == 8 && ph == 0 && p.pair_table && compressed && m.stereo) {
+            const PairKey key = pair_key(p, pkt, m);
+            const uint4 e = *reinterpret_cast<const uint4*>(&p.pair_table[key.idx + (uint32_t)sub]);
+            const uint32_t mine = (uint32_t)(__builtin_amdgcn_ballot_w64(pair_match(e, key)) >> (8 * g)) & 255u;
+            const uint32_t spare = (uint32_t)(__builtin_amdgcn_ballot_w64((e.x | e.y) == 0u) >> (8 * g)) & 255u;
+            // (the search for a free way starts at a way of the packet's own: two packets that claim ways of one set at the same
+            // moment, in two workgroups, seldom claim the same)
+            const int r = (int)(key.hash >> 29);
+            const uint32_t spare_r = ((spare >> r) | (spare << (8 - r))) & 255u;
+            const int way = mine ? __builtin_ctz(mine) : spare ? (__builtin_ctz(spare_r) + r) & 7 : r;
+            if (sub == way) *reinterpret_cast<uint4*>(&p.pair_table[key.idx + (uint32_t)sub]) = make_uint4(key.addr_lo, key.addr_hi_size, key.hash, end);
+        }
     }
     DIAG_ONLY(if (p.dbg && lane == 0) {
         unsigned long long* d = p.dbg + 8 * blockIdx.x;
@@ -636,12 +683,14 @@ __device__ __forceinline__ void ab_fir_block(FirB<T>& f, const typename XqSel<NS
 // the workgroup this wave serves (always 0 when NS == 8).  L = 16 (orders above 16): a row per stream, TWO waves share the 8
 // streams of the workgroup (w = 0 / 1: streams 0..3 / 4..7): half the taps per lane, so a step of either wave is a little more
 // than half as long -- and the FIR step's serial chain is what such a workgroup waits for.
-template <int T, bool WIDE, bool SPECIAL, int NS, int L = 8>
-__device__ __forceinline__ void ab_fir_wave(const alac_decode_params& p, uint32_t pkt0, int w, int lane, AbSharedT<NS>& sh, int ph, int nchunks) {
+// PAIR (the paired kernel): stream g is channel g >> 2 of packet g & 3, whatever `ph_in`.
+template <int T, bool WIDE, bool SPECIAL, int NS, int L = 8, bool PAIR = false>
+__device__ __forceinline__ void ab_fir_wave(const alac_decode_params& p, uint32_t pkt0, int w, int lane, AbSharedT<NS>& sh, int ph_in, int nchunks) {
     constexpr int QS = NS + 1;
     const int row = lane >> 4, l = lane & 15, par = L == 16 ? 0 : l & 1, jl = L == 16 ? l : l >> 1;
     const int g = L == 16 ? 4 * w + row : 8 * w + 2 * row + par;
-    const uint32_t pkt = pkt0 + (uint32_t)g;
+    const uint32_t pkt = pkt0 + (uint32_t)(PAIR ? g & 3 : g);
+    const int ph = PAIR ? g >> 2 : ph_in;
     const bool valid = pkt < p.n_packets;
     alacgpu_cfg_dev cfg;
     const Meta m = parse_meta(p, pkt, ph, valid, cfg);
@@ -769,11 +818,12 @@ struct AbRefill {
     int r, sub;
     uint32_t filled = 0, cnt = 0;
     uint4 v[ROUNDS];
-    __device__ AbRefill(const alac_decode_params& p, uint32_t pkt0, int w, int lane, AbSharedT<NS>& sh_) : sh(sh_) {
+    // pair (the paired kernel): stream r reads packet r & 3
+    __device__ AbRefill(const alac_decode_params& p, uint32_t pkt0, int w, int lane, AbSharedT<NS>& sh_, bool pair = false) : sh(sh_) {
         r = 8 * w + (lane >> 3);
         sub = lane & 7;
         ring = sh.rings[r];
-        const uint32_t pk = pkt0 + (uint32_t)r;
+        const uint32_t pk = pkt0 + (uint32_t)(pair ? r & 3 : r);
         base = p.blob;
         limit = 0;
         if (pk < p.n_packets) {                // as parse_meta: 16-byte aligned-down packet start, bytes up to the packet's end
@@ -1024,6 +1074,250 @@ __device__ __forceinline__ void ab_fir_role(const alac_decode_params& p, uint32_
     }
 }
 
+// The role of a workgroup's wave, by the SIMD it landed on and the workgroup's turn on its CU (ab_kernel_body says why); in
+// wave order without the counters or when the waves do not sit one per SIMD.
+template <int NS>
+__device__ __forceinline__ int ab_role(const alac_decode_params& p, AbSharedT<NS>& sh, int wave, int lane) {
+    int role = wave;
+    if (p.cu_arrivals) {
+        const uint32_t hw = __builtin_amdgcn_s_getreg(63492);                       // HW_ID
+        const uint32_t my_simd = (hw >> 4) & 3u;
+        if (threadIdx.x == 0) {
+            const uint32_t cu = ((__builtin_amdgcn_s_getreg(63508) & 7u) << 8) | (((hw >> 13) & 7u) << 5) | (((hw >> 12) & 1u) << 4) | ((hw >> 8) & 15u);
+            sh.ring_next[NS - 1] = atomicAdd(&p.cu_arrivals[cu], 1u);               // (ring_next / ring_on are free until the first pass)
+        }
+        if (lane == 0) sh.ring_on[wave] = my_simd;
+        wg_sync();
+        const uint32_t used = (1u << sh.ring_on[0]) | (1u << sh.ring_on[1]) | (1u << sh.ring_on[2]) | (1u << sh.ring_on[3]);
+        if (used == 15u) role = (int)((my_simd - sh.ring_next[NS - 1]) & 3u);       // (else: not one wave per SIMD -- wave order)
+    }
+    return role;
+}
+
+// ===================================================================================================================
+// The paired kernel: ONE pass over 4 packets per workgroup.  Stream g < 4 is channel A of packet g, stream g + 4 channel B of
+// the same packet, decoded side by side: B from the bit position an earlier decode of the packet remembered
+// (alac_decode_params::pair_table).  Where A ends is where B starts, so when A is done the entropy wave knows whether the
+// remembered start was right; only then it writes status and lengths.  A workgroup whose packets do not all qualify, or whose
+// remembered start was wrong, flags its group of 8 (AB_FLAG_PAIR_LEFT) for the two-pass kernel behind it, which overwrites
+// whatever PCM this one stored.  A decode from a wrong start reads its ring (address-masked; refills clamped to the packet)
+// and stores frames i < n of the packet's own slot, like any other: wrong values, never a wrong place.
+// The roles, the queues and the barriers are the two-pass kernels' (one pass of nchunks + 2); the output wave un-mixes
+// stream g with stream g + 4 straight from the FIR wave's queue: nothing is parked.
+// ===================================================================================================================
+__device__ __forceinline__ void ab_pair_entropy_wave(const alac_decode_params& p, uint32_t pkt0, int lane, AbSharedT<8>& sh, int nch,
+                                                     uint32_t start_b) {
+    const int g = lane >> 3, sub = lane & 7, ch = g >> 2;
+    const uint32_t pkt = pkt0 + (uint32_t)(g & 3);
+    const bool valid = pkt < p.n_packets;
+    alacgpu_cfg_dev cfg;
+    const Meta m = parse_meta(p, pkt, 0, valid, cfg);
+    const Meta mb = parse_meta(p, pkt, 1, valid, cfg);
+    const bool compressed = valid && m.status == 0 && !m.esc;
+    const bool two = compressed && m.stereo;
+    RiceCfg rc;
+    rc.kmod = cfg.rice_kmodifier;
+    rc.kmask = (1u << (cfg.rice_kmodifier & 31)) - 1u;
+    rc.hist_mult = (ch ? mb.ricemod : m.ricemod) * (cfg.rice_history_mult / 4);
+    rc.rss = m.rss;
+    int fl = 0;
+    DIAG_ONLY(SpecStats st;)
+    const uint32_t end = ab_entropy_pass<8>(p, sh, m, rc, cfg.rice_initial_history, ch ? start_b : m.ricebit, compressed && (ch == 0 || m.stereo),
+                                            g, sub, lane, nch, &fl DIAG_ONLY(, st));
+    const uint32_t end_a = (uint32_t)mirror_i((int)end, lane & 31), end_b = (uint32_t)mirror_i((int)end, (lane & 31) + 32);
+    const int flags_a = mirror_i(fl, lane & 31), flags_b = mirror_i(fl, (lane & 31) + 32);
+    // ---- the verification: A's end is B's start ----
+    const bool owner = valid && sub == 0 && ch == 0;      // one lane per packet
+    const uint64_t wrong = __builtin_amdgcn_ballot_w64(owner && two && end_a != start_b);
+    if (wrong != 0) {
+        if (lane == 0) {
+            atomicAdd(&p.pair_stats[2], (unsigned long long)__builtin_popcountll(wrong));
+            atomicAdd(&p.pair_stats[3], 1ull);
+            p.ab_flags[blockIdx.x >> 1] = AB_FLAG_PAIR_LEFT;
+        }
+        return;
+    }
+    const uint64_t hits = __builtin_amdgcn_ballot_w64(owner && two);
+    if (lane == 0) {
+        atomicAdd(&p.pair_stats[0], (unsigned long long)__builtin_popcountll(hits));
+        atomicAdd(&p.pair_stats[4], 1ull);
+    }
+    // ---- lengths and status, in the reference's control-flow order (as ab_entropy_wave) ----
+    if (owner) {
+        if (p.out_bytes) p.out_bytes[pkt] = m.out_bytes;
+        if (p.out_samples) p.out_samples[pkt] = m.n;
+        int st = m.status;
+        if (st == 0 && !m.esc) {
+            const int nchan = m.stereo ? 2 : 1;
+            for (int c = 0; c < nchan && st == 0; c++) {
+                const int f = c == 0 ? flags_a : flags_b;
+                const int pt = c == 0 ? m.predtype : mb.predtype;
+                const int Nc = c == 0 ? m.N : mb.N;
+                if (f & 1) st = ALACGPU_ST_OVERRUN_D;
+                else if (f & 2) st = ALACGPU_ST_UNSUPPORTED_PARAMS_D;
+                else if (pt != 0) st = ALACGPU_ST_UNSUPPORTED_PREDTYPE_D;
+                else if (Nc == 0 && m.n > 4096) st = ALACGPU_ST_REF_THROWS_D;
+            }
+            const uint32_t last = m.stereo ? end_b : end_a;
+            if (st == 0 && last > m.size_bits_end) st = ALACGPU_ST_OVERRUN_D;
+        } else if (st == 0 && m.esc) {
+            const uint32_t last = m.rawbit + (uint32_t)(m.n * (m.stereo ? 2 : 1) * m.ss);
+            if (last > m.size_bits_end) st = ALACGPU_ST_OVERRUN_D;
+        }
+        p.status[pkt] = st;
+    }
+}
+
+// The paired kernel's output wave.  Lane 2 t + par of row r of the FIR wave's queue holds out[last - t] of stream 2 r + par:
+// channel A of packet 2 r + par in rows 0 / 1, its channel B 32 lanes further on.  Lanes 0..31 take the first two blocks of 8
+// samples of a chunk, lanes 32..63 (the same packets) the other two.
+struct AbPairOut {
+    const alac_decode_params& p;
+    AbSharedT<8>& sh;
+    int lane, la, j, hsel;
+    Meta m;
+    int n_out, bias;
+    int32_t* pcm_slot;
+    AbRefill<8> rf;
+    int cs, cq;             // conversion: this lane's stream and the quantiser mask (1 << q) - 1 of its channel
+    __device__ __forceinline__ AbPairOut(const alac_decode_params& p_, uint32_t pkt0, int lane_, AbSharedT<8>& sh_)
+        : p(p_), sh(sh_), lane(lane_), rf(p_, pkt0, 0, lane_, sh_, true) {
+        la = lane & 31;
+        hsel = lane >> 5;
+        j = (la & 15) >> 1;
+        const uint32_t pkt = pkt0 + (uint32_t)(2 * (la >> 4) + (la & 1));
+        const bool valid = pkt < p.n_packets;
+        alacgpu_cfg_dev cfg;
+        m = parse_meta(p, pkt, 0, valid, cfg);
+        n_out = (valid && m.status == 0) ? m.n : 0;
+        bias = 1 << (m.rss - 1);
+        pcm_slot = p.pcm_out + (int64_t)pkt * p.slot_ints;
+        cs = QROWS ? lane >> 3 : lane & 7;
+        const uint32_t cpkt = pkt0 + (uint32_t)(cs & 3);
+        cq = (1 << parse_meta(p, cpkt, cs >> 2, cpkt < p.n_packets, cfg).q) - 1;
+    }
+    // after barrier b: chunk b's code values -> what the FIR step wants; chunk b-2's outputs are in the queue
+    __device__ __forceinline__ void step(int b, int nch) {
+        if (b < nch) {
+            rf.issue(b == 0);
+            const auto& src = sh.resq[b & 1];
+            XQ (*dst)[9] = sh.xq[b & 1];
+#pragma unroll
+            for (int k = 0; k < AB_CHUNK / 8; k++) {
+                const int i = QROWS ? (lane & 7) + 8 * k : (lane >> 3) + 8 * k;
+                XQ x;
+                xq_from_code(x, (uint32_t)(QROWS ? src[cs][i] : src[i][cs]), cq);
+                dst[i][cs] = x;
+            }
+        }
+        if (b >= 2) {
+            const int c = b - 2;
+            const UbWin none = {0u, 0u};
+#pragma unroll
+            for (int hh = 0; hh < AB_CHUNK / 16; hh++) {
+                const int half = (AB_CHUNK / 16) * hsel + hh;
+                const int ih = c * AB_CHUNK + 8 * half;
+                const int cnt = min(8, n_out - ih);
+                if (j >= cnt) continue;
+                const int a = sh.outq[c & 1][half][la] - bias;
+                if (m.esc) {                                            // uncompressed: raw samples (as AbOutBlock::pass0_step)
+                    const int i = ih + j;
+                    const int nchan = m.stereo ? 2 : 1;
+                    for (int ch = 0; ch < nchan; ch++) {
+                        const uint32_t bp = m.rawbit + (uint32_t)((i * nchan + ch) * m.ss);
+                        int val = __builtin_amdgcn_sbfe((int)peek_bits(m.base, m.limit, bp, m.ss), 0, m.ss);
+                        if (m.ss == 24) val = __builtin_amdgcn_sbfe(val, 0, 24);
+                        if (ch < m.nc) store_sample<false>(p, m, pcm_slot, 0u, i, ch, val);
+                    }
+                    if (!m.stereo && m.nc > 1) store_sample<false>(p, m, pcm_slot, 0u, i, 1, 0);
+                    continue;
+                }
+                const int i = ih + cnt - 1 - j;
+                if (!m.stereo) {                                        // one channel
+                    store_sample<false>(p, m, pcm_slot, 0u, i, 0, ab_finish24<false>(m, none, a, i, 0));
+                    if (m.nc > 1) store_sample<false>(p, m, pcm_slot, 0u, i, 1, 0);
+                    continue;
+                }
+                const int bb = sh.outq[c & 1][half][la + 32] - bias;
+                int left, right;
+                if (m.mixweight != 0) {                                 // AlacFile.cs:346-357 / :377-388
+                    right = wsub(a, wmul(bb, m.mixweight) >> (m.mixshift & 31));
+                    left = wadd(right, bb);
+                } else {
+                    left = a;
+                    right = bb;
+                }
+                store_sample<false>(p, m, pcm_slot, 0u, i, 0, ab_finish24<false>(m, none, left, i, 0));
+                if (m.nc > 1) store_sample<false>(p, m, pcm_slot, 0u, i, 1, ab_finish24<false>(m, none, right, i, 1));
+            }
+        }
+        if (b < nch) rf.commit();
+    }
+};
+
+__device__ __forceinline__ void ab_pair_body(const alac_decode_params& p, AbSharedT<8>& sh) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t pkt0 = blockIdx.x * 4u;
+    // every wave reads the four headers and looks the two-channel packets up: what the workgroup does is uniform
+    int n0 = 0;
+    bool bad = false, miss = false, two = false;
+    uint32_t start_b = 0;
+    {
+        const uint32_t pk = pkt0 + (uint32_t)(lane & 3);
+        const bool v = pk < p.n_packets;
+        alacgpu_cfg_dev c;
+        const Meta ma = parse_meta(p, pk, 0, v, c);
+        const Meta mb = parse_meta(p, pk, 1, v, c);
+        const bool ok = v && ma.status == 0;
+        const bool comp = ok && !ma.esc;
+        n0 = ok ? ma.n : 0;
+        // what the one-tap-per-lane FIR step without the wide multiply takes, and room for the two-pass kernels' parking place
+        // (parse_meta turns a slot without it into a status only for a one-channel stream cfg)
+        bad = comp && (ma.N < 1 || ma.N > 8 || (ma.stereo && (mb.N < 1 || mb.N > 8)) || (!ma.stereo && ma.predtype != 0) || ma.rss > 23 ||
+                       (ma.stereo && (uint64_t)2 * (uint64_t)ma.n > p.slot_ints));
+        // lane 4 w + k looks at way w of packet k's set (the upper half of the wave repeats the lower)
+        two = comp && ma.stereo;
+        uint4 e = make_uint4(0u, 0u, 0u, 0u);
+        bool found = false;
+        if (two) {
+            const PairKey key = pair_key(p, pk, ma);
+            e = *reinterpret_cast<const uint4*>(&p.pair_table[key.idx + (uint32_t)((lane >> 2) & (PAIR_WAYS - 1))]);
+            found = pair_match(e, key) && e.w >= ma.ricebit;
+        }
+        const uint32_t ways = (uint32_t)__builtin_amdgcn_ballot_w64(found) & (0x11111111u << (lane & 3));
+        miss = two && ways == 0u;
+        start_b = (uint32_t)mirror_i((int)e.w, ways ? __builtin_ctz(ways) : lane);
+    }
+    const uint64_t misses = __builtin_amdgcn_ballot_w64(miss && lane < 4);
+    // (a workgroup without a two-channel packet has nothing to pair: the two-pass kernel decodes 8 such packets per workgroup)
+    if (misses != 0 || __builtin_amdgcn_ballot_w64(bad) != 0 || __builtin_amdgcn_ballot_w64(two) == 0) {
+        if (threadIdx.x == 0) {
+            if (misses != 0) atomicAdd(&p.pair_stats[1], (unsigned long long)__builtin_popcountll(misses));
+            atomicAdd(&p.pair_stats[3], 1ull);
+            p.ab_flags[blockIdx.x >> 1] = AB_FLAG_PAIR_LEFT;
+        }
+        return;
+    }
+    const int nch = (__builtin_amdgcn_readfirstlane(wave_max(n0)) + AB_CHUNK - 1) / AB_CHUNK;
+    for (int t = threadIdx.x; t < 2 * AB_CHUNK; t += blockDim.x) xq_zero(sh.xq[t / AB_CHUNK][t % AB_CHUNK][8]);
+    const int role = ab_role<8>(p, sh, wave, lane);
+    if (role == 3) return;     // the fourth wave was only there to claim the fourth SIMD
+    wg_sync();
+    if (role == 0) {
+        __builtin_amdgcn_s_setprio(ALAC_ENTROPY_PRIO);
+        ab_pair_entropy_wave(p, pkt0, lane, sh, nch, (uint32_t)mirror_i((int)start_b, (lane >> 3) & 3));
+    } else if (role == 1) {
+        AbPairOut out(p, pkt0, lane, sh);
+        for (int b = 0; b <= nch + 1; b++) {
+            wg_sync();
+            out.step(b, nch);
+        }
+    } else {
+        __builtin_amdgcn_s_setprio(1);
+        ab_fir_wave<1, false, false, 8, 8, true>(p, pkt0, 0, lane, sh, 0, nch);
+    }
+}
+
 // TSEL: which groups of 8 packets this body decodes, by the FIR layout they need --
 //   1  first launch, 8-packet workgroups: orders 1..8 (one tap per lane); others are flagged for the second launch
 //   0  first launch, dense arrangement (NS == 16): orders 1..16, one or two taps per lane per FIR wave; others flagged
@@ -1035,7 +1329,16 @@ __device__ __forceinline__ void ab_kernel_body(const alac_decode_params& p, AbSh
     static_assert((TSEL == 0) == (NS == 16), "the dense arrangement exists for the first launch only");
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t pkt0 = blockIdx.x * (uint32_t)NS;
-    // ab_flags[group]: 0 = decoded by the first launch; left for the second launch (alac_decode_ab32_kernel): 1 = to its
+    // Behind the paired kernel: its counters go to their page-locked copy (the host looks at them without waiting), and the groups
+    // it finished are done -- their flag stays 0, which is what the second launch skips.
+    if (PAIRING && TSEL == 1 && !WIN && p.pair_ran) {
+        if (blockIdx.x == 0 && threadIdx.x < PAIR_COUNTERS) {
+            p.pair_stats_host[threadIdx.x] = p.pair_stats[threadIdx.x];
+            __threadfence_system();
+        }
+        if (p.ab_flags[blockIdx.x] != AB_FLAG_PAIR_LEFT) return;
+    }
+    // ab_flags[group]: 0 = decoded by the first launch; AB_FLAG_PAIR_LEFT = left to the first launch by the paired kernel; left for the second launch (alac_decode_ab32_kernel): 1 = to its
     // four-taps-per-lane code, 3 = to its two-taps-per-lane code; 2 / 4 = decoded there.
     // every wave reads all headers: pass lengths (uniform over the workgroup) and which FIR layout fits
     int n0 = 0, n1 = 0;
@@ -1100,19 +1403,7 @@ __device__ __forceinline__ void ab_kernel_body(const alac_decode_params& p, AbSh
     // wave for that, which leaves at once), takes its turn k on the CU from a counter, and puts entropy on SIMD k, output on
     // k + 1, FIR on k + 2 (the dense arrangement: its second FIR wave on k + 3).  Workgroups with consecutive turns so
     // never pair two heavy waves; four per CU load every SIMD alike.
-    int role = wave;
-    if (p.cu_arrivals) {
-        const uint32_t hw = __builtin_amdgcn_s_getreg(63492);                       // HW_ID
-        const uint32_t my_simd = (hw >> 4) & 3u;
-        if (threadIdx.x == 0) {
-            const uint32_t cu = ((__builtin_amdgcn_s_getreg(63508) & 7u) << 8) | (((hw >> 13) & 7u) << 5) | (((hw >> 12) & 1u) << 4) | ((hw >> 8) & 15u);
-            sh.ring_next[NS - 1] = atomicAdd(&p.cu_arrivals[cu], 1u);               // (ring_next / ring_on are free until the first pass)
-        }
-        if (lane == 0) sh.ring_on[wave] = my_simd;
-        wg_sync();
-        const uint32_t used = (1u << sh.ring_on[0]) | (1u << sh.ring_on[1]) | (1u << sh.ring_on[2]) | (1u << sh.ring_on[3]);
-        if (used == 15u) role = (int)((my_simd - sh.ring_next[NS - 1]) & 3u);       // (else: not one wave per SIMD -- wave order)
-    }
+    const int role = ab_role<NS>(p, sh, wave, lane);
     // Orders above 16: small batches (one workgroup per CU at most: every heavy wave has a SIMD to itself and the launch is as
     // long as the FIR step's serial chain) split the 8 streams over TWO FIR waves with 16 lanes per stream and two taps per lane
     // (a step of 41 issue slots instead of 65); bigger batches, where the SIMDs are shared, take the ONE wave with 8 lanes per
@@ -1122,7 +1413,7 @@ __device__ __forceinline__ void ab_kernel_body(const alac_decode_params& p, AbSh
     wg_sync();
     if (role == 0) {
         __builtin_amdgcn_s_setprio(ALAC_ENTROPY_PRIO);
-        ab_entropy_wave<NS>(p, pkt0, lane, sh, nch0, nch1);
+        ab_entropy_wave<NS, PAIRING && TSEL == 1 && !WIN>(p, pkt0, lane, sh, nch0, nch1);
     } else if (role == 1) {
         ab_output_wave<NS, WIN>(p, pkt0, lane, sh, nch0, nch1);
     } else {
@@ -1145,7 +1436,7 @@ __device__ __forceinline__ void ab_kernel_body(const alac_decode_params& p, AbSh
 
 }  // namespace
 
-// One kernel entry per object file: the Makefile compiles this source five times (-DALAC_EMIT=1 .. 5), each kernel with
+// One kernel entry per object file: the Makefile compiles this source six times (-DALAC_EMIT=1 .. 6), each kernel with
 // the instruction-scheduler settings it measured best with (Makefile: SCHED_*).  Without ALAC_EMIT all of them are emitted.
 #if !defined(ALAC_EMIT) || ALAC_EMIT == 1
 // The main kernel for batches whose workgroups fit the chip four per CU (up to 10240 packets): 128 registers, nothing spilled.
@@ -1171,6 +1462,14 @@ extern "C" __global__ __launch_bounds__(256, 4) void alac_decode_ab_small_kernel
 extern "C" __global__ __launch_bounds__(256, 4) void alac_decode_ab_small_win_kernel(alac_decode_params p) {
     __shared__ __attribute__((aligned(1024))) AbSharedT<8> sh;
     ab_kernel_body<1, 8, true>(p, sh);
+}
+#endif
+#if !defined(ALAC_EMIT) || ALAC_EMIT == 6
+// The paired kernel, its object compiled as the small-batch build's: batches of up to 4096 packets whose packets were decoded
+// before (alacgpu_api.hip: launch), in front of alac_decode_ab_small_kernel.
+extern "C" __global__ __launch_bounds__(256, 4) void alac_decode_ab_pair_kernel(alac_decode_params p) {
+    __shared__ __attribute__((aligned(1024))) AbSharedT<8> sh;
+    ab_pair_body(p, sh);
 }
 #endif
 #if !defined(ALAC_EMIT) || ALAC_EMIT == 4
@@ -1235,6 +1534,12 @@ extern "C" __global__ __launch_bounds__(256) void alac_window_first_kernel(const
                                                                           uint64_t* first, uint32_t n_packets) {
     const uint32_t pkt = blockIdx.x * 256u + threadIdx.x;
     if (pkt < n_packets) first[pkt] = src_skip[pkt] > (uint32_t)BUFFER_SIZE ? ~0ull : dst_first[pkt];
+}
+// Test hook (alacgpu_pairing_shift_starts): every remembered start of the pairing table one bit further on, so that the paired
+// kernel's verification has something to refuse.
+extern "C" __global__ __launch_bounds__(256) void alac_pair_shift_kernel(alac_pair_entry* table, uint32_t entries) {
+    const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+    if (e < entries) table[e].start += 1u;
 }
 #endif
 #if !defined(ALAC_EMIT) || ALAC_EMIT == 3

@@ -106,17 +106,87 @@ const void* window_build(const void* k) {
     return (const void*)alac_decode_ab_win_kernel;
 }
 
+// Pairing: the context's table and counters, made or grown for a batch of n_packets and zeroed on the call's stream.  A table that
+// grows is replaced once every launch in flight has finished with the old one (rare: the largest batch seen got larger); what a
+// launch on another stream reads of it before the zeros arrive is refused by the paired kernel's check like any stale entry.
+int pair_prepare(alacgpu_ctx* ctx, uint32_t n_packets, hipStream_t stream) {
+    constexpr size_t stats_bytes = PAIR_COUNTERS * sizeof(unsigned long long);
+    if (!ctx->d_pair_stats) {
+        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_pair_stats, stats_bytes, hipHostMallocDefault));
+        std::memset(ctx->h_pair_stats, 0, stats_bytes);
+        HIP_TRY(ctx, hipHostGetDevicePointer((void**)&ctx->h_pair_stats_dev, ctx->h_pair_stats, 0));
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_pair_stats, stats_bytes));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_pair_stats, 0, stats_bytes, stream));
+    }
+    size_t entries = PAIR_TABLE_MIN;
+    while (entries < (size_t)PAIR_TABLE_FACTOR * n_packets) entries *= 2;
+    if (entries * sizeof(alac_pair_entry) > ctx->pair_table_bytes) {
+        for (launch_slot& sl : ctx->slots)
+            if (sl.used) HIP_TRY(ctx, hipEventSynchronize(sl.ev1));
+        const int rc = grow(ctx, ctx->d_pair_table, ctx->pair_table_bytes, entries * sizeof(alac_pair_entry), entries * sizeof(alac_pair_entry));
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_pair_table, 0, ctx->pair_table_bytes, stream));
+    }
+    return ALACGPU_OK;
+}
+
+// A new window of the verdict below, from what the counters' page-locked copy says now.
+void pair_restart(alacgpu_ctx* ctx) {
+    ctx->pair_gave_up = false;
+    ctx->pair_first_window = true;
+    ctx->pair_launches = ctx->pair_idle = 0;
+    for (int i = 0; i < PAIR_COUNTERS; i++) ctx->pair_win[i] = ctx->h_pair_stats ? ((const volatile unsigned long long*)ctx->h_pair_stats)[i] : 0;
+}
+
+// Pairing switches itself off and, much later, tries again (alacgpu_ctx.h: PAIR_WINDOW).  Once per PAIR_WINDOW paired launches,
+// and only when the last launch has finished anyway (no wait), the counters' page-locked copy is set against the window's start.
+void pair_observe(alacgpu_ctx* ctx) {
+    if (ctx->pair_gave_up) {
+        if (++ctx->pair_idle >= PAIR_RETRY) pair_restart(ctx);
+        return;
+    }
+    if (ctx->pair_launches < PAIR_WINDOW || ctx->last_slot < 0) return;
+    if (hipEventQuery(ctx->slots[ctx->last_slot].ev1) != hipSuccess) { (void)hipGetLastError(); return; }
+    const volatile unsigned long long* h = ctx->h_pair_stats;
+    unsigned long long d[PAIR_COUNTERS];
+    for (int i = 0; i < PAIR_COUNTERS; i++) {
+        const unsigned long long now = h[i];
+        d[i] = now - ctx->pair_win[i];
+        ctx->pair_win[i] = now;
+    }
+    const unsigned long long hits = d[0], wrong = d[2], left = d[3], done = d[4];
+    if (done == 0 || wrong > hits || (!ctx->pair_first_window && left * PAIR_DONE_PER_LEFT > done)) ctx->pair_gave_up = true;
+    ctx->pair_first_window = false;
+    ctx->pair_launches = ctx->pair_idle = 0;
+}
+
 // The two-pass kernels: the first launch decodes the groups of 8 packets whose streams have LPC order 1..8 (the dense
 // arrangement: 1..16) and flags the others for the second launch right behind it on the same stream (two or four taps per
 // lane of the FIR wave).  A two-channel element needs room for parking channel A in its slot (2 n <= slot_ints): parse_meta
 // turns anything else into a per-packet status, also a two-channel element in a one-channel stream cfg, which is decoded
 // (its left channel comes out, AlacFile.cs:353-354) when the slot has that room.  Every decode entry point ends here, with
 // its arguments checked.
-int launch(alacgpu_ctx* ctx, const alac_decode_params& p_in, hipStream_t stream) {
+// Pairing: a plain call (slot layout, no window) of up to AB_SMALL_MAX_PACKETS packets on packets that stay where they are
+// (`resident`: not the host-buffer path, whose workspace holds other packets at the same addresses on every call) gets the paired
+// kernel in front: it decodes, in one pass, the groups of 4 packets whose channel B starts were remembered by an earlier call,
+// and the launch pair decodes the rest, remembering theirs.
+int launch(alacgpu_ctx* ctx, const alac_decode_params& p_in, hipStream_t stream, bool resident = true) {
     if (p_in.n_packets == 0) return ALACGPU_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     alac_decode_params p = p_in;
     p.cu_arrivals = ctx->d_cu_arrivals;
+    if (ctx->pairing) pair_observe(ctx);
+    const bool paired = resident && ctx->pairing && !ctx->pair_gave_up && !p.dst_first && !p.src_skip && !p.park &&
+                        first_kernel(ctx, p.n_packets) == (const void*)alac_decode_ab_small_kernel;
+    if (paired) {
+        const int prc = pair_prepare(ctx, p.n_packets, stream);
+        if (prc) return prc;
+        p.pair_table = ctx->d_pair_table;
+        p.pair_mask = (uint32_t)(ctx->pair_table_bytes / sizeof(alac_pair_entry) / PAIR_WAYS) - 1u;
+        p.pair_stats = ctx->d_pair_stats;
+        p.pair_stats_host = ctx->h_pair_stats_dev;
+        p.pair_ran = 1;
+    }
     const int si = (int)(ctx->next_slot++ % N_SLOTS);
     launch_slot& sl = ctx->slots[si];
     if (!sl.ev0) {   // slots come to life on first use (a context that makes one call at a time only ever touches... all eight, in turn)
@@ -153,6 +223,11 @@ int launch(alacgpu_ctx* ctx, const alac_decode_params& p_in, hipStream_t stream)
     if (p.src_skip) {    // window calls: the window builds of both launches (the plain builds carry no window test)
         k = window_build(k);
         k2 = window_build(k2);
+    }
+    if (paired) {   // the flags start at 0; the paired kernel (4 packets per workgroup) marks the groups it leaves
+        HIP_TRY(ctx, hipMemsetAsync(sl.d_flags, 0, sizeof(uint32_t) * groups, stream));
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_decode_ab_pair_kernel, dim3((p.n_packets + 3u) / 4u), dim3(256), kargs, 0, stream));
+        ctx->pair_launches++;
     }
     HIP_TRY(ctx, hipLaunchKernel(k, dim3((uint32_t)first_groups), dim3(256), kargs, 0, stream));
     HIP_TRY(ctx, hipLaunchKernel(k2, dim3((uint32_t)groups), dim3(256), kargs, 0, stream));
@@ -292,7 +367,7 @@ int decode_host(alacgpu_ctx* ctx, const uint8_t* blob, uint64_t blob_bytes, cons
             p.park = d_pcm + (size_t)lo[k] * park_stride;
             p.park_stride = park_stride;
         }
-        if ((rc = launch(ctx, p, s))) return rc;
+        if ((rc = launch(ctx, p, s, false))) return rc;   // (the workspace holds other packets on the next call: no pairing)
     }
     const size_t pitch = sizeof(int32_t) * (size_t)slot_ints;
     const size_t packed_w = std::min(pitch, packed_bytes_per_slot_int(ctx) * (size_t)slot_ints);
@@ -440,6 +515,9 @@ void alacgpu_destroy(alacgpu_ctx* ctx) {
         if (sl.ev1) (void)hipEventDestroy(sl.ev1);
     }
     if (ctx->d_ws) (void)hipFree(ctx->d_ws);
+    if (ctx->d_pair_table) (void)hipFree(ctx->d_pair_table);
+    if (ctx->d_pair_stats) (void)hipFree(ctx->d_pair_stats);
+    if (ctx->h_pair_stats) (void)hipHostFree(ctx->h_pair_stats);
     ctx->enc.destroy();
     ctx->scan.destroy();
     ctx->norm.destroy();
@@ -496,7 +574,7 @@ int alacgpu_dbg_decode_batch_device_stamps(alacgpu_ctx* ctx, const void* d_blob,
                          d_out_bytes, d_out_samples, d_status, ctx->out_format);
     if (rc) return rc;
     p.dbg = (unsigned long long*)d_stamps;
-    return launch(ctx, p, (hipStream_t)hip_stream);
+    return launch(ctx, p, (hipStream_t)hip_stream, false);   // (the stamps are the two-pass kernels': no paired kernel in front)
 }
 #endif
 
@@ -650,6 +728,37 @@ int alacgpu_decode_frame(alacgpu_ctx* ctx, uint32_t cfg_index, const uint8_t* in
 int alacgpu_set_output_format(alacgpu_ctx* ctx, int format) {
     if (!ctx || (format != ALACGPU_OUT_INT32 && format != ALACGPU_OUT_PACKED_LE)) return ALACGPU_ERR_BAD_ARG;
     ctx->out_format = (uint32_t)format;
+    return ALACGPU_OK;
+}
+
+int alacgpu_set_pairing(alacgpu_ctx* ctx, int on) {
+    if (!ctx) return ALACGPU_ERR_BAD_ARG;
+    ctx->pairing = on != 0;
+    if (on) pair_restart(ctx);   // switched on again: a new window
+    return ALACGPU_OK;
+}
+
+int alacgpu_pairing_stats(alacgpu_ctx* ctx, uint64_t* out) {
+    if (!ctx || !out) return ALACGPU_ERR_BAD_ARG;
+    out[0] = out[1] = out[2] = 0;
+    if (!ctx->d_pair_stats) return ALACGPU_OK;   // no paired launch yet
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    unsigned long long v[3];   // (the first three counters: the workgroup counts behind them are the context's own business)
+    HIP_TRY(ctx, hipMemcpy(v, ctx->d_pair_stats, sizeof(v), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 3; i++) out[i] = v[i];
+    return ALACGPU_OK;
+}
+
+int alacgpu_pairing_shift_starts(alacgpu_ctx* ctx) {
+    if (!ctx) return ALACGPU_ERR_BAD_ARG;
+    if (!ctx->d_pair_table) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    uint32_t entries = (uint32_t)(ctx->pair_table_bytes / sizeof(alac_pair_entry));
+    void* args[] = {&ctx->d_pair_table, &entries};
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_pair_shift_kernel, dim3((entries + 255u) / 256u), dim3(256), args, 0, nullptr));
+    HIP_TRY(ctx, hipDeviceSynchronize());
     return ALACGPU_OK;
 }
 

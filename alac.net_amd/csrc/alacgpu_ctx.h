@@ -16,6 +16,20 @@ constexpr int N_SLOTS = 8;          // launch pairs that may be in flight at onc
 constexpr uint32_t AB_SMALL_MAX_PACKETS = 4096;  // up to here: the build with 16-step speculative units (latency-bound launches)
 constexpr uint32_t AB5_MIN_PACKETS = 10241;     // above: the 96-register build of the 8-packet arrangement (five workgroups per CU)
 constexpr uint32_t DENSE_MIN_PACKETS = 12289;   // measured cross-over of the two arrangements of the main kernel
+// Pairing (the paired kernel in front of the small-batch launch).  The table: a power of two of entries, at
+// least PAIR_TABLE_FACTOR times the largest batch seen, in sets of PAIR_WAYS.  (A packet evicted by another sends its whole group
+// of 8 through the two-pass kernel, and ONE such group makes the launch as long as both kernels: direct-mapped at 4 entries per
+// packet, an eighth of cfg2's packets lost their entry and the warm call took 1.14 ms instead of 0.66.)  The verdict: the
+// context looks at the counters every PAIR_WINDOW paired launches and stops the paired launch when the window saw
+//   - no workgroup of the paired kernel finish (batches of one-channel packets, of orders above 8 or more than 23 bits, packets
+//     that are new in every call, a working set that outgrows the table: such calls only pay the empty launch), or
+//   - more packets with a wrong remembered start than packets finished (a caller that rewrites its packets in place), or
+//   - from the second window on (the first holds the cold calls) more than one workgroup that left its packets per
+//     PAIR_DONE_PER_LEFT that finished: a call in which any group falls back takes as long as both kernels.
+// PAIR_RETRY launches later the context tries a window again: what it decodes may have changed.
+constexpr uint32_t PAIR_TABLE_FACTOR = 64, PAIR_TABLE_MIN = 1024;
+constexpr unsigned PAIR_WINDOW = 16, PAIR_RETRY = 4096;
+constexpr unsigned long long PAIR_DONE_PER_LEFT = 1024;
 constexpr int N_HOST_STREAMS = 4;   // chunks of the host-buffer pipeline (H2D k+1 || decode k || D2H k-1)
 constexpr uint32_t MAX_FRAME = 16384;   // the longest frame the reference decodes (its scratch, AlacFile.cs:28)
 
@@ -90,6 +104,17 @@ struct alacgpu_ctx {
     uint32_t* d_cu_arrivals = nullptr; // per-CU workgroup counters (alac_decode_params::cu_arrivals): ONE array per device, shared by
                                        // every context of the process on it (cu_counters_acquire), so that launches of different
                                        // contexts take their turns on a CU from the same counter
+    // pairing: the switch (alacgpu_set_pairing), the context's own verdict (PAIR_WINDOW), the table, the device counters
+    // (alac_decode_params::pair_stats) and their page-locked copy, and what the copy said when the window began
+    bool pairing = true, pair_gave_up = false;
+    alac_pair_entry* d_pair_table = nullptr;
+    size_t pair_table_bytes = 0;
+    unsigned long long* d_pair_stats = nullptr;
+    unsigned long long* h_pair_stats = nullptr;
+    unsigned long long* h_pair_stats_dev = nullptr;   // the copy's device-side address
+    unsigned pair_launches = 0, pair_idle = 0;   // paired launches of the window; launches since the context gave up
+    bool pair_first_window = true;
+    unsigned long long pair_win[PAIR_COUNTERS] = {};
     bool zero_copy = true;             // host-buffer entry points store straight into page-locked output (ALACGPU_ZERO_COPY=0: A/B)
     // grow-only device workspace for the host-buffer entry points
     void* d_ws = nullptr;

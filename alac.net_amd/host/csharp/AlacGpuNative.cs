@@ -179,6 +179,11 @@ namespace ALACdotNET.Decoder
         /// <summary>0: one int per sample (default); 1: packed little-endian PCM, the bytes AlacContext.Read returns
         /// (AlacContext.FormatSamples fused into the store) at the start of every slot; out_bytes[p] of them.</summary>
         [DllImport(Lib)] public static extern int alacgpu_set_output_format(IntPtr ctx, int format);
+        /// <summary>Pairing (include/alacgpu.h): both channels of a resident packet in one pass, from a remembered and verified start
+        /// of channel B; on by default.  Stats: packets decoded paired, without a remembered start, with a wrong one.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_set_pairing(IntPtr ctx, int on);
+        [DllImport(Lib)] public static extern int alacgpu_pairing_stats(IntPtr ctx, [Out] ulong[] out3);
+        [DllImport(Lib)] public static extern int alacgpu_pairing_shift_starts(IntPtr ctx);
         [DllImport(Lib)] public static extern IntPtr alacgpu_alloc_pinned(UIntPtr bytes);
         [DllImport(Lib)] public static extern void alacgpu_free_pinned(IntPtr p);
         [DllImport(Lib)] public static extern float alacgpu_last_kernel_ms(IntPtr ctx);

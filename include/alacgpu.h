@@ -762,6 +762,20 @@ float alacgpu_last_kernel_ms(alacgpu_ctx* ctx);
 enum { ALACGPU_OUT_INT32 = 0, ALACGPU_OUT_PACKED_LE = 1 };
 int alacgpu_set_output_format(alacgpu_ctx* ctx, int format);
 
+/* Pairing: alacgpu_decode_batch_device on up to 4096 packets remembers, per packet (its device address, its size, a hash of its
+ * first 16 bytes), where channel B of a two-channel packet starts; a later call on the same resident packets decodes both channels
+ * side by side in one pass instead of one after the other, and checks the remembered start against where channel A ended: a
+ * packet whose bytes changed in place is decoded again the usual way, the output never depends on the memory being right.  On by
+ * default; a context whose calls gain nothing from it (packets it never finds again, nothing it can pair, starts that keep being
+ * wrong) stops the paired launch by itself after 16 calls and tries again 4096 calls later.  A call on packets it has not seen pays one
+ * nearly empty launch.  Calls with a destination or a window, bigger batches and the host-buffer entry points do not pair.
+ * alacgpu_pairing_stats: out[0] packets decoded paired, out[1] two-channel packets without a remembered start, out[2] packets
+ * whose remembered start was wrong, since the context was made; waits for the device.  alacgpu_pairing_shift_starts moves every
+ * remembered start one bit on (so that each is wrong): for tests of the check, waits for the device. */
+int alacgpu_set_pairing(alacgpu_ctx* ctx, int on);
+int alacgpu_pairing_stats(alacgpu_ctx* ctx, uint64_t* out);
+int alacgpu_pairing_shift_starts(alacgpu_ctx* ctx);
+
 /* Page-locked host memory for batch buffers (blob, offsets, pcm_out ...).  Optional -- every entry point takes ordinary memory
  * too -- but the faster choice: when pcm_out of alacgpu_decode_batch / alacgpu_decode_frame is page-locked (from here, from
  * hipHostMalloc, or registered with hipHostRegister) the kernels store the PCM straight into it while the batch decodes and

@@ -85,6 +85,12 @@ SYMBOLS = {
                                                    C.c_float, _VP]),
     "alacgpu_normalize_top_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
                                                C.c_float, C.c_int, _VP]),
+    "alacgpu_normalize_sliding_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, C.c_uint32,
+                                                   C.c_uint32, C.c_int, C.c_int, _VP]),
+    "alacgpu_vad_energy_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, _VP, C.c_float, C.c_float,
+                                            C.c_uint32, C.c_float, _VP, C.c_uint64, _VP]),
+    "alacgpu_select_frames_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, _VP, C.c_uint64,
+                                               _VP, _VP]),
     "alacgpu_mix_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _VP,
                                      _VP, _VP]),
     "alacgpu_reverb_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
@@ -458,6 +464,45 @@ class AlacGpuContext(_Closing):
         Two launches, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
         rc = lib().alacgpu_normalize_top_device(self._ctx, _dp(d_src), _dp(d_out), rows, lines_per_row, line_stride, line_len, top,
                                                 scale, offset, int(bool(relative)), _VP(stream))
+        _check(rc, self._ctx)
+
+    def normalize_sliding_device(self, d_src, d_out, rows, lines_per_row, line_stride, line_len, d_valid, window, min_window, center,
+                                 norm_vars, stream=0):
+        """alacgpu_normalize_sliding_device: Kaldi's sliding-window CMVN of every line of d_src (float32 device tensor
+        [rows, lines_per_row, line_stride], the first line_len of a line are frames): frame t below v = min(max(d_valid[row],
+        0), line_len) minus the mean of its window of `window` frames (around it with center, else behind it and at least
+        min_window frames long at the start), divided by the window's standard deviation with norm_vars; zeros behind v up to
+        line_len, into d_out (d_src itself or the same layout apart from it).  d_valid: an int64 device tensor [rows], or
+        None for whole lines.  sliding.py states the arithmetic.  One launch, asynchronous on `stream` (raw hipStream_t);
+        nothing is read back."""
+        rc = lib().alacgpu_normalize_sliding_device(self._ctx, _dp(d_src), _dp(d_out), rows, lines_per_row, line_stride, line_len,
+                                                    _dp(d_valid), window, min_window, int(bool(center)), int(bool(norm_vars)),
+                                                    _VP(stream))
+        _check(rc, self._ctx)
+
+    def vad_energy_device(self, d_src, rows, row_stride, line, line_len, d_valid, energy_threshold, energy_mean_scale, frames_context,
+                          proportion_threshold, d_mask, mask_stride, stream=0):
+        """alacgpu_vad_energy_device: Kaldi's energy VAD on the line_len floats at d_src + row * row_stride + line of every
+        row (d_src: a float32 device tensor; row_stride and line in elements) over the first v = min(max(d_valid[row], 0),
+        line_len) of them: frame t is voiced when at least proportion_threshold of the frames within frames_context of it
+        are above energy_threshold + energy_mean_scale * their mean; the decisions, 0 at and behind v, into d_mask (uint8
+        device tensor [rows, mask_stride]).  d_valid: an int64 device tensor [rows], or None for line_len.  vad.py states the
+        arithmetic.  One launch, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_vad_energy_device(self._ctx, _dp(d_src), rows, row_stride, line, line_len, _dp(d_valid), energy_threshold,
+                                             energy_mean_scale, frames_context, proportion_threshold, _dp(d_mask), mask_stride,
+                                             _VP(stream))
+        _check(rc, self._ctx)
+
+    def select_frames_device(self, d_src, d_out, rows, lines_per_row, line_stride, line_len, d_valid, d_mask, mask_stride,
+                             d_new_lengths, stream=0):
+        """alacgpu_select_frames_device: every line of d_src (float32 device tensor [rows, lines_per_row, line_stride], the
+        first line_len of a line are frames) keeps its frames t below v = min(max(d_valid[row], 0), line_len) with
+        d_mask[row, t] != 0 (uint8 device tensor [rows, mask_stride]), in order, zeros behind them up to line_len, into d_out
+        (d_src itself or the same layout apart from it); their number -- d_valid[row] itself where that is negative -- into
+        d_new_lengths (int64 device tensor [rows]; may be d_valid).  d_valid: an int64 device tensor [rows], or None for
+        line_len.  One launch, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_select_frames_device(self._ctx, _dp(d_src), _dp(d_out), rows, lines_per_row, line_stride, line_len,
+                                                _dp(d_valid), _dp(d_mask), mask_stride, _dp(d_new_lengths), _VP(stream))
         _check(rc, self._ctx)
 
     def mix_device(self, d_src, d_out, d_noise, rows, channels, noise_channels, stride, noise_stride, frames, d_valid, d_noise_valid,
@@ -1088,6 +1133,11 @@ from .deltas import Deltas, add_deltas, delta_scales, deltas_host, deltas_host_f
 
 # ---- normalised crops and features (alacgpu_normalize_meanvar_device, alacgpu_normalize_top_device) ------------------------------
 from .normalize import MeanVar, TopDb, normalize, normalize_host, normalize_host_f32  # noqa: E402
+
+# ---- Kaldi's sliding-window CMVN, a third kind of normalize's `how` (alacgpu_normalize_sliding_device), and the energy VAD with
+# ---- the selection of the voiced frames (alacgpu_vad_energy_device, alacgpu_select_frames_device) ---------------------------------
+from .sliding import SlidingMeanVar, sliding_host, sliding_host_f32, sliding_windows  # noqa: E402
+from .vad import EnergyVad, select_frames, select_host, vad_energy, vad_host, vad_host_f32  # noqa: E402
 # ---- noise at a target signal-to-noise ratio into crops and tensors (alacgpu_mix_device) ----------------------------------------
 from .mix import AddNoise, mix, mix_host, mix_host_f32  # noqa: E402
 # ---- room reverberation into crops and tensors (alacgpu_reverb_device) ------------------------------------------------------------

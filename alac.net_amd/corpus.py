@@ -17,11 +17,12 @@ from both tiers into a small staging blob in HBM, and the decode reads that.
 frames a crop needs are decoded as above into a scratch the corpus keeps, and one alacgpu_resample_device call (resample.py
 states the filter) resamples every crop out of it.
 
-`crops(..., reverb=, mix=, features=, normalize=)` runs up to four stages behind the waveform, and `crops` is the one place
+`crops(..., reverb=, mix=, features=, deltas=, vad=, normalize=, augment=)` runs up to eight stages behind the waveform, and `crops` is the one place
 that lists them: the refusals of all of them, the crops the second corpora make (`Corpus._companion_crops`: the noise of an
 AddNoise, then the impulse responses of a Reverb, each cropped by its own corpus at the rate of the crops), the waveform once
-(`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_logmel_device (or alacgpu_fbank_device or alacgpu_mfcc_device), alacgpu_deltas_device and
-the normalisation (reverb.py, mix.py, features.py and normalize.py state the arithmetic), each only if asked for.
+(`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_logmel_device (or alacgpu_fbank_device or alacgpu_mfcc_device), alacgpu_deltas_device,
+alacgpu_vad_energy_device, the normalisation, alacgpu_select_frames_device and alacgpu_specaugment_device (reverb.py, mix.py,
+features.py, deltas.py, vad.py, normalize.py, sliding.py and augment.py state the arithmetic), each only if asked for.
 
 `crops(..., speed=)` plays every crop at a drawn factor in front of all that (the same method, speed.py): the step of a corpus
 whose rates differ, with a ratio per (file rate, factor) in place of one per file rate; the crops at factor 1 go through the
@@ -47,6 +48,8 @@ from .mfcc import KaldiMfcc
 from .features import LogMel
 from .mix import AddNoise, _mix, snr_ratio
 from .normalize import MeanVar, TopDb, _normalize
+from .sliding import LDS_MAX as _SLIDING_LDS_MAX, RING_WINDOW_MAX as _SLIDING_RING_WINDOW_MAX, SlidingMeanVar
+from .vad import EnergyVad, _select_frames, _vad_energy
 from .reverb import Reverb, _reverb
 from .speed import MAX_WIDTH as _SPEED_MAX_WIDTH, SpeedPerturb, ratio as _speed_ratio
 
@@ -386,6 +389,7 @@ class Corpus(_Closing):
         self._rs_scratch = None                           # crops at another rate: the decoded source crops
         self._ft_scratch = None                           # crops(features=): the crops the feature kernel reads
         self._delta_scratch = None                        # crops(deltas=): the features the delta kernel reads
+        self._vad_scratch = None                          # crops(vad=): the decisions between the VAD and the selection
         self._mix_scratch = None                          # crops(mix=): the noise crops, whichever corpus makes them
         self._reverb_scratch = None                       # crops(reverb=): the impulse responses of the crops
         self._rates, self._windows = {}, {}               # `_rate` per (target rate, factors); `_window` per (rate or None, L, factors)
@@ -525,7 +529,7 @@ class Corpus(_Closing):
         if getattr(self, "_gpu", None) is not None:
             self._gpu.close()
             self._gpu = None
-            self._blob = self._plan = self._stage = self._stage_plan = self._rs_scratch = self._ft_scratch = self._delta_scratch = self._mix_scratch = self._reverb_scratch = None
+            self._blob = self._plan = self._stage = self._stage_plan = self._rs_scratch = self._ft_scratch = self._delta_scratch = self._vad_scratch = self._mix_scratch = self._reverb_scratch = None
         self._free_pinned()
 
     @property
@@ -643,7 +647,7 @@ class Corpus(_Closing):
         return torch.from_numpy(f.astype(np.int32)).to(self._dev), torch.from_numpy(o).to(self._dev), True
 
     def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True, features=None, normalize=None, mix=None,
-              reverb=None, speed=None, deltas=None, augment=None, sample_rate=None, mono=False):
+              reverb=None, speed=None, deltas=None, vad=None, augment=None, sample_rate=None, mono=False):
         """Decode crop b = frames frame_offsets[b] .. + num_frames of file files[b] for every b in ONE launch pair: returns
         (pcm [B, C, num_frames] on the device, zero behind lengths[b]; lengths [B], a DEVICE int64 tensor: min(num_frames,
         T_f - offset)).  float32 (default) or int32, as `load`.  files / frame_offsets: sequences, numpy arrays or torch
@@ -667,10 +671,10 @@ class Corpus(_Closing):
         the call without speed=.  Every stage behind it sees the perturbed waveform.  ValueError: int32 crops, a corpus of
         more than 2 channels, draws that are not an integer tensor [B] on the corpus's device.
 
-        The six stages behind the waveform go by keyword, as sample_rate and mono do, and run in this order whichever are
-        given -- reverb, mix, features, deltas, normalize, augment --, in place but for the features and the deltas, by the
-        corpus's own context on the same stream; lengths, `check` and last_status() are those of the
-        call without them (with check=True a second corpus's own check runs too, and first).  ValueError before any device
+        The stages behind the waveform go by keyword, as sample_rate and mono do, and run in this order whichever are
+        given -- reverb, mix, features, deltas, the VAD's decision, normalize, the selection of the voiced frames, augment --,
+        in place but for the features and the deltas, by the corpus's own context on the same stream; lengths (but for vad=,
+        which shortens them), `check` and last_status() are those of the call without them (with check=True a second corpus's own check runs too, and first).  ValueError before any device
         work for what a stage cannot take.
 
         reverb: room reverberation of the waveform: a reverb.Reverb, whose draws are then made here from the device's default
@@ -699,13 +703,24 @@ class Corpus(_Closing):
         feat_lengths): a crop outside the corpus keeps its features as computed and gets zero deltas.  The stages behind it
         see (order + 1) * n_mels lines.  ValueError: no features=.
 
+        vad: a vad.EnergyVad -- the last three steps of the Kaldi speaker recipes behind raw MFCCs, in Kaldi's order: ONE
+        alacgpu_vad_energy_device call decides on feature line vad.line of the first channel of the features as they are
+        behind the deltas and IN FRONT of normalize (compute-vad-decision on the raw features), into a scratch the corpus
+        keeps; normalize runs over all frames (apply-cmvn-sliding); then ONE alacgpu_select_frames_device call moves the
+        voiced frames of every line to its front, zeros behind them (select-voiced-frames).  feat_lengths are then the voiced
+        counts, -1 stays -1, and augment sees those; nothing is read back.  Bit for bit vad.vad_energy, normalize.normalize and
+        vad.select_frames applied in that order to what the call returns without vad= and normalize=.  The decisions are not
+        returned.  ValueError: no features=, vad.line not below the line count in front of it.
+
         normalize: a normalize.MeanVar -- every line over its valid elements: lengths for PCM, feat_lengths for features, so a
-        crop outside the corpus is zeros -- or a normalize.TopDb -- every crop of features, or every channel of it with
-        per_channel.  Bit for bit normalize.normalize(what the call returns without it, normalize, lengths).  ValueError: a
-        TopDb without features, a MeanVar with int32 crops.
+        crop outside the corpus is zeros --, a normalize.TopDb -- every crop of features, or every channel of it with
+        per_channel -- or a sliding.SlidingMeanVar: Kaldi's sliding-window CMVN of every line.  Bit for bit
+        normalize.normalize(what the call returns without it, normalize, lengths).  ValueError: a TopDb without features, a
+        MeanVar or a SlidingMeanVar with int32 crops, a SlidingMeanVar of a window above 7648 on lines of more than 16384
+        elements.
 
         augment: SpecAugment on the features, the last stage: an augment.SpecAugment, whose draws are then made here from the
-        device's default generator (behind an AddNoise's and a Reverb's), or the pair (SpecAugment, draws) with the three
+        device's default generator (behind an AddNoise's and a Reverb's; with vad= for the voiced counts), or the pair (SpecAugment, draws) with the three
         tensors that its `draw(n_mels, feat_lengths)` returned.  Bit for bit augment.spec_augment(what the call returns without
         it, augment, feat_lengths); a crop outside the corpus (feat_lengths -1) is left as it is.  ValueError: no features=,
         draws that are not three int32 tensors [B, 2], [B, masks, 2], [B, masks, 2] on the corpus's device, a time warp of
@@ -722,12 +737,19 @@ class Corpus(_Closing):
         if reverb is not None:
             reverb = self._second_corpus(reverb, _REVERB, dtype, rate, Co)
         if normalize is not None:
-            if not isinstance(normalize, (MeanVar, TopDb)):
-                raise ValueError(f"normalize must be a normalize.MeanVar or a normalize.TopDb, not {normalize!r}")
+            if not isinstance(normalize, (MeanVar, TopDb, SlidingMeanVar)):
+                raise ValueError(f"normalize must be a normalize.MeanVar, a normalize.TopDb or a sliding.SlidingMeanVar, not {normalize!r}")
             if features is None and isinstance(normalize, TopDb):
                 raise ValueError("a TopDb clamps log-mel features: it needs features=")
             if features is None and not _is_f32(torch, dtype):
-                raise ValueError("a MeanVar normalises float32 crops")
+                raise ValueError(f"a {type(normalize).__name__} normalises float32 crops")
+            if isinstance(normalize, SlidingMeanVar) and normalize.window > _SLIDING_RING_WINDOW_MAX:
+                n = _frame_count("num_frames", num_frames) if features is None else None
+                if n is None and isinstance(features, _FEATURES):
+                    n = features.frames(_frame_count("num_frames", num_frames))
+                if n is not None and n > _SLIDING_LDS_MAX:
+                    raise ValueError(f"lines of {n} frames: above {_SLIDING_LDS_MAX} a sliding window takes at most "
+                                     f"{_SLIDING_RING_WINDOW_MAX} frames")
         if features is not None:
             if not isinstance(features, _FEATURES):
                 raise ValueError(f"features must be a features.LogMel or a fbank.KaldiFbank or a mfcc.KaldiMfcc, not {features!r} "
@@ -743,6 +765,14 @@ class Corpus(_Closing):
                 raise ValueError(f"deltas must be a deltas.Deltas, not {deltas!r}")
             if features is None:
                 raise ValueError("Deltas are derivatives of features: they need features=")
+        if vad is not None:
+            if not isinstance(vad, EnergyVad):
+                raise ValueError(f"vad must be a vad.EnergyVad, not {vad!r}")
+            if features is None:
+                raise ValueError("an EnergyVad decides on a feature line: it needs features=")
+            lines = features.n_mels if deltas is None else deltas.lines(features.n_mels)
+            if vad.line >= lines:
+                raise ValueError(f"vad.line {vad.line} of features with {lines} lines")
         if augment is not None:
             augment = _how(augment, "augment")
             if features is None:
@@ -791,8 +821,13 @@ class Corpus(_Closing):
             res, lengths = feats, features.lengths(lengths)
         if deltas is not None:
             res = _add_deltas(ctx, res, deltas, lengths, stacked)
+        if vad is not None:         # Kaldi's order: the decision on the raw features, the selection behind the CMVN
+            voiced = self._scratch("_vad_scratch", ((res.shape[0] * res.shape[-1] + 3) // 4,)).view(torch.uint8)
+            voiced = _vad_energy(ctx, res, vad, lengths, out=voiced[:res.shape[0] * res.shape[-1]].view(res.shape[0], res.shape[-1]))
         if normalize is not None:
             _normalize(ctx, res, normalize, lengths, res)
+        if vad is not None:
+            res, lengths = _select_frames(ctx, res, voiced, lengths, res)
         if augment is not None:
             _spec_augment(ctx, res, augment[0] if augment[1] is None else augment, lengths, res)
         return res, lengths
@@ -1117,15 +1152,17 @@ class Corpus(_Closing):
         return out, lengths
 
     def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True, features=None, normalize=None,
-                     mix=None, reverb=None, speed=None, deltas=None, augment=None, sample_rate=None, mono=False):
+                     mix=None, reverb=None, speed=None, deltas=None, vad=None, augment=None, sample_rate=None, mono=False):
         """`batch` crops of num_frames frames drawn on the device: files uniform over the corpus, the first frame uniform in
         0 .. max(T_f - num_frames, 0).  generator: a torch.Generator (of the corpus's device, or of the CPU: then the draws are
         made there and uploaded).  Returns (pcm, lengths, files, frame_offsets), the draws as device int64 tensors.
         sample_rate / mono as for `crops`: the frames, T_f included, then count at sample_rate.  features as for `crops`:
-        (feats, feat_lengths, files, frame_offsets).  deltas and normalize as for `crops`.  mix as for `crops`; an AddNoise is drawn from
+        (feats, feat_lengths, files, frame_offsets).  deltas, vad and normalize as for `crops`: with vad= feat_lengths are the
+        voiced counts, and nothing is read back for them.  mix as for `crops`; an AddNoise is drawn from
         `generator`, behind the call's own two draws (AddNoise.draw states its four).  reverb as for `crops`; a Reverb is
         drawn from `generator` behind those (Reverb.draw states its two).  augment as for `crops`; a SpecAugment is drawn from
-        `generator` behind those, for the feat_lengths the call returns (augment.py states its draws).  speed as for `crops`;
+        `generator` behind those, for the feat_lengths the call returns (augment.py states its draws) -- with vad= for the
+        lengths in front of the selection, which are known without the device's decisions.  speed as for `crops`;
         a SpeedPerturb is drawn from `generator` behind the call's own two draws and in front of an AddNoise's
         (SpeedPerturb.draw states its two), and the first frame is then uniform in 0 .. max(Ty[f, k] - num_frames, 0), from the
         same u, with the frames of the file at its factor."""
@@ -1145,6 +1182,8 @@ class Corpus(_Closing):
                 raise ValueError("a SpecAugment masks log-mel features: it needs features=")
         if deltas is not None and features is None:
             raise ValueError("Deltas are derivatives of features: they need features=")
+        if vad is not None and features is None:
+            raise ValueError("an EnergyVad decides on a feature line: it needs features=")
         dev = generator.device if generator is not None else self._dev
         files = torch.randint(0, self.num_files, (B,), generator=generator, device=dev, dtype=torch.int64).to(self._dev)
         u = torch.rand(B, generator=generator, device=dev, dtype=torch.float64).to(self._dev)
@@ -1173,7 +1212,7 @@ class Corpus(_Closing):
             augment = (augment[0], augment[0].draw(lines, feat_lengths, generator=generator))
         pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,
                                   features=features, normalize=normalize, mix=mix, reverb=reverb, augment=augment, speed=speed,
-                                  deltas=deltas)
+                                  deltas=deltas, vad=vad)
         return pcm, lengths, files, offs
 
     def last_staged_bytes(self):

@@ -1,5 +1,5 @@
 // alacgpu_stages.hip -- C ABI of include/alacgpu.h, the stages around the decode: the crop planner, the scan with the packet
-// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the reverberation, the noise mix, the normalisations, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
+// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the reverberation, the noise mix, the normalisations, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
 // their own scratch; the decode path is alacgpu_api.hip.  No CPU fallback here either: every stage is its kernels.
 #include <algorithm>
 #include <cmath>
@@ -12,6 +12,8 @@
 #include "alac_mfcc.h"
 #include "alac_deltas.h"
 #include "alac_normalize.h"
+#include "alac_sliding.h"
+#include "alac_vad.h"
 #include "alac_augment.h"
 #include "alac_mix.h"
 #include "alac_reverb.h"
@@ -609,6 +611,117 @@ int alacgpu_normalize_top_device(alacgpu_ctx* ctx, const void* d_src, void* d_ou
     HIP_TRY(ctx, hipLaunchKernel((const void*)alac_top_apply_kernel, dim3((uint32_t)grid), dim3(ALAC_TOP_THREADS), kargs, 0, stream));
     HIP_TRY(ctx, hipGetLastError());
     return ctx->norm.release(ctx, stream);
+}
+
+int alacgpu_normalize_sliding_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t lines_per_row,
+                                     uint64_t line_stride, uint64_t line_len, const void* d_valid, uint32_t window, uint32_t min_window,
+                                     int center, int norm_vars, void* hip_stream) {
+    uint64_t lines;
+    if (!normalize_args_ok(ctx, d_src, d_out, rows, lines_per_row, line_stride, line_len, lines) || !args_ok({{d_valid, 8, false}}))
+        return ALACGPU_ERR_BAD_ARG;
+    if (window < 1 || window > 0x7FFFFFFFu || min_window < 1 || min_window > window) return ALACGPU_ERR_BAD_ARG;
+    if (line_len > ALAC_SLIDING_LDS_MAX && window > ALAC_SLIDING_RING_WINDOW_MAX) return ALACGPU_ERR_BAD_ARG;
+    const uint64_t grid = alac_sliding_grid(lines, line_len);
+    if (grid > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool wave = line_len <= ALAC_SLIDING_WAVE_MAX;
+    const void* const kernel = wave ? (const void*)alac_sliding_wave_kernel : (const void*)alac_sliding_line_kernel;
+    const size_t lds = alac_sliding_lds_bytes(line_len);          // (at most 68 KiB and a few bytes)
+    if (lds > 32768u) HIP_TRY(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    alac_sliding_params p;
+    p.src = (const float*)d_src;
+    p.out = (float*)d_out;
+    p.valid = (const int64_t*)d_valid;
+    p.lines = lines;
+    p.lines_per_row = lines_per_row;
+    p.line_stride = line_stride;
+    p.line_len = line_len;
+    p.window = window;
+    p.min_window = min_window;
+    p.center = center ? 1u : 0u;
+    p.norm_vars = norm_vars ? 1u : 0u;
+    p.ring = alac_sliding_ring(line_len);
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel(kernel, dim3((uint32_t)grid), dim3(wave ? ALAC_SLIDING_WAVE_THREADS : ALAC_SLIDING_LINE_THREADS), kargs, lds,
+                                 (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
+}
+
+int alacgpu_vad_energy_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint64_t row_stride, uint64_t line, uint64_t line_len,
+                              const void* d_valid, float energy_threshold, float energy_mean_scale, uint32_t frames_context,
+                              float proportion_threshold, void* d_mask, uint64_t mask_stride, void* hip_stream) {
+    if (!ctx || !args_ok({{d_src, 4}, {d_valid, 8, false}, {d_mask, 1}})) return ALACGPU_ERR_BAD_ARG;
+    if (line_len == 0 || line_len > mask_stride || line > row_stride || line_len > row_stride - line) return ALACGPU_ERR_BAD_ARG;
+    if (!std::isfinite(energy_threshold) || !std::isfinite(energy_mean_scale) || !(energy_mean_scale >= 0.0f) ||
+        frames_context > ALAC_VAD_MAX_CONTEXT || !(proportion_threshold >= 0.0f && proportion_threshold <= 1.0f))
+        return ALACGPU_ERR_BAD_ARG;
+    uint64_t extent;
+    if (!planes_extent(rows, row_stride, line + line_len, extent) || mask_stride > (1ull << 60) / std::max<uint64_t>(rows, 1u)) return ALACGPU_ERR_BAD_ARG;
+    const uint64_t mask_extent = rows ? (rows - 1u) * mask_stride + line_len : 0u;
+    if (!apart(d_src, extent, d_mask, mask_extent)) return ALACGPU_ERR_BAD_ARG;
+    const uint64_t grid = alac_vad_grid(rows, line_len);
+    if (grid > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    alac_vad_params p;
+    p.energy = (const float*)d_src + line;
+    p.valid = (const int64_t*)d_valid;
+    p.mask = (uint8_t*)d_mask;
+    p.rows = rows;
+    p.row_stride = row_stride;
+    p.line_len = line_len;
+    p.mask_stride = mask_stride;
+    p.threshold = energy_threshold;
+    p.mean_scale = energy_mean_scale;
+    p.proportion = proportion_threshold;
+    p.context = frames_context;
+    const bool wave = line_len <= ALAC_VAD_WAVE_MAX;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel(wave ? (const void*)alac_vad_wave_kernel : (const void*)alac_vad_line_kernel, dim3((uint32_t)grid),
+                                 dim3(wave ? ALAC_VAD_WAVE_THREADS : ALAC_VAD_LINE_THREADS), kargs, 0, (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
+}
+
+int alacgpu_select_frames_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t lines_per_row,
+                                 uint64_t line_stride, uint64_t line_len, const void* d_valid, const void* d_mask, uint64_t mask_stride,
+                                 void* d_new_lengths, void* hip_stream) {
+    uint64_t lines;
+    if (!normalize_args_ok(ctx, d_src, d_out, rows, lines_per_row, line_stride, line_len, lines) ||
+        !args_ok({{d_valid, 8, false}, {d_mask, 1}, {d_new_lengths, 8}}))
+        return ALACGPU_ERR_BAD_ARG;
+    if (line_len > mask_stride || mask_stride > (1ull << 60) / std::max<uint64_t>(rows, 1u)) return ALACGPU_ERR_BAD_ARG;
+    const uint64_t extent = lines ? sizeof(float) * ((lines - 1u) * line_stride + line_len) : 0u;
+    const uint64_t mask_extent = rows ? (rows - 1u) * mask_stride + line_len : 0u, lengths_extent = sizeof(int64_t) * (uint64_t)rows;
+    if (!apart(d_mask, mask_extent, d_src, extent) || !apart(d_mask, mask_extent, d_out, extent) ||
+        !apart(d_new_lengths, lengths_extent, d_src, extent) || !apart(d_new_lengths, lengths_extent, d_out, extent) ||
+        !apart(d_new_lengths, lengths_extent, d_mask, mask_extent))
+        return ALACGPU_ERR_BAD_ARG;
+    // new lengths over the old ones: a row's length may then be read by one workgroup only, the one that writes it
+    const bool over = d_valid && d_new_lengths == d_valid;
+    if (d_valid && !over && !apart(d_new_lengths, lengths_extent, d_valid, lengths_extent)) return ALACGPU_ERR_BAD_ARG;
+    const uint32_t groups = over ? 1u : (lines_per_row + ALAC_SELECT_LINES - 1u) / ALAC_SELECT_LINES;
+    if ((uint64_t)rows * groups > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    alac_select_params p;
+    p.src = (const float*)d_src;
+    p.out = (float*)d_out;
+    p.valid = (const int64_t*)d_valid;
+    p.mask = (const uint8_t*)d_mask;
+    p.new_lengths = (int64_t*)d_new_lengths;
+    p.lines_per_row = lines_per_row;
+    p.groups = groups;
+    p.line_stride = line_stride;
+    p.line_len = line_len;
+    p.mask_stride = mask_stride;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_select_frames_kernel, dim3(rows * groups), dim3(ALAC_SELECT_THREADS), kargs, 0,
+                                 (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
 }
 
 int alacgpu_specaugment_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t channels, uint32_t n_mels,

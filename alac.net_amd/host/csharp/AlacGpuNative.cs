@@ -143,6 +143,27 @@ namespace ALACdotNET.Decoder
         /// + offset into dOut; a row with a NaN is NaN throughout.  Two launches, asynchronous on hipStream.</summary>
         [DllImport(Lib)] public static extern int alacgpu_normalize_top_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, uint rows,
             uint linesPerRow, ulong lineStride, ulong lineLen, float top, float scale, float offset, int relative, IntPtr hipStream);
+        /// <summary>Kaldi's sliding-window CMVN per line of the same layout over the first min(max(dValid[row], 0), lineLen) frames
+        /// (dValid: long[rows] or IntPtr.Zero for whole lines): frame t minus the mean of its window of `window` frames (around it
+        /// with center, else behind it and at least minWindow long at the start), divided by the window's standard deviation with
+        /// normVars; zeros behind them, into dOut (dSrc itself or the same layout).  One launch, asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_normalize_sliding_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, uint rows,
+            uint linesPerRow, ulong lineStride, ulong lineLen, IntPtr dValid, uint window, uint minWindow, int center, int normVars,
+            IntPtr hipStream);
+        /// <summary>Kaldi's energy VAD on the lineLen floats at dSrc + row * rowStride + line of every row, over the first
+        /// min(max(dValid[row], 0), lineLen) of them: a frame is voiced (1 in dMask, byte[rows, maskStride]; 0 otherwise and behind
+        /// the length) when at least proportionThreshold of the frames within framesContext of it are above energyThreshold +
+        /// energyMeanScale * their mean.  One launch, asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_vad_energy_device(IntPtr ctx, IntPtr dSrc, uint rows, ulong rowStride,
+            ulong line, ulong lineLen, IntPtr dValid, float energyThreshold, float energyMeanScale, uint framesContext,
+            float proportionThreshold, IntPtr dMask, ulong maskStride, IntPtr hipStream);
+        /// <summary>Every line of float data in device memory ([rows, linesPerRow, lineStride]) keeps its frames below
+        /// min(max(dValid[row], 0), lineLen) whose dMask[row, t] is not 0, in order, zeros behind them, into dOut (dSrc itself or the
+        /// same layout); their number (dValid[row] itself where negative) into dNewLengths (long[rows]; may be dValid).  One launch,
+        /// asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_select_frames_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, uint rows,
+            uint linesPerRow, ulong lineStride, ulong lineLen, IntPtr dValid, IntPtr dMask, ulong maskStride, IntPtr dNewLengths,
+            IntPtr hipStream);
         /// <summary>Noise at a target signal-to-noise ratio into planar float crops in device memory (dSrc, dOut
         /// [rows, channels, stride], dNoise [rows, noiseChannels, noiseStride], noiseChannels 1 or channels; the first frames of a
         /// plane are data): y = x + g n with g = dRatio[row] * sqrt(Ps / Pn) over the first dValid[row] frames of the signal and

@@ -49,11 +49,15 @@ its own line and no other; one at or behind v is never read.  A constant line wi
 a NaN anywhere is NaN everywhere (the maximum keeps a NaN, as np.max and torch.amax do) and every other row is untouched;
 mx = +inf gives c = +inf, and inf - inf = NaN with relative.
 
+A third kind of `how` is sliding.SlidingMeanVar, Kaldi's sliding-window CMVN (alacgpu_normalize_sliding_device): sliding.py
+states it, and `normalize_host`, `normalize_host_f32` and `normalize` take it by handing it on.
+
 `MeanVar`, `TopDb`, `normalize_host` and `normalize_host_f32` need no device.  `normalize` is the call on device tensors.
 """
 import numpy as np
 
 from ._stageargs import _device_context, _f32_finite, _lengths_device, _lines, _Spec
+from .sliding import LDS_MAX as _SLIDING_LDS_MAX, RING_WINDOW_MAX as _SLIDING_RING_WINDOW_MAX, SlidingMeanVar, sliding_host, sliding_host_f32
 
 _U = 2.0 ** -24
 WAVE_MAX = 256            # ALAC_NORM_WAVE_MAX of csrc/alac_normalize.h: up to here a line has 64 partial sums, above 1024
@@ -126,7 +130,10 @@ def _host_args(x, how, lengths):
 def normalize_host(x, how, lengths=None, bound=False):
     """The specification in numpy: x float32 [B, ..., n] to float64 of that shape -- float64 arithmetic on the float32 input
     and the float32 values of `how`'s parameters.  lengths: [B] integers, MeanVar's (ignored by TopDb).  bound=True: returns
-    (y, dY), dY float64 like y: how far a float32 evaluation may be from y (the module docstring's chain)."""
+    (y, dY), dY float64 like y: how far a float32 evaluation may be from y (the module docstring's chain).  A SlidingMeanVar:
+    sliding.sliding_host."""
+    if isinstance(how, SlidingMeanVar):
+        return sliding_host(x, how, lengths, bound)
     x, v = _host_args(x, how, lengths)
     shape = x.shape
     B, n = shape[0], shape[-1]
@@ -202,7 +209,10 @@ def normalize_host_f32(x, how, lengths=None):
     """The kernel's arithmetic in numpy, one float32 operation at a time: x float32 [B, ..., n] to float32 of that shape.
     MeanVar: the sums in the kernel's documented order (the number of partial sums follows n, as the kernel's mapping does).
     TopDb: the four lines of the module docstring.  Its distance from `normalize_host` is what a correct float32 evaluation
-    costs: the tests hold the kernel to a small multiple of that."""
+    costs: the tests hold the kernel to a small multiple of that.  A SlidingMeanVar: sliding.sliding_host_f32, the kernel bit
+    for bit."""
+    if isinstance(how, SlidingMeanVar):
+        return sliding_host_f32(x, how, lengths)
     x, v = _host_args(x, how, lengths)
     f32 = np.float32
     shape = x.shape
@@ -245,8 +255,8 @@ def _normalize(ctx, x, how, lengths, out):
     """`normalize`; ctx() gives the context that runs it (the corpus's own inside `Corpus.crops`), asked for behind the checks"""
     import torch
 
-    if not isinstance(how, (MeanVar, TopDb)):
-        raise ValueError(f"how must be a MeanVar or a TopDb, not {how!r}")
+    if not isinstance(how, (MeanVar, TopDb, SlidingMeanVar)):
+        raise ValueError(f"how must be a MeanVar, a TopDb or a SlidingMeanVar, not {how!r}")
     if not isinstance(x, torch.Tensor) or x.device.type != "cuda" or x.dtype != torch.float32 or x.dim() < 2:
         raise ValueError("x must be a float32 device tensor [B, ..., n]")
     top = isinstance(how, TopDb)
@@ -256,6 +266,9 @@ def _normalize(ctx, x, how, lengths, out):
     if layout is None:
         raise ValueError("x must be contiguous or the slice [..., :n] of a contiguous tensor")
     S, n = layout
+    sliding = isinstance(how, SlidingMeanVar)
+    if sliding and n > _SLIDING_LDS_MAX and how.window > _SLIDING_RING_WINDOW_MAX:
+        raise ValueError(f"lines of {n} frames: above {_SLIDING_LDS_MAX} a sliding window takes at most {_SLIDING_RING_WINDOW_MAX} frames")
     if out is None:
         out = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=x.device)
     elif (not isinstance(out, torch.Tensor) or out.shape != x.shape or out.dtype != x.dtype or out.device != x.device
@@ -269,7 +282,10 @@ def _normalize(ctx, x, how, lengths, out):
     lines_per_row = x.numel() // n // rows
     with torch.cuda.device(x.device):
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        if top:
+        if sliding:
+            ctx().normalize_sliding_device(x, out, rows, lines_per_row, S, n, d_valid, how.window, how.min_window, how.center,
+                                           how.norm_vars, stream=stream)
+        elif top:
             ctx().normalize_top_device(x, out, rows, lines_per_row, S, n, how.top, how.scale, how.offset, how.relative, stream=stream)
         else:
             ctx().normalize_meanvar_device(x, out, rows, lines_per_row, S, n, d_valid, how.centre, how.scale, how.eps, stream=stream)
@@ -279,12 +295,13 @@ def _normalize(ctx, x, how, lengths, out):
 def normalize(x, how, lengths=None, out=None):
     """Normalise on the GPU: x float32 [B, ..., n] on the device, contiguous or the slice [..., :n] of a contiguous tensor
     (Whisper drops the last frame: normalize(feats[..., :-1], TopDb.whisper())); what lies behind the slice is neither read
-    nor written.  how: a `MeanVar` -- every line x[b, ..., :] over its first lengths[b] elements, zeros behind them -- or a
-    `TopDb` -- every row x[b], or x[b, c] with per_channel, against its own maximum.  lengths: [B] integers, a sequence or a
-    tensor (as `crops` returns them; -1 counts as 0, more than n as n), used by MeanVar only; default: whole lines.  out: x
+    nor written.  how: a `MeanVar` -- every line x[b, ..., :] over its first lengths[b] elements, zeros behind them --, a
+    `TopDb` -- every row x[b], or x[b, c] with per_channel, against its own maximum -- or a sliding.SlidingMeanVar -- every frame
+    of a line against the window around or behind it, zeros behind lengths[b].  lengths: [B] integers, a sequence or a
+    tensor (as `crops` returns them; -1 counts as 0, more than n as n), not used by TopDb; default: whole lines.  out: x
     itself (in place) or a tensor of x's shape and layout; default: a new one of x's layout.  Returns out.  One launch
-    (MeanVar) or two (TopDb), asynchronous on the current stream; ValueError before any device work."""
+    (MeanVar, SlidingMeanVar) or two (TopDb), asynchronous on the current stream; ValueError before any device work."""
     ctx = _device_context("x", x, "[B, ..., n]")
-    if not isinstance(how, (MeanVar, TopDb)):
-        raise ValueError(f"how must be a MeanVar or a TopDb, not {how!r}")
+    if not isinstance(how, (MeanVar, TopDb, SlidingMeanVar)):
+        raise ValueError(f"how must be a MeanVar, a TopDb or a SlidingMeanVar, not {how!r}")
     return _normalize(ctx, x, how, lengths, out)

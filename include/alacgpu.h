@@ -628,6 +628,93 @@ int alacgpu_normalize_top_device(alacgpu_ctx* ctx, const void* d_src, void* d_ou
                                  void* hip_stream);
 
 /*
+ * alacgpu_normalize_sliding_device: Kaldi's sliding-window mean (and variance) normalisation behind the features
+ * (apply-cmvn-sliding; no counterpart in the reference), one launch.  The layout and the in-place rule are
+ * alacgpu_normalize_meanvar_device's: float32 [rows, lines_per_row, line_stride], the first line_len of a line are frames, d_out
+ * is d_src itself or an array of that layout apart from it.  Neither Kaldi nor torchaudio is at hand where this is built: the
+ * parity is with this specification, SlidingWindowCmnInternal restated.  For line l of row r, v = min(max(d_valid[r], 0),
+ * line_len) (d_valid: int64 [rows]; NULL: v = line_len), and for frame t < v the window [s, e), Kaldi's with its quirks (the
+ * non-centred window behind frame `window` is window + 1 frames long):
+ *   center:      s = t - window / 2;  e = s + window            otherwise:   s = t - window;  e = t + 1
+ *   if s < 0:                 e -= s;  s = 0
+ *   if not center and e > t:  e = max(t + 1, min_window)
+ *   if e > v:                 s -= e - v;  e = v;  s = max(s, 0)
+ *   N = e - s;  m = (sum of x[s .. e)) / N
+ *   y[t] = x[t] - m                                                                  norm_vars 0
+ *   y[t] = N == 1 ? 0 : (x[t] - m) / sqrt(max((sum of x[s .. e)^2) / N - m^2, 1e-10))     norm_vars != 0
+ *   y[t] = 0                                                                         for v <= t < line_len
+ * v = 0 (d_valid[r] = -1 included) writes a line of zeros and reads nothing.  The float32 arithmetic, one IEEE operation at a
+ * time, nothing contracted, divisions and the root correctly rounded: the pivot p = fl(P / fl(v)), P the sum over [0, v) in
+ * alacgpu_normalize_meanvar_device's order (64 partial sums for line_len <= 256, 1024 above) of the elements that are finite
+ * (another counts as +0); d[t] = fl(x[t] - p), and everything else works on d, so the variance is never E[x^2] - m^2 on data with
+ * an offset.  Frames are in blocks of 32 from the line's start; a block's sum is a tree of halves (q[j] += q[j + h], h = 16 .. 1)
+ * over its elements, those at or behind v counting as +0, and the same over fl(d * d) with norm_vars.  A window's sums S1 (of d)
+ * and S2 (of fl(d * d)) are each one chain of additions from zero: with j0 = ceil(s / 32) and j1 = floor(e / 32) the elements
+ * s .. 32 j0 - 1, the blocks j0 .. j1 - 1, the elements 32 j1 .. e - 1, each ascending; all elements ascending where j0 >= j1.
+ * A window sum is never a difference of running sums: its error depends on N, not on t or line_len.  m = fl(S1 / fl(N)),
+ * y = fl(d[t] - m); with norm_vars var = fl(fl(S2 / fl(N)) - fl(m * m)), floored at 1e-10f (a NaN stays one), and
+ * y = fl(fl(d[t] - m) / sqrt(var)).  alac.net_amd/sliding.py derives the error bound.  A NaN or an infinity at t0 < v reaches
+ * exactly the frames whose window holds t0, one at or behind v nothing.  Lines of up to 256 frames are taken by a wave each,
+ * four to a workgroup; longer ones by a workgroup of 1024 threads each.  d and the block sums are held in LDS, the whole line up
+ * to 16384 frames (68 KiB: two workgroups fit the 160 KiB of a CU); a longer line goes through the same LDS as a ring, read a
+ * second time from memory in front of the chunk of 1024 frames that needs it and always before the chunk that writes it, which
+ * takes a window of at most 7648 frames.  Nothing of the ctx is used but its device, there is no ctx scratch: calls on
+ * different streams are independent.  Device pointers only, asynchronous on hip_stream, nothing is read back.  rows == 0: nothing
+ * happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx, d_src or d_out, a misaligned array (4; 8 for d_valid),
+ * lines_per_row 0, line_len 0 or above line_stride, d_src and d_out that overlap without being equal, an extent of 2^60 bytes
+ * or more, 2^31 workgroups or more; window or min_window 0 or above 2^31 - 1, min_window above window; a window above 7648 with
+ * a line_len above 16384.
+ */
+int alacgpu_normalize_sliding_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t lines_per_row,
+                                     uint64_t line_stride, uint64_t line_len, const void* d_valid, uint32_t window,
+                                     uint32_t min_window, int center, int norm_vars, void* hip_stream);
+
+/*
+ * The energy VAD of the Kaldi speaker recipes on one feature line (compute-vad-decision) and the selection of the voiced
+ * frames (select-voiced-frames); no counterpart in the reference, one launch each.  The parity is with this specification,
+ * Kaldi's ComputeVadEnergy restated.  Both: device pointers only, asynchronous on hip_stream, nothing is read back, nothing of
+ * the ctx is used but its device and there is no ctx scratch, so calls on different streams are independent.  rows == 0:
+ * nothing happens.
+ *
+ * alacgpu_vad_energy_device: E, the energy line of row r, is the line_len floats at d_src + r * row_stride + line (for features
+ * [B, C, lines, S]: row_stride = C * lines * S, line = the feature's index * S: the first channel's).  With v =
+ * min(max(d_valid[r], 0), line_len) (int64 [rows]; NULL: line_len) and c = frames_context,
+ *   thr     = energy_threshold + energy_mean_scale * (sum of E[0 .. v)) / v      (energy_threshold itself with a scale of 0)
+ *   num[t]  = #{t2 in [t - c, t + c] and [0, v) : E[t2] > thr},   den[t] = #{t2 in [t - c, t + c] and [0, v)}
+ *   d_mask[r * mask_stride + t] = num[t] >= den[t] * proportion_threshold ? 1 : 0   for t < v;   0 for v <= t < line_len
+ * in float32: the sum in alacgpu_normalize_meanvar_device's order (64 partial sums for line_len <= 256, 1024 above), mean =
+ * fl(sum / fl(v)), thr = fl(energy_threshold + fl(energy_mean_scale * mean)), nothing contracted; the counts are integers and
+ * the last comparison is float(num) >= fl(float(den) * proportion_threshold).  A NaN energy compares false; with a scale of 0
+ * the mean is not computed.  d_mask is uint8 [rows, mask_stride]: every t < line_len of a row is written, what lies behind is
+ * neither read nor written.  A wave per row of up to 256 frames, four to a workgroup, a workgroup of 1024 threads above.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx, d_src or d_mask, a misaligned array (4; 8 for d_valid; 1 for
+ * d_mask), line_len 0 or above mask_stride, line + line_len above row_stride, a threshold or the scale not finite, a negative
+ * scale, frames_context above 64, proportion_threshold outside 0 .. 1, a d_mask that overlaps d_src, an extent of 2^60 bytes or
+ * more, 2^31 workgroups or more.
+ *
+ * alacgpu_select_frames_device: the layout and the in-place rule of alacgpu_normalize_meanvar_device.  For every line of row r,
+ * with t_k the k-th t < v whose d_mask[r * mask_stride + t] != 0 and K their number,
+ *   y[k] = x[t_k]   for k < K;      y[k] = 0   for K <= k < line_len;      d_new_lengths[r] = d_valid[r] < 0 ? d_valid[r] : K
+ * bits are moved, nothing is computed.  What lies behind line_len is neither read nor written.  In place is safe because a
+ * frame only moves left: a workgroup of 1024 threads walks its lines in chunks of 1024 frames in ascending order -- a chunk is
+ * read, then a barrier, then it is stored -- with the mask's running count carried from chunk to chunk.  A workgroup takes
+ * 8 lines of a row; d_new_lengths (int64 [rows]) may be d_valid itself, and then one workgroup takes all lines of a row, since
+ * no other may read the length it writes.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx, d_src, d_out, d_mask or d_new_lengths, a misaligned array (4;
+ * 8 for d_valid and d_new_lengths; 1 for d_mask), lines_per_row 0, line_len 0 or above line_stride or mask_stride, d_src and
+ * d_out that overlap without being equal, a d_mask or d_new_lengths that overlaps d_src, d_out or one another, a d_new_lengths
+ * that overlaps d_valid without being equal, an extent of 2^60 bytes or more, 2^31 workgroups or more.
+ */
+int alacgpu_vad_energy_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint64_t row_stride, uint64_t line,
+                              uint64_t line_len, const void* d_valid, float energy_threshold, float energy_mean_scale,
+                              uint32_t frames_context, float proportion_threshold, void* d_mask, uint64_t mask_stride,
+                              void* hip_stream);
+int alacgpu_select_frames_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t lines_per_row,
+                                 uint64_t line_stride, uint64_t line_len, const void* d_valid, const void* d_mask,
+                                 uint64_t mask_stride, void* d_new_lengths, void* hip_stream);
+
+/*
  * alacgpu_mix_device: noise at a target signal-to-noise ratio into the crops, in front of the features (no counterpart in the
  * reference); two launches, no atomics.  The layout is planar float32: d_src and d_out [rows, channels, stride], d_noise
  * [rows, noise_channels, noise_stride] with noise_channels 1 (the one channel goes into every channel of the signal) or

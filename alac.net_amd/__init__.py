@@ -93,6 +93,8 @@ SYMBOLS = {
                                                _VP, _VP]),
     "alacgpu_mix_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _VP,
                                      _VP, _VP]),
+    "alacgpu_biquad_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, _VP, C.c_uint32, _VP, C.c_int,
+                                        _VP]),
     "alacgpu_reverb_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
                                         C.c_uint64, _VP, _VP, _VP]),
     "alacgpu_specaugment_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, _VP, _VP,
@@ -515,6 +517,17 @@ class AlacGpuContext(_Closing):
         states the arithmetic.  Two launches, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
         rc = lib().alacgpu_mix_device(self._ctx, _dp(d_src), _dp(d_out), _dp(d_noise), rows, channels, noise_channels, stride,
                                       noise_stride, frames, _dp(d_valid), _dp(d_noise_valid), _dp(d_ratio), _VP(stream))
+        _check(rc, self._ctx)
+
+    def biquad_device(self, d_src, d_out, rows, channels, stride, frames, d_valid, d_coeffs, sections, d_gain, clamp, stream=0):
+        """alacgpu_biquad_device: every row of d_src (float32 device tensor, planar [rows, channels, stride], the first `frames`
+        of a plane are data) through its cascade of `sections` biquad sections d_coeffs (float64 device tensor [rows, sections,
+        5] = (b0, b1, b2, a1, a2)) and its gain d_gain (float64 [rows], or None for 1), over the first v = min(max(d_valid[row],
+        0), frames) frames, limited to -1 .. 1 with clamp, into d_out (d_src itself or the same layout apart from it).  d_valid:
+        an int64 device tensor [rows], or None for `frames`.  biquad.py states the arithmetic.  One launch, asynchronous on
+        `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_biquad_device(self._ctx, _dp(d_src), _dp(d_out), rows, channels, stride, frames, _dp(d_valid),
+                                         _dp(d_coeffs), sections, _dp(d_gain), int(bool(clamp)), _VP(stream))
         _check(rc, self._ctx)
 
     def reverb_device(self, d_src, d_out, d_rir, rows, channels, rir_channels, stride, rir_stride, frames, rir_frames, d_valid,
@@ -1140,6 +1153,9 @@ from .sliding import SlidingMeanVar, sliding_host, sliding_host_f32, sliding_win
 from .vad import EnergyVad, select_frames, select_host, vad_energy, vad_host, vad_host_f32  # noqa: E402
 # ---- noise at a target signal-to-noise ratio into crops and tensors (alacgpu_mix_device) ----------------------------------------
 from .mix import AddNoise, mix, mix_host, mix_host_f32  # noqa: E402
+# ---- biquad filters and a gain on crops and tensors (alacgpu_biquad_device) ----------------------------------------------------------
+from .biquad import (Effects, RandomBiquad, allpass, bandpass, bandreject, biquad, biquad_host, biquad_host_twin, highpass,  # noqa: E402
+                     highshelf, lowpass, lowshelf, peaking)
 # ---- room reverberation into crops and tensors (alacgpu_reverb_device) ------------------------------------------------------------
 from .reverb import Reverb, reverb, reverb_host, reverb_host_f32  # noqa: E402
 # ---- SpecAugment on the features: time warp, frequency and time masks (alacgpu_specaugment_device) -------------------------------

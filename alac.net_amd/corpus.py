@@ -17,12 +17,12 @@ from both tiers into a small staging blob in HBM, and the decode reads that.
 frames a crop needs are decoded as above into a scratch the corpus keeps, and one alacgpu_resample_device call (resample.py
 states the filter) resamples every crop out of it.
 
-`crops(..., reverb=, mix=, features=, deltas=, vad=, normalize=, augment=)` runs up to eight stages behind the waveform, and `crops` is the one place
+`crops(..., reverb=, mix=, effects=, features=, deltas=, vad=, normalize=, augment=)` runs up to nine stages behind the waveform, and `crops` is the one place
 that lists them: the refusals of all of them, the crops the second corpora make (`Corpus._companion_crops`: the noise of an
 AddNoise, then the impulse responses of a Reverb, each cropped by its own corpus at the rate of the crops), the waveform once
-(`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_logmel_device (or alacgpu_fbank_device or alacgpu_mfcc_device), alacgpu_deltas_device,
+(`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_biquad_device, alacgpu_logmel_device (or alacgpu_fbank_device or alacgpu_mfcc_device), alacgpu_deltas_device,
 alacgpu_vad_energy_device, the normalisation, alacgpu_select_frames_device and alacgpu_specaugment_device (reverb.py, mix.py,
-features.py, deltas.py, vad.py, normalize.py, sliding.py and augment.py state the arithmetic), each only if asked for.
+biquad.py, features.py, deltas.py, vad.py, normalize.py, sliding.py and augment.py state the arithmetic), each only if asked for.
 
 `crops(..., speed=)` plays every crop at a drawn factor in front of all that (the same method, speed.py): the step of a corpus
 whose rates differ, with a ratio per (file rate, factor) in place of one per file rate; the crops at factor 1 go through the
@@ -42,6 +42,7 @@ from . import (MAX_FRAME, ST_OK, ST_UNSUPPORTED_ELEMENT, ST_UNSUPPORTED_PREDTYPE
                _Closing, _check, _check_batch_args, _compact_slots, _dp, _encode_slots, _frame_count, _status_text, _torch_dtype,
                _VP, _write_file, lib, make_cfgs)
 from .augment import LDS_MAX as _WARP_MAX, _check_draws, _how, _spec_augment
+from .biquad import Effects, _biquad
 from .deltas import Deltas, _add_deltas
 from .fbank import KaldiFbank
 from .mfcc import KaldiMfcc
@@ -647,7 +648,7 @@ class Corpus(_Closing):
         return torch.from_numpy(f.astype(np.int32)).to(self._dev), torch.from_numpy(o).to(self._dev), True
 
     def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True, features=None, normalize=None, mix=None,
-              reverb=None, speed=None, deltas=None, vad=None, augment=None, sample_rate=None, mono=False):
+              reverb=None, speed=None, effects=None, deltas=None, vad=None, augment=None, sample_rate=None, mono=False):
         """Decode crop b = frames frame_offsets[b] .. + num_frames of file files[b] for every b in ONE launch pair: returns
         (pcm [B, C, num_frames] on the device, zero behind lengths[b]; lengths [B], a DEVICE int64 tensor: min(num_frames,
         T_f - offset)).  float32 (default) or int32, as `load`.  files / frame_offsets: sequences, numpy arrays or torch
@@ -672,7 +673,7 @@ class Corpus(_Closing):
         more than 2 channels, draws that are not an integer tensor [B] on the corpus's device.
 
         The stages behind the waveform go by keyword, as sample_rate and mono do, and run in this order whichever are
-        given -- reverb, mix, features, deltas, the VAD's decision, normalize, the selection of the voiced frames, augment --,
+        given -- reverb, mix, effects, features, deltas, the VAD's decision, normalize, the selection of the voiced frames, augment --,
         in place but for the features and the deltas, by the corpus's own context on the same stream; lengths (but for vad=,
         which shortens them), `check` and last_status() are those of the call without them (with check=True a second corpus's own check runs too, and first).  ValueError before any device
         work for what a stage cannot take.
@@ -687,6 +688,14 @@ class Corpus(_Closing):
         rate of the crops)` returned.  Bit for bit mix.mix(the crops without it, the noise crops, snr_db, lengths, their
         lengths).  The noise and the responses are cropped by their own corpus's `crops` at the rate of the crops, as one
         channel when its channel count is not theirs, into scratches THIS corpus keeps: a second corpus may be this one.
+
+        effects: the channel, last on the waveform: a biquad.Effects -- a cascade of biquad sections and a gain per crop --,
+        whose draws are then made here from the device's default generator (behind a Reverb's and in front of a SpecAugment's --
+        and in front of a SpeedPerturb's, which `crops` draws with the waveform; `random_crops` draws the speed first),
+        or the pair (Effects, draws) with the (coeffs float64 [B, S, 5], gain float64 [B]) that its `draw(B, rate of the
+        crops)` returned.  Bit for bit biquad.biquad(the crops without it, coeffs, lengths, gain, effects.clamp); a crop
+        outside the corpus stays zeros.  ValueError: int32 crops, draws of another shape, dtype or device, a filter frequency at
+        or above the Nyquist frequency of the crops' rate.
 
         features: a features.LogMel, a fbank.KaldiFbank or a mfcc.KaldiMfcc -- the crops' log-mel, Kaldi fbank or Kaldi MFCC
         features instead of their PCM (n_mels below is then the transform's line count: a KaldiMfcc's n_ceps):
@@ -727,7 +736,7 @@ class Corpus(_Closing):
         more than 16384 feature frames."""
         import torch
 
-        # 1. every refusal that needs no device work: speed, mix, reverb, normalize, features, augment; the waveform's own are `_waveform`'s
+        # 1. every refusal that needs no device work: speed, mix, reverb, effects, normalize, features, augment; the waveform's own are `_waveform`'s
         rate = self.sample_rate if sample_rate is None else sample_rate
         Co = 1 if mono else self.channels
         if speed is not None:
@@ -736,6 +745,8 @@ class Corpus(_Closing):
             mix = self._second_corpus(mix, _MIX, dtype, rate, Co)
         if reverb is not None:
             reverb = self._second_corpus(reverb, _REVERB, dtype, rate, Co)
+        if effects is not None:
+            effects = self._effects_given(effects, dtype, rate)
         if normalize is not None:
             if not isinstance(normalize, (MeanVar, TopDb, SlidingMeanVar)):
                 raise ValueError(f"normalize must be a normalize.MeanVar, a normalize.TopDb or a sliding.SlidingMeanVar, not {normalize!r}")
@@ -777,7 +788,7 @@ class Corpus(_Closing):
             augment = _how(augment, "augment")
             if features is None:
                 raise ValueError("a SpecAugment masks log-mel features: it needs features=")
-        if features is not None or mix is not None or reverb is not None or speed is not None:
+        if features is not None or mix is not None or reverb is not None or speed is not None or effects is not None:
             L = _frame_count("num_frames", num_frames)
             if features is not None and L < features.min_frames:
                 raise ValueError(features.short(L))
@@ -785,6 +796,8 @@ class Corpus(_Closing):
             B = int(files.shape[0]) if isinstance(files, torch.Tensor) and files.dim() == 1 else len(np.asarray(files))
         if speed is not None and speed[1] is not None and speed[1].shape[0] != B:
             raise ValueError(f"{speed[1].shape[0]} draws of speed= for {B} crops")
+        if effects is not None and effects[1] is not None and effects[1][0].shape[0] != B:
+            raise ValueError(f"{effects[1][0].shape[0]} draws of effects= for {B} crops")
         if features is not None:
             if augment is not None:
                 if augment[1] is not None:
@@ -806,6 +819,8 @@ class Corpus(_Closing):
             from_0 = torch.zeros(B, dtype=torch.int64, device=self._dev)
             d_rir, rir_lengths = self._companion_crops(reverb[0].rirs, "_reverb_scratch", rf, from_0, reverb[0].frames(rate), B=B, Co=Co,
                                                        rate=rate, check=check)
+        if effects is not None and effects[1] is None:
+            effects = (effects[0], effects[0].draw(B, rate, device=self._dev))
         # 3. the waveform, once: into `out`, or into the scratch the features are computed from
         res, lengths = self._waveform(files, frame_offsets, num_frames, dtype=dtype, out=out, check=check, sample_rate=sample_rate,
                                       mono=mono, speed=speed)
@@ -815,6 +830,8 @@ class Corpus(_Closing):
             _reverb(ctx, res, d_rir, lengths, torch.where(keep, rir_lengths, 0), res)
         if mix is not None:
             _mix(ctx, res, d_noise, lambda: snr_ratio(snr, B, self._dev), lengths, noise_lengths, res)
+        if effects is not None:
+            _biquad(ctx, res, effects[1][0], lengths, effects[1][1], effects[0].clamp, res)
         if features is not None:
             if B:
                 features.launch(self._gpu, res, B, Co, L, L, feats, torch.cuda.current_stream(self._dev).cuda_stream)
@@ -902,6 +919,29 @@ class Corpus(_Closing):
             raise ValueError(f"{_NEEDS_RATE}, and {stage['they']} a rate to crop at")
         if other.channels != Co and other.channels not in (1, 2):
             raise ValueError(stage["channels"].format(n=other.channels, Co=Co))
+        return spec, draws
+
+    def _effects_given(self, given, dtype, rate):
+        """crops(effects=) as the pair (Effects, draws or None), checked: ValueError for anything else, for int32 crops, for
+        crops without a rate, for a filter at or above their Nyquist frequency and for draws that are not (float64 [B, S, 5],
+        float64 [B]) on the corpus's device.  Nothing is done on the device; B is `crops`'s to check."""
+        import torch
+
+        spec, draws = given if isinstance(given, tuple) and len(given) == 2 else (given, None)
+        if not isinstance(spec, Effects):
+            raise ValueError(f"effects must be a biquad.Effects or (Effects, what its draw() returned), not {given!r}")
+        if not _is_f32(torch, dtype):
+            raise ValueError("float32 crops are filtered")
+        if rate is None:
+            raise ValueError(_NEEDS_RATE)
+        spec.check_rate(rate)
+        if draws is not None:
+            ok = isinstance(draws, tuple) and len(draws) == 2 and all(isinstance(t, torch.Tensor) and t.dtype == torch.float64 for t in draws)
+            if not ok or draws[0].dim() != 3 or tuple(draws[0].shape[1:]) != (spec.sections, 5) or draws[1].shape != draws[0].shape[:1]:
+                raise ValueError(f"the draws of effects= must be the two float64 tensors (coeffs [B, {spec.sections}, 5], gain [B]) of "
+                                 f"Effects.draw")
+            if any(t.device != self._dev for t in draws):
+                raise ValueError(f"the draws of effects= must be on {self._dev}")
         return spec, draws
 
     def _speed_given(self, given, dtype, rate):
@@ -1152,7 +1192,8 @@ class Corpus(_Closing):
         return out, lengths
 
     def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True, features=None, normalize=None,
-                     mix=None, reverb=None, speed=None, deltas=None, vad=None, augment=None, sample_rate=None, mono=False):
+                     mix=None, reverb=None, speed=None, effects=None, deltas=None, vad=None, augment=None, sample_rate=None,
+                     mono=False):
         """`batch` crops of num_frames frames drawn on the device: files uniform over the corpus, the first frame uniform in
         0 .. max(T_f - num_frames, 0).  generator: a torch.Generator (of the corpus's device, or of the CPU: then the draws are
         made there and uploaded).  Returns (pcm, lengths, files, frame_offsets), the draws as device int64 tensors.
@@ -1160,7 +1201,8 @@ class Corpus(_Closing):
         (feats, feat_lengths, files, frame_offsets).  deltas, vad and normalize as for `crops`: with vad= feat_lengths are the
         voiced counts, and nothing is read back for them.  mix as for `crops`; an AddNoise is drawn from
         `generator`, behind the call's own two draws (AddNoise.draw states its four).  reverb as for `crops`; a Reverb is
-        drawn from `generator` behind those (Reverb.draw states its two).  augment as for `crops`; a SpecAugment is drawn from
+        drawn from `generator` behind those (Reverb.draw states its two).  effects as for `crops`; an Effects is drawn from
+        `generator` behind those (Effects.draw states its draws).  augment as for `crops`; a SpecAugment is drawn from
         `generator` behind those, for the feat_lengths the call returns (augment.py states its draws) -- with vad= for the
         lengths in front of the selection, which are known without the device's decisions.  speed as for `crops`;
         a SpeedPerturb is drawn from `generator` behind the call's own two draws and in front of an AddNoise's
@@ -1176,6 +1218,8 @@ class Corpus(_Closing):
             mix = self._second_corpus(mix, _MIX, dtype, rate, 1 if mono else self.channels)
         if reverb is not None:
             reverb = self._second_corpus(reverb, _REVERB, dtype, rate, 1 if mono else self.channels)
+        if effects is not None:
+            effects = self._effects_given(effects, dtype, rate)
         if augment is not None:
             augment = _how(augment, "augment")
             if features is None:
@@ -1206,13 +1250,15 @@ class Corpus(_Closing):
             mix = (mix[0], mix[0].draw(B, L, sample_rate=rate, generator=generator))
         if reverb is not None and reverb[1] is None:
             reverb = (reverb[0], reverb[0].draw(B, generator=generator))
+        if effects is not None and effects[1] is None:
+            effects = (effects[0], effects[0].draw(B, rate, generator=generator, device=self._dev))
         if augment is not None and augment[1] is None and isinstance(features, _FEATURES):
             feat_lengths = features.lengths((ends - offs).clamp(max=L))
             lines = deltas.lines(features.n_mels) if isinstance(deltas, Deltas) else features.n_mels
             augment = (augment[0], augment[0].draw(lines, feat_lengths, generator=generator))
         pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,
                                   features=features, normalize=normalize, mix=mix, reverb=reverb, augment=augment, speed=speed,
-                                  deltas=deltas, vad=vad)
+                                  deltas=deltas, vad=vad, effects=effects)
         return pcm, lengths, files, offs
 
     def last_staged_bytes(self):

@@ -1,5 +1,5 @@
 // alacgpu_stages.hip -- C ABI of include/alacgpu.h, the stages around the decode: the crop planner, the scan with the packet
-// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the reverberation, the noise mix, the normalisations, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
+// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the reverberation, the noise mix, the biquad cascade, the normalisations, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
 // their own scratch; the decode path is alacgpu_api.hip.  No CPU fallback here either: every stage is its kernels.
 #include <algorithm>
 #include <cmath>
@@ -16,6 +16,7 @@
 #include "alac_vad.h"
 #include "alac_augment.h"
 #include "alac_mix.h"
+#include "alac_biquad.h"
 #include "alac_reverb.h"
 #include "alac_encode.h"
 #include "alacgpu_ctx.h"
@@ -882,6 +883,40 @@ int alacgpu_mix_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, const v
     HIP_TRY(ctx, hipLaunchKernel((const void*)alac_mix_apply_kernel, dim3((uint32_t)grid), dim3(ALAC_MIX_THREADS), kargs, 0, stream));
     HIP_TRY(ctx, hipGetLastError());
     return ctx->mix.release(ctx, stream);
+}
+
+int alacgpu_biquad_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t channels, uint64_t stride,
+                          uint64_t frames, const void* d_valid, const void* d_coeffs, uint32_t sections, const void* d_gain, int clamp,
+                          void* hip_stream) {
+    if (!ctx || !args_ok({{d_src, 4}, {d_out, 4}, {d_valid, 8, false}, {d_coeffs, 8}, {d_gain, 8, false}})) return ALACGPU_ERR_BAD_ARG;
+    if (channels == 0 || sections == 0 || sections > ALAC_BIQUAD_MAX_SECTIONS || frames == 0 || frames > stride) return ALACGPU_ERR_BAD_ARG;
+    uint64_t extent;
+    if (!planes_extent((uint64_t)rows * channels, stride, frames, extent)) return ALACGPU_ERR_BAD_ARG;
+    const uint64_t coeff_bytes = sizeof(double) * 5u * (uint64_t)sections * rows, gain_bytes = d_gain ? sizeof(double) * (uint64_t)rows : 0u;
+    if ((d_src != d_out && !apart(d_src, extent, d_out, extent)) || !apart(d_coeffs, coeff_bytes, d_out, extent) ||
+        (d_gain && !apart(d_gain, gain_bytes, d_out, extent)))
+        return ALACGPU_ERR_BAD_ARG;
+    const uint64_t grid = (uint64_t)rows * channels;
+    if (grid > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    alac_biquad_params p;
+    p.src = (const float*)d_src;
+    p.out = (float*)d_out;
+    p.valid = (const int64_t*)d_valid;
+    p.coeffs = (const double*)d_coeffs;
+    p.gain = (const double*)d_gain;
+    p.channels = channels;
+    p.sections = sections;
+    p.stride = stride;
+    p.frames = frames;
+    p.clamp = clamp ? 1u : 0u;
+    p.vec = ((uintptr_t)d_src & 15u) == 0u && ((uintptr_t)d_out & 15u) == 0u && (stride & 3u) == 0u ? 1u : 0u;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_biquad_kernel, dim3((uint32_t)grid), dim3(ALAC_BIQUAD_THREADS), kargs, 0,
+                                 (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
 }
 
 size_t alacgpu_encode_max_packet_bytes(uint32_t frames, int sample_size, int channels) {

@@ -172,6 +172,15 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_mix_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, IntPtr dNoise, uint rows,
             uint channels, uint noiseChannels, ulong stride, ulong noiseStride, ulong frames, IntPtr dValid, IntPtr dNoiseValid,
             IntPtr dRatio, IntPtr hipStream);
+        /// <summary>A cascade of biquad sections and a gain per row on planar float crops in device memory (dSrc, dOut
+        /// [rows, channels, stride]; the first frames of a plane are data): dCoeffs double[rows, sections, 5] = (b0, b1, b2, a1,
+        /// a2), 1 to 8 sections, dGain double[rows] or IntPtr.Zero for 1, over the first dValid[row] frames (long[rows] or
+        /// IntPtr.Zero for all), limited to -1 .. 1 with clamp; float64 recurrences, rounded once to float.  A row of identity
+        /// sections with gain 1 is left as it is.  dOut is dSrc itself or apart from it.  One launch, asynchronous on
+        /// hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_biquad_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, uint rows,
+            uint channels, ulong stride, ulong frames, IntPtr dValid, IntPtr dCoeffs, uint sections, IntPtr dGain, int clamp,
+            IntPtr hipStream);
         /// <summary>Room reverberation into planar float crops in device memory (dSrc, dOut [rows, channels, stride], dRir
         /// [rows, rirChannels, rirStride], rirChannels 1 or channels; the first frames / rirFrames of a plane are data): every
         /// row convolved with its impulse response over the first dValid[row] frames of the signal and dRirValid[row] of the

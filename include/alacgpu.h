@@ -750,6 +750,39 @@ int alacgpu_mix_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, const v
                        const void* d_valid, const void* d_noise_valid, const void* d_ratio, void* hip_stream);
 
 /*
+ * alacgpu_biquad_device: a cascade of second-order IIR sections and a gain per row on the crops, behind the noise mix and in
+ * front of the features (no counterpart in the reference): volume perturbation, band-limiting, random EQ; one launch, no
+ * atomics, no scratch, the same inputs give the same bits.  The layout is planar float32: d_src and d_out [rows, channels,
+ * stride], the first `frames` elements of a plane are data, what lies behind them is neither read nor written.  d_out is d_src
+ * itself (in place) or an array of that layout apart from it.  For row r, with v = min(max(d_valid[r], 0), frames) (int64
+ * [rows]; NULL: frames), q = d_coeffs[r] (float64 [rows, sections, 5] = (b0, b1, b2, a1, a2), a0 divided out, 1 <= sections
+ * <= 8) and g = d_gain[r] (float64 [rows]; NULL: 1), u_0 = x widened to float64, every section from zero history,
+ *   u_{k+1}[n] = b0 u_k[n] + b1 u_k[n-1] + b2 u_k[n-2] - a1 u_{k+1}[n-1] - a2 u_{k+1}[n-2]     for n < v, in float64
+ *   y[c, n]    = fl32(g * u_sections[n])                           rounded once; with clamp then min(max(y, -1), 1), a NaN kept
+ * Frames at or behind v are untouched (out of place too: d_out keeps what it held), and a row whose sections are all exactly
+ * (1, 0, 0, 0, 0) with a gain of exactly 1 and no clamp is neither read nor written: "nothing for this crop".  The recurrence
+ * is evaluated blocked, not sample after sample: a workgroup of 256 lanes takes a (row, channel) in tiles of 4096 frames in
+ * ascending order, a lane 16 consecutive frames in registers as float64 through all sections, nothing rounded between them;
+ * per section the FIR part and the zero-state recursion over the chunk, the chunk-end states combined by a scan with the
+ * powers of the section's 2 x 2 transition matrix (6 steps within a wave, then wave after wave, the last state carried to the
+ * next tile), and the incoming state added through the section's two homogeneous responses, which are run once per row and
+ * section.  Every operation is one IEEE float64 operation in a fixed order, none fused (csrc/alac_biquad.h and
+ * alac.net_amd/biquad.py state it; the twin there equals the kernel bit for bit, and the module derives how far the blocked
+ * evaluation may be from the sequential one).  Anything else follows IEEE: coefficients and gains that are not finite, and
+ * poles outside the unit circle, are data; a NaN in x below v reaches later frames of its own plane only; one at or behind v
+ * is never read.  Loads and stores are 16 bytes wide where both bases and the stride are multiples of 16 bytes, single frames
+ * otherwise, with the same result.  A tile is read before it is written and nothing behind it is read again.  Nothing of the
+ * ctx is used but its device, so calls on different streams are independent.  Device pointers only, asynchronous on
+ * hip_stream, nothing is read back.  rows == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx, d_src, d_out or d_coeffs, a misaligned array (4; 8 for d_valid,
+ * d_coeffs and d_gain), channels 0, sections 0 or above 8, frames 0 or above stride, d_src and d_out that overlap without
+ * being equal, d_coeffs or d_gain overlapping d_out, an extent of 2^60 bytes or more, 2^31 workgroups or more.
+ */
+int alacgpu_biquad_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t channels, uint64_t stride,
+                          uint64_t frames, const void* d_valid, const void* d_coeffs, uint32_t sections, const void* d_gain,
+                          int clamp, void* hip_stream);
+
+/*
  * alacgpu_reverb_device: room reverberation into the crops, in front of the noise mix (no counterpart in the reference): every
  * crop convolved with its own impulse response by a uniformly partitioned overlap-save convolution; two launches, no atomics,
  * the same inputs give the same bits.  The layout is planar float32: d_src and d_out [rows, channels, stride], d_rir [rows,

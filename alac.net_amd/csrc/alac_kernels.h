@@ -61,7 +61,7 @@ struct alac_decode_params {
     // alac_decode_ab_kernel, then alac_decode_ab32_kernel: flag g covers packets 8g .. 8g+7.  The first writes 0 where it
     // decoded the group and 1 where it did not; the second decodes the groups flagged 1 and writes 2 there.  One array per
     // launch pair in flight (the host keeps a pool, alacgpu_api.hip: launch_slot).
-    // With the paired kernel in front (pair_ran): it sets the flag of a group of which it left four packets undecoded to
+    // With a paired kernel in front (pair_ran): it sets the flag of a group of which it left packets (four or all eight) undecoded to
     // AB_FLAG_PAIR_LEFT (the flags are zeroed in front of it); alac_decode_ab_small_kernel then decodes the groups flagged so,
     // all eight packets, and leaves the others alone (their flag stays 0).
     uint32_t* ab_flags;
@@ -89,7 +89,8 @@ struct alac_decode_params {
     // in calls that neither read nor write it; the two-pass kernels write an entry per compressed two-channel packet, the paired
     // kernel reads them.  pair_stats: PAIR_COUNTERS device counters -- packets the paired kernel finished with a verified start,
     // packets it found no entry for, packets whose remembered start was wrong, workgroups that left their packets to the launch
-    // behind (for any reason), workgroups that finished theirs; pair_stats_host: their page-locked copy, brought up
+    // behind (for any reason), groups of 4 packets that workgroups finished (one per workgroup of the 4-packet kernel, two per
+    // workgroup of the 8-packet one: a packet that sends its workgroup away weighs the same in both); pair_stats_host: their page-locked copy, brought up
     // to date by the launch behind the paired kernel.  pair_ran: the paired kernel ran in front of this launch.
     alac_pair_entry* pair_table;
     uint32_t pair_mask;
@@ -106,6 +107,8 @@ extern "C" __global__ void alac_decode_ab_small_kernel(alac_decode_params p);   
 // one pass, 4 packets / workgroup, both channels of a packet side by side from a remembered start of channel B; in front of
 // alac_decode_ab_small_kernel, which decodes what this one leaves
 extern "C" __global__ void alac_decode_ab_pair_kernel(alac_decode_params p);
+// the same on the dense layout: 8 packets x 2 channels / workgroup (one entropy wave with 4 lanes per stream, two FIR waves)
+extern "C" __global__ void alac_decode_ab_pair_dense_kernel(alac_decode_params p);
 // test hook (alacgpu_pairing_shift_starts): every remembered start + 1
 extern "C" __global__ void alac_pair_shift_kernel(alac_pair_entry* table, uint32_t entries);
 // the second launch, for the groups of 8 packets the first one flagged: two taps per lane of the FIR wave (orders 9..16) or

@@ -19,6 +19,7 @@
 #include "alac_kernels.h"
 #include "alac_device.h"
 #include "alac_diag.h"
+#include "alac_roles.h"
 
 using namespace alacdev;
 
@@ -683,14 +684,14 @@ __device__ __forceinline__ void ab_fir_block(FirB<T>& f, const typename XqSel<NS
 // the workgroup this wave serves (always 0 when NS == 8).  L = 16 (orders above 16): a row per stream, TWO waves share the 8
 // streams of the workgroup (w = 0 / 1: streams 0..3 / 4..7): half the taps per lane, so a step of either wave is a little more
 // than half as long -- and the FIR step's serial chain is what such a workgroup waits for.
-// PAIR (the paired kernel): stream g is channel g >> 2 of packet g & 3, whatever `ph_in`.
+// PAIR (the paired kernels): stream g is channel g / (NS / 2) of packet g % (NS / 2), whatever `ph_in`.
 template <int T, bool WIDE, bool SPECIAL, int NS, int L = 8, bool PAIR = false>
 __device__ __forceinline__ void ab_fir_wave(const alac_decode_params& p, uint32_t pkt0, int w, int lane, AbSharedT<NS>& sh, int ph_in, int nchunks) {
     constexpr int QS = NS + 1;
     const int row = lane >> 4, l = lane & 15, par = L == 16 ? 0 : l & 1, jl = L == 16 ? l : l >> 1;
     const int g = L == 16 ? 4 * w + row : 8 * w + 2 * row + par;
-    const uint32_t pkt = pkt0 + (uint32_t)(PAIR ? g & 3 : g);
-    const int ph = PAIR ? g >> 2 : ph_in;
+    const uint32_t pkt = pkt0 + (uint32_t)(PAIR ? g & (NS / 2 - 1) : g);
+    const int ph = PAIR ? g / (NS / 2) : ph_in;
     const bool valid = pkt < p.n_packets;
     alacgpu_cfg_dev cfg;
     const Meta m = parse_meta(p, pkt, ph, valid, cfg);
@@ -818,12 +819,12 @@ struct AbRefill {
     int r, sub;
     uint32_t filled = 0, cnt = 0;
     uint4 v[ROUNDS];
-    // pair (the paired kernel): stream r reads packet r & 3
+    // pair (the paired kernels): stream r reads packet r % (NS / 2)
     __device__ AbRefill(const alac_decode_params& p, uint32_t pkt0, int w, int lane, AbSharedT<NS>& sh_, bool pair = false) : sh(sh_) {
         r = 8 * w + (lane >> 3);
         sub = lane & 7;
         ring = sh.rings[r];
-        const uint32_t pk = pkt0 + (uint32_t)(pair ? r & 3 : r);
+        const uint32_t pk = pkt0 + (uint32_t)(pair ? r & (NS / 2 - 1) : r);
         base = p.blob;
         limit = 0;
         if (pk < p.n_packets) {                // as parse_meta: 16-byte aligned-down packet start, bytes up to the packet's end
@@ -1075,8 +1076,9 @@ __device__ __forceinline__ void ab_fir_role(const alac_decode_params& p, uint32_
 }
 
 // The role of a workgroup's wave, by the SIMD it landed on and the workgroup's turn on its CU (ab_kernel_body says why); in
-// wave order without the counters or when the waves do not sit one per SIMD.
-template <int NS>
+// wave order without the counters or when the waves do not sit one per SIMD.  PERM (the 16-stream paired kernel): the roles by
+// alac_roles.h's permutation instead of the rotation.
+template <int NS, bool PERM = false>
 __device__ __forceinline__ int ab_role(const alac_decode_params& p, AbSharedT<NS>& sh, int wave, int lane) {
     int role = wave;
     if (p.cu_arrivals) {
@@ -1089,26 +1091,32 @@ __device__ __forceinline__ int ab_role(const alac_decode_params& p, AbSharedT<NS
         if (lane == 0) sh.ring_on[wave] = my_simd;
         wg_sync();
         const uint32_t used = (1u << sh.ring_on[0]) | (1u << sh.ring_on[1]) | (1u << sh.ring_on[2]) | (1u << sh.ring_on[3]);
-        if (used == 15u) role = (int)((my_simd - sh.ring_next[NS - 1]) & 3u);       // (else: not one wave per SIMD -- wave order)
+        if (used == 15u)                                                            // (else: not one wave per SIMD -- wave order)
+            role = PERM ? pair_role_of_simd(sh.ring_next[NS - 1], my_simd) : (int)((my_simd - sh.ring_next[NS - 1]) & 3u);
     }
     return role;
 }
 
 // ===================================================================================================================
-// The paired kernel: ONE pass over 4 packets per workgroup.  Stream g < 4 is channel A of packet g, stream g + 4 channel B of
-// the same packet, decoded side by side: B from the bit position an earlier decode of the packet remembered
+// The paired kernels: ONE pass over P = NS / 2 packets per workgroup.  Stream g < P is channel A of packet g, stream g + P
+// channel B of the same packet, decoded side by side: B from the bit position an earlier decode of the packet remembered
 // (alac_decode_params::pair_table).  Where A ends is where B starts, so when A is done the entropy wave knows whether the
 // remembered start was right; only then it writes status and lengths.  A workgroup whose packets do not all qualify, or whose
 // remembered start was wrong, flags its group of 8 (AB_FLAG_PAIR_LEFT) for the two-pass kernel behind it, which overwrites
 // whatever PCM this one stored.  A decode from a wrong start reads its ring (address-masked; refills clamped to the packet)
 // and stores frames i < n of the packet's own slot, like any other: wrong values, never a wrong place.
 // The roles, the queues and the barriers are the two-pass kernels' (one pass of nchunks + 2); the output wave un-mixes
-// stream g with stream g + 4 straight from the FIR wave's queue: nothing is parked.
+// stream g with stream g + P straight from the FIR waves' queue: nothing is parked.
+// NS = 8: 4 packets on the 8-stream layout (8 lanes per stream in the entropy wave, one FIR wave).  NS = 16: 8 packets on the dense
+// layout -- one entropy wave with 4 lanes per stream, A on its lanes 0..31 and B on 32..63 in either form; FIR wave 0 takes the
+// A streams and FIR wave 1 the B streams; one output wave for all 16.
 // ===================================================================================================================
-__device__ __forceinline__ void ab_pair_entropy_wave(const alac_decode_params& p, uint32_t pkt0, int lane, AbSharedT<8>& sh, int nch,
+template <int NS>
+__device__ __forceinline__ void ab_pair_entropy_wave(const alac_decode_params& p, uint32_t pkt0, int lane, AbSharedT<NS>& sh, int nch,
                                                      uint32_t start_b) {
-    const int g = lane >> 3, sub = lane & 7, ch = g >> 2;
-    const uint32_t pkt = pkt0 + (uint32_t)(g & 3);
+    constexpr int LPS = 64 / NS, P = NS / 2;
+    const int g = lane / LPS, sub = lane % LPS, ch = g / P;
+    const uint32_t pkt = pkt0 + (uint32_t)(g & (P - 1));
     const bool valid = pkt < p.n_packets;
     alacgpu_cfg_dev cfg;
     const Meta m = parse_meta(p, pkt, 0, valid, cfg);
@@ -1122,8 +1130,8 @@ __device__ __forceinline__ void ab_pair_entropy_wave(const alac_decode_params& p
     rc.rss = m.rss;
     int fl = 0;
     DIAG_ONLY(SpecStats st;)
-    const uint32_t end = ab_entropy_pass<8>(p, sh, m, rc, cfg.rice_initial_history, ch ? start_b : m.ricebit, compressed && (ch == 0 || m.stereo),
-                                            g, sub, lane, nch, &fl DIAG_ONLY(, st));
+    const uint32_t end = ab_entropy_pass<NS>(p, sh, m, rc, cfg.rice_initial_history, ch ? start_b : m.ricebit, compressed && (ch == 0 || m.stereo),
+                                             g, sub, lane, nch, &fl DIAG_ONLY(, st));
     const uint32_t end_a = (uint32_t)mirror_i((int)end, lane & 31), end_b = (uint32_t)mirror_i((int)end, (lane & 31) + 32);
     const int flags_a = mirror_i(fl, lane & 31), flags_b = mirror_i(fl, (lane & 31) + 32);
     // ---- the verification: A's end is B's start ----
@@ -1133,14 +1141,14 @@ __device__ __forceinline__ void ab_pair_entropy_wave(const alac_decode_params& p
         if (lane == 0) {
             atomicAdd(&p.pair_stats[2], (unsigned long long)__builtin_popcountll(wrong));
             atomicAdd(&p.pair_stats[3], 1ull);
-            p.ab_flags[blockIdx.x >> 1] = AB_FLAG_PAIR_LEFT;
+            p.ab_flags[blockIdx.x * (uint32_t)P / 8u] = AB_FLAG_PAIR_LEFT;
         }
         return;
     }
     const uint64_t hits = __builtin_amdgcn_ballot_w64(owner && two);
     if (lane == 0) {
         atomicAdd(&p.pair_stats[0], (unsigned long long)__builtin_popcountll(hits));
-        atomicAdd(&p.pair_stats[4], 1ull);
+        atomicAdd(&p.pair_stats[4], (unsigned long long)(P / 4));   // in groups of 4 packets, whatever the workgroup holds
     }
     // ---- lengths and status, in the reference's control-flow order (as ab_entropy_wave) ----
     if (owner) {
@@ -1168,22 +1176,26 @@ __device__ __forceinline__ void ab_pair_entropy_wave(const alac_decode_params& p
     }
 }
 
-// The paired kernel's output wave.  Lane 2 t + par of row r of the FIR wave's queue holds out[last - t] of stream 2 r + par:
-// channel A of packet 2 r + par in rows 0 / 1, its channel B 32 lanes further on.  Lanes 0..31 take the first two blocks of 8
-// samples of a chunk, lanes 32..63 (the same packets) the other two.
+// The paired kernels' output wave.  Lane 2 t + par of row r of the FIR waves' queue holds out[last - t] of stream 2 r + par:
+// channel A of packet 2 r + par in the first W = 4 NS lanes of the queue, its channel B W lanes further on.  W lanes take a block
+// of 8 samples of every packet: with NS = 8 lanes 0..31 take the first two blocks of a chunk and lanes 32..63 (the same packets)
+// the other two; with NS = 16 the 64 lanes take all four, one after the other.  The conversion and the ring refill go by blocks of
+// 8 streams, as in AbOutBlock.
+template <int NS>
 struct AbPairOut {
+    static constexpr int P = NS / 2, NB = NS / 8, W = 4 * NS, HPL = (AB_CHUNK / 8) * W / 64;   // HPL: blocks of 8 samples per lane and chunk
     const alac_decode_params& p;
-    AbSharedT<8>& sh;
+    AbSharedT<NS>& sh;
     int lane, la, j, hsel;
     Meta m;
     int n_out, bias;
     int32_t* pcm_slot;
-    AbRefill<8> rf;
-    int cs, cq;             // conversion: this lane's stream and the quantiser mask (1 << q) - 1 of its channel
-    __device__ __forceinline__ AbPairOut(const alac_decode_params& p_, uint32_t pkt0, int lane_, AbSharedT<8>& sh_)
-        : p(p_), sh(sh_), lane(lane_), rf(p_, pkt0, 0, lane_, sh_, true) {
-        la = lane & 31;
-        hsel = lane >> 5;
+    AbRefill<NS> rf0, rf1;  // (rf1: the second block of 8 streams, NS = 16 only)
+    int cs, cq[NB];         // conversion: this lane's stream of block 0 and the quantiser mask (1 << q) - 1 of its channel, per block
+    __device__ __forceinline__ AbPairOut(const alac_decode_params& p_, uint32_t pkt0, int lane_, AbSharedT<NS>& sh_)
+        : p(p_), sh(sh_), lane(lane_), rf0(p_, pkt0, 0, lane_, sh_, true), rf1(p_, pkt0, NB - 1, lane_, sh_, true) {
+        la = lane & (W - 1);
+        hsel = lane / W;
         j = (la & 15) >> 1;
         const uint32_t pkt = pkt0 + (uint32_t)(2 * (la >> 4) + (la & 1));
         const bool valid = pkt < p.n_packets;
@@ -1193,29 +1205,38 @@ struct AbPairOut {
         bias = 1 << (m.rss - 1);
         pcm_slot = p.pcm_out + (int64_t)pkt * p.slot_ints;
         cs = QROWS ? lane >> 3 : lane & 7;
-        const uint32_t cpkt = pkt0 + (uint32_t)(cs & 3);
-        cq = (1 << parse_meta(p, cpkt, cs >> 2, cpkt < p.n_packets, cfg).q) - 1;
+#pragma unroll
+        for (int w = 0; w < NB; w++) {
+            const int s = 8 * w + cs;
+            const uint32_t cpkt = pkt0 + (uint32_t)(s & (P - 1));
+            cq[w] = (1 << parse_meta(p, cpkt, s / P, cpkt < p.n_packets, cfg).q) - 1;
+        }
     }
     // after barrier b: chunk b's code values -> what the FIR step wants; chunk b-2's outputs are in the queue
     __device__ __forceinline__ void step(int b, int nch) {
         if (b < nch) {
-            rf.issue(b == 0);
+            rf0.issue(b == 0);
+            if (NB > 1) rf1.issue(b == 0);
             const auto& src = sh.resq[b & 1];
-            XQ (*dst)[9] = sh.xq[b & 1];
+            typename XqSel<NS>::type (*dst)[NS + 1] = sh.xq[b & 1];
 #pragma unroll
-            for (int k = 0; k < AB_CHUNK / 8; k++) {
-                const int i = QROWS ? (lane & 7) + 8 * k : (lane >> 3) + 8 * k;
-                XQ x;
-                xq_from_code(x, (uint32_t)(QROWS ? src[cs][i] : src[i][cs]), cq);
-                dst[i][cs] = x;
+            for (int w = 0; w < NB; w++) {
+                const int s = 8 * w + cs;
+#pragma unroll
+                for (int k = 0; k < AB_CHUNK / 8; k++) {
+                    const int i = QROWS ? (lane & 7) + 8 * k : (lane >> 3) + 8 * k;
+                    typename XqSel<NS>::type x;
+                    xq_from_code(x, (uint32_t)(QROWS ? src[s][i] : src[i][s]), cq[w]);
+                    dst[i][s] = x;
+                }
             }
         }
         if (b >= 2) {
             const int c = b - 2;
             const UbWin none = {0u, 0u};
 #pragma unroll
-            for (int hh = 0; hh < AB_CHUNK / 16; hh++) {
-                const int half = (AB_CHUNK / 16) * hsel + hh;
+            for (int hh = 0; hh < HPL; hh++) {
+                const int half = HPL * hsel + hh;
                 const int ih = c * AB_CHUNK + 8 * half;
                 const int cnt = min(8, n_out - ih);
                 if (j >= cnt) continue;
@@ -1238,7 +1259,7 @@ struct AbPairOut {
                     if (m.nc > 1) store_sample<false>(p, m, pcm_slot, 0u, i, 1, 0);
                     continue;
                 }
-                const int bb = sh.outq[c & 1][half][la + 32] - bias;
+                const int bb = sh.outq[c & 1][half][la + W] - bias;
                 int left, right;
                 if (m.mixweight != 0) {                                 // AlacFile.cs:346-357 / :377-388
                     right = wsub(a, wmul(bb, m.mixweight) >> (m.mixshift & 31));
@@ -1251,19 +1272,29 @@ struct AbPairOut {
                 if (m.nc > 1) store_sample<false>(p, m, pcm_slot, 0u, i, 1, ab_finish24<false>(m, none, right, i, 1));
             }
         }
-        if (b < nch) rf.commit();
+        if (b < nch) {
+            rf0.commit();
+            if (NB > 1) rf1.commit();
+        }
     }
 };
 
-__device__ __forceinline__ void ab_pair_body(const alac_decode_params& p, AbSharedT<8>& sh) {
+// ALAC_PAIR_PERM: the 16-stream form takes its roles from alac_roles.h's permutation (1) or from the two-pass kernels' rotation (0)
+#ifndef ALAC_PAIR_PERM
+#define ALAC_PAIR_PERM 1
+#endif
+template <int NS>
+__device__ __forceinline__ void ab_pair_body(const alac_decode_params& p, AbSharedT<NS>& sh) {
+    constexpr int P = NS / 2, LPS = 64 / NS;
+    static_assert(P * PAIR_WAYS <= 64, "one way per lane");
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t pkt0 = blockIdx.x * 4u;
-    // every wave reads the four headers and looks the two-channel packets up: what the workgroup does is uniform
+    const uint32_t pkt0 = blockIdx.x * (uint32_t)P;
+    // every wave reads the P headers and looks the two-channel packets up: what the workgroup does is uniform
     int n0 = 0;
     bool bad = false, miss = false, two = false;
     uint32_t start_b = 0;
     {
-        const uint32_t pk = pkt0 + (uint32_t)(lane & 3);
+        const uint32_t pk = pkt0 + (uint32_t)(lane & (P - 1));
         const bool v = pk < p.n_packets;
         alacgpu_cfg_dev c;
         const Meta ma = parse_meta(p, pk, 0, v, c);
@@ -1275,46 +1306,46 @@ __device__ __forceinline__ void ab_pair_body(const alac_decode_params& p, AbShar
         // (parse_meta turns a slot without it into a status only for a one-channel stream cfg)
         bad = comp && (ma.N < 1 || ma.N > 8 || (ma.stereo && (mb.N < 1 || mb.N > 8)) || (!ma.stereo && ma.predtype != 0) || ma.rss > 23 ||
                        (ma.stereo && (uint64_t)2 * (uint64_t)ma.n > p.slot_ints));
-        // lane 4 w + k looks at way w of packet k's set (the upper half of the wave repeats the lower)
+        // lane P w + k looks at way w of packet k's set (P = 4: the upper half of the wave repeats the lower; P = 8: exactly one wave)
         two = comp && ma.stereo;
         uint4 e = make_uint4(0u, 0u, 0u, 0u);
         bool found = false;
         if (two) {
             const PairKey key = pair_key(p, pk, ma);
-            e = *reinterpret_cast<const uint4*>(&p.pair_table[key.idx + (uint32_t)((lane >> 2) & (PAIR_WAYS - 1))]);
+            e = *reinterpret_cast<const uint4*>(&p.pair_table[key.idx + (uint32_t)((lane / P) & (PAIR_WAYS - 1))]);
             found = pair_match(e, key) && e.w >= ma.ricebit;
         }
-        const uint32_t ways = (uint32_t)__builtin_amdgcn_ballot_w64(found) & (0x11111111u << (lane & 3));
+        const uint64_t ways = __builtin_amdgcn_ballot_w64(found) & ((P == 8 ? 0x0101010101010101ull : 0x1111111111111111ull) << (lane & (P - 1)));
         miss = two && ways == 0u;
-        start_b = (uint32_t)mirror_i((int)e.w, ways ? __builtin_ctz(ways) : lane);
+        start_b = (uint32_t)mirror_i((int)e.w, ways ? (int)__builtin_ctzll(ways) : lane);
     }
-    const uint64_t misses = __builtin_amdgcn_ballot_w64(miss && lane < 4);
+    const uint64_t misses = __builtin_amdgcn_ballot_w64(miss && lane < P);
     // (a workgroup without a two-channel packet has nothing to pair: the two-pass kernel decodes 8 such packets per workgroup)
     if (misses != 0 || __builtin_amdgcn_ballot_w64(bad) != 0 || __builtin_amdgcn_ballot_w64(two) == 0) {
         if (threadIdx.x == 0) {
             if (misses != 0) atomicAdd(&p.pair_stats[1], (unsigned long long)__builtin_popcountll(misses));
             atomicAdd(&p.pair_stats[3], 1ull);
-            p.ab_flags[blockIdx.x >> 1] = AB_FLAG_PAIR_LEFT;
+            p.ab_flags[blockIdx.x * (uint32_t)P / 8u] = AB_FLAG_PAIR_LEFT;
         }
         return;
     }
     const int nch = (__builtin_amdgcn_readfirstlane(wave_max(n0)) + AB_CHUNK - 1) / AB_CHUNK;
-    for (int t = threadIdx.x; t < 2 * AB_CHUNK; t += blockDim.x) xq_zero(sh.xq[t / AB_CHUNK][t % AB_CHUNK][8]);
-    const int role = ab_role<8>(p, sh, wave, lane);
-    if (role == 3) return;     // the fourth wave was only there to claim the fourth SIMD
+    for (int t = threadIdx.x; t < 2 * AB_CHUNK; t += blockDim.x) xq_zero(sh.xq[t / AB_CHUNK][t % AB_CHUNK][NS]);
+    const int role = ab_role<NS, NS == 16 && ALAC_PAIR_PERM != 0>(p, sh, wave, lane);
+    if (NS == 8 && role == 3) return;     // the fourth wave was only there to claim the fourth SIMD
     wg_sync();
     if (role == 0) {
         __builtin_amdgcn_s_setprio(ALAC_ENTROPY_PRIO);
-        ab_pair_entropy_wave(p, pkt0, lane, sh, nch, (uint32_t)mirror_i((int)start_b, (lane >> 3) & 3));
+        ab_pair_entropy_wave<NS>(p, pkt0, lane, sh, nch, (uint32_t)mirror_i((int)start_b, (lane / LPS) & (P - 1)));
     } else if (role == 1) {
-        AbPairOut out(p, pkt0, lane, sh);
+        AbPairOut<NS> out(p, pkt0, lane, sh);
         for (int b = 0; b <= nch + 1; b++) {
             wg_sync();
             out.step(b, nch);
         }
     } else {
         __builtin_amdgcn_s_setprio(1);
-        ab_fir_wave<1, false, false, 8, 8, true>(p, pkt0, 0, lane, sh, 0, nch);
+        ab_fir_wave<1, false, false, NS, 8, true>(p, pkt0, role - 2, lane, sh, 0, nch);
     }
 }
 
@@ -1436,7 +1467,7 @@ __device__ __forceinline__ void ab_kernel_body(const alac_decode_params& p, AbSh
 
 }  // namespace
 
-// One kernel entry per object file: the Makefile compiles this source six times (-DALAC_EMIT=1 .. 6), each kernel with
+// One kernel entry per object file: the Makefile compiles this source seven times (-DALAC_EMIT=1 .. 7), each kernel with
 // the instruction-scheduler settings it measured best with (Makefile: SCHED_*).  Without ALAC_EMIT all of them are emitted.
 #if !defined(ALAC_EMIT) || ALAC_EMIT == 1
 // The main kernel for batches whose workgroups fit the chip four per CU (up to 10240 packets): 128 registers, nothing spilled.
@@ -1469,7 +1500,15 @@ extern "C" __global__ __launch_bounds__(256, 4) void alac_decode_ab_small_win_ke
 // before (alacgpu_api.hip: launch), in front of alac_decode_ab_small_kernel.
 extern "C" __global__ __launch_bounds__(256, 4) void alac_decode_ab_pair_kernel(alac_decode_params p) {
     __shared__ __attribute__((aligned(1024))) AbSharedT<8> sh;
-    ab_pair_body(p, sh);
+    ab_pair_body<8>(p, sh);
+}
+#endif
+#if !defined(ALAC_EMIT) || ALAC_EMIT == 7
+// The paired kernel on the dense layout: 8 packets x 2 channels per workgroup, half as many workgroups and fewer instructions per
+// sample than the 4-packet form (one entropy wave and one output wave serve twice as many streams).
+extern "C" __global__ __launch_bounds__(256, 4) void alac_decode_ab_pair_dense_kernel(alac_decode_params p) {
+    __shared__ __attribute__((aligned(1024))) AbSharedT<16> sh;
+    ab_pair_body<16>(p, sh);
 }
 #endif
 #if !defined(ALAC_EMIT) || ALAC_EMIT == 4

@@ -224,9 +224,13 @@ int launch(alacgpu_ctx* ctx, const alac_decode_params& p_in, hipStream_t stream,
         k = window_build(k);
         k2 = window_build(k2);
     }
-    if (paired) {   // the flags start at 0; the paired kernel (4 packets per workgroup) marks the groups it leaves
+    if (paired) {   // the flags start at 0; the paired kernel (8 or 4 packets per workgroup) marks the groups it leaves
         HIP_TRY(ctx, hipMemsetAsync(sl.d_flags, 0, sizeof(uint32_t) * groups, stream));
-        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_decode_ab_pair_kernel, dim3((p.n_packets + 3u) / 4u), dim3(256), kargs, 0, stream));
+        const bool dense_form = ctx->pair_dense < 0 ? p.n_packets >= PAIR_DENSE_MIN_PACKETS : ctx->pair_dense != 0;
+        if (dense_form)
+            HIP_TRY(ctx, hipLaunchKernel((const void*)alac_decode_ab_pair_dense_kernel, dim3((p.n_packets + 7u) / 8u), dim3(256), kargs, 0, stream));
+        else
+            HIP_TRY(ctx, hipLaunchKernel((const void*)alac_decode_ab_pair_kernel, dim3((p.n_packets + 3u) / 4u), dim3(256), kargs, 0, stream));
         ctx->pair_launches++;
     }
     HIP_TRY(ctx, hipLaunchKernel(k, dim3((uint32_t)first_groups), dim3(256), kargs, 0, stream));
@@ -477,6 +481,7 @@ int alacgpu_create(const alacgpu_cfg* cfgs, uint32_t n_cfgs, int device, alacgpu
     ctx->device = device;
     ctx->n_cfgs = n_cfgs;
     if (const char* v = std::getenv("ALACGPU_DENSE")) ctx->dense = std::max(-1, std::min(std::atoi(v), 4));   // negative: auto
+    if (const char* v = std::getenv("ALACGPU_PAIR_DENSE")) ctx->pair_dense = std::max(-1, std::min(std::atoi(v), 1));   // negative: by batch size
     if (const char* v = std::getenv("ALACGPU_HOST_CHUNKS")) ctx->host_chunks = std::max(0, std::min(std::atoi(v), N_HOST_STREAMS));
     if (const char* v = std::getenv("ALACGPU_ZERO_COPY")) ctx->zero_copy = std::atoi(v) != 0;
     int rc = ALACGPU_OK;

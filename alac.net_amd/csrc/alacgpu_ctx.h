@@ -14,7 +14,8 @@
 
 constexpr int N_SLOTS = 8;          // launch pairs that may be in flight at once on one ctx (any streams)
 constexpr uint32_t AB_SMALL_MAX_PACKETS = 4096;  // up to here: the build with 16-step speculative units (latency-bound launches)
-constexpr uint32_t AB5_MIN_PACKETS = 10241;     // above: the 96-register build of the 8-packet arrangement (five workgroups per CU)
+constexpr uint32_t PAIR_DENSE_MIN_PACKETS = 2049;   // from here: the paired kernel's 8-packet form (more than one 4-packet workgroup per SIMD set)
+constexpr uint32_t AB5_MIN_PACKETS = 10241;    // above: the 96-register build of the 8-packet arrangement (five workgroups per CU)
 constexpr uint32_t DENSE_MIN_PACKETS = 12289;   // measured cross-over of the two arrangements of the main kernel
 // Pairing (the paired kernel in front of the small-batch launch).  The table: a power of two of entries, at
 // least PAIR_TABLE_FACTOR times the largest batch seen, in sets of PAIR_WAYS.  (A packet evicted by another sends its whole group
@@ -25,7 +26,8 @@ constexpr uint32_t DENSE_MIN_PACKETS = 12289;   // measured cross-over of the tw
 //     that are new in every call, a working set that outgrows the table: such calls only pay the empty launch), or
 //   - more packets with a wrong remembered start than packets finished (a caller that rewrites its packets in place), or
 //   - from the second window on (the first holds the cold calls) more than one workgroup that left its packets per
-//     PAIR_DONE_PER_LEFT that finished: a call in which any group falls back takes as long as both kernels.
+//     PAIR_DONE_PER_LEFT groups of 4 packets that finished (the 4-packet kernel counts one per workgroup, the 8-packet kernel
+//     two: a lost entry weighs the same in both): a call in which any group falls back takes as long as both kernels.
 // PAIR_RETRY launches later the context tries a window again: what it decodes may have changed.
 constexpr uint32_t PAIR_TABLE_FACTOR = 64, PAIR_TABLE_MIN = 1024;
 constexpr unsigned PAIR_WINDOW = 16, PAIR_RETRY = 4096;
@@ -101,6 +103,7 @@ struct alacgpu_ctx {
     uint32_t out_format = 0;           // 0 int32 per sample, 1 packed little-endian PCM
     int host_chunks = 0;               // 0 auto; 1..N_HOST_STREAMS forced (ALACGPU_HOST_CHUNKS, A/B only)
     int dense = DENSE_AUTO;            // the first launch's build (dense_mode, ALACGPU_DENSE)
+    int pair_dense = -1;               // the paired kernel's form (ALACGPU_PAIR_DENSE): negative by batch size, 0 the 4-packet one, 1 the 8-packet one
     uint32_t* d_cu_arrivals = nullptr; // per-CU workgroup counters (alac_decode_params::cu_arrivals): ONE array per device, shared by
                                        // every context of the process on it (cu_counters_acquire), so that launches of different
                                        // contexts take their turns on a CU from the same counter

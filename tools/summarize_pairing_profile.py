@@ -1,4 +1,4 @@
-"""profiles/pairing_pmc_summary_cfg2.json, profiles/traffic_cfg2.json and the two kernel-stats tables from a directory of rocprofv3 runs of
+"""profiles/pairing_dense_pmc_summary_cfg2.json, profiles/traffic_cfg2.json and the two kernel-stats tables (profiles/pairing_dense_kernel_stats_cfg2*.csv) from a directory of rocprofv3 runs of
 bench.py --config 2 --steps 12 --warmup 3 (one --kernel-trace --stats run of the parent tree in stats_parent/, of this tree in stats_cfg2/, and one
 --pmc run per counter group in pmc_fetch_cfg2/, pmc_write_cfg2/, pmc_sq_cfg2/).  Figures are medians over calls 4..15: the first call finds
 nothing remembered.   usage (repository root): python tools/summarize_pairing_profile.py DIR"""
@@ -35,7 +35,7 @@ doc["per_kernel"] = {k: {"FETCH_SIZE_KB": med(warm(fe[k]["FETCH_SIZE"])), "WRITE
                          "SQ_INSTS_VALU": med(warm(sq[k]["SQ_INSTS_VALU"])), "SQ_INSTS_SALU": med(warm(sq[k]["SQ_INSTS_SALU"])), "SQ_INSTS_LDS": med(warm(sq[k]["SQ_INSTS_LDS"])),
                          "first_call": {"FETCH_SIZE_KB": fe[k]["FETCH_SIZE"][0], "WRITE_SIZE_KB": wr[k]["WRITE_SIZE"][0], "SQ_INSTS_VALU": sq[k]["SQ_INSTS_VALU"][0]}} for k in fe}
 gui = tot(wr, "GRBM_GUI_ACTIVE"); 
-main = "alac_decode_ab_pair_kernel"
+main = "alac_decode_ab_pair_dense_kernel"
 wt = collections.defaultdict(list)
 doc["traffic"] = {"FETCH_SIZE_KB_raw": fetch_kb, "WRITE_SIZE_KB": write_kb, "read_bytes_per_launch": 2 * fetch_kb * 1024, "write_bytes_per_launch": write_kb * 1024,
                   "hbm_bytes_per_launch": 2 * fetch_kb * 1024 + write_kb * 1024, "bytes_per_sample": (2 * fetch_kb * 1024 + write_kb * 1024) / samples,
@@ -43,11 +43,11 @@ doc["traffic"] = {"FETCH_SIZE_KB_raw": fetch_kb, "WRITE_SIZE_KB": write_kb, "rea
 doc["issue"] = {"valu_wave_instr_per_launch": valu, "valu_wave_instr_per_sample": valu / samples}
 old = json.load(open("profiles/r3_final_pmc_summary_cfg2.json"))
 doc["two_pass_before"] = {"hbm_bytes_per_launch": old["traffic"]["hbm_bytes_per_launch"], "valu_wave_instr_per_sample": old["issue"].get("valu_wave_instr_per_sample"), "source": "profiles/r3_final_pmc_summary_cfg2.json"}
-json.dump(doc, open("profiles/pairing_pmc_summary_cfg2.json", "w"), indent=1)
+json.dump(doc, open("profiles/pairing_dense_pmc_summary_cfg2.json", "w"), indent=1)
 oldt = json.load(open("profiles/traffic_cfg2.json"))
 json.dump({"workload": "cfg2", "kernel": main, "hbm_bytes_per_launch": doc["traffic"]["hbm_bytes_per_launch"], "valu_wave_instr_per_launch": valu,
-           "effective_clock_GHz": oldt["effective_clock_GHz"], "kernel_source_sha": bench.kernel_source_sha(), "source": "profiles/pairing_pmc_summary_cfg2.json"},
+           "effective_clock_GHz": oldt["effective_clock_GHz"], "kernel_source_sha": bench.kernel_source_sha(), "source": "profiles/pairing_dense_pmc_summary_cfg2.json"},
           open("profiles/traffic_cfg2.json", "w"))
-shutil.copy(glob.glob(f"{P}/stats_cfg2/*/*_kernel_stats.csv")[0], "profiles/pairing_kernel_stats_cfg2.csv")
-shutil.copy(glob.glob(f"{P}/stats_parent/*/*_kernel_stats.csv")[0], "profiles/pairing_kernel_stats_cfg2_parent.csv")
+shutil.copy(glob.glob(f"{P}/stats_cfg2/*/*_kernel_stats.csv")[0], "profiles/pairing_dense_kernel_stats_cfg2.csv")
+shutil.copy(glob.glob(f"{P}/stats_parent/*/*_kernel_stats.csv")[0], "profiles/pairing_dense_kernel_stats_cfg2_parent.csv")
 print(json.dumps({k: doc[k] for k in ("kernel_ns_parent", "kernel_ns_this_tree", "launch_ns_parent", "launch_ns_this_tree", "traffic", "issue", "two_pass_before", "per_kernel")}, indent=1))

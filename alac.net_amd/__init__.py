@@ -95,6 +95,8 @@ SYMBOLS = {
                                      _VP, _VP]),
     "alacgpu_biquad_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, _VP, C.c_uint32, _VP, C.c_int,
                                         _VP]),
+    "alacgpu_level_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, C.c_uint32, C.c_uint32, _VP,
+                                       C.c_double, C.c_double, C.c_int, _VP, _VP, _VP, _VP]),
     "alacgpu_reverb_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
                                         C.c_uint64, _VP, _VP, _VP]),
     "alacgpu_specaugment_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, _VP, _VP,
@@ -528,6 +530,21 @@ class AlacGpuContext(_Closing):
         `stream` (raw hipStream_t); nothing is read back."""
         rc = lib().alacgpu_biquad_device(self._ctx, _dp(d_src), _dp(d_out), rows, channels, stride, frames, _dp(d_valid),
                                          _dp(d_coeffs), sections, _dp(d_gain), int(bool(clamp)), _VP(stream))
+        _check(rc, self._ctx)
+
+    def level_device(self, d_src, d_out, rows, channels, stride, frames, d_valid, mode, hop, d_kweight, target, max_peak, clamp,
+                     d_gain_out=None, d_energy_out=None, d_peak_out=None, stream=0):
+        """alacgpu_level_device: every row of d_src (float32 device tensor, planar [rows, channels, stride], the first `frames`
+        of a plane are data) brought to a level over its first v = min(max(d_valid[row], 0), frames) frames, into d_out (d_src
+        itself, the same layout apart from it, or None: measured only).  mode 0, 1, 2: peak, RMS, BS.1770 loudness with hops of
+        `hop` frames and the two K-weighting sections d_kweight (float64 device tensor [2, 5]; None for the other modes);
+        target: linear (the peak, the mean square, 10^((LUFS + 0.691) / 10)); max_peak: the gain's limit, 0 for none; clamp:
+        limited to -1 .. 1.  d_valid: an int64 device tensor [rows], or None for `frames`.  d_gain_out, d_energy_out, d_peak_out:
+        float64 device tensors [rows] for the gain, the measured energy and the peak, or None.  level.py states the arithmetic.
+        Two launches, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_level_device(self._ctx, _dp(d_src), _dp(d_out), rows, channels, stride, frames, _dp(d_valid), mode, hop,
+                                        _dp(d_kweight), float(target), float(max_peak), int(bool(clamp)), _dp(d_gain_out),
+                                        _dp(d_energy_out), _dp(d_peak_out), _VP(stream))
         _check(rc, self._ctx)
 
     def reverb_device(self, d_src, d_out, d_rir, rows, channels, rir_channels, stride, rir_stride, frames, rir_frames, d_valid,
@@ -1156,6 +1173,8 @@ from .mix import AddNoise, mix, mix_host, mix_host_f32  # noqa: E402
 # ---- biquad filters and a gain on crops and tensors (alacgpu_biquad_device) ----------------------------------------------------------
 from .biquad import (Effects, RandomBiquad, allpass, bandpass, bandreject, biquad, biquad_host, biquad_host_twin, highpass,  # noqa: E402
                      highshelf, lowpass, lowshelf, peaking)
+# ---- peak, RMS and loudness levelling of crops and tensors (alacgpu_level_device) --------------------------------------------------
+from .level import Level, kweight, level, level_host, level_host_twin, loudness, loudness_host  # noqa: E402
 # ---- room reverberation into crops and tensors (alacgpu_reverb_device) ------------------------------------------------------------
 from .reverb import Reverb, reverb, reverb_host, reverb_host_f32  # noqa: E402
 # ---- SpecAugment on the features: time warp, frequency and time masks (alacgpu_specaugment_device) -------------------------------

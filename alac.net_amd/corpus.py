@@ -17,12 +17,12 @@ from both tiers into a small staging blob in HBM, and the decode reads that.
 frames a crop needs are decoded as above into a scratch the corpus keeps, and one alacgpu_resample_device call (resample.py
 states the filter) resamples every crop out of it.
 
-`crops(..., reverb=, mix=, effects=, features=, deltas=, vad=, normalize=, augment=)` runs up to nine stages behind the waveform, and `crops` is the one place
+`crops(..., reverb=, mix=, level=, effects=, features=, deltas=, vad=, normalize=, augment=)` runs up to ten stages behind the waveform, and `crops` is the one place
 that lists them: the refusals of all of them, the crops the second corpora make (`Corpus._companion_crops`: the noise of an
 AddNoise, then the impulse responses of a Reverb, each cropped by its own corpus at the rate of the crops), the waveform once
-(`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_biquad_device, alacgpu_logmel_device (or alacgpu_fbank_device or alacgpu_mfcc_device), alacgpu_deltas_device,
+(`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_level_device, alacgpu_biquad_device, alacgpu_logmel_device (or alacgpu_fbank_device or alacgpu_mfcc_device), alacgpu_deltas_device,
 alacgpu_vad_energy_device, the normalisation, alacgpu_select_frames_device and alacgpu_specaugment_device (reverb.py, mix.py,
-biquad.py, features.py, deltas.py, vad.py, normalize.py, sliding.py and augment.py state the arithmetic), each only if asked for.
+level.py, biquad.py, features.py, deltas.py, vad.py, normalize.py, sliding.py and augment.py state the arithmetic), each only if asked for.
 
 `crops(..., speed=)` plays every crop at a drawn factor in front of all that (the same method, speed.py): the step of a corpus
 whose rates differ, with a ratio per (file rate, factor) in place of one per file rate; the crops at factor 1 go through the
@@ -43,6 +43,7 @@ from . import (MAX_FRAME, ST_OK, ST_UNSUPPORTED_ELEMENT, ST_UNSUPPORTED_PREDTYPE
                _VP, _write_file, lib, make_cfgs)
 from .augment import LDS_MAX as _WARP_MAX, _check_draws, _how, _spec_augment
 from .biquad import Effects, _biquad
+from .level import _checked as _level_checked, _level
 from .deltas import Deltas, _add_deltas
 from .fbank import KaldiFbank
 from .mfcc import KaldiMfcc
@@ -648,7 +649,7 @@ class Corpus(_Closing):
         return torch.from_numpy(f.astype(np.int32)).to(self._dev), torch.from_numpy(o).to(self._dev), True
 
     def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True, features=None, normalize=None, mix=None,
-              reverb=None, speed=None, effects=None, deltas=None, vad=None, augment=None, sample_rate=None, mono=False):
+              reverb=None, speed=None, effects=None, level=None, deltas=None, vad=None, augment=None, sample_rate=None, mono=False):
         """Decode crop b = frames frame_offsets[b] .. + num_frames of file files[b] for every b in ONE launch pair: returns
         (pcm [B, C, num_frames] on the device, zero behind lengths[b]; lengths [B], a DEVICE int64 tensor: min(num_frames,
         T_f - offset)).  float32 (default) or int32, as `load`.  files / frame_offsets: sequences, numpy arrays or torch
@@ -673,7 +674,7 @@ class Corpus(_Closing):
         more than 2 channels, draws that are not an integer tensor [B] on the corpus's device.
 
         The stages behind the waveform go by keyword, as sample_rate and mono do, and run in this order whichever are
-        given -- reverb, mix, effects, features, deltas, the VAD's decision, normalize, the selection of the voiced frames, augment --,
+        given -- reverb, mix, level, effects, features, deltas, the VAD's decision, normalize, the selection of the voiced frames, augment --,
         in place but for the features and the deltas, by the corpus's own context on the same stream; lengths (but for vad=,
         which shortens them), `check` and last_status() are those of the call without them (with check=True a second corpus's own check runs too, and first).  ValueError before any device
         work for what a stage cannot take.
@@ -688,6 +689,12 @@ class Corpus(_Closing):
         rate of the crops)` returned.  Bit for bit mix.mix(the crops without it, the noise crops, snr_db, lengths, their
         lengths).  The noise and the responses are cropped by their own corpus's `crops` at the rate of the crops, as one
         channel when its channel count is not theirs, into scratches THIS corpus keeps: a second corpus may be this one.
+
+        level: a level.Level -- every crop brought to a peak, an RMS level or a BS.1770 loudness over its valid frames, behind
+        the noise and in front of the effects, so that a random gain perturbs around the target.  Bit for bit
+        level.level(the crops without it, level, rate of the crops, lengths); a crop outside the corpus stays zeros, and so does
+        a silent one.  It draws nothing.  ValueError: int32 crops, something that is no Level, and for lufs more than 5
+        channels, crops without a rate, a rate below 160 Hz or not above 3000 Hz.
 
         effects: the channel, last on the waveform: a biquad.Effects -- a cascade of biquad sections and a gain per crop --,
         whose draws are then made here from the device's default generator (behind a Reverb's and in front of a SpecAugment's --
@@ -736,7 +743,7 @@ class Corpus(_Closing):
         more than 16384 feature frames."""
         import torch
 
-        # 1. every refusal that needs no device work: speed, mix, reverb, effects, normalize, features, augment; the waveform's own are `_waveform`'s
+        # 1. every refusal that needs no device work: speed, mix, reverb, level, effects, normalize, features, augment; the waveform's own are `_waveform`'s
         rate = self.sample_rate if sample_rate is None else sample_rate
         Co = 1 if mono else self.channels
         if speed is not None:
@@ -745,6 +752,8 @@ class Corpus(_Closing):
             mix = self._second_corpus(mix, _MIX, dtype, rate, Co)
         if reverb is not None:
             reverb = self._second_corpus(reverb, _REVERB, dtype, rate, Co)
+        if level is not None:
+            self._level_given(level, dtype, rate, Co)
         if effects is not None:
             effects = self._effects_given(effects, dtype, rate)
         if normalize is not None:
@@ -788,7 +797,7 @@ class Corpus(_Closing):
             augment = _how(augment, "augment")
             if features is None:
                 raise ValueError("a SpecAugment masks log-mel features: it needs features=")
-        if features is not None or mix is not None or reverb is not None or speed is not None or effects is not None:
+        if features is not None or mix is not None or reverb is not None or speed is not None or effects is not None or level is not None:
             L = _frame_count("num_frames", num_frames)
             if features is not None and L < features.min_frames:
                 raise ValueError(features.short(L))
@@ -830,6 +839,8 @@ class Corpus(_Closing):
             _reverb(ctx, res, d_rir, lengths, torch.where(keep, rir_lengths, 0), res)
         if mix is not None:
             _mix(ctx, res, d_noise, lambda: snr_ratio(snr, B, self._dev), lengths, noise_lengths, res)
+        if level is not None:
+            _level(ctx, res, level, rate, lengths, res)
         if effects is not None:
             _biquad(ctx, res, effects[1][0], lengths, effects[1][1], effects[0].clamp, res)
         if features is not None:
@@ -920,6 +931,16 @@ class Corpus(_Closing):
         if other.channels != Co and other.channels not in (1, 2):
             raise ValueError(stage["channels"].format(n=other.channels, Co=Co))
         return spec, draws
+
+    @staticmethod
+    def _level_given(spec, dtype, rate, Co):
+        """crops(level=) checked: ValueError for what is no Level, for int32 crops and, for lufs, for more than 5 channels, crops
+        without a rate and a rate the K-weighting cannot be designed at.  Nothing is done on the device."""
+        import torch
+
+        _level_checked(spec, rate, Co)
+        if not _is_f32(torch, dtype):
+            raise ValueError("float32 crops are levelled")
 
     def _effects_given(self, given, dtype, rate):
         """crops(effects=) as the pair (Effects, draws or None), checked: ValueError for anything else, for int32 crops, for
@@ -1192,7 +1213,7 @@ class Corpus(_Closing):
         return out, lengths
 
     def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True, features=None, normalize=None,
-                     mix=None, reverb=None, speed=None, effects=None, deltas=None, vad=None, augment=None, sample_rate=None,
+                     mix=None, reverb=None, speed=None, effects=None, level=None, deltas=None, vad=None, augment=None, sample_rate=None,
                      mono=False):
         """`batch` crops of num_frames frames drawn on the device: files uniform over the corpus, the first frame uniform in
         0 .. max(T_f - num_frames, 0).  generator: a torch.Generator (of the corpus's device, or of the CPU: then the draws are
@@ -1202,7 +1223,7 @@ class Corpus(_Closing):
         voiced counts, and nothing is read back for them.  mix as for `crops`; an AddNoise is drawn from
         `generator`, behind the call's own two draws (AddNoise.draw states its four).  reverb as for `crops`; a Reverb is
         drawn from `generator` behind those (Reverb.draw states its two).  effects as for `crops`; an Effects is drawn from
-        `generator` behind those (Effects.draw states its draws).  augment as for `crops`; a SpecAugment is drawn from
+        `generator` behind those (Effects.draw states its draws).  level as for `crops`: it draws nothing.  augment as for `crops`; a SpecAugment is drawn from
         `generator` behind those, for the feat_lengths the call returns (augment.py states its draws) -- with vad= for the
         lengths in front of the selection, which are known without the device's decisions.  speed as for `crops`;
         a SpeedPerturb is drawn from `generator` behind the call's own two draws and in front of an AddNoise's
@@ -1218,6 +1239,8 @@ class Corpus(_Closing):
             mix = self._second_corpus(mix, _MIX, dtype, rate, 1 if mono else self.channels)
         if reverb is not None:
             reverb = self._second_corpus(reverb, _REVERB, dtype, rate, 1 if mono else self.channels)
+        if level is not None:
+            self._level_given(level, dtype, rate, 1 if mono else self.channels)
         if effects is not None:
             effects = self._effects_given(effects, dtype, rate)
         if augment is not None:
@@ -1258,7 +1281,7 @@ class Corpus(_Closing):
             augment = (augment[0], augment[0].draw(lines, feat_lengths, generator=generator))
         pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,
                                   features=features, normalize=normalize, mix=mix, reverb=reverb, augment=augment, speed=speed,
-                                  deltas=deltas, vad=vad, effects=effects)
+                                  deltas=deltas, vad=vad, effects=effects, level=level)
         return pcm, lengths, files, offs
 
     def last_staged_bytes(self):

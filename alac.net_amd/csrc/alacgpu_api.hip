@@ -527,6 +527,7 @@ void alacgpu_destroy(alacgpu_ctx* ctx) {
     ctx->scan.destroy();
     ctx->norm.destroy();
     ctx->mix.destroy();
+    ctx->level.destroy();
     ctx->reverb.destroy();
     if (ctx->d_reverb_twiddles) (void)hipFree(ctx->d_reverb_twiddles);
     if (ctx->h_reverb_twiddles) (void)hipHostFree(ctx->h_reverb_twiddles);   // (reverb.destroy() has waited for the copy)

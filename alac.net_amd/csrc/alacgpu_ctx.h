@@ -127,6 +127,7 @@ struct alacgpu_ctx {
     scratch scan;    // alacgpu_compact_packets_device, alacgpu_stage_packets_device: the partial sums of the scan's upper levels
     scratch norm;    // alacgpu_normalize_top_device: the maxima of the parts of every row, [rows, parts] floats
     scratch mix;     // alacgpu_mix_device: the sums of the squares of the signal and the noise over the parts of every row, [rows, parts, 2] floats
+    scratch level;   // alacgpu_level_device: the sum of squares, the peak and the hop sums of every plane, [rows, channels, 2 + hops] doubles
     scratch reverb;  // alacgpu_reverb_device: the spectra of every block of the signal and partition of the impulse response of every row,
                      // [rows, units, ALAC_REVERB_N] float2, and behind them one alac_reverb_row per row (alac_reverb.h)
     void* d_reverb_twiddles = nullptr;   // alacgpu_reverb_device: exp(-2 pi i k / N), float2 [ALAC_REVERB_N], made at the first call

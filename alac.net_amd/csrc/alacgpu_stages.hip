@@ -1,5 +1,5 @@
 // alacgpu_stages.hip -- C ABI of include/alacgpu.h, the stages around the decode: the crop planner, the scan with the packet
-// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the reverberation, the noise mix, the biquad cascade, the normalisations, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
+// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the reverberation, the noise mix, the levelling, the biquad cascade, the normalisations, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
 // their own scratch; the decode path is alacgpu_api.hip.  No CPU fallback here either: every stage is its kernels.
 #include <algorithm>
 #include <cmath>
@@ -17,6 +17,7 @@
 #include "alac_augment.h"
 #include "alac_mix.h"
 #include "alac_biquad.h"
+#include "alac_level.h"
 #include "alac_reverb.h"
 #include "alac_encode.h"
 #include "alacgpu_ctx.h"
@@ -917,6 +918,64 @@ int alacgpu_biquad_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint
                                  (hipStream_t)hip_stream));
     HIP_TRY(ctx, hipGetLastError());
     return ALACGPU_OK;
+}
+
+int alacgpu_level_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t channels, uint64_t stride,
+                         uint64_t frames, const void* d_valid, uint32_t mode, uint32_t hop, const void* d_kweight, double target,
+                         double max_peak, int clamp, void* d_gain_out, void* d_energy_out, void* d_peak_out, void* hip_stream) {
+    const bool lufs = mode == ALAC_LEVEL_LUFS;
+    if (!ctx || !args_ok({{d_src, 4}, {d_out, 4, false}, {d_valid, 8, false}, {d_kweight, 8, lufs}, {d_gain_out, 8, false},
+                          {d_energy_out, 8, false}, {d_peak_out, 8, false}}))
+        return ALACGPU_ERR_BAD_ARG;
+    if (!d_out && !d_gain_out && !d_energy_out && !d_peak_out) return ALACGPU_ERR_BAD_ARG;      // (nothing asked for)
+    if (mode > ALAC_LEVEL_LUFS || channels == 0 || (lufs && (channels > ALAC_LEVEL_MAX_CHANNELS || hop < ALAC_LEVEL_MIN_HOP)) ||
+        frames == 0 || frames > stride || !(target > 0.0) || !std::isfinite(target) || !std::isfinite(max_peak))
+        return ALACGPU_ERR_BAD_ARG;
+    uint64_t extent;
+    if (!planes_extent((uint64_t)rows * channels, stride, frames, extent)) return ALACGPU_ERR_BAD_ARG;
+    if (d_out && d_src != d_out && !apart(d_src, extent, d_out, extent)) return ALACGPU_ERR_BAD_ARG;
+    const uint64_t per_row = sizeof(double) * (uint64_t)rows;
+    for (const void* o : {(const void*)d_gain_out, (const void*)d_energy_out, (const void*)d_peak_out})
+        if (o && (!apart(o, per_row, d_src, extent) || (d_out && !apart(o, per_row, d_out, extent)))) return ALACGPU_ERR_BAD_ARG;
+    if (lufs && d_out && !apart(d_kweight, sizeof(double) * 10u, d_out, extent)) return ALACGPU_ERR_BAD_ARG;
+    const uint32_t parts = d_out ? alac_level_parts(frames) : 1u;
+    const uint64_t planes = (uint64_t)rows * channels, grid = (uint64_t)rows * parts;
+    if (planes > 0x7FFFFFFFull || grid > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const uint64_t hops = alac_level_hops(mode, frames, hop);
+    const size_t need = sizeof(double) * (size_t)(planes * (ALAC_LEVEL_HEAD + hops));      // (below the signal's own extent and 2^36)
+    scratch_hold hold{ctx->level, stream};
+    int rc = ctx->level.acquire(ctx, stream, need, align_up(need + need / 4, 4096));
+    if (rc) return rc;
+    alac_level_params p;
+    p.src = (const float*)d_src;
+    p.out = (float*)d_out;
+    p.valid = (const int64_t*)d_valid;
+    p.kweight = (const double*)d_kweight;
+    p.scratch = (double*)ctx->level.buf[0];
+    p.gain_out = (double*)d_gain_out;
+    p.energy_out = (double*)d_energy_out;
+    p.peak_out = (double*)d_peak_out;
+    p.target = target;
+    p.max_peak = max_peak;
+    p.stride = stride;
+    p.frames = frames;
+    p.hops = hops;
+    p.part_frames = alac_level_part_frames(frames);
+    p.channels = channels;
+    p.mode = mode;
+    p.hop = lufs ? hop : 1u;
+    p.parts = parts;
+    p.clamp = clamp ? 1u : 0u;
+    p.vec = ((uintptr_t)d_src & 15u) == 0u && (stride & 3u) == 0u ? 1u : 0u;
+    p.vec_out = p.vec && ((uintptr_t)d_out & 15u) == 0u ? 1u : 0u;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_level_measure_kernel, dim3((uint32_t)planes), dim3(ALAC_LEVEL_THREADS), kargs, 0, stream));
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_level_apply_kernel, dim3((uint32_t)grid), dim3(ALAC_LEVEL_THREADS), kargs, 0, stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ctx->level.release(ctx, stream);
 }
 
 size_t alacgpu_encode_max_packet_bytes(uint32_t frames, int sample_size, int channels) {

@@ -181,6 +181,16 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_biquad_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, uint rows,
             uint channels, ulong stride, ulong frames, IntPtr dValid, IntPtr dCoeffs, uint sections, IntPtr dGain, int clamp,
             IntPtr hipStream);
+        /// <summary>Planar float crops in device memory (dSrc, dOut [rows, channels, stride]; the first frames of a plane are
+        /// data) brought to a level over the first dValid[row] frames (long[rows] or IntPtr.Zero for all): mode 0 the peak,
+        /// 1 the mean square, 2 the BS.1770-4 integrated loudness with hops of hop frames and the two K-weighting sections
+        /// dKweight double[2, 5] (IntPtr.Zero for the other modes).  target is linear (the peak, the mean square,
+        /// 10^((LUFS + 0.691) / 10)), maxPeak limits the gain (0: not), clamp limits the result to -1 .. 1.  dGainOut,
+        /// dEnergyOut, dPeakOut: double[rows] or IntPtr.Zero.  dOut is dSrc itself, apart from it, or IntPtr.Zero to measure
+        /// only.  A row with nothing to measure is left as it is.  Two launches, asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_level_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, uint rows,
+            uint channels, ulong stride, ulong frames, IntPtr dValid, uint mode, uint hop, IntPtr dKweight, double target,
+            double maxPeak, int clamp, IntPtr dGainOut, IntPtr dEnergyOut, IntPtr dPeakOut, IntPtr hipStream);
         /// <summary>Room reverberation into planar float crops in device memory (dSrc, dOut [rows, channels, stride], dRir
         /// [rows, rirChannels, rirStride], rirChannels 1 or channels; the first frames / rirFrames of a plane are data): every
         /// row convolved with its impulse response over the first dValid[row] frames of the signal and dRirValid[row] of the

@@ -783,6 +783,53 @@ int alacgpu_biquad_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint
                           int clamp, void* hip_stream);
 
 /*
+ * alacgpu_level_device: every crop brought to a known level, behind the noise mix and in front of the biquad cascade (no
+ * counterpart in the reference): peak, RMS or ITU-R BS.1770-4 integrated loudness; two launches, no atomics, nothing read back,
+ * the same inputs give the same bits.  The layout is planar float32: d_src and d_out [rows, channels, stride], the first
+ * `frames` elements of a plane are data, what lies behind them is neither read nor written.  d_out is d_src itself (in
+ * place), an array of that layout apart from it, or NULL: the row is then only measured.  The kernels evaluate no logarithm
+ * and no power: `target` is linear and the caller's, as alacgpu_mix_device's ratio is.  For row r, with
+ * v = min(max(d_valid[r], 0), frames) (int64 [rows]; NULL: frames), everything in float64 on x widened exactly:
+ *   P = max |x[c, i]| over all channels and i < v                  (mode 0, 1, 2: peak, rms, lufs)
+ *   peak: g = target / P                                           target: the peak to reach
+ *   rms:  E = (sum over c, i < v of x^2) / (channels v),  g = sqrt(target / E)          target: the mean square, 10^(db / 10)
+ *   lufs: every channel K-weighted by the two sections d_kweight (float64 [2, 5] = (b0, b1, b2, a1, a2): BS.1770's shelf and
+ *     high-pass at the rate of the crops, designed by the caller), each from zero history, by alacgpu_biquad_device's blocked
+ *     recurrence with nothing rounded to float32; s_c[k] the sum of its squares over hop k of `hop` frames (a tenth of a
+ *     second), k < nh = v / hop; for block j < nh - 3 (four hops, starting every hop)
+ *       z_c[j] = ((s_c[j] + s_c[j+1]) + (s_c[j+2] + s_c[j+3])) / (4 hop),   e[j] = sum over c of G_c z_c[j],   G = (1, 1, 1, 1.41, 1.41)
+ *     E = the mean of the e[j] that are above Gabs = 10^((-70 + 0.691) / 10) and above 0.1 times the mean of those above Gabs,
+ *     g = sqrt(target / E)                                         target: 10^((LUFS + 0.691) / 10)
+ *   max_peak > 0: g = min(g, max_peak / P)
+ *   y[c, i] = fl32(g * x[c, i]) for i < v, rounded once; with clamp then min(max(y, -1), 1), a NaN kept
+ * Frames at or behind v are untouched (out of place too: d_out keeps what it held).  A row with nothing to measure -- v == 0,
+ * P == 0, E == 0, for lufs fewer than 4 hops or no block above Gabs -- keeps g = 1 exactly and is neither read by the second
+ * launch nor written, and so is a row whose g comes out exactly 1 without clamp.  d_gain_out, d_energy_out and d_peak_out
+ * (float64 [rows], each may be NULL) receive g, E (the mean square in peak mode; 0 where there was nothing to gate) and P.
+ * The first launch, one workgroup per (row, channel), walks the plane in tiles of 4096 frames, 16 consecutive frames a lane,
+ * and writes the sum of squares, the peak and the hop sums into the ctx's scratch, float64 [rows, channels, 2 + frames / hop];
+ * the second, a grid of rows times parts of 4096 frames (the smallest multiple that keeps a row within 256 parts), combines
+ * its row's scratch in every workgroup and writes its part of y.  The order of every sum is fixed and does not depend on
+ * the width of the loads (csrc/alac_level.h states it, alac.net_amd/level.py follows it operation by operation): a lane's 16
+ * squares in ascending order; for the sum of squares the lanes of a wave and the waves as trees of halves and the tiles in
+ * ascending order; for a hop the partials of its chunks in ascending order, a chunk that straddles a hop boundary giving its
+ * first frames to one hop and its last to the next; blocks and channels in ascending order.  One correctly rounded division
+ * and root, no multiply fused into an add.  Anything else follows IEEE: a NaN or an infinity in x below v reaches its own row
+ * only (a NaN peak or energy makes g a NaN; a block whose energy is a NaN is above no gate); one at or behind v is never read.
+ * Loads and stores are 16 bytes wide where the bases and the stride are multiples of 16 bytes, single frames otherwise, with
+ * the same result.  Calls of one ctx share the scratch one after the other, whatever their streams (as alacgpu_mix_device's
+ * do).  Device pointers only, asynchronous on hip_stream.  rows == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx or d_src, a NULL d_kweight for lufs, a NULL d_out with all three
+ * outputs NULL, a misaligned array (4; 8 for d_valid, d_kweight and the three outputs), a mode above 2, channels 0 or above 5
+ * for lufs, hop below 16 for lufs, frames 0 or above stride, a target that is not positive and finite, a max_peak that is not
+ * finite, d_src and d_out that overlap without being equal, an output overlapping d_src or d_out, d_kweight overlapping d_out,
+ * an extent of 2^60 bytes or more, 2^31 workgroups or more.
+ */
+int alacgpu_level_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t channels, uint64_t stride,
+                         uint64_t frames, const void* d_valid, uint32_t mode, uint32_t hop, const void* d_kweight, double target,
+                         double max_peak, int clamp, void* d_gain_out, void* d_energy_out, void* d_peak_out, void* hip_stream);
+
+/*
  * alacgpu_reverb_device: room reverberation into the crops, in front of the noise mix (no counterpart in the reference): every
  * crop convolved with its own impulse response by a uniformly partitioned overlap-save convolution; two launches, no atomics,
  * the same inputs give the same bits.  The layout is planar float32: d_src and d_out [rows, channels, stride], d_rir [rows,

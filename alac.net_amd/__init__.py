@@ -99,6 +99,9 @@ SYMBOLS = {
                                        C.c_double, C.c_double, C.c_int, _VP, _VP, _VP, _VP]),
     "alacgpu_reverb_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
                                         C.c_uint64, _VP, _VP, _VP]),
+    "alacgpu_time_stretch_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _VP,
+                                              _VP, _VP, _VP, C.c_uint32, _VP]),
+    "alacgpu_copy_rows_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _VP]),
     "alacgpu_specaugment_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, _VP, _VP,
                                              C.c_uint32, _VP, C.c_uint32, C.c_float, _VP]),
     "alacgpu_encode_max_packet_bytes": (C.c_size_t, [C.c_uint32, C.c_int, C.c_int]),
@@ -557,6 +560,27 @@ class AlacGpuContext(_Closing):
         reverb.py states the arithmetic.  Two launches, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
         rc = lib().alacgpu_reverb_device(self._ctx, _dp(d_src), _dp(d_out), _dp(d_rir), rows, channels, rir_channels, stride,
                                          rir_stride, frames, rir_frames, _dp(d_valid), _dp(d_rir_valid), _VP(stream))
+        _check(rc, self._ctx)
+
+    def time_stretch_device(self, d_src, d_out, rows, channels, src_stride, out_stride, frames, out_frames, d_p, d_q, d_valid,
+                            d_valid_out, n_fft, stream=0):
+        """alacgpu_time_stretch_device: every row of d_src (float32 device tensor, planar [rows, channels, src_stride], the
+        first `frames` of a plane are data) stretched by d_p[row] / d_q[row] (int32 device tensors [rows]) over its first
+        v = min(max(d_valid[row], 0), frames) frames with the pitch kept, into d_out ([rows, channels, out_stride] apart from
+        it, of which the first out_frames are written: (2 v p + q) div (2 q) frames and zeros behind them); the new lengths
+        into d_valid_out (int64 device tensor [rows]).  A row with p == q or at most n_fft / 2 valid frames is neither read
+        nor written.  d_valid: an int64 device tensor [rows], or None for `frames`.  n_fft: 512, 1024 or 2048.  pitch.py states
+        the arithmetic.  Three launches, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_time_stretch_device(self._ctx, _dp(d_src), _dp(d_out), rows, channels, src_stride, out_stride, frames,
+                                               out_frames, _dp(d_p), _dp(d_q), _dp(d_valid), _dp(d_valid_out), n_fft, _VP(stream))
+        _check(rc, self._ctx)
+
+    def copy_rows_device(self, d_src, d_out, rows, channels, src_stride, out_stride, frames, d_valid, stream=0):
+        """alacgpu_copy_rows_device: the first min(max(d_valid[row], 0), frames) frames of every plane of d_src (float32
+        device tensor [rows, channels, src_stride]) into d_out ([rows, channels, out_stride], apart from it); nothing else is
+        written.  d_valid: an int64 device tensor [rows].  One launch, asynchronous on `stream` (raw hipStream_t)."""
+        rc = lib().alacgpu_copy_rows_device(self._ctx, _dp(d_src), _dp(d_out), rows, channels, src_stride, out_stride, frames,
+                                            _dp(d_valid), _VP(stream))
         _check(rc, self._ctx)
 
     def specaugment_device(self, d_src, d_out, rows, channels, n_mels, line_stride, line_len, d_valid, d_warp, d_freq, d_time, fill,
@@ -1175,6 +1199,10 @@ from .biquad import (Effects, RandomBiquad, allpass, bandpass, bandreject, biqua
                      highshelf, lowpass, lowshelf, peaking)
 # ---- peak, RMS and loudness levelling of crops and tensors (alacgpu_level_device) --------------------------------------------------
 from .level import Level, kweight, level, level_host, level_host_twin, loudness, loudness_host  # noqa: E402
+
+# ---- pitch shift and time stretch of crops and tensors (alacgpu_time_stretch_device) ------------------------------------------------
+from .pitch import (PitchShift, pitch_shift, pitch_shift_host, pitch_shift_host_f32, semitone_ratio, time_stretch,  # noqa: E402
+                    time_stretch_host, time_stretch_host_f32)
 # ---- room reverberation into crops and tensors (alacgpu_reverb_device) ------------------------------------------------------------
 from .reverb import Reverb, reverb, reverb_host, reverb_host_f32  # noqa: E402
 # ---- SpecAugment on the features: time warp, frequency and time masks (alacgpu_specaugment_device) -------------------------------

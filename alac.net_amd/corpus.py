@@ -28,6 +28,10 @@ level.py, biquad.py, features.py, deltas.py, vad.py, normalize.py, sliding.py an
 whose rates differ, with a ratio per (file rate, factor) in place of one per file rate; the crops at factor 1 go through the
 table kernels, the others through alacgpu_resample_ratio_rows_device, which evaluates its weights per tap.
 
+`crops(..., pitch=)` changes every crop's pitch by a drawn ratio and keeps its duration, behind the waveform and speed= and in
+front of reverb= (pitch.py): alacgpu_time_stretch_device into a scratch, alacgpu_resample_ratio_rows_device into a second one and
+alacgpu_copy_rows_device back into the crops, the ratios gathered from the draws on the device.
+
 `Corpus(sources, mixed_rates=True)` takes files of different sample rates.  Crops of such a corpus exist at a target rate only;
 a step is the same method and the same launches, with a source window per crop in the plan
 (alacgpu_plan_crops_frames_device) and a filter table per row in the resampler (alacgpu_resample_rows_device).
@@ -52,6 +56,7 @@ from .mix import AddNoise, _mix, snr_ratio
 from .normalize import MeanVar, TopDb, _normalize
 from .sliding import LDS_MAX as _SLIDING_LDS_MAX, RING_WINDOW_MAX as _SLIDING_RING_WINDOW_MAX, SlidingMeanVar
 from .vad import EnergyVad, _select_frames, _vad_energy
+from .pitch import PitchShift, _pitch_shift, _ratio_kinds
 from .reverb import Reverb, _reverb
 from .speed import MAX_WIDTH as _SPEED_MAX_WIDTH, SpeedPerturb, ratio as _speed_ratio
 
@@ -68,6 +73,8 @@ _MIX = dict(arg="mix", spec=AddNoise, corpus="noise", theirs="the noise corpus",
             channels="a noise corpus of {n} channels into crops of {Co}: it can become one channel from 1 or 2 only")
 _SPEED = dict(arg="speed", spec=SpeedPerturb, what="speed must be a speed.SpeedPerturb or (SpeedPerturb, what its draw() returned)",
               f32="float32 crops are speed-perturbed")
+_PITCH = dict(arg="pitch", spec=PitchShift, what="pitch must be a pitch.PitchShift or (PitchShift, what its draw() returned)",
+              f32="float32 crops are pitch-shifted")
 _REVERB = dict(arg="reverb", spec=Reverb, corpus="rirs", theirs="the corpus of impulse responses", they="the responses",
                what="reverb must be a reverb.Reverb or (Reverb, what its draw() returned)",
                draws=2, dtypes=lambda torch, files, keep: not files.is_floating_point and keep == torch.bool,
@@ -394,6 +401,8 @@ class Corpus(_Closing):
         self._vad_scratch = None                          # crops(vad=): the decisions between the VAD and the selection
         self._mix_scratch = None                          # crops(mix=): the noise crops, whichever corpus makes them
         self._reverb_scratch = None                       # crops(reverb=): the impulse responses of the crops
+        self._pitch_scratch = None                        # crops(pitch=): the stretched rows
+        self._pitch_back_scratch = None                   # ... and those rows resampled, in front of their copy into the crops
         self._rates, self._windows = {}, {}               # `_rate` per (target rate, factors); `_window` per (rate or None, L, factors)
         self._gpu = gpu if gpu is not None else AlacGpuContext(tb["cfgs"], device)
 
@@ -531,7 +540,7 @@ class Corpus(_Closing):
         if getattr(self, "_gpu", None) is not None:
             self._gpu.close()
             self._gpu = None
-            self._blob = self._plan = self._stage = self._stage_plan = self._rs_scratch = self._ft_scratch = self._delta_scratch = self._vad_scratch = self._mix_scratch = self._reverb_scratch = None
+            self._blob = self._plan = self._stage = self._stage_plan = self._rs_scratch = self._ft_scratch = self._delta_scratch = self._vad_scratch = self._mix_scratch = self._reverb_scratch = self._pitch_scratch = self._pitch_back_scratch = None
         self._free_pinned()
 
     @property
@@ -649,7 +658,8 @@ class Corpus(_Closing):
         return torch.from_numpy(f.astype(np.int32)).to(self._dev), torch.from_numpy(o).to(self._dev), True
 
     def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True, features=None, normalize=None, mix=None,
-              reverb=None, speed=None, effects=None, level=None, deltas=None, vad=None, augment=None, sample_rate=None, mono=False):
+              reverb=None, speed=None, pitch=None, effects=None, level=None, deltas=None, vad=None, augment=None, sample_rate=None,
+              mono=False):
         """Decode crop b = frames frame_offsets[b] .. + num_frames of file files[b] for every b in ONE launch pair: returns
         (pcm [B, C, num_frames] on the device, zero behind lengths[b]; lengths [B], a DEVICE int64 tensor: min(num_frames,
         T_f - offset)).  float32 (default) or int32, as `load`.  files / frame_offsets: sequences, numpy arrays or torch
@@ -673,8 +683,18 @@ class Corpus(_Closing):
         the call without speed=.  Every stage behind it sees the perturbed waveform.  ValueError: int32 crops, a corpus of
         more than 2 channels, draws that are not an integer tensor [B] on the corpus's device.
 
+        pitch: pitch shift of the waveform with the duration kept, behind speed= and in front of every other stage -- the
+        source's pitch changes, not the room's: a pitch.PitchShift, whose draws are then made here from the device's default
+        generator (in front of an AddNoise's), or the pair (PitchShift, draws) with the int64 tensor [B] that its `draw(B)`
+        returned.  Bit for bit pitch.pitch_shift(the crops without it, the drawn ratios, rate of the crops, lengths,
+        pitch.n_fft): a crop that draws the ratio 1, one of at most n_fft / 2 valid frames and one outside the corpus stay as
+        they are; lengths stay.  The stretched rows live in two scratches the corpus keeps.  ValueError: int32 crops, crops
+        without a rate, more than 2 channels, something that is no PitchShift, draws that are not an integer tensor [B] on the
+        corpus's device, num_frames of at most n_fft / 2.  Tempo perturbation is not a stage here: it changes the source window,
+        as speed= does; pitch.time_stretch on the result covers it.
+
         The stages behind the waveform go by keyword, as sample_rate and mono do, and run in this order whichever are
-        given -- reverb, mix, level, effects, features, deltas, the VAD's decision, normalize, the selection of the voiced frames, augment --,
+        given -- pitch, reverb, mix, level, effects, features, deltas, the VAD's decision, normalize, the selection of the voiced frames, augment --,
         in place but for the features and the deltas, by the corpus's own context on the same stream; lengths (but for vad=,
         which shortens them), `check` and last_status() are those of the call without them (with check=True a second corpus's own check runs too, and first).  ValueError before any device
         work for what a stage cannot take.
@@ -748,6 +768,8 @@ class Corpus(_Closing):
         Co = 1 if mono else self.channels
         if speed is not None:
             speed = self._speed_given(speed, dtype, rate)
+        if pitch is not None:
+            pitch = self._pitch_given(pitch, dtype, rate, Co, num_frames)
         if mix is not None:
             mix = self._second_corpus(mix, _MIX, dtype, rate, Co)
         if reverb is not None:
@@ -797,7 +819,8 @@ class Corpus(_Closing):
             augment = _how(augment, "augment")
             if features is None:
                 raise ValueError("a SpecAugment masks log-mel features: it needs features=")
-        if features is not None or mix is not None or reverb is not None or speed is not None or effects is not None or level is not None:
+        if (features is not None or mix is not None or reverb is not None or speed is not None or effects is not None or level is not None
+                or pitch is not None):
             L = _frame_count("num_frames", num_frames)
             if features is not None and L < features.min_frames:
                 raise ValueError(features.short(L))
@@ -805,6 +828,8 @@ class Corpus(_Closing):
             B = int(files.shape[0]) if isinstance(files, torch.Tensor) and files.dim() == 1 else len(np.asarray(files))
         if speed is not None and speed[1] is not None and speed[1].shape[0] != B:
             raise ValueError(f"{speed[1].shape[0]} draws of speed= for {B} crops")
+        if pitch is not None and pitch[1] is not None and pitch[1].shape[0] != B:
+            raise ValueError(f"{pitch[1].shape[0]} draws of pitch= for {B} crops")
         if effects is not None and effects[1] is not None and effects[1][0].shape[0] != B:
             raise ValueError(f"{effects[1][0].shape[0]} draws of effects= for {B} crops")
         if features is not None:
@@ -818,7 +843,9 @@ class Corpus(_Closing):
             if deltas is not None:      # the features into a scratch, their deltas into what the call returns
                 stacked, feats = feats, self._scratch("_delta_scratch", (B, Co, features.n_mels, features.frames(L)))
             out = self._scratch("_ft_scratch", (B, Co, L))
-        # 2. the companion crops, by the second corpora's own `crops`: the noise, then the responses
+        # 2. the pitch's draws; the companion crops, by the second corpora's own `crops`: the noise, then the responses
+        if pitch is not None and pitch[1] is None:
+            pitch = (pitch[0], pitch[0].draw(B, device=self._dev))
         if mix is not None:
             nf, no, snr = mix[0].draw(B, L, sample_rate=rate) if mix[1] is None else mix[1]
             d_noise, noise_lengths = self._companion_crops(mix[0].noise, "_mix_scratch", nf, no, L, B=B, Co=Co, rate=rate,
@@ -835,6 +862,8 @@ class Corpus(_Closing):
                                       mono=mono, speed=speed)
         # 4. the stages, in place and in this order on the same stream, by the corpus's own context
         ctx = lambda: self._gpu
+        if pitch is not None and B:
+            self._pitch(ctx, res, pitch, rate, lengths)
         if reverb is not None:
             _reverb(ctx, res, d_rir, lengths, torch.where(keep, rir_lengths, 0), res)
         if mix is not None:
@@ -931,6 +960,43 @@ class Corpus(_Closing):
         if other.channels != Co and other.channels not in (1, 2):
             raise ValueError(stage["channels"].format(n=other.channels, Co=Co))
         return spec, draws
+
+    def _pitch_given(self, given, dtype, rate, Co, num_frames):
+        """crops(pitch=) as the pair (PitchShift, draws or None), checked: ValueError for anything else, for int32 crops, for
+        crops of more than 2 channels or without a rate and for crops too short to reflect.  Nothing is done on the device;
+        the draws' length is `crops`'s to check, where B is known."""
+        import torch
+
+        spec, draws = self._pair(given, _PITCH)
+        if not _is_f32(torch, dtype):
+            raise ValueError(_PITCH["f32"])
+        if Co not in (1, 2):
+            raise ValueError(f"{Co} channels: the resampler behind the vocoder takes 1 or 2")
+        if rate is None:
+            raise ValueError(_NEEDS_RATE)
+        L = _frame_count("num_frames", num_frames)
+        if L <= spec.n_fft // 2:
+            raise ValueError(f"crops of {L} frames: a PitchShift of n_fft {spec.n_fft} reflects {spec.n_fft // 2} and needs more")
+        if draws is not None and (not isinstance(draws, torch.Tensor) or draws.dim() != 1 or draws.dtype.is_floating_point
+                                  or draws.dtype == torch.bool or draws.device != self._dev):
+            raise ValueError(f"the draws of pitch= must be the integer tensor [B] of PitchShift.draw on {self._dev}")
+        return spec, draws
+
+    def _pitch(self, ctx, res, pitch, rate, lengths):
+        """crops(pitch=(spec, draws)) on the crops `res`, in place: the ratios of the draws, gathered on the device"""
+        import torch
+
+        spec, draws = pitch
+        key = (spec.ratios, rate)
+        if getattr(self, "_pitch_tables", None) is None or self._pitch_tables[0] != key:
+            pq = np.array([[f.numerator, f.denominator] for f in spec.ratios], dtype=np.int32)
+            self._pitch_tables = (key, _ratio_kinds(spec.ratios, int(rate)), torch.from_numpy(np.ascontiguousarray(pq[:, 0])).to(self._dev),
+                                  torch.from_numpy(np.ascontiguousarray(pq[:, 1])).to(self._dev))
+        _, kinds, d_ps, d_qs = self._pitch_tables
+        k = draws.long().clamp(0, len(spec.ratios) - 1)
+        names = dict(stretched="_pitch_scratch", resampled="_pitch_back_scratch")
+        _pitch_shift(ctx, res, d_ps[k], d_qs[k], kinds, k.to(torch.int32), lengths, spec.n_fft, res,
+                     lambda name, shape: self._scratch(names[name], shape))
 
     @staticmethod
     def _level_given(spec, dtype, rate, Co):
@@ -1213,8 +1279,8 @@ class Corpus(_Closing):
         return out, lengths
 
     def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True, features=None, normalize=None,
-                     mix=None, reverb=None, speed=None, effects=None, level=None, deltas=None, vad=None, augment=None, sample_rate=None,
-                     mono=False):
+                     mix=None, reverb=None, speed=None, pitch=None, effects=None, level=None, deltas=None, vad=None, augment=None,
+                     sample_rate=None, mono=False):
         """`batch` crops of num_frames frames drawn on the device: files uniform over the corpus, the first frame uniform in
         0 .. max(T_f - num_frames, 0).  generator: a torch.Generator (of the corpus's device, or of the CPU: then the draws are
         made there and uploaded).  Returns (pcm, lengths, files, frame_offsets), the draws as device int64 tensors.
@@ -1228,13 +1294,18 @@ class Corpus(_Closing):
         lengths in front of the selection, which are known without the device's decisions.  speed as for `crops`;
         a SpeedPerturb is drawn from `generator` behind the call's own two draws and in front of an AddNoise's
         (SpeedPerturb.draw states its two), and the first frame is then uniform in 0 .. max(Ty[f, k] - num_frames, 0), from the
-        same u, with the frames of the file at its factor."""
+        same u, with the frames of the file at its factor.  pitch as for `crops`; a PitchShift is drawn from `generator` behind a
+        SpeedPerturb's and in front of an AddNoise's (PitchShift.draw states its two)."""
         import torch
 
         B, L = _frame_count("batch", batch), _frame_count("num_frames", num_frames)
         rate = self.sample_rate if sample_rate is None else sample_rate
         if speed is not None:
             speed = self._speed_given(speed, dtype, rate)
+        if pitch is not None:
+            pitch = self._pitch_given(pitch, dtype, rate, 1 if mono else self.channels, num_frames)
+            if pitch[1] is not None and pitch[1].shape[0] != B:
+                raise ValueError(f"{pitch[1].shape[0]} draws of pitch= for {B} crops")
         if mix is not None:
             mix = self._second_corpus(mix, _MIX, dtype, rate, 1 if mono else self.channels)
         if reverb is not None:
@@ -1269,6 +1340,8 @@ class Corpus(_Closing):
             ends = rt["d_Ty"][self._at(files, draws, rt["nk"])]
         span = (ends - L).clamp(min=0)
         offs = torch.minimum(torch.floor(u * (span + 1).to(torch.float64)).to(torch.int64), span)
+        if pitch is not None and pitch[1] is None:
+            pitch = (pitch[0], pitch[0].draw(B, generator=generator, device=self._dev))
         if mix is not None and mix[1] is None:
             mix = (mix[0], mix[0].draw(B, L, sample_rate=rate, generator=generator))
         if reverb is not None and reverb[1] is None:
@@ -1281,7 +1354,7 @@ class Corpus(_Closing):
             augment = (augment[0], augment[0].draw(lines, feat_lengths, generator=generator))
         pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,
                                   features=features, normalize=normalize, mix=mix, reverb=reverb, augment=augment, speed=speed,
-                                  deltas=deltas, vad=vad, effects=effects, level=level)
+                                  deltas=deltas, vad=vad, effects=effects, level=level, pitch=pitch)
         return pcm, lengths, files, offs
 
     def last_staged_bytes(self):

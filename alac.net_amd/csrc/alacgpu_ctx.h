@@ -132,6 +132,11 @@ struct alacgpu_ctx {
                      // [rows, units, ALAC_REVERB_N] float2, and behind them one alac_reverb_row per row (alac_reverb.h)
     void* d_reverb_twiddles = nullptr;   // alacgpu_reverb_device: exp(-2 pi i k / N), float2 [ALAC_REVERB_N], made at the first call
     void* h_reverb_twiddles = nullptr;   // ... and the page-locked table it is copied from on that call's stream
+    scratch stretch; // alacgpu_time_stretch_device: the spectra of the STFT frames, [rows, channels, 1 + frames / hop, n_fft / 2 + 1] float2
+                     // (buf[0]), and of the output frames, [rows, channels, alac_stretch_cap(out_frames), n_fft / 2 + 1] float2 (buf[1])
+    void* d_stretch_tables[3] = {};      // alacgpu_time_stretch_device, for n_fft 512, 1024, 2048: exp(-2 pi i k / n_fft), float2 [n_fft], and
+                                         // behind it the periodic Hann window, float [n_fft]; made at the first call with that n_fft
+    void* h_stretch_tables[3] = {};      // ... and the page-locked tables they are copied from on that call's stream
     std::string last_error;
 };
 

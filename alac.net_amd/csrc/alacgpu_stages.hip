@@ -1,5 +1,5 @@
 // alacgpu_stages.hip -- C ABI of include/alacgpu.h, the stages around the decode: the crop planner, the scan with the packet
-// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the reverberation, the noise mix, the levelling, the biquad cascade, the normalisations, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
+// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the phase vocoder, the reverberation, the noise mix, the levelling, the biquad cascade, the normalisations, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
 // their own scratch; the decode path is alacgpu_api.hip.  No CPU fallback here either: every stage is its kernels.
 #include <algorithm>
 #include <cmath>
@@ -19,6 +19,7 @@
 #include "alac_biquad.h"
 #include "alac_level.h"
 #include "alac_reverb.h"
+#include "alac_stretch.h"
 #include "alac_encode.h"
 #include "alacgpu_ctx.h"
 
@@ -976,6 +977,117 @@ int alacgpu_level_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint3
     HIP_TRY(ctx, hipLaunchKernel((const void*)alac_level_apply_kernel, dim3((uint32_t)grid), dim3(ALAC_LEVEL_THREADS), kargs, 0, stream));
     HIP_TRY(ctx, hipGetLastError());
     return ctx->level.release(ctx, stream);
+}
+
+int alacgpu_time_stretch_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t channels, uint64_t src_stride,
+                                uint64_t out_stride, uint64_t frames, uint64_t out_frames, const void* d_p, const void* d_q,
+                                const void* d_valid, void* d_valid_out, uint32_t n_fft, void* hip_stream) {
+    if (!ctx || !args_ok({{d_src, 4}, {d_out, 4}, {d_p, 4}, {d_q, 4}, {d_valid, 8, false}, {d_valid_out, 8}})) return ALACGPU_ERR_BAD_ARG;
+    const int which = n_fft == 512u ? 0 : n_fft == 1024u ? 1 : n_fft == 2048u ? 2 : -1;
+    if (which < 0 || channels == 0 || frames == 0 || frames > src_stride || out_frames == 0 || out_frames > out_stride ||
+        frames >= (1ull << 40) || out_frames >= (1ull << 40))
+        return ALACGPU_ERR_BAD_ARG;
+    const uint64_t planes = (uint64_t)rows * channels;
+    uint64_t extent, out_extent;
+    if (!planes_extent(planes, src_stride, frames, extent) || !planes_extent(planes, out_stride, out_frames, out_extent))
+        return ALACGPU_ERR_BAD_ARG;
+    const uint64_t terms = sizeof(int32_t) * (uint64_t)rows, lens = sizeof(int64_t) * (uint64_t)rows;
+    if (!apart(d_src, extent, d_out, out_extent) || !apart(d_p, terms, d_out, out_extent) || !apart(d_q, terms, d_out, out_extent) ||
+        !apart(d_valid_out, lens, d_out, out_extent) || !apart(d_valid_out, lens, d_src, extent) || !apart(d_valid_out, lens, d_p, terms) ||
+        !apart(d_valid_out, lens, d_q, terms) || (d_valid && (!apart(d_valid, lens, d_out, out_extent) || !apart(d_valid, lens, d_valid_out, lens))))
+        return ALACGPU_ERR_BAD_ARG;
+    const uint64_t bins = n_fft / 2u + 1u, t_max = alac_stretch_frames(frames, n_fft), t_cap = alac_stretch_cap(out_frames, n_fft);
+    const uint64_t tiles = alac_stretch_tiles(out_frames, n_fft), many = std::max<uint64_t>(planes, 1u);
+    if (planes > 0x7FFFFFFFull || t_max > 0x7FFFFFFFull / many || tiles > 0x7FFFFFFFull / many || t_cap > 0x7FFFFFFFull ||
+        planes * bins > 0x7FFFFFFFull * (uint64_t)ALAC_STRETCH_SCAN_THREADS)
+        return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const size_t need_x = sizeof(float2) * (size_t)(planes * t_max * bins), need_y = sizeof(float2) * (size_t)(planes * t_cap * bins);
+    scratch_hold hold{ctx->stretch, stream};
+    int rc = ctx->stretch.acquire(ctx, stream, need_x, align_up(need_x + need_x / 4, 4096), need_y, align_up(need_y + need_y / 4, 4096));
+    if (rc) return rc;
+    const size_t table_bytes = (sizeof(float2) + sizeof(float)) * (size_t)n_fft;
+    if (!ctx->d_stretch_tables[which]) {
+        // once per ctx and n_fft: the twiddles and the window in double, rounded once, in page-locked memory of the ctx and copied
+        // on the call's own stream in front of its launches (as alacgpu_reverb_device's table is)
+        if (!ctx->h_stretch_tables[which]) HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_stretch_tables[which], table_bytes));
+        float2* const table = (float2*)ctx->h_stretch_tables[which];
+        float* const window = (float*)(table + n_fft);
+        for (uint32_t k = 0; k < n_fft; k++) {
+            const double a = 2.0 * 3.14159265358979323846 * (double)k / (double)n_fft;
+            table[k] = make_float2((float)std::cos(a), (float)-std::sin(a));
+            window[k] = (float)(0.5 - 0.5 * std::cos(a));
+        }
+        void* d_table = nullptr;
+        HIP_TRY(ctx, hipMalloc(&d_table, table_bytes));
+        const hipError_t e = hipMemcpyAsync(d_table, table, table_bytes, hipMemcpyHostToDevice, stream);
+        if (e != hipSuccess) {
+            (void)hipFree(d_table);
+            HIP_TRY(ctx, e);
+        }
+        ctx->d_stretch_tables[which] = d_table;   // (a later call on another stream waits for this call's event, so for the copy)
+    }
+    alac_stretch_params p;
+    p.src = (const float*)d_src;
+    p.out = (float*)d_out;
+    p.p = (const int32_t*)d_p;
+    p.q = (const int32_t*)d_q;
+    p.valid = (const int64_t*)d_valid;
+    p.valid_out = (int64_t*)d_valid_out;
+    p.table = (const float2*)ctx->d_stretch_tables[which];
+    p.window = (const float*)(p.table + n_fft);
+    p.X = (float2*)ctx->stretch.buf[0];
+    p.Y = (float2*)ctx->stretch.buf[1];
+    p.src_stride = src_stride;
+    p.out_stride = out_stride;
+    p.frames = frames;
+    p.out_frames = out_frames;
+    p.chains = planes * bins;
+    p.channels = channels;
+    p.t_max = (uint32_t)t_max;
+    p.t_cap = (uint32_t)t_cap;
+    p.out_tiles = (uint32_t)tiles;
+    const void *analyse, *scan, *synth;
+    alac_stretch_kernels(n_fft, analyse, scan, synth);
+    const uint32_t threads = alac_stretch_threads(n_fft);
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel(analyse, dim3((uint32_t)(planes * t_max)), dim3(threads), kargs, 0, stream));
+    HIP_TRY(ctx, hipLaunchKernel(scan, dim3((uint32_t)((p.chains + ALAC_STRETCH_SCAN_THREADS - 1u) / ALAC_STRETCH_SCAN_THREADS)),
+                                 dim3(ALAC_STRETCH_SCAN_THREADS), kargs, 0, stream));
+    HIP_TRY(ctx, hipLaunchKernel(synth, dim3((uint32_t)(planes * tiles)), dim3(threads), kargs, 0, stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ctx->stretch.release(ctx, stream);
+}
+
+int alacgpu_copy_rows_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t channels, uint64_t src_stride,
+                             uint64_t out_stride, uint64_t frames, const void* d_valid, void* hip_stream) {
+    if (!ctx || !args_ok({{d_src, 4}, {d_out, 4}, {d_valid, 8}})) return ALACGPU_ERR_BAD_ARG;
+    if (channels == 0 || frames == 0 || frames > src_stride || frames > out_stride) return ALACGPU_ERR_BAD_ARG;
+    const uint64_t planes = (uint64_t)rows * channels;
+    uint64_t extent, out_extent;
+    if (!planes_extent(planes, src_stride, frames, extent) || !planes_extent(planes, out_stride, frames, out_extent) ||
+        !apart(d_src, extent, d_out, out_extent) || !apart(d_valid, sizeof(int64_t) * (uint64_t)rows, d_out, out_extent))
+        return ALACGPU_ERR_BAD_ARG;
+    const uint64_t tiles = (frames + ALAC_STRETCH_COPY_TILE - 1u) / ALAC_STRETCH_COPY_TILE;
+    if (tiles > 0x7FFFFFFFull / std::max<uint64_t>(planes, 1u)) return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    alac_copy_rows_params p;
+    p.src = (const float*)d_src;
+    p.out = (float*)d_out;
+    p.valid = (const int64_t*)d_valid;
+    p.src_stride = src_stride;
+    p.out_stride = out_stride;
+    p.frames = frames;
+    p.channels = channels;
+    p.tiles = (uint32_t)tiles;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_copy_rows_kernel, dim3((uint32_t)(planes * tiles)), dim3(ALAC_STRETCH_COPY_THREADS), kargs, 0,
+                                 (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
 }
 
 size_t alacgpu_encode_max_packet_bytes(uint32_t frames, int sample_size, int channels) {

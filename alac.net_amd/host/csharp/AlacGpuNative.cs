@@ -200,6 +200,20 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_reverb_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, IntPtr dRir, uint rows,
             uint channels, uint rirChannels, ulong stride, ulong rirStride, ulong frames, ulong rirFrames, IntPtr dValid,
             IntPtr dRirValid, IntPtr hipStream);
+        /// <summary>Time stretch of planar float crops in device memory with the pitch kept, a phase vocoder (dSrc [rows,
+        /// channels, srcStride] of which the first frames are data, dOut [rows, channels, outStride] apart from it, of which
+        /// the first outFrames are written): row r is stretched by dP[r] / dQ[r] (int[rows]) over its first dValid[r] frames
+        /// (long[rows] or IntPtr.Zero for all) to (2 v p + q) / (2 q) frames, zeros behind them; the new lengths into
+        /// dValidOut (long[rows]).  A row with p == q or at most nFft / 2 valid frames is neither read nor written.  nFft: 512,
+        /// 1024 or 2048.  Followed by alacgpu_resample_ratio_rows_device at the same ratio it is a pitch shift.  Three
+        /// launches, asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_time_stretch_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, uint rows,
+            uint channels, ulong srcStride, ulong outStride, ulong frames, ulong outFrames, IntPtr dP, IntPtr dQ, IntPtr dValid,
+            IntPtr dValidOut, uint nFft, IntPtr hipStream);
+        /// <summary>The first dValid[row] frames (long[rows]) of every plane of dSrc [rows, channels, srcStride] copied to dOut
+        /// [rows, channels, outStride], apart from it; nothing else is written.  One launch, asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_copy_rows_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, uint rows,
+            uint channels, ulong srcStride, ulong outStride, ulong frames, IntPtr dValid, IntPtr hipStream);
         /// <summary>SpecAugment on float features in device memory (dSrc, dOut [rows, channels, nMels, lineStride], the first
         /// lineLen of a line are frames), one launch: per row a time warp (dWarp int[rows, 2]: (c, c'), or IntPtr.Zero for
         /// none), nFreq frequency masks and nTime time masks (dFreq int[rows, nFreq, 2], dTime int[rows, nTime, 2]: (first,

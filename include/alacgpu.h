@@ -867,6 +867,54 @@ int alacgpu_reverb_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, cons
                           const void* d_valid, const void* d_rir_valid, void* hip_stream);
 
 /*
+ * alacgpu_time_stretch_device: time stretch of the crops with the pitch kept, a phase vocoder (no counterpart in the reference;
+ * the specification is torchaudio's phase_vocoder with the STFT and iSTFT around it); three launches, no atomics, nothing read
+ * back, the same inputs give the same bits.  Followed by alacgpu_resample_ratio_rows_device at the same ratio it is a pitch
+ * shift.  The layout is planar float32: d_src [rows, channels, src_stride] of which the first `frames` of a plane are data,
+ * d_out [rows, channels, out_stride] of which the first out_frames are written; the two are apart.  n_fft = N is 512, 1024 or
+ * 2048, the hop H = N / 4, the window w[n] = 0.5 - 0.5 cos(2 pi n / N).  Row r with v = min(max(d_valid[r], 0), frames) (int64
+ * [rows]; NULL: frames) is stretched by p / q = d_p[r] / d_q[r] (int32 [rows], output length over input length):
+ *   T = 1 + v / H frames X_t = DFT(w[n] x[refl(t H - N / 2 + n)]), refl(i) = -i below 0, 2 (v - 1) - i from v on; two zero frames
+ *     behind them;
+ *   output frame j < T' = ceil(T p / q) reads i = (j q) / p and i + 1 with alpha = ((j q) % p) / p:
+ *     Y_j = (alpha |X_{i+1}| + (1 - alpha) |X_i|) P_j,   P_0 = ph(X_0),   P_{j+1} = ph(P_j (ph(X_{i+1}) conj(ph(X_i)))),
+ *     ph(z) = z / |z| and 1 where |z| is not above 0 -- the phase advance of torchaudio's vocoder modulo 2 pi, without an angle;
+ *   sample n of the output is sum over the frames j < T' that cover it of w[i] IDFT(Y_j)[i], i = n + N / 2 - j H, divided by the
+ *     sum of w[i]^2 over the same frames (at least 1.25), for n <= (T' - 1) H and n < Ls = (2 v p + q) / (2 q); zero from there
+ *     up to out_frames.  (torch.istft divides the last N / 2 samples by envelopes down to 1e-11 instead.)
+ * d_valid_out[r] (int64 [rows]) receives min(Ls, out_frames).  A row is left alone -- neither read nor written, and
+ * d_valid_out[r] = min(d_valid[r], frames) -- where p == q, where v <= N / 2 (no reflection) and where p or q is outside
+ * 1 .. 2^20.  The arithmetic is float32, every operation rounded once, none fused, division and root correctly rounded, in a
+ * fixed order that csrc/alac_stretch.h states and alac.net_amd/pitch.py follows operation by operation: an N-point complex
+ * transform in LDS (radix 4, for 512 and 2048 behind one radix-2 stage) whose twiddles and window are tables made in double
+ * precision and rounded once; one lane per bin walks the output frames in ascending order; a workgroup per four hops of output
+ * transforms the seven frames that cover them back and adds them in ascending order.  The spectra of the input and output
+ * frames live in the ctx's scratch (8 bytes a bin, N / 2 + 1 bins a frame); calls of one ctx share it one after the other,
+ * whatever their streams (as alacgpu_reverb_device's do); the first call of a ctx with an n_fft uploads its tables on
+ * hip_stream.  A NaN or an infinity in x below v reaches its own plane only; one at or behind v is never read.  Device pointers
+ * only, asynchronous on hip_stream.  rows == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx, d_src, d_out, d_p, d_q or d_valid_out, a misaligned array (4; 8
+ * for d_valid and d_valid_out), another n_fft, channels 0, frames 0 or above src_stride, out_frames 0 or above out_stride,
+ * either of 2^40 or more, arrays that overlap (but for d_src with d_p, d_q and d_valid), an extent of 2^60 bytes or more, 2^31
+ * workgroups or more in a launch.
+ */
+int alacgpu_time_stretch_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t channels,
+                                uint64_t src_stride, uint64_t out_stride, uint64_t frames, uint64_t out_frames, const void* d_p,
+                                const void* d_q, const void* d_valid, void* d_valid_out, uint32_t n_fft, void* hip_stream);
+
+/*
+ * alacgpu_copy_rows_device: the first v = min(max(d_valid[r], 0), frames) frames of every plane of row r copied from d_src
+ * [rows, channels, src_stride] to d_out [rows, channels, out_stride] (planar float32, apart), nothing else written: how a
+ * stage that works out of place -- the pitch shift: stretch, resample -- puts its rows back behind the lengths' guard.  d_valid:
+ * int64 [rows].  One launch, no scratch, asynchronous on hip_stream.  rows == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx, d_src, d_out or d_valid, a misaligned array (4; 8 for d_valid),
+ * channels 0, frames 0 or above either stride, d_src or d_valid overlapping d_out, an extent of 2^60 bytes or more, 2^31
+ * workgroups or more.
+ */
+int alacgpu_copy_rows_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t channels,
+                             uint64_t src_stride, uint64_t out_stride, uint64_t frames, const void* d_valid, void* hip_stream);
+
+/*
  * alacgpu_specaugment_device: SpecAugment on the features, behind the normalisations (no counterpart in the reference): a time
  * warp, frequency masks and time masks per crop in one launch, no atomics, no scratch.  The data is float32 [rows, channels,
  * n_mels, line_stride]: a line is one mel bin of one channel of a row, its first line_len <= line_stride elements are

@@ -76,6 +76,30 @@ squares of rounded weights, within gamma_8 of the true one, and the division add
 It assumes that nothing underflows and is first order in u.  It is loose by design -- the cap of 2 stands for every bin that
 is ever small --; tests/test_stretch_spec.py prints the share of it that the twin uses.
 
+The stages.  Specification, twin and bound are each three functions that `vocoder_host` and `vocoder_host_f32` compose:
+
+    analyse      x -> X [C, T_ + 2, K]       `analyse_host`      `analyse_host_f32`       `analyse_bound`      e_t, 2-norm of a frame
+    scan         X, p, q -> Y [C, T', K]     `scan_host`         `scan_host_f32`          `scan_bound`         dY per element
+    synthesise   Y, v, p, q -> y [C, Ls]     `synthesise_host`   `synthesise_host_f32`    `synthesise_bound`   dy per sample
+
+(`scan_host` is the phasor form, `scan_host(..., phasor=False)` the angles; the twins take and give (real, imaginary) pairs of
+float32 arrays; `hermitian_host_f32` is the copy that lays Y out as the spectra of N points in front of the inverse transform.)
+A stage's bound is how far its float32 evaluation may be from its float64 one on the same, exact input: the formulas above
+with the incoming error at zero --
+
+    analyse      e_t as above
+    scan         dmag = 8 u mag + u alpha |X_i|,  dP_0 = 4 u,  dP_{j+1} = dP_j + 24 u,  dY = dmag + (mag + dmag)(dP + 2 u)
+    synthesise   E_j = f ||Y_j||_2 / sqrt(N),  dy[n] as above
+
+-- and `vocoder_host(..., bound=True)` is the three fed into each other (`scan_bound(e=)`, `synthesise_bound(dY=)`).  The
+condition of the vocoder sits in that feeding, in e / |X|, not in any stage, so the stage bounds are tight where the
+end-to-end one cannot be: tests/test_stretch_stages.py holds every stage of the twin to them (profiles/stretch_stages.json).
+The term u alpha |X_i| is one the end-to-end derivation lacks: alpha is a rounded quotient, off by u alpha, and 1 - alpha
+inherits that absolutely, not relative to itself, so (1 - alpha) |X_i| is off by u alpha |X_i| -- which 8 u mag does not cover
+where alpha is near 1 and |X_{i+1}| small (the zero frames behind the last one, terms up to 2^20).  `scan_bound` has it;
+`vocoder_host(..., bound=True)` returns what it always has, without it: there (mag + dmag) dP is larger by orders of magnitude
+on every row that has been measured, but that is an observation, not part of the derivation.
+
 Pitch shift by the ratio rho = p / q: stretch by rho, then play rho times faster through speed.py's resampler, unchanged:
 the ratio a : b = p : q, new length ceil(q Ls / p); the first min(v, new length) frames are written and zeros behind them up
 to v; lengths stay and what lies behind them is not touched.  `pitch_shift_host` composes `time_stretch_host` with
@@ -269,25 +293,52 @@ def _fft_factor(n_fft):
     return s * eta / (1 - s * eta)
 
 
-def vocoder_host(xr, p, q, n_fft, phasor=False, bound=False):
-    """One row through the vocoder in float64, whatever p / q is (1 too): xr float32 or float64 [C, v], v > n_fft / 2, to
-    float64 [C, Ls].  phasor: the phasor form instead of torchaudio's angles.  bound=True: returns (y, dy), dy how far a
-    float32 evaluation in the kernel's order may be from y (the module docstring)."""
+def _windowed(xr, n_fft):
+    """[C, T_, N] float64: the reflected, windowed frames of xr [C, v]"""
     xr = np.asarray(xr, dtype=np.float64)
-    C, v = xr.shape
-    N, H, K = n_fft, n_fft // 4, n_fft // 2 + 1
-    if v <= N // 2:
-        raise ValueError(f"{v} frames cannot be reflected by {N // 2}")
-    w = window(N)
-    T = stft_frames(v, N)
-    frames = xr[:, _reflect(v, N, T)] * w                                       # [C, T, N]
-    X = np.zeros((C, T + 2, K), dtype=np.complex128)
+    v = xr.shape[1]
+    if v <= n_fft // 2:
+        raise ValueError(f"{v} frames cannot be reflected by {n_fft // 2}")
+    return xr[:, _reflect(v, n_fft, stft_frames(v, n_fft))] * window(n_fft)
+
+
+def analyse_host(xr, n_fft):
+    """The analysis stage in float64: xr float32 or float64 [C, v], v > n_fft / 2, to X complex128 [C, T_ + 2, K], the STFT
+    frames and the two zero frames behind them"""
+    frames = _windowed(xr, n_fft)                                               # [C, T, N]
+    C, T, _ = frames.shape
+    X = np.zeros((C, T + 2, n_fft // 2 + 1), dtype=np.complex128)
     X[:, :T] = np.fft.rfft(frames, axis=-1)
-    i, num = steps(T, p, q)
-    Tp = len(i)
+    return X
+
+
+def analyse_bound(xr, n_fft):
+    """e [C, T_ + 2]: how far, in the 2-norm over a frame's bins, a float32 `analyse_host_f32` of an exact xr may be from
+    `analyse_host` (e_t of the module docstring; 0 for the two zero frames)"""
+    frames = _windowed(xr, n_fft)
+    C, T, N = frames.shape
+    f = _fft_factor(N)
+    e = np.zeros((C, T + 2))
+    e[:, :T] = (f + (2 * _U + _U * _U) * (1 + f)) * math.sqrt(N) * np.sqrt((frames ** 2).sum(axis=-1))
+    return e
+
+
+def _scan_parts(X, p, q):
+    """(i, alpha [1, T', 1], a = X_i, b = X_{i + 1}, mag) of X [C, T_ + 2, K]"""
+    X = np.asarray(X, dtype=np.complex128)
+    i, num = steps(X.shape[1] - 2, p, q)
     alpha = (num.astype(np.float64) / float(p))[None, :, None]
     a, b = X[:, i], X[:, i + 1]
-    mag = alpha * np.abs(b) + (1.0 - alpha) * np.abs(a)
+    return i, alpha, a, b, alpha * np.abs(b) + (1.0 - alpha) * np.abs(a)
+
+
+def scan_host(X, p, q, phasor=True):
+    """The scan stage in float64: X complex [C, T_ + 2, K] to Y complex128 [C, T', K]; the phasor form, or (phasor=False)
+    torchaudio's angles"""
+    X = np.asarray(X, dtype=np.complex128)
+    C, _, K = X.shape
+    i, alpha, a, b, mag = _scan_parts(X, p, q)
+    Tp = len(i)
     if phasor:
         ph = lambda z: np.where(np.abs(z) > 0, z / np.where(np.abs(z) > 0, np.abs(z), 1.0), 1.0)
         d = ph(b) * np.conj(ph(a))
@@ -295,14 +346,47 @@ def vocoder_host(xr, p, q, n_fft, phasor=False, bound=False):
         P[:, 0] = ph(X[:, 0])
         for j in range(Tp - 1):
             P[:, j + 1] = ph(P[:, j] * d[:, j])
-        Y = mag * P
-    else:
-        advance = np.linspace(0.0, math.pi * H, K)[None, None, :]
-        phase = np.angle(b) - np.angle(a) - advance
-        phase = phase - 2.0 * math.pi * np.round(phase / (2.0 * math.pi))
-        phase = phase + advance
-        phase = np.concatenate([np.angle(X[:, :1]), phase[:, :-1]], axis=1)
-        Y = mag * np.exp(1j * np.cumsum(phase, axis=1))
+        return mag * P
+    advance = np.linspace(0.0, math.pi * ((K - 1) // 2), K)[None, None, :]
+    phase = np.angle(b) - np.angle(a) - advance
+    phase = phase - 2.0 * math.pi * np.round(phase / (2.0 * math.pi))
+    phase = phase + advance
+    phase = np.concatenate([np.angle(X[:, :1]), phase[:, :-1]], axis=1)
+    return mag * np.exp(1j * np.cumsum(phase, axis=1))
+
+
+def scan_bound(X, p, q, e=None, alpha_term=True):
+    """dY [C, T', K]: how far a float32 `scan_host_f32` may be from `scan_host`, per element.  e: None for an exact X (the
+    stage's own bound: dmag = 8 u mag + u alpha |X_i|, dP_0 = 4 u, dP_{j+1} = dP_j + 24 u), or [C, T_ + 2], how far every bin
+    of a frame of the X it got may be from this one.  alpha_term: the u alpha |X_i| of the module docstring (`vocoder_host`
+    leaves it out, as it always has)."""
+    X = np.asarray(X, dtype=np.complex128)
+    C, _, K = X.shape
+    i, alpha, a, b, mag = _scan_parts(X, p, q)
+    Tp = len(i)
+    if e is None:
+        e = np.zeros((C, X.shape[1]))
+    ea, eb = e[:, i][:, :, None], e[:, i + 1][:, :, None]
+    dmag = (1 + 8 * _U) * (alpha * eb + (1 - alpha) * ea) + 8 * _U * mag
+    if alpha_term:
+        dmag = dmag + _U * alpha * np.abs(a)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        turn = lambda err, z: np.where(err > 0, np.minimum(2.0 * err / np.abs(z), 2.0), 0.0)
+        step = turn(ea, a) + turn(eb, b) + 24 * _U
+        dP = np.empty((C, Tp, K))
+        dP[:, 0] = np.minimum(turn(e[:, 0][:, None], X[:, 0]) + 4 * _U, 2.0)
+        for j in range(Tp - 1):
+            dP[:, j + 1] = np.minimum(dP[:, j] + step[:, j], 2.0)
+    return dmag + (mag + dmag) * (dP + 2 * _U)
+
+
+def _overlap_add(Y, v, p, q, dY=None):
+    """What `synthesise_host` and `synthesise_bound` share: (y [C, Ls], dy [C, Ls] or None) of Y complex [C, T', K]"""
+    Y = np.asarray(Y, dtype=np.complex128)
+    C, Tp, K = Y.shape
+    N = 2 * (K - 1)
+    H = N // 4
+    w = window(N)
     fr = np.fft.irfft(Y, n=N, axis=-1) * w                                      # [C, T', N]
     Ls = stretched_frames(v, p, q)
     total = (Tp - 1) * H + N
@@ -314,25 +398,13 @@ def vocoder_host(xr, p, q, n_fft, phasor=False, bound=False):
     n = min(Ls, (Tp - 1) * H + 1)
     y = np.zeros((C, Ls))
     y[:, :n] = acc[:, N // 2:N // 2 + n] / env[N // 2:N // 2 + n]
-    if not bound:
-        return y
+    if dY is None:
+        return y, None
     f = _fft_factor(N)
-    e = np.zeros((C, T + 2))
-    e[:, :T] = (f + (2 * _U + _U * _U) * (1 + f)) * math.sqrt(N) * np.sqrt((frames ** 2).sum(axis=-1))
-    ea, eb = e[:, i][:, :, None], e[:, i + 1][:, :, None]
-    dmag = (1 + 8 * _U) * (alpha * eb + (1 - alpha) * ea) + 8 * _U * mag
-    with np.errstate(divide="ignore", invalid="ignore"):
-        turn = lambda err, z: np.where(err > 0, np.minimum(2.0 * err / np.abs(z), 2.0), 0.0)
-        step = turn(ea, a) + turn(eb, b) + 24 * _U
-        dP = np.empty((C, Tp, K))
-        dP[:, 0] = np.minimum(turn(e[:, 0][:, None], X[:, 0]) + 4 * _U, 2.0)
-        for j in range(Tp - 1):
-            dP[:, j + 1] = np.minimum(dP[:, j] + step[:, j], 2.0)
-    dYk = dmag + (mag + dmag) * (dP + 2 * _U)
     twice = np.full(K, 2.0)
     twice[0] = twice[-1] = 1.0
     norm = lambda z: np.sqrt((twice * z * z).sum(axis=-1))
-    E = (twice * dYk).sum(axis=-1) / N + f * (norm(np.abs(Y)) + norm(dYk)) / math.sqrt(N)      # [C, T']
+    E = (twice * dY).sum(axis=-1) / N + f * (norm(np.abs(Y)) + norm(dY)) / math.sqrt(N)        # [C, T']
     eacc = np.zeros((C, total))
     for j in range(Tp):
         eacc[:, j * H:j * H + N] += w * E[:, j][:, None]
@@ -340,6 +412,32 @@ def vocoder_host(xr, p, q, n_fft, phasor=False, bound=False):
     s = slice(N // 2, N // 2 + n)
     dy[:, :n] = ((1 + 16 * _U) * eacc[:, s] + 16 * _U * absacc[:, s]) / env[s]
     return y, dy
+
+
+def synthesise_host(Y, v, p, q):
+    """The synthesis stage in float64: Y complex [C, T', K] of a row of v valid frames at p / q to y float64 [C, Ls]"""
+    return _overlap_add(Y, v, p, q)[0]
+
+
+def synthesise_bound(Y, v, p, q, dY=None):
+    """dy [C, Ls]: how far a float32 `synthesise_host_f32` may be from `synthesise_host`, per sample.  dY: None for an exact
+    Y (the stage's own bound: E_j = f ||Y_j||_2 / sqrt(N)), or [C, T', K], how far every element of the Y it got may be from
+    this one."""
+    Y = np.asarray(Y, dtype=np.complex128)
+    return _overlap_add(Y, v, p, q, np.zeros(Y.shape) if dY is None else dY)[1]
+
+
+def vocoder_host(xr, p, q, n_fft, phasor=False, bound=False):
+    """One row through the vocoder in float64, whatever p / q is (1 too): xr float32 or float64 [C, v], v > n_fft / 2, to
+    float64 [C, Ls]: `analyse_host`, `scan_host`, `synthesise_host`.  phasor: the phasor form instead of torchaudio's angles.
+    bound=True: returns (y, dy), dy how far a float32 evaluation in the kernel's order may be from y (the module docstring):
+    the three stage bounds, each fed the one before."""
+    v = np.shape(xr)[1]
+    X = analyse_host(xr, n_fft)
+    Y = scan_host(X, p, q, phasor=phasor)
+    if not bound:
+        return synthesise_host(Y, v, p, q)
+    return _overlap_add(Y, v, p, q, scan_bound(X, p, q, analyse_bound(xr, n_fft), alpha_term=False))
 
 
 def _rows(x, factors, lengths, n_fft, row, dtype):
@@ -455,13 +553,13 @@ def _ph32(z):
     return np.where(ok, z[0] / safe, np.float32(1)).astype(np.float32), np.where(ok, z[1] / safe, np.float32(0)).astype(np.float32)
 
 
-def vocoder_host_f32(xr, p, q, n_fft):
-    """One row through the kernel's scheme in numpy float32, operation for operation (the module docstring): xr float32
-    [C, v], v > n_fft / 2, to float32 [C, Ls]"""
+def analyse_host_f32(xr, n_fft):
+    """The kernel's analysis in numpy float32: xr float32 [C, v], v > n_fft / 2, to X = (Xr, Xi), float32 [C, T_ + 2, K] each,
+    the STFT frames and the two zero frames behind them"""
     f32 = np.float32
     xr = np.asarray(xr, dtype=f32)
     C, v = xr.shape
-    N, H, K = n_fft, n_fft // 4, n_fft // 2 + 1
+    N, K = n_fft, n_fft // 2 + 1
     w, tw, pos = window(N, f32), twiddles(N), positions(N)
     T = stft_frames(v, N)
     zr = np.ascontiguousarray((w * xr[:, _reflect(v, N, T)]).reshape(C * T, N), dtype=f32)
@@ -469,7 +567,15 @@ def vocoder_host_f32(xr, p, q, n_fft):
     _forward(zr, zi, tw)
     Xr, Xi = np.zeros((C, T + 2, K), dtype=f32), np.zeros((C, T + 2, K), dtype=f32)
     Xr[:, :T], Xi[:, :T] = zr[:, pos[:K]].reshape(C, T, K), zi[:, pos[:K]].reshape(C, T, K)
-    i, num = steps(T, p, q)
+    return Xr, Xi
+
+
+def scan_host_f32(X, p, q):
+    """The kernel's scan in numpy float32: X = (Xr, Xi) float32 [C, T_ + 2, K] to Y = (Yr, Yi), float32 [C, T', K] each"""
+    f32 = np.float32
+    Xr, Xi = X
+    C, T2, K = Xr.shape
+    i, num = steps(T2 - 2, p, q)
     Tp = len(i)
     alpha = num.astype(f32) / f32(p)
     Yr, Yi = np.zeros((C, Tp, K), dtype=f32), np.zeros((C, Tp, K), dtype=f32)
@@ -480,12 +586,37 @@ def vocoder_host_f32(xr, p, q, n_fft):
         Yr[:, j], Yi[:, j] = mag * P[0], mag * P[1]
         pa, pb = _ph32(a), _ph32(b)
         P = _ph32(_cmul(P, _cmul(pb, (pa[0], -pa[1]))))
+    return Yr, Yi
+
+
+def hermitian_host_f32(Y):
+    """The spectra of N points the kernel's inverse transform starts from: Y = (Yr, Yi) float32 [C, T', K] to (zr, zi) float32
+    [C T', N]: Y_j[k] at positions(N)[k] for k <= N / 2, the imaginary parts of the bins 0 and N / 2 dropped, and its conjugate
+    at positions(N)[N - k].  A copy: no arithmetic."""
+    f32 = np.float32
+    Yr, Yi = Y
+    C, Tp, K = Yr.shape
+    N = 2 * (K - 1)
+    pos = positions(N)
     zr, zi = np.zeros((C * Tp, N), dtype=f32), np.zeros((C * Tp, N), dtype=f32)
     zr[:, pos[:K]] = Yr.reshape(C * Tp, K)
     zi[:, pos[1:K - 1]] = Yi.reshape(C * Tp, K)[:, 1:K - 1]
     mirror = pos[N - np.arange(1, K - 1)]
     zr[:, mirror] = Yr.reshape(C * Tp, K)[:, 1:K - 1]
     zi[:, mirror] = -Yi.reshape(C * Tp, K)[:, 1:K - 1]
+    return zr, zi
+
+
+def synthesise_host_f32(Y, v, p, q):
+    """The kernel's synthesis in numpy float32: Y = (Yr, Yi) float32 [C, T', K] of a row of v valid frames at p / q to y
+    float32 [C, Ls]"""
+    f32 = np.float32
+    Yr, Yi = Y
+    C, Tp, K = Yr.shape
+    N = 2 * (K - 1)
+    H = N // 4
+    w, tw = window(N, f32), twiddles(N)
+    zr, zi = hermitian_host_f32(Y)
     _inverse(zr, zi, tw)
     fr = (w * (zr * f32(1.0 / N))).reshape(C, Tp, N)
     total = (Tp - 1) * H + N
@@ -499,6 +630,13 @@ def vocoder_host_f32(xr, p, q, n_fft):
     y = np.zeros((C, Ls), dtype=f32)
     y[:, :n] = acc[:, N // 2:N // 2 + n] / env[N // 2:N // 2 + n]
     return y
+
+
+def vocoder_host_f32(xr, p, q, n_fft):
+    """One row through the kernel's scheme in numpy float32, operation for operation (the module docstring): xr float32
+    [C, v], v > n_fft / 2, to float32 [C, Ls]: `analyse_host_f32`, `scan_host_f32`, `synthesise_host_f32`"""
+    v = np.shape(xr)[1]
+    return synthesise_host_f32(scan_host_f32(analyse_host_f32(xr, n_fft), p, q), v, p, q)
 
 
 def time_stretch_host_f32(x, factors, lengths=None, n_fft=512):

@@ -97,6 +97,8 @@ SYMBOLS = {
                                         _VP]),
     "alacgpu_level_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, C.c_uint32, C.c_uint32, _VP,
                                        C.c_double, C.c_double, C.c_int, _VP, _VP, _VP, _VP]),
+    "alacgpu_yin_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, C.c_uint32, C.c_uint32, C.c_uint32,
+                                     C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _VP, C.c_uint64, _VP]),
     "alacgpu_reverb_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
                                         C.c_uint64, _VP, _VP, _VP]),
     "alacgpu_time_stretch_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _VP,
@@ -548,6 +550,17 @@ class AlacGpuContext(_Closing):
         rc = lib().alacgpu_level_device(self._ctx, _dp(d_src), _dp(d_out), rows, channels, stride, frames, _dp(d_valid), mode, hop,
                                         _dp(d_kweight), float(target), float(max_peak), int(bool(clamp)), _dp(d_gain_out),
                                         _dp(d_energy_out), _dp(d_peak_out), _VP(stream))
+        _check(rc, self._ctx)
+
+    def yin_device(self, d_src, rows, channels, stride, frames, d_valid, sample_rate, win_length, hop, tau_min, tau_max, align_length,
+                   threshold, d_out, out_frames, stream=0):
+        """alacgpu_yin_device: the YIN F0 estimate of every frame of every row of d_src (float32 device tensor, planar [rows,
+        channels, stride], the first `frames` of a plane are data) over its first v = min(max(d_valid[row], 0), frames) samples,
+        into d_out (float32 device tensor [rows, channels, 2, out_frames]: f0 in Hz, the aperiodicity; zeros behind a row's
+        frames).  d_valid: an int64 device tensor [rows], or None for `frames`.  align_length 0: centred frames.  yin.py states
+        the arithmetic.  One launch, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_yin_device(self._ctx, _dp(d_src), rows, channels, stride, frames, _dp(d_valid), sample_rate, win_length, hop,
+                                      tau_min, tau_max, align_length, float(threshold), _dp(d_out), out_frames, _VP(stream))
         _check(rc, self._ctx)
 
     def reverb_device(self, d_src, d_out, d_rir, rows, channels, rir_channels, stride, rir_stride, frames, rir_frames, d_valid,
@@ -1199,6 +1212,8 @@ from .biquad import (Effects, RandomBiquad, allpass, bandpass, bandreject, biqua
                      highshelf, lowpass, lowshelf, peaking)
 # ---- peak, RMS and loudness levelling of crops and tensors (alacgpu_level_device) --------------------------------------------------
 from .level import Level, kweight, level, level_host, level_host_twin, loudness, loudness_host  # noqa: E402
+# ---- F0 contours of crops and tensors: the YIN estimator (alacgpu_yin_device) ----------------------------------------------------------
+from .yin import Yin, hz_to_cents, yin, yin_host, yin_host_f32  # noqa: E402
 
 # ---- pitch shift and time stretch of crops and tensors (alacgpu_time_stretch_device) ------------------------------------------------
 from .pitch import (PitchShift, pitch_shift, pitch_shift_host, pitch_shift_host_f32, semitone_ratio, time_stretch,  # noqa: E402

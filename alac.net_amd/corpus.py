@@ -17,12 +17,12 @@ from both tiers into a small staging blob in HBM, and the decode reads that.
 frames a crop needs are decoded as above into a scratch the corpus keeps, and one alacgpu_resample_device call (resample.py
 states the filter) resamples every crop out of it.
 
-`crops(..., reverb=, mix=, level=, effects=, features=, deltas=, vad=, normalize=, augment=)` runs up to ten stages behind the waveform, and `crops` is the one place
+`crops(..., reverb=, mix=, level=, effects=, f0=, features=, deltas=, vad=, normalize=, augment=)` runs up to eleven stages behind the waveform, and `crops` is the one place
 that lists them: the refusals of all of them, the crops the second corpora make (`Corpus._companion_crops`: the noise of an
 AddNoise, then the impulse responses of a Reverb, each cropped by its own corpus at the rate of the crops), the waveform once
-(`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_level_device, alacgpu_biquad_device, alacgpu_logmel_device (or alacgpu_fbank_device or alacgpu_mfcc_device), alacgpu_deltas_device,
+(`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_level_device, alacgpu_biquad_device, alacgpu_yin_device (beside the waveform: it writes a track of its own), alacgpu_logmel_device (or alacgpu_fbank_device or alacgpu_mfcc_device), alacgpu_deltas_device,
 alacgpu_vad_energy_device, the normalisation, alacgpu_select_frames_device and alacgpu_specaugment_device (reverb.py, mix.py,
-level.py, biquad.py, features.py, deltas.py, vad.py, normalize.py, sliding.py and augment.py state the arithmetic), each only if asked for.
+level.py, biquad.py, yin.py, features.py, deltas.py, vad.py, normalize.py, sliding.py and augment.py state the arithmetic), each only if asked for.
 
 `crops(..., speed=)` plays every crop at a drawn factor in front of all that (the same method, speed.py): the step of a corpus
 whose rates differ, with a ratio per (file rate, factor) in place of one per file rate; the crops at factor 1 go through the
@@ -56,6 +56,7 @@ from .mix import AddNoise, _mix, snr_ratio
 from .normalize import MeanVar, TopDb, _normalize
 from .sliding import LDS_MAX as _SLIDING_LDS_MAX, RING_WINDOW_MAX as _SLIDING_RING_WINDOW_MAX, SlidingMeanVar
 from .vad import EnergyVad, _select_frames, _vad_energy
+from .yin import Yin, _yin
 from .pitch import PitchShift, _pitch_shift, _ratio_kinds
 from .reverb import Reverb, _reverb
 from .speed import MAX_WIDTH as _SPEED_MAX_WIDTH, SpeedPerturb, ratio as _speed_ratio
@@ -399,6 +400,7 @@ class Corpus(_Closing):
         self._ft_scratch = None                           # crops(features=): the crops the feature kernel reads
         self._delta_scratch = None                        # crops(deltas=): the features the delta kernel reads
         self._vad_scratch = None                          # crops(vad=): the decisions between the VAD and the selection
+        self._f0_scratch = None                           # crops(f0=): the F0 track the call returns
         self._mix_scratch = None                          # crops(mix=): the noise crops, whichever corpus makes them
         self._reverb_scratch = None                       # crops(reverb=): the impulse responses of the crops
         self._pitch_scratch = None                        # crops(pitch=): the stretched rows
@@ -540,7 +542,7 @@ class Corpus(_Closing):
         if getattr(self, "_gpu", None) is not None:
             self._gpu.close()
             self._gpu = None
-            self._blob = self._plan = self._stage = self._stage_plan = self._rs_scratch = self._ft_scratch = self._delta_scratch = self._vad_scratch = self._mix_scratch = self._reverb_scratch = self._pitch_scratch = self._pitch_back_scratch = None
+            self._blob = self._plan = self._stage = self._stage_plan = self._rs_scratch = self._ft_scratch = self._delta_scratch = self._vad_scratch = self._f0_scratch = self._mix_scratch = self._reverb_scratch = self._pitch_scratch = self._pitch_back_scratch = None
         self._free_pinned()
 
     @property
@@ -658,7 +660,7 @@ class Corpus(_Closing):
         return torch.from_numpy(f.astype(np.int32)).to(self._dev), torch.from_numpy(o).to(self._dev), True
 
     def crops(self, files, frame_offsets, num_frames, dtype=None, out=None, check=True, features=None, normalize=None, mix=None,
-              reverb=None, speed=None, pitch=None, effects=None, level=None, deltas=None, vad=None, augment=None, sample_rate=None,
+              reverb=None, speed=None, pitch=None, f0=None, effects=None, level=None, deltas=None, vad=None, augment=None, sample_rate=None,
               mono=False):
         """Decode crop b = frames frame_offsets[b] .. + num_frames of file files[b] for every b in ONE launch pair: returns
         (pcm [B, C, num_frames] on the device, zero behind lengths[b]; lengths [B], a DEVICE int64 tensor: min(num_frames,
@@ -694,7 +696,7 @@ class Corpus(_Closing):
         as speed= does; pitch.time_stretch on the result covers it.
 
         The stages behind the waveform go by keyword, as sample_rate and mono do, and run in this order whichever are
-        given -- pitch, reverb, mix, level, effects, features, deltas, the VAD's decision, normalize, the selection of the voiced frames, augment --,
+        given -- pitch, reverb, mix, level, effects, f0, features, deltas, the VAD's decision, normalize, the selection of the voiced frames, augment --,
         in place but for the features and the deltas, by the corpus's own context on the same stream; lengths (but for vad=,
         which shortens them), `check` and last_status() are those of the call without them (with check=True a second corpus's own check runs too, and first).  ValueError before any device
         work for what a stage cannot take.
@@ -723,6 +725,15 @@ class Corpus(_Closing):
         crops)` returned.  Bit for bit biquad.biquad(the crops without it, coeffs, lengths, gain, effects.clamp); a crop
         outside the corpus stays zeros.  ValueError: int32 crops, draws of another shape, dtype or device, a filter frequency at
         or above the Nyquist frequency of the crops' rate.
+
+        f0: a yin.Yin -- the F0 track of the final waveform, the one behind speed=, pitch=, reverb=, mix=, level= and effects=
+        that features= reads: ONE alacgpu_yin_device call.  The result then gains one element at its end: (pcm or feats,
+        lengths, track), track float32 [B, 1 if mono else C, 2, f0.frames(num_frames)] -- f0 in Hz and the aperiodicity,
+        yin.py states them --, cut from a scratch the corpus keeps: the next call with f0= writes it again.  Bit for bit
+        yin.yin(the waveform the call returns with the same arguments and draws and without features=, f0, lengths); a crop
+        outside the corpus is silence.  `Yin.like(features)` has the frames of the features.  ValueError: something that is no
+        Yin, a Yin for another rate than the crops', int32 crops, vad= (the selected frames would no longer line up with the
+        track), num_frames below f0.min_frames.
 
         features: a features.LogMel, a fbank.KaldiFbank or a mfcc.KaldiMfcc -- the crops' log-mel, Kaldi fbank or Kaldi MFCC
         features instead of their PCM (n_mels below is then the transform's line count: a KaldiMfcc's n_ceps):
@@ -778,6 +789,8 @@ class Corpus(_Closing):
             self._level_given(level, dtype, rate, Co)
         if effects is not None:
             effects = self._effects_given(effects, dtype, rate)
+        if f0 is not None:
+            self._f0_given(f0, dtype, rate, vad, num_frames)
         if normalize is not None:
             if not isinstance(normalize, (MeanVar, TopDb, SlidingMeanVar)):
                 raise ValueError(f"normalize must be a normalize.MeanVar, a normalize.TopDb or a sliding.SlidingMeanVar, not {normalize!r}")
@@ -820,7 +833,7 @@ class Corpus(_Closing):
             if features is None:
                 raise ValueError("a SpecAugment masks log-mel features: it needs features=")
         if (features is not None or mix is not None or reverb is not None or speed is not None or effects is not None or level is not None
-                or pitch is not None):
+                or pitch is not None or f0 is not None):
             L = _frame_count("num_frames", num_frames)
             if features is not None and L < features.min_frames:
                 raise ValueError(features.short(L))
@@ -872,6 +885,8 @@ class Corpus(_Closing):
             _level(ctx, res, level, rate, lengths, res)
         if effects is not None:
             _biquad(ctx, res, effects[1][0], lengths, effects[1][1], effects[0].clamp, res)
+        if f0 is not None:
+            track = _yin(ctx, res, f0, lengths, self._scratch("_f0_scratch", (B, Co, 2, int(f0.frames(L)))))
         if features is not None:
             if B:
                 features.launch(self._gpu, res, B, Co, L, L, feats, torch.cuda.current_stream(self._dev).cuda_stream)
@@ -887,7 +902,7 @@ class Corpus(_Closing):
             res, lengths = _select_frames(ctx, res, voiced, lengths, res)
         if augment is not None:
             _spec_augment(ctx, res, augment[0] if augment[1] is None else augment, lengths, res)
-        return res, lengths
+        return (res, lengths) if f0 is None else (res, lengths, track)
 
     def _waveform(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, speed=None):
         """The crops themselves, what `crops` returns without a stage: through `_resampled_crops` with speed=, at another
@@ -1007,6 +1022,26 @@ class Corpus(_Closing):
         _level_checked(spec, rate, Co)
         if not _is_f32(torch, dtype):
             raise ValueError("float32 crops are levelled")
+
+    @staticmethod
+    def _f0_given(spec, dtype, rate, vad, num_frames):
+        """crops(f0=) checked: ValueError for what is no Yin, for a Yin of another rate than the crops', for int32 crops, together
+        with vad= and for crops too short for a frame.  Nothing is done on the device."""
+        import torch
+
+        if not isinstance(spec, Yin):
+            raise ValueError(f"f0 must be a yin.Yin, not {spec!r}")
+        if rate is None:
+            raise ValueError(_NEEDS_RATE)
+        if spec.sample_rate != rate:
+            raise ValueError(f"f0 for {spec.sample_rate} Hz, crops at {rate} Hz")
+        if not _is_f32(torch, dtype):
+            raise ValueError("F0 is estimated from float32 crops")
+        if vad is not None:
+            raise ValueError("f0= with vad=: the selected frames would no longer line up with the track")
+        L = _frame_count("num_frames", num_frames)
+        if L < spec.min_frames:
+            raise ValueError(spec.short(L))
 
     def _effects_given(self, given, dtype, rate):
         """crops(effects=) as the pair (Effects, draws or None), checked: ValueError for anything else, for int32 crops, for
@@ -1279,7 +1314,7 @@ class Corpus(_Closing):
         return out, lengths
 
     def random_crops(self, batch, num_frames, generator=None, dtype=None, out=None, check=True, features=None, normalize=None,
-                     mix=None, reverb=None, speed=None, pitch=None, effects=None, level=None, deltas=None, vad=None, augment=None,
+                     mix=None, reverb=None, speed=None, pitch=None, f0=None, effects=None, level=None, deltas=None, vad=None, augment=None,
                      sample_rate=None, mono=False):
         """`batch` crops of num_frames frames drawn on the device: files uniform over the corpus, the first frame uniform in
         0 .. max(T_f - num_frames, 0).  generator: a torch.Generator (of the corpus's device, or of the CPU: then the draws are
@@ -1295,7 +1330,8 @@ class Corpus(_Closing):
         a SpeedPerturb is drawn from `generator` behind the call's own two draws and in front of an AddNoise's
         (SpeedPerturb.draw states its two), and the first frame is then uniform in 0 .. max(Ty[f, k] - num_frames, 0), from the
         same u, with the frames of the file at its factor.  pitch as for `crops`; a PitchShift is drawn from `generator` behind a
-        SpeedPerturb's and in front of an AddNoise's (PitchShift.draw states its two)."""
+        SpeedPerturb's and in front of an AddNoise's (PitchShift.draw states its two).  f0 as for `crops`: it draws nothing, and the
+        result gains the track at its end: (pcm or feats, lengths, files, frame_offsets, track)."""
         import torch
 
         B, L = _frame_count("batch", batch), _frame_count("num_frames", num_frames)
@@ -1314,6 +1350,8 @@ class Corpus(_Closing):
             self._level_given(level, dtype, rate, 1 if mono else self.channels)
         if effects is not None:
             effects = self._effects_given(effects, dtype, rate)
+        if f0 is not None:
+            self._f0_given(f0, dtype, rate, vad, num_frames)
         if augment is not None:
             augment = _how(augment, "augment")
             if features is None:
@@ -1352,10 +1390,10 @@ class Corpus(_Closing):
             feat_lengths = features.lengths((ends - offs).clamp(max=L))
             lines = deltas.lines(features.n_mels) if isinstance(deltas, Deltas) else features.n_mels
             augment = (augment[0], augment[0].draw(lines, feat_lengths, generator=generator))
-        pcm, lengths = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,
-                                  features=features, normalize=normalize, mix=mix, reverb=reverb, augment=augment, speed=speed,
-                                  deltas=deltas, vad=vad, effects=effects, level=level, pitch=pitch)
-        return pcm, lengths, files, offs
+        res = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,
+                         features=features, normalize=normalize, mix=mix, reverb=reverb, augment=augment, speed=speed,
+                         deltas=deltas, vad=vad, effects=effects, level=level, pitch=pitch, f0=f0)
+        return (res[0], res[1], files, offs) + tuple(res[2:])
 
     def last_staged_bytes(self):
         """The bytes the last crops call of a tiered corpus staged (every packet rounded up to 16): a device int64 tensor of one

@@ -1,5 +1,5 @@
 // alacgpu_stages.hip -- C ABI of include/alacgpu.h, the stages around the decode: the crop planner, the scan with the packet
-// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the phase vocoder, the reverberation, the noise mix, the levelling, the biquad cascade, the normalisations, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
+// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the phase vocoder, the reverberation, the noise mix, the levelling, the biquad cascade, the YIN pitch estimator, the normalisations, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
 // their own scratch; the decode path is alacgpu_api.hip.  No CPU fallback here either: every stage is its kernels.
 #include <algorithm>
 #include <cmath>
@@ -17,6 +17,7 @@
 #include "alac_augment.h"
 #include "alac_mix.h"
 #include "alac_biquad.h"
+#include "alac_yin.h"
 #include "alac_level.h"
 #include "alac_reverb.h"
 #include "alac_stretch.h"
@@ -1086,6 +1087,53 @@ int alacgpu_copy_rows_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, u
     void* kargs[] = {&p};
     HIP_TRY(ctx, hipLaunchKernel((const void*)alac_copy_rows_kernel, dim3((uint32_t)(planes * tiles)), dim3(ALAC_STRETCH_COPY_THREADS), kargs, 0,
                                  (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
+}
+
+int alacgpu_yin_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t stride, uint64_t frames,
+                       const void* d_valid, uint32_t sample_rate, uint32_t win_length, uint32_t hop, uint32_t tau_min, uint32_t tau_max,
+                       uint32_t align_length, float threshold, void* d_out, uint64_t out_frames, void* hip_stream) {
+    if (!ctx || !args_ok({{d_src, 4}, {d_valid, 8, false}, {d_out, 4}})) return ALACGPU_ERR_BAD_ARG;
+    if (channels == 0 || frames == 0 || frames > stride || sample_rate == 0 || hop == 0) return ALACGPU_ERR_BAD_ARG;
+    if (win_length < ALAC_YIN_MIN_WIN || win_length > ALAC_YIN_MAX_WIN || win_length % 64u != 0u || tau_min < 2u ||
+        tau_max > ALAC_YIN_MAX_LAG || tau_max <= tau_min + 1u || !(threshold > 0.0f && threshold <= 1.0f))
+        return ALACGPU_ERR_BAD_ARG;
+    const uint64_t expect = align_length ? (frames < align_length ? 0u : 1u + (frames - align_length) / hop) : frames / hop + 1u;
+    if (out_frames != expect) return ALACGPU_ERR_BAD_ARG;
+    const uint64_t planes = (uint64_t)rows * channels;
+    uint64_t extent, out_extent;
+    if (!planes_extent(planes, stride, frames, extent) || !planes_extent(planes, 2u * out_frames, 2u * out_frames, out_extent) ||
+        !apart(d_src, extent, d_out, out_extent))
+        return ALACGPU_ERR_BAD_ARG;
+    const uint32_t tile = alac_yin_tile(win_length, tau_max, hop);
+    const uint64_t tiles = (out_frames + tile - 1u) / tile;
+    if (tiles > 0x7FFFFFFFull || tiles * std::max<uint64_t>(planes, 1u) > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0 || out_frames == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    alac_yin_params p;
+    p.src = (const float*)d_src;
+    p.valid = (const int64_t*)d_valid;
+    p.out = (float*)d_out;
+    p.channels = channels;
+    p.stride = stride;
+    p.frames = frames;
+    p.out_frames = out_frames;
+    p.win = win_length;
+    p.hop = hop;
+    p.tau_min = tau_min;
+    p.tau_max = tau_max;
+    p.align = align_length;
+    p.first = (int64_t)(align_length / 2u) - (int64_t)((win_length + tau_max) / 2u);
+    p.tile = tile;
+    p.tiles = (uint32_t)tiles;
+    p.samples = alac_yin_samples(win_length, tau_max, hop, tile);
+    p.threshold = threshold;
+    p.rate = (float)sample_rate;
+    const size_t lds = sizeof(float) * ((size_t)p.samples + (size_t)tile * (tau_max + 1u));
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel(hop % 4u == 0u ? (const void*)alac_yin_kernel_vec : (const void*)alac_yin_kernel,
+                                 dim3((uint32_t)(tiles * planes)), dim3(ALAC_YIN_THREADS), kargs, lds, (hipStream_t)hip_stream));
     HIP_TRY(ctx, hipGetLastError());
     return ALACGPU_OK;
 }

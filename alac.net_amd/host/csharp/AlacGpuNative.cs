@@ -191,6 +191,15 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_level_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, uint rows,
             uint channels, ulong stride, ulong frames, IntPtr dValid, uint mode, uint hop, IntPtr dKweight, double target,
             double maxPeak, int clamp, IntPtr dGainOut, IntPtr dEnergyOut, IntPtr dPeakOut, IntPtr hipStream);
+        /// <summary>The fundamental frequency of planar float crops in device memory (dSrc [rows, channels, stride]; the first
+        /// frames of a plane are data), frame by frame: the YIN estimator over the lags tauMin .. tauMax with windows of
+        /// winLength samples every hop samples, over the first dValid[row] samples (long[rows] or IntPtr.Zero for all), zeros
+        /// outside them; frames centred on t * hop (alignLength 0) or counted and placed as Kaldi's snip_edges frames of
+        /// alignLength samples.  dOut is float[rows, channels, 2, outFrames]: f0 in Hz and the aperiodicity, which is below
+        /// threshold exactly for a voiced frame; zeros behind a row's frames.  One launch, asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_yin_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
+            ulong stride, ulong frames, IntPtr dValid, uint sampleRate, uint winLength, uint hop, uint tauMin, uint tauMax,
+            uint alignLength, float threshold, IntPtr dOut, ulong outFrames, IntPtr hipStream);
         /// <summary>Room reverberation into planar float crops in device memory (dSrc, dOut [rows, channels, stride], dRir
         /// [rows, rirChannels, rirStride], rirChannels 1 or channels; the first frames / rirFrames of a plane are data): every
         /// row convolved with its impulse response over the first dValid[row] frames of the signal and dRirValid[row] of the

@@ -830,6 +830,40 @@ int alacgpu_level_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint3
                          double max_peak, int clamp, void* d_gain_out, void* d_energy_out, void* d_peak_out, void* hip_stream);
 
 /*
+ * alacgpu_yin_device: the fundamental frequency of the crops, frame by frame (no counterpart in the reference): the YIN
+ * estimator of de Cheveigne and Kawahara (JASA 2002), steps 1 to 5; one launch, no atomics, no scratch, the same inputs give
+ * the same bits.  d_src is planar float32 [rows, channels, stride], the first `frames` elements of a plane are data, what lies
+ * behind them is not read; d_out is float32 [rows, channels, 2, out_frames], apart from d_src.  For row r, with v =
+ * min(max(d_valid[r], 0), frames) (int64 [rows]; NULL: frames), span = win_length + tau_max, samples outside [0, v) reading as
+ * zero, the row has v / hop + 1 frames centred on c_t = t hop (align_length 0), or 1 + (v - align_length) / hop frames, none
+ * for v < align_length, centred on c_t = t hop + align_length / 2; frame t starts at s = c_t - span / 2, and
+ *   d[tau]  = sum_{j < win_length} (x[s + j] - x[s + j + tau])^2                      tau = 0 .. tau_max, the direct sum
+ *   d'[tau] = d[tau] tau / (d[1] + .. + d[tau]), 1 where that sum is 0; d'[0] = 1
+ *   tau     = the first of tau_min .. tau_max - 1 with d'[tau] < threshold, then forward while d'[tau + 1] < d'[tau] (up to
+ *             tau_max - 1); without one the first argmin of d' over that range (a NaN as +infinity)
+ *   shift   = (a - c) / (2 (a - 2 b + c)) for (a, b, c) = d'[tau - 1 .. tau + 1] when b <= a, b <= c and a - 2 b + c > 0, else 0
+ *   out[r, ch, 0, t] = sample_rate / (tau + shift),  out[r, ch, 1, t] = b           f0 in Hz, and the aperiodicity
+ * and (0, 1) for a frame whose d[1] + .. + d[tau_max] is 0 (silence, a constant).  The frame is voiced exactly when its
+ * aperiodicity is below the threshold.  Frames at and behind the row's count, up to out_frames, are zero in both lines.  A
+ * workgroup of 256 lanes takes a plane and a tile of up to 8 consecutive frames, whose samples it loads once into LDS; every
+ * lag's sum runs over j in ascending order as e = fl(x[s + j] - x[s + j + tau]), acc = fma(e, e, acc); a wave per frame then
+ * scans the lags in chunks of 64 and searches.  Every other operation is one IEEE float32 operation, the divisions correctly
+ * rounded (csrc/alac_yin.h and alac.net_amd/yin.py state the order; the twin there equals the kernel bit for bit, and the
+ * module derives how far any float32 evaluation may be from the exact one).  Anything else follows IEEE: a NaN sample makes d'
+ * NaN from the first lag whose sum reaches it, in the frames whose span holds it, and no other.  Nothing of the ctx is used but
+ * its device, so calls on different streams are independent.  Device pointers only, asynchronous on hip_stream, nothing is
+ * read back.  rows == 0 or out_frames == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx, d_src or d_out, a misaligned array (4; 8 for d_valid), channels
+ * 0, frames 0 or above stride, sample_rate 0, hop 0, a win_length that is no multiple of 64 in 64 .. 2048, tau_min below 2,
+ * tau_max above 2048 or not above tau_min + 1, a threshold outside (0, 1], out_frames that is not the frame count of a row of
+ * `frames` samples, d_src and d_out that overlap, an extent of 2^60 bytes or more, 2^31 workgroups or more.
+ */
+int alacgpu_yin_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t stride, uint64_t frames,
+                       const void* d_valid, uint32_t sample_rate, uint32_t win_length, uint32_t hop, uint32_t tau_min,
+                       uint32_t tau_max, uint32_t align_length, float threshold, void* d_out, uint64_t out_frames,
+                       void* hip_stream);
+
+/*
  * alacgpu_reverb_device: room reverberation into the crops, in front of the noise mix (no counterpart in the reference): every
  * crop convolved with its own impulse response by a uniformly partitioned overlap-save convolution; two launches, no atomics,
  * the same inputs give the same bits.  The layout is planar float32: d_src and d_out [rows, channels, stride], d_rir [rows,

@@ -99,6 +99,8 @@ SYMBOLS = {
                                        C.c_double, C.c_double, C.c_int, _VP, _VP, _VP, _VP]),
     "alacgpu_yin_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _VP, C.c_uint64, _VP]),
+    "alacgpu_cqt_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _VP, _VP, _VP,
+                                     C.c_int, C.c_int, C.c_float, _VP, C.c_uint64, _VP]),
     "alacgpu_reverb_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
                                         C.c_uint64, _VP, _VP, _VP]),
     "alacgpu_time_stretch_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _VP,
@@ -418,6 +420,20 @@ class AlacGpuContext(_Closing):
         max(., floor).  Asynchronous on `stream` (raw hipStream_t); nothing is read back."""
         rc = lib().alacgpu_logmel_device(self._ctx, _dp(d_src), rows, channels, src_stride, frames, n_fft, hop, n_mels, _dp(d_window),
                                          _dp(d_basis), _dp(d_fb), log_mode, floor, _dp(d_out), out_frames, _VP(stream))
+        _check(rc, self._ctx)
+
+    def cqt_device(self, d_src, rows, channels, src_stride, frames, hop, n_bins, lengths, d_lengths, d_table, power, log_mode, floor,
+                   d_out, out_frames, stream=0):
+        """alacgpu_cqt_device: the constant-Q features of d_src (float32 device tensor, planar [rows, channels, src_stride], the
+        first `frames` of a plane are signal) into d_out (float32 [rows, channels, n_bins, out_frames], out_frames =
+        1 + frames // hop, every element written); lengths: the N_k [n_bins] (host), d_lengths the same on the device (int32),
+        d_table the kernels in blocks of 16 bins (cqt.ConstantQ builds them); power 1: magnitude, 2: power; log_mode 0: none,
+        1: ln, 2: log10 of max(., floor).  Asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+        if lengths.shape != (n_bins,):
+            raise ValueError(f"lengths must be {n_bins} integers, not {lengths.shape}")
+        rc = lib().alacgpu_cqt_device(self._ctx, _dp(d_src), rows, channels, src_stride, frames, hop, n_bins, _ptr(lengths), _dp(d_lengths),
+                                      _dp(d_table), power, log_mode, floor, _dp(d_out), out_frames, _VP(stream))
         _check(rc, self._ctx)
 
     def fbank_device(self, d_src, rows, channels, src_stride, frames, win_length, n_fft, hop, n_mels, d_window, d_basis, d_fb, flags,
@@ -1212,6 +1228,8 @@ from .biquad import (Effects, RandomBiquad, allpass, bandpass, bandreject, biqua
                      highshelf, lowpass, lowshelf, peaking)
 # ---- peak, RMS and loudness levelling of crops and tensors (alacgpu_level_device) --------------------------------------------------
 from .level import Level, kweight, level, level_host, level_host_twin, loudness, loudness_host  # noqa: E402
+# ---- constant-Q features of crops and tensors (alacgpu_cqt_device) --------------------------------------------------------------------
+from .cqt import ConstantQ, cqt, cqt_frequencies, cqt_host, cqt_host_f32, cqt_lengths, cqt_work  # noqa: E402
 # ---- F0 contours of crops and tensors: the YIN estimator (alacgpu_yin_device) ----------------------------------------------------------
 from .yin import Yin, hz_to_cents, yin, yin_host, yin_host_f32  # noqa: E402
 

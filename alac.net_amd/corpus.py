@@ -49,6 +49,7 @@ from .augment import LDS_MAX as _WARP_MAX, _check_draws, _how, _spec_augment
 from .biquad import Effects, _biquad
 from .level import _checked as _level_checked, _level
 from .deltas import Deltas, _add_deltas
+from .cqt import ConstantQ
 from .fbank import KaldiFbank
 from .mfcc import KaldiMfcc
 from .features import LogMel
@@ -64,7 +65,7 @@ from .speed import MAX_WIDTH as _SPEED_MAX_WIDTH, SpeedPerturb, ratio as _speed_
 PAD_CFG = 0xFFFF        # a padding entry's cfg_idx: never a row of the context, so the kernels switch the entry off
 MAX_CFGS = 65535
 _NEEDS_RATE = "the files of this corpus differ in sample rate: crops need sample_rate="
-_FEATURES = (LogMel, KaldiFbank, KaldiMfcc)              # what crops(features=) takes
+_FEATURES = (LogMel, KaldiFbank, KaldiMfcc, ConstantQ)              # what crops(features=) takes
 # crops(mix=) and crops(reverb=) for `Corpus._second_corpus`: the specification's class, its attribute that holds the second
 # corpus, how many tensors its draw() returns and what their dtypes have to be, and the nouns of the messages
 _MIX = dict(arg="mix", spec=AddNoise, corpus="noise", theirs="the noise corpus", they="the noise",
@@ -735,8 +736,8 @@ class Corpus(_Closing):
         Yin, a Yin for another rate than the crops', int32 crops, vad= (the selected frames would no longer line up with the
         track), num_frames below f0.min_frames.
 
-        features: a features.LogMel, a fbank.KaldiFbank or a mfcc.KaldiMfcc -- the crops' log-mel, Kaldi fbank or Kaldi MFCC
-        features instead of their PCM (n_mels below is then the transform's line count: a KaldiMfcc's n_ceps):
+        features: a features.LogMel, a fbank.KaldiFbank, a mfcc.KaldiMfcc or a cqt.ConstantQ -- the crops' log-mel, Kaldi fbank, Kaldi MFCC
+        or constant-Q features instead of their PCM (n_mels below is then the transform's line count: a KaldiMfcc's n_ceps, a ConstantQ's n_bins):
         the waveform goes into a float32 scratch the corpus keeps and ONE alacgpu_logmel_device, alacgpu_fbank_device or
         alacgpu_mfcc_device call turns every row, the zeros behind its length included, into features.  Returns (feats float32 [B, 1 if mono else C,
         n_mels, features.frames(num_frames)], feat_lengths [B] int64 on the device: features.lengths(lengths) -- lengths // hop
@@ -807,7 +808,7 @@ class Corpus(_Closing):
                                      f"{_SLIDING_RING_WINDOW_MAX} frames")
         if features is not None:
             if not isinstance(features, _FEATURES):
-                raise ValueError(f"features must be a features.LogMel or a fbank.KaldiFbank or a mfcc.KaldiMfcc, not {features!r} "
+                raise ValueError(f"features must be a features.LogMel or a fbank.KaldiFbank or a mfcc.KaldiMfcc or a cqt.ConstantQ, not {features!r} "
                                  f"(sample_rate= and mono= go by keyword)")
             if rate is None:
                 raise ValueError(_NEEDS_RATE)

@@ -1,5 +1,5 @@
 // alacgpu_stages.hip -- C ABI of include/alacgpu.h, the stages around the decode: the crop planner, the scan with the packet
-// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the phase vocoder, the reverberation, the noise mix, the levelling, the biquad cascade, the YIN pitch estimator, the normalisations, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
+// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the phase vocoder, the reverberation, the noise mix, the levelling, the biquad cascade, the YIN pitch estimator, the constant-Q transform, the normalisations, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
 // their own scratch; the decode path is alacgpu_api.hip.  No CPU fallback here either: every stage is its kernels.
 #include <algorithm>
 #include <cmath>
@@ -18,6 +18,7 @@
 #include "alac_mix.h"
 #include "alac_biquad.h"
 #include "alac_yin.h"
+#include "alac_cqt.h"
 #include "alac_level.h"
 #include "alac_reverb.h"
 #include "alac_stretch.h"
@@ -1134,6 +1135,59 @@ int alacgpu_yin_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint3
     void* kargs[] = {&p};
     HIP_TRY(ctx, hipLaunchKernel(hop % 4u == 0u ? (const void*)alac_yin_kernel_vec : (const void*)alac_yin_kernel,
                                  dim3((uint32_t)(tiles * planes)), dim3(ALAC_YIN_THREADS), kargs, lds, (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
+}
+
+int alacgpu_cqt_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride, uint64_t frames,
+                       uint32_t hop, uint32_t n_bins, const uint32_t* lengths, const void* d_lengths, const void* d_table, int power,
+                       int log_mode, float floor, void* d_out, uint64_t out_frames, void* hip_stream) {
+    if (!ctx || !args_ok({{d_src, 4}, {lengths, 4}, {d_lengths, 4}, {d_table, 4}, {d_out, 4}})) return ALACGPU_ERR_BAD_ARG;
+    if (n_bins < 1 || n_bins > ALAC_CQT_MAX_BINS || hop < 1 || hop > ALAC_CQT_MAX_HOP || channels == 0 || (power != 1 && power != 2))
+        return ALACGPU_ERR_BAD_ARG;
+    if (!(floor > 0.0f) || !std::isfinite(floor)) return ALACGPU_ERR_BAD_ARG;
+    if (log_mode != ALAC_CQT_LOG_NONE && log_mode != ALAC_CQT_LOG_LN && log_mode != ALAC_CQT_LOG_10) return ALACGPU_ERR_BAD_ARG;
+    if (frames < 1 || frames > src_stride || frames > (1ull << 62) || out_frames != 1u + frames / hop) return ALACGPU_ERR_BAD_ARG;
+    for (uint32_t k = 0; k < n_bins; ++k)      // the lengths fall with the bin, from at most ALAC_CQT_MAX_TAPS to at least 2
+        if (lengths[k] < 2u || lengths[k] > (k ? lengths[k - 1u] : ALAC_CQT_MAX_TAPS)) return ALACGPU_ERR_BAD_ARG;
+    alac_cqt_params p;
+    p.n0 = lengths[0];
+    p.c0 = p.n0 / 2u;
+    p.n_blocks = (n_bins + ALAC_CQT_BLOCK_BINS - 1u) / ALAC_CQT_BLOCK_BINS;
+    uint32_t off = 0;
+    for (uint32_t b = 0; b < p.n_blocks; ++b) {       // the table's layout: cqt.py's _blocks
+        const uint32_t n = lengths[b * ALAC_CQT_BLOCK_BINS];
+        p.blk_k[b] = (n + 1u) & ~1u;
+        p.blk_off[b] = off;
+        p.blk_start[b] = p.c0 - n / 2u;
+        off += 32u * p.blk_k[b];
+    }
+    for (uint32_t b = p.n_blocks; b < ALAC_CQT_MAX_BLOCKS; ++b) p.blk_k[b] = p.blk_off[b] = p.blk_start[b] = 0u;
+    const uint32_t tile = alac_cqt_tile(p.n0, hop);
+    const uint64_t tiles = (out_frames + tile - 1u) / tile;
+    if (tiles > 0x7FFFFFFFull || tiles * channels > 0x7FFFFFFFull || tiles * channels * rows > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    const size_t lds = sizeof(float) * (size_t)alac_cqt_lds_floats(p.n0, hop, tile);
+    if (rows == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (lds > ALAC_CQT_LDS_DEFAULT)
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)alac_cqt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    p.src = (const float*)d_src;
+    p.src_stride = src_stride;
+    p.frames = frames;
+    p.out = (float*)d_out;
+    p.out_frames = out_frames;
+    p.table = (const float*)d_table;
+    p.lengths = (const uint32_t*)d_lengths;
+    p.n_bins = n_bins;
+    p.hop = hop;
+    p.tile = tile;
+    p.tiles = (uint32_t)tiles;
+    p.power = (uint32_t)power;
+    p.log_mode = (uint32_t)log_mode;
+    p.floor = floor;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_cqt_kernel, dim3((uint32_t)(tiles * channels * rows)), dim3(ALAC_CQT_THREADS), kargs, lds,
+                                 (hipStream_t)hip_stream));
     HIP_TRY(ctx, hipGetLastError());
     return ALACGPU_OK;
 }

@@ -200,6 +200,12 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_yin_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
             ulong stride, ulong frames, IntPtr dValid, uint sampleRate, uint winLength, uint hop, uint tauMin, uint tauMax,
             uint alignLength, float threshold, IntPtr dOut, ulong outFrames, IntPtr hipStream);
+        /// <summary>Constant-Q features of planar float crops in device memory (dSrc [rows, channels, srcStride] to dOut
+        /// [rows, channels, nBins, outFrames], outFrames = 1 + frames / hop): lengths is the N_k in host memory, dLengths
+        /// the same in device memory, dTable the kernels in blocks of 16 bins (include/alacgpu.h).</summary>
+        [DllImport(Lib)] public static extern int alacgpu_cqt_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
+            ulong srcStride, ulong frames, uint hop, uint nBins, uint[] lengths, IntPtr dLengths, IntPtr dTable, int power,
+            int logMode, float floor, IntPtr dOut, ulong outFrames, IntPtr hipStream);
         /// <summary>Room reverberation into planar float crops in device memory (dSrc, dOut [rows, channels, stride], dRir
         /// [rows, rirChannels, rirStride], rirChannels 1 or channels; the first frames / rirFrames of a plane are data): every
         /// row convolved with its impulse response over the first dValid[row] frames of the signal and dRirValid[row] of the

@@ -864,6 +864,33 @@ int alacgpu_yin_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint3
                        void* hip_stream);
 
 /*
+ * alacgpu_cqt_device: constant-Q features of the crops (no counterpart in the reference): the direct constant-Q transform,
+ * every bin's own windowed complex exponential against the signal; one launch, no atomics, no scratch, the same inputs give the
+ * same bits.  d_src is planar float32 [rows, channels, src_stride], the first `frames` elements of a plane are signal, zeros
+ * are read outside them and nothing is reflected; d_out is float32 [rows, channels, n_bins, out_frames], out_frames =
+ * 1 + frames / hop, every element written.  Frame t is centred on sample t hop; with N_k = lengths[k] (host memory, uint32
+ * [n_bins], falling with k, 2 .. 36864; d_lengths is the same array in device memory) and c_k = N_k / 2,
+ *   C[k, t] = sum over n < N_k of g_k[n] x[t hop - c_k + n],   P = Re(C)^2 + Im(C)^2,
+ *   out[k, t] = sqrt(P) (power 1) or P (power 2); log_mode 1 or 2: ln or log10 of max(that, floor)
+ * d_table holds the g_k as float32 in blocks of 16 bins: block b is [K_b][32], K_b the even number at or above N_{16 b}, row r
+ * the real ((r >> 3) & 1 == 0) or imaginary part of the block's bin (r >> 4) 8 + (r & 7), bin k's taps at n' = c_{16 b} - c_k + n
+ * with zeros around them (alac.net_amd/cqt.py builds it and states the arithmetic, csrc/alac_cqt.h the layout).  A workgroup
+ * of 256 lanes takes a plane and a tile of up to 32 frames, whose span it loads once into LDS; a block is one accumulator of
+ * v_mfma_f32_32x32x2_f32 over its K_b taps: k-ordered chains of float32 fused multiply-adds, P = fma(re, re, round(im im)),
+ * the root correctly rounded.  A NaN or an infinity reaches element (k, t) exactly through bin k's own taps of frame t (a
+ * tile whose span holds one is evaluated bin by bin); every other element is what it is without it.  Nothing of the ctx is
+ * used but its device, so calls on different streams are independent.  Device pointers (but `lengths`), asynchronous on
+ * hip_stream, nothing is read back.  rows == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx or array, a misaligned array (4), channels 0, n_bins outside
+ * 1 .. 512, hop outside 1 .. 2^20, lengths that rise, exceed 36864 or fall below 2, a power that is not 1 or 2, an unknown
+ * log_mode, a floor that is not positive and finite, frames 0 or above src_stride, out_frames that is not 1 + frames / hop,
+ * 2^31 workgroups or more.
+ */
+int alacgpu_cqt_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride, uint64_t frames,
+                       uint32_t hop, uint32_t n_bins, const uint32_t* lengths, const void* d_lengths, const void* d_table, int power,
+                       int log_mode, float floor, void* d_out, uint64_t out_frames, void* hip_stream);
+
+/*
  * alacgpu_reverb_device: room reverberation into the crops, in front of the noise mix (no counterpart in the reference): every
  * crop convolved with its own impulse response by a uniformly partitioned overlap-save convolution; two launches, no atomics,
  * the same inputs give the same bits.  The layout is planar float32: d_src and d_out [rows, channels, stride], d_rir [rows,

@@ -103,6 +103,8 @@ SYMBOLS = {
                                      C.c_int, C.c_int, C.c_float, _VP, C.c_uint64, _VP]),
     "alacgpu_reverb_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
                                         C.c_uint64, _VP, _VP, _VP]),
+    "alacgpu_rir_shoebox_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int32, C.c_double, _VP,
+                                             C.c_uint64, _VP, _VP]),
     "alacgpu_time_stretch_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _VP,
                                               _VP, _VP, _VP, C.c_uint32, _VP]),
     "alacgpu_copy_rows_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _VP]),
@@ -589,6 +591,16 @@ class AlacGpuContext(_Closing):
         reverb.py states the arithmetic.  Two launches, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
         rc = lib().alacgpu_reverb_device(self._ctx, _dp(d_src), _dp(d_out), _dp(d_rir), rows, channels, rir_channels, stride,
                                          rir_stride, frames, rir_frames, _dp(d_valid), _dp(d_rir_valid), _VP(stream))
+        _check(rc, self._ctx)
+
+    def rir_shoebox_device(self, d_geometry, d_beta, rows, sample_rate, frames, taps, max_order, sound_speed, d_out, out_stride,
+                           d_lengths, stream=0):
+        """alacgpu_rir_shoebox_device: the image-source response of every row's room (d_geometry float64 device tensor
+        [rows, 9], d_beta float32 [rows, 6]) into the first `frames` of every row of d_out (float32 [rows, out_stride]) and its
+        length -- frames, or 0 where the row is refused -- into d_lengths (int32 [rows]).  max_order -1: every order.  rir.py
+        states the arithmetic.  One launch, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_rir_shoebox_device(self._ctx, _dp(d_geometry), _dp(d_beta), rows, sample_rate, frames, taps, max_order,
+                                              float(sound_speed), _dp(d_out), out_stride, _dp(d_lengths), _VP(stream))
         _check(rc, self._ctx)
 
     def time_stretch_device(self, d_src, d_out, rows, channels, src_stride, out_stride, frames, out_frames, d_p, d_q, d_valid,
@@ -1238,6 +1250,9 @@ from .pitch import (PitchShift, pitch_shift, pitch_shift_host, pitch_shift_host_
                     time_stretch_host, time_stretch_host_f32)
 # ---- room reverberation into crops and tensors (alacgpu_reverb_device) ------------------------------------------------------------
 from .reverb import Reverb, reverb, reverb_host, reverb_host_f32  # noqa: E402
+
+# ---- simulated room responses behind Reverb (alacgpu_rir_shoebox_device) -----------------------------------------------------------
+from .rir import ShoeboxRooms, image_counts, rir_host, rir_host_f32, simulate_rir  # noqa: E402
 # ---- SpecAugment on the features: time warp, frequency and time masks (alacgpu_specaugment_device) -------------------------------
 from .augment import SpecAugment, spec_augment, specaugment_host, specaugment_host_f32  # noqa: E402
 from .speed import SpeedPerturb, speed_host, speed_host_f32, speed_perturb  # noqa: E402

@@ -60,6 +60,7 @@ from .vad import EnergyVad, _select_frames, _vad_energy
 from .yin import Yin, _yin
 from .pitch import PitchShift, _pitch_shift, _ratio_kinds
 from .reverb import Reverb, _reverb
+from .rir import _simulate
 from .speed import MAX_WIDTH as _SPEED_MAX_WIDTH, SpeedPerturb, ratio as _speed_ratio
 
 PAD_CFG = 0xFFFF        # a padding entry's cfg_idx: never a row of the context, so the kernels switch the entry off
@@ -705,7 +706,8 @@ class Corpus(_Closing):
         reverb: room reverberation of the waveform: a reverb.Reverb, whose draws are then made here from the device's default
         generator, or the pair (Reverb, draws) with the draws that its `draw(B)` returned.  Bit for bit reverb.reverb(the crops
         without it, the first Reverb.frames(rate) frames of the drawn responses at the rate of the crops, lengths, their
-        lengths, 0 where a crop drew none).
+        lengths, 0 where a crop drew none).  A Reverb over a rir.ShoeboxRooms: the responses are rir.simulate_rir(geometry,
+        beta of the draws, rate, Reverb.frames(rate)) instead, one channel, their lengths 0 where a room is refused.
 
         mix: noise from a second corpus into the waveform: a mix.AddNoise, whose draws are then made here from the device's
         default generator (in front of a Reverb's), or the pair (AddNoise, draws) with the draws that its `draw(B, num_frames,
@@ -865,10 +867,19 @@ class Corpus(_Closing):
             d_noise, noise_lengths = self._companion_crops(mix[0].noise, "_mix_scratch", nf, no, L, B=B, Co=Co, rate=rate,
                                                            check=check)
         if reverb is not None:
-            rf, keep = reverb[0].draw(B) if reverb[1] is None else reverb[1]
-            from_0 = torch.zeros(B, dtype=torch.int64, device=self._dev)
-            d_rir, rir_lengths = self._companion_crops(reverb[0].rirs, "_reverb_scratch", rf, from_0, reverb[0].frames(rate), B=B, Co=Co,
-                                                       rate=rate, check=check)
+            draws = reverb[0].draw(B, device=self._dev) if reverb[1] is None else reverb[1]
+            keep = draws[-1]
+            if reverb[0].rooms is not None:       # simulated rooms: one channel, computed into the same scratch
+                rooms = reverb[0].rooms
+                if draws[0].shape[0] != B:
+                    raise ValueError(f"the draws of reverb= are for {draws[0].shape[0]} crops, not {B}")
+                d_rir = self._scratch("_reverb_scratch", (B, 1, reverb[0].frames(rate)))
+                _, rir_lengths = _simulate(lambda: self._gpu, draws[0], draws[1], int(rate), reverb[0].frames(rate), rooms.taps,
+                                           rooms.max_order, rooms.sound_speed, d_rir)
+            else:
+                from_0 = torch.zeros(B, dtype=torch.int64, device=self._dev)
+                d_rir, rir_lengths = self._companion_crops(reverb[0].rirs, "_reverb_scratch", draws[0], from_0, reverb[0].frames(rate),
+                                                           B=B, Co=Co, rate=rate, check=check)
         if effects is not None and effects[1] is None:
             effects = (effects[0], effects[0].draw(B, rate, device=self._dev))
         # 3. the waveform, once: into `out`, or into the scratch the features are computed from
@@ -957,6 +968,8 @@ class Corpus(_Closing):
         import torch
 
         spec, draws = self._pair(given, stage)
+        if stage is _REVERB and spec.rooms is not None:
+            return self._rooms_given(spec, draws, dtype, rate)
         if draws is not None:
             ok = isinstance(draws, tuple) and len(draws) == stage["draws"] and all(isinstance(t, torch.Tensor) and t.dim() == 1
                                                                                    for t in draws)
@@ -975,6 +988,27 @@ class Corpus(_Closing):
             raise ValueError(f"{_NEEDS_RATE}, and {stage['they']} a rate to crop at")
         if other.channels != Co and other.channels not in (1, 2):
             raise ValueError(stage["channels"].format(n=other.channels, Co=Co))
+        return spec, draws
+
+    def _rooms_given(self, spec, draws, dtype, rate):
+        """`_second_corpus` for a Reverb over simulated rooms: the draws are (geometry float64 [B, 9], beta float32 [B, 6], keep
+        bool [B]) on the corpus's device; ValueError for anything else, for int32 crops, for crops without a rate and for a
+        policy whose smallest room is refused at that rate.  Nothing is done on the device."""
+        import torch
+
+        if draws is not None:
+            ok = isinstance(draws, tuple) and len(draws) == 3 and all(isinstance(t, torch.Tensor) for t in draws)
+            if not (ok and draws[0].dim() == 2 and draws[0].shape[1] == 9 and draws[0].dtype == torch.float64
+                    and draws[1].shape == (draws[0].shape[0], 6) and draws[1].dtype == torch.float32
+                    and draws[2].shape == (draws[0].shape[0],) and draws[2].dtype == torch.bool):
+                raise ValueError("the draws of reverb= must be the three tensors (geometry, beta, keep) of Reverb.draw")
+            if any(t.device != self._dev for t in draws):
+                raise ValueError(f"the draws of reverb= must be on {self._dev}")
+        if not _is_f32(torch, dtype):
+            raise ValueError(_REVERB["f32"])
+        if rate is None:
+            raise ValueError(f"{_NEEDS_RATE}, and the responses a rate to be computed at")
+        spec.check_rate(int(rate))
         return spec, draws
 
     def _pitch_given(self, given, dtype, rate, Co, num_frames):
@@ -1384,7 +1418,7 @@ class Corpus(_Closing):
         if mix is not None and mix[1] is None:
             mix = (mix[0], mix[0].draw(B, L, sample_rate=rate, generator=generator))
         if reverb is not None and reverb[1] is None:
-            reverb = (reverb[0], reverb[0].draw(B, generator=generator))
+            reverb = (reverb[0], reverb[0].draw(B, generator=generator, device=self._dev))
         if effects is not None and effects[1] is None:
             effects = (effects[0], effects[0].draw(B, rate, generator=generator, device=self._dev))
         if augment is not None and augment[1] is None and isinstance(features, _FEATURES):

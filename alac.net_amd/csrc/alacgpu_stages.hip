@@ -1,5 +1,5 @@
 // alacgpu_stages.hip -- C ABI of include/alacgpu.h, the stages around the decode: the crop planner, the scan with the packet
-// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the phase vocoder, the reverberation, the noise mix, the levelling, the biquad cascade, the YIN pitch estimator, the constant-Q transform, the normalisations, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
+// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the phase vocoder, the reverberation, the simulated room responses, the noise mix, the levelling, the biquad cascade, the YIN pitch estimator, the constant-Q transform, the normalisations, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
 // their own scratch; the decode path is alacgpu_api.hip.  No CPU fallback here either: every stage is its kernels.
 #include <algorithm>
 #include <cmath>
@@ -21,6 +21,7 @@
 #include "alac_cqt.h"
 #include "alac_level.h"
 #include "alac_reverb.h"
+#include "alac_rir.h"
 #include "alac_stretch.h"
 #include "alac_encode.h"
 #include "alacgpu_ctx.h"
@@ -840,6 +841,49 @@ int alacgpu_reverb_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, cons
                                  kargs, 0, stream));
     HIP_TRY(ctx, hipGetLastError());
     return ctx->reverb.release(ctx, stream);
+}
+
+int alacgpu_rir_shoebox_device(alacgpu_ctx* ctx, const void* d_geometry, const void* d_beta, uint32_t rows, uint32_t sample_rate,
+                               uint64_t frames, uint32_t taps, int32_t max_order, double sound_speed, void* d_out, uint64_t out_stride,
+                               void* d_lengths, void* hip_stream) {
+    if (!ctx || !args_ok({{d_geometry, 8}, {d_beta, 4}, {d_out, 4}, {d_lengths, 4}})) return ALACGPU_ERR_BAD_ARG;
+    if (sample_rate == 0 || sample_rate > 0x7FFFFFFFu || frames == 0 || frames > ALAC_RIR_MAX_FRAMES || frames > out_stride || taps < 3u ||
+        taps > ALAC_RIR_MAX_TAPS || taps % 2u == 0u || max_order < -1 || !(sound_speed > 0.0) || !std::isfinite(sound_speed))
+        return ALACGPU_ERR_BAD_ARG;
+    uint64_t extent, geometry_extent, beta_extent, lengths_extent;
+    if (!planes_extent(rows, out_stride, frames, extent) || !planes_extent(rows, 18u, 18u, geometry_extent) ||
+        !planes_extent(rows, 6u, 6u, beta_extent) || !planes_extent(rows, 1u, 1u, lengths_extent))
+        return ALACGPU_ERR_BAD_ARG;
+    if (!apart(d_geometry, geometry_extent, d_out, extent) || !apart(d_beta, beta_extent, d_out, extent) ||
+        !apart(d_lengths, lengths_extent, d_out, extent) || !apart(d_lengths, lengths_extent, d_geometry, geometry_extent) ||
+        !apart(d_lengths, lengths_extent, d_beta, beta_extent))
+        return ALACGPU_ERR_BAD_ARG;
+    const uint64_t tiles = (frames + ALAC_RIR_TILE - 1u) / ALAC_RIR_TILE;
+    if (tiles * std::max<uint64_t>(rows, 1u) > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    alac_rir_params p = {};
+    p.geometry = (const double*)d_geometry;
+    p.beta = (const float*)d_beta;
+    p.out = (float*)d_out;
+    p.lengths = (int32_t*)d_lengths;
+    p.out_stride = out_stride;
+    p.frames = (uint32_t)frames;
+    p.taps = taps;
+    p.tiles = (uint32_t)tiles;
+    p.max_order = max_order;
+    p.scale = (double)sample_rate / sound_speed;
+    p.tw = (float)(2.0 * 3.14159265358979323846 / (double)taps);
+    for (uint32_t j = 0; j <= taps / 2u; j++) {      // the window's table, in double and rounded once (rir.window_table)
+        const double a = 2.0 * 3.14159265358979323846 * (double)j / (double)taps;
+        p.cw[j] = (float)std::cos(a);
+        p.sw[j] = (float)std::sin(a);
+    }
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel((const void*)alac_rir_shoebox_kernel, dim3((uint32_t)(tiles * rows)), dim3(ALAC_RIR_THREADS), kargs, 0,
+                                 (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
 }
 
 int alacgpu_mix_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, const void* d_noise, uint32_t rows, uint32_t channels,

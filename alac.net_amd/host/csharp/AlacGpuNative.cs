@@ -215,6 +215,13 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_reverb_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, IntPtr dRir, uint rows,
             uint channels, uint rirChannels, ulong stride, ulong rirStride, ulong frames, ulong rirFrames, IntPtr dValid,
             IntPtr dRirValid, IntPtr hipStream);
+        /// <summary>Image-source impulse responses of shoebox rooms in device memory (dGeometry double[rows, 9]: room, source
+        /// and microphone in metres; dBeta float[rows, 6]: the walls' reflection coefficients; dOut float[rows, outStride] of
+        /// which the first frames of a row are written; dLengths int[rows]: frames, or 0 where the row is refused and zeros).
+        /// maxOrder -1 takes every reflection order.  One launch, asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_rir_shoebox_device(IntPtr ctx, IntPtr dGeometry, IntPtr dBeta, uint rows,
+            uint sampleRate, ulong frames, uint taps, int maxOrder, double soundSpeed, IntPtr dOut, ulong outStride,
+            IntPtr dLengths, IntPtr hipStream);
         /// <summary>Time stretch of planar float crops in device memory with the pitch kept, a phase vocoder (dSrc [rows,
         /// channels, srcStride] of which the first frames are data, dOut [rows, channels, outStride] apart from it, of which
         /// the first outFrames are written): row r is stretched by dP[r] / dQ[r] (int[rows]) over its first dValid[r] frames

@@ -80,8 +80,10 @@ def twiddles():
 
 
 class Reverb(_Spec):
-    """Room reverberation from a corpus of impulse responses, for `Corpus.crops(reverb=)` and `Corpus.random_crops(reverb=)`.
-    rirs: an open `Corpus` on the device of the corpus whose crops it reverberates; its rate or rates and its channel count
+    """Room reverberation from a corpus of impulse responses or from simulated rooms, for `Corpus.crops(reverb=)` and
+    `Corpus.random_crops(reverb=)`.  rirs: a `rir.ShoeboxRooms` -- every crop then gets the image-source response of a room
+    drawn for it, one channel, max_seconds long (`rooms` is that policy, else None); a policy whose smallest room holds more
+    than rir.LIMIT candidate images within max_seconds is refused here, and again at the crops' rate --, or an open `Corpus` on the device of the corpus whose crops it reverberates; its rate or rates and its channel count
     (1 or 2) may differ: the first max_seconds of the drawn file are taken at the rate of the crops, and as one channel when
     its channel count is not theirs.  p in 0 .. 1: the probability that a crop is reverberated at all.  max_seconds: a
     positive number.  Immutable.  ValueError otherwise."""
@@ -91,12 +93,16 @@ class Reverb(_Spec):
     def __init__(self, rirs, p=1.0, max_seconds=1.0):
         from .corpus import Corpus
 
+        from .rir import ShoeboxRooms
+
         s = object.__setattr__
-        if not isinstance(rirs, Corpus):
-            raise ValueError(f"rirs must be a Corpus, not {rirs!r}")
-        if getattr(rirs, "_gpu", None) is None:
+        if isinstance(rirs, ShoeboxRooms):
+            pass
+        elif not isinstance(rirs, Corpus):
+            raise ValueError(f"rirs must be a Corpus or a ShoeboxRooms, not {rirs!r}")
+        elif getattr(rirs, "_gpu", None) is None:
             raise ValueError("the corpus of impulse responses is closed")
-        if rirs.channels not in (1, 2):
+        elif rirs.channels not in (1, 2):
             raise ValueError(f"a corpus of impulse responses has 1 or 2 channels, not {rirs.channels}")
         p = _f32_finite("p", p)
         if not 0.0 <= p <= 1.0:
@@ -104,16 +110,45 @@ class Reverb(_Spec):
         max_seconds = _f32_finite("max_seconds", max_seconds)
         if not max_seconds > 0.0:
             raise ValueError(f"max_seconds must be positive, not {max_seconds!r}")
+        if isinstance(rirs, ShoeboxRooms):
+            from .rir import LIMIT, box_candidates
+
+            most = box_candidates(rirs.smallest(), max_seconds, rirs.sound_speed)
+            if most > LIMIT and rirs.max_order is None:
+                raise ValueError(f"the smallest room {rirs.smallest()!r} of {rirs!r} has {most:.3g} candidate images within "
+                                 f"{max_seconds!r} s, more than {LIMIT}: every such row would be refused")
         s(self, "rirs", rirs)
         s(self, "p", p)
         s(self, "max_seconds", max_seconds)
+
+    @property
+    def rooms(self):
+        """The ShoeboxRooms of a Reverb over simulated rooms, else None"""
+        from .rir import ShoeboxRooms
+
+        return self.rirs if isinstance(self.rirs, ShoeboxRooms) else None
+
+    def check_rate(self, sample_rate):
+        """ValueError where the smallest room of a Reverb over rooms is refused at `sample_rate`; nothing for a Corpus"""
+        rooms = self.rooms
+        if rooms is not None:
+            from .rir import LIMIT, candidate_box
+
+            low = rooms.smallest()
+            geom = np.array(low + tuple(0.5 * v for v in low) * 2, dtype=np.float64)
+            if candidate_box(geom, float(sample_rate) / rooms.sound_speed, self.frames(sample_rate), rooms.taps // 2,
+                             -1 if rooms.max_order is None else rooms.max_order) is None:
+                raise ValueError(f"the smallest room {low!r} of {rooms!r} has more than {LIMIT} candidate images in "
+                                 f"{self.frames(sample_rate)} frames at {sample_rate} Hz: every such row would be refused")
 
     def frames(self, sample_rate):
         """K: the frames of a response at sample_rate, max(1, round(max_seconds * sample_rate))"""
         return max(1, int(round(self.max_seconds * sample_rate)))
 
-    def draw(self, batch, generator=None):
-        """The draws of `batch` crops as device tensors: (rir_files int64 [B], keep bool [B], False where the crop is not
+    def draw(self, batch, generator=None, device=None):
+        """The draws of `batch` crops as device tensors.  Over rooms: (geometry float64 [B, 9], beta float32 [B, 6], keep bool
+        [B]) on `device` (which only this kind needs): the four draws of `ShoeboxRooms.draw` first, then rand float64 k, keep
+        where k < p.  Over a corpus: (rir_files int64 [B], keep bool [B], False where the crop is not
         reverberated).  Two draws of B values, always in this order, whatever p is, so that a seeded generator reproduces
         them: the files (randint, uniform over the corpus of responses), then rand float64 k, keep where k < p.  generator:
         a torch.Generator of the corpus's device or of the CPU (the draws are then made there and uploaded); default: the
@@ -123,6 +158,14 @@ class Reverb(_Spec):
         from . import _frame_count
 
         rirs = self.rirs
+        if self.rooms is not None:
+            B = _frame_count("batch", batch)
+            if device is None:
+                raise ValueError("the draws of a Reverb over rooms need device=")
+            geometry, beta = rirs.draw(B, generator=generator, device=device)
+            dev = generator.device if generator is not None else device
+            keep = (torch.rand(B, generator=generator, device=dev, dtype=torch.float64) < self.p).to(device)
+            return geometry, beta, keep
         if rirs._gpu is None:
             raise ValueError("the corpus of impulse responses is closed")
         if rirs.num_files == 0:

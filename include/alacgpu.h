@@ -928,6 +928,32 @@ int alacgpu_reverb_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, cons
                           const void* d_valid, const void* d_rir_valid, void* hip_stream);
 
 /*
+ * alacgpu_rir_shoebox_device: room impulse responses of shoebox rooms by the image-source method, what alacgpu_reverb_device
+ * convolves a crop with where there is no recorded response (no counterpart in the reference); one launch, no atomics, no
+ * scratch, nothing read back, the same inputs give the same bits.  d_geometry float64 [rows, 9]: the room (Lx, Ly, Lz), the
+ * source and the microphone in metres; d_beta float32 [rows, 6]: the reflection coefficients of the walls at 0 and at L_a of
+ * the axes x, y, z; d_out float32 [rows, out_stride] of which the first `frames` of a row are written; d_lengths int32 [rows].
+ * Image (n, p), n in Z^3, p in {0, 1}^3, has the coordinate (1 - 2 p_a) s_a + 2 n_a L_a - r_a on axis a, the distance d, the
+ * delay tau = d sample_rate / sound_speed, the order sum |2 n_a - p_a| and the amplitude
+ * A = prod beta[a][0]^|n_a - p_a| beta[a][1]^|n_a| / (4 pi d), and
+ *   h[k] = sum over the images with |k - tau| < taps / 2 of A * 0.5 (1 + cos(2 pi t / taps)) * sinc(t),  t = k - tau,  k < frames
+ * in ascending (nx, ny, nz, 4 px + 2 py + pz); max_order -1 takes every order, else only images of an order up to it.
+ * d_lengths[r] = frames.  A row is refused -- zeros, d_lengths[r] = 0, which alacgpu_reverb_device leaves alone -- where one of
+ * its nine numbers is not finite, a dimension is not positive, the source or the microphone lies outside the room, or the
+ * candidate box 8 (2 Nx + 1)(2 Ny + 1)(2 Nz + 1), N_a = floor((frames + taps) / (sample_rate / sound_speed) / (2 L_a)) + 2 (with
+ * max_order at most (max_order + 1) / 2), exceeds 2^25 or a quotient 2^20: decided in the kernel.  An image at d == 0 gives an
+ * infinity.  The geometry of an image is float64, a tap's arithmetic float32 from explicit polynomials, every operation rounded
+ * once, none fused; csrc/alac_rir.h states the scheme, alac.net_amd/rir.py every operation and the derived bound.  Device
+ * pointers only, asynchronous on hip_stream.  rows == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx or array, a misaligned array (8 for d_geometry, 4), sample_rate 0
+ * or above 2^31 - 1, frames 0, above 2^20 or above out_stride, taps even or outside 3 .. 127, max_order below -1, a sound_speed
+ * that is not positive and finite, arrays that overlap d_out or d_lengths, 2^31 workgroups or more.
+ */
+int alacgpu_rir_shoebox_device(alacgpu_ctx* ctx, const void* d_geometry, const void* d_beta, uint32_t rows, uint32_t sample_rate,
+                               uint64_t frames, uint32_t taps, int32_t max_order, double sound_speed, void* d_out, uint64_t out_stride,
+                               void* d_lengths, void* hip_stream);
+
+/*
  * alacgpu_time_stretch_device: time stretch of the crops with the pitch kept, a phase vocoder (no counterpart in the reference;
  * the specification is torchaudio's phase_vocoder with the STFT and iSTFT around it); three launches, no atomics, nothing read
  * back, the same inputs give the same bits.  Followed by alacgpu_resample_ratio_rows_device at the same ratio it is a pitch

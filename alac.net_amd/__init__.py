@@ -87,6 +87,8 @@ SYMBOLS = {
                                                C.c_float, C.c_int, _VP]),
     "alacgpu_normalize_sliding_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, C.c_uint32,
                                                    C.c_uint32, C.c_int, C.c_int, _VP]),
+    "alacgpu_pcen_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, C.c_float, C.c_float, C.c_float,
+                                      C.c_float, C.c_float, C.c_float, C.c_float, _VP, C.c_uint32, C.c_int, _VP]),
     "alacgpu_vad_energy_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, _VP, C.c_float, C.c_float,
                                             C.c_uint32, C.c_float, _VP, C.c_uint64, _VP]),
     "alacgpu_select_frames_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, _VP, C.c_uint64,
@@ -505,6 +507,20 @@ class AlacGpuContext(_Closing):
         rc = lib().alacgpu_normalize_sliding_device(self._ctx, _dp(d_src), _dp(d_out), rows, lines_per_row, line_stride, line_len,
                                                     _dp(d_valid), window, min_window, int(bool(center)), int(bool(norm_vars)),
                                                     _VP(stream))
+        _check(rc, self._ctx)
+
+    def pcen_device(self, d_src, d_out, rows, lines_per_row, line_stride, line_len, d_valid, b, gain, bias, power, bias_pow, eps, scale,
+                    d_table=None, lines_per_param=0, stage=0, stream=0):
+        """alacgpu_pcen_device: per-channel energy normalisation of every line of d_src (float32 device tensor
+        [rows, lines_per_row, line_stride], the first line_len of a line are frames) over its first v = min(max(d_valid[row],
+        0), line_len) frames: s = scale * x, M the first-order smoothing of s with coefficient b from M[0] = s[0], and
+        (s / (eps + M)^gain + bias)^power - bias_pow; zeros behind v up to line_len, into d_out (d_src itself or the same
+        layout apart from it).  bias_pow: bias^power from float64.  d_table: None, or a float32 device tensor
+        [5, lines_per_param] with b, gain, bias, power and bias^power of line % lines_per_param, in place of the five scalars.
+        stage 1 writes M.  d_valid: an int64 device tensor [rows], or None for whole lines.  pcen.py states the arithmetic.
+        One launch, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_pcen_device(self._ctx, _dp(d_src), _dp(d_out), rows, lines_per_row, line_stride, line_len, _dp(d_valid), b,
+                                       gain, bias, power, bias_pow, eps, scale, _dp(d_table), lines_per_param, stage, _VP(stream))
         _check(rc, self._ctx)
 
     def vad_energy_device(self, d_src, rows, row_stride, line, line_len, d_valid, energy_threshold, energy_mean_scale, frames_context,
@@ -1232,6 +1248,8 @@ from .normalize import MeanVar, TopDb, normalize, normalize_host, normalize_host
 # ---- Kaldi's sliding-window CMVN, a third kind of normalize's `how` (alacgpu_normalize_sliding_device), and the energy VAD with
 # ---- the selection of the voiced frames (alacgpu_vad_energy_device, alacgpu_select_frames_device) ---------------------------------
 from .sliding import SlidingMeanVar, sliding_host, sliding_host_f32, sliding_windows  # noqa: E402
+# ---- per-channel energy normalisation, a fourth kind of normalize's `how` (alacgpu_pcen_device) --------------------------------------
+from .pcen import Pcen, pcen, pcen_host, pcen_host_f32, pcen_smoother_host, pcen_smoother_host_f32  # noqa: E402
 from .vad import EnergyVad, select_frames, select_host, vad_energy, vad_host, vad_host_f32  # noqa: E402
 # ---- noise at a target signal-to-noise ratio into crops and tensors (alacgpu_mix_device) ----------------------------------------
 from .mix import AddNoise, mix, mix_host, mix_host_f32  # noqa: E402

@@ -22,7 +22,7 @@ that lists them: the refusals of all of them, the crops the second corpora make 
 AddNoise, then the impulse responses of a Reverb, each cropped by its own corpus at the rate of the crops), the waveform once
 (`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_level_device, alacgpu_biquad_device, alacgpu_yin_device (beside the waveform: it writes a track of its own), alacgpu_logmel_device (or alacgpu_fbank_device or alacgpu_mfcc_device), alacgpu_deltas_device,
 alacgpu_vad_energy_device, the normalisation, alacgpu_select_frames_device and alacgpu_specaugment_device (reverb.py, mix.py,
-level.py, biquad.py, yin.py, features.py, deltas.py, vad.py, normalize.py, sliding.py and augment.py state the arithmetic), each only if asked for.
+level.py, biquad.py, yin.py, features.py, deltas.py, vad.py, normalize.py, sliding.py, pcen.py and augment.py state the arithmetic), each only if asked for.
 
 `crops(..., speed=)` plays every crop at a drawn factor in front of all that (the same method, speed.py): the step of a corpus
 whose rates differ, with a ratio per (file rate, factor) in place of one per file rate; the crops at factor 1 go through the
@@ -55,6 +55,7 @@ from .mfcc import KaldiMfcc
 from .features import LogMel
 from .mix import AddNoise, _mix, snr_ratio
 from .normalize import MeanVar, TopDb, _normalize
+from .pcen import Pcen
 from .sliding import LDS_MAX as _SLIDING_LDS_MAX, RING_WINDOW_MAX as _SLIDING_RING_WINDOW_MAX, SlidingMeanVar
 from .vad import EnergyVad, _select_frames, _vad_energy
 from .yin import Yin, _yin
@@ -764,10 +765,14 @@ class Corpus(_Closing):
 
         normalize: a normalize.MeanVar -- every line over its valid elements: lengths for PCM, feat_lengths for features, so a
         crop outside the corpus is zeros --, a normalize.TopDb -- every crop of features, or every channel of it with
-        per_channel -- or a sliding.SlidingMeanVar: Kaldi's sliding-window CMVN of every line.  Bit for bit
+        per_channel --, a sliding.SlidingMeanVar: Kaldi's sliding-window CMVN of every line, or a pcen.Pcen: per-channel energy
+        normalisation of every line of mel or constant-Q energies over its feat_lengths frames, in place of the logarithm (one
+        launch between the feature kernel and the selection and augment).  Bit for bit
         normalize.normalize(what the call returns without it, normalize, lengths).  ValueError: a TopDb without features, a
         MeanVar or a SlidingMeanVar with int32 crops, a SlidingMeanVar of a window above 7648 on lines of more than 16384
-        elements.
+        elements; a Pcen without features=, with features that are not energies (a LogMel or a ConstantQ whose log is not
+        None, a KaldiFbank with log=True, any KaldiMfcc), with deltas=, or with per-bin sequences of another length than the
+        features have lines.
 
         augment: SpecAugment on the features, the last stage: an augment.SpecAugment, whose draws are then made here from the
         device's default generator (behind an AddNoise's and a Reverb's; with vad= for the voiced counts), or the pair (SpecAugment, draws) with the three
@@ -795,8 +800,19 @@ class Corpus(_Closing):
         if f0 is not None:
             self._f0_given(f0, dtype, rate, vad, num_frames)
         if normalize is not None:
-            if not isinstance(normalize, (MeanVar, TopDb, SlidingMeanVar)):
-                raise ValueError(f"normalize must be a normalize.MeanVar, a normalize.TopDb or a sliding.SlidingMeanVar, not {normalize!r}")
+            if not isinstance(normalize, (MeanVar, TopDb, SlidingMeanVar, Pcen)):
+                raise ValueError(f"normalize must be a normalize.MeanVar, a normalize.TopDb, a sliding.SlidingMeanVar or a pcen.Pcen, "
+                                 f"not {normalize!r}")
+            if isinstance(normalize, Pcen):
+                if features is None:
+                    raise ValueError("a Pcen compresses mel or constant-Q energies: it needs features=")
+                if isinstance(features, KaldiMfcc) or (isinstance(features, _FEATURES) and features.log not in (None, False)):
+                    raise ValueError(f"a Pcen compresses energies: features with log=None (a LogMel, a ConstantQ) or log=False "
+                                     f"(a KaldiFbank), not {features!r}")
+                if deltas is not None:
+                    raise ValueError("a Pcen compresses energies: deltas= of them are none")
+                if normalize.lines is not None and isinstance(features, _FEATURES) and normalize.lines != features.n_mels:
+                    raise ValueError(f"a Pcen with {normalize.lines} values per parameter, features with {features.n_mels} lines")
             if features is None and isinstance(normalize, TopDb):
                 raise ValueError("a TopDb clamps log-mel features: it needs features=")
             if features is None and not _is_f32(torch, dtype):

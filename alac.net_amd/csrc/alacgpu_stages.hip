@@ -1,5 +1,5 @@
 // alacgpu_stages.hip -- C ABI of include/alacgpu.h, the stages around the decode: the crop planner, the scan with the packet
-// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the phase vocoder, the reverberation, the simulated room responses, the noise mix, the levelling, the biquad cascade, the YIN pitch estimator, the constant-Q transform, the normalisations, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
+// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the phase vocoder, the reverberation, the simulated room responses, the noise mix, the levelling, the biquad cascade, the YIN pitch estimator, the constant-Q transform, the normalisations, the per-channel energy normalisation, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
 // their own scratch; the decode path is alacgpu_api.hip.  No CPU fallback here either: every stage is its kernels.
 #include <algorithm>
 #include <cmath>
@@ -13,6 +13,7 @@
 #include "alac_deltas.h"
 #include "alac_normalize.h"
 #include "alac_sliding.h"
+#include "alac_pcen.h"
 #include "alac_vad.h"
 #include "alac_augment.h"
 #include "alac_mix.h"
@@ -650,6 +651,52 @@ int alacgpu_normalize_sliding_device(alacgpu_ctx* ctx, const void* d_src, void* 
     p.ring = alac_sliding_ring(line_len);
     void* kargs[] = {&p};
     HIP_TRY(ctx, hipLaunchKernel(kernel, dim3((uint32_t)grid), dim3(wave ? ALAC_SLIDING_WAVE_THREADS : ALAC_SLIDING_LINE_THREADS), kargs, lds,
+                                 (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
+}
+
+int alacgpu_pcen_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t lines_per_row, uint64_t line_stride,
+                        uint64_t line_len, const void* d_valid, float b, float gain, float bias, float power, float bias_pow, float eps,
+                        float scale, const void* d_table, uint32_t lines_per_param, int stage, void* hip_stream) {
+    uint64_t lines;
+    if (!normalize_args_ok(ctx, d_src, d_out, rows, lines_per_row, line_stride, line_len, lines) ||
+        !args_ok({{d_valid, 8, false}, {d_table, 4, false}}))
+        return ALACGPU_ERR_BAD_ARG;
+    if (stage != 0 && stage != 1) return ALACGPU_ERR_BAD_ARG;
+    if (!(eps > 0.0f) || !std::isfinite(eps) || !(scale > 0.0f) || !std::isfinite(scale)) return ALACGPU_ERR_BAD_ARG;
+    if (d_table) {
+        if (lines_per_param == 0 || lines_per_row % lines_per_param != 0) return ALACGPU_ERR_BAD_ARG;
+    } else if (!(b > 0.0f && b <= 1.0f) || !(gain >= 0.0f) || !std::isfinite(gain) || !(bias >= 0.0f) || !std::isfinite(bias) ||
+               !(power > 0.0f) || !std::isfinite(power) || !(bias_pow >= 0.0f) || !std::isfinite(bias_pow)) {
+        return ALACGPU_ERR_BAD_ARG;
+    }
+    const uint64_t grid = alac_pcen_grid(lines, line_len);
+    if (grid > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool wave = line_len <= ALAC_PCEN_WAVE_MAX;
+    const void* const kernel = wave ? (const void*)alac_pcen_wave_kernel : (const void*)alac_pcen_line_kernel;
+    alac_pcen_params p;
+    p.src = (const float*)d_src;
+    p.out = (float*)d_out;
+    p.valid = (const int64_t*)d_valid;
+    p.table = (const float*)d_table;
+    p.lines = lines;
+    p.lines_per_row = lines_per_row;
+    p.lines_per_param = d_table ? lines_per_param : 1u;
+    p.line_stride = line_stride;
+    p.line_len = line_len;
+    p.b = b;
+    p.gain = gain;
+    p.bias = bias;
+    p.power = power;
+    p.bias_pow = bias_pow;
+    p.eps = eps;
+    p.scale = scale;
+    p.stage = (uint32_t)stage;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel(kernel, dim3((uint32_t)grid), dim3(wave ? ALAC_PCEN_WAVE_THREADS : ALAC_PCEN_LINE_THREADS), kargs, 0,
                                  (hipStream_t)hip_stream));
     HIP_TRY(ctx, hipGetLastError());
     return ALACGPU_OK;

@@ -150,6 +150,14 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_normalize_sliding_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, uint rows,
             uint linesPerRow, ulong lineStride, ulong lineLen, IntPtr dValid, uint window, uint minWindow, int center, int normVars,
             IntPtr hipStream);
+        /// <summary>Per-channel energy normalisation per line of the same layout over the first min(max(dValid[row], 0), lineLen)
+        /// frames: s = scale * x, M the first-order smoothing of s with coefficient b from M[0] = s[0], (s / (eps + M)^gain +
+        /// bias)^power - biasPow; zeros behind them, into dOut (dSrc itself or the same layout).  biasPow: bias^power.  dTable:
+        /// IntPtr.Zero or float[5, linesPerParam] with b, gain, bias, power and bias^power per line % linesPerParam.  stage 1
+        /// writes M.  One launch, asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_pcen_device(IntPtr ctx, IntPtr dSrc, IntPtr dOut, uint rows,
+            uint linesPerRow, ulong lineStride, ulong lineLen, IntPtr dValid, float b, float gain, float bias, float power,
+            float biasPow, float eps, float scale, IntPtr dTable, uint linesPerParam, int stage, IntPtr hipStream);
         /// <summary>Kaldi's energy VAD on the lineLen floats at dSrc + row * rowStride + line of every row, over the first
         /// min(max(dValid[row], 0), lineLen) of them: a frame is voiced (1 in dMask, byte[rows, maskStride]; 0 otherwise and behind
         /// the length) when at least proportionThreshold of the frames within framesContext of it are above energyThreshold +

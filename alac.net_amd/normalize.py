@@ -52,11 +52,15 @@ mx = +inf gives c = +inf, and inf - inf = NaN with relative.
 A third kind of `how` is sliding.SlidingMeanVar, Kaldi's sliding-window CMVN (alacgpu_normalize_sliding_device): sliding.py
 states it, and `normalize_host`, `normalize_host_f32` and `normalize` take it by handing it on.
 
+A fourth kind is pcen.Pcen, per-channel energy normalisation of mel or constant-Q energies (alacgpu_pcen_device), the one
+kind that is a recurrence along time: pcen.py states it, and the same three calls take it by handing it on.
+
 `MeanVar`, `TopDb`, `normalize_host` and `normalize_host_f32` need no device.  `normalize` is the call on device tensors.
 """
 import numpy as np
 
 from ._stageargs import _device_context, _f32_finite, _lengths_device, _lines, _Spec
+from .pcen import Pcen, _launch as _pcen_launch, pcen_host, pcen_host_f32
 from .sliding import LDS_MAX as _SLIDING_LDS_MAX, RING_WINDOW_MAX as _SLIDING_RING_WINDOW_MAX, SlidingMeanVar, sliding_host, sliding_host_f32
 
 _U = 2.0 ** -24
@@ -131,9 +135,11 @@ def normalize_host(x, how, lengths=None, bound=False):
     """The specification in numpy: x float32 [B, ..., n] to float64 of that shape -- float64 arithmetic on the float32 input
     and the float32 values of `how`'s parameters.  lengths: [B] integers, MeanVar's (ignored by TopDb).  bound=True: returns
     (y, dY), dY float64 like y: how far a float32 evaluation may be from y (the module docstring's chain).  A SlidingMeanVar:
-    sliding.sliding_host."""
+    sliding.sliding_host.  A Pcen: pcen.pcen_host."""
     if isinstance(how, SlidingMeanVar):
         return sliding_host(x, how, lengths, bound)
+    if isinstance(how, Pcen):
+        return pcen_host(x, how, lengths, bound)
     x, v = _host_args(x, how, lengths)
     shape = x.shape
     B, n = shape[0], shape[-1]
@@ -210,9 +216,11 @@ def normalize_host_f32(x, how, lengths=None):
     MeanVar: the sums in the kernel's documented order (the number of partial sums follows n, as the kernel's mapping does).
     TopDb: the four lines of the module docstring.  Its distance from `normalize_host` is what a correct float32 evaluation
     costs: the tests hold the kernel to a small multiple of that.  A SlidingMeanVar: sliding.sliding_host_f32, the kernel bit
-    for bit."""
+    for bit.  A Pcen: pcen.pcen_host_f32, the kernel bit for bit."""
     if isinstance(how, SlidingMeanVar):
         return sliding_host_f32(x, how, lengths)
+    if isinstance(how, Pcen):
+        return pcen_host_f32(x, how, lengths)
     x, v = _host_args(x, how, lengths)
     f32 = np.float32
     shape = x.shape
@@ -255,13 +263,16 @@ def _normalize(ctx, x, how, lengths, out):
     """`normalize`; ctx() gives the context that runs it (the corpus's own inside `Corpus.crops`), asked for behind the checks"""
     import torch
 
-    if not isinstance(how, (MeanVar, TopDb, SlidingMeanVar)):
-        raise ValueError(f"how must be a MeanVar, a TopDb or a SlidingMeanVar, not {how!r}")
+    if not isinstance(how, (MeanVar, TopDb, SlidingMeanVar, Pcen)):
+        raise ValueError(f"how must be a MeanVar, a TopDb, a SlidingMeanVar or a Pcen, not {how!r}")
     if not isinstance(x, torch.Tensor) or x.device.type != "cuda" or x.dtype != torch.float32 or x.dim() < 2:
         raise ValueError("x must be a float32 device tensor [B, ..., n]")
     top = isinstance(how, TopDb)
     if top and how.per_channel and x.dim() < 3:
         raise ValueError("per_channel needs x [B, C, ..., n]")
+    pcen = isinstance(how, Pcen)
+    if pcen and how.lines is not None and (x.dim() != 4 or x.shape[2] != how.lines):
+        raise ValueError(f"a Pcen with {how.lines} values per parameter needs x [B, C, {how.lines}, n], not {tuple(x.shape)}")
     layout = _lines(x) if x.numel() else (max(x.shape[-1], 1), x.shape[-1])
     if layout is None:
         raise ValueError("x must be contiguous or the slice [..., :n] of a contiguous tensor")
@@ -282,7 +293,9 @@ def _normalize(ctx, x, how, lengths, out):
     lines_per_row = x.numel() // n // rows
     with torch.cuda.device(x.device):
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        if sliding:
+        if pcen:
+            _pcen_launch(ctx(), x, out, rows, lines_per_row, S, n, d_valid, how, stream)
+        elif sliding:
             ctx().normalize_sliding_device(x, out, rows, lines_per_row, S, n, d_valid, how.window, how.min_window, how.center,
                                            how.norm_vars, stream=stream)
         elif top:
@@ -297,11 +310,12 @@ def normalize(x, how, lengths=None, out=None):
     (Whisper drops the last frame: normalize(feats[..., :-1], TopDb.whisper())); what lies behind the slice is neither read
     nor written.  how: a `MeanVar` -- every line x[b, ..., :] over its first lengths[b] elements, zeros behind them --, a
     `TopDb` -- every row x[b], or x[b, c] with per_channel, against its own maximum -- or a sliding.SlidingMeanVar -- every frame
-    of a line against the window around or behind it, zeros behind lengths[b].  lengths: [B] integers, a sequence or a
+    of a line against the window around or behind it, zeros behind lengths[b] -- or a pcen.Pcen -- per-channel energy
+    normalisation of every line of energies, zeros behind lengths[b]; one with per-bin sequences needs x [B, C, L, n].  lengths: [B] integers, a sequence or a
     tensor (as `crops` returns them; -1 counts as 0, more than n as n), not used by TopDb; default: whole lines.  out: x
     itself (in place) or a tensor of x's shape and layout; default: a new one of x's layout.  Returns out.  One launch
-    (MeanVar, SlidingMeanVar) or two (TopDb), asynchronous on the current stream; ValueError before any device work."""
+    (MeanVar, SlidingMeanVar, Pcen) or two (TopDb), asynchronous on the current stream; ValueError before any device work."""
     ctx = _device_context("x", x, "[B, ..., n]")
-    if not isinstance(how, (MeanVar, TopDb, SlidingMeanVar)):
-        raise ValueError(f"how must be a MeanVar, a TopDb or a SlidingMeanVar, not {how!r}")
+    if not isinstance(how, (MeanVar, TopDb, SlidingMeanVar, Pcen)):
+        raise ValueError(f"how must be a MeanVar, a TopDb, a SlidingMeanVar or a Pcen, not {how!r}")
     return _normalize(ctx, x, how, lengths, out)

@@ -671,6 +671,39 @@ int alacgpu_normalize_sliding_device(alacgpu_ctx* ctx, const void* d_src, void* 
                                      uint32_t min_window, int center, int norm_vars, void* hip_stream);
 
 /*
+ * alacgpu_pcen_device: per-channel energy normalisation of mel or constant-Q energies (Wang et al. 2017, librosa.pcen; no
+ * counterpart in the reference), one launch.  The layout and the in-place rule are alacgpu_normalize_meanvar_device's: float32
+ * [rows, lines_per_row, line_stride], the first line_len of a line are frames, d_out is d_src itself or an array of that layout
+ * apart from it.  For line l of row r, v = min(max(d_valid[r], 0), line_len) (d_valid: int64 [rows]; NULL: v = line_len):
+ *   s[t] = scale * x[t]
+ *   M[0] = s[0];  M[t] = (1 - b) M[t - 1] + b s[t]                            0 < t < v
+ *   y[t] = (s[t] / (eps + M[t])^gain + bias)^power - bias^power                 t < v
+ *   y[t] = 0                                                                    v <= t < line_len
+ * M[0] = s[0] is the steady state librosa.pcen starts from.  stage 1 writes M instead of y.  bias_pow is bias^power, computed in
+ * float64 and rounded once by the caller.  d_table: NULL, and b, gain, bias, power and bias_pow hold for every line; or float32
+ * [5, lines_per_param] -- the rows b, gain, bias, power, bias^power --, and line l takes column l % lines_per_param (the
+ * per-bin values of a trained front end; lines_per_param divides lines_per_row), the five scalars are then ignored.
+ * The float32 arithmetic, one IEEE operation at a time, nothing contracted: the smoother is a blocked scan -- a lane takes 4
+ * consecutive frames, a wave scans its 64 affine maps (A, B), A = a^k by repeated multiplication, with __shfl_up, a carry goes
+ * from a pass to the next -- in the order csrc/alac_pcen.h states, and x^gain and w^power are exp2(gain log2 x) from two explicit
+ * polynomials of that header, so that alac.net_amd/pcen.py's twin is the kernel bit for bit; that module derives the error bound.
+ * A NaN or an infinity at t0 < v reaches the frames t0 .. v - 1 of its own line, one at or behind v nothing; v = 0 (d_valid[r] =
+ * -1 included) writes a line of zeros and reads nothing.  Lines of up to 1024 frames are taken by a wave each, four to a
+ * workgroup; longer ones by a workgroup of 256 threads each; no line length is refused.  Nothing of the ctx is used but its
+ * device, there is no ctx scratch and no atomic: calls on different streams are independent.  Device pointers only,
+ * asynchronous on hip_stream, nothing is read back.  rows == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx, d_src or d_out, a misaligned array (4; 8 for d_valid),
+ * lines_per_row 0, line_len 0 or above line_stride, d_src and d_out that overlap without being equal, an extent of 2^60 bytes
+ * or more, 2^31 workgroups or more; a stage other than 0 and 1; eps or scale not above 0 or not finite; without d_table: b outside
+ * (0, 1], gain, bias or bias_pow below 0, power not above 0, any of them not finite; with d_table: lines_per_param 0 or not a
+ * divisor of lines_per_row.
+ */
+int alacgpu_pcen_device(alacgpu_ctx* ctx, const void* d_src, void* d_out, uint32_t rows, uint32_t lines_per_row,
+                        uint64_t line_stride, uint64_t line_len, const void* d_valid, float b, float gain, float bias, float power,
+                        float bias_pow, float eps, float scale, const void* d_table, uint32_t lines_per_param, int stage,
+                        void* hip_stream);
+
+/*
  * The energy VAD of the Kaldi speaker recipes on one feature line (compute-vad-decision) and the selection of the voiced
  * frames (select-voiced-frames); no counterpart in the reference, one launch each.  The parity is with this specification,
  * Kaldi's ComputeVadEnergy restated.  Both: device pointers only, asynchronous on hip_stream, nothing is read back, nothing of

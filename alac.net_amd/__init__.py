@@ -101,6 +101,9 @@ SYMBOLS = {
                                        C.c_double, C.c_double, C.c_int, _VP, _VP, _VP, _VP]),
     "alacgpu_yin_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _VP, C.c_uint64, _VP]),
+    "alacgpu_pyin_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _VP, _VP, _VP, _VP,
+                                      _VP, _VP, C.c_uint64, C.c_int, _VP]),
     "alacgpu_cqt_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _VP, _VP, _VP,
                                      C.c_int, C.c_int, C.c_float, _VP, C.c_uint64, _VP]),
     "alacgpu_reverb_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
@@ -595,6 +598,23 @@ class AlacGpuContext(_Closing):
         the arithmetic.  One launch, asynchronous on `stream` (raw hipStream_t); nothing is read back."""
         rc = lib().alacgpu_yin_device(self._ctx, _dp(d_src), rows, channels, stride, frames, _dp(d_valid), sample_rate, win_length, hop,
                                       tau_min, tau_max, align_length, float(threshold), _dp(d_out), out_frames, _VP(stream))
+        _check(rc, self._ctx)
+
+    def pyin_device(self, d_src, rows, channels, stride, frames, d_valid, sample_rate, win_length, hop, tau_min, tau_max, align_length,
+                    n_thresholds, n_bins, band, no_trough_prob, d_table, d_obs_voiced, d_obs_unvoiced, d_vp, d_out, d_states, out_frames,
+                    stage=0, stream=0):
+        """alacgpu_pyin_device: probabilistic YIN on every row of d_src (float32 device tensor, planar [rows, channels, stride],
+        framed as `yin_device` frames it) with the packed float32 tables d_table of a pyin.PYin.  stage 0: both launches, into
+        d_out (float32 [rows, channels, 3, out_frames]: the decoded bin's frequency, 1 where voiced, the voicing probability;
+        zeros behind a row's frames), the observations and backpointers in the context's scratch; stage 1: the observations
+        alone into d_obs_voiced [rows, channels, out_frames, n_bins], d_obs_unvoiced and d_vp [rows, channels, out_frames];
+        stage 2: the decode alone on d_obs_voiced and d_obs_unvoiced into d_states (int32 [rows, channels, out_frames], -1
+        behind a row's frames), d_valid then counting frames.  Tensors a stage does not use are None.  pyin.py states the
+        arithmetic.  Asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_pyin_device(self._ctx, _dp(d_src), rows, channels, stride, frames, _dp(d_valid), sample_rate, win_length, hop,
+                                       tau_min, tau_max, align_length, n_thresholds, n_bins, band, float(no_trough_prob), _dp(d_table),
+                                       _dp(d_obs_voiced), _dp(d_obs_unvoiced), _dp(d_vp), _dp(d_out), _dp(d_states), out_frames, int(stage),
+                                       _VP(stream))
         _check(rc, self._ctx)
 
     def reverb_device(self, d_src, d_out, d_rir, rows, channels, rir_channels, stride, rir_stride, frames, rir_frames, d_valid,
@@ -1262,6 +1282,9 @@ from .level import Level, kweight, level, level_host, level_host_twin, loudness,
 from .cqt import ConstantQ, cqt, cqt_frequencies, cqt_host, cqt_host_f32, cqt_lengths, cqt_work  # noqa: E402
 # ---- F0 contours of crops and tensors: the YIN estimator (alacgpu_yin_device) ----------------------------------------------------------
 from .yin import Yin, hz_to_cents, yin, yin_host, yin_host_f32  # noqa: E402
+
+# ---- smoothed F0 tracks: probabilistic YIN with a Viterbi decode (alacgpu_pyin_device) ---------------------------------------------------
+from .pyin import PYin, pyin, pyin_decode, pyin_host, pyin_host_f32, pyin_observation  # noqa: E402
 
 # ---- pitch shift and time stretch of crops and tensors (alacgpu_time_stretch_device) ------------------------------------------------
 from .pitch import (PitchShift, pitch_shift, pitch_shift_host, pitch_shift_host_f32, semitone_ratio, time_stretch,  # noqa: E402

@@ -20,9 +20,9 @@ states the filter) resamples every crop out of it.
 `crops(..., reverb=, mix=, level=, effects=, f0=, features=, deltas=, vad=, normalize=, augment=)` runs up to eleven stages behind the waveform, and `crops` is the one place
 that lists them: the refusals of all of them, the crops the second corpora make (`Corpus._companion_crops`: the noise of an
 AddNoise, then the impulse responses of a Reverb, each cropped by its own corpus at the rate of the crops), the waveform once
-(`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_level_device, alacgpu_biquad_device, alacgpu_yin_device (beside the waveform: it writes a track of its own), alacgpu_logmel_device (or alacgpu_fbank_device or alacgpu_mfcc_device), alacgpu_deltas_device,
+(`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_level_device, alacgpu_biquad_device, alacgpu_yin_device or alacgpu_pyin_device (beside the waveform: it writes a track of its own), alacgpu_logmel_device (or alacgpu_fbank_device or alacgpu_mfcc_device), alacgpu_deltas_device,
 alacgpu_vad_energy_device, the normalisation, alacgpu_select_frames_device and alacgpu_specaugment_device (reverb.py, mix.py,
-level.py, biquad.py, yin.py, features.py, deltas.py, vad.py, normalize.py, sliding.py, pcen.py and augment.py state the arithmetic), each only if asked for.
+level.py, biquad.py, yin.py, pyin.py, features.py, deltas.py, vad.py, normalize.py, sliding.py, pcen.py and augment.py state the arithmetic), each only if asked for.
 
 `crops(..., speed=)` plays every crop at a drawn factor in front of all that (the same method, speed.py): the step of a corpus
 whose rates differ, with a ratio per (file rate, factor) in place of one per file rate; the crops at factor 1 go through the
@@ -58,6 +58,7 @@ from .normalize import MeanVar, TopDb, _normalize
 from .pcen import Pcen
 from .sliding import LDS_MAX as _SLIDING_LDS_MAX, RING_WINDOW_MAX as _SLIDING_RING_WINDOW_MAX, SlidingMeanVar
 from .vad import EnergyVad, _select_frames, _vad_energy
+from .pyin import PYin, _pyin
 from .yin import Yin, _yin
 from .pitch import PitchShift, _pitch_shift, _ratio_kinds
 from .reverb import Reverb, _reverb
@@ -737,7 +738,10 @@ class Corpus(_Closing):
         yin.yin(the waveform the call returns with the same arguments and draws and without features=, f0, lengths); a crop
         outside the corpus is silence.  `Yin.like(features)` has the frames of the features.  ValueError: something that is no
         Yin, a Yin for another rate than the crops', int32 crops, vad= (the selected frames would no longer line up with the
-        track), num_frames below f0.min_frames.
+        track), num_frames below f0.min_frames.  Or a pyin.PYin, wherever a Yin is taken and with the same refusals: the
+        smoothed track of probabilistic YIN, ONE alacgpu_pyin_device call (two launches), track float32 [B, 1 if mono else C,
+        3, f0.frames(num_frames)] -- the decoded bin's frequency in Hz, 1.0 where voiced, the voicing probability, pyin.py
+        states them --, bit for bit pyin.pyin of that waveform.
 
         features: a features.LogMel, a fbank.KaldiFbank, a mfcc.KaldiMfcc or a cqt.ConstantQ -- the crops' log-mel, Kaldi fbank, Kaldi MFCC
         or constant-Q features instead of their PCM (n_mels below is then the transform's line count: a KaldiMfcc's n_ceps, a ConstantQ's n_bins):
@@ -914,7 +918,10 @@ class Corpus(_Closing):
         if effects is not None:
             _biquad(ctx, res, effects[1][0], lengths, effects[1][1], effects[0].clamp, res)
         if f0 is not None:
-            track = _yin(ctx, res, f0, lengths, self._scratch("_f0_scratch", (B, Co, 2, int(f0.frames(L)))))
+            if isinstance(f0, PYin):
+                track = _pyin(ctx, res, f0, lengths, self._scratch("_f0_scratch", (B, Co, 3, int(f0.frames(L)))))
+            else:
+                track = _yin(ctx, res, f0, lengths, self._scratch("_f0_scratch", (B, Co, 2, int(f0.frames(L)))))
         if features is not None:
             if B:
                 features.launch(self._gpu, res, B, Co, L, L, feats, torch.cuda.current_stream(self._dev).cuda_stream)
@@ -1076,12 +1083,12 @@ class Corpus(_Closing):
 
     @staticmethod
     def _f0_given(spec, dtype, rate, vad, num_frames):
-        """crops(f0=) checked: ValueError for what is no Yin, for a Yin of another rate than the crops', for int32 crops, together
+        """crops(f0=) checked: ValueError for what is neither a Yin nor a PYin, for one of another rate than the crops', for int32 crops, together
         with vad= and for crops too short for a frame.  Nothing is done on the device."""
         import torch
 
-        if not isinstance(spec, Yin):
-            raise ValueError(f"f0 must be a yin.Yin, not {spec!r}")
+        if not isinstance(spec, (Yin, PYin)):
+            raise ValueError(f"f0 must be a yin.Yin or a pyin.PYin, not {spec!r}")
         if rate is None:
             raise ValueError(_NEEDS_RATE)
         if spec.sample_rate != rate:

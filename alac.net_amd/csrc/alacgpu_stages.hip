@@ -1,5 +1,5 @@
 // alacgpu_stages.hip -- C ABI of include/alacgpu.h, the stages around the decode: the crop planner, the scan with the packet
-// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the phase vocoder, the reverberation, the simulated room responses, the noise mix, the levelling, the biquad cascade, the YIN pitch estimator, the constant-Q transform, the normalisations, the per-channel energy normalisation, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
+// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the phase vocoder, the reverberation, the simulated room responses, the noise mix, the levelling, the biquad cascade, the YIN pitch estimator, probabilistic YIN with its Viterbi decode, the constant-Q transform, the normalisations, the per-channel energy normalisation, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
 // their own scratch; the decode path is alacgpu_api.hip.  No CPU fallback here either: every stage is its kernels.
 #include <algorithm>
 #include <cmath>
@@ -19,6 +19,7 @@
 #include "alac_mix.h"
 #include "alac_biquad.h"
 #include "alac_yin.h"
+#include "alac_pyin.h"
 #include "alac_cqt.h"
 #include "alac_level.h"
 #include "alac_reverb.h"
@@ -1228,6 +1229,116 @@ int alacgpu_yin_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint3
                                  dim3((uint32_t)(tiles * planes)), dim3(ALAC_YIN_THREADS), kargs, lds, (hipStream_t)hip_stream));
     HIP_TRY(ctx, hipGetLastError());
     return ALACGPU_OK;
+}
+
+int alacgpu_pyin_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t stride, uint64_t frames,
+                        const void* d_valid, uint32_t sample_rate, uint32_t win_length, uint32_t hop, uint32_t tau_min, uint32_t tau_max,
+                        uint32_t align_length, uint32_t n_thresholds, uint32_t n_bins, uint32_t band, float no_trough_prob,
+                        const void* d_table, void* d_obs_voiced, void* d_obs_unvoiced, void* d_vp, void* d_out, void* d_states,
+                        uint64_t out_frames, int stage, void* hip_stream) {
+    if (!ctx || stage < 0 || stage > 2) return ALACGPU_ERR_BAD_ARG;
+    const bool observe = stage != 2, decode = stage != 1;
+    if (!args_ok({{d_src, 4, observe}, {d_valid, 8, false}, {d_table, 4}, {d_obs_voiced, 4, stage != 0}, {d_obs_unvoiced, 4, stage != 0},
+                  {d_vp, 4, stage == 1}, {d_out, 4, stage == 0}, {d_states, 4, stage == 2}}))
+        return ALACGPU_ERR_BAD_ARG;
+    if (channels == 0 || sample_rate == 0 || hop == 0) return ALACGPU_ERR_BAD_ARG;
+    if (win_length < ALAC_YIN_MIN_WIN || win_length > ALAC_YIN_MAX_WIN || win_length % 64u != 0u || tau_min < 2u ||
+        tau_max > ALAC_YIN_MAX_LAG || tau_max <= tau_min + 1u)
+        return ALACGPU_ERR_BAD_ARG;
+    if (n_thresholds < 1u || n_thresholds > ALAC_PYIN_MAX_THRESHOLDS || n_bins < 1u || n_bins > ALAC_PYIN_MAX_BINS || band >= n_bins ||
+        !(no_trough_prob >= 0.0f && no_trough_prob <= 1.0f))
+        return ALACGPU_ERR_BAD_ARG;
+    const uint64_t planes = (uint64_t)rows * channels;
+    if (planes > 0x7FFFFFFFull || out_frames >= (1ull << 31)) return ALACGPU_ERR_BAD_ARG;
+    // the observations (voiced, unvoiced, vp) and the backpointers: in the ctx's scratch where the caller holds neither
+    const uint64_t cells = planes * out_frames;
+    const uint64_t obs_bytes = sizeof(float) * cells * ((uint64_t)n_bins + 2u), back_bytes = sizeof(uint16_t) * cells * 2u * n_bins;
+    if ((stage == 0 ? obs_bytes : 0u) + (decode ? back_bytes : 0u) > (1ull << 31)) return ALACGPU_ERR_BAD_ARG;
+    uint32_t tile = 0;
+    uint64_t tiles = 0;
+    if (observe) {
+        if (frames == 0 || frames > stride) return ALACGPU_ERR_BAD_ARG;
+        const uint64_t expect = align_length ? (frames < align_length ? 0u : 1u + (frames - align_length) / hop) : frames / hop + 1u;
+        if (out_frames != expect) return ALACGPU_ERR_BAD_ARG;
+        uint64_t extent, out_extent;
+        if (!planes_extent(planes, stride, frames, extent) || !planes_extent(planes, 3u * out_frames, 3u * out_frames, out_extent) ||
+            (stage == 0 && !apart(d_src, extent, d_out, out_extent)) ||
+            (stage == 1 && (!apart(d_src, extent, d_obs_voiced, sizeof(float) * cells * n_bins) ||
+                            !apart(d_src, extent, d_obs_unvoiced, sizeof(float) * cells) || !apart(d_src, extent, d_vp, sizeof(float) * cells))))
+            return ALACGPU_ERR_BAD_ARG;
+        tile = alac_yin_tile(win_length, tau_max, hop);
+        tiles = (out_frames + tile - 1u) / tile;
+        if (tiles > 0x7FFFFFFFull || tiles * std::max<uint64_t>(planes, 1u) > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    }
+    if (rows == 0 || out_frames == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    scratch_hold hold{ctx->pyin, stream};
+    const size_t need_obs = stage == 0 ? (size_t)obs_bytes : 0u, need_back = decode ? (size_t)back_bytes : 0u;
+    int rc = ctx->pyin.acquire(ctx, stream, need_obs, align_up(need_obs + need_obs / 4, 4096), need_back, align_up(need_back + need_back / 4, 4096));
+    if (rc) return rc;
+    const uint32_t K = alac_pyin_max_troughs(tau_min, tau_max);
+    const alac_pyin_tables tab = alac_pyin_tables_at((const float*)d_table, n_thresholds, K, n_bins, band);
+    float* obs_voiced = (float*)(stage == 0 ? ctx->pyin.buf[0] : d_obs_voiced);
+    float* obs_unvoiced = stage == 0 ? obs_voiced + cells * n_bins : (float*)d_obs_unvoiced;
+    float* vp = stage == 0 ? obs_unvoiced + cells : (float*)d_vp;
+    if (observe) {
+        alac_pyin_obs_params q;
+        alac_yin_params& p = q.y;
+        p.src = (const float*)d_src;
+        p.valid = (const int64_t*)d_valid;
+        p.out = nullptr;
+        p.channels = channels;
+        p.stride = stride;
+        p.frames = frames;
+        p.out_frames = out_frames;
+        p.win = win_length;
+        p.hop = hop;
+        p.tau_min = tau_min;
+        p.tau_max = tau_max;
+        p.align = align_length;
+        p.first = (int64_t)(align_length / 2u) - (int64_t)((win_length + tau_max) / 2u);
+        p.tile = tile;
+        p.tiles = (uint32_t)tiles;
+        p.samples = alac_yin_samples(win_length, tau_max, hop, tile);
+        p.threshold = 0.0f;
+        p.rate = (float)sample_rate;
+        q.tab = tab;
+        q.obs_voiced = obs_voiced;
+        q.obs_unvoiced = obs_unvoiced;
+        q.vp = vp;
+        q.n_thresholds = n_thresholds;
+        q.n_bins = n_bins;
+        q.max_troughs = K;
+        q.no_trough = no_trough_prob;
+        const size_t lds = sizeof(float) * alac_pyin_obs_lds_floats(p, K, n_bins);
+        void* kargs[] = {&q};
+        HIP_TRY(ctx, hipLaunchKernel(hop % 4u == 0u ? (const void*)alac_pyin_obs_kernel_vec : (const void*)alac_pyin_obs_kernel,
+                                     dim3((uint32_t)(tiles * planes)), dim3(ALAC_YIN_THREADS), kargs, lds, stream));
+    }
+    if (decode) {
+        alac_pyin_decode_params q;
+        q.obs_voiced = obs_voiced;
+        q.obs_unvoiced = obs_unvoiced;
+        q.vp = stage == 0 ? vp : nullptr;
+        q.valid = (const int64_t*)d_valid;
+        q.back = (uint16_t*)ctx->pyin.buf[1];
+        q.out = stage == 0 ? (float*)d_out : nullptr;
+        q.states = stage == 2 ? (int32_t*)d_states : nullptr;
+        q.tab = tab;
+        q.channels = channels;
+        q.n_bins = n_bins;
+        q.band = band;
+        q.frames = frames;
+        q.out_frames = out_frames;
+        q.hop = hop;
+        q.align = align_length;
+        q.counts_are_frames = stage == 2 ? 1u : 0u;
+        void* kargs[] = {&q};
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_pyin_decode_kernel, dim3((uint32_t)planes), dim3(ALAC_PYIN_DECODE_THREADS), kargs, 0, stream));
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return ctx->pyin.release(ctx, stream);
 }
 
 int alacgpu_cqt_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride, uint64_t frames,

@@ -208,6 +208,17 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_yin_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
             ulong stride, ulong frames, IntPtr dValid, uint sampleRate, uint winLength, uint hop, uint tauMin, uint tauMax,
             uint alignLength, float threshold, IntPtr dOut, ulong outFrames, IntPtr hipStream);
+        /// <summary>The smoothed fundamental frequency of planar float crops in device memory: probabilistic YIN, the troughs of
+        /// the YIN estimator's d' with a probability each, then a Viterbi decode over voiced and unvoiced pitch bins along every
+        /// plane.  dSrc, dValid and the framing as for alacgpu_yin_device; dTable the specification's packed float tables
+        /// (include/alacgpu.h).  stage 0: dOut is float[rows, channels, 3, outFrames] -- the bin's frequency in Hz, 1 where
+        /// voiced, the voicing probability; stage 1: the observations alone into dObsVoiced, dObsUnvoiced and dVp; stage 2: the
+        /// decode alone on given observations into dStates (int[rows, channels, outFrames]), dValid then counting frames.  Two
+        /// launches, asynchronous on hipStream.</summary>
+        [DllImport(Lib)] public static extern int alacgpu_pyin_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
+            ulong stride, ulong frames, IntPtr dValid, uint sampleRate, uint winLength, uint hop, uint tauMin, uint tauMax,
+            uint alignLength, uint nThresholds, uint nBins, uint band, float noTroughProb, IntPtr dTable, IntPtr dObsVoiced,
+            IntPtr dObsUnvoiced, IntPtr dVp, IntPtr dOut, IntPtr dStates, ulong outFrames, int stage, IntPtr hipStream);
         /// <summary>Constant-Q features of planar float crops in device memory (dSrc [rows, channels, srcStride] to dOut
         /// [rows, channels, nBins, outFrames], outFrames = 1 + frames / hop): lengths is the N_k in host memory, dLengths
         /// the same in device memory, dTable the kernels in blocks of 16 bins (include/alacgpu.h).</summary>

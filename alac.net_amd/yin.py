@@ -302,6 +302,18 @@ def _choose(dp, c_last, spec, thr, rate, f, margin):
     return f0, b, tau, m, kappa
 
 
+def _dprime_f64(seg, spec):
+    """Steps 1 and 2 of the specification on the frames' samples seg [F, span] float64: (d' [F, tau_max + 1], c[tau_max] [F])"""
+    W = spec.win_length
+    lag = np.arange(spec.tau_max + 1, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        d = np.stack([np.sum((seg[:, :W] - seg[:, tau:tau + W]) ** 2, axis=1) for tau in range(spec.tau_max + 1)], axis=1)
+        c = np.cumsum(d[:, 1:], axis=1)
+        dp = np.ones_like(d)
+        dp[:, 1:] = np.where(c == 0, 1.0, d[:, 1:] * lag[1:] / np.where(c == 0, 1.0, c))
+    return dp, c[:, -1]
+
+
 def yin_host(x, spec, lengths=None, margin=False):
     """The specification in numpy: float64 [B, C, 2, T'] ([B, 2, T'] for x [B, T]) from x float32, float64 arithmetic on the
     float32 input and on the float32 values of the threshold and the rate.  lengths: [B] integers (below 0 counts as 0, above
@@ -315,22 +327,16 @@ def yin_host(x, spec, lengths=None, margin=False):
     taus = np.zeros((B, C, n), dtype=np.int64)
     margins = np.full((B, C, n), np.inf)
     kappas = np.zeros((B, C, n))
-    thr, rate, W = np.float64(np.float32(spec.threshold)), np.float64(np.float32(spec.sample_rate)), spec.win_length
-    lag = np.arange(spec.tau_max + 1, dtype=np.float64)
+    thr, rate = np.float64(np.float32(spec.threshold)), np.float64(np.float32(spec.sample_rate))
     for b in range(B):
         v = int(lens[b])
         count = min(int(spec.frames(v)), n)
         for ch in range(C):
             if count == 0:
                 continue
-            seg = _segments(x3[b, ch], v, spec, 0, count, np.float64)
-            with np.errstate(all="ignore"):
-                d = np.stack([np.sum((seg[:, :W] - seg[:, tau:tau + W]) ** 2, axis=1) for tau in range(spec.tau_max + 1)], axis=1)
-                c = np.cumsum(d[:, 1:], axis=1)
-                dp = np.ones_like(d)
-                dp[:, 1:] = np.where(c == 0, 1.0, d[:, 1:] * lag[1:] / np.where(c == 0, 1.0, c))
+            dp, last = _dprime_f64(_segments(x3[b, ch], v, spec, 0, count, np.float64), spec)
             for t in range(count):
-                f0, ap, tau, m, k = _choose(dp[t], c[t, -1], spec, thr, rate, np.float64, margin)
+                f0, ap, tau, m, k = _choose(dp[t], last[t], spec, thr, rate, np.float64, margin)
                 y[b, ch, 0, t], y[b, ch, 1, t], taus[b, ch, t], margins[b, ch, t], kappas[b, ch, t] = f0, ap, tau, m, k
     if not had_c:
         y, taus, margins, kappas = y[:, 0], taus[:, 0], margins[:, 0], kappas[:, 0]
@@ -356,6 +362,22 @@ def _scan64(d):
     return c.reshape(F, K * 64)[:, :n], carry
 
 
+def _dprime_f32(seg, spec):
+    """Steps 1 and 2 in the kernel's arithmetic on the frames' samples seg [F, span] float32: (d' [F, tau_max + 1], c[tau_max] [F])"""
+    f32 = np.float32
+    W, L = spec.win_length, spec.tau_max + 1
+    lag = np.arange(L).astype(f32)
+    acc = np.zeros((seg.shape[0], L), dtype=f32)
+    with np.errstate(all="ignore"):
+        for j in range(W):
+            e = (seg[:, j, None] - seg[:, j:j + L]).astype(f32)
+            acc = _fma32(e, e, acc)
+        c, last = _scan64(acc[:, 1:])
+        dp = np.ones_like(acc)
+        dp[:, 1:] = np.where(c != 0, ((acc[:, 1:] * lag[1:]).astype(f32) / np.where(c != 0, c, f32(1))).astype(f32), f32(1))
+    return dp, last
+
+
 def yin_host_f32(x, spec, lengths=None, tile=None, taus=False):
     """The kernel's arithmetic in numpy, bit for bit: float32 [B, C, 2, T'] ([B, 2, T'] for x [B, T]).  tile: how many frames
     are evaluated together (default `tile_frames(spec)`, the kernel's): every frame is its own, so it changes nothing.
@@ -367,23 +389,14 @@ def yin_host_f32(x, spec, lengths=None, tile=None, taus=False):
     tile = tile_frames(spec) if tile is None else _int("tile", tile, 1)
     y = np.zeros((B, C, 2, n), dtype=f32)
     chosen = np.zeros((B, C, n), dtype=np.int64)
-    thr, rate, W, L = f32(spec.threshold), f32(spec.sample_rate), spec.win_length, spec.tau_max + 1
-    lag = np.arange(L).astype(f32)
+    thr, rate = f32(spec.threshold), f32(spec.sample_rate)
     for b in range(B):
         v = int(lens[b])
         count = min(int(spec.frames(v)), n)
         for ch in range(C):
             for t0 in range(0, count, tile):
                 t1 = min(t0 + tile, count)
-                seg = _segments(x3[b, ch], v, spec, t0, t1, f32)
-                acc = np.zeros((t1 - t0, L), dtype=f32)
-                with np.errstate(all="ignore"):
-                    for j in range(W):
-                        e = (seg[:, j, None] - seg[:, j:j + L]).astype(f32)
-                        acc = _fma32(e, e, acc)
-                    c, last = _scan64(acc[:, 1:])
-                    dp = np.ones_like(acc)
-                    dp[:, 1:] = np.where(c != 0, ((acc[:, 1:] * lag[1:]).astype(f32) / np.where(c != 0, c, f32(1))).astype(f32), f32(1))
+                dp, last = _dprime_f32(_segments(x3[b, ch], v, spec, t0, t1, f32), spec)
                 for t in range(t0, t1):
                     f0, ap, tau, _, _ = _choose(dp[t - t0], last[t - t0], spec, thr, rate, f32, False)
                     y[b, ch, 0, t], y[b, ch, 1, t], chosen[b, ch, t] = f0, ap, tau

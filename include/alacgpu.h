@@ -897,6 +897,40 @@ int alacgpu_yin_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint3
                        void* hip_stream);
 
 /*
+ * alacgpu_pyin_device: the smoothed fundamental frequency of the crops (no counterpart in the reference): probabilistic YIN of
+ * Mauch and Dixon (ICASSP 2014), what librosa.pyin computes -- per frame the troughs of alacgpu_yin_device's d' with a
+ * probability each, then a Viterbi decode over 2 n_bins states (voiced and unvoiced pitch bins) along every plane.  Two
+ * launches, no atomics, the same inputs give the same bits.  d_src, d_valid, sample_rate, win_length, hop, tau_min, tau_max,
+ * align_length and the frames of a row are alacgpu_yin_device's.  d_table is the float32 tables of the specification, packed
+ * in the order of alac_pyin_tables (csrc/alac_pyin.h) for n_thresholds thresholds, (tau_max - tau_min + 1) / 2 troughs at most,
+ * n_bins bins and a transition band of `band` = min(h, n_bins - 1) bins to either side; alac.net_amd/pyin.py states the tables,
+ * every operation in order, the tie rule (the lowest source state) and the bounds, and its twin equals the kernels bit for bit.
+ *   stage 0  both launches: d_out is float32 [rows, channels, 3, out_frames], apart from d_src: the decoded bin's frequency in
+ *            Hz, 1 where the state is voiced and 0 where not, the voicing probability; zeros at and behind a row's frame
+ *            count.  The log2 observations (float32 [planes, out_frames, n_bins + 2]) and the uint16 backpointers
+ *            ([planes, out_frames, 2 n_bins]) lie in a scratch of the ctx that its calls share one after the other, whatever
+ *            their streams.  The other four arrays are not used.
+ *   stage 1  the observation alone, into d_obs_voiced float32 [rows, channels, out_frames, n_bins], d_obs_unvoiced and d_vp
+ *            [rows, channels, out_frames]; zeros at and behind a row's frame count.  No scratch.
+ *   stage 2  the decode alone, on d_obs_voiced and d_obs_unvoiced as stage 1 leaves them (finite values), into d_states int32
+ *            [rows, channels, out_frames]: the path, -1 at and behind a row's count.  d_valid then holds FRAMES per row
+ *            (NULL: out_frames); d_src, stride and frames are not used.  The backpointers lie in the scratch.
+ * A line without frames runs no recursion.  Device pointers only, asynchronous on hip_stream, nothing is read back.  rows == 0
+ * or out_frames == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx, a stage outside 0 .. 2, a NULL among the arrays the stage uses
+ * (d_table always), a misaligned array (4; 8 for d_valid), channels 0, sample_rate 0, hop 0, the win_length, tau_min and
+ * tau_max alacgpu_yin_device refuses, n_thresholds outside 1 .. 256, n_bins outside 1 .. 1024, band not below n_bins,
+ * no_trough_prob outside [0, 1], 2^31 planes or frames or more, a scratch above 2^31 bytes, and in stages 0 and 1 frames 0 or
+ * above stride, out_frames that is not the frame count of a row of `frames` samples, d_src overlapping what is written, an
+ * extent of 2^60 bytes or more, 2^31 workgroups or more.
+ */
+int alacgpu_pyin_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t stride, uint64_t frames,
+                        const void* d_valid, uint32_t sample_rate, uint32_t win_length, uint32_t hop, uint32_t tau_min,
+                        uint32_t tau_max, uint32_t align_length, uint32_t n_thresholds, uint32_t n_bins, uint32_t band,
+                        float no_trough_prob, const void* d_table, void* d_obs_voiced, void* d_obs_unvoiced, void* d_vp,
+                        void* d_out, void* d_states, uint64_t out_frames, int stage, void* hip_stream);
+
+/*
  * alacgpu_cqt_device: constant-Q features of the crops (no counterpart in the reference): the direct constant-Q transform,
  * every bin's own windowed complex exponential against the signal; one launch, no atomics, no scratch, the same inputs give the
  * same bits.  d_src is planar float32 [rows, channels, src_stride], the first `frames` elements of a plane are signal, zeros

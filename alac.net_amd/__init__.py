@@ -106,6 +106,8 @@ SYMBOLS = {
                                       _VP, _VP, C.c_uint64, C.c_int, _VP]),
     "alacgpu_cqt_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _VP, _VP, _VP,
                                      C.c_int, C.c_int, C.c_float, _VP, C.c_uint64, _VP]),
+    "alacgpu_stft_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _VP, _VP, C.c_int,
+                                      C.c_uint32, _VP, _VP, _VP, C.c_int, C.c_float, _VP, C.c_uint64, _VP]),
     "alacgpu_reverb_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
                                         C.c_uint64, _VP, _VP, _VP]),
     "alacgpu_rir_shoebox_device": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int32, C.c_double, _VP,
@@ -441,6 +443,25 @@ class AlacGpuContext(_Closing):
             raise ValueError(f"lengths must be {n_bins} integers, not {lengths.shape}")
         rc = lib().alacgpu_cqt_device(self._ctx, _dp(d_src), rows, channels, src_stride, frames, hop, n_bins, _ptr(lengths), _dp(d_lengths),
                                       _dp(d_table), power, log_mode, floor, _dp(d_out), out_frames, _VP(stream))
+        _check(rc, self._ctx)
+
+    def stft_device(self, d_src, rows, channels, src_stride, frames, n_fft, hop, d_window, d_table, power, bands, d_bands, d_weights,
+                    log_mode, floor, d_out, out_frames, stream=0):
+        """alacgpu_stft_device: the spectrogram of d_src (float32 device tensor, planar [rows, channels, src_stride], the first
+        `frames` of a plane are signal) into d_out (float32 [rows, channels, lines, out_frames], out_frames = 1 + frames // hop,
+        every element written) with the tables d_window [n_fft] and d_table [n_fft, 2] (stft.Spectrogram builds them); power 0:
+        the complex spectrum (lines 2 n_bins), 1: magnitude, 2: power (lines n_bins); bands: None, or the filterbank's (first,
+        count, offset) per line [lines, 3] (host), d_bands the same on the device (int32) and d_weights the packed weights;
+        log_mode 0: none, 1: ln, 2: log10 of max(., floor).  Asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        if bands is None:
+            fb_lines, h_bands, d_bands, d_weights = 0, None, None, None
+        else:
+            bands = np.ascontiguousarray(bands, dtype=np.uint32)
+            if bands.ndim != 2 or bands.shape[1] != 3:
+                raise ValueError(f"bands must be [lines, 3], not {bands.shape}")
+            fb_lines, h_bands, d_bands, d_weights = len(bands), _ptr(bands), _dp(d_bands), _dp(d_weights)
+        rc = lib().alacgpu_stft_device(self._ctx, _dp(d_src), rows, channels, src_stride, frames, n_fft, hop, _dp(d_window), _dp(d_table),
+                                       power, fb_lines, h_bands, d_bands, d_weights, log_mode, floor, _dp(d_out), out_frames, _VP(stream))
         _check(rc, self._ctx)
 
     def fbank_device(self, d_src, rows, channels, src_stride, frames, win_length, n_fft, hop, n_mels, d_window, d_basis, d_fb, flags,
@@ -1280,6 +1301,8 @@ from .biquad import (Effects, RandomBiquad, allpass, bandpass, bandreject, biqua
 from .level import Level, kweight, level, level_host, level_host_twin, loudness, loudness_host  # noqa: E402
 # ---- constant-Q features of crops and tensors (alacgpu_cqt_device) --------------------------------------------------------------------
 from .cqt import ConstantQ, cqt, cqt_frequencies, cqt_host, cqt_host_f32, cqt_lengths, cqt_work  # noqa: E402
+# ---- linear, complex and banded spectrograms of crops and tensors (alacgpu_stft_device) -----------------------------------------------
+from .stft import Spectrogram, as_complex, spectrogram, spectrogram_host, spectrogram_host_f32  # noqa: E402
 # ---- F0 contours of crops and tensors: the YIN estimator (alacgpu_yin_device) ----------------------------------------------------------
 from .yin import Yin, hz_to_cents, yin, yin_host, yin_host_f32  # noqa: E402
 

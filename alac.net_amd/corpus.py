@@ -50,6 +50,7 @@ from .biquad import Effects, _biquad
 from .level import _checked as _level_checked, _level
 from .deltas import Deltas, _add_deltas
 from .cqt import ConstantQ
+from .stft import Spectrogram
 from .fbank import KaldiFbank
 from .mfcc import KaldiMfcc
 from .features import LogMel
@@ -68,7 +69,7 @@ from .speed import MAX_WIDTH as _SPEED_MAX_WIDTH, SpeedPerturb, ratio as _speed_
 PAD_CFG = 0xFFFF        # a padding entry's cfg_idx: never a row of the context, so the kernels switch the entry off
 MAX_CFGS = 65535
 _NEEDS_RATE = "the files of this corpus differ in sample rate: crops need sample_rate="
-_FEATURES = (LogMel, KaldiFbank, KaldiMfcc, ConstantQ)              # what crops(features=) takes
+_FEATURES = (LogMel, KaldiFbank, KaldiMfcc, ConstantQ, Spectrogram)              # what crops(features=) takes
 # crops(mix=) and crops(reverb=) for `Corpus._second_corpus`: the specification's class, its attribute that holds the second
 # corpus, how many tensors its draw() returns and what their dtypes have to be, and the nouns of the messages
 _MIX = dict(arg="mix", spec=AddNoise, corpus="noise", theirs="the noise corpus", they="the noise",
@@ -743,8 +744,9 @@ class Corpus(_Closing):
         3, f0.frames(num_frames)] -- the decoded bin's frequency in Hz, 1.0 where voiced, the voicing probability, pyin.py
         states them --, bit for bit pyin.pyin of that waveform.
 
-        features: a features.LogMel, a fbank.KaldiFbank, a mfcc.KaldiMfcc or a cqt.ConstantQ -- the crops' log-mel, Kaldi fbank, Kaldi MFCC
-        or constant-Q features instead of their PCM (n_mels below is then the transform's line count: a KaldiMfcc's n_ceps, a ConstantQ's n_bins):
+        features: a features.LogMel, a fbank.KaldiFbank, a mfcc.KaldiMfcc, a cqt.ConstantQ or a stft.Spectrogram -- the crops' log-mel, Kaldi fbank, Kaldi MFCC,
+        constant-Q features or spectrogram instead of their PCM (n_mels below is then the transform's line count: a KaldiMfcc's n_ceps, a ConstantQ's n_bins,
+        a Spectrogram's bins, filterbank rows or, for the complex spectrum, twice its bins -- that kind takes no deltas=, normalize=, vad= or augment=):
         the waveform goes into a float32 scratch the corpus keeps and ONE alacgpu_logmel_device, alacgpu_fbank_device or
         alacgpu_mfcc_device call turns every row, the zeros behind its length included, into features.  Returns (feats float32 [B, 1 if mono else C,
         n_mels, features.frames(num_frames)], feat_lengths [B] int64 on the device: features.lengths(lengths) -- lengths // hop
@@ -811,7 +813,7 @@ class Corpus(_Closing):
                 if features is None:
                     raise ValueError("a Pcen compresses mel or constant-Q energies: it needs features=")
                 if isinstance(features, KaldiMfcc) or (isinstance(features, _FEATURES) and features.log not in (None, False)):
-                    raise ValueError(f"a Pcen compresses energies: features with log=None (a LogMel, a ConstantQ) or log=False "
+                    raise ValueError(f"a Pcen compresses energies: features with log=None (a LogMel, a ConstantQ, a Spectrogram) or log=False "
                                      f"(a KaldiFbank), not {features!r}")
                 if deltas is not None:
                     raise ValueError("a Pcen compresses energies: deltas= of them are none")
@@ -830,7 +832,7 @@ class Corpus(_Closing):
                                      f"{_SLIDING_RING_WINDOW_MAX} frames")
         if features is not None:
             if not isinstance(features, _FEATURES):
-                raise ValueError(f"features must be a features.LogMel or a fbank.KaldiFbank or a mfcc.KaldiMfcc or a cqt.ConstantQ, not {features!r} "
+                raise ValueError(f"features must be a features.LogMel or a fbank.KaldiFbank or a mfcc.KaldiMfcc or a cqt.ConstantQ or a stft.Spectrogram, not {features!r} "
                                  f"(sample_rate= and mono= go by keyword)")
             if rate is None:
                 raise ValueError(_NEEDS_RATE)
@@ -838,6 +840,10 @@ class Corpus(_Closing):
                 raise ValueError(f"features for {features.sample_rate} Hz, crops at {rate} Hz")
             if not _is_f32(torch, dtype):
                 raise ValueError("features are computed from float32 crops")
+            if isinstance(features, Spectrogram) and features.power is None:
+                for name, given in (("deltas", deltas), ("normalize", normalize), ("vad", vad), ("augment", augment)):
+                    if given is not None:
+                        raise ValueError(f"a Spectrogram with power=None gives real and imaginary parts: {name}= takes magnitudes, powers or their logs")
         if deltas is not None:
             if not isinstance(deltas, Deltas):
                 raise ValueError(f"deltas must be a deltas.Deltas, not {deltas!r}")

@@ -6,103 +6,23 @@
 // order of the sums.  Every operation is one IEEE float32 operation, rounded once: this file is compiled with -ffp-contract=off
 // and the products and sums go through __fmul_rn / __fadd_rn / __fsub_rn; the division is `/` and the root sqrtf, which
 // -fhip-fp32-correctly-rounded-divide-sqrt makes the correctly rounded ones.  The copy of rows that the pitch shift ends with
-// is here too.
+// is here too.  The transform itself (shape, pos_of, forward, inverse) is alac_fft_tile.h's, which alac_stft.hip runs too.
 #include "alac_stretch.h"
+#include "alac_fft_tile.h"
 
 #pragma clang fp contract(off)
 
+using namespace alac_fft;
+static_assert(alac_stretch_threads(512u) == alac_fft_threads(512u) && alac_stretch_threads(1024u) == alac_fft_threads(1024u) &&
+              alac_stretch_threads(2048u) == alac_fft_threads(2048u), "the transform's threads are the launch's");
+
 namespace {
 
-__device__ inline float2 cadd(float2 a, float2 b) { return make_float2(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y)); }
-__device__ inline float2 csub(float2 a, float2 b) { return make_float2(__fsub_rn(a.x, b.x), __fsub_rn(a.y, b.y)); }
-__device__ inline float2 cmul(float2 a, float2 b) {
-    return make_float2(__fsub_rn(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y)), __fadd_rn(__fmul_rn(a.x, b.y), __fmul_rn(a.y, b.x)));
-}
-__device__ inline float2 conj(float2 a) { return make_float2(a.x, -a.y); }
 __device__ inline float cabs(float2 a) { return sqrtf(__fadd_rn(__fmul_rn(a.x, a.x), __fmul_rn(a.y, a.y))); }
 // z / |z|, 1 where |z| is not above 0 (a NaN too)
 __device__ inline float2 phasor(float2 a) {
     const float m = cabs(a);
     return m > 0.0f ? make_float2(a.x / m, a.y / m) : make_float2(1.0f, 0.0f);
-}
-
-template <uint32_t N> struct shape {
-    static_assert(N == 512u || N == 1024u || N == 2048u, "n_fft is 512, 1024 or 2048");
-    static constexpr uint32_t H = N / 4u, K = N / 2u + 1u, THREADS = alac_stretch_threads(N);
-    static constexpr bool ODD = N != 1024u;               // a radix-2 stage in front of the radix-4 stages
-    static constexpr uint32_t DIGITS = N == 512u ? 4u : 5u;   // the base-4 digits behind it
-    static constexpr uint32_t L0 = ODD ? N / 8u : N / 4u;     // the first radix-4 span
-    static_assert(H % THREADS == 0u, "a thread's elements of a frame fall on its own elements of a tile");
-};
-
-// where bin k of the forward transform lies (alac_stretch.h)
-template <uint32_t N> __device__ inline uint32_t pos_of(uint32_t k) {
-    uint32_t kk = shape<N>::ODD ? k >> 1 : k, rev = 0u;
-#pragma unroll
-    for (uint32_t d = 0; d < shape<N>::DIGITS; d++) {
-        rev = (rev << 2) | (kk & 3u);
-        kk >>= 2;
-    }
-    return shape<N>::ODD ? (k & 1u) * (N / 2u) + rev : rev;
-}
-
-// The forward transform of z[N] in LDS, in place, natural order in, bin k at pos_of(k) out.  A butterfly reads and writes its
-// own elements; a barrier stands in front of every stage and behind the last.
-template <uint32_t N> __device__ inline void forward(float2* z, const float2* tw) {
-    constexpr uint32_t THREADS = shape<N>::THREADS;
-    if (shape<N>::ODD) {
-        __syncthreads();
-        for (uint32_t q = threadIdx.x; q < N / 2u; q += THREADS) {
-            const float2 a = z[q], b = z[q + N / 2u];
-            z[q] = cadd(a, b);
-            z[q + N / 2u] = cmul(csub(a, b), tw[q]);
-        }
-    }
-    for (uint32_t L = shape<N>::L0; L >= 1u; L >>= 2) {
-        const uint32_t step = N / (4u * L);
-        __syncthreads();
-        for (uint32_t q = threadIdx.x; q < N / 4u; q += THREADS) {
-            const uint32_t j = q & (L - 1u), i0 = ((q - j) << 2) + j;
-            const float2 a = z[i0], b = z[i0 + L], c = z[i0 + 2u * L], d = z[i0 + 3u * L];
-            const float2 t0 = cadd(a, c), t1 = csub(a, c), t2 = cadd(b, d), bd = csub(b, d);
-            const float2 t3 = make_float2(bd.y, -bd.x);                       // -i (b - d)
-            z[i0] = cadd(t0, t2);
-            z[i0 + L] = cmul(cadd(t1, t3), tw[j * step]);
-            z[i0 + 2u * L] = cmul(csub(t0, t2), tw[2u * j * step]);
-            z[i0 + 3u * L] = cmul(csub(t1, t3), tw[3u * j * step]);
-        }
-    }
-    __syncthreads();
-}
-
-// The inverse transform, not divided by N: bin k at pos_of(k) in, natural order out; the forward stages' conjugate transposes
-// in the opposite order
-template <uint32_t N> __device__ inline void inverse(float2* z, const float2* tw) {
-    constexpr uint32_t THREADS = shape<N>::THREADS;
-    for (uint32_t L = 1u; L <= shape<N>::L0; L <<= 2) {
-        const uint32_t step = N / (4u * L);
-        __syncthreads();
-        for (uint32_t q = threadIdx.x; q < N / 4u; q += THREADS) {
-            const uint32_t j = q & (L - 1u), i0 = ((q - j) << 2) + j;
-            const float2 z0 = z[i0], z1 = cmul(z[i0 + L], conj(tw[j * step])), z2 = cmul(z[i0 + 2u * L], conj(tw[2u * j * step])),
-                         z3 = cmul(z[i0 + 3u * L], conj(tw[3u * j * step]));
-            const float2 u0 = cadd(z0, z2), u1 = csub(z0, z2), u2 = cadd(z1, z3), dz = csub(z1, z3);
-            const float2 u3 = make_float2(-dz.y, dz.x);                       // i (z1 - z3)
-            z[i0] = cadd(u0, u2);
-            z[i0 + L] = cadd(u1, u3);
-            z[i0 + 2u * L] = csub(u0, u2);
-            z[i0 + 3u * L] = csub(u1, u3);
-        }
-    }
-    if (shape<N>::ODD) {
-        __syncthreads();
-        for (uint32_t q = threadIdx.x; q < N / 2u; q += THREADS) {
-            const float2 a = z[q], b = cmul(z[q + N / 2u], conj(tw[q]));
-            z[q] = cadd(a, b);
-            z[q + N / 2u] = csub(a, b);
-        }
-    }
-    __syncthreads();
 }
 
 // A row's integers (alac_stretch.h); workgroup-uniform

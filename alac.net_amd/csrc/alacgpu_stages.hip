@@ -1,5 +1,5 @@
 // alacgpu_stages.hip -- C ABI of include/alacgpu.h, the stages around the decode: the crop planner, the scan with the packet
-// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the phase vocoder, the reverberation, the simulated room responses, the noise mix, the levelling, the biquad cascade, the YIN pitch estimator, probabilistic YIN with its Viterbi decode, the constant-Q transform, the normalisations, the per-channel energy normalisation, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
+// compaction and staging, the resamplers, log-mel, Kaldi fbank and MFCC, the delta features, the phase vocoder, the reverberation, the simulated room responses, the noise mix, the levelling, the biquad cascade, the YIN pitch estimator, probabilistic YIN with its Viterbi decode, the constant-Q transform, the STFT, the normalisations, the per-channel energy normalisation, the energy VAD with the selection of the voiced frames, SpecAugment and the encoder.  Of the ctx they use the device, the cfgs, last_error and
 // their own scratch; the decode path is alacgpu_api.hip.  No CPU fallback here either: every stage is its kernels.
 #include <algorithm>
 #include <cmath>
@@ -21,6 +21,7 @@
 #include "alac_yin.h"
 #include "alac_pyin.h"
 #include "alac_cqt.h"
+#include "alac_stft.h"
 #include "alac_level.h"
 #include "alac_reverb.h"
 #include "alac_rir.h"
@@ -1389,6 +1390,61 @@ int alacgpu_cqt_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint3
     p.floor = floor;
     void* kargs[] = {&p};
     HIP_TRY(ctx, hipLaunchKernel((const void*)alac_cqt_kernel, dim3((uint32_t)(tiles * channels * rows)), dim3(ALAC_CQT_THREADS), kargs, lds,
+                                 (hipStream_t)hip_stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return ALACGPU_OK;
+}
+
+int alacgpu_stft_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride, uint64_t frames,
+                        uint32_t n_fft, uint32_t hop, const void* d_window, const void* d_table, int power, uint32_t fb_lines,
+                        const uint32_t* bands, const void* d_bands, const void* d_weights, int log_mode, float floor, void* d_out,
+                        uint64_t out_frames, void* hip_stream) {
+    const bool fb = fb_lines != 0u;
+    if (!ctx || !args_ok({{d_src, 4}, {d_window, 4}, {d_table, 8}, {bands, 4, fb}, {d_bands, 4, fb}, {d_weights, 4, fb}, {d_out, 4}}))
+        return ALACGPU_ERR_BAD_ARG;
+    if (!alac_stft_n_fft_ok(n_fft) || hop < 1 || hop > n_fft || channels == 0 || fb_lines > ALAC_STFT_MAX_LINES) return ALACGPU_ERR_BAD_ARG;
+    if (power != ALAC_STFT_COMPLEX && power != ALAC_STFT_MAGNITUDE && power != ALAC_STFT_POWER) return ALACGPU_ERR_BAD_ARG;
+    if (log_mode != ALAC_STFT_LOG_NONE && log_mode != ALAC_STFT_LOG_LN && log_mode != ALAC_STFT_LOG_10) return ALACGPU_ERR_BAD_ARG;
+    if (power == ALAC_STFT_COMPLEX && (fb || log_mode != ALAC_STFT_LOG_NONE)) return ALACGPU_ERR_BAD_ARG;
+    if (!(floor > 0.0f) || !std::isfinite(floor)) return ALACGPU_ERR_BAD_ARG;
+    if (frames < n_fft / 2u + 1u || frames > src_stride || frames > (1ull << 62) || out_frames != 1u + frames / hop) return ALACGPU_ERR_BAD_ARG;
+    const uint32_t n_bins = n_fft / 2u + 1u;
+    uint64_t packed = 0;
+    for (uint32_t m = 0; m < fb_lines; ++m) {     // a band lies in 0 .. n_bins, its weights behind the line's before
+        const uint32_t first = bands[3u * m], count = bands[3u * m + 1u];
+        if (first > n_bins || count > n_bins - first || bands[3u * m + 2u] != packed) return ALACGPU_ERR_BAD_ARG;
+        packed += count;
+    }
+    const uint32_t lines = alac_stft_lines(n_fft, power, fb_lines);
+    const uint32_t tile = alac_stft_tile(n_fft, lines, fb);
+    const uint64_t tiles = (out_frames + tile - 1u) / tile;
+    if (tiles > 0x7FFFFFFFull || tiles * channels > 0x7FFFFFFFull || tiles * channels * rows > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    const size_t lds = alac_stft_lds_bytes(n_fft, lines, fb, tile);
+    if (lds > ALAC_STFT_LDS_MAX) return ALACGPU_ERR_BAD_ARG;      // (no shape within the limits above is)
+    if (rows == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const void* const kernel = alac_stft_kernel_of(n_fft);
+    if (lds > ALAC_STFT_LDS_DEFAULT) HIP_TRY(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    alac_stft_params p;
+    p.src = (const float*)d_src;
+    p.src_stride = src_stride;
+    p.frames = frames;
+    p.out = (float*)d_out;
+    p.out_frames = out_frames;
+    p.window = (const float*)d_window;
+    p.table = (const float2*)d_table;
+    p.bands = (const uint32_t*)d_bands;
+    p.weights = (const float*)d_weights;
+    p.hop = hop;
+    p.lines = lines;
+    p.fb_lines = fb_lines;
+    p.tile = tile;
+    p.tiles = (uint32_t)tiles;
+    p.power = (uint32_t)power;
+    p.log_mode = (uint32_t)log_mode;
+    p.floor = floor;
+    void* kargs[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel(kernel, dim3((uint32_t)(tiles * channels * rows)), dim3(alac_fft_threads(n_fft)), kargs, lds,
                                  (hipStream_t)hip_stream));
     HIP_TRY(ctx, hipGetLastError());
     return ALACGPU_OK;

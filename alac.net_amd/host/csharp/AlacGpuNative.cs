@@ -225,6 +225,15 @@ namespace ALACdotNET.Decoder
         [DllImport(Lib)] public static extern int alacgpu_cqt_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
             ulong srcStride, ulong frames, uint hop, uint nBins, uint[] lengths, IntPtr dLengths, IntPtr dTable, int power,
             int logMode, float floor, IntPtr dOut, ulong outFrames, IntPtr hipStream);
+        /// <summary>Linear, complex or banded (mel) spectrograms of planar float crops in device memory by an FFT (dSrc [rows,
+        /// channels, srcStride] to dOut [rows, channels, lines, outFrames], outFrames = 1 + frames / hop): nFft 256, 512, 1024
+        /// or 2048; dWindow float[nFft], dTable float[nFft][2]; power 0 the complex spectrum (2 (nFft / 2 + 1) lines), 1
+        /// magnitude, 2 power; fbLines 0, or the lines of a filterbank whose bands (first, count, offset per line) are in host
+        /// memory, dBands the same in device memory and dWeights the packed weights (include/alacgpu.h).</summary>
+        [DllImport(Lib)] public static extern int alacgpu_stft_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
+            ulong srcStride, ulong frames, uint nFft, uint hop, IntPtr dWindow, IntPtr dTable, int power, uint fbLines,
+            uint[] bands, IntPtr dBands, IntPtr dWeights, int logMode, float floor, IntPtr dOut, ulong outFrames,
+            IntPtr hipStream);
         /// <summary>Room reverberation into planar float crops in device memory (dSrc, dOut [rows, channels, stride], dRir
         /// [rows, rirChannels, rirStride], rirChannels 1 or channels; the first frames / rirFrames of a plane are data): every
         /// row convolved with its impulse response over the first dValid[row] frames of the signal and dRirValid[row] of the

@@ -154,14 +154,15 @@ class Pcen(_Spec):
 
     @classmethod
     def like(cls, spec, **kw):
-        """The Pcen whose frame rate is that of `spec`, a features.LogMel, a fbank.KaldiFbank or a cqt.ConstantQ:
+        """The Pcen whose frame rate is that of `spec`, a features.LogMel, a fbank.KaldiFbank, a cqt.ConstantQ or a stft.Spectrogram:
         sample_rate / hop_length.  kw: the other arguments of `Pcen` (time_constant among them)."""
         from .cqt import ConstantQ
         from .fbank import KaldiFbank
         from .features import LogMel
+        from .stft import Spectrogram
 
-        if not isinstance(spec, (LogMel, KaldiFbank, ConstantQ)):
-            raise ValueError(f"spec must be a features.LogMel, a fbank.KaldiFbank or a cqt.ConstantQ, not {spec!r}")
+        if not isinstance(spec, (LogMel, KaldiFbank, ConstantQ, Spectrogram)):
+            raise ValueError(f"spec must be a features.LogMel, a fbank.KaldiFbank or a cqt.ConstantQ or a stft.Spectrogram, not {spec!r}")
         if "b" in kw or "frame_rate" in kw:
             raise ValueError("Pcen.like takes the frame rate from spec: neither b nor frame_rate")
         return cls(frame_rate=spec.sample_rate / spec.hop_length, **kw)

@@ -129,20 +129,21 @@ class Yin(_Spec):
 
     @classmethod
     def like(cls, spec, **kw):
-        """The Yin whose frames are those of `spec`, a features.LogMel, a cqt.ConstantQ, a fbank.KaldiFbank or a mfcc.KaldiMfcc: its
-        rate and hop, centred for a LogMel and a ConstantQ, align_length = spec.win_length for the Kaldi kinds (with snip_edges, the only Kaldi framing
+        """The Yin whose frames are those of `spec`, a features.LogMel, a cqt.ConstantQ, a stft.Spectrogram, a fbank.KaldiFbank or a mfcc.KaldiMfcc: its
+        rate and hop, centred for a LogMel, a ConstantQ and a Spectrogram, align_length = spec.win_length for the Kaldi kinds (with snip_edges, the only Kaldi framing
         whose count this estimator has: ValueError without).  kw: the other arguments of `Yin`."""
         from .cqt import ConstantQ
         from .fbank import _KaldiFraming
         from .features import LogMel
+        from .stft import Spectrogram
 
-        if isinstance(spec, (LogMel, ConstantQ)):
+        if isinstance(spec, (LogMel, ConstantQ, Spectrogram)):
             return cls(spec.sample_rate, hop_length=spec.hop_length, center=True, **kw)
         if isinstance(spec, _KaldiFraming):
             if not spec.snip_edges:
                 raise ValueError("a Kaldi transform with snip_edges=False reflects its last frames: no Yin has its frame count")
             return cls(spec.sample_rate, hop_length=spec.hop_length, center=False, align_length=spec.win_length, **kw)
-        raise ValueError(f"spec must be a features.LogMel, a cqt.ConstantQ, a fbank.KaldiFbank or a mfcc.KaldiMfcc, not {spec!r}")
+        raise ValueError(f"spec must be a features.LogMel, a cqt.ConstantQ, a fbank.KaldiFbank or a mfcc.KaldiMfcc or a stft.Spectrogram, not {spec!r}")
 
     @property
     def span(self):

@@ -958,6 +958,36 @@ int alacgpu_cqt_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint3
                        int log_mode, float floor, void* d_out, uint64_t out_frames, void* hip_stream);
 
 /*
+ * alacgpu_stft_device: linear, complex or banded (mel) spectrograms of the crops (no counterpart in the reference): the
+ * short-time Fourier transform by an FFT; one launch, no atomics, no scratch, the same inputs give the same bits.  d_src is
+ * planar float32 [rows, channels, src_stride], the first `frames` elements of a plane are signal; d_out is float32 [rows,
+ * channels, lines, out_frames], out_frames = 1 + frames / hop, every element written.  n_fft is 256, 512, 1024 or 2048,
+ * n_bins = n_fft / 2 + 1.  Frame t is centred on sample t hop and reflected once at both ends as alacgpu_logmel_device's:
+ *   X_t[k] = sum over n < n_fft of d_window[n] x_t[n] exp(-2 pi i k n / n_fft),   k < n_bins
+ * d_window is float32 [n_fft] (a shorter window stands at offset (n_fft - win_length) / 2 with zeros around it), d_table is
+ * float32 [n_fft][2], (cos, -sin)(2 pi k / n_fft).  power 0: the complex spectrum, lines = 2 n_bins, the real parts in the
+ * lines 0 .. n_bins, the imaginary parts behind them (fb_lines 0 and log_mode 0 then); power 1: |X|; power 2: |X|^2, lines =
+ * n_bins.  fb_lines in 1 .. 256: a filterbank on that, lines = fb_lines: line m is the sum over i < count_m of
+ * d_weights[offset_m + i] v[first_m + i], with `bands` (host memory, uint32 [fb_lines][3]: first, count, offset; d_bands is
+ * the same array in device memory) naming each line's band of bins and where its weights begin in d_weights, packed in the
+ * order of the lines; a count of 0 gives 0.  log_mode 1 or 2: ln or log10 of max(that, floor).  The frames 2 j and 2 j + 1
+ * of a plane are the real and imaginary part of one complex n_fft-point transform in LDS; a workgroup takes a tile of 8 to 64
+ * consecutive frames of a plane and stores whole runs of a line (alac.net_amd/stft.py states the arithmetic operation by
+ * operation, csrc/alac_stft.h the tile).  A NaN or an infinity reaches the two frames of the pair that holds it and no other.
+ * Nothing of the ctx is used but its device, so calls on different streams are independent.  Device pointers (but `bands`),
+ * asynchronous on hip_stream, nothing is read back.  rows == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx or array (the three of the filterbank may be NULL with fb_lines
+ * 0), a misaligned array (4; d_table 8), channels 0, another n_fft, hop outside 1 .. n_fft, frames below n_fft / 2 + 1 or above
+ * src_stride, out_frames that is not 1 + frames / hop, fb_lines above 256, a band that leaves 0 .. n_bins or whose offset is
+ * not the sum of the counts before it, a power that is not 0, 1 or 2, power 0 with a filterbank or a log, an unknown log_mode,
+ * a floor that is not positive and finite, 2^31 workgroups or more.
+ */
+int alacgpu_stft_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride, uint64_t frames,
+                        uint32_t n_fft, uint32_t hop, const void* d_window, const void* d_table, int power, uint32_t fb_lines,
+                        const uint32_t* bands, const void* d_bands, const void* d_weights, int log_mode, float floor, void* d_out,
+                        uint64_t out_frames, void* hip_stream);
+
+/*
  * alacgpu_reverb_device: room reverberation into the crops, in front of the noise mix (no counterpart in the reference): every
  * crop convolved with its own impulse response by a uniformly partitioned overlap-save convolution; two launches, no atomics,
  * the same inputs give the same bits.  The layout is planar float32: d_src and d_out [rows, channels, stride], d_rir [rows,

@@ -3,7 +3,8 @@ call: the immutable specification base (`_Spec`, `_f32_finite`), the lengths on 
 `_lengths_device`), the layouts a kernel takes (`_lines`, `_planes`, `_span`), the context of a tensor's device
 (`_device_context`), the tree of halves and the exact fused multiply-add of the float32 twins (`_tree`, `_fma32`), and `_signal_and_companion`: the one check of a
 float32 signal [B, C, T] with a companion [B, C or 1, T'], two optional lengths and an `out`, which is all of `_mix` and
-`_reverb` but their library call.  A new stage takes what it needs from here, never from another stage's module.
+`_reverb` but their library call.  A new stage takes what its tensor function needs from here, never from another stage's
+module; what its keyword of `Corpus.crops` refuses and draws goes into `_cropstages.py`, what it runs into `Corpus._run`.
 """
 import math
 

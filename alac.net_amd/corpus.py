@@ -17,12 +17,12 @@ from both tiers into a small staging blob in HBM, and the decode reads that.
 frames a crop needs are decoded as above into a scratch the corpus keeps, and one alacgpu_resample_device call (resample.py
 states the filter) resamples every crop out of it.
 
-`crops(..., reverb=, mix=, level=, effects=, f0=, features=, deltas=, vad=, normalize=, augment=)` runs up to eleven stages behind the waveform, and `crops` is the one place
-that lists them: the refusals of all of them, the crops the second corpora make (`Corpus._companion_crops`: the noise of an
-AddNoise, then the impulse responses of a Reverb, each cropped by its own corpus at the rate of the crops), the waveform once
-(`Corpus._waveform`), then in place on the same stream alacgpu_reverb_device, alacgpu_mix_device, alacgpu_level_device, alacgpu_biquad_device, alacgpu_yin_device or alacgpu_pyin_device (beside the waveform: it writes a track of its own), alacgpu_logmel_device (or alacgpu_fbank_device or alacgpu_mfcc_device), alacgpu_deltas_device,
-alacgpu_vad_energy_device, the normalisation, alacgpu_select_frames_device and alacgpu_specaugment_device (reverb.py, mix.py,
-level.py, biquad.py, yin.py, pyin.py, features.py, deltas.py, vad.py, normalize.py, sliding.py, pcen.py and augment.py state the arithmetic), each only if asked for.
+`crops(..., <a stage keyword>=)` runs stages on the waveform and behind it, in three steps.  `_cropstages._stage_plan` is the
+one place that lists the keywords and refuses what a stage cannot take, before any device work, for `crops` and `random_crops`
+alike; `_cropstages._middle_draws` makes the draws nobody gave; `Corpus._run` is the one place that lists what runs, in order:
+the crops the second corpora make (`Corpus._companion_crops`: the noise of an AddNoise, then the impulse responses of a Reverb,
+each cropped by its own corpus at the rate of the crops), the waveform once (`Corpus._waveform`), then every stage that was
+asked for by its one library call, in place on the same stream (each stage's module states its arithmetic).
 
 `crops(..., speed=)` plays every crop at a drawn factor in front of all that (the same method, speed.py): the step of a corpus
 whose rates differ, with a ratio per (file rate, factor) in place of one per file rate; the crops at factor 1 go through the
@@ -45,51 +45,23 @@ import numpy as np
 from . import (MAX_FRAME, ST_OK, ST_UNSUPPORTED_ELEMENT, ST_UNSUPPORTED_PREDTYPE, AlacGpuContext, AlacGpuError, PinnedBuffer,
                _Closing, _check, _check_batch_args, _compact_slots, _dp, _encode_slots, _frame_count, _status_text, _torch_dtype,
                _VP, _write_file, lib, make_cfgs)
-from .augment import LDS_MAX as _WARP_MAX, _check_draws, _how, _spec_augment
-from .biquad import Effects, _biquad
-from .level import _checked as _level_checked, _level
-from .deltas import Deltas, _add_deltas
-from .cqt import ConstantQ
-from .stft import Spectrogram
-from .fbank import KaldiFbank
-from .mfcc import KaldiMfcc
-from .features import LogMel
-from .mix import AddNoise, _mix, snr_ratio
-from .normalize import MeanVar, TopDb, _normalize
-from .pcen import Pcen
-from .sliding import LDS_MAX as _SLIDING_LDS_MAX, RING_WINDOW_MAX as _SLIDING_RING_WINDOW_MAX, SlidingMeanVar
-from .vad import EnergyVad, _select_frames, _vad_energy
+from ._cropstages import _NEEDS_RATE, _TWO_CHANNELS, _for_batch, _is_f32, _middle_draws, _stage_plan
+from .augment import _spec_augment
+from .biquad import _biquad
+from .level import _level
+from .deltas import _add_deltas
+from .mix import _mix, snr_ratio
+from .normalize import _normalize
+from .vad import _select_frames, _vad_energy
 from .pyin import PYin, _pyin
-from .yin import Yin, _yin
-from .pitch import PitchShift, _pitch_shift, _ratio_kinds
-from .reverb import Reverb, _reverb
+from .yin import _yin
+from .pitch import _pitch_shift, _ratio_kinds
+from .reverb import _reverb
 from .rir import _simulate
 from .speed import MAX_WIDTH as _SPEED_MAX_WIDTH, SpeedPerturb, ratio as _speed_ratio
 
 PAD_CFG = 0xFFFF        # a padding entry's cfg_idx: never a row of the context, so the kernels switch the entry off
 MAX_CFGS = 65535
-_NEEDS_RATE = "the files of this corpus differ in sample rate: crops need sample_rate="
-_FEATURES = (LogMel, KaldiFbank, KaldiMfcc, ConstantQ, Spectrogram)              # what crops(features=) takes
-# crops(mix=) and crops(reverb=) for `Corpus._second_corpus`: the specification's class, its attribute that holds the second
-# corpus, how many tensors its draw() returns and what their dtypes have to be, and the nouns of the messages
-_MIX = dict(arg="mix", spec=AddNoise, corpus="noise", theirs="the noise corpus", they="the noise",
-            what="mix must be a mix.AddNoise or (AddNoise, what its draw() returned)",
-            draws=3, dtypes=lambda torch, files, offsets, snr_db: snr_db.is_floating_point,
-            tensors="the three tensors (noise_files, noise_offsets, snr_db) of AddNoise.draw", f32="noise is mixed into float32 crops",
-            channels="a noise corpus of {n} channels into crops of {Co}: it can become one channel from 1 or 2 only")
-_SPEED = dict(arg="speed", spec=SpeedPerturb, what="speed must be a speed.SpeedPerturb or (SpeedPerturb, what its draw() returned)",
-              f32="float32 crops are speed-perturbed")
-_PITCH = dict(arg="pitch", spec=PitchShift, what="pitch must be a pitch.PitchShift or (PitchShift, what its draw() returned)",
-              f32="float32 crops are pitch-shifted")
-_REVERB = dict(arg="reverb", spec=Reverb, corpus="rirs", theirs="the corpus of impulse responses", they="the responses",
-               what="reverb must be a reverb.Reverb or (Reverb, what its draw() returned)",
-               draws=2, dtypes=lambda torch, files, keep: not files.is_floating_point and keep == torch.bool,
-               tensors="the two tensors (rir_files, keep) of Reverb.draw", f32="float32 crops are reverberated",
-               channels="impulse responses of {n} channels into crops of {Co}: they can become one channel from 1 or 2 only")
-
-
-def _is_f32(torch, dtype):
-    return _torch_dtype(torch, torch.float32 if dtype is None else dtype) == torch.float32
 
 
 def corpus_tables(tables, mixed_rates=False):
@@ -701,10 +673,11 @@ class Corpus(_Closing):
         as speed= does; pitch.time_stretch on the result covers it.
 
         The stages behind the waveform go by keyword, as sample_rate and mono do, and run in this order whichever are
-        given -- pitch, reverb, mix, level, effects, f0, features, deltas, the VAD's decision, normalize, the selection of the voiced frames, augment --,
-        in place but for the features and the deltas, by the corpus's own context on the same stream; lengths (but for vad=,
-        which shortens them), `check` and last_status() are those of the call without them (with check=True a second corpus's own check runs too, and first).  ValueError before any device
-        work for what a stage cannot take.
+        given -- pitch, reverb, mix, level, effects, f0, features, deltas, the VAD's decision, normalize, the selection of the
+        voiced frames, augment --, in place but for the features and the deltas, by the corpus's own context on the same
+        stream; lengths (but for vad=, which shortens them), `check` and last_status() are those of the call without them
+        (with check=True a second corpus's own check runs too, and first).  ValueError before any device work for what a
+        stage cannot take (`_cropstages._stage_plan`, which `random_crops` runs in front of its first draw).
 
         reverb: room reverberation of the waveform: a reverb.Reverb, whose draws are then made here from the device's default
         generator, or the pair (Reverb, draws) with the draws that its `draw(B)` returned.  Bit for bit reverb.reverb(the crops
@@ -788,112 +761,39 @@ class Corpus(_Closing):
         more than 16384 feature frames."""
         import torch
 
-        # 1. every refusal that needs no device work: speed, mix, reverb, level, effects, normalize, features, augment; the waveform's own are `_waveform`'s
-        rate = self.sample_rate if sample_rate is None else sample_rate
-        Co = 1 if mono else self.channels
-        if speed is not None:
-            speed = self._speed_given(speed, dtype, rate)
-        if pitch is not None:
-            pitch = self._pitch_given(pitch, dtype, rate, Co, num_frames)
-        if mix is not None:
-            mix = self._second_corpus(mix, _MIX, dtype, rate, Co)
-        if reverb is not None:
-            reverb = self._second_corpus(reverb, _REVERB, dtype, rate, Co)
-        if level is not None:
-            self._level_given(level, dtype, rate, Co)
-        if effects is not None:
-            effects = self._effects_given(effects, dtype, rate)
-        if f0 is not None:
-            self._f0_given(f0, dtype, rate, vad, num_frames)
-        if normalize is not None:
-            if not isinstance(normalize, (MeanVar, TopDb, SlidingMeanVar, Pcen)):
-                raise ValueError(f"normalize must be a normalize.MeanVar, a normalize.TopDb, a sliding.SlidingMeanVar or a pcen.Pcen, "
-                                 f"not {normalize!r}")
-            if isinstance(normalize, Pcen):
-                if features is None:
-                    raise ValueError("a Pcen compresses mel or constant-Q energies: it needs features=")
-                if isinstance(features, KaldiMfcc) or (isinstance(features, _FEATURES) and features.log not in (None, False)):
-                    raise ValueError(f"a Pcen compresses energies: features with log=None (a LogMel, a ConstantQ, a Spectrogram) or log=False "
-                                     f"(a KaldiFbank), not {features!r}")
-                if deltas is not None:
-                    raise ValueError("a Pcen compresses energies: deltas= of them are none")
-                if normalize.lines is not None and isinstance(features, _FEATURES) and normalize.lines != features.n_mels:
-                    raise ValueError(f"a Pcen with {normalize.lines} values per parameter, features with {features.n_mels} lines")
-            if features is None and isinstance(normalize, TopDb):
-                raise ValueError("a TopDb clamps log-mel features: it needs features=")
-            if features is None and not _is_f32(torch, dtype):
-                raise ValueError(f"a {type(normalize).__name__} normalises float32 crops")
-            if isinstance(normalize, SlidingMeanVar) and normalize.window > _SLIDING_RING_WINDOW_MAX:
-                n = _frame_count("num_frames", num_frames) if features is None else None
-                if n is None and isinstance(features, _FEATURES):
-                    n = features.frames(_frame_count("num_frames", num_frames))
-                if n is not None and n > _SLIDING_LDS_MAX:
-                    raise ValueError(f"lines of {n} frames: above {_SLIDING_LDS_MAX} a sliding window takes at most "
-                                     f"{_SLIDING_RING_WINDOW_MAX} frames")
-        if features is not None:
-            if not isinstance(features, _FEATURES):
-                raise ValueError(f"features must be a features.LogMel or a fbank.KaldiFbank or a mfcc.KaldiMfcc or a cqt.ConstantQ or a stft.Spectrogram, not {features!r} "
-                                 f"(sample_rate= and mono= go by keyword)")
-            if rate is None:
-                raise ValueError(_NEEDS_RATE)
-            if features.sample_rate != rate:
-                raise ValueError(f"features for {features.sample_rate} Hz, crops at {rate} Hz")
-            if not _is_f32(torch, dtype):
-                raise ValueError("features are computed from float32 crops")
-            if isinstance(features, Spectrogram) and features.power is None:
-                for name, given in (("deltas", deltas), ("normalize", normalize), ("vad", vad), ("augment", augment)):
-                    if given is not None:
-                        raise ValueError(f"a Spectrogram with power=None gives real and imaginary parts: {name}= takes magnitudes, powers or their logs")
-        if deltas is not None:
-            if not isinstance(deltas, Deltas):
-                raise ValueError(f"deltas must be a deltas.Deltas, not {deltas!r}")
-            if features is None:
-                raise ValueError("Deltas are derivatives of features: they need features=")
-        if vad is not None:
-            if not isinstance(vad, EnergyVad):
-                raise ValueError(f"vad must be a vad.EnergyVad, not {vad!r}")
-            if features is None:
-                raise ValueError("an EnergyVad decides on a feature line: it needs features=")
-            lines = features.n_mels if deltas is None else deltas.lines(features.n_mels)
-            if vad.line >= lines:
-                raise ValueError(f"vad.line {vad.line} of features with {lines} lines")
-        if augment is not None:
-            augment = _how(augment, "augment")
-            if features is None:
-                raise ValueError("a SpecAugment masks log-mel features: it needs features=")
-        if (features is not None or mix is not None or reverb is not None or speed is not None or effects is not None or level is not None
-                or pitch is not None or f0 is not None):
-            L = _frame_count("num_frames", num_frames)
-            if features is not None and L < features.min_frames:
-                raise ValueError(features.short(L))
+        plan = _stage_plan(self.channels, self.sample_rate, self._dev, dtype, num_frames, sample_rate, mono, speed=speed, pitch=pitch,
+                           mix=mix, reverb=reverb, level=level, effects=effects, f0=f0, features=features, deltas=deltas, vad=vad,
+                           normalize=normalize, augment=augment)
+        B = None
+        if plan.L is not None:
             self._open()
             B = int(files.shape[0]) if isinstance(files, torch.Tensor) and files.dim() == 1 else len(np.asarray(files))
-        if speed is not None and speed[1] is not None and speed[1].shape[0] != B:
-            raise ValueError(f"{speed[1].shape[0]} draws of speed= for {B} crops")
-        if pitch is not None and pitch[1] is not None and pitch[1].shape[0] != B:
-            raise ValueError(f"{pitch[1].shape[0]} draws of pitch= for {B} crops")
-        if effects is not None and effects[1] is not None and effects[1][0].shape[0] != B:
-            raise ValueError(f"{effects[1][0].shape[0]} draws of effects= for {B} crops")
+            plan = _for_batch(plan, B, self._dev)
+        return self._run(plan, files, frame_offsets, num_frames, B, dtype, out, check)
+
+    def _run(self, plan, files, frame_offsets, num_frames, B, dtype, out, check):
+        """`crops` behind its checks: `plan` is what `_stage_plan` returned, and `_for_batch` has seen it for the B crops (B None:
+        a plan without a stage in front of the waveform, which has no L either).  Nothing of it is checked again."""
+        import torch
+
+        rate, Co, L, features, deltas, vad, f0 = plan.rate, plan.Co, plan.L, plan.features, plan.deltas, plan.vad, plan.f0
+        # 1. the outputs: with features= `out` is theirs, and the waveform goes into the scratch they are computed from
         if features is not None:
-            if augment is not None:
-                if augment[1] is not None:
-                    augment = (augment[0], tuple(_check_draws(augment[1], B, self._dev)))
-                if augment[0].time_warp and features.frames(L) > _WARP_MAX:
-                    raise ValueError(f"features of {features.frames(L)} frames: a time warp takes at most {_WARP_MAX}")
-            lines = features.n_mels if deltas is None else deltas.lines(features.n_mels)
-            feats = self._out(out, (B, Co, lines, features.frames(L)), torch.float32, zero=False)
+            feats = self._out(out, (B, Co, plan.lines, plan.frames), torch.float32, zero=False)
             if deltas is not None:      # the features into a scratch, their deltas into what the call returns
-                stacked, feats = feats, self._scratch("_delta_scratch", (B, Co, features.n_mels, features.frames(L)))
+                stacked, feats = feats, self._scratch("_delta_scratch", (B, Co, features.n_mels, plan.frames))
             out = self._scratch("_ft_scratch", (B, Co, L))
-        # 2. the pitch's draws; the companion crops, by the second corpora's own `crops`: the noise, then the responses
-        if pitch is not None and pitch[1] is None:
-            pitch = (pitch[0], pitch[0].draw(B, device=self._dev))
+        # 2. the draws nobody gave, from the device's default generator; the companion crops, by the second corpora's own
+        #    `crops`: the noise, then the responses
+        if B is not None:
+            plan = _middle_draws(plan, B, self._dev)
+        pitch, mix, reverb, effects = plan.pitch, plan.mix, plan.reverb, plan.effects
         if mix is not None:
-            nf, no, snr = mix[0].draw(B, L, sample_rate=rate) if mix[1] is None else mix[1]
+            nf, no, snr = mix[1]
             d_noise, noise_lengths = self._companion_crops(mix[0].noise, "_mix_scratch", nf, no, L, B=B, Co=Co, rate=rate,
                                                            check=check)
         if reverb is not None:
-            draws = reverb[0].draw(B, device=self._dev) if reverb[1] is None else reverb[1]
+            draws = reverb[1]
             keep = draws[-1]
             if reverb[0].rooms is not None:       # simulated rooms: one channel, computed into the same scratch
                 rooms = reverb[0].rooms
@@ -906,11 +806,9 @@ class Corpus(_Closing):
                 from_0 = torch.zeros(B, dtype=torch.int64, device=self._dev)
                 d_rir, rir_lengths = self._companion_crops(reverb[0].rirs, "_reverb_scratch", draws[0], from_0, reverb[0].frames(rate),
                                                            B=B, Co=Co, rate=rate, check=check)
-        if effects is not None and effects[1] is None:
-            effects = (effects[0], effects[0].draw(B, rate, device=self._dev))
         # 3. the waveform, once: into `out`, or into the scratch the features are computed from
-        res, lengths = self._waveform(files, frame_offsets, num_frames, dtype=dtype, out=out, check=check, sample_rate=sample_rate,
-                                      mono=mono, speed=speed)
+        res, lengths = self._waveform(files, frame_offsets, num_frames, dtype=dtype, out=out, check=check, sample_rate=plan.sample_rate,
+                                      mono=plan.mono, speed=plan.speed)
         # 4. the stages, in place and in this order on the same stream, by the corpus's own context
         ctx = lambda: self._gpu
         if pitch is not None and B:
@@ -919,8 +817,8 @@ class Corpus(_Closing):
             _reverb(ctx, res, d_rir, lengths, torch.where(keep, rir_lengths, 0), res)
         if mix is not None:
             _mix(ctx, res, d_noise, lambda: snr_ratio(snr, B, self._dev), lengths, noise_lengths, res)
-        if level is not None:
-            _level(ctx, res, level, rate, lengths, res)
+        if plan.level is not None:
+            _level(ctx, res, plan.level, rate, lengths, res)
         if effects is not None:
             _biquad(ctx, res, effects[1][0], lengths, effects[1][1], effects[0].clamp, res)
         if f0 is not None:
@@ -937,12 +835,12 @@ class Corpus(_Closing):
         if vad is not None:         # Kaldi's order: the decision on the raw features, the selection behind the CMVN
             voiced = self._scratch("_vad_scratch", ((res.shape[0] * res.shape[-1] + 3) // 4,)).view(torch.uint8)
             voiced = _vad_energy(ctx, res, vad, lengths, out=voiced[:res.shape[0] * res.shape[-1]].view(res.shape[0], res.shape[-1]))
-        if normalize is not None:
-            _normalize(ctx, res, normalize, lengths, res)
+        if plan.normalize is not None:
+            _normalize(ctx, res, plan.normalize, lengths, res)
         if vad is not None:
             res, lengths = _select_frames(ctx, res, voiced, lengths, res)
-        if augment is not None:
-            _spec_augment(ctx, res, augment[0] if augment[1] is None else augment, lengths, res)
+        if plan.augment is not None:
+            _spec_augment(ctx, res, plan.augment[0] if plan.augment[1] is None else plan.augment, lengths, res)
         return (res, lengths) if f0 is None else (res, lengths, track)
 
     def _waveform(self, files, frame_offsets, num_frames, dtype, out, check, sample_rate, mono, speed=None):
@@ -981,86 +879,6 @@ class Corpus(_Closing):
             self._check_last(lengths, d_files, d_offs, L, K)
         return out, lengths
 
-    @staticmethod
-    def _pair(given, stage):
-        """The front of `_second_corpus` and `_speed_given`: crops(mix= / reverb= / speed=) as the pair (its specification, draws
-        or None); ValueError for anything else"""
-        spec, draws = given if isinstance(given, tuple) and len(given) == 2 else (given, None)
-        if not isinstance(spec, stage["spec"]):
-            raise ValueError(f"{stage['what']}, not {given!r}")
-        return spec, draws
-
-    def _second_corpus(self, given, stage, dtype, rate, Co):
-        """crops(mix=) or crops(reverb=) (`stage`: _MIX or _REVERB) as the pair (its specification, draws or None), checked:
-        ValueError for anything else, for int32 crops, for a second corpus that is closed, on another device or of a channel
-        count that crops of Co channels cannot take, and for crops without a rate.  Nothing is done on the device."""
-        import torch
-
-        spec, draws = self._pair(given, stage)
-        if stage is _REVERB and spec.rooms is not None:
-            return self._rooms_given(spec, draws, dtype, rate)
-        if draws is not None:
-            ok = isinstance(draws, tuple) and len(draws) == stage["draws"] and all(isinstance(t, torch.Tensor) and t.dim() == 1
-                                                                                   for t in draws)
-            if not ok or any(t.shape != draws[0].shape for t in draws) or not stage["dtypes"](torch, *(t.dtype for t in draws)):
-                raise ValueError(f"the draws of {stage['arg']}= must be {stage['tensors']}")
-            if any(t.device != self._dev for t in draws):
-                raise ValueError(f"the draws of {stage['arg']}= must be on {self._dev}")
-        if not _is_f32(torch, dtype):
-            raise ValueError(stage["f32"])
-        other = getattr(spec, stage["corpus"])
-        if other._gpu is None:
-            raise ValueError(f"{stage['theirs']} is closed")
-        if other._dev != self._dev:
-            raise ValueError(f"{stage['theirs']} is on {other._dev}, the crops on {self._dev}")
-        if rate is None:
-            raise ValueError(f"{_NEEDS_RATE}, and {stage['they']} a rate to crop at")
-        if other.channels != Co and other.channels not in (1, 2):
-            raise ValueError(stage["channels"].format(n=other.channels, Co=Co))
-        return spec, draws
-
-    def _rooms_given(self, spec, draws, dtype, rate):
-        """`_second_corpus` for a Reverb over simulated rooms: the draws are (geometry float64 [B, 9], beta float32 [B, 6], keep
-        bool [B]) on the corpus's device; ValueError for anything else, for int32 crops, for crops without a rate and for a
-        policy whose smallest room is refused at that rate.  Nothing is done on the device."""
-        import torch
-
-        if draws is not None:
-            ok = isinstance(draws, tuple) and len(draws) == 3 and all(isinstance(t, torch.Tensor) for t in draws)
-            if not (ok and draws[0].dim() == 2 and draws[0].shape[1] == 9 and draws[0].dtype == torch.float64
-                    and draws[1].shape == (draws[0].shape[0], 6) and draws[1].dtype == torch.float32
-                    and draws[2].shape == (draws[0].shape[0],) and draws[2].dtype == torch.bool):
-                raise ValueError("the draws of reverb= must be the three tensors (geometry, beta, keep) of Reverb.draw")
-            if any(t.device != self._dev for t in draws):
-                raise ValueError(f"the draws of reverb= must be on {self._dev}")
-        if not _is_f32(torch, dtype):
-            raise ValueError(_REVERB["f32"])
-        if rate is None:
-            raise ValueError(f"{_NEEDS_RATE}, and the responses a rate to be computed at")
-        spec.check_rate(int(rate))
-        return spec, draws
-
-    def _pitch_given(self, given, dtype, rate, Co, num_frames):
-        """crops(pitch=) as the pair (PitchShift, draws or None), checked: ValueError for anything else, for int32 crops, for
-        crops of more than 2 channels or without a rate and for crops too short to reflect.  Nothing is done on the device;
-        the draws' length is `crops`'s to check, where B is known."""
-        import torch
-
-        spec, draws = self._pair(given, _PITCH)
-        if not _is_f32(torch, dtype):
-            raise ValueError(_PITCH["f32"])
-        if Co not in (1, 2):
-            raise ValueError(f"{Co} channels: the resampler behind the vocoder takes 1 or 2")
-        if rate is None:
-            raise ValueError(_NEEDS_RATE)
-        L = _frame_count("num_frames", num_frames)
-        if L <= spec.n_fft // 2:
-            raise ValueError(f"crops of {L} frames: a PitchShift of n_fft {spec.n_fft} reflects {spec.n_fft // 2} and needs more")
-        if draws is not None and (not isinstance(draws, torch.Tensor) or draws.dim() != 1 or draws.dtype.is_floating_point
-                                  or draws.dtype == torch.bool or draws.device != self._dev):
-            raise ValueError(f"the draws of pitch= must be the integer tensor [B] of PitchShift.draw on {self._dev}")
-        return spec, draws
-
     def _pitch(self, ctx, res, pitch, rate, lengths):
         """crops(pitch=(spec, draws)) on the crops `res`, in place: the ratios of the draws, gathered on the device"""
         import torch
@@ -1076,77 +894,6 @@ class Corpus(_Closing):
         names = dict(stretched="_pitch_scratch", resampled="_pitch_back_scratch")
         _pitch_shift(ctx, res, d_ps[k], d_qs[k], kinds, k.to(torch.int32), lengths, spec.n_fft, res,
                      lambda name, shape: self._scratch(names[name], shape))
-
-    @staticmethod
-    def _level_given(spec, dtype, rate, Co):
-        """crops(level=) checked: ValueError for what is no Level, for int32 crops and, for lufs, for more than 5 channels, crops
-        without a rate and a rate the K-weighting cannot be designed at.  Nothing is done on the device."""
-        import torch
-
-        _level_checked(spec, rate, Co)
-        if not _is_f32(torch, dtype):
-            raise ValueError("float32 crops are levelled")
-
-    @staticmethod
-    def _f0_given(spec, dtype, rate, vad, num_frames):
-        """crops(f0=) checked: ValueError for what is neither a Yin nor a PYin, for one of another rate than the crops', for int32 crops, together
-        with vad= and for crops too short for a frame.  Nothing is done on the device."""
-        import torch
-
-        if not isinstance(spec, (Yin, PYin)):
-            raise ValueError(f"f0 must be a yin.Yin or a pyin.PYin, not {spec!r}")
-        if rate is None:
-            raise ValueError(_NEEDS_RATE)
-        if spec.sample_rate != rate:
-            raise ValueError(f"f0 for {spec.sample_rate} Hz, crops at {rate} Hz")
-        if not _is_f32(torch, dtype):
-            raise ValueError("F0 is estimated from float32 crops")
-        if vad is not None:
-            raise ValueError("f0= with vad=: the selected frames would no longer line up with the track")
-        L = _frame_count("num_frames", num_frames)
-        if L < spec.min_frames:
-            raise ValueError(spec.short(L))
-
-    def _effects_given(self, given, dtype, rate):
-        """crops(effects=) as the pair (Effects, draws or None), checked: ValueError for anything else, for int32 crops, for
-        crops without a rate, for a filter at or above their Nyquist frequency and for draws that are not (float64 [B, S, 5],
-        float64 [B]) on the corpus's device.  Nothing is done on the device; B is `crops`'s to check."""
-        import torch
-
-        spec, draws = given if isinstance(given, tuple) and len(given) == 2 else (given, None)
-        if not isinstance(spec, Effects):
-            raise ValueError(f"effects must be a biquad.Effects or (Effects, what its draw() returned), not {given!r}")
-        if not _is_f32(torch, dtype):
-            raise ValueError("float32 crops are filtered")
-        if rate is None:
-            raise ValueError(_NEEDS_RATE)
-        spec.check_rate(rate)
-        if draws is not None:
-            ok = isinstance(draws, tuple) and len(draws) == 2 and all(isinstance(t, torch.Tensor) and t.dtype == torch.float64 for t in draws)
-            if not ok or draws[0].dim() != 3 or tuple(draws[0].shape[1:]) != (spec.sections, 5) or draws[1].shape != draws[0].shape[:1]:
-                raise ValueError(f"the draws of effects= must be the two float64 tensors (coeffs [B, {spec.sections}, 5], gain [B]) of "
-                                 f"Effects.draw")
-            if any(t.device != self._dev for t in draws):
-                raise ValueError(f"the draws of effects= must be on {self._dev}")
-        return spec, draws
-
-    def _speed_given(self, given, dtype, rate):
-        """crops(speed=) as the pair (SpeedPerturb, draws or None), checked: ValueError for anything else, for int32 crops,
-        for a corpus of more than 2 channels and for crops without a rate.  Nothing is done on the device; the draws' length
-        is `_resampled_crops`'s to check, where B is known."""
-        import torch
-
-        spec, draws = self._pair(given, _SPEED)
-        if not _is_f32(torch, dtype):
-            raise ValueError(_SPEED["f32"])
-        if self.channels not in (1, 2):
-            raise ValueError(f"{self.channels} channels: the resampler takes 1 or 2")
-        if rate is None:
-            raise ValueError(_NEEDS_RATE)
-        if draws is not None and (not isinstance(draws, torch.Tensor) or draws.dim() != 1 or draws.dtype.is_floating_point
-                                  or draws.dtype == torch.bool or draws.device != self._dev):
-            raise ValueError(f"the draws of speed= must be the integer tensor [B] of SpeedPerturb.draw on {self._dev}")
-        return spec, draws
 
     def _companion_crops(self, other, scratch, files, offsets, frames, B, Co, rate, check):
         """What a stage needs of a second corpus for B crops of Co channels at `rate`: other.crops(files, offsets, frames) at
@@ -1330,7 +1077,7 @@ class Corpus(_Closing):
         L = _frame_count("num_frames", num_frames)
         self._open()
         if self.channels not in (1, 2):
-            raise ValueError(f"{self.channels} channels: the resampler takes 1 or 2")
+            raise ValueError(_TWO_CHANNELS.format(n=self.channels))
         spec, draws = (None, None) if speed is None else speed
         rt = self._rate(sample_rate, spec)
         win = self._window(rt["rate"], L, spec)
@@ -1338,9 +1085,7 @@ class Corpus(_Closing):
         d_files, d_offs, _ = self._indices(files, frame_offsets, rt["Ty_max"])
         B, C_ = int(d_files.shape[0]), self.channels
         if spec is not None and draws is None:
-            draws = spec.draw(B, device=self._dev)
-        if draws is not None and draws.shape[0] != B:
-            raise ValueError(f"{draws.shape[0]} draws for {B} crops")
+            draws = spec.draw(B, device=self._dev)      # (given draws are B: `_cropstages._for_batch`)
         out = self._out(out, (B, 1 if mono else C_, L), torch.float32, zero=False)
         if B * K >= 1 << 32:
             raise ValueError(f"{B} crops of up to {K} packets: a call plans fewer than 2^32 entries")
@@ -1399,42 +1144,21 @@ class Corpus(_Closing):
         import torch
 
         B, L = _frame_count("batch", batch), _frame_count("num_frames", num_frames)
-        rate = self.sample_rate if sample_rate is None else sample_rate
-        if speed is not None:
-            speed = self._speed_given(speed, dtype, rate)
-        if pitch is not None:
-            pitch = self._pitch_given(pitch, dtype, rate, 1 if mono else self.channels, num_frames)
-            if pitch[1] is not None and pitch[1].shape[0] != B:
-                raise ValueError(f"{pitch[1].shape[0]} draws of pitch= for {B} crops")
-        if mix is not None:
-            mix = self._second_corpus(mix, _MIX, dtype, rate, 1 if mono else self.channels)
-        if reverb is not None:
-            reverb = self._second_corpus(reverb, _REVERB, dtype, rate, 1 if mono else self.channels)
-        if level is not None:
-            self._level_given(level, dtype, rate, 1 if mono else self.channels)
-        if effects is not None:
-            effects = self._effects_given(effects, dtype, rate)
-        if f0 is not None:
-            self._f0_given(f0, dtype, rate, vad, num_frames)
-        if augment is not None:
-            augment = _how(augment, "augment")
-            if features is None:
-                raise ValueError("a SpecAugment masks log-mel features: it needs features=")
-        if deltas is not None and features is None:
-            raise ValueError("Deltas are derivatives of features: they need features=")
-        if vad is not None and features is None:
-            raise ValueError("an EnergyVad decides on a feature line: it needs features=")
+        plan = _stage_plan(self.channels, self.sample_rate, self._dev, dtype, num_frames, sample_rate, mono, speed=speed, pitch=pitch,
+                           mix=mix, reverb=reverb, level=level, effects=effects, f0=f0, features=features, deltas=deltas, vad=vad,
+                           normalize=normalize, augment=augment)
+        if self.sample_rate is None and sample_rate is None:
+            raise ValueError(_NEEDS_RATE)
+        if plan.L is not None:
+            self._open()
+            plan = _for_batch(plan, B, self._dev)
         dev = generator.device if generator is not None else self._dev
         files = torch.randint(0, self.num_files, (B,), generator=generator, device=dev, dtype=torch.int64).to(self._dev)
         u = torch.rand(B, generator=generator, device=dev, dtype=torch.float64).to(self._dev)
-        if self.sample_rate is None and sample_rate is None:
-            raise ValueError(_NEEDS_RATE)
-        if speed is not None:
-            if speed[1] is None:
-                speed = (speed[0], speed[0].draw(B, generator=generator, device=self._dev))
-            elif speed[1].shape[0] != B:
-                raise ValueError(f"{speed[1].shape[0]} draws for {B} crops")
-        spec, draws = (None, None) if speed is None else speed
+        spec, draws = (None, None) if plan.speed is None else plan.speed
+        if spec is not None and draws is None:
+            draws = spec.draw(B, generator=generator, device=self._dev)
+            plan = plan._replace(speed=(spec, draws))
         if sample_rate is None and spec is None:    # the native crops: the files' own frames, and nothing to upload
             ends = self._d_num_frames[files]
         else:                                       # the frames of the crop's file at the rate of the crops, played at its factor
@@ -1442,21 +1166,12 @@ class Corpus(_Closing):
             ends = rt["d_Ty"][self._at(files, draws, rt["nk"])]
         span = (ends - L).clamp(min=0)
         offs = torch.minimum(torch.floor(u * (span + 1).to(torch.float64)).to(torch.int64), span)
-        if pitch is not None and pitch[1] is None:
-            pitch = (pitch[0], pitch[0].draw(B, generator=generator, device=self._dev))
-        if mix is not None and mix[1] is None:
-            mix = (mix[0], mix[0].draw(B, L, sample_rate=rate, generator=generator))
-        if reverb is not None and reverb[1] is None:
-            reverb = (reverb[0], reverb[0].draw(B, generator=generator, device=self._dev))
-        if effects is not None and effects[1] is None:
-            effects = (effects[0], effects[0].draw(B, rate, generator=generator, device=self._dev))
-        if augment is not None and augment[1] is None and isinstance(features, _FEATURES):
-            feat_lengths = features.lengths((ends - offs).clamp(max=L))
-            lines = deltas.lines(features.n_mels) if isinstance(deltas, Deltas) else features.n_mels
-            augment = (augment[0], augment[0].draw(lines, feat_lengths, generator=generator))
-        res = self.crops(files, offs, L, dtype=dtype, out=out, check=check, sample_rate=sample_rate, mono=mono,
-                         features=features, normalize=normalize, mix=mix, reverb=reverb, augment=augment, speed=speed,
-                         deltas=deltas, vad=vad, effects=effects, level=level, pitch=pitch, f0=f0)
+        plan = _middle_draws(plan, B, self._dev, generator)
+        augment = plan.augment
+        if augment is not None and augment[1] is None:      # for the feat_lengths the call is going to return
+            feat_lengths = plan.features.lengths((ends - offs).clamp(max=L))
+            plan = plan._replace(augment=(augment[0], augment[0].draw(plan.lines, feat_lengths, generator=generator)))
+        res = self._run(plan, files, offs, L, B, dtype, out, check)
         return (res[0], res[1], files, offs) + tuple(res[2:])
 
     def last_staged_bytes(self):

@@ -256,3 +256,86 @@ def test_the_draws_of_a_step_come_in_the_documented_order(staged, path):
     ndraws = add.draw(6, SL, sample_rate=rate)
     rdraws = aug.draw(6)
     assert torch.equal(corpus.crops(a[2], a[3], SL, mix=(add, ndraws), reverb=(aug, rdraws), check=False, **stages, **kw)[0], drawn)
+
+
+def test_all_six_drawing_stages_draw_in_the_documented_order(staged):
+    """speed=, pitch=, mix=, reverb=, effects= and augment= at once, with features= and deltas=: random_crops draws files, u,
+    speed, pitch, mix, reverb, effects, augment from its generator; crops draws pitch, mix, reverb, effects, speed, augment
+    from the device's default generator -- the SpeedPerturb behind the Effects"""
+    import torch
+
+    import alac.net_amd as pkg
+
+    kw = PATHS["rate"]
+    corpus, rate, dev = staged["sig"], TARGET, torch.device("cuda", 0)
+    sp, ps = pkg.SpeedPerturb(), pkg.PitchShift()
+    add, aug = pkg.AddNoise(staged["noise"], (0, 20), p=0.8), pkg.Reverb(staged["rirs"], p=0.8, max_seconds=RIR_FRAMES / rate)
+    fx = pkg.Effects(pkg.RandomBiquad("peaking", (200.0, 6000.0), q=(0.5, 2.0), gain_db=(-3.0, 0.0)), gain_db=(-3.0, 0.0))
+    sa = pkg.SpecAugment(freq_width=10, time_width=5, time_warp=3)
+    spec, dl = pkg.LogMel(rate, 400, 160, 80), pkg.Deltas()
+    stages = dict(features=spec, deltas=dl)
+    lines, frames = dl.lines(spec.n_mels), spec.frames(SL)
+    seeded = lambda: torch.Generator(device="cuda").manual_seed(11)
+    a = corpus.random_crops(6, SL, generator=seeded(), speed=sp, pitch=ps, mix=add, reverb=aug, effects=fx, augment=sa, check=False,
+                            **stages, **kw)
+    assert len(a) == 4 and a[0].shape == (6, 1, lines, frames)
+
+    def by_hand(order):
+        """The draws of random_crops from an equally seeded generator, the four middle ones in `order`"""
+        g = seeded()
+        files = torch.randint(0, corpus.num_files, (6,), generator=g, device=dev, dtype=torch.int64)
+        u = torch.rand(6, generator=g, device=dev, dtype=torch.float64)
+        sdraws = sp.draw(6, generator=g, device=dev)
+        ends = torch.from_numpy(corpus.resampled_frames(rate, sp)).to(dev)[files, sdraws]
+        span = (ends - SL).clamp(min=0)
+        offs = torch.minimum(torch.floor(u * (span + 1).to(torch.float64)).to(torch.int64), span)
+        draw = dict(pitch=lambda: ps.draw(6, generator=g, device=dev), mix=lambda: add.draw(6, SL, sample_rate=rate, generator=g),
+                    reverb=lambda: aug.draw(6, generator=g, device=dev), effects=lambda: fx.draw(6, rate, generator=g, device=dev))
+        drawn = {k: draw[k]() for k in order}
+        adraws = sa.draw(lines, spec.lengths((ends - offs).clamp(max=SL)), generator=g)
+        return files, offs, corpus.crops(files, offs, SL, speed=(sp, sdraws), pitch=(ps, drawn["pitch"]), mix=(add, drawn["mix"]),
+                                         reverb=(aug, drawn["reverb"]), effects=(fx, drawn["effects"]), augment=(sa, adraws),
+                                         check=False, **stages, **kw)
+
+    files, offs, again = by_hand(("pitch", "mix", "reverb", "effects"))
+    assert torch.equal(files, a[2]) and torch.equal(offs, a[3])
+    assert torch.equal(again[0], a[0]) and torch.equal(again[1], a[1])
+    files, offs, swapped = by_hand(("pitch", "mix", "effects", "reverb"))
+    assert torch.equal(files, a[2]) and torch.equal(offs, a[3]) and not torch.equal(swapped[0], a[0])
+
+    # crops without draws: from the device's default generator, the speed behind the effects
+    torch.cuda.manual_seed(13)
+    got, got_len = corpus.crops(a[2], a[3], SL, speed=sp, pitch=ps, mix=add, reverb=aug, effects=fx, augment=sa, check=False, **stages, **kw)
+    got, got_len = got.clone(), got_len.clone()
+    assert (got_len > 0).all() and not torch.equal(got, a[0])
+
+    def by_default_generator(order):
+        torch.cuda.manual_seed(13)
+        draw = dict(pitch=lambda: ps.draw(6, device=dev), mix=lambda: add.draw(6, SL, sample_rate=rate), reverb=lambda: aug.draw(6, device=dev),
+                    effects=lambda: fx.draw(6, rate, device=dev), speed=lambda: sp.draw(6, device=dev))
+        drawn = {k: draw[k]() for k in order}
+        adraws = sa.draw(lines, got_len.clamp(max=frames))
+        return corpus.crops(a[2], a[3], SL, speed=(sp, drawn["speed"]), pitch=(ps, drawn["pitch"]), mix=(add, drawn["mix"]),
+                            reverb=(aug, drawn["reverb"]), effects=(fx, drawn["effects"]), augment=(sa, adraws), check=False, **stages, **kw)
+
+    again = by_default_generator(("pitch", "mix", "reverb", "effects", "speed"))
+    assert torch.equal(again[0], got) and torch.equal(again[1], got_len)
+    assert not torch.equal(by_default_generator(("pitch", "mix", "reverb", "speed", "effects"))[0], got)
+
+
+def test_a_refused_random_crops_call_leaves_its_generator_where_it_was(staged):
+    """What only the stage checks refuse -- a normalize= of a wrong type, a vad.line beyond the line count -- is refused
+    before the first draw"""
+    import torch
+
+    import alac.net_amd as pkg
+
+    corpus, spec = staged["sig"], pkg.LogMel(SIG_RATE, 400, 160, 80)
+    for match, kw in (("normalize must be", dict(normalize="meanvar")),
+                      ("vad.line 80 of features with 80 lines", dict(features=spec, vad=pkg.EnergyVad(line=80))),
+                      ("features must be", dict(features="logmel", augment=pkg.SpecAugment()))):
+        g = torch.Generator(device="cuda").manual_seed(3)
+        before = g.get_state().clone()
+        with pytest.raises(ValueError, match=match):
+            corpus.random_crops(6, SL, generator=g, check=False, **kw)
+        assert torch.equal(g.get_state(), before), match

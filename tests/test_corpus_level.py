@@ -19,9 +19,9 @@ def bits(t):
     return t.contiguous().view(torch.int32)
 
 
-def write(pkg, torch, d, rate, tag):
+def write(pkg, torch, d, rate, tag, files=FILES):
     paths = []
-    for i, (frames, size, fl, seed, amp) in enumerate(FILES):
+    for i, (frames, size, fl, seed, amp) in enumerate(files):
         rng = np.random.default_rng(seed)
         t = np.arange(frames) / rate
         x = np.stack([amp * np.sin(2 * np.pi * (200.0 + 150 * seed) * t + c) + 0.1 * amp * rng.standard_normal(frames) for c in (0, 1)])
@@ -124,6 +124,30 @@ def test_a_corpus_of_mixed_rates(tmp_path):
         assert torch.equal(bits(got), bits(pkg.level(pcm, spec, 8000, lengths)))
         with pytest.raises(ValueError):
             c.crops(cf, co, L, check=False, level=spec)              # no rate of its own
+
+
+def test_a_corpus_at_44100_hz_a_hop_longer_than_a_tile(tmp_path):
+    """The rate of the project's own material: hops of 4410 frames, longer than the measure launch's tile of 4096, so a hop's sum
+    is carried from tile to tile; crops of six hops and 37 frames, one that runs off its file's end and one outside the corpus"""
+    import torch
+
+    import alac.net_amd as pkg
+
+    rate, n = 44100, 6 * 4410 + 37
+    files = [(40000, 16, 4096, 1, 0.3), (30011, 24, 1024, 2, 0.01), (36000, 16, 4096, 3, 0.1)]
+    with pkg.Corpus(write(pkg, torch, tmp_path, rate, "cd", files)) as c:
+        cf, co = torch.tensor([0, 1, 2, c.num_files], device="cuda"), torch.tensor([0, 1000, 36000 - 5 * 4410, 0], device="cuda")
+        pcm, lengths = c.crops(cf, co, n, check=False)
+        pcm = pcm.clone()
+        assert lengths.tolist() == [n, n, 5 * 4410, -1]
+        for spec in (pkg.Level.lufs(), pkg.Level.lufs(-16.0, max_peak=0.5, clamp=True)):
+            want = pkg.level(pcm, spec, rate, lengths)
+            got, glen = c.crops(cf, co, n, check=False, level=spec)
+            assert torch.equal(glen, lengths) and torch.equal(bits(got), bits(want)), spec
+            assert bool((got[-1] == 0).all()) and all(not torch.equal(bits(got[b]), bits(pcm[b])) for b in range(3))
+        got, glen = c.crops(cf, co, n, check=False, level=pkg.Level.lufs())
+        loud = pkg.loudness(got, rate, glen)
+        assert float((loud[:3] - -23.0).abs().max()) < 1e-3 and float(loud[3]) == float("-inf"), loud
 
 
 def test_random_crops_draw_what_they_drew_without_level(corpus):

@@ -1,7 +1,8 @@
 """The host side of the level stage (alac.net_amd/level.py), without a device: the twin against the specification within the
 module's bound on the rows the kernel tests use, the designed K-weighting against BS.1770's printed table, EBU Tech 3341's
-readings within +-0.1 LU with both gates shown to matter, the rows that stay as they are, max_peak, clamp and NaNs, what Level
-refuses, the keyword's place in both signatures, the C ABI entry and the header's constants."""
+readings within +-0.1 LU with both gates shown to matter and, in its five-channel case 6, the surround weight, the rows that
+stay as they are, max_peak, clamp and NaNs, what Level refuses, the keyword's place in both signatures, the C ABI entry and
+the header's constants."""
 import ctypes as C
 import functools
 import inspect
@@ -151,6 +152,26 @@ def test_ebu_tech_3341_readings():
     a, b = pkg.loudness_host(x[None], 8000), pkg.loudness_host(x[None], 8000, twin=True)
     assert abs(float(a[0]) - float(b[0])) < 1e-9
     assert pkg.loudness_host(np.zeros((1, 1, 8000), dtype=np.float32), 8000)[0] == -np.inf
+
+
+def test_ebu_tech_3341_case_6_and_the_surround_weight(monkeypatch):
+    """An outside yardstick for the channel weights: EBU Tech 3341 case 6, 997 Hz at -28.0 dBFS in L and R, -24.0 in C and
+    -30.0 in Ls and Rs (the channel order of alac_level.h), reads -23.0 +- 0.1 LUFS: 2 10^-2.8 + 10^-2.4 + 2 1.41 10^-3.0 =
+    9.97e-3, less 3.01 dB for a sine's mean square, is -23.02.  With every weight 1.0 the same signal reads 0.37 LU less."""
+    import alac.net_amd as pkg
+
+    lv = mod()
+    x = np.concatenate([sine(db, 5, channels=1) for db in (-28.0, -28.0, -24.0, -30.0, -30.0)])[None]
+    by_hand = 10.0 * np.log10(2 * 10 ** -2.8 + 10 ** -2.4 + 2 * 1.41 * 10 ** -3.0) - 3.0103
+    assert abs(by_hand - -23.0) <= 0.05
+    got = float(pkg.loudness_host(x, RATE, twin=True)[0])
+    monkeypatch.setattr(lv, "WEIGHTS", (1.0,) * 5)
+    plain = float(pkg.loudness_host(x, RATE, twin=True)[0])
+    print("EBU Tech 3341 case 6:", got, "with every weight 1.0:", plain)
+    assert abs(got - -23.0) <= 0.1 and abs(plain - -23.0) > 0.1
+    # the order is L, R, C, Ls, Rs: the centre's level in a surround channel reads otherwise
+    monkeypatch.undo()
+    assert abs(float(pkg.loudness_host(x[:, [0, 1, 3, 2, 4]], RATE, twin=True)[0]) - -23.0) > 0.1
 
 
 def test_the_rows_that_stay_as_they_are():

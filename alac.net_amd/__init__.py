@@ -104,6 +104,8 @@ SYMBOLS = {
     "alacgpu_pyin_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP, C.c_uint32, C.c_uint32, C.c_uint32,
                                       C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _VP, _VP, _VP, _VP,
                                       _VP, _VP, C.c_uint64, C.c_int, _VP]),
+    "alacgpu_kaldi_pitch_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _VP] + [C.c_uint32] * 17 +
+                                   [_VP, _VP, _VP, _VP, C.c_uint64, C.c_int, _VP]),
     "alacgpu_cqt_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _VP, _VP, _VP,
                                      C.c_int, C.c_int, C.c_float, _VP, C.c_uint64, _VP]),
     "alacgpu_stft_device": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _VP, _VP, C.c_int,
@@ -636,6 +638,22 @@ class AlacGpuContext(_Closing):
                                        tau_min, tau_max, align_length, n_thresholds, n_bins, band, float(no_trough_prob), _dp(d_table),
                                        _dp(d_obs_voiced), _dp(d_obs_unvoiced), _dp(d_vp), _dp(d_out), _dp(d_states), out_frames, int(stage),
                                        _VP(stream))
+        _check(rc, self._ctx)
+
+    def kaldi_pitch_device(self, d_src, rows, channels, stride, frames, d_valid, sample_rate, resample_freq, win_length, hop, window, shift,
+                           first_lag, last_lag, n_states, phases, in_per_unit, down_taps, up_taps, flags, left_context, right_context,
+                           delta_window, d_table, d_nccf, d_raw, d_out, out_frames, stage=0, stream=0):
+        """alacgpu_kaldi_pitch_device: Kaldi's pitch features of every row of d_src (float32 device tensor, planar [rows, channels,
+        stride]) with the packed float32 tables d_table of a kaldi_pitch.KaldiPitch.  stage 0: all three launches, into d_out
+        (float32 [rows, channels, lines, out_frames]; zeros behind a row's frames), the NCCF planes and backpointers in the
+        context's scratch; stage 1: the downsampler and the NCCF alone into d_nccf [rows, channels, 2, out_frames, n_states];
+        stage 2: the decode alone on d_nccf into d_raw [rows, channels, 2, out_frames]; stage 3: the post-processing alone on
+        d_raw into d_out; in stages 2 and 3 d_valid counts frames.  Tensors a stage does not use are None.  kaldi_pitch.py states
+        the arithmetic.  Asynchronous on `stream` (raw hipStream_t); nothing is read back."""
+        rc = lib().alacgpu_kaldi_pitch_device(self._ctx, _dp(d_src), rows, channels, stride, frames, _dp(d_valid), sample_rate, resample_freq,
+                                              win_length, hop, window, shift, first_lag, last_lag, n_states, phases, in_per_unit, down_taps,
+                                              up_taps, flags, left_context, right_context, delta_window, _dp(d_table), _dp(d_nccf),
+                                              _dp(d_raw), _dp(d_out), out_frames, int(stage), _VP(stream))
         _check(rc, self._ctx)
 
     def reverb_device(self, d_src, d_out, d_rir, rows, channels, rir_channels, stride, rir_stride, frames, rir_frames, d_valid,
@@ -1308,6 +1326,10 @@ from .yin import Yin, hz_to_cents, yin, yin_host, yin_host_f32  # noqa: E402
 
 # ---- smoothed F0 tracks: probabilistic YIN with a Viterbi decode (alacgpu_pyin_device) ---------------------------------------------------
 from .pyin import PYin, pyin, pyin_decode, pyin_host, pyin_host_f32, pyin_observation  # noqa: E402
+
+# ---- Kaldi's pitch features: NCCF on a lag grid, a dense Viterbi decode, the post-processing (alacgpu_kaldi_pitch_device) -----------------
+from .kaldi_pitch import (KaldiPitch, kaldi_pitch, kaldi_pitch_decode, kaldi_pitch_host, kaldi_pitch_host_f32, kaldi_pitch_nccf,  # noqa: E402
+                          kaldi_pitch_process)
 
 # ---- pitch shift and time stretch of crops and tensors (alacgpu_time_stretch_device) ------------------------------------------------
 from .pitch import (PitchShift, pitch_shift, pitch_shift_host, pitch_shift_host_f32, semitone_ratio, time_stretch,  # noqa: E402

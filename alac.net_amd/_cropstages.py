@@ -14,6 +14,7 @@ from .biquad import Effects
 from .cqt import ConstantQ
 from .deltas import Deltas
 from .fbank import KaldiFbank
+from .kaldi_pitch import KaldiPitch
 from .features import LogMel
 from .level import _checked as _level_checked
 from .mfcc import KaldiMfcc
@@ -177,10 +178,10 @@ def _effects_given(torch, given, dtype, rate, device):
 
 
 def _f0_given(torch, spec, dtype, rate, vad, num_frames):
-    """crops(f0=): ValueError for what is neither a Yin nor a PYin, for one of another rate than the crops', for int32 crops,
+    """crops(f0=): ValueError for what is neither a Yin nor a PYin nor a KaldiPitch, for one of another rate than the crops', for int32 crops,
     together with vad= and for crops too short for a frame"""
-    if not isinstance(spec, (Yin, PYin)):
-        raise ValueError(f"f0 must be a yin.Yin or a pyin.PYin, not {spec!r}")
+    if not isinstance(spec, (Yin, PYin, KaldiPitch)):
+        raise ValueError(f"f0 must be a yin.Yin or a pyin.PYin, not {spec!r}; the third kind taken is a kaldi_pitch.KaldiPitch")
     _has_rate(rate)
     if spec.sample_rate != rate:
         raise ValueError(f"f0 for {spec.sample_rate} Hz, crops at {rate} Hz")

@@ -53,6 +53,7 @@ from .deltas import _add_deltas
 from .mix import _mix, snr_ratio
 from .normalize import _normalize
 from .vad import _select_frames, _vad_energy
+from .kaldi_pitch import KaldiPitch, _kaldi_pitch
 from .pyin import PYin, _pyin
 from .yin import _yin
 from .pitch import _pitch_shift, _ratio_kinds
@@ -715,7 +716,10 @@ class Corpus(_Closing):
         track), num_frames below f0.min_frames.  Or a pyin.PYin, wherever a Yin is taken and with the same refusals: the
         smoothed track of probabilistic YIN, ONE alacgpu_pyin_device call (two launches), track float32 [B, 1 if mono else C,
         3, f0.frames(num_frames)] -- the decoded bin's frequency in Hz, 1.0 where voiced, the voicing probability, pyin.py
-        states them --, bit for bit pyin.pyin of that waveform.
+        states them --, bit for bit pyin.pyin of that waveform.  Or a kaldi_pitch.KaldiPitch, again with the same refusals:
+        Kaldi's pitch features, ONE alacgpu_kaldi_pitch_device call (three launches), track float32 [B, 1 if mono else C,
+        f0.lines, f0.frames(num_frames)] -- kaldi_pitch.py states the lines --, bit for bit kaldi_pitch.kaldi_pitch of that
+        waveform; with features=spec and f0=KaldiPitch.like(spec), torch.cat([feats, track], 2) is the pasted matrix.
 
         features: a features.LogMel, a fbank.KaldiFbank, a mfcc.KaldiMfcc, a cqt.ConstantQ or a stft.Spectrogram -- the crops' log-mel, Kaldi fbank, Kaldi MFCC,
         constant-Q features or spectrogram instead of their PCM (n_mels below is then the transform's line count: a KaldiMfcc's n_ceps, a ConstantQ's n_bins,
@@ -822,7 +826,9 @@ class Corpus(_Closing):
         if effects is not None:
             _biquad(ctx, res, effects[1][0], lengths, effects[1][1], effects[0].clamp, res)
         if f0 is not None:
-            if isinstance(f0, PYin):
+            if isinstance(f0, KaldiPitch):
+                track = _kaldi_pitch(ctx, res, f0, lengths, self._scratch("_f0_scratch", (B, Co, f0.lines, int(f0.frames(L)))))
+            elif isinstance(f0, PYin):
                 track = _pyin(ctx, res, f0, lengths, self._scratch("_f0_scratch", (B, Co, 3, int(f0.frames(L)))))
             else:
                 track = _yin(ctx, res, f0, lengths, self._scratch("_f0_scratch", (B, Co, 2, int(f0.frames(L)))))

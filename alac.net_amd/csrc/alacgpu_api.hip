@@ -533,6 +533,7 @@ void alacgpu_destroy(alacgpu_ctx* ctx) {
     if (ctx->h_reverb_twiddles) (void)hipHostFree(ctx->h_reverb_twiddles);   // (reverb.destroy() has waited for the copy)
     ctx->stretch.destroy();
     ctx->pyin.destroy();
+    ctx->kaldi_pitch.destroy();
     for (void* t : ctx->d_stretch_tables) (void)hipFree(t);           // (a null pointer is a no-op)
     for (void* t : ctx->h_stretch_tables)
         if (t) (void)hipHostFree(t);                                  // (stretch.destroy() has waited for the copies)

@@ -136,6 +136,9 @@ struct alacgpu_ctx {
                      // (buf[0]), and of the output frames, [rows, channels, alac_stretch_cap(out_frames), n_fft / 2 + 1] float2 (buf[1])
     scratch pyin;    // alacgpu_pyin_device: the log2 observations of every frame, [planes, frames, n_bins] voiced and [planes, frames] unvoiced and vp
                      // (buf[0]), and the decode's uint16 backpointers, [planes, frames, 2 n_bins] (buf[1])
+    scratch kaldi_pitch;   // alacgpu_kaldi_pitch_device: the partial sums, the downsampled rows, the NCCF planes, the raw track and the
+                     // epilogue's weights (buf[0], alac_kpitch_scratch of alac_kaldi_pitch.h), and the decode's uint16 backpointers,
+                     // [planes, frames, n_states] (buf[1])
     void* d_stretch_tables[3] = {};      // alacgpu_time_stretch_device, for n_fft 512, 1024, 2048: exp(-2 pi i k / n_fft), float2 [n_fft], and
                                          // behind it the periodic Hann window, float [n_fft]; made at the first call with that n_fft
     void* h_stretch_tables[3] = {};      // ... and the page-locked tables they are copied from on that call's stream

@@ -20,6 +20,7 @@
 #include "alac_biquad.h"
 #include "alac_yin.h"
 #include "alac_pyin.h"
+#include "alac_kaldi_pitch.h"
 #include "alac_cqt.h"
 #include "alac_stft.h"
 #include "alac_level.h"
@@ -1340,6 +1341,125 @@ int alacgpu_pyin_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint
     }
     HIP_TRY(ctx, hipGetLastError());
     return ctx->pyin.release(ctx, stream);
+}
+
+int alacgpu_kaldi_pitch_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t stride, uint64_t frames,
+                               const void* d_valid, uint32_t sample_rate, uint32_t resample_freq, uint32_t win_length, uint32_t hop,
+                               uint32_t window, uint32_t shift, uint32_t first_lag, uint32_t last_lag, uint32_t n_states, uint32_t phases,
+                               uint32_t in_per_unit, uint32_t down_taps, uint32_t up_taps, uint32_t flags, uint32_t left_context,
+                               uint32_t right_context, uint32_t delta_window, const void* d_table, void* d_nccf, void* d_raw, void* d_out,
+                               uint64_t out_frames, int stage, void* hip_stream) {
+    if (!ctx || stage < 0 || stage > 3) return ALACGPU_ERR_BAD_ARG;
+    const bool front = stage <= 1, decode = stage == 0 || stage == 2, process = (flags & ALAC_KPITCH_PROCESS) != 0u;
+    const bool epilogue = process && (stage == 0 || stage == 3);
+    if (!args_ok({{d_src, 4, front}, {d_valid, 8, false}, {d_table, 4}, {d_nccf, 4, stage == 1 || stage == 2}, {d_raw, 4, stage >= 2},
+                  {d_out, 4, stage == 0 || stage == 3}}))
+        return ALACGPU_ERR_BAD_ARG;
+    if (channels == 0 || sample_rate == 0 || resample_freq == 0 || resample_freq > sample_rate || win_length == 0 || hop == 0 || window < 2u ||
+        shift == 0)
+        return ALACGPU_ERR_BAD_ARG;
+    if (first_lag < 1u || last_lag <= first_lag || n_states < 1u || n_states > ALAC_KPITCH_MAX_STATES || phases == 0 || in_per_unit == 0 ||
+        down_taps == 0 || (uint64_t)phases * down_taps > ALAC_KPITCH_MAX_DOWN || up_taps == 0 || up_taps > last_lag - first_lag + 1u ||
+        window > (1u << 20) || last_lag > (1u << 20) || alac_kpitch_nccf_lds(window, first_lag, last_lag) > ALAC_KPITCH_MAX_LDS ||
+        (flags >> 5) != 0u || (process && alac_kpitch_lines(flags) == 0u) || (stage == 3 && !process) || delta_window < 1u || delta_window > 64u ||
+        left_context > (1u << 20) || right_context > (1u << 20))
+        return ALACGPU_ERR_BAD_ARG;
+    const uint64_t planes = (uint64_t)rows * channels;
+    if (planes > 0x7FFFFFFFull || out_frames >= (1ull << 31) || frames >= (1ull << 40)) return ALACGPU_ERR_BAD_ARG;
+    alac_kpitch_framing fr{sample_rate, resample_freq, win_length, hop, window, shift};
+    const uint32_t lines = alac_kpitch_lines(flags);
+    const uint64_t n_max = front ? alac_kpitch_samples(fr, frames) : 0u;
+    const uint64_t chunks = std::max<uint64_t>((n_max + ALAC_KPITCH_CHUNK - 1u) / ALAC_KPITCH_CHUNK, 1u);
+    const uint64_t groups = (out_frames + ALAC_KPITCH_THREADS / 64 - 1u) / (ALAC_KPITCH_THREADS / 64);
+    const alac_kpitch_scratch sc = alac_kpitch_scratch_of(planes, n_max, out_frames, n_states, front, stage == 0, decode,
+                                                          (stage == 0 && process) || epilogue);
+    if (sc.bytes0 + sc.bytes1 > (1ull << 31)) return ALACGPU_ERR_BAD_ARG;
+    if (front) {
+        if (frames == 0 || frames > stride || out_frames != alac_kpitch_frames(fr, frames)) return ALACGPU_ERR_BAD_ARG;
+        uint64_t extent, out_extent;
+        if (!planes_extent(planes, stride, frames, extent)) return ALACGPU_ERR_BAD_ARG;
+        out_extent = sizeof(float) * planes * out_frames * (stage == 0 ? (uint64_t)lines : 2ull * n_states);
+        if (!apart(d_src, extent, stage == 0 ? d_out : d_nccf, out_extent)) return ALACGPU_ERR_BAD_ARG;
+        if (planes * chunks > 0x7FFFFFFFull || planes * std::max<uint64_t>(groups, 1u) > 0x7FFFFFFFull) return ALACGPU_ERR_BAD_ARG;
+    }
+    const uint64_t cells = sizeof(float) * planes * out_frames;
+    if ((stage == 2 && !apart(d_nccf, cells * 2u * n_states, d_raw, cells * 2u)) || (stage == 3 && !apart(d_raw, cells * 2u, d_out, cells * lines)))
+        return ALACGPU_ERR_BAD_ARG;
+    if (rows == 0 || out_frames == 0) return ALACGPU_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    scratch_hold hold{ctx->kaldi_pitch, stream};
+    int rc = ctx->kaldi_pitch.acquire(ctx, stream, (size_t)sc.bytes0, align_up(sc.bytes0 + sc.bytes0 / 4, 4096), (size_t)sc.bytes1,
+                                      align_up(sc.bytes1 + sc.bytes1 / 4, 4096));
+    if (rc) return rc;
+    const alac_kpitch_tables tab = alac_kpitch_tables_at((const float*)d_table, phases, down_taps, n_states, up_taps);
+    char* buf = (char*)ctx->kaldi_pitch.buf[0];
+    float* nccf = stage == 0 ? (float*)(buf + sc.nccf) : (float*)d_nccf;
+    if (front) {
+        alac_kpitch_down_params q;
+        q.src = (const float*)d_src;
+        q.valid = (const int64_t*)d_valid;
+        q.down = (float*)(buf + sc.down);
+        q.sums = (double*)(buf + sc.sums);
+        q.tab = tab;
+        q.fr = fr;
+        q.channels = channels;
+        q.phases = phases;
+        q.in_per_unit = in_per_unit;
+        q.down_taps = down_taps;
+        q.chunks = (uint32_t)chunks;
+        q.stride = stride;
+        q.frames = frames;
+        q.n_max = n_max;
+        void* kargs[] = {&q};
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_kpitch_down_kernel, dim3((uint32_t)(planes * chunks)), dim3(ALAC_KPITCH_THREADS), kargs, 0,
+                                     stream));
+        alac_kpitch_nccf_params n;
+        n.valid = (const int64_t*)d_valid;
+        n.down = q.down;
+        n.sums = q.sums;
+        n.nccf = nccf;
+        n.tab = tab;
+        n.fr = fr;
+        n.channels = channels;
+        n.chunks = (uint32_t)chunks;
+        n.first_lag = first_lag;
+        n.last_lag = last_lag;
+        n.n_states = n_states;
+        n.up_taps = up_taps;
+        n.groups = (uint32_t)groups;
+        n.frames = frames;
+        n.n_max = n_max;
+        n.out_frames = out_frames;
+        void* nargs[] = {&n};
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_kpitch_nccf_kernel, dim3((uint32_t)(planes * groups)), dim3(ALAC_KPITCH_THREADS), nargs,
+                                     alac_kpitch_nccf_lds(window, first_lag, last_lag), stream));
+    }
+    if (stage != 1) {
+        alac_kpitch_decode_params q;
+        q.nccf = decode ? nccf : nullptr;
+        q.valid = (const int64_t*)d_valid;
+        q.back = (uint16_t*)ctx->kaldi_pitch.buf[1];
+        q.raw = stage >= 2 ? (float*)d_raw : (process ? (float*)(buf + sc.raw) : (float*)d_out);
+        q.work = epilogue ? (float*)(buf + sc.work) : nullptr;
+        q.out = epilogue ? (float*)d_out : nullptr;
+        q.tab = tab;
+        q.fr = fr;
+        q.channels = channels;
+        q.n_states = n_states;
+        q.flags = flags;
+        q.left = left_context;
+        q.right = right_context;
+        q.delta_window = delta_window;
+        q.counts_are_frames = stage >= 2 ? 1u : 0u;
+        q.frames = frames;
+        q.out_frames = out_frames;
+        void* kargs[] = {&q};
+        HIP_TRY(ctx, hipLaunchKernel((const void*)alac_kpitch_decode_kernel, dim3((uint32_t)planes), dim3(ALAC_KPITCH_DECODE_THREADS), kargs, 0,
+                                     stream));
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return ctx->kaldi_pitch.release(ctx, stream);
 }
 
 int alacgpu_cqt_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t src_stride, uint64_t frames,

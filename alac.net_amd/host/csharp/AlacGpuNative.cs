@@ -219,6 +219,15 @@ namespace ALACdotNET.Decoder
             ulong stride, ulong frames, IntPtr dValid, uint sampleRate, uint winLength, uint hop, uint tauMin, uint tauMax,
             uint alignLength, uint nThresholds, uint nBins, uint band, float noTroughProb, IntPtr dTable, IntPtr dObsVoiced,
             IntPtr dObsUnvoiced, IntPtr dVp, IntPtr dOut, IntPtr dStates, ulong outFrames, int stage, IntPtr hipStream);
+        /// <summary>Kaldi's pitch features of planar float crops in device memory (compute-kaldi-pitch-feats and
+        /// process-kaldi-pitch-feats): stage 0 everything into dOut [rows, channels, lines, outFrames], 1 the NCCF planes into
+        /// dNccf, 2 the decode of dNccf into dRaw, 3 the post-processing of dRaw into dOut; dTable the packed tables of
+        /// kaldi_pitch.KaldiPitch.table (include/alacgpu.h).</summary>
+        [DllImport(Lib)] public static extern int alacgpu_kaldi_pitch_device(IntPtr ctx, IntPtr dSrc, uint rows, uint channels,
+            ulong stride, ulong frames, IntPtr dValid, uint sampleRate, uint resampleFreq, uint winLength, uint hop, uint window,
+            uint shift, uint firstLag, uint lastLag, uint nStates, uint phases, uint inPerUnit, uint downTaps, uint upTaps,
+            uint flags, uint leftContext, uint rightContext, uint deltaWindow, IntPtr dTable, IntPtr dNccf, IntPtr dRaw,
+            IntPtr dOut, ulong outFrames, int stage, IntPtr hipStream);
         /// <summary>Constant-Q features of planar float crops in device memory (dSrc [rows, channels, srcStride] to dOut
         /// [rows, channels, nBins, outFrames], outFrames = 1 + frames / hop): lengths is the N_k in host memory, dLengths
         /// the same in device memory, dTable the kernels in blocks of 16 bins (include/alacgpu.h).</summary>

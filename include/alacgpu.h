@@ -931,6 +931,51 @@ int alacgpu_pyin_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint
                         void* d_out, void* d_states, uint64_t out_frames, int stage, void* hip_stream);
 
 /*
+ * alacgpu_kaldi_pitch_device: Kaldi's pitch features of the crops (no counterpart in the reference): what
+ * compute-kaldi-pitch-feats | process-kaldi-pitch-feats produce (Ghahremani et al., ICASSP 2014) -- the signal downsampled to
+ * resample_freq, the NCCF of every frame interpolated onto a logarithmic lag grid of n_states states, a dense Viterbi decode
+ * along every plane (a quadratic transition cost over ALL source states, every tie to the lowest), and the post-processing as
+ * the decode's epilogue.  Three launches, no atomics, the same inputs give the same bits.  d_src is planar float32
+ * [rows, channels, stride], the first `frames` elements of a plane are signal, of which a row's first
+ * v = min(max(d_valid[row], 0), frames) count (d_valid NULL: frames).  win_length and hop are the frame and the shift in input
+ * samples, window and shift those at resample_freq; a row of v samples has min(v < win_length ? 0 : 1 + (v - win_length) / hop,
+ * n < window ? 0 : 1 + (n - window) / shift) frames, n = ceil(v resample_freq / sample_rate), and out_frames is that count of
+ * `frames`.  d_table is the float32 tables of the specification, packed in the order of alac_kpitch_tables
+ * (csrc/alac_kaldi_pitch.h) for `phases` phases of down_taps taps (an output sample n reads the input from
+ * (n / phases) in_per_unit + first[n % phases] on), the integer lags first_lag .. last_lag, n_states states of up_taps
+ * interpolation taps and 2 delta_window + 1 delta coefficients; alac.net_amd/kaldi_pitch.py states the tables, every operation
+ * in order, the deviations from Kaldi and the bounds, and its twin equals the kernels bit for bit.  flags: 1 post-process, and
+ * with it 2 the POV feature, 4 the normalised log-pitch (over left_context and right_context frames), 8 the delta (over
+ * delta_window frames), 16 the raw log-pitch: `lines` is 2 without bit 1, else the number of bits 2 .. 16 set.
+ *   stage 0  everything: d_out is float32 [rows, channels, lines, out_frames], apart from d_src: without post-processing the POV
+ *            NCCF at the decoded lag and the pitch in Hz, else the lines asked for in Kaldi's order; zeros at and behind a row's
+ *            frame count.  The downsampled rows, the NCCF planes and the uint16 backpointers ([planes, out_frames, n_states]) lie
+ *            in a scratch of the ctx that its calls share one after the other, whatever their streams.
+ *   stage 1  the downsampler and the NCCF alone, into d_nccf float32 [rows, channels, 2, out_frames, n_states], apart from d_src:
+ *            the pitch NCCF (with the ballast) and the POV NCCF (without); zeros at and behind a row's frame count.
+ *   stage 2  the decode alone, on d_nccf (finite values), into d_raw float32 [rows, channels, 2, out_frames]: stage 0's output
+ *            without post-processing.  d_valid then holds FRAMES per row (NULL: out_frames); d_src, stride and frames are not used.
+ *   stage 3  the post-processing alone (flags bit 1 must be set), on d_raw into d_out [rows, channels, lines, out_frames]; d_valid
+ *            as in stage 2.
+ * A line without frames runs no recursion.  Device pointers only, asynchronous on hip_stream, nothing is read back.  rows == 0
+ * or out_frames == 0: nothing happens.
+ * ALACGPU_ERR_BAD_ARG, before anything is enqueued: a NULL ctx, a stage outside 0 .. 3, a NULL among the arrays the stage uses
+ * (d_table always), a misaligned array (4; 8 for d_valid), channels 0, a rate, win_length, hop or shift of 0, resample_freq above
+ * sample_rate, window below 2, first_lag 0, last_lag not above first_lag, n_states outside 1 .. 1024, phases, in_per_unit or
+ * down_taps 0, more than 4096 downsampler weights, up_taps 0 or above the number of integer lags, a frame whose LDS image passes
+ * 64 KiB, flags above 31 or post-processing without a line, stage 3 without post-processing, delta_window outside 1 .. 64, a
+ * context above 2^20, 2^31 planes or frames or more, a scratch above 2^31 bytes, and in stages 0 and 1 frames 0 or above stride,
+ * out_frames that is not the frame count of a row of `frames` samples, d_src overlapping what is written, an extent of 2^60
+ * bytes or more, 2^31 workgroups or more; in stage 2 d_nccf overlapping d_raw, in stage 3 d_raw overlapping d_out.
+ */
+int alacgpu_kaldi_pitch_device(alacgpu_ctx* ctx, const void* d_src, uint32_t rows, uint32_t channels, uint64_t stride, uint64_t frames,
+                               const void* d_valid, uint32_t sample_rate, uint32_t resample_freq, uint32_t win_length, uint32_t hop,
+                               uint32_t window, uint32_t shift, uint32_t first_lag, uint32_t last_lag, uint32_t n_states,
+                               uint32_t phases, uint32_t in_per_unit, uint32_t down_taps, uint32_t up_taps, uint32_t flags,
+                               uint32_t left_context, uint32_t right_context, uint32_t delta_window, const void* d_table,
+                               void* d_nccf, void* d_raw, void* d_out, uint64_t out_frames, int stage, void* hip_stream);
+
+/*
  * alacgpu_cqt_device: constant-Q features of the crops (no counterpart in the reference): the direct constant-Q transform,
  * every bin's own windowed complex exponential against the signal; one launch, no atomics, no scratch, the same inputs give the
  * same bits.  d_src is planar float32 [rows, channels, src_stride], the first `frames` elements of a plane are signal, zeros
